@@ -23,7 +23,14 @@ fused pass + RCCL all-reduce of the normal-equation buffer (what a solver
 iteration needs) is timed after the headline region and reported under
 "fused" (it does not contribute to `value`).
 
+A plain run sets up, warms up, times the `--steps` steps and prints the line: only what `value` and
+`ms_per_step` need.  Everything else measured or checked above and below (rooflines and their ceilings,
+the full-overlap, fused, shipped, multi-context, TSDF, config-5 and config-2 workloads, the solve, the
+CPU baseline, the same-run parity gate) runs with `--full`.  `--dump-outputs DIR` writes a fixed, seeded
+sample of the rows the last timed pass computed (DIR/*.npy), so that two builds can be compared.
+
   python bench.py --gpus 1 --steps 10 --warmup 3
+  python bench.py --gpus 1 --steps 10 --warmup 3 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -109,7 +116,7 @@ def multi_context_child(args, n_devices, timeout_s=240):
                         "TORCHELASTIC_MAX_RESTARTS", "TORCHELASTIC_USE_AGENT_STORE", "TORCH_NCCL_ASYNC_ERROR_HANDLING")}
     with tempfile.TemporaryDirectory() as tmp:
         detail = os.path.join(tmp, "inprocess.json")
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(n_devices), "--inprocess", "--no-cpu-baseline", "--no-tsdf",
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(n_devices), "--inprocess", "--full", "--no-cpu-baseline", "--no-tsdf",
                "--no-solve", "--no-config5", "--no-config2", "--no-parity", "--no-full-overlap", "--no-shipped",
                "--placement-candidates", "1",      # (only the child's multi_context block is used)
                "--steps", str(max(min(args.steps, 5), 1)), "--warmup", "1", "--inner", str(args.inner),
@@ -151,6 +158,25 @@ def emit(full, detail_path, full_line=False):
     else:
         sys.stdout.write(out)
         sys.stdout.flush()
+
+
+DUMP_ROWS = 1 << 20     # rows written by --dump-outputs: 44 B each (index, residual, two Jacobian rows), 46 MB in all
+DUMP_SEED = 0
+
+
+def dump_outputs(dirname, R, residuals, jac_ref, jac_read, torch):
+    """What the caller of the timed pass receives -- its residuals and both Jacobian blocks -- for DUMP_ROWS rows of
+    the last timed pass, the same rows in every run with the same arguments (the whole arrays are ~20 GB at the
+    default size).  rows.npy holds their indices (float64: exact below 2^53)."""
+    os.makedirs(dirname, exist_ok=True)
+    rows = np.arange(R) if R <= DUMP_ROWS else np.sort(np.random.default_rng(DUMP_SEED).choice(R, DUMP_ROWS, replace=False))
+    idx = torch.from_numpy(rows.astype(np.int64)).to(residuals.device)
+    arrays = {"rows": rows.astype(np.float64),
+              "residuals": residuals.index_select(0, idx).cpu().numpy(),
+              "jacobian_ref": jac_ref.index_select(0, idx).cpu().numpy(),
+              "jacobian_read": jac_read.index_select(0, idx).cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def main():
@@ -217,7 +243,24 @@ def main():
     ap.add_argument("--calibrate", action="store_true",
                     help="PMC calibration: first launch evaluates poses 10 km apart, so every "
                          "evaluation reads exactly 20 B and writes exactly 36 B (profiles/README.md)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything besides the headline (rooflines, the other workloads, the solve, "
+                         "TSDF, CPU baseline, parity gate); the --no-* options then leave parts out.  Without it a run "
+                         "times the headline loop only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write a fixed, seeded sample of the rows the last timed pass computed "
+                         "(residuals, both Jacobians, their row indices) as DIR/*.npy; one rank only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--dump-outputs needs a single rank (each rank holds only its shard of the rows)")
+    if args.dump_outputs and args.config != 3:
+        ap.error("--dump-outputs writes the config-3 rows (--config 3)")
+    if not args.full:
+        for opt in ("no_parity", "no_full_overlap", "no_shipped", "no_cpu_baseline", "no_fused", "no_solve", "no_tsdf",
+                    "no_config2", "no_config5", "no_multi_ctx"):
+            setattr(args, opt, True)
     claim_stdout()           # (after --help had its chance to print)
     bench_common.PLACEMENT = args.placement
 
@@ -294,7 +337,7 @@ def main():
     n_sub, n_con = len(true_poses), len(pairs)
     global PROFILE_TRAFFIC
     tpath = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-    PROFILE_TRAFFIC = json.load(open(tpath)) if os.path.exists(tpath) else {}
+    PROFILE_TRAFFIC = json.load(open(tpath)) if args.full and os.path.exists(tpath) else {}
 
     # ---- resident inputs: every rank holds every finished submap -------------
     t_setup = time.perf_counter()
@@ -385,7 +428,7 @@ def main():
     # ---- which box is this?  clocks / power cap / partition modes, and what its memory system sustains for a float4
     # copy and for a non-temporal fill of the very row buffers the timed kernel writes
     from harness import box_state
-    box = box_state.snapshot(local_rank) if rank == 0 else None
+    box = box_state.snapshot(local_rank) if rank == 0 and args.full else None
     n16 = (R * 16) & ~15
 
     def ceilings():
@@ -393,7 +436,7 @@ def main():
         fill_ms = capi.stream_ceiling_ms(ctx, None, 0, jac_read.data_ptr(), n16, 3)
         return {"copy_GBs": 2 * n16 / (copy_ms * 1e-3) / 1e9, "fill_GBs": n16 / (fill_ms * 1e-3) / 1e9,
                 "copy_ms": copy_ms, "fill_ms": fill_ms, "bytes_each_way": n16}
-    ceil_before = ceilings()
+    ceil_before = ceilings() if args.full else None
 
     if args.calibrate:
         far = poses.copy()
@@ -409,7 +452,7 @@ def main():
     torch.cuda.synchronize()
     barrier()
     sampler = box_state.Sampler(local_rank if rank == 0 else 0)
-    if rank == 0:
+    if rank == 0 and args.full:
         sampler.__enter__()                # a host thread reading sysfs clocks / power every 20 ms; touches no queue
     ctx.timer_start()                      # HIP events on the stream the kernel runs on
     t0 = time.perf_counter()
@@ -419,7 +462,7 @@ def main():
     torch.cuda.synchronize()
     barrier()
     dt = time.perf_counter() - t0
-    if rank == 0:
+    if rank == 0 and args.full:
         sampler.__exit__()
     tmax = torch.tensor([dt], dtype=torch.float64, device="cuda")
     rtot = torch.tensor([float(R)], dtype=torch.float64, device="cuda")
@@ -429,14 +472,18 @@ def main():
         dist.all_reduce(rtot, op=dist.ReduceOp.SUM)
         dist.all_reduce(kmax, op=dist.ReduceOp.MAX)
     dt, total_evals, kernel_ms_max = float(tmax.item()), float(rtot.item()), float(kmax.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, R, residuals, jac_ref, jac_read, torch)
 
     # correspondences on this rank (for the conservative byte count)
-    with_corr = int((jac_ref[:R].abs().sum(dim=1) > 0).sum().item())
-    checksum = float(residuals[:R].double().pow(2).sum().item())
-    wc_tot = torch.tensor([float(with_corr)], dtype=torch.float64, device="cuda")
-    if use_dist:
-        dist.all_reduce(wc_tot, op=dist.ReduceOp.SUM)
-    with_corr_total = float(wc_tot.item())
+    with_corr, checksum, with_corr_total = 0, None, 0.0
+    if args.full:
+        with_corr = int((jac_ref[:R].abs().sum(dim=1) > 0).sum().item())
+        checksum = float(residuals[:R].double().pow(2).sum().item())
+        wc_tot = torch.tensor([float(with_corr)], dtype=torch.float64, device="cuda")
+        if use_dist:
+            dist.all_reduce(wc_tot, op=dist.ReduceOp.SUM)
+        with_corr_total = float(wc_tot.item())
 
     # ---- parity gate, config 3: rows of the LAST TIMED PASS (still in the output buffers) ----
     parity_entries = []
@@ -467,20 +514,21 @@ def main():
         grouped = bt.launch_order(points_pass=True)
         return {"live": int(lv), "distinct": int(uq), "grouped": int(grouped),
                 "read": int(uq if grouped == 1 else lv)}
-    pr = points_read(batch, poses)
+    pr = points_read(batch, poses) if args.full else None
     # the same two ceilings again after the timed region (a box that heats up or is throttled shows here), and a
     # launch of the headline kernel's own shape: its algorithmic read : write proportion, non-temporal stores
     # (the output buffers hold nothing any more that a later section reads: the parity gate above is done)
-    ceil_after = ceilings()
-    rd = ((pr["read"] * BYTES_POINT + with_corr * BYTES_NEIGHBOURS) * n16 // max(R * BYTES_OUT, 1)) & ~15
-    rd = min(rd, n16)
-    mix_ms = capi.stream_ceiling_ms(ctx, jac_ref.data_ptr(), rd, jac_read.data_ptr(), n16, 3)
-    ceil_after["kernel_shaped_GBs"] = (rd + n16) / (mix_ms * 1e-3) / 1e9
-    ceil_after["kernel_shaped_read_fraction"] = rd / max(rd + n16, 1)
+    ceil_after = ceilings() if args.full else None
+    if args.full:
+        rd = ((pr["read"] * BYTES_POINT + with_corr * BYTES_NEIGHBOURS) * n16 // max(R * BYTES_OUT, 1)) & ~15
+        rd = min(rd, n16)
+        mix_ms = capi.stream_ceiling_ms(ctx, jac_ref.data_ptr(), rd, jac_read.data_ptr(), n16, 3)
+        ceil_after["kernel_shaped_GBs"] = (rd + n16) / (mix_ms * 1e-3) / 1e9
+        ceil_after["kernel_shaped_read_fraction"] = rd / max(rd + n16, 1)
     # the placement-proof entry point on the same workload, same run: ONE array of tile blocks (one write front,
     # vgx_reg_batch_evaluate_points_blocked) -- what a device-resident consumer gets without choosing anything
     blocked_ms = None
-    if R > 0:
+    if R > 0 and args.full:
         try:
             nbytes_blk, _rows, _first = batch.blocked_layout()
             blocks = torch.empty(nbytes_blk // 4, dtype=torch.float32, device="cuda")
@@ -498,7 +546,7 @@ def main():
     # the same pass in Ceres' own types (vgx_reg_batch_evaluate_points_f64: f64 rows, 72 B written per row -- SURVEY.md
     # 8d's "124 B" variant, reported alongside, never instead); its f32 rounding must be the timed pass's rows
     f64_rows_ms, f64_rows_match = None, None
-    if R > 0 and world == 1:
+    if R > 0 and world == 1 and args.full:
         try:
             r64 = torch.empty(R, dtype=torch.float64, device="cuda")
             jo64 = torch.empty((R, 4), dtype=torch.float64, device="cuda")
@@ -875,8 +923,10 @@ def main():
         # lets them share a reference submap's points in one L2, else once per constraint), and 32 B of
         # neighbours per evaluation that interpolates.  Chunk-granular count: conservative, the kernel
         # culls whole 1024-point tiles.
-        bytes_conservative = R * BYTES_OUT + pr["read"] * BYTES_POINT + with_corr * BYTES_NEIGHBOURS
-        achieved = bytes_conservative / (kernel_ms * 1e-3) / 1e9
+        bytes_conservative = achieved = None
+        if args.full:
+            bytes_conservative = R * BYTES_OUT + pr["read"] * BYTES_POINT + with_corr * BYTES_NEIGHBOURS
+            achieved = bytes_conservative / (kernel_ms * 1e-3) / 1e9
         traffic = traffic_fo = traffic_fo_plain = None
         if PROFILE_TRAFFIC:
             t = PROFILE_TRAFFIC
@@ -916,7 +966,7 @@ def main():
                                           "rule); solve.reference_stop_rule: parameter_tolerance 3e-3 "
                                           "(pose_graph.cpp:93), which fires on the first step of this graph"},
             "value_per_gpu": value / world,
-            "value_with_correspondence": with_corr_total * passes / dt / 1e6,
+            "value_with_correspondence": with_corr_total * passes / dt / 1e6 if args.full else None,
             "ms_per_pass": dt / passes * 1e3,
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
@@ -980,14 +1030,14 @@ def main():
                                     "contract figure describes",
                          "all_88B_would_read_GBs": bytes_contract / (kernel_ms * 1e-3) / 1e9,
                          "traffic_GBs": (traffic / (kernel_ms * 1e-3) / 1e9) if traffic else None,
-                         "with_correspondence_frac": with_corr / max(R, 1)},
+                         "with_correspondence_frac": with_corr / max(R, 1)} if args.full else None,
             "fused": fused,
             "shipped_config": shipped,
             "multi_context": multi_ctx,
             "solve": solve,
             "setup_s": setup_s,
             "residual_checksum": checksum,
-            "box": {"before": box, "during_timed_region": sampler.summary()},
+            "box": {"before": box, "during_timed_region": sampler.summary()} if args.full else None,
         }
         if fo_out:
             fk = fo_out["kernel_ms"] * 1e-3

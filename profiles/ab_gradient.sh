@@ -3,7 +3,7 @@
 # replaced (a library built from the commit before: make SUFFIX=_oldgrad on the stashed tree), alternated twice on one lease
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $REPO
-ARGS="--steps 10 --warmup 2 --placement-candidates 1 --no-cpu-baseline --no-solve --no-tsdf --no-config5 --no-config2 --no-multi-ctx --no-parity --no-fo-plain"
+ARGS="--full --steps 10 --warmup 2 --placement-candidates 1 --no-cpu-baseline --no-solve --no-tsdf --no-config5 --no-config2 --no-multi-ctx --no-parity --no-fo-plain"
 for rep in 1 2; do
 for lib in libvoxgraph_amd.so libvoxgraph_amd_oldgrad.so; do
   VGX_LIB=$REPO/voxgraph_amd/lib/$lib python bench.py $ARGS --detail /tmp/ab_grad.json > /dev/null 2> /tmp/ab_grad.err

@@ -4,7 +4,7 @@
 # what a guarded two-speed locate_axis could save).  make SUFFIX=_fastloc EXTRA=-DVGX_LOCATE_UPPER_BOUND
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $REPO
-ARGS="--steps 10 --warmup 2 --placement-candidates 1 --no-cpu-baseline --no-solve --no-tsdf --no-config5 --no-config2 --no-multi-ctx --no-parity --no-shipped --no-fo-plain"
+ARGS="--full --steps 10 --warmup 2 --placement-candidates 1 --no-cpu-baseline --no-solve --no-tsdf --no-config5 --no-config2 --no-multi-ctx --no-parity --no-shipped --no-fo-plain"
 for rep in 1 2; do
 for lib in libvoxgraph_amd.so libvoxgraph_amd_fastloc.so; do
   VGX_LIB=$REPO/voxgraph_amd/lib/$lib python bench.py $ARGS --detail /tmp/ab_locate.json > /dev/null 2> /tmp/ab_locate.err

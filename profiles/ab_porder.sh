@@ -7,7 +7,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
-ARGS="--steps 10 --warmup 2 --inner 4 --no-cpu-baseline --no-solve --no-tsdf --no-shipped --no-config2 --no-config5 --no-fused --no-multi-ctx"
+ARGS="--full --steps 10 --warmup 2 --inner 4 --no-cpu-baseline --no-solve --no-tsdf --no-shipped --no-config2 --no-config5 --no-fused --no-multi-ctx"
 pick='import json,sys
 d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith("{")][-1])
 fo=d["roofline_full_overlap"]
@@ -23,7 +23,7 @@ cd /tmp
 for v in 0 1; do
   VGX_POINTS_TILE_ORDER=$v timeout 300 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum \
       --kernel-trace -f csv --kernel-include-regex "reg_eval_points" -d $OUT/prof_porder$v -o rd -- \
-      python $REPO/bench.py --steps 3 --inner 1 --warmup 1 --no-cpu-baseline --no-solve --no-tsdf --no-shipped --no-config5 --no-config2 \
+      python $REPO/bench.py --full --steps 3 --inner 1 --warmup 1 --no-cpu-baseline --no-solve --no-tsdf --no-shipped --no-config5 --no-config2 \
       > /dev/null 2> $OUT/prof_porder$v.err
   python - <<PY
 import csv, glob, collections

@@ -1,12 +1,12 @@
 #!/bin/bash
-# the driver's exact command N times in a row on one lease: how the headline moves from process to process (the placement
+# the benchmark with --full N times in a row on one box: how the headline moves from process to process (the placement
 # lottery: every process gets other physical pages for its candidate arrays)   gpurun -- 'N=5 bash profiles/driver_cmd_runs.sh'
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $REPO
 mkdir -p gpurun_out
 : > gpurun_out/driver_cmd_runs.txt
 for k in $(seq 1 ${N:-5}); do
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 > /tmp/line.json 2> /tmp/line.err
+  python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > /tmp/line.json 2> /tmp/line.err
   python3 - "$k" <<'PY' | tee -a gpurun_out/driver_cmd_runs.txt
 import json, sys
 l = [x for x in open("/tmp/line.json") if x.startswith("{")][-1]

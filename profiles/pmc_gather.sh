@@ -8,7 +8,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
 rocprofv3 -L 2>/dev/null | grep -oE "\b(TA|TCP|TD|GRBM|SQ|SQC|TCC)_[A-Za-z0-9_]+" | sort -u > $OUT/pmc_names.txt
-ARGS="--steps 2 --warmup 1 --inner 1 --no-cpu-baseline --no-solve --no-tsdf --no-shipped --no-config5 --no-config2 --no-multi-ctx --no-parity --no-fo-plain"
+ARGS="--full --steps 2 --warmup 1 --inner 1 --no-cpu-baseline --no-solve --no-tsdf --no-shipped --no-config5 --no-config2 --no-multi-ctx --no-parity --no-fo-plain"
 i=0
 while read -r group; do
   i=$((i+1))

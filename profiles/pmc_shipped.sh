@@ -8,7 +8,7 @@ OUT=$REPO/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-ARGS="--steps 3 --warmup 1 --inner 1 --no-cpu-baseline --no-tsdf --no-solve --no-config5 --no-config2 --no-multi-ctx --no-parity --no-full-overlap ${EXTRA_ARGS:-}"
+ARGS="--full --steps 3 --warmup 1 --inner 1 --no-cpu-baseline --no-tsdf --no-solve --no-config5 --no-config2 --no-multi-ctx --no-parity --no-full-overlap ${EXTRA_ARGS:-}"
 rm -rf $OUT/prof_shipped_rd $OUT/prof_shipped_wr
 timeout 300 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum \
     --kernel-trace -f csv --kernel-include-regex "reg_draw|reg_gather|mt_generate|reg_eval_reduce" \

@@ -5,7 +5,7 @@
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 run() {
   echo "== $*"
-  env "$@" python3 $REPO/bench.py --gpus 1 --steps 2 --warmup 1 --no-tsdf --no-config5 --no-solve --no-cpu-baseline --no-shipped \
+  env "$@" python3 $REPO/bench.py --full --gpus 1 --steps 2 --warmup 1 --no-tsdf --no-config5 --no-solve --no-cpu-baseline --no-shipped \
       --no-parity --no-full-overlap --no-multi-ctx --detail $REPO/gpurun_out/pd_detail.json > /dev/null 2> $REPO/gpurun_out/pd_err.txt
   python3 - <<PY
 import json

@@ -2,7 +2,7 @@
 # the fused pass's experiment switches swept again on the round-6 kernel (lighter arithmetic: has an optimum moved?)
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $REPO
-ARGS="--steps 10 --warmup 2 --placement-candidates 1 --no-cpu-baseline --no-solve --no-tsdf --no-config5 --no-config2 --no-multi-ctx --no-parity --no-fo-plain"
+ARGS="--full --steps 10 --warmup 2 --placement-candidates 1 --no-cpu-baseline --no-solve --no-tsdf --no-config5 --no-config2 --no-multi-ctx --no-parity --no-fo-plain"
 one() {
   env "$@" python bench.py $ARGS --detail /tmp/sweep.json > /dev/null 2> /tmp/sweep.err
   python - "$*" <<'PY'

@@ -8,7 +8,7 @@ OUT=$REPO/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-ARGS="--steps 20 --warmup 1 --inner 1 --no-cpu-baseline --no-tsdf --no-solve --no-config5 --no-config2 --no-multi-ctx --no-parity --no-full-overlap"
+ARGS="--full --steps 20 --warmup 1 --inner 1 --no-cpu-baseline --no-tsdf --no-solve --no-config5 --no-config2 --no-multi-ctx --no-parity --no-full-overlap"
 rm -rf $OUT/prof_shipped
 timeout 600 rocprofv3 --kernel-trace --stats -f csv -d $OUT/prof_shipped -o shipped -- \
     python $REPO/bench.py $ARGS --detail $OUT/shipped_detail.json > $OUT/shipped_line.json 2> $OUT/shipped.err

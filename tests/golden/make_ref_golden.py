@@ -6,7 +6,12 @@ oracle/ref_shims).  Run here (needs /root/reference):
 
 Inputs are the seeded config-1 pair (oracle/synth.py), rebuilt by the tests from the seed and
 checked against the stored digests; outputs are stored for every `STRIDE`-th residual row plus a
-SHA-256 of each complete output array (value-exactness check)."""
+SHA-256 of each complete output array (value-exactness check).
+
+tests/golden/ref_outputs.json (the outputs the randomised pin tests of test_ref_pin.py and test_ref_submap_pin.py
+hold the oracle to where the library cannot be built) is written by those tests themselves, where it can:
+
+    VGX_RECORD_REF_OUTPUTS=1 python -m pytest tests/test_ref_pin.py tests/test_ref_submap_pin.py"""
 import hashlib
 import os
 import sys

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -40,9 +41,14 @@ def _run(cmd, tmp, env=None, timeout=900):
 
 
 @pytest.fixture(scope="module")
-def single_run(tmp_path_factory):
-    return _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--cpu-seconds", "1"] + SMALL,
-                str(tmp_path_factory.mktemp("bench1")), timeout=600)
+def single_dir(tmp_path_factory):
+    return str(tmp_path_factory.mktemp("bench1"))
+
+
+@pytest.fixture(scope="module")
+def single_run(single_dir):
+    return _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--cpu-seconds", "1",
+                 "--dump-outputs", os.path.join(single_dir, "rows")] + SMALL, single_dir, timeout=600)
 
 
 @pytest.fixture(scope="module")
@@ -134,6 +140,39 @@ def test_single_gpu_line_has_the_contract_fields(single):
     assert 0 < c2["reproducible_tsdf_mode"]["xy_rmse_m_optimised"] < c2["xy_rmse_m_odometry_only"]
 
 
+DUMPED = {"rows": np.float64, "residuals": np.float32, "jacobian_ref": np.float32, "jacobian_read": np.float32}
+
+
+def _load_rows(d):
+    return {k: np.load(os.path.join(d, k + ".npy")) for k in DUMPED}
+
+
+def test_plain_run_times_the_headline_only_and_dumps_the_rows_it_computed(single, single_dir, tmp_path):
+    """Without --full: the headline loop and nothing else -- no roofline, other workload, solve, CPU baseline or parity
+    gate -- and --dump-outputs writes the same sampled rows of the last timed pass as the --full run does."""
+    rows_dir = os.path.join(str(tmp_path), "rows")
+    small = [a for a in SMALL if a != "--no-tsdf"]
+    d, line, _ = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dump-outputs", rows_dir] + small,
+                      str(tmp_path), timeout=300)
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["metric"] == single["metric"] and line["unit"] == single["unit"] and line["dtype"] == "f32"
+    assert line["higher_is_better"] is True
+    assert abs(line["ms_per_step"] - line["ms_per_pass"] * single["config"]["passes_per_step"]) <= 1e-3 * line["ms_per_step"]
+    assert d["config"]["residuals_per_pass"] == single["config"]["residuals_per_pass"]
+    for k in ("roofline", "cpu_baseline", "parity", "fused", "value_with_correspondence"):
+        assert line.get(k) is None, k
+    for k in ("solve", "tsdf", "config5", "pipeline_config2", "shipped_config", "multi_context", "roofline_full_overlap"):
+        assert d.get(k) is None, k
+    got, want = _load_rows(rows_dir), _load_rows(os.path.join(single_dir, "rows"))
+    assert sum(os.path.getsize(os.path.join(rows_dir, k + ".npy")) for k in DUMPED) <= 64 << 20
+    n = len(got["rows"])
+    assert n > 0 and got["residuals"].shape == (n,) and got["jacobian_ref"].shape == got["jacobian_read"].shape == (n, 4)
+    assert np.all(np.diff(got["rows"]) > 0) and got["rows"][-1] < d["config"]["residuals_per_pass"]
+    for k, dt in DUMPED.items():
+        assert got[k].dtype == dt, k
+        assert np.array_equal(got[k].view(np.uint8), want[k].view(np.uint8)), k      # same inputs, same bits
+
+
 def c5_headline(c5):
     """config 5's headline is the time to within 1e-3 of the final cost, never above solve_ms"""
     return 0 < c5["solve_ms_to_within_1e-3_of_final_cost"] <= c5["solve_ms"] * 1.001
@@ -142,7 +181,8 @@ def c5_headline(c5):
 def test_two_rank_path_dry_run_on_one_gpu(single, tmp_path):
     env = dict(os.environ, VGX_BENCH_DRYRUN="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-           "--master-addr", "127.0.0.1", "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2"] + SMALL
+           "--master-addr", "127.0.0.1", "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2",
+           "--full"] + SMALL
     d, line, _ = _run(cmd, str(tmp_path), env=env)
     assert line["n_gpus"] == 2 and line["cpu_baseline"] is None and line["rccl_ranks"] == 0     # dry run: gloo
     assert d["n_gpus"] == 2 and "DRY RUN" in d["data"] and d["cpu_baseline"] is None
@@ -177,7 +217,7 @@ def test_one_rank_under_torchrun_goes_through_rccl(single, tmp_path):
     env = {k: v for k, v in os.environ.items() if k != "VGX_BENCH_DRYRUN"}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "1",
-           "--cpu-seconds", "1"] + SMALL
+           "--full", "--cpu-seconds", "1"] + SMALL
     d, line, _ = _run(cmd, str(tmp_path), env=env)
     assert line["n_gpus"] == 1 and line["rccl_ranks"] == 1
     assert "DRY RUN" not in d["data"]
@@ -192,7 +232,7 @@ def test_inprocess_flag_dry_run_on_one_gpu(single, tmp_path):
     """`bench.py --gpus 2 --inprocess`: ONE process, two contexts (here both on the one GPU), the headline loop
     on context 0 and vgx_reg_multi_evaluate_fused over both in `multi_context` -- same line, same keys"""
     env = dict(os.environ, VGX_BENCH_DRYRUN="gloo")
-    d, line, _ = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--inprocess", "--no-cpu-baseline",
+    d, line, _ = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--inprocess", "--full", "--no-cpu-baseline",
                        "--no-config5", "--no-config2", "--no-solve", "--no-shipped"] + SMALL, str(tmp_path), env=env, timeout=600)
     assert d["n_gpus"] == 1 and d["inprocess_gpus"] == 2
     mc = d["multi_context"]
