@@ -87,7 +87,7 @@ VGX_API const char* vgx_last_error(vgx_ctx ctx);
  * Measured per-scan latency under a running solve: bench.py `tsdf.*.latency_under_solve_us`,
  * profiles/r06_scan_latency.txt.  Streams handed in by the caller keep the priority
  * the caller gave them.  vgx_ctx_stream_priorities: 1 when the own streams were created that way (0: the device offers
- * one level only, or VGX_STREAM_PRIORITY=0 in the environment -- A/B aid).
+ * one level only).
  *
  * vgx_ctx_set_stream: launch the registration side on an existing hipStream_t (e.g. the caller's PyTorch stream);
  * vgx_ctx_set_tsdf_stream: the same for the TSDF side (waits for what that side has queued so far).  NULL restores

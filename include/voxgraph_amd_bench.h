@@ -62,7 +62,7 @@ VGX_API int vgx_bench_stream_ceiling(vgx_ctx ctx, const void* d_src, int64_t rea
 /* What the rays of the last COUNTED racing scan did (vgx_tsdf_integrate[_device] with n_updates != NULL resets the
  * statistics before the scan and makes the kernel gather them; an uncounted scan gathers nothing):
  *   stats[0]  the longest chain of DEPENDENT round trips to the observed set any ray needed (rounds of the cooperative
- *             walk; with VGX_TSDF_KERNEL=v1: voxel steps, one exchange each)
+ *             walk)
  *   stats[1]  exchanges on the observed set, all rays together       stats[2]  voxel updates that also blended a colour
  *   stats[3]  peeks (plain loads of an observed-set slot ahead of the exchanges)
  *   stats[4]  per-voxel folds (one block lookup + one {distance, weight} load + one compare-and-swap each, + colour)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of the XCD-aware launch order of the materialising pass's tiles (VGX_POINTS_TILE_ORDER,
 # vgx_reg.hip make_xcd_order, uniform_work): ms per pass on config 3 / full overlap, interleaved, two
-# rounds, crossed with the chunk culling of that pass (VGX_POINTS_CULL); then one PMC pass per setting for the points kernel's fabric read bytes.
+# rounds; then one PMC pass per setting for the points kernel's fabric read bytes.
 #   gpurun -- 'bash profiles/ab_porder.sh'
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out
@@ -14,10 +14,10 @@ fo=d["roofline_full_overlap"]
 print("points kernel config3 %.3f ms/pass (%.1f G evals/s) | full overlap %.3f ms (%.1f G evals/s)" % (
  d["roofline"]["kernel_ms"],d["value"]/1e3,fo["kernel_ms"],fo["value"]/1e3))'
 for round in 1 2; do
-  for v in 0 1; do for k in 0 1; do
-    printf "round %s VGX_POINTS_TILE_ORDER=%s VGX_POINTS_CULL=%s " $round $v $k
-    VGX_POINTS_CULL=$k VGX_POINTS_TILE_ORDER=$v timeout 300 python $REPO/bench.py --full-line $ARGS 2>$OUT/ab_porder.err | python -c "$pick" || tail -3 $OUT/ab_porder.err
-  done; done
+  for v in 0 1; do
+    printf "round %s VGX_POINTS_TILE_ORDER=%s " $round $v
+    VGX_POINTS_TILE_ORDER=$v timeout 300 python $REPO/bench.py --full-line $ARGS 2>$OUT/ab_porder.err | python -c "$pick" || tail -3 $OUT/ab_porder.err
+  done
 done
 cd /tmp
 for v in 0 1; do

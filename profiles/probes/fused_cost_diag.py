@@ -39,4 +39,3 @@ for c, (a, b) in enumerate(pairs):
                 abs(float(r32 @ r32) - cost) / max(cost, 1e-300)))
 for o in sorted(out, reverse=True)[:5]:
     print("fused cost rel err %.3e  pair %s cost %.6g  nonzero rows %d  max|r| %.3g median|r| %.3g   (f32-rounded rows' own sum rel err %.1e)" % o)
-print("variant", os.environ.get("VGX_FUSED_KERNEL", "default"))

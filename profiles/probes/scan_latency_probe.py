@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """Per-scan latency of the racing TSDF mode while a solve runs on the same context: LiDAR 64 x 1024 at
 10 Hz and 640 x 480 depth images at 30 Hz on thread A, thread B looping (a) fused solver evaluations or (b) materialising
-passes of the config-3 graph.  Run once with VGX_STREAM_PRIORITY=1 (shipped: TSDF stream high, registration stream low) and
-once with 0 (both default): profiles/probes/run_scan_latency.sh."""
+passes of the config-3 graph (TSDF stream high priority, registration stream low)."""
 import json
 import os
 import sys
@@ -56,7 +55,7 @@ def fused_device_step():
 for _ in range(3):
     fused_step()
     points_step()
-print(json.dumps({"stream_priorities": ctx.stream_priorities(), "VGX_STREAM_PRIORITY": os.environ.get("VGX_STREAM_PRIORITY")}))
+print(json.dumps({"stream_priorities": ctx.stream_priorities()}))
 for name, (dirs, vs, kw, bmin, bdim) in sensor_cases().items():
     sensor = "rgbd" if name.startswith("rgbd") else "lidar"
     T, clouds = session_scans(dirs, 20)

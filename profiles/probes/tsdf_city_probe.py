@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """The racing TSDF kernel on the config-2 session's scans (64 x 1024 beams sphere-traced against the analytic city, 16 m
 rays, 0.2 m voxels: LONG rays and many cast rays per workgroup -- the regime opposite to the room sessions of
-tsdf_racing_probe.py): median kernel time per scan (HIP events, stream drained before) and one counted scan's statistics.
-The kernel is chosen by the environment (VGX_TSDF_KERNEL=v1) as in tsdf_racing_probe.py."""
+tsdf_racing_probe.py): median kernel time per scan (HIP events, stream drained before) and one counted scan's statistics."""
 import gc
 import json
 import os
@@ -48,20 +47,19 @@ def main(n_submaps=2, scans_per_submap=30):
             if m == 1 and j == first + 10:
                 u = integ.integrate_device(T, pts.data_ptr(), None, n_az * n_el, count=True)
                 stats = dict(integ.walk_stats(), updates=u)
-                if os.environ.get("VGX_TSDF_KERNEL") != "v1":
-                    t = integ.read_trace(4096)
-                    has = t[:, 2] > 0
-                    trace = {"rays_total": float(t[:, 4].sum()), "rays_max": float(t[:, 4].max()), "rounds_max": float(t[:, 5].max()),
-                             "folds_total": float(t[:, 6].sum()), "span_us": float(t[:, 3].max()),
-                             "phase1_us_mean": float((t[:, 1] - t[:, 0]).mean()),
-                             "walk_us_mean": float((t[has, 2] - t[has, 1]).mean()), "walk_us_max": float((t[has, 2] - t[has, 1]).max()),
-                             "flush_us_mean": float((t[has, 3] - t[has, 2]).mean()), "flush_us_max": float((t[has, 3] - t[has, 2]).max())}
+                t = integ.read_trace(4096)
+                has = t[:, 2] > 0
+                trace = {"rays_total": float(t[:, 4].sum()), "rays_max": float(t[:, 4].max()), "rounds_max": float(t[:, 5].max()),
+                         "folds_total": float(t[:, 6].sum()), "span_us": float(t[:, 3].max()),
+                         "phase1_us_mean": float((t[:, 1] - t[:, 0]).mean()),
+                         "walk_us_mean": float((t[has, 2] - t[has, 1]).mean()), "walk_us_max": float((t[has, 2] - t[has, 1]).max()),
+                         "flush_us_mean": float((t[has, 3] - t[has, 2]).mean()), "flush_us_max": float((t[has, 3] - t[has, 2]).max())}
                 continue
             ctx.timer_start()
             integ.integrate_device(T, pts.data_ptr(), None, n_az * n_el)
             per.append(ctx.timer_stop())
     gc.enable()
-    print(json.dumps({"kernel": os.environ.get("VGX_TSDF_KERNEL", "coop"), "organised": organised,
+    print(json.dumps({"kernel": "coop", "organised": organised,
                       "kernel_us_median": float(np.median(per)) * 1e3, "kernel_us_min": float(np.min(per)) * 1e3,
                       "kernel_us_mean": float(np.mean(per)) * 1e3, "kernel_us_max": float(np.max(per)) * 1e3, "stats": stats, "trace": trace}))
 

@@ -1,8 +1,6 @@
 #!/usr/bin/env python3
 """The racing TSDF kernel by itself on the two bench sessions: per-scan kernel time (HIP events, stream drained before each
-launch), back-to-back time, and what the rays did (vgx_tsdf_integrator_walk_stats).  The kernel is chosen by the
-environment (VGX_TSDF_KERNEL=v1: the one-thread-per-point kernel of rounds 1-4), so an A/B is two processes:
-    VGX_TSDF_KERNEL=v1 python profiles/probes/tsdf_racing_probe.py ; python profiles/probes/tsdf_racing_probe.py
+launch), back-to-back time, and what the rays did (vgx_tsdf_integrator_walk_stats).
 Also checks the layer of every session against the other modes' order-independent facts: update count > 0, nothing dropped."""
 import json
 import os
@@ -20,7 +18,7 @@ def main(scans=20):
     from voxgraph_amd import capi
     capi.load()
     ctx = capi.Context(0)
-    out = {"kernel": os.environ.get("VGX_TSDF_KERNEL", "v2 (cooperative)")}
+    out = {"kernel": "cooperative"}
     for name, (dirs, vs, kw, _, _) in sensor_cases().items():
         poses, clouds = session_scans(dirs, scans)
         n_pts = clouds[0].shape[0]
@@ -59,11 +57,10 @@ def main(scans=20):
         integ.setLayer(layer3)
         stats, traces = [], []
         wgs = (n_pts + 255) // 256 if not width else ((width + 15) // 16) * ((n_pts // width + 15) // 16)
-        v1 = os.environ.get("VGX_TSDF_KERNEL") == "v1"
         for k in range(scans):
             u = integ.integrate_device(poses[k], dev[k].data_ptr(), None, n_pts, count=True)
             stats.append(dict(integ.walk_stats(), updates=u))
-            if not v1 and k >= 1:
+            if k >= 1:
                 t = integ.read_trace(wgs)
                 has_walk = t[:, 2] > 0
                 traces.append({"start_spread_us": float(t[:, 0].max()), "span_us": float(t[:, 3].max()),

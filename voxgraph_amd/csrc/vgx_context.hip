@@ -341,11 +341,9 @@ int vgx_ctx_create(int device, vgx_ctx* out) {
   // (voxgraph_mapper.cpp:218-238: optimisation runs in the background of the mapping thread).  So the TSDF stream is
   // created with the device's highest priority and the registration stream with its lowest: the scan's workgroups are
   // dispatched as soon as workgroups of the evaluation retire instead of queueing behind all of them
-  // (profiles/r06_scan_latency.txt: per-scan latency under a running solve with and without).  VGX_STREAM_PRIORITY=0: both
-  // at the default priority (A/B aid).
+  // (profiles/r06_scan_latency.txt: per-scan latency under a running solve with and without).
   int prio_least = 0, prio_greatest = 0;
-  const char* prio_env = getenv("VGX_STREAM_PRIORITY");
-  const bool use_prio = !(prio_env && atoi(prio_env) == 0) && hipSetDevice(device) == hipSuccess &&
+  const bool use_prio = hipSetDevice(device) == hipSuccess &&
                         hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) == hipSuccess;
   ctx->stream_priorities = use_prio && prio_least != prio_greatest;
   if (hipSetDevice(device) != hipSuccess ||

@@ -34,13 +34,10 @@ namespace vgx {
 //      d(x,y+1,z+1)}, x fastest.  A neighbourhood is two consecutive float4: 32 contiguous bytes, one or
 //      two cache lines.  4.25 x memory.  Fastest where evaluations are scattered (sampling mode: every
 //      touched line is an HBM fetch): -14 % per evaluation of the shipped configuration, +18-25 % on the
-//      all-points passes (profiles/ab_layout.sh).
+//      all-points passes (profiles/README.md, round 3).
 //   2  4^3 sub-tiles with their own aprons (5^3 floats, padded to 128): the four x-pairs of a
-//      neighbourhood lie within 128 B.  2 x memory.  Measured in between; kept as an experiment
-//      (compile-time default only: -DVGX_BRICK_LAYOUT_DEFAULT=2).
-#ifndef VGX_BRICK_LAYOUT_DEFAULT
-#define VGX_BRICK_LAYOUT_DEFAULT 0
-#endif
+//      neighbourhood lie within 128 B.  2 x memory.  Measured in between; not selectable through
+//      vgx_ctx_set_brick_layout.
 template <int VPS, int LAYOUT>
 struct BrickLayout {
   static constexpr int B = VPS + 1;
@@ -162,7 +159,7 @@ struct Context {
   std::mutex err_mu;       // guards last_error only (set_error is called with and without `mu`)
   std::string last_error;
   int cu_count = 256;
-  int brick_layout = VGX_BRICK_LAYOUT_DEFAULT;  // of the submaps created from now on (vgx_ctx_set_brick_layout)
+  int brick_layout = 0;  // of the submaps created from now on (vgx_ctx_set_brick_layout)
   int sampling_bricks = 1;  // VGX_SAMPLING_BRICKS_QUAD: all-sampling batches read quad bricks made on demand
   // Evaluation slots of the drop-in Evaluate path.  A call takes a free slot for its duration
   // (stream, ordering event, device staging for the f64 outputs, pinned + device staging for the

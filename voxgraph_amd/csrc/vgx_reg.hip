@@ -124,20 +124,6 @@ __device__ __forceinline__ const VGX_GLOBAL T* as_global(const T* p) {
 template <int VPS>
 __device__ __forceinline__ void locate_axis(float p, const GridDev& g, int& blk, int& vox,
                                             float& delta) {
-#ifdef VGX_LOCATE_UPPER_BOUND
-  // EXPERIMENT ONLY (profiles/r06_locate_upper_bound.txt; `make SUFFIX=_fastloc EXTRA=-DVGX_LOCATE_UPPER_BOUND`): the
-  // cheapest conceivable point location -- one fma, one floor, shifts; no guard, offsets NOT the reference's bits -- to
-  // bound from above what a guarded two-speed locate_axis could gain.  Never shipped.
-  {
-    const float t = fmaf(p, g.voxel_size_inv, -0.5f);
-    const float fl = floorf(t);
-    const int gi = (int)fl;
-    blk = gi >> (VPS == 16 ? 4 : 3);
-    vox = gi & (VPS - 1);
-    delta = t - fl;
-    return;
-  }
-#endif
   blk = (int)floorf(p * g.block_size_inv + 1e-6f);
   float origin = (float)blk * g.block_size;
   int v = (int)floorf((p - origin) * g.voxel_size_inv + 1e-6f);
@@ -305,20 +291,11 @@ struct Out4<double> {
   }
 };
 
-// Optional XCD-aware tile order: workgroup b runs on XCD b % 8 (observed dispatch
-// order), so each XCD could be handed one contiguous range of tiles to keep
-// neighbouring bricks in one L2.  MEASURED SLOWER here (5.24-5.55 ms vs 5.03-5.31 ms for
-// the materialising kernel, 2.66 vs 2.54 ms fused; profiles/ab_swizzle.sh): the kernels
-// are HBM-stream bound, the gathers already hit in L2/MALL, and eight XCDs streaming eight
-// distant address ranges is worse for the memory system than one interleaved front.
-// Default: off (identity mapping); VGX_XCD_SWIZZLE=1 re-enables it for experiments.
-__constant__ int g_xcd_swizzle = 0;
-__constant__ int g_points_cull = 1;  // VGX_POINTS_CULL=0: the materialising pass reads every point (A/B)
-__device__ __forceinline__ int swizzle_tile(int b, int n_tiles) {
-  if (!g_xcd_swizzle) return b;
-  int chunk = (n_tiles + 7) >> 3;
-  return (b & 7) * chunk + (b >> 3);
-}
+// Tiles run in launch order.  An XCD-aware order (workgroup b runs on XCD b % 8, so each XCD could be
+// handed one contiguous range of tiles to keep neighbouring bricks in one L2) MEASURED SLOWER here
+// (5.24-5.55 ms vs 5.03-5.31 ms for the materialising kernel, 2.66 vs 2.54 ms fused): the kernels are
+// HBM-stream bound, the gathers already hit in L2/MALL, and eight XCDs streaming eight distant address
+// ranges is worse for the memory system than one interleaved front.
 
 // True when no point inside the sphere (centre in the reference frame) can have a
 // correspondence in grid g under pose pack P: the base block of p' is the block of p'
@@ -341,26 +318,17 @@ __host__ __device__ __forceinline__ bool chunk_outside(const GridDev& g, const P
 // ---------------------------------------------------------------------------
 // kernel 1: materialise residuals + Jacobians (88 B / evaluation as f32)
 // ---------------------------------------------------------------------------
-// Registration points are read exactly once per constraint evaluation: stream them with
-// the non-temporal hint (A/B switch VGX_NT_LOADS, compile-time default below).
-template <bool NT, typename T>
-__device__ __forceinline__ T load_stream(const VGX_GLOBAL T* p) {
-  if constexpr (NT) return __builtin_nontemporal_load(p); else return *p;
-}
-
-// Output rows are written once and never re-read by this kernel: with NT the stores
-// carry the non-temporal hint so the 36 B/row write stream does not evict the bricks
-// and block tables the gathers re-use from L2.
-template <bool NT, typename T>
+// Output rows are written once and never re-read by this kernel: the f32 stores carry the
+// non-temporal hint so the 36 B/row write stream does not evict the bricks and block tables the
+// gathers re-use from L2 (measured 6.08 -> 5.40 ms).  Point loads stay plain.
+template <typename T>
 __device__ __forceinline__ void store_out(T* p, T v) {
-  if constexpr (NT) __builtin_nontemporal_store(v, p); else *p = v;
+  __builtin_nontemporal_store(v, p);
 }
-template <bool NT>
 __device__ __forceinline__ void store_out4(float4* p, float4 v) {
   f32x4 x = {v.x, v.y, v.z, v.w};
-  if constexpr (NT) __builtin_nontemporal_store(x, reinterpret_cast<f32x4*>(p)); else *p = v;
+  __builtin_nontemporal_store(x, reinterpret_cast<f32x4*>(p));
 }
-template <bool NT>
 __device__ __forceinline__ void store_out4(double4* p, double4 v) {
   *p = v;  // drop-in f64 path: followed by a D2H copy, keep it cacheable
 }
@@ -558,10 +526,10 @@ __global__ __launch_bounds__(256) void reg_points_tile_dead_kernel(const Constra
   if (t >= n_tiles) return;
   const Tile tile = tiles[t];
   const ConstraintDev& C = cons[tile.constraint];
-  dead[t] = g_points_cull && tile_cullable(C) && tile_outside<PPT>(C, packs[tile.constraint], tile);
+  dead[t] = tile_cullable(C) && tile_outside<PPT>(C, packs[tile.constraint], tile);
 }
 
-template <int VPS, int LAYOUT, typename OUT, int PPT, bool NT, bool NTL>
+template <int VPS, int LAYOUT, typename OUT, int PPT>
 __device__ __forceinline__ void reg_eval_points_body(
     const ConstraintDev& C, const PosePack& P, const Tile& tile, int dead_hint, OUT* __restrict__ residuals,
     typename Out4<OUT>::type* __restrict__ jac_ref, typename Out4<OUT>::type* __restrict__ jac_read) {
@@ -582,7 +550,7 @@ __device__ __forceinline__ void reg_eval_points_body(
     bool any_live = dead_hint == 0;
     if (dead_hint < 0) {
       any_live = true;
-      if (g_points_cull && tile_cullable(C)) any_live = !tile_outside<PPT>(C, P, tile);
+      if (tile_cullable(C)) any_live = !tile_outside<PPT>(C, P, tile);
     }
     if (!any_live) {
 #pragma unroll
@@ -590,9 +558,9 @@ __device__ __forceinline__ void reg_eval_points_body(
         int local = j * kBlockThreads + (int)threadIdx.x;
         if (local >= tile.count) continue;
         int64_t row = C.row0 + tile.start + local;
-        store_out<NT>(&residuals[row], (OUT)0);  // r = w * 0, Jacobians zero (RCF:165-170)
-        if (jac_ref) store_out4<NT>(&jac_ref[row], Out4<OUT>::make(0.0, 0.0, 0.0, 0.0));
-        if (jac_read) store_out4<NT>(&jac_read[row], Out4<OUT>::make(0.0, 0.0, 0.0, 0.0));
+        store_out(&residuals[row], (OUT)0);  // r = w * 0, Jacobians zero (RCF:165-170)
+        if (jac_ref) store_out4(&jac_ref[row], Out4<OUT>::make(0.0, 0.0, 0.0, 0.0));
+        if (jac_read) store_out4(&jac_read[row], Out4<OUT>::make(0.0, 0.0, 0.0, 0.0));
       }
       return;
     }
@@ -612,8 +580,8 @@ __device__ __forceinline__ void reg_eval_points_body(
       pt[j] = sampled_point(C, i);
       w[j] = 1.0f;  // RCF:121
     } else {
-      pt[j] = load_stream<NTL>(as_global(reinterpret_cast<const f32x4*>(C.xyzd)) + i);
-      w[j] = load_stream<NTL>(as_global(C.weight) + i);
+      pt[j] = as_global(reinterpret_cast<const f32x4*>(C.xyzd))[i];
+      w[j] = as_global(C.weight)[i];
     }
   }
   // stage 1: exact base voxel of every point (registers only)
@@ -653,24 +621,24 @@ __device__ __forceinline__ void reg_eval_points_body(
                              pt[j].x, pt[j].y, pt[j].w, w[j], C.no_corr_cost, want_jac);
     int64_t row = C.row0 + tile.start + local;
     const double f = C.factor;  // RCF:274-291
-    store_out<NT>(&residuals[row], (OUT)(e.r * f));
+    store_out(&residuals[row], (OUT)(e.r * f));
     if (jac_ref)
-      store_out4<NT>(&jac_ref[row], Out4<OUT>::make((double)e.jo0 * f, (double)e.jo1 * f,
-                                                    (double)e.jo2 * f, (double)e.jo3 * f));
+      store_out4(&jac_ref[row], Out4<OUT>::make((double)e.jo0 * f, (double)e.jo1 * f,
+                                                (double)e.jo2 * f, (double)e.jo3 * f));
     if (jac_read)
-      store_out4<NT>(&jac_read[row], Out4<OUT>::make((double)-e.jo0 * f, (double)-e.jo1 * f,
-                                                     (double)-e.jo2 * f, (double)e.je3 * f));
+      store_out4(&jac_read[row], Out4<OUT>::make((double)-e.jo0 * f, (double)-e.jo1 * f,
+                                                 (double)-e.jo2 * f, (double)e.je3 * f));
   }
 }
 
 // batched form: descriptors, pose packs and tiles live in device memory
-template <int VPS, int LAYOUT, typename OUT, int PPT, bool NT, bool NTL>
+template <int VPS, int LAYOUT, typename OUT, int PPT>
 __global__ __launch_bounds__(kBlockThreads) void reg_eval_points_kernel(
     const ConstraintDev* __restrict__ cons, const PosePack* __restrict__ packs,
     const Tile* __restrict__ tiles, const unsigned char* __restrict__ tile_dead, int n_tiles,
     OUT* __restrict__ residuals, typename Out4<OUT>::type* __restrict__ jac_ref,
     typename Out4<OUT>::type* __restrict__ jac_read, int blocked) {
-  int t = swizzle_tile(blockIdx.x, n_tiles);
+  const int t = blockIdx.x;
   if (t >= n_tiles) return;
   const Tile tile = tiles[t];
   const int dead = tile_dead[t];
@@ -686,26 +654,26 @@ __global__ __launch_bounds__(kBlockThreads) void reg_eval_points_kernel(
     OUT* r_t = reinterpret_cast<OUT*>(blk) - first;
     O4* jr_t = reinterpret_cast<O4*>(blk + (long long)(PPT * kBlockThreads) * (long long)sizeof(OUT)) - first;
     O4* je_t = reinterpret_cast<O4*>(blk + (long long)(PPT * kBlockThreads) * (long long)(sizeof(OUT) + sizeof(O4))) - first;
-    reg_eval_points_body<VPS, LAYOUT, OUT, PPT, NT, NTL>(C, packs[tile.constraint], tile, dead, r_t, jr_t, je_t);
+    reg_eval_points_body<VPS, LAYOUT, OUT, PPT>(C, packs[tile.constraint], tile, dead, r_t, jr_t, je_t);
     return;
   }
-  reg_eval_points_body<VPS, LAYOUT, OUT, PPT, NT, NTL>(C, packs[tile.constraint], tile, dead, residuals, jac_ref, jac_read);
+  reg_eval_points_body<VPS, LAYOUT, OUT, PPT>(C, packs[tile.constraint], tile, dead, residuals, jac_ref, jac_read);
 }
 
 // drop-in form (one constraint per Evaluate): descriptor and pose pack travel as kernel
 // arguments and tiles are implicit, so an Evaluate needs no host->device copy at all
-template <int VPS, int LAYOUT, typename OUT, int PPT, bool NT, bool NTL>
+template <int VPS, int LAYOUT, typename OUT, int PPT>
 __global__ __launch_bounds__(kBlockThreads) void reg_eval_points_single_kernel(
     ConstraintDev C, PosePack P, int n_tiles, OUT* __restrict__ residuals,
     typename Out4<OUT>::type* __restrict__ jac_ref, typename Out4<OUT>::type* __restrict__ jac_read) {
-  int t = swizzle_tile(blockIdx.x, n_tiles);
+  const int t = blockIdx.x;
   if (t >= n_tiles) return;
   Tile tile;
   tile.constraint = 0;
   tile.start = (int64_t)t * (kBlockThreads * PPT);
   int64_t left = C.n - tile.start;
   tile.count = (int32_t)(left < kBlockThreads * PPT ? left : kBlockThreads * PPT);
-  reg_eval_points_body<VPS, LAYOUT, OUT, PPT, NT, NTL>(C, P, tile, /*dead_hint=*/-1, residuals, jac_ref, jac_read);
+  reg_eval_points_body<VPS, LAYOUT, OUT, PPT>(C, P, tile, /*dead_hint=*/-1, residuals, jac_ref, jac_read);
 }
 
 // ---------------------------------------------------------------------------
@@ -714,19 +682,14 @@ __global__ __launch_bounds__(kBlockThreads) void reg_eval_points_single_kernel(
 // u = (jo0, jo1, jo2, jo3, je3, r): [J r]^T [J r] (9x9) is a signed
 // re-arrangement of the 21 unique products of u because je0..2 == -jo0..2.
 constexpr int kReduceIters = 10;  // a fused-pass tile of a large constraint = kTilePoints * kReduceIters residuals (round 4: 20)
-constexpr bool kNonTemporalLoads = false;  // A/B: VGX_NT_LOADS=1
-constexpr bool kNonTemporalStores = true;  // measured 6.08 -> 5.40 ms (profiles/ab_nt.sh, VGX_NT_STORES=0/1)
-constexpr int kMaxReduceIters = 64;
-// Fused-kernel variant: 100 * waves_per_simd + 10 * points_per_thread + (1 = f64, 2 = f32
-// accumulators); VGX_FUSED_KERNEL overrides it for A/B runs (profiles/ab_fused2.sh).  Measured on
-// config 3: 421 2.17 ms, 422 1.79, 522 1.80, 622 1.76, 612 2.07, 812 1.95 (the round-1 kernel --
-// reference operation order, f64 accumulators, 124 VGPRs -- 2.23 ms).
-constexpr int kFusedVariantDefault = 622;
-#ifndef VGX_BALLOT_SKIP
-#define VGX_BALLOT_SKIP 1
-#endif
-constexpr bool kBallotSkip = VGX_BALLOT_SKIP != 0;
-
+// Fused-kernel shape: 2 points per thread, f32 accumulators, 6 waves per SIMD.  Measured on config 3 as
+// waves / points per thread / accumulator: 4/2/f64 2.17 ms, 4/2/f32 1.79, 5/2/f32 1.80, 6/2/f32 1.76,
+// 6/1/f32 2.07, 8/1/f32 1.95 (the round-1 kernel -- reference operation order, f64 accumulators,
+// 124 VGPRs -- 2.23 ms).
+constexpr int kLeanPointsPerThread = 2;
+constexpr int kLeanWaves = 6;
+// a wavefront none of whose points found a reading block skips its gathers and products
+constexpr bool kBallotSkip = true;
 
 // ---------------------------------------------------------------------------
 // kernel 2: fused normal equations (lean form)
@@ -753,7 +716,7 @@ constexpr bool kBallotSkip = VGX_BALLOT_SKIP != 0;
 // (profiles/fuzz_reg_large.py, 1 440 constraints of 128^3 submaps; rows exact throughout).  Gradients have
 // no such cancellation (they are differences of neighbours in both associations).  What must not happen in
 // either kernel -- a point assigned to the neighbouring cell -- cannot, because locate_stage1 is shared.
-// ACC = float keeps the 21 running products in f32 per thread across a tile (<= 2 * kMaxReduceIters
+// The 21 running products stay in f32 per thread across a tile (<= 2 * kReduceIters
 // terms), widened to f64 for the wave / workgroup / constraint reduction: half the accumulator
 // registers and no f64 FMA in the loop.  Fixed order throughout => bitwise reproducible.
 __device__ __forceinline__ bool eval_point_lean(const float c[8], bool have, float Dx, float Dy, float Dz,
@@ -802,25 +765,19 @@ __device__ __forceinline__ void lean_basis(const PosePack& P, double T[6][6]) {
   T[1][0] = (double)P.sin_e;  T[1][1] = (double)P.cos_e;
 }
 
-template <typename ACC>
-__device__ __forceinline__ void accumulate21(ACC acc[21], const float u[6]) {
+__device__ __forceinline__ void accumulate21(float acc[21], const float u[6]) {
 #pragma clang fp contract(fast)
-  ACC x[6];
-#pragma unroll
-  for (int a = 0; a < 6; ++a) x[a] = (ACC)u[a];
   int k = 0;
 #pragma unroll
   for (int a = 0; a < 6; ++a)
 #pragma unroll
-    for (int b = a; b < 6; ++b, ++k) acc[k] = x[a] * x[b] + acc[k];
+    for (int b = a; b < 6; ++b, ++k) acc[k] = u[a] * u[b] + acc[k];
 }
 
 // product 20 of accumulate21 (u[5] * u[5]) by itself: the cost-only pass's running sum
-template <typename ACC>
-__device__ __forceinline__ void accumulate_square(ACC& acc, float r) {
+__device__ __forceinline__ void accumulate_square(float& acc, float r) {
 #pragma clang fp contract(fast)
-  const ACC x = (ACC)r;
-  acc = x * x + acc;
+  acc = r * r + acc;
 }
 
 // Tiles are launched in an XCD-aware order (make_xcd_order); every tile still writes its partial
@@ -832,13 +789,15 @@ __device__ __forceinline__ void accumulate_square(ACC& acc, float r) {
 // 20 of the full pass, reduced through the same tree -- so the cost it returns is the full pass's cost BIT FOR BIT, and a
 // step accepted on the one is judged on the other's number.  No gradient, no pose-Jacobian products, a sixth of the
 // accumulator registers, a one-sum epilogue.
-template <int VPS, int LAYOUT, int PPT, typename ACC, int WAVES, bool COST_ONLY = false>
-__global__ __launch_bounds__(kBlockThreads, WAVES) void reg_eval_reduce_lean_kernel(
+template <int VPS, int LAYOUT, bool COST_ONLY>
+__global__ __launch_bounds__(kBlockThreads, kLeanWaves) void reg_eval_reduce_lean_kernel(
     const ConstraintDev* __restrict__ cons, const PosePack* __restrict__ packs,
     const Tile* __restrict__ tiles, int n_tiles, const int32_t* __restrict__ tile_first,
     double* __restrict__ partials) {
+  constexpr int PPT = kLeanPointsPerThread;
   constexpr int kIterPoints = kBlockThreads * PPT;
   static_assert(kChunkPoints % kIterPoints == 0, "an inner iteration never straddles a culling chunk");
+  static_assert(kReduceIters * kTilePoints <= 64 * kChunkPoints, "one ballot covers a tile's chunks");
   const int t = blockIdx.x;
   if (t >= n_tiles) return;
   const Tile tile = tiles[t];
@@ -852,22 +811,19 @@ __global__ __launch_bounds__(kBlockThreads, WAVES) void reg_eval_reduce_lean_ker
   const bool sampled = C.sample_raw != nullptr;
   const float4* bounds = (!count_misses && !sampled && C.chunk_bounds) ? C.chunk_bounds : nullptr;
   const long long chunk0 = tile.start / kChunkPoints;  // tiles start on chunk boundaries
-  // Which of the tile's chunks can touch the reading grid: a 128-bit mask PER WAVEFRONT (two ballots), no LDS and no
+  // Which of the tile's chunks can touch the reading grid: a 64-bit mask PER WAVEFRONT (one ballot), no LDS and no
   // barrier: the kernel needs no LDS of its own since round 6 (a tile's four wavefronts leave a row of sums each and the
   // finalize kernels add them).  What it is GIVEN at launch is another matter: launch_fused_tiles pads it with dynamic LDS
   // it never touches while the context integrates scans, to keep one workgroup's worth of registers free per CU.
   const int n_chunks = (tile.count + kChunkPoints - 1) / kChunkPoints;
   const int wlane = (int)(threadIdx.x & 63);
-  const unsigned long long live_lo =
+  const unsigned long long live =
       __ballot(wlane < n_chunks && !(bounds && chunk_outside(g, P, bounds[chunk0 + wlane])));
-  unsigned long long live_hi = 0ull;
-  if (n_chunks > 64)   // (VGX_FUSED_TILE_ITERS > 32 only; uniform)
-    live_hi = __ballot(wlane + 64 < n_chunks && !(bounds && chunk_outside(g, P, bounds[chunk0 + wlane + 64])));
-  auto chunk_live = [&](int k) { return ((k < 64 ? live_lo >> k : live_hi >> (k - 64)) & 1ull) != 0ull; };
+  auto chunk_live = [&](int k) { return ((live >> k) & 1ull) != 0ull; };
   constexpr int kAcc = COST_ONLY ? 1 : 21;
-  ACC acc[kAcc];
+  float acc[kAcc];
 #pragma unroll
-  for (int k = 0; k < kAcc; ++k) acc[k] = (ACC)0;
+  for (int k = 0; k < kAcc; ++k) acc[k] = 0.0f;
   const float nc = (float)C.no_corr_cost;
   const bool grid_empty = g.bricks == nullptr;
 
@@ -964,8 +920,8 @@ __global__ __launch_bounds__(kBlockThreads, WAVES) void reg_eval_reduce_lean_ker
       // (u[0..4] are zeros without a correspondence: eval_point_lean)  RCF:165-166: w * no_correspondence_cost with zero
       // Jacobian rows
       u[5] = ok ? u[5] : ((count_misses && in_range) ? w[j] * nc : 0.0f);
-      if (COST_ONLY) accumulate_square<ACC>(acc[0], u[5]);   // (the five Jacobian entries are dead code here)
-      else accumulate21<ACC>(acc, u);
+      if (COST_ONLY) accumulate_square(acc[0], u[5]);   // (the five Jacobian entries are dead code here)
+      else accumulate21(acc, u);
     }
   }
   // A tile leaves ONE ROW OF SUMS PER WAVEFRONT -- partials[tile slot][wave][22] -- and the finalize kernels add a tile's
@@ -1275,22 +1231,18 @@ static std::vector<Tile> make_draw_order(const std::vector<ConstraintDev>& desc,
 // Groups (constraints with the same point array) are dealt to the 8 XCD streams heaviest first, by
 // the points their tiles really load under chunk culling at the poses of the first evaluation (the
 // pattern barely moves between solver iterations), so that the XCDs finish together; launch
-// position 8 i + x takes the i-th tile of stream x.  VGX_FUSED_TILE_ORDER=0 keeps the plain
-// constraint-major order (A/B, profiles/ab_order.sh).  Only the launch order changes: every tile
+// position 8 i + x takes the i-th tile of stream x.  Only the launch order changes: every tile
 // writes its partial sums to its own slot, so results are bit for bit the same either way.
 static bool make_xcd_order(const std::vector<ConstraintDev>& desc, const std::vector<int32_t>& tile_first,
                            const std::vector<int32_t>& tile_work, std::vector<Tile>& tiles, bool points_pass) {
-  static const bool enabled_fused = [] {
-    const char* e = getenv("VGX_FUSED_TILE_ORDER");
-    return e ? atoi(e) != 0 : true;
-  }();
-  // read per batch (not once per process): bench.py measures one workload both ways in one process
-  const bool enabled_points = [] {
+  // VGX_POINTS_TILE_ORDER=0 keeps the materialising pass in plain constraint-major order.  Read per batch (not once per
+  // process): bench.py measures one workload both ways in one process.
+  if (points_pass) {
     const char* e = getenv("VGX_POINTS_TILE_ORDER");
-    return e ? atoi(e) != 0 : true;
-  }();
+    if (e && atoi(e) == 0) return false;
+  }
   const int n = (int)desc.size();
-  if (!(points_pass ? enabled_points : enabled_fused) || n < 2 || tiles.size() < 16) return false;
+  if (n < 2 || tiles.size() < 16) return false;
   // groups of constraints reading the same points (sampling constraints read scattered points: alone)
   std::vector<std::vector<int>> groups;
   {
@@ -1326,11 +1278,14 @@ static bool make_xcd_order(const std::vector<ConstraintDev>& desc, const std::ve
         }
   }
   // How much of the point traffic is shareable at all: per (group, chunk range) everything beyond the
-  // heaviest constraint's points could come out of the L2.  Measured (profiles/ab_order.sh): the
+  // heaviest constraint's points could come out of the L2.  Measured: the
   // full-overlap workload (0.83 shareable) 4.03 -> 2.67 ms and 27.7 -> 11.9 GB of fabric reads; config 3
   // (constraints of a group overlap DIFFERENT parts of the reference, little to share) 1.66 -> 1.64 ms;
   // config 5 1.17 -> 1.42 ms: long runs of heavy and of culled tiles per XCD stall the in-order
-  // dispatcher.  So the grouped order is used only where there is something to share and little is culled.
+  // dispatcher.  So the grouped order is used only where there is something to share (at least this
+  // fraction of the loaded points) and little is culled (at least this fraction of all points loaded).
+  constexpr double kOrderShareMin = 0.3;
+  constexpr double kOrderLiveMin = 0.75;
   {
     int64_t total = 0, shareable = 0;
     for (size_t g = 0; g < groups.size(); ++g) {
@@ -1348,23 +1303,12 @@ static bool make_xcd_order(const std::vector<ConstraintDev>& desc, const std::ve
         shareable += sum - mx;
       }
     }
-    static const double threshold = [] {
-      const char* e = getenv("VGX_FUSED_SHARE_THRESHOLD");
-      return e ? atof(e) : 0.3;
-    }();
-    if (getenv("VGX_DEBUG_ORDER"))
-      fprintf(stderr, "[vgx] %s tile order: %zu tiles, %zu groups, shareable %.3f of %lld loaded points\n",
-              points_pass ? "points" : "fused", tiles.size(), groups.size(), total ? (double)shareable / (double)total : 0.0, (long long)total);
-    if (total == 0 || (double)shareable < threshold * (double)total) return false;
+    if (total == 0 || (double)shareable < kOrderShareMin * (double)total) return false;
     // ... and only when few tiles are culled: with long runs of culled (instant) and of heavy tiles in
     // one XCD's sequence the in-order dispatcher stalls the other XCDs (config 5 above: 56 % culled)
     int64_t all_points = 0;
     for (const Tile& t : tiles) all_points += t.count;
-    static const double live_min = [] {
-      const char* e = getenv("VGX_ORDER_LIVE_MIN");
-      return e ? atof(e) : 0.75;
-    }();
-    if ((double)total < live_min * (double)all_points) return false;
+    if ((double)total < kOrderLiveMin * (double)all_points) return false;
   }
   std::vector<Tile> out = deal_to_xcds(group_tiles, group_work, tiles.size());
   tiles.swap(out);
@@ -1556,68 +1500,30 @@ __global__ void reg_scatter_normal_kernel(const double* __restrict__ normal, int
 // ---------------------------------------------------------------------------
 // launch helpers
 // ---------------------------------------------------------------------------
-// one-time application of the VGX_XCD_SWIZZLE experiment switch
-static void apply_swizzle_env() {
-  static const bool done = [] {
-    const char* e = getenv("VGX_XCD_SWIZZLE");
-    if (e) {
-      int v = atoi(e) != 0;
-      (void)hipMemcpyToSymbol(HIP_SYMBOL(g_xcd_swizzle), &v, sizeof(int));
-    }
-    if ((e = getenv("VGX_POINTS_CULL"))) {
-      int v = atoi(e) != 0;
-      (void)hipMemcpyToSymbol(HIP_SYMBOL(g_points_cull), &v, sizeof(int));
-    }
-    return true;
-  }();
-  (void)done;
-}
-
 template <typename OUT>
 static void launch_points(vgx_ctx ctx, int vps, int layout, const ConstraintDev* d_desc, const PosePack* d_pack,
                           const Tile* d_tiles, unsigned char* d_tile_dead, int n_tiles, void* res, void* jr,
                           void* je, bool blocked = false) {
   if (n_tiles <= 0) return;
-  apply_swizzle_env();
   hipLaunchKernelGGL(reg_points_tile_dead_kernel<kPointsPerThread>, dim3((n_tiles + 255) / 256), dim3(256), 0,
                      ctx->stream, d_desc, d_pack, d_tiles, n_tiles, d_tile_dead);
   dim3 grid(((n_tiles + 7) / 8) * 8), block(kBlockThreads);
   using O4 = typename Out4<OUT>::type;
-  static const bool nt = [] {
-    const char* e = getenv("VGX_NT_STORES");
-    return e ? atoi(e) != 0 : kNonTemporalStores;
-  }();
-  static const bool ntl = [] {
-    const char* e = getenv("VGX_NT_LOADS");
-    return e ? atoi(e) != 0 : kNonTemporalLoads;
-  }();
-#define VGX_LAUNCH_POINTS(VPS, LAYOUT, NT, NTL)                                                             \
-  hipLaunchKernelGGL((reg_eval_points_kernel<VPS, LAYOUT, OUT, kPointsPerThread, NT, NTL>), grid, block, 0, \
+#define VGX_LAUNCH_POINTS(VPS, LAYOUT)                                                              \
+  hipLaunchKernelGGL((reg_eval_points_kernel<VPS, LAYOUT, OUT, kPointsPerThread>), grid, block, 0, \
                      ctx->stream, d_desc, d_pack, d_tiles, d_tile_dead, n_tiles, (OUT*)res, (O4*)jr, (O4*)je, blocked ? 1 : 0)
-  if (sizeof(OUT) == 8 && layout == 0) {
-    // f64 rows (vgx_reg_batch_evaluate_points_f64): the default hints only (no A/B switches)
-    if (vps == 16) VGX_LAUNCH_POINTS(16, 0, kNonTemporalStores, kNonTemporalLoads);
-    else VGX_LAUNCH_POINTS(8, 0, kNonTemporalStores, kNonTemporalLoads);
-  } else if (layout == 0) {  // apron bricks: the A/B switches of the non-temporal hints live here
-    if (vps == 16) {
-      if (nt && ntl) VGX_LAUNCH_POINTS(16, 0, true, true);
-      else if (nt) VGX_LAUNCH_POINTS(16, 0, true, false);
-      else if (ntl) VGX_LAUNCH_POINTS(16, 0, false, true);
-      else VGX_LAUNCH_POINTS(16, 0, false, false);
-    } else {
-      if (nt) VGX_LAUNCH_POINTS(8, 0, true, kNonTemporalLoads);
-      else VGX_LAUNCH_POINTS(8, 0, false, kNonTemporalLoads);
-    }
+  if (layout == 0) {
+    if (vps == 16) VGX_LAUNCH_POINTS(16, 0);
+    else VGX_LAUNCH_POINTS(8, 0);
   } else if (layout == 1) {
-    if (vps == 16) VGX_LAUNCH_POINTS(16, 1, kNonTemporalStores, kNonTemporalLoads);
-    else VGX_LAUNCH_POINTS(8, 1, kNonTemporalStores, kNonTemporalLoads);
+    if (vps == 16) VGX_LAUNCH_POINTS(16, 1);
+    else VGX_LAUNCH_POINTS(8, 1);
   } else {
-    if (vps == 16) VGX_LAUNCH_POINTS(16, 2, kNonTemporalStores, kNonTemporalLoads);
-    else VGX_LAUNCH_POINTS(8, 2, kNonTemporalStores, kNonTemporalLoads);
+    if (vps == 16) VGX_LAUNCH_POINTS(16, 2);
+    else VGX_LAUNCH_POINTS(8, 2);
   }
 #undef VGX_LAUNCH_POINTS
 }
-
 
 template <typename OUT>
 static void launch_points_single(hipStream_t stream, int vps, const ConstraintDev& desc, const PosePack& pack,
@@ -1626,25 +1532,19 @@ static void launch_points_single(hipStream_t stream, int vps, const ConstraintDe
   if (n_tiles <= 0) return;
   dim3 grid(((n_tiles + 7) / 8) * 8), block(kBlockThreads);
   using O4 = typename Out4<OUT>::type;
-  static const bool nt = [] {
-    const char* e = getenv("VGX_NT_STORES");
-    return e ? atoi(e) != 0 : kNonTemporalStores;
-  }();
-#define VGX_LAUNCH_SINGLE(VPS, LAYOUT, NT)                                                                  \
-  hipLaunchKernelGGL((reg_eval_points_single_kernel<VPS, LAYOUT, OUT, kPointsPerThread, NT, kNonTemporalLoads>), \
-                     grid, block, 0, stream, desc, pack, n_tiles, (OUT*)res, (O4*)jr, (O4*)je)
+#define VGX_LAUNCH_SINGLE(VPS, LAYOUT)                                                                       \
+  hipLaunchKernelGGL((reg_eval_points_single_kernel<VPS, LAYOUT, OUT, kPointsPerThread>), grid, block, 0, stream, \
+                     desc, pack, n_tiles, (OUT*)res, (O4*)jr, (O4*)je)
   const int layout = desc.grid.layout;
   if (layout == 0) {
-    if (vps == 16 && nt) VGX_LAUNCH_SINGLE(16, 0, true);
-    else if (vps == 16) VGX_LAUNCH_SINGLE(16, 0, false);
-    else if (nt) VGX_LAUNCH_SINGLE(8, 0, true);
-    else VGX_LAUNCH_SINGLE(8, 0, false);
+    if (vps == 16) VGX_LAUNCH_SINGLE(16, 0);
+    else VGX_LAUNCH_SINGLE(8, 0);
   } else if (layout == 1) {
-    if (vps == 16) VGX_LAUNCH_SINGLE(16, 1, kNonTemporalStores);
-    else VGX_LAUNCH_SINGLE(8, 1, kNonTemporalStores);
+    if (vps == 16) VGX_LAUNCH_SINGLE(16, 1);
+    else VGX_LAUNCH_SINGLE(8, 1);
   } else {
-    if (vps == 16) VGX_LAUNCH_SINGLE(16, 2, kNonTemporalStores);
-    else VGX_LAUNCH_SINGLE(8, 2, kNonTemporalStores);
+    if (vps == 16) VGX_LAUNCH_SINGLE(16, 2);
+    else VGX_LAUNCH_SINGLE(8, 2);
   }
 #undef VGX_LAUNCH_SINGLE
 }
@@ -2131,11 +2031,6 @@ int vgx_reg_batch_create(vgx_ctx ctx, int32_t n, const vgx_reg* regs, const int3
   // that is a multiple of 8: tile t runs on XCD t % 8 and chunk culling is spatially structured, so with 16 tiles per
   // constraint the same XCDs got the live tiles of every constraint (config 3 1.58 -> 1.77 ms).
   auto reduce_iters_of = [](int64_t n_residuals) {
-    static const int forced = [] {
-      const char* e = getenv("VGX_FUSED_TILE_ITERS");  // A/B switch
-      return e ? atoi(e) : 0;
-    }();
-    if (forced > 0) return std::min(forced, kMaxReduceIters);
     return (int)std::min<int64_t>(kReduceIters, std::max<int64_t>(1, n_residuals / ((int64_t)kTilePoints * 5)));
   };
   int max_node = -1;
@@ -2335,12 +2230,8 @@ static int batch_begin(vgx_reg_batch b) {
   hipLaunchKernelGGL(mt_generate_kernel, dim3((unsigned)b->stream_jobs.size()), dim3(kMtThreads), 0, ctx->stream,
                      (const StreamJobDev*)b->d_stream_jobs);
   VGX_HIP(ctx, hipGetLastError());
-  static const int wgs_per_xcd = [] {
-    const char* e = getenv("VGX_DRAW_WGS_PER_XCD");  // A/B switch: tiles in flight per XCD (0: one workgroup per tile)
-    return e ? atoi(e) : kDrawWgsPerXcdDefault;
-  }();
-  // persistent: 8 x wgs_per_xcd workgroups walk the tile sequence; 0 / more workgroups than tiles: one per tile
-  const int per_xcd = (wgs_per_xcd > 0 && 8 * wgs_per_xcd < b->n_draw_tiles) ? wgs_per_xcd : (b->n_draw_tiles + 7) / 8;
+  // persistent: 8 x kDrawWgsPerXcdDefault workgroups walk the tile sequence; more workgroups than tiles: one per tile
+  const int per_xcd = 8 * kDrawWgsPerXcdDefault < b->n_draw_tiles ? kDrawWgsPerXcdDefault : (b->n_draw_tiles + 7) / 8;
   const dim3 grid((unsigned)(8 * per_xcd));
   hipLaunchKernelGGL(reg_draw_kernel, grid, dim3(256), 0, ctx->stream, (const ConstraintDev*)b->d_desc,
                      (const Tile*)b->d_draw_tiles, (int)b->n_draw_tiles, per_xcd, b->d_drawn_idx);
@@ -2727,10 +2618,6 @@ static int launch_fused_tiles(vgx_reg_batch b) {
     if (rc != VGX_OK) return rc;
     b->launch_order_made = true;
   }
-  static const int variant = [] {
-    const char* e = getenv("VGX_FUSED_KERNEL");  // A/B switch (profiles/ab_fused2.sh)
-    return e ? atoi(e) : kFusedVariantDefault;
-  }();
   // ROOM FOR A SCAN.  At 77 VGPRs the tile kernel is resident six workgroups deep on every CU (6 x 80 of a SIMD's 512
   // registers), and a racing TSDF scan's wavefronts need 104: while a solver evaluation ran, a scan submitted from the mapping
   // thread got a few workgroups in and the rest waited for the launch to drain -- 0.7 ms median, 1.4 ms worst (this kernel's
@@ -2740,47 +2627,24 @@ static int launch_fused_tiles(vgx_reg_batch b) {
   // is launched with 27 KB of dynamic LDS it never touches: FIVE resident workgroups per CU (160 KB / 27), 112 registers
   // free on every SIMD, room for one scan workgroup on every CU at any time: scans at 0.14-0.32 ms median / 0.22-0.45 ms
   // worst under a running solve, solver evaluations + 3 % (1.49 -> 1.53 ms).  Four per CU: 0.18 / 0.20 ms at + 12 %: not
-  // taken.  Without an integrator on the context: no padding.  VGX_FUSED_LDS_PAD=bytes overrides (0: never pad).
-  static const int pad_env = [] {
-    const char* e = getenv("VGX_FUSED_LDS_PAD");
-    return e ? atoi(e) : -1;
-  }();
-  const unsigned occupancy_pad = pad_env >= 0 ? (unsigned)pad_env : (ctx->tsdf_integrators.load() > 0 ? 27u * 1024u : 0u);
+  // taken.  Without an integrator on the context: no padding.
+  const unsigned occupancy_pad = ctx->tsdf_integrators.load() > 0 ? 27u * 1024u : 0u;
   if (n_tiles > 0) {
     dim3 grid(n_tiles), block(kBlockThreads);
     const int vps = b->regs[0]->reading->vps;
-#define VGX_LAUNCH_LEAN(VPS, LAYOUT, PPT, ACC, W)                                                                       \
-  hipLaunchKernelGGL((reg_eval_reduce_lean_kernel<VPS, LAYOUT, PPT, ACC, W, COST_ONLY>), grid, block, occupancy_pad, ctx->stream,  \
+#define VGX_LAUNCH_LEAN(VPS, LAYOUT)                                                                                \
+  hipLaunchKernelGGL((reg_eval_reduce_lean_kernel<VPS, LAYOUT, COST_ONLY>), grid, block, occupancy_pad, ctx->stream, \
                      b->d_desc, b->d_pack, b->d_reduce_tiles, n_tiles, b->d_tile_first, b->d_partials)
-#define VGX_LEAN_CASE(CODE, PPT, ACC, W)                                  \
-  case CODE:                                                              \
-    if (vps == 16) VGX_LAUNCH_LEAN(16, 0, PPT, ACC, W);                   \
-    else VGX_LAUNCH_LEAN(8, 0, PPT, ACC, W);                              \
-    break
-    if (b->layout == 1) {  // quad bricks: the shipped variant only
-      if (vps == 16) VGX_LAUNCH_LEAN(16, 1, 2, float, 6);
-      else VGX_LAUNCH_LEAN(8, 1, 2, float, 6);
+    if (b->layout == 1) {
+      if (vps == 16) VGX_LAUNCH_LEAN(16, 1);
+      else VGX_LAUNCH_LEAN(8, 1);
     } else if (b->layout == 2) {
-      if (vps == 16) VGX_LAUNCH_LEAN(16, 2, 2, float, 6);
-      else VGX_LAUNCH_LEAN(8, 2, 2, float, 6);
-    } else if (COST_ONLY) {
-      // one variant: with a single accumulator the register budget no longer chooses between them (the cost is the same
-      // bits as any f32-accumulating variant's; VGX_FUSED_KERNEL=421, the f64 one, has no cost-only twin)
-      if (variant == 421) return set_error(ctx, VGX_ERR_INVALID, "VGX_FUSED_KERNEL=421 (f64 accumulators) has no cost-only form");
-      if (vps == 16) VGX_LAUNCH_LEAN(16, 0, 2, float, 6);
-      else VGX_LAUNCH_LEAN(8, 0, 2, float, 6);
-    } else
-    switch (variant) {
-      VGX_LEAN_CASE(421, 2, double, 4);
-      VGX_LEAN_CASE(422, 2, float, 4);
-      VGX_LEAN_CASE(522, 2, float, 5);
-      VGX_LEAN_CASE(622, 2, float, 6);
-      VGX_LEAN_CASE(612, 1, float, 6);
-      VGX_LEAN_CASE(812, 1, float, 8);
-      default:
-        return set_error(ctx, VGX_ERR_INVALID, "VGX_FUSED_KERNEL: unknown variant");
+      if (vps == 16) VGX_LAUNCH_LEAN(16, 2);
+      else VGX_LAUNCH_LEAN(8, 2);
+    } else {
+      if (vps == 16) VGX_LAUNCH_LEAN(16, 0);
+      else VGX_LAUNCH_LEAN(8, 0);
     }
-#undef VGX_LEAN_CASE
 #undef VGX_LAUNCH_LEAN
     VGX_HIP(ctx, hipGetLastError());
   }

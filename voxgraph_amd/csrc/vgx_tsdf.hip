@@ -2,8 +2,8 @@
 // (call site voxgraph/src/frontend/measurement_processors/pointcloud_integrator.cpp:83;
 // arithmetic restated from voxblox [recalled], see oracle/tsdf_oracle.h).
 //
-// One thread per ray.  The reference's worker threads become 10^4..10^5 concurrent
-// rays with the same shared state and the same primitives:
+// The reference's worker threads become 10^4..10^5 concurrent rays (racing mode:
+// vgx_tsdf_coop_kernel.h) with the same shared state and the same primitives:
 //   * the two approximate hash sets are arrays of 64-bit words updated with
 //     atomic exchange (ApproxHashSet::replaceHash),
 //   * the per-voxel mutex + read-modify-write becomes a 64-bit compare-and-swap
@@ -33,337 +33,6 @@
 
 namespace vgx {
 
-
-
-// updateTsdfVoxel + computeDistance + Color::blendTwoColors [recalled]
-__device__ __forceinline__ void update_voxel(const TsdfLayerDev& L, const vgx_tsdf_config& c,
-                                             size_t at, float ox, float oy, float oz, float gx,
-                                             float gy, float gz, int vx, int vy, int vz,
-                                             uint32_t color, float weight) {
-  const float vs = L.voxel_size;
-  // getCenterPointFromGridIndex: (idx + 0.5) * voxel_size
-  float cx = ((float)vx + 0.5f) * vs, cy = ((float)vy + 0.5f) * vs, cz = ((float)vz + 0.5f) * vs;
-  float vvx = cx - ox, vvy = cy - oy, vvz = cz - oz;
-  float vpx = gx - ox, vpy = gy - oy, vpz = gz - oz;
-  float dist_G = norm3(vpx, vpy, vpz);
-  float dot = (vvx * vpx + vvy * vpy) + vvz * vpz;
-  float dist_G_V = dot / dist_G;
-  float sdf = dist_G - dist_G_V;
-  float updated_weight = weight;
-  const float trunc = c.default_truncation_distance;
-  if (c.use_weight_dropoff && sdf < -vs) {
-    updated_weight = weight * (trunc + sdf) / (trunc - vs);
-    updated_weight = fmaxf(updated_weight, 0.0f);
-  }
-  if (c.use_sparsity_compensation_factor && fabsf(sdf) < trunc)
-    updated_weight *= c.sparsity_compensation_factor;
-
-  unsigned long long* addr = &L.voxels[at];
-  unsigned long long old = __hip_atomic_load(addr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  float old_w;
-  while (true) {
-    float d = __uint_as_float((unsigned)(old & 0xffffffffull));
-    old_w = __uint_as_float((unsigned)(old >> 32));
-    float new_weight = old_w + updated_weight;
-    if (new_weight < 1e-6f) return;  // kFloatEpsilon
-    float new_sdf = (sdf * updated_weight + d * old_w) / new_weight;
-    float nd = (new_sdf > 0.0f) ? fminf(trunc, new_sdf) : fmaxf(-trunc, new_sdf);
-    float nw = fminf(c.max_weight, new_weight);
-    unsigned long long prev = atomicCAS(addr, old, pack_voxel(nd, nw));
-    if (prev == old) break;
-    old = prev;
-  }
-  if (fabsf(sdf) < trunc) {
-    // blend with the weight this update saw
-    uint32_t* caddr = &L.rgba[at];
-    uint32_t oc = __hip_atomic_load(caddr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    float total = old_w + updated_weight;
-    float fw = old_w / total, sw = updated_weight / total;
-    while (true) {
-      uint32_t nc = 0;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        float a = (float)((oc >> (8 * k)) & 0xffu), b = (float)((color >> (8 * k)) & 0xffu);
-        nc |= ((uint32_t)(uint8_t)roundf(a * fw + b * sw)) << (8 * k);
-      }
-      uint32_t prev = atomicCAS(caddr, oc, nc);
-      if (prev == oc) break;
-      oc = prev;
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// Software-pipelined voxel updates.  updateTsdfVoxel is a chain of dependent memory round trips
-// (load {d,w} -> CAS {d,w} -> load colour -> CAS colour), and the ray walk adds the approximate
-// set's exchange in front of it: up to five L2 round trips per DDA step, and the scan's kernel time
-// is the LONGEST ray's chain.  A ray never visits a voxel twice, so the update of voxel k-1 does
-// not depend on the walk's step k: the walk keeps three updates in flight, one per stage,
-//   stage 1: load {d,w} and colour      (voxel k-1)
-//   stage 2: CAS {d,w}                  (voxel k-2, expected value from its stage 1)
-//   stage 3: CAS colour                 (voxel k-3, blend weight from its stage 2)
-// and issues them together with step k's exchange: one round trip per step.  Values loaded a step
-// earlier may be stale when another ray got in between; the CAS then fails and is retried, exactly
-// as in the unpipelined loop.  Per ray the updates are still applied in walk order.
-struct PendingUpdate {
-  size_t at = 0;
-  float sdf = 0.0f, w = 0.0f, old_w = 0.0f;
-  unsigned long long expected = 0ull;
-  uint32_t expected_color = 0u;
-  bool active = false, blend = false;
-};
-
-// geometry of updateTsdfVoxel + computeDistance (same operations as update_voxel)
-__device__ __forceinline__ PendingUpdate make_update(const TsdfLayerDev& L, const vgx_tsdf_config& c,
-                                                     size_t at, float ox, float oy, float oz, float gx,
-                                                     float gy, float gz, int vx, int vy, int vz,
-                                                     float weight) {
-  PendingUpdate u;
-  const float vs = L.voxel_size;
-  float cx = ((float)vx + 0.5f) * vs, cy = ((float)vy + 0.5f) * vs, cz = ((float)vz + 0.5f) * vs;
-  float vvx = cx - ox, vvy = cy - oy, vvz = cz - oz;
-  float vpx = gx - ox, vpy = gy - oy, vpz = gz - oz;
-  float dist_G = norm3(vpx, vpy, vpz);
-  float dot = (vvx * vpx + vvy * vpy) + vvz * vpz;
-  float dist_G_V = dot / dist_G;
-  float sdf = dist_G - dist_G_V;
-  float updated_weight = weight;
-  const float trunc = c.default_truncation_distance;
-  if (c.use_weight_dropoff && sdf < -vs) {
-    updated_weight = weight * (trunc + sdf) / (trunc - vs);
-    updated_weight = fmaxf(updated_weight, 0.0f);
-  }
-  if (c.use_sparsity_compensation_factor && fabsf(sdf) < trunc)
-    updated_weight *= c.sparsity_compensation_factor;
-  u.at = at;
-  u.sdf = sdf;
-  u.w = updated_weight;
-  u.blend = fabsf(sdf) < trunc;
-  u.active = true;
-  return u;
-}
-
-__device__ __forceinline__ unsigned long long blended_voxel(const vgx_tsdf_config& c, const PendingUpdate& u,
-                                                            unsigned long long old, bool* skip) {
-  const float trunc = c.default_truncation_distance;
-  float d = __uint_as_float((unsigned)(old & 0xffffffffull));
-  float old_w = __uint_as_float((unsigned)(old >> 32));
-  float new_weight = old_w + u.w;
-  *skip = new_weight < 1e-6f;  // kFloatEpsilon: updateTsdfVoxel returns without touching the voxel
-  float new_sdf = (u.sdf * u.w + d * old_w) / new_weight;
-  float nd = (new_sdf > 0.0f) ? fminf(trunc, new_sdf) : fmaxf(-trunc, new_sdf);
-  float nw = fminf(c.max_weight, new_weight);
-  return pack_voxel(nd, nw);
-}
-
-
-// One pipeline beat: issues every stage's memory operation, then consumes the results and
-// shifts.  `s1` enters with an address only; leaves through s2 and s3.
-__device__ __forceinline__ void pipeline_beat(const TsdfLayerDev& L, const vgx_tsdf_config& c, uint32_t color,
-                                              PendingUpdate& s1, PendingUpdate& s2, PendingUpdate& s3) {
-  // ---- issue ----
-  unsigned long long e1 = 0ull, prev2 = 0ull, want2 = 0ull;
-  uint32_t ec1 = 0u, prevc3 = 0u, wantc3 = 0u;
-  bool skip2 = false;
-  if (s1.active) {
-    e1 = __hip_atomic_load(&L.voxels[s1.at], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (s1.blend) ec1 = __hip_atomic_load(&L.rgba[s1.at], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  if (s2.active) {
-    want2 = blended_voxel(c, s2, s2.expected, &skip2);
-    if (!skip2) prev2 = atomicCAS(&L.voxels[s2.at], s2.expected, want2);
-  }
-  const bool do3 = s3.active && s3.blend;
-  if (do3) {
-    wantc3 = blended_color(s3.expected_color, color, s3.old_w, s3.w);
-    prevc3 = atomicCAS(&L.rgba[s3.at], s3.expected_color, wantc3);
-  }
-  // ---- consume ----
-  if (do3) {
-    uint32_t oc = s3.expected_color;
-    while (prevc3 != oc) {  // another ray blended in between: retry on what it left
-      oc = prevc3;
-      prevc3 = atomicCAS(&L.rgba[s3.at], oc, blended_color(oc, color, s3.old_w, s3.w));
-    }
-  }
-  if (s2.active) {
-    unsigned long long old = s2.expected;
-    while (!skip2 && prev2 != old) {
-      old = prev2;
-      want2 = blended_voxel(c, s2, old, &skip2);
-      if (!skip2) prev2 = atomicCAS(&L.voxels[s2.at], old, want2);
-    }
-    s2.old_w = __uint_as_float((unsigned)(old >> 32));  // the weight this update saw
-    if (skip2) s2.active = false;                        // no colour blend either
-  }
-  if (s1.active) {
-    s1.expected = e1;
-    s1.expected_color = ec1;
-  }
-  // ---- shift ----
-  s3 = s2;
-  s2 = s1;
-  s1.active = false;
-}
-
-template <bool PIPELINED>
-__global__ __launch_bounds__(256) void tsdf_integrate_kernel(TsdfLayerDev L, TsdfIntegratorDev I,
-                                                            float qw, float qx, float qy, float qz,
-                                                            float tx, float ty, float tz,
-                                                            const float* __restrict__ points_C,
-                                                            const uint32_t* __restrict__ rgba,
-                                                            long long n, int freespace_points) {
-  const vgx_tsdf_config& c = I.cfg;
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  unsigned long long my_updates = 0, my_dropped = 0, my_walk = 0, my_blends = 0;
-  if (i < n) {
-    float px = points_C[3 * i], py = points_C[3 * i + 1], pz = points_C[3 * i + 2];
-    uint32_t color = rgba ? rgba[i] : 0u;
-    // isPointValid
-    bool valid = true, is_clearing = false;
-    float ray_distance = norm3(px, py, pz);
-    if (ray_distance < c.min_ray_length_m) {
-      valid = false;
-    } else if (ray_distance > c.max_ray_length_m) {
-      if (c.allow_clear || freespace_points) is_clearing = true; else valid = false;
-    } else {
-      is_clearing = freespace_points != 0;
-    }
-    if (valid) {
-      // T_G_C * point_C: Eigen _transformVector + translation
-      float uvx = qy * pz - qz * py, uvy = qz * px - qx * pz, uvz = qx * py - qy * px;
-      uvx += uvx; uvy += uvy; uvz += uvz;
-      float ccx = qy * uvz - qz * uvy, ccy = qz * uvx - qx * uvz, ccz = qx * uvy - qy * uvx;
-      float gx = (px + qw * uvx + ccx) + tx;
-      float gy = (py + qw * uvy + ccy) + ty;
-      float gz = (pz + qw * uvz + ccz) + tz;
-      const float vsi = L.voxel_size_inv;
-      const float sub_inv = c.start_voxel_subsampling_factor * vsi;
-      int sx = grid_index(gx * sub_inv + 1e-6f), sy = grid_index(gy * sub_inv + 1e-6f),
-          sz = grid_index(gz * sub_inv + 1e-6f);
-      if (approx_replace(I.start_set, I.start_offset, sx, sy, sz)) {
-        // RayCaster(origin, point_G, is_clearing, carving, max_ray, vsi, trunc, cast_from_origin=false)
-        float dx = gx - tx, dy = gy - ty, dz = gz - tz;
-        float len = norm3(dx, dy, dz);
-        float ux = dx / len, uy = dy / len, uz = dz / len;
-        const float trunc = c.default_truncation_distance;
-        float sxx, syy, szz, exx, eyy, ezz;  // ray_start, ray_end
-        if (is_clearing) {
-          float ray_length = fminf(fmaxf(len - trunc, 0.0f), c.max_ray_length_m);
-          exx = tx + ux * ray_length; eyy = ty + uy * ray_length; ezz = tz + uz * ray_length;
-          sxx = c.voxel_carving_enabled ? tx : exx;
-          syy = c.voxel_carving_enabled ? ty : eyy;
-          szz = c.voxel_carving_enabled ? tz : ezz;
-        } else {
-          exx = gx + ux * trunc; eyy = gy + uy * trunc; ezz = gz + uz * trunc;
-          sxx = c.voxel_carving_enabled ? tx : (gx - ux * trunc);
-          syy = c.voxel_carving_enabled ? ty : (gy - uy * trunc);
-          szz = c.voxel_carving_enabled ? tz : (gz - uz * trunc);
-        }
-        // setupRayCaster(end_scaled, start_scaled): walk from the surface to the sensor
-        float ss[3] = {exx * vsi, eyy * vsi, ezz * vsi};
-        float es[3] = {sxx * vsi, syy * vsi, szz * vsi};
-        bool bad = false;
-        int curr[3], sign[3];
-        float t_next[3], t_step[3];
-        long long steps = 0;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-          bad |= (ss[a] != ss[a]) | (es[a] != es[a]);
-          curr[a] = grid_index(ss[a] + 1e-6f);
-          int end_index = grid_index(es[a] + 1e-6f);
-          int diff = end_index - curr[a];
-          steps += diff < 0 ? -diff : diff;
-          float ray_scaled = es[a] - ss[a];
-          sign[a] = signum(ray_scaled);
-          float corrected = (float)(sign[a] > 0 ? sign[a] : 0);
-          float shifted = ss[a] - (float)curr[a];
-          float dist_b = corrected - shifted;
-          if (ray_scaled == 0.0f) {
-            t_next[a] = INFINITY;
-            t_step[a] = INFINITY;
-          } else {
-            t_next[a] = dist_b / ray_scaled;
-            t_step[a] = (float)sign[a] / ray_scaled;
-          }
-        }
-        if (!bad) {
-          // getVoxelWeight
-          float weight = 1.0f;
-          if (!c.use_const_weight) {
-            float dist_z = fabsf(pz);
-            weight = dist_z > 1e-6f ? 1.0f / (dist_z * dist_z) : 0.0f;
-          }
-          int collisions = 0;
-          const int vps = L.vps, shift = L.vps_shift, mask = vps - 1;
-          int last_b[3] = {INT32_MIN, INT32_MIN, INT32_MIN}, last_slot = -1;
-          PendingUpdate s1, s2, s3;
-          for (long long step = 0; step <= steps; ++step) {
-            int vx = curr[0], vy = curr[1], vz = curr[2];
-            int m = 0;
-            if (t_next[1] < t_next[m]) m = 1;
-            if (t_next[2] < t_next[m]) m = 2;
-            // (kept branch-free on the register arrays)
-            curr[0] += m == 0 ? sign[0] : 0; curr[1] += m == 1 ? sign[1] : 0; curr[2] += m == 2 ? sign[2] : 0;
-            t_next[0] += m == 0 ? t_step[0] : 0.0f; t_next[1] += m == 1 ? t_step[1] : 0.0f;
-            t_next[2] += m == 2 ? t_step[2] : 0.0f;
-            // ApproxHashSet::replaceHash, issued first; its result is consumed after the pending
-            // updates of the previous voxels have been issued as well
-            unsigned int h = (unsigned int)vx + (unsigned int)vy * 17191u + (unsigned int)vz * 295530481u;
-            unsigned long long v = (unsigned long long)h + I.observed_offset;
-            unsigned long long seen = atomicExch(&I.observed_set[v & kSetMask], v);
-            ++my_walk;  // dependent exchanges on this ray: the scan's critical path is the longest such chain
-            if (PIPELINED) pipeline_beat(L, c, color, s1, s2, s3);
-            if (seen == v) ++collisions; else collisions = 0;
-            if (collisions > c.max_consecutive_ray_collisions) break;
-            int bx = vx >> shift, by = vy >> shift, bz = vz >> shift;  // floor division (vps = 2^shift)
-            if (bx != last_b[0] || by != last_b[1] || bz != last_b[2]) {
-              last_slot = get_or_allocate_block(L, bx, by, bz);
-              last_b[0] = bx; last_b[1] = by; last_b[2] = bz;
-            }
-            if (last_slot < 0) {
-              ++my_dropped;
-              continue;
-            }
-            size_t at = (size_t)last_slot * ((size_t)vps * vps * vps) +
-                        (size_t)((vx & mask) + vps * ((vy & mask) + vps * (vz & mask)));
-            if (PIPELINED) {
-              s1 = make_update(L, c, at, tx, ty, tz, gx, gy, gz, vx, vy, vz, weight);
-              my_blends += s1.blend ? 1u : 0u;
-            } else
-              update_voxel(L, c, at, tx, ty, tz, gx, gy, gz, vx, vy, vz, color, weight);
-            ++my_updates;
-          }
-          if (PIPELINED) {  // drain
-            pipeline_beat(L, c, color, s1, s2, s3);
-            pipeline_beat(L, c, color, s1, s2, s3);
-            pipeline_beat(L, c, color, s1, s2, s3);
-          }
-        }
-      }
-    }
-  }
-  // one atomic per wave for the statistics
-  unsigned long long my_total = my_walk;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    my_updates += __shfl_xor(my_updates, off, 64);
-    my_dropped += __shfl_xor(my_dropped, off, 64);
-    my_blends += __shfl_xor(my_blends, off, 64);
-    my_total += __shfl_xor(my_total, off, 64);
-    const unsigned long long other = __shfl_xor(my_walk, off, 64);
-    my_walk = other > my_walk ? other : my_walk;
-  }
-  if ((threadIdx.x & 63) == 0) {
-    if (my_updates) atomicAdd(I.n_updates, my_updates);
-    if (my_dropped) atomicAdd(L.dropped, my_dropped);
-    if (my_walk) {  // vgx_tsdf_integrator_walk_stats (bench header)
-      atomicMax(I.n_updates + 1, my_walk);
-      atomicAdd(I.n_updates + 2, my_total);
-      if (my_blends) atomicAdd(I.n_updates + 3, my_blends);
-    }
-  }
-}
 
 // ---------------------------------------------------------------------------
 // voxblox::MergedTsdfIntegrator [recalled, integrator/tsdf_integrator.cc]
@@ -1291,43 +960,22 @@ static int integrate_locked(vgx_tsdf_integrator I, const float T[7], const void*
       }
       return rc;
     }
-    // VGX_TSDF_KERNEL=v1: the one-thread-per-point kernel of rounds 1-4 (A/B runs: profiles/ab_tsdf_coop.sh)
-    static const int kernel_version = [] {
-      const char* e = getenv("VGX_TSDF_KERNEL");
-      return (e && !strcmp(e, "v1")) ? 1 : 2;
-    }();
-    if (kernel_version == 2) {
-      I->dev.wg_stats = nullptr;
-      if (n_updates) {  // a counted scan: one row of statistics per workgroup
-        const long long wgs = racing_scan_workgroups((long long)n, I->cloud_width);
-        if (wgs > I->wg_stats_cap) {
-          VGX_HIP(ctx, hipStreamSynchronize(ctx->tsdf_stream));
-          if (I->d_wg_stats) (void)hipFree(I->d_wg_stats);
-          I->d_wg_stats = nullptr;
-          I->wg_stats_cap = 0;
-          VGX_HIP(ctx, hipMalloc(&I->d_wg_stats, (size_t)wgs * kWgStatWords * 8));
-          I->wg_stats_cap = wgs;
-        }
-        I->dev.wg_stats = I->d_wg_stats;
-        I->wg_stats_rows = wgs;
+    I->dev.wg_stats = nullptr;
+    if (n_updates) {  // a counted scan: one row of statistics per workgroup
+      const long long wgs = racing_scan_workgroups((long long)n, I->cloud_width);
+      if (wgs > I->wg_stats_cap) {
+        VGX_HIP(ctx, hipStreamSynchronize(ctx->tsdf_stream));
+        if (I->d_wg_stats) (void)hipFree(I->d_wg_stats);
+        I->d_wg_stats = nullptr;
+        I->wg_stats_cap = 0;
+        VGX_HIP(ctx, hipMalloc(&I->d_wg_stats, (size_t)wgs * kWgStatWords * 8));
+        I->wg_stats_cap = wgs;
       }
-      VGX_HIP(ctx, (I->racing_launch ? I->racing_launch : launch_racing_scan)(ctx->tsdf_stream, I->layer->dev, I->dev, T, (const float*)d_points, (const uint32_t*)d_rgba,
-                                      (long long)n, (int)freespace, n_updates != nullptr, I->cloud_width));
-    } else {
-      dim3 grid((unsigned)((n + 255) / 256)), block(256);
-      static const bool pipelined = [] {
-        const char* e = getenv("VGX_TSDF_PIPELINED");  // A/B switch (profiles/ab_tsdf.sh)
-        return e ? atoi(e) != 0 : true;
-      }();
-      if (pipelined)
-        hipLaunchKernelGGL(tsdf_integrate_kernel<true>, grid, block, 0, ctx->tsdf_stream, I->layer->dev, I->dev,
-                           T[0], T[1], T[2], T[3], T[4], T[5], T[6], (const float*)d_points,
-                           (const uint32_t*)d_rgba, (long long)n, (int)freespace);
-      else
-        hipLaunchKernelGGL(tsdf_integrate_kernel<false>, grid, block, 0, ctx->tsdf_stream, I->layer->dev, I->dev,
-                           T[0], T[1], T[2], T[3], T[4], T[5], T[6], (const float*)d_points,
-                           (const uint32_t*)d_rgba, (long long)n, (int)freespace);
+      I->dev.wg_stats = I->d_wg_stats;
+      I->wg_stats_rows = wgs;
     }
+    VGX_HIP(ctx, (I->racing_launch ? I->racing_launch : launch_racing_scan)(ctx->tsdf_stream, I->layer->dev, I->dev, T, (const float*)d_points, (const uint32_t*)d_rgba,
+                                    (long long)n, (int)freespace, n_updates != nullptr, I->cloud_width));
     VGX_HIP(ctx, hipGetLastError());
     request_readback(I->layer);
   }

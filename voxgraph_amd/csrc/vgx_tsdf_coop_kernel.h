@@ -1,7 +1,6 @@
 // TSDF path, racing mode (the default): voxblox::FastTsdfIntegrator::integratePointCloud as its worker threads run
 // it -- every ray its own thread, rays racing on the two approximate sets and on the voxels -- laid out for a
-// wavefront machine (round 5; the one-thread-per-point kernel it replaces is tsdf_integrate_kernel in vgx_tsdf.hip,
-// still reachable with VGX_TSDF_KERNEL=v1 for A/B runs).
+// wavefront machine (round 5; it replaces the one-thread-per-point kernel of rounds 1-4, tsdf_integrate_kernel).
 //
 // What the one-thread-per-point kernel paid for (profiles/r04_sq_breakdown.json: waves wait on memory 81-91 % of
 // their cycles; 52 us for a LiDAR scan whose longest chain of exchanges is 4 us):
@@ -133,7 +132,7 @@ __global__ __launch_bounds__(256) void tsdf_integrate_coop_kernel(TsdfLayerDev L
                                                                  float qz, float tx, float ty, float tz,
                                                                  const float* __restrict__ points_C,
                                                                  const uint32_t* __restrict__ rgba, long long n,
-                                                                 int freespace_points, int cloud_width, int ablate) {
+                                                                 int freespace_points, int cloud_width) {
   __shared__ RayRec rays[256];
   __shared__ UpdateRec recs[kMaxRecs];
   __shared__ unsigned long long tkey[kTable];
@@ -301,7 +300,7 @@ __global__ __launch_bounds__(256) void tsdf_integrate_coop_kernel(TsdfLayerDev L
   // wavefront per SIMD nothing hides any of it: a barrier per round made every wavefront pay for the slowest).  The
   // workgroup meets only to fold: when every wavefront has run out of rays, or when the record pool may not take
   // another round of all four (each checks the count BEFORE a round and adds at most 64 records: 512 + 4 x 64 fit).
-  bool all_done = n_rays == 0 || ablate >= 2;  // (ablate: attribution runs only, profiles/probes/run_racing_probe.sh)
+  bool all_done = n_rays == 0;
   uint32_t wg_rounds = 0, wg_folds = 0, my_retry_max = 0;
   while (!all_done) {
     while (true) {
@@ -519,17 +518,12 @@ __global__ __launch_bounds__(256) void tsdf_integrate_coop_kernel(TsdfLayerDev L
       // ------------------------------------------------------------ phase 3: one lane per distinct voxel
       const uint32_t n_occ = sh_n_occ;
       wg_folds += n_occ;
-      if (ablate >= 1)
-        for (uint32_t o = (uint32_t)tid; o < n_occ; o += 256) {
-          tkey[occ[o]] = kEmptyKey;
-          thead[occ[o]] = kNil;
-        }
       // New blocks first, in list order (one lane; a plain look at the table tells which voxels need one -- a handful per
       // scan once the layer exists): the order a sequential walk allocates them in when the scan is a single ray, and
       // SOME serial order otherwise, as under voxblox's block mutex.
       {
         bool need = false;
-        for (uint32_t o = (uint32_t)tid; o < n_occ && ablate < 1; o += 256) {
+        for (uint32_t o = (uint32_t)tid; o < n_occ; o += 256) {
           const unsigned long long key = tkey[occ[o] & 0x3ffu];
           const int bx = ((int)((key >> 42) & 0x1fffffull) - kBias) >> shift, by = ((int)((key >> 21) & 0x1fffffull) - kBias) >> shift,
                     bz = ((int)(key & 0x1fffffull) - kBias) >> shift;
@@ -593,7 +587,7 @@ __global__ __launch_bounds__(256) void tsdf_integrate_coop_kernel(TsdfLayerDev L
 #pragma unroll
       for (int e = 0; e < kFoldsPerLane; ++e) {
         const uint32_t o = (uint32_t)tid + 256u * (uint32_t)e;
-        f_on[e] = o < n_occ && ablate < 1;
+        f_on[e] = o < n_occ;
         f_head[e] = kNil;
         f_at[e] = 0;
         f_retries[e] = 0;
@@ -814,14 +808,13 @@ inline hipError_t launch_racing_scan_t(hipStream_t stream, const TsdfLayerDev& L
   const long long wgs = racing_scan_workgroups(n, tiled ? cloud_width : 0);
   const dim3 grid((unsigned)wgs), block(256);
   const int cw = tiled ? cloud_width : 0;
-  static const int ablate = getenv("VGX_TSDF_ABLATE") ? atoi(getenv("VGX_TSDF_ABLATE")) : 0;
   if (stats) {
     hipLaunchKernelGGL((tsdf_integrate_coop_kernel<true, TRACE>), grid, block, 0, stream, L, I, T[0], T[1], T[2], T[3], T[4], T[5],
-                       T[6], d_points, d_rgba, n, freespace, cw, ablate);
+                       T[6], d_points, d_rgba, n, freespace, cw);
     hipLaunchKernelGGL(reduce_wg_stats_kernel, dim3(1), block, 0, stream, I.wg_stats, (long long)grid.x, I.n_updates);
   } else
     hipLaunchKernelGGL((tsdf_integrate_coop_kernel<false, TRACE>), grid, block, 0, stream, L, I, T[0], T[1], T[2], T[3], T[4], T[5],
-                       T[6], d_points, d_rgba, n, freespace, cw, ablate);
+                       T[6], d_points, d_rgba, n, freespace, cw);
   return hipGetLastError();
 }
 

@@ -346,12 +346,6 @@ __global__ __launch_bounds__(256) void det_gather_kernel(size_t N, const uint32_
 }
 
 // scan inputs
-struct HappenedOp {  // position + 1 of an access whose exchange happens, else 0
-  const uint32_t* s_r;
-  const uint32_t* s_k;
-  const int32_t* T;
-  __host__ __device__ uint32_t operator()(uint32_t p) const { return (int32_t)s_k[p] <= T[s_r[p]] ? p + 1u : 0u; }
-};
 struct UpdateOp {  // 1 for an access that updates its voxel
   const uint32_t* s_r;
   const uint32_t* s_k;
@@ -371,22 +365,6 @@ struct UpdateOp {  // 1 for an access that updates its voxel
 };
 
 // ---- 2c. one sweep: what every access finds in its slot ... ---------------------------------------
-// (the two-kernel form over a rocprim scan: kept for the 1 / 4 of the comparison in profiles/ -- VGX_DET_SWEEP=scan)
-__global__ __launch_bounds__(256) void det_seen_kernel(size_t N, const uint32_t* __restrict__ s_key,
-                                                      const uint32_t* __restrict__ s_idx,
-                                                      const uint32_t* __restrict__ s_h,
-                                                      const uint32_t* __restrict__ last,
-                                                      const unsigned long long* __restrict__ observed_set,
-                                                      unsigned long long observed_offset, uint8_t* __restrict__ seen) {
-  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= N) return;
-  const uint32_t key = s_key[p], h = s_h[p], prev = last[p];
-  bool present;
-  if (prev > 0 && s_key[prev - 1] == key) present = s_h[prev - 1] == h;           // an earlier access of this scan
-  else present = observed_set[key] == (unsigned long long)h + observed_offset;    // what earlier scans left
-  seen[s_idx[p]] = present ? 1 : 0;
-}
-
 // The sweep in ONE launch: the exclusive max-scan of "position + 1 if the access happened" and what it is used
 // for, without the scan's output ever reaching memory.  Tiles of 2048 consecutive sorted accesses, taken in
 // the order the workgroups start (a ticket), chained by one 8-byte state per tile:
@@ -398,10 +376,7 @@ __global__ __launch_bounds__(256) void det_seen_kernel(size_t N, const uint32_t*
 // never wait for it).  The words are the whole exchange between workgroups (relaxed agent-scope 8-byte loads
 // and stores, tag and value in one word); the epoch is the sweep's number, so no word is ever cleared.
 // Also written, for det_finish_kernel: `last` at the end of every slot run.
-#ifndef VGX_SWEEP_IPT
-#define VGX_SWEEP_IPT 8  // (A/B builds: make SUFFIX=_ipt16 EXTRA=-DVGX_SWEEP_IPT=16)
-#endif
-constexpr int kSweepIpt = VGX_SWEEP_IPT;
+constexpr int kSweepIpt = 8;
 static_assert(kSweepIpt % 4 == 0, "whole 16-byte loads");
 constexpr uint32_t kSweepTile = 256u * kSweepIpt;
 constexpr unsigned long long kSweepEpochMax = (1ull << 30) - 1;
@@ -623,7 +598,7 @@ __global__ __launch_bounds__(256) void det_finish_kernel(uint32_t N, const uint3
     for (int e = 0; e < kSweepIpt; ++e) {
       const bool in = base + e < N;
       const int32_t step = (int32_t)k[e];
-      // the exchange happened and did not stop the ray (UpdateOp); it happened at all (HappenedOp)
+      // the exchange happened and did not stop the ray (UpdateOp); it happened at all
       u[e] = (in && (step < stop[e] || (step == stop[e] && !broke[e]))) ? 1u : 0u;
       hp[e] = (in && step <= stop[e]) ? base + e + 1u : 0u;
     }
@@ -732,7 +707,7 @@ __global__ void det_assign_kernel(TsdfLayerDev L, uint32_t n_new, int32_t base, 
 }
 
 // ---- 3c. updateTsdfVoxel in a fixed order -----------------------------------------------------------
-// computeDistance + updateTsdfVoxel's weight [recalled]; the same operations as update_voxel (vgx_tsdf.hip)
+// computeDistance + updateTsdfVoxel's weight [recalled]; the same operations as the racing kernel's (vgx_tsdf_coop_kernel.h)
 struct UpdateTerm {
   float sdf, w;
 };
@@ -1144,32 +1119,6 @@ inline unsigned blocks_for(size_t n) { return (unsigned)((n + 255) / 256); }
     if (rc_ != VGX_OK) return rc_; \
   } while (0)
 
-// experiment aid (VGX_DET_PHASES=1): host-side time between the points of a scan where the host has waited for
-// the stream, so what is queued in between is charged to the wait after it
-struct PhaseClock {
-  bool on;
-  std::chrono::steady_clock::time_point t;
-  double us[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  long long sweeps = 0, attempts = 0;
-  PhaseClock() {
-    static const bool enabled = getenv("VGX_DET_PHASES") != nullptr;
-    on = enabled;
-    if (on) t = std::chrono::steady_clock::now();
-  }
-  void mark(int phase) {
-    if (!on) return;
-    const auto now = std::chrono::steady_clock::now();
-    us[phase] += std::chrono::duration<double, std::micro>(now - t).count();
-    t = now;
-  }
-  void print(size_t N) const {
-    if (!on) return;
-    fprintf(stderr, "[vgx det phases] to count read-back %.0f us | walk+sort+gather+first sweep %.0f | other sweeps %.0f | "
-                    "extend %.0f | commit to its read-back %.0f | rest queued %.0f   (%lld attempts, %lld sweeps, %zu accesses)\n",
-            us[0], us[1], us[2], us[3], us[4], us[5], attempts, sweeps, N);
-  }
-};
-
 // a 4-byte device value into one of the pinned words behind the counters' mirror (valid after read_counters)
 int fetch_u32(vgx_ctx ctx, DetScratch* S, int word, const void* dev) {
   S->h_ctr[word] = 0ull;
@@ -1262,10 +1211,9 @@ __global__ __launch_bounds__(64) void det_report_kernel(const unsigned long long
 // The scan's counters on the host, and everything queued before this call finished.  Through the pinned report words:
 // one tiny kernel behind the producers and a poll (a few microseconds after the producer ends) instead of a copy through
 // the blit path and a stream synchronisation (20-45 us of bubble per read-back in profiles/r05_tsdf_launches.txt, two per
-// scan).  VGX_DET_REPORT=0: the copy + synchronise of rounds 3-4 (A/B aid; also the fallback without pinned memory).
+// scan).  Without pinned memory: the copy + synchronise of rounds 3-4.
 int read_counters(vgx_ctx ctx, DetScratch* S) {
-  static const bool by_report = !(getenv("VGX_DET_REPORT") && atoi(getenv("VGX_DET_REPORT")) == 0);
-  if (!by_report || !S->h_report) {
+  if (!S->h_report) {
     VGX_HIP(ctx, hipMemcpyAsync(S->h_ctr, S->d_ctr, kCtrCount * 8, hipMemcpyDeviceToHost, ctx->tsdf_stream));
     VGX_HIP(ctx, hipStreamSynchronize(ctx->tsdf_stream));
     return VGX_OK;
@@ -1369,7 +1317,7 @@ static int det_error_code(vgx_ctx ctx, unsigned long long code) {
 
 static int det_commit(vgx_tsdf_integrator I, DetScratch* S, const float T[7], size_t N,
                       const UpdateOp* update, bool update_set, bool ordered_blocks, const float4* ray_pg,
-                      const uint32_t* ray_color, int64_t* n_updates, PhaseClock* pc = nullptr) {
+                      const uint32_t* ray_color, int64_t* n_updates) {
   vgx_ctx ctx = I->ctx;
   vgx_tsdf_layer layer = I->layer;
   const vgx_tsdf_config& c = I->dev.cfg;
@@ -1436,7 +1384,6 @@ static int det_commit(vgx_tsdf_integrator I, DetScratch* S, const float T[7], si
     // would be wrong -- nothing is applied to the layer
     if (S->h_ctr[kCtrError]) return det_error_code(ctx, S->h_ctr[kCtrError]);
   }
-  if (pc) pc->mark(4);
   if (ordered_blocks) {
     M = (size_t)S->h_ctr[kCtrM];
     n_blocks_now = (int32_t)(uint32_t)S->h_ctr[kCtrBlocks];
@@ -1495,19 +1442,9 @@ static int det_commit(vgx_tsdf_integrator I, DetScratch* S, const float T[7], si
                      S->t_sdf.as<float>(), S->t_w.as<float>(), S->t_color.as<uint32_t>(), S->t_far.as<uint8_t>(),
                      S->long_runs.as<uint32_t>(), S->d_ctr);
   VGX_HIP(ctx, hipGetLastError());
-  static const bool debug = getenv("VGX_DET_DEBUG") != nullptr;  // experiment aid: sizes of the ordered application
-  if (debug) {
-    DET_TRY(read_counters(ctx, S));
-    fprintf(stderr, "[vgx det] updates %zu, long runs %llu (of more than %d), accesses sorted %zu\n", M,
-            (unsigned long long)S->h_ctr[kCtrLong], kShortRun, N);
-  }
   if (n_updates) {
     DET_TRY(read_counters(ctx, S));
     *n_updates = (int64_t)M - (int64_t)S->h_ctr[kCtrDropped];
-  }
-  if (pc) {
-    pc->mark(5);
-    pc->print(N);
   }
   return VGX_OK;
 }
@@ -1522,7 +1459,6 @@ int det_integrate(vgx_tsdf_integrator I, const float T[7], const void* d_points,
   if (n >= (1ll << 31)) return set_error(ctx, VGX_ERR_UNSUPPORTED, "TSDF reproducible mode: more than 2^31 points in a scan");
   DET_TRY(ensure_scratch(I));
   DetScratch* S = I->det;
-  PhaseClock pc;
   const float vsi = layer->dev.voxel_size_inv;
   const size_t np = (size_t)n;
   // ---- 1. points, start set ----
@@ -1570,17 +1506,12 @@ int det_integrate(vgx_tsdf_integrator I, const float T[7], const void* d_points,
   // the rays that ran on kept from scan to scan (det_extend_kernel).
   bool capped = start_capped;  // this attempt cut rays short: whether one of them ran on has to be looked at afterwards
   bool may_cap = may_cap_at_all && !start_capped;
-  // (experiment aids: VGX_DET_CAP / VGX_DET_CAP_THRESHOLD override the integrator's speculation depth / threshold)
-  static const long long cap_env = getenv("VGX_DET_CAP") ? atoll(getenv("VGX_DET_CAP")) : 0;
-  static const long long thr_env = getenv("VGX_DET_CAP_THRESHOLD") ? atoll(getenv("VGX_DET_CAP_THRESHOLD")) : -1;
-  const uint32_t kCapThreshold = thr_env >= 0 ? (uint32_t)std::min<long long>(thr_env, 0xffffffffll) : I->det_cap_threshold;
-  const uint32_t cap = std::max<uint32_t>(cap_env > 0 ? (uint32_t)cap_env : I->det_cap, 1u);
-  static const int mark_life = getenv("VGX_DET_MARK_LIFE") ? std::max(1, std::min(200, atoi(getenv("VGX_DET_MARK_LIFE")))) : 2;  // (depth image, ms per scan: 1 -> 1.25, 2 -> 1.17, 4 -> 1.18, 8 -> 1.21)
-  static const bool scan_sweeps = getenv("VGX_DET_SWEEP") && !strcmp(getenv("VGX_DET_SWEEP"), "scan");  // A/B aid
+  const uint32_t kCapThreshold = I->det_cap_threshold;
+  const uint32_t cap = std::max<uint32_t>(I->det_cap, 1u);
+  constexpr int kMarkLife = 2;  // scans a ray's "ran on" mark lasts (depth image, ms per scan: 1 -> 1.25, 2 -> 1.17, 4 -> 1.18, 8 -> 1.21)
   size_t N = 0;
   int walks_done = 0;
   bool range_error = false;
-  HappenedOp happened{nullptr, nullptr, nullptr};
   UpdateOp update{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u};
   for (int attempt = 0;; ++attempt) {
     if (attempt > 64) return set_error(ctx, VGX_ERR_HIP, "TSDF reproducible mode: speculation did not settle (internal error)");
@@ -1595,8 +1526,6 @@ int det_integrate(vgx_tsdf_integrator I, const float T[7], const void* d_points,
       VGX_HIP(ctx, hipGetLastError());
     }
     DET_TRY(read_counters(ctx, S));
-    pc.mark(0);
-    ++pc.attempts;
     if (S->h_ctr[kCtrError]) return det_error_code(ctx, S->h_ctr[kCtrError]);
     const unsigned long long total = S->h_ctr[kCtrTotal];
     if (may_cap) {
@@ -1641,16 +1570,8 @@ int det_integrate(vgx_tsdf_integrator I, const float T[7], const void* d_points,
                        S->s_r.as<uint32_t>(), S->s_k.as<uint32_t>(), S->s_h.as<uint32_t>());
     VGX_HIP(ctx, hipGetLastError());
     // ---- sweeps to the fixed point ----
-    happened = HappenedOp{S->s_r.as<uint32_t>(), S->s_k.as<uint32_t>(), S->T.as<int32_t>()};
     update = UpdateOp{S->s_r.as<uint32_t>(), S->s_k.as<uint32_t>(), S->T.as<int32_t>(), S->broke.as<uint8_t>(),
                       nullptr, nullptr, (uint32_t)N};
-    auto pos = rocprim::make_counting_iterator<uint32_t>(0u);
-    if (scan_sweeps) {  // (A/B aid: the sweep over a rocprim scan)
-      size_t scan_bytes = 0;
-      VGX_HIP(ctx, rocprim::exclusive_scan(nullptr, scan_bytes, rocprim::make_transform_iterator(pos, happened),
-                                           S->last.as<uint32_t>(), 0u, N, rocprim::maximum<uint32_t>(), st));
-      DET_TRY(grow(ctx, S->tmp, scan_bytes));
-    }
     const uint32_t tiles = (uint32_t)((N + kSweepTile - 1) / kSweepTile);
     DET_TRY(grow_zeroed(ctx, S->tile_state, (size_t)tiles * 8));
     {
@@ -1661,39 +1582,24 @@ int det_integrate(vgx_tsdf_integrator I, const float T[7], const void* d_points,
       // copy + stream synchronise every look, 20-40 us each, and four launches a sweep).  Sweeps past the fixed
       // point change nothing, so what was queued in vain costs their run time only: on small scans (a sweep over
       // < 1 M accesses is ~10 us, less than the bubble of waiting) two are kept queued, on large ones none.
-      static const int ahead_env = getenv("VGX_DET_AHEAD") ? atoi(getenv("VGX_DET_AHEAD")) : -1;  // experiment aid
-      const int ahead = ahead_env >= 0 ? ahead_env : N <= (1u << 20) ? 2 : 0;
+      const int ahead = N <= (1u << 20) ? 2 : 0;
       const unsigned long long seq0 = S->flag_seq;  // sweep j of this attempt reports as seq0 + j + 1
       long long issued = 0, heard = -1;              // sweeps launched; the latest sweep the host has heard from
       bool settled = false;
-      struct Tally {  // (experiment aid)
-        PhaseClock& pc;
-        long long& issued;
-        ~Tally() { pc.sweeps += issued; }
-      } tally{pc, issued};
       while (!settled) {
         if (issued > n + 2 + ahead + (walks_done > 1 ? (long long)N : 0))  // (a warm start: at least a step a sweep)
           return set_error(ctx, VGX_ERR_HIP, "TSDF reproducible mode: the sweeps did not settle (internal error)");
         while (issued <= heard + 1 + ahead) {
-          if (scan_sweeps) {
-            size_t bytes = S->tmp.bytes;
-            VGX_HIP(ctx, rocprim::exclusive_scan(S->tmp.p, bytes, rocprim::make_transform_iterator(pos, happened),
-                                                 S->last.as<uint32_t>(), 0u, N, rocprim::maximum<uint32_t>(), st));
-            hipLaunchKernelGGL(det_seen_kernel, dim3(blocks_for(N)), dim3(256), 0, st, N, S->s_key.as<uint32_t>(),
-                               S->s_idx.as<uint32_t>(), S->s_h.as<uint32_t>(), S->last.as<uint32_t>(), I->dev.observed_set,
-                               I->dev.observed_offset, S->seen.as<uint8_t>());
-          } else {
-            if (S->sweep_epoch >= kSweepEpochMax) {  // (after 2^30 sweeps: start the tags over)
-              VGX_HIP(ctx, hipMemsetAsync(S->tile_state.p, 0, S->tile_state.bytes, st));
-              S->sweep_epoch = 0;
-            }
-            ++S->sweep_epoch;
-            hipLaunchKernelGGL(det_sweep_kernel, dim3(tiles), dim3(256), 0, st, (uint32_t)N, (unsigned long long)S->sweep_epoch,
-                               S->d_ctr, S->tile_state.as<unsigned long long>(), S->s_key.as<uint32_t>(),
-                               S->s_idx.as<uint32_t>(), S->s_h.as<uint32_t>(), S->s_r.as<uint32_t>(), S->s_k.as<uint32_t>(),
-                               S->T.as<int32_t>(), I->dev.observed_set, I->dev.observed_offset, S->seen.as<uint8_t>(),
-                               S->last.as<uint32_t>());
+          if (S->sweep_epoch >= kSweepEpochMax) {  // (after 2^30 sweeps: start the tags over)
+            VGX_HIP(ctx, hipMemsetAsync(S->tile_state.p, 0, S->tile_state.bytes, st));
+            S->sweep_epoch = 0;
           }
+          ++S->sweep_epoch;
+          hipLaunchKernelGGL(det_sweep_kernel, dim3(tiles), dim3(256), 0, st, (uint32_t)N, (unsigned long long)S->sweep_epoch,
+                             S->d_ctr, S->tile_state.as<unsigned long long>(), S->s_key.as<uint32_t>(),
+                             S->s_idx.as<uint32_t>(), S->s_h.as<uint32_t>(), S->s_r.as<uint32_t>(), S->s_k.as<uint32_t>(),
+                             S->T.as<int32_t>(), I->dev.observed_set, I->dev.observed_offset, S->seen.as<uint8_t>(),
+                             S->last.as<uint32_t>());
           VGX_HIP(ctx, hipGetLastError());
           ++S->flag_seq;
           hipLaunchKernelGGL(det_ray_kernel, dim3(blocks_for(np)), dim3(256), 0, st, (long long)n,
@@ -1705,7 +1611,6 @@ int det_integrate(vgx_tsdf_integrator I, const float T[7], const void* d_points,
         }
         unsigned long long word = 0;
         DET_TRY(wait_for_sweep(ctx, S, seq0 + (unsigned long long)heard + 2ull, &word));  // ... at least the next one
-        pc.mark(heard < 0 ? 1 : 2);
         heard = (long long)((word >> 2) - seq0) - 1;
         if (word & 2ull) range_error = true;
         if (range_error || !(word & 1ull)) settled = true;
@@ -1714,10 +1619,9 @@ int det_integrate(vgx_tsdf_integrator I, const float T[7], const void* d_points,
     if (range_error) break;
     if (!capped) break;  // every ray was written out completely: nothing can have been cut short
     hipLaunchKernelGGL(det_extend_kernel, dim3(blocks_for(np)), dim3(256), 0, st, (long long)n, S->count.as<uint32_t>(),
-                       S->full_count.as<uint32_t>(), S->broke.as<uint8_t>(), S->T.as<int32_t>(), S->ext.as<uint8_t>(), cap, mark_life, S->d_ctr);
+                       S->full_count.as<uint32_t>(), S->broke.as<uint8_t>(), S->T.as<int32_t>(), S->ext.as<uint8_t>(), cap, kMarkLife, S->d_ctr);
     VGX_HIP(ctx, hipGetLastError());
     DET_TRY(read_counters(ctx, S));
-    pc.mark(3);
     if (S->h_ctr[kCtrError]) {
       range_error = true;
       break;
@@ -1731,8 +1635,7 @@ int det_integrate(vgx_tsdf_integrator I, const float T[7], const void* d_points,
     DET_TRY(read_counters(ctx, S));  // (also: what the sweeps queued ahead were still writing is off the stream)
     return det_error_code(ctx, S->h_ctr[kCtrError] ? S->h_ctr[kCtrError] : 2ull);
   }
-  return det_commit(I, S, T, N, &update, true, true, S->ray_pg.as<float4>(), S->ray_color.as<uint32_t>(), n_updates,
-                    &pc);
+  return det_commit(I, S, T, N, &update, true, true, S->ray_pg.as<float4>(), S->ray_color.as<uint32_t>(), n_updates);
 }
 
 int det_merged_commit(vgx_tsdf_integrator I, const float T[7], long long n, const float4* g_pg, const uint32_t* g_color,
@@ -1767,11 +1670,9 @@ int det_merged_commit(vgx_tsdf_integrator I, const float T[7], long long n, cons
   {
     // lanes per group for the next scan's merge kernel: about as many as a group has points
     const unsigned long long groups = S->h_ctr[kCtrGroups], points = S->h_ctr[kCtrGroupPoints];
-    static const int forced = getenv("VGX_MERGED_LANES") ? atoi(getenv("VGX_MERGED_LANES")) : 0;  // experiment aid
-    if (forced == 4 || forced == 8 || forced == 16) I->merged_lanes = forced;
     // (measured, ms per scan with 4 / 8 / 16 lanes: depth image, ~8 points a group, 0.794 / 0.812 / 0.852; LiDAR, one or
     // two, 0.210 / 0.208 / 0.207 -- wide groups only pay where a group's points outnumber them several times)
-    else if (groups > 0) I->merged_lanes = points <= 16 * groups ? 4 : points <= 48 * groups ? 8 : 16;
+    if (groups > 0) I->merged_lanes = points <= 16 * groups ? 4 : points <= 48 * groups ? 8 : 16;
   }
   const size_t N = total;
   if (N == 0) return VGX_OK;

@@ -340,22 +340,16 @@ void det_scratch_free(DetScratch* s);
 // two launches (partition + merge path).  At these sizes a pass is a launch's latency, not bandwidth
 // (profiles/r04_tsdf_launches.txt: 17 launches of 4-7 us for 237 568 records), so: 4096 items per sorted block
 // (two passes fewer) and the one-launch odd-even merge all the way to 2^20 items (7 launches for the same
-// records).  Above 2^20 items: rocprim's onesweep, as before.  VGX_TSDF_SORT=default switches back (A/B aid).
+// records).  Above 2^20 items: rocprim's onesweep, as before.
 // (An own LSD radix sort -- one counting launch + one launch per 8 key bits, tiles chained by epoch-tagged words or
 // by a count matrix -- was written, is correct, and is NOT faster: fewer launches, but three dependent memory
 // round trips in each against the merge passes' two.  profiles/dropped/vgx_slot_sort.hip, profiles/README.md.)
 using FewPassSort = rocprim::radix_sort_config<rocprim::default_config, rocprim::merge_sort_config<256, 512, 8, 128, 128, 4, (1u << 20)>,
                                                rocprim::default_config, (1u << 20)>;
-inline bool few_pass_sort() {
-  static const bool on = !(getenv("VGX_TSDF_SORT") && !strcmp(getenv("VGX_TSDF_SORT"), "default"));
-  return on;
-}
 template <class KeyIn, class KeyOut, class ValIn, class ValOut>
 inline hipError_t stable_sort_pairs(void* tmp, size_t& bytes, KeyIn keys_in, KeyOut keys_out, ValIn vals_in, ValOut vals_out,
                                     size_t n, unsigned end_bit, hipStream_t st) {
-  if (few_pass_sort())
-    return rocprim::radix_sort_pairs<FewPassSort>(tmp, bytes, keys_in, keys_out, vals_in, vals_out, n, 0, end_bit, st);
-  return rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, n, 0, end_bit, st);
+  return rocprim::radix_sort_pairs<FewPassSort>(tmp, bytes, keys_in, keys_out, vals_in, vals_out, n, 0, end_bit, st);
 }
 // 64-bit keys (the merged integrator's {clearing, end voxel} keys): the radix block sort of the configuration above
 // walks all 64 bits (30 us for 65 536 records); a comparison sort does not care how wide the key is.  rocprim's
@@ -365,7 +359,7 @@ using WideKeySortSmall = rocprim::merge_sort_config<256, 256, 4, 128, 128, 4, (1
 using WideKeySortLarge = rocprim::merge_sort_config<256, 256, 8, 128, 128, 4, (1u << 20)>;
 inline hipError_t stable_sort_pairs_u64(void* tmp, size_t& bytes, const unsigned long long* keys_in, unsigned long long* keys_out,
                                         const unsigned int* vals_in, unsigned int* vals_out, size_t n, hipStream_t st) {
-  if (!few_pass_sort() || n > (1u << 20))
+  if (n > (1u << 20))
     return rocprim::radix_sort_pairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, n, 0, 64, st);
   if (n > (1u << 17))
     return rocprim::merge_sort<WideKeySortLarge>(tmp, bytes, keys_in, keys_out, vals_in, vals_out, n, rocprim::less<unsigned long long>(), st);
@@ -445,7 +439,7 @@ struct vgx_tsdf_integrator_s {
   // vgx_tsdf_integrator_set_speculation (bench header) lets the tests drive the extension logic on small scans.
   uint32_t det_cap = 32;
   uint32_t det_cap_threshold = 8u << 20;  // (a city LiDAR scan's 5 M steps: 1.54 ms swept as they are, 2.0-2.1 ms cut to 32 and extended twice;
-                                          //  a depth image's 18 M: cut.  profiles/probes/pipeline_det.sh)
+                                          //  a depth image's 18 M: cut.  profiles/README.md)
   // merged integrator: lanes per group in merged_merge_kernel (4 / 8 / 16), chosen from the previous scan's points per
   // group -- a LiDAR scan's groups hold one or two points, a depth image's five to ten.  Results do not depend on it.
   int merged_lanes = 4;
