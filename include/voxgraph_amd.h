@@ -704,6 +704,38 @@ VGX_API int vgx_tsdf_integrate_merged_device(vgx_tsdf_integrator integrator, con
 VGX_API int vgx_submap_from_tsdf_layer(vgx_ctx ctx, vgx_tsdf_layer layer, int32_t submap_id,
                                        vgx_submap* out);
 
+/* The projected map: voxblox::mergeLayerAintoLayerB(submap TSDF layer, T_L_S, layer) applied to n submaps in ARRAY
+ * order.  cblox::SubmapCollection::getProjectedMap() is this call on an empty layer (vgx_tsdf_layer_upload(layer, 0,
+ * ...)) with the collection's submaps in ascending ID order and T_L_S = submap.getPose(); merging into a layer that
+ * already holds data (an integrated one) behaves as repeated mergeLayerAintoLayerB calls would.  T_L_S [n][7] f32
+ * {qw,qx,qy,qz, tx,ty,tz}.  *n_blocks_out (nullable): blocks in the layer afterwards.
+ * Preconditions, each refused with VGX_ERR_INVALID (vgx_last_error says which) before the layer is touched: a submap
+ * whose voxel_size or voxels_per_side differs from the layer's (voxblox would resample: not supported), whose raw TSDF
+ * layer has been released (vgx_submap_release_raw_layers: keep the raw layers of submaps that will be projected), a
+ * pose value that is not finite, |q.q - 1| > 1e-4, n < 0, NULL arrays with n > 0.  n = 0: VGX_OK, nothing changes.
+ * Semantics (what the kernel and tests/projected_map_ref.py both follow):
+ *   transform      T_S_L = T_L_S.inverse() once per submap in f32 (conjugate quaternion, translation -(q^-1 t)); the
+ *                  sample point of layer voxel c is T_S_L * c (Eigen _transformVector, then + t), c the voxel centre
+ *                  origin + (idx + 0.5) * voxel_size.
+ *   interpolation  Interpolator<TsdfVoxel>::getVoxel(p, &v, true) [recalled], as the isosurface points use it: all 8
+ *                  neighbours allocated with weight > 0, distance and weight interpolated trilinearly.
+ *   coverage       submap s contributes to layer block b iff at least one voxel centre of b interpolates in s.  Then b
+ *                  is allocated if absent (new voxels d = 0, w = 0, rgba = 0) and EVERY voxel of b is merged, one that
+ *                  did not interpolate as the default voxel (0, 0) -- which is not a no-op: (0*0 + d*w) / w need not be
+ *                  d.  [recalled] voxblox allocates the intermediate layer's blocks from the transformed extent of each
+ *                  input block and drops blocks that received no data; this rule is what that yields wherever that
+ *                  allocation covers every block with an interpolable centre.
+ *   merge          mergeVoxelAIntoVoxelB [recalled] (A: the submap's voxel, B: the layer's): w' = wA + wB; if w' > 0,
+ *                  d = (dA*wA + dB*wB) / w' and w = w' (f32, that association, no contraction); else unchanged.  No
+ *                  weight cap.
+ *   colour         rgba is left untouched (device submaps carry no colour): a stated deviation, voxblox blends it.
+ * Runs on the context's TSDF stream behind the registration stream (where submap layers are produced); takes the TSDF
+ * lock, then the registration lock; returns once the sources have been read, so the caller may destroy a submap or
+ * release its raw layers right after.  Room for every candidate block is reserved first: VGX_ERR_NOMEM then, before
+ * any voxel is touched.  Values do not depend on scheduling; the slots of newly allocated blocks (their order in
+ * vgx_tsdf_layer_download) may, as after a scan. */
+VGX_API int vgx_tsdf_layer_merge_submaps(vgx_tsdf_layer layer, int32_t n, const vgx_submap* submaps, const float* T_L_S, int64_t* n_blocks_out);
+
 /* ---------------------------------------------------------------------------
  * Saved maps: cblox submap-collection files and voxblox layer files.
  *

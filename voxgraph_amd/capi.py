@@ -170,6 +170,7 @@ SIGNATURES = {
     "vgx_tsdf_layer_growths": (C.c_int64, [vp]),
     "vgx_tsdf_layer_download": (C.c_int, [vp, i32p, f32p, f32p, u8p]),
     "vgx_tsdf_layer_upload": (C.c_int, [vp, C.c_int32, i32p, f32p, f32p, u8p]),
+    "vgx_tsdf_layer_merge_submaps": (C.c_int, [vp, C.c_int32, C.POINTER(vp), f32p, i64p]),
     "vgx_tsdf_integrator_create": (C.c_int, [vp, C.POINTER(TsdfConfig), vp, C.POINTER(vp)]),
     "vgx_tsdf_integrator_destroy": (C.c_int, [vp]),
     "vgx_tsdf_integrator_set_layer": (C.c_int, [vp, vp]),
@@ -920,6 +921,16 @@ class TsdfLayer:
         self.ctx.check(self.ctx.lib.vgx_tsdf_layer_stats(self.h, C.byref(n), C.byref(d)))
         return n.value, d.value
 
+    def merge_submaps(self, submaps, T_L_S):
+        """voxblox::mergeLayerAintoLayerB(submap TSDF layer, T_L_S[i], this layer) for each submap in array order
+        (T_L_S [n][7] qw,qx,qy,qz,tx,ty,tz); returns the layer's block count afterwards."""
+        n = len(submaps)
+        arr = (vp * max(n, 1))(*[s.h for s in submaps])
+        T = np.ascontiguousarray(T_L_S, np.float32).reshape(n, 7)
+        nb = C.c_int64()
+        self.ctx.check(self.ctx.lib.vgx_tsdf_layer_merge_submaps(self.h, n, arr, _ptr(T, f32p), C.byref(nb)))
+        return nb.value
+
     def download(self):
         n, _ = self.stats()
         nv = self.vps ** 3
@@ -935,6 +946,18 @@ class TsdfLayer:
         if self.h:
             self.ctx.lib.vgx_tsdf_layer_destroy(self.h)
             self.h = None
+
+
+def projected_map(ctx, submaps, poses, layer):
+    """cblox::SubmapCollection::getProjectedMap() into `layer` (emptied first): the submaps merged in ascending
+    vgx_submap_id order (the collection's std::map order) at poses[i] = submaps[i].getPose() ([n][7] qw,qx,qy,qz,
+    tx,ty,tz).  Returns the layer."""
+    ids = [int(ctx.lib.vgx_submap_id(s.h)) for s in submaps]
+    order = sorted(range(len(submaps)), key=lambda i: ids[i])
+    poses = np.ascontiguousarray(poses, np.float32).reshape(len(submaps), 7)
+    layer.upload(np.zeros((0, 3), np.int32), np.zeros(0, np.float32), np.zeros(0, np.float32))
+    layer.merge_submaps([submaps[i] for i in order], poses[order])
+    return layer
 
 
 class FastTsdfIntegrator:

@@ -631,6 +631,7 @@ int vgx_submap_destroy(vgx_submap sm) {
   if (sm->d_lut) (void)hipFree(sm->d_lut);
   if (sm->d_block_index) (void)hipFree(sm->d_block_index);
   if (sm->d_iso_block_index) (void)hipFree(sm->d_iso_block_index);
+  if (sm->d_block_has_data) (void)hipFree(sm->d_block_has_data);
   for (int k = 0; k < 2; ++k) {
     if (sm->grid[k].d_bricks) (void)hipFree(sm->grid[k].d_bricks);
     if (sm->grid[k].d_quad) (void)hipFree(sm->grid[k].d_quad);

@@ -279,6 +279,9 @@ struct vgx_submap_s {
   vgx::PointSet points[2]; // by VGX_POINTS_*
   std::vector<int32_t> isosurface_blocks;  // block slots holding isosurface vertices (VSM:237-240)
   int32_t* d_iso_block_index = nullptr;    // [isosurface_blocks.size()][3]
+  // per block: 1 if any voxel of the raw TSDF layer has weight > 0 (vgx_project.hip), computed at first use and kept:
+  // a finished submap is immutable, and the flags stay valid after vgx_submap_release_raw_layers
+  uint8_t* d_block_has_data = nullptr;
   vgx::GridDev grid_dev(int which) const;
   int ensure_quad_grid(int which);  // apron bricks -> quad bricks, once (vgx_context.hip)
   // Lifetime (guarded by vgx::lifetime_mu()): cost functions made from this submap.  vgx_submap_destroy while users > 0

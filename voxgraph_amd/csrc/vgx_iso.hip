@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "vgx_internal.h"
+#include "vgx_interp.h"
 
 #pragma clang fp contract(off)
 
@@ -150,74 +151,6 @@ __device__ __forceinline__ unsigned long long iso_cell_key(const IsoParams& p, c
   return key;
 }
 
-// Interpolator<TsdfVoxel>::getVoxelsAndQVector + interpVoxel on the raw layer
-template <int VPS>
-__device__ bool iso_interp(const IsoParams& p, const float pos[3], float& dist, float& wgt) {
-  constexpr int VOX = VPS * VPS * VPS;
-  int blk[3], vox[3];
-  float dl[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    int b0 = (int)floorf(pos[a] * p.block_size_inv + 1e-6f);
-    float origin = (float)b0 * p.block_size;
-    int v = (int)floorf((pos[a] - origin) * p.voxel_size_inv + 1e-6f);
-    v = min(max(v, 0), VPS - 1);
-    float centre = origin + ((float)v + 0.5f) * p.voxel_size;
-    if (a == 0) {
-      // setIndexes: the block containing pos must exist (checked below through neighbours:
-      // it is the block of one of the 8 neighbours)
-    }
-    if (pos[a] - centre < 0.0f) {
-      v--;
-      if (v < 0) {
-        b0--;
-        v += VPS;
-      }
-    }
-    float origin2 = (float)b0 * p.block_size;
-    dl[a] = (pos[a] - (origin2 + ((float)v + 0.5f) * p.voxel_size)) * p.voxel_size_inv;
-    blk[a] = b0;
-    vox[a] = v;
-  }
-  float d[8], w[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    int off[3] = {(k >> 2) & 1, (k >> 1) & 1, k & 1};
-    int nb[3], nv[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      nb[a] = blk[a];
-      nv[a] = vox[a] + off[a];
-      if (nv[a] >= VPS) {
-        nb[a]++;
-        nv[a] -= VPS;
-      }
-    }
-    int rx = nb[0] - p.lut_min.x, ry = nb[1] - p.lut_min.y, rz = nb[2] - p.lut_min.z;
-    if ((unsigned)rx >= (unsigned)p.lut_dim.x || (unsigned)ry >= (unsigned)p.lut_dim.y ||
-        (unsigned)rz >= (unsigned)p.lut_dim.z)
-      return false;
-    int slot = p.lut[rx + p.lut_dim.x * (ry + p.lut_dim.y * rz)];
-    if (slot < 0) return false;
-    size_t at = (size_t)slot * VOX + (size_t)(nv[0] + VPS * (nv[1] + VPS * nv[2]));
-    d[k] = p.tsdf_d[at];
-    w[k] = p.tsdf_w[at];
-    if (!(w[k] > 0.0f)) return false;  // Interpolator<TsdfVoxel>::isVoxelValid
-  }
-  auto interp = [&](const float x[8]) {
-    float c0 = x[0], c1 = -x[0] + x[4], c2 = -x[0] + x[2], c3 = -x[0] + x[1];
-    float c4 = ((x[0] - x[2]) - x[4]) + x[6];
-    float c5 = ((x[0] - x[1]) - x[2]) + x[3];
-    float c6 = ((x[0] - x[1]) - x[4]) + x[5];
-    float c7 = ((((((-x[0] + x[1]) + x[2]) - x[3]) + x[4]) - x[5]) - x[6]) + x[7];
-    float q4 = dl[0] * dl[1], q5 = dl[1] * dl[2], q6 = dl[2] * dl[0], q7 = dl[0] * dl[1] * dl[2];
-    return ((((((c0 + dl[0] * c1) + dl[1] * c2) + dl[2] * c3) + q4 * c4) + q5 * c5) + q6 * c6) + q7 * c7;
-  };
-  dist = interp(d);
-  wgt = interp(w);
-  return true;
-}
-
 // mode 0: count candidates; 1: dedup insert; 2: count survivors; 3: write survivors
 template <int VPS, int MODE>
 __global__ __launch_bounds__(256) void iso_pass_kernel(IsoParams p, int32_t* __restrict__ counts,
@@ -258,7 +191,7 @@ __global__ __launch_bounds__(256) void iso_pass_kernel(IsoParams p, int32_t* __r
         }
       } else {
         while (p.keys[h] != key) h = (h + 1) & p.mask;   // present: inserted in pass 1
-        keep = p.ids[h] == id && iso_interp<VPS>(p, vert, dist, wgt);
+        keep = p.ids[h] == id && tsdf_interp<VPS>(p, vert, dist, wgt);
       }
     }
     if (MODE == 0 || MODE == 2) my_count += keep ? 1 : 0;

@@ -516,6 +516,49 @@ int reserve_for_scan(vgx_tsdf_layer L, const float origin[3], float reach) {
   return VGX_OK;
 }
 
+// Before a kernel that may allocate up to `extra_blocks` blocks anywhere in the block box [lo, hi] (the projected map,
+// vgx_project.hip): the table covers the box and the pool holds the exact current count plus all of them.  Waits for
+// the stream.  Refuses (VGX_ERR_NOMEM) while earlier dropped updates are unacknowledged, like a scan.
+int reserve_blocks(vgx_tsdf_layer L, const int32_t lo[3], const int32_t hi[3], int64_t extra_blocks) {
+  vgx_ctx ctx = L->ctx;
+  TsdfLayerDev& d = L->dev;
+  TsdfStats st{};
+  int rc = read_stats_sync(L, &st);
+  if (rc != VGX_OK) return rc;
+  if (st.dropped != 0)
+    return set_error(ctx, VGX_ERR_NOMEM, "TSDF layer: voxel updates were dropped by an earlier scan (allocation failed)");
+  bool inside = L->lut_cells > 0;
+  for (int a = 0; a < 3 && inside; ++a) inside = lo[a] >= d.lut_min[a] && hi[a] < d.lut_min[a] + d.lut_dim[a];
+  if (!inside) {
+    int32_t mn[3], dm[3];
+    for (int a = 0; a < 3; ++a) {
+      int64_t nlo = lo[a], nhi = hi[a];
+      if (L->lut_cells > 0) {
+        nlo = std::min<int64_t>(nlo, d.lut_min[a]);
+        nhi = std::max<int64_t>(nhi, (int64_t)d.lut_min[a] + d.lut_dim[a] - 1);
+      }
+      if (nhi - nlo + 1 > (int64_t)1 << 28)
+        return set_error(ctx, VGX_ERR_UNSUPPORTED, "TSDF layer: block box exceeds 2^28 cells (dense lookup table)");
+      mn[a] = (int32_t)nlo;
+      dm[a] = (int32_t)(nhi - nlo + 1);
+    }
+    rc = rebox(L, mn, dm);
+    if (rc != VGX_OK) return rc;
+    ++L->growths;
+  }
+  if ((int64_t)st.n_blocks + extra_blocks > (int64_t)d.max_blocks) {
+    const int64_t want = std::max<int64_t>(2 * (int64_t)d.max_blocks, (int64_t)st.n_blocks + extra_blocks);
+    if (want > INT32_MAX) return set_error(ctx, VGX_ERR_UNSUPPORTED, "TSDF layer: more than 2^31 blocks");
+    rc = grow_pool(L, (int32_t)want, st.n_blocks);
+    if (rc != VGX_OK) return rc;
+    hipLaunchKernelGGL(tsdf_lut_clear_exhausted_kernel, dim3((unsigned)((L->lut_cells + 255) / 256)), dim3(256), 0,
+                       ctx->tsdf_stream, d.lut, (long long)L->lut_cells);
+    VGX_HIP(ctx, hipGetLastError());
+    ++L->growths;
+  }
+  return VGX_OK;
+}
+
 // after a scan's kernel: ask for the counters without waiting for them -- but only once the
 // unconfirmed bounds have eaten half of the pool's headroom: a copy between two kernels costs the
 // stream a few microseconds, and at 16 scans of slack one look every ~8 scans is plenty
@@ -540,6 +583,18 @@ void request_readback(vgx_tsdf_layer L) {
 
 namespace vgx {
 int tsdf_reserve_for_scan(vgx_tsdf_layer L, const float origin[3], float reach) { return reserve_for_scan(L, origin, reach); }
+int tsdf_reserve_blocks(vgx_tsdf_layer L, const int32_t lo[3], const int32_t hi[3], int64_t extra_blocks) {
+  return reserve_blocks(L, lo, hi, extra_blocks);
+}
+int tsdf_read_stats(vgx_tsdf_layer L, int32_t* n_blocks, unsigned long long* dropped) {
+  TsdfStats st{};
+  const int rc = read_stats_sync(L, &st);
+  if (rc == VGX_OK) {
+    *n_blocks = st.n_blocks;
+    *dropped = st.dropped;
+  }
+  return rc;
+}
 int64_t tsdf_last_scan_bound(vgx_tsdf_layer L) { return L->recent.empty() ? 0 : L->recent.back().second; }
 void tsdf_request_readback(vgx_tsdf_layer L) { request_readback(L); }
 }  // namespace vgx

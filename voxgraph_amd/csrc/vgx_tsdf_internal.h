@@ -455,6 +455,10 @@ namespace vgx {
 // vgx_tsdf.hip: room for a scan (block table box + pool), counters read-back, ApproxHashSet reset
 int tsdf_reserve_for_scan(vgx_tsdf_layer L, const float origin[3], float reach);
 int64_t tsdf_last_scan_bound(vgx_tsdf_layer L);
+// room for a kernel that may allocate up to extra_blocks blocks inside the block box [lo, hi] (waits for the stream)
+int tsdf_reserve_blocks(vgx_tsdf_layer L, const int32_t lo[3], const int32_t hi[3], int64_t extra_blocks);
+// exact block count and dropped updates (waits for the stream; the caller holds tsdf_mu)
+int tsdf_read_stats(vgx_tsdf_layer L, int32_t* n_blocks, unsigned long long* dropped);
 void tsdf_request_readback(vgx_tsdf_layer L);
 // vgx_tsdf_coop.hip: the racing scan (one workgroup per 256 points: start set, cooperative walk, per-voxel folds);
 // stats: gather vgx_tsdf_integrator_walk_stats' numbers (a counted scan: I.wg_stats must hold a row per workgroup)
