@@ -736,6 +736,70 @@ VGX_API int vgx_submap_from_tsdf_layer(vgx_ctx ctx, vgx_tsdf_layer layer, int32_
  * vgx_tsdf_layer_download) may, as after a scan. */
 VGX_API int vgx_tsdf_layer_merge_submaps(vgx_tsdf_layer layer, int32_t n, const vgx_submap* submaps, const float* T_L_S, int64_t* n_blocks_out);
 
+/* The combined mesh: voxblox::MeshIntegrator<TsdfVoxel>::generateMesh(false, false) [recalled] over a whole TSDF layer.
+ * cblox SubmapMesher::generateCombinedMesh (SubmapVisuals::publishCombinedMesh / saveCombinedMesh) is the projected map
+ * (vgx_tsdf_layer_merge_submaps) followed by this call on the layer; the active-submap mesh and MapEvaluation's
+ * ground-truth mesh are the same call on one layer (vgx_submap_generate_mesh reads a finished submap's raw layer, in the
+ * submap frame).  Everything about voxblox here is [recalled]: voxblox is not vendored.
+ * Semantics (what the kernels, vgx_mesh.hip, and tests/mesh_ref.py both follow):
+ *   cubes          block b owns the cube whose low corner is its voxel (x,y,z), every x,y,z in [0, vps)
+ *                  (MeshIntegrator::extractBlockMesh).  Its 8 corners are that voxel + cube_index_offsets_ in the order
+ *                  (0,0,0) (1,0,0) (1,1,0) (0,1,0) (0,0,1) (1,0,1) (1,1,1) (0,1,1); a corner outside b is read from the
+ *                  neighbouring block (+x, +y, +z and their combinations).  A cube is meshed only if every corner exists
+ *                  and has weight > min_weight (utils::getSdfIfValid); a missing neighbour block skips the cube.
+ *   visiting order (fixes the triangle order within a block) 1. the interior cubes x,y,z < vps-1, x outermost, z
+ *                  innermost; 2. the max-X plane x = vps-1 (z outer, y inner, both in [0, vps)); 3. the max-Y plane
+ *                  y = vps-1 (z outer, x inner, x < vps-1); 4. the max-Z plane z = vps-1 (y outer, x inner, x,y < vps-1).
+ *   coordinates    corner i = coords + offset_i * voxel_size, coords the low voxel's centre origin + (idx + 0.5f) *
+ *                  voxel_size, origin = block_index * block_size (f32; the rule of vgx_tsdf_layer_merge_submaps).  A
+ *                  corner is NOT the neighbour voxel's own centre recomputed: the two round differently.
+ *   per cube       (MarchingCubes::meshCube) configuration bit i set when sdf_i < 0; edges kEdgeIndexPairs {0,1} {1,2}
+ *                  {2,3} {3,0} {4,5} {5,6} {6,7} {7,4} {0,4} {1,5} {2,6} {3,7} in that direction; the vertex on edge
+ *                  (a, b) is pa + t * (pb - pa), t = sa / (sa - sb), when |sa - sb| >= 1e-6f, else 0.5f * (pa + pb)
+ *                  (f32, that association, no contraction).  Each triple (e0, e1, e2) of the classic Lorensen / Bourke
+ *                  table (voxgraph_amd/csrc/vgx_mc_tables.h) is emitted as the vertices e2, e1, e0; its normal is
+ *                  (p1 - p0) x (p2 - p0) over the emitted order (Eigen's cross-product formulas) divided by
+ *                  sqrt((x*x + y*y) + z*z), the zero vector kept when that sum is 0 (Eigen normalized()).
+ *   triangle soup  edge direction is not shared between cubes: edges 2, 3, 6, 7 run high to low, so the up to four cubes
+ *                  around one grid edge may give bitwise-different copies of its vertex -- voxblox's soup, reproduced.
+ *                  The isosurface points (vgx_submap_extract_isosurface_points) interpolate low to high from independently
+ *                  computed centres and stay as they are: the two agree to the last bits only.
+ *   output         one entry per allocated TSDF block (voxblox's MeshLayer: one mesh per block, possibly empty), in
+ *                  ascending (x, y, z) block-index order whatever the layer's slot order.  Block k owns the triangles
+ *                  [first[k], first[k+1]); vertices [T][3][3] f32 in the emitted order (voxblox's indices are implicitly
+ *                  0..3n-1 per block); normals [T][3] f32, one per triangle (voxblox stores it three times).
+ *   deviations     no colour (voxgraph colours the combined mesh by normal or per submap; the projected map carries none):
+ *                  the config has no use_color.  only_mesh_updated_blocks / clear_updated_flag are not supported (every
+ *                  caller passes false, false).
+ * A mesh handle is reused from call to call (the mapper re-meshes after every submap): its device buffers grow on demand;
+ * one call at a time per handle.  Refused with VGX_ERR_INVALID before anything is written: NULL handles, a min_weight that
+ * is negative or not finite, a source and mesh of different contexts, a submap whose raw TSDF layer was released.  An
+ * empty layer gives VGX_OK and 0 blocks.  Out of device memory: VGX_ERR_NOMEM, and the handle then holds no mesh (stats
+ * report 0).  The layer source runs on the context's TSDF stream behind the scans and merges already queued, under the
+ * TSDF lock and then the registration lock (so a projected map can be meshed right after it is built); the submap source
+ * runs on the registration stream under the registration lock.  Both return with the mesh complete; values and their
+ * order do not depend on scheduling. */
+typedef struct vgx_mesh_s* vgx_mesh;
+typedef struct vgx_mesh_config {
+  float min_weight; /* 1e-4 (MeshIntegratorConfig [recalled]) */
+} vgx_mesh_config;
+VGX_API void vgx_mesh_config_default(vgx_mesh_config* cfg);
+VGX_API int vgx_mesh_create(vgx_ctx ctx, vgx_mesh* out);
+VGX_API int vgx_mesh_destroy(vgx_mesh mesh);
+/* cfg == NULL: the defaults */
+VGX_API int vgx_tsdf_layer_generate_mesh(vgx_tsdf_layer layer, const vgx_mesh_config* cfg, vgx_mesh mesh);
+VGX_API int vgx_submap_generate_mesh(vgx_submap submap, const vgx_mesh_config* cfg, vgx_mesh mesh);
+VGX_API int vgx_mesh_stats(vgx_mesh mesh, int32_t* n_blocks, int64_t* n_triangles);
+/* block_index [nb][3], first [nb+1], vertices [T][3][3], normals [T][3]; any may be NULL */
+VGX_API int vgx_mesh_download(vgx_mesh mesh, int32_t* block_index, int64_t* first, float* vertices, float* normals);
+/* Host code: binary_little_endian PLY of the triangle soup -- vertex x y z nx ny nz (float; the triangle's normal on each
+ * of its three vertices), face `list uchar int vertex_indices` = (3t, 3t+1, 3t+2).  A stated format, not byte parity
+ * with voxblox's outputMeshLayerAsPly. */
+VGX_API int vgx_mesh_write_ply(vgx_mesh mesh, const char* path);
+/* The triangle table the kernels use (voxgraph_amd/csrc/vgx_mc_tables.h): row c = the triangles of configuration c as
+ * edge triples, -1 terminated.  Host only (no device needed). */
+VGX_API int vgx_mesh_triangle_table(int8_t out[256][16]);
+
 /* ---------------------------------------------------------------------------
  * Saved maps: cblox submap-collection files and voxblox layer files.
  *

@@ -63,6 +63,10 @@ class MapFileSubmapData(C.Structure):
                 ("esdf_distance", C.POINTER(C.c_float)), ("esdf_observed", C.POINTER(C.c_uint8))]
 
 
+class MeshConfig(C.Structure):
+    _fields_ = [("min_weight", C.c_float)]
+
+
 class TsdfConfig(C.Structure):
     """vgx_tsdf_config == voxblox::TsdfIntegratorBase::Config (the fields that matter on a GPU)."""
     _fields_ = [("default_truncation_distance", C.c_float), ("max_weight", C.c_float),
@@ -179,6 +183,15 @@ SIGNATURES = {
     "vgx_tsdf_integrate_device": (C.c_int, [vp, f32p, vp, vp, C.c_int64, C.c_int32, i64p]),
     "vgx_tsdf_integrate_merged": (C.c_int, [vp, f32p, f32p, u8p, C.c_int64, C.c_int32, i64p]),
     "vgx_tsdf_integrate_merged_device": (C.c_int, [vp, f32p, vp, vp, C.c_int64, C.c_int32, i64p]),
+    "vgx_mesh_config_default": (None, [C.POINTER(MeshConfig)]),
+    "vgx_mesh_create": (C.c_int, [vp, C.POINTER(vp)]),
+    "vgx_mesh_destroy": (C.c_int, [vp]),
+    "vgx_tsdf_layer_generate_mesh": (C.c_int, [vp, C.POINTER(MeshConfig), vp]),
+    "vgx_submap_generate_mesh": (C.c_int, [vp, C.POINTER(MeshConfig), vp]),
+    "vgx_mesh_stats": (C.c_int, [vp, i32p, i64p]),
+    "vgx_mesh_download": (C.c_int, [vp, i32p, i64p, f32p, f32p]),
+    "vgx_mesh_write_ply": (C.c_int, [vp, C.c_char_p]),
+    "vgx_mesh_triangle_table": (C.c_int, [C.POINTER(C.c_int8)]),
     "vgx_map_file_open": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(vp)]),
     "vgx_map_file_close": (C.c_int, [vp]),
     "vgx_map_file_last_error": (C.c_char_p, [vp]),
@@ -468,6 +481,14 @@ class Submap:
         self.ctx.check(self.ctx.lib.vgx_submap_download_points(
             self.h, point_type, _ptr(xyz, f32p), _ptr(d, f32p), _ptr(w, f32p)))
         return xyz, d, w
+
+    def generate_mesh(self, mesh=None, min_weight=1e-4):
+        """MeshIntegrator::generateMesh(false, false) over the submap's raw TSDF layer, in the submap frame
+        (vgx_submap_generate_mesh).  Returns the Mesh (a new one when mesh is None)."""
+        mesh = mesh if mesh is not None else Mesh(self.ctx)
+        cfg = MeshConfig(float(min_weight))
+        self.ctx.check(self.ctx.lib.vgx_submap_generate_mesh(self.h, C.byref(cfg), mesh.h))
+        return mesh
 
     def release_raw_layers(self):
         self.ctx.check(self.ctx.lib.vgx_submap_release_raw_layers(self.h))
@@ -931,6 +952,14 @@ class TsdfLayer:
         self.ctx.check(self.ctx.lib.vgx_tsdf_layer_merge_submaps(self.h, n, arr, _ptr(T, f32p), C.byref(nb)))
         return nb.value
 
+    def generate_mesh(self, mesh=None, min_weight=1e-4):
+        """MeshIntegrator::generateMesh(false, false) over this layer (vgx_tsdf_layer_generate_mesh).  Returns the Mesh
+        (a new one when mesh is None)."""
+        mesh = mesh if mesh is not None else Mesh(self.ctx)
+        cfg = MeshConfig(float(min_weight))
+        self.ctx.check(self.ctx.lib.vgx_tsdf_layer_generate_mesh(self.h, C.byref(cfg), mesh.h))
+        return mesh
+
     def download(self):
         n, _ = self.stats()
         nv = self.vps ** 3
@@ -958,6 +987,58 @@ def projected_map(ctx, submaps, poses, layer):
     layer.upload(np.zeros((0, 3), np.int32), np.zeros(0, np.float32), np.zeros(0, np.float32))
     layer.merge_submaps([submaps[i] for i in order], poses[order])
     return layer
+
+
+def combined_mesh(ctx, submaps, poses, layer, mesh=None, min_weight=1e-4):
+    """cblox SubmapMesher::generateCombinedMesh: projected_map(ctx, submaps, poses, layer), then the layer's mesh.
+    Returns the Mesh."""
+    projected_map(ctx, submaps, poses, layer)
+    return layer.generate_mesh(mesh, min_weight)
+
+
+class Mesh:
+    """A voxblox MeshLayer on the GPU (vgx_mesh): per allocated block, in ascending block-index order, a range of
+    triangles; reused from call to call."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        h = vp()
+        ctx.check(ctx.lib.vgx_mesh_create(ctx.h, C.byref(h)))
+        self.h = h
+
+    def stats(self):
+        """(blocks, triangles)"""
+        nb, nt = C.c_int32(), C.c_int64()
+        self.ctx.check(self.ctx.lib.vgx_mesh_stats(self.h, C.byref(nb), C.byref(nt)))
+        return nb.value, nt.value
+
+    def download(self):
+        """(block_index [nb][3] int32, first [nb+1] int64, vertices [T][3][3] f32, normals [T][3] f32)"""
+        nb, nt = self.stats()
+        bi = np.zeros((nb, 3), np.int32)
+        first = np.zeros(nb + 1, np.int64)
+        v = np.zeros((nt, 3, 3), np.float32)
+        n = np.zeros((nt, 3), np.float32)
+        self.ctx.check(self.ctx.lib.vgx_mesh_download(self.h, _ptr(bi, i32p), _ptr(first, i64p), _ptr(v, f32p),
+                                                      _ptr(n, f32p)))
+        return bi, first, v, n
+
+    def write_ply(self, path):
+        self.ctx.check(self.ctx.lib.vgx_mesh_write_ply(self.h, os.fsencode(path)))
+
+    def destroy(self):
+        if self.h:
+            self.ctx.lib.vgx_mesh_destroy(self.h)
+            self.h = None
+
+
+def mc_triangle_table():
+    """the [256][16] int8 triangle table the mesh kernels read (vgx_mesh_triangle_table; no device needed)"""
+    out = np.zeros((256, 16), np.int8)
+    rc = load().vgx_mesh_triangle_table(out.ctypes.data_as(C.POINTER(C.c_int8)))
+    if rc != OK:
+        raise VgxError(rc, "vgx_mesh_triangle_table")
+    return out
 
 
 class FastTsdfIntegrator:

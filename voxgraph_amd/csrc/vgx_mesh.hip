@@ -1,0 +1,608 @@
+// The combined mesh on the device: voxblox::MeshIntegrator<TsdfVoxel>::generateMesh(false, false) [recalled] over a TSDF
+// layer (a projected map, an active submap) or a finished submap's raw layer.  The semantics are stated in
+// include/voxgraph_amd.h (vgx_tsdf_layer_generate_mesh); the layout and the passes in DESIGN.md 11.
+//
+//   1. order   the allocated blocks by block index: 64-bit keys (the block's cell in the dense block table, x-major) and
+//              their slots, one radix sort
+//   2. count   one workgroup per block in that order: the block's (vps+1)^3 corners staged in LDS (its own voxels and up
+//              to 7 neighbour blocks through the table), per cube the configuration and its triangle count
+//   3. scan    an inclusive scan of the counts gives every block's first triangle; the output grows once, to the total
+//   4. emit    one workgroup per block again: the cubes in voxblox's visiting order, a workgroup-wide exclusive scan of
+//              their counts per round of 256 cubes, each cube writing its triangles at its own offset.  No atomics on the
+//              output: values and order do not depend on scheduling.
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "vgx_internal.h"
+#include "vgx_mc_tables.h"
+#include "vgx_tsdf_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace vgx {
+
+__constant__ int8_t c_mc_tri[256][16] = VGX_MC_TRIANGLE_TABLE;
+__constant__ McCounts c_mc_count = mc_counts();
+
+constexpr int kMeshThreads = 256;
+
+// a TSDF source: the layer's packed {distance, weight} words or a submap's two raw arrays
+struct MeshSrc {
+  const int32_t* lut;  // dense [dim.z][dim.y][dim.x]: slot, or < 0
+  int32_t lut_min[3], lut_dim[3];
+  const int32_t* block_index;       // [slot][3]
+  const unsigned long long* words;  // layer: [slot][vps^3]
+  const float* dist;                // submap: [slot][vps^3]
+  const float* weight;
+  float voxel_size;
+};
+
+__device__ __forceinline__ int mesh_lookup(const MeshSrc& s, int bx, int by, int bz) {
+  const int rx = bx - s.lut_min[0], ry = by - s.lut_min[1], rz = bz - s.lut_min[2];
+  if ((unsigned)rx >= (unsigned)s.lut_dim[0] || (unsigned)ry >= (unsigned)s.lut_dim[1] || (unsigned)rz >= (unsigned)s.lut_dim[2])
+    return -1;
+  const int v = s.lut[rx + s.lut_dim[0] * (ry + s.lut_dim[1] * rz)];
+  return v >= 0 ? v : -1;
+}
+
+// key = the block's cell in the table, x-major (ascending key = ascending (x, y, z))
+__global__ __launch_bounds__(256) void mesh_keys_kernel(MeshSrc s, int32_t n, unsigned long long* __restrict__ keys,
+                                                        int32_t* __restrict__ slots) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int32_t* b = s.block_index + 3 * (size_t)i;
+  keys[i] = ((unsigned long long)(b[0] - s.lut_min[0]) * (unsigned long long)s.lut_dim[1] +
+             (unsigned long long)(b[1] - s.lut_min[1])) * (unsigned long long)s.lut_dim[2] +
+            (unsigned long long)(b[2] - s.lut_min[2]);
+  slots[i] = i;
+}
+
+template <int VPS>
+struct MeshLds {
+  static constexpr int C = VPS + 1;
+  float sdf[C * C * C];
+  uint8_t ok[C * C * C];
+  int nbr[8];
+  int wave_sum[kMeshThreads / 64];
+};
+
+// the block's corners: voxel (cx, cy, cz) of [0, vps]^3, from the block or its +x / +y / +z neighbours
+template <int VPS, bool PACKED>
+__device__ __forceinline__ void stage_corners(const MeshSrc& s, int slot, const int32_t* bi, float min_weight, MeshLds<VPS>& m) {
+  constexpr int C = VPS + 1, VOX = VPS * VPS * VPS;
+  if (threadIdx.x < 8) {
+    const int n = threadIdx.x;
+    m.nbr[n] = n == 0 ? slot : mesh_lookup(s, bi[0] + (n & 1), bi[1] + ((n >> 1) & 1), bi[2] + ((n >> 2) & 1));
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < C * C * C; i += kMeshThreads) {
+    const int cx = i % C, cy = (i / C) % C, cz = i / (C * C);
+    const int n = (cx == VPS ? 1 : 0) | (cy == VPS ? 2 : 0) | (cz == VPS ? 4 : 0);
+    const int lin = (cx & (VPS - 1)) + VPS * ((cy & (VPS - 1)) + VPS * (cz & (VPS - 1)));
+    const int sl = m.nbr[n];
+    float d = 0.0f;
+    bool ok = false;
+    if (sl >= 0) {
+      float w;
+      if (PACKED) {
+        const unsigned long long v = s.words[(size_t)sl * VOX + lin];
+        d = __uint_as_float((uint32_t)v);
+        w = __uint_as_float((uint32_t)(v >> 32));
+      } else {
+        d = s.dist[(size_t)sl * VOX + lin];
+        w = s.weight[(size_t)sl * VOX + lin];
+      }
+      ok = w > min_weight;  // utils::getSdfIfValid
+    }
+    m.sdf[i] = d;
+    m.ok[i] = ok ? 1 : 0;
+  }
+  __syncthreads();
+}
+
+// corner i of the cube with low corner (x, y, z): cube_index_offsets_
+__device__ __forceinline__ int corner_ox(int i) { return ((i + 1) >> 1) & 1; }  // 0 1 1 0 0 1 1 0
+__device__ __forceinline__ int corner_oy(int i) { return (i >> 1) & 1; }        // 0 0 1 1 0 0 1 1
+__device__ __forceinline__ int corner_oz(int i) { return (i >> 2) & 1; }        // 0 0 0 0 1 1 1 1
+
+// configuration of the cube, or -1 when a corner is missing or too light
+template <int VPS>
+__device__ __forceinline__ int cube_config(const MeshLds<VPS>& m, int x, int y, int z, float sdf[8]) {
+  constexpr int C = VPS + 1;
+  int cfg = 0;
+  bool ok = true;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int idx = (x + corner_ox(i)) + C * ((y + corner_oy(i)) + C * (z + corner_oz(i)));
+    sdf[i] = m.sdf[idx];
+    ok = ok && m.ok[idx];
+    cfg |= sdf[i] < 0.0f ? (1 << i) : 0;
+  }
+  return ok ? cfg : -1;
+}
+
+// rank -> cube in voxblox's visiting order (extractBlockMesh)
+template <int VPS>
+__device__ __forceinline__ void visit(int r, int& x, int& y, int& z) {
+  constexpr int M = VPS - 1;
+  if (r < M * M * M) {
+    x = r / (M * M);
+    y = (r / M) % M;
+    z = r % M;
+    return;
+  }
+  r -= M * M * M;
+  if (r < VPS * VPS) {
+    x = M;
+    z = r / VPS;
+    y = r % VPS;
+    return;
+  }
+  r -= VPS * VPS;
+  if (r < VPS * M) {
+    y = M;
+    z = r / M;
+    x = r % M;
+    return;
+  }
+  r -= VPS * M;
+  z = M;
+  y = r / M;
+  x = r % M;
+}
+
+template <int VPS, bool PACKED>
+__global__ __launch_bounds__(kMeshThreads) void mesh_count_kernel(MeshSrc s, const int32_t* __restrict__ order, float min_weight,
+                                                                   int64_t* __restrict__ counts, int32_t* __restrict__ out_bi) {
+  __shared__ MeshLds<VPS> m;
+  __shared__ int total;
+  const int slot = order[blockIdx.x];
+  const int32_t* bi = s.block_index + 3 * (size_t)slot;
+  if (threadIdx.x == 0) total = 0;
+  stage_corners<VPS, PACKED>(s, slot, bi, min_weight, m);
+  int cnt = 0;
+  for (int r = threadIdx.x; r < VPS * VPS * VPS; r += kMeshThreads) {
+    float sdf[8];
+    const int cfg = cube_config<VPS>(m, r % VPS, (r / VPS) % VPS, r / (VPS * VPS), sdf);
+    if (cfg >= 0) cnt += c_mc_count.n[cfg];
+  }
+  atomicAdd(&total, cnt);  // (integer sum in LDS: exact in any order)
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    counts[blockIdx.x] = total;
+    out_bi[3 * (size_t)blockIdx.x + 0] = bi[0];
+    out_bi[3 * (size_t)blockIdx.x + 1] = bi[1];
+    out_bi[3 * (size_t)blockIdx.x + 2] = bi[2];
+  }
+}
+
+__device__ __forceinline__ void edge_vertex(const float pa[3], const float pb[3], float sa, float sb, float out[3]) {
+  const float diff = sa - sb;
+  if (fabsf(diff) >= 1e-6f) {
+    const float t = sa / diff;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) out[a] = pa[a] + t * (pb[a] - pa[a]);
+  } else {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) out[a] = 0.5f * (pa[a] + pb[a]);
+  }
+}
+
+__device__ __forceinline__ void cube_edge_vertex(int e, const float base[3], float vs, const float sdf[8], float out[3]) {
+  // kEdgeIndexPairs: 0-1 1-2 2-3 3-0 4-5 5-6 6-7 7-4 0-4 1-5 2-6 3-7
+  const int a = e < 8 ? e : e - 8;
+  const int b = e < 8 ? ((e & 3) == 3 ? e - 3 : e + 1) : e - 4;
+  const float pa[3] = {base[0] + (corner_ox(a) ? vs : 0.0f), base[1] + (corner_oy(a) ? vs : 0.0f), base[2] + (corner_oz(a) ? vs : 0.0f)};
+  const float pb[3] = {base[0] + (corner_ox(b) ? vs : 0.0f), base[1] + (corner_oy(b) ? vs : 0.0f), base[2] + (corner_oz(b) ? vs : 0.0f)};
+  edge_vertex(pa, pb, sdf[a], sdf[b], out);
+}
+
+template <int VPS, bool PACKED>
+__global__ __launch_bounds__(kMeshThreads) void mesh_emit_kernel(MeshSrc s, const int32_t* __restrict__ order, float min_weight,
+                                                                  const int64_t* __restrict__ first, float* __restrict__ vertices,
+                                                                  float* __restrict__ normals) {
+  constexpr int NW = kMeshThreads / 64;
+  __shared__ MeshLds<VPS> m;
+  const int slot = order[blockIdx.x];
+  const int32_t* bi = s.block_index + 3 * (size_t)slot;
+  stage_corners<VPS, PACKED>(s, slot, bi, min_weight, m);
+  const int64_t end = first[blockIdx.x + 1];
+  int64_t base = first[blockIdx.x];
+  const float vs = s.voxel_size, bs = (float)VPS * vs;
+  const float ox = (float)bi[0] * bs, oy = (float)bi[1] * bs, oz = (float)bi[2] * bs;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int r0 = 0; r0 < VPS * VPS * VPS; r0 += kMeshThreads) {
+    int x, y, z;
+    visit<VPS>(r0 + threadIdx.x, x, y, z);
+    float sdf[8];
+    const int cfg = cube_config<VPS>(m, x, y, z, sdf);
+    const int n = cfg >= 0 ? (int)c_mc_count.n[cfg] : 0;
+    // workgroup-wide exclusive prefix of n in visiting order
+    int inc = n;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int o = __shfl_up(inc, d);
+      if (lane >= d) inc += o;
+    }
+    if (lane == 63) m.wave_sum[wave] = inc;
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      before += w < wave ? m.wave_sum[w] : 0;
+      all += m.wave_sum[w];
+    }
+    __syncthreads();  // (wave_sum is rewritten next round)
+    int64_t at = base + before + inc - n;
+    if (n > 0) {
+      // Block::computeCoordinatesFromLinearIndex of the low voxel
+      const float c[3] = {ox + ((float)x + 0.5f) * vs, oy + ((float)y + 0.5f) * vs, oz + ((float)z + 0.5f) * vs};
+      for (int k = 0; k < n; ++k, ++at) {
+        if (at >= end) break;  // (count and emit stage the same corners: not reached)
+        float p[3][3];
+        cube_edge_vertex(c_mc_tri[cfg][3 * k + 2], c, vs, sdf, p[0]);
+        cube_edge_vertex(c_mc_tri[cfg][3 * k + 1], c, vs, sdf, p[1]);
+        cube_edge_vertex(c_mc_tri[cfg][3 * k + 0], c, vs, sdf, p[2]);
+        const float ax = p[1][0] - p[0][0], ay = p[1][1] - p[0][1], az = p[1][2] - p[0][2];
+        const float bx = p[2][0] - p[0][0], by = p[2][1] - p[0][1], bz = p[2][2] - p[0][2];
+        float nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
+        const float sq = (nx * nx + ny * ny) + nz * nz;
+        if (sq > 0.0f) {
+          const float len = sqrtf(sq);
+          nx = nx / len;
+          ny = ny / len;
+          nz = nz / len;
+        }
+        float* v = vertices + 9 * at;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+          v[3 * q + 0] = p[q][0];
+          v[3 * q + 1] = p[q][1];
+          v[3 * q + 2] = p[q][2];
+        }
+        normals[3 * at + 0] = nx;
+        normals[3 * at + 1] = ny;
+        normals[3 * at + 2] = nz;
+      }
+    }
+    base += all;
+  }
+}
+
+}  // namespace vgx
+
+using namespace vgx;
+
+struct vgx_mesh_s {
+  vgx_ctx ctx = nullptr;
+  std::mutex mu;
+  int32_t n_blocks = 0;  // the mesh held now
+  int64_t n_tris = 0;
+  // output, grown on demand
+  int32_t* d_block_index = nullptr;  // [block_cap][3]
+  int64_t* d_first = nullptr;        // [block_cap + 1]
+  float* d_vertices = nullptr;       // [tri_cap][3][3]
+  float* d_normals = nullptr;        // [tri_cap][3]
+  // per-block scratch
+  unsigned long long* d_keys[2] = {nullptr, nullptr};
+  int32_t* d_slots[2] = {nullptr, nullptr};
+  int64_t* d_counts = nullptr;
+  void* d_tmp = nullptr;
+  size_t tmp_bytes = 0;
+  int64_t block_cap = 0, tri_cap = 0;
+};
+
+namespace {
+
+void free_blocks(vgx_mesh M) {
+  void* ps[] = {M->d_block_index, M->d_first, M->d_keys[0], M->d_keys[1], M->d_slots[0], M->d_slots[1], M->d_counts, M->d_tmp};
+  for (void* p : ps)
+    if (p) (void)hipFree(p);
+  M->d_block_index = nullptr;
+  M->d_first = nullptr;
+  M->d_keys[0] = M->d_keys[1] = nullptr;
+  M->d_slots[0] = M->d_slots[1] = nullptr;
+  M->d_counts = nullptr;
+  M->d_tmp = nullptr;
+  M->tmp_bytes = 0;
+  M->block_cap = 0;
+}
+
+void free_tris(vgx_mesh M) {
+  if (M->d_vertices) (void)hipFree(M->d_vertices);
+  if (M->d_normals) (void)hipFree(M->d_normals);
+  M->d_vertices = M->d_normals = nullptr;
+  M->tri_cap = 0;
+}
+
+int alloc_error(vgx_ctx ctx, hipError_t e, const char* what) {
+  (void)hipGetLastError();  // (clear the sticky out-of-memory status)
+  return set_error(ctx, e == hipErrorOutOfMemory ? VGX_ERR_NOMEM : VGX_ERR_HIP,
+                   std::string("mesh: allocating ") + what + ": " + hipGetErrorString(e));
+}
+
+int ensure_blocks(vgx_mesh M, int64_t nb, size_t tmp_bytes) {
+  if (nb > M->block_cap) {
+    free_blocks(M);
+    const int64_t cap = std::max<int64_t>(nb, 1024);
+    hipError_t e = hipMalloc(&M->d_block_index, (size_t)cap * 12);
+    if (e == hipSuccess) e = hipMalloc(&M->d_first, (size_t)(cap + 1) * 8);
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+      e = hipMalloc(&M->d_keys[k], (size_t)cap * 8);
+      if (e == hipSuccess) e = hipMalloc(&M->d_slots[k], (size_t)cap * 4);
+    }
+    if (e == hipSuccess) e = hipMalloc(&M->d_counts, (size_t)cap * 8);
+    if (e != hipSuccess) {
+      free_blocks(M);
+      return alloc_error(M->ctx, e, "block arrays");
+    }
+    M->block_cap = cap;
+  }
+  if (tmp_bytes > M->tmp_bytes) {
+    if (M->d_tmp) (void)hipFree(M->d_tmp);
+    M->d_tmp = nullptr;
+    M->tmp_bytes = 0;
+    const hipError_t e = hipMalloc(&M->d_tmp, tmp_bytes);
+    if (e != hipSuccess) {
+      free_blocks(M);
+      return alloc_error(M->ctx, e, "sort workspace");
+    }
+    M->tmp_bytes = tmp_bytes;
+  }
+  return VGX_OK;
+}
+
+int ensure_tris(vgx_mesh M, int64_t nt) {
+  if (nt <= M->tri_cap) return VGX_OK;
+  free_tris(M);
+  const int64_t cap = std::max<int64_t>(nt + nt / 4, 4096);  // (a quarter of slack: the next map is a little larger)
+  hipError_t e = hipMalloc(&M->d_vertices, (size_t)cap * 36);
+  if (e == hipSuccess) e = hipMalloc(&M->d_normals, (size_t)cap * 12);
+  if (e != hipSuccess) {
+    free_tris(M);
+    return alloc_error(M->ctx, e, "triangles");
+  }
+  M->tri_cap = cap;
+  return VGX_OK;
+}
+
+template <bool PACKED>
+hipError_t launch_count(int vps, hipStream_t st, int32_t nb, const MeshSrc& s, const int32_t* order, float mw, int64_t* counts,
+                        int32_t* out_bi) {
+  if (vps == 16)
+    hipLaunchKernelGGL((mesh_count_kernel<16, PACKED>), dim3((unsigned)nb), dim3(kMeshThreads), 0, st, s, order, mw, counts, out_bi);
+  else
+    hipLaunchKernelGGL((mesh_count_kernel<8, PACKED>), dim3((unsigned)nb), dim3(kMeshThreads), 0, st, s, order, mw, counts, out_bi);
+  return hipGetLastError();
+}
+
+template <bool PACKED>
+hipError_t launch_emit(int vps, hipStream_t st, int32_t nb, const MeshSrc& s, const int32_t* order, float mw, const int64_t* first,
+                       float* vert, float* norm) {
+  if (vps == 16)
+    hipLaunchKernelGGL((mesh_emit_kernel<16, PACKED>), dim3((unsigned)nb), dim3(kMeshThreads), 0, st, s, order, mw, first, vert, norm);
+  else
+    hipLaunchKernelGGL((mesh_emit_kernel<8, PACKED>), dim3((unsigned)nb), dim3(kMeshThreads), 0, st, s, order, mw, first, vert, norm);
+  return hipGetLastError();
+}
+
+// the passes, on `st` (the caller holds the source's locks and M->mu, and has reset M's stats)
+template <bool PACKED>
+int generate(vgx_ctx ctx, hipStream_t st, const MeshSrc& s, int vps, int32_t nb, float mw, vgx_mesh M) {
+  if (nb == 0) return VGX_OK;
+  double cells = 1.0;
+  for (int a = 0; a < 3; ++a) cells *= (double)s.lut_dim[a];
+  unsigned end_bit = 1;
+  while (end_bit < 64 && std::ldexp(1.0, (int)end_bit) < cells) ++end_bit;
+  // 1. order
+  size_t sort_bytes = 0, scan_bytes = 0;
+  VGX_HIP(ctx, rocprim::radix_sort_pairs(nullptr, sort_bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                                         (int32_t*)nullptr, (int32_t*)nullptr, (size_t)nb, 0u, end_bit, st));
+  VGX_HIP(ctx, rocprim::inclusive_scan(nullptr, scan_bytes, (int64_t*)nullptr, (int64_t*)nullptr, (size_t)nb,
+                                       rocprim::plus<int64_t>(), st));
+  int rc = ensure_blocks(M, nb, std::max<size_t>(std::max(sort_bytes, scan_bytes), 4));
+  if (rc != VGX_OK) return rc;
+  hipLaunchKernelGGL(mesh_keys_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, s, nb, M->d_keys[0], M->d_slots[0]);
+  VGX_HIP(ctx, hipGetLastError());
+  VGX_HIP(ctx, rocprim::radix_sort_pairs(M->d_tmp, sort_bytes, M->d_keys[0], M->d_keys[1], M->d_slots[0], M->d_slots[1], (size_t)nb,
+                                         0u, end_bit, st));
+  // 2. count
+  VGX_HIP(ctx, launch_count<PACKED>(vps, st, nb, s, M->d_slots[1], mw, M->d_counts, M->d_block_index));
+  // 3. scan
+  VGX_HIP(ctx, hipMemsetAsync(M->d_first, 0, sizeof(int64_t), st));
+  VGX_HIP(ctx, rocprim::inclusive_scan(M->d_tmp, scan_bytes, M->d_counts, M->d_first + 1, (size_t)nb, rocprim::plus<int64_t>(), st));
+  int64_t total = 0;
+  VGX_HIP(ctx, hipMemcpyAsync(&total, M->d_first + nb, sizeof(total), hipMemcpyDeviceToHost, st));
+  VGX_HIP(ctx, hipStreamSynchronize(st));
+  // 4. emit
+  rc = ensure_tris(M, total);
+  if (rc != VGX_OK) return rc;
+  if (total > 0) {
+    VGX_HIP(ctx, launch_emit<PACKED>(vps, st, nb, s, M->d_slots[1], mw, M->d_first, M->d_vertices, M->d_normals));
+    VGX_HIP(ctx, hipStreamSynchronize(st));
+  }
+  M->n_blocks = nb;
+  M->n_tris = total;
+  return VGX_OK;
+}
+
+// shared refusals; *mw the threshold to use
+int check_args(vgx_ctx ctx, const vgx_mesh_config* cfg, vgx_mesh M, const char* fn, float* mw) {
+  vgx_mesh_config c;
+  vgx_mesh_config_default(&c);
+  if (cfg) c = *cfg;
+  if (!M) return set_error(ctx, VGX_ERR_INVALID, std::string(fn) + ": NULL mesh");
+  if (M->ctx != ctx) return set_error(ctx, VGX_ERR_INVALID, std::string(fn) + ": mesh of another context");
+  if (!std::isfinite(c.min_weight) || c.min_weight < 0.0f)
+    return set_error(ctx, VGX_ERR_INVALID, std::string(fn) + ": min_weight negative or not finite");
+  *mw = c.min_weight;
+  return VGX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void vgx_mesh_config_default(vgx_mesh_config* cfg) {
+  if (cfg) cfg->min_weight = 1e-4f;
+}
+
+int vgx_mesh_create(vgx_ctx ctx, vgx_mesh* out) {
+  if (!ctx || !out) return set_error(ctx, VGX_ERR_INVALID, "vgx_mesh_create: NULL argument");
+  vgx_mesh M = new vgx_mesh_s;
+  M->ctx = ctx;
+  *out = M;
+  return VGX_OK;
+}
+
+int vgx_mesh_destroy(vgx_mesh M) {
+  if (!M) return VGX_ERR_INVALID;
+  (void)hipSetDevice(M->ctx->device);
+  free_blocks(M);
+  free_tris(M);
+  delete M;
+  return VGX_OK;
+}
+
+int vgx_tsdf_layer_generate_mesh(vgx_tsdf_layer L, const vgx_mesh_config* cfg, vgx_mesh M) {
+  if (!L) return set_error(M ? M->ctx : nullptr, VGX_ERR_INVALID, "vgx_tsdf_layer_generate_mesh: NULL layer");
+  vgx_ctx ctx = L->ctx;
+  float mw = 0.0f;
+  int rc = check_args(ctx, cfg, M, "vgx_tsdf_layer_generate_mesh", &mw);
+  if (rc != VGX_OK) return rc;
+  std::lock_guard<std::mutex> mesh_lk(M->mu);
+  std::lock_guard<std::mutex> tsdf_lk(ctx->tsdf_mu);
+  std::lock_guard<std::mutex> reg_lk(ctx->mu);  // (lock order: tsdf_mu, then mu -- as vgx_tsdf_layer_merge_submaps)
+  VGX_HIP(ctx, hipSetDevice(ctx->device));
+  M->n_blocks = 0;
+  M->n_tris = 0;
+  int32_t nb = 0;
+  unsigned long long dropped = 0;
+  rc = tsdf_read_stats(L, &nb, &dropped);  // (behind the scans and merges queued on the TSDF stream)
+  if (rc != VGX_OK) return rc;
+  const TsdfLayerDev& d = L->dev;
+  MeshSrc s{};
+  s.lut = d.lut;
+  for (int a = 0; a < 3; ++a) {
+    s.lut_min[a] = d.lut_min[a];
+    s.lut_dim[a] = d.lut_dim[a];
+  }
+  s.block_index = d.block_index;
+  s.words = d.voxels;
+  s.voxel_size = d.voxel_size;
+  return generate<true>(ctx, ctx->tsdf_stream, s, d.vps, nb, mw, M);
+}
+
+int vgx_submap_generate_mesh(vgx_submap sm, const vgx_mesh_config* cfg, vgx_mesh M) {
+  if (!sm) return set_error(M ? M->ctx : nullptr, VGX_ERR_INVALID, "vgx_submap_generate_mesh: NULL submap");
+  vgx_ctx ctx = sm->ctx;
+  float mw = 0.0f;
+  int rc = check_args(ctx, cfg, M, "vgx_submap_generate_mesh", &mw);
+  if (rc != VGX_OK) return rc;
+  if (sm->n_blocks > 0 && (!sm->d_tsdf_distance || !sm->d_tsdf_weight))
+    return set_error(ctx, VGX_ERR_INVALID, "vgx_submap_generate_mesh: raw TSDF layer not resident (released?)");
+  if (sm->vps != 8 && sm->vps != 16)
+    return set_error(ctx, VGX_ERR_UNSUPPORTED, "vgx_submap_generate_mesh: voxels_per_side must be 8 or 16");
+  std::lock_guard<std::mutex> mesh_lk(M->mu);
+  std::lock_guard<std::mutex> reg_lk(ctx->mu);
+  VGX_HIP(ctx, hipSetDevice(ctx->device));
+  M->n_blocks = 0;
+  M->n_tris = 0;
+  MeshSrc s{};
+  s.lut = sm->d_lut;
+  for (int a = 0; a < 3; ++a) {
+    s.lut_min[a] = sm->lut_min[a];
+    s.lut_dim[a] = sm->lut_dim[a];
+  }
+  s.block_index = sm->d_block_index;
+  s.dist = sm->d_tsdf_distance;
+  s.weight = sm->d_tsdf_weight;
+  s.voxel_size = sm->voxel_size;
+  return generate<false>(ctx, ctx->stream, s, sm->vps, sm->n_blocks, mw, M);
+}
+
+int vgx_mesh_stats(vgx_mesh M, int32_t* n_blocks, int64_t* n_triangles) {
+  if (!M) return VGX_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(M->mu);
+  if (n_blocks) *n_blocks = M->n_blocks;
+  if (n_triangles) *n_triangles = M->n_tris;
+  return VGX_OK;
+}
+
+int vgx_mesh_download(vgx_mesh M, int32_t* block_index, int64_t* first, float* vertices, float* normals) {
+  if (!M) return VGX_ERR_INVALID;
+  vgx_ctx ctx = M->ctx;
+  std::lock_guard<std::mutex> lk(M->mu);
+  VGX_HIP(ctx, hipSetDevice(ctx->device));
+  const int64_t nb = M->n_blocks, nt = M->n_tris;
+  if (first && nb == 0) first[0] = 0;
+  if (nb > 0) {
+    if (block_index) VGX_HIP(ctx, hipMemcpy(block_index, M->d_block_index, (size_t)nb * 12, hipMemcpyDeviceToHost));
+    if (first) VGX_HIP(ctx, hipMemcpy(first, M->d_first, (size_t)(nb + 1) * 8, hipMemcpyDeviceToHost));
+  }
+  if (nt > 0) {
+    if (vertices) VGX_HIP(ctx, hipMemcpy(vertices, M->d_vertices, (size_t)nt * 36, hipMemcpyDeviceToHost));
+    if (normals) VGX_HIP(ctx, hipMemcpy(normals, M->d_normals, (size_t)nt * 12, hipMemcpyDeviceToHost));
+  }
+  return VGX_OK;
+}
+
+int vgx_mesh_triangle_table(int8_t out[256][16]) {
+  if (!out) return VGX_ERR_INVALID;
+  std::memcpy(out, kMcTriangleTable, sizeof(kMcTriangleTable));
+  return VGX_OK;
+}
+
+int vgx_mesh_write_ply(vgx_mesh M, const char* path) {
+  if (!M || !path) return set_error(M ? M->ctx : nullptr, VGX_ERR_INVALID, "vgx_mesh_write_ply: NULL argument");
+  int64_t nt = 0;
+  int rc = vgx_mesh_stats(M, nullptr, &nt);
+  if (rc != VGX_OK) return rc;
+  if (3 * nt > INT32_MAX) return set_error(M->ctx, VGX_ERR_UNSUPPORTED, "vgx_mesh_write_ply: more than 2^31 vertices (int indices)");
+  std::vector<float> v((size_t)nt * 9), n((size_t)nt * 3);
+  rc = vgx_mesh_download(M, nullptr, nullptr, v.data(), n.data());
+  if (rc != VGX_OK) return rc;
+  std::FILE* f = std::fopen(path, "wb");
+  if (!f) return set_error(M->ctx, VGX_ERR_INVALID, std::string("vgx_mesh_write_ply: cannot open ") + path);
+  const std::string header = "ply\nformat binary_little_endian 1.0\nelement vertex " + std::to_string(3 * nt) +
+                             "\nproperty float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\n"
+                             "property float nz\nelement face " + std::to_string(nt) +
+                             "\nproperty list uchar int vertex_indices\nend_header\n";
+  bool ok = std::fwrite(header.data(), 1, header.size(), f) == header.size();
+  std::vector<float> vrec;
+  std::vector<unsigned char> frec;
+  constexpr int64_t kChunk = 1 << 16;  // triangles per write
+  for (int64_t t0 = 0; ok && t0 < nt; t0 += kChunk) {
+    const int64_t t1 = std::min(nt, t0 + kChunk);
+    vrec.clear();
+    for (int64_t t = t0; t < t1; ++t)
+      for (int q = 0; q < 3; ++q) {
+        vrec.insert(vrec.end(), &v[(size_t)t * 9 + 3 * q], &v[(size_t)t * 9 + 3 * q] + 3);
+        vrec.insert(vrec.end(), &n[(size_t)t * 3], &n[(size_t)t * 3] + 3);
+      }
+    ok = std::fwrite(vrec.data(), sizeof(float), vrec.size(), f) == vrec.size();
+  }
+  for (int64_t t0 = 0; ok && t0 < nt; t0 += kChunk) {
+    const int64_t t1 = std::min(nt, t0 + kChunk);
+    frec.assign((size_t)(t1 - t0) * 13, 0);
+    for (int64_t t = t0; t < t1; ++t) {
+      unsigned char* r = &frec[(size_t)(t - t0) * 13];
+      r[0] = 3;
+      for (int q = 0; q < 3; ++q) {
+        const int32_t idx = (int32_t)(3 * t + q);
+        std::memcpy(r + 1 + 4 * q, &idx, 4);
+      }
+    }
+    ok = std::fwrite(frec.data(), 1, frec.size(), f) == frec.size();
+  }
+  ok = (std::fclose(f) == 0) && ok;
+  if (!ok) return set_error(M->ctx, VGX_ERR_INVALID, std::string("vgx_mesh_write_ply: write failed: ") + path);
+  return VGX_OK;
+}
+
+}  // extern "C"
