@@ -736,6 +736,23 @@ VGX_API int vgx_submap_from_tsdf_layer(vgx_ctx ctx, vgx_tsdf_layer layer, int32_
  * vgx_tsdf_layer_download) may, as after a scan. */
 VGX_API int vgx_tsdf_layer_merge_submaps(vgx_tsdf_layer layer, int32_t n, const vgx_submap* submaps, const float* T_L_S, int64_t* n_blocks_out);
 
+/* voxblox::transformLayer(submap TSDF layer, T_L_S, layer) [recalled] into an EMPTY layer: the resampling behind
+ * VoxgraphSubmap::transformSubmap (voxgraph_submap.cpp:38-59), which MapEvaluation::evaluate applies to the ground truth
+ * once it is aligned (map_evaluation.cpp:86).  transformSubmap on the device is this call, then vgx_submap_from_tsdf_layer
+ * and vgx_submap_generate_esdf.  T_L_S {qw,qx,qy,qz, tx,ty,tz} f32.  *n_blocks_out (nullable): blocks in the layer.
+ * The rules are those of vgx_tsdf_layer_merge_submaps with n = 1 -- the f32 inverse pose, the voxel centres, the
+ * interpolation and the coverage rule (a block is kept iff one of its voxel centres interpolates) -- except that the
+ * voxel is COPIED, not merged: an interpolated voxel gets {d, w} as interpolated, every other voxel of a kept block stays
+ * (0, 0).  That is not a merge into an empty layer: (d*w + 0*0) / w need not round back to d.  rgba is left untouched
+ * (the deviation of vgx_tsdf_layer_merge_submaps).  [recalled] some voxblox versions fall back to the nearest voxel where
+ * trilinear interpolation fails; the pinned version could not be checked: here a voxel that does not interpolate is not
+ * written ("Known gaps").
+ * Preconditions, each refused with VGX_ERR_INVALID before anything is written: NULL handles or pose, a layer that is not
+ * empty, a voxel_size or voxels_per_side that differs from the layer's, a released raw TSDF layer, a pose that is not
+ * finite or whose |q.q - 1| > 1e-4.  Streams, locks and lifetimes: those of vgx_tsdf_layer_merge_submaps. */
+VGX_API int vgx_tsdf_layer_transform_submap(vgx_tsdf_layer layer, vgx_submap submap, const float T_L_S[7],
+                                            int64_t* n_blocks_out);
+
 /* The combined mesh: voxblox::MeshIntegrator<TsdfVoxel>::generateMesh(false, false) [recalled] over a whole TSDF layer.
  * cblox SubmapMesher::generateCombinedMesh (SubmapVisuals::publishCombinedMesh / saveCombinedMesh) is the projected map
  * (vgx_tsdf_layer_merge_submaps) followed by this call on the layer; the active-submap mesh and MapEvaluation's
@@ -799,6 +816,55 @@ VGX_API int vgx_mesh_write_ply(vgx_mesh mesh, const char* path);
 /* The triangle table the kernels use (voxgraph_amd/csrc/vgx_mc_tables.h): row c = the triangles of configuration c as
  * edge triples, -1 terminated.  Host only (no device needed). */
 VGX_API int vgx_mesh_triangle_table(int8_t out[256][16]);
+
+/* ---- Map evaluation: voxblox::utils::evaluateLayersRmse ------------------- */
+/* MapEvaluation::evaluate (map_evaluation.cpp:59-114) scores a map against a ground truth: projected map
+ * (vgx_tsdf_layer_merge_submaps), finishSubmap() of both (vgx_submap_from_tsdf_layer, vgx_submap_generate_esdf,
+ * vgx_submap_extract_voxel_points), alignment (REG), transformSubmap (vgx_tsdf_layer_transform_submap) and then
+ * evaluateLayersRmse(gt ESDF, test ESDF, kIgnoreErrorBehindTestSurface, &details, &error_layer), which is this call.
+ * gt and test are finished submaps of one context; `layer` picks their raw ESDF or raw TSDF layer.
+ * Rules (what the kernels, vgx_eval.hip, and tests/map_eval_ref.py both follow; [recalled]: voxblox owns them):
+ *   blocks    matched by index through each submap's dense block table.  A test block without a gt block of the same
+ *             index adds vps^3 to num_non_overlapping_voxels; so does a gt block without a test block.
+ *   observed  ESDF: observed != 0; TSDF: weight > 1e-6f [recalled].
+ *   voxel     unobserved in either layer: non-overlapping.  Else, if the mode ignores the test side (IGNORE_BEHIND_TEST,
+ *             _ALL) and d_test < 0, or the gt side (IGNORE_BEHIND_GT, _ALL) and d_gt < 0: ignored (and overlapping).
+ *             Else evaluated (and overlapping): e = d_test - d_gt in f32; the sum gains (double)(e*e), the product in f32;
+ *             max_error = max |e| (from 0).
+ *   results   rmse = (float)sqrt(total_squared_error / num_evaluated_voxels), 0 when nothing was evaluated (voxblox
+ *             divides by zero there).  min_error: voxblox starts it at 0 and only takes min(), so it reports 0 [recalled];
+ *             that is what is reported.  min_abs_error is the true minimum of |e| (0 when nothing was evaluated).
+ *   sum order (fixed, so the f64 sum is bit-identical run to run) per test block: voxel v = 4 (t + T k) + j is summed
+ *             by thread t (T = min(256, vps^3 / 4) threads), k outer and j inner, from 0.0; the threads of a wave are
+ *             folded by a __shfl_down tree (offsets 32, 16, .., 1; lane 0 keeps the result), the waves in order
+ *             ((w0 + w1) + w2) + ...  Over the test blocks, in slot order: block b is summed by thread b mod 1024 of one
+ *             1024-thread workgroup, in ascending b from 0.0; then the same wave tree and waves in order.
+ *   error     one error block per test block that has a gt counterpart, in test-slot order (*n_error_blocks of them):
+ *   layer     error_block_index [m][3], and per voxel error_distance = e, error_set = 1 for an evaluated voxel, (0, 0)
+ *             for every other -- voxblox's setVoxelSdf / setVoxelWeight(1) into an ESDF or TSDF error layer.  The
+ *             three arrays are sized for n_test blocks (vps^3 entries per block); any may be NULL.
+ * Refused with VGX_ERR_INVALID before anything is written: NULL handles or details, submaps of different contexts, a
+ * voxel_size or vps mismatch (the reference's CHECK_EQ), a layer or mode value out of range, a layer the submap no longer
+ * holds in raw form (released, or an ESDF never generated).  Runs on the context's registration stream under its lock,
+ * as vgx_submap_generate_esdf (which produces the ESDF layers read here) does; returns with the results on the host:
+ * one D2H of the details, plus the error layer when asked for. */
+#define VGX_EVAL_ALL_VOXELS 0 /* voxblox VoxelEvaluationMode order [recalled] */
+#define VGX_EVAL_IGNORE_BEHIND_TEST 1
+#define VGX_EVAL_IGNORE_BEHIND_GT 2
+#define VGX_EVAL_IGNORE_BEHIND_ALL 3
+#define VGX_EVAL_LAYER_ESDF 0
+#define VGX_EVAL_LAYER_TSDF 1
+typedef struct vgx_voxel_evaluation_details {
+  float rmse, max_error, min_error; /* as voxblox stores them (f32)                  */
+  double total_squared_error;       /* the f64 sum rmse comes from                    */
+  float min_abs_error;              /* the true minimum; see min_error above          */
+  int64_t num_evaluated_voxels, num_ignored_voxels, num_overlapping_voxels, num_non_overlapping_voxels;
+} vgx_voxel_evaluation_details;
+VGX_API int vgx_evaluate_layers_rmse(vgx_submap gt, vgx_submap test, int32_t layer, int32_t mode,
+                                     vgx_voxel_evaluation_details* details,
+                                     int32_t* error_block_index /* [n_test][3] or NULL */,
+                                     float* error_distance /* [n_test][vps^3] or NULL */,
+                                     uint8_t* error_set /* [n_test][vps^3] or NULL */, int32_t* n_error_blocks);
 
 /* ---------------------------------------------------------------------------
  * Saved maps: cblox submap-collection files and voxblox layer files.

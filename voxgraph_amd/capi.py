@@ -5,6 +5,7 @@ the HIP library.  There is no fallback: if the shared object is missing the
 import fails, and without a gfx950 device Context() raises.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -65,6 +66,22 @@ class MapFileSubmapData(C.Structure):
 
 class MeshConfig(C.Structure):
     _fields_ = [("min_weight", C.c_float)]
+
+
+class EvaluationDetails(C.Structure):
+    """vgx_voxel_evaluation_details: voxblox::utils::VoxelEvaluationDetails plus the f64 sum and the true min |e|."""
+    _fields_ = [("rmse", C.c_float), ("max_error", C.c_float), ("min_error", C.c_float),
+                ("total_squared_error", C.c_double), ("min_abs_error", C.c_float),
+                ("num_evaluated_voxels", C.c_int64), ("num_ignored_voxels", C.c_int64),
+                ("num_overlapping_voxels", C.c_int64), ("num_non_overlapping_voxels", C.c_int64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+# voxblox VoxelEvaluationMode order; which layer of the two submaps vgx_evaluate_layers_rmse compares
+EVAL_ALL_VOXELS, EVAL_IGNORE_BEHIND_TEST, EVAL_IGNORE_BEHIND_GT, EVAL_IGNORE_BEHIND_ALL = 0, 1, 2, 3
+EVAL_LAYER_ESDF, EVAL_LAYER_TSDF = 0, 1
 
 
 class TsdfConfig(C.Structure):
@@ -175,6 +192,9 @@ SIGNATURES = {
     "vgx_tsdf_layer_download": (C.c_int, [vp, i32p, f32p, f32p, u8p]),
     "vgx_tsdf_layer_upload": (C.c_int, [vp, C.c_int32, i32p, f32p, f32p, u8p]),
     "vgx_tsdf_layer_merge_submaps": (C.c_int, [vp, C.c_int32, C.POINTER(vp), f32p, i64p]),
+    "vgx_tsdf_layer_transform_submap": (C.c_int, [vp, vp, f32p, i64p]),
+    "vgx_evaluate_layers_rmse": (C.c_int, [vp, vp, C.c_int32, C.c_int32, C.POINTER(EvaluationDetails), i32p, f32p, u8p,
+                                           i32p]),
     "vgx_tsdf_integrator_create": (C.c_int, [vp, C.POINTER(TsdfConfig), vp, C.POINTER(vp)]),
     "vgx_tsdf_integrator_destroy": (C.c_int, [vp]),
     "vgx_tsdf_integrator_set_layer": (C.c_int, [vp, vp]),
@@ -381,6 +401,7 @@ class Submap:
                                             _ptr(bi, i32p), _ptr(td, f32p), _ptr(tw, f32p),
                                             _ptr(ed, f32p), _ptr(eo, u8p), C.byref(h)))
         self.h = h
+        self.voxel_size, self.vps = float(voxel_size), int(vps)
 
     @classmethod
     def synth_city(cls, ctx, submap_id, voxel_size, vps, block_min, block_dims, truncation,
@@ -397,6 +418,7 @@ class Submap:
             float(truncation), float(esdf_max), float(tsdf_weight), _ptr(pose, f64p), seed,
             int(build_tsdf_grid), C.byref(h)))
         self.h = h
+        self.voxel_size, self.vps = float(voxel_size), int(vps)
         return self
 
     @classmethod
@@ -407,6 +429,7 @@ class Submap:
         h = vp()
         ctx.check(ctx.lib.vgx_submap_from_tsdf_layer(ctx.h, layer.h, submap_id, C.byref(h)))
         self.h = h
+        self.voxel_size, self.vps = layer.voxel_size, layer.vps
         return self
 
     def generate_esdf(self, config=None):
@@ -912,7 +935,7 @@ class TsdfLayer:
 
     def __init__(self, ctx, voxel_size, vps, lut_min=None, lut_dim=None, max_blocks=0):
         """lut_min / lut_dim / max_blocks are only an initial reservation: the layer grows."""
-        self.ctx, self.vps = ctx, vps
+        self.ctx, self.vps, self.voxel_size = ctx, vps, float(voxel_size)
         mn = None if lut_min is None else np.ascontiguousarray(lut_min, np.int32)
         dm = None if lut_dim is None else np.ascontiguousarray(lut_dim, np.int32)
         h = vp()
@@ -950,6 +973,14 @@ class TsdfLayer:
         T = np.ascontiguousarray(T_L_S, np.float32).reshape(n, 7)
         nb = C.c_int64()
         self.ctx.check(self.ctx.lib.vgx_tsdf_layer_merge_submaps(self.h, n, arr, _ptr(T, f32p), C.byref(nb)))
+        return nb.value
+
+    def transform_submap(self, submap, T_L_S):
+        """voxblox::transformLayer(submap TSDF layer, T_L_S, this layer) into this EMPTY layer
+        (vgx_tsdf_layer_transform_submap: interpolated voxels copied, not merged); returns the layer's block count."""
+        T = np.ascontiguousarray(T_L_S, np.float32).reshape(7)
+        nb = C.c_int64()
+        self.ctx.check(self.ctx.lib.vgx_tsdf_layer_transform_submap(self.h, submap.h, _ptr(T, f32p), C.byref(nb)))
         return nb.value
 
     def generate_mesh(self, mesh=None, min_weight=1e-4):
@@ -994,6 +1025,84 @@ def combined_mesh(ctx, submaps, poses, layer, mesh=None, min_weight=1e-4):
     Returns the Mesh."""
     projected_map(ctx, submaps, poses, layer)
     return layer.generate_mesh(mesh, min_weight)
+
+
+def evaluate_layers_rmse(gt, test, layer=EVAL_LAYER_ESDF, mode=EVAL_IGNORE_BEHIND_TEST, error_layer=False):
+    """voxblox::utils::evaluateLayersRmse(gt layer, test layer, mode, &details[, &error_layer]) over two finished submaps
+    (vgx_evaluate_layers_rmse).  Returns the details as a dict; with error_layer=True, (details, (block_index [m][3],
+    distance [m][vps^3], set [m][vps^3])) -- one error block per test block with a gt counterpart, in test-slot order."""
+    ctx = gt.ctx
+    det = EvaluationDetails()
+    if not error_layer:
+        ctx.check(ctx.lib.vgx_evaluate_layers_rmse(gt.h, test.h, int(layer), int(mode), C.byref(det), None, None, None,
+                                                   None))
+        return det.as_dict()
+    n, nv = test.num_blocks(), test.vps ** 3
+    bi = np.zeros((n, 3), np.int32)
+    d = np.zeros((n, nv), np.float32)
+    st = np.zeros((n, nv), np.uint8)
+    m = C.c_int32()
+    ctx.check(ctx.lib.vgx_evaluate_layers_rmse(gt.h, test.h, int(layer), int(mode), C.byref(det), _ptr(bi, i32p),
+                                               _ptr(d, f32p), _ptr(st, u8p), C.byref(m)))
+    m = m.value
+    return det.as_dict(), (bi[:m], d[:m], st[:m])
+
+
+def decoupled_exp_pose(pose4):
+    """Transformation::exp((x, y, z, 0, 0, yaw)) as [qw,qx,qy,qz, tx,ty,tz] f64: minkindr's decoupled exp (the
+    translation is taken as it is, the rotation is about z) -- map_evaluation.cpp:155-159.  Formed in f64; the library
+    rounds it to f32, as gpu_map_evaluation.h does."""
+    x, y, z, yaw = (float(v) for v in pose4)
+    return np.array([math.cos(0.5 * yaw), 0.0, 0.0, math.sin(0.5 * yaw), x, y, z])
+
+
+def pose7_inverse(T):
+    """T.inverse() of [qw,qx,qy,qz, tx,ty,tz] (f64): conjugate rotation, translation -(q^-1 t)."""
+    T = np.asarray(T, np.float64)
+    w, v = T[0], -T[1:4]
+    t = T[4:7]
+    uv = 2.0 * np.cross(v, t)
+    r = t + w * uv + np.cross(v, uv)
+    return np.concatenate([[w], v, -r])
+
+
+def map_evaluation(ctx, submaps, poses, gt_submap, align, voxel_size=None, vps=None, error_layer=False,
+                   min_voxel_weight=1.0, max_voxel_distance=0.3):
+    """MapEvaluation::evaluate (map_evaluation.cpp:59-114) on the device.  submaps / poses ([n][7]) are the collection,
+    gt_submap the ground truth (a submap holding its raw TSDF layer, identity pose).  Steps: the projected map; both
+    finished (ESDF, kVoxels points); pose4 = align(reference = projected map, reading = ground truth) -- the caller's
+    solver over a RegistrationCostFunction(reference, reading) with the reference constant at 0, as
+    alignSubmapAtoSubmapB does; the ground truth resampled by T = Transformation::exp(x, y, z, 0, 0, yaw)
+    (vgx_tsdf_layer_transform_submap) and its ESDF regenerated; evaluateLayersRmse(gt ESDF, projected ESDF,
+    kIgnoreErrorBehindTestSurface).  Returns {"details", "pose4", "T_ground_truth__reading" (= T.inverse(), [7] f64)}
+    and, with error_layer=True, "error_layer"."""
+    vs = float(voxel_size if voxel_size is not None else gt_submap.voxel_size)
+    vps = int(vps if vps is not None else gt_submap.vps)
+    proj_layer = TsdfLayer(ctx, vs, vps)
+    gt_layer = TsdfLayer(ctx, vs, vps)
+    proj = gt_t = None
+    try:
+        projected_map(ctx, submaps, poses, proj_layer)
+        proj = Submap.from_tsdf_layer(ctx, proj_layer, 1)
+        for sm in (proj, gt_submap):       # finishSubmap()
+            sm.generate_esdf()
+            sm.extract_voxel_points(min_voxel_weight, max_voxel_distance)
+        pose4 = np.asarray(align(proj, gt_submap), np.float64).reshape(4)
+        T = decoupled_exp_pose(pose4)
+        gt_layer.transform_submap(gt_submap, T)           # transformSubmap(T): transformLayer, then finishSubmap()
+        gt_t = Submap.from_tsdf_layer(ctx, gt_layer, int(ctx.lib.vgx_submap_id(gt_submap.h)))
+        gt_t.generate_esdf()
+        res = evaluate_layers_rmse(gt_t, proj, EVAL_LAYER_ESDF, EVAL_IGNORE_BEHIND_TEST, error_layer)
+        out = {"pose4": pose4, "T_ground_truth__reading": pose7_inverse(T)}
+        if error_layer:
+            out["details"], out["error_layer"] = res
+        else:
+            out["details"] = res
+        return out
+    finally:
+        for o in (gt_t, proj, gt_layer, proj_layer):
+            if o is not None:
+                o.destroy()
 
 
 class Mesh:

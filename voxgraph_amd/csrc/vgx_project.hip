@@ -11,6 +11,8 @@
 //   4. one workgroup per target block (project_merge_kernel): the block's voxels in registers, every candidate submap
 //      interpolated at every voxel centre and merged if any voxel interpolated; stored (and allocated) only if some
 //      submap contributed.  No atomics on voxels: the result does not depend on scheduling.
+// voxblox::transformLayer (vgx_tsdf_layer_transform_submap) is the same passes with n = 1 into an empty layer; only step 4
+// differs (COPY: the interpolated voxel is stored as it is, not merged).
 #include <cmath>
 #include <string>
 #include <vector>
@@ -143,7 +145,9 @@ __global__ __launch_bounds__(256) void segment_heads_kernel(const unsigned long 
 // One workgroup per target block: its existing voxels (or the default voxel) in registers, merged with every candidate
 // submap in array order.  PER voxels per thread, VPS^3 / PER threads: 4 x 1024 at vps = 16 (16 x 256 kept 253 VGPRs
 // live -- the unrolled gathers and divisions of 16 voxels -- one wave per SIMD), 2 x 256 at vps = 8.
-template <int VPS, int PER>
+// COPY (transformLayer): the layer is empty and each target has one candidate submap; an interpolated voxel is stored as
+// {d, w}, every other voxel of a kept block as (0, 0) -- not the merge, whose (d*w + 0*0) / w need not round back to d.
+template <int VPS, int PER, bool COPY>
 __global__ __launch_bounds__(VPS * VPS * VPS / PER) void project_merge_kernel(const unsigned long long* __restrict__ keys,
                                                                               const uint32_t* __restrict__ seg_start, uint32_t n_pairs,
                                                                               const ProjectSrc* __restrict__ src, TsdfLayerDev L,
@@ -200,6 +204,15 @@ __global__ __launch_bounds__(VPS * VPS * VPS / PER) void project_merge_kernel(co
     }
     if (__syncthreads_or(ok != 0)) {
       contributed = true;
+      if (COPY) {
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+          const bool hit = (ok >> k) & 1u;
+          d[k] = hit ? sd[k] : 0.0f;
+          w[k] = hit ? sw[k] : 0.0f;
+        }
+        continue;
+      }
       // mergeVoxelAIntoVoxelB(A = the interpolated voxel or the default one, B = the layer's)
 #pragma unroll
       for (int k = 0; k < PER; ++k) {
@@ -233,9 +246,7 @@ using namespace vgx;
 
 namespace {
 
-const char* kFn = "vgx_tsdf_layer_merge_submaps: ";
-
-int fail(vgx_ctx ctx, int code, const std::string& msg) { return set_error(ctx, code, kFn + msg); }
+int fail_fn(vgx_ctx ctx, int code, const char* fn, const std::string& msg) { return set_error(ctx, code, fn + msg); }
 
 // T.inverse() in f32 as kindr forms it: conjugate rotation, translation -(q^-1 t)
 void inverse_pose(const float q[4], const float t[3], float qi[4], float ti[3]) {
@@ -249,10 +260,11 @@ void inverse_pose(const float q[4], const float t[3], float qi[4], float ti[3]) 
   for (int a = 0; a < 3; ++a) ti[a] = -r[a];
 }
 
-}  // namespace
-
-extern "C" int vgx_tsdf_layer_merge_submaps(vgx_tsdf_layer L, int32_t n, const vgx_submap* submaps, const float* T_L_S,
-                                            int64_t* n_blocks_out) {
+// vgx_tsdf_layer_merge_submaps (copy = false) and vgx_tsdf_layer_transform_submap (copy = true, n = 1): one pair build,
+// one sort, one reservation; the copy additionally refuses a layer that is not empty
+int project_submaps(vgx_tsdf_layer L, int32_t n, const vgx_submap* submaps, const float* T_L_S, int64_t* n_blocks_out,
+                    bool copy, const char* kFn) {
+  auto fail = [kFn](vgx_ctx c, int code, const std::string& msg) { return fail_fn(c, code, kFn, msg); };
   if (!L) return VGX_ERR_INVALID;
   vgx_ctx ctx = L->ctx;
   if (n < 0) return fail(ctx, VGX_ERR_INVALID, "n < 0");
@@ -277,6 +289,11 @@ extern "C" int vgx_tsdf_layer_merge_submaps(vgx_tsdf_layer L, int32_t n, const v
   VGX_HIP(ctx, hipSetDevice(ctx->device));
   int32_t nb_now = 0;
   unsigned long long dropped = 0;
+  if (copy) {
+    int rc = tsdf_read_stats(L, &nb_now, &dropped);
+    if (rc != VGX_OK) return rc;
+    if (nb_now != 0) return fail(ctx, VGX_ERR_INVALID, "the layer is not empty (transformLayer writes into an empty layer)");
+  }
   if (n == 0) {
     if (n_blocks_out) {
       int rc = tsdf_read_stats(L, &nb_now, &dropped);
@@ -444,12 +461,10 @@ extern "C" int vgx_tsdf_layer_merge_submaps(vgx_tsdf_layer L, int32_t n, const v
   int rc = tsdf_reserve_blocks(L, blo, hi3, (int64_t)n_seg);
   if (rc != VGX_OK) return rc;
   if (n_seg > 0) {
-    if (vps == 16)
-      hipLaunchKernelGGL((project_merge_kernel<16, 4>), dim3(n_seg), dim3(1024), 0, st, d_sorted.as<unsigned long long>(),
-                         d_seg.as<uint32_t>(), n_pairs, d_src.as<ProjectSrc>(), L->dev, box_lo3, box_dim3, pos_bits);
-    else
-      hipLaunchKernelGGL((project_merge_kernel<8, 2>), dim3(n_seg), dim3(256), 0, st, d_sorted.as<unsigned long long>(),
-                         d_seg.as<uint32_t>(), n_pairs, d_src.as<ProjectSrc>(), L->dev, box_lo3, box_dim3, pos_bits);
+    auto kernel = vps == 16 ? (copy ? project_merge_kernel<16, 4, true> : project_merge_kernel<16, 4, false>)
+                            : (copy ? project_merge_kernel<8, 2, true> : project_merge_kernel<8, 2, false>);
+    hipLaunchKernelGGL(kernel, dim3(n_seg), dim3(vps == 16 ? 1024 : 256), 0, st, d_sorted.as<unsigned long long>(),
+                       d_seg.as<uint32_t>(), n_pairs, d_src.as<ProjectSrc>(), L->dev, box_lo3, box_dim3, pos_bits);
     VGX_HIP(ctx, hipGetLastError());
   }
   // the sources have been read once the stream is drained (tsdf_read_stats waits for it): the caller may destroy them
@@ -458,4 +473,17 @@ extern "C" int vgx_tsdf_layer_merge_submaps(vgx_tsdf_layer L, int32_t n, const v
   if (dropped != 0) return fail(ctx, VGX_ERR_NOMEM, std::to_string(dropped) + " voxel updates dropped (allocation failed)");
   if (n_blocks_out) *n_blocks_out = nb_now;
   return VGX_OK;
+}
+
+}  // namespace
+
+extern "C" int vgx_tsdf_layer_merge_submaps(vgx_tsdf_layer L, int32_t n, const vgx_submap* submaps, const float* T_L_S,
+                                            int64_t* n_blocks_out) {
+  return project_submaps(L, n, submaps, T_L_S, n_blocks_out, false, "vgx_tsdf_layer_merge_submaps: ");
+}
+
+extern "C" int vgx_tsdf_layer_transform_submap(vgx_tsdf_layer L, vgx_submap submap, const float T_L_S[7], int64_t* n_blocks_out) {
+  if (!L) return VGX_ERR_INVALID;
+  if (!submap || !T_L_S) return set_error(L->ctx, VGX_ERR_INVALID, "vgx_tsdf_layer_transform_submap: NULL submap / T_L_S");
+  return project_submaps(L, 1, &submap, T_L_S, n_blocks_out, true, "vgx_tsdf_layer_transform_submap: ");
 }
