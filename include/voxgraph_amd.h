@@ -810,12 +810,52 @@ VGX_API int vgx_mesh_stats(vgx_mesh mesh, int32_t* n_blocks, int64_t* n_triangle
 /* block_index [nb][3], first [nb+1], vertices [T][3][3], normals [T][3]; any may be NULL */
 VGX_API int vgx_mesh_download(vgx_mesh mesh, int32_t* block_index, int64_t* first, float* vertices, float* normals);
 /* Host code: binary_little_endian PLY of the triangle soup -- vertex x y z nx ny nz (float; the triangle's normal on each
- * of its three vertices), face `list uchar int vertex_indices` = (3t, 3t+1, 3t+2).  A stated format, not byte parity
+ * of its three vertices; then red green blue alpha (uchar) when the mesh has colours), face
+ * `list uchar int vertex_indices` = (3t, 3t+1, 3t+2).  A stated format, not byte parity
  * with voxblox's outputMeshLayerAsPly. */
 VGX_API int vgx_mesh_write_ply(vgx_mesh mesh, const char* path);
 /* The triangle table the kernels use (voxgraph_amd/csrc/vgx_mc_tables.h): row c = the triangles of configuration c as
  * edge triples, -1 terminated.  Host only (no device needed). */
 VGX_API int vgx_mesh_triangle_table(int8_t out[256][16]);
+
+/* The separated mesh: cblox SubmapMesher::generateSeparatedMesh [recalled] (SubmapVisuals::publishSeparatedMesh /
+ * saveSeparatedMesh, submap_visuals.cpp:67-97) over n finished submaps, into one mesh handle.  cblox meshes each submap
+ * in its own frame (generateMesh(false, false)), colours it (colorMeshLayer), transforms it (transformMeshLayer(T_M_S))
+ * and appends it to one MeshLayer keyed by the submap-frame block index.  T_M_S [n][7] f32 {qw,qx,qy,qz, tx,ty,tz} (the
+ * collection's submaps in ascending ID order at getPose(), as the projected map takes them); rgba [n][4] u8.
+ * Rules (what the kernels, vgx_mesh.hip, and tests/separated_mesh_ref.py all follow):
+ *   triangles      per submap exactly those of vgx_submap_generate_mesh on that submap: the same cubes, visiting order,
+ *                  f32 edge interpolation, and the normal computed in the submap frame.  Only then each vertex becomes
+ *                  transform_point(q, t, p) (Eigen _transformVector, then + t; no contraction) and each normal the same
+ *                  rotation without t, not renormalised.
+ *   colour         every triangle of submap s gets rgba[s], stored once per triangle ([T][4] u8; voxblox stores it on each
+ *                  of the three vertices).  The colour is an input: the rule that picks it is not pinned (voxgraph's own
+ *                  per-submap rule for its active-submap mesh is rainbowColorMap(id / 20) [recalled]; the Python and C++
+ *                  layers default to it).
+ *   combination    every allocated block of every submap, empty mesh or not, makes or joins one output entry keyed by its
+ *                  submap-frame block index; entries in ascending (x, y, z) order (block_index has no duplicates).
+ *                  Within an entry the submaps' triangles come in ARRAY order, each submap's in its own block order.
+ *                  first [nb+1], vertices and normals: the layout of vgx_tsdf_layer_generate_mesh.
+ *   handle         afterwards vgx_mesh_has_colors reports 1; vgx_tsdf_layer_generate_mesh and vgx_submap_generate_mesh
+ *                  clear it and change in nothing else.  vgx_mesh_download_colors on a mesh without colours:
+ *                  VGX_ERR_INVALID.  vgx_mesh_download and vgx_mesh_stats are unchanged.
+ * Refused with VGX_ERR_INVALID before anything is launched (vgx_last_error says which): NULL ctx or mesh, a mesh of
+ * another context, n < 0, NULL arrays with n > 0, a NULL submap or one of another context, a released raw TSDF layer,
+ * voxel_size or voxels_per_side that differ across the submaps, a pose that is not finite or whose |q.q - 1| > 1e-4, a
+ * min_weight that is negative or not finite.  VGX_ERR_UNSUPPORTED: voxels_per_side other than 8 or 16, a union block box
+ * whose cell count x n does not fit a 64-bit key, more than 2^31 - 1 blocks in all.  n = 0 (or only empty submaps):
+ * VGX_OK, 0 blocks and a mesh with colours.  Out of device memory: VGX_ERR_NOMEM, and the handle then holds no mesh.
+ * Streams and locks: those of vgx_submap_generate_mesh (the registration stream, under the registration lock).  One pass
+ * over all n submaps: a fixed number of launches and two host synchronisations whatever n; returns with the mesh
+ * complete; values and their order do not depend on scheduling.
+ * vgx_mesh_write_ply adds `property uchar red / green / blue / alpha` after the normals when the mesh has colours (the
+ * triangle's colour on each of its vertices); a mesh without colours gives the file it always gave. */
+VGX_API int vgx_submaps_generate_separated_mesh(vgx_ctx ctx, int32_t n, const vgx_submap* submaps, const float* T_M_S,
+                                                const uint8_t* rgba, const vgx_mesh_config* cfg, vgx_mesh mesh);
+/* *has = 1 when the mesh carries colours (a separated mesh), else 0 */
+VGX_API int vgx_mesh_has_colors(vgx_mesh mesh, int32_t* has);
+/* rgba [T][4]: one colour per triangle */
+VGX_API int vgx_mesh_download_colors(vgx_mesh mesh, uint8_t* rgba);
 
 /* ---- Map evaluation: voxblox::utils::evaluateLayersRmse ------------------- */
 /* MapEvaluation::evaluate (map_evaluation.cpp:59-114) scores a map against a ground truth: projected map

@@ -212,6 +212,9 @@ SIGNATURES = {
     "vgx_mesh_download": (C.c_int, [vp, i32p, i64p, f32p, f32p]),
     "vgx_mesh_write_ply": (C.c_int, [vp, C.c_char_p]),
     "vgx_mesh_triangle_table": (C.c_int, [C.POINTER(C.c_int8)]),
+    "vgx_submaps_generate_separated_mesh": (C.c_int, [vp, C.c_int32, C.POINTER(vp), f32p, u8p, C.POINTER(MeshConfig), vp]),
+    "vgx_mesh_has_colors": (C.c_int, [vp, i32p]),
+    "vgx_mesh_download_colors": (C.c_int, [vp, u8p]),
     "vgx_map_file_open": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(vp)]),
     "vgx_map_file_close": (C.c_int, [vp]),
     "vgx_map_file_last_error": (C.c_char_p, [vp]),
@@ -1027,6 +1030,47 @@ def combined_mesh(ctx, submaps, poses, layer, mesh=None, min_weight=1e-4):
     return layer.generate_mesh(mesh, min_weight)
 
 
+DEFAULT_COLOR_CYCLE_LENGTH = 20  # cblox::kDefaultColorCycleLength [recalled]
+
+
+def rainbow_color_map(h):
+    """voxblox rainbowColorMap(h) [recalled]: an HSV blend at s = v = 1 in double, each channel truncated to uint8,
+    a = 255.  Returns [r, g, b, a] uint8."""
+    h = float(h)
+    h -= math.floor(h)
+    h *= 6.0
+    i = int(math.floor(h))
+    f = h - i
+    if not (i & 1):
+        f = 1.0 - f
+    v, m, n = 1.0, 0.0, 1.0 - f
+    rgb = {0: (v, n, m), 6: (v, n, m), 1: (n, v, m), 2: (m, v, n), 3: (m, n, v), 4: (n, m, v), 5: (v, m, n)}.get(i)
+    if rgb is None:
+        return np.array([255, 127, 127, 255], np.uint8)
+    return np.array([int(255 * c) for c in rgb] + [255], np.uint8)
+
+
+def submap_color(submap_id):
+    """voxgraph's colour of a submap's mesh: rainbowColorMap(id / kDefaultColorCycleLength)
+    (VoxgraphMapper::publishActiveSubmapMeshCallback)"""
+    return rainbow_color_map(float(submap_id) / float(DEFAULT_COLOR_CYCLE_LENGTH))
+
+
+def separated_mesh(ctx, submaps, poses, colors=None, mesh=None, min_weight=1e-4):
+    """cblox SubmapMesher::generateSeparatedMesh: every submap meshed in its own frame, coloured, moved to its pose and
+    appended into one mesh keyed by block index; the submaps in ascending vgx_submap_id order (the collection's std::map
+    order) at poses[i] ([n][7] qw,qx,qy,qz, tx,ty,tz), coloured colors[i] ([n][4] uint8; default submap_color(id)).
+    Returns the Mesh (a new one when mesh is None), which has colours."""
+    ids = [int(ctx.lib.vgx_submap_id(s.h)) for s in submaps]
+    order = sorted(range(len(submaps)), key=lambda i: ids[i])
+    poses = np.ascontiguousarray(poses, np.float32).reshape(len(submaps), 7)
+    if colors is None:
+        colors = np.array([submap_color(i) for i in ids], np.uint8).reshape(len(submaps), 4)
+    colors = np.ascontiguousarray(colors, np.uint8).reshape(len(submaps), 4)
+    mesh = mesh if mesh is not None else Mesh(ctx)
+    return mesh.generate_separated([submaps[i] for i in order], poses[order], colors[order], min_weight)
+
+
 def evaluate_layers_rmse(gt, test, layer=EVAL_LAYER_ESDF, mode=EVAL_IGNORE_BEHIND_TEST, error_layer=False):
     """voxblox::utils::evaluateLayersRmse(gt layer, test layer, mode, &details[, &error_layer]) over two finished submaps
     (vgx_evaluate_layers_rmse).  Returns the details as a dict; with error_layer=True, (details, (block_index [m][3],
@@ -1131,6 +1175,31 @@ class Mesh:
         self.ctx.check(self.ctx.lib.vgx_mesh_download(self.h, _ptr(bi, i32p), _ptr(first, i64p), _ptr(v, f32p),
                                                       _ptr(n, f32p)))
         return bi, first, v, n
+
+    def has_colors(self):
+        """True after a separated mesh (vgx_mesh_has_colors)"""
+        has = C.c_int32()
+        self.ctx.check(self.ctx.lib.vgx_mesh_has_colors(self.h, C.byref(has)))
+        return bool(has.value)
+
+    def download_colors(self):
+        """rgba [T][4] uint8, one colour per triangle (vgx_mesh_download_colors; a mesh without colours raises)"""
+        _, nt = self.stats()
+        out = np.zeros((nt, 4), np.uint8)
+        self.ctx.check(self.ctx.lib.vgx_mesh_download_colors(self.h, _ptr(out, u8p)))
+        return out
+
+    def generate_separated(self, submaps, poses, colors, min_weight=1e-4):
+        """vgx_submaps_generate_separated_mesh in ARRAY order: submaps[i] at poses[i] ([n][7] qw,qx,qy,qz, tx,ty,tz)
+        coloured colors[i] ([n][4] uint8).  Returns self."""
+        n = len(submaps)
+        arr = (vp * max(n, 1))(*[s.h for s in submaps])
+        T = np.ascontiguousarray(poses, np.float32).reshape(n, 7)
+        rgba = np.ascontiguousarray(colors, np.uint8).reshape(n, 4)
+        cfg = MeshConfig(float(min_weight))
+        self.ctx.check(self.ctx.lib.vgx_submaps_generate_separated_mesh(self.ctx.h, n, arr, _ptr(T, f32p), _ptr(rgba, u8p),
+                                                                        C.byref(cfg), self.h))
+        return self
 
     def write_ply(self, path):
         self.ctx.check(self.ctx.lib.vgx_mesh_write_ply(self.h, os.fsencode(path)))

@@ -12,11 +12,18 @@
 //
 // Semantics and deviations (no colour, no incremental meshing) are stated at vgx_tsdf_layer_generate_mesh in
 // include/voxgraph_amd.h.
+//
+// The separated mesh (SubmapVisuals::publishSeparatedMesh / saveSeparatedMesh: cblox generateSeparatedMesh) is one call
+// over the whole collection, each submap in voxgraph's colour (vgx_submaps_generate_separated_mesh):
+//
+//   voxgraph_amd::GenerateSeparatedMeshOnGpu(submap_collection, mesh_config.min_weight, &gpu_mesh);
+//   voxgraph_amd::DownloadColoredMeshLayer(gpu_mesh, &mesh_layer);
 #ifndef VOXGRAPH_AMD_CPP_GPU_MESH_H_
 #define VOXGRAPH_AMD_CPP_GPU_MESH_H_
 
 #include <voxblox/core/common.h>
 
+#include <cmath>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -52,6 +59,19 @@ class GpuMesh {
     check(vgx_mesh_download(mesh_, block_index->data(), first->data(), vertices->data(), normals->data()), "vgx_mesh_download");
   }
   void writePly(const std::string& path) const { check(vgx_mesh_write_ply(mesh_, path.c_str()), "vgx_mesh_write_ply"); }
+  bool hasColors() const {
+    int32_t has = 0;
+    check(vgx_mesh_has_colors(mesh_, &has), "vgx_mesh_has_colors");
+    return has != 0;
+  }
+  // rgba [T][4], one colour per triangle (a separated mesh; throws on a mesh without colours)
+  void downloadColors(std::vector<uint8_t>* rgba) const {
+    int32_t nb = 0;
+    int64_t nt = 0;
+    stats(&nb, &nt);
+    rgba->resize(4 * static_cast<size_t>(nt));
+    check(vgx_mesh_download_colors(mesh_, rgba->data()), "vgx_mesh_download_colors");
+  }
 
  private:
   void check(int rc, const char* what) const {
@@ -80,6 +100,80 @@ GpuMesh& GenerateCombinedMeshOnGpu(const CollectionT& collection, GpuTsdfLayer* 
   return GenerateMeshOnGpu(*gpu_layer, min_weight, mesh);
 }
 
+// voxblox rainbowColorMap [recalled]: an HSV blend at s = v = 1 in double, channels truncated to uint8, a = 255
+inline voxblox::Color RainbowColorMap(double h) {
+  h -= std::floor(h);
+  h *= 6.0;
+  const int i = static_cast<int>(std::floor(h));
+  double f = h - i;
+  if (!(i & 1)) f = 1.0 - f;
+  const double v = 1.0, m = 0.0, n = 1.0 - f;
+  double r = 255, g = 127, b = 127;
+  switch (i) {
+    case 6:
+    case 0: r = 255 * v; g = 255 * n; b = 255 * m; break;
+    case 1: r = 255 * n; g = 255 * v; b = 255 * m; break;
+    case 2: r = 255 * m; g = 255 * v; b = 255 * n; break;
+    case 3: r = 255 * m; g = 255 * n; b = 255 * v; break;
+    case 4: r = 255 * n; g = 255 * m; b = 255 * v; break;
+    case 5: r = 255 * v; g = 255 * m; b = 255 * n; break;
+    default: break;
+  }
+  return voxblox::Color(static_cast<uint8_t>(r), static_cast<uint8_t>(g), static_cast<uint8_t>(b), 255);
+}
+
+constexpr int kDefaultColorCycleLength = 20;  // cblox::kDefaultColorCycleLength [recalled]
+
+// voxgraph's colour of a submap's mesh (VoxgraphMapper::publishActiveSubmapMeshCallback)
+inline voxblox::Color SubmapColor(int submap_id) {
+  return RainbowColorMap(static_cast<double>(submap_id) / static_cast<double>(kDefaultColorCycleLength));
+}
+
+// cblox SubmapMesher::generateSeparatedMesh: the collection's submaps in ascending ID order at getPose(), submap ID
+// coloured colors[k] (k its rank in that order), meshed in one call (vgx_submaps_generate_separated_mesh)
+template <typename CollectionT>
+GpuMesh& GenerateSeparatedMeshOnGpu(const CollectionT& collection, const std::vector<voxblox::Color>& colors, float min_weight,
+                                    GpuMesh* mesh) {
+  if (!mesh) throw std::invalid_argument("GenerateSeparatedMeshOnGpu: mesh == nullptr");
+  GpuSubmapRegistry& registry = GpuSubmapRegistry::instance();
+  std::vector<vgx_submap> handles;
+  std::vector<float> T_M_S;
+  std::vector<uint8_t> rgba;
+  for (const auto id : collection.getIDs()) {  // cblox keeps its submaps in a std::map: ascending IDs
+    const auto submap_ptr = collection.getSubmapConstPtr(id);
+    handles.push_back(registry.handleOf(submap_ptr));
+    const auto& pose = submap_ptr->getPose();
+    const auto& q = pose.getRotation();
+    const auto& t = pose.getPosition();
+    const float T[7] = {static_cast<float>(q.w()), static_cast<float>(q.x()), static_cast<float>(q.y()),
+                        static_cast<float>(q.z()), static_cast<float>(t[0]),  static_cast<float>(t[1]),
+                        static_cast<float>(t[2])};
+    T_M_S.insert(T_M_S.end(), T, T + 7);
+  }
+  if (colors.size() != handles.size()) throw std::invalid_argument("GenerateSeparatedMeshOnGpu: one colour per submap");
+  for (const voxblox::Color& c : colors) {
+    rgba.push_back(c.r);
+    rgba.push_back(c.g);
+    rgba.push_back(c.b);
+    rgba.push_back(c.a);
+  }
+  vgx_mesh_config cfg;
+  vgx_mesh_config_default(&cfg);
+  cfg.min_weight = min_weight;
+  if (vgx_submaps_generate_separated_mesh(registry.context(), static_cast<int32_t>(handles.size()), handles.data(),
+                                          T_M_S.data(), rgba.data(), &cfg, mesh->handle()) != VGX_OK)
+    throw std::runtime_error(std::string("vgx_submaps_generate_separated_mesh: ") + mesh->last_error());
+  return *mesh;
+}
+
+// ... with voxgraph's colours (SubmapColor of each ID)
+template <typename CollectionT>
+GpuMesh& GenerateSeparatedMeshOnGpu(const CollectionT& collection, float min_weight, GpuMesh* mesh) {
+  std::vector<voxblox::Color> colors;
+  for (const auto id : collection.getIDs()) colors.push_back(SubmapColor(static_cast<int>(id)));
+  return GenerateSeparatedMeshOnGpu(collection, colors, min_weight, mesh);
+}
+
 // Fills a voxblox-shaped MeshLayer (allocateMeshPtrByIndex(BlockIndex) returning a mesh pointer with vertices, normals
 // and indices): one mesh per allocated TSDF block, possibly empty, each holding its triangle soup -- three vertices per
 // triangle, the triangle's normal on each, indices 0..3n-1.  No colours (the GPU mesh has none).
@@ -106,6 +200,41 @@ void DownloadMeshLayer(const GpuMesh& gpu_mesh, MeshLayerT* mesh_layer) {
         mesh->indices.push_back(static_cast<int>(mesh->vertices.size()));
         mesh->vertices.push_back(voxblox::Point(p[0], p[1], p[2]));
         mesh->normals.push_back(normal);
+      }
+    }
+  }
+}
+
+// DownloadMeshLayer plus the colours of a separated mesh: mesh->colors gets the triangle's colour on each of its three
+// vertices (voxblox's layout).  The MeshLayer's mesh type needs a `colors` vector of voxblox::Color.
+template <typename MeshLayerT>
+void DownloadColoredMeshLayer(const GpuMesh& gpu_mesh, MeshLayerT* mesh_layer) {
+  if (!mesh_layer) throw std::invalid_argument("DownloadColoredMeshLayer: mesh_layer == nullptr");
+  std::vector<int32_t> bi;
+  std::vector<int64_t> first;
+  std::vector<float> v, n;
+  std::vector<uint8_t> rgba;
+  gpu_mesh.download(&bi, &first, &v, &n);
+  gpu_mesh.downloadColors(&rgba);
+  for (size_t b = 0; b + 1 < first.size(); ++b) {
+    voxblox::BlockIndex index;
+    index[0] = bi[3 * b];
+    index[1] = bi[3 * b + 1];
+    index[2] = bi[3 * b + 2];
+    auto mesh = mesh_layer->allocateMeshPtrByIndex(index);
+    mesh->vertices.clear();
+    mesh->normals.clear();
+    mesh->colors.clear();
+    mesh->indices.clear();
+    for (int64_t t = first[b]; t < first[b + 1]; ++t) {
+      const voxblox::Point normal(n[3 * t], n[3 * t + 1], n[3 * t + 2]);
+      const voxblox::Color color(rgba[4 * t], rgba[4 * t + 1], rgba[4 * t + 2], rgba[4 * t + 3]);
+      for (int q = 0; q < 3; ++q) {
+        const float* p = &v[9 * t + 3 * q];
+        mesh->indices.push_back(static_cast<int>(mesh->vertices.size()));
+        mesh->vertices.push_back(voxblox::Point(p[0], p[1], p[2]));
+        mesh->normals.push_back(normal);
+        mesh->colors.push_back(color);
       }
     }
   }

@@ -10,6 +10,10 @@
 //   4. emit    one workgroup per block again: the cubes in voxblox's visiting order, a workgroup-wide exclusive scan of
 //              their counts per round of 256 cubes, each cube writing its triangles at its own offset.  No atomics on the
 //              output: values and order do not depend on scheduling.
+// The separated mesh (vgx_submaps_generate_separated_mesh) runs the same count and emit over every (submap,
+// block) entry of n submaps at once: keys union_cell(block_index) * n + s, one sort, count (plus a flag where the block
+// index changes), two scans, the unique blocks, one read-back, then emit with the submap's pose and colour applied just
+// before the stores.  A fixed number of launches and two host synchronisations, whatever n.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -156,6 +160,18 @@ __device__ __forceinline__ void visit(int r, int& x, int& y, int& z) {
   x = r % M;
 }
 
+// this thread's share of the block's triangle count (cubes r = threadIdx.x, + 256, ...)
+template <int VPS>
+__device__ __forceinline__ int thread_triangle_count(const MeshLds<VPS>& m) {
+  int cnt = 0;
+  for (int r = threadIdx.x; r < VPS * VPS * VPS; r += kMeshThreads) {
+    float sdf[8];
+    const int cfg = cube_config<VPS>(m, r % VPS, (r / VPS) % VPS, r / (VPS * VPS), sdf);
+    if (cfg >= 0) cnt += c_mc_count.n[cfg];
+  }
+  return cnt;
+}
+
 template <int VPS, bool PACKED>
 __global__ __launch_bounds__(kMeshThreads) void mesh_count_kernel(MeshSrc s, const int32_t* __restrict__ order, float min_weight,
                                                                    int64_t* __restrict__ counts, int32_t* __restrict__ out_bi) {
@@ -165,13 +181,7 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_count_kernel(MeshSrc s, con
   const int32_t* bi = s.block_index + 3 * (size_t)slot;
   if (threadIdx.x == 0) total = 0;
   stage_corners<VPS, PACKED>(s, slot, bi, min_weight, m);
-  int cnt = 0;
-  for (int r = threadIdx.x; r < VPS * VPS * VPS; r += kMeshThreads) {
-    float sdf[8];
-    const int cfg = cube_config<VPS>(m, r % VPS, (r / VPS) % VPS, r / (VPS * VPS), sdf);
-    if (cfg >= 0) cnt += c_mc_count.n[cfg];
-  }
-  atomicAdd(&total, cnt);  // (integer sum in LDS: exact in any order)
+  atomicAdd(&total, thread_triangle_count<VPS>(m));  // (integer sum in LDS: exact in any order)
   __syncthreads();
   if (threadIdx.x == 0) {
     counts[blockIdx.x] = total;
@@ -202,17 +212,30 @@ __device__ __forceinline__ void cube_edge_vertex(int e, const float base[3], flo
   edge_vertex(pa, pb, sdf[a], sdf[b], out);
 }
 
-template <int VPS, bool PACKED>
-__global__ __launch_bounds__(kMeshThreads) void mesh_emit_kernel(MeshSrc s, const int32_t* __restrict__ order, float min_weight,
-                                                                  const int64_t* __restrict__ first, float* __restrict__ vertices,
-                                                                  float* __restrict__ normals) {
+// a rigid transform applied just before the stores (the separated mesh), or none
+struct EmitPose {
+  float q[4], t[3];  // T_M_S {w, x, y, z}, t
+  uint32_t rgba;     // the triangle's colour, bytes r g b a
+  uint32_t* colors;  // [T]
+};
+
+// Eigen _transformVector without the translation: transform_point's formula up to its `+ t`
+__device__ __forceinline__ void rotate_vector(const float q[4], float px, float py, float pz, float& gx, float& gy, float& gz) {
+  float uvx = q[2] * pz - q[3] * py, uvy = q[3] * px - q[1] * pz, uvz = q[1] * py - q[2] * px;
+  uvx += uvx; uvy += uvy; uvz += uvz;
+  const float ccx = q[2] * uvz - q[3] * uvy, ccy = q[3] * uvx - q[1] * uvz, ccz = q[1] * uvy - q[2] * uvx;
+  gx = (px + q[0] * uvx) + ccx;
+  gy = (py + q[0] * uvy) + ccy;
+  gz = (pz + q[0] * uvz) + ccz;
+}
+
+// One block's triangles at [base, end), its corners staged into m: the cubes in visiting order, a workgroup-wide exclusive
+// scan of their counts per round of 256 cubes, each cube writing its triangles at its own offset.  POSED: each vertex
+// through transform_point(T), the normal through the rotation alone (not renormalised), the colour stored per triangle.
+template <int VPS, bool POSED>
+__device__ __forceinline__ void emit_block(const MeshSrc& s, const int32_t* bi, int64_t base, int64_t end, MeshLds<VPS>& m,
+                                           float* __restrict__ vertices, float* __restrict__ normals, const EmitPose& T) {
   constexpr int NW = kMeshThreads / 64;
-  __shared__ MeshLds<VPS> m;
-  const int slot = order[blockIdx.x];
-  const int32_t* bi = s.block_index + 3 * (size_t)slot;
-  stage_corners<VPS, PACKED>(s, slot, bi, min_weight, m);
-  const int64_t end = first[blockIdx.x + 1];
-  int64_t base = first[blockIdx.x];
   const float vs = s.voxel_size, bs = (float)VPS * vs;
   const float ox = (float)bi[0] * bs, oy = (float)bi[1] * bs, oz = (float)bi[2] * bs;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -258,6 +281,14 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_emit_kernel(MeshSrc s, cons
           ny = ny / len;
           nz = nz / len;
         }
+        if (POSED) {
+#pragma unroll
+          for (int q = 0; q < 3; ++q)
+            transform_point(T.q[0], T.q[1], T.q[2], T.q[3], T.t[0], T.t[1], T.t[2], p[q][0], p[q][1], p[q][2], p[q][0], p[q][1],
+                            p[q][2]);
+          rotate_vector(T.q, nx, ny, nz, nx, ny, nz);
+          T.colors[at] = T.rgba;
+        }
         float* v = vertices + 9 * at;
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
@@ -272,6 +303,124 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_emit_kernel(MeshSrc s, cons
     }
     base += all;
   }
+}
+
+template <int VPS, bool PACKED>
+__global__ __launch_bounds__(kMeshThreads) void mesh_emit_kernel(MeshSrc s, const int32_t* __restrict__ order, float min_weight,
+                                                                  const int64_t* __restrict__ first, float* __restrict__ vertices,
+                                                                  float* __restrict__ normals) {
+  __shared__ MeshLds<VPS> m;
+  const int slot = order[blockIdx.x];
+  const int32_t* bi = s.block_index + 3 * (size_t)slot;
+  stage_corners<VPS, PACKED>(s, slot, bi, min_weight, m);
+  const int64_t end = first[blockIdx.x + 1];
+  const int64_t base = first[blockIdx.x];
+  const EmitPose none{};
+  emit_block<VPS, false>(s, bi, base, end, m, vertices, normals, none);
+}
+
+// ---- the separated mesh (vgx_submaps_generate_separated_mesh): n submaps in one pass -------------------------------
+// One entry per (submap, block), keyed by union_cell(block_index) * n + s: sorted, a block index's entries are
+// consecutive and in array order.  DESIGN.md 13.
+
+// one submap: its raw layer, its pose and colour, its first entry
+struct SepSrc {
+  MeshSrc m;
+  EmitPose pose;  // (colors is the same for every submap: set on the device side of the copy)
+  int64_t entry0;
+};
+
+// the union of the submaps' block tables
+struct SepBox {
+  long long lo[3];
+  unsigned long long dim[3];
+};
+
+__global__ __launch_bounds__(256) void sep_keys_kernel(const SepSrc* __restrict__ src, int32_t n_src, int64_t n_entries, SepBox box,
+                                                       unsigned long long* __restrict__ keys, int32_t* __restrict__ slots) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= n_entries) return;
+  int a = 0, b = n_src;  // the last submap with entry0 <= g (an empty submap shares its entry0 with the next one)
+  while (b - a > 1) {
+    const int m = (a + b) >> 1;
+    if (src[m].entry0 <= g) a = m; else b = m;
+  }
+  const int32_t slot = (int32_t)(g - src[a].entry0);
+  const int32_t* bi = src[a].m.block_index + 3 * (size_t)slot;
+  const unsigned long long cell =
+      ((unsigned long long)((long long)bi[0] - box.lo[0]) * box.dim[1] + (unsigned long long)((long long)bi[1] - box.lo[1])) * box.dim[2] +
+      (unsigned long long)((long long)bi[2] - box.lo[2]);
+  keys[g] = cell * (unsigned long long)n_src + (unsigned long long)a;
+  slots[g] = slot;
+}
+
+// one workgroup per entry in key order: its triangle count, and whether it starts a new block index
+template <int VPS>
+__global__ __launch_bounds__(kMeshThreads) void sep_count_kernel(const SepSrc* __restrict__ src, unsigned long long n_src,
+                                                                  const unsigned long long* __restrict__ keys,
+                                                                  const int32_t* __restrict__ slots, float min_weight,
+                                                                  int64_t* __restrict__ counts, int32_t* __restrict__ heads) {
+  __shared__ MeshLds<VPS> m;
+  __shared__ int total;
+  const unsigned long long key = keys[blockIdx.x];
+  const MeshSrc s = src[key % n_src].m;  // (uniform: one submap per workgroup)
+  const int slot = slots[blockIdx.x];
+  const int32_t* bi = s.block_index + 3 * (size_t)slot;
+  if (threadIdx.x == 0) total = 0;
+  stage_corners<VPS, false>(s, slot, bi, min_weight, m);
+  atomicAdd(&total, thread_triangle_count<VPS>(m));  // (integer sum in LDS: exact in any order)
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    counts[blockIdx.x] = total;
+    heads[blockIdx.x] = (blockIdx.x == 0 || keys[blockIdx.x - 1] / n_src != key / n_src) ? 1 : 0;
+  }
+}
+
+// the block index of each head entry and the first triangle of its block; the last entry also writes first[nb] and
+// tail = {triangles, blocks}
+__global__ __launch_bounds__(256) void sep_unique_kernel(const SepSrc* __restrict__ src, unsigned long long n_src,
+                                                         const unsigned long long* __restrict__ keys,
+                                                         const int32_t* __restrict__ slots, int32_t n_entries,
+                                                         const int32_t* __restrict__ heads, const int32_t* __restrict__ uid,
+                                                         const int64_t* __restrict__ efirst, int32_t* __restrict__ out_bi,
+                                                         int64_t* __restrict__ out_first, int64_t* __restrict__ tail) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_entries) return;
+  if (heads[i]) {
+    const int u = uid[i] - 1;
+    const int32_t* bi = src[keys[i] % n_src].m.block_index + 3 * (size_t)slots[i];
+    out_bi[3 * (size_t)u + 0] = bi[0];
+    out_bi[3 * (size_t)u + 1] = bi[1];
+    out_bi[3 * (size_t)u + 2] = bi[2];
+    out_first[u] = efirst[i];
+  }
+  if (i == n_entries - 1) {
+    out_first[uid[i]] = efirst[n_entries];
+    tail[0] = efirst[n_entries];
+    tail[1] = uid[i];
+  }
+}
+
+// one workgroup per entry in key order: its triangles at [efirst[i], efirst[i+1]), posed and coloured
+template <int VPS>
+// (__launch_bounds__' second argument: at least 6 waves per SIMD, the LDS bound of MeshLds<16> -- no spill results)
+__global__ __launch_bounds__(kMeshThreads, 6) void sep_emit_kernel(const SepSrc* __restrict__ src, unsigned long long n_src,
+                                                                 const unsigned long long* __restrict__ keys,
+                                                                 const int32_t* __restrict__ slots, float min_weight,
+                                                                 const int64_t* __restrict__ efirst, float* __restrict__ vertices,
+                                                                 float* __restrict__ normals, uint32_t* __restrict__ colors) {
+  __shared__ MeshLds<VPS> m;
+  const SepSrc& d = src[keys[blockIdx.x] % n_src];  // (uniform: one submap per workgroup)
+  const MeshSrc s = d.m;
+  EmitPose T = d.pose;
+  T.colors = colors;
+  const int64_t end = efirst[blockIdx.x + 1];
+  const int64_t base = efirst[blockIdx.x];
+  if (base == end) return;  // (no triangles: nothing to stage; uniform across the workgroup, before any barrier)
+  const int slot = slots[blockIdx.x];
+  const int32_t* bi = s.block_index + 3 * (size_t)slot;
+  stage_corners<VPS, false>(s, slot, bi, min_weight, m);
+  emit_block<VPS, true>(s, bi, base, end, m, vertices, normals, T);
 }
 
 }  // namespace vgx
@@ -295,6 +444,18 @@ struct vgx_mesh_s {
   void* d_tmp = nullptr;
   size_t tmp_bytes = 0;
   int64_t block_cap = 0, tri_cap = 0;
+  // the separated mesh: colours [tri_cap2] (one per triangle), per-entry scratch beside the block arrays, descriptors
+  bool has_colors = false;
+  uint32_t* d_colors = nullptr;
+  int64_t color_cap = 0;
+  int64_t* d_efirst = nullptr;  // [entry_cap + 1]
+  int32_t* d_heads = nullptr;   // [entry_cap]
+  int32_t* d_uid = nullptr;     // [entry_cap]
+  int64_t* d_tail = nullptr;    // {triangles, blocks}
+  int64_t entry_cap = 0;
+  std::vector<SepSrc> h_src;    // (the host side of the descriptor copy: outlives it)
+  SepSrc* d_src = nullptr;
+  int64_t src_cap = 0;
 };
 
 namespace {
@@ -354,6 +515,65 @@ int ensure_blocks(vgx_mesh M, int64_t nb, size_t tmp_bytes) {
     }
     M->tmp_bytes = tmp_bytes;
   }
+  return VGX_OK;
+}
+
+void free_separated(vgx_mesh M) {
+  void* ps[] = {M->d_colors, M->d_efirst, M->d_heads, M->d_uid, M->d_tail, M->d_src};
+  for (void* p : ps)
+    if (p) (void)hipFree(p);
+  M->d_colors = nullptr;
+  M->d_efirst = nullptr;
+  M->d_heads = M->d_uid = nullptr;
+  M->d_tail = nullptr;
+  M->d_src = nullptr;
+  M->color_cap = M->entry_cap = M->src_cap = 0;
+}
+
+// per-entry scratch and descriptors (the block arrays come from ensure_blocks)
+int ensure_entries(vgx_mesh M, int64_t ne, int64_t n_src) {
+  if (ne > M->entry_cap) {
+    for (void* p : {(void*)M->d_efirst, (void*)M->d_heads, (void*)M->d_uid, (void*)M->d_tail})
+      if (p) (void)hipFree(p);
+    M->d_efirst = nullptr;
+    M->d_heads = M->d_uid = nullptr;
+    M->d_tail = nullptr;
+    M->entry_cap = 0;
+    const int64_t cap = std::max<int64_t>(ne, 1024);
+    hipError_t e = hipMalloc(&M->d_efirst, (size_t)(cap + 1) * 8);
+    if (e == hipSuccess) e = hipMalloc(&M->d_heads, (size_t)cap * 4);
+    if (e == hipSuccess) e = hipMalloc(&M->d_uid, (size_t)cap * 4);
+    if (e == hipSuccess) e = hipMalloc(&M->d_tail, 2 * sizeof(int64_t));
+    if (e != hipSuccess) {
+      free_separated(M);
+      return alloc_error(M->ctx, e, "entry arrays");
+    }
+    M->entry_cap = cap;
+  }
+  if (n_src > M->src_cap) {
+    if (M->d_src) (void)hipFree(M->d_src);
+    M->d_src = nullptr;
+    M->src_cap = 0;
+    const int64_t cap = std::max<int64_t>(n_src, 64);
+    const hipError_t e = hipMalloc(&M->d_src, (size_t)cap * sizeof(SepSrc));
+    if (e != hipSuccess) {
+      free_separated(M);
+      return alloc_error(M->ctx, e, "submap descriptors");
+    }
+    M->src_cap = cap;
+  }
+  return VGX_OK;
+}
+
+int ensure_colors(vgx_mesh M, int64_t nt) {
+  if (nt <= M->color_cap) return VGX_OK;
+  if (M->d_colors) (void)hipFree(M->d_colors);
+  M->d_colors = nullptr;
+  M->color_cap = 0;
+  const int64_t cap = std::max<int64_t>(nt + nt / 4, 4096);
+  const hipError_t e = hipMalloc(&M->d_colors, (size_t)cap * 4);
+  if (e != hipSuccess) return alloc_error(M->ctx, e, "colours");
+  M->color_cap = cap;
   return VGX_OK;
 }
 
@@ -431,6 +651,66 @@ int generate(vgx_ctx ctx, hipStream_t st, const MeshSrc& s, int vps, int32_t nb,
   return VGX_OK;
 }
 
+template <int VPS>
+hipError_t launch_separated(bool emit, hipStream_t st, int32_t ne, vgx_mesh M, unsigned long long n_src, float mw) {
+  if (emit)
+    hipLaunchKernelGGL(sep_emit_kernel<VPS>, dim3((unsigned)ne), dim3(kMeshThreads), 0, st, M->d_src, n_src, M->d_keys[1],
+                       M->d_slots[1], mw, M->d_efirst, M->d_vertices, M->d_normals, M->d_colors);
+  else
+    hipLaunchKernelGGL(sep_count_kernel<VPS>, dim3((unsigned)ne), dim3(kMeshThreads), 0, st, M->d_src, n_src, M->d_keys[1],
+                       M->d_slots[1], mw, M->d_counts, M->d_heads);
+  return hipGetLastError();
+}
+
+// the separated passes over ne > 0 entries, on `st` (the caller holds the registration lock and M->mu, has reset M's
+// stats and filled M->h_src)
+int generate_separated(vgx_ctx ctx, hipStream_t st, int vps, int32_t ne, const SepBox& box, unsigned end_bit, float mw,
+                       vgx_mesh M) {
+  const int32_t n = (int32_t)M->h_src.size();
+  size_t sort_bytes = 0, scan_bytes = 0, flag_bytes = 0;
+  VGX_HIP(ctx, rocprim::radix_sort_pairs(nullptr, sort_bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                                         (int32_t*)nullptr, (int32_t*)nullptr, (size_t)ne, 0u, end_bit, st));
+  VGX_HIP(ctx, rocprim::inclusive_scan(nullptr, scan_bytes, (int64_t*)nullptr, (int64_t*)nullptr, (size_t)ne,
+                                       rocprim::plus<int64_t>(), st));
+  VGX_HIP(ctx, rocprim::inclusive_scan(nullptr, flag_bytes, (int32_t*)nullptr, (int32_t*)nullptr, (size_t)ne,
+                                       rocprim::plus<int32_t>(), st));
+  int rc = ensure_blocks(M, ne, std::max<size_t>(std::max(std::max(sort_bytes, scan_bytes), flag_bytes), 4));
+  if (rc == VGX_OK) rc = ensure_entries(M, ne, n);
+  if (rc != VGX_OK) return rc;
+  // 1. descriptors, keys, one sort
+  VGX_HIP(ctx, hipMemcpyAsync(M->d_src, M->h_src.data(), M->h_src.size() * sizeof(SepSrc), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(sep_keys_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, M->d_src, n, (int64_t)ne, box, M->d_keys[0],
+                     M->d_slots[0]);
+  VGX_HIP(ctx, hipGetLastError());
+  VGX_HIP(ctx, rocprim::radix_sort_pairs(M->d_tmp, sort_bytes, M->d_keys[0], M->d_keys[1], M->d_slots[0], M->d_slots[1], (size_t)ne,
+                                         0u, end_bit, st));
+  // 2. count, 3. scan the counts and the block heads; the unique blocks and their first triangles
+  VGX_HIP(ctx, vps == 16 ? launch_separated<16>(false, st, ne, M, (unsigned long long)n, mw)
+                         : launch_separated<8>(false, st, ne, M, (unsigned long long)n, mw));
+  VGX_HIP(ctx, hipMemsetAsync(M->d_efirst, 0, sizeof(int64_t), st));
+  VGX_HIP(ctx, rocprim::inclusive_scan(M->d_tmp, scan_bytes, M->d_counts, M->d_efirst + 1, (size_t)ne, rocprim::plus<int64_t>(), st));
+  VGX_HIP(ctx, rocprim::inclusive_scan(M->d_tmp, flag_bytes, M->d_heads, M->d_uid, (size_t)ne, rocprim::plus<int32_t>(), st));
+  hipLaunchKernelGGL(sep_unique_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, M->d_src, (unsigned long long)n,
+                     M->d_keys[1], M->d_slots[1], ne, M->d_heads, M->d_uid, M->d_efirst, M->d_block_index, M->d_first, M->d_tail);
+  VGX_HIP(ctx, hipGetLastError());
+  int64_t tail[2] = {0, 0};
+  VGX_HIP(ctx, hipMemcpyAsync(tail, M->d_tail, sizeof(tail), hipMemcpyDeviceToHost, st));
+  VGX_HIP(ctx, hipStreamSynchronize(st));
+  // 4. emit
+  const int64_t total = tail[0];
+  rc = ensure_tris(M, total);
+  if (rc == VGX_OK) rc = ensure_colors(M, total);
+  if (rc != VGX_OK) return rc;
+  if (total > 0) {
+    VGX_HIP(ctx, vps == 16 ? launch_separated<16>(true, st, ne, M, (unsigned long long)n, mw)
+                           : launch_separated<8>(true, st, ne, M, (unsigned long long)n, mw));
+    VGX_HIP(ctx, hipStreamSynchronize(st));
+  }
+  M->n_blocks = (int32_t)tail[1];
+  M->n_tris = total;
+  return VGX_OK;
+}
+
 // shared refusals; *mw the threshold to use
 int check_args(vgx_ctx ctx, const vgx_mesh_config* cfg, vgx_mesh M, const char* fn, float* mw) {
   vgx_mesh_config c;
@@ -465,6 +745,7 @@ int vgx_mesh_destroy(vgx_mesh M) {
   (void)hipSetDevice(M->ctx->device);
   free_blocks(M);
   free_tris(M);
+  free_separated(M);
   delete M;
   return VGX_OK;
 }
@@ -481,6 +762,7 @@ int vgx_tsdf_layer_generate_mesh(vgx_tsdf_layer L, const vgx_mesh_config* cfg, v
   VGX_HIP(ctx, hipSetDevice(ctx->device));
   M->n_blocks = 0;
   M->n_tris = 0;
+  M->has_colors = false;
   int32_t nb = 0;
   unsigned long long dropped = 0;
   rc = tsdf_read_stats(L, &nb, &dropped);  // (behind the scans and merges queued on the TSDF stream)
@@ -513,6 +795,7 @@ int vgx_submap_generate_mesh(vgx_submap sm, const vgx_mesh_config* cfg, vgx_mesh
   VGX_HIP(ctx, hipSetDevice(ctx->device));
   M->n_blocks = 0;
   M->n_tris = 0;
+  M->has_colors = false;
   MeshSrc s{};
   s.lut = sm->d_lut;
   for (int a = 0; a < 3; ++a) {
@@ -524,6 +807,114 @@ int vgx_submap_generate_mesh(vgx_submap sm, const vgx_mesh_config* cfg, vgx_mesh
   s.weight = sm->d_tsdf_weight;
   s.voxel_size = sm->voxel_size;
   return generate<false>(ctx, ctx->stream, s, sm->vps, sm->n_blocks, mw, M);
+}
+
+int vgx_submaps_generate_separated_mesh(vgx_ctx ctx, int32_t n, const vgx_submap* submaps, const float* T_M_S, const uint8_t* rgba,
+                                        const vgx_mesh_config* cfg, vgx_mesh M) {
+  static const char* kFn = "vgx_submaps_generate_separated_mesh: ";
+  auto fail = [ctx](int code, const std::string& msg) { return set_error(ctx, code, kFn + msg); };
+  if (!ctx) return set_error(nullptr, VGX_ERR_INVALID, std::string(kFn) + "NULL context");
+  float mw = 0.0f;
+  int rc = check_args(ctx, cfg, M, "vgx_submaps_generate_separated_mesh", &mw);
+  if (rc != VGX_OK) return rc;
+  if (n < 0) return fail(VGX_ERR_INVALID, "n < 0");
+  if (n > 0 && (!submaps || !T_M_S || !rgba)) return fail(VGX_ERR_INVALID, "NULL submaps / T_M_S / rgba with n > 0");
+  int64_t n_entries = 0;
+  long long lo[3] = {0, 0, 0}, hi[3] = {-1, -1, -1};
+  bool any = false;
+  for (int32_t i = 0; i < n; ++i) {
+    const vgx_submap sm = submaps[i];
+    const std::string at = "submap " + std::to_string(i) + ": ";
+    if (!sm || sm->ctx != ctx) return fail(VGX_ERR_INVALID, at + "NULL or of another context");
+    if (sm->n_blocks > 0 && (!sm->d_tsdf_distance || !sm->d_tsdf_weight))
+      return fail(VGX_ERR_INVALID, at + "raw TSDF layer not resident (released?)");
+    if (sm->voxel_size != submaps[0]->voxel_size || sm->vps != submaps[0]->vps)
+      return fail(VGX_ERR_INVALID, at + "voxel_size / voxels_per_side differ from submap 0's");
+    const float* T = T_M_S + 7 * (size_t)i;
+    for (int k = 0; k < 7; ++k)
+      if (!std::isfinite(T[k])) return fail(VGX_ERR_INVALID, at + "pose value not finite");
+    const double n2 = (double)T[0] * T[0] + (double)T[1] * T[1] + (double)T[2] * T[2] + (double)T[3] * T[3];
+    if (std::fabs(n2 - 1.0) > 1e-4) return fail(VGX_ERR_INVALID, at + "pose quaternion not unit (|q|^2 - 1 > 1e-4)");
+    n_entries += sm->n_blocks;
+    if (sm->n_blocks == 0) continue;
+    for (int a = 0; a < 3; ++a) {
+      const long long l = sm->lut_min[a], h = (long long)sm->lut_min[a] + sm->lut_dim[a] - 1;
+      lo[a] = any ? std::min(lo[a], l) : l;
+      hi[a] = any ? std::max(hi[a], h) : h;
+    }
+    any = true;
+  }
+  if (n > 0 && submaps[0]->vps != 8 && submaps[0]->vps != 16) return fail(VGX_ERR_UNSUPPORTED, "voxels_per_side must be 8 or 16");
+  if (n_entries > INT32_MAX) return fail(VGX_ERR_UNSUPPORTED, "more than 2^31 - 1 blocks in all");
+  SepBox box{};
+  unsigned end_bit = 1;
+  if (any) {
+    unsigned __int128 cells = 1;
+    for (int a = 0; a < 3; ++a) {
+      box.lo[a] = lo[a];
+      box.dim[a] = (unsigned long long)(hi[a] - lo[a] + 1);
+      cells *= box.dim[a];
+    }
+    const unsigned __int128 keys = cells * (unsigned __int128)n;  // (dims < 2^33 each: no overflow of 128 bits)
+    if (keys > ((unsigned __int128)1 << 64)) return fail(VGX_ERR_UNSUPPORTED, "union block box x n does not fit a 64-bit key");
+    while (end_bit < 64 && ((unsigned __int128)1 << end_bit) < keys) ++end_bit;
+  }
+  std::lock_guard<std::mutex> mesh_lk(M->mu);
+  std::lock_guard<std::mutex> reg_lk(ctx->mu);
+  VGX_HIP(ctx, hipSetDevice(ctx->device));
+  M->n_blocks = 0;
+  M->n_tris = 0;
+  M->has_colors = false;
+  if (n_entries == 0) {
+    M->has_colors = true;
+    return VGX_OK;
+  }
+  M->h_src.assign((size_t)n, SepSrc{});
+  int64_t e0 = 0;
+  for (int32_t i = 0; i < n; ++i) {
+    const vgx_submap sm = submaps[i];
+    SepSrc& d = M->h_src[(size_t)i];
+    d.m.lut = sm->d_lut;
+    for (int a = 0; a < 3; ++a) {
+      d.m.lut_min[a] = sm->lut_min[a];
+      d.m.lut_dim[a] = sm->lut_dim[a];
+    }
+    d.m.block_index = sm->d_block_index;
+    d.m.dist = sm->d_tsdf_distance;
+    d.m.weight = sm->d_tsdf_weight;
+    d.m.voxel_size = sm->voxel_size;
+    const float* T = T_M_S + 7 * (size_t)i;
+    for (int k = 0; k < 4; ++k) d.pose.q[k] = T[k];
+    for (int k = 0; k < 3; ++k) d.pose.t[k] = T[4 + k];
+    std::memcpy(&d.pose.rgba, rgba + 4 * (size_t)i, 4);
+    d.entry0 = e0;
+    e0 += sm->n_blocks;
+  }
+  rc = generate_separated(ctx, ctx->stream, submaps[0]->vps, (int32_t)n_entries, box, end_bit, mw, M);
+  if (rc != VGX_OK) {
+    M->n_blocks = 0;
+    M->n_tris = 0;
+    return rc;
+  }
+  M->has_colors = true;
+  return VGX_OK;
+}
+
+int vgx_mesh_has_colors(vgx_mesh M, int32_t* has) {
+  if (!M || !has) return set_error(M ? M->ctx : nullptr, VGX_ERR_INVALID, "vgx_mesh_has_colors: NULL argument");
+  std::lock_guard<std::mutex> lk(M->mu);
+  *has = M->has_colors ? 1 : 0;
+  return VGX_OK;
+}
+
+int vgx_mesh_download_colors(vgx_mesh M, uint8_t* rgba) {
+  if (!M || !rgba) return set_error(M ? M->ctx : nullptr, VGX_ERR_INVALID, "vgx_mesh_download_colors: NULL argument");
+  vgx_ctx ctx = M->ctx;
+  std::lock_guard<std::mutex> lk(M->mu);
+  if (!M->has_colors) return set_error(ctx, VGX_ERR_INVALID, "vgx_mesh_download_colors: the mesh has no colours");
+  VGX_HIP(ctx, hipSetDevice(ctx->device));
+  if (M->n_tris > 0) VGX_HIP(ctx, hipMemcpy(rgba, M->d_colors, (size_t)M->n_tris * 4, hipMemcpyDeviceToHost));
+  return VGX_OK;
 }
 
 int vgx_mesh_stats(vgx_mesh M, int32_t* n_blocks, int64_t* n_triangles) {
@@ -567,17 +958,39 @@ int vgx_mesh_write_ply(vgx_mesh M, const char* path) {
   std::vector<float> v((size_t)nt * 9), n((size_t)nt * 3);
   rc = vgx_mesh_download(M, nullptr, nullptr, v.data(), n.data());
   if (rc != VGX_OK) return rc;
+  int32_t colored = 0;
+  std::vector<uint8_t> rgba;
+  rc = vgx_mesh_has_colors(M, &colored);
+  if (rc == VGX_OK && colored) {
+    rgba.resize((size_t)nt * 4);
+    rc = vgx_mesh_download_colors(M, rgba.data());
+  }
+  if (rc != VGX_OK) return rc;
   std::FILE* f = std::fopen(path, "wb");
   if (!f) return set_error(M->ctx, VGX_ERR_INVALID, std::string("vgx_mesh_write_ply: cannot open ") + path);
   const std::string header = "ply\nformat binary_little_endian 1.0\nelement vertex " + std::to_string(3 * nt) +
                              "\nproperty float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\n"
-                             "property float nz\nelement face " + std::to_string(nt) +
+                             "property float nz\n" +
+                             (colored ? "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty uchar alpha\n" : "") +
+                             "element face " + std::to_string(nt) +
                              "\nproperty list uchar int vertex_indices\nend_header\n";
   bool ok = std::fwrite(header.data(), 1, header.size(), f) == header.size();
   std::vector<float> vrec;
   std::vector<unsigned char> frec;
   constexpr int64_t kChunk = 1 << 16;  // triangles per write
-  for (int64_t t0 = 0; ok && t0 < nt; t0 += kChunk) {
+  for (int64_t t0 = 0; ok && colored && t0 < nt; t0 += kChunk) {  // x y z nx ny nz (f32) r g b a (u8): 28 B per vertex
+    const int64_t t1 = std::min(nt, t0 + kChunk);
+    frec.assign((size_t)(t1 - t0) * 3 * 28, 0);
+    for (int64_t t = t0; t < t1; ++t)
+      for (int q = 0; q < 3; ++q) {
+        unsigned char* r = &frec[((size_t)(t - t0) * 3 + q) * 28];
+        std::memcpy(r, &v[(size_t)t * 9 + 3 * q], 12);
+        std::memcpy(r + 12, &n[(size_t)t * 3], 12);
+        std::memcpy(r + 24, &rgba[(size_t)t * 4], 4);
+      }
+    ok = std::fwrite(frec.data(), 1, frec.size(), f) == frec.size();
+  }
+  for (int64_t t0 = 0; ok && !colored && t0 < nt; t0 += kChunk) {
     const int64_t t1 = std::min(nt, t0 + kChunk);
     vrec.clear();
     for (int64_t t = t0; t < t1; ++t)
