@@ -906,6 +906,56 @@ VGX_API int vgx_evaluate_layers_rmse(vgx_submap gt, vgx_submap test, int32_t lay
                                      float* error_distance /* [n_test][vps^3] or NULL */,
                                      uint8_t* error_set /* [n_test][vps^3] or NULL */, int32_t* n_error_blocks);
 
+/* ---- Map queries: voxblox EsdfMap / TsdfMap lookups ----------------------- */
+/* What a consumer of voxgraph's map asks of it: VoxgraphSubmap is a cblox::TsdfEsdfSubmap, and getEsdfMap() /
+ * getTsdfMap() expose voxblox's EsdfMap / TsdfMap [recalled]: getDistanceAtPosition, getDistanceAndGradientAtPosition,
+ * isObserved, getWeightAtPosition and their batchGet... forms, over Interpolator::getDistance / getGradient.  This call
+ * answers n such questions about one finished submap's raw ESDF or TSDF layer (layer = VGX_EVAL_LAYER_ESDF / _TSDF).
+ * The projected map becomes queryable through vgx_tsdf_layer_merge_submaps, vgx_submap_from_tsdf_layer and
+ * vgx_submap_generate_esdf.  Everything about voxblox here is [recalled]: voxblox is not vendored.
+ * Rules (what the kernel, vgx_query_kernel.h, and tests/map_query_ref.py all follow; f32, no contraction):
+ *   point        without a pose p = the query point x.  With T_Q_S {qw,qx,qy,qz, tx,ty,tz}, p = T_S_Q * x, T_S_Q =
+ *                T_Q_S.inverse() formed once in f32 as vgx_tsdf_layer_merge_submaps forms it (conjugate quaternion,
+ *                translation -(q^-1 t)), applied as its transform_point (Eigen _transformVector, then + t).
+ *   validity     an ESDF voxel is valid when observed != 0, a TSDF voxel when weight > 0.  A missing block is invalid.
+ *   nearest      (getNearestDistance; flags without VGX_QUERY_INTERPOLATE) block b = floorf(p * block_size_inv + 1e-6f)
+ *                per axis must exist; the voxel v = floorf((p - b * block_size) * voxel_size_inv + 1e-6f), clamped to
+ *                [0, vps), must be valid; distance and (TSDF) weight are the voxel's own.
+ *   interpolated (getInterpDistance; VGX_QUERY_INTERPOLATE) the 8 neighbours and the trilinear association of the
+ *                isosurface points and the projected map (Interpolator::getVoxel(p, &v, true)); all 8 must exist and be
+ *                valid.  A TSDF weight is interpolated the same way from the 8 weights.
+ *   gradient     (getGradient; VGX_QUERY_GRADIENT) for each axis a in x, y, z and each sign s in -1, +1: d = the distance
+ *                at p + s voxel_size e_a (the coordinate a alone changes: p_a - voxel_size, p_a + voxel_size), with the
+ *                same interpolate flag; g_a = (d(+1) - d(-1)) / (2 voxel_size) (the sum s d, bit for bit).  Any of the six
+ *                failing fails the query; p's own block must exist (implied: a valid distance at p reads it).  With a
+ *                pose the gradient is rotated back into the query frame by q of T_Q_S (the rotation alone, not
+ *                renormalised).  `valid` is then the conjunction of the gradient and the distance at p, as
+ *                getDistanceAndGradientAtPosition returns it.
+ *   invalid      an invalid query writes valid = 0 and +0.0f into every output it has (distance, gradient when asked
+ *                for, weight when given); voxblox leaves the caller's values alone there (the C++ layer,
+ *                voxgraph_amd/cpp/gpu_esdf_map.h, restores that).  A point with a coordinate |p_a * block_size_inv| >=
+ *                2^30 -- every non-finite coordinate among them -- is invalid: the defined answer where voxblox's int
+ *                cast of the block index is undefined.
+ *   outputs      distance [n], gradient [n][3] (VGX_QUERY_GRADIENT only; not written otherwise), weight [n] (TSDF only;
+ *                nullable), valid [n] u8 (1 / 0).
+ * Refused with VGX_ERR_INVALID before anything is written (vgx_last_error says which): a NULL submap; n < 0; NULL points
+ * / distance / valid with n > 0; VGX_QUERY_GRADIENT without a gradient array; a weight array on an ESDF query; unknown
+ * flag bits or a layer value out of range; a layer the submap no longer holds in raw form (vgx_submap_release_raw_layers,
+ * or an ESDF never generated); a pose that is not finite or whose |q.q - 1| > 1e-4.  n = 0: VGX_OK.
+ * Streams and lifetimes: both calls run on the context's registration stream under the registration lock, ordered behind
+ * vgx_submap_generate_esdf.  vgx_submap_query takes host arrays and returns with the results on the host;
+ * vgx_submap_query_device takes device arrays and returns once the work is queued (vgx_ctx_synchronize waits for it).
+ * One launch whatever n; values do not depend on scheduling. */
+#define VGX_QUERY_INTERPOLATE 1 /* Interpolator::getDistance(.., interpolate = true); else the nearest voxel */
+#define VGX_QUERY_GRADIENT 2    /* also Interpolator::getGradient (central differences, above)            */
+VGX_API int vgx_submap_query(vgx_submap submap, int32_t layer, int32_t flags, const float T_Q_S[7] /* nullable */,
+                             int64_t n, const float* points /* [n][3] */, float* distance /* [n] */,
+                             float* gradient /* [n][3] or NULL */, float* weight /* [n] or NULL; TSDF only */,
+                             uint8_t* valid /* [n] */);
+VGX_API int vgx_submap_query_device(vgx_submap submap, int32_t layer, int32_t flags, const float T_Q_S[7] /* nullable, host */,
+                                    int64_t n, const float* points, float* distance, float* gradient, float* weight,
+                                    uint8_t* valid);
+
 /* ---------------------------------------------------------------------------
  * Saved maps: cblox submap-collection files and voxblox layer files.
  *

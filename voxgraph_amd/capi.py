@@ -4,6 +4,7 @@ This module only declares the C ABI and wraps handles; all arithmetic happens in
 the HIP library.  There is no fallback: if the shared object is missing the
 import fails, and without a gfx950 device Context() raises.
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -82,6 +83,7 @@ class EvaluationDetails(C.Structure):
 # voxblox VoxelEvaluationMode order; which layer of the two submaps vgx_evaluate_layers_rmse compares
 EVAL_ALL_VOXELS, EVAL_IGNORE_BEHIND_TEST, EVAL_IGNORE_BEHIND_GT, EVAL_IGNORE_BEHIND_ALL = 0, 1, 2, 3
 EVAL_LAYER_ESDF, EVAL_LAYER_TSDF = 0, 1
+QUERY_INTERPOLATE, QUERY_GRADIENT = 1, 2
 
 
 class TsdfConfig(C.Structure):
@@ -215,6 +217,8 @@ SIGNATURES = {
     "vgx_submaps_generate_separated_mesh": (C.c_int, [vp, C.c_int32, C.POINTER(vp), f32p, u8p, C.POINTER(MeshConfig), vp]),
     "vgx_mesh_has_colors": (C.c_int, [vp, i32p]),
     "vgx_mesh_download_colors": (C.c_int, [vp, u8p]),
+    "vgx_submap_query": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.c_int64, f32p, f32p, f32p, f32p, u8p]),
+    "vgx_submap_query_device": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.c_int64, vp, vp, vp, vp, vp]),
     "vgx_map_file_open": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(vp)]),
     "vgx_map_file_close": (C.c_int, [vp]),
     "vgx_map_file_last_error": (C.c_char_p, [vp]),
@@ -390,6 +394,9 @@ class Context:
             self.h = None
 
 
+MapQuery = collections.namedtuple("MapQuery", ["distance", "gradient", "weight", "valid"])
+
+
 class Submap:
     """A finished VoxgraphSubmap resident on the GPU."""
 
@@ -515,6 +522,48 @@ class Submap:
         cfg = MeshConfig(float(min_weight))
         self.ctx.check(self.ctx.lib.vgx_submap_generate_mesh(self.h, C.byref(cfg), mesh.h))
         return mesh
+
+    def _query_args(self, layer, interpolate, gradient, pose, weight):
+        lay = {"esdf": EVAL_LAYER_ESDF, "tsdf": EVAL_LAYER_TSDF}.get(layer, layer)
+        flags = (QUERY_INTERPOLATE if interpolate else 0) | (QUERY_GRADIENT if gradient else 0)
+        T = None if pose is None else np.ascontiguousarray(pose, np.float32).reshape(7)
+        return int(lay), flags, T
+
+    def query(self, points, layer="esdf", interpolate=True, gradient=False, pose=None, weight=False):
+        """voxblox's EsdfMap / TsdfMap lookups at points [n][3] (vgx_submap_query): layer "esdf" or "tsdf", interpolate
+        (getInterpDistance; else the nearest voxel), gradient (getGradient), pose T_Q_S [7] (qw,qx,qy,qz, tx,ty,tz: the
+        points are in frame Q; None: the submap frame), weight (TSDF only).  Returns MapQuery(distance [n], gradient [n][3]
+        or None, weight [n] or None, valid [n] bool); an invalid query has valid False and zeros elsewhere."""
+        lay, flags, T = self._query_args(layer, interpolate, gradient, pose, weight)
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        d = np.zeros(n, np.float32)
+        g = np.zeros((n, 3), np.float32) if gradient else None
+        w = np.zeros(n, np.float32) if weight else None
+        v = np.zeros(n, np.uint8)
+        self.ctx.check(self.ctx.lib.vgx_submap_query(self.h, lay, flags, _ptr(T, f32p), n, _ptr(pts, f32p), _ptr(d, f32p),
+                                                     _ptr(g, f32p), _ptr(w, f32p), _ptr(v, u8p)))
+        return MapQuery(d, g, w, v.view(np.bool_))
+
+    def query_device(self, points, layer="esdf", interpolate=True, gradient=False, pose=None, weight=False, sync=True):
+        """query() over torch tensors on the context's device (vgx_submap_query_device): points float32 [n][3] ->
+        MapQuery of tensors (valid as uint8).  The caller's current stream is waited for first; sync=False returns once the
+        work is queued on the context's registration stream (ctx.synchronize() waits for it)."""
+        import torch
+        lay, flags, T = self._query_args(layer, interpolate, gradient, pose, weight)
+        pts = points.to(torch.float32).contiguous().reshape(-1, 3)
+        n = pts.shape[0]
+        d = torch.empty(n, dtype=torch.float32, device=pts.device)
+        g = torch.empty((n, 3), dtype=torch.float32, device=pts.device) if gradient else None
+        w = torch.empty(n, dtype=torch.float32, device=pts.device) if weight else None
+        v = torch.empty(n, dtype=torch.uint8, device=pts.device)
+        torch.cuda.current_stream(pts.device).synchronize()
+        self.ctx.check(self.ctx.lib.vgx_submap_query_device(
+            self.h, lay, flags, _ptr(T, f32p), n, vp(pts.data_ptr()), vp(d.data_ptr()),
+            vp(g.data_ptr()) if g is not None else None, vp(w.data_ptr()) if w is not None else None, vp(v.data_ptr())))
+        if sync:
+            self.ctx.synchronize()
+        return MapQuery(d, g, w, v)
 
     def release_raw_layers(self):
         self.ctx.check(self.ctx.lib.vgx_submap_release_raw_layers(self.h))

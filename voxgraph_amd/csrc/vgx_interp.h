@@ -1,4 +1,4 @@
-// Trilinear TSDF interpolation on a submap's raw layer (device side).  gfx950 only.
+// Trilinear interpolation on a submap's raw TSDF or ESDF layer (device side).  gfx950 only.
 #ifndef VGX_INTERP_H_
 #define VGX_INTERP_H_
 
@@ -6,22 +6,17 @@
 
 #include <cmath>
 #include <cstddef>
+#include <cstdint>
 
 #pragma clang fp contract(off)
 
 namespace vgx {
 
-// Interpolator<TsdfVoxel>::getVoxel(p, &v, true) [recalled], i.e. getVoxelsAndQVector + interpVoxel, on a raw
-// TSDF layer ([n_blocks][VPS^3] distance and weight, voxblox linear voxel order, blocks found through a dense
-// lookup table): false unless all 8 neighbours exist with weight > 0; then distance and weight interpolated in
-// oracle/iso_oracle.c's association.  P carries lut, lut_min / lut_dim (int3), tsdf_d, tsdf_w, voxel_size,
-// voxel_size_inv, block_size, block_size_inv.  Shared by the isosurface points (vgx_iso.hip) and the projected map
-// (vgx_project.hip); both are pinned to the oracle bit for bit, so this is the one copy.
+// Interpolator<VoxelType>::getVoxelsAndQVector [recalled], split so that a caller can form the indices of several
+// interpolations before it reads any voxel (vgx_query.hip): blk / vox the low neighbour's block and voxel index, dl the
+// position within the cube in voxels.  P carries voxel_size, voxel_size_inv, block_size, block_size_inv.
 template <int VPS, class P>
-__device__ bool tsdf_interp(const P& p, const float pos[3], float& dist, float& wgt) {
-  constexpr int VOX = VPS * VPS * VPS;
-  int blk[3], vox[3];
-  float dl[3];
+__device__ __forceinline__ void interp_base(const P& p, const float pos[3], int blk[3], int vox[3], float dl[3]) {
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     int b0 = (int)floorf(pos[a] * p.block_size_inv + 1e-6f);
@@ -29,10 +24,8 @@ __device__ bool tsdf_interp(const P& p, const float pos[3], float& dist, float& 
     int v = (int)floorf((pos[a] - origin) * p.voxel_size_inv + 1e-6f);
     v = min(max(v, 0), VPS - 1);
     float centre = origin + ((float)v + 0.5f) * p.voxel_size;
-    if (a == 0) {
-      // setIndexes: the block containing pos must exist (checked below through neighbours:
-      // it is the block of one of the 8 neighbours)
-    }
+    // setIndexes: the block containing pos must exist (checked by the caller through neighbours: it is the block of
+    // one of the 8 neighbours)
     if (pos[a] - centre < 0.0f) {
       v--;
       if (v < 0) {
@@ -45,6 +38,45 @@ __device__ bool tsdf_interp(const P& p, const float pos[3], float& dist, float& 
     blk[a] = b0;
     vox[a] = v;
   }
+}
+
+// the block's slot through the dense lookup table (P: lut, lut_min / lut_dim as int3), -1 when absent.  (layer_interp keeps
+// its own copy of these lines: routed through this function, the projected-map kernels took two more VGPRs.)
+template <class P>
+__device__ __forceinline__ int interp_slot(const P& p, int bx, int by, int bz) {
+  int rx = bx - p.lut_min.x, ry = by - p.lut_min.y, rz = bz - p.lut_min.z;
+  if ((unsigned)rx >= (unsigned)p.lut_dim.x || (unsigned)ry >= (unsigned)p.lut_dim.y || (unsigned)rz >= (unsigned)p.lut_dim.z)
+    return -1;
+  return p.lut[rx + p.lut_dim.x * (ry + p.lut_dim.y * rz)];
+}
+
+// interpVoxel's trilinear form over the 8 neighbours (k: x = bit 2, y = bit 1, z = bit 0) in oracle/iso_oracle.c's
+// association
+__device__ __forceinline__ float interp_trilinear(const float x[8], const float dl[3]) {
+  float c0 = x[0], c1 = -x[0] + x[4], c2 = -x[0] + x[2], c3 = -x[0] + x[1];
+  float c4 = ((x[0] - x[2]) - x[4]) + x[6];
+  float c5 = ((x[0] - x[1]) - x[2]) + x[3];
+  float c6 = ((x[0] - x[1]) - x[4]) + x[5];
+  float c7 = ((((((-x[0] + x[1]) + x[2]) - x[3]) + x[4]) - x[5]) - x[6]) + x[7];
+  float q4 = dl[0] * dl[1], q5 = dl[1] * dl[2], q6 = dl[2] * dl[0], q7 = dl[0] * dl[1] * dl[2];
+  return ((((((c0 + dl[0] * c1) + dl[1] * c2) + dl[2] * c3) + q4 * c4) + q5 * c5) + q6 * c6) + q7 * c7;
+}
+
+// Interpolator<VoxelType>::isVoxelValid on the layer's validity array: TSDF weight > 0, ESDF observed != 0
+__device__ __forceinline__ bool interp_valid(float w) { return w > 0.0f; }
+__device__ __forceinline__ bool interp_valid(uint8_t o) { return o != 0; }
+
+// Interpolator<VoxelType>::getVoxel(p, &v, true) [recalled], i.e. getVoxelsAndQVector + interpVoxel, on one raw layer
+// ([n_blocks][VPS^3] values and validity, voxblox linear voxel order, blocks found through a dense lookup table): false
+// unless all 8 neighbours exist and are valid; then the value interpolated and -- for a TSDF layer, whose validity array
+// is the weight -- the weight too (`wgt` is left alone for an ESDF layer).
+template <int VPS, class P, class V>
+__device__ bool layer_interp(const P& p, const float* val, const V* vld, const float pos[3], float& dist, float& wgt) {
+  constexpr bool kTsdf = sizeof(V) == sizeof(float);
+  constexpr int VOX = VPS * VPS * VPS;
+  int blk[3], vox[3];
+  float dl[3];
+  interp_base<VPS>(p, pos, blk, vox, dl);
   float d[8], w[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
@@ -66,22 +98,24 @@ __device__ bool tsdf_interp(const P& p, const float pos[3], float& dist, float& 
     int slot = p.lut[rx + p.lut_dim.x * (ry + p.lut_dim.y * rz)];
     if (slot < 0) return false;
     size_t at = (size_t)slot * VOX + (size_t)(nv[0] + VPS * (nv[1] + VPS * nv[2]));
-    d[k] = p.tsdf_d[at];
-    w[k] = p.tsdf_w[at];
-    if (!(w[k] > 0.0f)) return false;  // Interpolator<TsdfVoxel>::isVoxelValid
+    d[k] = val[at];
+    const V v = vld[at];
+    if (kTsdf) w[k] = (float)v;
+    if (!interp_valid(v)) return false;  // Interpolator<VoxelType>::isVoxelValid
   }
-  auto interp = [&](const float x[8]) {
-    float c0 = x[0], c1 = -x[0] + x[4], c2 = -x[0] + x[2], c3 = -x[0] + x[1];
-    float c4 = ((x[0] - x[2]) - x[4]) + x[6];
-    float c5 = ((x[0] - x[1]) - x[2]) + x[3];
-    float c6 = ((x[0] - x[1]) - x[4]) + x[5];
-    float c7 = ((((((-x[0] + x[1]) + x[2]) - x[3]) + x[4]) - x[5]) - x[6]) + x[7];
-    float q4 = dl[0] * dl[1], q5 = dl[1] * dl[2], q6 = dl[2] * dl[0], q7 = dl[0] * dl[1] * dl[2];
-    return ((((((c0 + dl[0] * c1) + dl[1] * c2) + dl[2] * c3) + q4 * c4) + q5 * c5) + q6 * c6) + q7 * c7;
-  };
+  auto interp = [&](const float x[8]) { return interp_trilinear(x, dl); };
   dist = interp(d);
-  wgt = interp(w);
+  if (kTsdf) wgt = interp(w);
   return true;
+}
+
+// Interpolator<TsdfVoxel>::getVoxel(p, &v, true) on a submap's raw TSDF layer: layer_interp over distance and weight.
+// P carries lut, lut_min / lut_dim (int3), tsdf_d, tsdf_w, voxel_size, voxel_size_inv, block_size, block_size_inv.
+// Shared by the isosurface points (vgx_iso.hip), the projected map (vgx_project.hip) and the map queries
+// (vgx_query.hip); the first two are pinned to the oracle bit for bit, so this is the one copy.
+template <int VPS, class P>
+__device__ bool tsdf_interp(const P& p, const float pos[3], float& dist, float& wgt) {
+  return layer_interp<VPS>(p, p.tsdf_d, p.tsdf_w, pos, dist, wgt);
 }
 
 }  // namespace vgx
