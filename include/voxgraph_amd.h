@@ -857,6 +857,56 @@ VGX_API int vgx_mesh_has_colors(vgx_mesh mesh, int32_t* has);
 /* rgba [T][4]: one colour per triangle */
 VGX_API int vgx_mesh_download_colors(vgx_mesh mesh, uint8_t* rgba);
 
+/* The connected mesh: voxblox MeshLayer::getConnectedMesh / createConnectedMesh [recalled] over the triangle soup a
+ * vgx_mesh holds -- what voxblox::outputMeshLayerAsPly writes (SubmapVisuals::saveCombinedMesh / saveSeparatedMesh,
+ * submap_visuals.cpp:89-107) and what VoxgraphSubmap::findIsosurfaceVertices asks for at 0.5 * voxel_size.  Vertices
+ * that fall into the same cell of a grid of pitch `approximate_vertex_proximity_threshold` become one vertex, and the
+ * triangles an index list.  The source is any vgx_mesh that holds a mesh (of a layer, of a submap, a separated mesh); it
+ * is not changed.  Everything about voxblox here is [recalled]: voxblox is not vendored.
+ * Rules (what the kernels, vgx_connect.hip, and tests/connected_mesh_ref.py all follow):
+ *   soup order     soup vertex j = 3 t + c is corner c of triangle t in the order vgx_mesh_download returns: blocks in
+ *                  ascending (x, y, z) block index, then the block's triangles, then the three corners.  DEVIATION:
+ *                  voxblox walks its block meshes in hash-map order, which is not defined; ascending block order is this
+ *                  library's stated order (the "output" rule of vgx_tsdf_layer_generate_mesh).  It decides which copy of
+ *                  a welded vertex is the "first".
+ *   key            inv = 1.0 / (double)threshold, the threshold an f32 (voxblox's FloatingPoint; its default 1e-10f).
+ *                  Per coordinate k = (int64) round((double)v * inv): one f64 multiply, std::round (halves away from
+ *                  zero), so -0.0 and +0.0 share key 0.  The key is the three int64 together, compared exactly (192
+ *                  bits): a hash of them finds the slot, it never decides equality.
+ *   vertices       a key's vertex is its FIRST soup vertex (smallest j): its three floats copied bit for bit, the normal
+ *                  of that soup vertex's triangle j / 3 (voxblox stores the triangle normal on each corner) and, when the
+ *                  source has colours, the colour of triangle j / 3.  Unique vertices are numbered in order of first
+ *                  occurrence (ascending j).
+ *   indices        indices[j] = the number of the unique vertex of key(j): [T][3] u32, triangle order unchanged.
+ *                  Triangles whose corners weld together are kept (voxblox keeps them).  Blocks without triangles
+ *                  contribute nothing.
+ * The output handle is reused from call to call: its device buffers grow on demand; one call at a time per handle.
+ * Refused with VGX_ERR_INVALID before anything is launched: NULL handles, handles of different contexts, a threshold that
+ * is not finite or not > 0, a source handle that holds no mesh because its last generating call failed.
+ * VGX_ERR_UNSUPPORTED: 3 T >= 2^32; a vertex with a coordinate that is not finite or with |v * inv| >= 2^62 (the int64
+ * cast is undefined there; found by a device flag after the first passes, and the output handle then holds no mesh: stats
+ * report 0).  Out of device memory: VGX_ERR_NOMEM, and the output handle then holds no mesh.  A source with 0 triangles:
+ * VGX_OK, 0 vertices, 0 triangles.  has_colors follows the source.
+ * Runs on the registration stream under the registration lock (a vgx_mesh is complete when its generating call returns,
+ * whichever stream made it); returns with the connected mesh complete.  Two memsets, three kernels and one scan whatever
+ * the size, and two host synchronisations (the vertex count and the range flag in one; the end).  Values and order do not
+ * depend on scheduling: the only atomics are integer ones whose final value is order-independent (the claim of an empty
+ * slot, a minimum, the OR of the range flag). */
+typedef struct vgx_connected_mesh_s* vgx_connected_mesh;
+VGX_API int vgx_connected_mesh_create(vgx_ctx ctx, vgx_connected_mesh* out);
+VGX_API int vgx_connected_mesh_destroy(vgx_connected_mesh cm);
+VGX_API int vgx_mesh_connect(vgx_mesh mesh, float approximate_vertex_proximity_threshold, vgx_connected_mesh out);
+/* any pointer may be NULL */
+VGX_API int vgx_connected_mesh_stats(vgx_connected_mesh cm, int64_t* n_vertices, int64_t* n_triangles, int32_t* has_colors);
+/* vertices [V][3], normals [V][3], rgba [V][4], indices [T][3]; any may be NULL.  rgba on a mesh without colours:
+ * VGX_ERR_INVALID. */
+VGX_API int vgx_connected_mesh_download(vgx_connected_mesh cm, float* vertices, float* normals, uint8_t* rgba,
+                                        uint32_t* indices);
+/* Host code: binary_little_endian PLY -- element vertex V: x y z nx ny nz (float), then red green blue alpha (uchar) when
+ * the mesh has colours; element face T: `list uchar int vertex_indices`.  VGX_ERR_UNSUPPORTED when V >= 2^31.  A stated
+ * format, not byte parity with voxblox's outputMeshLayerAsPly.  vgx_mesh_write_ply (the soup) is unchanged. */
+VGX_API int vgx_connected_mesh_write_ply(vgx_connected_mesh cm, const char* path);
+
 /* ---- Map evaluation: voxblox::utils::evaluateLayersRmse ------------------- */
 /* MapEvaluation::evaluate (map_evaluation.cpp:59-114) scores a map against a ground truth: projected map
  * (vgx_tsdf_layer_merge_submaps), finishSubmap() of both (vgx_submap_from_tsdf_layer, vgx_submap_generate_esdf,

@@ -36,6 +36,7 @@ f64p = C.POINTER(C.c_double)
 i32p = C.POINTER(C.c_int32)
 i64p = C.POINTER(C.c_int64)
 u8p = C.POINTER(C.c_uint8)
+u32p = C.POINTER(C.c_uint32)
 
 
 class RegConfig(C.Structure):
@@ -217,6 +218,12 @@ SIGNATURES = {
     "vgx_submaps_generate_separated_mesh": (C.c_int, [vp, C.c_int32, C.POINTER(vp), f32p, u8p, C.POINTER(MeshConfig), vp]),
     "vgx_mesh_has_colors": (C.c_int, [vp, i32p]),
     "vgx_mesh_download_colors": (C.c_int, [vp, u8p]),
+    "vgx_connected_mesh_create": (C.c_int, [vp, C.POINTER(vp)]),
+    "vgx_connected_mesh_destroy": (C.c_int, [vp]),
+    "vgx_mesh_connect": (C.c_int, [vp, C.c_float, vp]),
+    "vgx_connected_mesh_stats": (C.c_int, [vp, i64p, i64p, i32p]),
+    "vgx_connected_mesh_download": (C.c_int, [vp, f32p, f32p, u8p, u32p]),
+    "vgx_connected_mesh_write_ply": (C.c_int, [vp, C.c_char_p]),
     "vgx_submap_query": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.c_int64, f32p, f32p, f32p, f32p, u8p]),
     "vgx_submap_query_device": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.c_int64, vp, vp, vp, vp, vp]),
     "vgx_map_file_open": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(vp)]),
@@ -1253,9 +1260,53 @@ class Mesh:
     def write_ply(self, path):
         self.ctx.check(self.ctx.lib.vgx_mesh_write_ply(self.h, os.fsencode(path)))
 
+    def connect(self, threshold=1e-10, out=None):
+        """voxblox createConnectedMesh over this mesh's triangle soup (vgx_mesh_connect): vertices in the same cell of a
+        grid of pitch `threshold` (an f32; voxblox's default 1e-10f) become one.  Returns the ConnectedMesh (a new one
+        when out is None)."""
+        out = out if out is not None else ConnectedMesh(self.ctx)
+        self.ctx.check(self.ctx.lib.vgx_mesh_connect(self.h, C.c_float(threshold), out.h))
+        return out
+
     def destroy(self):
         if self.h:
             self.ctx.lib.vgx_mesh_destroy(self.h)
+            self.h = None
+
+
+class ConnectedMesh:
+    """A voxblox connected Mesh on the GPU (vgx_connected_mesh): unique vertices in order of first occurrence, with the
+    normal (and colour) of their first triangle, and [T][3] indices; reused from call to call."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        h = vp()
+        ctx.check(ctx.lib.vgx_connected_mesh_create(ctx.h, C.byref(h)))
+        self.h = h
+
+    def stats(self):
+        """(vertices, triangles, has_colors)"""
+        nv, nt, has = C.c_int64(), C.c_int64(), C.c_int32()
+        self.ctx.check(self.ctx.lib.vgx_connected_mesh_stats(self.h, C.byref(nv), C.byref(nt), C.byref(has)))
+        return nv.value, nt.value, bool(has.value)
+
+    def download(self):
+        """(vertices [V][3] f32, normals [V][3] f32, rgba [V][4] uint8 or None, indices [T][3] uint32)"""
+        nv, nt, has = self.stats()
+        v = np.zeros((nv, 3), np.float32)
+        n = np.zeros((nv, 3), np.float32)
+        c = np.zeros((nv, 4), np.uint8) if has else None
+        idx = np.zeros((nt, 3), np.uint32)
+        self.ctx.check(self.ctx.lib.vgx_connected_mesh_download(self.h, _ptr(v, f32p), _ptr(n, f32p),
+                                                                None if c is None else _ptr(c, u8p), _ptr(idx, u32p)))
+        return v, n, c, idx
+
+    def write_ply(self, path):
+        self.ctx.check(self.ctx.lib.vgx_connected_mesh_write_ply(self.h, os.fsencode(path)))
+
+    def destroy(self):
+        if self.h:
+            self.ctx.lib.vgx_connected_mesh_destroy(self.h)
             self.h = None
 
 

@@ -18,6 +18,13 @@
 //
 //   voxgraph_amd::GenerateSeparatedMeshOnGpu(submap_collection, mesh_config.min_weight, &gpu_mesh);
 //   voxgraph_amd::DownloadColoredMeshLayer(gpu_mesh, &mesh_layer);
+//
+// The connected mesh (what saveCombinedMesh / saveSeparatedMesh write through voxblox::outputMeshLayerAsPly, and
+// MeshLayer::getConnectedMesh returns): the soup's vertices welded on the GPU, an index list (vgx_mesh_connect):
+//
+//   voxgraph_amd::GpuConnectedMesh gpu_connected(ctx);                            (kept: its buffers are reused)
+//   voxgraph_amd::ConnectMeshOnGpu(gpu_mesh, 1e-10f, &gpu_connected);
+//   gpu_connected.writePly(filepath);              or   voxblox::Mesh mesh; DownloadConnectedMesh(gpu_connected, &mesh);
 #ifndef VOXGRAPH_AMD_CPP_GPU_MESH_H_
 #define VOXGRAPH_AMD_CPP_GPU_MESH_H_
 
@@ -238,6 +245,78 @@ void DownloadColoredMeshLayer(const GpuMesh& gpu_mesh, MeshLayerT* mesh_layer) {
       }
     }
   }
+}
+
+// A connected mesh on the GPU (vgx_connected_mesh): unique vertices in order of first occurrence, [T][3] indices.
+class GpuConnectedMesh {
+ public:
+  explicit GpuConnectedMesh(vgx_ctx ctx) : ctx_(ctx) {
+    if (vgx_connected_mesh_create(ctx, &mesh_) != VGX_OK)
+      throw std::runtime_error(std::string("vgx_connected_mesh_create: ") + vgx_last_error(ctx));
+  }
+  ~GpuConnectedMesh() { vgx_connected_mesh_destroy(mesh_); }
+  GpuConnectedMesh(const GpuConnectedMesh&) = delete;
+  GpuConnectedMesh& operator=(const GpuConnectedMesh&) = delete;
+  vgx_connected_mesh handle() const { return mesh_; }
+  const char* last_error() const { return vgx_last_error(ctx_); }
+  void stats(int64_t* n_vertices, int64_t* n_triangles, bool* has_colors) const {
+    int32_t has = 0;
+    check(vgx_connected_mesh_stats(mesh_, n_vertices, n_triangles, &has), "vgx_connected_mesh_stats");
+    if (has_colors) *has_colors = has != 0;
+  }
+  // vertices [V][3], normals [V][3], rgba [V][4] (left empty when the mesh has no colours), indices [T][3]
+  void download(std::vector<float>* vertices, std::vector<float>* normals, std::vector<uint8_t>* rgba,
+                std::vector<uint32_t>* indices) const {
+    int64_t nv = 0, nt = 0;
+    bool has = false;
+    stats(&nv, &nt, &has);
+    vertices->resize(3 * static_cast<size_t>(nv));
+    normals->resize(3 * static_cast<size_t>(nv));
+    rgba->resize(has ? 4 * static_cast<size_t>(nv) : 0);
+    indices->resize(3 * static_cast<size_t>(nt));
+    check(vgx_connected_mesh_download(mesh_, vertices->data(), normals->data(), has ? rgba->data() : nullptr, indices->data()),
+          "vgx_connected_mesh_download");
+  }
+  void writePly(const std::string& path) const { check(vgx_connected_mesh_write_ply(mesh_, path.c_str()), "vgx_connected_mesh_write_ply"); }
+
+ private:
+  void check(int rc, const char* what) const {
+    if (rc != VGX_OK) throw std::runtime_error(std::string(what) + ": " + vgx_last_error(ctx_));
+  }
+  vgx_ctx ctx_;
+  vgx_connected_mesh mesh_ = nullptr;
+};
+
+// MeshLayer::getConnectedMesh(&connected, approximate_vertex_proximity_threshold) over a mesh on the GPU
+inline GpuConnectedMesh& ConnectMeshOnGpu(const GpuMesh& mesh, float approximate_vertex_proximity_threshold,
+                                          GpuConnectedMesh* connected) {
+  if (!connected) throw std::invalid_argument("ConnectMeshOnGpu: connected == nullptr");
+  if (vgx_mesh_connect(mesh.handle(), approximate_vertex_proximity_threshold, connected->handle()) != VGX_OK)
+    throw std::runtime_error(std::string("vgx_mesh_connect: ") + mesh.last_error());
+  return *connected;
+}
+
+// Fills a voxblox-shaped Mesh (vertices, normals, colors, indices): the connected mesh as createConnectedMesh leaves it.
+// colors stays empty when the GPU mesh has none.
+template <typename MeshT>
+void DownloadConnectedMesh(const GpuConnectedMesh& gpu_connected, MeshT* mesh) {
+  if (!mesh) throw std::invalid_argument("DownloadConnectedMesh: mesh == nullptr");
+  std::vector<float> v, n;
+  std::vector<uint8_t> rgba;
+  std::vector<uint32_t> idx;
+  gpu_connected.download(&v, &n, &rgba, &idx);
+  mesh->vertices.clear();
+  mesh->normals.clear();
+  mesh->colors.clear();
+  mesh->indices.clear();
+  for (size_t i = 0; 3 * i < v.size(); ++i) {
+    mesh->vertices.push_back(voxblox::Point(v[3 * i], v[3 * i + 1], v[3 * i + 2]));
+    mesh->normals.push_back(voxblox::Point(n[3 * i], n[3 * i + 1], n[3 * i + 2]));
+  }
+  for (size_t i = 0; 4 * i < rgba.size(); ++i)
+    mesh->colors.push_back(voxblox::Color(rgba[4 * i], rgba[4 * i + 1], rgba[4 * i + 2], rgba[4 * i + 3]));
+  mesh->indices.reserve(idx.size());
+  for (const uint32_t i : idx) mesh->indices.push_back(i);
 }
 
 }  // namespace voxgraph_amd

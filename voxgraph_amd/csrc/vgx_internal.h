@@ -417,6 +417,20 @@ void set_global_error(const std::string& msg);
                             std::string(#call) + ": " + hipGetErrorString(e__)); \
   } while (0)
 
+// What vgx_connect.hip reads of a mesh handle (vgx_mesh_s lives in vgx_mesh.hip).  mesh_view: the caller holds
+// mesh_mutex(M), except for `ctx`, which never changes.
+struct MeshView {
+  vgx_ctx ctx;
+  bool holds_mesh;   // false after a generating call that failed
+  bool has_colors;
+  int64_t n_tris;
+  const float* vertices;   // [n_tris][3][3]
+  const float* normals;    // [n_tris][3]
+  const uint32_t* colors;  // [n_tris] bytes r g b a, or null
+};
+std::mutex& mesh_mutex(vgx_mesh M);
+MeshView mesh_view(vgx_mesh M);
+
 // kernels' launch wrappers implemented in the .hip files
 #ifndef VGX_TOOLING_LIBRARY
 int launch_brickify(vgx_submap sm, int which);

@@ -432,6 +432,7 @@ struct vgx_mesh_s {
   std::mutex mu;
   int32_t n_blocks = 0;  // the mesh held now
   int64_t n_tris = 0;
+  bool holds_mesh = true;  // false from the moment a generating call resets the handle until one succeeds (vgx_mesh_connect)
   // output, grown on demand
   int32_t* d_block_index = nullptr;  // [block_cap][3]
   int64_t* d_first = nullptr;        // [block_cap + 1]
@@ -726,6 +727,24 @@ int check_args(vgx_ctx ctx, const vgx_mesh_config* cfg, vgx_mesh M, const char* 
 
 }  // namespace
 
+namespace vgx {
+
+std::mutex& mesh_mutex(vgx_mesh M) { return M->mu; }
+
+MeshView mesh_view(vgx_mesh M) {
+  MeshView v{};
+  v.ctx = M->ctx;
+  v.holds_mesh = M->holds_mesh;
+  v.n_tris = M->n_tris;
+  v.vertices = M->d_vertices;
+  v.normals = M->d_normals;
+  v.colors = M->has_colors ? M->d_colors : nullptr;
+  v.has_colors = M->has_colors;
+  return v;
+}
+
+}  // namespace vgx
+
 extern "C" {
 
 void vgx_mesh_config_default(vgx_mesh_config* cfg) {
@@ -763,6 +782,7 @@ int vgx_tsdf_layer_generate_mesh(vgx_tsdf_layer L, const vgx_mesh_config* cfg, v
   M->n_blocks = 0;
   M->n_tris = 0;
   M->has_colors = false;
+  M->holds_mesh = false;
   int32_t nb = 0;
   unsigned long long dropped = 0;
   rc = tsdf_read_stats(L, &nb, &dropped);  // (behind the scans and merges queued on the TSDF stream)
@@ -777,7 +797,9 @@ int vgx_tsdf_layer_generate_mesh(vgx_tsdf_layer L, const vgx_mesh_config* cfg, v
   s.block_index = d.block_index;
   s.words = d.voxels;
   s.voxel_size = d.voxel_size;
-  return generate<true>(ctx, ctx->tsdf_stream, s, d.vps, nb, mw, M);
+  rc = generate<true>(ctx, ctx->tsdf_stream, s, d.vps, nb, mw, M);
+  M->holds_mesh = rc == VGX_OK;
+  return rc;
 }
 
 int vgx_submap_generate_mesh(vgx_submap sm, const vgx_mesh_config* cfg, vgx_mesh M) {
@@ -796,6 +818,7 @@ int vgx_submap_generate_mesh(vgx_submap sm, const vgx_mesh_config* cfg, vgx_mesh
   M->n_blocks = 0;
   M->n_tris = 0;
   M->has_colors = false;
+  M->holds_mesh = false;
   MeshSrc s{};
   s.lut = sm->d_lut;
   for (int a = 0; a < 3; ++a) {
@@ -806,7 +829,9 @@ int vgx_submap_generate_mesh(vgx_submap sm, const vgx_mesh_config* cfg, vgx_mesh
   s.dist = sm->d_tsdf_distance;
   s.weight = sm->d_tsdf_weight;
   s.voxel_size = sm->voxel_size;
-  return generate<false>(ctx, ctx->stream, s, sm->vps, sm->n_blocks, mw, M);
+  rc = generate<false>(ctx, ctx->stream, s, sm->vps, sm->n_blocks, mw, M);
+  M->holds_mesh = rc == VGX_OK;
+  return rc;
 }
 
 int vgx_submaps_generate_separated_mesh(vgx_ctx ctx, int32_t n, const vgx_submap* submaps, const float* T_M_S, const uint8_t* rgba,
@@ -865,8 +890,10 @@ int vgx_submaps_generate_separated_mesh(vgx_ctx ctx, int32_t n, const vgx_submap
   M->n_blocks = 0;
   M->n_tris = 0;
   M->has_colors = false;
+  M->holds_mesh = false;
   if (n_entries == 0) {
     M->has_colors = true;
+    M->holds_mesh = true;
     return VGX_OK;
   }
   M->h_src.assign((size_t)n, SepSrc{});
@@ -897,6 +924,7 @@ int vgx_submaps_generate_separated_mesh(vgx_ctx ctx, int32_t n, const vgx_submap
     return rc;
   }
   M->has_colors = true;
+  M->holds_mesh = true;
   return VGX_OK;
 }
 
