@@ -8,6 +8,9 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# (seeds, first) of the two map-product fuzzers: tests/test_fuzz_map_cpu.py checks the generator over exactly these
+MAP_LAYERS = (36, 300)
+MAP_MESHES = (60, 300)
 
 
 def _run(script, seeds, first):
@@ -65,3 +68,15 @@ def test_sharded_evaluation_is_the_single_batch_bit_for_bit():
     """random pose graphs sharded over 1-8 contexts by LPT / contiguous / arbitrary placements: fused buffer,
     per-constraint blocks and the scatter -> int64 sum -> assemble route equal the single batch's bits (25 graphs)"""
     assert _run("fuzz_multi", 25, 700) == 0
+
+
+def test_map_layers_random_scenes_bit_identical_to_the_restatements():
+    """the projected map into an empty and a non-empty layer, transformLayer, queries and the evaluation on the projected
+    map: grid-aligned poses, dyadic voxel sizes, planted validity thresholds, block boxes far from the origin"""
+    assert _run("fuzz_map_layers", *MAP_LAYERS) == 0
+
+
+def test_map_meshes_random_scenes_bit_identical_to_the_restatements():
+    """the combined, submap and separated meshes at the drawn min_weight, each welded at two thresholds from 1e-10 to
+    four times the scene's extent (thousands of soup vertices into one key)"""
+    assert _run("fuzz_map_meshes", *MAP_MESHES) == 0
