@@ -1006,6 +1006,86 @@ VGX_API int vgx_submap_query_device(vgx_submap submap, int32_t layer, int32_t fl
                                     int64_t n, const float* points, float* distance, float* gradient, float* weight,
                                     uint8_t* valid);
 
+/* ---- Layer point clouds: voxblox_ros ptcloud_vis.h -------------------------- */
+/* The point-cloud views of a layer that MapEvaluation publishes (map_evaluation.cpp:39, :105, :106):
+ * createSurfaceDistancePointcloudFromTsdfLayer(gt TSDF, 0.6), createDistancePointcloudFromEsdfLayer(error layer) and
+ * createDistancePointcloudFromEsdfLayerSlice(error layer, 2, 3 * voxel_size) -- and the same views of an active submap,
+ * the projected map or a finished submap's ESDF.  A vgx_cloud holds the result on the device: per point the voxel centre
+ * xyz [n][3] f32, intensity [n] f32 and, for VGX_CLOUD_SURFACE_COLOR, rgba [n][4] u8.  Everything about voxblox_ros here
+ * is [recalled]: it is not vendored.
+ * Rules (what the kernels, vgx_cloud.hip, and tests/layer_cloud_ref.py both follow; f32, no contraction):
+ *   observed   an ESDF voxel when observed != 0; a TSDF voxel when weight > min_weight (strictly; a NaN weight is not
+ *              observed).  min_weight defaults to ptcloud_vis.h's kMinWeight = 1e-3f [recalled] and is not used for ESDF
+ *              sources.  The error layer of vgx_evaluate_layers_rmse_cloud is an ESDF-style layer: observed =
+ *              error_set != 0, distance = e.
+ *   kind       VGX_CLOUD_DISTANCE: every observed voxel (a distance that is NaN or infinite passes).
+ *              VGX_CLOUD_SURFACE_DISTANCE: observed and fabsf(distance) < surface_distance (strictly; NaN and infinite
+ *              distances fail).  VGX_CLOUD_SURFACE_COLOR: the same predicate, and the voxel's colour is copied, byte for
+ *              byte, into rgba; only a vgx_tsdf_layer carries colours.
+ *   slice      slice_axis -1: none.  Else a voxel also has to satisfy fabsf(c - slice_value) <= 0.5f * voxel_size + 1e-6f
+ *              (not strictly), c its centre's coordinate on that axis: voxblox_ros' rule with voxblox's
+ *              kFloatingPointTolerance = 1e-6 [recalled], here with the right-hand side formed in f32.  A plane on a
+ *              block face (exactly half a voxel from the rows of centres on either side) therefore takes both rows,
+ *              where those centres and the plane are exact in f32.  A block none of whose vps rows on that axis
+ *              satisfies this is skipped without reading a voxel; the rows are tested with the very comparison above, so
+ *              skipping never changes the result.
+ *   position   the voxel centre origin + (idx + 0.5f) * voxel_size per axis, origin = (float)block_index * block_size,
+ *              block_size = (float)vps * voxel_size -- exactly the centre of vgx_submap_extract_voxel_points and
+ *              vgx_tsdf_layer_merge_submaps (one helper, vgx_internal.h voxel_centre), in the layer's own frame.
+ *   intensity  the voxel's distance, bit for bit, for every kind.
+ *   order      blocks in slot order -- the order of vgx_submap_block_index / vgx_tsdf_layer_download, and for
+ *              vgx_evaluate_layers_rmse_cloud the error blocks' order (test-slot order) -- and inside a block the voxels
+ *              in linear-index order (x fastest).  DEVIATION: voxblox walks its block hash map, whose order is not
+ *              defined; this one is fixed, so a cloud is bit-identical run to run.
+ * The handle is reused from call to call: its device buffers grow on demand; one call at a time per handle.
+ * Refused with VGX_ERR_INVALID before anything is written, the cloud keeping what it held (vgx_last_error says which): a
+ * NULL source or cloud, a cloud of another context, an unknown kind, a slice_axis outside [-1, 2], a surface_distance or
+ * slice_value that is not finite, a min_weight that is negative or not finite (every field is checked whatever the kind),
+ * VGX_CLOUD_SURFACE_COLOR on a submap layer or an error layer, a layer value that is neither VGX_EVAL_LAYER_ESDF nor
+ * _TSDF, a submap layer that is no longer resident in raw form (vgx_submap_release_raw_layers, or an ESDF never
+ * generated), and for vgx_evaluate_layers_rmse_cloud everything vgx_evaluate_layers_rmse refuses.  cfg == NULL: the
+ * defaults.  VGX_ERR_UNSUPPORTED: voxels_per_side other than 8 or 16.  An empty result (an empty layer, nothing passes) is
+ * VGX_OK with n_points = 0.  Out of device memory: VGX_ERR_NOMEM, and the cloud then holds 0 points.
+ * Passes: count per block, rocprim exclusive scan, emit -- two kernels, one scan and one 8-byte memset whatever the size,
+ * and two host synchronisations (the total, to size the output; the end).  Positions come from ballots and popcounts,
+ * never from atomics.  vgx_submap_layer_cloud and vgx_evaluate_layers_rmse_cloud run on the registration stream under
+ * the registration lock; vgx_tsdf_layer_cloud on the TSDF stream under the TSDF lock, behind the scans and merges already
+ * queued (it launches one workgroup per slot of the layer's block pool and reads the allocation counter on the device, so
+ * it does not wait for them first).  All three return with the cloud complete.
+ * vgx_evaluate_layers_rmse_cloud is vgx_evaluate_layers_rmse and the cloud of its error layer in one call: it queues the
+ * same kernels, keeps the error layer in device scratch that dies with the call, and brings back the details with the
+ * point total -- nothing proportional to the layer crosses to the host.  *details is bit for bit what
+ * vgx_evaluate_layers_rmse returns for the same arguments. */
+#define VGX_CLOUD_DISTANCE 0
+#define VGX_CLOUD_SURFACE_DISTANCE 1
+#define VGX_CLOUD_SURFACE_COLOR 2
+/* Fill it with vgx_cloud_config_default() before setting fields; every field is validated. */
+typedef struct vgx_cloud_config {
+  int32_t kind;           /* VGX_CLOUD_DISTANCE */
+  float surface_distance; /* 0.6 (metres; what voxgraph passes, map_evaluation.cpp:39) */
+  float min_weight;       /* 1e-3 (ptcloud_vis.h kMinWeight [recalled]) */
+  int32_t slice_axis;     /* -1: no slice; 0, 1, 2: x, y, z */
+  float slice_value;      /* 0: the plane's coordinate on slice_axis (metres) */
+} vgx_cloud_config;
+typedef struct vgx_cloud_s* vgx_cloud;
+VGX_API void vgx_cloud_config_default(vgx_cloud_config* cfg);
+VGX_API int vgx_cloud_create(vgx_ctx ctx, vgx_cloud* out);
+VGX_API int vgx_cloud_destroy(vgx_cloud cloud);
+/* any pointer may be NULL; *has_colors = 1 after a VGX_CLOUD_SURFACE_COLOR call */
+VGX_API int vgx_cloud_stats(vgx_cloud cloud, int64_t* n_points, int32_t* has_colors);
+/* xyz [n][3] f32, intensity [n] f32, rgba [n][4] u8; any may be NULL.  rgba on a cloud without colours: VGX_ERR_INVALID. */
+VGX_API int vgx_cloud_download(vgx_cloud cloud, float* xyz, float* intensity, uint8_t* rgba);
+/* DEVICE pointers to the same three arrays, for a consumer that stays on the device (NULL where the cloud has none: 0
+ * points, no colours); valid until the next producing call on the handle or its destruction.  Any may be NULL. */
+VGX_API int vgx_cloud_device_pointers(vgx_cloud cloud, const float** xyz, const float** intensity, const uint8_t** rgba);
+/* a finished submap's raw layer: layer = VGX_EVAL_LAYER_ESDF / VGX_EVAL_LAYER_TSDF */
+VGX_API int vgx_submap_layer_cloud(vgx_submap submap, int32_t layer, const vgx_cloud_config* cfg, vgx_cloud cloud);
+/* a vgx_tsdf_layer: the active submap or the projected map, colours included */
+VGX_API int vgx_tsdf_layer_cloud(vgx_tsdf_layer layer, const vgx_cloud_config* cfg, vgx_cloud cloud);
+VGX_API int vgx_evaluate_layers_rmse_cloud(vgx_submap gt, vgx_submap test, int32_t layer, int32_t mode,
+                                           vgx_voxel_evaluation_details* details, const vgx_cloud_config* cfg,
+                                           vgx_cloud cloud);
+
 /* ---------------------------------------------------------------------------
  * Saved maps: cblox submap-collection files and voxblox layer files.
  *

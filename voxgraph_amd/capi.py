@@ -70,6 +70,15 @@ class MeshConfig(C.Structure):
     _fields_ = [("min_weight", C.c_float)]
 
 
+class CloudConfig(C.Structure):
+    """vgx_cloud_config: which voxels of a layer become points (include/voxgraph_amd.h, "Layer point clouds")."""
+    _fields_ = [("kind", C.c_int32), ("surface_distance", C.c_float), ("min_weight", C.c_float),
+                ("slice_axis", C.c_int32), ("slice_value", C.c_float)]
+
+
+CLOUD_DISTANCE, CLOUD_SURFACE_DISTANCE, CLOUD_SURFACE_COLOR = 0, 1, 2
+
+
 class EvaluationDetails(C.Structure):
     """vgx_voxel_evaluation_details: voxblox::utils::VoxelEvaluationDetails plus the f64 sum and the true min |e|."""
     _fields_ = [("rmse", C.c_float), ("max_error", C.c_float), ("min_error", C.c_float),
@@ -224,6 +233,16 @@ SIGNATURES = {
     "vgx_connected_mesh_stats": (C.c_int, [vp, i64p, i64p, i32p]),
     "vgx_connected_mesh_download": (C.c_int, [vp, f32p, f32p, u8p, u32p]),
     "vgx_connected_mesh_write_ply": (C.c_int, [vp, C.c_char_p]),
+    "vgx_cloud_config_default": (None, [C.POINTER(CloudConfig)]),
+    "vgx_cloud_create": (C.c_int, [vp, C.POINTER(vp)]),
+    "vgx_cloud_destroy": (C.c_int, [vp]),
+    "vgx_cloud_stats": (C.c_int, [vp, i64p, i32p]),
+    "vgx_cloud_download": (C.c_int, [vp, f32p, f32p, u8p]),
+    "vgx_cloud_device_pointers": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+    "vgx_submap_layer_cloud": (C.c_int, [vp, C.c_int32, C.POINTER(CloudConfig), vp]),
+    "vgx_tsdf_layer_cloud": (C.c_int, [vp, C.POINTER(CloudConfig), vp]),
+    "vgx_evaluate_layers_rmse_cloud": (C.c_int, [vp, vp, C.c_int32, C.c_int32, C.POINTER(EvaluationDetails),
+                                                 C.POINTER(CloudConfig), vp]),
     "vgx_submap_query": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.c_int64, f32p, f32p, f32p, f32p, u8p]),
     "vgx_submap_query_device": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.c_int64, vp, vp, vp, vp, vp]),
     "vgx_map_file_open": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(vp)]),
@@ -571,6 +590,15 @@ class Submap:
         if sync:
             self.ctx.synchronize()
         return MapQuery(d, g, w, v)
+
+    def layer_cloud(self, layer="esdf", config=None, cloud=None):
+        """The point-cloud view of the raw ESDF or TSDF layer (vgx_submap_layer_cloud; config: cloud_config(...)).
+        Returns the Cloud (a new one when cloud is None)."""
+        cloud = cloud if cloud is not None else Cloud(self.ctx)
+        which = {"esdf": EVAL_LAYER_ESDF, "tsdf": EVAL_LAYER_TSDF}.get(layer, layer)
+        self.ctx.check(self.ctx.lib.vgx_submap_layer_cloud(self.h, int(which), None if config is None else C.byref(config),
+                                                           cloud.h))
+        return cloud
 
     def release_raw_layers(self):
         self.ctx.check(self.ctx.lib.vgx_submap_release_raw_layers(self.h))
@@ -1050,6 +1078,13 @@ class TsdfLayer:
         self.ctx.check(self.ctx.lib.vgx_tsdf_layer_generate_mesh(self.h, C.byref(cfg), mesh.h))
         return mesh
 
+    def cloud(self, config=None, cloud=None):
+        """The point-cloud view of this layer, colours included (vgx_tsdf_layer_cloud; config: cloud_config(...)).
+        Returns the Cloud (a new one when cloud is None)."""
+        cloud = cloud if cloud is not None else Cloud(self.ctx)
+        self.ctx.check(self.ctx.lib.vgx_tsdf_layer_cloud(self.h, None if config is None else C.byref(config), cloud.h))
+        return cloud
+
     def download(self):
         n, _ = self.stats()
         nv = self.vps ** 3
@@ -1148,6 +1183,65 @@ def evaluate_layers_rmse(gt, test, layer=EVAL_LAYER_ESDF, mode=EVAL_IGNORE_BEHIN
     return det.as_dict(), (bi[:m], d[:m], st[:m])
 
 
+def cloud_config(**kw):
+    """vgx_cloud_config_default() with fields overridden: kind, surface_distance, min_weight, slice_axis, slice_value."""
+    cfg = CloudConfig()
+    load().vgx_cloud_config_default(C.byref(cfg))
+    for k, v in kw.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(k)
+        setattr(cfg, k, v)
+    return cfg
+
+
+class Cloud:
+    """A layer's point cloud on the GPU (vgx_cloud): voxel centres, intensity = distance, optionally colours; reused from
+    call to call."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        h = vp()
+        ctx.check(ctx.lib.vgx_cloud_create(ctx.h, C.byref(h)))
+        self.h = h
+
+    def stats(self):
+        """(points, has_colors)"""
+        n, has = C.c_int64(), C.c_int32()
+        self.ctx.check(self.ctx.lib.vgx_cloud_stats(self.h, C.byref(n), C.byref(has)))
+        return n.value, bool(has.value)
+
+    def download(self):
+        """(xyz [n][3] f32, intensity [n] f32, rgba [n][4] uint8 or None)"""
+        n, has = self.stats()
+        xyz = np.zeros((n, 3), np.float32)
+        inten = np.zeros(n, np.float32)
+        rgba = np.zeros((n, 4), np.uint8) if has else None
+        self.ctx.check(self.ctx.lib.vgx_cloud_download(self.h, _ptr(xyz, f32p), _ptr(inten, f32p), _ptr(rgba, u8p)))
+        return xyz, inten, rgba
+
+    def device_pointers(self):
+        """(xyz, intensity, rgba) device addresses as ints (None where the cloud has none)"""
+        p = [vp(), vp(), vp()]
+        self.ctx.check(self.ctx.lib.vgx_cloud_device_pointers(self.h, C.byref(p[0]), C.byref(p[1]), C.byref(p[2])))
+        return tuple(x.value for x in p)
+
+    def destroy(self):
+        if self.h:
+            self.ctx.lib.vgx_cloud_destroy(self.h)
+            self.h = None
+
+
+def evaluate_layers_rmse_cloud(gt, test, layer=EVAL_LAYER_ESDF, mode=EVAL_IGNORE_BEHIND_TEST, config=None, cloud=None):
+    """evaluateLayersRmse and the point-cloud view of its error layer in one call (vgx_evaluate_layers_rmse_cloud): the
+    error layer never leaves the device.  Returns (details dict, Cloud)."""
+    ctx = gt.ctx
+    cloud = cloud if cloud is not None else Cloud(ctx)
+    det = EvaluationDetails()
+    ctx.check(ctx.lib.vgx_evaluate_layers_rmse_cloud(gt.h, test.h, int(layer), int(mode), C.byref(det),
+                                                     None if config is None else C.byref(config), cloud.h))
+    return det.as_dict(), cloud
+
+
 def decoupled_exp_pose(pose4):
     """Transformation::exp((x, y, z, 0, 0, yaw)) as [qw,qx,qy,qz, tx,ty,tz] f64: minkindr's decoupled exp (the
     translation is taken as it is, the rotation is about z) -- map_evaluation.cpp:155-159.  Formed in f64; the library
@@ -1167,7 +1261,7 @@ def pose7_inverse(T):
 
 
 def map_evaluation(ctx, submaps, poses, gt_submap, align, voxel_size=None, vps=None, error_layer=False,
-                   min_voxel_weight=1.0, max_voxel_distance=0.3):
+                   min_voxel_weight=1.0, max_voxel_distance=0.3, cloud=None):
     """MapEvaluation::evaluate (map_evaluation.cpp:59-114) on the device.  submaps / poses ([n][7]) are the collection,
     gt_submap the ground truth (a submap holding its raw TSDF layer, identity pose).  Steps: the projected map; both
     finished (ESDF, kVoxels points); pose4 = align(reference = projected map, reading = ground truth) -- the caller's
@@ -1175,7 +1269,9 @@ def map_evaluation(ctx, submaps, poses, gt_submap, align, voxel_size=None, vps=N
     alignSubmapAtoSubmapB does; the ground truth resampled by T = Transformation::exp(x, y, z, 0, 0, yaw)
     (vgx_tsdf_layer_transform_submap) and its ESDF regenerated; evaluateLayersRmse(gt ESDF, projected ESDF,
     kIgnoreErrorBehindTestSurface).  Returns {"details", "pose4", "T_ground_truth__reading" (= T.inverse(), [7] f64)}
-    and, with error_layer=True, "error_layer"."""
+    and, with error_layer=True, "error_layer".  cloud=cloud_config(...): the evaluation goes through
+    vgx_evaluate_layers_rmse_cloud instead and "error_cloud" holds the Cloud of the error layer (the caller destroys it);
+    the details are the same bit for bit."""
     vs = float(voxel_size if voxel_size is not None else gt_submap.voxel_size)
     vps = int(vps if vps is not None else gt_submap.vps)
     proj_layer = TsdfLayer(ctx, vs, vps)
@@ -1192,8 +1288,14 @@ def map_evaluation(ctx, submaps, poses, gt_submap, align, voxel_size=None, vps=N
         gt_layer.transform_submap(gt_submap, T)           # transformSubmap(T): transformLayer, then finishSubmap()
         gt_t = Submap.from_tsdf_layer(ctx, gt_layer, int(ctx.lib.vgx_submap_id(gt_submap.h)))
         gt_t.generate_esdf()
-        res = evaluate_layers_rmse(gt_t, proj, EVAL_LAYER_ESDF, EVAL_IGNORE_BEHIND_TEST, error_layer)
         out = {"pose4": pose4, "T_ground_truth__reading": pose7_inverse(T)}
+        if cloud is not None:
+            if error_layer:
+                raise ValueError("map_evaluation: error_layer and cloud are alternatives")
+            out["details"], out["error_cloud"] = evaluate_layers_rmse_cloud(gt_t, proj, EVAL_LAYER_ESDF,
+                                                                            EVAL_IGNORE_BEHIND_TEST, cloud)
+            return out
+        res = evaluate_layers_rmse(gt_t, proj, EVAL_LAYER_ESDF, EVAL_IGNORE_BEHIND_TEST, error_layer)
         if error_layer:
             out["details"], out["error_layer"] = res
         else:

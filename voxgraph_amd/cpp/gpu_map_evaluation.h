@@ -110,8 +110,12 @@ class GpuMapEvaluation {
   GpuMapEvaluation(vgx_ctx ctx, vgx_submap ground_truth, float voxel_size, int voxels_per_side)
       : ctx_(ctx), ground_truth_(ground_truth), voxel_size_(voxel_size), vps_(voxels_per_side) {}
 
+  // error_cloud (with its config; gpu_layer_pointcloud.h): the evaluation goes through vgx_evaluate_layers_rmse_cloud and
+  // the handle receives the point-cloud view of the error layer, which then never leaves the device -- the same details
+  // bit for bit.  An alternative to error_layer, not an addition to it.
   template <typename CollectionT>
-  EvaluationDetails evaluate(const CollectionT& collection, GpuErrorLayer* error_layer = nullptr) const {
+  EvaluationDetails evaluate(const CollectionT& collection, GpuErrorLayer* error_layer = nullptr,
+                             const vgx_cloud_config* error_cloud_config = nullptr, vgx_cloud error_cloud = nullptr) const {
     using map_evaluation_detail::check;
     // the projected map, as a submap (map_evaluation.cpp:72-76)
     map_evaluation_detail::OwnedSubmap projected;
@@ -157,8 +161,16 @@ class GpuMapEvaluation {
     // transformSubmap(T) (:86), then evaluateLayersRmse(gt ESDF, projected ESDF, kIgnoreErrorBehindTestSurface) (:90-95)
     map_evaluation_detail::OwnedSubmap transformed;
     transformed.h = TransformSubmapOnGpu(ctx_, ground_truth_, T, voxel_size_, vps_, vgx_submap_id(ground_truth_));
-    out.details = EvaluateLayersRmseOnGpu(ctx_, transformed.h, projected.h, VGX_EVAL_LAYER_ESDF, VGX_EVAL_IGNORE_BEHIND_TEST,
-                                          vps_, error_layer);
+    if (error_cloud) {
+      if (error_layer) throw std::invalid_argument("GpuMapEvaluation::evaluate: error_layer and error_cloud are alternatives");
+      check(ctx_,
+            vgx_evaluate_layers_rmse_cloud(transformed.h, projected.h, VGX_EVAL_LAYER_ESDF, VGX_EVAL_IGNORE_BEHIND_TEST,
+                                           &out.details, error_cloud_config, error_cloud),
+            "vgx_evaluate_layers_rmse_cloud");
+    } else {
+      out.details = EvaluateLayersRmseOnGpu(ctx_, transformed.h, projected.h, VGX_EVAL_LAYER_ESDF, VGX_EVAL_IGNORE_BEHIND_TEST,
+                                            vps_, error_layer);
+    }
     // T_projected_map__ground_truth.inverse(): rotation about -yaw, translation -(R^-1 t)
     const double c = std::cos(layer_A_pose[3]), s = std::sin(layer_A_pose[3]);
     const double tx = layer_A_pose[0], ty = layer_A_pose[1], tz = layer_A_pose[2];

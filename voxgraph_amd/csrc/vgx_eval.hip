@@ -27,12 +27,6 @@ struct EvalPartial {  // per test block, 32 B
   int32_t n_eval, n_ign, n_non, pad;
 };
 
-struct EvalTotals {
-  double sum;
-  float max_abs, min_abs;
-  long long n_eval, n_ign, n_non, n_err_blocks;
-};
-
 struct EvalLut {
   const int32_t* lut;
   int3 mn, dim;
@@ -233,10 +227,6 @@ using namespace vgx;
 
 namespace {
 
-const char* kEvalFn = "vgx_evaluate_layers_rmse: ";
-
-int eval_fail(vgx_ctx ctx, const std::string& msg) { return set_error(ctx, VGX_ERR_INVALID, kEvalFn + msg); }
-
 EvalLut lut_of(vgx_submap sm) {
   return EvalLut{sm->d_lut, make_int3(sm->lut_min[0], sm->lut_min[1], sm->lut_min[2]),
                  make_int3(sm->lut_dim[0], sm->lut_dim[1], sm->lut_dim[2])};
@@ -249,49 +239,51 @@ bool layer_resident(vgx_submap sm, int32_t layer) {
 
 }  // namespace
 
-extern "C" int vgx_evaluate_layers_rmse(vgx_submap gt, vgx_submap test, int32_t layer, int32_t mode,
-                                        vgx_voxel_evaluation_details* details, int32_t* error_block_index,
-                                        float* error_distance, uint8_t* error_set, int32_t* n_error_blocks) {
+namespace vgx {
+
+int eval_check(const char* fn, vgx_submap gt, vgx_submap test, int32_t layer, int32_t mode, const void* details) {
   if (!gt || !test) return VGX_ERR_INVALID;
   vgx_ctx ctx = gt->ctx;
-  if (test->ctx != ctx) return eval_fail(ctx, "the submaps belong to different contexts");
-  if (!details) return eval_fail(ctx, "NULL details");
-  if (layer != VGX_EVAL_LAYER_ESDF && layer != VGX_EVAL_LAYER_TSDF) return eval_fail(ctx, "layer is neither ESDF nor TSDF");
-  if (mode < VGX_EVAL_ALL_VOXELS || mode > VGX_EVAL_IGNORE_BEHIND_ALL) return eval_fail(ctx, "mode out of range");
+  auto fail = [ctx, fn](const std::string& msg) { return set_error(ctx, VGX_ERR_INVALID, std::string(fn) + ": " + msg); };
+  if (test->ctx != ctx) return fail("the submaps belong to different contexts");
+  if (!details) return fail("NULL details");
+  if (layer != VGX_EVAL_LAYER_ESDF && layer != VGX_EVAL_LAYER_TSDF) return fail("layer is neither ESDF nor TSDF");
+  if (mode < VGX_EVAL_ALL_VOXELS || mode > VGX_EVAL_IGNORE_BEHIND_ALL) return fail("mode out of range");
   if (gt->voxel_size != test->voxel_size || gt->vps != test->vps)
-    return eval_fail(ctx, "voxel_size / voxels_per_side differ (CHECK_EQ in the reference)");
+    return fail("voxel_size / voxels_per_side differ (CHECK_EQ in the reference)");
   if (!layer_resident(gt, layer) || !layer_resident(test, layer))
-    return eval_fail(ctx, std::string(layer == VGX_EVAL_LAYER_ESDF ? "ESDF" : "TSDF") +
-                              " layer not resident (released, or never generated)");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  VGX_HIP(ctx, hipSetDevice(ctx->device));
+    return fail(std::string(layer == VGX_EVAL_LAYER_ESDF ? "ESDF" : "TSDF") + " layer not resident (released, or never generated)");
+  return VGX_OK;
+}
+
+int eval_enqueue(vgx_submap gt, vgx_submap test, int32_t layer, int32_t mode, bool want_index, bool want_distance, bool want_set,
+                 EvalDevice& D) {
+  vgx_ctx ctx = gt->ctx;
   hipStream_t st = ctx->stream;
   const int vps = test->vps, vox = vps * vps * vps;
   const int n_test = test->n_blocks, n_gt = gt->n_blocks;
   const bool tsdf = layer == VGX_EVAL_LAYER_TSDF;
-  const bool want_err = error_block_index || error_distance || error_set;
-
-  DeviceScratch d_slot, d_has, d_pos, d_part, d_tot, d_tmp, d_ed, d_es, d_ebi;
-  VGX_HIP(ctx, d_tot.alloc(sizeof(EvalTotals)));
+  const bool want_err = want_index || want_distance || want_set;
+  VGX_HIP(ctx, D.tot.alloc(sizeof(EvalTotals)));
   if (n_test > 0) {
-    VGX_HIP(ctx, d_slot.alloc((size_t)n_test * 4));
-    VGX_HIP(ctx, d_has.alloc((size_t)n_test * 4));
-    VGX_HIP(ctx, d_part.alloc((size_t)n_test * sizeof(EvalPartial)));
+    VGX_HIP(ctx, D.slot.alloc((size_t)n_test * 4));
+    VGX_HIP(ctx, D.has.alloc((size_t)n_test * 4));
+    VGX_HIP(ctx, D.part.alloc((size_t)n_test * sizeof(EvalPartial)));
     hipLaunchKernelGGL(eval_match_kernel, dim3((unsigned)((n_test + 255) / 256)), dim3(256), 0, st, test->d_block_index, n_test,
-                       lut_of(gt), d_slot.as<int32_t>(), d_has.as<int32_t>());
+                       lut_of(gt), D.slot.as<int32_t>(), D.has.as<int32_t>());
     VGX_HIP(ctx, hipGetLastError());
     if (want_err) {
-      VGX_HIP(ctx, d_pos.alloc((size_t)n_test * 4));
+      VGX_HIP(ctx, D.pos.alloc((size_t)n_test * 4));
       size_t scan_bytes = 0;
-      VGX_HIP(ctx, rocprim::exclusive_scan(nullptr, scan_bytes, d_has.as<int32_t>(), d_pos.as<int32_t>(), 0, (size_t)n_test,
+      VGX_HIP(ctx, rocprim::exclusive_scan(nullptr, scan_bytes, D.has.as<int32_t>(), D.pos.as<int32_t>(), 0, (size_t)n_test,
                                            rocprim::plus<int32_t>(), st));
-      VGX_HIP(ctx, d_tmp.alloc(std::max<size_t>(scan_bytes, 4)));
-      VGX_HIP(ctx, rocprim::exclusive_scan(d_tmp.p, scan_bytes, d_has.as<int32_t>(), d_pos.as<int32_t>(), 0, (size_t)n_test,
+      VGX_HIP(ctx, D.tmp.alloc(std::max<size_t>(scan_bytes, 4)));
+      VGX_HIP(ctx, rocprim::exclusive_scan(D.tmp.p, scan_bytes, D.has.as<int32_t>(), D.pos.as<int32_t>(), 0, (size_t)n_test,
                                            rocprim::plus<int32_t>(), st));
       // room for every test block: the error blocks are the test blocks with a gt counterpart
-      if (error_distance) VGX_HIP(ctx, d_ed.alloc((size_t)n_test * vox * 4));
-      if (error_set) VGX_HIP(ctx, d_es.alloc((size_t)n_test * vox));
-      if (error_block_index) VGX_HIP(ctx, d_ebi.alloc((size_t)n_test * 12));
+      if (want_distance) VGX_HIP(ctx, D.ed.alloc((size_t)n_test * vox * 4));
+      if (want_set) VGX_HIP(ctx, D.es.alloc((size_t)n_test * vox));
+      if (want_index) VGX_HIP(ctx, D.ebi.alloc((size_t)n_test * 12));
     }
     const float* gd = tsdf ? gt->d_tsdf_distance : gt->d_esdf_distance;
     const void* go = tsdf ? (const void*)gt->d_tsdf_weight : (const void*)gt->d_esdf_observed;
@@ -299,24 +291,18 @@ extern "C" int vgx_evaluate_layers_rmse(vgx_submap gt, vgx_submap test, int32_t 
     const void* to = tsdf ? (const void*)test->d_tsdf_weight : (const void*)test->d_esdf_observed;
     auto kernel = vps == 16 ? (tsdf ? eval_block_kernel<16, true> : eval_block_kernel<16, false>)
                             : (tsdf ? eval_block_kernel<8, true> : eval_block_kernel<8, false>);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)n_test), dim3(vps == 16 ? 256 : 128), 0, st, d_slot.as<int32_t>(), gd, go, td, to,
-                       test->d_block_index, (int)mode, d_part.as<EvalPartial>(), want_err ? d_pos.as<int32_t>() : nullptr,
-                       d_ed.as<float>(), d_es.as<uint8_t>(), d_ebi.as<int32_t>());
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n_test), dim3(vps == 16 ? 256 : 128), 0, st, D.slot.as<int32_t>(), gd, go, td, to,
+                       test->d_block_index, (int)mode, D.part.as<EvalPartial>(), want_err ? D.pos.as<int32_t>() : nullptr,
+                       D.ed.as<float>(), D.es.as<uint8_t>(), D.ebi.as<int32_t>());
     VGX_HIP(ctx, hipGetLastError());
   }
-  hipLaunchKernelGGL(eval_fold_kernel, dim3(1), dim3(1024), 0, st, d_part.as<EvalPartial>(), n_test, d_has.as<int32_t>(),
-                     gt->d_block_index, n_gt, lut_of(test), vox, d_tot.as<EvalTotals>());
+  hipLaunchKernelGGL(eval_fold_kernel, dim3(1), dim3(1024), 0, st, D.part.as<EvalPartial>(), n_test, D.has.as<int32_t>(),
+                     gt->d_block_index, n_gt, lut_of(test), vox, D.tot.as<EvalTotals>());
   VGX_HIP(ctx, hipGetLastError());
-  EvalTotals tot{};
-  VGX_HIP(ctx, hipMemcpyAsync(&tot, d_tot.p, sizeof(tot), hipMemcpyDeviceToHost, st));
-  VGX_HIP(ctx, hipStreamSynchronize(st));
-  const size_t m = (size_t)tot.n_err_blocks;
-  if (m > 0) {
-    if (error_distance) VGX_HIP(ctx, hipMemcpyAsync(error_distance, d_ed.p, m * vox * 4, hipMemcpyDeviceToHost, st));
-    if (error_set) VGX_HIP(ctx, hipMemcpyAsync(error_set, d_es.p, m * vox, hipMemcpyDeviceToHost, st));
-    if (error_block_index) VGX_HIP(ctx, hipMemcpyAsync(error_block_index, d_ebi.p, m * 12, hipMemcpyDeviceToHost, st));
-    VGX_HIP(ctx, hipStreamSynchronize(st));
-  }
+  return VGX_OK;
+}
+
+void eval_details(const EvalTotals& tot, vgx_voxel_evaluation_details* details) {
   vgx_voxel_evaluation_details r{};
   r.total_squared_error = tot.sum;
   r.num_evaluated_voxels = tot.n_eval;
@@ -328,6 +314,34 @@ extern "C" int vgx_evaluate_layers_rmse(vgx_submap gt, vgx_submap test, int32_t 
   r.min_error = 0.0f;  // voxblox: initialised to 0, then only min() [recalled]
   r.min_abs_error = tot.n_eval > 0 ? tot.min_abs : 0.0f;
   *details = r;
+}
+
+}  // namespace vgx
+
+extern "C" int vgx_evaluate_layers_rmse(vgx_submap gt, vgx_submap test, int32_t layer, int32_t mode,
+                                        vgx_voxel_evaluation_details* details, int32_t* error_block_index,
+                                        float* error_distance, uint8_t* error_set, int32_t* n_error_blocks) {
+  int rc = eval_check("vgx_evaluate_layers_rmse", gt, test, layer, mode, details);
+  if (rc != VGX_OK) return rc;
+  vgx_ctx ctx = gt->ctx;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  VGX_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const int vox = test->vps * test->vps * test->vps;
+  EvalDevice D;
+  rc = eval_enqueue(gt, test, layer, mode, error_block_index != nullptr, error_distance != nullptr, error_set != nullptr, D);
+  if (rc != VGX_OK) return rc;
+  EvalTotals tot{};
+  VGX_HIP(ctx, hipMemcpyAsync(&tot, D.tot.p, sizeof(tot), hipMemcpyDeviceToHost, st));
+  VGX_HIP(ctx, hipStreamSynchronize(st));
+  const size_t m = (size_t)tot.n_err_blocks;
+  if (m > 0) {
+    if (error_distance) VGX_HIP(ctx, hipMemcpyAsync(error_distance, D.ed.p, m * vox * 4, hipMemcpyDeviceToHost, st));
+    if (error_set) VGX_HIP(ctx, hipMemcpyAsync(error_set, D.es.p, m * vox, hipMemcpyDeviceToHost, st));
+    if (error_block_index) VGX_HIP(ctx, hipMemcpyAsync(error_block_index, D.ebi.p, m * 12, hipMemcpyDeviceToHost, st));
+    VGX_HIP(ctx, hipStreamSynchronize(st));
+  }
+  eval_details(tot, details);
   if (n_error_blocks) *n_error_blocks = (int32_t)tot.n_err_blocks;
   return VGX_OK;
 }

@@ -93,9 +93,9 @@ __global__ __launch_bounds__(256) void extract_write_kernel(
     if (keep) {
       int64_t at = running + wave_off + before;
       int ix = v % VPS, iy = (v / VPS) % VPS, iz = v / (VPS * VPS);
-      float x = ox + ((float)ix + 0.5f) * voxel_size;
-      float y = oy + ((float)iy + 0.5f) * voxel_size;
-      float z = oz + ((float)iz + 0.5f) * voxel_size;
+      float x = voxel_centre(ox, ix, voxel_size);
+      float y = voxel_centre(oy, iy, voxel_size);
+      float z = voxel_centre(oz, iz, voxel_size);
       float d = esdf_d ? esdf_d[base + v] : td;  // VSM:185-192
       xyzd[at] = make_float4(x, y, z, d);
       weight[at] = tw;  // VSM:195-197

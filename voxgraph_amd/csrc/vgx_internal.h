@@ -409,6 +409,13 @@ struct DeviceScratch {
 };
 void set_global_error(const std::string& msg);
 
+// The centre of voxel `idx` (one axis) of the block whose low corner on that axis is `origin` = (float)block_index *
+// block_size, block_size = (float)vps * voxel_size: Block::computeCoordinatesFromLinearIndex [recalled], in f32, no
+// contraction.  The one place this is written: the kVoxels points, the projected map and the layer clouds call it.
+__host__ __device__ __forceinline__ float voxel_centre(float origin, int idx, float voxel_size) {
+  return origin + ((float)idx + 0.5f) * voxel_size;
+}
+
 #define VGX_HIP(ctx, call)                                                      \
   do {                                                                          \
     hipError_t e__ = (call);                                                    \
@@ -430,6 +437,23 @@ struct MeshView {
 };
 std::mutex& mesh_mutex(vgx_mesh M);
 MeshView mesh_view(vgx_mesh M);
+
+// vgx_eval.hip for vgx_cloud.hip (vgx_evaluate_layers_rmse_cloud): one evaluation left on the device.  eval_check
+// refuses what vgx_evaluate_layers_rmse refuses (fn: the prefix of the message); eval_enqueue (the caller holds ctx->mu,
+// the device is set) queues the passes of vgx_evaluate_layers_rmse on ctx->stream and leaves the totals and, when asked
+// for, the error layer in `D` (freed with it); eval_details turns the totals, once on the host, into the details.
+struct EvalTotals {
+  double sum;
+  float max_abs, min_abs;
+  long long n_eval, n_ign, n_non, n_err_blocks;
+};
+struct EvalDevice {
+  DeviceScratch slot, has, pos, part, tot, tmp, ed, es, ebi;  // tot: EvalTotals; ed / es / ebi: [n_test] error blocks
+};
+int eval_check(const char* fn, vgx_submap gt, vgx_submap test, int32_t layer, int32_t mode, const void* details);
+int eval_enqueue(vgx_submap gt, vgx_submap test, int32_t layer, int32_t mode, bool want_index, bool want_distance, bool want_set,
+                 EvalDevice& D);
+void eval_details(const EvalTotals& tot, vgx_voxel_evaluation_details* details);
 
 // kernels' launch wrappers implemented in the .hip files
 #ifndef VGX_TOOLING_LIBRARY

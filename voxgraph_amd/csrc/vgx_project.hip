@@ -195,7 +195,7 @@ __global__ __launch_bounds__(VPS * VPS * VPS / PER) void project_merge_kernel(co
       const int lin = threadIdx.x + T * k;
       const int vx = lin % VPS, vy = (lin / VPS) % VPS, vz = lin / (VPS * VPS);
       // Block::computeCoordinatesFromLinearIndex: origin + (idx + 0.5) * voxel_size
-      const float c[3] = {ox + ((float)vx + 0.5f) * vs, oy + ((float)vy + 0.5f) * vs, oz + ((float)vz + 0.5f) * vs};
+      const float c[3] = {voxel_centre(ox, vx, vs), voxel_centre(oy, vy, vs), voxel_centre(oz, vz, vs)};
       float p[3];
       rigid_apply(s.q_sl, s.t_sl, c, p);
       sd[k] = 0.0f;
