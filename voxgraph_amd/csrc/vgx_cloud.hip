@@ -227,49 +227,22 @@ struct vgx_cloud_s {
   std::mutex mu;
   int64_t n_points = 0;  // the cloud held now
   bool has_colors = false;
-  // output, grown on demand
-  float* d_xyz = nullptr;        // [cap][3]
-  float* d_intensity = nullptr;  // [cap]
-  uint32_t* d_rgba = nullptr;    // [color_cap] bytes r g b a
-  int64_t cap = 0, color_cap = 0;
+  // output, grown on demand to exactly what a cloud needs (no slack, no floor)
+  DeviceBuffer d_xyz;        // float [cap][3]
+  DeviceBuffer d_intensity;  // float [cap]
+  DeviceBuffer d_rgba;       // u32 [color_cap] bytes r g b a
 };
 
 namespace {
 
-void free_points(vgx_cloud C) {
-  for (void* p : {(void*)C->d_xyz, (void*)C->d_intensity, (void*)C->d_rgba})
-    if (p) (void)hipFree(p);
-  C->d_xyz = C->d_intensity = nullptr;
-  C->d_rgba = nullptr;
-  C->cap = C->color_cap = 0;
-}
-
-int cloud_alloc_error(vgx_ctx ctx, hipError_t e, const char* what) {
-  (void)hipGetLastError();  // (clear the sticky out-of-memory status)
-  return set_error(ctx, e == hipErrorOutOfMemory ? VGX_ERR_NOMEM : VGX_ERR_HIP,
-                   std::string("cloud: allocating ") + what + ": " + hipGetErrorString(e));
-}
-
 int ensure_points(vgx_cloud C, int64_t n, bool colors) {
-  if (n > C->cap) {
-    free_points(C);
-    hipError_t e = hipMalloc(&C->d_xyz, (size_t)n * 12);
-    if (e == hipSuccess) e = hipMalloc(&C->d_intensity, (size_t)n * 4);
-    if (e != hipSuccess) {
-      free_points(C);
-      return cloud_alloc_error(C->ctx, e, "points");
-    }
-    C->cap = n;
+  if ((size_t)n * 4 > C->d_intensity.bytes) {
+    C->d_rgba.release();
+    const hipError_t e = alloc_group({{&C->d_xyz, (size_t)n * 12}, {&C->d_intensity, (size_t)n * 4}});
+    if (e != hipSuccess) return alloc_error(C->ctx, e, "cloud: allocating points");
   }
-  if (colors && n > C->color_cap) {
-    if (C->d_rgba) (void)hipFree(C->d_rgba);
-    C->d_rgba = nullptr;
-    C->color_cap = 0;
-    const hipError_t e = hipMalloc(&C->d_rgba, (size_t)n * 4);
-    if (e != hipSuccess) return cloud_alloc_error(C->ctx, e, "colours");
-    C->color_cap = n;
-  }
-  return VGX_OK;
+  const hipError_t e = colors ? C->d_rgba.reserve((size_t)n * 4) : hipSuccess;
+  return e == hipSuccess ? VGX_OK : alloc_error(C->ctx, e, "cloud: allocating colours");
 }
 
 // Refusals shared by the three producers, before anything is written; cfg == NULL: the defaults.
@@ -299,7 +272,7 @@ template <int VPS, int SRC>
 void launch_emit(hipStream_t st, const CloudSrc& s, const CloudRule& r, int slots, const long long* offsets, vgx_cloud C,
                  bool colors) {
   hipLaunchKernelGGL((cloud_emit_kernel<VPS, SRC>), dim3((unsigned)slots), dim3(VPS == 16 ? 256 : 128), 0, st, s, r, offsets,
-                     C->d_xyz, C->d_intensity, colors ? C->d_rgba : nullptr);
+                     C->d_xyz.as<float>(), C->d_intensity.as<float>(), colors ? C->d_rgba.as<uint32_t>() : nullptr);
 }
 
 // The three passes over `slots` block slots on stream st (the caller holds the cloud's and the stream's locks).  `extra`
@@ -310,7 +283,7 @@ int cloud_generate(vgx_ctx ctx, hipStream_t st, int src, int vps, const CloudSrc
   C->n_points = 0;
   C->has_colors = colors;
   long long total = 0;
-  DeviceScratch d_counts, d_offsets, d_tmp;
+  DeviceBuffer d_counts, d_offsets, d_tmp;
   if (slots > 0) {
     const size_t n = (size_t)slots + 1;  // the last item is 0: its exclusive sum is the total
     VGX_HIP(ctx, d_counts.alloc(n * 8));
@@ -326,12 +299,11 @@ int cloud_generate(vgx_ctx ctx, hipStream_t st, int src, int vps, const CloudSrc
       else launch_count<8, kCloudSrcPacked>(st, s, r, slots, d_counts.as<long long>());
     }
     VGX_HIP(ctx, hipGetLastError());
-    size_t scan_bytes = 0;
-    VGX_HIP(ctx, rocprim::exclusive_scan(nullptr, scan_bytes, d_counts.as<long long>(), d_offsets.as<long long>(), 0ll, n,
-                                         rocprim::plus<long long>(), st));
-    VGX_HIP(ctx, d_tmp.alloc(std::max<size_t>(scan_bytes, 8)));
-    VGX_HIP(ctx, rocprim::exclusive_scan(d_tmp.p, scan_bytes, d_counts.as<long long>(), d_offsets.as<long long>(), 0ll, n,
-                                         rocprim::plus<long long>(), st));
+    auto scan = [&](void* tmp, size_t& bytes) {
+      return rocprim::exclusive_scan(tmp, bytes, d_counts.as<long long>(), d_offsets.as<long long>(), 0ll, n, rocprim::plus<long long>(),
+                                     st);
+    };
+    VGX_HIP(ctx, run_with_temp(d_tmp, scan));
     VGX_HIP(ctx, hipMemcpyAsync(&total, d_offsets.as<long long>() + slots, 8, hipMemcpyDeviceToHost, st));
   }
   if (extra) VGX_HIP(ctx, hipMemcpyAsync(h_extra, d_extra, extra, hipMemcpyDeviceToHost, st));
@@ -378,7 +350,6 @@ int vgx_cloud_create(vgx_ctx ctx, vgx_cloud* out) {
 int vgx_cloud_destroy(vgx_cloud C) {
   if (!C) return VGX_ERR_INVALID;
   (void)hipSetDevice(C->ctx->device);
-  free_points(C);
   delete C;
   return VGX_OK;
 }
@@ -395,9 +366,9 @@ int vgx_cloud_device_pointers(vgx_cloud C, const float** xyz, const float** inte
   if (!C) return VGX_ERR_INVALID;
   std::lock_guard<std::mutex> lk(C->mu);
   const bool any = C->n_points > 0;
-  if (xyz) *xyz = any ? C->d_xyz : nullptr;
-  if (intensity) *intensity = any ? C->d_intensity : nullptr;
-  if (rgba) *rgba = any && C->has_colors ? reinterpret_cast<const uint8_t*>(C->d_rgba) : nullptr;
+  if (xyz) *xyz = any ? C->d_xyz.as<float>() : nullptr;
+  if (intensity) *intensity = any ? C->d_intensity.as<float>() : nullptr;
+  if (rgba) *rgba = any && C->has_colors ? C->d_rgba.as<uint8_t>() : nullptr;
   return VGX_OK;
 }
 
@@ -411,9 +382,9 @@ int vgx_cloud_download(vgx_cloud C, float* xyz, float* intensity, uint8_t* rgba)
   VGX_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;  // (the cloud was complete when its producer returned, whichever stream made it)
   const size_t n = (size_t)C->n_points;
-  if (xyz) VGX_HIP(ctx, hipMemcpyAsync(xyz, C->d_xyz, n * 12, hipMemcpyDeviceToHost, st));
-  if (intensity) VGX_HIP(ctx, hipMemcpyAsync(intensity, C->d_intensity, n * 4, hipMemcpyDeviceToHost, st));
-  if (rgba) VGX_HIP(ctx, hipMemcpyAsync(rgba, C->d_rgba, n * 4, hipMemcpyDeviceToHost, st));
+  if (xyz) VGX_HIP(ctx, hipMemcpyAsync(xyz, C->d_xyz.p, n * 12, hipMemcpyDeviceToHost, st));
+  if (intensity) VGX_HIP(ctx, hipMemcpyAsync(intensity, C->d_intensity.p, n * 4, hipMemcpyDeviceToHost, st));
+  if (rgba) VGX_HIP(ctx, hipMemcpyAsync(rgba, C->d_rgba.p, n * 4, hipMemcpyDeviceToHost, st));
   VGX_HIP(ctx, hipStreamSynchronize(st));
   return VGX_OK;
 }

@@ -157,48 +157,19 @@ struct vgx_connected_mesh_s {
   int64_t n_verts = 0, n_tris = 0;  // the mesh held now
   bool has_colors = false;
   // output, grown on demand
-  float* d_vertices = nullptr;  // [vert_cap][3]
-  float* d_normals = nullptr;   // [vert_cap][3]
-  uint32_t* d_colors = nullptr; // [vert_cap] bytes r g b a
-  uint32_t* d_indices = nullptr;  // [soup_cap]: [T][3]
-  int64_t vert_cap = 0;
+  DeviceBuffer d_vertices;  // float [vert_cap][3]
+  DeviceBuffer d_normals;   // float [vert_cap][3]
+  DeviceBuffer d_colors;    // u32 [vert_cap] bytes r g b a
+  DeviceBuffer d_indices;   // u32 [soup_cap]: [T][3]
   // scratch
-  uint32_t* d_table = nullptr;  // [table_cap] slots
-  uint32_t* d_rep = nullptr;    // [soup_cap]
-  uint32_t* d_number = nullptr; // [soup_cap]: flags, then their inclusive scan
-  int32_t* d_bad = nullptr;     // the out-of-range flag
-  void* d_tmp = nullptr;
-  size_t tmp_bytes = 0;
-  int64_t table_cap = 0, soup_cap = 0;
+  DeviceBuffer d_table;     // u32 [table_slots(soup_cap)] slots
+  DeviceBuffer d_rep;       // u32 [soup_cap]
+  DeviceBuffer d_number;    // u32 [soup_cap]: flags, then their inclusive scan
+  DeviceBuffer d_bad;       // int32: the out-of-range flag
+  DeviceBuffer d_tmp;       // the scan's workspace
 };
 
 namespace {
-
-int connect_alloc_error(vgx_ctx ctx, hipError_t e, const char* what) {
-  (void)hipGetLastError();  // (clear the sticky out-of-memory status)
-  return set_error(ctx, e == hipErrorOutOfMemory ? VGX_ERR_NOMEM : VGX_ERR_HIP,
-                   std::string("connected mesh: allocating ") + what + ": " + hipGetErrorString(e));
-}
-
-void free_soup(vgx_connected_mesh C) {
-  void* ps[] = {C->d_indices, C->d_table, C->d_rep, C->d_number, C->d_bad, C->d_tmp};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
-  C->d_indices = C->d_table = C->d_rep = C->d_number = nullptr;
-  C->d_bad = nullptr;
-  C->d_tmp = nullptr;
-  C->tmp_bytes = 0;
-  C->table_cap = C->soup_cap = 0;
-}
-
-void free_verts(vgx_connected_mesh C) {
-  void* ps[] = {C->d_vertices, C->d_normals, C->d_colors};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
-  C->d_vertices = C->d_normals = nullptr;
-  C->d_colors = nullptr;
-  C->vert_cap = 0;
-}
 
 // the power of two >= 2 n (n < 2^32)
 int64_t table_slots(int64_t n) {
@@ -207,76 +178,64 @@ int64_t table_slots(int64_t n) {
   return s;
 }
 
-// per-soup-vertex arrays (indices, rep, number), the table and the scan's workspace
+// a quarter of slack (the next map is a little larger), at least 4096 vertices
+size_t vertex_capacity(int64_t n) { return (size_t)std::max<int64_t>(n + n / 4, 4096); }
+
+// per-soup-vertex arrays (indices, rep, number), the table (sized from the capacity) and the scan's workspace, which goes
+// when they go
 int ensure_soup(vgx_connected_mesh C, int64_t n, size_t tmp_bytes) {
-  if (n > C->soup_cap || !C->d_bad) {
-    free_soup(C);
-    const int64_t cap = std::max<int64_t>(n + n / 4, 4096);  // (a quarter of slack: the next map is a little larger)
-    const int64_t slots = table_slots(cap);
-    hipError_t e = hipMalloc(&C->d_indices, (size_t)cap * 4);
-    if (e == hipSuccess) e = hipMalloc(&C->d_rep, (size_t)cap * 4);
-    if (e == hipSuccess) e = hipMalloc(&C->d_number, (size_t)cap * 4);
-    if (e == hipSuccess) e = hipMalloc(&C->d_table, (size_t)slots * 4);
-    if (e == hipSuccess) e = hipMalloc(&C->d_bad, sizeof(int32_t));
-    if (e != hipSuccess) {
-      free_soup(C);
-      return connect_alloc_error(C->ctx, e, "per-vertex arrays and table");
-    }
-    C->soup_cap = cap;
-    C->table_cap = slots;
+  if ((size_t)n * 4 > C->d_rep.bytes) {
+    const size_t cap = vertex_capacity(n);
+    C->d_tmp.release();
+    const hipError_t e = alloc_group({{&C->d_indices, cap * 4}, {&C->d_rep, cap * 4}, {&C->d_number, cap * 4},
+                                      {&C->d_table, (size_t)table_slots((int64_t)cap) * 4}, {&C->d_bad, sizeof(int32_t)}});
+    if (e != hipSuccess) return alloc_error(C->ctx, e, "connected mesh: allocating per-vertex arrays and table");
   }
-  if (tmp_bytes > C->tmp_bytes) {
-    if (C->d_tmp) (void)hipFree(C->d_tmp);
-    C->d_tmp = nullptr;
-    C->tmp_bytes = 0;
-    const hipError_t e = hipMalloc(&C->d_tmp, tmp_bytes);
-    if (e != hipSuccess) return connect_alloc_error(C->ctx, e, "scan workspace");
-    C->tmp_bytes = tmp_bytes;
-  }
-  return VGX_OK;
+  const hipError_t e = C->d_tmp.reserve(tmp_bytes);
+  return e == hipSuccess ? VGX_OK : alloc_error(C->ctx, e, "connected mesh: allocating scan workspace");
 }
 
 int ensure_verts(vgx_connected_mesh C, int64_t nv) {
-  if (nv <= C->vert_cap) return VGX_OK;
-  free_verts(C);
-  const int64_t cap = std::max<int64_t>(nv + nv / 4, 4096);
-  hipError_t e = hipMalloc(&C->d_vertices, (size_t)cap * 12);
-  if (e == hipSuccess) e = hipMalloc(&C->d_normals, (size_t)cap * 12);
-  if (e == hipSuccess) e = hipMalloc(&C->d_colors, (size_t)cap * 4);
-  if (e != hipSuccess) {
-    free_verts(C);
-    return connect_alloc_error(C->ctx, e, "vertices");
-  }
-  C->vert_cap = cap;
-  return VGX_OK;
+  if ((size_t)nv * 4 <= C->d_colors.bytes) return VGX_OK;
+  const size_t cap = vertex_capacity(nv);
+  const hipError_t e = alloc_group({{&C->d_vertices, cap * 12}, {&C->d_normals, cap * 12}, {&C->d_colors, cap * 4}});
+  return e == hipSuccess ? VGX_OK : alloc_error(C->ctx, e, "connected mesh: allocating vertices");
 }
 
 // the passes over n = 3 T > 0 soup vertices, on `st` (the caller holds both handles' locks and the registration lock,
 // and has reset C's stats)
 int connect(vgx_ctx ctx, hipStream_t st, const MeshView& src, double inv, vgx_connected_mesh C) {
   const int64_t n = 3 * src.n_tris;
+  // all the room is made before the first launch
+  auto scan = [&](void* tmp, size_t& bytes) {
+    return rocprim::inclusive_scan(tmp, bytes, C->d_number.as<uint32_t>(), C->d_number.as<uint32_t>(), (size_t)n,
+                                   rocprim::plus<uint32_t>(), st);
+  };
   size_t scan_bytes = 0;
-  VGX_HIP(ctx, rocprim::inclusive_scan(nullptr, scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n,
-                                       rocprim::plus<uint32_t>(), st));
+  VGX_HIP(ctx, temp_bytes(scan, &scan_bytes));
   int rc = ensure_soup(C, n, std::max<size_t>(scan_bytes, 4));
   if (rc != VGX_OK) return rc;
-  const int64_t slots = table_slots(n);  // (<= table_cap: table_slots is monotone)
+  const int64_t slots = table_slots(n);  // (<= the table's capacity: table_slots is monotone)
+  uint32_t* const table = C->d_table.as<uint32_t>();
+  uint32_t* const rep = C->d_rep.as<uint32_t>();
+  uint32_t* const number = C->d_number.as<uint32_t>();
+  int32_t* const d_bad = C->d_bad.as<int32_t>();
   const unsigned long long mask = (unsigned long long)slots - 1ull;
   const dim3 grid((unsigned)((n + kConnectThreads - 1) / kConnectThreads)), block(kConnectThreads);
   const uint32_t n32 = (uint32_t)n;
   // 1. insert
-  VGX_HIP(ctx, hipMemsetAsync(C->d_table, 0xFF, (size_t)slots * 4, st));
-  VGX_HIP(ctx, hipMemsetAsync(C->d_bad, 0, sizeof(int32_t), st));
-  hipLaunchKernelGGL(connect_insert_kernel, grid, block, 0, st, src.vertices, n32, inv, C->d_table, mask, C->d_bad);
+  VGX_HIP(ctx, hipMemsetAsync(table, 0xFF, (size_t)slots * 4, st));
+  VGX_HIP(ctx, hipMemsetAsync(d_bad, 0, sizeof(int32_t), st));
+  hipLaunchKernelGGL(connect_insert_kernel, grid, block, 0, st, src.vertices, n32, inv, table, mask, d_bad);
   VGX_HIP(ctx, hipGetLastError());
   // 2. resolve, 3. scan
-  hipLaunchKernelGGL(connect_resolve_kernel, grid, block, 0, st, src.vertices, n32, inv, C->d_table, mask, C->d_rep, C->d_number);
+  hipLaunchKernelGGL(connect_resolve_kernel, grid, block, 0, st, src.vertices, n32, inv, table, mask, rep, number);
   VGX_HIP(ctx, hipGetLastError());
-  VGX_HIP(ctx, rocprim::inclusive_scan(C->d_tmp, scan_bytes, C->d_number, C->d_number, (size_t)n, rocprim::plus<uint32_t>(), st));
+  VGX_HIP(ctx, scan(C->d_tmp.p, scan_bytes));
   uint32_t nv = 0;
   int32_t bad = 0;
-  VGX_HIP(ctx, hipMemcpyAsync(&nv, C->d_number + (n - 1), sizeof(nv), hipMemcpyDeviceToHost, st));
-  VGX_HIP(ctx, hipMemcpyAsync(&bad, C->d_bad, sizeof(bad), hipMemcpyDeviceToHost, st));
+  VGX_HIP(ctx, hipMemcpyAsync(&nv, number + (n - 1), sizeof(nv), hipMemcpyDeviceToHost, st));
+  VGX_HIP(ctx, hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, st));
   VGX_HIP(ctx, hipStreamSynchronize(st));
   if (bad)
     return set_error(ctx, VGX_ERR_UNSUPPORTED,
@@ -284,8 +243,8 @@ int connect(vgx_ctx ctx, hipStream_t st, const MeshView& src, double inv, vgx_co
   // 4. emit
   rc = ensure_verts(C, nv);
   if (rc != VGX_OK) return rc;
-  hipLaunchKernelGGL(connect_emit_kernel, grid, block, 0, st, src.vertices, src.normals, src.colors, n32, C->d_rep, C->d_number,
-                     C->d_vertices, C->d_normals, C->d_colors, C->d_indices);
+  hipLaunchKernelGGL(connect_emit_kernel, grid, block, 0, st, src.vertices, src.normals, src.colors, n32, rep, number,
+                     C->d_vertices.as<float>(), C->d_normals.as<float>(), C->d_colors.as<uint32_t>(), C->d_indices.as<uint32_t>());
   VGX_HIP(ctx, hipGetLastError());
   VGX_HIP(ctx, hipStreamSynchronize(st));
   C->n_verts = nv;
@@ -308,8 +267,6 @@ int vgx_connected_mesh_create(vgx_ctx ctx, vgx_connected_mesh* out) {
 int vgx_connected_mesh_destroy(vgx_connected_mesh C) {
   if (!C) return VGX_ERR_INVALID;
   (void)hipSetDevice(C->ctx->device);
-  free_soup(C);
-  free_verts(C);
   delete C;
   return VGX_OK;
 }
@@ -356,11 +313,11 @@ int vgx_connected_mesh_download(vgx_connected_mesh C, float* vertices, float* no
   VGX_HIP(ctx, hipSetDevice(ctx->device));
   const int64_t nv = C->n_verts, nt = C->n_tris;
   if (nv > 0) {
-    if (vertices) VGX_HIP(ctx, hipMemcpy(vertices, C->d_vertices, (size_t)nv * 12, hipMemcpyDeviceToHost));
-    if (normals) VGX_HIP(ctx, hipMemcpy(normals, C->d_normals, (size_t)nv * 12, hipMemcpyDeviceToHost));
-    if (rgba) VGX_HIP(ctx, hipMemcpy(rgba, C->d_colors, (size_t)nv * 4, hipMemcpyDeviceToHost));
+    if (vertices) VGX_HIP(ctx, hipMemcpy(vertices, C->d_vertices.p, (size_t)nv * 12, hipMemcpyDeviceToHost));
+    if (normals) VGX_HIP(ctx, hipMemcpy(normals, C->d_normals.p, (size_t)nv * 12, hipMemcpyDeviceToHost));
+    if (rgba) VGX_HIP(ctx, hipMemcpy(rgba, C->d_colors.p, (size_t)nv * 4, hipMemcpyDeviceToHost));
   }
-  if (nt > 0 && indices) VGX_HIP(ctx, hipMemcpy(indices, C->d_indices, (size_t)nt * 12, hipMemcpyDeviceToHost));
+  if (nt > 0 && indices) VGX_HIP(ctx, hipMemcpy(indices, C->d_indices.p, (size_t)nt * 12, hipMemcpyDeviceToHost));
   return VGX_OK;
 }
 

@@ -163,7 +163,7 @@ int build_chunk_bounds(vgx_ctx ctx, PointSet& ps) {
   if (ps.n <= 0) return VGX_OK;
   const long long chunks = (ps.n + kChunkPoints - 1) / kChunkPoints;
   VGX_HIP(ctx, hipMalloc(&ps.d_chunk_bounds, (size_t)chunks * sizeof(float4)));
-  DeviceScratch s_minmax;
+  DeviceBuffer s_minmax;
   VGX_HIP(ctx, s_minmax.alloc((size_t)chunks * 6 * sizeof(float)));
   float* d_minmax = s_minmax.as<float>();
   hipLaunchKernelGGL(chunk_bounds_kernel, dim3((unsigned)chunks), dim3(64), 0, ctx->stream, ps.d_xyzd,

@@ -166,7 +166,7 @@ int vgx_submap_generate_esdf(vgx_submap sm, const vgx_esdf_config* cfg_in, int32
   VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (!sm->d_esdf_distance) VGX_HIP(ctx, hipMalloc(&sm->d_esdf_distance, nvox * sizeof(float)));
   if (!sm->d_esdf_observed) VGX_HIP(ctx, hipMalloc(&sm->d_esdf_observed, nvox));
-  DeviceScratch s_changed;
+  DeviceBuffer s_changed;
   VGX_HIP(ctx, s_changed.alloc(sizeof(int)));
   int* d_changed = s_changed.as<int>();
   hipLaunchKernelGGL(esdf_init_kernel, dim3((unsigned)((nvox + 255) / 256)), dim3(256), 0, ctx->stream,

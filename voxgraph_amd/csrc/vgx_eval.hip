@@ -274,12 +274,11 @@ int eval_enqueue(vgx_submap gt, vgx_submap test, int32_t layer, int32_t mode, bo
     VGX_HIP(ctx, hipGetLastError());
     if (want_err) {
       VGX_HIP(ctx, D.pos.alloc((size_t)n_test * 4));
-      size_t scan_bytes = 0;
-      VGX_HIP(ctx, rocprim::exclusive_scan(nullptr, scan_bytes, D.has.as<int32_t>(), D.pos.as<int32_t>(), 0, (size_t)n_test,
-                                           rocprim::plus<int32_t>(), st));
-      VGX_HIP(ctx, D.tmp.alloc(std::max<size_t>(scan_bytes, 4)));
-      VGX_HIP(ctx, rocprim::exclusive_scan(D.tmp.p, scan_bytes, D.has.as<int32_t>(), D.pos.as<int32_t>(), 0, (size_t)n_test,
-                                           rocprim::plus<int32_t>(), st));
+      auto scan = [&](void* tmp, size_t& bytes) {
+        return rocprim::exclusive_scan(tmp, bytes, D.has.as<int32_t>(), D.pos.as<int32_t>(), 0, (size_t)n_test, rocprim::plus<int32_t>(),
+                                       st);
+      };
+      VGX_HIP(ctx, run_with_temp(D.tmp, scan));
       // room for every test block: the error blocks are the test blocks with a gt counterpart
       if (want_distance) VGX_HIP(ctx, D.ed.alloc((size_t)n_test * vox * 4));
       if (want_set) VGX_HIP(ctx, D.es.alloc((size_t)n_test * vox));

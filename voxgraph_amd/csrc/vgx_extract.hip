@@ -129,7 +129,7 @@ extern "C" int vgx_submap_extract_voxel_points(vgx_submap sm, double min_voxel_w
     if (n_points_out) *n_points_out = 0;
     return VGX_OK;
   }
-  DeviceScratch s_counts, s_wsum, s_offsets;
+  DeviceBuffer s_counts, s_wsum, s_offsets;
   VGX_HIP(ctx, s_counts.alloc((size_t)nb * sizeof(int32_t)));
   VGX_HIP(ctx, s_wsum.alloc((size_t)nb * sizeof(double)));
   VGX_HIP(ctx, s_offsets.alloc(((size_t)nb + 1) * sizeof(int64_t)));

@@ -4,12 +4,15 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdint>
 #include <mutex>
 #include <condition_variable>
+#include <initializer_list>
 #include <random>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "voxgraph_amd.h"
@@ -392,21 +395,80 @@ inline int set_error(vgx_ctx ctx, int code, const std::string& msg);
 // the one lock behind the users / destroy_requested fields of submaps and cost functions (vgx_context.hip)
 std::mutex& lifetime_mu();
 
-// Scope-bound device scratch: freed on every exit path (the VGX_HIP macro returns early).
-struct DeviceScratch {
+// The one owner of device memory on the host side: frees in its destructor, so scratch declared in a function
+// is freed on every exit path (the VGX_HIP macro returns early) and a handle's arrays go with the handle.  It neither
+// synchronises nor zeroes: whoever frees an array that a queued kernel may still read synchronises that stream first.
+struct DeviceBuffer {
   void* p = nullptr;
-  DeviceScratch() = default;
-  DeviceScratch(const DeviceScratch&) = delete;
-  DeviceScratch& operator=(const DeviceScratch&) = delete;
-  ~DeviceScratch() {
-    if (p) (void)hipFree(p);
+  size_t bytes = 0;  // capacity
+  DeviceBuffer() = default;
+  DeviceBuffer(const DeviceBuffer&) = delete;
+  DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+  DeviceBuffer(DeviceBuffer&& o) noexcept { swap(o); }
+  DeviceBuffer& operator=(DeviceBuffer&& o) noexcept {
+    swap(o);
+    return *this;
   }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
+  ~DeviceBuffer() { release(); }
+  void swap(DeviceBuffer& o) {
+    std::swap(p, o.p);
+    std::swap(bytes, o.bytes);
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+  // exactly `n` bytes; what was held is freed first, and after a failure the buffer is empty
+  hipError_t alloc(size_t n) {
+    release();
+    const hipError_t e = hipMalloc(&p, n);
+    if (e == hipSuccess) bytes = n;
+    else p = nullptr;
+    return e;
+  }
+  // grow-only: nothing when the capacity suffices, else max(n [+ n / 4], min_bytes) fresh bytes (the contents are lost)
+  hipError_t reserve(size_t n, size_t min_bytes = 0, bool slack = false) {
+    if (n <= bytes) return hipSuccess;
+    return alloc(std::max(slack ? n + n / 4 : n, min_bytes));
+  }
   template <typename T>
   T* as() const {
     return static_cast<T*>(p);
   }
 };
+// Arrays that share one capacity grow together: all are freed before the first is allocated (the peak does not rise while
+// a handle grows), and after a failure all are empty.
+struct DeviceBufferSize {
+  DeviceBuffer* buffer;
+  size_t bytes;
+};
+inline hipError_t alloc_group(std::initializer_list<DeviceBufferSize> group) {
+  for (const DeviceBufferSize& g : group) g.buffer->release();
+  hipError_t e = hipSuccess;
+  for (const DeviceBufferSize& g : group)
+    if (e == hipSuccess) e = g.buffer->alloc(g.bytes);
+  if (e != hipSuccess)
+    for (const DeviceBufferSize& g : group) g.buffer->release();
+  return e;
+}
+
+// rocPRIM's two calls -- the size of the temporary storage with a null pointer, then the work with identical arguments --
+// from ONE lambda hipError_t(void* tmp, size_t& bytes) that holds the rocPRIM call.  run_with_temp may reallocate `tmp`:
+// only where nothing queued still uses it; launches that share a workspace ask with temp_bytes and make room once.
+template <class Call>
+hipError_t temp_bytes(Call& call, size_t* bytes) {
+  *bytes = 0;
+  return call(nullptr, *bytes);
+}
+template <class Call>
+hipError_t run_with_temp(DeviceBuffer& tmp, Call& call) {
+  size_t bytes = 0;
+  hipError_t e = temp_bytes(call, &bytes);
+  if (e == hipSuccess) e = tmp.reserve(bytes, 8);  // (never null: to rocPRIM a null workspace is the size query)
+  if (e == hipSuccess) e = call(tmp.p, bytes);
+  return e;
+}
 void set_global_error(const std::string& msg);
 
 // The centre of voxel `idx` (one axis) of the block whose low corner on that axis is `origin` = (float)block_index *
@@ -423,6 +485,12 @@ __host__ __device__ __forceinline__ float voxel_centre(float origin, int idx, fl
       return vgx::set_error((ctx), VGX_ERR_HIP,                                 \
                             std::string(#call) + ": " + hipGetErrorString(e__)); \
   } while (0)
+
+// a failed device allocation of a product handle; `what`: "<product>: allocating <arrays>"
+inline int alloc_error(vgx_ctx ctx, hipError_t e, const char* what) {
+  (void)hipGetLastError();  // (clear the sticky out-of-memory status)
+  return set_error(ctx, e == hipErrorOutOfMemory ? VGX_ERR_NOMEM : VGX_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
 
 // What vgx_connect.hip reads of a mesh handle (vgx_mesh_s lives in vgx_mesh.hip).  mesh_view: the caller holds
 // mesh_mutex(M), except for `ctx`, which never changes.
@@ -448,7 +516,7 @@ struct EvalTotals {
   long long n_eval, n_ign, n_non, n_err_blocks;
 };
 struct EvalDevice {
-  DeviceScratch slot, has, pos, part, tot, tmp, ed, es, ebi;  // tot: EvalTotals; ed / es / ebi: [n_test] error blocks
+  DeviceBuffer slot, has, pos, part, tot, tmp, ed, es, ebi;  // tot: EvalTotals; ed / es / ebi: [n_test] error blocks
 };
 int eval_check(const char* fn, vgx_submap gt, vgx_submap test, int32_t layer, int32_t mode, const void* details);
 int eval_enqueue(vgx_submap gt, vgx_submap test, int32_t layer, int32_t mode, bool want_index, bool want_distance, bool want_set,

@@ -247,6 +247,74 @@ static void launch_iso(vgx_submap sm, const IsoParams& p, int32_t* counts, const
                        offsets, xyzd, weight, has, block_list);
 }
 
+// The passes of vgx_submap_extract_isosurface_points over nb > 0 blocks: fills ps (n, the arrays, sum_weight) and the
+// submap's isosurface block list.  The caller holds ctx->mu and resets the point set when this fails.
+static int extract_isosurface(vgx_submap sm, IsoParams p, PointSet& ps) {
+  static const std::string kFn = "vgx_submap_extract_isosurface_points: ";
+  vgx_ctx ctx = sm->ctx;
+  hipStream_t st = ctx->stream;
+  const int nb = sm->n_blocks;
+  DeviceBuffer d_counts, d_offsets, d_has, d_keys, d_ids, d_active;
+  if (d_counts.alloc((size_t)nb * 4) != hipSuccess || d_offsets.alloc(((size_t)nb + 1) * 8) != hipSuccess ||
+      d_has.alloc((size_t)nb) != hipSuccess)
+    return set_error(ctx, VGX_ERR_NOMEM, kFn + "device allocation failed");
+  std::vector<int32_t> counts((size_t)nb);
+  auto fetch_counts = [&]() {
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), d_counts.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    return e;
+  };
+  launch_iso<0>(sm, p, d_counts.as<int32_t>(), nullptr, nullptr, nullptr, nullptr);
+  VGX_HIP(ctx, fetch_counts());
+  int64_t candidates = 0;
+  std::vector<int32_t> active;  // blocks with candidates, in block order
+  for (int b = 0; b < nb; ++b) {
+    candidates += counts[(size_t)b];
+    if (counts[(size_t)b] > 0) active.push_back(b);
+  }
+  if (candidates == 0) return VGX_OK;
+  unsigned long long cap = 1024;
+  while (cap < 2ull * (unsigned long long)candidates) cap <<= 1;
+  p.mask = cap - 1;
+  if (d_keys.alloc(cap * 8) != hipSuccess || d_ids.alloc(cap * 8) != hipSuccess)
+    return set_error(ctx, VGX_ERR_NOMEM, kFn + "dedup table allocation failed");
+  p.keys = d_keys.as<unsigned long long>();
+  p.ids = d_ids.as<unsigned long long>();
+  VGX_HIP(ctx, hipMemsetAsync(p.keys, 0xff, cap * 8, st));
+  VGX_HIP(ctx, hipMemsetAsync(p.ids, 0xff, cap * 8, st));
+  VGX_HIP(ctx, hipMemsetAsync(d_has.p, 0, (size_t)nb, st));
+  VGX_HIP(ctx, hipMemsetAsync(d_counts.p, 0, (size_t)nb * 4, st));  // (pass 2 writes the active blocks' only)
+  VGX_HIP(ctx, d_active.alloc(active.size() * 4));
+  VGX_HIP(ctx, hipMemcpyAsync(d_active.p, active.data(), active.size() * 4, hipMemcpyHostToDevice, st));
+  launch_iso<1>(sm, p, d_counts.as<int32_t>(), nullptr, nullptr, nullptr, nullptr, d_active.as<int32_t>(), (int)active.size());
+  launch_iso<2>(sm, p, d_counts.as<int32_t>(), nullptr, nullptr, nullptr, nullptr, d_active.as<int32_t>(), (int)active.size());
+  VGX_HIP(ctx, fetch_counts());
+  std::vector<int64_t> offsets((size_t)nb + 1, 0);
+  for (int b = 0; b < nb; ++b) offsets[(size_t)b + 1] = offsets[(size_t)b] + counts[(size_t)b];
+  const int64_t n = offsets[(size_t)nb];
+  ps.n = n;
+  if (n == 0) return VGX_OK;
+  if (hipMalloc(&ps.d_xyzd, (size_t)n * sizeof(float4)) != hipSuccess || hipMalloc(&ps.d_weight, (size_t)n * sizeof(float)) != hipSuccess)
+    return set_error(ctx, VGX_ERR_NOMEM, kFn + "point allocation failed");
+  VGX_HIP(ctx, hipMemcpyAsync(d_offsets.p, offsets.data(), ((size_t)nb + 1) * 8, hipMemcpyHostToDevice, st));
+  launch_iso<3>(sm, p, d_counts.as<int32_t>(), d_offsets.as<int64_t>(), ps.d_xyzd, ps.d_weight, d_has.as<unsigned char>(),
+                d_active.as<int32_t>(), (int)active.size());
+  VGX_HIP(ctx, hipGetLastError());
+  // sum of weights (RCF:124) and the isosurface block list
+  std::vector<float> w((size_t)n);
+  std::vector<unsigned char> has((size_t)nb);
+  VGX_HIP(ctx, hipMemcpyAsync(w.data(), ps.d_weight, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  VGX_HIP(ctx, hipMemcpyAsync(has.data(), d_has.p, (size_t)nb, hipMemcpyDeviceToHost, st));
+  VGX_HIP(ctx, hipStreamSynchronize(st));
+  double sw = 0;
+  for (int64_t i = 0; i < n; ++i) sw += (double)w[(size_t)i];
+  ps.sum_weight = sw;
+  for (int b = 0; b < nb; ++b)
+    if (has[(size_t)b]) sm->isosurface_blocks.push_back(b);
+  return VGX_OK;
+}
+
 }  // namespace vgx
 
 using namespace vgx;
@@ -268,8 +336,7 @@ extern "C" int vgx_submap_extract_isosurface_points(vgx_submap sm, double min_vo
     sm->d_iso_block_index = nullptr;
   }
   if (n_points_out) *n_points_out = 0;
-  const int nb = sm->n_blocks;
-  if (nb == 0) {
+  if (sm->n_blocks == 0) {
     ps.present = true;
     return VGX_OK;
   }
@@ -290,95 +357,7 @@ extern "C" int vgx_submap_extract_isosurface_points(vgx_submap sm, double min_vo
   const float threshold = (float)(0.5 * (double)sm->voxel_size);
   p.threshold_inv = 1.0 / (double)threshold;
 
-  int32_t* d_counts = nullptr;
-  int64_t* d_offsets = nullptr;
-  unsigned char* d_has = nullptr;
-  std::vector<int32_t> counts((size_t)nb);
-  std::vector<int64_t> offsets((size_t)nb + 1, 0);
-  int rc = VGX_OK;
-  auto fail = [&](hipError_t e) {
-    rc = set_error(ctx, VGX_ERR_HIP, std::string("vgx_submap_extract_isosurface_points: ") + hipGetErrorString(e));
-  };
-  auto fetch_counts = [&]() {
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), d_counts, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) fail(e);
-  };
-  if (hipMalloc(&d_counts, (size_t)nb * 4) != hipSuccess || hipMalloc(&d_offsets, ((size_t)nb + 1) * 8) != hipSuccess ||
-      hipMalloc(&d_has, (size_t)nb) != hipSuccess)
-    rc = set_error(ctx, VGX_ERR_NOMEM, "vgx_submap_extract_isosurface_points: device allocation failed");
-  if (rc == VGX_OK) {
-    launch_iso<0>(sm, p, d_counts, nullptr, nullptr, nullptr, nullptr);
-    fetch_counts();
-  }
-  int64_t candidates = 0;
-  std::vector<int32_t> active;   // blocks with candidates, in block order
-  int32_t* d_active = nullptr;
-  if (rc == VGX_OK)
-    for (int b = 0; b < nb; ++b) {
-      candidates += counts[(size_t)b];
-      if (counts[(size_t)b] > 0) active.push_back(b);
-    }
-  if (rc == VGX_OK && candidates > 0) {
-    unsigned long long cap = 1024;
-    while (cap < 2ull * (unsigned long long)candidates) cap <<= 1;
-    p.mask = cap - 1;
-    if (hipMalloc(&p.keys, cap * 8) != hipSuccess || hipMalloc(&p.ids, cap * 8) != hipSuccess) {
-      rc = set_error(ctx, VGX_ERR_NOMEM, "vgx_submap_extract_isosurface_points: dedup table allocation failed");
-    } else {
-      hipError_t e = hipMemsetAsync(p.keys, 0xff, cap * 8, ctx->stream);
-      if (e == hipSuccess) e = hipMemsetAsync(p.ids, 0xff, cap * 8, ctx->stream);
-      if (e == hipSuccess) e = hipMemsetAsync(d_has, 0, (size_t)nb, ctx->stream);
-      if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, (size_t)nb * 4, ctx->stream);   // (pass 2 writes the active blocks' only)
-      if (e == hipSuccess) e = hipMalloc(&d_active, active.size() * 4);
-      if (e == hipSuccess) e = hipMemcpyAsync(d_active, active.data(), active.size() * 4, hipMemcpyHostToDevice, ctx->stream);
-      if (e != hipSuccess) fail(e);
-    }
-    if (rc == VGX_OK) {
-      launch_iso<1>(sm, p, d_counts, nullptr, nullptr, nullptr, nullptr, d_active, (int)active.size());
-      launch_iso<2>(sm, p, d_counts, nullptr, nullptr, nullptr, nullptr, d_active, (int)active.size());
-      fetch_counts();
-    }
-    if (rc == VGX_OK) {
-      for (int b = 0; b < nb; ++b) offsets[(size_t)b + 1] = offsets[(size_t)b] + counts[(size_t)b];
-      const int64_t n = offsets[(size_t)nb];
-      ps.n = n;
-      if (n > 0) {
-        if (hipMalloc(&ps.d_xyzd, (size_t)n * sizeof(float4)) != hipSuccess ||
-            hipMalloc(&ps.d_weight, (size_t)n * sizeof(float)) != hipSuccess) {
-          rc = set_error(ctx, VGX_ERR_NOMEM, "vgx_submap_extract_isosurface_points: point allocation failed");
-        } else {
-          hipError_t e = hipMemcpyAsync(d_offsets, offsets.data(), ((size_t)nb + 1) * 8, hipMemcpyHostToDevice, ctx->stream);
-          if (e == hipSuccess) {
-            launch_iso<3>(sm, p, d_counts, d_offsets, ps.d_xyzd, ps.d_weight, d_has, d_active, (int)active.size());
-            e = hipGetLastError();
-          }
-          // sum of weights (RCF:124) and the isosurface block list
-          std::vector<float> w((size_t)n);
-          std::vector<unsigned char> has((size_t)nb);
-          if (e == hipSuccess) e = hipMemcpyAsync(w.data(), ps.d_weight, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream);
-          if (e == hipSuccess) e = hipMemcpyAsync(has.data(), d_has, (size_t)nb, hipMemcpyDeviceToHost, ctx->stream);
-          if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-          if (e != hipSuccess) {
-            fail(e);
-          } else {
-            double sw = 0;
-            for (int64_t i = 0; i < n; ++i) sw += (double)w[(size_t)i];
-            ps.sum_weight = sw;
-            for (int b = 0; b < nb; ++b)
-              if (has[(size_t)b]) sm->isosurface_blocks.push_back(b);
-          }
-        }
-      }
-    }
-  }
-  if (p.keys) (void)hipFree(p.keys);
-  if (p.ids) (void)hipFree(p.ids);
-  if (d_counts) (void)hipFree(d_counts);
-  if (d_active) (void)hipFree(d_active);
-  if (d_offsets) (void)hipFree(d_offsets);
-  if (d_has) (void)hipFree(d_has);
+  int rc = extract_isosurface(sm, p, ps);
   if (rc == VGX_OK) rc = build_chunk_bounds(ctx, ps);
   if (rc == VGX_OK && !sm->isosurface_blocks.empty()) {
     std::vector<int32_t> ib(3 * sm->isosurface_blocks.size());

@@ -434,162 +434,75 @@ struct vgx_mesh_s {
   int64_t n_tris = 0;
   bool holds_mesh = true;  // false from the moment a generating call resets the handle until one succeeds (vgx_mesh_connect)
   // output, grown on demand
-  int32_t* d_block_index = nullptr;  // [block_cap][3]
-  int64_t* d_first = nullptr;        // [block_cap + 1]
-  float* d_vertices = nullptr;       // [tri_cap][3][3]
-  float* d_normals = nullptr;        // [tri_cap][3]
+  DeviceBuffer d_block_index;  // int32 [block_cap][3]
+  DeviceBuffer d_first;        // int64 [block_cap + 1]
+  DeviceBuffer d_vertices;     // float [tri_cap][3][3]
+  DeviceBuffer d_normals;      // float [tri_cap][3]
   // per-block scratch
-  unsigned long long* d_keys[2] = {nullptr, nullptr};
-  int32_t* d_slots[2] = {nullptr, nullptr};
-  int64_t* d_counts = nullptr;
-  void* d_tmp = nullptr;
-  size_t tmp_bytes = 0;
-  int64_t block_cap = 0, tri_cap = 0;
-  // the separated mesh: colours [tri_cap2] (one per triangle), per-entry scratch beside the block arrays, descriptors
+  DeviceBuffer d_keys[2];      // u64 [block_cap]
+  DeviceBuffer d_slots[2];     // int32 [block_cap]
+  DeviceBuffer d_counts;       // int64 [block_cap]
+  DeviceBuffer d_tmp;          // rocPRIM's workspace: the largest any of a call's sorts and scans asks for
+  // the separated mesh: colours (one per triangle), per-entry scratch beside the block arrays, descriptors
   bool has_colors = false;
-  uint32_t* d_colors = nullptr;
-  int64_t color_cap = 0;
-  int64_t* d_efirst = nullptr;  // [entry_cap + 1]
-  int32_t* d_heads = nullptr;   // [entry_cap]
-  int32_t* d_uid = nullptr;     // [entry_cap]
-  int64_t* d_tail = nullptr;    // {triangles, blocks}
-  int64_t entry_cap = 0;
-  std::vector<SepSrc> h_src;    // (the host side of the descriptor copy: outlives it)
-  SepSrc* d_src = nullptr;
-  int64_t src_cap = 0;
+  DeviceBuffer d_colors;       // u32 [color_cap] bytes r g b a
+  DeviceBuffer d_efirst;       // int64 [entry_cap + 1]
+  DeviceBuffer d_heads;        // int32 [entry_cap]
+  DeviceBuffer d_uid;          // int32 [entry_cap]
+  DeviceBuffer d_tail;         // int64 {triangles, blocks}
+  std::vector<SepSrc> h_src;   // (the host side of the descriptor copy: outlives it)
+  DeviceBuffer d_src;          // SepSrc [src_cap]
+  // a generating call starts from a handle that holds nothing
+  void reset_stats() {
+    n_blocks = 0;
+    n_tris = 0;
+    has_colors = false;
+    holds_mesh = false;
+  }
 };
 
 namespace {
 
-void free_blocks(vgx_mesh M) {
-  void* ps[] = {M->d_block_index, M->d_first, M->d_keys[0], M->d_keys[1], M->d_slots[0], M->d_slots[1], M->d_counts, M->d_tmp};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
-  M->d_block_index = nullptr;
-  M->d_first = nullptr;
-  M->d_keys[0] = M->d_keys[1] = nullptr;
-  M->d_slots[0] = M->d_slots[1] = nullptr;
-  M->d_counts = nullptr;
-  M->d_tmp = nullptr;
-  M->tmp_bytes = 0;
-  M->block_cap = 0;
-}
-
-void free_tris(vgx_mesh M) {
-  if (M->d_vertices) (void)hipFree(M->d_vertices);
-  if (M->d_normals) (void)hipFree(M->d_normals);
-  M->d_vertices = M->d_normals = nullptr;
-  M->tri_cap = 0;
-}
-
-int alloc_error(vgx_ctx ctx, hipError_t e, const char* what) {
-  (void)hipGetLastError();  // (clear the sticky out-of-memory status)
-  return set_error(ctx, e == hipErrorOutOfMemory ? VGX_ERR_NOMEM : VGX_ERR_HIP,
-                   std::string("mesh: allocating ") + what + ": " + hipGetErrorString(e));
-}
-
+// the block arrays (capacity: at least 1024 blocks, no slack) and the workspace, which goes when they go
 int ensure_blocks(vgx_mesh M, int64_t nb, size_t tmp_bytes) {
-  if (nb > M->block_cap) {
-    free_blocks(M);
-    const int64_t cap = std::max<int64_t>(nb, 1024);
-    hipError_t e = hipMalloc(&M->d_block_index, (size_t)cap * 12);
-    if (e == hipSuccess) e = hipMalloc(&M->d_first, (size_t)(cap + 1) * 8);
-    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-      e = hipMalloc(&M->d_keys[k], (size_t)cap * 8);
-      if (e == hipSuccess) e = hipMalloc(&M->d_slots[k], (size_t)cap * 4);
-    }
-    if (e == hipSuccess) e = hipMalloc(&M->d_counts, (size_t)cap * 8);
-    if (e != hipSuccess) {
-      free_blocks(M);
-      return alloc_error(M->ctx, e, "block arrays");
-    }
-    M->block_cap = cap;
+  if ((size_t)nb * 8 > M->d_counts.bytes) {
+    const size_t cap = (size_t)std::max<int64_t>(nb, 1024);
+    M->d_tmp.release();
+    const hipError_t e = alloc_group({{&M->d_block_index, cap * 12}, {&M->d_first, (cap + 1) * 8}, {&M->d_keys[0], cap * 8},
+                                      {&M->d_slots[0], cap * 4}, {&M->d_keys[1], cap * 8}, {&M->d_slots[1], cap * 4},
+                                      {&M->d_counts, cap * 8}});
+    if (e != hipSuccess) return alloc_error(M->ctx, e, "mesh: allocating block arrays");
   }
-  if (tmp_bytes > M->tmp_bytes) {
-    if (M->d_tmp) (void)hipFree(M->d_tmp);
-    M->d_tmp = nullptr;
-    M->tmp_bytes = 0;
-    const hipError_t e = hipMalloc(&M->d_tmp, tmp_bytes);
-    if (e != hipSuccess) {
-      free_blocks(M);
-      return alloc_error(M->ctx, e, "sort workspace");
-    }
-    M->tmp_bytes = tmp_bytes;
-  }
-  return VGX_OK;
+  const hipError_t e = M->d_tmp.reserve(tmp_bytes);
+  return e == hipSuccess ? VGX_OK : alloc_error(M->ctx, e, "mesh: allocating sort workspace");
 }
 
-void free_separated(vgx_mesh M) {
-  void* ps[] = {M->d_colors, M->d_efirst, M->d_heads, M->d_uid, M->d_tail, M->d_src};
-  for (void* p : ps)
-    if (p) (void)hipFree(p);
-  M->d_colors = nullptr;
-  M->d_efirst = nullptr;
-  M->d_heads = M->d_uid = nullptr;
-  M->d_tail = nullptr;
-  M->d_src = nullptr;
-  M->color_cap = M->entry_cap = M->src_cap = 0;
-}
-
-// per-entry scratch and descriptors (the block arrays come from ensure_blocks)
+// per-entry scratch (at least 1024 entries) and descriptors (at least 64); the block arrays come from ensure_blocks
 int ensure_entries(vgx_mesh M, int64_t ne, int64_t n_src) {
-  if (ne > M->entry_cap) {
-    for (void* p : {(void*)M->d_efirst, (void*)M->d_heads, (void*)M->d_uid, (void*)M->d_tail})
-      if (p) (void)hipFree(p);
-    M->d_efirst = nullptr;
-    M->d_heads = M->d_uid = nullptr;
-    M->d_tail = nullptr;
-    M->entry_cap = 0;
-    const int64_t cap = std::max<int64_t>(ne, 1024);
-    hipError_t e = hipMalloc(&M->d_efirst, (size_t)(cap + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc(&M->d_heads, (size_t)cap * 4);
-    if (e == hipSuccess) e = hipMalloc(&M->d_uid, (size_t)cap * 4);
-    if (e == hipSuccess) e = hipMalloc(&M->d_tail, 2 * sizeof(int64_t));
-    if (e != hipSuccess) {
-      free_separated(M);
-      return alloc_error(M->ctx, e, "entry arrays");
-    }
-    M->entry_cap = cap;
+  if ((size_t)ne * 4 > M->d_heads.bytes) {
+    const size_t cap = (size_t)std::max<int64_t>(ne, 1024);
+    const hipError_t e = alloc_group({{&M->d_efirst, (cap + 1) * 8}, {&M->d_heads, cap * 4}, {&M->d_uid, cap * 4},
+                                      {&M->d_tail, 2 * sizeof(int64_t)}});
+    if (e != hipSuccess) return alloc_error(M->ctx, e, "mesh: allocating entry arrays");
   }
-  if (n_src > M->src_cap) {
-    if (M->d_src) (void)hipFree(M->d_src);
-    M->d_src = nullptr;
-    M->src_cap = 0;
-    const int64_t cap = std::max<int64_t>(n_src, 64);
-    const hipError_t e = hipMalloc(&M->d_src, (size_t)cap * sizeof(SepSrc));
-    if (e != hipSuccess) {
-      free_separated(M);
-      return alloc_error(M->ctx, e, "submap descriptors");
-    }
-    M->src_cap = cap;
-  }
-  return VGX_OK;
+  const hipError_t e = M->d_src.reserve((size_t)n_src * sizeof(SepSrc), 64 * sizeof(SepSrc));
+  return e == hipSuccess ? VGX_OK : alloc_error(M->ctx, e, "mesh: allocating submap descriptors");
 }
+
+// a quarter of slack (the next map is a little larger), at least 4096 triangles
+size_t tri_capacity(int64_t nt) { return (size_t)std::max<int64_t>(nt + nt / 4, 4096); }
 
 int ensure_colors(vgx_mesh M, int64_t nt) {
-  if (nt <= M->color_cap) return VGX_OK;
-  if (M->d_colors) (void)hipFree(M->d_colors);
-  M->d_colors = nullptr;
-  M->color_cap = 0;
-  const int64_t cap = std::max<int64_t>(nt + nt / 4, 4096);
-  const hipError_t e = hipMalloc(&M->d_colors, (size_t)cap * 4);
-  if (e != hipSuccess) return alloc_error(M->ctx, e, "colours");
-  M->color_cap = cap;
-  return VGX_OK;
+  if ((size_t)nt * 4 <= M->d_colors.bytes) return VGX_OK;
+  const hipError_t e = M->d_colors.alloc(tri_capacity(nt) * 4);
+  return e == hipSuccess ? VGX_OK : alloc_error(M->ctx, e, "mesh: allocating colours");
 }
 
 int ensure_tris(vgx_mesh M, int64_t nt) {
-  if (nt <= M->tri_cap) return VGX_OK;
-  free_tris(M);
-  const int64_t cap = std::max<int64_t>(nt + nt / 4, 4096);  // (a quarter of slack: the next map is a little larger)
-  hipError_t e = hipMalloc(&M->d_vertices, (size_t)cap * 36);
-  if (e == hipSuccess) e = hipMalloc(&M->d_normals, (size_t)cap * 12);
-  if (e != hipSuccess) {
-    free_tris(M);
-    return alloc_error(M->ctx, e, "triangles");
-  }
-  M->tri_cap = cap;
-  return VGX_OK;
+  if ((size_t)nt * 12 <= M->d_normals.bytes) return VGX_OK;
+  const size_t cap = tri_capacity(nt);
+  const hipError_t e = alloc_group({{&M->d_vertices, cap * 36}, {&M->d_normals, cap * 12}});
+  return e == hipSuccess ? VGX_OK : alloc_error(M->ctx, e, "mesh: allocating triangles");
 }
 
 template <bool PACKED>
@@ -620,31 +533,40 @@ int generate(vgx_ctx ctx, hipStream_t st, const MeshSrc& s, int vps, int32_t nb,
   for (int a = 0; a < 3; ++a) cells *= (double)s.lut_dim[a];
   unsigned end_bit = 1;
   while (end_bit < 64 && std::ldexp(1.0, (int)end_bit) < cells) ++end_bit;
-  // 1. order
+  // the sort and the scan share M->d_tmp and queue back to back: room for the larger is made once, before the first launch
+  auto sort = [&](void* tmp, size_t& bytes) {
+    return rocprim::radix_sort_pairs(tmp, bytes, M->d_keys[0].as<unsigned long long>(), M->d_keys[1].as<unsigned long long>(),
+                                     M->d_slots[0].as<int32_t>(), M->d_slots[1].as<int32_t>(), (size_t)nb, 0u, end_bit, st);
+  };
+  auto scan = [&](void* tmp, size_t& bytes) {
+    return rocprim::inclusive_scan(tmp, bytes, M->d_counts.as<int64_t>(), M->d_first.as<int64_t>() + 1, (size_t)nb,
+                                   rocprim::plus<int64_t>(), st);
+  };
   size_t sort_bytes = 0, scan_bytes = 0;
-  VGX_HIP(ctx, rocprim::radix_sort_pairs(nullptr, sort_bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                                         (int32_t*)nullptr, (int32_t*)nullptr, (size_t)nb, 0u, end_bit, st));
-  VGX_HIP(ctx, rocprim::inclusive_scan(nullptr, scan_bytes, (int64_t*)nullptr, (int64_t*)nullptr, (size_t)nb,
-                                       rocprim::plus<int64_t>(), st));
+  VGX_HIP(ctx, temp_bytes(sort, &sort_bytes));
+  VGX_HIP(ctx, temp_bytes(scan, &scan_bytes));
   int rc = ensure_blocks(M, nb, std::max<size_t>(std::max(sort_bytes, scan_bytes), 4));
   if (rc != VGX_OK) return rc;
-  hipLaunchKernelGGL(mesh_keys_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, s, nb, M->d_keys[0], M->d_slots[0]);
+  // 1. order
+  hipLaunchKernelGGL(mesh_keys_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, s, nb, M->d_keys[0].as<unsigned long long>(),
+                     M->d_slots[0].as<int32_t>());
   VGX_HIP(ctx, hipGetLastError());
-  VGX_HIP(ctx, rocprim::radix_sort_pairs(M->d_tmp, sort_bytes, M->d_keys[0], M->d_keys[1], M->d_slots[0], M->d_slots[1], (size_t)nb,
-                                         0u, end_bit, st));
+  VGX_HIP(ctx, sort(M->d_tmp.p, sort_bytes));
   // 2. count
-  VGX_HIP(ctx, launch_count<PACKED>(vps, st, nb, s, M->d_slots[1], mw, M->d_counts, M->d_block_index));
+  VGX_HIP(ctx, launch_count<PACKED>(vps, st, nb, s, M->d_slots[1].as<int32_t>(), mw, M->d_counts.as<int64_t>(),
+                                    M->d_block_index.as<int32_t>()));
   // 3. scan
-  VGX_HIP(ctx, hipMemsetAsync(M->d_first, 0, sizeof(int64_t), st));
-  VGX_HIP(ctx, rocprim::inclusive_scan(M->d_tmp, scan_bytes, M->d_counts, M->d_first + 1, (size_t)nb, rocprim::plus<int64_t>(), st));
+  VGX_HIP(ctx, hipMemsetAsync(M->d_first.p, 0, sizeof(int64_t), st));
+  VGX_HIP(ctx, scan(M->d_tmp.p, scan_bytes));
   int64_t total = 0;
-  VGX_HIP(ctx, hipMemcpyAsync(&total, M->d_first + nb, sizeof(total), hipMemcpyDeviceToHost, st));
+  VGX_HIP(ctx, hipMemcpyAsync(&total, M->d_first.as<int64_t>() + nb, sizeof(total), hipMemcpyDeviceToHost, st));
   VGX_HIP(ctx, hipStreamSynchronize(st));
   // 4. emit
   rc = ensure_tris(M, total);
   if (rc != VGX_OK) return rc;
   if (total > 0) {
-    VGX_HIP(ctx, launch_emit<PACKED>(vps, st, nb, s, M->d_slots[1], mw, M->d_first, M->d_vertices, M->d_normals));
+    VGX_HIP(ctx, launch_emit<PACKED>(vps, st, nb, s, M->d_slots[1].as<int32_t>(), mw, M->d_first.as<int64_t>(), M->d_vertices.as<float>(),
+                                     M->d_normals.as<float>()));
     VGX_HIP(ctx, hipStreamSynchronize(st));
   }
   M->n_blocks = nb;
@@ -655,11 +577,13 @@ int generate(vgx_ctx ctx, hipStream_t st, const MeshSrc& s, int vps, int32_t nb,
 template <int VPS>
 hipError_t launch_separated(bool emit, hipStream_t st, int32_t ne, vgx_mesh M, unsigned long long n_src, float mw) {
   if (emit)
-    hipLaunchKernelGGL(sep_emit_kernel<VPS>, dim3((unsigned)ne), dim3(kMeshThreads), 0, st, M->d_src, n_src, M->d_keys[1],
-                       M->d_slots[1], mw, M->d_efirst, M->d_vertices, M->d_normals, M->d_colors);
+    hipLaunchKernelGGL(sep_emit_kernel<VPS>, dim3((unsigned)ne), dim3(kMeshThreads), 0, st, M->d_src.as<SepSrc>(), n_src,
+                       M->d_keys[1].as<unsigned long long>(), M->d_slots[1].as<int32_t>(), mw, M->d_efirst.as<int64_t>(),
+                       M->d_vertices.as<float>(), M->d_normals.as<float>(), M->d_colors.as<uint32_t>());
   else
-    hipLaunchKernelGGL(sep_count_kernel<VPS>, dim3((unsigned)ne), dim3(kMeshThreads), 0, st, M->d_src, n_src, M->d_keys[1],
-                       M->d_slots[1], mw, M->d_counts, M->d_heads);
+    hipLaunchKernelGGL(sep_count_kernel<VPS>, dim3((unsigned)ne), dim3(kMeshThreads), 0, st, M->d_src.as<SepSrc>(), n_src,
+                       M->d_keys[1].as<unsigned long long>(), M->d_slots[1].as<int32_t>(), mw, M->d_counts.as<int64_t>(),
+                       M->d_heads.as<int32_t>());
   return hipGetLastError();
 }
 
@@ -668,34 +592,45 @@ hipError_t launch_separated(bool emit, hipStream_t st, int32_t ne, vgx_mesh M, u
 int generate_separated(vgx_ctx ctx, hipStream_t st, int vps, int32_t ne, const SepBox& box, unsigned end_bit, float mw,
                        vgx_mesh M) {
   const int32_t n = (int32_t)M->h_src.size();
+  // the sort and the two scans share M->d_tmp and queue back to back: room for the largest is made once, before the
+  // first launch
+  auto sort = [&](void* tmp, size_t& bytes) {
+    return rocprim::radix_sort_pairs(tmp, bytes, M->d_keys[0].as<unsigned long long>(), M->d_keys[1].as<unsigned long long>(),
+                                     M->d_slots[0].as<int32_t>(), M->d_slots[1].as<int32_t>(), (size_t)ne, 0u, end_bit, st);
+  };
+  auto scan = [&](void* tmp, size_t& bytes) {
+    return rocprim::inclusive_scan(tmp, bytes, M->d_counts.as<int64_t>(), M->d_efirst.as<int64_t>() + 1, (size_t)ne,
+                                   rocprim::plus<int64_t>(), st);
+  };
+  auto flag_scan = [&](void* tmp, size_t& bytes) {
+    return rocprim::inclusive_scan(tmp, bytes, M->d_heads.as<int32_t>(), M->d_uid.as<int32_t>(), (size_t)ne, rocprim::plus<int32_t>(), st);
+  };
   size_t sort_bytes = 0, scan_bytes = 0, flag_bytes = 0;
-  VGX_HIP(ctx, rocprim::radix_sort_pairs(nullptr, sort_bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                                         (int32_t*)nullptr, (int32_t*)nullptr, (size_t)ne, 0u, end_bit, st));
-  VGX_HIP(ctx, rocprim::inclusive_scan(nullptr, scan_bytes, (int64_t*)nullptr, (int64_t*)nullptr, (size_t)ne,
-                                       rocprim::plus<int64_t>(), st));
-  VGX_HIP(ctx, rocprim::inclusive_scan(nullptr, flag_bytes, (int32_t*)nullptr, (int32_t*)nullptr, (size_t)ne,
-                                       rocprim::plus<int32_t>(), st));
+  VGX_HIP(ctx, temp_bytes(sort, &sort_bytes));
+  VGX_HIP(ctx, temp_bytes(scan, &scan_bytes));
+  VGX_HIP(ctx, temp_bytes(flag_scan, &flag_bytes));
   int rc = ensure_blocks(M, ne, std::max<size_t>(std::max(std::max(sort_bytes, scan_bytes), flag_bytes), 4));
   if (rc == VGX_OK) rc = ensure_entries(M, ne, n);
   if (rc != VGX_OK) return rc;
   // 1. descriptors, keys, one sort
-  VGX_HIP(ctx, hipMemcpyAsync(M->d_src, M->h_src.data(), M->h_src.size() * sizeof(SepSrc), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(sep_keys_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, M->d_src, n, (int64_t)ne, box, M->d_keys[0],
-                     M->d_slots[0]);
+  VGX_HIP(ctx, hipMemcpyAsync(M->d_src.p, M->h_src.data(), M->h_src.size() * sizeof(SepSrc), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(sep_keys_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, M->d_src.as<SepSrc>(), n, (int64_t)ne, box,
+                     M->d_keys[0].as<unsigned long long>(), M->d_slots[0].as<int32_t>());
   VGX_HIP(ctx, hipGetLastError());
-  VGX_HIP(ctx, rocprim::radix_sort_pairs(M->d_tmp, sort_bytes, M->d_keys[0], M->d_keys[1], M->d_slots[0], M->d_slots[1], (size_t)ne,
-                                         0u, end_bit, st));
+  VGX_HIP(ctx, sort(M->d_tmp.p, sort_bytes));
   // 2. count, 3. scan the counts and the block heads; the unique blocks and their first triangles
   VGX_HIP(ctx, vps == 16 ? launch_separated<16>(false, st, ne, M, (unsigned long long)n, mw)
                          : launch_separated<8>(false, st, ne, M, (unsigned long long)n, mw));
-  VGX_HIP(ctx, hipMemsetAsync(M->d_efirst, 0, sizeof(int64_t), st));
-  VGX_HIP(ctx, rocprim::inclusive_scan(M->d_tmp, scan_bytes, M->d_counts, M->d_efirst + 1, (size_t)ne, rocprim::plus<int64_t>(), st));
-  VGX_HIP(ctx, rocprim::inclusive_scan(M->d_tmp, flag_bytes, M->d_heads, M->d_uid, (size_t)ne, rocprim::plus<int32_t>(), st));
-  hipLaunchKernelGGL(sep_unique_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, M->d_src, (unsigned long long)n,
-                     M->d_keys[1], M->d_slots[1], ne, M->d_heads, M->d_uid, M->d_efirst, M->d_block_index, M->d_first, M->d_tail);
+  VGX_HIP(ctx, hipMemsetAsync(M->d_efirst.p, 0, sizeof(int64_t), st));
+  VGX_HIP(ctx, scan(M->d_tmp.p, scan_bytes));
+  VGX_HIP(ctx, flag_scan(M->d_tmp.p, flag_bytes));
+  hipLaunchKernelGGL(sep_unique_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, M->d_src.as<SepSrc>(), (unsigned long long)n,
+                     M->d_keys[1].as<unsigned long long>(), M->d_slots[1].as<int32_t>(), ne, M->d_heads.as<int32_t>(),
+                     M->d_uid.as<int32_t>(), M->d_efirst.as<int64_t>(), M->d_block_index.as<int32_t>(), M->d_first.as<int64_t>(),
+                     M->d_tail.as<int64_t>());
   VGX_HIP(ctx, hipGetLastError());
   int64_t tail[2] = {0, 0};
-  VGX_HIP(ctx, hipMemcpyAsync(tail, M->d_tail, sizeof(tail), hipMemcpyDeviceToHost, st));
+  VGX_HIP(ctx, hipMemcpyAsync(tail, M->d_tail.p, sizeof(tail), hipMemcpyDeviceToHost, st));
   VGX_HIP(ctx, hipStreamSynchronize(st));
   // 4. emit
   const int64_t total = tail[0];
@@ -710,6 +645,21 @@ int generate_separated(vgx_ctx ctx, hipStream_t st, int vps, int32_t ne, const S
   M->n_blocks = (int32_t)tail[1];
   M->n_tris = total;
   return VGX_OK;
+}
+
+// a finished submap's raw TSDF layer as a source
+MeshSrc mesh_src(vgx_submap sm) {
+  MeshSrc s{};
+  s.lut = sm->d_lut;
+  for (int a = 0; a < 3; ++a) {
+    s.lut_min[a] = sm->lut_min[a];
+    s.lut_dim[a] = sm->lut_dim[a];
+  }
+  s.block_index = sm->d_block_index;
+  s.dist = sm->d_tsdf_distance;
+  s.weight = sm->d_tsdf_weight;
+  s.voxel_size = sm->voxel_size;
+  return s;
 }
 
 // shared refusals; *mw the threshold to use
@@ -736,9 +686,9 @@ MeshView mesh_view(vgx_mesh M) {
   v.ctx = M->ctx;
   v.holds_mesh = M->holds_mesh;
   v.n_tris = M->n_tris;
-  v.vertices = M->d_vertices;
-  v.normals = M->d_normals;
-  v.colors = M->has_colors ? M->d_colors : nullptr;
+  v.vertices = M->d_vertices.as<float>();
+  v.normals = M->d_normals.as<float>();
+  v.colors = M->has_colors ? M->d_colors.as<uint32_t>() : nullptr;
   v.has_colors = M->has_colors;
   return v;
 }
@@ -762,9 +712,6 @@ int vgx_mesh_create(vgx_ctx ctx, vgx_mesh* out) {
 int vgx_mesh_destroy(vgx_mesh M) {
   if (!M) return VGX_ERR_INVALID;
   (void)hipSetDevice(M->ctx->device);
-  free_blocks(M);
-  free_tris(M);
-  free_separated(M);
   delete M;
   return VGX_OK;
 }
@@ -779,10 +726,7 @@ int vgx_tsdf_layer_generate_mesh(vgx_tsdf_layer L, const vgx_mesh_config* cfg, v
   std::lock_guard<std::mutex> tsdf_lk(ctx->tsdf_mu);
   std::lock_guard<std::mutex> reg_lk(ctx->mu);  // (lock order: tsdf_mu, then mu -- as vgx_tsdf_layer_merge_submaps)
   VGX_HIP(ctx, hipSetDevice(ctx->device));
-  M->n_blocks = 0;
-  M->n_tris = 0;
-  M->has_colors = false;
-  M->holds_mesh = false;
+  M->reset_stats();
   int32_t nb = 0;
   unsigned long long dropped = 0;
   rc = tsdf_read_stats(L, &nb, &dropped);  // (behind the scans and merges queued on the TSDF stream)
@@ -815,21 +759,8 @@ int vgx_submap_generate_mesh(vgx_submap sm, const vgx_mesh_config* cfg, vgx_mesh
   std::lock_guard<std::mutex> mesh_lk(M->mu);
   std::lock_guard<std::mutex> reg_lk(ctx->mu);
   VGX_HIP(ctx, hipSetDevice(ctx->device));
-  M->n_blocks = 0;
-  M->n_tris = 0;
-  M->has_colors = false;
-  M->holds_mesh = false;
-  MeshSrc s{};
-  s.lut = sm->d_lut;
-  for (int a = 0; a < 3; ++a) {
-    s.lut_min[a] = sm->lut_min[a];
-    s.lut_dim[a] = sm->lut_dim[a];
-  }
-  s.block_index = sm->d_block_index;
-  s.dist = sm->d_tsdf_distance;
-  s.weight = sm->d_tsdf_weight;
-  s.voxel_size = sm->voxel_size;
-  rc = generate<false>(ctx, ctx->stream, s, sm->vps, sm->n_blocks, mw, M);
+  M->reset_stats();
+  rc = generate<false>(ctx, ctx->stream, mesh_src(sm), sm->vps, sm->n_blocks, mw, M);
   M->holds_mesh = rc == VGX_OK;
   return rc;
 }
@@ -887,10 +818,7 @@ int vgx_submaps_generate_separated_mesh(vgx_ctx ctx, int32_t n, const vgx_submap
   std::lock_guard<std::mutex> mesh_lk(M->mu);
   std::lock_guard<std::mutex> reg_lk(ctx->mu);
   VGX_HIP(ctx, hipSetDevice(ctx->device));
-  M->n_blocks = 0;
-  M->n_tris = 0;
-  M->has_colors = false;
-  M->holds_mesh = false;
+  M->reset_stats();
   if (n_entries == 0) {
     M->has_colors = true;
     M->holds_mesh = true;
@@ -901,15 +829,7 @@ int vgx_submaps_generate_separated_mesh(vgx_ctx ctx, int32_t n, const vgx_submap
   for (int32_t i = 0; i < n; ++i) {
     const vgx_submap sm = submaps[i];
     SepSrc& d = M->h_src[(size_t)i];
-    d.m.lut = sm->d_lut;
-    for (int a = 0; a < 3; ++a) {
-      d.m.lut_min[a] = sm->lut_min[a];
-      d.m.lut_dim[a] = sm->lut_dim[a];
-    }
-    d.m.block_index = sm->d_block_index;
-    d.m.dist = sm->d_tsdf_distance;
-    d.m.weight = sm->d_tsdf_weight;
-    d.m.voxel_size = sm->voxel_size;
+    d.m = mesh_src(sm);
     const float* T = T_M_S + 7 * (size_t)i;
     for (int k = 0; k < 4; ++k) d.pose.q[k] = T[k];
     for (int k = 0; k < 3; ++k) d.pose.t[k] = T[4 + k];
@@ -941,7 +861,7 @@ int vgx_mesh_download_colors(vgx_mesh M, uint8_t* rgba) {
   std::lock_guard<std::mutex> lk(M->mu);
   if (!M->has_colors) return set_error(ctx, VGX_ERR_INVALID, "vgx_mesh_download_colors: the mesh has no colours");
   VGX_HIP(ctx, hipSetDevice(ctx->device));
-  if (M->n_tris > 0) VGX_HIP(ctx, hipMemcpy(rgba, M->d_colors, (size_t)M->n_tris * 4, hipMemcpyDeviceToHost));
+  if (M->n_tris > 0) VGX_HIP(ctx, hipMemcpy(rgba, M->d_colors.p, (size_t)M->n_tris * 4, hipMemcpyDeviceToHost));
   return VGX_OK;
 }
 
@@ -961,12 +881,12 @@ int vgx_mesh_download(vgx_mesh M, int32_t* block_index, int64_t* first, float* v
   const int64_t nb = M->n_blocks, nt = M->n_tris;
   if (first && nb == 0) first[0] = 0;
   if (nb > 0) {
-    if (block_index) VGX_HIP(ctx, hipMemcpy(block_index, M->d_block_index, (size_t)nb * 12, hipMemcpyDeviceToHost));
-    if (first) VGX_HIP(ctx, hipMemcpy(first, M->d_first, (size_t)(nb + 1) * 8, hipMemcpyDeviceToHost));
+    if (block_index) VGX_HIP(ctx, hipMemcpy(block_index, M->d_block_index.p, (size_t)nb * 12, hipMemcpyDeviceToHost));
+    if (first) VGX_HIP(ctx, hipMemcpy(first, M->d_first.p, (size_t)(nb + 1) * 8, hipMemcpyDeviceToHost));
   }
   if (nt > 0) {
-    if (vertices) VGX_HIP(ctx, hipMemcpy(vertices, M->d_vertices, (size_t)nt * 36, hipMemcpyDeviceToHost));
-    if (normals) VGX_HIP(ctx, hipMemcpy(normals, M->d_normals, (size_t)nt * 12, hipMemcpyDeviceToHost));
+    if (vertices) VGX_HIP(ctx, hipMemcpy(vertices, M->d_vertices.p, (size_t)nt * 36, hipMemcpyDeviceToHost));
+    if (normals) VGX_HIP(ctx, hipMemcpy(normals, M->d_normals.p, (size_t)nt * 12, hipMemcpyDeviceToHost));
   }
   return VGX_OK;
 }

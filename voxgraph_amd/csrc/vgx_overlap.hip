@@ -171,27 +171,18 @@ int vgx_find_overlapping_pairs(vgx_ctx ctx, int32_t n, const vgx_submap* submaps
       cand.push_back(p);
     }
   if (cand.empty()) return VGX_OK;
-  OverlapSubmapDev* d_subs = nullptr;
-  OverlapPairDev* d_pairs = nullptr;
-  int32_t* d_res = nullptr;
+  DeviceBuffer d_subs, d_pairs, d_res;
   std::vector<int32_t> res(cand.size());
-  int rc = VGX_OK;
-  hipError_t e = hipMalloc(&d_subs, subs.size() * sizeof(OverlapSubmapDev));
-  if (e == hipSuccess) e = hipMalloc(&d_pairs, cand.size() * sizeof(OverlapPairDev));
-  if (e == hipSuccess) e = hipMalloc(&d_res, cand.size() * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMemcpy(d_subs, subs.data(), subs.size() * sizeof(OverlapSubmapDev), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_pairs, cand.data(), cand.size() * sizeof(OverlapPairDev), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(overlap_kernel, dim3((unsigned)cand.size()), dim3(256), 0, ctx->stream, d_subs, d_pairs, d_res);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(res.data(), d_res, res.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) rc = set_error(ctx, VGX_ERR_HIP, std::string("vgx_find_overlapping_pairs: ") + hipGetErrorString(e));
-  if (d_subs) (void)hipFree(d_subs);
-  if (d_pairs) (void)hipFree(d_pairs);
-  if (d_res) (void)hipFree(d_res);
-  if (rc != VGX_OK) return rc;
+  VGX_HIP(ctx, d_subs.alloc(subs.size() * sizeof(OverlapSubmapDev)));
+  VGX_HIP(ctx, d_pairs.alloc(cand.size() * sizeof(OverlapPairDev)));
+  VGX_HIP(ctx, d_res.alloc(cand.size() * sizeof(int32_t)));
+  VGX_HIP(ctx, hipMemcpy(d_subs.p, subs.data(), subs.size() * sizeof(OverlapSubmapDev), hipMemcpyHostToDevice));
+  VGX_HIP(ctx, hipMemcpy(d_pairs.p, cand.data(), cand.size() * sizeof(OverlapPairDev), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(overlap_kernel, dim3((unsigned)cand.size()), dim3(256), 0, ctx->stream, d_subs.as<OverlapSubmapDev>(),
+                     d_pairs.as<OverlapPairDev>(), d_res.as<int32_t>());
+  VGX_HIP(ctx, hipGetLastError());
+  VGX_HIP(ctx, hipMemcpyAsync(res.data(), d_res.p, res.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   int32_t k = 0;
   for (size_t c = 0; c < cand.size(); ++c)
     if (res[c]) {

@@ -404,7 +404,7 @@ int project_submaps(vgx_tsdf_layer L, int32_t n, const vgx_submap* submaps, cons
   }
 
   // 2. candidate pairs: count, then emit
-  DeviceScratch d_src, d_first, d_cursor;
+  DeviceBuffer d_src, d_first, d_cursor;
   VGX_HIP(ctx, d_src.alloc(src.size() * sizeof(ProjectSrc)));
   VGX_HIP(ctx, d_first.alloc(src_first.size() * sizeof(int64_t)));
   VGX_HIP(ctx, d_cursor.alloc(sizeof(unsigned long long)));
@@ -425,7 +425,7 @@ int project_submaps(vgx_tsdf_layer L, int32_t n, const vgx_submap* submaps, cons
     if (rc == VGX_OK && n_blocks_out) *n_blocks_out = nb_now;
     return rc;
   }
-  DeviceScratch d_keys, d_sorted, d_heads, d_seg, d_nseg, d_tmp;
+  DeviceBuffer d_keys, d_sorted, d_heads, d_seg, d_nseg, d_tmp;
   VGX_HIP(ctx, d_keys.alloc((size_t)n_pairs * 8));
   VGX_HIP(ctx, d_sorted.alloc((size_t)n_pairs * 8));
   VGX_HIP(ctx, d_heads.alloc((size_t)n_pairs));
@@ -437,21 +437,24 @@ int project_submaps(vgx_tsdf_layer L, int32_t n, const vgx_submap* submaps, cons
                      (unsigned long long)n_pairs);
   VGX_HIP(ctx, hipGetLastError());
 
-  // 3. sort; segment starts
+  // 3. sort; segment starts.  The two share d_tmp and queue back to back: room for the larger is made once, before the sort
+  auto sort = [&](void* tmp, size_t& bytes) {
+    return rocprim::radix_sort_keys(tmp, bytes, d_keys.as<unsigned long long>(), d_sorted.as<unsigned long long>(), (size_t)n_pairs, 0u,
+                                    end_bit, st);
+  };
+  auto select = [&](void* tmp, size_t& bytes) {
+    return rocprim::select(tmp, bytes, rocprim::make_counting_iterator<uint32_t>(0u), d_heads.as<uint8_t>(), d_seg.as<uint32_t>(),
+                           d_nseg.as<uint32_t>(), (size_t)n_pairs, st);
+  };
   size_t sort_bytes = 0, select_bytes = 0;
-  auto iota = rocprim::make_counting_iterator<uint32_t>(0u);
-  VGX_HIP(ctx, rocprim::radix_sort_keys(nullptr, sort_bytes, d_keys.as<unsigned long long>(), d_sorted.as<unsigned long long>(),
-                                        (size_t)n_pairs, 0u, end_bit, st));
-  VGX_HIP(ctx, rocprim::select(nullptr, select_bytes, iota, d_heads.as<uint8_t>(), d_seg.as<uint32_t>(), d_nseg.as<uint32_t>(),
-                               (size_t)n_pairs, st));
+  VGX_HIP(ctx, temp_bytes(sort, &sort_bytes));
+  VGX_HIP(ctx, temp_bytes(select, &select_bytes));
   VGX_HIP(ctx, d_tmp.alloc(std::max<size_t>(std::max(sort_bytes, select_bytes), 4)));
-  VGX_HIP(ctx, rocprim::radix_sort_keys(d_tmp.p, sort_bytes, d_keys.as<unsigned long long>(), d_sorted.as<unsigned long long>(),
-                                        (size_t)n_pairs, 0u, end_bit, st));
+  VGX_HIP(ctx, sort(d_tmp.p, sort_bytes));
   hipLaunchKernelGGL(segment_heads_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, st, d_sorted.as<unsigned long long>(), n_pairs,
                      pos_bits, d_heads.as<uint8_t>());
   VGX_HIP(ctx, hipGetLastError());
-  VGX_HIP(ctx, rocprim::select(d_tmp.p, select_bytes, iota, d_heads.as<uint8_t>(), d_seg.as<uint32_t>(), d_nseg.as<uint32_t>(),
-                               (size_t)n_pairs, st));
+  VGX_HIP(ctx, select(d_tmp.p, select_bytes));
   uint32_t n_seg = 0;
   VGX_HIP(ctx, hipMemcpyAsync(&n_seg, d_nseg.p, sizeof(n_seg), hipMemcpyDeviceToHost, st));
   VGX_HIP(ctx, hipStreamSynchronize(st));

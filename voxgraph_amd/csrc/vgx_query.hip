@@ -31,7 +31,7 @@ int query_run(vgx_submap sm, int32_t layer, int32_t flags, const float* T_Q_S, i
   std::lock_guard<std::mutex> lk(ctx->mu);
   VGX_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  DeviceScratch d_pts, d_dist, d_grad, d_wgt, d_valid;
+  DeviceBuffer d_pts, d_dist, d_grad, d_wgt, d_valid;
   const size_t un = (size_t)n;
   if (host) {
     VGX_HIP(ctx, d_pts.alloc(un * 12));

@@ -2274,7 +2274,7 @@ static int apply_launch_order(vgx_reg_batch b, const std::vector<Tile>& tiles, T
   vgx_ctx ctx = b->ctx;
   bool& grouped = points_pass ? b->points_order_grouped : b->launch_order_grouped;
   const int n_tiles = (int)tiles.size();
-  DeviceScratch s_live;
+  DeviceBuffer s_live;
   VGX_HIP(ctx, s_live.alloc((size_t)n_tiles * sizeof(int32_t)));
   hipLaunchKernelGGL(reg_tile_live_kernel, dim3(n_tiles), dim3(64), 0, ctx->stream, b->d_desc, b->d_pack,
                      d_tiles, n_tiles, s_live.as<int32_t>());
@@ -2722,7 +2722,7 @@ int vgx_reg_batch_launch_order(vgx_reg_batch b, int32_t pass, int32_t* grouped) 
 static int count_live_each(vgx_reg_batch b, std::vector<unsigned long long>& each) {
   vgx_ctx ctx = b->ctx;
   each.assign((size_t)b->n, 0);
-  DeviceScratch counter;
+  DeviceBuffer counter;
   VGX_HIP(ctx, counter.alloc((size_t)b->n * sizeof(unsigned long long)));
   VGX_HIP(ctx, hipMemsetAsync(counter.p, 0, (size_t)b->n * sizeof(unsigned long long), ctx->stream));
   hipLaunchKernelGGL(reg_count_live_kernel, dim3(b->n), dim3(256), 0, ctx->stream, b->d_desc, b->d_pack, b->n,

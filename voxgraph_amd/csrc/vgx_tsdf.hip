@@ -757,7 +757,7 @@ int vgx_tsdf_layer_upload(vgx_tsdf_layer L, int32_t n_blocks, const int32_t* blo
   if (rc != VGX_OK) return rc;
   if (n_blocks > 0) {
     const size_t nv = (size_t)n_blocks * vpb;
-    DeviceScratch sd, sw;
+    DeviceBuffer sd, sw;
     VGX_HIP(ctx, sd.alloc(nv * 4));
     VGX_HIP(ctx, sw.alloc(nv * 4));
     VGX_HIP(ctx, hipMemcpy(sd.p, distance, nv * 4, hipMemcpyHostToDevice));

@@ -51,26 +51,15 @@
 
 namespace vgx {
 
-namespace {
-
-struct Buf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  template <class T>
-  T* as() const { return (T*)p; }
-};
-
-}  // namespace
-
 struct DetScratch {
   // per point, indexed by position in the visiting order
-  Buf ray_pg, ray_color, ray_flags, start_val, start_key, start_key_sorted, start_seq_sorted, count, off, T, broke,
+  DeviceBuffer ray_pg, ray_color, ray_flags, start_val, start_key, start_key_sorted, start_seq_sorted, count, off, T, broke,
       full_count, ext, walked;
   // per speculative access
-  Buf acc_vox, acc_key, acc_ray, s_key, s_idx, s_r, s_k, s_h, last, seen, c_idx, c_key;
-  Buf tmp;  // rocprim temporary storage
+  DeviceBuffer acc_vox, acc_key, acc_ray, s_key, s_idx, s_r, s_k, s_h, last, seen, c_idx, c_key;
+  DeviceBuffer tmp;  // rocprim temporary storage
   // block allocation
-  Buf first_touch, new_cells, new_cells_sorted, new_keys, new_keys_sorted, long_runs, t_at, t_sdf, t_w, t_color, t_far;
+  DeviceBuffer first_touch, new_cells, new_cells_sorted, new_keys, new_keys_sorted, long_runs, t_at, t_sdf, t_w, t_color, t_far;
   bool first_touch_dirty = false;  // a scan failed between marking and assigning: refill
   // device counters (u64 each, enum below) + a pinned mirror; behind the mirror, pinned too, the other small
   // values a scan reads back (kHost*): every copy of a read-back queues behind the previous one and only the
@@ -79,7 +68,7 @@ struct DetScratch {
   unsigned long long* h_ctr = nullptr;
   // the sweeps (det_sweep_kernel): one 8-byte state per tile of the sorted accesses, tagged with the sweep's
   // epoch so that nothing has to be cleared between sweeps; zeroed when (re)allocated
-  Buf tile_state;
+  DeviceBuffer tile_state;
   uint32_t sweep_epoch = 0;      // ... and of every TileChain launch (one counter: the words are shared)
   uint32_t chain_tickets = 0;    // TileChain workgroups launched since the scan's first kernel zeroed kCtrChainTicket
   // what the sweep's last block tells the host (pinned, written from the kernel): sweep sequence number << 2 |
@@ -102,13 +91,6 @@ constexpr long long kVoxBias = 1ll << 20;  // 21 bits per axis
 
 void det_scratch_free(DetScratch* s) {
   if (!s) return;
-  Buf* all[] = {&s->ray_pg, &s->ray_color, &s->ray_flags, &s->start_val, &s->start_key, &s->start_key_sorted,
-                &s->start_seq_sorted, &s->count, &s->off, &s->T, &s->broke, &s->full_count, &s->ext, &s->walked, &s->acc_vox, &s->acc_key, &s->acc_ray,
-                &s->s_key, &s->s_idx, &s->s_r, &s->s_k, &s->s_h, &s->last, &s->seen, &s->c_idx, &s->c_key, &s->tmp,
-                &s->first_touch, &s->new_cells, &s->new_cells_sorted, &s->new_keys, &s->new_keys_sorted, &s->long_runs,
-                &s->t_at, &s->t_sdf, &s->t_w, &s->t_color, &s->t_far, &s->tile_state};
-  for (Buf* b : all)
-    if (b->p) (void)hipFree(b->p);
   if (s->d_ctr) (void)hipFree(s->d_ctr);
   if (s->h_ctr) (void)hipHostFree(s->h_ctr);
   if (s->h_flag) (void)hipHostFree(s->h_flag);
@@ -1096,18 +1078,14 @@ __global__ __launch_bounds__(256) void det_merged_walk_kernel(vgx_tsdf_config c,
 }
 
 // ---------------------------------------------------------------------------------------------------
-int grow(vgx_ctx ctx, Buf& b, size_t bytes) {
+int grow(vgx_ctx ctx, DeviceBuffer& b, size_t bytes) {
   if (b.bytes >= bytes) return VGX_OK;
-  VGX_HIP(ctx, hipStreamSynchronize(ctx->tsdf_stream));
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
-  const size_t want = std::max<size_t>(bytes + bytes / 4, 256);  // a quarter of slack: scans of a session vary
-  if (hipMalloc(&b.p, want) != hipSuccess) {
+  VGX_HIP(ctx, hipStreamSynchronize(ctx->tsdf_stream));  // (kernels queued on it may still read the old array)
+  if (b.reserve(bytes, 256, true) != hipSuccess) {  // a quarter of slack: scans of a session vary
     (void)hipGetLastError();
-    return set_error(ctx, VGX_ERR_NOMEM, "TSDF reproducible mode: scratch allocation failed (" + std::to_string(want) + " bytes)");
+    return set_error(ctx, VGX_ERR_NOMEM, "TSDF reproducible mode: scratch allocation failed (" +
+                                             std::to_string(std::max<size_t>(bytes + bytes / 4, 256)) + " bytes)");
   }
-  b.bytes = want;
   return VGX_OK;
 }
 
@@ -1126,7 +1104,7 @@ int fetch_u32(vgx_ctx ctx, DetScratch* S, int word, const void* dev) {
   return VGX_OK;
 }
 
-int grow_zeroed(vgx_ctx ctx, Buf& b, size_t bytes) {
+int grow_zeroed(vgx_ctx ctx, DeviceBuffer& b, size_t bytes) {
   if (b.bytes >= bytes) return VGX_OK;
   int rc = grow(ctx, b, bytes);
   if (rc != VGX_OK) return rc;
@@ -1163,17 +1141,25 @@ int wait_for_sweep(vgx_ctx ctx, DetScratch* S, unsigned long long seq, unsigned 
   }
 }
 
+// a rocPRIM call on S->tmp, grown (behind a synchronisation of the TSDF stream: grow) to what the call asks for
+template <class Call>
+int sort_with_temp(vgx_ctx ctx, DetScratch* S, Call& call) {
+  size_t bytes = 0;
+  VGX_HIP(ctx, temp_bytes(call, &bytes));
+  DET_TRY(grow(ctx, S->tmp, bytes));
+  bytes = S->tmp.bytes;
+  VGX_HIP(ctx, call(S->tmp.p, bytes));
+  return VGX_OK;
+}
+
 // keys (end_bit bits) -> keys_sorted, and where every sorted key came from; stable
 int sort_by_slot(vgx_ctx ctx, DetScratch* S, const uint32_t* keys, uint32_t* keys_sorted, uint32_t* idx_sorted, size_t n,
                  unsigned end_bit) {
-  size_t bytes = 0;
-  auto iota = rocprim::make_counting_iterator<uint32_t>(0u);
-  VGX_HIP(ctx, stable_sort_pairs(nullptr, bytes, keys, keys_sorted, iota, idx_sorted, n, end_bit, ctx->tsdf_stream));
-  int rc = grow(ctx, S->tmp, bytes);
-  if (rc != VGX_OK) return rc;
-  bytes = S->tmp.bytes;
-  VGX_HIP(ctx, stable_sort_pairs(S->tmp.p, bytes, keys, keys_sorted, iota, idx_sorted, n, end_bit, ctx->tsdf_stream));
-  return VGX_OK;
+  auto sort = [&](void* tmp, size_t& bytes) {
+    return stable_sort_pairs(tmp, bytes, keys, keys_sorted, rocprim::make_counting_iterator<uint32_t>(0u), idx_sorted, n, end_bit,
+                             ctx->tsdf_stream);
+  };
+  return sort_with_temp(ctx, S, sort);
 }
 
 // the chain of the next prefix-sum launch over `tiles` workgroups: room for its words, its epoch, its ticket base
@@ -1403,15 +1389,11 @@ static int det_commit(vgx_tsdf_integrator I, DetScratch* S, const float T[7], si
                          S->new_cells.as<int32_t>(), S->first_touch.as<unsigned long long>(),
                          S->new_keys.as<unsigned long long>());
       VGX_HIP(ctx, hipGetLastError());
-      size_t bytes = 0;
-      VGX_HIP(ctx, rocprim::radix_sort_pairs(nullptr, bytes, S->new_keys.as<unsigned long long>(),
-                                             S->new_keys_sorted.as<unsigned long long>(), S->new_cells.as<int32_t>(),
-                                             S->new_cells_sorted.as<int32_t>(), n_new, 0, 64, st));
-      DET_TRY(grow(ctx, S->tmp, bytes));
-      bytes = S->tmp.bytes;
-      VGX_HIP(ctx, rocprim::radix_sort_pairs(S->tmp.p, bytes, S->new_keys.as<unsigned long long>(),
-                                             S->new_keys_sorted.as<unsigned long long>(), S->new_cells.as<int32_t>(),
-                                             S->new_cells_sorted.as<int32_t>(), n_new, 0, 64, st));
+      auto sort = [&](void* tmp, size_t& bytes) {
+        return rocprim::radix_sort_pairs(tmp, bytes, S->new_keys.as<unsigned long long>(), S->new_keys_sorted.as<unsigned long long>(),
+                                         S->new_cells.as<int32_t>(), S->new_cells_sorted.as<int32_t>(), n_new, 0, 64, st);
+      };
+      DET_TRY(sort_with_temp(ctx, S, sort));
       hipLaunchKernelGGL(det_assign_kernel, dim3(blocks_for(n_new)), dim3(256), 0, st, L, (uint32_t)n_new, n_blocks_now,
                          S->new_cells_sorted.as<int32_t>(), S->first_touch.as<unsigned long long>());
       VGX_HIP(ctx, hipGetLastError());
