@@ -697,6 +697,87 @@ VGX_API int vgx_tsdf_integrate_merged_device(vgx_tsdf_integrator integrator, con
                                              const void* d_points_C, const void* d_rgba, int64_t n,
                                              int32_t freespace_points, int64_t* n_updates);
 
+/* ---- Scans: a raw sensor_msgs/PointCloud2 decoded on the device ------------------ */
+/* What PointcloudIntegrator::integratePointcloud does on the host before it reaches the integrator
+ * (pointcloud_integrator.cpp:29-63): pcl::fromROSMsg into a PointXYZ / PointXYZI / PointXYZRGB cloud and
+ * voxblox::convertPointcloud, which drops the points that are not finite and makes one colour per kept point.  A vgx_scan
+ * holds the result on the device -- the kept points [n][3] f32 and their colours [n][4] u8, in message order -- and the
+ * integrators take it as it is.  The caller resolves the message's field names to byte offsets (vgx_scan_layout; the C++
+ * mirror gpu_pointcloud_integrator.h does it from a message).  PCL and voxblox_ros are not vendored: every colour rule
+ * and the filter are [recalled] from voxblox_ros/conversions.h, voxblox/utils/color_maps.h and PCL's point layouts.
+ * Rules (what the kernel, vgx_scan.hip, and tests/scan_msg_ref.py both follow; f32, no contraction):
+ *   addressing  point i = r * width + c lies at data + r * row_step + c * point_step; fields are little-endian.  Any
+ *               point_step >= 1 and any offsets whose 4 bytes fit in point_step are legal: unaligned fields, overlapping
+ *               fields and padded rows included.  When data, point_step, row_step and the offsets are all multiples of
+ *               4 the kernel loads dwords, else it assembles every field from byte loads; the result is the same.
+ *   filter      kept iff isfinite(x) && isfinite(y) && isfinite(z) (convertPointcloud's isPointFinite [recalled]); the
+ *               three floats are copied bit for bit (-0.0 stays -0.0).  Kept points stay in ascending i: the order the
+ *               reproducible mode visits them in and the one that decides which point takes a start voxel.
+ *               n_dropped = width * height - n_points.
+ *   colour      VGX_SCAN_COLOR_RGB: bytes b0 b1 b2 b3 at color_offset give rgba = (b2, b1, b0, b3) -- PCL's packed
+ *               0xAARRGGBB and Color(p.r, p.g, p.b, p.a).  VGX_SCAN_COLOR_INTENSITY: v the f32 at color_offset;
+ *               v = (min < v) ? v : min; v = (v < max) ? v : max (std::max(min, v), std::min(max, .) with their argument
+ *               order: NaN becomes min); h = (v - min) / (max - min) in f32; g = (uint8) std::round((double)h * 255.0)
+ *               (grayColorMap); rgba = (g, g, g, 255).  VGX_SCAN_COLOR_NONE: every kept point gets constant_rgba.
+ * Refused with VGX_ERR_INVALID before anything is uploaded or launched, the scan keeping what it held (vgx_last_error
+ * says which): NULL arguments, a scan of another context, point_step == 0, a field whose 4 bytes do not fit in
+ * point_step, row_step < width * point_step, an unknown color_kind, n_bytes < (height - 1) * row_step + width *
+ * point_step when width * height > 0, an intensity range that is not finite or not max > min (the decode
+ * calls check it, whatever the color_kind).  VGX_ERR_UNSUPPORTED: is_bigendian != 0; width * height >= 2^31.  Coordinates that are not FLOAT32 cannot be
+ * expressed in the layout.  width * height == 0, or a cloud whose every point is dropped: VGX_OK and 0 points;
+ * integrating such a scan is the empty scan of vgx_tsdf_integrate.  Out of device memory: VGX_ERR_NOMEM, and the handle
+ * then holds no scan (stats report 0).
+ * Streams: decoding runs on the context's TSDF stream under the TSDF lock: the upload (host variant: through two pinned
+ * staging buffers filled in turn, so that the host copy of one piece overlaps the upload of the piece before; pageable
+ * memory where no pinned memory is to be had), ONE kernel whatever the size -- the compaction's prefix sum is taken inside
+ * the launch -- and a 16-byte read-back of the kept-point count, which is the call's one host synchronisation.
+ * vgx_scan_stats costs nothing afterwards.  The arrays hold width * height points' room and grow on demand behind a
+ * stream synchronisation.  vgx_tsdf_integrate[_merged]_scan is vgx_tsdf_integrate[_merged]_device on the scan's arrays
+ * and count: n_updates == NULL returns with the scan queued, and because decode and integration share a stream the handle
+ * may be decoded into again as soon as the integrate call has returned.  One call at a time per handle. */
+#define VGX_SCAN_COLOR_NONE 0      /* pcl::PointXYZ */
+#define VGX_SCAN_COLOR_RGB 1       /* pcl::PointXYZRGB: 4 bytes at color_offset */
+#define VGX_SCAN_COLOR_INTENSITY 2 /* pcl::PointXYZI: FLOAT32 at color_offset */
+/* the sensor_msgs/PointCloud2 header with the field names resolved to byte offsets inside a point */
+typedef struct vgx_scan_layout {
+  uint32_t width, height, point_step, row_step;
+  uint32_t offset_x, offset_y, offset_z; /* FLOAT32 each */
+  int32_t color_kind;                    /* VGX_SCAN_COLOR_* */
+  uint32_t color_offset;                 /* not read for VGX_SCAN_COLOR_NONE */
+  int32_t is_bigendian;
+} vgx_scan_layout;
+/* Fill it with vgx_scan_config_default() before setting fields; every field is validated. */
+typedef struct vgx_scan_config {
+  float intensity_min, intensity_max; /* 0, 10000: GrayscaleColorMap with setMaxValue(10000.0) (pointcloud_integrator.cpp:12-14) */
+  uint8_t constant_rgba[4];           /* 0, 0, 0, 0: the colour of a cloud without colours, a default voxblox::Color [recalled] */
+} vgx_scan_config;
+typedef struct vgx_scan_s* vgx_scan;
+VGX_API void vgx_scan_config_default(vgx_scan_config* cfg);
+/* HOST ONLY (no device, no context): VGX_OK, or the code a decode of n_bytes bytes in this layout is refused with.  It
+ * takes no config: the intensity range is checked by the decode calls alone. */
+VGX_API int vgx_scan_layout_check(const vgx_scan_layout* layout, int64_t n_bytes);
+VGX_API int vgx_scan_create(vgx_ctx ctx, vgx_scan* out);
+VGX_API int vgx_scan_destroy(vgx_scan scan);
+/* data: the message's bytes in host memory (pageable is fine: they are read before the call returns); cfg == NULL: the
+ * defaults.  Returns with the scan decoded and counted. */
+VGX_API int vgx_scan_decode_msg(vgx_scan scan, const vgx_scan_layout* layout, const vgx_scan_config* cfg, const void* data,
+                                int64_t n_bytes);
+/* the same with the message already in DEVICE memory, ready with respect to the TSDF stream (vgx_ctx_tsdf_wait_for_stream) */
+VGX_API int vgx_scan_decode_msg_device(vgx_scan scan, const vgx_scan_layout* layout, const vgx_scan_config* cfg,
+                                       const void* d_data, int64_t n_bytes);
+/* either may be NULL; no device work */
+VGX_API int vgx_scan_stats(vgx_scan scan, int64_t* n_points, int64_t* n_dropped);
+/* points [n][3] f32, rgba [n][4] u8; either may be NULL.  Waits for the TSDF stream. */
+VGX_API int vgx_scan_download(vgx_scan scan, float* points, uint8_t* rgba);
+/* DEVICE pointers to the same arrays (NULL for a scan of 0 points); valid until the next decode into the handle or its
+ * destruction.  Either may be NULL. */
+VGX_API int vgx_scan_device_pointers(vgx_scan scan, const void** d_points, const void** d_rgba);
+/* vgx_tsdf_integrate_device / vgx_tsdf_integrate_merged_device on the scan's points, colours and count */
+VGX_API int vgx_tsdf_integrate_scan(vgx_tsdf_integrator integrator, const float T_G_C[7], vgx_scan scan,
+                                    int32_t freespace_points, int64_t* n_updates);
+VGX_API int vgx_tsdf_integrate_merged_scan(vgx_tsdf_integrator integrator, const float T_G_C[7], vgx_scan scan,
+                                           int32_t freespace_points, int64_t* n_updates);
+
 /* finishSubmap() hand-off without a host round trip: turns the active layer's blocks
  * into a (not yet finished) submap holding the raw TSDF layer and its TSDF sampling
  * grid; follow with vgx_submap_generate_esdf and vgx_submap_extract_voxel_points.  The

@@ -79,6 +79,21 @@ class CloudConfig(C.Structure):
 CLOUD_DISTANCE, CLOUD_SURFACE_DISTANCE, CLOUD_SURFACE_COLOR = 0, 1, 2
 
 
+class ScanLayout(C.Structure):
+    """vgx_scan_layout: a sensor_msgs/PointCloud2 header with the field names resolved to byte offsets."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("point_step", C.c_uint32), ("row_step", C.c_uint32),
+                ("offset_x", C.c_uint32), ("offset_y", C.c_uint32), ("offset_z", C.c_uint32),
+                ("color_kind", C.c_int32), ("color_offset", C.c_uint32), ("is_bigendian", C.c_int32)]
+
+
+class ScanConfig(C.Structure):
+    """vgx_scan_config: the grey scale's range and the colour of a cloud without colours."""
+    _fields_ = [("intensity_min", C.c_float), ("intensity_max", C.c_float), ("constant_rgba", C.c_uint8 * 4)]
+
+
+SCAN_COLOR_NONE, SCAN_COLOR_RGB, SCAN_COLOR_INTENSITY = 0, 1, 2
+
+
 class EvaluationDetails(C.Structure):
     """vgx_voxel_evaluation_details: voxblox::utils::VoxelEvaluationDetails plus the f64 sum and the true min |e|."""
     _fields_ = [("rmse", C.c_float), ("max_error", C.c_float), ("min_error", C.c_float),
@@ -215,6 +230,17 @@ SIGNATURES = {
     "vgx_tsdf_integrate_device": (C.c_int, [vp, f32p, vp, vp, C.c_int64, C.c_int32, i64p]),
     "vgx_tsdf_integrate_merged": (C.c_int, [vp, f32p, f32p, u8p, C.c_int64, C.c_int32, i64p]),
     "vgx_tsdf_integrate_merged_device": (C.c_int, [vp, f32p, vp, vp, C.c_int64, C.c_int32, i64p]),
+    "vgx_scan_config_default": (None, [C.POINTER(ScanConfig)]),
+    "vgx_scan_layout_check": (C.c_int, [C.POINTER(ScanLayout), C.c_int64]),
+    "vgx_scan_create": (C.c_int, [vp, C.POINTER(vp)]),
+    "vgx_scan_destroy": (C.c_int, [vp]),
+    "vgx_scan_decode_msg": (C.c_int, [vp, C.POINTER(ScanLayout), C.POINTER(ScanConfig), vp, C.c_int64]),
+    "vgx_scan_decode_msg_device": (C.c_int, [vp, C.POINTER(ScanLayout), C.POINTER(ScanConfig), vp, C.c_int64]),
+    "vgx_scan_stats": (C.c_int, [vp, i64p, i64p]),
+    "vgx_scan_download": (C.c_int, [vp, f32p, u8p]),
+    "vgx_scan_device_pointers": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp)]),
+    "vgx_tsdf_integrate_scan": (C.c_int, [vp, f32p, vp, C.c_int32, i64p]),
+    "vgx_tsdf_integrate_merged_scan": (C.c_int, [vp, f32p, vp, C.c_int32, i64p]),
     "vgx_mesh_config_default": (None, [C.POINTER(MeshConfig)]),
     "vgx_mesh_create": (C.c_int, [vp, C.POINTER(vp)]),
     "vgx_mesh_destroy": (C.c_int, [vp]),
@@ -1231,6 +1257,85 @@ class Cloud:
             self.h = None
 
 
+def scan_layout(**kw):
+    """A vgx_scan_layout from keywords (fields not given are 0; row_step defaults to width * point_step)."""
+    lay = ScanLayout()
+    for k, v in kw.items():
+        if not hasattr(lay, k):
+            raise AttributeError(k)
+        setattr(lay, k, v)
+    if "row_step" not in kw:
+        lay.row_step = lay.width * lay.point_step
+    return lay
+
+
+def scan_config(intensity_min=None, intensity_max=None, constant_rgba=None):
+    """vgx_scan_config_default() with fields overridden."""
+    cfg = ScanConfig()
+    load().vgx_scan_config_default(C.byref(cfg))
+    if intensity_min is not None:
+        cfg.intensity_min = intensity_min
+    if intensity_max is not None:
+        cfg.intensity_max = intensity_max
+    if constant_rgba is not None:
+        cfg.constant_rgba[:] = [int(v) for v in constant_rgba]
+    return cfg
+
+
+def scan_layout_check(layout, n_bytes):
+    """vgx_scan_layout_check (host only): OK, or the code a decode of n_bytes bytes in this layout is refused with"""
+    return load().vgx_scan_layout_check(None if layout is None else C.byref(layout), int(n_bytes))
+
+
+class Scan:
+    """A raw PointCloud2 decoded on the GPU (vgx_scan): the finite points and their colours in message order; reused
+    from message to message.  FastTsdfIntegrator.integrate_scan / integrate_merged_scan consume it."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        h = vp()
+        ctx.check(ctx.lib.vgx_scan_create(ctx.h, C.byref(h)))
+        self.h = h
+
+    def decode_msg(self, layout, data, config=None):
+        """data: the message's bytes (bytes, bytearray or a contiguous array).  Returns (points, dropped)."""
+        buf = np.frombuffer(data, np.uint8)
+        self.ctx.check(self.ctx.lib.vgx_scan_decode_msg(self.h, C.byref(layout), None if config is None else C.byref(config),
+                                                        vp(buf.ctypes.data) if buf.size else None, buf.size))
+        return self.stats()
+
+    def decode_msg_device(self, layout, d_data, n_bytes, config=None):
+        """the same with the message at device address d_data (ready with respect to the TSDF stream)"""
+        self.ctx.check(self.ctx.lib.vgx_scan_decode_msg_device(self.h, C.byref(layout), None if config is None else C.byref(config),
+                                                               vp(d_data) if d_data else None, int(n_bytes)))
+        return self.stats()
+
+    def stats(self):
+        """(points, dropped)"""
+        n, d = C.c_int64(), C.c_int64()
+        self.ctx.check(self.ctx.lib.vgx_scan_stats(self.h, C.byref(n), C.byref(d)))
+        return n.value, d.value
+
+    def download(self):
+        """(points [n][3] f32, rgba [n][4] uint8)"""
+        n, _ = self.stats()
+        pts = np.zeros((n, 3), np.float32)
+        rgba = np.zeros((n, 4), np.uint8)
+        self.ctx.check(self.ctx.lib.vgx_scan_download(self.h, _ptr(pts, f32p), _ptr(rgba, u8p)))
+        return pts, rgba
+
+    def device_pointers(self):
+        """(points, rgba) device addresses as ints (None for a scan of 0 points)"""
+        p = [vp(), vp()]
+        self.ctx.check(self.ctx.lib.vgx_scan_device_pointers(self.h, C.byref(p[0]), C.byref(p[1])))
+        return tuple(x.value for x in p)
+
+    def destroy(self):
+        if self.h:
+            self.ctx.lib.vgx_scan_destroy(self.h)
+            self.h = None
+
+
 def evaluate_layers_rmse_cloud(gt, test, layer=EVAL_LAYER_ESDF, mode=EVAL_IGNORE_BEHIND_TEST, config=None, cloud=None):
     """evaluateLayersRmse and the point-cloud view of its error layer in one call (vgx_evaluate_layers_rmse_cloud): the
     error layer never leaves the device.  Returns (details dict, Cloud)."""
@@ -1471,6 +1576,22 @@ class FastTsdfIntegrator:
         self.ctx.check(self.ctx.lib.vgx_tsdf_integrate_device(
             self.h, _ptr(T, f32p), vp(d_points), vp(d_rgba) if d_rgba else None, n,
             int(freespace_points), C.byref(out) if count else None))
+        return out.value
+
+    def integrate_scan(self, T_G_C, scan, freespace_points=False, count=True):
+        """integratePointCloud of a decoded Scan (vgx_tsdf_integrate_scan); count=False: returns with the scan queued"""
+        T = _f32(T_G_C)
+        out = C.c_int64()
+        self.ctx.check(self.ctx.lib.vgx_tsdf_integrate_scan(self.h, _ptr(T, f32p), scan.h, int(freespace_points),
+                                                            C.byref(out) if count else None))
+        return out.value
+
+    def integrate_merged_scan(self, T_G_C, scan, freespace_points=False, count=True):
+        """MergedTsdfIntegrator::integratePointCloud of a decoded Scan (vgx_tsdf_integrate_merged_scan)"""
+        T = _f32(T_G_C)
+        out = C.c_int64()
+        self.ctx.check(self.ctx.lib.vgx_tsdf_integrate_merged_scan(self.h, _ptr(T, f32p), scan.h, int(freespace_points),
+                                                                   C.byref(out) if count else None))
         return out.value
 
     def set_cloud_width(self, width):

@@ -73,6 +73,7 @@ class GpuFastTsdfIntegrator {
   ~GpuFastTsdfIntegrator() { vgx_tsdf_integrator_destroy(integ_); }
   GpuFastTsdfIntegrator(const GpuFastTsdfIntegrator&) = delete;
   GpuFastTsdfIntegrator& operator=(const GpuFastTsdfIntegrator&) = delete;
+  vgx_tsdf_integrator handle() const { return integ_; }
 
   void setLayer(GpuTsdfLayer* layer) {
     if (vgx_tsdf_integrator_set_layer(integ_, layer->handle()) != VGX_OK)

@@ -1,0 +1,390 @@
+// A raw sensor_msgs/PointCloud2 decoded on the device: what PointcloudIntegrator::integratePointcloud does on the host
+// before it reaches the integrator (pointcloud_integrator.cpp:29-63) -- pcl::fromROSMsg + voxblox::convertPointcloud
+// [recalled]: drop the points that are not finite, one colour per kept point, message order kept.  The rules are stated
+// in include/voxgraph_amd.h (vgx_scan), the measurement in DESIGN.md 17.
+//
+// ONE kernel whatever the size: a workgroup takes a tile of 1024 consecutive points (a ticket: TileChain,
+// vgx_tsdf_internal.h), every thread reads four consecutive points and tests them, the kept ones are ranked inside the
+// workgroup (block_exclusive_sum) and across the tiles before it (chain_exclusive_sum: the prefix sum inside the launch),
+// and each thread writes its kept points and their colours at its rank.  No atomics decide a position: the order is the
+// message's.  The last tile leaves the total for the host.
+#include <cmath>
+#include <cstring>
+#include <string>
+
+#include "vgx_internal.h"
+#include "vgx_tsdf_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace vgx {
+
+constexpr int kScanIpt = 4;                    // consecutive points per thread
+constexpr int kScanTile = 256 * kScanIpt;      // points per workgroup
+constexpr size_t kScanStageBytes = 1u << 20;   // one pinned staging buffer (two of them, filled in turn)
+enum { kScanTicket = 0, kScanError = 1, kScanTotal = 2, kScanCtlWords = 4 };  // u64 words of vgx_scan_s::d_ctl
+
+struct ScanMsg {
+  const uint8_t* data;
+  uint32_t n, width, point_step, row_step;
+  uint32_t offset_x, offset_y, offset_z, color_offset;
+  int32_t color_kind;
+  float intensity_min, intensity_max;
+  uint32_t constant;  // constant_rgba as the word the colour array holds (r in the low byte)
+};
+
+// the little-endian 32-bit field at p
+template <bool DWORDS>
+__device__ __forceinline__ uint32_t scan_field(const uint8_t* p) {
+  if (DWORDS) return *reinterpret_cast<const uint32_t*>(p);
+  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+
+__device__ __forceinline__ bool scan_finite(uint32_t bits) { return (bits & 0x7f800000u) != 0x7f800000u; }
+
+// the colour word (bytes r g b a, r lowest) of a kept point from the 4 bytes at its colour field
+__device__ __forceinline__ uint32_t scan_colour(const ScanMsg& m, uint32_t field) {
+  if (m.color_kind == VGX_SCAN_COLOR_RGB)  // b0 b1 b2 b3 -> (b2, b1, b0, b3)
+    return ((field >> 16) & 0xffu) | (field & 0xff00u) | ((field & 0xffu) << 16) | (field & 0xff000000u);
+  float v = __uint_as_float(field);
+  v = (m.intensity_min < v) ? v : m.intensity_min;  // std::max(min, v): NaN -> min
+  v = (v < m.intensity_max) ? v : m.intensity_max;  // std::min(max, v)
+  const float h = (v - m.intensity_min) / (m.intensity_max - m.intensity_min);
+  const uint32_t g = (uint32_t)(uint8_t)round((double)h * 255.0);
+  return g | (g << 8) | (g << 16) | 0xff000000u;
+}
+
+template <bool DWORDS>
+__global__ __launch_bounds__(256) void scan_decode_kernel(ScanMsg m, TileChain chain, float* __restrict__ points,
+                                                          uint32_t* __restrict__ rgba, unsigned long long* __restrict__ total) {
+  __shared__ uint32_t sh_word, sh4[4];
+  const uint32_t tile = chain_tile(chain, &sh_word);
+  const uint32_t base = (tile * 256u + threadIdx.x) * (uint32_t)kScanIpt;  // (n < 2^31: no overflow)
+  uint32_t x[kScanIpt], y[kScanIpt], z[kScanIpt], c[kScanIpt], keep = 0;
+#pragma unroll
+  for (int e = 0; e < kScanIpt; ++e) {
+    const uint32_t i = base + (uint32_t)e;
+    x[e] = y[e] = z[e] = 0u;
+    c[e] = m.constant;
+    if (i < m.n) {
+      const uint32_t row = i / m.width, col = i - row * m.width;
+      const uint8_t* p = m.data + (size_t)row * m.row_step + (size_t)col * m.point_step;
+      x[e] = scan_field<DWORDS>(p + m.offset_x);
+      y[e] = scan_field<DWORDS>(p + m.offset_y);
+      z[e] = scan_field<DWORDS>(p + m.offset_z);
+      if (scan_finite(x[e]) && scan_finite(y[e]) && scan_finite(z[e])) {
+        keep |= 1u << e;
+        if (m.color_kind != VGX_SCAN_COLOR_NONE) c[e] = scan_colour(m, scan_field<DWORDS>(p + m.color_offset));
+      }
+    }
+  }
+  uint32_t in_tile = 0;
+  const uint32_t before = block_exclusive_sum((uint32_t)__popc(keep), sh4, in_tile);
+  const uint32_t prefix = chain_exclusive_sum(chain, tile, in_tile, &sh_word);
+  if (tile == gridDim.x - 1 && threadIdx.x == 0) *total = (unsigned long long)prefix + in_tile;
+  size_t at = (size_t)prefix + before;
+#pragma unroll
+  for (int e = 0; e < kScanIpt; ++e) {
+    if ((keep >> e) & 1u) {
+      points[3 * at + 0] = __uint_as_float(x[e]);
+      points[3 * at + 1] = __uint_as_float(y[e]);
+      points[3 * at + 2] = __uint_as_float(z[e]);
+      rgba[at] = c[e];
+      ++at;
+    }
+  }
+}
+
+}  // namespace vgx
+
+using namespace vgx;
+
+struct vgx_scan_s {
+  vgx_ctx ctx = nullptr;
+  std::mutex mu;
+  int64_t n_points = 0, n_dropped = 0;  // the scan held now
+  DeviceBuffer d_points;                // float [cap][3]: room for every point of the largest message so far
+  DeviceBuffer d_rgba;                  // u32 [cap] bytes r g b a
+  DeviceBuffer d_msg;                   // the host variant's upload
+  // TileChain of the decode kernel: {ticket, error, total} and one word per tile, tagged with the launch's epoch
+  DeviceBuffer d_ctl, d_state;
+  uint32_t epoch = 0, tickets = 0;
+  // host variant: two pinned buffers of kScanStageBytes filled in turn; an event per buffer says when its upload is done
+  char* h_stage[2] = {nullptr, nullptr};
+  hipEvent_t uploaded[2] = {nullptr, nullptr};
+  bool pageable = false;  // no pinned memory was to be had: uploads go straight from the caller's bytes
+};
+
+namespace {
+
+// Everything a decode is refused for that the layout, the configuration and the byte count alone decide; VGX_OK, or the
+// code with `why`.
+int scan_check(const vgx_scan_layout* l, const vgx_scan_config* c, int64_t n_bytes, std::string* why) {
+  auto fail = [why](int code, const char* msg) {
+    if (why) *why = msg;
+    return code;
+  };
+  if (!l) return fail(VGX_ERR_INVALID, "NULL layout");
+  if (n_bytes < 0) return fail(VGX_ERR_INVALID, "n_bytes is negative");
+  if (l->point_step == 0) return fail(VGX_ERR_INVALID, "point_step is 0");
+  if (l->color_kind != VGX_SCAN_COLOR_NONE && l->color_kind != VGX_SCAN_COLOR_RGB && l->color_kind != VGX_SCAN_COLOR_INTENSITY)
+    return fail(VGX_ERR_INVALID, "unknown color_kind");
+  const uint64_t step = l->point_step;
+  if ((uint64_t)l->offset_x + 4 > step || (uint64_t)l->offset_y + 4 > step || (uint64_t)l->offset_z + 4 > step)
+    return fail(VGX_ERR_INVALID, "a coordinate field does not fit in point_step");
+  if (l->color_kind != VGX_SCAN_COLOR_NONE && (uint64_t)l->color_offset + 4 > step)
+    return fail(VGX_ERR_INVALID, "the colour field does not fit in point_step");
+  if ((uint64_t)l->row_step < (uint64_t)l->width * step) return fail(VGX_ERR_INVALID, "row_step is less than width * point_step");
+  if (c && (!std::isfinite(c->intensity_min) || !std::isfinite(c->intensity_max) || !(c->intensity_max > c->intensity_min)))
+    return fail(VGX_ERR_INVALID, "the intensity range is not finite or not max > min");
+  if (l->is_bigendian != 0) return fail(VGX_ERR_UNSUPPORTED, "big-endian messages are not supported");
+  const uint64_t n = (uint64_t)l->width * l->height;
+  if (n >= (1ull << 31)) return fail(VGX_ERR_UNSUPPORTED, "width * height is 2^31 or more");
+  if (n > 0 && (uint64_t)n_bytes < (uint64_t)(l->height - 1) * l->row_step + (uint64_t)l->width * step)
+    return fail(VGX_ERR_INVALID, "n_bytes is less than (height - 1) * row_step + width * point_step");
+  return VGX_OK;
+}
+
+void scan_free_staging(vgx_scan S) {
+  for (int k = 0; k < 2; ++k) {
+    if (S->h_stage[k]) (void)hipHostFree(S->h_stage[k]);
+    if (S->uploaded[k]) (void)hipEventDestroy(S->uploaded[k]);
+    S->h_stage[k] = nullptr;
+    S->uploaded[k] = nullptr;
+  }
+}
+
+// the caller's bytes -> S->d_msg on stream st.  Through the pinned buffers piece by piece: the host copy of piece k
+// overlaps the upload of piece k - 1, and the caller's bytes have been read when the last piece is queued.
+int scan_upload(vgx_scan S, hipStream_t st, const void* data, size_t bytes) {
+  vgx_ctx ctx = S->ctx;
+  if (!S->pageable && !S->h_stage[0]) {
+    bool ok = true;
+    for (int k = 0; k < 2 && ok; ++k)
+      ok = hipHostMalloc((void**)&S->h_stage[k], kScanStageBytes, hipHostMallocDefault) == hipSuccess &&
+           hipEventCreateWithFlags(&S->uploaded[k], hipEventDisableTiming) == hipSuccess;
+    if (!ok) {  // no pinned memory to be had: remembered, the pageable path below from now on
+      (void)hipGetLastError();
+      scan_free_staging(S);
+      S->pageable = true;
+    }
+  }
+  if (S->pageable) {
+    VGX_HIP(ctx, hipMemcpyAsync(S->d_msg.p, data, bytes, hipMemcpyHostToDevice, st));
+    return VGX_OK;  // (the decode's closing synchronisation is behind it: the bytes are the caller's again on return)
+  }
+  int k = 0;
+  for (size_t at = 0; at < bytes; at += kScanStageBytes, k ^= 1) {
+    const size_t piece = std::min(kScanStageBytes, bytes - at);
+    // this buffer's last upload: of this call, or of an earlier one that failed before its closing synchronisation (an
+    // event never recorded is complete)
+    VGX_HIP(ctx, hipEventSynchronize(S->uploaded[k]));
+    std::memcpy(S->h_stage[k], static_cast<const char*>(data) + at, piece);
+    VGX_HIP(ctx, hipMemcpyAsync(S->d_msg.as<char>() + at, S->h_stage[k], piece, hipMemcpyHostToDevice, st));
+    VGX_HIP(ctx, hipEventRecord(S->uploaded[k], st));
+  }
+  return VGX_OK;
+}
+
+// The decode of a message at d_data (device) on the TSDF stream; the caller holds S->mu and ctx->tsdf_mu, the device is
+// set, the layout has passed scan_check.  Ends with the call's one host synchronisation.
+int scan_decode_queued(vgx_scan S, const vgx_scan_layout& l, const vgx_scan_config& c, const uint8_t* d_data) {
+  vgx_ctx ctx = S->ctx;
+  hipStream_t st = ctx->tsdf_stream;
+  const uint32_t n = l.width * l.height;
+  const uint32_t tiles = (n + kScanTile - 1) / kScanTile;
+  if ((size_t)n * 4 > S->d_rgba.bytes) {
+    VGX_HIP(ctx, hipStreamSynchronize(st));  // (a queued scan may still read the arrays)
+    const hipError_t e = alloc_group({{&S->d_points, (size_t)n * 12}, {&S->d_rgba, (size_t)n * 4}});
+    if (e != hipSuccess) return alloc_error(ctx, e, "scan: allocating points and colours");
+  }
+  if (!S->d_ctl.p) {
+    const hipError_t e = S->d_ctl.alloc(kScanCtlWords * 8);
+    if (e != hipSuccess) return alloc_error(ctx, e, "scan: allocating counters");
+    VGX_HIP(ctx, hipMemsetAsync(S->d_ctl.p, 0, kScanCtlWords * 8, st));
+    S->tickets = 0;
+  }
+  if ((size_t)tiles * 8 > S->d_state.bytes) {
+    VGX_HIP(ctx, hipStreamSynchronize(st));
+    const hipError_t e = S->d_state.alloc((size_t)tiles * 8);
+    if (e != hipSuccess) return alloc_error(ctx, e, "scan: allocating tile words");
+    VGX_HIP(ctx, hipMemsetAsync(S->d_state.p, 0, S->d_state.bytes, st));  // (epoch 0: no launch's tag)
+  }
+  if (S->epoch >= kChainEpochMax) {  // (after 2^30 decodes: start the tags over)
+    VGX_HIP(ctx, hipMemsetAsync(S->d_state.p, 0, S->d_state.bytes, st));
+    S->epoch = 0;
+  }
+  unsigned long long* ctl = S->d_ctl.as<unsigned long long>();
+  TileChain chain;
+  chain.state = S->d_state.as<unsigned long long>();
+  chain.epoch = ++S->epoch;
+  chain.ticket = ctl + kScanTicket;
+  chain.ticket_base = S->tickets;
+  chain.error = ctl + kScanError;
+  S->tickets += tiles;
+  ScanMsg m{};
+  m.data = d_data;
+  m.n = n;
+  m.width = l.width;
+  m.point_step = l.point_step;
+  m.row_step = l.row_step;
+  m.offset_x = l.offset_x;
+  m.offset_y = l.offset_y;
+  m.offset_z = l.offset_z;
+  m.color_offset = l.color_kind == VGX_SCAN_COLOR_NONE ? 0u : l.color_offset;
+  m.color_kind = l.color_kind;
+  m.intensity_min = c.intensity_min;
+  m.intensity_max = c.intensity_max;
+  std::memcpy(&m.constant, c.constant_rgba, 4);
+  const bool dwords = ((uintptr_t)d_data | l.point_step | l.row_step | l.offset_x | l.offset_y | l.offset_z | m.color_offset) % 4 == 0;
+  if (dwords)
+    hipLaunchKernelGGL(scan_decode_kernel<true>, dim3(tiles), dim3(256), 0, st, m, chain, S->d_points.as<float>(),
+                       S->d_rgba.as<uint32_t>(), ctl + kScanTotal);
+  else
+    hipLaunchKernelGGL(scan_decode_kernel<false>, dim3(tiles), dim3(256), 0, st, m, chain, S->d_points.as<float>(),
+                       S->d_rgba.as<uint32_t>(), ctl + kScanTotal);
+  VGX_HIP(ctx, hipGetLastError());
+  unsigned long long back[2] = {0, 0};  // {error, total}
+  VGX_HIP(ctx, hipMemcpyAsync(back, ctl + kScanError, 16, hipMemcpyDeviceToHost, st));
+  VGX_HIP(ctx, hipStreamSynchronize(st));
+  if (back[0] != 0) {
+    (void)hipMemsetAsync(ctl + kScanError, 0, 8, st);
+    return set_error(ctx, VGX_ERR_HIP, "scan: a tile of the decode never reported (internal error)");
+  }
+  S->n_points = (int64_t)back[1];
+  S->n_dropped = (int64_t)n - S->n_points;
+  return VGX_OK;
+}
+
+int scan_decode(const char* fn, vgx_scan S, const vgx_scan_layout* l, const vgx_scan_config* cfg, const void* data, int64_t n_bytes,
+                bool on_device) {
+  if (!S) return VGX_ERR_INVALID;
+  vgx_ctx ctx = S->ctx;
+  vgx_scan_config c;
+  vgx_scan_config_default(&c);
+  if (cfg) c = *cfg;
+  std::string why;
+  int rc = scan_check(l, &c, n_bytes, &why);
+  const size_t n = rc == VGX_OK ? (size_t)l->width * l->height : 0;
+  if (rc == VGX_OK && n > 0 && !data) {
+    rc = VGX_ERR_INVALID;
+    why = "NULL data";
+  }
+  if (rc != VGX_OK) return set_error(ctx, rc, std::string(fn) + ": " + why);
+  std::lock_guard<std::mutex> lk(S->mu);
+  std::lock_guard<std::mutex> tsdf_lk(ctx->tsdf_mu);
+  VGX_HIP(ctx, hipSetDevice(ctx->device));
+  S->n_points = S->n_dropped = 0;  // (what a failure below leaves: no scan)
+  if (n == 0) return VGX_OK;
+  const uint8_t* d_data = static_cast<const uint8_t*>(data);
+  if (!on_device) {
+    const size_t bytes = (size_t)(l->height - 1) * l->row_step + (size_t)l->width * l->point_step;
+    if (bytes > S->d_msg.bytes) {
+      VGX_HIP(ctx, hipStreamSynchronize(ctx->tsdf_stream));
+      const hipError_t e = S->d_msg.alloc(bytes);
+      if (e != hipSuccess) return alloc_error(ctx, e, "scan: allocating the message");
+    }
+    rc = scan_upload(S, ctx->tsdf_stream, data, bytes);
+    if (rc != VGX_OK) return rc;
+    d_data = S->d_msg.as<uint8_t>();
+  }
+  return scan_decode_queued(S, *l, c, d_data);
+}
+
+int scan_integrate(const char* fn, bool merged, vgx_tsdf_integrator I, const float T[7], vgx_scan S, int32_t freespace,
+                   int64_t* n_updates) {
+  vgx_ctx ctx = I ? I->ctx : (S ? S->ctx : nullptr);
+  if (!I || !T || !S) return set_error(ctx, VGX_ERR_INVALID, std::string(fn) + ": NULL argument");
+  if (S->ctx != I->ctx) return set_error(ctx, VGX_ERR_INVALID, std::string(fn) + ": the scan belongs to another context");
+  std::lock_guard<std::mutex> lk(S->mu);
+  const int64_t n = S->n_points;
+  const void* p = n > 0 ? S->d_points.p : nullptr;
+  const void* col = n > 0 ? S->d_rgba.p : nullptr;
+  return merged ? vgx_tsdf_integrate_merged_device(I, T, p, col, n, freespace, n_updates)
+                : vgx_tsdf_integrate_device(I, T, p, col, n, freespace, n_updates);
+}
+
+}  // namespace
+
+extern "C" {
+
+void vgx_scan_config_default(vgx_scan_config* cfg) {
+  if (!cfg) return;
+  cfg->intensity_min = 0.0f;
+  cfg->intensity_max = 10000.0f;  // color_map_->setMaxValue(10000.0) (pointcloud_integrator.cpp:14)
+  std::memset(cfg->constant_rgba, 0, 4);
+}
+
+int vgx_scan_layout_check(const vgx_scan_layout* layout, int64_t n_bytes) { return scan_check(layout, nullptr, n_bytes, nullptr); }
+
+int vgx_scan_create(vgx_ctx ctx, vgx_scan* out) {
+  if (!ctx || !out) return set_error(ctx, VGX_ERR_INVALID, "vgx_scan_create: NULL argument");
+  vgx_scan S = new vgx_scan_s;
+  S->ctx = ctx;
+  *out = S;
+  return VGX_OK;
+}
+
+int vgx_scan_destroy(vgx_scan S) {
+  if (!S) return VGX_ERR_INVALID;
+  vgx_ctx ctx = S->ctx;
+  {
+    std::lock_guard<std::mutex> tsdf_lk(ctx->tsdf_mu);
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->tsdf_stream);  // (a queued scan may still read the arrays)
+    scan_free_staging(S);
+  }
+  delete S;
+  return VGX_OK;
+}
+
+int vgx_scan_decode_msg(vgx_scan S, const vgx_scan_layout* layout, const vgx_scan_config* cfg, const void* data, int64_t n_bytes) {
+  return scan_decode("vgx_scan_decode_msg", S, layout, cfg, data, n_bytes, false);
+}
+
+int vgx_scan_decode_msg_device(vgx_scan S, const vgx_scan_layout* layout, const vgx_scan_config* cfg, const void* d_data,
+                               int64_t n_bytes) {
+  return scan_decode("vgx_scan_decode_msg_device", S, layout, cfg, d_data, n_bytes, true);
+}
+
+int vgx_scan_stats(vgx_scan S, int64_t* n_points, int64_t* n_dropped) {
+  if (!S) return VGX_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(S->mu);
+  if (n_points) *n_points = S->n_points;
+  if (n_dropped) *n_dropped = S->n_dropped;
+  return VGX_OK;
+}
+
+int vgx_scan_device_pointers(vgx_scan S, const void** d_points, const void** d_rgba) {
+  if (!S) return VGX_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(S->mu);
+  const bool any = S->n_points > 0;
+  if (d_points) *d_points = any ? S->d_points.p : nullptr;
+  if (d_rgba) *d_rgba = any ? S->d_rgba.p : nullptr;
+  return VGX_OK;
+}
+
+int vgx_scan_download(vgx_scan S, float* points, uint8_t* rgba) {
+  if (!S) return VGX_ERR_INVALID;
+  vgx_ctx ctx = S->ctx;
+  std::lock_guard<std::mutex> lk(S->mu);
+  if (S->n_points == 0) return VGX_OK;
+  std::lock_guard<std::mutex> tsdf_lk(ctx->tsdf_mu);
+  VGX_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->tsdf_stream;
+  const size_t n = (size_t)S->n_points;
+  if (points) VGX_HIP(ctx, hipMemcpyAsync(points, S->d_points.p, n * 12, hipMemcpyDeviceToHost, st));
+  if (rgba) VGX_HIP(ctx, hipMemcpyAsync(rgba, S->d_rgba.p, n * 4, hipMemcpyDeviceToHost, st));
+  VGX_HIP(ctx, hipStreamSynchronize(st));
+  return VGX_OK;
+}
+
+int vgx_tsdf_integrate_scan(vgx_tsdf_integrator I, const float T[7], vgx_scan S, int32_t freespace, int64_t* n_updates) {
+  return scan_integrate("vgx_tsdf_integrate_scan", false, I, T, S, freespace, n_updates);
+}
+
+int vgx_tsdf_integrate_merged_scan(vgx_tsdf_integrator I, const float T[7], vgx_scan S, int32_t freespace, int64_t* n_updates) {
+  return scan_integrate("vgx_tsdf_integrate_merged_scan", true, I, T, S, freespace, n_updates);
+}
+
+}  // extern "C"
