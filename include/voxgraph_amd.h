@@ -1167,6 +1167,98 @@ VGX_API int vgx_evaluate_layers_rmse_cloud(vgx_submap gt, vgx_submap test, int32
                                            vgx_voxel_evaluation_details* details, const vgx_cloud_config* cfg,
                                            vgx_cloud cloud);
 
+/* ---- Map messages: layers and the surface cloud as voxgraph publishes them ------ */
+/* What voxgraph sends at the end of every submap and every optimisation: SubmapServer::publishSubmapTsdf /
+ * publishSubmapTsdfAndEsdf (submap_server.cpp:83-105, cblox serializeSubmapToMsg), ProjectedMapServer::publishProjectedMap
+ * (projected_map_server.cpp:21-38: voxblox::serializeLayerAsMsg<TsdfVoxel>(layer, false, &msg.tsdf_layer), action kReset)
+ * and SubmapServer::publishSubmapSurfacePointcloud (submap_server.cpp:107-163: a PointCloud2 of pcl::PointXYZI) -- and
+ * the receiving end, voxblox::deserializeMsgToLayer.  A vgx_map_msg holds one result on the device: a layer message
+ * (block indices [n][3] i32 and words [n][vps^3 * W] u32) or a surface cloud (32 n bytes).  voxblox, cblox and PCL are
+ * not vendored: the word formats, the three actions, the merge and the PointXYZI layout are [recalled].
+ * Rules (what the kernels, vgx_msg.hip, and tests/map_msg_ref.py both follow; f32, no contraction):
+ *   words       Block<TsdfVoxel>::serializeToIntegers: W = 3 words per voxel -- distance bits, weight bits,
+ *               a | b << 8 | g << 16 | r << 24.  Block<EsdfVoxel>: W = 2 -- distance bits, observed ? 1 : 0 (parent bytes
+ *               zero: this library keeps no parents).  Exactly what vgx_map_file_write emits for the same arrays
+ *               (csrc/vgx_mapfile_schema.h).  Floats travel as bit patterns: NaN payloads and -0.0 survive.
+ *   sources     a vgx_tsdf_layer (active submap, projected map: colours included); a finished submap's raw TSDF layer
+ *               (colour word 0: device submaps carry no colour, the deviation of vgx_tsdf_layer_merge_submaps) or raw
+ *               ESDF layer (layer = VGX_EVAL_LAYER_TSDF / _ESDF).
+ *   order       blocks in slot order -- the order of vgx_tsdf_layer_download / vgx_submap_block_index -- voxels in
+ *               linear-index order (x fastest).  only_updated = true (Update::kMap flags) does not exist here: nothing
+ *               tracks updated blocks, and voxgraph passes false.
+ *   actions     vgx_tsdf_layer_deserialize[_msg], MapDerializationAction's values [recalled].  VGX_MSG_ACTION_UPDATE: each
+ *               message block replaces the layer's block of that index, allocated if absent (voxels and colours; colour
+ *               bytes r g b a from the word above); other blocks are untouched.  VGX_MSG_ACTION_MERGE: an absent block
+ *               is allocated and takes the message voxels; a present one gets mergeVoxelAIntoVoxelB(A = message voxel,
+ *               B = layer voxel) per voxel: w' = wA + wB; if w' > 0, d = (dA*wA + dB*wB) / w', w = w' and the colour
+ *               becomes Color::blendTwoColors as the integrators form it (per channel (uint8) roundf(cB * (wB / t) +
+ *               cA * (wA / t)), t = wB + wA); else the voxel is unchanged (a NaN w' leaves it unchanged).  No weight
+ *               cap.  VGX_MSG_ACTION_RESET: the layer is emptied, then UPDATE.
+ *   surface     vgx_submap_surface_msg: point i of the device point set (the order of vgx_submap_download_points) fills
+ *               bytes 32 i .. 32 i + 31: x y z FLOAT32 at 0 / 4 / 8, 1.0f at 12 (PCL's data[3]), intensity FLOAT32 at 16
+ *               = the point's weight bit for bit, bytes 20..31 zero -- pcl::PointXYZI as pcl::toROSMsg lays it out:
+ *               point_step 32, height 1, width n, row_step 32 n, little-endian, is_dense 1.  T == NULL copies the
+ *               positions bit for bit; else T is a row-major 3 x 4 f32 affine applied as pcl::transformPoint does: per
+ *               row ((m0*x + m1*y) + m2*z) + t.  Making T from a pose (T_B_S) is the caller's business
+ *               (voxgraph_amd/cpp/gpu_map_messages.h does it).  vgx_scan_decode_msg_device reads these bytes back with
+ *               the layout {point_step 32, offsets 0 / 4 / 8, VGX_SCAN_COLOR_INTENSITY at 16}.
+ * The handle is reused from call to call: its device buffers grow on demand; one call at a time per handle.
+ * Refused with VGX_ERR_INVALID before anything is written (vgx_last_error says which) -- by the producers, the handle
+ * keeping what it held: a NULL source or message, a message of another context, a layer value that is neither
+ * VGX_EVAL_LAYER_ESDF nor _TSDF, a submap layer no longer resident in raw form (vgx_submap_release_raw_layers, or an ESDF
+ * never generated), an unknown point type, a point set that was never extracted or uploaded, a T entry that is not finite;
+ * by the deserialising calls, the layer unchanged: a voxels_per_side other than the layer's, a voxel_size further than
+ * 1e-5 from the layer's (deserializeMsgToLayer's kVoxelSizeEpsilon [recalled]), a layer type that is not TSDF (an ESDF
+ * message handle included), a words length other than n_blocks * vps^3 * 3, an unknown action, n_blocks < 0, NULL arrays
+ * with n_blocks > 0, a handle that holds no layer message, and the same block index twice (DEVIATION: voxblox would apply
+ * duplicates in order).  n_blocks = 0: VGX_OK; with VGX_MSG_ACTION_RESET it empties the layer.  Deserialising an ESDF
+ * message into a submap does not exist: submaps are immutable, a caller decodes on the host and uses vgx_submap_create.
+ * VGX_ERR_UNSUPPORTED: voxels_per_side other than 8 or 16.  Out of device memory: VGX_ERR_NOMEM; a producer's handle then
+ * holds nothing, a deserialising call has reserved the table and the pool for every message block before it touches a
+ * voxel and leaves the layer unchanged.
+ * Streams and locks: vgx_tsdf_layer_serialize and both deserialising calls run on the TSDF stream under the TSDF lock,
+ * behind the scans and merges already queued; vgx_submap_serialize_layer and vgx_submap_surface_msg on the registration
+ * stream under the registration lock.  A layer serialisation is one kernel and one device-to-device copy of the block
+ * indices whatever the size, with at most two host synchronisations (the block total of a vgx_tsdf_layer, which only the
+ * device knows -- the kernel still reads the allocation counter there and never passes it; the end); the surface cloud is
+ * one kernel and one synchronisation.  A deserialisation is at most four memsets (RESET) and one kernel; values never
+ * depend on scheduling, the slots of newly allocated blocks may, as after a scan.  Every call returns with its result
+ * complete; the host-array form has read the caller's arrays by then. */
+#define VGX_MSG_NONE 0 /* a new handle, or one whose last producer failed */
+#define VGX_MSG_TSDF_LAYER 1
+#define VGX_MSG_ESDF_LAYER 2
+#define VGX_MSG_SURFACE_CLOUD 3
+#define VGX_MSG_ACTION_UPDATE 0 /* voxblox MapDerializationAction::kUpdate [recalled] */
+#define VGX_MSG_ACTION_MERGE 1
+#define VGX_MSG_ACTION_RESET 2
+typedef struct vgx_map_msg_s* vgx_map_msg;
+VGX_API int vgx_map_msg_create(vgx_ctx ctx, vgx_map_msg* out);
+VGX_API int vgx_map_msg_destroy(vgx_map_msg msg);
+/* any pointer may be NULL.  *n: blocks, or points; *words_per_voxel: 3, 2, or 0 for a cloud; *n_bytes: of the payload
+ * (words, or cloud data) */
+VGX_API int vgx_map_msg_stats(vgx_map_msg msg, int32_t* kind, int64_t* n, int32_t* words_per_voxel, int64_t* n_bytes);
+/* the voxel size and voxels per side of the layer a layer message was made from (VGX_ERR_INVALID otherwise) */
+VGX_API int vgx_map_msg_layer_geometry(vgx_map_msg msg, float* voxel_size, int32_t* voxels_per_side);
+/* block_index [n][3] i32 (layer messages only), payload n_bytes bytes; either may be NULL */
+VGX_API int vgx_map_msg_download(vgx_map_msg msg, int32_t* block_index, void* payload);
+/* DEVICE pointers to the same two arrays (NULL where the message has none); valid until the next producing call on the
+ * handle or its destruction.  Either may be NULL. */
+VGX_API int vgx_map_msg_device_pointers(vgx_map_msg msg, const int32_t** block_index, const void** payload);
+/* voxblox::serializeLayerAsMsg(layer, only_updated = false) of a vgx_tsdf_layer: the active submap, the projected map */
+VGX_API int vgx_tsdf_layer_serialize(vgx_tsdf_layer layer, vgx_map_msg msg);
+/* ... of a finished submap's raw layer: layer = VGX_EVAL_LAYER_TSDF / VGX_EVAL_LAYER_ESDF */
+VGX_API int vgx_submap_serialize_layer(vgx_submap submap, int32_t layer, vgx_map_msg msg);
+/* the data bytes of publishSubmapSurfacePointcloud's PointCloud2; point_type = VGX_POINTS_ISOSURFACE / _VOXELS */
+VGX_API int vgx_submap_surface_msg(vgx_submap submap, int32_t point_type, const float* T /* [12] row-major 3 x 4, or NULL */,
+                                   vgx_map_msg msg);
+/* voxblox::deserializeMsgToLayer from host arrays: layer_type = VGX_EVAL_LAYER_TSDF (anything else is refused),
+ * block_index [n_blocks][3], words [n_words], n_words = n_blocks * vps^3 * 3 */
+VGX_API int vgx_tsdf_layer_deserialize(vgx_tsdf_layer layer, int32_t action, int32_t layer_type, double voxel_size,
+                                       int32_t voxels_per_side, int32_t n_blocks, const int32_t* block_index,
+                                       const uint32_t* words, int64_t n_words);
+/* ... from a handle that holds a TSDF layer message: no host copy of the words */
+VGX_API int vgx_tsdf_layer_deserialize_msg(vgx_tsdf_layer layer, int32_t action, vgx_map_msg msg);
+
 /* ---------------------------------------------------------------------------
  * Saved maps: cblox submap-collection files and voxblox layer files.
  *

@@ -126,6 +126,9 @@ class TsdfConfig(C.Structure):
 
 
 TSDF_ORDER_MIXED, TSDF_ORDER_SORTED = 0, 1
+# what a vgx_map_msg holds; voxblox MapDerializationAction (include/voxgraph_amd.h, "Map messages")
+MSG_NONE, MSG_TSDF_LAYER, MSG_ESDF_LAYER, MSG_SURFACE_CLOUD = 0, 1, 2, 3
+MSG_ACTION_UPDATE, MSG_ACTION_MERGE, MSG_ACTION_RESET = 0, 1, 2
 
 # every symbol include/voxgraph_amd.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -269,6 +272,17 @@ SIGNATURES = {
     "vgx_tsdf_layer_cloud": (C.c_int, [vp, C.POINTER(CloudConfig), vp]),
     "vgx_evaluate_layers_rmse_cloud": (C.c_int, [vp, vp, C.c_int32, C.c_int32, C.POINTER(EvaluationDetails),
                                                  C.POINTER(CloudConfig), vp]),
+    "vgx_map_msg_create": (C.c_int, [vp, C.POINTER(vp)]),
+    "vgx_map_msg_destroy": (C.c_int, [vp]),
+    "vgx_map_msg_stats": (C.c_int, [vp, i32p, i64p, i32p, i64p]),
+    "vgx_map_msg_layer_geometry": (C.c_int, [vp, f32p, i32p]),
+    "vgx_map_msg_download": (C.c_int, [vp, i32p, vp]),
+    "vgx_map_msg_device_pointers": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp)]),
+    "vgx_tsdf_layer_serialize": (C.c_int, [vp, vp]),
+    "vgx_submap_serialize_layer": (C.c_int, [vp, C.c_int32, vp]),
+    "vgx_submap_surface_msg": (C.c_int, [vp, C.c_int32, f32p, vp]),
+    "vgx_tsdf_layer_deserialize": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32, i32p, u32p, C.c_int64]),
+    "vgx_tsdf_layer_deserialize_msg": (C.c_int, [vp, C.c_int32, vp]),
     "vgx_submap_query": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.c_int64, f32p, f32p, f32p, f32p, u8p]),
     "vgx_submap_query_device": (C.c_int, [vp, C.c_int32, C.c_int32, f32p, C.c_int64, vp, vp, vp, vp, vp]),
     "vgx_map_file_open": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(vp)]),
@@ -625,6 +639,22 @@ class Submap:
         self.ctx.check(self.ctx.lib.vgx_submap_layer_cloud(self.h, int(which), None if config is None else C.byref(config),
                                                            cloud.h))
         return cloud
+
+    def serialize_layer(self, layer="tsdf", msg=None):
+        """voxblox::serializeLayerAsMsg of the raw TSDF or ESDF layer (vgx_submap_serialize_layer).  Returns the MapMsg
+        (a new one when msg is None)."""
+        msg = msg if msg is not None else MapMsg(self.ctx)
+        which = {"esdf": EVAL_LAYER_ESDF, "tsdf": EVAL_LAYER_TSDF}.get(layer, layer)
+        self.ctx.check(self.ctx.lib.vgx_submap_serialize_layer(self.h, int(which), msg.h))
+        return msg
+
+    def surface_msg(self, point_type=POINTS_ISOSURFACE, T=None, msg=None):
+        """The data bytes of publishSubmapSurfacePointcloud's PointXYZI cloud (vgx_submap_surface_msg); T: a row-major
+        3 x 4 f32 affine or None.  Returns the MapMsg (a new one when msg is None)."""
+        msg = msg if msg is not None else MapMsg(self.ctx)
+        t = None if T is None else np.ascontiguousarray(T, np.float32).reshape(12)
+        self.ctx.check(self.ctx.lib.vgx_submap_surface_msg(self.h, int(point_type), _ptr(t, f32p), msg.h))
+        return msg
 
     def release_raw_layers(self):
         self.ctx.check(self.ctx.lib.vgx_submap_release_raw_layers(self.h))
@@ -1111,6 +1141,26 @@ class TsdfLayer:
         self.ctx.check(self.ctx.lib.vgx_tsdf_layer_cloud(self.h, None if config is None else C.byref(config), cloud.h))
         return cloud
 
+    def serialize(self, msg=None):
+        """voxblox::serializeLayerAsMsg of this layer, colours included (vgx_tsdf_layer_serialize).  Returns the MapMsg
+        (a new one when msg is None)."""
+        msg = msg if msg is not None else MapMsg(self.ctx)
+        self.ctx.check(self.ctx.lib.vgx_tsdf_layer_serialize(self.h, msg.h))
+        return msg
+
+    def deserialize(self, action, block_index, words, voxel_size=None, vps=None, layer_type=EVAL_LAYER_TSDF):
+        """voxblox::deserializeMsgToLayer from host arrays (vgx_tsdf_layer_deserialize): block_index [n][3], words
+        [n][vps^3 * 3] u32; voxel_size / vps: the message's (default: this layer's)."""
+        bi = np.ascontiguousarray(block_index, np.int32).reshape(-1, 3)
+        w = np.ascontiguousarray(words, np.uint32)
+        self.ctx.check(self.ctx.lib.vgx_tsdf_layer_deserialize(
+            self.h, int(action), int(layer_type), self.voxel_size if voxel_size is None else float(voxel_size),
+            self.vps if vps is None else int(vps), bi.shape[0], _ptr(bi, i32p), _ptr(w, u32p), w.size))
+
+    def deserialize_msg(self, action, msg):
+        """the same from a MapMsg that holds a TSDF layer message: the words never leave the device"""
+        self.ctx.check(self.ctx.lib.vgx_tsdf_layer_deserialize_msg(self.h, int(action), msg.h))
+
     def download(self):
         n, _ = self.stats()
         nv = self.vps ** 3
@@ -1255,6 +1305,58 @@ class Cloud:
         if self.h:
             self.ctx.lib.vgx_cloud_destroy(self.h)
             self.h = None
+
+
+class MapMsg:
+    """A map message on the GPU (vgx_map_msg): a serialised TSDF / ESDF layer (block indices and block words) or a
+    submap's surface cloud (PointXYZI bytes); reused from call to call."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        h = vp()
+        ctx.check(ctx.lib.vgx_map_msg_create(ctx.h, C.byref(h)))
+        self.h = h
+
+    def stats(self):
+        """(kind, blocks or points, words per voxel, payload bytes)"""
+        kind, n, wpv, nb = C.c_int32(), C.c_int64(), C.c_int32(), C.c_int64()
+        self.ctx.check(self.ctx.lib.vgx_map_msg_stats(self.h, C.byref(kind), C.byref(n), C.byref(wpv), C.byref(nb)))
+        return kind.value, n.value, wpv.value, nb.value
+
+    def layer_geometry(self):
+        """(voxel_size, voxels_per_side) of the layer a layer message was made from"""
+        vs, vps = C.c_float(), C.c_int32()
+        self.ctx.check(self.ctx.lib.vgx_map_msg_layer_geometry(self.h, C.byref(vs), C.byref(vps)))
+        return vs.value, vps.value
+
+    def download(self):
+        """a layer message: (block_index [n][3] i32, words [n][vps^3 * W] u32); a surface cloud: bytes [n][32] uint8"""
+        kind, n, wpv, _ = self.stats()
+        if kind == MSG_SURFACE_CLOUD:
+            data = np.zeros((n, 32), np.uint8)
+            self.ctx.check(self.ctx.lib.vgx_map_msg_download(self.h, None, vp(data.ctypes.data)))
+            return data
+        bi = np.zeros((n, 3), np.int32)
+        words = np.zeros((n, self.layer_geometry()[1] ** 3 * wpv if kind != MSG_NONE else 0), np.uint32)
+        self.ctx.check(self.ctx.lib.vgx_map_msg_download(self.h, _ptr(bi, i32p), vp(words.ctypes.data)))
+        return bi, words
+
+    def device_pointers(self):
+        """(block_index, payload) device addresses as ints (None where the message has none)"""
+        p = [vp(), vp()]
+        self.ctx.check(self.ctx.lib.vgx_map_msg_device_pointers(self.h, C.byref(p[0]), C.byref(p[1])))
+        return tuple(x.value for x in p)
+
+    def destroy(self):
+        if self.h:
+            self.ctx.lib.vgx_map_msg_destroy(self.h)
+            self.h = None
+
+
+def surface_msg_layout(n):
+    """the vgx_scan_layout of a surface cloud of n points: pcl::PointXYZI as pcl::toROSMsg lays it out"""
+    return scan_layout(width=int(n), height=1, point_step=32, offset_x=0, offset_y=4, offset_z=8,
+                       color_kind=SCAN_COLOR_INTENSITY, color_offset=16)
 
 
 def scan_layout(**kw):
