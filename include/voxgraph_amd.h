@@ -988,6 +988,74 @@ VGX_API int vgx_connected_mesh_download(vgx_connected_mesh cm, float* vertices, 
  * format, not byte parity with voxblox's outputMeshLayerAsPly.  vgx_mesh_write_ply (the soup) is unchanged. */
 VGX_API int vgx_connected_mesh_write_ply(vgx_connected_mesh cm, const char* path);
 
+/* Mesh markers: voxblox_ros fillMarkerWithMesh [recalled] over the triangle soup a vgx_mesh holds -- marker.points and
+ * marker.colors of the visualization_msgs/Marker (TRIANGLE_LIST) that SubmapVisuals::publishCombinedMesh
+ * (submap_visuals.cpp:78-87, ColorMode::kNormals), publishSeparatedMesh (:68-76) and publishMesh (:45-66, after cblox
+ * colorMeshLayer; both with the default kLambertColor, submap_visuals.h:25-29) publish, with mesh_opacity_ written into
+ * every alpha (:36-39).  The source is any vgx_mesh that holds a mesh (of a layer, of a submap, a separated mesh); it is
+ * not changed.  Everything about voxblox_ros here is [recalled]: it is not vendored.
+ * Rules (what the kernel, vgx_marker.hip, and tests/mesh_marker_ref.py both follow):
+ *   order          marker point j = 3 t + c is soup vertex j in the order of vgx_mesh_download (corner c of triangle t);
+ *                  blocks without triangles contribute nothing; n_points = 3 T.
+ *   points         [n][3] f64: each f32 coordinate widened (exact).
+ *   colors         [n][4] f32 r g b a.  a = opacity on every vertex, whatever the mode.
+ *   vertex colour  the colour of its triangle (vgx_mesh_download_colors), or constant_rgba when use_constant_color is
+ *                  set (cblox colorMeshLayer before the colouring).  c8(k) = (float)((double)k / 255.0) of a channel
+ *                  byte k: a 256-entry f32 table built on the host, so no device division decides a bit.
+ *   GRAY           r = g = b = 0.5f.
+ *   COLOR          (c8(r), c8(g), c8(b)).
+ *   NORMALS        per channel (float)((double)n * 0.5 + 0.5), n the triangle normal's component (the product is exact in
+ *                  f64, so contraction cannot change it).
+ *   LAMBERT_COLOR  all f32, no contraction.  L1 = (0.8f, -0.2f, 0.7f), L2 = (-0.5f, 0.2f, 0.2f), each divided component
+ *                  by component by sqrtf((x*x + y*y) + z*z) (on the host, once).  d_i = (n.x*Li.x + n.y*Li.y) + n.z*Li.z,
+ *                  then d_i = (d_i < 0.0f) ? 0.0f : d_i.  Per channel with c = c8(.): v = (d1*c + d2*c) + 0.2f, and the
+ *                  output is (1.0f < v) ? 1.0f : v.
+ *   LAMBERT        LAMBERT_COLOR with the colour (127, 127, 127).
+ *   HEIGHT         per vertex, from its own z: t = (float)(((double)z + 1.0) / 11.0), t = (t < 0) ? 0 : t, then
+ *                  t = (1.0f < t) ? 1.0f : t; the bytes of rainbowColorMap((double)t) (the map of the separated mesh's
+ *                  default colours), each channel through c8.  A z that is not a number takes the map's default case
+ *                  (255, 127, 127).
+ *   degenerate     a zero normal (a degenerate triangle keeps it) goes through the same formulas: NORMALS gives 0.5,
+ *   triangles      LAMBERT the ambient 0.2.
+ * The marker handle is reused from call to call: its device buffers grow on demand; one call at a time per handle.
+ * Refused with VGX_ERR_INVALID before anything is written, the handle keeping what it held (vgx_last_error says which):
+ * NULL handles, handles of different contexts, an unknown color_mode, an opacity that is not finite, a source handle that
+ * holds no mesh because its last generating call failed, COLOR or LAMBERT_COLOR on a mesh without colours and without
+ * use_constant_color (voxblox CHECKs hasColors() there).  VGX_ERR_UNSUPPORTED (the handle keeps what it held, too):
+ * 3 T >= 2^32, a ROS array length being a u32.  Out of device memory: VGX_ERR_NOMEM, and the handle then holds nothing
+ * (stats report 0 points).  A source with 0 triangles: VGX_OK and 0 points.  A NULL cfg means the defaults.
+ * Runs on the registration stream under the registration lock (a vgx_mesh is complete when its generating call returns,
+ * whichever stream made it); returns with the marker complete.  One kernel whatever the size (and, on a handle's first
+ * use, the 1 KiB copy of the c8 table), one host synchronisation; no atomics, no scan: T is known on the host.
+ * Out of scope: vertex colours taken from TSDF voxels (MeshIntegratorConfig::use_color, updateMeshColor: a mesh keeps one
+ * colour per triangle), voxblox_msgs/Mesh (generateVoxbloxMeshMsg), ROS message types and the serialisation of the header
+ * fields, the other markers voxgraph publishes (boxes, pose-graph edges, the cost-function visuals), markers from a
+ * connected mesh. */
+#define VGX_MARKER_COLOR 0 /* voxblox ColorMode, in its order [recalled] */
+#define VGX_MARKER_HEIGHT 1
+#define VGX_MARKER_NORMALS 2
+#define VGX_MARKER_GRAY 3
+#define VGX_MARKER_LAMBERT 4
+#define VGX_MARKER_LAMBERT_COLOR 5
+typedef struct vgx_mesh_marker_config {
+  int32_t color_mode;         /* VGX_MARKER_LAMBERT_COLOR (submap_visuals.h:28-29) */
+  float opacity;              /* 1.0f: SubmapVisuals::mesh_opacity_ */
+  int32_t use_constant_color; /* 0; 1 = cblox colorMeshLayer(constant_rgba) before colouring */
+  uint8_t constant_rgba[4];   /* 0 0 0 0 */
+} vgx_mesh_marker_config;
+VGX_API void vgx_mesh_marker_config_default(vgx_mesh_marker_config* cfg);
+typedef struct vgx_mesh_marker_s* vgx_mesh_marker;
+VGX_API int vgx_mesh_marker_create(vgx_ctx ctx, vgx_mesh_marker* out);
+VGX_API int vgx_mesh_marker_destroy(vgx_mesh_marker marker);
+/* cfg NULL: the defaults */
+VGX_API int vgx_mesh_fill_marker(vgx_mesh mesh, const vgx_mesh_marker_config* cfg, vgx_mesh_marker out);
+/* either pointer may be NULL; color_mode: that of the last accepted fill */
+VGX_API int vgx_mesh_marker_stats(vgx_mesh_marker marker, int64_t* n_points, int32_t* color_mode);
+/* points [n][3] f64, colors [n][4] f32; either may be NULL */
+VGX_API int vgx_mesh_marker_download(vgx_mesh_marker marker, double* points, float* colors);
+/* the device arrays of the marker held now (NULL when it holds 0 points); valid until the next fill or destroy */
+VGX_API int vgx_mesh_marker_device_pointers(vgx_mesh_marker marker, const double** points, const float** colors);
+
 /* ---- Map evaluation: voxblox::utils::evaluateLayersRmse ------------------- */
 /* MapEvaluation::evaluate (map_evaluation.cpp:59-114) scores a map against a ground truth: projected map
  * (vgx_tsdf_layer_merge_submaps), finishSubmap() of both (vgx_submap_from_tsdf_layer, vgx_submap_generate_esdf,

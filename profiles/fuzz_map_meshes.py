@@ -10,6 +10,9 @@ bit, on the scenes of profiles/fuzz_map_scene.py.  Per seed, at the drawn min_we
      block, four times the scene's extent, one log-uniform in [1e-20, 10]), against connected_mesh_ref.connect: vertices,
      normals, colours, indices, V and T.  A threshold the library is specified to refuse (|v * inv| >= 2^62) must be
      refused with VGX_ERR_UNSUPPORTED and raised by the restatement too.
+  4. the marker of each of the three (vgx_mesh_fill_marker) in a drawn colour mode at a drawn opacity, with a drawn
+     constant colour where the mesh has none and the mode needs one (and on one case in four besides), against
+     mesh_marker_ref.fill_marker: points, colours and the point count.
 A case whose restatement gives no triangle, or a weld that welds nothing or is refused, is counted as degenerate; more
 than one in five per product fails.  The slowest vgx_mesh_connect call is reported with its scene.
     SEEDS=200 FIRST=1000 python profiles/fuzz_map_meshes.py"""
@@ -45,6 +48,7 @@ def largest_weld(want):
 
 def main():
     from profiles import fuzz_map_scene as S
+    from tests import mesh_marker_ref as kr
     from tests import mesh_ref as mr
     from tests import separated_mesh_ref as sr
     from voxgraph_amd import capi
@@ -52,7 +56,8 @@ def main():
     ctx = capi.Context(0)
     n_seeds, first = int(os.environ.get("SEEDS", "100")), int(os.environ.get("FIRST", "0"))
     deg = S.Degenerate()
-    tot = dict(cases=0, blocks=0, triangles=0, welds=0, refused=0, soup=0, vertices=0)
+    tot = dict(cases=0, blocks=0, triangles=0, welds=0, refused=0, soup=0, vertices=0, markers=0, marker_points=0)
+    modes = {}
     slowest = (0.0, None)
     heaviest = (0, None)
 
@@ -62,8 +67,10 @@ def main():
 
     out = capi.ConnectedMesh(ctx)
     mesh = capi.Mesh(ctx)
+    marker = capi.MeshMarker(ctx)
     for seed in range(first, first + n_seeds):
         sc = S.draw(seed)
+        mrng = np.random.default_rng([seed, 0x6D6B])                     # the markers' own stream: the scene's is not touched
         vs, vps, mw = sc.voxel_size, sc.vps, sc.min_weight
         handles = [capi.Submap(ctx, i, vs, vps, s.block_index, s.tsdf_distance, s.tsdf_weight) for i, s in enumerate(sc.subs)]
         layer = capi.TsdfLayer(ctx, vs, vps)
@@ -91,6 +98,17 @@ def main():
             tot["blocks"] += len(want[0])
             tot["triangles"] += len(want[2])
             soup = (want[2], want[3], want[4] if len(want) > 4 else None)
+            mode, opacity = int(mrng.integers(0, 6)), float(F(mrng.uniform(0, 1)))
+            needs = soup[2] is None and mode in (kr.COLOR, kr.LAMBERT_COLOR)
+            const = tuple(int(c) for c in mrng.integers(0, 256, 4)) if needs or mrng.random() < 0.25 else None
+            capi.fill_marker(mesh, mode, opacity, const, marker)
+            what = f"{name} marker in mode {mode} at opacity {opacity!r}, constant colour {const}"
+            msg = S.compare(what, marker.download(), kr.fill_marker(soup[0], soup[1], soup[2], mode, opacity, const))
+            if msg or marker.stats() != (3 * len(want[2]), mode):
+                return fail(sc, what, msg or f"stats {marker.stats()}, want {(3 * len(want[2]), mode)}")
+            modes[mode] = modes.get(mode, 0) + 1
+            tot["markers"] += 1
+            tot["marker_points"] += 3 * len(want[2])
             for kind, thr in sc.thresholds[2 * m:2 * m + 2]:
                 wc = connect_reference(soup, thr)
                 t0 = time.perf_counter()
@@ -123,6 +141,7 @@ def main():
             h.destroy()
         tot["cases"] += 1
     out.destroy()
+    marker.destroy()
     mesh.destroy()
     ctx.close()
     over = deg.exceeded()
@@ -133,7 +152,8 @@ def main():
         print("TOO MANY DEGENERATE CASES (more than one in five):", over)
         return 1
     print("no mismatch:", tot["cases"], "scenes,", tot["blocks"], "mesh blocks,", tot["triangles"], "triangles,", tot["welds"],
-          "welds (", tot["refused"], "refused as specified ),", tot["soup"], "soup vertices welded into", tot["vertices"])
+          "welds (", tot["refused"], "refused as specified ),", tot["soup"], "soup vertices welded into", tot["vertices"], ";",
+          tot["markers"], "markers,", tot["marker_points"], "points, per mode", dict(sorted(modes.items())))
     return 0
 
 

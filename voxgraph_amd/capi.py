@@ -70,6 +70,16 @@ class MeshConfig(C.Structure):
     _fields_ = [("min_weight", C.c_float)]
 
 
+class MeshMarkerConfig(C.Structure):
+    """vgx_mesh_marker_config: voxblox ColorMode, SubmapVisuals::mesh_opacity_ and cblox colorMeshLayer's colour."""
+    _fields_ = [("color_mode", C.c_int32), ("opacity", C.c_float), ("use_constant_color", C.c_int32),
+                ("constant_rgba", C.c_uint8 * 4)]
+
+
+# voxblox ColorMode, in its order [recalled]
+MARKER_COLOR, MARKER_HEIGHT, MARKER_NORMALS, MARKER_GRAY, MARKER_LAMBERT, MARKER_LAMBERT_COLOR = 0, 1, 2, 3, 4, 5
+
+
 class CloudConfig(C.Structure):
     """vgx_cloud_config: which voxels of a layer become points (include/voxgraph_amd.h, "Layer point clouds")."""
     _fields_ = [("kind", C.c_int32), ("surface_distance", C.c_float), ("min_weight", C.c_float),
@@ -262,6 +272,13 @@ SIGNATURES = {
     "vgx_connected_mesh_stats": (C.c_int, [vp, i64p, i64p, i32p]),
     "vgx_connected_mesh_download": (C.c_int, [vp, f32p, f32p, u8p, u32p]),
     "vgx_connected_mesh_write_ply": (C.c_int, [vp, C.c_char_p]),
+    "vgx_mesh_marker_config_default": (None, [C.POINTER(MeshMarkerConfig)]),
+    "vgx_mesh_marker_create": (C.c_int, [vp, C.POINTER(vp)]),
+    "vgx_mesh_marker_destroy": (C.c_int, [vp]),
+    "vgx_mesh_fill_marker": (C.c_int, [vp, C.POINTER(MeshMarkerConfig), vp]),
+    "vgx_mesh_marker_stats": (C.c_int, [vp, i64p, i32p]),
+    "vgx_mesh_marker_download": (C.c_int, [vp, f64p, f32p]),
+    "vgx_mesh_marker_device_pointers": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp)]),
     "vgx_cloud_config_default": (None, [C.POINTER(CloudConfig)]),
     "vgx_cloud_create": (C.c_int, [vp, C.POINTER(vp)]),
     "vgx_cloud_destroy": (C.c_int, [vp]),
@@ -1617,6 +1634,67 @@ class ConnectedMesh:
         if self.h:
             self.ctx.lib.vgx_connected_mesh_destroy(self.h)
             self.h = None
+
+
+class MeshMarker:
+    """marker.points and marker.colors of a mesh's visualization_msgs/Marker on the GPU (vgx_mesh_marker): [3T][3] f64
+    and [3T][4] f32 in soup order; reused from call to call."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        h = vp()
+        ctx.check(ctx.lib.vgx_mesh_marker_create(ctx.h, C.byref(h)))
+        self.h = h
+
+    def stats(self):
+        """(points, color mode of the last accepted fill)"""
+        n, mode = C.c_int64(), C.c_int32()
+        self.ctx.check(self.ctx.lib.vgx_mesh_marker_stats(self.h, C.byref(n), C.byref(mode)))
+        return n.value, mode.value
+
+    def download(self):
+        """(points [n][3] f64, colors [n][4] f32)"""
+        n, _ = self.stats()
+        points = np.zeros((n, 3), np.float64)
+        colors = np.zeros((n, 4), np.float32)
+        self.ctx.check(self.ctx.lib.vgx_mesh_marker_download(self.h, _ptr(points, f64p), _ptr(colors, f32p)))
+        return points, colors
+
+    def device_pointers(self):
+        """(points, colors) device addresses as ints (None when the marker holds no points)"""
+        p = [vp(), vp()]
+        self.ctx.check(self.ctx.lib.vgx_mesh_marker_device_pointers(self.h, C.byref(p[0]), C.byref(p[1])))
+        return tuple(x.value for x in p)
+
+    def destroy(self):
+        if self.h:
+            self.ctx.lib.vgx_mesh_marker_destroy(self.h)
+            self.h = None
+
+
+def mesh_marker_config(**kw):
+    """vgx_mesh_marker_config_default with fields replaced: color_mode, opacity, use_constant_color, constant_rgba"""
+    cfg = MeshMarkerConfig()
+    load().vgx_mesh_marker_config_default(C.byref(cfg))
+    for k, v in kw.items():
+        if k == "constant_rgba":
+            cfg.constant_rgba = (C.c_uint8 * 4)(*[int(x) for x in v])
+        else:
+            setattr(cfg, k, v)
+    return cfg
+
+
+def fill_marker(mesh, color_mode=MARKER_LAMBERT_COLOR, opacity=1.0, constant_rgba=None, out=None):
+    """voxblox_ros fillMarkerWithMesh over `mesh` (a Mesh) in `color_mode` (vgx_mesh_fill_marker), `opacity` in every
+    alpha; constant_rgba: cblox colorMeshLayer(constant_rgba) first.  Returns the MeshMarker (a new one when out is
+    None)."""
+    cfg = mesh_marker_config(color_mode=int(color_mode), opacity=float(opacity))
+    if constant_rgba is not None:
+        cfg = mesh_marker_config(color_mode=int(color_mode), opacity=float(opacity), use_constant_color=1,
+                                 constant_rgba=constant_rgba)
+    out = out if out is not None else MeshMarker(mesh.ctx)
+    mesh.ctx.check(mesh.ctx.lib.vgx_mesh_fill_marker(mesh.h, C.byref(cfg), out.h))
+    return out
 
 
 def mc_triangle_table():
