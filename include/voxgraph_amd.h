@@ -785,6 +785,24 @@ VGX_API int vgx_tsdf_integrate_merged_scan(vgx_tsdf_integrator integrator, const
 VGX_API int vgx_submap_from_tsdf_layer(vgx_ctx ctx, vgx_tsdf_layer layer, int32_t submap_id,
                                        vgx_submap* out);
 
+/* Submaps that carry the TSDF voxels' colours (opt-in: a submap made by vgx_submap_create, vgx_submap_from_tsdf_layer or
+ * vgx_map_file_load_submap has none, and every call on such a submap behaves as it always did).  Storage is one packed
+ * uint32 per voxel (bytes r g b a, r lowest), as the layer keeps it: 4 B per voxel, spent only on submaps that asked.
+ *   vgx_submap_from_tsdf_layer_colored  vgx_submap_from_tsdf_layer plus a device-to-device copy of the layer's rgba, in
+ *                  the submap's block order, on the same stream and under the same locks; no host round trip.
+ *   vgx_submap_set_colors  for host-built submaps (vgx_submap_create, or vgx_map_file_read_submap's tsdf_rgba): rgba
+ *                  [n_blocks][vps^3][4] u8 in the order of vgx_submap_block_index; replaces colours already held
+ *                  (staged through a fresh buffer: after any failure the old ones are whole).
+ *                  VGX_ERR_INVALID, the submap unchanged: NULL rgba, a released raw TSDF layer.
+ *   vgx_submap_has_colors  *has = 1 / 0.
+ *   vgx_submap_download_colors  rgba [n_blocks][vps^3][4]; VGX_ERR_INVALID on a submap without colours.
+ * vgx_submap_release_raw_layers frees the colours too (has_colors then reports 0).  What reads them: the projected map
+ * and transformLayer (below), vgx_submap_generate_mesh_colored, vgx_submap_serialize_layer. */
+VGX_API int vgx_submap_from_tsdf_layer_colored(vgx_ctx ctx, vgx_tsdf_layer layer, int32_t submap_id, vgx_submap* out);
+VGX_API int vgx_submap_set_colors(vgx_submap submap, const uint8_t* rgba);
+VGX_API int vgx_submap_has_colors(vgx_submap submap, int32_t* has);
+VGX_API int vgx_submap_download_colors(vgx_submap submap, uint8_t* rgba);
+
 /* The projected map: voxblox::mergeLayerAintoLayerB(submap TSDF layer, T_L_S, layer) applied to n submaps in ARRAY
  * order.  cblox::SubmapCollection::getProjectedMap() is this call on an empty layer (vgx_tsdf_layer_upload(layer, 0,
  * ...)) with the collection's submaps in ascending ID order and T_L_S = submap.getPose(); merging into a layer that
@@ -809,7 +827,22 @@ VGX_API int vgx_submap_from_tsdf_layer(vgx_ctx ctx, vgx_tsdf_layer layer, int32_
  *   merge          mergeVoxelAIntoVoxelB [recalled] (A: the submap's voxel, B: the layer's): w' = wA + wB; if w' > 0,
  *                  d = (dA*wA + dB*wB) / w' and w = w' (f32, that association, no contraction); else unchanged.  No
  *                  weight cap.
- *   colour         rgba is left untouched (device submaps carry no colour): a stated deviation, voxblox blends it.
+ *   colour         a submap without colours leaves rgba untouched, exactly as before (voxblox blends it: a submap has to
+ *                  carry colours for that, vgx_submap_from_tsdf_layer_colored / vgx_submap_set_colors).  A submap with
+ *                  colours also merges colour, all [recalled]:
+ *                    colour of A, interpolated voxel: Interpolator<TsdfVoxel>::interpVoxel per channel -- the 8
+ *                      neighbours' channel bytes widened to f32, in the neighbour order of the interpolation (k = 0..7:
+ *                      x offset = bit 2, y = bit 1, z = bit 0), through the same trilinear form with the same dl as
+ *                      distance and weight.  voxblox assigns that float to a uint8_t member; here the value is clamped
+ *                      to [0, 255] first, then truncated toward zero: a stated definition for the few-ulp overshoots
+ *                      that the C++ cast leaves undefined.
+ *                    colour of A, voxel that did not interpolate: the default voxel's (0, 0, 0, 0), w = 0.
+ *                    merge: where the rule above updates the voxel (w' = wA + wB > 0) the colour becomes
+ *                      Color::blendTwoColors(cB, wB, cA, wA) with the PRE-merge weights (per channel
+ *                      round(b * (wB / w') + a * (wA / w')), f32, as the integrators and the MERGE action blend);
+ *                      otherwise it is unchanged.
+ *                  Array order is the merge order for colour as for distance; submaps with and without colours may be
+ *                  mixed in one call.  Newly allocated blocks start at rgba 0.
  * Runs on the context's TSDF stream behind the registration stream (where submap layers are produced); takes the TSDF
  * lock, then the registration lock; returns once the sources have been read, so the caller may destroy a submap or
  * release its raw layers right after.  Room for every candidate block is reserved first: VGX_ERR_NOMEM then, before
@@ -818,16 +851,18 @@ VGX_API int vgx_submap_from_tsdf_layer(vgx_ctx ctx, vgx_tsdf_layer layer, int32_
 VGX_API int vgx_tsdf_layer_merge_submaps(vgx_tsdf_layer layer, int32_t n, const vgx_submap* submaps, const float* T_L_S, int64_t* n_blocks_out);
 
 /* voxblox::transformLayer(submap TSDF layer, T_L_S, layer) [recalled] into an EMPTY layer: the resampling behind
- * VoxgraphSubmap::transformSubmap (voxgraph_submap.cpp:38-59), which MapEvaluation::evaluate applies to the ground truth
- * once it is aligned (map_evaluation.cpp:86).  transformSubmap on the device is this call, then vgx_submap_from_tsdf_layer
- * and vgx_submap_generate_esdf.  T_L_S {qw,qx,qy,qz, tx,ty,tz} f32.  *n_blocks_out (nullable): blocks in the layer.
- * The rules are those of vgx_tsdf_layer_merge_submaps with n = 1 -- the f32 inverse pose, the voxel centres, the
- * interpolation and the coverage rule (a block is kept iff one of its voxel centres interpolates) -- except that the
- * voxel is COPIED, not merged: an interpolated voxel gets {d, w} as interpolated, every other voxel of a kept block stays
- * (0, 0).  That is not a merge into an empty layer: (d*w + 0*0) / w need not round back to d.  rgba is left untouched
- * (the deviation of vgx_tsdf_layer_merge_submaps).  [recalled] some voxblox versions fall back to the nearest voxel where
- * trilinear interpolation fails; the pinned version could not be checked: here a voxel that does not interpolate is not
- * written ("Known gaps").
+ * VoxgraphSubmap::transformSubmap (voxgraph_submap.cpp:38-59), which MapEvaluation::evaluate applies to the ground
+ * truth once it is aligned (map_evaluation.cpp:86).  transformSubmap on the device is this call, then
+ * vgx_submap_from_tsdf_layer and vgx_submap_generate_esdf.  T_L_S {qw,qx,qy,qz, tx,ty,tz} f32.  *n_blocks_out
+ * (nullable): blocks in the layer.  The rules are those of vgx_tsdf_layer_merge_submaps with n = 1 -- the f32 inverse
+ * pose, the voxel centres, the interpolation and the coverage rule (a block is kept iff one of its voxel centres
+ * interpolates) -- except that the voxel is COPIED, not merged: an interpolated voxel gets {d, w} as interpolated,
+ * every other voxel of a kept block stays (0, 0).  That is not a merge into an empty layer: (d*w + 0*0) / w need not
+ * round back to d.  A submap without colours leaves rgba untouched; a submap with colours stores an interpolated
+ * voxel's interpolated colour (the colour rule of vgx_tsdf_layer_merge_submaps) and (0, 0, 0, 0) on every other voxel
+ * of a kept block.  [recalled] some voxblox versions fall back to the nearest voxel where trilinear interpolation
+ * fails; the pinned version could not be checked: here a voxel that does not interpolate is not written (DESIGN.md 9,
+ * "Known gaps").
  * Preconditions, each refused with VGX_ERR_INVALID before anything is written: NULL handles or pose, a layer that is not
  * empty, a voxel_size or voxels_per_side that differs from the layer's, a released raw TSDF layer, a pose that is not
  * finite or whose |q.q - 1| > 1e-4.  Streams, locks and lifetimes: those of vgx_tsdf_layer_merge_submaps. */
@@ -866,9 +901,9 @@ VGX_API int vgx_tsdf_layer_transform_submap(vgx_tsdf_layer layer, vgx_submap sub
  *                  ascending (x, y, z) block-index order whatever the layer's slot order.  Block k owns the triangles
  *                  [first[k], first[k+1]); vertices [T][3][3] f32 in the emitted order (voxblox's indices are implicitly
  *                  0..3n-1 per block); normals [T][3] f32, one per triangle (voxblox stores it three times).
- *   deviations     no colour (voxgraph colours the combined mesh by normal or per submap; the projected map carries none):
- *                  the config has no use_color.  only_mesh_updated_blocks / clear_updated_flag are not supported (every
- *                  caller passes false, false).
+ *   colour         these two calls make no colour (MeshIntegratorConfig::use_color = false); the _colored forms below
+ *                  are use_color = true.
+ *   deviations     only_mesh_updated_blocks / clear_updated_flag are not supported (every caller passes false, false).
  * A mesh handle is reused from call to call (the mapper re-meshes after every submap): its device buffers grow on demand;
  * one call at a time per handle.  Refused with VGX_ERR_INVALID before anything is written: NULL handles, a min_weight that
  * is negative or not finite, a source and mesh of different contexts, a submap whose raw TSDF layer was released.  An
@@ -887,13 +922,27 @@ VGX_API int vgx_mesh_destroy(vgx_mesh mesh);
 /* cfg == NULL: the defaults */
 VGX_API int vgx_tsdf_layer_generate_mesh(vgx_tsdf_layer layer, const vgx_mesh_config* cfg, vgx_mesh mesh);
 VGX_API int vgx_submap_generate_mesh(vgx_submap submap, const vgx_mesh_config* cfg, vgx_mesh mesh);
+/* MeshIntegratorConfig::use_color = true: the generator above, unchanged, then MeshIntegrator::updateMeshColor
+ * [recalled] as one streaming kernel over the soup -- same stream, same locks, no further host synchronisation.  Vertices,
+ * normals, first and block_index are those of the plain call; the mesh additionally holds one colour per soup vertex
+ * ([T][3][4] u8, vgx_mesh_download_vertex_colors).  The submap form needs a submap with colours (VGX_ERR_INVALID
+ * otherwise, the handle keeping what it held); the layer form reads the layer's rgba.
+ * Rule for vertex p of a triangle of block b (origin = block_index * block_size, f32): the voxel index in b is
+ * floorf((p[a] - origin[a]) * voxel_size_inv + 1e-6f) per axis; if all three lie in [0, vps) that voxel is taken.
+ * Otherwise (a vertex on one of b's max planes) the block is floorf(p[a] * block_size_inv + 1e-6f) and the index the
+ * formula above against that block's origin, clamped to [0, vps - 1] (the nearest-voxel rule of vgx_submap_query).  The
+ * vertex gets the voxel's colour byte for byte if its weight >= min_weight (utils::getColorIfValid); else it keeps the
+ * default (0, 0, 0, 0), as does a vertex whose block is absent (voxblox would dereference null there).  A vertex lies on
+ * an edge between two corners that passed weight > min_weight, so the default is reached only through rounding. */
+VGX_API int vgx_tsdf_layer_generate_mesh_colored(vgx_tsdf_layer layer, const vgx_mesh_config* cfg, vgx_mesh mesh);
+VGX_API int vgx_submap_generate_mesh_colored(vgx_submap submap, const vgx_mesh_config* cfg, vgx_mesh mesh);
 VGX_API int vgx_mesh_stats(vgx_mesh mesh, int32_t* n_blocks, int64_t* n_triangles);
 /* block_index [nb][3], first [nb+1], vertices [T][3][3], normals [T][3]; any may be NULL */
 VGX_API int vgx_mesh_download(vgx_mesh mesh, int32_t* block_index, int64_t* first, float* vertices, float* normals);
-/* Host code: binary_little_endian PLY of the triangle soup -- vertex x y z nx ny nz (float; the triangle's normal on each
- * of its three vertices; then red green blue alpha (uchar) when the mesh has colours), face
- * `list uchar int vertex_indices` = (3t, 3t+1, 3t+2).  A stated format, not byte parity
- * with voxblox's outputMeshLayerAsPly. */
+/* Host code: binary_little_endian PLY of the triangle soup -- vertex x y z nx ny nz (float; the triangle's normal on
+ * each of its three vertices; then red green blue alpha (uchar) when the mesh has colours: the vertex's own on a
+ * per-vertex mesh, else its triangle's), face `list uchar int vertex_indices` = (3t, 3t+1, 3t+2).  A stated format, not
+ * byte parity with voxblox's outputMeshLayerAsPly. */
 VGX_API int vgx_mesh_write_ply(vgx_mesh mesh, const char* path);
 /* The triangle table the kernels use (voxgraph_amd/csrc/vgx_mc_tables.h): row c = the triangles of configuration c as
  * edge triples, -1 terminated.  Host only (no device needed). */
@@ -933,10 +982,17 @@ VGX_API int vgx_mesh_triangle_table(int8_t out[256][16]);
  * triangle's colour on each of its vertices); a mesh without colours gives the file it always gave. */
 VGX_API int vgx_submaps_generate_separated_mesh(vgx_ctx ctx, int32_t n, const vgx_submap* submaps, const float* T_M_S,
                                                 const uint8_t* rgba, const vgx_mesh_config* cfg, vgx_mesh mesh);
-/* *has = 1 when the mesh carries colours (a separated mesh), else 0 */
+/* *has = 1 when the mesh carries colours (a separated mesh, a _colored mesh), else 0 */
 VGX_API int vgx_mesh_has_colors(vgx_mesh mesh, int32_t* has);
-/* rgba [T][4]: one colour per triangle */
+/* *layout = which colours: none, one per triangle (a separated mesh), one per soup vertex (a _colored mesh) */
+#define VGX_MESH_COLORS_NONE 0
+#define VGX_MESH_COLORS_PER_TRIANGLE 1
+#define VGX_MESH_COLORS_PER_VERTEX 2
+VGX_API int vgx_mesh_color_layout(vgx_mesh mesh, int32_t* layout);
+/* rgba [T][4]: one colour per triangle.  VGX_ERR_INVALID on a per-vertex mesh (the size differs) */
 VGX_API int vgx_mesh_download_colors(vgx_mesh mesh, uint8_t* rgba);
+/* rgba [T][3][4]: one colour per soup vertex.  VGX_ERR_INVALID unless the layout is per vertex */
+VGX_API int vgx_mesh_download_vertex_colors(vgx_mesh mesh, uint8_t* rgba);
 
 /* The connected mesh: voxblox MeshLayer::getConnectedMesh / createConnectedMesh [recalled] over the triangle soup a
  * vgx_mesh holds -- what voxblox::outputMeshLayerAsPly writes (SubmapVisuals::saveCombinedMesh / saveSeparatedMesh,
@@ -954,10 +1010,10 @@ VGX_API int vgx_mesh_download_colors(vgx_mesh mesh, uint8_t* rgba);
  *                  Per coordinate k = (int64) round((double)v * inv): one f64 multiply, std::round (halves away from
  *                  zero), so -0.0 and +0.0 share key 0.  The key is the three int64 together, compared exactly (192
  *                  bits): a hash of them finds the slot, it never decides equality.
- *   vertices       a key's vertex is its FIRST soup vertex (smallest j): its three floats copied bit for bit, the normal
- *                  of that soup vertex's triangle j / 3 (voxblox stores the triangle normal on each corner) and, when the
- *                  source has colours, the colour of triangle j / 3.  Unique vertices are numbered in order of first
- *                  occurrence (ascending j).
+ *   vertices       a key's vertex is its FIRST soup vertex (smallest j): its three floats copied bit for bit, the
+ *                  normal of that soup vertex's triangle j / 3 (voxblox stores the triangle normal on each corner) and,
+ *                  when the source has colours, the colour of triangle j / 3 -- or, on a per-vertex mesh, soup vertex
+ *                  j's own colour.  Unique vertices are numbered in order of first occurrence (ascending j).
  *   indices        indices[j] = the number of the unique vertex of key(j): [T][3] u32, triangle order unchanged.
  *                  Triangles whose corners weld together are kept (voxblox keeps them).  Blocks without triangles
  *                  contribute nothing.
@@ -999,9 +1055,11 @@ VGX_API int vgx_connected_mesh_write_ply(vgx_connected_mesh cm, const char* path
  *                  blocks without triangles contribute nothing; n_points = 3 T.
  *   points         [n][3] f64: each f32 coordinate widened (exact).
  *   colors         [n][4] f32 r g b a.  a = opacity on every vertex, whatever the mode.
- *   vertex colour  the colour of its triangle (vgx_mesh_download_colors), or constant_rgba when use_constant_color is
- *                  set (cblox colorMeshLayer before the colouring).  c8(k) = (float)((double)k / 255.0) of a channel
- *                  byte k: a 256-entry f32 table built on the host, so no device division decides a bit.
+ *   vertex colour  the colour of its triangle (vgx_mesh_download_colors) or, on a per-vertex mesh, its own
+ *                  (vgx_mesh_download_vertex_colors: COLOR and LAMBERT_COLOR shade every vertex apart), or
+ *                  constant_rgba when use_constant_color is set (cblox colorMeshLayer before the colouring).  c8(k) =
+ *                  (float)((double)k / 255.0) of a channel byte k: a 256-entry f32 table built on the host, so no
+ *                  device division decides a bit.
  *   GRAY           r = g = b = 0.5f.
  *   COLOR          (c8(r), c8(g), c8(b)).
  *   NORMALS        per channel (float)((double)n * 0.5 + 0.5), n the triangle normal's component (the product is exact in
@@ -1026,11 +1084,9 @@ VGX_API int vgx_connected_mesh_write_ply(vgx_connected_mesh cm, const char* path
  * (stats report 0 points).  A source with 0 triangles: VGX_OK and 0 points.  A NULL cfg means the defaults.
  * Runs on the registration stream under the registration lock (a vgx_mesh is complete when its generating call returns,
  * whichever stream made it); returns with the marker complete.  One kernel whatever the size (and, on a handle's first
- * use, the 1 KiB copy of the c8 table), one host synchronisation; no atomics, no scan: T is known on the host.
- * Out of scope: vertex colours taken from TSDF voxels (MeshIntegratorConfig::use_color, updateMeshColor: a mesh keeps one
- * colour per triangle), voxblox_msgs/Mesh (generateVoxbloxMeshMsg), ROS message types and the serialisation of the header
- * fields, the other markers voxgraph publishes (boxes, pose-graph edges, the cost-function visuals), markers from a
- * connected mesh. */
+ * use, the 1 KiB copy of the c8 table), one host synchronisation; no atomics, no scan: T is known on the host.  Out of
+ * scope: voxblox_msgs/Mesh (generateVoxbloxMeshMsg), ROS message types and the serialisation of the header fields, the
+ * other markers voxgraph publishes (boxes, pose-graph edges, the cost-function visuals), markers from a connected mesh. */
 #define VGX_MARKER_COLOR 0 /* voxblox ColorMode, in its order [recalled] */
 #define VGX_MARKER_HEIGHT 1
 #define VGX_MARKER_NORMALS 2
@@ -1249,7 +1305,7 @@ VGX_API int vgx_evaluate_layers_rmse_cloud(vgx_submap gt, vgx_submap test, int32
  *               zero: this library keeps no parents).  Exactly what vgx_map_file_write emits for the same arrays
  *               (csrc/vgx_mapfile_schema.h).  Floats travel as bit patterns: NaN payloads and -0.0 survive.
  *   sources     a vgx_tsdf_layer (active submap, projected map: colours included); a finished submap's raw TSDF layer
- *               (colour word 0: device submaps carry no colour, the deviation of vgx_tsdf_layer_merge_submaps) or raw
+ *               (its colour words when the submap has colours; a submap without colours writes colour word 0) or raw
  *               ESDF layer (layer = VGX_EVAL_LAYER_TSDF / _ESDF).
  *   order       blocks in slot order -- the order of vgx_tsdf_layer_download / vgx_submap_block_index -- voxels in
  *               linear-index order (x fastest).  only_updated = true (Update::kMap flags) does not exist here: nothing

@@ -10,10 +10,15 @@ block boxes far from the origin, one-block submaps and slabs).  Per seed:
      combinations, the points those of tests/test_map_query_gpu.py plus voxel centres and faces seen through the pose;
   5. vgx_evaluate_layers_rmse of it and a partly overlapping partner against map_eval_ref.evaluate_layers_rmse: every
      detail (the f64 sum by its bits) and the error layer, two drawn layer / mode combinations.
+With COLOUR=1 (off by default; the draws above do not change: the colours come from a stream of their own) also
+  6. the same merges and the transform with submaps that carry colours (vgx_submap_set_colors; on two seeds in three one
+     drawn submap stays colourless), distance, weight and rgba against map_colour_ref.merge_submaps / transform_submap.
 A case whose restatement gives an empty product is counted as degenerate; more than one in five per product fails.
-    SEEDS=200 FIRST=1000 python profiles/fuzz_map_layers.py"""
+    SEEDS=200 FIRST=1000 python profiles/fuzz_map_layers.py
+    COLOUR=1 SEEDS=200 FIRST=3000 python profiles/fuzz_map_layers.py"""
 import os
 import sys
+import types
 
 import numpy as np
 
@@ -48,9 +53,31 @@ def eval_reference(gt, test, layer, mode, vps):
     return me.evaluate_layers_rmse(g, t, mode, vps)
 
 
+def draw_colours(seed, subs, vps):
+    """COLOUR=1: per submap [n][vps^3][4] u8 from a stream of its own -- four distinct bytes per voxel, three voxels in ten
+    all 0 / 255 (where the clamp of the interpolated channel is reached) -- or None for the submap left colourless"""
+    crng = np.random.default_rng([seed, 0x636F])
+    out = []
+    for s in subs:
+        n = len(s.block_index)
+        c = crng.integers(0, 256, (n, vps ** 3, 4), dtype=np.uint8)
+        slab = crng.random((n, vps ** 3)) < 0.3
+        c[slab] = crng.choice(np.array([0, 255], np.uint8), (int(slab.sum()), 4))
+        out.append(c)
+    if seed % 3 and len(out) > 1:
+        out[int(crng.integers(0, len(out)))] = None
+    return out
+
+
+def with_colours(s, rgba):
+    return types.SimpleNamespace(voxel_size=s.voxel_size, vps=s.vps, block_index=s.block_index, tsdf_distance=s.tsdf_distance,
+                                 tsdf_weight=s.tsdf_weight, tsdf_rgba=rgba)
+
+
 def main():
     from oracle import synth
     from profiles import fuzz_map_scene as S
+    from tests import map_colour_ref as mc
     from tests import map_eval_ref as me
     from tests import map_query_ref as mq
     from tests import projected_map_ref as pm
@@ -58,8 +85,9 @@ def main():
     capi.load()
     ctx = capi.Context(0)
     n_seeds, first = int(os.environ.get("SEEDS", "100")), int(os.environ.get("FIRST", "0"))
+    colour = os.environ.get("COLOUR", "0") == "1"
     deg = S.Degenerate()
-    tot = dict(cases=0, blocks=0, points=0, voxels=0)
+    tot = dict(cases=0, blocks=0, points=0, voxels=0, coloured_blocks=0, blended=0)
 
     def fail(sc, product, msg):
         print("MISMATCH seed", sc.seed, "product", product, "\n ", msg, "\n ", S.describe(sc))
@@ -110,6 +138,39 @@ def main():
         tl.destroy()
         tot["blocks"] += len(want_t)
         tot["voxels"] += len(want_t) * vps ** 3
+        # 6. the same with colours
+        if colour:
+            rgbas = draw_colours(seed, sc.subs, vps)
+            csubs = [with_colours(s, c) for s, c in zip(sc.subs, rgbas)]
+            for h, c in zip(handles, rgbas):
+                if c is not None:
+                    h.set_colors(c)
+            for name, start in (("coloured merge into empty", None), ("coloured merge into a layer with data", sc.base)):
+                cl = capi.TsdfLayer(ctx, vs, vps)
+                if start is not None:
+                    cl.upload(*start)
+                cl.merge_submaps(handles, sc.poses)
+                cbi, cd, cw, crgba = cl.download()
+                want_c = mc.merge_submaps({} if start is None else mc.layer_from_arrays(*start), csubs, sc.poses)
+                got_c = {tuple(int(v) for v in b): x for b, *x in zip(cbi, cd, cw, crgba)}
+                msg = S.compare_layers(name, got_c, want_c)
+                if msg:
+                    return fail(sc, "coloured merge", msg + f" (colourless: {[i for i, c in enumerate(rgbas) if c is None]})")
+                deg.count("coloured merge", len(want_c) == 0)
+                tot["coloured_blocks"] += len(want_c)
+                cl.destroy()
+            kc = next((i for i in range(len(rgbas)) if rgbas[(k + i) % len(rgbas)] is not None), 0)
+            kc = (k + kc) % len(rgbas)
+            cl = capi.TsdfLayer(ctx, vs, vps)
+            cl.transform_submap(handles[kc], sc.transform_pose)
+            cbi, cd, cw, crgba = cl.download()
+            want_c = mc.transform_submap(csubs[kc], sc.transform_pose)
+            msg = S.compare_layers("coloured transform", {tuple(int(v) for v in b): x for b, *x in zip(cbi, cd, cw, crgba)}, want_c)
+            if msg:
+                return fail(sc, "coloured transform", msg + f" (submap {kc})")
+            deg.count("coloured transform", len(want_c) == 0)
+            tot["coloured_blocks"] += len(want_c)
+            cl.destroy()
         for h in handles:
             h.destroy()
         if len(want) == 0:
@@ -163,7 +224,7 @@ def main():
         print("TOO MANY DEGENERATE CASES (more than one in five):", over)
         return 1
     print("no mismatch:", tot["cases"], "scenes,", tot["blocks"], "blocks,", tot["points"], "query points,", tot["voxels"],
-          "voxels compared")
+          "voxels compared" + (f"; with colours {tot['coloured_blocks']} blocks (distance, weight, rgba)" if colour else ""))
     return 0
 
 

@@ -13,9 +13,15 @@ bit, on the scenes of profiles/fuzz_map_scene.py.  Per seed, at the drawn min_we
   4. the marker of each of the three (vgx_mesh_fill_marker) in a drawn colour mode at a drawn opacity, with a drawn
      constant colour where the mesh has none and the mode needs one (and on one case in four besides), against
      mesh_marker_ref.fill_marker: points, colours and the point count.
+With COLOUR=1 (off by default; the draws above do not change: the colours come from a stream of their own) also
+  5. the projected map of the same submaps carrying colours, meshed with one colour per vertex
+     (vgx_tsdf_layer_generate_mesh_colored), and one raw coloured submap (vgx_submap_generate_mesh_colored): the plain
+     mesh unchanged, the vertex colours against map_colour_ref.vertex_colours; each welded at one drawn threshold and
+     filled into a marker in COLOR or LAMBERT_COLOR, against map_colour_ref.connect / fill_marker.
 A case whose restatement gives no triangle, or a weld that welds nothing or is refused, is counted as degenerate; more
 than one in five per product fails.  The slowest vgx_mesh_connect call is reported with its scene.
-    SEEDS=200 FIRST=1000 python profiles/fuzz_map_meshes.py"""
+    SEEDS=200 FIRST=1000 python profiles/fuzz_map_meshes.py
+    COLOUR=1 SEEDS=200 FIRST=3000 python profiles/fuzz_map_meshes.py"""
 import os
 import sys
 import time
@@ -48,6 +54,8 @@ def largest_weld(want):
 
 def main():
     from profiles import fuzz_map_scene as S
+    from profiles.fuzz_map_layers import draw_colours
+    from tests import map_colour_ref as mc
     from tests import mesh_marker_ref as kr
     from tests import mesh_ref as mr
     from tests import separated_mesh_ref as sr
@@ -55,8 +63,9 @@ def main():
     capi.load()
     ctx = capi.Context(0)
     n_seeds, first = int(os.environ.get("SEEDS", "100")), int(os.environ.get("FIRST", "0"))
+    colour = os.environ.get("COLOUR", "0") == "1"
     deg = S.Degenerate()
-    tot = dict(cases=0, blocks=0, triangles=0, welds=0, refused=0, soup=0, vertices=0, markers=0, marker_points=0)
+    tot = dict(cases=0, blocks=0, triangles=0, welds=0, refused=0, soup=0, vertices=0, markers=0, marker_points=0, coloured=0, coloured_triangles=0, moved=0)
     modes = {}
     slowest = (0.0, None)
     heaviest = (0, None)
@@ -136,6 +145,53 @@ def main():
                         heaviest = (largest_weld(wc), f"{what}, seed {seed}: {dt * 1e3:.2f} ms")
                 deg.count("connected " + name, weld_is_degenerate(wc))
                 tot["welds"] += 1
+        # 5. one colour per vertex
+        if colour:
+            rgbas = draw_colours(seed, sc.subs, vps)
+            for h, c in zip(handles, rgbas):
+                if c is not None:
+                    h.set_colors(c)
+            layer.upload(np.zeros((0, 3), np.int32), np.zeros(0, F), np.zeros(0, F))
+            layer.merge_submaps(handles, sc.poses)
+            cbi, cd, cw, crgba = layer.download()
+            kc = next(((k + i) % len(rgbas) for i in range(len(rgbas)) if rgbas[(k + i) % len(rgbas)] is not None))
+            sk = sc.subs[kc]
+            cases = [("coloured combined mesh", lambda: layer.generate_mesh_colored(mesh, mw), (cbi, cd, cw, crgba)),
+                     ("coloured submap mesh", lambda: handles[kc].generate_mesh_colored(mesh, mw),
+                      (sk.block_index, sk.tsdf_distance, sk.tsdf_weight, rgbas[kc]))]
+            for m, (name, device, (sbi, sd, sw, srgba)) in enumerate(cases):
+                device()
+                want = mr.generate_mesh(sbi, sd, sw, vps, vs, mw)[:4]
+                wcol, moved = mc.vertex_colours(want[0], want[1], want[2], sbi, sw, srgba, vps, vs, mw)
+                msg = S.compare(name, mesh.download() + (mesh.download_vertex_colors(),), want + (wcol,))
+                if msg or mesh.color_layout() != capi.MESH_COLORS_PER_VERTEX:
+                    return fail(sc, name, msg or f"colour layout {mesh.color_layout()}")
+                deg.count(name, len(want[2]) == 0)
+                tot["coloured"] += 1
+                tot["coloured_triangles"] += len(want[2])
+                tot["moved"] += int(moved.sum())
+                mode, opacity = (kr.COLOR, kr.LAMBERT_COLOR)[int(mrng.integers(0, 2))], float(F(mrng.uniform(0, 1)))
+                capi.fill_marker(mesh, mode, opacity, None, marker)
+                msg = S.compare(f"{name} marker in mode {mode}", marker.download(), mc.fill_marker(want[2], want[3], wcol, mode, opacity))
+                if msg:
+                    return fail(sc, name, msg)
+                kind, thr = sc.thresholds[int(mrng.integers(0, len(sc.thresholds)))]
+                try:
+                    wc = mc.connect(want[2], want[3], wcol, thr)
+                except OverflowError:
+                    wc = None
+                try:
+                    mesh.connect(thr, out)
+                    refused = None
+                except capi.VgxError as e:
+                    refused = e.code
+                what = f"{name} connected at {kind} {float(thr)!r}"
+                if (wc is None) != (refused is not None):
+                    return fail(sc, what, f"library refused with {refused}, restatement {'refused' if wc is None else 'did not'}")
+                if wc is not None:
+                    msg = S.compare(what, out.download(), wc)
+                    if msg or out.stats() != (len(wc[0]), len(wc[3]), True):
+                        return fail(sc, what, msg or f"stats {out.stats()}")
         layer.destroy()
         for h in handles:
             h.destroy()
@@ -154,6 +210,9 @@ def main():
     print("no mismatch:", tot["cases"], "scenes,", tot["blocks"], "mesh blocks,", tot["triangles"], "triangles,", tot["welds"],
           "welds (", tot["refused"], "refused as specified ),", tot["soup"], "soup vertices welded into", tot["vertices"], ";",
           tot["markers"], "markers,", tot["marker_points"], "points, per mode", dict(sorted(modes.items())))
+    if colour:
+        print("with colours:", tot["coloured"], "meshes,", tot["coloured_triangles"], "triangles,", tot["moved"],
+              "vertices coloured from a neighbouring block; each welded once and filled into a COLOR / LAMBERT_COLOR marker")
     return 0
 
 

@@ -171,6 +171,10 @@ SIGNATURES = {
     "vgx_esdf_config_default": (None, [C.POINTER(EsdfConfig)]),
     "vgx_submap_generate_esdf": (C.c_int, [vp, C.POINTER(EsdfConfig), i32p]),
     "vgx_submap_from_tsdf_layer": (C.c_int, [vp, vp, C.c_int32, C.POINTER(vp)]),
+    "vgx_submap_from_tsdf_layer_colored": (C.c_int, [vp, vp, C.c_int32, C.POINTER(vp)]),
+    "vgx_submap_set_colors": (C.c_int, [vp, u8p]),
+    "vgx_submap_has_colors": (C.c_int, [vp, i32p]),
+    "vgx_submap_download_colors": (C.c_int, [vp, u8p]),
     "vgx_submap_release_raw_layers": (C.c_int, [vp]),
     "vgx_submap_download_layers": (C.c_int, [vp, f32p, f32p, f32p, u8p]),
     "vgx_submap_block_index": (C.c_int, [vp, i32p]),
@@ -259,6 +263,8 @@ SIGNATURES = {
     "vgx_mesh_destroy": (C.c_int, [vp]),
     "vgx_tsdf_layer_generate_mesh": (C.c_int, [vp, C.POINTER(MeshConfig), vp]),
     "vgx_submap_generate_mesh": (C.c_int, [vp, C.POINTER(MeshConfig), vp]),
+    "vgx_tsdf_layer_generate_mesh_colored": (C.c_int, [vp, C.POINTER(MeshConfig), vp]),
+    "vgx_submap_generate_mesh_colored": (C.c_int, [vp, C.POINTER(MeshConfig), vp]),
     "vgx_mesh_stats": (C.c_int, [vp, i32p, i64p]),
     "vgx_mesh_download": (C.c_int, [vp, i32p, i64p, f32p, f32p]),
     "vgx_mesh_write_ply": (C.c_int, [vp, C.c_char_p]),
@@ -266,6 +272,8 @@ SIGNATURES = {
     "vgx_submaps_generate_separated_mesh": (C.c_int, [vp, C.c_int32, C.POINTER(vp), f32p, u8p, C.POINTER(MeshConfig), vp]),
     "vgx_mesh_has_colors": (C.c_int, [vp, i32p]),
     "vgx_mesh_download_colors": (C.c_int, [vp, u8p]),
+    "vgx_mesh_color_layout": (C.c_int, [vp, i32p]),
+    "vgx_mesh_download_vertex_colors": (C.c_int, [vp, u8p]),
     "vgx_connected_mesh_create": (C.c_int, [vp, C.POINTER(vp)]),
     "vgx_connected_mesh_destroy": (C.c_int, [vp]),
     "vgx_mesh_connect": (C.c_int, [vp, C.c_float, vp]),
@@ -525,6 +533,36 @@ class Submap:
         self.voxel_size, self.vps = layer.voxel_size, layer.vps
         return self
 
+    @classmethod
+    def from_tsdf_layer_colored(cls, ctx, layer, submap_id):
+        """from_tsdf_layer plus the layer's voxel colours, copied on the device (vgx_submap_from_tsdf_layer_colored)."""
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        h = vp()
+        ctx.check(ctx.lib.vgx_submap_from_tsdf_layer_colored(ctx.h, layer.h, submap_id, C.byref(h)))
+        self.h = h
+        self.voxel_size, self.vps = layer.voxel_size, layer.vps
+        return self
+
+    def set_colors(self, rgba):
+        """rgba [n_blocks][vps^3][4] uint8 in the order of block_index() (vgx_submap_set_colors)"""
+        c = None if rgba is None else np.ascontiguousarray(rgba, np.uint8)
+        if c is not None and c.size != self.num_blocks() * self.vps ** 3 * 4:
+            raise ValueError("rgba must hold n_blocks * vps^3 * 4 bytes")
+        self.ctx.check(self.ctx.lib.vgx_submap_set_colors(self.h, _ptr(c, u8p)))
+
+    def has_colors(self):
+        """True for a submap that carries voxel colours (vgx_submap_has_colors)"""
+        has = C.c_int32()
+        self.ctx.check(self.ctx.lib.vgx_submap_has_colors(self.h, C.byref(has)))
+        return bool(has.value)
+
+    def download_colors(self):
+        """rgba [n_blocks][vps^3][4] uint8 (vgx_submap_download_colors; a submap without colours raises)"""
+        out = np.zeros((self.num_blocks(), self.vps ** 3, 4), np.uint8)
+        self.ctx.check(self.ctx.lib.vgx_submap_download_colors(self.h, _ptr(out, u8p)))
+        return out
+
     def generate_esdf(self, config=None):
         """cblox::TsdfEsdfSubmap::generateEsdf() on the device; returns global passes used."""
         n = C.c_int32()
@@ -604,6 +642,14 @@ class Submap:
         mesh = mesh if mesh is not None else Mesh(self.ctx)
         cfg = MeshConfig(float(min_weight))
         self.ctx.check(self.ctx.lib.vgx_submap_generate_mesh(self.h, C.byref(cfg), mesh.h))
+        return mesh
+
+    def generate_mesh_colored(self, mesh=None, min_weight=1e-4):
+        """generate_mesh plus one TSDF colour per soup vertex, MeshIntegratorConfig::use_color
+        (vgx_submap_generate_mesh_colored; a submap without colours raises).  Returns the Mesh."""
+        mesh = mesh if mesh is not None else Mesh(self.ctx)
+        cfg = MeshConfig(float(min_weight))
+        self.ctx.check(self.ctx.lib.vgx_submap_generate_mesh_colored(self.h, C.byref(cfg), mesh.h))
         return mesh
 
     def _query_args(self, layer, interpolate, gradient, pose, weight):
@@ -1151,6 +1197,14 @@ class TsdfLayer:
         self.ctx.check(self.ctx.lib.vgx_tsdf_layer_generate_mesh(self.h, C.byref(cfg), mesh.h))
         return mesh
 
+    def generate_mesh_colored(self, mesh=None, min_weight=1e-4):
+        """generate_mesh plus one TSDF colour per soup vertex, MeshIntegratorConfig::use_color
+        (vgx_tsdf_layer_generate_mesh_colored).  Returns the Mesh."""
+        mesh = mesh if mesh is not None else Mesh(self.ctx)
+        cfg = MeshConfig(float(min_weight))
+        self.ctx.check(self.ctx.lib.vgx_tsdf_layer_generate_mesh_colored(self.h, C.byref(cfg), mesh.h))
+        return mesh
+
     def cloud(self, config=None, cloud=None):
         """The point-cloud view of this layer, colours included (vgx_tsdf_layer_cloud; config: cloud_config(...)).
         Returns the Cloud (a new one when cloud is None)."""
@@ -1207,11 +1261,12 @@ def projected_map(ctx, submaps, poses, layer):
     return layer
 
 
-def combined_mesh(ctx, submaps, poses, layer, mesh=None, min_weight=1e-4):
-    """cblox SubmapMesher::generateCombinedMesh: projected_map(ctx, submaps, poses, layer), then the layer's mesh.
+def combined_mesh(ctx, submaps, poses, layer, mesh=None, min_weight=1e-4, use_color=False):
+    """cblox SubmapMesher::generateCombinedMesh: projected_map(ctx, submaps, poses, layer), then the layer's mesh
+    (use_color: with one TSDF colour per vertex -- the submaps must carry colours for it to be more than zeros).
     Returns the Mesh."""
     projected_map(ctx, submaps, poses, layer)
-    return layer.generate_mesh(mesh, min_weight)
+    return layer.generate_mesh_colored(mesh, min_weight) if use_color else layer.generate_mesh(mesh, min_weight)
 
 
 DEFAULT_COLOR_CYCLE_LENGTH = 20  # cblox::kDefaultColorCycleLength [recalled]
@@ -1531,6 +1586,9 @@ def map_evaluation(ctx, submaps, poses, gt_submap, align, voxel_size=None, vps=N
                 o.destroy()
 
 
+MESH_COLORS_NONE, MESH_COLORS_PER_TRIANGLE, MESH_COLORS_PER_VERTEX = 0, 1, 2
+
+
 class Mesh:
     """A voxblox MeshLayer on the GPU (vgx_mesh): per allocated block, in ascending block-index order, a range of
     triangles; reused from call to call."""
@@ -1559,10 +1617,23 @@ class Mesh:
         return bi, first, v, n
 
     def has_colors(self):
-        """True after a separated mesh (vgx_mesh_has_colors)"""
+        """True after a separated mesh or a coloured mesh (vgx_mesh_has_colors)"""
         has = C.c_int32()
         self.ctx.check(self.ctx.lib.vgx_mesh_has_colors(self.h, C.byref(has)))
         return bool(has.value)
+
+    def color_layout(self):
+        """MESH_COLORS_NONE / _PER_TRIANGLE / _PER_VERTEX (vgx_mesh_color_layout)"""
+        layout = C.c_int32()
+        self.ctx.check(self.ctx.lib.vgx_mesh_color_layout(self.h, C.byref(layout)))
+        return layout.value
+
+    def download_vertex_colors(self):
+        """rgba [T][3][4] uint8, one colour per soup vertex (vgx_mesh_download_vertex_colors; any other layout raises)"""
+        _, nt = self.stats()
+        out = np.zeros((nt, 3, 4), np.uint8)
+        self.ctx.check(self.ctx.lib.vgx_mesh_download_vertex_colors(self.h, _ptr(out, u8p)))
+        return out
 
     def download_colors(self):
         """rgba [T][4] uint8, one colour per triangle (vgx_mesh_download_colors; a mesh without colours raises)"""

@@ -10,8 +10,10 @@
 //   voxblox::MeshLayer mesh_layer(submap_collection.block_size());
 //   voxgraph_amd::DownloadMeshLayer(gpu_mesh, &mesh_layer);
 //
-// Semantics and deviations (no colour, no incremental meshing) are stated at vgx_tsdf_layer_generate_mesh in
-// include/voxgraph_amd.h.
+// Semantics and deviations (no incremental meshing) are stated at vgx_tsdf_layer_generate_mesh in include/voxgraph_amd.h.
+// MeshIntegratorConfig::use_color is an opt-in, off by default (the last argument of GenerateMeshOnGpu /
+// GenerateCombinedMeshOnGpu): one TSDF colour per vertex, which DownloadColoredMeshLayer, writePly, the weld and the
+// markers then carry -- more than zeros only when the submaps kept their colours (GpuSubmapRegistry::setKeepColors).
 //
 // The separated mesh (SubmapVisuals::publishSeparatedMesh / saveSeparatedMesh: cblox generateSeparatedMesh) is one call
 // over the whole collection, each submap in voxgraph's colour (vgx_submaps_generate_separated_mesh):
@@ -71,13 +73,27 @@ class GpuMesh {
     check(vgx_mesh_has_colors(mesh_, &has), "vgx_mesh_has_colors");
     return has != 0;
   }
-  // rgba [T][4], one colour per triangle (a separated mesh; throws on a mesh without colours)
+  // VGX_MESH_COLORS_NONE / _PER_TRIANGLE (a separated mesh) / _PER_VERTEX (a use_color mesh)
+  int32_t colorLayout() const {
+    int32_t layout = 0;
+    check(vgx_mesh_color_layout(mesh_, &layout), "vgx_mesh_color_layout");
+    return layout;
+  }
+  // rgba [T][4], one colour per triangle (a separated mesh; throws on any other mesh)
   void downloadColors(std::vector<uint8_t>* rgba) const {
     int32_t nb = 0;
     int64_t nt = 0;
     stats(&nb, &nt);
     rgba->resize(4 * static_cast<size_t>(nt));
     check(vgx_mesh_download_colors(mesh_, rgba->data()), "vgx_mesh_download_colors");
+  }
+  // rgba [T][3][4], one colour per soup vertex (a use_color mesh; throws on any other mesh)
+  void downloadVertexColors(std::vector<uint8_t>* rgba) const {
+    int32_t nb = 0;
+    int64_t nt = 0;
+    stats(&nb, &nt);
+    rgba->resize(12 * static_cast<size_t>(nt));
+    check(vgx_mesh_download_vertex_colors(mesh_, rgba->data()), "vgx_mesh_download_vertex_colors");
   }
 
  private:
@@ -88,23 +104,28 @@ class GpuMesh {
   vgx_mesh mesh_ = nullptr;
 };
 
-// MeshIntegrator<TsdfVoxel>::generateMesh(false, false) over a layer on the GPU (queued behind its scans / merges)
-inline GpuMesh& GenerateMeshOnGpu(const GpuTsdfLayer& layer, float min_weight, GpuMesh* mesh) {
+// MeshIntegrator<TsdfVoxel>::generateMesh(false, false) over a layer on the GPU (queued behind its scans / merges).
+// use_color (MeshIntegratorConfig::use_color; off by default): one TSDF colour per vertex as well
+inline GpuMesh& GenerateMeshOnGpu(const GpuTsdfLayer& layer, float min_weight, GpuMesh* mesh, bool use_color = false) {
   if (!mesh) throw std::invalid_argument("GenerateMeshOnGpu: mesh == nullptr");
   vgx_mesh_config cfg;
   vgx_mesh_config_default(&cfg);
   cfg.min_weight = min_weight;
-  if (vgx_tsdf_layer_generate_mesh(layer.handle(), &cfg, mesh->handle()) != VGX_OK)
-    throw std::runtime_error(std::string("vgx_tsdf_layer_generate_mesh: ") + layer.last_error());
+  const int rc = use_color ? vgx_tsdf_layer_generate_mesh_colored(layer.handle(), &cfg, mesh->handle())
+                           : vgx_tsdf_layer_generate_mesh(layer.handle(), &cfg, mesh->handle());
+  if (rc != VGX_OK)
+    throw std::runtime_error(std::string(use_color ? "vgx_tsdf_layer_generate_mesh_colored: " : "vgx_tsdf_layer_generate_mesh: ") +
+                             layer.last_error());
   return *mesh;
 }
 
 // cblox SubmapMesher::generateCombinedMesh: the projected map of the collection (submaps in ID order, at their poses)
 // into gpu_layer, then its mesh
 template <typename CollectionT>
-GpuMesh& GenerateCombinedMeshOnGpu(const CollectionT& collection, GpuTsdfLayer* gpu_layer, float min_weight, GpuMesh* mesh) {
+GpuMesh& GenerateCombinedMeshOnGpu(const CollectionT& collection, GpuTsdfLayer* gpu_layer, float min_weight, GpuMesh* mesh,
+                                   bool use_color = false) {
   GetProjectedMapOnGpu(collection, gpu_layer);
-  return GenerateMeshOnGpu(*gpu_layer, min_weight, mesh);
+  return GenerateMeshOnGpu(*gpu_layer, min_weight, mesh, use_color);
 }
 
 // voxblox rainbowColorMap [recalled]: an HSV blend at s = v = 1 in double, channels truncated to uint8, a = 255
@@ -212,8 +233,9 @@ void DownloadMeshLayer(const GpuMesh& gpu_mesh, MeshLayerT* mesh_layer) {
   }
 }
 
-// DownloadMeshLayer plus the colours of a separated mesh: mesh->colors gets the triangle's colour on each of its three
-// vertices (voxblox's layout).  The MeshLayer's mesh type needs a `colors` vector of voxblox::Color.
+// DownloadMeshLayer plus the colours: mesh->colors gets, on each vertex, the triangle's colour (a separated mesh) or the
+// vertex's own (a use_color mesh) -- voxblox's layout either way.  The MeshLayer's mesh type needs a `colors` vector of
+// voxblox::Color.
 template <typename MeshLayerT>
 void DownloadColoredMeshLayer(const GpuMesh& gpu_mesh, MeshLayerT* mesh_layer) {
   if (!mesh_layer) throw std::invalid_argument("DownloadColoredMeshLayer: mesh_layer == nullptr");
@@ -222,7 +244,9 @@ void DownloadColoredMeshLayer(const GpuMesh& gpu_mesh, MeshLayerT* mesh_layer) {
   std::vector<float> v, n;
   std::vector<uint8_t> rgba;
   gpu_mesh.download(&bi, &first, &v, &n);
-  gpu_mesh.downloadColors(&rgba);
+  const bool per_vertex = gpu_mesh.colorLayout() == VGX_MESH_COLORS_PER_VERTEX;
+  if (per_vertex) gpu_mesh.downloadVertexColors(&rgba);
+  else gpu_mesh.downloadColors(&rgba);
   for (size_t b = 0; b + 1 < first.size(); ++b) {
     voxblox::BlockIndex index;
     index[0] = bi[3 * b];
@@ -235,8 +259,9 @@ void DownloadColoredMeshLayer(const GpuMesh& gpu_mesh, MeshLayerT* mesh_layer) {
     mesh->indices.clear();
     for (int64_t t = first[b]; t < first[b + 1]; ++t) {
       const voxblox::Point normal(n[3 * t], n[3 * t + 1], n[3 * t + 2]);
-      const voxblox::Color color(rgba[4 * t], rgba[4 * t + 1], rgba[4 * t + 2], rgba[4 * t + 3]);
       for (int q = 0; q < 3; ++q) {
+        const uint8_t* c = &rgba[per_vertex ? 12 * t + 4 * q : 4 * t];
+        const voxblox::Color color(c[0], c[1], c[2], c[3]);
         const float* p = &v[9 * t + 3 * q];
         mesh->indices.push_back(static_cast<int>(mesh->vertices.size()));
         mesh->vertices.push_back(voxblox::Point(p[0], p[1], p[2]));

@@ -103,12 +103,16 @@ inline GpuMeshMarker& ColoredMeshMarkerOnGpu(const GpuMesh& mesh, const voxblox:
   return FillMarkerWithMeshOnGpu(mesh, cfg, marker);
 }
 
-// SubmapVisuals::publishCombinedMesh: the projected map into gpu_layer, its mesh into `mesh`, the marker in kNormals
+// SubmapVisuals::publishCombinedMesh: the projected map into gpu_layer, its mesh into `mesh`, the marker in kNormals.
+// On a mesh with one colour per vertex (gpu_mesh.h, use_color) kColor and kLambertColor shade every vertex with its own
+// colour; nothing else in this header depends on the layout.  use_color (off by default) makes such a mesh here, for a
+// color_mode that shows it.
 template <typename CollectionT>
 GpuMeshMarker& CombinedMeshMarkerOnGpu(const CollectionT& collection, GpuTsdfLayer* gpu_layer, float min_weight, float opacity,
-                                       GpuMesh* mesh, GpuMeshMarker* marker) {
-  GenerateCombinedMeshOnGpu(collection, gpu_layer, min_weight, mesh);
-  return FillMarkerWithMeshOnGpu(*mesh, MarkerColorMode::kNormals, opacity, marker);
+                                       GpuMesh* mesh, GpuMeshMarker* marker, bool use_color = false,
+                                       MarkerColorMode color_mode = MarkerColorMode::kNormals) {
+  GenerateCombinedMeshOnGpu(collection, gpu_layer, min_weight, mesh, use_color);
+  return FillMarkerWithMeshOnGpu(*mesh, color_mode, opacity, marker);
 }
 
 // SubmapVisuals::publishSeparatedMesh: every submap in voxgraph's colour into `mesh`, the marker in kLambertColor

@@ -66,6 +66,12 @@ class GpuSubmapRegistry {
     std::lock_guard<std::mutex> lk(mu_);
     return ctx_;
   }
+  // Off by default.  On: the submaps uploaded FROM NOW ON keep their TSDF voxels' colours (UploadFinishedSubmap's
+  // keep_colors); copies already made stay as they are until they are released or uploaded again.
+  void setKeepColors(bool keep_colors) {
+    std::lock_guard<std::mutex> lk(mu_);
+    keep_colors_ = keep_colors;
+  }
   // The device copy of the submap behind `submap_ptr` (VoxgraphSubmap::ConstPtr, a std::shared_ptr), uploaded on first
   // use.  The cache is keyed by the object's address but BELIEVES an entry only while (a) the shared_ptr that made it
   // still owns the same object -- voxgraph dropping a submap without release() and the allocator handing the address to
@@ -97,7 +103,7 @@ class GpuSubmapRegistry {
       ++stale_replaced_;
     }
     Entry e;
-    e.handle = UploadFinishedSubmap(ctx_, *submap_ptr);
+    e.handle = UploadFinishedSubmap(ctx_, *submap_ptr, keep_colors_);
     e.owner = std::shared_ptr<const void>(submap_ptr);
     e.stamp = stamp;
     handles_[key] = e;
@@ -134,6 +140,7 @@ class GpuSubmapRegistry {
   GpuSubmapRegistry() = default;
   mutable std::mutex mu_;
   vgx_ctx ctx_ = nullptr;
+  bool keep_colors_ = false;
   std::map<const void*, Entry> handles_;
   long stale_replaced_ = 0;
 };

@@ -101,6 +101,20 @@ inline void UploadTsdfLayer(const voxblox::Layer<voxblox::TsdfVoxel>& layer, Gpu
     throw std::runtime_error(std::string("vgx_tsdf_layer_upload: ") + gpu->last_error());
 }
 
+// finishSubmap() on the device: the GPU layer's blocks become a vgx_submap without a host round trip
+// (vgx_submap_from_tsdf_layer; follow with vgx_submap_generate_esdf and the point extraction).  keep_colors (off by
+// default): the layer's colours are copied too, device to device (vgx_submap_from_tsdf_layer_colored).  The caller owns
+// the handle (vgx_submap_destroy).
+inline vgx_submap FinishSubmapOnGpu(vgx_ctx ctx, const GpuTsdfLayer& gpu, int32_t submap_id, bool keep_colors = false) {
+  vgx_submap out = nullptr;
+  const int rc = keep_colors ? vgx_submap_from_tsdf_layer_colored(ctx, gpu.handle(), submap_id, &out)
+                             : vgx_submap_from_tsdf_layer(ctx, gpu.handle(), submap_id, &out);
+  if (rc != VGX_OK)
+    throw std::runtime_error(std::string(keep_colors ? "vgx_submap_from_tsdf_layer_colored: " : "vgx_submap_from_tsdf_layer: ") +
+                             gpu.last_error());
+  return out;
+}
+
 }  // namespace voxgraph_amd
 
 #endif  // VOXGRAPH_AMD_CPP_GPU_TSDF_LAYER_BRIDGE_H_

@@ -57,8 +57,10 @@ void UploadRegistrationPoints(vgx_ctx ctx, const SubmapT& submap, PointTypeT poi
 
 // Uploads a FINISHED submap: both layers (block by block, voxblox linear voxel order) and both
 // cached registration-point sets.  The returned handle is immutable and independent of `submap`.
+// keep_colors (off by default: 4 B per voxel more on the device): the TSDF voxels' colours travel too
+// (vgx_submap_set_colors), for a projected map and meshes that carry them (gpu_mesh.h, use_color)
 template <typename SubmapT>
-vgx_submap UploadFinishedSubmap(vgx_ctx ctx, const SubmapT& submap) {
+vgx_submap UploadFinishedSubmap(vgx_ctx ctx, const SubmapT& submap, bool keep_colors = false) {
   // The registration cost function is 4-DoF: the reference CHECKs that both submaps' Z axes are
   // gravity aligned when it is constructed (registration_cost_function.cpp:25-36, a signed compare
   // of roll and pitch against 1e-6).  The GPU cost function never sees the 6-DoF pose, so the same
@@ -81,6 +83,7 @@ vgx_submap UploadFinishedSubmap(vgx_ctx ctx, const SubmapT& submap) {
   std::vector<int32_t> block_index(3 * nb);
   std::vector<float> tsdf_distance(nb * vox), tsdf_weight(nb * vox), esdf_distance(nb * vox);
   std::vector<uint8_t> esdf_observed(nb * vox);
+  std::vector<uint8_t> tsdf_rgba(keep_colors ? 4 * nb * vox : 0);
   for (size_t b = 0; b < nb; ++b) {
     for (int a = 0; a < 3; ++a) block_index[3 * b + a] = block_list[b][a];
     const auto& tb = tsdf.getBlockByIndex(block_list[b]);
@@ -89,6 +92,13 @@ vgx_submap UploadFinishedSubmap(vgx_ctx ctx, const SubmapT& submap) {
       const auto& tv = tb.getVoxelByLinearIndex(i);
       tsdf_distance[b * vox + i] = tv.distance;
       tsdf_weight[b * vox + i] = tv.weight;
+      if (keep_colors) {
+        uint8_t* c = &tsdf_rgba[4 * (b * vox + i)];
+        c[0] = tv.color.r;
+        c[1] = tv.color.g;
+        c[2] = tv.color.b;
+        c[3] = tv.color.a;
+      }
       if (eb) {
         const auto& ev = eb->getVoxelByLinearIndex(i);
         esdf_distance[b * vox + i] = ev.distance;
@@ -105,6 +115,14 @@ vgx_submap UploadFinishedSubmap(vgx_ctx ctx, const SubmapT& submap) {
                                    tsdf_distance.data(), tsdf_weight.data(), esdf_distance.data(),
                                    esdf_observed.data(), &out);
   if (rc != VGX_OK) throw std::runtime_error(std::string("vgx_submap_create: ") + vgx_last_error(ctx));
+  if (keep_colors) {
+    tsdf_rgba.resize(tsdf_rgba.size() + 4);  // (never a null pointer, also without blocks: null is what the call refuses)
+    if (vgx_submap_set_colors(out, tsdf_rgba.data()) != VGX_OK) {
+      const std::string msg = std::string("vgx_submap_set_colors: ") + vgx_last_error(ctx);
+      vgx_submap_destroy(out);
+      throw std::runtime_error(msg);
+    }
+  }
   using PointType = typename SubmapT::RegistrationPointType;
   UploadRegistrationPoints(ctx, submap, PointType::kVoxels, VGX_POINTS_VOXELS, out);
   UploadRegistrationPoints(ctx, submap, PointType::kIsosurfacePoints, VGX_POINTS_ISOSURFACE, out);

@@ -127,7 +127,7 @@ __global__ __launch_bounds__(kConnectThreads) void connect_resolve_kernel(const 
 
 // number [n]: the inclusive scan of the flags
 __global__ __launch_bounds__(kConnectThreads) void connect_emit_kernel(const float* __restrict__ soup, const float* __restrict__ tri_normals,
-                                                                       const uint32_t* __restrict__ tri_colors, uint32_t n,
+                                                                       const uint32_t* __restrict__ tri_colors, bool per_vertex, uint32_t n,
                                                                        const uint32_t* __restrict__ rep, const uint32_t* __restrict__ number,
                                                                        float* __restrict__ vertices, float* __restrict__ normals,
                                                                        uint32_t* __restrict__ colors, uint32_t* __restrict__ indices) {
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(kConnectThreads) void connect_emit_kernel(const flo
     vertices[3 * (size_t)u + a] = soup[3 * (size_t)j + a];
     normals[3 * (size_t)u + a] = tri_normals[3 * t + a];
   }
-  if (tri_colors) colors[u] = tri_colors[t];
+  if (tri_colors) colors[u] = tri_colors[per_vertex ? (size_t)j : t];  // (per vertex: the first soup vertex's own colour)
 }
 
 }  // namespace vgx
@@ -243,7 +243,7 @@ int connect(vgx_ctx ctx, hipStream_t st, const MeshView& src, double inv, vgx_co
   // 4. emit
   rc = ensure_verts(C, nv);
   if (rc != VGX_OK) return rc;
-  hipLaunchKernelGGL(connect_emit_kernel, grid, block, 0, st, src.vertices, src.normals, src.colors, n32, rep, number,
+  hipLaunchKernelGGL(connect_emit_kernel, grid, block, 0, st, src.vertices, src.normals, src.colors, src.per_vertex, n32, rep, number,
                      C->d_vertices.as<float>(), C->d_normals.as<float>(), C->d_colors.as<uint32_t>(), C->d_indices.as<uint32_t>());
   VGX_HIP(ctx, hipGetLastError());
   VGX_HIP(ctx, hipStreamSynchronize(st));

@@ -585,8 +585,55 @@ int vgx_submap_release_raw_layers(vgx_submap sm) {
   if (sm->d_tsdf_weight) (void)hipFree(sm->d_tsdf_weight);
   if (sm->d_esdf_distance) (void)hipFree(sm->d_esdf_distance);
   if (sm->d_esdf_observed) (void)hipFree(sm->d_esdf_observed);
+  if (sm->d_tsdf_rgba) (void)hipFree(sm->d_tsdf_rgba);
   sm->d_tsdf_distance = sm->d_tsdf_weight = sm->d_esdf_distance = nullptr;
   sm->d_esdf_observed = nullptr;
+  sm->d_tsdf_rgba = nullptr;
+  return VGX_OK;
+}
+
+int vgx_submap_set_colors(vgx_submap sm, const uint8_t* rgba) {
+  if (!sm) return VGX_ERR_INVALID;
+  vgx_ctx ctx = sm->ctx;
+  if (!rgba) return set_error(ctx, VGX_ERR_INVALID, "vgx_submap_set_colors: NULL rgba");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (sm->n_blocks > 0 && (!sm->d_tsdf_distance || !sm->d_tsdf_weight))
+    return set_error(ctx, VGX_ERR_INVALID, "vgx_submap_set_colors: raw TSDF layer not resident (released?)");
+  VGX_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = std::max<size_t>((size_t)sm->n_blocks * sm->vps * sm->vps * sm->vps * 4, 4);  // (never null: null means none)
+  // staged through a fresh buffer, so that colours already held are whole or replaced, never half of each
+  uint32_t* fresh = nullptr;
+  hipError_t e = hipMalloc(&fresh, bytes);
+  if (e != hipSuccess) return vgx::alloc_error(ctx, e, "vgx_submap_set_colors: allocating colours");
+  if (sm->n_blocks > 0) e = hipMemcpyAsync(fresh, rgba, bytes, hipMemcpyHostToDevice, ctx->stream);
+  // (pageable host memory: finished before the caller's array goes away; what was queued on the old colours has run too)
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) {
+    (void)hipFree(fresh);
+    VGX_HIP(ctx, e);
+  }
+  if (sm->d_tsdf_rgba) (void)hipFree(sm->d_tsdf_rgba);
+  sm->d_tsdf_rgba = fresh;
+  return VGX_OK;
+}
+
+int vgx_submap_has_colors(vgx_submap sm, int32_t* has) {
+  if (!sm || !has) return VGX_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(sm->ctx->mu);
+  *has = sm->d_tsdf_rgba ? 1 : 0;
+  return VGX_OK;
+}
+
+int vgx_submap_download_colors(vgx_submap sm, uint8_t* rgba) {
+  if (!sm) return VGX_ERR_INVALID;
+  vgx_ctx ctx = sm->ctx;
+  if (!rgba) return set_error(ctx, VGX_ERR_INVALID, "vgx_submap_download_colors: NULL rgba");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!sm->d_tsdf_rgba) return set_error(ctx, VGX_ERR_INVALID, "vgx_submap_download_colors: the submap has no colours");
+  VGX_HIP(ctx, hipSetDevice(ctx->device));
+  VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const size_t bytes = (size_t)sm->n_blocks * sm->vps * sm->vps * sm->vps * 4;
+  if (bytes) VGX_HIP(ctx, hipMemcpy(rgba, sm->d_tsdf_rgba, bytes, hipMemcpyDeviceToHost));
   return VGX_OK;
 }
 

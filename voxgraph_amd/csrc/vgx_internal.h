@@ -276,6 +276,9 @@ struct vgx_submap_s {
   // raw layers (voxblox layout), kept for point extraction
   float* d_tsdf_distance = nullptr;
   float* d_tsdf_weight = nullptr;
+  // the TSDF voxels' colours, one packed word per voxel (bytes r g b a, r lowest: TsdfLayerDev::rgba), or null: only a
+  // submap that asked for them pays the 4 B per voxel (vgx_submap_from_tsdf_layer_colored, vgx_submap_set_colors)
+  uint32_t* d_tsdf_rgba = nullptr;
   float* d_esdf_distance = nullptr;
   uint8_t* d_esdf_observed = nullptr;
   vgx::Grid grid[2];       // [0] TSDF, [1] ESDF sampling grids
@@ -498,10 +501,11 @@ struct MeshView {
   vgx_ctx ctx;
   bool holds_mesh;   // false after a generating call that failed
   bool has_colors;
+  bool per_vertex;   // colors is [3 n_tris], one per soup vertex (vgx_*_generate_mesh_colored); else [n_tris]
   int64_t n_tris;
   const float* vertices;   // [n_tris][3][3]
   const float* normals;    // [n_tris][3]
-  const uint32_t* colors;  // [n_tris] bytes r g b a, or null
+  const uint32_t* colors;  // [n_tris] or [3 n_tris] bytes r g b a, or null
 };
 std::mutex& mesh_mutex(vgx_mesh M);
 MeshView mesh_view(vgx_mesh M);

@@ -118,6 +118,47 @@ __device__ bool tsdf_interp(const P& p, const float pos[3], float& dist, float& 
   return layer_interp<VPS>(p, p.tsdf_d, p.tsdf_w, pos, dist, wgt);
 }
 
+// Interpolator<TsdfVoxel>::interpVoxel's colour [recalled] at a point where tsdf_interp returned true (all 8 neighbours
+// exist): per channel the 8 neighbours' bytes widened to f32, in layer_interp's neighbour order, through interp_trilinear
+// with the same dl as distance and weight.  voxblox assigns that float to a uint8_t member; here it is clamped to [0, 255]
+// first and then truncated toward zero -- a stated definition for the few-ulp overshoots the C++ cast leaves undefined.
+// rgba: [n_blocks][VPS^3] words, bytes r g b a (r lowest).  A pass of its own, after tsdf_interp, so that the 8 colour
+// words are not live next to the 16 distance / weight values.
+template <int VPS, class P>
+__device__ __forceinline__ uint32_t tsdf_color_interp(const P& p, const uint32_t* __restrict__ rgba, const float pos[3]) {
+  constexpr int VOX = VPS * VPS * VPS;
+  int blk[3], vox[3];
+  float dl[3];
+  interp_base<VPS>(p, pos, blk, vox, dl);
+  uint32_t c[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    int off[3] = {(k >> 2) & 1, (k >> 1) & 1, k & 1};
+    int nb[3], nv[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      nb[a] = blk[a];
+      nv[a] = vox[a] + off[a];
+      if (nv[a] >= VPS) {
+        nb[a]++;
+        nv[a] -= VPS;
+      }
+    }
+    const int slot = interp_slot(p, nb[0], nb[1], nb[2]);
+    c[k] = slot >= 0 ? rgba[(size_t)slot * VOX + (size_t)(nv[0] + VPS * (nv[1] + VPS * nv[2]))] : 0u;  // (present: the caller checked)
+  }
+  uint32_t out = 0;
+#pragma unroll
+  for (int ch = 0; ch < 4; ++ch) {
+    float x[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) x[k] = (float)((c[k] >> (8 * ch)) & 0xffu);
+    const float v = fminf(fmaxf(interp_trilinear(x, dl), 0.0f), 255.0f);
+    out |= (uint32_t)v << (8 * ch);
+  }
+  return out;
+}
+
 }  // namespace vgx
 
 #endif  // VGX_INTERP_H_

@@ -12,6 +12,9 @@
 //     colours  thread i writes the 16 bytes of vertices i, i + 256, i + 512 of the workgroup (the LDS colour of triangle
 //              vertex / 3, or under HEIGHT the rainbow of the vertex's own z): again 1024 contiguous bytes per wave
 // No atomics, no scan: T is known on the host, and every output byte has one writer.
+// PV (COLOR and LAMBERT_COLOR on a mesh with one colour per soup vertex): the colour step keeps only the triangle's two
+// light terms in LDS, and the colours step shades vertex j from its own word vert_colors[j] (a wave reads 256 contiguous
+// bytes) through the same table and formulas; the stores are the same 1024 contiguous bytes per wave.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -72,7 +75,7 @@ __device__ __forceinline__ void marker_height(float z, const float* __restrict__
 
 // soup [T][3][3], tri_normals [T][3], tri_colors [T] (bytes r g b a) or null: P.constant_rgba for every triangle.
 // points [3 T][3] f64 and colors [3 T][4] f32 are 16-byte aligned (device allocations).
-template <int MODE>
+template <int MODE, bool PV = false>
 __global__ __launch_bounds__(kMarkerThreads) void marker_fill_kernel(const float* __restrict__ soup, const float* __restrict__ tri_normals,
                                                                      const uint32_t* __restrict__ tri_colors, unsigned long long n_tris,
                                                                      const float* __restrict__ c8, MarkerParams P,
@@ -94,13 +97,18 @@ __global__ __launch_bounds__(kMarkerThreads) void marker_fill_kernel(const float
       for (int a = 0; a < 3; ++a) n[a] = tri_normals[3 * t + a];
     }
     float c[3];
-    if (MODE == VGX_MARKER_COLOR || MODE == VGX_MARKER_LAMBERT_COLOR) {
+    if (!PV && (MODE == VGX_MARKER_COLOR || MODE == VGX_MARKER_LAMBERT_COLOR)) {
       const uint32_t w = tri_colors ? tri_colors[t] : P.constant_rgba;
       c[0] = s_c8[w & 255u];
       c[1] = s_c8[(w >> 8) & 255u];
       c[2] = s_c8[(w >> 16) & 255u];
     }
-    if (MODE == VGX_MARKER_COLOR) {
+    if (PV) {  // tri_colors is [3 T]: the lights here, the shading per vertex below
+      if (MODE == VGX_MARKER_LAMBERT_COLOR) {
+        rgb[0] = marker_light(n, P.light1);
+        rgb[1] = marker_light(n, P.light2);
+      }
+    } else if (MODE == VGX_MARKER_COLOR) {
 #pragma unroll
       for (int a = 0; a < 3; ++a) rgb[a] = c[a];
     } else if (MODE == VGX_MARKER_NORMALS) {
@@ -138,6 +146,15 @@ __global__ __launch_bounds__(kMarkerThreads) void marker_fill_kernel(const float
     if (MODE == VGX_MARKER_HEIGHT) {
       float rgb[3];
       marker_height(soup[3 * j + 2], s_c8, rgb);
+      colors[j] = make_float4(rgb[0], rgb[1], rgb[2], P.opacity);
+    } else if (PV) {
+      const uint32_t w = tri_colors[j];
+      float rgb[3] = {s_c8[w & 255u], s_c8[(w >> 8) & 255u], s_c8[(w >> 16) & 255u]};
+      if (MODE == VGX_MARKER_LAMBERT_COLOR) {
+        const float4 l = s_colour[jl / 3u];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) rgb[a] = marker_lambert(rgb[a], l.x, l.y);
+      }
       colors[j] = make_float4(rgb[0], rgb[1], rgb[2], P.opacity);
     } else {
       colors[j] = s_colour[jl / 3u];
@@ -219,12 +236,21 @@ int fill_marker(vgx_ctx ctx, hipStream_t st, const MeshView& src, const vgx_mesh
   float4* colors = K->d_colors.as<float4>();
 #define VGX_MARKER_LAUNCH(M) \
   hipLaunchKernelGGL(marker_fill_kernel<M>, grid, block, 0, st, src.vertices, src.normals, tri_colors, T, c8, P, points, colors)
-  switch (mode) {
-    case VGX_MARKER_COLOR: VGX_MARKER_LAUNCH(VGX_MARKER_COLOR); break;
-    case VGX_MARKER_HEIGHT: VGX_MARKER_LAUNCH(VGX_MARKER_HEIGHT); break;
-    case VGX_MARKER_NORMALS: VGX_MARKER_LAUNCH(VGX_MARKER_NORMALS); break;
-    case VGX_MARKER_GRAY: VGX_MARKER_LAUNCH(VGX_MARKER_GRAY); break;
-    default: VGX_MARKER_LAUNCH(VGX_MARKER_LAMBERT_COLOR); break;
+  const bool pv = tri_colors && src.per_vertex;  // one colour per soup vertex: COLOR and LAMBERT_COLOR shade each apart
+  if (pv && mode == VGX_MARKER_COLOR) {
+    hipLaunchKernelGGL((marker_fill_kernel<VGX_MARKER_COLOR, true>), grid, block, 0, st, src.vertices, src.normals, tri_colors, T, c8, P,
+                       points, colors);
+  } else if (pv && mode == VGX_MARKER_LAMBERT_COLOR) {
+    hipLaunchKernelGGL((marker_fill_kernel<VGX_MARKER_LAMBERT_COLOR, true>), grid, block, 0, st, src.vertices, src.normals, tri_colors, T,
+                       c8, P, points, colors);
+  } else {
+    switch (mode) {
+      case VGX_MARKER_COLOR: VGX_MARKER_LAUNCH(VGX_MARKER_COLOR); break;
+      case VGX_MARKER_HEIGHT: VGX_MARKER_LAUNCH(VGX_MARKER_HEIGHT); break;
+      case VGX_MARKER_NORMALS: VGX_MARKER_LAUNCH(VGX_MARKER_NORMALS); break;
+      case VGX_MARKER_GRAY: VGX_MARKER_LAUNCH(VGX_MARKER_GRAY); break;
+      default: VGX_MARKER_LAUNCH(VGX_MARKER_LAMBERT_COLOR); break;
+    }
   }
 #undef VGX_MARKER_LAUNCH
   VGX_HIP(ctx, hipGetLastError());

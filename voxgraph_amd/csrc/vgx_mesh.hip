@@ -423,6 +423,60 @@ __global__ __launch_bounds__(kMeshThreads, 6) void sep_emit_kernel(const SepSrc*
   emit_block<VPS, true>(s, bi, base, end, m, vertices, normals, T);
 }
 
+// MeshIntegrator::updateMeshColor [recalled]: one thread per triangle of the soup, its three vertices coloured from the
+// voxel each lies in.  k: the triangle's block (first[k] <= t < first[k + 1]) by bisection; the voxel index in that block is
+// floorf((p - origin) * voxel_size_inv + 1e-6f) per axis; outside [0, VPS) on any axis (a vertex on the block's max
+// planes) the block is floorf(p * block_size_inv + 1e-6f) and the index is recomputed against its origin and clamped
+// (query_nearest's lines, vgx_query_kernel.h).  The colour word is copied when the voxel's weight >= min_weight
+// (getColorIfValid); else, or when the block is absent (voxblox would dereference null), the vertex keeps (0, 0, 0, 0).
+// A thread reads 36 contiguous bytes and writes 12; every output word has one writer.
+template <int VPS, bool PACKED>
+__global__ __launch_bounds__(256) void mesh_vertex_color_kernel(MeshSrc s, const uint32_t* __restrict__ rgba, float min_weight,
+                                                                float voxel_size_inv, float block_size, float block_size_inv,
+                                                                const int32_t* __restrict__ block_index, const int64_t* __restrict__ first,
+                                                                int32_t n_blocks, int64_t n_tris, const float* __restrict__ vertices,
+                                                                uint32_t* __restrict__ colors) {
+  constexpr int VOX = VPS * VPS * VPS;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= n_tris) return;
+  int lo = 0, hi = n_blocks;  // last k with first[k] <= t (first[0] = 0 <= t < first[n_blocks])
+  while (hi - lo > 1) {
+    const int m = (lo + hi) >> 1;
+    if (first[m] <= t) lo = m; else hi = m;
+  }
+  const int b[3] = {block_index[3 * (size_t)lo], block_index[3 * (size_t)lo + 1], block_index[3 * (size_t)lo + 2]};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    float p[3];
+    int nb[3], v[3];
+    bool inside = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      p[a] = vertices[9 * (size_t)t + 3 * c + a];
+      nb[a] = b[a];
+      const float origin = (float)b[a] * block_size;
+      v[a] = (int)floorf((p[a] - origin) * voxel_size_inv + 1e-6f);
+      inside = inside && (unsigned)v[a] < (unsigned)VPS;
+    }
+    if (!inside) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        nb[a] = (int)floorf(p[a] * block_size_inv + 1e-6f);
+        const float origin = (float)nb[a] * block_size;
+        v[a] = min(max((int)floorf((p[a] - origin) * voxel_size_inv + 1e-6f), 0), VPS - 1);
+      }
+    }
+    uint32_t word = 0u;
+    const int slot = mesh_lookup(s, nb[0], nb[1], nb[2]);
+    if (slot >= 0) {
+      const size_t at = (size_t)slot * VOX + (size_t)(v[0] + VPS * (v[1] + VPS * v[2]));
+      const float w = PACKED ? __uint_as_float((uint32_t)(s.words[at] >> 32)) : s.weight[at];
+      if (w >= min_weight) word = rgba[at];
+    }
+    colors[3 * (size_t)t + c] = word;
+  }
+}
+
 }  // namespace vgx
 
 using namespace vgx;
@@ -443,8 +497,10 @@ struct vgx_mesh_s {
   DeviceBuffer d_slots[2];     // int32 [block_cap]
   DeviceBuffer d_counts;       // int64 [block_cap]
   DeviceBuffer d_tmp;          // rocPRIM's workspace: the largest any of a call's sorts and scans asks for
-  // the separated mesh: colours (one per triangle), per-entry scratch beside the block arrays, descriptors
+  // colours: one per triangle (the separated mesh) or, per_vertex, one per soup vertex (the _colored generators); the
+  // separated mesh's per-entry scratch beside the block arrays, descriptors
   bool has_colors = false;
+  bool per_vertex = false;
   DeviceBuffer d_colors;       // u32 [color_cap] bytes r g b a
   DeviceBuffer d_efirst;       // int64 [entry_cap + 1]
   DeviceBuffer d_heads;        // int32 [entry_cap]
@@ -457,6 +513,7 @@ struct vgx_mesh_s {
     n_blocks = 0;
     n_tris = 0;
     has_colors = false;
+    per_vertex = false;
     holds_mesh = false;
   }
 };
@@ -525,9 +582,26 @@ hipError_t launch_emit(int vps, hipStream_t st, int32_t nb, const MeshSrc& s, co
   return hipGetLastError();
 }
 
-// the passes, on `st` (the caller holds the source's locks and M->mu, and has reset M's stats)
 template <bool PACKED>
-int generate(vgx_ctx ctx, hipStream_t st, const MeshSrc& s, int vps, int32_t nb, float mw, vgx_mesh M) {
+hipError_t launch_vertex_colors(int vps, hipStream_t st, const MeshSrc& s, const uint32_t* rgba, float mw, const int32_t* out_bi,
+                                const int64_t* first, int32_t nb, int64_t total, const float* vert, uint32_t* colors) {
+  // voxblox::Layer / Block constants, f32 [recalled] (vgx_submap_create)
+  const float vsi = 1.0f / s.voxel_size, bs = (float)vps * s.voxel_size, bsi = 1.0f / bs;
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  if (vps == 16)
+    hipLaunchKernelGGL((mesh_vertex_color_kernel<16, PACKED>), grid, block, 0, st, s, rgba, mw, vsi, bs, bsi, out_bi, first, nb, total, vert,
+                       colors);
+  else
+    hipLaunchKernelGGL((mesh_vertex_color_kernel<8, PACKED>), grid, block, 0, st, s, rgba, mw, vsi, bs, bsi, out_bi, first, nb, total, vert,
+                       colors);
+  return hipGetLastError();
+}
+
+// the passes, on `st` (the caller holds the source's locks and M->mu, and has reset M's stats).  rgba: the source's colour
+// words ([slot][vps^3]) for one colour per soup vertex (the streaming pass queued behind the emit, before the one wait), or
+// null: the plain mesh
+template <bool PACKED>
+int generate(vgx_ctx ctx, hipStream_t st, const MeshSrc& s, int vps, int32_t nb, float mw, vgx_mesh M, const uint32_t* rgba = nullptr) {
   if (nb == 0) return VGX_OK;
   double cells = 1.0;
   for (int a = 0; a < 3; ++a) cells *= (double)s.lut_dim[a];
@@ -563,10 +637,14 @@ int generate(vgx_ctx ctx, hipStream_t st, const MeshSrc& s, int vps, int32_t nb,
   VGX_HIP(ctx, hipStreamSynchronize(st));
   // 4. emit
   rc = ensure_tris(M, total);
+  if (rc == VGX_OK && rgba) rc = ensure_colors(M, 3 * total);
   if (rc != VGX_OK) return rc;
   if (total > 0) {
     VGX_HIP(ctx, launch_emit<PACKED>(vps, st, nb, s, M->d_slots[1].as<int32_t>(), mw, M->d_first.as<int64_t>(), M->d_vertices.as<float>(),
                                      M->d_normals.as<float>()));
+    if (rgba)
+      VGX_HIP(ctx, launch_vertex_colors<PACKED>(vps, st, s, rgba, mw, M->d_block_index.as<int32_t>(), M->d_first.as<int64_t>(), nb, total,
+                                                M->d_vertices.as<float>(), M->d_colors.as<uint32_t>()));
     VGX_HIP(ctx, hipStreamSynchronize(st));
   }
   M->n_blocks = nb;
@@ -690,6 +768,7 @@ MeshView mesh_view(vgx_mesh M) {
   v.normals = M->d_normals.as<float>();
   v.colors = M->has_colors ? M->d_colors.as<uint32_t>() : nullptr;
   v.has_colors = M->has_colors;
+  v.per_vertex = M->per_vertex;
   return v;
 }
 
@@ -716,11 +795,16 @@ int vgx_mesh_destroy(vgx_mesh M) {
   return VGX_OK;
 }
 
-int vgx_tsdf_layer_generate_mesh(vgx_tsdf_layer L, const vgx_mesh_config* cfg, vgx_mesh M) {
-  if (!L) return set_error(M ? M->ctx : nullptr, VGX_ERR_INVALID, "vgx_tsdf_layer_generate_mesh: NULL layer");
+}  // extern "C"
+
+namespace {
+
+// vgx_tsdf_layer_generate_mesh, and with colored the same passes plus the vertex-colour kernel (fn: the call's name)
+int layer_generate_mesh(vgx_tsdf_layer L, const vgx_mesh_config* cfg, vgx_mesh M, bool colored, const char* fn) {
+  if (!L) return set_error(M ? M->ctx : nullptr, VGX_ERR_INVALID, std::string(fn) + ": NULL layer");
   vgx_ctx ctx = L->ctx;
   float mw = 0.0f;
-  int rc = check_args(ctx, cfg, M, "vgx_tsdf_layer_generate_mesh", &mw);
+  int rc = check_args(ctx, cfg, M, fn, &mw);
   if (rc != VGX_OK) return rc;
   std::lock_guard<std::mutex> mesh_lk(M->mu);
   std::lock_guard<std::mutex> tsdf_lk(ctx->tsdf_mu);
@@ -741,28 +825,51 @@ int vgx_tsdf_layer_generate_mesh(vgx_tsdf_layer L, const vgx_mesh_config* cfg, v
   s.block_index = d.block_index;
   s.words = d.voxels;
   s.voxel_size = d.voxel_size;
-  rc = generate<true>(ctx, ctx->tsdf_stream, s, d.vps, nb, mw, M);
+  rc = generate<true>(ctx, ctx->tsdf_stream, s, d.vps, nb, mw, M, colored ? d.rgba : nullptr);
   M->holds_mesh = rc == VGX_OK;
+  M->has_colors = M->per_vertex = colored && rc == VGX_OK;
   return rc;
 }
 
-int vgx_submap_generate_mesh(vgx_submap sm, const vgx_mesh_config* cfg, vgx_mesh M) {
-  if (!sm) return set_error(M ? M->ctx : nullptr, VGX_ERR_INVALID, "vgx_submap_generate_mesh: NULL submap");
+int submap_generate_mesh(vgx_submap sm, const vgx_mesh_config* cfg, vgx_mesh M, bool colored, const char* fn) {
+  if (!sm) return set_error(M ? M->ctx : nullptr, VGX_ERR_INVALID, std::string(fn) + ": NULL submap");
   vgx_ctx ctx = sm->ctx;
   float mw = 0.0f;
-  int rc = check_args(ctx, cfg, M, "vgx_submap_generate_mesh", &mw);
+  int rc = check_args(ctx, cfg, M, fn, &mw);
   if (rc != VGX_OK) return rc;
   if (sm->n_blocks > 0 && (!sm->d_tsdf_distance || !sm->d_tsdf_weight))
-    return set_error(ctx, VGX_ERR_INVALID, "vgx_submap_generate_mesh: raw TSDF layer not resident (released?)");
+    return set_error(ctx, VGX_ERR_INVALID, std::string(fn) + ": raw TSDF layer not resident (released?)");
   if (sm->vps != 8 && sm->vps != 16)
-    return set_error(ctx, VGX_ERR_UNSUPPORTED, "vgx_submap_generate_mesh: voxels_per_side must be 8 or 16");
+    return set_error(ctx, VGX_ERR_UNSUPPORTED, std::string(fn) + ": voxels_per_side must be 8 or 16");
   std::lock_guard<std::mutex> mesh_lk(M->mu);
   std::lock_guard<std::mutex> reg_lk(ctx->mu);
+  if (colored && !sm->d_tsdf_rgba) return set_error(ctx, VGX_ERR_INVALID, std::string(fn) + ": the submap has no colours");
   VGX_HIP(ctx, hipSetDevice(ctx->device));
   M->reset_stats();
-  rc = generate<false>(ctx, ctx->stream, mesh_src(sm), sm->vps, sm->n_blocks, mw, M);
+  rc = generate<false>(ctx, ctx->stream, mesh_src(sm), sm->vps, sm->n_blocks, mw, M, colored ? sm->d_tsdf_rgba : nullptr);
   M->holds_mesh = rc == VGX_OK;
+  M->has_colors = M->per_vertex = colored && rc == VGX_OK;
   return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vgx_tsdf_layer_generate_mesh(vgx_tsdf_layer L, const vgx_mesh_config* cfg, vgx_mesh M) {
+  return layer_generate_mesh(L, cfg, M, false, "vgx_tsdf_layer_generate_mesh");
+}
+
+int vgx_tsdf_layer_generate_mesh_colored(vgx_tsdf_layer L, const vgx_mesh_config* cfg, vgx_mesh M) {
+  return layer_generate_mesh(L, cfg, M, true, "vgx_tsdf_layer_generate_mesh_colored");
+}
+
+int vgx_submap_generate_mesh(vgx_submap sm, const vgx_mesh_config* cfg, vgx_mesh M) {
+  return submap_generate_mesh(sm, cfg, M, false, "vgx_submap_generate_mesh");
+}
+
+int vgx_submap_generate_mesh_colored(vgx_submap sm, const vgx_mesh_config* cfg, vgx_mesh M) {
+  return submap_generate_mesh(sm, cfg, M, true, "vgx_submap_generate_mesh_colored");
 }
 
 int vgx_submaps_generate_separated_mesh(vgx_ctx ctx, int32_t n, const vgx_submap* submaps, const float* T_M_S, const uint8_t* rgba,
@@ -855,13 +962,33 @@ int vgx_mesh_has_colors(vgx_mesh M, int32_t* has) {
   return VGX_OK;
 }
 
+int vgx_mesh_color_layout(vgx_mesh M, int32_t* layout) {
+  if (!M || !layout) return set_error(M ? M->ctx : nullptr, VGX_ERR_INVALID, "vgx_mesh_color_layout: NULL argument");
+  std::lock_guard<std::mutex> lk(M->mu);
+  *layout = !M->has_colors ? VGX_MESH_COLORS_NONE : (M->per_vertex ? VGX_MESH_COLORS_PER_VERTEX : VGX_MESH_COLORS_PER_TRIANGLE);
+  return VGX_OK;
+}
+
 int vgx_mesh_download_colors(vgx_mesh M, uint8_t* rgba) {
   if (!M || !rgba) return set_error(M ? M->ctx : nullptr, VGX_ERR_INVALID, "vgx_mesh_download_colors: NULL argument");
   vgx_ctx ctx = M->ctx;
   std::lock_guard<std::mutex> lk(M->mu);
   if (!M->has_colors) return set_error(ctx, VGX_ERR_INVALID, "vgx_mesh_download_colors: the mesh has no colours");
+  if (M->per_vertex)
+    return set_error(ctx, VGX_ERR_INVALID, "vgx_mesh_download_colors: one colour per vertex (vgx_mesh_download_vertex_colors)");
   VGX_HIP(ctx, hipSetDevice(ctx->device));
   if (M->n_tris > 0) VGX_HIP(ctx, hipMemcpy(rgba, M->d_colors.p, (size_t)M->n_tris * 4, hipMemcpyDeviceToHost));
+  return VGX_OK;
+}
+
+int vgx_mesh_download_vertex_colors(vgx_mesh M, uint8_t* rgba) {
+  if (!M || !rgba) return set_error(M ? M->ctx : nullptr, VGX_ERR_INVALID, "vgx_mesh_download_vertex_colors: NULL argument");
+  vgx_ctx ctx = M->ctx;
+  std::lock_guard<std::mutex> lk(M->mu);
+  if (!M->has_colors || !M->per_vertex)
+    return set_error(ctx, VGX_ERR_INVALID, "vgx_mesh_download_vertex_colors: the mesh has no per-vertex colours");
+  VGX_HIP(ctx, hipSetDevice(ctx->device));
+  if (M->n_tris > 0) VGX_HIP(ctx, hipMemcpy(rgba, M->d_colors.p, (size_t)M->n_tris * 12, hipMemcpyDeviceToHost));
   return VGX_OK;
 }
 
@@ -906,10 +1033,14 @@ int vgx_mesh_write_ply(vgx_mesh M, const char* path) {
   std::vector<float> v((size_t)nt * 9), n((size_t)nt * 3);
   rc = vgx_mesh_download(M, nullptr, nullptr, v.data(), n.data());
   if (rc != VGX_OK) return rc;
-  int32_t colored = 0;
+  int32_t colored = 0;  // VGX_MESH_COLORS_*
   std::vector<uint8_t> rgba;
-  rc = vgx_mesh_has_colors(M, &colored);
-  if (rc == VGX_OK && colored) {
+  rc = vgx_mesh_color_layout(M, &colored);
+  const size_t cstride = colored == VGX_MESH_COLORS_PER_VERTEX ? 4 : 0;  // bytes from one corner's colour to the next
+  if (rc == VGX_OK && colored == VGX_MESH_COLORS_PER_VERTEX) {
+    rgba.resize((size_t)nt * 12);
+    rc = vgx_mesh_download_vertex_colors(M, rgba.data());
+  } else if (rc == VGX_OK && colored) {
     rgba.resize((size_t)nt * 4);
     rc = vgx_mesh_download_colors(M, rgba.data());
   }
@@ -934,7 +1065,7 @@ int vgx_mesh_write_ply(vgx_mesh M, const char* path) {
         unsigned char* r = &frec[((size_t)(t - t0) * 3 + q) * 28];
         std::memcpy(r, &v[(size_t)t * 9 + 3 * q], 12);
         std::memcpy(r + 12, &n[(size_t)t * 3], 12);
-        std::memcpy(r + 24, &rgba[(size_t)t * 4], 4);
+        std::memcpy(r + 24, &rgba[(size_t)t * (4 + 2 * cstride) + q * cstride], 4);
       }
     ok = std::fwrite(frec.data(), 1, frec.size(), f) == frec.size();
   }

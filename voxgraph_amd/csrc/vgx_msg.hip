@@ -27,11 +27,11 @@
 
 namespace vgx {
 
-enum { kMsgSrcPacked = 0, kMsgSrcTsdf = 1, kMsgSrcEsdf = 2 };
+enum { kMsgSrcPacked = 0, kMsgSrcTsdf = 1, kMsgSrcEsdf = 2, kMsgSrcTsdfColor = 3 };  // (3: a submap with colours)
 
 struct MsgSrc {
   const unsigned long long* words;  // packed: {distance (lo), weight (hi)}
-  const uint32_t* rgba;             // packed: bytes r g b a
+  const uint32_t* rgba;             // packed, coloured submap TSDF: bytes r g b a
   const float* dist;                // submap TSDF / ESDF
   const void* seen;                 // submap TSDF: f32 weight; ESDF: u8 observed
   const int32_t* live_blocks;       // packed: the layer's allocation counter (device); null: every block of the grid
@@ -66,6 +66,13 @@ __global__ __launch_bounds__(256) void msg_serialize_kernel(MsgSrc s, size_t qua
     out[3 * q + 0] = make_uint4(d.x, w.x, 0u, d.y);
     out[3 * q + 1] = make_uint4(w.y, 0u, d.z, w.z);
     out[3 * q + 2] = make_uint4(0u, d.w, w.w, 0u);
+  } else if (SRC == kMsgSrcTsdfColor) {
+    const uint4 d = reinterpret_cast<const uint4*>(s.dist)[q];
+    const uint4 w = reinterpret_cast<const uint4*>(s.seen)[q];
+    const uint4 c = reinterpret_cast<const uint4*>(s.rgba)[q];
+    out[3 * q + 0] = make_uint4(d.x, w.x, msg_colour_word(c.x), d.y);
+    out[3 * q + 1] = make_uint4(w.y, msg_colour_word(c.y), d.z, w.z);
+    out[3 * q + 2] = make_uint4(msg_colour_word(c.z), d.w, w.w, msg_colour_word(c.w));
   } else {
     const uint4 d = reinterpret_cast<const uint4*>(s.dist)[q];
     const uint32_t o = reinterpret_cast<const uint32_t*>(s.seen)[q];
@@ -212,6 +219,7 @@ int msg_serialize(vgx_ctx ctx, hipStream_t st, int src, const MsgSrc& s, const i
     VGX_HIP(ctx, hipMemcpyAsync(M->d_index.p, d_block_index, (size_t)nb * 12, hipMemcpyDeviceToDevice, st));
     if (src == kMsgSrcPacked) hipLaunchKernelGGL(msg_serialize_kernel<kMsgSrcPacked>, dim3(grid), dim3(256), 0, st, s, quads, vox / 4, out);
     else if (src == kMsgSrcTsdf) hipLaunchKernelGGL(msg_serialize_kernel<kMsgSrcTsdf>, dim3(grid), dim3(256), 0, st, s, quads, vox / 4, out);
+    else if (src == kMsgSrcTsdfColor) hipLaunchKernelGGL(msg_serialize_kernel<kMsgSrcTsdfColor>, dim3(grid), dim3(256), 0, st, s, quads, vox / 4, out);
     else hipLaunchKernelGGL(msg_serialize_kernel<kMsgSrcEsdf>, dim3(grid), dim3(256), 0, st, s, quads, vox / 4, out);
     VGX_HIP(ctx, hipGetLastError());
     VGX_HIP(ctx, hipStreamSynchronize(st));
@@ -398,7 +406,8 @@ int vgx_submap_serialize_layer(vgx_submap sm, int32_t layer, vgx_map_msg M) {
   MsgSrc s{};
   s.dist = tsdf ? sm->d_tsdf_distance : sm->d_esdf_distance;
   s.seen = tsdf ? (const void*)sm->d_tsdf_weight : (const void*)sm->d_esdf_observed;
-  return msg_serialize(ctx, ctx->stream, tsdf ? kMsgSrcTsdf : kMsgSrcEsdf, s, sm->d_block_index, sm->n_blocks, sm->vps, sm->voxel_size, M);
+  s.rgba = tsdf ? sm->d_tsdf_rgba : nullptr;
+  return msg_serialize(ctx, ctx->stream, tsdf ? (s.rgba ? kMsgSrcTsdfColor : kMsgSrcTsdf) : kMsgSrcEsdf, s, sm->d_block_index, sm->n_blocks, sm->vps, sm->voxel_size, M);
 }
 
 int vgx_submap_surface_msg(vgx_submap sm, int32_t point_type, const float* T, vgx_map_msg M) {

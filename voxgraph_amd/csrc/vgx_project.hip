@@ -37,6 +37,7 @@ struct alignas(16) ProjectSrc {
   const uint8_t* has_data;
   float q_ls[4], t_ls[3];  // T_L_S {w, x, y, z}, t: source corners into the layer
   float q_sl[4], t_sl[3];  // T_S_L = T_L_S.inverse(): layer voxel centres into the source
+  const uint32_t* tsdf_rgba;  // the submap's colours, or null (read by the COLOR instantiations only)
 };
 
 // Eigen's _transformVector plus translation (the oracle's quat_rotate, then + t)
@@ -147,7 +148,11 @@ __global__ __launch_bounds__(256) void segment_heads_kernel(const unsigned long 
 // live -- the unrolled gathers and divisions of 16 voxels -- one wave per SIMD), 2 x 256 at vps = 8.
 // COPY (transformLayer): the layer is empty and each target has one candidate submap; an interpolated voxel is stored as
 // {d, w}, every other voxel of a kept block as (0, 0) -- not the merge, whose (d*w + 0*0) / w need not round back to d.
-template <int VPS, int PER, bool COPY>
+// COLOR (launched only when a submap of the call has colours): the voxels' rgba words ride along -- a coloured submap's
+// interpolated colour (tsdf_color_interp, a second pass over the 8 neighbours) is blended in with the pre-merge weights
+// wherever the merge updates the voxel; a colourless submap leaves rgba alone.  The colourless instantiations are the
+// kernels they were: every colour line is behind `if (COLOR)`.
+template <int VPS, int PER, bool COPY, bool COLOR>
 __global__ __launch_bounds__(VPS * VPS * VPS / PER) void project_merge_kernel(const unsigned long long* __restrict__ keys,
                                                                               const uint32_t* __restrict__ seg_start, uint32_t n_pairs,
                                                                               const ProjectSrc* __restrict__ src, TsdfLayerDev L,
@@ -168,16 +173,20 @@ __global__ __launch_bounds__(VPS * VPS * VPS / PER) void project_merge_kernel(co
   }
   int slot = L.lut[rx + L.lut_dim[0] * (ry + L.lut_dim[1] * rz)];
   float d[PER], w[PER];
+  uint32_t col[COLOR ? PER : 1];
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
     d[k] = 0.0f;
     w[k] = 0.0f;
+    if (COLOR) col[k] = 0u;
     if (slot >= 0) {
       const unsigned long long v = L.voxels[(size_t)slot * VOX + threadIdx.x + T * k];
       d[k] = __uint_as_float((uint32_t)v);
       w[k] = __uint_as_float((uint32_t)(v >> 32));
+      if (COLOR && !COPY) col[k] = L.rgba[(size_t)slot * VOX + threadIdx.x + T * k];
     }
   }
+  bool col_touched = false;  // COLOR: a coloured submap contributed (uniform across the workgroup)
   const float vs = L.voxel_size, bs = (float)VPS * L.voxel_size;
   const float ox = (float)bx * bs, oy = (float)by * bs, oz = (float)bz * bs;
   const unsigned long long pos_mask = (1ull << pos_bits) - 1ull;
@@ -189,6 +198,8 @@ __global__ __launch_bounds__(VPS * VPS * VPS / PER) void project_merge_kernel(co
     prev = pos;
     const ProjectSrc& s = src[pos];
     float sd[PER], sw[PER];
+    uint32_t sc[COLOR ? PER : 1];
+    const uint32_t* const src_rgba = COLOR ? s.tsdf_rgba : nullptr;
     unsigned ok = 0;
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
@@ -200,16 +211,20 @@ __global__ __launch_bounds__(VPS * VPS * VPS / PER) void project_merge_kernel(co
       rigid_apply(s.q_sl, s.t_sl, c, p);
       sd[k] = 0.0f;
       sw[k] = 0.0f;
-      if (tsdf_interp<VPS>(s, p, sd[k], sw[k])) ok |= 1u << k;
+      const bool hit = tsdf_interp<VPS>(s, p, sd[k], sw[k]);
+      if (hit) ok |= 1u << k;
+      if (COLOR) sc[k] = (hit && src_rgba) ? tsdf_color_interp<VPS>(s, src_rgba, p) : 0u;  // (else the default voxel's colour)
     }
     if (__syncthreads_or(ok != 0)) {
       contributed = true;
+      if (COLOR && src_rgba) col_touched = true;
       if (COPY) {
 #pragma unroll
         for (int k = 0; k < PER; ++k) {
           const bool hit = (ok >> k) & 1u;
           d[k] = hit ? sd[k] : 0.0f;
           w[k] = hit ? sw[k] : 0.0f;
+          if (COLOR) col[k] = sc[k];
         }
         continue;
       }
@@ -220,6 +235,7 @@ __global__ __launch_bounds__(VPS * VPS * VPS / PER) void project_merge_kernel(co
         const float da = hit ? sd[k] : 0.0f, wa = hit ? sw[k] : 0.0f;
         const float wn = wa + w[k];
         if (wn > 0.0f) {
+          if (COLOR && src_rgba) col[k] = blended_color(col[k], sc[k], w[k], wa);  // (the pre-merge weights)
           d[k] = (da * wa + d[k] * w[k]) / wn;
           w[k] = wn;
         }
@@ -238,6 +254,10 @@ __global__ __launch_bounds__(VPS * VPS * VPS / PER) void project_merge_kernel(co
   }
 #pragma unroll
   for (int k = 0; k < PER; ++k) L.voxels[(size_t)slot * VOX + threadIdx.x + T * k] = pack_voxel(d[k], w[k]);
+  if (COLOR && col_touched) {  // (a block only colourless submaps reached keeps its bytes)
+#pragma unroll
+    for (int k = 0; k < PER; ++k) L.rgba[(size_t)slot * VOX + threadIdx.x + T * k] = col[k];
+  }
 }
 
 }  // namespace vgx
@@ -309,7 +329,7 @@ int project_submaps(vgx_tsdf_layer L, int32_t n, const vgx_submap* submaps, cons
   std::vector<ProjectSrc> src((size_t)n);
   std::vector<int64_t> src_first((size_t)n + 1, 0);
   int64_t box_lo[3] = {0, 0, 0}, box_hi[3] = {-1, -1, -1};
-  bool any_box = false;
+  bool any_box = false, any_colors = false;
   for (int32_t i = 0; i < n; ++i) {
     vgx_submap sm = submaps[i];
     if (sm->n_blocks > 0 && !sm->d_block_has_data) {
@@ -339,6 +359,8 @@ int project_submaps(vgx_tsdf_layer L, int32_t n, const vgx_submap* submaps, cons
     s.block_size_inv = sm->block_size_inv;
     s.block_index = sm->d_block_index;
     s.has_data = sm->d_block_has_data;
+    s.tsdf_rgba = sm->d_tsdf_rgba;
+    any_colors = any_colors || sm->d_tsdf_rgba != nullptr;
     const float* T = T_L_S + 7 * (size_t)i;
     for (int k = 0; k < 4; ++k) s.q_ls[k] = T[k];
     for (int k = 0; k < 3; ++k) s.t_ls[k] = T[4 + k];
@@ -464,8 +486,12 @@ int project_submaps(vgx_tsdf_layer L, int32_t n, const vgx_submap* submaps, cons
   int rc = tsdf_reserve_blocks(L, blo, hi3, (int64_t)n_seg);
   if (rc != VGX_OK) return rc;
   if (n_seg > 0) {
-    auto kernel = vps == 16 ? (copy ? project_merge_kernel<16, 4, true> : project_merge_kernel<16, 4, false>)
-                            : (copy ? project_merge_kernel<8, 2, true> : project_merge_kernel<8, 2, false>);
+    // the colour variant only when a submap of the call has colours
+    auto kernel = vps == 16 ? (copy ? project_merge_kernel<16, 4, true, false> : project_merge_kernel<16, 4, false, false>)
+                            : (copy ? project_merge_kernel<8, 2, true, false> : project_merge_kernel<8, 2, false, false>);
+    if (any_colors)
+      kernel = vps == 16 ? (copy ? project_merge_kernel<16, 4, true, true> : project_merge_kernel<16, 4, false, true>)
+                         : (copy ? project_merge_kernel<8, 2, true, true> : project_merge_kernel<8, 2, false, true>);
     hipLaunchKernelGGL(kernel, dim3(n_seg), dim3(vps == 16 ? 1024 : 256), 0, st, d_sorted.as<unsigned long long>(),
                        d_seg.as<uint32_t>(), n_pairs, d_src.as<ProjectSrc>(), L->dev, box_lo3, box_dim3, pos_bits);
     VGX_HIP(ctx, hipGetLastError());

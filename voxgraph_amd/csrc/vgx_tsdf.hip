@@ -783,7 +783,11 @@ int vgx_tsdf_layer_upload(vgx_tsdf_layer L, int32_t n_blocks, const int32_t* blo
   return VGX_OK;
 }
 
-int vgx_submap_from_tsdf_layer(vgx_ctx ctx, vgx_tsdf_layer L, int32_t submap_id, vgx_submap* out) {
+// vgx_submap_from_tsdf_layer, and with keep_colors vgx_submap_from_tsdf_layer_colored: the layer's rgba words copied device
+// to device behind the voxels, on the same stream and under the same locks (slot order is the submap's block order)
+// (fn: the call's name, for its messages)
+static int submap_from_tsdf_layer(vgx_ctx ctx, vgx_tsdf_layer L, int32_t submap_id, bool keep_colors, const char* fn,
+                                  vgx_submap* out) {
   if (!ctx || !L || !out || L->ctx != ctx) return VGX_ERR_INVALID;
   *out = nullptr;
   int32_t nb = 0;
@@ -791,7 +795,7 @@ int vgx_submap_from_tsdf_layer(vgx_ctx ctx, vgx_tsdf_layer L, int32_t submap_id,
   if (rc != VGX_OK) return rc;
   std::lock_guard<std::mutex> lk(ctx->tsdf_mu);
   vgx_submap sm = new (std::nothrow) vgx_submap_s();
-  if (!sm) return set_error(ctx, VGX_ERR_NOMEM, "vgx_submap_from_tsdf_layer: out of host memory");
+  if (!sm) return set_error(ctx, VGX_ERR_NOMEM, std::string(fn) + ": out of host memory");
   const TsdfLayerDev& d = L->dev;
   sm->ctx = ctx;
   sm->id = submap_id;
@@ -803,14 +807,16 @@ int vgx_submap_from_tsdf_layer(vgx_ctx ctx, vgx_tsdf_layer L, int32_t submap_id,
   sm->block_size_inv = 1.0f / sm->block_size;
   sm->block_index.resize(3 * (size_t)nb);
   if (nb > 0 && hipMemcpy(sm->block_index.data(), d.block_index, (size_t)nb * 12, hipMemcpyDeviceToHost) != hipSuccess)
-    rc = set_error(ctx, VGX_ERR_HIP, "vgx_submap_from_tsdf_layer: block index download failed");
+    rc = set_error(ctx, VGX_ERR_HIP, std::string(fn) + ": block index download failed");
   if (rc == VGX_OK) rc = build_block_lut(sm);
   if (rc == VGX_OK && nb > 0) {
     const size_t nvox = (size_t)nb * d.vps * d.vps * d.vps;
     if (hipMalloc(&sm->d_block_index, (size_t)nb * 12) != hipSuccess ||
         hipMalloc(&sm->d_tsdf_distance, nvox * sizeof(float)) != hipSuccess ||
-        hipMalloc(&sm->d_tsdf_weight, nvox * sizeof(float)) != hipSuccess) {
-      rc = set_error(ctx, VGX_ERR_NOMEM, "vgx_submap_from_tsdf_layer: device allocation failed");
+        hipMalloc(&sm->d_tsdf_weight, nvox * sizeof(float)) != hipSuccess ||
+        (keep_colors && hipMalloc(&sm->d_tsdf_rgba, nvox * sizeof(uint32_t)) != hipSuccess)) {
+      (void)hipGetLastError();  // (clear the sticky out-of-memory status, for both calls: alloc_error does the same)
+      rc = set_error(ctx, VGX_ERR_NOMEM, std::string(fn) + ": device allocation failed");
     } else {
       hipError_t e = hipMemcpyAsync(sm->d_block_index, d.block_index, (size_t)nb * 12,
                                     hipMemcpyDeviceToDevice, ctx->tsdf_stream);
@@ -819,18 +825,25 @@ int vgx_submap_from_tsdf_layer(vgx_ctx ctx, vgx_tsdf_layer L, int32_t submap_id,
                            ctx->tsdf_stream, d.voxels, nvox, sm->d_tsdf_distance, sm->d_tsdf_weight);
         e = hipGetLastError();
       }
+      if (e == hipSuccess && keep_colors)
+        e = hipMemcpyAsync(sm->d_tsdf_rgba, d.rgba, nvox * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->tsdf_stream);
       // finishSubmap(): the TSDF side hands the layer's voxels to the registration side -- the submap's own kernels run
       // on the context's registration stream, behind an event on the TSDF stream
       if (e == hipSuccess) e = hipEventRecord(ctx->ev_handover, ctx->tsdf_stream);
       if (e != hipSuccess)
-        rc = set_error(ctx, VGX_ERR_HIP, std::string("vgx_submap_from_tsdf_layer: ") + hipGetErrorString(e));
+        rc = set_error(ctx, VGX_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
     }
     if (rc == VGX_OK) {
       std::lock_guard<std::mutex> reg(ctx->mu);  // (lock order: tsdf_mu, then mu)
       if (hipStreamWaitEvent(ctx->stream, ctx->ev_handover, 0) != hipSuccess)
-        rc = set_error(ctx, VGX_ERR_HIP, "vgx_submap_from_tsdf_layer: hipStreamWaitEvent failed");
+        rc = set_error(ctx, VGX_ERR_HIP, std::string(fn) + ": hipStreamWaitEvent failed");
       if (rc == VGX_OK) rc = launch_brickify(sm, 0);
     }
+  }
+  // (an empty layer: one word, so that the submap still reports colours)
+  if (rc == VGX_OK && nb == 0 && keep_colors && hipMalloc(&sm->d_tsdf_rgba, sizeof(uint32_t)) != hipSuccess) {
+    (void)hipGetLastError();
+    rc = set_error(ctx, VGX_ERR_NOMEM, std::string(fn) + ": device allocation failed");
   }
   if (rc != VGX_OK) {
     vgx_submap_destroy(sm);
@@ -838,6 +851,14 @@ int vgx_submap_from_tsdf_layer(vgx_ctx ctx, vgx_tsdf_layer L, int32_t submap_id,
   }
   *out = sm;
   return VGX_OK;
+}
+
+int vgx_submap_from_tsdf_layer(vgx_ctx ctx, vgx_tsdf_layer L, int32_t submap_id, vgx_submap* out) {
+  return submap_from_tsdf_layer(ctx, L, submap_id, false, "vgx_submap_from_tsdf_layer", out);
+}
+
+int vgx_submap_from_tsdf_layer_colored(vgx_ctx ctx, vgx_tsdf_layer L, int32_t submap_id, vgx_submap* out) {
+  return submap_from_tsdf_layer(ctx, L, submap_id, true, "vgx_submap_from_tsdf_layer_colored", out);
 }
 
 int vgx_tsdf_integrator_create(vgx_ctx ctx, const vgx_tsdf_config* cfg, vgx_tsdf_layer layer,
