@@ -247,7 +247,9 @@ VGX_API int vgx_submap_release_raw_layers(vgx_submap submap);
 
 /* ---- REG: one registration constraint ---------------------------------- */
 /* RegistrationCostFunction::Config (registration_cost_function.h:17-41).
- * jacobian_evaluation_method is always analytic; visualize_* are ignored. */
+ * jacobian_evaluation_method is always analytic.  visualize_residuals / visualize_gradients are the two want_* arguments
+ * of vgx_reg_evaluate_visuals ("Cost-function visuals" below); visualize_transforms_ needs no device: the C++ adapter
+ * hands T_mission__reading to its sink (voxgraph_amd/cpp/gpu_cost_function_visuals.h). */
 typedef struct vgx_reg_config {
   int32_t registration_point_type; /* VGX_POINTS_*, default ISOSURFACE (h:20) */
   float sampling_ratio;            /* -1 disables sampling (h:28)             */
@@ -294,6 +296,59 @@ VGX_API int vgx_reg_evaluate_device_f32(vgx_reg reg, const double ref_pose[4],
                                         const double read_pose[4],
                                         void* d_residuals, void* d_jac_ref,
                                         void* d_jac_read);
+
+/* ---- REG: cost-function visuals ------------------------------------------ */
+/* Cost-function visuals: what RegistrationCostFunction::Evaluate hands to CostFunctionVisuals while it evaluates
+ * (registration_cost_function.cpp:169-176, 244-252, 293-295, cited as RCF; cost_function_visuals.cpp:43-101, CFV) -- the
+ * residual cloud (pcl::PointCloud<pcl::PointXYZI>, topic cost_residuals) and the two Jacobian markers (cost_jacobians)
+ * that registration_test_bench shows while a registration converges.  vgx_reg_evaluate_visuals is vgx_reg_evaluate plus
+ * the visuals of that same evaluation, left in a reusable handle.
+ * Rules (what the kernel, vgx_reg.hip, and the restatement, tests/cost_visuals_ref.py, both follow):
+ *   rows        row i runs over the registration points, or in sampling mode over this evaluation's draws in draw
+ *               order with weight 1 (RCF:113-122); n = num_residuals.
+ *   p_read      T_reading__reference * p_ref in f32: the point the residual is interpolated at.
+ *   p_m         T_mission__reading * p_read in f32, minkindr's point transform (v + w uv + u x uv with uv = 2 u x v,
+ *               then + t), T_mission__reading = exp of the reading pose narrowed to f32 (RCF:80-88).
+ *   r_u, j      the UNSCALED f64 residual (RCF:161-166; w * no_correspondence_cost without a correspondence) and the
+ *               unscaled f32 pResidual_pParamRead.head<3>() (RCF:249; zero without a correspondence).
+ *   factor      num_residuals / summed_weight (RCF:274); 1 in sampling mode.
+ *   cloud       one 32-byte pcl::PointXYZI record per row, in row order, the layout of vgx_submap_surface_msg: x y z
+ *               f32 of p_m at bytes 0, 4, 8, 1.0f at byte 12, intensity at byte 16, bytes 20..31 zero.
+ *               intensity = (float)((double)(float)r_u * factor): CFV:49 narrows, CFV:75 multiplies a float by a double
+ *               in f64 and rounds once.
+ *   gradients   filled iff want_gradients and at least one of jac_ref / jac_read is given (RCF:179: jacobians !=
+ *               nullptr).  o = (double)p_m; t = (double)j * (factor * 0.05) + o, in f64: the product factor * 0.05
+ *               first, then one multiply, then one add, never contracted (CFV:82-89).
+ *               arrow_points [2n][3] f64 = o0 t0 o1 t1 .. (the LINE_LIST marker), origin_points [n][3] f64 = o0 o1 ..
+ *               (the SPHERE_LIST marker).  The fixed marker fields (CFV:13-40) are host constants of the C++ adapter.
+ *   false       when the summed weight is 0 Evaluate returns false before anything is published (RCF:273): VGX_EVALUATE_
+ *               FALSE, and the handle holds 0 points.  The reference does NOT reset its accumulators on that path, so
+ *               its next publication carries the stale points too; that is its bug and is not reproduced.
+ * residuals / jac_ref / jac_read are bit for bit what vgx_reg_evaluate returns at the same poses; in sampling mode the
+ * call consumes exactly one evaluation's engine outputs and the visuals show that evaluation's draws.  One more kernel
+ * on the evaluation slot's stream (no dead-tile shortcut: a tile outside the reading grid still has positions and the
+ * no-correspondence intensity), no host synchronisation beyond vgx_reg_evaluate's own.  Per row the kernel writes 32 B
+ * (cloud) + 48 B + 24 B (gradients) in 16-byte stores.
+ * Refused with VGX_ERR_INVALID before anything is launched: a NULL visuals handle, one of another context (the handle
+ * keeps what it held), residuals == NULL, registration points replaced since the cost function was created.  The handle
+ * is reused from call to call: its device buffers grow on demand; one call at a time per handle.  want_residual_cloud
+ * == 0: 0 cloud points.  Out of scope: the batched entry points, ROS / PCL types, the box, pose-history and pose-graph-
+ * edge markers. */
+typedef struct vgx_reg_visuals_s* vgx_reg_visuals;
+VGX_API int vgx_reg_visuals_create(vgx_ctx ctx, vgx_reg_visuals* out);
+VGX_API int vgx_reg_visuals_destroy(vgx_reg_visuals visuals);
+VGX_API int vgx_reg_evaluate_visuals(vgx_reg reg, const double ref_pose[4], const double read_pose[4],
+                                     double* residuals, double* jac_ref, double* jac_read,
+                                     int32_t want_residual_cloud, int32_t want_gradients, vgx_reg_visuals visuals);
+/* of the last evaluation into the handle; n_jacobians is 0 when no Jacobians were asked for; either may be NULL */
+VGX_API int vgx_reg_visuals_stats(vgx_reg_visuals visuals, int64_t* n_residual_points, int64_t* n_jacobians);
+/* cloud_bytes [32 n_residual_points], arrow_points [2 n_jacobians][3] f64, origin_points [n_jacobians][3] f64, the
+ * factor of that evaluation (0 when the handle holds nothing); any argument may be NULL */
+VGX_API int vgx_reg_visuals_download(vgx_reg_visuals visuals, void* cloud_bytes, double* arrow_points,
+                                     double* origin_points, double* factor);
+/* the device arrays held now (NULL for an array with 0 rows); valid until the next evaluation into the handle or destroy */
+VGX_API int vgx_reg_visuals_device_pointers(vgx_reg_visuals visuals, const void** cloud, const double** arrow_points,
+                                            const double** origin_points);
 
 /* ---- REG: all constraints of a pose graph in one launch ----------------- */
 /* Mirrors one pass of the Ceres evaluator over every registration residual

@@ -184,6 +184,12 @@ SIGNATURES = {
     "vgx_reg_num_residuals": (C.c_int64, [vp]),
     "vgx_reg_evaluate": (C.c_int, [vp, f64p, f64p, f64p, f64p, f64p]),
     "vgx_reg_evaluate_device_f32": (C.c_int, [vp, f64p, f64p, vp, vp, vp]),
+    "vgx_reg_visuals_create": (C.c_int, [vp, C.POINTER(vp)]),
+    "vgx_reg_visuals_destroy": (C.c_int, [vp]),
+    "vgx_reg_evaluate_visuals": (C.c_int, [vp, f64p, f64p, f64p, f64p, f64p, C.c_int32, C.c_int32, vp]),
+    "vgx_reg_visuals_stats": (C.c_int, [vp, i64p, i64p]),
+    "vgx_reg_visuals_download": (C.c_int, [vp, vp, f64p, f64p, f64p]),
+    "vgx_reg_visuals_device_pointers": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
     "vgx_reg_batch_create": (C.c_int, [vp, C.c_int32, C.POINTER(vp), i32p, i32p, C.c_int32,
                                        C.POINTER(vp)]),
     "vgx_reg_batch_destroy": (C.c_int, [vp]),
@@ -772,6 +778,22 @@ class RegistrationCostFunction:
             _ptr(je, f64p)))
         return rc == OK
 
+    def evaluate_visuals(self, parameters, residuals, jacobians, visuals, want_residual_cloud=True, want_gradients=True):
+        """Evaluate plus the cost-function visuals of that same evaluation (vgx_reg_evaluate_visuals): the rows come
+        back as in Evaluate, `visuals` (a RegVisuals) is left holding the residual cloud and -- when Jacobians were
+        asked for -- the Jacobian markers.  `visuals` may be None only to see the call refused."""
+        ref = _f64(parameters[0])
+        read = _f64(parameters[1])
+        jr = je = None
+        if jacobians is not None:
+            jr, je = jacobians[0], jacobians[1]
+        for a in (residuals, jr, je):
+            assert a is None or (a.dtype == np.float64 and a.flags.c_contiguous)
+        rc = self.ctx.check(self.ctx.lib.vgx_reg_evaluate_visuals(
+            self.h, _ptr(ref, f64p), _ptr(read, f64p), _ptr(residuals, f64p), _ptr(jr, f64p), _ptr(je, f64p),
+            1 if want_residual_cloud else 0, 1 if want_gradients else 0, visuals.h if visuals is not None else None))
+        return rc == OK
+
     def evaluate_device_f32(self, ref_pose, read_pose, d_residuals, d_jac_ref, d_jac_read):
         """Device pointers (ints); asynchronous on the context's stream."""
         rc = self.ctx.check(self.ctx.lib.vgx_reg_evaluate_device_f32(
@@ -782,6 +804,48 @@ class RegistrationCostFunction:
     def destroy(self):
         if self.h:
             self.ctx.lib.vgx_reg_destroy(self.h)
+            self.h = None
+
+
+Registration = RegistrationCostFunction
+
+
+class RegVisuals:
+    """The cost-function visuals of one evaluation on the GPU (vgx_reg_visuals): the residual cloud as 32-byte
+    pcl::PointXYZI records and the Jacobian markers' points; reused from call to call."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        h = vp()
+        ctx.check(ctx.lib.vgx_reg_visuals_create(ctx.h, C.byref(h)))
+        self.h = h
+
+    def stats(self):
+        """(residual points, Jacobians) of the last evaluation into this handle"""
+        n, m = C.c_int64(), C.c_int64()
+        self.ctx.check(self.ctx.lib.vgx_reg_visuals_stats(self.h, C.byref(n), C.byref(m)))
+        return n.value, m.value
+
+    def download(self):
+        """(cloud bytes [n][32] u8, arrow points [2m][3] f64, origin points [m][3] f64, factor)"""
+        n, m = self.stats()
+        cloud = np.zeros((n, 32), np.uint8)
+        arrows = np.zeros((2 * m, 3), np.float64)
+        origins = np.zeros((m, 3), np.float64)
+        factor = C.c_double()
+        self.ctx.check(self.ctx.lib.vgx_reg_visuals_download(self.h, cloud.ctypes.data_as(vp), _ptr(arrows, f64p),
+                                                             _ptr(origins, f64p), C.byref(factor)))
+        return cloud, arrows, origins, factor.value
+
+    def device_pointers(self):
+        """(cloud, arrow points, origin points) device addresses as ints (None for an array with 0 rows)"""
+        p = [vp(), vp(), vp()]
+        self.ctx.check(self.ctx.lib.vgx_reg_visuals_device_pointers(self.h, C.byref(p[0]), C.byref(p[1]), C.byref(p[2])))
+        return tuple(x.value for x in p)
+
+    def destroy(self):
+        if self.h:
+            self.ctx.lib.vgx_reg_visuals_destroy(self.h)
             self.h = None
 
 

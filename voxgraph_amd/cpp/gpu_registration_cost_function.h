@@ -17,9 +17,11 @@
 
 #include <ceres/ceres.h>
 
+#include <memory>
 #include <stdexcept>
 #include <string>
 
+#include "gpu_cost_function_visuals.h"
 #include "voxgraph_amd.h"
 
 namespace voxgraph_amd {
@@ -33,12 +35,19 @@ class GpuRegistrationCostFunction : public ceres::CostFunction {
     float sampling_ratio = -1;
     double no_correspondence_cost = 0;
     bool use_esdf_distance = true;
-    // visualize_* flags of the reference are debug-only and ignored on the GPU path
+    // the cost-function visuals (registration_cost_function.h:36-40), all off by default as in the reference: they
+    // go to the sink given to the constructor (gpu_cost_function_visuals.h); without a sink they do nothing
+    bool visualize_residuals = false;
+    bool visualize_gradients = false;
+    bool visualize_transforms_ = false;
   };
 
   GpuRegistrationCostFunction(vgx_ctx ctx, vgx_submap reference_submap,
-                              vgx_submap reading_submap, const Config& config)
-      : ctx_(ctx) {
+                              vgx_submap reading_submap, const Config& config,
+                              CostFunctionVisualsSink* visuals_sink = nullptr)
+      : ctx_(ctx), config_(config), sink_(visuals_sink) {
+    if (sink_ && (config.visualize_residuals || config.visualize_gradients))
+      visuals_.reset(new GpuCostFunctionVisuals(ctx));
     vgx_reg_config cfg;
     vgx_reg_config_default(&cfg);
     cfg.registration_point_type = config.registration_point_type;
@@ -67,10 +76,21 @@ class GpuRegistrationCostFunction : public ceres::CostFunction {
                 double** jacobians) const override {
     double* jac_ref = jacobians ? jacobians[0] : nullptr;
     double* jac_read = jacobians ? jacobians[1] : nullptr;
-    const int rc = vgx_reg_evaluate(reg_, parameters[0], parameters[1], residuals, jac_ref, jac_read);
-    if (rc == VGX_OK) return true;
-    if (rc == VGX_EVALUATE_FALSE) return false;  // summed_reference_weight == 0 (.cpp:273)
-    throw std::runtime_error(std::string("vgx_reg_evaluate: ") + vgx_last_error(ctx_));
+    // .cpp:102-106: the TF of the reading submap's pose, before the points are visited
+    if (sink_ && config_.visualize_transforms_) sink_->OnTransform(MissionReadingTransform(parameters[1]));
+    if (!visuals_) {  // no visuals asked for: the plain evaluation, exactly as without the flags
+      const int rc = vgx_reg_evaluate(reg_, parameters[0], parameters[1], residuals, jac_ref, jac_read);
+      if (rc == VGX_OK) return true;
+      if (rc == VGX_EVALUATE_FALSE) return false;  // summed_reference_weight == 0 (.cpp:273)
+      throw std::runtime_error(std::string("vgx_reg_evaluate: ") + vgx_last_error(ctx_));
+    }
+    const int rc = vgx_reg_evaluate_visuals(reg_, parameters[0], parameters[1], residuals, jac_ref, jac_read,
+                                            config_.visualize_residuals ? 1 : 0, config_.visualize_gradients ? 1 : 0,
+                                            visuals_->handle());
+    if (rc == VGX_EVALUATE_FALSE) return false;  // nothing is published (.cpp:273 returns before .cpp:294)
+    if (rc != VGX_OK) throw std::runtime_error(std::string("vgx_reg_evaluate_visuals: ") + vgx_last_error(ctx_));
+    visuals_->Publish(sink_);  // .cpp:294
+    return true;
   }
 
   vgx_reg handle() const { return reg_; }
@@ -78,6 +98,9 @@ class GpuRegistrationCostFunction : public ceres::CostFunction {
  private:
   vgx_ctx ctx_;
   vgx_reg reg_ = nullptr;
+  Config config_;
+  CostFunctionVisualsSink* sink_ = nullptr;          // not owned; outlives the cost function
+  std::unique_ptr<GpuCostFunctionVisuals> visuals_;  // only with a sink and a visuals flag set
 };
 
 }  // namespace voxgraph_amd

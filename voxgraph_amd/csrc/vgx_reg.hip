@@ -677,6 +677,140 @@ __global__ __launch_bounds__(kBlockThreads) void reg_eval_points_single_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// kernel 1v: the cost-function visuals of one constraint (vgx_reg_evaluate_visuals)
+// ---------------------------------------------------------------------------
+// The visuals instantiation of the drop-in materialising pass: same tiles, same point loads (sampled_point: the same
+// draws from the same engine outputs), same locate_stage1 / load_neighbours / eval_point, so r_u and j below are the
+// values the rows kernel scales.  What it writes per row (rules: include/voxgraph_amd.h, "Cost-function visuals"):
+//   cloud    32 B  pcl::PointXYZI {p_m.x, p_m.y, p_m.z, 1.0f | f32(f64(f32(r_u)) * factor), 0, 0, 0}: two 16-byte stores
+//   arrows   48 B  {o, t} f64, o = f64(p_m), t = f64(j) * (factor * 0.05) + o: three 16-byte stores           (GRAD)
+//   origins  24 B  o: a tile's origins are one contiguous run that starts 16-byte aligned (kTilePoints is even), so
+//                  they are staged in LDS and leave as 16-byte stores, thread k the pair k, k + 256, ..          (GRAD)
+// No dead-tile shortcut: a tile outside the reading grid still needs every point's p_m, and its intensity is
+// f32(f64(f32(w * no_correspondence_cost)) * factor).
+struct VisualsPose {
+  float qw, qz;      // T_mission__reading: minkindr exp of (x, y, z, 0, 0, yaw) in f32 (RCF:80-88)
+  float tx, ty, tz;
+};
+
+template <int VPS, int LAYOUT, int PPT, bool GRAD>
+__global__ __launch_bounds__(kBlockThreads) void reg_visuals_single_kernel(ConstraintDev C, PosePack P, VisualsPose M,
+                                                                           int n_tiles, f32x4* __restrict__ cloud,
+                                                                           double* __restrict__ arrows,
+                                                                           double* __restrict__ origins) {
+  __shared__ double s_origin[GRAD ? 3 * kBlockThreads * PPT : 1];
+  const int t = blockIdx.x;
+  if (t >= n_tiles) return;
+  const int64_t start = (int64_t)t * (kBlockThreads * PPT);
+  const int64_t left = C.n - start;
+  const int count = (int)(left < kBlockThreads * PPT ? left : kBlockThreads * PPT);
+  const GridDev g = C.grid;
+  const bool sampled = C.sample_raw != nullptr;
+
+  f32x4 pt[PPT];
+  float w[PPT];
+  const float* cell[PPT];
+  float d[PPT][8];
+#pragma unroll
+  for (int j = 0; j < PPT; ++j) {
+    int local = j * kBlockThreads + (int)threadIdx.x;
+    bool active = local < count;
+    int64_t i = start + (active ? local : 0);
+    if (sampled) {
+      pt[j] = sampled_point(C, i);
+      w[j] = 1.0f;  // RCF:121
+    } else {
+      pt[j] = as_global(reinterpret_cast<const f32x4*>(C.xyzd))[i];
+      w[j] = as_global(C.weight)[i];
+    }
+  }
+  Located loc[PPT];
+  bool have[PPT];
+  const bool grid_empty = g.bricks == nullptr;  // reading submap without blocks
+#pragma unroll
+  for (int j = 0; j < PPT; ++j) {
+    loc[j] = locate_stage1<VPS, LAYOUT>(g, P, pt[j].x, pt[j].y, pt[j].z);
+    have[j] = false;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) d[j][k] = 0.0f;
+    cell[j] = nullptr;
+  }
+  if (!grid_empty) {
+    int slot[PPT];
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) slot[j] = as_global(g.lut)[loc[j].lut_index];
+    constexpr int CELLS = BrickLayout<VPS, LAYOUT>::cells;
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) {
+      have[j] = loc[j].inside && slot[j] >= 0;
+      cell[j] = g.bricks + (size_t)(have[j] ? slot[j] : 0) * CELLS + loc[j].cell_off;
+    }
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) load_neighbours<VPS, LAYOUT>(cell[j], d[j]);
+  }
+  const double f = C.factor;
+  const double arrow_scale = __dmul_rn(f, 0.05);  // CFV:82-84: factor * 0.05 first
+#pragma unroll
+  for (int j = 0; j < PPT; ++j) {
+    int local = j * kBlockThreads + (int)threadIdx.x;
+    if (local >= count) continue;
+    PointEval e = eval_point(d[j], have[j], loc[j].Dx, loc[j].Dy, loc[j].Dz, g.voxel_size_inv, P, pt[j].x, pt[j].y,
+                             pt[j].w, w[j], C.no_corr_cost, GRAD);
+    // p_read = T_reading__reference * p_ref: locate_stage1's own steps (RCF:128-129)
+    const float x = pt[j].x, y = pt[j].y, z = pt[j].z;
+    float uv0 = -(P.qz * y);
+    float uv1 = P.qz * x;
+    uv0 += uv0;
+    uv1 += uv1;
+    float c0 = -(P.qz * uv1);
+    float c1 = P.qz * uv0;
+    const float px = (x + P.qw * uv0 + c0) + P.tx;
+    const float py = (y + P.qw * uv1 + c1) + P.ty;
+    const float pz = z + P.tz;
+    // p_m = T_mission__reading * p_read (RCF:172-173, 247-248): the same point transform
+    uv0 = -(M.qz * py);
+    uv1 = M.qz * px;
+    uv0 += uv0;
+    uv1 += uv1;
+    c0 = -(M.qz * uv1);
+    c1 = M.qz * uv0;
+    const float mx = (px + M.qw * uv0 + c0) + M.tx;
+    const float my = (py + M.qw * uv1 + c1) + M.ty;
+    const float mz = pz + M.tz;
+    const int64_t row = start + local;
+    if (cloud) {
+      // CFV:49 narrows the unscaled residual, CFV:75 multiplies float by double in f64 and rounds once
+      const float intensity = (float)__dmul_rn((double)(float)e.r, f);
+      const f32x4 lo = {mx, my, mz, 1.0f}, hi = {intensity, 0.0f, 0.0f, 0.0f};
+      cloud[2 * row] = lo;
+      cloud[2 * row + 1] = hi;
+    }
+    if (GRAD) {
+      const double ox = (double)mx, oy = (double)my, oz = (double)mz;
+      // j = pResidual_pParamRead.head<3>() (RCF:249): je0..2 == -jo0..2
+      const double tx = __dadd_rn(__dmul_rn((double)-e.jo0, arrow_scale), ox);
+      const double ty = __dadd_rn(__dmul_rn((double)-e.jo1, arrow_scale), oy);
+      const double tz = __dadd_rn(__dmul_rn((double)-e.jo2, arrow_scale), oz);
+      double2* a = reinterpret_cast<double2*>(arrows + 6 * row);
+      a[0] = make_double2(ox, oy);
+      a[1] = make_double2(oz, tx);
+      a[2] = make_double2(ty, tz);
+      s_origin[3 * local] = ox;
+      s_origin[3 * local + 1] = oy;
+      s_origin[3 * local + 2] = oz;
+    }
+  }
+  if (GRAD) {
+    __syncthreads();
+    double* out = origins + 3 * start;  // 24 * start bytes: start is a multiple of kBlockThreads * PPT
+    const int total = 3 * count, pairs = total / 2;
+    for (int k = (int)threadIdx.x; k < pairs; k += kBlockThreads)
+      reinterpret_cast<double2*>(out)[k] = make_double2(s_origin[2 * k], s_origin[2 * k + 1]);
+    if ((total & 1) && threadIdx.x == 0) out[total - 1] = s_origin[total - 1];  // (an odd tail tile: its last double alone)
+  }
+}
+
+// ---------------------------------------------------------------------------
 // kernel 2: fused normal equations (52 B / evaluation, no per-point output)
 // ---------------------------------------------------------------------------
 // u = (jo0, jo1, jo2, jo3, je3, r): [J r]^T [J r] (9x9) is a signed
@@ -1549,7 +1683,54 @@ static void launch_points_single(hipStream_t stream, int vps, const ConstraintDe
 #undef VGX_LAUNCH_SINGLE
 }
 
+// the visuals of the same evaluation: same grid, descriptor and pose pack as launch_points_single; cloud may be null
+// (no residual cloud), arrows / origins are null together (no gradients)
+static void launch_visuals_single(hipStream_t stream, int vps, const ConstraintDev& desc, const PosePack& pack,
+                                  const VisualsPose& mission, void* cloud, double* arrows, double* origins) {
+  const int n_tiles = (int)((desc.n + kTilePoints - 1) / kTilePoints);
+  if (n_tiles <= 0 || (!cloud && !arrows)) return;
+  dim3 grid(n_tiles), block(kBlockThreads);
+#define VGX_LAUNCH_VISUALS(VPS, LAYOUT)                                                                              \
+  do {                                                                                                               \
+    if (arrows)                                                                                                      \
+      hipLaunchKernelGGL((reg_visuals_single_kernel<VPS, LAYOUT, kPointsPerThread, true>), grid, block, 0, stream,   \
+                         desc, pack, mission, n_tiles, (f32x4*)cloud, arrows, origins);                              \
+    else                                                                                                             \
+      hipLaunchKernelGGL((reg_visuals_single_kernel<VPS, LAYOUT, kPointsPerThread, false>), grid, block, 0, stream,  \
+                         desc, pack, mission, n_tiles, (f32x4*)cloud, arrows, origins);                              \
+  } while (0)
+  const int layout = desc.grid.layout;
+  if (layout == 0) {
+    if (vps == 16) VGX_LAUNCH_VISUALS(16, 0);
+    else VGX_LAUNCH_VISUALS(8, 0);
+  } else if (layout == 1) {
+    if (vps == 16) VGX_LAUNCH_VISUALS(16, 1);
+    else VGX_LAUNCH_VISUALS(8, 1);
+  } else {
+    if (vps == 16) VGX_LAUNCH_VISUALS(16, 2);
+    else VGX_LAUNCH_VISUALS(8, 2);
+  }
+#undef VGX_LAUNCH_VISUALS
+}
+
+// T_mission__reading as RCF:80-88 builds it: the reading pose narrowed to f32, minkindr's exp
+static VisualsPose make_visuals_pose(const double read_pose[4]) {
+  const YawQuat q = yaw_exp((float)read_pose[3]);
+  return {q.w, q.z, (float)read_pose[0], (float)read_pose[1], (float)read_pose[2]};
+}
+
 }  // namespace vgx
+
+// The cost-function visuals of the last vgx_reg_evaluate_visuals on this handle; the buffers grow on demand
+struct vgx_reg_visuals_s {
+  vgx_ctx ctx = nullptr;
+  std::mutex mu;
+  int64_t n_residual_points = 0, n_jacobians = 0;
+  double factor = 0;
+  vgx::DeviceBuffer d_cloud;    // [cap] 32-byte PointXYZI records
+  vgx::DeviceBuffer d_arrows;   // double [cap][2][3]
+  vgx::DeviceBuffer d_origins;  // double [cap][3]
+};
 
 using namespace vgx;
 
@@ -1809,19 +1990,29 @@ struct SlotLease {  // gives the slot back on every exit path; declare it BEFORE
 };
 }  // namespace
 
-int vgx_reg_evaluate(vgx_reg r, const double ref_pose[4], const double read_pose[4],
-                     double* residuals, double* jac_ref, double* jac_read) {
-  if (!r || !ref_pose || !read_pose) return VGX_ERR_INVALID;
+// vgx_reg_evaluate, and -- with a visuals handle K (its lock held by the caller) -- vgx_reg_evaluate_visuals: the same
+// evaluation plus one more kernel on the slot's stream that reads the same descriptor (the same engine outputs in
+// sampling mode) and the same pose pack; the one host synchronisation below covers both.
+static int reg_evaluate_impl(const char* fn, vgx_reg r, const double ref_pose[4], const double read_pose[4],
+                             double* residuals, double* jac_ref, double* jac_read, vgx_reg_visuals K, bool want_cloud,
+                             bool want_gradients) {
   vgx_ctx ctx = r->ctx;
   std::lock_guard<std::mutex> own(r->mu);
   const int64_t n = r->num_residuals;
   SlotLease lease{ctx, -1};
   std::unique_lock<std::mutex> lk(ctx->mu);  // launch under the context lock ...
-  if (!residuals) return set_error(ctx, VGX_ERR_INVALID, "vgx_reg_evaluate: residuals == NULL");
+  if (!residuals) return set_error(ctx, VGX_ERR_INVALID, std::string(fn) + ": residuals == NULL");
   if (!r->points_current())
     return set_error(ctx, VGX_ERR_INVALID,
-                     "vgx_reg_evaluate: the reference submap's registration points were replaced after "
+                     std::string(fn) + ": the reference submap's registration points were replaced after "
                      "this cost function was created");
+  const bool do_cloud = K && want_cloud;
+  const bool do_grad = K && want_gradients && (jac_ref || jac_read);  // RCF:179: only when Jacobians were asked for
+  if (K) {  // from here on the handle holds this evaluation's visuals, or none
+    K->n_residual_points = 0;
+    K->n_jacobians = 0;
+    K->factor = 0;
+  }
   if (n == 0) return reg_status(r);
   const int k = acquire_slot(ctx, lk);
   lease.k = k;
@@ -1850,6 +2041,15 @@ int vgx_reg_evaluate(vgx_reg r, const double ref_pose[4], const double read_pose
     VGX_HIP(ctx, hipHostMalloc((void**)&sl.h_raw, (size_t)n * 2 * sizeof(uint32_t), hipHostMallocDefault));
     sl.raw_cap = 2 * n;
   }
+  if (do_cloud) {
+    const hipError_t e = K->d_cloud.reserve((size_t)n * 32, 4096 * 32, true);
+    if (e != hipSuccess) return alloc_error(ctx, e, "cost-function visuals: allocating the residual cloud");
+  }
+  if (do_grad && (size_t)n * 48 > K->d_arrows.bytes) {
+    const size_t cap = (size_t)std::max<int64_t>(n + n / 4, 4096);
+    const hipError_t e = alloc_group({{&K->d_arrows, cap * 48}, {&K->d_origins, cap * 24}});
+    if (e != hipSuccess) return alloc_error(ctx, e, "cost-function visuals: allocating the Jacobian markers");
+  }
   PosePack pack;
   make_pose_pack(ref_pose, read_pose, &pack);
   double* d_res = sl.d_out;
@@ -1869,6 +2069,10 @@ int vgx_reg_evaluate(vgx_reg r, const double ref_pose[4], const double read_pose
   }
   if (reg_status(r) == VGX_EVALUATE_FALSE) return VGX_EVALUATE_FALSE;
   launch_points_single<double>(sl.stream, r->reading->vps, desc, pack, d_res, d_jr, d_je);
+  if (do_cloud || do_grad)
+    launch_visuals_single(sl.stream, r->reading->vps, desc, pack, make_visuals_pose(read_pose),
+                          do_cloud ? K->d_cloud.p : nullptr, do_grad ? K->d_arrows.as<double>() : nullptr,
+                          do_grad ? K->d_origins.as<double>() : nullptr);
   VGX_HIP(ctx, hipGetLastError());
   lk.unlock();
   // ... and copy + wait outside it: other cost functions' evaluations proceed meanwhile.  Small
@@ -1895,8 +2099,82 @@ int vgx_reg_evaluate(vgx_reg r, const double ref_pose[4], const double read_pose
   }
   if (e != hipSuccess) {
     lk.lock();
-    return set_error(ctx, VGX_ERR_HIP, std::string("vgx_reg_evaluate: ") + hipGetErrorString(e));
+    return set_error(ctx, VGX_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
   }
+  if (K) {
+    K->n_residual_points = do_cloud ? n : 0;
+    K->n_jacobians = do_grad ? n : 0;
+    K->factor = desc.factor;
+  }
+  return VGX_OK;
+}
+
+int vgx_reg_evaluate(vgx_reg r, const double ref_pose[4], const double read_pose[4],
+                     double* residuals, double* jac_ref, double* jac_read) {
+  if (!r || !ref_pose || !read_pose) return VGX_ERR_INVALID;
+  return reg_evaluate_impl("vgx_reg_evaluate", r, ref_pose, read_pose, residuals, jac_ref, jac_read, nullptr, false, false);
+}
+
+int vgx_reg_evaluate_visuals(vgx_reg r, const double ref_pose[4], const double read_pose[4], double* residuals,
+                             double* jac_ref, double* jac_read, int32_t want_residual_cloud, int32_t want_gradients,
+                             vgx_reg_visuals K) {
+  if (!r || !ref_pose || !read_pose) return VGX_ERR_INVALID;
+  if (!K) return set_error(r->ctx, VGX_ERR_INVALID, "vgx_reg_evaluate_visuals: NULL visuals");
+  if (K->ctx != r->ctx) return set_error(r->ctx, VGX_ERR_INVALID, "vgx_reg_evaluate_visuals: visuals of another context");
+  std::lock_guard<std::mutex> out_lk(K->mu);
+  return reg_evaluate_impl("vgx_reg_evaluate_visuals", r, ref_pose, read_pose, residuals, jac_ref, jac_read, K,
+                           want_residual_cloud != 0, want_gradients != 0);
+}
+
+int vgx_reg_visuals_create(vgx_ctx ctx, vgx_reg_visuals* out) {
+  if (!ctx || !out) return set_error(ctx, VGX_ERR_INVALID, "vgx_reg_visuals_create: NULL argument");
+  vgx_reg_visuals K = new (std::nothrow) vgx_reg_visuals_s;
+  if (!K) return set_error(ctx, VGX_ERR_NOMEM, "vgx_reg_visuals_create: out of host memory");
+  K->ctx = ctx;
+  *out = K;
+  return VGX_OK;
+}
+
+int vgx_reg_visuals_destroy(vgx_reg_visuals K) {
+  if (!K) return VGX_ERR_INVALID;
+  (void)hipSetDevice(K->ctx->device);
+  delete K;
+  return VGX_OK;
+}
+
+int vgx_reg_visuals_stats(vgx_reg_visuals K, int64_t* n_residual_points, int64_t* n_jacobians) {
+  if (!K) return VGX_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(K->mu);
+  if (n_residual_points) *n_residual_points = K->n_residual_points;
+  if (n_jacobians) *n_jacobians = K->n_jacobians;
+  return VGX_OK;
+}
+
+int vgx_reg_visuals_download(vgx_reg_visuals K, void* cloud_bytes, double* arrow_points, double* origin_points,
+                             double* factor) {
+  if (!K) return VGX_ERR_INVALID;
+  vgx_ctx ctx = K->ctx;
+  std::lock_guard<std::mutex> lk(K->mu);
+  if (factor) *factor = K->factor;
+  if (K->n_residual_points == 0 && K->n_jacobians == 0) return VGX_OK;
+  VGX_HIP(ctx, hipSetDevice(ctx->device));
+  // (the evaluation that filled the handle waited for its stream: the arrays are complete)
+  if (cloud_bytes && K->n_residual_points > 0)
+    VGX_HIP(ctx, hipMemcpy(cloud_bytes, K->d_cloud.p, (size_t)K->n_residual_points * 32, hipMemcpyDeviceToHost));
+  if (arrow_points && K->n_jacobians > 0)
+    VGX_HIP(ctx, hipMemcpy(arrow_points, K->d_arrows.p, (size_t)K->n_jacobians * 48, hipMemcpyDeviceToHost));
+  if (origin_points && K->n_jacobians > 0)
+    VGX_HIP(ctx, hipMemcpy(origin_points, K->d_origins.p, (size_t)K->n_jacobians * 24, hipMemcpyDeviceToHost));
+  return VGX_OK;
+}
+
+int vgx_reg_visuals_device_pointers(vgx_reg_visuals K, const void** cloud, const double** arrow_points,
+                                    const double** origin_points) {
+  if (!K) return VGX_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(K->mu);
+  if (cloud) *cloud = K->n_residual_points > 0 ? K->d_cloud.p : nullptr;
+  if (arrow_points) *arrow_points = K->n_jacobians > 0 ? K->d_arrows.as<double>() : nullptr;
+  if (origin_points) *origin_points = K->n_jacobians > 0 ? K->d_origins.as<double>() : nullptr;
   return VGX_OK;
 }
 
