@@ -129,6 +129,16 @@ def test_tsdf_initial_box_and_pool_are_only_a_reservation(capi, ctx):
 def test_create_destroy_cycles_do_not_leak_device_memory(capi, ctx):
     import torch
     sm, _ = synth.config1_pair(asymmetric=True)
+    T = np.array([1, 0, 0, 0, 0, 0, 0], F)
+    one = np.array([[1.0, 0.2, 0.1]], F)
+    rng = np.random.default_rng(3)
+    d = rng.normal(size=(300, 3))
+    many = (d / np.linalg.norm(d, axis=1, keepdims=True) * rng.uniform(0.5, 1.5, (300, 1))).astype(F)
+    msg = np.zeros((len(many), 4), F)      # a PointCloud2 of x y z + one word of padding
+    msg[:, :3] = many
+    layout = capi.scan_layout(width=len(many), height=1, point_step=16, offset_x=0, offset_y=4, offset_z=8,
+                              color_kind=capi.SCAN_COLOR_NONE)
+    poses = np.zeros((2, 4))
 
     def cycle():
         g = H.gpu_submap(capi, ctx, sm)
@@ -144,13 +154,34 @@ def test_create_destroy_cycles_do_not_leak_device_memory(capi, ctx):
         r2 = np.zeros(cs.num_residuals())
         cs.Evaluate([np.zeros(4), np.zeros(4)], r2, None)
         b = capi.RegistrationBatch(ctx, [cf, cf], [(0, 1), (1, 0)])
-        b.evaluate_normal(np.zeros((2, 4)))
-        pairs = capi.find_overlapping_pairs(ctx, [g, g], np.zeros((2, 4)))
+        b.evaluate_normal(poses)
+        # the batch's own rows and their pinned mirror, row arrays chosen by placement, a sampling batch (engine
+        # outputs, drawn points, stream jobs), the node structure of a constraint list
+        b.evaluate_rows_f64(poses)
+        out = b.alloc_outputs(poses, n_candidates=2)
+        b.free_outputs(*out[:3])
+        bs = capi.RegistrationBatch(ctx, [cs], [(0, 1)])
+        bs.evaluate_normal(poses)
+        asm = capi.RegistrationAssembler(ctx, [(0, 1), (1, 0)])
+        pairs = capi.find_overlapping_pairs(ctx, [g, g], poses)
         layer = capi.TsdfLayer(ctx, 0.1, 16, (-2, -2, -2), (4, 4, 4), 64)
         integ = capi.FastTsdfIntegrator(ctx, capi.tsdf_config(), layer)
-        integ.integratePointCloud(np.array([1, 0, 0, 0, 0, 0, 0], F), np.array([[1.0, 0.2, 0.1]], F))
+        integ_sorted = capi.FastTsdfIntegrator(ctx, capi.tsdf_config(deterministic=1, integration_order=capi.TSDF_ORDER_SORTED), layer)
+        # a one-point scan, then a larger one through the same integrators: every grow block runs with something to free
+        for pts in (one, many):
+            integ.integratePointCloud(T, pts)
+            integ.integratePointCloudMerged(T, pts)
+            integ_sorted.integratePointCloud(T, pts)
+        scan = capi.Scan(ctx)
+        assert scan.decode_msg(layout, msg.tobytes()) == (len(many), 0)
+        integ.integrate_scan(T, scan)
+        # a box of one block and a pool of one block, the ray outside both: one rebox and one grow_pool
+        small = capi.TsdfLayer(ctx, 0.1, 16, (0, 0, 0), (1, 1, 1), 1)
+        integ_small = capi.FastTsdfIntegrator(ctx, capi.tsdf_config(), small)
+        integ_small.integratePointCloud(T, np.array([[3.0, 0.2, 0.1]], F))
+        assert small.growths() >= 1 and small.stats()[0] > 1
         s2 = capi.Submap.from_tsdf_layer(ctx, layer, 3)
-        for o in (s2, integ, layer, b, cs, cf, g):
+        for o in (s2, integ_small, small, scan, integ_sorted, integ, layer, asm, bs, b, cs, cf, g):
             o.destroy()
         return pairs
 

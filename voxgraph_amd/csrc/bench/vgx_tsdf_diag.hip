@@ -62,7 +62,7 @@ int vgx_tsdf_integrator_read_trace(vgx_tsdf_integrator I, int64_t* rows, int64_t
   }
   const long long take = I->wg_stats_rows < max_workgroups ? I->wg_stats_rows : max_workgroups;
   if (rows && take > 0) {
-    VGX_HIP(ctx, hipMemcpyAsync(rows, I->d_wg_stats, (size_t)take * kWgStatWords * 8, hipMemcpyDeviceToHost, ctx->tsdf_stream));
+    VGX_HIP(ctx, hipMemcpyAsync(rows, I->d_wg_stats.p, (size_t)take * kWgStatWords * 8, hipMemcpyDeviceToHost, ctx->tsdf_stream));
     VGX_HIP(ctx, hipStreamSynchronize(ctx->tsdf_stream));
   }
   return VGX_OK;
@@ -79,18 +79,17 @@ int vgx_tsdf_integrator_set_event_trace(vgx_tsdf_integrator I, int64_t capacity_
   std::lock_guard<std::mutex> lk(ctx->tsdf_mu);
   VGX_HIP(ctx, hipSetDevice(ctx->device));
   VGX_HIP(ctx, hipStreamSynchronize(ctx->tsdf_stream));
-  if (I->d_trace) (void)hipFree(I->d_trace);
-  I->d_trace = nullptr;
+  I->d_trace.release();
   I->dev.trace = nullptr;
   I->dev.trace_words = 0;
   I->racing_launch = nullptr;
   if (capacity_words == 0) return VGX_OK;
   if (capacity_words < (int64_t)kTraceHeaderWords + 8)
     return set_error(ctx, VGX_ERR_INVALID, "vgx_tsdf_integrator_set_event_trace: capacity below one event");
-  VGX_HIP(ctx, hipMalloc(&I->d_trace, (size_t)capacity_words * 8));
+  VGX_HIP(ctx, I->d_trace.alloc((size_t)capacity_words * 8));
   const unsigned long long header[2] = {kTraceHeaderWords, 0ull};
-  VGX_HIP(ctx, hipMemcpy(I->d_trace, header, sizeof(header), hipMemcpyHostToDevice));
-  I->dev.trace = I->d_trace;
+  VGX_HIP(ctx, hipMemcpy(I->d_trace.p, header, sizeof(header), hipMemcpyHostToDevice));
+  I->dev.trace = I->d_trace.as<unsigned long long>();
   I->dev.trace_words = (unsigned long long)capacity_words;
   I->racing_launch = launch_racing_scan_traced;
   return VGX_OK;
@@ -104,19 +103,19 @@ int vgx_tsdf_integrator_read_event_trace(vgx_tsdf_integrator I, uint64_t* words,
   std::lock_guard<std::mutex> own(I->mu);
   vgx_ctx ctx = I->ctx;
   std::lock_guard<std::mutex> lk(ctx->tsdf_mu);
-  if (!I->d_trace) return set_error(ctx, VGX_ERR_INVALID, "vgx_tsdf_integrator_read_event_trace: no event trace set");
+  if (!I->d_trace.p) return set_error(ctx, VGX_ERR_INVALID, "vgx_tsdf_integrator_read_event_trace: no event trace set");
   VGX_HIP(ctx, hipSetDevice(ctx->device));
   VGX_HIP(ctx, hipStreamSynchronize(ctx->tsdf_stream));
   unsigned long long header[2] = {0, 0};
-  VGX_HIP(ctx, hipMemcpy(header, I->d_trace, sizeof(header), hipMemcpyDeviceToHost));
+  VGX_HIP(ctx, hipMemcpy(header, I->d_trace.p, sizeof(header), hipMemcpyDeviceToHost));
   // (events that did not fit still moved the cursor)
   const unsigned long long used = header[0] < I->dev.trace_words ? header[0] : I->dev.trace_words;
   *n_words = (int64_t)(used - kTraceHeaderWords);
   if (lost) *lost = (int64_t)header[1];
   if (*n_words > max_words || (*n_words > 0 && !words)) return VGX_ERR_INVALID;
-  if (*n_words > 0) VGX_HIP(ctx, hipMemcpy(words, I->d_trace + kTraceHeaderWords, (size_t)*n_words * 8, hipMemcpyDeviceToHost));
+  if (*n_words > 0) VGX_HIP(ctx, hipMemcpy(words, I->dev.trace + kTraceHeaderWords, (size_t)*n_words * 8, hipMemcpyDeviceToHost));
   const unsigned long long fresh[2] = {kTraceHeaderWords, 0ull};
-  VGX_HIP(ctx, hipMemcpy(I->d_trace, fresh, sizeof(fresh), hipMemcpyHostToDevice));
+  VGX_HIP(ctx, hipMemcpy(I->d_trace.p, fresh, sizeof(fresh), hipMemcpyHostToDevice));
   return VGX_OK;
 }
 

@@ -382,10 +382,11 @@ int vgx_ctx_destroy(vgx_ctx ctx) {
       (void)hipStreamDestroy(sl.stream);
     }
     if (sl.order) (void)hipEventDestroy(sl.order);
-    if (sl.d_out) (void)hipFree(sl.d_out);
-    if (sl.d_raw) (void)hipFree(sl.d_raw);
-    if (sl.h_raw) (void)hipHostFree(sl.h_raw);
-    if (sl.h_out) (void)hipHostFree(sl.h_out);
+    // (here, not with `delete ctx`: before the context's own streams go)
+    sl.d_out.release();
+    sl.d_raw.release();
+    sl.h_raw.release();
+    sl.h_out.release();
   }
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
   if (ctx->tsdf_own_stream) (void)hipStreamDestroy(ctx->tsdf_own_stream);

@@ -139,6 +139,172 @@ constexpr int kNormalSize = 45;     // per-constraint fused output (doubles)
 constexpr int kPartialSize = 22;    // 21 unique products + reserved
 
 // ---------------------------------------------------------------------------
+// Owners of device and pinned host memory
+// ---------------------------------------------------------------------------
+// The one owner of device memory on the host side (DESIGN.md 2): frees in its destructor, so scratch declared in a function
+// is freed on every exit path (the VGX_HIP macro returns early) and a handle's arrays go with the handle.  It neither
+// synchronises nor zeroes: whoever frees an array that a queued kernel may still read synchronises that stream first.
+struct DeviceBuffer {
+  void* p = nullptr;
+  size_t bytes = 0;  // capacity
+  DeviceBuffer() = default;
+  DeviceBuffer(const DeviceBuffer&) = delete;
+  DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+  DeviceBuffer(DeviceBuffer&& o) noexcept { swap(o); }
+  DeviceBuffer& operator=(DeviceBuffer&& o) noexcept {
+    swap(o);
+    return *this;
+  }
+  ~DeviceBuffer() { release(); }
+  void swap(DeviceBuffer& o) {
+    std::swap(p, o.p);
+    std::swap(bytes, o.bytes);
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+  // exactly `n` bytes; what was held is freed first, and after a failure the buffer is empty
+  hipError_t alloc(size_t n) {
+    release();
+    const hipError_t e = hipMalloc(&p, n);
+    if (e == hipSuccess) bytes = n;
+    else p = nullptr;
+    return e;
+  }
+  // grow-only: nothing when the capacity suffices, else max(n [+ n / 4], min_bytes) fresh bytes (the contents are lost)
+  hipError_t reserve(size_t n, size_t min_bytes = 0, bool slack = false) {
+    if (n <= bytes) return hipSuccess;
+    return alloc(std::max(slack ? n + n / 4 : n, min_bytes));
+  }
+  // hands the array to the caller (who frees it) and leaves the buffer empty
+  void* detach() {
+    void* q = p;
+    p = nullptr;
+    bytes = 0;
+    return q;
+  }
+  template <typename T>
+  T* as() const {
+    return static_cast<T*>(p);
+  }
+};
+// Pinned host memory, the same shape: staging buffers and host mirrors go with their handle.
+struct PinnedBuffer {
+  void* p = nullptr;
+  size_t bytes = 0;  // capacity
+  PinnedBuffer() = default;
+  PinnedBuffer(const PinnedBuffer&) = delete;
+  PinnedBuffer& operator=(const PinnedBuffer&) = delete;
+  PinnedBuffer(PinnedBuffer&& o) noexcept { swap(o); }
+  PinnedBuffer& operator=(PinnedBuffer&& o) noexcept {
+    swap(o);
+    return *this;
+  }
+  ~PinnedBuffer() { release(); }
+  void swap(PinnedBuffer& o) {
+    std::swap(p, o.p);
+    std::swap(bytes, o.bytes);
+  }
+  void release() {
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+  // exactly `n` bytes; what was held is freed first, and after a failure the buffer is empty
+  hipError_t alloc(size_t n, unsigned flags = hipHostMallocDefault) {
+    release();
+    const hipError_t e = hipHostMalloc(&p, n, flags);
+    if (e == hipSuccess) bytes = n;
+    else p = nullptr;
+    return e;
+  }
+  // grow-only: nothing when the capacity suffices (the contents are lost otherwise)
+  hipError_t reserve(size_t n) { return n <= bytes ? hipSuccess : alloc(n); }
+  template <typename T>
+  T* as() const {
+    return static_cast<T*>(p);
+  }
+};
+// The double-buffered pinned upload: two pinned halves filled in turn, so that the caller's (pageable) data is consumed
+// when the call returns while the host-to-device copy runs behind it.  An event per half says when the copies that read
+// it have finished and it may be filled again.  Like the buffers it never synchronises a stream: whoever lets `reserve`
+// reallocate while a queued copy may still read a half synchronises that stream first.
+struct UploadStage {
+  PinnedBuffer half[2];
+  hipEvent_t copied[2] = {nullptr, nullptr};
+  int turn = 0;
+  UploadStage() = default;
+  UploadStage(const UploadStage&) = delete;
+  UploadStage& operator=(const UploadStage&) = delete;
+  ~UploadStage() {
+    for (hipEvent_t e : copied)
+      if (e) (void)hipEventDestroy(e);
+  }
+  size_t bytes() const { return half[0].bytes; }  // capacity of each half
+  // grow-only, both halves; after a failure both are empty
+  hipError_t reserve(size_t n) {
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 2 && e == hipSuccess; ++k)
+      if (!copied[k]) e = hipEventCreateWithFlags(&copied[k], hipEventDisableTiming);
+    if (e == hipSuccess && n > bytes()) {
+      half[0].release();
+      half[1].release();
+      e = half[0].alloc(n);
+      if (e == hipSuccess) e = half[1].alloc(n);
+    }
+    if (e != hipSuccess) {
+      half[0].release();
+      half[1].release();
+    }
+    return e;
+  }
+  // the half to fill next, once the copies that last read it have finished; null (and *err) when that wait failed
+  void* next(int* k, hipError_t* err = nullptr) {
+    *k = turn;
+    turn ^= 1;
+    const hipError_t e = hipEventSynchronize(copied[*k]);
+    if (err) *err = e;
+    return e == hipSuccess ? half[*k].p : nullptr;
+  }
+  // after the copies that read half k have been queued on `stream`
+  hipError_t record(int k, hipStream_t stream) { return hipEventRecord(copied[k], stream); }
+};
+// Arrays that share one capacity grow together: all are freed before the first is allocated (the peak does not rise while
+// a handle grows), and after a failure all are empty.
+struct DeviceBufferSize {
+  DeviceBuffer* buffer;
+  size_t bytes;
+};
+inline hipError_t alloc_group(std::initializer_list<DeviceBufferSize> group) {
+  for (const DeviceBufferSize& g : group) g.buffer->release();
+  hipError_t e = hipSuccess;
+  for (const DeviceBufferSize& g : group)
+    if (e == hipSuccess) e = g.buffer->alloc(g.bytes);
+  if (e != hipSuccess)
+    for (const DeviceBufferSize& g : group) g.buffer->release();
+  return e;
+}
+
+// rocPRIM's two calls -- the size of the temporary storage with a null pointer, then the work with identical arguments --
+// from ONE lambda hipError_t(void* tmp, size_t& bytes) that holds the rocPRIM call.  run_with_temp may reallocate `tmp`:
+// only where nothing queued still uses it; launches that share a workspace ask with temp_bytes and make room once.
+template <class Call>
+hipError_t temp_bytes(Call& call, size_t* bytes) {
+  *bytes = 0;
+  return call(nullptr, *bytes);
+}
+template <class Call>
+hipError_t run_with_temp(DeviceBuffer& tmp, Call& call) {
+  size_t bytes = 0;
+  hipError_t e = temp_bytes(call, &bytes);
+  if (e == hipSuccess) e = tmp.reserve(bytes, 8);  // (never null: to rocPRIM a null workspace is the size query)
+  if (e == hipSuccess) e = call(tmp.p, bytes);
+  return e;
+}
+
+// ---------------------------------------------------------------------------
 // Host objects behind the opaque handles
 // ---------------------------------------------------------------------------
 struct Context {
@@ -173,12 +339,10 @@ struct Context {
   struct EvalSlot {
     hipStream_t stream = nullptr;
     hipEvent_t order = nullptr;
-    double* d_out = nullptr;
-    int64_t out_rows = 0;
-    uint32_t* d_raw = nullptr;
-    uint32_t* h_raw = nullptr;
-    int64_t raw_cap = 0;
-    double* h_out = nullptr;   // pinned, kSmallOutputBytes: small evaluations come back in ONE copy
+    DeviceBuffer d_out;        // [n][9] doubles
+    DeviceBuffer d_raw;        // [2 n] engine outputs, and their pinned staging
+    PinnedBuffer h_raw;
+    PinnedBuffer h_out;        // kSmallOutputBytes: small evaluations come back in ONE copy
     bool busy = false;
   };
   static constexpr int kEvalSlots = 8;
@@ -308,8 +472,8 @@ struct vgx_reg_s {
   vgx::SamplerEngine rng;
   // vgx_reg_evaluate_device_f32 in sampling mode only (it does not wait for its kernel, so it
   // cannot borrow a slot): own staging for the engine outputs, allocated at first use
-  uint32_t* d_sample_raw = nullptr;
-  uint32_t* h_sample_raw = nullptr;
+  vgx::DeviceBuffer d_sample_raw;
+  vgx::PinnedBuffer h_sample_raw;
   // Drop-in Evaluate calls arrive from several Ceres threads (pose_graph.cpp:96), each on its own
   // cost function; each call borrows one of the context's evaluation slots (Context::EvalSlot).
   std::mutex mu;                // two threads on the SAME cost function are serialised
@@ -334,23 +498,22 @@ struct vgx_reg_batch_s {
   std::vector<int32_t> global_index;  // [n]
   std::vector<int64_t> row_offset;    // [n+1]
   std::vector<vgx::Tile> tiles;
-  vgx::ConstraintDev* d_desc = nullptr;
-  vgx::PosePack* d_pack = nullptr;
-  vgx::PosePack* h_pack = nullptr;    // pinned, 2 x n (double-buffered staging)
-  hipEvent_t pack_copied[2] = {nullptr, nullptr};  // H2D of staging half k finished
-  int pack_turn = 0;
-  vgx::Tile* d_tiles = nullptr;
-  vgx::Tile* d_draw_tiles = nullptr;     // the sampling constraints' tiles in the draw kernel's launch order
+  // device arrays, typed at their uses (as<T>()); all go with the handle
+  vgx::DeviceBuffer d_desc;           // ConstraintDev [n]
+  vgx::DeviceBuffer d_pack;           // PosePack [n]
+  vgx::UploadStage pack_stage;        // ... and their pinned staging, [n] per half
+  vgx::DeviceBuffer d_tiles;          // Tile
+  vgx::DeviceBuffer d_draw_tiles;     // Tile: the sampling constraints' tiles in the draw kernel's launch order
   int32_t n_draw_tiles = 0;
-  float4* d_drawn = nullptr;             // sampling: the point {x,y,z,d} every row uses in this evaluation (reg_gather_points_kernel)
-  int32_t* d_drawn_idx = nullptr;        // ... and its index in the point set (reg_draw_kernel)
-  unsigned char* d_tile_dead = nullptr;  // per materialising-pass tile, per launch: every chunk culled (rows are zeros)
-  int32_t* d_tile_first = nullptr;    // [n+1] first tile of each constraint
-  double* d_partials = nullptr;       // [n_tiles][4 wavefronts][kPartialSize]
-  double* d_normal = nullptr;         // [n][45] (internal, when caller passes none)
-  double* h_normal = nullptr;         // pinned [n][45]: staging of the host copies (normal_host / cost_host)
-  int32_t* d_node_pair = nullptr;
-  int32_t* d_global_index = nullptr;
+  vgx::DeviceBuffer d_drawn;          // float4; sampling: the point {x,y,z,d} every row uses in this evaluation (reg_gather_points_kernel)
+  vgx::DeviceBuffer d_drawn_idx;      // int32 ... and its index in the point set (reg_draw_kernel)
+  vgx::DeviceBuffer d_tile_dead;      // bytes; per materialising-pass tile, per launch: every chunk culled (rows are zeros)
+  vgx::DeviceBuffer d_tile_first;     // int32 [n+1] first tile of each constraint
+  vgx::DeviceBuffer d_partials;       // double [n_tiles][4 wavefronts][kPartialSize]
+  vgx::DeviceBuffer d_normal;         // double [n][45] (internal, when caller passes none)
+  vgx::PinnedBuffer h_normal;         // double [n][45]: staging of the host copies (normal_host / cost_host)
+  vgx::DeviceBuffer d_node_pair;      // int32
+  vgx::DeviceBuffer d_global_index;   // int32
   // fused pass: coarser tiles, and node -> incident (constraint<<1 | side) CSR
   std::vector<vgx::Tile> reduce_tiles;  // constraint-major; the device copy is re-ordered for launch at
                                         // the first evaluation (XCD-aware, make_xcd_order)
@@ -360,10 +523,10 @@ struct vgx_reg_batch_s {
   bool launch_order_grouped = false, points_order_grouped = false;  // what make_xcd_order decided
   bool points_order_made = false;              // same, for the materialising pass's 1024-point tiles
   std::vector<int32_t> host_points_tile_first;
-  vgx::Tile* d_reduce_tiles = nullptr;
+  vgx::DeviceBuffer d_reduce_tiles;   // Tile
   int32_t csr_nodes = 0;
-  int32_t* d_node_first = nullptr;
-  int32_t* d_node_items = nullptr;
+  vgx::DeviceBuffer d_node_first;     // int32
+  vgx::DeviceBuffer d_node_items;     // int32
   // sampling constraints (sampling_ratio != -1): one stream job per distinct engine, in order of
   // first appearance; the engine's constraints consume consecutive ranges of its stream in
   // constraint order, as successive Evaluate calls on one thread would (RCF:113-122)
@@ -373,14 +536,14 @@ struct vgx_reg_batch_s {
     int64_t count;    // words generated per evaluation
   };
   std::vector<StreamJob> stream_jobs;
-  uint32_t* d_raw = nullptr;       // all engine outputs of one evaluation
-  void* d_stream_jobs = nullptr;   // device copy of {state*, out*, count} per job
+  vgx::DeviceBuffer d_raw;         // uint32: all engine outputs of one evaluation
+  vgx::DeviceBuffer d_stream_jobs; // device copy of {state*, out*, count} per job
   bool any_sampling = false;
   bool holds_regs = false;         // regs[*]->users were incremented (vgx_reg_batch_create succeeded)
   // vgx_reg_batch_evaluate_rows_f64 / _fetch_rows_f64: f64 rows the batch keeps itself (allocated at first use), and -- while
   // they are small enough (kRowsMirrorLimit) -- their pinned host mirror, filled by ONE device-to-host copy per evaluation
-  double* d_rows[3] = {nullptr, nullptr, nullptr};   // residuals [R], jac_ref [R][4], jac_read [R][4]
-  char* h_rows = nullptr;                            // [R x 8][R x 32][R x 32] pinned, or NULL (too large: fetches copy slices)
+  vgx::DeviceBuffer d_rows[3];                       // double: residuals [R], jac_ref [R][4], jac_read [R][4]
+  vgx::PinnedBuffer h_rows;                          // [R x 8][R x 32][R x 32], or empty (too large: fetches copy slices)
   bool rows_have[3] = {false, false, false};         // what the last rows evaluation produced
   bool rows_mirrored = false;                        // the mirror holds the last evaluation (its copy may still be in flight)
 };
@@ -398,80 +561,6 @@ inline int set_error(vgx_ctx ctx, int code, const std::string& msg);
 // the one lock behind the users / destroy_requested fields of submaps and cost functions (vgx_context.hip)
 std::mutex& lifetime_mu();
 
-// The one owner of device memory on the host side (DESIGN.md 2): frees in its destructor, so scratch declared in a function
-// is freed on every exit path (the VGX_HIP macro returns early) and a handle's arrays go with the handle.  It neither
-// synchronises nor zeroes: whoever frees an array that a queued kernel may still read synchronises that stream first.
-struct DeviceBuffer {
-  void* p = nullptr;
-  size_t bytes = 0;  // capacity
-  DeviceBuffer() = default;
-  DeviceBuffer(const DeviceBuffer&) = delete;
-  DeviceBuffer& operator=(const DeviceBuffer&) = delete;
-  DeviceBuffer(DeviceBuffer&& o) noexcept { swap(o); }
-  DeviceBuffer& operator=(DeviceBuffer&& o) noexcept {
-    swap(o);
-    return *this;
-  }
-  ~DeviceBuffer() { release(); }
-  void swap(DeviceBuffer& o) {
-    std::swap(p, o.p);
-    std::swap(bytes, o.bytes);
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  // exactly `n` bytes; what was held is freed first, and after a failure the buffer is empty
-  hipError_t alloc(size_t n) {
-    release();
-    const hipError_t e = hipMalloc(&p, n);
-    if (e == hipSuccess) bytes = n;
-    else p = nullptr;
-    return e;
-  }
-  // grow-only: nothing when the capacity suffices, else max(n [+ n / 4], min_bytes) fresh bytes (the contents are lost)
-  hipError_t reserve(size_t n, size_t min_bytes = 0, bool slack = false) {
-    if (n <= bytes) return hipSuccess;
-    return alloc(std::max(slack ? n + n / 4 : n, min_bytes));
-  }
-  template <typename T>
-  T* as() const {
-    return static_cast<T*>(p);
-  }
-};
-// Arrays that share one capacity grow together: all are freed before the first is allocated (the peak does not rise while
-// a handle grows), and after a failure all are empty.
-struct DeviceBufferSize {
-  DeviceBuffer* buffer;
-  size_t bytes;
-};
-inline hipError_t alloc_group(std::initializer_list<DeviceBufferSize> group) {
-  for (const DeviceBufferSize& g : group) g.buffer->release();
-  hipError_t e = hipSuccess;
-  for (const DeviceBufferSize& g : group)
-    if (e == hipSuccess) e = g.buffer->alloc(g.bytes);
-  if (e != hipSuccess)
-    for (const DeviceBufferSize& g : group) g.buffer->release();
-  return e;
-}
-
-// rocPRIM's two calls -- the size of the temporary storage with a null pointer, then the work with identical arguments --
-// from ONE lambda hipError_t(void* tmp, size_t& bytes) that holds the rocPRIM call.  run_with_temp may reallocate `tmp`:
-// only where nothing queued still uses it; launches that share a workspace ask with temp_bytes and make room once.
-template <class Call>
-hipError_t temp_bytes(Call& call, size_t* bytes) {
-  *bytes = 0;
-  return call(nullptr, *bytes);
-}
-template <class Call>
-hipError_t run_with_temp(DeviceBuffer& tmp, Call& call) {
-  size_t bytes = 0;
-  hipError_t e = temp_bytes(call, &bytes);
-  if (e == hipSuccess) e = tmp.reserve(bytes, 8);  // (never null: to rocPRIM a null workspace is the size query)
-  if (e == hipSuccess) e = call(tmp.p, bytes);
-  return e;
-}
 void set_global_error(const std::string& msg);
 
 // The centre of voxel `idx` (one axis) of the block whose low corner on that axis is `origin` = (float)block_index *
@@ -493,6 +582,15 @@ __host__ __device__ __forceinline__ float voxel_centre(float origin, int idx, fl
 inline int alloc_error(vgx_ctx ctx, hipError_t e, const char* what) {
   (void)hipGetLastError();  // (clear the sticky out-of-memory status)
   return set_error(ctx, e == hipErrorOutOfMemory ? VGX_ERR_NOMEM : VGX_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// a host array as a fresh device array of exactly `bytes` (blocking copy); nothing for bytes == 0: `buffer` stays empty
+inline int upload_new(vgx_ctx ctx, DeviceBuffer& buffer, const void* src, size_t bytes) {
+  buffer.release();
+  if (bytes == 0) return VGX_OK;
+  VGX_HIP(ctx, buffer.alloc(bytes));
+  VGX_HIP(ctx, hipMemcpy(buffer.p, src, bytes, hipMemcpyHostToDevice));
+  return VGX_OK;
 }
 
 // What vgx_connect.hip reads of a mesh handle (vgx_mesh_s lives in vgx_mesh.hip).  mesh_view: the caller holds

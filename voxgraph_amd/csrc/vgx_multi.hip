@@ -115,8 +115,9 @@ struct vgx_reg_multi_s {
     vgx_reg_batch batch = nullptr;
     std::vector<int32_t> global;   // global constraint index of local constraint c
     std::vector<int32_t> status;   // per local constraint
-    double* d_all = nullptr;       // VGX_REDUCE_RCCL: [n][45], this shard's rows filled, the rest zero
-    double* h_normal = nullptr;    // pinned [n_local][45]
+    // (both on the shard's device: released with that device set, vgx_reg_multi_destroy)
+    DeviceBuffer d_all;            // double; VGX_REDUCE_RCCL: [n][45], this shard's rows filled, the rest zero
+    PinnedBuffer h_normal;         // double [n_local][45]
     hipEvent_t done = nullptr;
     int rc = VGX_OK;
     std::thread th;
@@ -135,12 +136,11 @@ struct vgx_reg_multi_s {
   int32_t n_nodes = 0;
   // context 0: the complete [n][45] array (gathered from the shards), the list's node structure, the fused
   // buffer it assembles and its pinned mirror
-  double* d_normal_all = nullptr;
-  const double** d_src = nullptr;  // [n] where each constraint's block lies (peer pointers)
+  DeviceBuffer d_normal_all;       // double
+  DeviceBuffer d_src;              // const double* [n]: where each constraint's block lies (peer pointers)
   vgx_reg_assembler assembler = nullptr;
-  double* d_sum = nullptr;
-  double* h_sum = nullptr;         // pinned
-  int64_t sum_cap = 0;
+  DeviceBuffer d_sum;              // double
+  PinnedBuffer h_sum;
   std::mutex call_mu;              // one evaluation at a time
   // VGX_REDUCE_RCCL: one communicator per shard (ncclCommInitAll over the shards' devices)
   int reduction = VGX_REDUCE_PEER_SUM;
@@ -154,16 +154,16 @@ static void run_shard(vgx_reg_multi_s* m, vgx_reg_multi_s::Shard& s) {
     s.rc = vgx_reg_batch_evaluate_normal(s.batch, m->poses, m->n_nodes, nullptr, nullptr,
                                          nl ? s.status.data() : nullptr);
     if (s.rc == VGX_OK && m->reduction == VGX_REDUCE_RCCL)
-      s.rc = vgx_reg_batch_scatter_normal(s.batch, nullptr, s.d_all, 1);
+      s.rc = vgx_reg_batch_scatter_normal(s.batch, nullptr, s.d_all.p, 1);
     if (s.rc == VGX_OK && (hipSetDevice(s.ctx->device) != hipSuccess ||
                            hipEventRecord(s.done, s.ctx->stream) != hipSuccess))
       s.rc = VGX_ERR_HIP;
   } else if (m->mode == 1) {
-    s.rc = vgx_reg_batch_evaluate_normal(s.batch, m->poses, m->n_nodes, nullptr, nl ? s.h_normal : nullptr,
+    s.rc = vgx_reg_batch_evaluate_normal(s.batch, m->poses, m->n_nodes, nullptr, nl ? s.h_normal.as<double>() : nullptr,
                                          nl ? s.status.data() : nullptr);
   } else {
     // cost only (vgx_reg_multi_evaluate_cost): the shard's costs into the first n_local doubles of its pinned block array
-    s.rc = vgx_reg_batch_evaluate_cost(s.batch, m->poses, m->n_nodes, nullptr, nl ? s.h_normal : nullptr,
+    s.rc = vgx_reg_batch_evaluate_cost(s.batch, m->poses, m->n_nodes, nullptr, nl ? s.h_normal.as<double>() : nullptr,
                                        nl ? s.status.data() : nullptr);
   }
 }
@@ -260,17 +260,13 @@ int vgx_reg_multi_destroy(vgx_reg_multi m) {
   for (auto& s : m->shards) {
     (void)hipSetDevice(s->ctx->device);
     if (s->batch) vgx_reg_batch_destroy(s->batch);
-    if (s->d_all) (void)hipFree(s->d_all);
-    if (s->h_normal) (void)hipHostFree(s->h_normal);
+    s->d_all.release();
+    s->h_normal.release();
     if (s->done) (void)hipEventDestroy(s->done);
   }
   if (!m->shards.empty()) (void)hipSetDevice(m->shards[0]->ctx->device);
   if (m->assembler) vgx_reg_assembler_destroy(m->assembler);
-  if (m->d_normal_all) (void)hipFree(m->d_normal_all);
-  if (m->d_src) (void)hipFree((void*)m->d_src);
-  if (m->d_sum) (void)hipFree(m->d_sum);
-  if (m->h_sum) (void)hipHostFree(m->h_sum);
-  delete m;
+  delete m;  // (context 0's buffers, its device set)
   return VGX_OK;
 }
 
@@ -321,7 +317,7 @@ int vgx_reg_multi_create(int32_t n_ctx, const vgx_ctx* ctxs, int32_t n, const vg
     s.status.assign((size_t)nl, 0);
     if (hipSetDevice(s.ctx->device) != hipSuccess ||
         hipEventCreateWithFlags(&s.done, hipEventDisableTiming) != hipSuccess ||
-        (nl > 0 && hipHostMalloc((void**)&s.h_normal, (size_t)nl * kNormalSize * sizeof(double), hipHostMallocDefault) != hipSuccess))
+        (nl > 0 && s.h_normal.alloc((size_t)nl * kNormalSize * sizeof(double)) != hipSuccess))
       rc = set_error(ctx0, VGX_ERR_HIP, "vgx_reg_multi_create: event / pinned buffer creation failed");
     // shard 0 reads the other shards' buffers directly (xGMI peer mapping)
     if (rc == VGX_OK && k > 0 && s.ctx->device != ctx0->device) {
@@ -344,11 +340,11 @@ int vgx_reg_multi_create(int32_t n_ctx, const vgx_ctx* ctxs, int32_t n, const vg
       std::vector<const double*> src((size_t)n, nullptr);
       for (auto& sp : m->shards)
         for (size_t c = 0; c < sp->global.size(); ++c)
-          src[(size_t)sp->global[c]] = sp->batch->d_normal + c * kNormalSize;
+          src[(size_t)sp->global[c]] = sp->batch->d_normal.as<double>() + c * kNormalSize;
       if (hipSetDevice(ctx0->device) != hipSuccess ||
-          hipMalloc((void**)&m->d_src, (size_t)n * sizeof(double*)) != hipSuccess ||
-          hipMemcpy((void*)m->d_src, src.data(), (size_t)n * sizeof(double*), hipMemcpyHostToDevice) != hipSuccess ||
-          hipMalloc(&m->d_normal_all, (size_t)n * kNormalSize * sizeof(double)) != hipSuccess)
+          m->d_src.alloc((size_t)n * sizeof(double*)) != hipSuccess ||
+          hipMemcpy(m->d_src.p, src.data(), (size_t)n * sizeof(double*), hipMemcpyHostToDevice) != hipSuccess ||
+          m->d_normal_all.alloc((size_t)n * kNormalSize * sizeof(double)) != hipSuccess)
         rc = set_error(ctx0, VGX_ERR_NOMEM, "vgx_reg_multi_create: context 0's gather buffers");
     }
   }
@@ -387,9 +383,9 @@ int vgx_reg_multi_set_reduction(vgx_reg_multi m, int32_t reduction) {
   }
   if (reduction == VGX_REDUCE_RCCL)
     for (auto& sp : m->shards)
-      if (!sp->d_all) {
+      if (!sp->d_all.p) {
         VGX_HIP(ctx0, hipSetDevice(sp->ctx->device));
-        VGX_HIP(ctx0, hipMalloc(&sp->d_all, std::max<size_t>((size_t)m->n * kNormalSize * sizeof(double), 8)));
+        VGX_HIP(ctx0, sp->d_all.alloc(std::max<size_t>((size_t)m->n * kNormalSize * sizeof(double), 8)));
       }
   m->reduction = reduction;
   return VGX_OK;
@@ -409,16 +405,11 @@ int vgx_reg_multi_evaluate_fused(vgx_reg_multi m, const double* poses, int32_t n
   vgx_ctx ctx0 = m->shards[0]->ctx;
   const int64_t size = vgx_reg_fused_size(n_nodes, m->n);
   VGX_HIP(ctx0, hipSetDevice(ctx0->device));
-  if (m->sum_cap < size) {
+  const size_t sum_bytes = (size_t)size * sizeof(double);
+  if (sum_bytes > m->d_sum.bytes || sum_bytes > m->h_sum.bytes) {
     VGX_HIP(ctx0, hipStreamSynchronize(ctx0->stream));
-    if (m->d_sum) (void)hipFree(m->d_sum);
-    if (m->h_sum) (void)hipHostFree(m->h_sum);
-    m->d_sum = nullptr;
-    m->h_sum = nullptr;
-    m->sum_cap = 0;
-    VGX_HIP(ctx0, hipMalloc(&m->d_sum, (size_t)size * sizeof(double)));
-    VGX_HIP(ctx0, hipHostMalloc((void**)&m->h_sum, (size_t)size * sizeof(double), hipHostMallocDefault));
-    m->sum_cap = size;
+    VGX_HIP(ctx0, m->d_sum.reserve(sum_bytes));
+    VGX_HIP(ctx0, m->h_sum.reserve(sum_bytes));
   }
   int rc = dispatch(m, 0, poses, n_nodes);
   if (rc != VGX_OK) {
@@ -429,7 +420,7 @@ int vgx_reg_multi_evaluate_fused(vgx_reg_multi m, const double* poses, int32_t n
   // The per-constraint blocks meet on context 0 -- copied, not summed -- and the fused buffer is assembled
   // there ONCE, in list order: bit for bit what one vgx_reg_batch over the whole list computes, whatever the
   // number of contexts and the placement (tests/test_multi_gpu.py: 8 contexts == 2 contexts == single batch).
-  const double* d_all = m->d_normal_all;
+  const double* d_all = m->d_normal_all.as<double>();
   if (m->reduction == VGX_REDUCE_RCCL) {
     // one all-reduce per solver evaluation: every context's [n][45] array in place, each on its own stream
     // (behind that context's evaluation and scatter).  A row is non-zero on exactly one context, so the sum is
@@ -448,7 +439,7 @@ int vgx_reg_multi_evaluate_fused(vgx_reg_multi m, const double* poses, int32_t n
       }
       // summed as 64-bit INTEGERS: every word is non-zero on at most one context, so the integer sum IS that
       // context's bit pattern whatever the order -- an f64 sum would also turn a -0.0 into +0.0
-      r = api.AllReduce(s.d_all, s.d_all, (size_t)m->n * kNormalSize, ncclInt64, ncclSum, m->comms[k], s.ctx->stream);
+      r = api.AllReduce(s.d_all.p, s.d_all.p, (size_t)m->n * kNormalSize, ncclInt64, ncclSum, m->comms[k], s.ctx->stream);
     }
     if (group_open) {
       const ncclResult_t r2 = api.GroupEnd();
@@ -457,23 +448,23 @@ int vgx_reg_multi_evaluate_fused(vgx_reg_multi m, const double* poses, int32_t n
     if (device_failed) return set_error(ctx0, VGX_ERR_HIP, "vgx_reg_multi: hipSetDevice failed while enqueuing the all-reduce");
     if (r != ncclSuccess) return set_error(ctx0, VGX_ERR_HIP, std::string("ncclAllReduce: ") + api.GetErrorString(r));
     VGX_HIP(ctx0, hipSetDevice(ctx0->device));
-    d_all = m->shards[0]->d_all;
+    d_all = m->shards[0]->d_all.as<double>();
   } else if (m->n > 0) {
     // one gather per solver evaluation, on context 0's stream, behind every context's evaluation
     VGX_HIP(ctx0, hipSetDevice(ctx0->device));
     for (size_t k = 1; k < m->shards.size(); ++k)
       VGX_HIP(ctx0, hipStreamWaitEvent(ctx0->stream, m->shards[k]->done, 0));
     const long long work = (long long)m->n * kNormalSize;
-    hipLaunchKernelGGL(multi_gather_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, ctx0->stream, m->d_src,
-                       (long long)m->n, m->d_normal_all);
+    hipLaunchKernelGGL(multi_gather_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, ctx0->stream,
+                       m->d_src.as<const double*>(), (long long)m->n, m->d_normal_all.as<double>());
     VGX_HIP(ctx0, hipGetLastError());
   }
-  rc = vgx_reg_assembler_assemble(m->assembler, d_all, n_nodes, m->d_sum);
+  rc = vgx_reg_assembler_assemble(m->assembler, d_all, n_nodes, m->d_sum.p);
   if (rc != VGX_OK) return rc;
-  const double* d_result = m->d_sum;
-  VGX_HIP(ctx0, hipMemcpyAsync(m->h_sum, d_result, (size_t)size * sizeof(double), hipMemcpyDeviceToHost, ctx0->stream));
+  const double* d_result = m->d_sum.as<double>();
+  VGX_HIP(ctx0, hipMemcpyAsync(m->h_sum.p, d_result, (size_t)size * sizeof(double), hipMemcpyDeviceToHost, ctx0->stream));
   VGX_HIP(ctx0, hipStreamSynchronize(ctx0->stream));
-  std::memcpy(fused_host, m->h_sum, (size_t)size * sizeof(double));
+  std::memcpy(fused_host, m->h_sum.p, (size_t)size * sizeof(double));
   if (status)
     for (auto& s : m->shards)
       for (size_t c = 0; c < s->global.size(); ++c) status[s->global[c]] = s->status[c];
@@ -494,7 +485,7 @@ int vgx_reg_multi_evaluate_normal(vgx_reg_multi m, const double* poses, int32_t 
   // no collective: every shard hands its own constraints' blocks back
   for (auto& s : m->shards)
     for (size_t c = 0; c < s->global.size(); ++c) {
-      std::memcpy(normal_host + (size_t)s->global[c] * kNormalSize, s->h_normal + c * kNormalSize,
+      std::memcpy(normal_host + (size_t)s->global[c] * kNormalSize, s->h_normal.as<double>() + c * kNormalSize,
                   kNormalSize * sizeof(double));
       if (status) status[s->global[c]] = s->status[c];
     }
@@ -515,7 +506,7 @@ int vgx_reg_multi_evaluate_cost(vgx_reg_multi m, const double* poses, int32_t n_
   }
   for (auto& s : m->shards)
     for (size_t c = 0; c < s->global.size(); ++c) {
-      cost_host[s->global[c]] = s->h_normal[c];
+      cost_host[s->global[c]] = s->h_normal.as<double>()[c];
       if (status) status[s->global[c]] = s->status[c];
     }
   return VGX_OK;

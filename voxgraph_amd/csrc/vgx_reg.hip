@@ -1745,7 +1745,7 @@ vgx::ConstraintDev vgx_reg_s::describe() const {
   c.xyzd = ps.d_xyzd;
   c.weight = ps.d_weight;
   if (cfg.sampling_ratio != -1.0f) {
-    c.sample_raw = d_sample_raw;  // callers that stage elsewhere overwrite this
+    c.sample_raw = d_sample_raw.as<uint32_t>();  // callers that stage elsewhere overwrite this
     c.cumulative = ps.d_cumulative;
     c.search_lut = ps.d_search_lut;
     c.search_buckets = ps.search_buckets;
@@ -1934,8 +1934,6 @@ int vgx_reg_destroy(vgx_reg r) {
   }
   (void)hipSetDevice(r->ctx->device);
   (void)hipStreamSynchronize(r->ctx->stream);
-  if (r->d_sample_raw) (void)hipFree(r->d_sample_raw);
-  if (r->h_sample_raw) (void)hipHostFree(r->h_sample_raw);
   if (r->rng.d_state) (void)hipFree(r->rng.d_state);
   // the submaps this cost function kept alive (vgx_submap_destroy was called on them while it existed)
   vgx_submap orphan[2] = {nullptr, nullptr};
@@ -2021,25 +2019,13 @@ static int reg_evaluate_impl(const char* fn, vgx_reg r, const double ref_pose[4]
   if (!sl.stream) {
     VGX_HIP(ctx, hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking));
     VGX_HIP(ctx, hipEventCreateWithFlags(&sl.order, hipEventDisableTiming));
-    VGX_HIP(ctx, hipHostMalloc((void**)&sl.h_out, Context::kSmallOutputBytes, hipHostMallocDefault));
+    VGX_HIP(ctx, sl.h_out.alloc(Context::kSmallOutputBytes));
   }
-  if (sl.out_rows < n) {
-    if (sl.d_out) (void)hipFree(sl.d_out);
-    sl.d_out = nullptr;
-    sl.out_rows = 0;
-    VGX_HIP(ctx, hipMalloc(&sl.d_out, (size_t)n * 9 * sizeof(double)));
-    sl.out_rows = n;
-  }
+  VGX_HIP(ctx, sl.d_out.reserve((size_t)n * 9 * sizeof(double)));
   const bool sampled = r->cfg.sampling_ratio != -1.0f;
-  if (sampled && sl.raw_cap < 2 * n) {
-    if (sl.d_raw) (void)hipFree(sl.d_raw);
-    if (sl.h_raw) (void)hipHostFree(sl.h_raw);
-    sl.d_raw = nullptr;
-    sl.h_raw = nullptr;
-    sl.raw_cap = 0;
-    VGX_HIP(ctx, hipMalloc(&sl.d_raw, (size_t)n * 2 * sizeof(uint32_t)));
-    VGX_HIP(ctx, hipHostMalloc((void**)&sl.h_raw, (size_t)n * 2 * sizeof(uint32_t), hipHostMallocDefault));
-    sl.raw_cap = 2 * n;
+  if (sampled) {
+    VGX_HIP(ctx, sl.d_raw.reserve((size_t)n * 2 * sizeof(uint32_t)));
+    VGX_HIP(ctx, sl.h_raw.reserve((size_t)n * 2 * sizeof(uint32_t)));
   }
   if (do_cloud) {
     const hipError_t e = K->d_cloud.reserve((size_t)n * 32, 4096 * 32, true);
@@ -2052,20 +2038,20 @@ static int reg_evaluate_impl(const char* fn, vgx_reg r, const double ref_pose[4]
   }
   PosePack pack;
   make_pose_pack(ref_pose, read_pose, &pack);
-  double* d_res = sl.d_out;
-  double* d_jr = jac_ref ? sl.d_out + n : nullptr;
-  double* d_je = jac_read ? sl.d_out + 5 * n : nullptr;
+  double* d_res = sl.d_out.as<double>();
+  double* d_jr = jac_ref ? d_res + n : nullptr;
+  double* d_je = jac_read ? d_res + 5 * n : nullptr;
   // everything already enqueued on the context stream (uploads, extraction) happens before this
   VGX_HIP(ctx, hipEventRecord(sl.order, ctx->stream));
   VGX_HIP(ctx, hipStreamWaitEvent(sl.stream, sl.order, 0));
   ConstraintDev desc = r->describe();
   if (sampled) {
     // this Evaluate's engine outputs (drawn under the lock: the engine is shared)
-    const int rc_draw = r->draw_raw(sl.h_raw);
+    const int rc_draw = r->draw_raw(sl.h_raw.as<uint32_t>());
     if (rc_draw != VGX_OK) return rc_draw;
-    VGX_HIP(ctx, hipMemcpyAsync(sl.d_raw, sl.h_raw, (size_t)n * 2 * sizeof(uint32_t), hipMemcpyHostToDevice,
+    VGX_HIP(ctx, hipMemcpyAsync(sl.d_raw.p, sl.h_raw.p, (size_t)n * 2 * sizeof(uint32_t), hipMemcpyHostToDevice,
                                 sl.stream));
-    desc.sample_raw = sl.d_raw;
+    desc.sample_raw = sl.d_raw.as<uint32_t>();
   }
   if (reg_status(r) == VGX_EVALUATE_FALSE) return VGX_EVALUATE_FALSE;
   launch_points_single<double>(sl.stream, r->reading->vps, desc, pack, d_res, d_jr, d_je);
@@ -2081,13 +2067,14 @@ static int reg_evaluate_impl(const char* fn, vgx_reg r, const double ref_pose[4]
   // caller's (pageable) arrays, three copies that block their caller.
   hipError_t e = hipSuccess;
   const size_t out_bytes = (size_t)n * 9 * sizeof(double);
-  if (out_bytes <= Context::kSmallOutputBytes && sl.h_out) {
-    e = hipMemcpyAsync(sl.h_out, d_res, out_bytes, hipMemcpyDeviceToHost, sl.stream);
+  if (out_bytes <= Context::kSmallOutputBytes && sl.h_out.p) {
+    e = hipMemcpyAsync(sl.h_out.p, d_res, out_bytes, hipMemcpyDeviceToHost, sl.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(sl.stream);
     if (e == hipSuccess) {
-      std::memcpy(residuals, sl.h_out, (size_t)n * sizeof(double));
-      if (jac_ref) std::memcpy(jac_ref, sl.h_out + n, (size_t)n * 4 * sizeof(double));
-      if (jac_read) std::memcpy(jac_read, sl.h_out + 5 * n, (size_t)n * 4 * sizeof(double));
+      const double* h_out = sl.h_out.as<double>();
+      std::memcpy(residuals, h_out, (size_t)n * sizeof(double));
+      if (jac_ref) std::memcpy(jac_ref, h_out + n, (size_t)n * 4 * sizeof(double));
+      if (jac_read) std::memcpy(jac_read, h_out + 5 * n, (size_t)n * 4 * sizeof(double));
     }
   } else {
     e = hipMemcpyAsync(residuals, d_res, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, sl.stream);
@@ -2194,13 +2181,11 @@ int vgx_reg_evaluate_device_f32(vgx_reg r, const double ref_pose[4], const doubl
   const int64_t n = r->num_residuals;
   if (r->cfg.sampling_ratio != -1.0f && n > 0) {
     VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (!r->d_sample_raw) {
-      VGX_HIP(ctx, hipMalloc(&r->d_sample_raw, (size_t)n * 2 * sizeof(uint32_t)));
-      VGX_HIP(ctx, hipHostMalloc((void**)&r->h_sample_raw, (size_t)n * 2 * sizeof(uint32_t), hipHostMallocDefault));
-    }
-    const int rc_draw = r->draw_raw(r->h_sample_raw);
+    VGX_HIP(ctx, r->d_sample_raw.reserve((size_t)n * 2 * sizeof(uint32_t)));
+    VGX_HIP(ctx, r->h_sample_raw.reserve((size_t)n * 2 * sizeof(uint32_t)));
+    const int rc_draw = r->draw_raw(r->h_sample_raw.as<uint32_t>());
     if (rc_draw != VGX_OK) return rc_draw;
-    VGX_HIP(ctx, hipMemcpyAsync(r->d_sample_raw, r->h_sample_raw, (size_t)n * 2 * sizeof(uint32_t),
+    VGX_HIP(ctx, hipMemcpyAsync(r->d_sample_raw.p, r->h_sample_raw.p, (size_t)n * 2 * sizeof(uint32_t),
                                 hipMemcpyHostToDevice, ctx->stream));
   }
   if (reg_status(r) == VGX_EVALUATE_FALSE) return VGX_EVALUATE_FALSE;
@@ -2358,9 +2343,9 @@ int vgx_reg_batch_create(vgx_ctx ctx, int32_t n, const vgx_reg* regs, const int3
     }
     b->any_sampling = total > 0;
     if (b->any_sampling) {
-      if (hipMalloc(&b->d_raw, (size_t)total * sizeof(uint32_t)) != hipSuccess ||
-          hipMalloc(&b->d_drawn, (size_t)b->row_offset[(size_t)n] * sizeof(float4)) != hipSuccess ||
-          hipMalloc(&b->d_drawn_idx, (size_t)b->row_offset[(size_t)n] * sizeof(int32_t)) != hipSuccess) {
+      if (b->d_raw.alloc((size_t)total * sizeof(uint32_t)) != hipSuccess ||
+          b->d_drawn.alloc((size_t)b->row_offset[(size_t)n] * sizeof(float4)) != hipSuccess ||
+          b->d_drawn_idx.alloc((size_t)b->row_offset[(size_t)n] * sizeof(int32_t)) != hipSuccess) {
         vgx_reg_batch_destroy(b);
         return set_error(ctx, VGX_ERR_NOMEM, "vgx_reg_batch_create: sampler stream buffer allocation failed");
       }
@@ -2368,8 +2353,8 @@ int vgx_reg_batch_create(vgx_ctx ctx, int32_t n, const vgx_reg* regs, const int3
       for (int c = 0; c < n; ++c) {
         const int j = job_of[(size_t)c];
         if (j < 0) continue;
-        desc[(size_t)c].sample_raw = b->d_raw + b->stream_jobs[(size_t)j].offset + used[(size_t)j];
-        desc[(size_t)c].sample_pts = b->d_drawn;  // this evaluation's drawn points, by row (reg_draw_kernel)
+        desc[(size_t)c].sample_raw = b->d_raw.as<uint32_t>() + b->stream_jobs[(size_t)j].offset + used[(size_t)j];
+        desc[(size_t)c].sample_pts = b->d_drawn.as<float4>();  // this evaluation's drawn points, by row (reg_draw_kernel)
         used[(size_t)j] += 2 * regs[c]->num_residuals;
       }
       std::vector<StreamJobDev> jd(b->stream_jobs.size());
@@ -2379,10 +2364,10 @@ int vgx_reg_batch_create(vgx_ctx ctx, int32_t n, const vgx_reg* regs, const int3
           vgx_reg_batch_destroy(b);
           return set_error(ctx, VGX_ERR_NOMEM, "vgx_reg_batch_create: sampler state allocation failed");
         }
-        jd[j] = {e->d_state, b->d_raw + b->stream_jobs[j].offset, (long long)b->stream_jobs[j].count};
+        jd[j] = {e->d_state, b->d_raw.as<uint32_t>() + b->stream_jobs[j].offset, (long long)b->stream_jobs[j].count};
       }
-      if (hipMalloc(&b->d_stream_jobs, jd.size() * sizeof(StreamJobDev)) != hipSuccess ||
-          hipMemcpy(b->d_stream_jobs, jd.data(), jd.size() * sizeof(StreamJobDev), hipMemcpyHostToDevice) != hipSuccess) {
+      if (b->d_stream_jobs.alloc(jd.size() * sizeof(StreamJobDev)) != hipSuccess ||
+          hipMemcpy(b->d_stream_jobs.p, jd.data(), jd.size() * sizeof(StreamJobDev), hipMemcpyHostToDevice) != hipSuccess) {
         vgx_reg_batch_destroy(b);
         return set_error(ctx, VGX_ERR_NOMEM, "vgx_reg_batch_create: sampler job table upload failed");
       }
@@ -2394,35 +2379,27 @@ int vgx_reg_batch_create(vgx_ctx ctx, int32_t n, const vgx_reg* regs, const int3
   ex->csr_nodes = max_node + 1;
   std::vector<int32_t> first, items;
   build_node_csr(n, node_pair, ex->csr_nodes, first, items);
-  auto up = [&](const void* src, size_t bytes, void** dst) -> int {
-    *dst = nullptr;
-    if (bytes == 0) return VGX_OK;
-    VGX_HIP(ctx, hipMalloc(dst, bytes));
-    VGX_HIP(ctx, hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-    return VGX_OK;
-  };
-  int rc = up(desc.data(), desc.size() * sizeof(ConstraintDev), (void**)&b->d_desc);
-  if (rc == VGX_OK) rc = up(b->tiles.data(), b->tiles.size() * sizeof(Tile), (void**)&b->d_tiles);
-  if (rc == VGX_OK && !b->tiles.empty() && hipMalloc(&b->d_tile_dead, b->tiles.size()) != hipSuccess) rc = VGX_ERR_NOMEM;
+  int rc = upload_new(ctx, b->d_desc, desc.data(), desc.size() * sizeof(ConstraintDev));
+  if (rc == VGX_OK) rc = upload_new(ctx, b->d_tiles, b->tiles.data(), b->tiles.size() * sizeof(Tile));
+  if (rc == VGX_OK && !b->tiles.empty() && b->d_tile_dead.alloc(b->tiles.size()) != hipSuccess) rc = VGX_ERR_NOMEM;
   if (rc == VGX_OK && b->any_sampling) {
     const std::vector<Tile> dt = make_draw_order(desc, points_tile_first, b->tiles);
     b->n_draw_tiles = (int32_t)dt.size();
-    rc = up(dt.data(), dt.size() * sizeof(Tile), (void**)&b->d_draw_tiles);
+    rc = upload_new(ctx, b->d_draw_tiles, dt.data(), dt.size() * sizeof(Tile));
   }
-  if (rc == VGX_OK) rc = up(ex->reduce_tiles.data(), ex->reduce_tiles.size() * sizeof(Tile), (void**)&ex->d_reduce_tiles);
-  if (rc == VGX_OK) rc = up(tile_first.data(), tile_first.size() * sizeof(int32_t), (void**)&b->d_tile_first);
-  if (rc == VGX_OK) rc = up(b->node_pair.data(), b->node_pair.size() * sizeof(int32_t), (void**)&b->d_node_pair);
-  if (rc == VGX_OK) rc = up(b->global_index.data(), b->global_index.size() * sizeof(int32_t), (void**)&b->d_global_index);
-  if (rc == VGX_OK) rc = up(first.data(), first.size() * sizeof(int32_t), (void**)&ex->d_node_first);
-  if (rc == VGX_OK) rc = up(items.data(), items.size() * sizeof(int32_t), (void**)&ex->d_node_items);
+  if (rc == VGX_OK) rc = upload_new(ctx, ex->d_reduce_tiles, ex->reduce_tiles.data(), ex->reduce_tiles.size() * sizeof(Tile));
+  if (rc == VGX_OK) rc = upload_new(ctx, b->d_tile_first, tile_first.data(), tile_first.size() * sizeof(int32_t));
+  if (rc == VGX_OK) rc = upload_new(ctx, b->d_node_pair, b->node_pair.data(), b->node_pair.size() * sizeof(int32_t));
+  if (rc == VGX_OK) rc = upload_new(ctx, b->d_global_index, b->global_index.data(), b->global_index.size() * sizeof(int32_t));
+  if (rc == VGX_OK) rc = upload_new(ctx, ex->d_node_first, first.data(), first.size() * sizeof(int32_t));
+  if (rc == VGX_OK) rc = upload_new(ctx, ex->d_node_items, items.data(), items.size() * sizeof(int32_t));
   if (rc == VGX_OK && n > 0) {
-    if (hipMalloc(&b->d_pack, (size_t)n * sizeof(PosePack)) != hipSuccess ||
-        hipHostMalloc(&b->h_pack, 2 * (size_t)n * sizeof(PosePack)) != hipSuccess ||
-        hipEventCreateWithFlags(&b->pack_copied[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&b->pack_copied[1], hipEventDisableTiming) != hipSuccess ||
-        hipMalloc(&b->d_partials, std::max<size_t>(1, ex->reduce_tiles.size()) * (kBlockThreads / 64) * kPartialSize * sizeof(double)) != hipSuccess ||
-        hipMalloc(&b->d_normal, (size_t)n * kNormalSize * sizeof(double)) != hipSuccess ||
-        hipHostMalloc((void**)&b->h_normal, (size_t)n * kNormalSize * sizeof(double), hipHostMallocDefault) != hipSuccess)
+    // (allocated once, in this order: the headline kernel's speed depends on where its arrays land)
+    if (b->d_pack.alloc((size_t)n * sizeof(PosePack)) != hipSuccess ||
+        b->pack_stage.reserve((size_t)n * sizeof(PosePack)) != hipSuccess ||
+        b->d_partials.alloc(std::max<size_t>(1, ex->reduce_tiles.size()) * (kBlockThreads / 64) * kPartialSize * sizeof(double)) != hipSuccess ||
+        b->d_normal.alloc((size_t)n * kNormalSize * sizeof(double)) != hipSuccess ||
+        b->h_normal.alloc((size_t)n * kNormalSize * sizeof(double)) != hipSuccess)
       rc = set_error(ctx, VGX_ERR_NOMEM, "vgx_reg_batch_create: device allocation failed");
   }
   if (rc != VGX_OK) {
@@ -2449,30 +2426,6 @@ int vgx_reg_batch_destroy(vgx_reg_batch b) {
       if (--r->users == 0 && r->destroy_requested) orphans.push_back(r);
   }
   for (vgx_reg r : orphans) (void)vgx_reg_destroy(r);
-  for (int a = 0; a < 3; ++a)
-    if (b->d_rows[a]) (void)hipFree(b->d_rows[a]);
-  if (b->h_rows) (void)hipHostFree(b->h_rows);
-  if (b->d_raw) (void)hipFree(b->d_raw);
-  if (b->d_stream_jobs) (void)hipFree(b->d_stream_jobs);
-  if (b->d_node_first) (void)hipFree(b->d_node_first);
-  if (b->d_node_items) (void)hipFree(b->d_node_items);
-  if (b->d_reduce_tiles) (void)hipFree(b->d_reduce_tiles);
-  if (b->d_desc) (void)hipFree(b->d_desc);
-  if (b->d_pack) (void)hipFree(b->d_pack);
-  if (b->h_pack) (void)hipHostFree(b->h_pack);
-  if (b->h_normal) (void)hipHostFree(b->h_normal);
-  for (int k = 0; k < 2; ++k)
-    if (b->pack_copied[k]) (void)hipEventDestroy(b->pack_copied[k]);
-  if (b->d_tiles) (void)hipFree(b->d_tiles);
-  if (b->d_tile_dead) (void)hipFree(b->d_tile_dead);
-  if (b->d_drawn) (void)hipFree(b->d_drawn);
-  if (b->d_drawn_idx) (void)hipFree(b->d_drawn_idx);
-  if (b->d_draw_tiles) (void)hipFree(b->d_draw_tiles);
-  if (b->d_tile_first) (void)hipFree(b->d_tile_first);
-  if (b->d_partials) (void)hipFree(b->d_partials);
-  if (b->d_normal) (void)hipFree(b->d_normal);
-  if (b->d_node_pair) (void)hipFree(b->d_node_pair);
-  if (b->d_global_index) (void)hipFree(b->d_global_index);
   delete b;
   return VGX_OK;
 }
@@ -2506,17 +2459,17 @@ static int batch_begin(vgx_reg_batch b) {
     if (rc != VGX_OK) return rc;
   }
   hipLaunchKernelGGL(mt_generate_kernel, dim3((unsigned)b->stream_jobs.size()), dim3(kMtThreads), 0, ctx->stream,
-                     (const StreamJobDev*)b->d_stream_jobs);
+                     b->d_stream_jobs.as<StreamJobDev>());
   VGX_HIP(ctx, hipGetLastError());
   // persistent: 8 x kDrawWgsPerXcdDefault workgroups walk the tile sequence; more workgroups than tiles: one per tile
   const int per_xcd = 8 * kDrawWgsPerXcdDefault < b->n_draw_tiles ? kDrawWgsPerXcdDefault : (b->n_draw_tiles + 7) / 8;
   const dim3 grid((unsigned)(8 * per_xcd));
-  hipLaunchKernelGGL(reg_draw_kernel, grid, dim3(256), 0, ctx->stream, (const ConstraintDev*)b->d_desc,
-                     (const Tile*)b->d_draw_tiles, (int)b->n_draw_tiles, per_xcd, b->d_drawn_idx);
+  hipLaunchKernelGGL(reg_draw_kernel, grid, dim3(256), 0, ctx->stream, b->d_desc.as<ConstraintDev>(),
+                     b->d_draw_tiles.as<Tile>(), (int)b->n_draw_tiles, per_xcd, b->d_drawn_idx.as<int32_t>());
   VGX_HIP(ctx, hipGetLastError());
-  hipLaunchKernelGGL(reg_gather_points_kernel, grid, dim3(256), 0, ctx->stream, (const ConstraintDev*)b->d_desc,
-                     (const Tile*)b->d_draw_tiles, (int)b->n_draw_tiles, per_xcd, (const int32_t*)b->d_drawn_idx,
-                     b->d_drawn);
+  hipLaunchKernelGGL(reg_gather_points_kernel, grid, dim3(256), 0, ctx->stream, b->d_desc.as<ConstraintDev>(),
+                     b->d_draw_tiles.as<Tile>(), (int)b->n_draw_tiles, per_xcd, b->d_drawn_idx.as<int32_t>(),
+                     b->d_drawn.as<float4>());
   VGX_HIP(ctx, hipGetLastError());
   return VGX_OK;
 }
@@ -2527,10 +2480,10 @@ static int batch_begin(vgx_reg_batch b) {
 static int batch_upload_packs(vgx_reg_batch b, const double* poses, int32_t n_nodes, int32_t* status) {
   vgx_ctx ctx = b->ctx;
   if (b->n == 0) return VGX_OK;
-  const int turn = b->pack_turn;
-  b->pack_turn ^= 1;
-  VGX_HIP(ctx, hipEventSynchronize(b->pack_copied[turn]));
-  PosePack* stage = b->h_pack + (size_t)turn * b->n;
+  int turn = 0;
+  hipError_t waited = hipSuccess;
+  PosePack* stage = static_cast<PosePack*>(b->pack_stage.next(&turn, &waited));
+  VGX_HIP(ctx, waited);
   for (int c = 0; c < b->n; ++c) {
     int i = b->node_pair[2 * (size_t)c], j = b->node_pair[2 * (size_t)c + 1];
     if (i >= n_nodes || j >= n_nodes)
@@ -2538,9 +2491,9 @@ static int batch_upload_packs(vgx_reg_batch b, const double* poses, int32_t n_no
     make_pose_pack(poses + 4 * (size_t)i, poses + 4 * (size_t)j, &stage[c]);
     if (status) status[c] = reg_status(b->regs[(size_t)c]);
   }
-  VGX_HIP(ctx, hipMemcpyAsync(b->d_pack, stage, (size_t)b->n * sizeof(PosePack),
+  VGX_HIP(ctx, hipMemcpyAsync(b->d_pack.as<PosePack>(), stage, (size_t)b->n * sizeof(PosePack),
                               hipMemcpyHostToDevice, ctx->stream));
-  VGX_HIP(ctx, hipEventRecord(b->pack_copied[turn], ctx->stream));
+  VGX_HIP(ctx, b->pack_stage.record(turn, ctx->stream));
   return VGX_OK;
 }
 
@@ -2554,7 +2507,7 @@ static int apply_launch_order(vgx_reg_batch b, const std::vector<Tile>& tiles, T
   const int n_tiles = (int)tiles.size();
   DeviceBuffer s_live;
   VGX_HIP(ctx, s_live.alloc((size_t)n_tiles * sizeof(int32_t)));
-  hipLaunchKernelGGL(reg_tile_live_kernel, dim3(n_tiles), dim3(64), 0, ctx->stream, b->d_desc, b->d_pack,
+  hipLaunchKernelGGL(reg_tile_live_kernel, dim3(n_tiles), dim3(64), 0, ctx->stream, b->d_desc.as<ConstraintDev>(), b->d_pack.as<PosePack>(),
                      d_tiles, n_tiles, s_live.as<int32_t>());
   VGX_HIP(ctx, hipGetLastError());
   std::vector<int32_t> work((size_t)n_tiles);
@@ -2579,12 +2532,12 @@ int vgx_reg_batch_evaluate_points(vgx_reg_batch b, const double* poses, int32_t 
   if (rc != VGX_OK) return rc;
   if (b->n == 0) return VGX_OK;
   if (!b->points_order_made && !b->tiles.empty()) {
-    rc = apply_launch_order(b, b->tiles, b->d_tiles, b->host_points_tile_first, /*points_pass=*/true);
+    rc = apply_launch_order(b, b->tiles, b->d_tiles.as<Tile>(), b->host_points_tile_first, /*points_pass=*/true);
     if (rc != VGX_OK) return rc;
     b->points_order_made = true;
   }
-  launch_points<float>(ctx, b->regs[0]->reading->vps, b->layout, b->d_desc, b->d_pack, b->d_tiles, b->d_tile_dead,
-                       (int)b->tiles.size(), d_residuals, d_jac_ref, d_jac_read);
+  launch_points<float>(ctx, b->regs[0]->reading->vps, b->layout, b->d_desc.as<ConstraintDev>(), b->d_pack.as<PosePack>(),
+                       b->d_tiles.as<Tile>(), b->d_tile_dead.as<unsigned char>(), (int)b->tiles.size(), d_residuals, d_jac_ref, d_jac_read);
   VGX_HIP(ctx, hipGetLastError());
   return VGX_OK;
 }
@@ -2604,12 +2557,12 @@ int vgx_reg_batch_evaluate_points_f64(vgx_reg_batch b, const double* poses, int3
   if (rc != VGX_OK) return rc;
   if (b->n == 0) return VGX_OK;
   if (!b->points_order_made && !b->tiles.empty()) {
-    rc = apply_launch_order(b, b->tiles, b->d_tiles, b->host_points_tile_first, /*points_pass=*/true);
+    rc = apply_launch_order(b, b->tiles, b->d_tiles.as<Tile>(), b->host_points_tile_first, /*points_pass=*/true);
     if (rc != VGX_OK) return rc;
     b->points_order_made = true;
   }
-  launch_points<double>(ctx, b->regs[0]->reading->vps, b->layout, b->d_desc, b->d_pack, b->d_tiles, b->d_tile_dead,
-                        (int)b->tiles.size(), d_residuals, d_jac_ref, d_jac_read);
+  launch_points<double>(ctx, b->regs[0]->reading->vps, b->layout, b->d_desc.as<ConstraintDev>(), b->d_pack.as<PosePack>(),
+                       b->d_tiles.as<Tile>(), b->d_tile_dead.as<unsigned char>(), (int)b->tiles.size(), d_residuals, d_jac_ref, d_jac_read);
   VGX_HIP(ctx, hipGetLastError());
   return VGX_OK;
 }
@@ -2629,30 +2582,27 @@ int vgx_reg_batch_evaluate_rows_f64(vgx_reg_batch b, const double* poses, int32_
     const size_t bytes[3] = {(size_t)std::max<int64_t>(R, 1) * 8, (size_t)std::max<int64_t>(R, 1) * 32, (size_t)std::max<int64_t>(R, 1) * 32};
     const bool want[3] = {true, want_jac_ref != 0, want_jac_read != 0};
     for (int a = 0; a < 3; ++a)
-      if (want[a] && !b->d_rows[a] && hipMalloc(&b->d_rows[a], bytes[a]) != hipSuccess) {
+      if (want[a] && !b->d_rows[a].p && b->d_rows[a].alloc(bytes[a]) != hipSuccess) {
         (void)hipGetLastError();
         return set_error(ctx, VGX_ERR_NOMEM, "vgx_reg_batch_evaluate_rows_f64: no device memory for the batch's own rows");
       }
-    if (!b->h_rows && R > 0 && R * 72 <= kRowsMirrorLimit &&
-        hipHostMalloc((void**)&b->h_rows, (size_t)R * 72, hipHostMallocDefault) != hipSuccess) {
+    if (!b->h_rows.p && R > 0 && R * 72 <= kRowsMirrorLimit && b->h_rows.alloc((size_t)R * 72) != hipSuccess)
       (void)hipGetLastError();   // no pinned memory: fetches copy their slices from the device
-      b->h_rows = nullptr;
-    }
     b->rows_mirrored = false;
   }
-  int rc = vgx_reg_batch_evaluate_points_f64(b, poses, n_nodes, b->d_rows[0], want_jac_ref ? b->d_rows[1] : nullptr,
-                                             want_jac_read ? b->d_rows[2] : nullptr, status);
+  int rc = vgx_reg_batch_evaluate_points_f64(b, poses, n_nodes, b->d_rows[0].as<double>(), want_jac_ref ? b->d_rows[1].as<double>() : nullptr,
+                                             want_jac_read ? b->d_rows[2].as<double>() : nullptr, status);
   if (rc != VGX_OK) return rc;
   std::lock_guard<std::mutex> lk(ctx->mu);
   b->rows_have[0] = true;
   b->rows_have[1] = want_jac_ref != 0;
   b->rows_have[2] = want_jac_read != 0;
-  if (b->h_rows && R > 0) {   // the whole evaluation in (up to) three copies behind the kernel: every fetch is a host copy
-    VGX_HIP(ctx, hipMemcpyAsync(b->h_rows, b->d_rows[0], (size_t)R * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (b->h_rows.p && R > 0) {   // the whole evaluation in (up to) three copies behind the kernel: every fetch is a host copy
+    VGX_HIP(ctx, hipMemcpyAsync(b->h_rows.p, b->d_rows[0].p, (size_t)R * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (b->rows_have[1])
-      VGX_HIP(ctx, hipMemcpyAsync(b->h_rows + (size_t)R * 8, b->d_rows[1], (size_t)R * 32, hipMemcpyDeviceToHost, ctx->stream));
+      VGX_HIP(ctx, hipMemcpyAsync(b->h_rows.as<char>() + (size_t)R * 8, b->d_rows[1].p, (size_t)R * 32, hipMemcpyDeviceToHost, ctx->stream));
     if (b->rows_have[2])
-      VGX_HIP(ctx, hipMemcpyAsync(b->h_rows + (size_t)R * 40, b->d_rows[2], (size_t)R * 32, hipMemcpyDeviceToHost, ctx->stream));
+      VGX_HIP(ctx, hipMemcpyAsync(b->h_rows.as<char>() + (size_t)R * 40, b->d_rows[2].p, (size_t)R * 32, hipMemcpyDeviceToHost, ctx->stream));
     b->rows_mirrored = true;
   }
   return VGX_OK;
@@ -2670,14 +2620,14 @@ int vgx_reg_batch_fetch_rows_f64(vgx_reg_batch b, int32_t c, double* residuals, 
   const int64_t R = b->row_offset.back(), r0 = b->row_offset[(size_t)c], n = b->row_offset[(size_t)c + 1] - r0;
   if (n <= 0) return VGX_OK;
   if (b->rows_mirrored) {
-    if (residuals) std::memcpy(residuals, b->h_rows + (size_t)r0 * 8, (size_t)n * 8);
-    if (jac_ref) std::memcpy(jac_ref, b->h_rows + (size_t)R * 8 + (size_t)r0 * 32, (size_t)n * 32);
-    if (jac_read) std::memcpy(jac_read, b->h_rows + (size_t)R * 40 + (size_t)r0 * 32, (size_t)n * 32);
+    if (residuals) std::memcpy(residuals, b->h_rows.as<char>() + (size_t)r0 * 8, (size_t)n * 8);
+    if (jac_ref) std::memcpy(jac_ref, b->h_rows.as<char>() + (size_t)R * 8 + (size_t)r0 * 32, (size_t)n * 32);
+    if (jac_read) std::memcpy(jac_read, b->h_rows.as<char>() + (size_t)R * 40 + (size_t)r0 * 32, (size_t)n * 32);
     return VGX_OK;
   }
-  if (residuals) VGX_HIP(ctx, hipMemcpy(residuals, b->d_rows[0] + r0, (size_t)n * 8, hipMemcpyDeviceToHost));
-  if (jac_ref) VGX_HIP(ctx, hipMemcpy(jac_ref, b->d_rows[1] + 4 * r0, (size_t)n * 32, hipMemcpyDeviceToHost));
-  if (jac_read) VGX_HIP(ctx, hipMemcpy(jac_read, b->d_rows[2] + 4 * r0, (size_t)n * 32, hipMemcpyDeviceToHost));
+  if (residuals) VGX_HIP(ctx, hipMemcpy(residuals, b->d_rows[0].as<double>() + r0, (size_t)n * 8, hipMemcpyDeviceToHost));
+  if (jac_ref) VGX_HIP(ctx, hipMemcpy(jac_ref, b->d_rows[1].as<double>() + 4 * r0, (size_t)n * 32, hipMemcpyDeviceToHost));
+  if (jac_read) VGX_HIP(ctx, hipMemcpy(jac_read, b->d_rows[2].as<double>() + 4 * r0, (size_t)n * 32, hipMemcpyDeviceToHost));
   return VGX_OK;
 }
 
@@ -2712,12 +2662,12 @@ int vgx_reg_batch_evaluate_points_blocked(vgx_reg_batch b, const double* poses, 
   if (rc != VGX_OK) return rc;
   if (b->n == 0) return VGX_OK;
   if (!b->points_order_made && !b->tiles.empty()) {
-    rc = apply_launch_order(b, b->tiles, b->d_tiles, b->host_points_tile_first, /*points_pass=*/true);
+    rc = apply_launch_order(b, b->tiles, b->d_tiles.as<Tile>(), b->host_points_tile_first, /*points_pass=*/true);
     if (rc != VGX_OK) return rc;
     b->points_order_made = true;
   }
-  launch_points<float>(ctx, b->regs[0]->reading->vps, b->layout, b->d_desc, b->d_pack, b->d_tiles, b->d_tile_dead,
-                       (int)b->tiles.size(), d_blocks, d_blocks, d_blocks, /*blocked=*/true);
+  launch_points<float>(ctx, b->regs[0]->reading->vps, b->layout, b->d_desc.as<ConstraintDev>(), b->d_pack.as<PosePack>(),
+                       b->d_tiles.as<Tile>(), b->d_tile_dead.as<unsigned char>(), (int)b->tiles.size(), d_blocks, d_blocks, d_blocks, /*blocked=*/true);
   VGX_HIP(ctx, hipGetLastError());
   return VGX_OK;
 }
@@ -2829,7 +2779,8 @@ int vgx_reg_batch_alloc_outputs(vgx_reg_batch b, const double* poses, int32_t n_
   if (d_jac_ref) *d_jac_ref = nullptr;
   if (d_jac_read) *d_jac_read = nullptr;
   const size_t rows = (size_t)std::max<int64_t>(b->row_offset.back(), 1);
-  void* cand[3][16] = {};
+  DeviceBuffer cand[3][16];
+  void* cand_p[3][16] = {};  // what vgx_reg_batch_choose_outputs reads
   const size_t bytes[3] = {rows * 4, rows * 16, rows * 16};
   const bool want[3] = {true, want_jac_ref != 0, want_jac_read != 0};
   int have = 0, rc = VGX_OK;
@@ -2839,13 +2790,13 @@ int vgx_reg_batch_alloc_outputs(vgx_reg_batch b, const double* poses, int32_t n_
     for (; have < n_candidates; ++have) {
       bool ok = true;
       for (int a = 0; a < 3 && ok; ++a)
-        if (want[a]) ok = hipMalloc(&cand[a][have], bytes[a]) == hipSuccess;
+        if (want[a]) ok = cand[a][have].alloc(bytes[a]) == hipSuccess;
       if (!ok) {  // out of memory: choose among the complete sets there are (at least one is needed)
         (void)hipGetLastError();
-        for (int a = 0; a < 3; ++a)
-          if (cand[a][have]) (void)hipFree(cand[a][have]), cand[a][have] = nullptr;
+        for (int a = 0; a < 3; ++a) cand[a][have].release();
         break;
       }
+      for (int a = 0; a < 3; ++a) cand_p[a][have] = cand[a][have].p;
     }
   }
   if (have == 0) return set_error(ctx, VGX_ERR_NOMEM, "vgx_reg_batch_alloc_outputs: no memory for one set of row arrays");
@@ -2853,7 +2804,7 @@ int vgx_reg_batch_alloc_outputs(vgx_reg_batch b, const double* poses, int32_t n_
   // (a sampling batch cannot be timed without advancing its engines -- vgx_reg_batch_choose_outputs refuses it: the first
   // set is kept as it is; a batch without rows has nothing to time)
   if (have > 1 && !b->any_sampling && b->row_offset.back() > 0)
-    rc = vgx_reg_batch_choose_outputs(b, poses, n_nodes, have, cand[0], want[1] ? cand[1] : nullptr, want[2] ? cand[2] : nullptr, 3,
+    rc = vgx_reg_batch_choose_outputs(b, poses, n_nodes, have, cand_p[0], want[1] ? cand_p[1] : nullptr, want[2] ? cand_p[2] : nullptr, 3,
                                       chosen, ms_chosen, nullptr);
   else if (ms_chosen)
     *ms_chosen = 0.0f;
@@ -2861,15 +2812,15 @@ int vgx_reg_batch_alloc_outputs(vgx_reg_batch b, const double* poses, int32_t n_
     std::lock_guard<std::mutex> lk(ctx->mu);
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
+    if (rc == VGX_OK) {  // the chosen ones are the caller's from here (vgx_reg_batch_free_outputs)
+      *d_residuals = cand[0][chosen[0]].detach();
+      if (want[1]) *d_jac_ref = cand[1][chosen[1]].detach();
+      if (want[2]) *d_jac_read = cand[2][chosen[2]].detach();
+    }
     for (int a = 0; a < 3; ++a)
-      for (int k = 0; k < have; ++k)
-        if (cand[a][k] && (rc != VGX_OK || k != chosen[a])) (void)hipFree(cand[a][k]);
+      for (int k = 0; k < have; ++k) cand[a][k].release();
   }
-  if (rc != VGX_OK) return rc;
-  *d_residuals = cand[0][chosen[0]];
-  if (want[1]) *d_jac_ref = cand[1][chosen[1]];
-  if (want[2]) *d_jac_read = cand[2][chosen[2]];
-  return VGX_OK;
+  return rc;
 }
 
 int vgx_reg_batch_free_outputs(vgx_reg_batch b, void* d_residuals, void* d_jac_ref, void* d_jac_read) {
@@ -2878,6 +2829,7 @@ int vgx_reg_batch_free_outputs(vgx_reg_batch b, void* d_residuals, void* d_jac_r
   std::lock_guard<std::mutex> lk(ctx->mu);
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
+  // (the one raw free outside the owner types: vgx_reg_batch_alloc_outputs detached these arrays for the caller)
   for (void* p : {d_residuals, d_jac_ref, d_jac_read})
     if (p) (void)hipFree(p);
   return VGX_OK;
@@ -2892,7 +2844,7 @@ static int launch_fused_tiles(vgx_reg_batch b) {
   vgx_ctx ctx = b->ctx;
   const int n_tiles = (int)b->reduce_tiles.size();
   if (!b->launch_order_made && n_tiles > 0) {
-    int rc = apply_launch_order(b, b->reduce_tiles, b->d_reduce_tiles, b->host_tile_first, /*points_pass=*/false);
+    int rc = apply_launch_order(b, b->reduce_tiles, b->d_reduce_tiles.as<Tile>(), b->host_tile_first, /*points_pass=*/false);
     if (rc != VGX_OK) return rc;
     b->launch_order_made = true;
   }
@@ -2912,7 +2864,8 @@ static int launch_fused_tiles(vgx_reg_batch b) {
     const int vps = b->regs[0]->reading->vps;
 #define VGX_LAUNCH_LEAN(VPS, LAYOUT)                                                                                \
   hipLaunchKernelGGL((reg_eval_reduce_lean_kernel<VPS, LAYOUT, COST_ONLY>), grid, block, occupancy_pad, ctx->stream, \
-                     b->d_desc, b->d_pack, b->d_reduce_tiles, n_tiles, b->d_tile_first, b->d_partials)
+                     b->d_desc.as<ConstraintDev>(), b->d_pack.as<PosePack>(), b->d_reduce_tiles.as<Tile>(), n_tiles, \
+                     b->d_tile_first.as<int32_t>(), b->d_partials.as<double>())
     if (b->layout == 1) {
       if (vps == 16) VGX_LAUNCH_LEAN(16, 1);
       else VGX_LAUNCH_LEAN(8, 1);
@@ -2941,20 +2894,20 @@ int vgx_reg_batch_evaluate_normal(vgx_reg_batch b, const double* poses, int32_t 
   if (rc == VGX_OK) rc = batch_upload_packs(b, poses, n_nodes, status);
   if (rc != VGX_OK) return rc;
   if (b->n == 0) return VGX_OK;
-  double* out = d_normal ? (double*)d_normal : b->d_normal;
+  double* out = d_normal ? (double*)d_normal : b->d_normal.as<double>();
   rc = launch_fused_tiles<false>(b);
   if (rc != VGX_OK) return rc;
-  hipLaunchKernelGGL(reg_finalize_kernel, dim3(b->n), dim3(256), 0, ctx->stream, b->d_desc, b->d_pack,
-                     b->d_tile_first, b->d_partials, out);
+  hipLaunchKernelGGL(reg_finalize_kernel, dim3(b->n), dim3(256), 0, ctx->stream, b->d_desc.as<ConstraintDev>(), b->d_pack.as<PosePack>(),
+                     b->d_tile_first.as<int32_t>(), b->d_partials.as<double>(), out);
   VGX_HIP(ctx, hipGetLastError());
   if (normal_host) {
     // through the batch's own PINNED block: a copy into the caller's pageable memory is staged by the runtime behind a
     // process-wide lock, and a scan submitted from the mapping thread meanwhile waited for this evaluation to finish
     // (profiles/r06_scan_latency.txt: 0.7 ms median per scan under a running solve, 0.1 ms with this)
     const size_t bytes = (size_t)b->n * kNormalSize * sizeof(double);
-    VGX_HIP(ctx, hipMemcpyAsync(b->h_normal, out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    VGX_HIP(ctx, hipMemcpyAsync(b->h_normal.as<double>(), out, bytes, hipMemcpyDeviceToHost, ctx->stream));
     VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::memcpy(normal_host, b->h_normal, bytes);
+    std::memcpy(normal_host, b->h_normal.as<double>(), bytes);
   }
   return VGX_OK;
 }
@@ -2974,16 +2927,16 @@ int vgx_reg_batch_evaluate_cost(vgx_reg_batch b, const double* poses, int32_t n_
   if (b->n == 0) return VGX_OK;
   // (the internal [n][45] array's first n doubles when the caller passes no device array: a cost-only evaluation
   // invalidates nothing the caller can see -- vgx_reg_batch_evaluate_normal rewrites the array before anyone reads it)
-  double* out = d_cost ? (double*)d_cost : b->d_normal;
+  double* out = d_cost ? (double*)d_cost : b->d_normal.as<double>();
   rc = launch_fused_tiles<true>(b);
   if (rc != VGX_OK) return rc;
-  hipLaunchKernelGGL(reg_finalize_cost_kernel, dim3((unsigned)((b->n + 3) / 4)), dim3(64), 0, ctx->stream, b->d_desc, (int)b->n,
-                     b->d_tile_first, b->d_partials, out);
+  hipLaunchKernelGGL(reg_finalize_cost_kernel, dim3((unsigned)((b->n + 3) / 4)), dim3(64), 0, ctx->stream, b->d_desc.as<ConstraintDev>(), (int)b->n,
+                     b->d_tile_first.as<int32_t>(), b->d_partials.as<double>(), out);
   VGX_HIP(ctx, hipGetLastError());
   if (cost_host) {
-    VGX_HIP(ctx, hipMemcpyAsync(b->h_normal, out, (size_t)b->n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    VGX_HIP(ctx, hipMemcpyAsync(b->h_normal.as<double>(), out, (size_t)b->n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::memcpy(cost_host, b->h_normal, (size_t)b->n * sizeof(double));
+    std::memcpy(cost_host, b->h_normal.as<double>(), (size_t)b->n * sizeof(double));
   }
   return VGX_OK;
 }
@@ -3003,7 +2956,7 @@ static int count_live_each(vgx_reg_batch b, std::vector<unsigned long long>& eac
   DeviceBuffer counter;
   VGX_HIP(ctx, counter.alloc((size_t)b->n * sizeof(unsigned long long)));
   VGX_HIP(ctx, hipMemsetAsync(counter.p, 0, (size_t)b->n * sizeof(unsigned long long), ctx->stream));
-  hipLaunchKernelGGL(reg_count_live_kernel, dim3(b->n), dim3(256), 0, ctx->stream, b->d_desc, b->d_pack, b->n,
+  hipLaunchKernelGGL(reg_count_live_kernel, dim3(b->n), dim3(256), 0, ctx->stream, b->d_desc.as<ConstraintDev>(), b->d_pack.as<PosePack>(), b->n,
                      counter.as<unsigned long long>());
   VGX_HIP(ctx, hipGetLastError());
   VGX_HIP(ctx, hipMemcpyAsync(each.data(), counter.p, each.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
@@ -3100,7 +3053,7 @@ int vgx_reg_batch_assemble(vgx_reg_batch b, const void* d_normal, int32_t n_node
   if (n_nodes < ex->csr_nodes)
     return set_error(ctx, VGX_ERR_INVALID, "vgx_reg_batch_assemble: n_nodes smaller than the largest node index");
   VGX_HIP(ctx, hipSetDevice(ctx->device));
-  const double* nb = d_normal ? (const double*)d_normal : b->d_normal;
+  const double* nb = d_normal ? (const double*)d_normal : b->d_normal.as<double>();
   if (zero_first)
     VGX_HIP(ctx, hipMemsetAsync(d_fused, 0, (size_t)vgx_reg_fused_size(n_nodes, b->n_global) * sizeof(double), ctx->stream));
   // nodes beyond the batch's CSR have no incident constraints: cover only the
@@ -3112,7 +3065,8 @@ int vgx_reg_batch_assemble(vgx_reg_batch b, const void* d_normal, int32_t n_node
   // The kernel indexes node elements by the CSR's node count but lays the
   // buffer out with the caller's n_nodes.
   hipLaunchKernelGGL(reg_assemble_kernel, dim3(blocks), dim3(threads), 0, ctx->stream, nb, b->n,
-                     ex->csr_nodes, n_nodes, b->d_node_pair, b->d_global_index, ex->d_node_first, ex->d_node_items,
+                     ex->csr_nodes, n_nodes, b->d_node_pair.as<int32_t>(), b->d_global_index.as<int32_t>(),
+                     ex->d_node_first.as<int32_t>(), ex->d_node_items.as<int32_t>(),
                      (double*)d_fused, zero_first ? 0 : 1);
   VGX_HIP(ctx, hipGetLastError());
   return VGX_OK;
@@ -3128,10 +3082,10 @@ int vgx_reg_batch_scatter_normal(vgx_reg_batch b, const void* d_normal, void* d_
   if (zero_first)
     VGX_HIP(ctx, hipMemsetAsync(d_normal_all, 0, (size_t)b->n_global * kNormalSize * sizeof(double), ctx->stream));
   if (b->n == 0) return VGX_OK;
-  const double* nb = d_normal ? (const double*)d_normal : b->d_normal;
+  const double* nb = d_normal ? (const double*)d_normal : b->d_normal.as<double>();
   const int64_t work = (int64_t)b->n * kNormalSize;
   hipLaunchKernelGGL(reg_scatter_normal_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, ctx->stream, nb, b->n,
-                     b->d_global_index, (double*)d_normal_all);
+                     b->d_global_index.as<int32_t>(), (double*)d_normal_all);
   VGX_HIP(ctx, hipGetLastError());
   return VGX_OK;
 }
@@ -3144,10 +3098,7 @@ int vgx_reg_batch_scatter_normal(vgx_reg_batch b, const void* d_normal, void* d_
 struct vgx_reg_assembler_s {
   vgx_ctx ctx = nullptr;
   int32_t n = 0, csr_nodes = 0;
-  int32_t* d_node_pair = nullptr;
-  int32_t* d_identity = nullptr;
-  int32_t* d_node_first = nullptr;
-  int32_t* d_node_items = nullptr;
+  DeviceBuffer d_node_pair, d_identity, d_node_first, d_node_items;  // int32
 };
 
 extern "C" {
@@ -3156,8 +3107,6 @@ int vgx_reg_assembler_destroy(vgx_reg_assembler a) {
   if (!a) return VGX_ERR_INVALID;
   (void)hipSetDevice(a->ctx->device);
   (void)hipStreamSynchronize(a->ctx->stream);
-  for (void* p : {(void*)a->d_node_pair, (void*)a->d_identity, (void*)a->d_node_first, (void*)a->d_node_items})
-    if (p) (void)hipFree(p);
   delete a;
   return VGX_OK;
 }
@@ -3180,12 +3129,10 @@ int vgx_reg_assembler_create(vgx_ctx ctx, int32_t n, const int32_t* node_pair, v
   std::vector<int32_t> first, items, identity((size_t)n);
   build_node_csr(n, node_pair, a->csr_nodes, first, items);
   std::iota(identity.begin(), identity.end(), 0);
-  auto up = [&](const void* src, size_t bytes, int32_t** dst) -> bool {
-    if (bytes == 0) return true;
-    return hipMalloc((void**)dst, bytes) == hipSuccess && hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
-  };
-  if (!up(node_pair, 2 * (size_t)n * 4, &a->d_node_pair) || !up(identity.data(), (size_t)n * 4, &a->d_identity) ||
-      !up(first.data(), first.size() * 4, &a->d_node_first) || !up(items.data(), items.size() * 4, &a->d_node_items)) {
+  if (upload_new(ctx, a->d_node_pair, node_pair, 2 * (size_t)n * 4) != VGX_OK ||
+      upload_new(ctx, a->d_identity, identity.data(), (size_t)n * 4) != VGX_OK ||
+      upload_new(ctx, a->d_node_first, first.data(), first.size() * 4) != VGX_OK ||
+      upload_new(ctx, a->d_node_items, items.data(), items.size() * 4) != VGX_OK) {
     (void)hipGetLastError();
     vgx_reg_assembler_destroy(a);
     return set_error(ctx, VGX_ERR_NOMEM, "vgx_reg_assembler_create: device allocation failed");
@@ -3206,7 +3153,8 @@ int vgx_reg_assembler_assemble(vgx_reg_assembler a, const void* d_normal_all, in
   if (work == 0) work = 1;
   const int blocks = (int)((work + 255) / 256) + 1;  // + the cost-summing workgroup
   hipLaunchKernelGGL(reg_assemble_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const double*)d_normal_all, a->n,
-                     a->csr_nodes, n_nodes, a->d_node_pair, a->d_identity, a->d_node_first, a->d_node_items,
+                     a->csr_nodes, n_nodes, a->d_node_pair.as<int32_t>(), a->d_identity.as<int32_t>(), a->d_node_first.as<int32_t>(),
+                     a->d_node_items.as<int32_t>(),
                      (double*)d_fused, 0);
   VGX_HIP(ctx, hipGetLastError());
   return VGX_OK;

@@ -109,9 +109,7 @@ struct vgx_scan_s {
   // TileChain of the decode kernel: {ticket, error, total} and one word per tile, tagged with the launch's epoch
   DeviceBuffer d_ctl, d_state;
   uint32_t epoch = 0, tickets = 0;
-  // host variant: two pinned buffers of kScanStageBytes filled in turn; an event per buffer says when its upload is done
-  char* h_stage[2] = {nullptr, nullptr};
-  hipEvent_t uploaded[2] = {nullptr, nullptr};
+  UploadStage stage;      // host variant: halves of kScanStageBytes, allocated at first use
   bool pageable = false;  // no pinned memory was to be had: uploads go straight from the caller's bytes
 };
 
@@ -145,43 +143,29 @@ int scan_check(const vgx_scan_layout* l, const vgx_scan_config* c, int64_t n_byt
   return VGX_OK;
 }
 
-void scan_free_staging(vgx_scan S) {
-  for (int k = 0; k < 2; ++k) {
-    if (S->h_stage[k]) (void)hipHostFree(S->h_stage[k]);
-    if (S->uploaded[k]) (void)hipEventDestroy(S->uploaded[k]);
-    S->h_stage[k] = nullptr;
-    S->uploaded[k] = nullptr;
-  }
-}
-
 // the caller's bytes -> S->d_msg on stream st.  Through the pinned buffers piece by piece: the host copy of piece k
 // overlaps the upload of piece k - 1, and the caller's bytes have been read when the last piece is queued.
 int scan_upload(vgx_scan S, hipStream_t st, const void* data, size_t bytes) {
   vgx_ctx ctx = S->ctx;
-  if (!S->pageable && !S->h_stage[0]) {
-    bool ok = true;
-    for (int k = 0; k < 2 && ok; ++k)
-      ok = hipHostMalloc((void**)&S->h_stage[k], kScanStageBytes, hipHostMallocDefault) == hipSuccess &&
-           hipEventCreateWithFlags(&S->uploaded[k], hipEventDisableTiming) == hipSuccess;
-    if (!ok) {  // no pinned memory to be had: remembered, the pageable path below from now on
-      (void)hipGetLastError();
-      scan_free_staging(S);
-      S->pageable = true;
-    }
+  if (!S->pageable && S->stage.reserve(kScanStageBytes) != hipSuccess) {
+    (void)hipGetLastError();  // no pinned memory to be had: remembered, the pageable path below from now on
+    S->pageable = true;
   }
   if (S->pageable) {
     VGX_HIP(ctx, hipMemcpyAsync(S->d_msg.p, data, bytes, hipMemcpyHostToDevice, st));
     return VGX_OK;  // (the decode's closing synchronisation is behind it: the bytes are the caller's again on return)
   }
-  int k = 0;
-  for (size_t at = 0; at < bytes; at += kScanStageBytes, k ^= 1) {
+  for (size_t at = 0; at < bytes; at += kScanStageBytes) {
     const size_t piece = std::min(kScanStageBytes, bytes - at);
-    // this buffer's last upload: of this call, or of an earlier one that failed before its closing synchronisation (an
-    // event never recorded is complete)
-    VGX_HIP(ctx, hipEventSynchronize(S->uploaded[k]));
-    std::memcpy(S->h_stage[k], static_cast<const char*>(data) + at, piece);
-    VGX_HIP(ctx, hipMemcpyAsync(S->d_msg.as<char>() + at, S->h_stage[k], piece, hipMemcpyHostToDevice, st));
-    VGX_HIP(ctx, hipEventRecord(S->uploaded[k], st));
+    // (waits for this half's last upload: of this call, or of an earlier one that failed before its closing
+    // synchronisation; an event never recorded is complete)
+    int k = 0;
+    hipError_t waited = hipSuccess;
+    void* h = S->stage.next(&k, &waited);
+    VGX_HIP(ctx, waited);
+    std::memcpy(h, static_cast<const char*>(data) + at, piece);
+    VGX_HIP(ctx, hipMemcpyAsync(S->d_msg.as<char>() + at, h, piece, hipMemcpyHostToDevice, st));
+    VGX_HIP(ctx, S->stage.record(k, st));
   }
   return VGX_OK;
 }
@@ -332,7 +316,6 @@ int vgx_scan_destroy(vgx_scan S) {
     std::lock_guard<std::mutex> tsdf_lk(ctx->tsdf_mu);
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->tsdf_stream);  // (a queued scan may still read the arrays)
-    scan_free_staging(S);
   }
   delete S;
   return VGX_OK;

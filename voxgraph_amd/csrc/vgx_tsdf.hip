@@ -327,6 +327,14 @@ constexpr int32_t kDefaultPoolBlocks = 256;
 
 size_t voxels_per_block(const TsdfLayerDev& d) { return (size_t)d.vps * d.vps * d.vps; }
 
+// the kernel-facing pointers, after the layer's buffers changed
+void refresh_dev(vgx_tsdf_layer L) {
+  L->dev.voxels = L->voxels.as<unsigned long long>();
+  L->dev.rgba = L->rgba.as<uint32_t>();
+  L->dev.block_index = L->block_index.as<int32_t>();
+  L->dev.lut = L->lut.as<int32_t>();
+}
+
 // New pool of `blocks` blocks: the first `used` blocks keep their contents, the rest is zero
 // (a fresh voxblox block: distance 0, weight 0, colour 0).  Stream-ordered; the old arrays are
 // released once the copies have run.
@@ -334,35 +342,29 @@ int grow_pool(vgx_tsdf_layer L, int32_t blocks, int32_t used) {
   vgx_ctx ctx = L->ctx;
   TsdfLayerDev& d = L->dev;
   const size_t vpb = voxels_per_block(d);
-  unsigned long long* voxels = nullptr;
-  uint32_t* rgba = nullptr;
-  int32_t* block_index = nullptr;
-  bool ok = hipMalloc(&voxels, (size_t)blocks * vpb * 8) == hipSuccess &&
-            hipMalloc(&rgba, (size_t)blocks * vpb * 4) == hipSuccess &&
-            hipMalloc(&block_index, (size_t)blocks * 12) == hipSuccess;
+  DeviceBuffer voxels, rgba, block_index;
+  bool ok = voxels.alloc((size_t)blocks * vpb * 8) == hipSuccess &&
+            rgba.alloc((size_t)blocks * vpb * 4) == hipSuccess &&
+            block_index.alloc((size_t)blocks * 12) == hipSuccess;
   if (ok) {
     const size_t keep = (size_t)used * vpb;
-    ok = (keep == 0 || (hipMemcpyAsync(voxels, d.voxels, keep * 8, hipMemcpyDeviceToDevice, ctx->tsdf_stream) == hipSuccess &&
-                        hipMemcpyAsync(rgba, d.rgba, keep * 4, hipMemcpyDeviceToDevice, ctx->tsdf_stream) == hipSuccess &&
-                        hipMemcpyAsync(block_index, d.block_index, (size_t)used * 12, hipMemcpyDeviceToDevice, ctx->tsdf_stream) == hipSuccess)) &&
-         hipMemsetAsync(voxels + keep, 0, ((size_t)blocks * vpb - keep) * 8, ctx->tsdf_stream) == hipSuccess &&
-         hipMemsetAsync(rgba + keep, 0, ((size_t)blocks * vpb - keep) * 4, ctx->tsdf_stream) == hipSuccess &&
+    ok = (keep == 0 || (hipMemcpyAsync(voxels.p, d.voxels, keep * 8, hipMemcpyDeviceToDevice, ctx->tsdf_stream) == hipSuccess &&
+                        hipMemcpyAsync(rgba.p, d.rgba, keep * 4, hipMemcpyDeviceToDevice, ctx->tsdf_stream) == hipSuccess &&
+                        hipMemcpyAsync(block_index.p, d.block_index, (size_t)used * 12, hipMemcpyDeviceToDevice, ctx->tsdf_stream) == hipSuccess)) &&
+         hipMemsetAsync(voxels.as<unsigned long long>() + keep, 0, ((size_t)blocks * vpb - keep) * 8, ctx->tsdf_stream) == hipSuccess &&
+         hipMemsetAsync(rgba.as<uint32_t>() + keep, 0, ((size_t)blocks * vpb - keep) * 4, ctx->tsdf_stream) == hipSuccess &&
          hipStreamSynchronize(ctx->tsdf_stream) == hipSuccess;
   }
   if (!ok) {
-    void* fresh[] = {voxels, rgba, block_index};
-    for (void* q : fresh)
-      if (q) (void)hipFree(q);
     (void)hipGetLastError();
     return set_error(ctx, VGX_ERR_NOMEM, "TSDF layer: block pool allocation failed (" + std::to_string(blocks) + " blocks)");
   }
-  void* old[] = {d.voxels, d.rgba, d.block_index};
-  for (void* q : old)
-    if (q) (void)hipFree(q);
-  d.voxels = voxels;
-  d.rgba = rgba;
-  d.block_index = block_index;
+  // (the old arrays go with the locals)
+  L->voxels.swap(voxels);
+  L->rgba.swap(rgba);
+  L->block_index.swap(block_index);
   d.max_blocks = blocks;
+  refresh_dev(L);
   return VGX_OK;
 }
 
@@ -374,24 +376,21 @@ int rebox(vgx_tsdf_layer L, const int32_t mn[3], const int32_t dm[3]) {
   for (int a = 0; a < 3; ++a) cells *= (size_t)dm[a];
   if (cells > ((size_t)1 << 28))
     return set_error(ctx, VGX_ERR_UNSUPPORTED, "TSDF layer: block box exceeds 2^28 cells (dense lookup table)");
-  int32_t* lut = nullptr;
-  if (hipMalloc(&lut, cells * 4) != hipSuccess)
+  DeviceBuffer lut;
+  if (lut.alloc(cells * 4) != hipSuccess)
     return set_error(ctx, VGX_ERR_NOMEM, "TSDF layer: block table allocation failed");
-  hipError_t e = hipMemsetAsync(lut, 0xff, cells * 4, ctx->tsdf_stream);
+  hipError_t e = hipMemsetAsync(lut.p, 0xff, cells * 4, ctx->tsdf_stream);
   if (e == hipSuccess && d.lut && L->lut_cells > 0) {
     hipLaunchKernelGGL(tsdf_lut_remap_kernel, dim3((unsigned)((L->lut_cells + 255) / 256)), dim3(256), 0, ctx->tsdf_stream,
                        d.lut, make_int3(d.lut_min[0], d.lut_min[1], d.lut_min[2]),
-                       make_int3(d.lut_dim[0], d.lut_dim[1], d.lut_dim[2]), lut, make_int3(mn[0], mn[1], mn[2]),
+                       make_int3(d.lut_dim[0], d.lut_dim[1], d.lut_dim[2]), lut.as<int32_t>(), make_int3(mn[0], mn[1], mn[2]),
                        make_int3(dm[0], dm[1], dm[2]));
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->tsdf_stream);
-  if (e != hipSuccess) {
-    (void)hipFree(lut);
-    return set_error(ctx, VGX_ERR_HIP, std::string("TSDF layer: re-boxing failed: ") + hipGetErrorString(e));
-  }
-  if (d.lut) (void)hipFree(d.lut);
-  d.lut = lut;
+  if (e != hipSuccess) return set_error(ctx, VGX_ERR_HIP, std::string("TSDF layer: re-boxing failed: ") + hipGetErrorString(e));
+  L->lut.swap(lut);  // (the old table goes with the local)
+  refresh_dev(L);
   L->lut_cells = cells;
   for (int a = 0; a < 3; ++a) {
     d.lut_min[a] = mn[a];
@@ -405,7 +404,7 @@ int read_stats_sync(vgx_tsdf_layer L, TsdfStats* out) {
   vgx_ctx ctx = L->ctx;
   VGX_HIP(ctx, hipSetDevice(ctx->device));
   VGX_HIP(ctx, hipStreamSynchronize(ctx->tsdf_stream));
-  VGX_HIP(ctx, hipMemcpy(out, L->d_stats, sizeof(TsdfStats), hipMemcpyDeviceToHost));
+  VGX_HIP(ctx, hipMemcpy(out, L->d_stats.p, sizeof(TsdfStats), hipMemcpyDeviceToHost));
   L->known_blocks = out->n_blocks;
   L->known_seq = L->scan_seq;
   L->recent.clear();
@@ -418,9 +417,9 @@ int read_stats_sync(vgx_tsdf_layer L, TsdfStats* out) {
 void poll_readback(vgx_tsdf_layer L) {
   if (!L->readback_inflight || hipEventQuery(L->readback_done) != hipSuccess) return;
   L->readback_inflight = false;
-  L->known_blocks = L->h_stats->n_blocks;
+  L->known_blocks = L->h_stats.as<TsdfStats>()->n_blocks;
   L->known_seq = L->inflight_seq;
-  L->dropped_seen = L->h_stats->dropped;
+  L->dropped_seen = L->h_stats.as<TsdfStats>()->dropped;
   size_t keep = 0;
   for (auto& r : L->recent)
     if (r.first > L->known_seq) L->recent[keep++] = r;
@@ -568,7 +567,7 @@ void request_readback(vgx_tsdf_layer L) {
   for (auto& r : L->recent) pending += r.second;
   if (2 * pending < (int64_t)L->dev.max_blocks - L->known_blocks) return;
   vgx_ctx ctx = L->ctx;
-  if (hipMemcpyAsync(L->h_stats, L->d_stats, sizeof(TsdfStats), hipMemcpyDeviceToHost, ctx->tsdf_stream) != hipSuccess ||
+  if (hipMemcpyAsync(L->h_stats.p, L->d_stats.p, sizeof(TsdfStats), hipMemcpyDeviceToHost, ctx->tsdf_stream) != hipSuccess ||
       hipEventRecord(L->readback_done, ctx->tsdf_stream) != hipSuccess) {
     (void)hipGetLastError();
     return;  // the synchronous path still works
@@ -625,14 +624,14 @@ int vgx_tsdf_layer_create(vgx_ctx ctx, float voxel_size, int32_t vps, const int3
   d.voxel_size = voxel_size;
   d.voxel_size_inv = 1.0f / voxel_size;
   int rc = VGX_OK;
-  if (hipMalloc(&L->d_stats, sizeof(TsdfStats)) != hipSuccess ||
-      hipHostMalloc((void**)&L->h_stats, sizeof(TsdfStats), hipHostMallocDefault) != hipSuccess ||
+  if (L->d_stats.alloc(sizeof(TsdfStats)) != hipSuccess ||
+      L->h_stats.alloc(sizeof(TsdfStats)) != hipSuccess ||
       hipEventCreateWithFlags(&L->readback_done, hipEventDisableTiming) != hipSuccess ||
-      hipMemsetAsync(L->d_stats, 0, sizeof(TsdfStats), ctx->tsdf_stream) != hipSuccess)
+      hipMemsetAsync(L->d_stats.p, 0, sizeof(TsdfStats), ctx->tsdf_stream) != hipSuccess)
     rc = set_error(ctx, VGX_ERR_NOMEM, "vgx_tsdf_layer_create: device allocation failed");
   if (rc == VGX_OK) {
-    d.n_blocks = &L->d_stats->n_blocks;
-    d.dropped = &L->d_stats->dropped;
+    d.n_blocks = &L->d_stats.as<TsdfStats>()->n_blocks;
+    d.dropped = &L->d_stats.as<TsdfStats>()->dropped;
     rc = grow_pool(L, max_blocks, 0);
   }
   // the box is only an initial reservation: scans re-box the table as they need (reserve_for_scan)
@@ -649,11 +648,6 @@ int vgx_tsdf_layer_destroy(vgx_tsdf_layer L) {
   if (!L) return VGX_ERR_INVALID;
   (void)hipSetDevice(L->ctx->device);
   (void)hipStreamSynchronize(L->ctx->tsdf_stream);
-  TsdfLayerDev& d = L->dev;
-  void* ptrs[] = {d.voxels, d.rgba, d.lut, d.block_index, L->d_stats};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  if (L->h_stats) (void)hipHostFree(L->h_stats);
   if (L->readback_done) (void)hipEventDestroy(L->readback_done);
   delete L;
   return VGX_OK;
@@ -741,8 +735,8 @@ int vgx_tsdf_layer_upload(vgx_tsdf_layer L, int32_t n_blocks, const int32_t* blo
       if (b == 0 || v < mn[a]) mn[a] = v;
       if (b == 0 || v > mx[a]) mx[a] = v;
     }
-  if (d.lut) (void)hipFree(d.lut);
-  d.lut = nullptr;
+  L->lut.release();
+  refresh_dev(L);
   L->lut_cells = 0;
   int rc = VGX_OK;
   if (n_blocks > 0) {
@@ -773,7 +767,7 @@ int vgx_tsdf_layer_upload(vgx_tsdf_layer L, int32_t n_blocks, const int32_t* blo
   }
   TsdfStats st{};
   st.n_blocks = n_blocks;
-  VGX_HIP(ctx, hipMemcpyAsync(L->d_stats, &st, sizeof(st), hipMemcpyHostToDevice, ctx->tsdf_stream));
+  VGX_HIP(ctx, hipMemcpyAsync(L->d_stats.p, &st, sizeof(st), hipMemcpyHostToDevice, ctx->tsdf_stream));
   VGX_HIP(ctx, hipStreamSynchronize(ctx->tsdf_stream));
   L->known_blocks = n_blocks;
   L->known_seq = L->scan_seq;
@@ -875,9 +869,12 @@ int vgx_tsdf_integrator_create(vgx_ctx ctx, const vgx_tsdf_config* cfg, vgx_tsdf
   I->layer = layer;
   I->dev.cfg = *cfg;
   const size_t set_bytes = ((size_t)1 << kSetBits) * 8;
-  bool ok = hipMalloc(&I->dev.start_set, set_bytes) == hipSuccess &&
-            hipMalloc(&I->dev.observed_set, set_bytes) == hipSuccess &&
-            hipMalloc(&I->dev.n_updates, 8 * kScanStatWords) == hipSuccess;
+  bool ok = I->start_set.alloc(set_bytes) == hipSuccess &&
+            I->observed_set.alloc(set_bytes) == hipSuccess &&
+            I->n_updates.alloc(8 * kScanStatWords) == hipSuccess;
+  I->dev.start_set = I->start_set.as<unsigned long long>();
+  I->dev.observed_set = I->observed_set.as<unsigned long long>();
+  I->dev.n_updates = I->n_updates.as<unsigned long long>();
   const unsigned long long poison = ~0ull;
   if (ok)
     ok = hipMemset(I->dev.start_set, 0, set_bytes) == hipSuccess &&
@@ -901,16 +898,6 @@ int vgx_tsdf_integrator_destroy(vgx_tsdf_integrator I) {
   if (I->counted_on_ctx) I->ctx->tsdf_integrators.fetch_sub(1);
   (void)hipSetDevice(I->ctx->device);
   (void)hipStreamSynchronize(I->ctx->tsdf_stream);
-  void* ptrs[] = {I->dev.start_set, I->dev.observed_set, I->dev.n_updates, I->d_points, I->d_rgba, I->d_wg_stats, I->d_trace,
-                  I->d_mkeys[0], I->d_mkeys[1], I->d_midx[0], I->d_midx[1], I->d_mstart, I->d_mcounters, I->d_msort,
-                  I->d_mrank, I->d_gpg, I->d_gcolor, I->d_gflags, I->d_gcount, I->d_okey[0], I->d_okey[1], I->d_oidx[0],
-                  I->d_oidx[1], I->d_osort};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  for (int k = 0; k < 2; ++k) {
-    if (I->h_stage[k]) (void)hipHostFree(I->h_stage[k]);
-    if (I->stage_uploaded[k]) (void)hipEventDestroy(I->stage_uploaded[k]);
-  }
   if (I->det) det_scratch_free(I->det);
   delete I;
   return VGX_OK;
@@ -963,32 +950,26 @@ static int visiting_order(vgx_tsdf_integrator I, const void* d_points, int64_t n
   if (I->dev.cfg.integration_order != VGX_TSDF_ORDER_SORTED)
     return set_error(ctx, VGX_ERR_INVALID, "vgx_tsdf_config.integration_order: neither VGX_TSDF_ORDER_MIXED nor VGX_TSDF_ORDER_SORTED");
   if (n >= (1ll << 32)) return set_error(ctx, VGX_ERR_UNSUPPORTED, "integration_order sorted: more than 2^32 points in a scan");
+  auto sort = [&](void* tmp, size_t& bytes) {
+    return stable_sort_pairs(tmp, bytes, I->d_okey[0].as<uint32_t>(), I->d_okey[1].as<uint32_t>(), I->d_oidx[0].as<uint32_t>(),
+                             I->d_oidx[1].as<uint32_t>(), (size_t)n, 32, ctx->tsdf_stream);
+  };
   if (n > I->order_cap) {
     VGX_HIP(ctx, hipStreamSynchronize(ctx->tsdf_stream));
-    void* old[] = {I->d_okey[0], I->d_okey[1], I->d_oidx[0], I->d_oidx[1], I->d_osort};
-    for (void* q : old)
-      if (q) (void)hipFree(q);
-    I->d_okey[0] = I->d_okey[1] = I->d_oidx[0] = I->d_oidx[1] = nullptr;
-    I->d_osort = nullptr;
     I->order_cap = 0;
-    for (int k = 0; k < 2; ++k) {
-      VGX_HIP(ctx, hipMalloc(&I->d_okey[k], (size_t)n * 4));
-      VGX_HIP(ctx, hipMalloc(&I->d_oidx[k], (size_t)n * 4));
-    }
-    size_t bytes = 0;
-    VGX_HIP(ctx, stable_sort_pairs(nullptr, bytes, I->d_okey[0], I->d_okey[1], I->d_oidx[0], I->d_oidx[1], (size_t)n, 32,
-                                   ctx->tsdf_stream));
-    VGX_HIP(ctx, hipMalloc(&I->d_osort, std::max<size_t>(bytes, 16)));
-    I->osort_bytes = bytes;
+    I->d_osort.release();
+    VGX_HIP(ctx, alloc_group({{&I->d_okey[0], (size_t)n * 4}, {&I->d_oidx[0], (size_t)n * 4},
+                              {&I->d_okey[1], (size_t)n * 4}, {&I->d_oidx[1], (size_t)n * 4}}));
+    VGX_HIP(ctx, temp_bytes(sort, &I->osort_bytes));
+    VGX_HIP(ctx, I->d_osort.alloc(std::max<size_t>(I->osort_bytes, 16)));
     I->order_cap = n;
   }
   hipLaunchKernelGGL(sorted_order_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->tsdf_stream,
-                     (const float*)d_points, (long long)n, I->d_okey[0], I->d_oidx[0]);
+                     (const float*)d_points, (long long)n, I->d_okey[0].as<uint32_t>(), I->d_oidx[0].as<uint32_t>());
   VGX_HIP(ctx, hipGetLastError());
   size_t bytes = I->osort_bytes;
-  VGX_HIP(ctx, stable_sort_pairs(I->d_osort, bytes, I->d_okey[0], I->d_okey[1], I->d_oidx[0], I->d_oidx[1], (size_t)n, 32,
-                                 ctx->tsdf_stream));
-  *order = I->d_oidx[1];
+  VGX_HIP(ctx, sort(I->d_osort.p, bytes));
+  *order = I->d_oidx[1].as<uint32_t>();
   return VGX_OK;
 }
 
@@ -1039,15 +1020,11 @@ static int integrate_locked(vgx_tsdf_integrator I, const float T[7], const void*
     I->dev.wg_stats = nullptr;
     if (n_updates) {  // a counted scan: one row of statistics per workgroup
       const long long wgs = racing_scan_workgroups((long long)n, I->cloud_width);
-      if (wgs > I->wg_stats_cap) {
+      if ((size_t)wgs * kWgStatWords * 8 > I->d_wg_stats.bytes) {
         VGX_HIP(ctx, hipStreamSynchronize(ctx->tsdf_stream));
-        if (I->d_wg_stats) (void)hipFree(I->d_wg_stats);
-        I->d_wg_stats = nullptr;
-        I->wg_stats_cap = 0;
-        VGX_HIP(ctx, hipMalloc(&I->d_wg_stats, (size_t)wgs * kWgStatWords * 8));
-        I->wg_stats_cap = wgs;
+        VGX_HIP(ctx, I->d_wg_stats.reserve((size_t)wgs * kWgStatWords * 8));
       }
-      I->dev.wg_stats = I->d_wg_stats;
+      I->dev.wg_stats = I->d_wg_stats.as<unsigned long long>();
       I->wg_stats_rows = wgs;
     }
     VGX_HIP(ctx, (I->racing_launch ? I->racing_launch : launch_racing_scan)(ctx->tsdf_stream, I->layer->dev, I->dev, T, (const float*)d_points, (const uint32_t*)d_rgba,
@@ -1072,11 +1049,11 @@ static int merged_integrate_locked(vgx_tsdf_integrator I, const float T[7], cons
   vgx_ctx ctx = I->ctx;
   std::lock_guard<std::mutex> lk(ctx->tsdf_mu);
   const int rc = merged_integrate_body(I, T, d_points, d_rgba, n, freespace, n_updates);
-  if (rc != VGX_OK && I->d_mcounters) {
+  if (rc != VGX_OK && I->d_mcounters.p) {
     // a scan that stopped between its bundle and merge kernels would leave the "key corner" flag (counters[5]: set by
     // the bundle kernel, cleared by the merge kernel of the same scan) for the NEXT scan to be refused by
     const std::string why = vgx_last_error(ctx);
-    (void)hipMemsetAsync(I->d_mcounters + 5, 0, 4, ctx->tsdf_stream);
+    (void)hipMemsetAsync(I->d_mcounters.as<unsigned int>() + 5, 0, 4, ctx->tsdf_stream);
     (void)hipGetLastError();
     set_error(ctx, rc, why);
   }
@@ -1093,38 +1070,35 @@ static int merged_integrate_body(vgx_tsdf_integrator I, const float T[7], const 
   if (n > 0) {
     const unsigned long long* keys_sorted = nullptr;
     const unsigned int* idx_sorted = nullptr;
+    // stable: equal keys keep the visiting order they were written in
+    auto sort = [&](void* tmp, size_t& bytes) {
+      return stable_sort_pairs_u64(tmp, bytes, I->d_mkeys[0].as<unsigned long long>(), I->d_mkeys[1].as<unsigned long long>(),
+                                   I->d_midx[0].as<unsigned int>(), I->d_midx[1].as<unsigned int>(), (size_t)n, ctx->tsdf_stream);
+    };
     if (n > I->merged_cap) {
       VGX_HIP(ctx, hipStreamSynchronize(ctx->tsdf_stream));
-      void* old[] = {I->d_mkeys[0], I->d_mkeys[1], I->d_midx[0], I->d_midx[1], I->d_mstart, I->d_msort,
-                     I->d_mrank, I->d_gpg, I->d_gcolor, I->d_gflags, I->d_gcount};
-      for (void* q : old)
-        if (q) (void)hipFree(q);
-      I->d_mkeys[0] = I->d_mkeys[1] = nullptr;
-      I->d_midx[0] = I->d_midx[1] = nullptr;
-      I->d_mstart = I->d_mrank = I->d_gcolor = I->d_gflags = I->d_gcount = nullptr;
-      I->d_gpg = nullptr;
-      I->d_msort = nullptr;
       I->merged_cap = 0;
-      for (int k = 0; k < 2; ++k) {
-        VGX_HIP(ctx, hipMalloc(&I->d_mkeys[k], (size_t)n * 8));
-        VGX_HIP(ctx, hipMalloc(&I->d_midx[k], (size_t)n * 4));
+      I->d_msort.release();
+      VGX_HIP(ctx, alloc_group({{&I->d_mkeys[0], (size_t)n * 8}, {&I->d_midx[0], (size_t)n * 4},
+                                {&I->d_mkeys[1], (size_t)n * 8}, {&I->d_midx[1], (size_t)n * 4},
+                                {&I->d_mstart, (size_t)n * 4}, {&I->d_gpg, (size_t)n * 16}, {&I->d_gcolor, (size_t)n * 4},
+                                {&I->d_gflags, (size_t)n * 4}, {&I->d_gcount, ((size_t)n + 1) * 4}}));
+      if (!I->d_mcounters.p) {
+        VGX_HIP(ctx, I->d_mcounters.alloc(32));
+        VGX_HIP(ctx, hipMemsetAsync(I->d_mcounters.p, 0, 32, ctx->tsdf_stream));  // ([5]: set by a scan, cleared by the same scan)
       }
-      VGX_HIP(ctx, hipMalloc(&I->d_mstart, (size_t)n * 4));
-      VGX_HIP(ctx, hipMalloc(&I->d_gpg, (size_t)n * 16));
-      VGX_HIP(ctx, hipMalloc(&I->d_gcolor, (size_t)n * 4));
-      VGX_HIP(ctx, hipMalloc(&I->d_gflags, (size_t)n * 4));
-      VGX_HIP(ctx, hipMalloc(&I->d_gcount, ((size_t)n + 1) * 4));
-      if (!I->d_mcounters) {
-        VGX_HIP(ctx, hipMalloc(&I->d_mcounters, 32));
-        VGX_HIP(ctx, hipMemsetAsync(I->d_mcounters, 0, 32, ctx->tsdf_stream));  // ([5]: set by a scan, cleared by the same scan)
-      }
-      size_t bytes = 0;
-      VGX_HIP(ctx, stable_sort_pairs_u64(nullptr, bytes, I->d_mkeys[0], I->d_mkeys[1], I->d_midx[0], I->d_midx[1], (size_t)n,
-                                         ctx->tsdf_stream));
-      VGX_HIP(ctx, hipMalloc(&I->d_msort, std::max<size_t>(bytes, 16)));
-      I->msort_bytes = bytes;
+      VGX_HIP(ctx, temp_bytes(sort, &I->msort_bytes));
+      VGX_HIP(ctx, I->d_msort.alloc(std::max<size_t>(I->msort_bytes, 16)));
       I->merged_cap = n;
     }
+    unsigned long long* const mkeys[2] = {I->d_mkeys[0].as<unsigned long long>(), I->d_mkeys[1].as<unsigned long long>()};
+    unsigned int* const midx[2] = {I->d_midx[0].as<unsigned int>(), I->d_midx[1].as<unsigned int>()};
+    unsigned int* const mstart = I->d_mstart.as<unsigned int>();
+    unsigned int* const mcounters = I->d_mcounters.as<unsigned int>();
+    uint32_t* const gcolor = I->d_gcolor.as<uint32_t>();
+    uint32_t* const gflags = I->d_gflags.as<uint32_t>();
+    uint32_t* const gcount = I->d_gcount.as<uint32_t>();
+    float4* const gpg = I->d_gpg.as<float4>();
     const vgx_tsdf_config& c = I->dev.cfg;
     const float origin[3] = {T[4], T[5], T[6]};
     const float reach = c.max_ray_length_m + c.default_truncation_distance + 2.0f * I->layer->dev.voxel_size;
@@ -1139,22 +1113,20 @@ static int merged_integrate_body(vgx_tsdf_integrator I, const float T[7], const 
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     hipLaunchKernelGGL(merged_bundle_kernel, grid, block, 0, ctx->tsdf_stream, c, I->layer->dev.voxel_size_inv, T[0], T[1],
                        T[2], T[3], T[4], T[5], T[6], (const float*)d_points, (long long)n, order, (int)freespace,
-                       I->d_mkeys[0], I->d_midx[0], I->d_mcounters, I->d_gcount, scan_ctr);
+                       mkeys[0], midx[0], mcounters, gcount, scan_ctr);
     VGX_HIP(ctx, hipGetLastError());
     size_t bytes = I->msort_bytes;
-    // stable: equal keys keep the visiting order they were written in
-    VGX_HIP(ctx, stable_sort_pairs_u64(I->d_msort, bytes, I->d_mkeys[0], I->d_mkeys[1], I->d_midx[0], I->d_midx[1], (size_t)n,
-                                       ctx->tsdf_stream));
-    keys_sorted = I->d_mkeys[1];
-    idx_sorted = I->d_midx[1];
+    VGX_HIP(ctx, sort(I->d_msort.p, bytes));
+    keys_sorted = mkeys[1];
+    idx_sorted = midx[1];
     {
       // group heads and their ranks in ONE launch (the prefix sum inside it: TileChain)
       const uint32_t head_tiles = (uint32_t)((n + 256 * kHeadsIpt - 1) / (256 * kHeadsIpt));
       TileChain chain;
       rc = det_next_chain(I, head_tiles, &chain);
       if (rc != VGX_OK) return rc;
-      hipLaunchKernelGGL(merged_heads_kernel, dim3(head_tiles), block, 0, ctx->tsdf_stream, keys_sorted, (long long)n, chain, I->d_mstart,
-                         I->d_mcounters);
+      hipLaunchKernelGGL(merged_heads_kernel, dim3(head_tiles), block, 0, ctx->tsdf_stream, keys_sorted, (long long)n, chain, mstart,
+                         mcounters);
       VGX_HIP(ctx, hipGetLastError());
     }
     // one L-lane sub-group per group, grid-stride (the number of groups stays on the device)
@@ -1165,7 +1137,7 @@ static int merged_integrate_body(vgx_tsdf_integrator I, const float T[7], const 
 #define VGX_LAUNCH_MERGE(L)                                                                                                        \
     hipLaunchKernelGGL(merged_merge_kernel<L>, dim3(work_groups), block, 0, ctx->tsdf_stream, c, I->layer->dev.voxel_size_inv, T[0],    \
                        T[1], T[2], T[3], T[4], T[5], T[6], (const float*)d_points, (const uint32_t*)d_rgba, keys_sorted, idx_sorted, \
-                       I->d_mstart, I->d_mcounters, I->d_gpg, I->d_gcolor, I->d_gflags, I->d_gcount, I->d_mcounters + 5, scan_ctr)
+                       mstart, mcounters, gpg, gcolor, gflags, gcount, mcounters + 5, scan_ctr)
     if (lanes == 4) VGX_LAUNCH_MERGE(4);
     else if (lanes == 8) VGX_LAUNCH_MERGE(8);
     else VGX_LAUNCH_MERGE(16);
@@ -1177,8 +1149,7 @@ static int merged_integrate_body(vgx_tsdf_integrator I, const float T[7], const 
     // applies its updates in group order -- surface groups in key order, then clearing groups: the
     // single thread's order (vgx_tsdf_det.hip).  The voxel VALUES are therefore the same on every run in
     // either mode; vgx_tsdf_config.deterministic additionally fixes the order blocks are allocated in.
-    rc = det_merged_commit(I, T, (long long)n, I->d_gpg, I->d_gcolor, I->d_gflags, I->d_gcount, keys_sorted, I->d_mstart,
-                           I->d_mcounters, n_updates);
+    rc = det_merged_commit(I, T, (long long)n, gpg, gcolor, gflags, gcount, keys_sorted, mstart, mcounters, n_updates);
     if (rc == VGX_OK) request_readback(I->layer);
     return rc;
   }
@@ -1204,54 +1175,31 @@ static int stage_scan(vgx_tsdf_integrator I, const float* points, const uint8_t*
   VGX_HIP(ctx, hipSetDevice(ctx->device));
   if (n > I->staging_cap) {
     VGX_HIP(ctx, hipStreamSynchronize(ctx->tsdf_stream));
-    if (I->d_points) (void)hipFree(I->d_points);
-    if (I->d_rgba) (void)hipFree(I->d_rgba);
-    I->d_points = nullptr;
-    I->d_rgba = nullptr;
     I->staging_cap = 0;
-    VGX_HIP(ctx, hipMalloc(&I->d_points, (size_t)n * 12));
-    VGX_HIP(ctx, hipMalloc(&I->d_rgba, (size_t)n * 4));
+    VGX_HIP(ctx, alloc_group({{&I->d_points, (size_t)n * 12}, {&I->d_rgba, (size_t)n * 4}}));
     I->staging_cap = n;
   }
   if (n > 0) {
     // Through pinned memory, two buffers in turn: the caller's arrays are read HERE (a host copy), the upload and the scan
     // run behind the call.  (Straight from pageable memory the runtime stages the copy itself and the call waits for it.)
-    if (n > I->h_stage_cap) {
+    if ((size_t)n * 16 > I->stage.bytes()) {
       VGX_HIP(ctx, hipStreamSynchronize(ctx->tsdf_stream));
-      for (int k = 0; k < 2; ++k) {
-        if (I->h_stage[k]) (void)hipHostFree(I->h_stage[k]);
-        I->h_stage[k] = nullptr;
-      }
-      I->h_stage_cap = 0;
-      bool ok = true;
-      for (int k = 0; k < 2 && ok; ++k) {
-        ok = hipHostMalloc((void**)&I->h_stage[k], (size_t)n * 16, hipHostMallocDefault) == hipSuccess;
-        if (ok && !I->stage_uploaded[k]) ok = hipEventCreateWithFlags(&I->stage_uploaded[k], hipEventDisableTiming) == hipSuccess;
-      }
-      if (ok) {
-        I->h_stage_cap = n;
-      } else {  // no pinned memory to be had: the pageable path below
-        (void)hipGetLastError();
-        for (int k = 0; k < 2; ++k) {
-          if (I->h_stage[k]) (void)hipHostFree(I->h_stage[k]);
-          I->h_stage[k] = nullptr;
-        }
-      }
+      if (I->stage.reserve((size_t)n * 16) != hipSuccess) (void)hipGetLastError();  // no pinned memory to be had: the pageable path below
     }
-    if (I->h_stage_cap >= n) {
-      const int k = I->stage_turn;
-      I->stage_turn ^= 1;
-      VGX_HIP(ctx, hipEventSynchronize(I->stage_uploaded[k]));   // (the upload that last read this buffer: two scans ago)
-      char* h = I->h_stage[k];
+    if (I->stage.bytes() >= (size_t)n * 16) {
+      int k = 0;
+      hipError_t waited = hipSuccess;
+      char* h = static_cast<char*>(I->stage.next(&k, &waited));   // (waits for the upload that last read this half: two scans ago)
+      VGX_HIP(ctx, waited);
       std::memcpy(h, points, (size_t)n * 12);
       if (rgba) std::memcpy(h + (size_t)n * 12, rgba, (size_t)n * 4);
-      VGX_HIP(ctx, hipMemcpyAsync(I->d_points, h, (size_t)n * 12, hipMemcpyHostToDevice, ctx->tsdf_stream));
-      if (rgba) VGX_HIP(ctx, hipMemcpyAsync(I->d_rgba, h + (size_t)n * 12, (size_t)n * 4, hipMemcpyHostToDevice, ctx->tsdf_stream));
-      VGX_HIP(ctx, hipEventRecord(I->stage_uploaded[k], ctx->tsdf_stream));
+      VGX_HIP(ctx, hipMemcpyAsync(I->d_points.p, h, (size_t)n * 12, hipMemcpyHostToDevice, ctx->tsdf_stream));
+      if (rgba) VGX_HIP(ctx, hipMemcpyAsync(I->d_rgba.p, h + (size_t)n * 12, (size_t)n * 4, hipMemcpyHostToDevice, ctx->tsdf_stream));
+      VGX_HIP(ctx, I->stage.record(k, ctx->tsdf_stream));
     } else {
-      VGX_HIP(ctx, hipMemcpyAsync(I->d_points, points, (size_t)n * 12, hipMemcpyHostToDevice, ctx->tsdf_stream));
+      VGX_HIP(ctx, hipMemcpyAsync(I->d_points.p, points, (size_t)n * 12, hipMemcpyHostToDevice, ctx->tsdf_stream));
       if (rgba)
-        VGX_HIP(ctx, hipMemcpyAsync(I->d_rgba, rgba, (size_t)n * 4, hipMemcpyHostToDevice, ctx->tsdf_stream));
+        VGX_HIP(ctx, hipMemcpyAsync(I->d_rgba.p, rgba, (size_t)n * 4, hipMemcpyHostToDevice, ctx->tsdf_stream));
       VGX_HIP(ctx, hipStreamSynchronize(ctx->tsdf_stream));   // the caller's arrays are his again when the call returns
     }
   }
@@ -1265,7 +1213,7 @@ int vgx_tsdf_integrate_merged(vgx_tsdf_integrator I, const float T[7], const flo
   int rc = stage_scan(I, points, rgba, n);
   if (rc != VGX_OK) return rc;
   // (n_updates == NULL: nothing is counted and nothing is waited for -- the call returns with the scan queued)
-  return merged_integrate_locked(I, T, I->d_points, rgba ? I->d_rgba : nullptr, n, freespace, n_updates);
+  return merged_integrate_locked(I, T, I->d_points.p, rgba ? I->d_rgba.p : nullptr, n, freespace, n_updates);
 }
 
 int vgx_tsdf_integrate_device(vgx_tsdf_integrator I, const float T[7], const void* d_points,
@@ -1286,7 +1234,7 @@ int vgx_tsdf_integrate(vgx_tsdf_integrator I, const float T[7], const float* poi
   // n_updates == NULL (what GpuFastTsdfIntegrator::integratePointCloud passes: voxblox's call returns nothing): an uncounted
   // scan, and the call returns with it QUEUED -- the points have been read, the layer is the device's and every reader of it
   // (download, finish, the next scan) is ordered behind the scan on the TSDF stream.  With a count the call waits for it.
-  return integrate_locked(I, T, I->d_points, rgba ? I->d_rgba : nullptr, n, freespace, n_updates);
+  return integrate_locked(I, T, I->d_points.p, rgba ? I->d_rgba.p : nullptr, n, freespace, n_updates);
 }
 
 }  // extern "C"

@@ -64,8 +64,10 @@ struct DetScratch {
   // device counters (u64 each, enum below) + a pinned mirror; behind the mirror, pinned too, the other small
   // values a scan reads back (kHost*): every copy of a read-back queues behind the previous one and only the
   // last synchronise waits (a copy into pageable memory is a stream round trip of its own)
-  unsigned long long* d_ctr = nullptr;
-  unsigned long long* h_ctr = nullptr;
+  DeviceBuffer ctr_mem;
+  PinnedBuffer ctr_host_mem, flag_mem, report_mem;  // (flag / report: mapped, see ensure_scratch)
+  unsigned long long* d_ctr = nullptr;  // ctr_mem, typed
+  unsigned long long* h_ctr = nullptr;  // ctr_host_mem, typed
   // the sweeps (det_sweep_kernel): one 8-byte state per tile of the sorted accesses, tagged with the sweep's
   // epoch so that nothing has to be cleared between sweeps; zeroed when (re)allocated
   DeviceBuffer tile_state;
@@ -73,12 +75,12 @@ struct DetScratch {
   uint32_t chain_tickets = 0;    // TileChain workgroups launched since the scan's first kernel zeroed kCtrChainTicket
   // what the sweep's last block tells the host (pinned, written from the kernel): sweep sequence number << 2 |
   // error << 1 | "a stopping step moved"
-  unsigned long long* h_flag = nullptr;
+  unsigned long long* h_flag = nullptr;  // flag_mem, typed
   unsigned long long* d_flag = nullptr;  // the same word as the device addresses it
   unsigned long long flag_seq = 0;
   // the counters' way to the host (read_counters): a one-workgroup kernel stores them into pinned, coherent words and
   // then a sequence number, the host polls that number -- no copy engine, no stream synchronisation (round 5)
-  unsigned long long* h_report = nullptr;
+  unsigned long long* h_report = nullptr;  // report_mem, typed, or null
   unsigned long long* d_report = nullptr;  // the same words as the device addresses them
   unsigned long long report_seq = 0;
   bool start_capped = false;  // the previous scan's complete walks were too many to write out: count capped at once
@@ -89,14 +91,7 @@ enum { kRayValid = 1u, kRayClearing = 2u, kRayCast = 4u };
 constexpr uint32_t kInvalidStartKey = 1u << kSetBits;
 constexpr long long kVoxBias = 1ll << 20;  // 21 bits per axis
 
-void det_scratch_free(DetScratch* s) {
-  if (!s) return;
-  if (s->d_ctr) (void)hipFree(s->d_ctr);
-  if (s->h_ctr) (void)hipHostFree(s->h_ctr);
-  if (s->h_flag) (void)hipHostFree(s->h_flag);
-  if (s->h_report) (void)hipHostFree(s->h_report);
-  delete s;
-}
+void det_scratch_free(DetScratch* s) { delete s; }
 
 namespace {
 
@@ -1235,17 +1230,18 @@ static int ensure_scratch(vgx_tsdf_integrator I) {
   I->det = new (std::nothrow) DetScratch();
   if (!I->det) return set_error(ctx, VGX_ERR_NOMEM, "TSDF reproducible mode: out of host memory");
   DetScratch* S = I->det;
-  if (hipMalloc(&S->d_ctr, kCtrCount * 8) != hipSuccess ||
-      hipHostMalloc((void**)&S->h_ctr, kHostWords * 8, hipHostMallocDefault) != hipSuccess)
+  if (S->ctr_mem.alloc(kCtrCount * 8) != hipSuccess || S->ctr_host_mem.alloc(kHostWords * 8) != hipSuccess)
     return set_error(ctx, VGX_ERR_NOMEM, "TSDF reproducible mode: counter allocation failed");
+  S->d_ctr = S->ctr_mem.as<unsigned long long>();
+  S->h_ctr = S->ctr_host_mem.as<unsigned long long>();
   // the word the sweeps report through: host memory the kernel writes while it runs and the host reads while
   // the stream is busy, so it has to be coherent (fine-grained), not merely pinned
-  if (hipHostMalloc((void**)&S->h_flag, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
+  if (S->flag_mem.alloc(64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
     (void)hipGetLastError();
-    S->h_flag = nullptr;
-    if (hipHostMalloc((void**)&S->h_flag, 64, hipHostMallocMapped) != hipSuccess)
+    if (S->flag_mem.alloc(64, hipHostMallocMapped) != hipSuccess)
       return set_error(ctx, VGX_ERR_NOMEM, "TSDF reproducible mode: flag allocation failed");
   }
+  S->h_flag = S->flag_mem.as<unsigned long long>();
   S->h_flag[0] = 0ull;
   void* dp = nullptr;
   if (hipHostGetDevicePointer(&dp, S->h_flag, 0) != hipSuccess || !dp) {
@@ -1254,10 +1250,10 @@ static int ensure_scratch(vgx_tsdf_integrator I) {
   }
   S->d_flag = (unsigned long long*)dp;
   // the counters' report words: coherent or nothing (read_counters then copies and synchronises as before)
-  if (hipHostMalloc((void**)&S->h_report, kReportWords * 8, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
+  if (S->report_mem.alloc(kReportWords * 8, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
     (void)hipGetLastError();
-    S->h_report = nullptr;
   } else {
+    S->h_report = S->report_mem.as<unsigned long long>();
     for (int i = 0; i < kReportWords; ++i) S->h_report[i] = 0ull;
     void* rp = nullptr;
     if (hipHostGetDevicePointer(&rp, S->h_report, 0) != hipSuccess || !rp) {

@@ -376,13 +376,16 @@ struct TsdfStats {  // one device allocation: TsdfLayerDev::n_blocks / ::dropped
 
 struct vgx_tsdf_layer_s {
   vgx_ctx ctx = nullptr;
+  // what the kernels see: plain pointers into the buffers below, refreshed wherever those change (refresh_dev)
   vgx::TsdfLayerDev dev{};
+  vgx::DeviceBuffer voxels, rgba, block_index;  // the block pool: dev.max_blocks blocks
+  vgx::DeviceBuffer lut;                        // the block table: lut_cells entries
   size_t lut_cells = 0;
-  TsdfStats* d_stats = nullptr;
+  vgx::DeviceBuffer d_stats;  // TsdfStats
   // What the host knows about the device's allocation counter without waiting for it: the value
   // as of scan `known_seq` (read back asynchronously after scans) plus an upper bound on what the
   // scans launched since may have allocated.  known + pending is never below the true count.
-  TsdfStats* h_stats = nullptr;  // pinned
+  vgx::PinnedBuffer h_stats;  // TsdfStats
   hipEvent_t readback_done = nullptr;
   bool readback_inflight = false;
   uint64_t scan_seq = 0, inflight_seq = 0, known_seq = 0;
@@ -397,41 +400,37 @@ struct vgx_tsdf_layer_s {
 struct vgx_tsdf_integrator_s {
   vgx_ctx ctx = nullptr;
   vgx_tsdf_layer layer = nullptr;
-  vgx::TsdfIntegratorDev dev{};
+  vgx::TsdfIntegratorDev dev{};  // its pointers: into the buffers below, set after allocation
+  vgx::DeviceBuffer start_set, observed_set, n_updates;
   long long reset_counter = 0;
-  float* d_points = nullptr;  // staging for host-pointer scans
-  uint32_t* d_rgba = nullptr;
-  long long staging_cap = 0;
-  // ... and its host side: two pinned buffers ([n x 12 B points][n x 4 B colours]) filled in turn, so that the caller's
-  // (pageable) arrays are consumed when vgx_tsdf_integrate returns while the upload and the scan run behind it; an event per
-  // buffer says when its upload has finished and the buffer may be filled again
-  char* h_stage[2] = {nullptr, nullptr};
-  hipEvent_t stage_uploaded[2] = {nullptr, nullptr};
-  long long h_stage_cap = 0;
-  int stage_turn = 0;
+  vgx::DeviceBuffer d_points;  // float [n][3]: staging for host-pointer scans
+  vgx::DeviceBuffer d_rgba;    // uint32 [n]
+  long long staging_cap = 0;   // points
+  // ... and its host side ([n x 12 B points][n x 4 B colours] per half): the caller's (pageable) arrays are consumed when
+  // vgx_tsdf_integrate returns while the upload and the scan run behind it
+  vgx::UploadStage stage;
   std::mutex mu;  // one scan at a time per integrator: the staging buffers belong to the scan in flight
   // MergedTsdfIntegrator scratch (grown on demand): sort keys / point indices (double-buffered),
   // group starts, {groups, surface entries} counters, radix-sort workspace
-  unsigned long long* d_mkeys[2] = {nullptr, nullptr};
-  unsigned int* d_midx[2] = {nullptr, nullptr};
-  unsigned int* d_mstart = nullptr;
-  unsigned int* d_mrank = nullptr;     // rank of every sorted entry's group
-  unsigned int* d_mcounters = nullptr; // {groups, surface entries, surface groups, valid entries, a ray too long}
-  float4* d_gpg = nullptr;             // per group: merged point (layer frame) + merged weight
-  uint32_t* d_gcolor = nullptr;
-  uint32_t* d_gflags = nullptr;
-  uint32_t* d_gcount = nullptr;        // voxels on the group's ray
-  void* d_msort = nullptr;
-  size_t msort_bytes = 0;
-  long long merged_cap = 0;
-  unsigned long long* d_wg_stats = nullptr;  // counted racing scans: one row per workgroup (grown on demand)
-  long long wg_stats_cap = 0, wg_stats_rows = 0;
+  vgx::DeviceBuffer d_mkeys[2];   // u64
+  vgx::DeviceBuffer d_midx[2];    // u32
+  vgx::DeviceBuffer d_mstart;     // u32
+  vgx::DeviceBuffer d_mcounters;  // u32 {groups, surface entries, surface groups, valid entries, a ray too long}; allocated once
+  vgx::DeviceBuffer d_gpg;        // float4 per group: merged point (layer frame) + merged weight
+  vgx::DeviceBuffer d_gcolor;     // u32
+  vgx::DeviceBuffer d_gflags;     // u32
+  vgx::DeviceBuffer d_gcount;     // u32: voxels on the group's ray
+  vgx::DeviceBuffer d_msort;
+  size_t msort_bytes = 0;         // what rocPRIM asked for (d_msort holds at least 16 bytes)
+  long long merged_cap = 0;       // points
+  vgx::DeviceBuffer d_wg_stats;   // u64; counted racing scans: one row per workgroup (grown on demand)
+  long long wg_stats_rows = 0;
   int cloud_width = 0;  // vgx_tsdf_integrator_set_cloud_width: points per row of the scans to come (0: unorganised)
   // the racing scan's launcher: vgx::launch_racing_scan unless the diagnostics library installed its event-logging twin
   // (same kernel template, TRACE = true; include/voxgraph_amd_bench.h vgx_tsdf_integrator_set_event_trace)
   hipError_t (*racing_launch)(hipStream_t, const vgx::TsdfLayerDev&, const vgx::TsdfIntegratorDev&, const float*, const float*,
                               const uint32_t*, long long, int, bool, int) = nullptr;
-  unsigned long long* d_trace = nullptr;   // owned by the integrator once set (freed with it)
+  vgx::DeviceBuffer d_trace;               // u64: the event log, once set
   bool counted_on_ctx = false;             // Context::tsdf_integrators holds this one
   vgx::DetScratch* det = nullptr;  // reproducible mode's buffers (vgx_tsdf_det.hip), grown on demand
   // reproducible mode, bounded speculation (vgx_tsdf_det.hip det_count_kernel): a scan whose complete walks are more
@@ -444,11 +443,11 @@ struct vgx_tsdf_integrator_s {
   // group -- a LiDAR scan's groups hold one or two points, a depth image's five to ten.  Results do not depend on it.
   int merged_lanes = 4;
   // integration_order "sorted": squared-norm keys / point indices (double-buffered) + radix-sort workspace
-  uint32_t* d_okey[2] = {nullptr, nullptr};
-  uint32_t* d_oidx[2] = {nullptr, nullptr};
-  void* d_osort = nullptr;
+  vgx::DeviceBuffer d_okey[2];  // u32
+  vgx::DeviceBuffer d_oidx[2];  // u32
+  vgx::DeviceBuffer d_osort;
   size_t osort_bytes = 0;
-  long long order_cap = 0;
+  long long order_cap = 0;      // points
 };
 
 namespace vgx {
