@@ -139,12 +139,18 @@ def test_create_destroy_cycles_do_not_leak_device_memory(capi, ctx):
     layout = capi.scan_layout(width=len(many), height=1, point_step=16, offset_x=0, offset_y=4, offset_z=8,
                               color_kind=capi.SCAN_COLOR_NONE)
     poses = np.zeros((2, 4))
+    rgba = np.full((len(sm.block_index), sm.vps ** 3, 4), 200, np.uint8)
+    zeros, ones = np.zeros(len(many), F), np.ones(len(many), F)
 
     def cycle():
         g = H.gpu_submap(capi, ctx, sm)
-        g.generate_esdf()
-        g.extract_voxel_points()
-        g.extract_isosurface_points()
+        # every call that replaces what the submap holds runs twice: the second has something to free
+        for _ in range(2):
+            g.generate_esdf()
+            g.extract_voxel_points()
+            g.extract_isosurface_points()
+            g.set_colors(rgba)
+        assert g.download_colors().shape == rgba.shape
         cfg = capi.default_config(registration_point_type=capi.POINTS_VOXELS)
         cf = capi.RegistrationCostFunction(ctx, g, g, cfg)
         cs = capi.RegistrationCostFunction(ctx, g, g, capi.default_config(sampling_ratio=0.1))
@@ -162,6 +168,27 @@ def test_create_destroy_cycles_do_not_leak_device_memory(capi, ctx):
         b.free_outputs(*out[:3])
         bs = capi.RegistrationBatch(ctx, [cs], [(0, 1)])
         bs.evaluate_normal(poses)
+        # uploaded points replaced in both orders, then the sampler tables of the Morton-sorted set (cumulative weights,
+        # search table, inverse order) and -- through a sampling batch -- the engines' device states: the point set's own
+        # (cm) and a seeded cost function's (cseed)
+        p = H.gpu_submap(capi, ctx, sm, 1)
+        p.extract_isosurface_points()
+        p.set_points(capi.POINTS_ISOSURFACE, many, zeros, ones, capi.POINTS_KEEP_ORDER)
+        p.set_points(capi.POINTS_ISOSURFACE, many, zeros, ones, capi.POINTS_SORT_MORTON)
+        cm = capi.RegistrationCostFunction(ctx, p, g, capi.default_config(sampling_ratio=0.1))
+        cseed = capi.RegistrationCostFunction(ctx, g, g, capi.default_config(sampling_ratio=0.1, sampler_seed=7))
+        assert cm.num_residuals() == 30 and cseed.num_residuals() > 0
+        r3 = np.zeros(cm.num_residuals())
+        cm.Evaluate([np.zeros(4), np.zeros(4)], r3, None)
+        bseed = capi.RegistrationBatch(ctx, [cm, cseed], [(0, 1), (1, 0)])
+        bseed.evaluate_normal(poses)
+        bseed.destroy()
+        p.destroy()       # deferred: cm still reads its points ...
+        cm.destroy()      # ... and carries it out
+        # the per-block data flags of the projected map, and a submap made by the tooling library
+        proj = capi.TsdfLayer(ctx, sm.voxel_size, sm.vps, (0, 0, 0), (4, 4, 4), 64)
+        assert proj.merge_submaps([g], T[None]) > 0
+        city = capi.Submap.synth_city(ctx, 2, 0.1, 16, (0, 0, 0), (2, 2, 1), 0.3, 2.0, 10.0, np.zeros(4), 2)
         asm = capi.RegistrationAssembler(ctx, [(0, 1), (1, 0)])
         pairs = capi.find_overlapping_pairs(ctx, [g, g], poses)
         layer = capi.TsdfLayer(ctx, 0.1, 16, (-2, -2, -2), (4, 4, 4), 64)
@@ -181,7 +208,10 @@ def test_create_destroy_cycles_do_not_leak_device_memory(capi, ctx):
         integ_small.integratePointCloud(T, np.array([[3.0, 0.2, 0.1]], F))
         assert small.growths() >= 1 and small.stats()[0] > 1
         s2 = capi.Submap.from_tsdf_layer(ctx, layer, 3)
-        for o in (s2, integ_small, small, scan, integ_sorted, integ, layer, asm, bs, b, cs, cf, g):
+        s3 = capi.Submap.from_tsdf_layer_colored(ctx, layer, 4)
+        assert s3.has_colors()
+        s3.release_raw_layers()
+        for o in (s3, city, proj, cseed, s2, integ_small, small, scan, integ_sorted, integ, layer, asm, bs, b, cs, cf, g):
             o.destroy()
         return pairs
 

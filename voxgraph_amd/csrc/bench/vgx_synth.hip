@@ -166,8 +166,9 @@ extern "C" int vgx_bench_atomic_roundtrip(vgx_ctx ctx, int64_t table_bytes, int3
     return VGX_ERR_INVALID;
   std::lock_guard<std::mutex> lk(ctx->mu);
   VGX_HIP(ctx, hipSetDevice(ctx->device));
-  unsigned long long* table = nullptr;
-  VGX_HIP(ctx, hipMalloc(&table, (size_t)table_bytes + 8));
+  DeviceBuffer s_table;
+  VGX_HIP(ctx, s_table.alloc((size_t)table_bytes + 8));
+  unsigned long long* table = s_table.as<unsigned long long>();
   hipEvent_t e[3];
   for (auto& ev : e) (void)hipEventCreate(&ev);
   int rc = VGX_OK;
@@ -188,7 +189,6 @@ extern "C" int vgx_bench_atomic_roundtrip(vgx_ctx ctx, int64_t table_bytes, int3
       rc = VGX_ERR_HIP;
   }
   for (auto& ev : e) (void)hipEventDestroy(ev);
-  (void)hipFree(table);
   if (rc != VGX_OK) return set_error(ctx, rc, "vgx_bench_atomic_roundtrip: HIP failure");
   // two launches of `chain` and 3 x `chain` steps: the difference cancels the launch itself
   *ns_per_step = (ms2 - ms1) * 1e6f / (2.0f * (float)chain);
@@ -283,11 +283,9 @@ extern "C" int vgx_synth_city_submap(vgx_ctx ctx, int32_t submap_id, float voxel
   int rc = build_block_lut(sm);
   const size_t nvox = (size_t)nb * vps * vps * vps;
   if (rc == VGX_OK) {
-    if (hipMalloc(&sm->d_block_index, 3 * (size_t)nb * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc(&sm->d_tsdf_distance, nvox * sizeof(float)) != hipSuccess ||
-        hipMalloc(&sm->d_tsdf_weight, nvox * sizeof(float)) != hipSuccess ||
-        hipMalloc(&sm->d_esdf_distance, nvox * sizeof(float)) != hipSuccess ||
-        hipMalloc(&sm->d_esdf_observed, nvox * sizeof(uint8_t)) != hipSuccess)
+    if (sm->d_block_index.alloc_n(3 * (size_t)nb) != hipSuccess || sm->d_tsdf_distance.alloc_n(nvox) != hipSuccess ||
+        sm->d_tsdf_weight.alloc_n(nvox) != hipSuccess || sm->d_esdf_distance.alloc_n(nvox) != hipSuccess ||
+        sm->d_esdf_observed.alloc_n(nvox) != hipSuccess)
       rc = set_error(ctx, VGX_ERR_NOMEM, "vgx_synth_city_submap: device allocation failed");
   }
   if (rc == VGX_OK &&

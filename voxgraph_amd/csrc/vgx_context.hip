@@ -77,8 +77,8 @@ __global__ __launch_bounds__(256) void brickify_kernel(
 int launch_brickify(vgx_submap sm, int which) {
   vgx_ctx ctx = sm->ctx;
   const float* dist = which == 0 ? sm->d_tsdf_distance : sm->d_esdf_distance;
-  const float* w = which == 0 ? sm->d_tsdf_weight : nullptr;
-  const uint8_t* obs = which == 0 ? nullptr : sm->d_esdf_observed;
+  const float* w = which == 0 ? sm->d_tsdf_weight.get() : nullptr;
+  const uint8_t* obs = which == 0 ? nullptr : sm->d_esdf_observed.get();
   const int layout = ctx->brick_layout;
   const size_t cells = brick_cells(sm->vps, layout);
   // the fused REG kernel addresses a brick cell with a 32-bit `slot * cells + offset` (vgx_reg.hip,
@@ -89,7 +89,7 @@ int launch_brickify(vgx_submap sm, int which) {
                      "submap too large for 32-bit brick addressing: " + std::to_string(sm->n_blocks) + " blocks x " +
                          std::to_string(cells) + " cells per brick");
   size_t bytes = (size_t)sm->n_blocks * cells * sizeof(float);
-  VGX_HIP(ctx, hipMalloc(&sm->grid[which].d_bricks, bytes));
+  VGX_HIP(ctx, sm->grid[which].d_bricks.alloc(bytes));
   sm->grid[which].layout = layout;
   int3 mn = make_int3(sm->lut_min[0], sm->lut_min[1], sm->lut_min[2]);
   int3 dm = make_int3(sm->lut_dim[0], sm->lut_dim[1], sm->lut_dim[2]);
@@ -156,13 +156,10 @@ __global__ __launch_bounds__(64) void chunk_bounds_kernel(const float4* __restri
 }
 
 int build_chunk_bounds(vgx_ctx ctx, PointSet& ps) {
-  if (ps.d_chunk_bounds) {
-    (void)hipFree(ps.d_chunk_bounds);
-    ps.d_chunk_bounds = nullptr;
-  }
+  ps.d_chunk_bounds.release();
   if (ps.n <= 0) return VGX_OK;
   const long long chunks = (ps.n + kChunkPoints - 1) / kChunkPoints;
-  VGX_HIP(ctx, hipMalloc(&ps.d_chunk_bounds, (size_t)chunks * sizeof(float4)));
+  VGX_HIP(ctx, ps.d_chunk_bounds.alloc_n((size_t)chunks));
   DeviceBuffer s_minmax;
   VGX_HIP(ctx, s_minmax.alloc((size_t)chunks * 6 * sizeof(float)));
   float* d_minmax = s_minmax.as<float>();
@@ -216,7 +213,7 @@ int build_block_lut(vgx_submap sm) {
     size_t iz = (size_t)(block_index[3 * b + 2] - mn[2]);
     lut[ix + (size_t)sm->lut_dim[0] * (iy + (size_t)sm->lut_dim[1] * iz)] = b;
   }
-  VGX_HIP(ctx, hipMalloc(&sm->d_lut, total * sizeof(int32_t)));
+  VGX_HIP(ctx, sm->d_lut.alloc_n(total));
   VGX_HIP(ctx, hipMemcpy(sm->d_lut, lut.data(), total * sizeof(int32_t), hipMemcpyHostToDevice));
   return VGX_OK;
 }
@@ -226,16 +223,9 @@ int build_block_lut(vgx_submap sm) {
 namespace vgx {
 void reset_point_set(PointSet& ps) {
   static std::atomic<uint64_t> next_version{1};
-  if (ps.d_xyzd) (void)hipFree(ps.d_xyzd);
-  if (ps.d_weight) (void)hipFree(ps.d_weight);
-  if (ps.d_chunk_bounds) (void)hipFree(ps.d_chunk_bounds);
-  if (ps.d_cumulative) (void)hipFree(ps.d_cumulative);
-  if (ps.d_search_lut) (void)hipFree(ps.d_search_lut);
-  if (ps.d_inv_order) (void)hipFree(ps.d_inv_order);
-  if (ps.rng.d_state) (void)hipFree(ps.rng.d_state);
-  ps = PointSet();
+  ps = PointSet();  // (the move assignment frees what was held)
   // cost functions and batches built on the old points notice the change (they hold raw device
-  // pointers into the arrays freed above)
+  // pointers into the arrays just freed)
   ps.version = next_version.fetch_add(1);
 }
 
@@ -249,7 +239,7 @@ int engine_to_host(vgx_ctx ctx, SamplerEngine& e) {
 
 int engine_to_device(vgx_ctx ctx, SamplerEngine& e) {
   if (e.on_device) return VGX_OK;
-  if (!e.d_state) VGX_HIP(ctx, hipMalloc(&e.d_state, sizeof(Mt19937)));
+  if (!e.d_state) VGX_HIP(ctx, e.d_state.alloc(sizeof(Mt19937)));
   // pageable source: the copy has left the host buffer when the call returns
   VGX_HIP(ctx, hipMemcpyAsync(e.d_state, &e.host, sizeof(Mt19937), hipMemcpyHostToDevice, ctx->stream));
   e.on_device = true;
@@ -270,9 +260,8 @@ int vgx_submap_s::ensure_quad_grid(int which) {
   static const long fail_after = getenv("VGX_TEST_QUAD_ALLOC_FAILS_AFTER") ? atol(getenv("VGX_TEST_QUAD_ALLOC_FAILS_AFTER")) : -1;
   static long made_so_far = 0;
   const bool pretend_oom = fail_after >= 0 && made_so_far++ >= fail_after;
-  if (pretend_oom || hipMalloc(&g.d_quad, (size_t)n_blocks * cells * sizeof(float)) != hipSuccess) {
+  if (pretend_oom || g.d_quad.alloc_n((size_t)n_blocks * cells) != hipSuccess) {
     (void)hipGetLastError();
-    g.d_quad = nullptr;
     return set_error(ctx, VGX_ERR_NOMEM, "quad bricks for a sampling session: device allocation failed (" +
                                              std::to_string((size_t)n_blocks * cells * sizeof(float)) + " bytes; "
                                              "vgx_ctx_set_sampling_bricks(ctx, VGX_SAMPLING_BRICKS_SAME) does without)");
@@ -518,11 +507,10 @@ int vgx_ctx_timer_stop(vgx_ctx ctx, float* elapsed_ms) {
 // ---------------------------------------------------------------------------
 // submaps
 // ---------------------------------------------------------------------------
-static int upload(vgx_ctx ctx, const void* src, size_t bytes, void** dst) {
-  *dst = nullptr;
+static int upload(vgx_ctx ctx, const void* src, size_t bytes, DeviceBuffer& dst) {
   if (!src || bytes == 0) return VGX_OK;
-  VGX_HIP(ctx, hipMalloc(dst, bytes));
-  VGX_HIP(ctx, hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+  VGX_HIP(ctx, dst.alloc(bytes));
+  VGX_HIP(ctx, hipMemcpyAsync(dst.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
   return VGX_OK;
 }
 
@@ -558,11 +546,11 @@ int vgx_submap_create(vgx_ctx ctx, int32_t submap_id, float voxel_size, int32_t 
   int rc = build_block_lut(sm);
   if (rc == VGX_OK && n_blocks > 0) {
     const size_t nvox = (size_t)n_blocks * vps * vps * vps;
-    rc = upload(ctx, block_index, 3 * (size_t)n_blocks * sizeof(int32_t), (void**)&sm->d_block_index);
-    if (rc == VGX_OK) rc = upload(ctx, tsdf_distance, nvox * sizeof(float), (void**)&sm->d_tsdf_distance);
-    if (rc == VGX_OK) rc = upload(ctx, tsdf_weight, nvox * sizeof(float), (void**)&sm->d_tsdf_weight);
-    if (rc == VGX_OK) rc = upload(ctx, esdf_distance, nvox * sizeof(float), (void**)&sm->d_esdf_distance);
-    if (rc == VGX_OK) rc = upload(ctx, esdf_observed, nvox * sizeof(uint8_t), (void**)&sm->d_esdf_observed);
+    rc = upload(ctx, block_index, 3 * (size_t)n_blocks * sizeof(int32_t), sm->d_block_index);
+    if (rc == VGX_OK) rc = upload(ctx, tsdf_distance, nvox * sizeof(float), sm->d_tsdf_distance);
+    if (rc == VGX_OK) rc = upload(ctx, tsdf_weight, nvox * sizeof(float), sm->d_tsdf_weight);
+    if (rc == VGX_OK) rc = upload(ctx, esdf_distance, nvox * sizeof(float), sm->d_esdf_distance);
+    if (rc == VGX_OK) rc = upload(ctx, esdf_observed, nvox * sizeof(uint8_t), sm->d_esdf_observed);
     // the H2D copies above read pageable host memory: finish them before the
     // caller's arrays go away
     if (rc == VGX_OK && hipStreamSynchronize(ctx->stream) != hipSuccess)
@@ -582,14 +570,11 @@ int vgx_submap_create(vgx_ctx ctx, int32_t submap_id, float voxel_size, int32_t 
 int vgx_submap_release_raw_layers(vgx_submap sm) {
   if (!sm) return VGX_ERR_INVALID;
   (void)hipStreamSynchronize(sm->ctx->stream);
-  if (sm->d_tsdf_distance) (void)hipFree(sm->d_tsdf_distance);
-  if (sm->d_tsdf_weight) (void)hipFree(sm->d_tsdf_weight);
-  if (sm->d_esdf_distance) (void)hipFree(sm->d_esdf_distance);
-  if (sm->d_esdf_observed) (void)hipFree(sm->d_esdf_observed);
-  if (sm->d_tsdf_rgba) (void)hipFree(sm->d_tsdf_rgba);
-  sm->d_tsdf_distance = sm->d_tsdf_weight = sm->d_esdf_distance = nullptr;
-  sm->d_esdf_observed = nullptr;
-  sm->d_tsdf_rgba = nullptr;
+  sm->d_tsdf_distance.release();
+  sm->d_tsdf_weight.release();
+  sm->d_esdf_distance.release();
+  sm->d_esdf_observed.release();
+  sm->d_tsdf_rgba.release();
   return VGX_OK;
 }
 
@@ -603,18 +588,14 @@ int vgx_submap_set_colors(vgx_submap sm, const uint8_t* rgba) {
   VGX_HIP(ctx, hipSetDevice(ctx->device));
   const size_t bytes = std::max<size_t>((size_t)sm->n_blocks * sm->vps * sm->vps * sm->vps * 4, 4);  // (never null: null means none)
   // staged through a fresh buffer, so that colours already held are whole or replaced, never half of each
-  uint32_t* fresh = nullptr;
-  hipError_t e = hipMalloc(&fresh, bytes);
+  DeviceArray<uint32_t> fresh;
+  hipError_t e = fresh.alloc(bytes);
   if (e != hipSuccess) return vgx::alloc_error(ctx, e, "vgx_submap_set_colors: allocating colours");
   if (sm->n_blocks > 0) e = hipMemcpyAsync(fresh, rgba, bytes, hipMemcpyHostToDevice, ctx->stream);
   // (pageable host memory: finished before the caller's array goes away; what was queued on the old colours has run too)
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) {
-    (void)hipFree(fresh);
-    VGX_HIP(ctx, e);
-  }
-  if (sm->d_tsdf_rgba) (void)hipFree(sm->d_tsdf_rgba);
-  sm->d_tsdf_rgba = fresh;
+  VGX_HIP(ctx, e);
+  sm->d_tsdf_rgba.swap(fresh);  // the old colours leave with `fresh`
   return VGX_OK;
 }
 
@@ -675,16 +656,7 @@ int vgx_submap_destroy(vgx_submap sm) {
     }
   }
   (void)hipSetDevice(sm->ctx->device);
-  vgx_submap_release_raw_layers(sm);
-  if (sm->d_lut) (void)hipFree(sm->d_lut);
-  if (sm->d_block_index) (void)hipFree(sm->d_block_index);
-  if (sm->d_iso_block_index) (void)hipFree(sm->d_iso_block_index);
-  if (sm->d_block_has_data) (void)hipFree(sm->d_block_has_data);
-  for (int k = 0; k < 2; ++k) {
-    if (sm->grid[k].d_bricks) (void)hipFree(sm->grid[k].d_bricks);
-    if (sm->grid[k].d_quad) (void)hipFree(sm->grid[k].d_quad);
-    reset_point_set(sm->points[k]);
-  }
+  (void)hipStreamSynchronize(sm->ctx->stream);
   delete sm;
   return VGX_OK;
 }
@@ -766,8 +738,8 @@ int vgx_submap_set_points(vgx_submap sm, int32_t point_type, int64_t n, const fl
     for (int64_t i = 0; i < n; ++i) ps.inv_order[(size_t)order[(size_t)i]] = (int32_t)i;
   }
   if (n > 0) {
-    VGX_HIP(ctx, hipMalloc(&ps.d_xyzd, (size_t)n * sizeof(float4)));
-    VGX_HIP(ctx, hipMalloc(&ps.d_weight, (size_t)n * sizeof(float)));
+    VGX_HIP(ctx, ps.d_xyzd.alloc_n((size_t)n));
+    VGX_HIP(ctx, ps.d_weight.alloc_n((size_t)n));
     VGX_HIP(ctx, hipMemcpy(ps.d_xyzd, h_xyzd.data(), (size_t)n * sizeof(float4), hipMemcpyHostToDevice));
     VGX_HIP(ctx, hipMemcpy(ps.d_weight, h_w.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
   }

@@ -164,8 +164,8 @@ int vgx_submap_generate_esdf(vgx_submap sm, const vgx_esdf_config* cfg_in, int32
   if (sm->n_blocks == 0) return VGX_OK;
   const size_t nvox = (size_t)sm->n_blocks * sm->vps * sm->vps * sm->vps;
   VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (!sm->d_esdf_distance) VGX_HIP(ctx, hipMalloc(&sm->d_esdf_distance, nvox * sizeof(float)));
-  if (!sm->d_esdf_observed) VGX_HIP(ctx, hipMalloc(&sm->d_esdf_observed, nvox));
+  if (!sm->d_esdf_distance) VGX_HIP(ctx, sm->d_esdf_distance.alloc_n(nvox));
+  if (!sm->d_esdf_observed) VGX_HIP(ctx, sm->d_esdf_observed.alloc_n(nvox));
   DeviceBuffer s_changed;
   VGX_HIP(ctx, s_changed.alloc(sizeof(int)));
   int* d_changed = s_changed.as<int>();
@@ -207,14 +207,10 @@ int vgx_submap_generate_esdf(vgx_submap sm, const vgx_esdf_config* cfg_in, int32
   if (sweeps_out) *sweeps_out = passes;
   // (re)build the ESDF sampling grid
   if (sm->grid[1].d_bricks) {
-    (void)hipFree(sm->grid[1].d_bricks);
-    sm->grid[1].d_bricks = nullptr;
+    sm->grid[1].d_bricks.release();
     sm->grid[1].present = false;
   }
-  if (sm->grid[1].d_quad) {  // (made on demand from the bricks just dropped: made again when next asked for)
-    (void)hipFree(sm->grid[1].d_quad);
-    sm->grid[1].d_quad = nullptr;
-  }
+  sm->grid[1].d_quad.release();  // (made on demand from the bricks just dropped: made again when next asked for)
   return launch_brickify(sm, 1);
 }
 

@@ -164,14 +164,13 @@ extern "C" int vgx_submap_extract_voxel_points(vgx_submap sm, double min_voxel_w
     ps.n = n;
     ps.sum_weight = sum_w;
     if (rc == VGX_OK && n > 0) {
-      if (hipMalloc(&ps.d_xyzd, (size_t)n * sizeof(float4)) != hipSuccess ||
-          hipMalloc(&ps.d_weight, (size_t)n * sizeof(float)) != hipSuccess)
+      if (ps.d_xyzd.alloc_n((size_t)n) != hipSuccess || ps.d_weight.alloc_n((size_t)n) != hipSuccess)
         rc = set_error(ctx, VGX_ERR_NOMEM, "extract: device allocation failed");
     }
     if (rc == VGX_OK && n > 0) {
       e = hipMemcpyAsync(d_offsets, offsets.data(), ((size_t)nb + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
       if (e == hipSuccess) {
-        const float* esdf = use_esdf_distance ? sm->d_esdf_distance : nullptr;
+        const float* esdf = use_esdf_distance ? sm->d_esdf_distance.get() : nullptr;
         if (sm->vps == 16)
           hipLaunchKernelGGL(extract_write_kernel<16>, dim3(nb), dim3(256), 0, ctx->stream,
                              sm->d_block_index, sm->d_tsdf_distance, sm->d_tsdf_weight, esdf,

@@ -190,6 +190,14 @@ struct DeviceBuffer {
     return static_cast<T*>(p);
   }
 };
+// A DeviceBuffer with its element type: it reads as the T* it replaces (a kernel argument, a descriptor field, a null test),
+// so only where no conversion is looked for -- an arm of ?:, a deduced template argument -- does a reader write get().
+template <class T>
+struct DeviceArray : DeviceBuffer {
+  T* get() const { return static_cast<T*>(p); }
+  operator T*() const { return get(); }
+  hipError_t alloc_n(size_t count) { return alloc(count * sizeof(T)); }
+};
 // Pinned host memory, the same shape: staging buffers and host mirrors go with their handle.
 struct PinnedBuffer {
   void* p = nullptr;
@@ -388,38 +396,38 @@ static_assert(sizeof(Mt19937) == 625 * 4, "Mt19937 is copied to the device as 62
 // (mt_generate_kernel).  Exactly one copy is current at any time.
 struct SamplerEngine {
   Mt19937 host;
-  uint32_t* d_state = nullptr;  // 625 words, allocated at first device use
+  DeviceArray<uint32_t> d_state;  // 625 words, allocated at first device use
   bool on_device = false;       // the device copy is the current one
 };
 
 struct PointSet {
   int64_t n = 0;
   uint64_t version = 0;  // bumped whenever the points are replaced (cost functions remember theirs)
-  float4* d_xyzd = nullptr;
-  float* d_weight = nullptr;
-  float4* d_chunk_bounds = nullptr;  // per kChunkPoints points: bounding sphere {cx,cy,cz,r}
+  DeviceArray<float4> d_xyzd;
+  DeviceArray<float> d_weight;
+  DeviceArray<float4> d_chunk_bounds;  // per kChunkPoints points: bounding sphere {cx,cy,cz,r}
   float aabb_min[3] = {0, 0, 0}, aabb_max[3] = {0, 0, 0};  // of the point positions (n > 0)
   double sum_weight = 0;
   bool present = false;
   std::vector<int64_t> order;            // order[i] = uploaded index of point i (empty = identity)
   std::vector<int32_t> inv_order;        // uploaded index -> device index (for sampling)
   std::vector<double> cumulative_weight; // WeightedSampler::cumulative_item_weights_ (upload order)
-  double* d_cumulative = nullptr;        // device copy, made when a sampling cost function is created
+  DeviceArray<double> d_cumulative;      // device copy, made when a sampling cost function is created
   int32_t search_buckets = 0;
-  int32_t* d_search_lut = nullptr;       // bucket table of the draw (search_buckets + 1 entries), same moment
-  int32_t* d_inv_order = nullptr;        // device copy of inv_order (Morton-sorted sets only)
+  DeviceArray<int32_t> d_search_lut;     // bucket table of the draw (search_buckets + 1 entries), same moment
+  DeviceArray<int32_t> d_inv_order;      // device copy of inv_order (Morton-sorted sets only)
   // WeightedSampler's mutable engine (weighted_sampler.h:36-39): ONE default-seeded std::mt19937 per
   // point set, shared by every cost function that samples this set (vgx_reg_config.sampler_seed == 0)
   SamplerEngine rng;
 };
 
 struct Grid {
-  float* d_bricks = nullptr;
+  DeviceArray<float> d_bricks;
   bool present = false;
   int layout = 0;  // the context's brick layout when this grid was built
   // the same grid as quad bricks, made on demand from the apron bricks for a batch whose constraints all
   // SAMPLE (scattered evaluations: a neighbourhood in 32 contiguous bytes; vgx_ctx_set_sampling_bricks)
-  float* d_quad = nullptr;
+  DeviceArray<float> d_quad;
 };
 
 }  // namespace vgx
@@ -433,25 +441,25 @@ struct vgx_submap_s {
   int32_t vps = 0;
   int32_t n_blocks = 0;
   std::vector<int32_t> block_index;  // host copy [n][3]
-  int32_t* d_block_index = nullptr;
-  int32_t* d_lut = nullptr;
+  vgx::DeviceArray<int32_t> d_block_index;
+  vgx::DeviceArray<int32_t> d_lut;
   int32_t lut_min[3] = {0, 0, 0};
   int32_t lut_dim[3] = {0, 0, 0};
   // raw layers (voxblox layout), kept for point extraction
-  float* d_tsdf_distance = nullptr;
-  float* d_tsdf_weight = nullptr;
+  vgx::DeviceArray<float> d_tsdf_distance;
+  vgx::DeviceArray<float> d_tsdf_weight;
   // the TSDF voxels' colours, one packed word per voxel (bytes r g b a, r lowest: TsdfLayerDev::rgba), or null: only a
   // submap that asked for them pays the 4 B per voxel (vgx_submap_from_tsdf_layer_colored, vgx_submap_set_colors)
-  uint32_t* d_tsdf_rgba = nullptr;
-  float* d_esdf_distance = nullptr;
-  uint8_t* d_esdf_observed = nullptr;
+  vgx::DeviceArray<uint32_t> d_tsdf_rgba;
+  vgx::DeviceArray<float> d_esdf_distance;
+  vgx::DeviceArray<uint8_t> d_esdf_observed;
   vgx::Grid grid[2];       // [0] TSDF, [1] ESDF sampling grids
   vgx::PointSet points[2]; // by VGX_POINTS_*
   std::vector<int32_t> isosurface_blocks;  // block slots holding isosurface vertices (VSM:237-240)
-  int32_t* d_iso_block_index = nullptr;    // [isosurface_blocks.size()][3]
+  vgx::DeviceArray<int32_t> d_iso_block_index;  // [isosurface_blocks.size()][3]
   // per block: 1 if any voxel of the raw TSDF layer has weight > 0 (vgx_project.hip), computed at first use and kept:
   // a finished submap is immutable, and the flags stay valid after vgx_submap_release_raw_layers
-  uint8_t* d_block_has_data = nullptr;
+  vgx::DeviceArray<uint8_t> d_block_has_data;
   vgx::GridDev grid_dev(int which) const;
   int ensure_quad_grid(int which);  // apron bricks -> quad bricks, once (vgx_context.hip)
   // Lifetime (guarded by vgx::lifetime_mu()): cost functions made from this submap.  vgx_submap_destroy while users > 0

@@ -295,7 +295,7 @@ static int extract_isosurface(vgx_submap sm, IsoParams p, PointSet& ps) {
   const int64_t n = offsets[(size_t)nb];
   ps.n = n;
   if (n == 0) return VGX_OK;
-  if (hipMalloc(&ps.d_xyzd, (size_t)n * sizeof(float4)) != hipSuccess || hipMalloc(&ps.d_weight, (size_t)n * sizeof(float)) != hipSuccess)
+  if (ps.d_xyzd.alloc_n((size_t)n) != hipSuccess || ps.d_weight.alloc_n((size_t)n) != hipSuccess)
     return set_error(ctx, VGX_ERR_NOMEM, kFn + "point allocation failed");
   VGX_HIP(ctx, hipMemcpyAsync(d_offsets.p, offsets.data(), ((size_t)nb + 1) * 8, hipMemcpyHostToDevice, st));
   launch_iso<3>(sm, p, d_counts.as<int32_t>(), d_offsets.as<int64_t>(), ps.d_xyzd, ps.d_weight, d_has.as<unsigned char>(),
@@ -331,10 +331,7 @@ extern "C" int vgx_submap_extract_isosurface_points(vgx_submap sm, double min_vo
   PointSet& ps = sm->points[VGX_POINTS_ISOSURFACE];
   reset_point_set(ps);
   sm->isosurface_blocks.clear();
-  if (sm->d_iso_block_index) {
-    (void)hipFree(sm->d_iso_block_index);
-    sm->d_iso_block_index = nullptr;
-  }
+  sm->d_iso_block_index.release();
   if (n_points_out) *n_points_out = 0;
   if (sm->n_blocks == 0) {
     ps.present = true;
@@ -363,7 +360,7 @@ extern "C" int vgx_submap_extract_isosurface_points(vgx_submap sm, double min_vo
     std::vector<int32_t> ib(3 * sm->isosurface_blocks.size());
     for (size_t k = 0; k < sm->isosurface_blocks.size(); ++k)
       for (int a = 0; a < 3; ++a) ib[3 * k + a] = sm->block_index[3 * (size_t)sm->isosurface_blocks[k] + a];
-    if (hipMalloc(&sm->d_iso_block_index, ib.size() * 4) != hipSuccess ||
+    if (sm->d_iso_block_index.alloc_n(ib.size()) != hipSuccess ||
         hipMemcpy(sm->d_iso_block_index, ib.data(), ib.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
       rc = set_error(ctx, VGX_ERR_NOMEM, "vgx_submap_extract_isosurface_points: block list upload failed");
   }

@@ -333,7 +333,7 @@ int project_submaps(vgx_tsdf_layer L, int32_t n, const vgx_submap* submaps, cons
   for (int32_t i = 0; i < n; ++i) {
     vgx_submap sm = submaps[i];
     if (sm->n_blocks > 0 && !sm->d_block_has_data) {
-      VGX_HIP(ctx, hipMalloc(&sm->d_block_has_data, (size_t)sm->n_blocks));
+      VGX_HIP(ctx, sm->d_block_has_data.alloc_n((size_t)sm->n_blocks));
       if (vps == 16)
         hipLaunchKernelGGL(block_has_data_kernel<16>, dim3((unsigned)sm->n_blocks), dim3(256), 0, ctx->stream, sm->d_tsdf_weight,
                            sm->d_block_has_data);
@@ -342,8 +342,7 @@ int project_submaps(vgx_tsdf_layer L, int32_t n, const vgx_submap* submaps, cons
                            sm->d_block_has_data);
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) {
-        (void)hipFree(sm->d_block_has_data);
-        sm->d_block_has_data = nullptr;
+        sm->d_block_has_data.release();
         return fail(ctx, VGX_ERR_HIP, std::string("flag kernel: ") + hipGetErrorString(e));
       }
     }

@@ -1880,7 +1880,7 @@ int vgx_reg_create(vgx_ctx ctx, vgx_submap reference, vgx_submap reading, const 
       // only the entries inside its range, so it never has to clamp the addresses
       std::vector<double> padded(mps.cumulative_weight);
       padded.insert(padded.end(), 3, INFINITY);
-      e = hipMalloc(&mps.d_cumulative, padded.size() * sizeof(double));
+      e = mps.d_cumulative.alloc_n(padded.size());
       if (e == hipSuccess)
         e = hipMemcpy(mps.d_cumulative, padded.data(), padded.size() * sizeof(double), hipMemcpyHostToDevice);
     }
@@ -1898,13 +1898,13 @@ int vgx_reg_create(vgx_ctx ctx, vgx_submap reference, vgx_submap reading, const 
         while (pos < cum.size() && !(target < cum[pos])) ++pos;  // first element > target
         lut[(size_t)k] = (int32_t)pos;
       }
-      e = hipMalloc(&mps.d_search_lut, lut.size() * sizeof(int32_t));
+      e = mps.d_search_lut.alloc_n(lut.size());
       if (e == hipSuccess)
         e = hipMemcpy(mps.d_search_lut, lut.data(), lut.size() * sizeof(int32_t), hipMemcpyHostToDevice);
       mps.search_buckets = (int32_t)K;
     }
     if (e == hipSuccess && !mps.inv_order.empty() && !mps.d_inv_order) {
-      e = hipMalloc(&mps.d_inv_order, (size_t)mps.n * sizeof(int32_t));
+      e = mps.d_inv_order.alloc_n((size_t)mps.n);
       if (e == hipSuccess)
         e = hipMemcpy(mps.d_inv_order, mps.inv_order.data(), (size_t)mps.n * sizeof(int32_t),
                       hipMemcpyHostToDevice);
@@ -1934,7 +1934,6 @@ int vgx_reg_destroy(vgx_reg r) {
   }
   (void)hipSetDevice(r->ctx->device);
   (void)hipStreamSynchronize(r->ctx->stream);
-  if (r->rng.d_state) (void)hipFree(r->rng.d_state);
   // the submaps this cost function kept alive (vgx_submap_destroy was called on them while it existed)
   vgx_submap orphan[2] = {nullptr, nullptr};
   {
@@ -2255,10 +2254,7 @@ int vgx_reg_batch_create(vgx_ctx ctx, int32_t n, const vgx_reg* regs, const int3
       }
       if (rc_q != VGX_ERR_NOMEM) return rc_q;
       VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the copies' kernels are in flight)
-      for (auto& m : made) {
-        (void)hipFree(m.first->grid[m.second].d_quad);
-        m.first->grid[m.second].d_quad = nullptr;
-      }
+      for (auto& m : made) m.first->grid[m.second].d_quad.release();
       static bool told = false;
       if (!told) {
         told = true;
@@ -2360,7 +2356,7 @@ int vgx_reg_batch_create(vgx_ctx ctx, int32_t n, const vgx_reg* regs, const int3
       std::vector<StreamJobDev> jd(b->stream_jobs.size());
       for (size_t j = 0; j < jd.size(); ++j) {
         SamplerEngine* e = b->stream_jobs[j].engine;
-        if (!e->d_state && hipMalloc(&e->d_state, sizeof(Mt19937)) != hipSuccess) {
+        if (!e->d_state && e->d_state.alloc(sizeof(Mt19937)) != hipSuccess) {
           vgx_reg_batch_destroy(b);
           return set_error(ctx, VGX_ERR_NOMEM, "vgx_reg_batch_create: sampler state allocation failed");
         }

@@ -805,10 +805,8 @@ static int submap_from_tsdf_layer(vgx_ctx ctx, vgx_tsdf_layer L, int32_t submap_
   if (rc == VGX_OK) rc = build_block_lut(sm);
   if (rc == VGX_OK && nb > 0) {
     const size_t nvox = (size_t)nb * d.vps * d.vps * d.vps;
-    if (hipMalloc(&sm->d_block_index, (size_t)nb * 12) != hipSuccess ||
-        hipMalloc(&sm->d_tsdf_distance, nvox * sizeof(float)) != hipSuccess ||
-        hipMalloc(&sm->d_tsdf_weight, nvox * sizeof(float)) != hipSuccess ||
-        (keep_colors && hipMalloc(&sm->d_tsdf_rgba, nvox * sizeof(uint32_t)) != hipSuccess)) {
+    if (sm->d_block_index.alloc_n(3 * (size_t)nb) != hipSuccess || sm->d_tsdf_distance.alloc_n(nvox) != hipSuccess ||
+        sm->d_tsdf_weight.alloc_n(nvox) != hipSuccess || (keep_colors && sm->d_tsdf_rgba.alloc_n(nvox) != hipSuccess)) {
       (void)hipGetLastError();  // (clear the sticky out-of-memory status, for both calls: alloc_error does the same)
       rc = set_error(ctx, VGX_ERR_NOMEM, std::string(fn) + ": device allocation failed");
     } else {
@@ -835,7 +833,7 @@ static int submap_from_tsdf_layer(vgx_ctx ctx, vgx_tsdf_layer L, int32_t submap_
     }
   }
   // (an empty layer: one word, so that the submap still reports colours)
-  if (rc == VGX_OK && nb == 0 && keep_colors && hipMalloc(&sm->d_tsdf_rgba, sizeof(uint32_t)) != hipSuccess) {
+  if (rc == VGX_OK && nb == 0 && keep_colors && sm->d_tsdf_rgba.alloc_n(1) != hipSuccess) {
     (void)hipGetLastError();
     rc = set_error(ctx, VGX_ERR_NOMEM, std::string(fn) + ": device allocation failed");
   }
