@@ -38,6 +38,7 @@ extern "C" {
 #define VGX_ERR_NOMEM (-3)       /* host or device allocation failed         */
 #define VGX_ERR_UNSUPPORTED (-4) /* e.g. voxels_per_side not in {8,16}       */
 #define VGX_ERR_NO_DEVICE (-5)   /* no HIP device / not gfx950               */
+#define VGX_ERR_NOT_POSITIVE_DEFINITE (-6) /* vgx_dense_spd_solve: a pivot that is not positive or not finite */
 
 typedef struct vgx_ctx_s* vgx_ctx;
 typedef struct vgx_submap_s* vgx_submap;
@@ -1502,6 +1503,128 @@ typedef struct vgx_map_file_submap_data {
 VGX_API int vgx_map_file_write(const char* path, int32_t format, double voxel_size,
                                int32_t voxels_per_side, int32_t n_submaps,
                                const vgx_map_file_submap_data* submaps);
+
+/* ---- Pose graph: the solve ----------------------------------------------- */
+/* PoseGraph::optimize() (voxgraph/src/backend/pose_graph.cpp:85-106) as a library call: Levenberg-Marquardt over the
+ * 4-DoF poses {x, y, z, yaw} of the graph's nodes, the registration constraints evaluated by a vgx_reg_batch, the
+ * relative-pose constraints (odometry, loop closures, heights: RelativePoseCostFunction,
+ * relative_pose_cost_function_inl.h:8-70) on the host in f64, and the damped normal equations assembled, factorised
+ * (dense Cholesky) and solved on the device in f64.  No robust loss (the reference passes none, constraint.h:34), no
+ * ordering, no sparsity: the reduced matrix is DENSE, (4 x free nodes)^2 doubles twice over -- more than 4096 free
+ * nodes are refused with VGX_ERR_UNSUPPORTED (4 GiB at the limit).
+ *
+ * THE LOOP (what harness/lm.py restates for Ceres' trust-region minimiser).  Per iteration, at the accepted poses x
+ * with cost, gradient g and Gauss-Newton matrix H over the free variables in ascending node order:
+ *   stop GRADIENT_TOLERANCE when max |g| <= gradient_tolerance;
+ *   D^2 = clip(diag(H), 1e-6, 1e32), A = H + diag(D^2 / radius), step = -A^-1 g (Cholesky; a pivot that is not
+ *   positive or not finite: radius /= decrease, decrease *= 2, next iteration);
+ *   stop PARAMETER_TOLERANCE when |step| <= parameter_tolerance * (|x_free| + parameter_tolerance);
+ *   candidate = x + step, every yaw wrapped as a - 2 pi floor((a + pi) / 2 pi); its cost by a COST-ONLY evaluation
+ *   (vgx_reg_batch_evaluate_cost); gain ratio rho = (cost - trial cost) / -(g.step + 0.5 step.(H step)), -1 when the
+ *   model does not decrease;
+ *   rho > 1e-3: accept -- one full evaluation at the candidate, radius = min(radius / max(1/3, 1 - (2 rho - 1)^3),
+ *   1e16), decrease = 2, stop FUNCTION_TOLERANCE when |cost change| / cost <= function_tolerance;
+ *   else radius /= decrease, decrease *= 2;
+ *   stop MAX_SOLVER_TIME / MAX_ITERATIONS.
+ * cost = 0.5 (registration + edges); the registration cost is the per-constraint costs added in list order from 0.0,
+ * for both kinds of evaluation, so a trial cost and the full evaluation at the same poses agree bit for bit
+ * (all-points batches; a sampling batch draws anew at every evaluation, and the full one's cost is then kept).
+ *
+ * THE ORDER CONTRACT.  Every number of a solve is reproducible from a sequential restatement
+ * (tests/pose_graph_ref.py), bit for bit:
+ *   assembly   every 4x4 block of H is 0.0 plus its contributions in this order: the fused buffer's diagonal block;
+ *              the registration off-diagonal blocks in constraint-list order (constraint c = (a, b): off[c] at (a, b),
+ *              its transpose at (b, a)); the edges in list order (aa, bb, ab, ab^T).  g likewise.  No atomics.
+ *   Cholesky   right-looking, 64-wide panels; every element's history is a_ij <- a_ij - l_ik l_jk for k ascending,
+ *              one rounded multiply and one rounded subtract at a time, then one division by l_jj (one sqrt on the
+ *              diagonal): the blocked factor IS the unblocked right-looking one.  No FMA, no f64 MFMA.
+ *   solves     column-oriented forward and back substitution, the same per-element order; H step: per row, ascending
+ *              columns, from 0.0; the host's dot products and norms: ascending, from 0.0.
+ *
+ * vgx_pose_graph_create: n_nodes nodes; constant[i] != 0 fixes node i (the reference fixes the first submap,
+ * pose_graph_interface.cpp:30-32, and every reference-frame node).  constant == NULL: node 0 alone is constant.
+ * vgx_pose_graph_set_registration: the registration constraints, or NULL for none.  The batch is NOT owned; it must
+ * hold the whole list (n_global == n) over node indices < n_nodes.  Destroying a batch a graph was given is deferred
+ * until the graph lets go of it (another batch, NULL, or vgx_pose_graph_destroy); the graph refuses to solve meanwhile.
+ * vgx_pose_graph_set_edges: replaces the list of relative-pose edges (allowed between solves): residual =
+ * sqrt_information * [R(yaw_a)^T (t_b - t_a) - t_obs, normalize(yaw_b - yaw_a - yaw_obs)], sqrt_information a full
+ * row-major 4x4 (the reference multiplies by a matrix, :60).  An absolute constraint is an edge from a constant
+ * reference-frame node. */
+typedef struct vgx_pose_graph_s* vgx_pose_graph;
+typedef struct vgx_pose_graph_edge {
+  int32_t a, b;
+  double t_obs[3];
+  double yaw_obs;
+  double sqrt_information[16];
+} vgx_pose_graph_edge;
+typedef struct vgx_pose_graph_options {
+  double parameter_tolerance;              /* 3e-3 (pose_graph.cpp:93) */
+  double function_tolerance;               /* 1e-6  */
+  double gradient_tolerance;               /* 1e-10 */
+  double max_solver_time_in_seconds;       /* 4 (pose_graph.cpp:95) */
+  double initial_trust_region_radius;      /* 1e4   */
+  int32_t max_num_iterations;              /* 50    */
+  int32_t exclude_registration_constraints; /* 0; pose_graph.cpp:74-83: the first stage after a loop closure */
+} vgx_pose_graph_options;
+/* ceres::TerminationType */
+#define VGX_CONVERGENCE 0
+#define VGX_NO_CONVERGENCE 1
+#define VGX_FAILURE 2
+/* which rule ended the solve */
+#define VGX_TERMINATION_PARAMETER_TOLERANCE 0
+#define VGX_TERMINATION_FUNCTION_TOLERANCE 1
+#define VGX_TERMINATION_GRADIENT_TOLERANCE 2
+#define VGX_TERMINATION_MAX_ITERATIONS 3
+#define VGX_TERMINATION_MAX_SOLVER_TIME 4
+#define VGX_TERMINATION_NO_FREE_NODES 5
+typedef struct vgx_pose_graph_summary {
+  int32_t termination_type;         /* VGX_CONVERGENCE / VGX_NO_CONVERGENCE / VGX_FAILURE */
+  int32_t termination_reason;       /* VGX_TERMINATION_* */
+  int32_t num_iterations;
+  int32_t num_successful_steps;
+  int32_t num_full_evaluations;     /* residuals and Jacobians: the first one and one per accepted step */
+  int32_t num_cost_evaluations;     /* cost only: one per trial step */
+  int32_t num_factorization_failures;
+  int32_t num_free_nodes;
+  double initial_cost, final_cost;
+  double total_seconds;
+  double registration_seconds;      /* inside the vgx_reg_batch evaluations (launch to result on the host) */
+  double linear_algebra_seconds;    /* damping, factorisation, substitutions, H step (launch to result on the host) */
+} vgx_pose_graph_summary;
+/* one record per iteration of the last solve; what an iteration did not get to is 0 */
+typedef struct vgx_pose_graph_iteration {
+  double cost;          /* at the accepted poses the iteration started from */
+  double trial_cost;
+  double gain_ratio;
+  double radius;        /* the radius the step was computed with */
+  double step_norm;
+  int32_t accepted;
+  int32_t factorization_failed;
+} vgx_pose_graph_iteration;
+VGX_API int vgx_pose_graph_create(vgx_ctx ctx, int32_t n_nodes, const int32_t* constant /* [n_nodes] or NULL */,
+                                  vgx_pose_graph* out);
+VGX_API int vgx_pose_graph_destroy(vgx_pose_graph graph);
+VGX_API int vgx_pose_graph_set_registration(vgx_pose_graph graph, vgx_reg_batch batch);
+VGX_API int vgx_pose_graph_set_edges(vgx_pose_graph graph, int32_t n_edges, const vgx_pose_graph_edge* edges);
+VGX_API void vgx_pose_graph_options_default(vgx_pose_graph_options* options);
+/* poses: host [n_nodes][4] f64, in and out (constant nodes keep their position; every yaw comes back wrapped once a
+ * step was tried).  options NULL: the defaults.  summary nullable.  Synchronous; one call at a time per graph.
+ * Refused with VGX_ERR_INVALID (vgx_last_error says which): NULL graph or poses, a graph with neither registration
+ * constraints nor edges, a batch that was destroyed, is sharded, or names a node >= n_nodes, a pose that is not finite.
+ * A graph whose nodes are all constant returns VGX_OK at once with zero iterations. */
+VGX_API int vgx_pose_graph_optimize(vgx_pose_graph graph, const vgx_pose_graph_options* options, double* poses,
+                                    vgx_pose_graph_summary* summary);
+/* the last solve's iterations: *n_iterations (nullable) = their number; the first min(capacity, n) are written */
+VGX_API int vgx_pose_graph_history(vgx_pose_graph graph, int32_t capacity, vgx_pose_graph_iteration* iterations,
+                                   int32_t* n_iterations);
+/* the reduced normal equations at the poses the last solve ended at (its last full evaluation): n_free_variables
+ * (nullable) = 4 x free nodes = N; H host [N][N] row-major and g host [N], either nullable. */
+VGX_API int vgx_pose_graph_download_system(vgx_pose_graph graph, int32_t* n_free_variables, double* H, double* g);
+/* The factorisation on its own, for a caller with a trust-region loop of their own: solves A x = b for a symmetric
+ * positive definite A (host row-major [n][n], the LOWER triangle is read), b and x host [n]; L (nullable) host [n][n]
+ * receives the Cholesky factor, zeros above the diagonal.  1 <= n <= 16384.  VGX_ERR_NOT_POSITIVE_DEFINITE when a
+ * pivot is not positive or not finite (x and L are then unspecified); the solve above uses the same kernels. */
+VGX_API int vgx_dense_spd_solve(vgx_ctx ctx, int32_t n, const double* A, const double* b, double* x, double* L);
 
 #ifdef __cplusplus
 }

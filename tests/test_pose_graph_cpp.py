@@ -1,0 +1,65 @@
+"""voxgraph_amd/cpp/gpu_pose_graph.h from plain C++ (tests/cpp/pose_graph_smoke.cpp): the header compiles and its host
+parts work without a device; on the GPU the graph it builds ends at the poses the Python wrapper reaches on the same
+nodes and edges (to rounding: the sqrt-information comes from two 4x4 factorisations)."""
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "cpp", "pose_graph_smoke.cpp")
+
+
+def _build(tmp_path):
+    import __graft_entry__ as g
+    g.build()
+    exe = str(tmp_path / "pose_graph_smoke")
+    lib = os.path.join(ROOT, "voxgraph_amd", "lib")
+    inc = ["-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "voxgraph_amd", "cpp")]
+    subprocess.check_call(["g++", "-std=c++14", "-O1", "-Wall", "-Wextra", "-Werror", *inc, SRC, "-o", exe, "-L", lib, "-lvoxgraph_amd",
+                           "-lpthread", f"-Wl,-rpath,{lib}", "-Wl,-rpath,/opt/rocm/lib"])
+    return exe
+
+
+def test_pose_graph_header_compiles_and_its_host_parts_work(tmp_path):
+    r = subprocess.run([_build(tmp_path), "compile"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "POSE_GRAPH_COMPILE_OK" in r.stdout, (r.returncode, r.stdout + r.stderr)
+
+
+@pytest.mark.gpu
+def test_cpp_graph_ends_where_the_python_wrapper_ends(tmp_path):
+    from voxgraph_amd import capi
+    dst = tmp_path / "out.bin"
+    r = subprocess.run([_build(tmp_path), str(dst)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "POSE_GRAPH_SMOKE_OK" in r.stdout, (r.returncode, r.stdout + r.stderr)
+    got = np.fromfile(dst, np.float64)
+    # the same graph: node 0 the reference frame, nodes 1..8 the submaps
+    n, pi = 8, math.pi
+    poses = np.zeros((n + 1, 4))
+    for k in range(n):
+        a = 2.0 * pi * k / n
+        poses[k + 1] = [2.0 * math.cos(a) - 2.0 + 0.05 * k, 2.0 * math.sin(a) - 0.03 * k, 0.01 * k, 0.9 * a / pi - 0.01 * k]
+    odo = np.diag(np.sqrt([1.0, 1.0, 2500.0, 2500.0]))
+    loop = np.linalg.cholesky(np.array([[100.0, 20, 0, 0], [20, 100, 0, 0], [0, 0, 2500, 0], [0, 0, 0, 2500]])).T
+    edges = []
+    for k in range(n - 1):
+        a, b = 2.0 * pi * k / n, 2.0 * pi * (k + 1) / n
+        dx, dy, ya = 2.0 * (math.cos(b) - math.cos(a)), 2.0 * (math.sin(b) - math.sin(a)), 0.9 * a / pi
+        t = [math.cos(ya) * dx + math.sin(ya) * dy, -math.sin(ya) * dx + math.cos(ya) * dy, 0.0]
+        edges.append(capi.pose_graph_edge(k + 1, k + 2, t, 0.9 * (b - a) / pi, odo))
+    a = 2.0 * pi * (n - 1) / n
+    ya, dx, dy = 0.9 * a / pi, 2.0 * (1.0 - math.cos(a)), -2.0 * math.sin(a)
+    edges.append(capi.pose_graph_edge(n, 1, [math.cos(ya) * dx + math.sin(ya) * dy, -math.sin(ya) * dx + math.cos(ya) * dy, 0.0], -ya, loop))
+    edges.append(capi.pose_graph_edge(0, 1 + n // 2, [-4.0, 0.0, 0.0], 0.9, odo))
+    ctx = capi.Context(0)
+    pg = capi.PoseGraph(ctx, n + 1, [1, 1] + [0] * (n - 1))
+    pg.set_edges(edges)
+    x, s = pg.optimize(poses)
+    pg.destroy()
+    ctx.close()
+    assert got[0] == s["num_iterations"] >= 2 and got[1] == s["termination_reason"]
+    # the header's 4x4 LLT and numpy's agree to rounding, not to the bit: the costs and poses to 1e-12
+    np.testing.assert_allclose(got[2:4], [s["initial_cost"], s["final_cost"]], rtol=1e-10)
+    np.testing.assert_allclose(got[4:].reshape(n, 4), x[1:], rtol=0, atol=1e-10)

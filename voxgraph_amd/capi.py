@@ -20,6 +20,7 @@ BENCH_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), os.path.basename(LIB_PA
 OK = 0
 EVALUATE_FALSE = 1
 ERR_INVALID, ERR_HIP, ERR_NOMEM, ERR_UNSUPPORTED, ERR_NO_DEVICE = -1, -2, -3, -4, -5
+ERR_NOT_POSITIVE_DEFINITE = -6
 
 BRICKS_APRON, BRICKS_QUAD = 0, 1
 SAMPLING_BRICKS_SAME, SAMPLING_BRICKS_QUAD = 0, 1
@@ -134,6 +135,39 @@ class TsdfConfig(C.Structure):
                 ("clear_checks_every_n_frames", C.c_int32), ("enable_anti_grazing", C.c_int32),
                 ("deterministic", C.c_int32), ("integration_order", C.c_int32)]
 
+
+class PoseGraphEdge(C.Structure):
+    _fields_ = [("a", C.c_int32), ("b", C.c_int32), ("t_obs", C.c_double * 3), ("yaw_obs", C.c_double),
+                ("sqrt_information", C.c_double * 16)]
+
+
+class PoseGraphOptions(C.Structure):
+    _fields_ = [("parameter_tolerance", C.c_double), ("function_tolerance", C.c_double), ("gradient_tolerance", C.c_double),
+                ("max_solver_time_in_seconds", C.c_double), ("initial_trust_region_radius", C.c_double),
+                ("max_num_iterations", C.c_int32), ("exclude_registration_constraints", C.c_int32)]
+
+
+class PoseGraphSummary(C.Structure):
+    _fields_ = [("termination_type", C.c_int32), ("termination_reason", C.c_int32), ("num_iterations", C.c_int32),
+                ("num_successful_steps", C.c_int32), ("num_full_evaluations", C.c_int32), ("num_cost_evaluations", C.c_int32),
+                ("num_factorization_failures", C.c_int32), ("num_free_nodes", C.c_int32), ("initial_cost", C.c_double),
+                ("final_cost", C.c_double), ("total_seconds", C.c_double), ("registration_seconds", C.c_double),
+                ("linear_algebra_seconds", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class PoseGraphIteration(C.Structure):
+    _fields_ = [("cost", C.c_double), ("trial_cost", C.c_double), ("gain_ratio", C.c_double), ("radius", C.c_double),
+                ("step_norm", C.c_double), ("accepted", C.c_int32), ("factorization_failed", C.c_int32)]
+
+
+CONVERGENCE, NO_CONVERGENCE, FAILURE = 0, 1, 2      # ceres::TerminationType
+(TERMINATION_PARAMETER_TOLERANCE, TERMINATION_FUNCTION_TOLERANCE, TERMINATION_GRADIENT_TOLERANCE, TERMINATION_MAX_ITERATIONS,
+ TERMINATION_MAX_SOLVER_TIME, TERMINATION_NO_FREE_NODES) = range(6)
+TERMINATION_NAMES = ("parameter_tolerance", "function_tolerance", "gradient_tolerance", "max_iterations", "max_solver_time",
+                     "no_free_nodes")          # harness/lm.py's names for the same rules
 
 TSDF_ORDER_MIXED, TSDF_ORDER_SORTED = 0, 1
 # what a vgx_map_msg holds; voxblox MapDerializationAction (include/voxgraph_amd.h, "Map messages")
@@ -325,6 +359,15 @@ SIGNATURES = {
     "vgx_map_file_load_submap": (C.c_int, [vp, vp, C.c_int32, C.POINTER(vp)]),
     "vgx_map_file_write": (C.c_int, [C.c_char_p, C.c_int32, C.c_double, C.c_int32, C.c_int32,
                                      C.POINTER(MapFileSubmapData)]),
+    "vgx_pose_graph_create": (C.c_int, [vp, C.c_int32, i32p, C.POINTER(vp)]),
+    "vgx_pose_graph_destroy": (C.c_int, [vp]),
+    "vgx_pose_graph_set_registration": (C.c_int, [vp, vp]),
+    "vgx_pose_graph_set_edges": (C.c_int, [vp, C.c_int32, C.POINTER(PoseGraphEdge)]),
+    "vgx_pose_graph_options_default": (None, [C.POINTER(PoseGraphOptions)]),
+    "vgx_pose_graph_optimize": (C.c_int, [vp, C.POINTER(PoseGraphOptions), f64p, C.POINTER(PoseGraphSummary)]),
+    "vgx_pose_graph_history": (C.c_int, [vp, C.c_int32, C.POINTER(PoseGraphIteration), i32p]),
+    "vgx_pose_graph_download_system": (C.c_int, [vp, i32p, f64p, f64p]),
+    "vgx_dense_spd_solve": (C.c_int, [vp, C.c_int32, f64p, f64p, f64p, f64p]),
 }
 
 # every symbol include/voxgraph_amd_bench.h declares (libvoxgraph_amd_bench.so: test and benchmark tooling)
@@ -1011,6 +1054,84 @@ class RegistrationBatch:
     def destroy(self):
         if self.h:
             self.ctx.lib.vgx_reg_batch_destroy(self.h)
+            self.h = None
+
+
+def pose_graph_options(**kw):
+    """vgx_pose_graph_options with the defaults of pose_graph.cpp:85-106, overridden by keyword"""
+    o = PoseGraphOptions()
+    load().vgx_pose_graph_options_default(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise TypeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def pose_graph_edge(a, b, t_obs, yaw_obs, sqrt_information):
+    e = PoseGraphEdge()
+    e.a, e.b, e.yaw_obs = int(a), int(b), float(yaw_obs)
+    e.t_obs[:] = [float(v) for v in t_obs]
+    e.sqrt_information[:] = [float(v) for v in np.asarray(sqrt_information, np.float64).reshape(16)]
+    return e
+
+
+def dense_spd_solve(ctx, A, b, want_factor=True):
+    """vgx_dense_spd_solve -> (x, L or None); raises VgxError(ERR_NOT_POSITIVE_DEFINITE) at a bad pivot"""
+    A, b = _f64(A), _f64(b)
+    n = len(b)
+    x = np.zeros(n)
+    L = np.zeros((n, n)) if want_factor else None
+    ctx.check(ctx.lib.vgx_dense_spd_solve(ctx.h, n, _ptr(A, f64p), _ptr(b, f64p), _ptr(x, f64p), _ptr(L, f64p)))
+    return x, L
+
+
+class PoseGraph:
+    """vgx_pose_graph: PoseGraph::optimize() on the device (include/voxgraph_amd.h, "Pose graph: the solve")."""
+
+    def __init__(self, ctx, n_nodes, constant=None):
+        self.ctx, self.n_nodes = ctx, int(n_nodes)
+        flags = None if constant is None else np.ascontiguousarray(constant, np.int32)
+        h = vp()
+        ctx.check(ctx.lib.vgx_pose_graph_create(ctx.h, self.n_nodes, _ptr(flags, i32p), C.byref(h)))
+        self.h = h
+
+    def set_registration(self, batch):
+        self.ctx.check(self.ctx.lib.vgx_pose_graph_set_registration(self.h, batch.h if batch is not None else None))
+
+    def set_edges(self, edges):
+        """edges: PoseGraphEdge items (pose_graph_edge(...))"""
+        arr = (PoseGraphEdge * max(len(edges), 1))(*edges)
+        self.ctx.check(self.ctx.lib.vgx_pose_graph_set_edges(self.h, len(edges), arr))
+
+    def optimize(self, poses, options=None, **kw):
+        """-> (poses [n_nodes][4], summary dict); keywords override the default options"""
+        opts = options if options is not None else pose_graph_options(**kw)
+        x = np.array(poses, np.float64).reshape(self.n_nodes, 4).copy()
+        s = PoseGraphSummary()
+        self.ctx.check(self.ctx.lib.vgx_pose_graph_optimize(self.h, C.byref(opts), _ptr(x, f64p), C.byref(s)))
+        d = s.as_dict()
+        d["termination"] = TERMINATION_NAMES[s.termination_reason]
+        return x, d
+
+    def history(self):
+        n = C.c_int32()
+        self.ctx.check(self.ctx.lib.vgx_pose_graph_history(self.h, 0, None, C.byref(n)))
+        arr = (PoseGraphIteration * max(n.value, 1))()
+        self.ctx.check(self.ctx.lib.vgx_pose_graph_history(self.h, n.value, arr, None))
+        return [{name: getattr(arr[k], name) for name, _ in PoseGraphIteration._fields_} for k in range(n.value)]
+
+    def download_system(self):
+        """-> (H [N][N], g [N]) of the last full evaluation, N = 4 x free nodes"""
+        n = C.c_int32()
+        self.ctx.check(self.ctx.lib.vgx_pose_graph_download_system(self.h, C.byref(n), None, None))
+        H, g = np.zeros((n.value, n.value)), np.zeros(n.value)
+        self.ctx.check(self.ctx.lib.vgx_pose_graph_download_system(self.h, None, _ptr(H, f64p), _ptr(g, f64p)))
+        return H, g
+
+    def destroy(self):
+        if self.h:
+            self.ctx.lib.vgx_pose_graph_destroy(self.h)
             self.h = None
 
 

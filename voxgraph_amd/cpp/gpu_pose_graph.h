@@ -1,0 +1,207 @@
+// A host mirror of voxgraph::PoseGraph (voxgraph/include/voxgraph/backend/pose_graph.h) as far as solving goes, on
+// vgx_pose_graph (include/voxgraph_amd.h, "Pose graph: the solve"): nodes, registration / relative / absolute pose
+// constraints, optimize(), getSubmapPoses() and the stored summaries.  No Ceres, no Eigen.
+//
+//   voxgraph_amd::GpuPoseGraph graph(gpu_ctx);
+//   graph.addSubmapNode(id, pose, /*constant=*/id == first);            // pose_graph_interface.cpp:24-48
+//   graph.addRegistrationConstraint(reg_first_second, first, second);   // registration_constraint.cpp:33-42
+//   graph.addRelativePoseConstraint(a, b, t_ab, yaw_ab, information);   // odometry, loop closures
+//   graph.addAbsolutePoseConstraint(frame, id, t, yaw, information);    // from a constant reference-frame node
+//   int rc = graph.optimize(/*exclude_registration_constraints=*/false);
+//
+// Error convention: nothing is thrown out of optimize(); it returns the library's status and last_error() its text.
+#ifndef VOXGRAPH_AMD_CPP_GPU_POSE_GRAPH_H_
+#define VOXGRAPH_AMD_CPP_GPU_POSE_GRAPH_H_
+
+#include <array>
+#include <cmath>
+#include <cstdint>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "voxgraph_amd.h"
+
+namespace voxgraph_amd {
+
+// Constraint::Constraint (constraint.cpp:4-38): sqrt_information = L^T of the LLT of the information matrix (row-major
+// 4x4).  false when the matrix is not positive definite.
+inline bool SqrtInformation(const double information[16], double sqrt_information[16]) {
+  double L[16] = {0};
+  for (int j = 0; j < 4; ++j) {
+    double d = information[4 * j + j];
+    for (int k = 0; k < j; ++k) d -= L[4 * j + k] * L[4 * j + k];
+    if (!(d > 0.0) || std::isinf(d)) return false;
+    L[4 * j + j] = std::sqrt(d);
+    for (int i = j + 1; i < 4; ++i) {
+      double v = information[4 * i + j];
+      for (int k = 0; k < j; ++k) v -= L[4 * i + k] * L[4 * j + k];
+      L[4 * i + j] = v / L[4 * j + j];
+    }
+  }
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 4; ++j) sqrt_information[4 * i + j] = L[4 * j + i];
+  return true;
+}
+
+class GpuPoseGraph {
+ public:
+  using Pose = std::array<double, 4>;  // x, y, z, yaw
+  explicit GpuPoseGraph(vgx_ctx ctx) : ctx_(ctx) { vgx_pose_graph_options_default(&options_); }
+  GpuPoseGraph(const GpuPoseGraph&) = delete;
+  GpuPoseGraph& operator=(const GpuPoseGraph&) = delete;
+  ~GpuPoseGraph() { Release(); }
+
+  vgx_pose_graph_options& options() { return options_; }
+
+  // nodes: submaps and reference frames share one numbering, in the order they were added
+  int addSubmapNode(int64_t submap_id, const Pose& pose, bool constant) { return AddNode(submap_index_, submap_id, pose, constant); }
+  int addReferenceFrameNode(int64_t frame_id, const Pose& pose) { return AddNode(frame_index_, frame_id, pose, true); }
+  bool hasSubmapNode(int64_t submap_id) const { return submap_index_.count(submap_id) != 0; }
+
+  // registration constraints: cost functions the caller made and keeps (vgx_reg_create(ctx, reference, reading, ...)).
+  // pose_graph.cpp:62-71 adds the MIRRORED constraint for isosurface points: pass the second cost function, built with
+  // the submaps swapped, as `mirrored` (NULL otherwise).
+  bool addRegistrationConstraint(vgx_reg reg, int64_t first_submap_id, int64_t second_submap_id, vgx_reg mirrored = nullptr) {
+    if (!reg || !hasSubmapNode(first_submap_id) || !hasSubmapNode(second_submap_id)) return Fail("addRegistrationConstraint: unknown submap or NULL cost function");
+    const int32_t a = submap_index_[first_submap_id], b = submap_index_[second_submap_id];
+    regs_.push_back(reg);
+    pairs_.push_back(a);
+    pairs_.push_back(b);
+    if (mirrored) {
+      regs_.push_back(mirrored);
+      pairs_.push_back(b);
+      pairs_.push_back(a);
+    }
+    dirty_ = true;
+    return true;
+  }
+  bool addRelativePoseConstraint(int64_t origin_submap_id, int64_t destination_submap_id, const double t[3], double yaw,
+                                 const double information[16]) {
+    if (!hasSubmapNode(origin_submap_id) || !hasSubmapNode(destination_submap_id)) return Fail("addRelativePoseConstraint: unknown submap");
+    return AddEdge(submap_index_[origin_submap_id], submap_index_[destination_submap_id], t, yaw, information);
+  }
+  bool addAbsolutePoseConstraint(int64_t frame_id, int64_t submap_id, const double t[3], double yaw, const double information[16]) {
+    if (!frame_index_.count(frame_id) || !hasSubmapNode(submap_id)) return Fail("addAbsolutePoseConstraint: unknown frame or submap");
+    return AddEdge(frame_index_[frame_id], submap_index_[submap_id], t, yaw, information);
+  }
+  void resetRegistrationConstraints() {
+    regs_.clear();
+    pairs_.clear();
+    dirty_ = true;
+  }
+  void resetRelativePoseConstraints() {
+    edges_.clear();
+    dirty_ = true;
+  }
+
+  // PoseGraph::optimize(bool exclude_registration_constraints): VGX_OK or the library's status; never throws
+  int optimize(bool exclude_registration_constraints = false) {
+    int rc = Build();
+    if (rc != VGX_OK) return rc;
+    vgx_pose_graph_options opt = options_;
+    opt.exclude_registration_constraints = exclude_registration_constraints ? 1 : 0;
+    vgx_pose_graph_summary summary;
+    rc = vgx_pose_graph_optimize(graph_, &opt, poses_.data(), &summary);
+    if (rc != VGX_OK) return Status(rc);
+    summaries_.push_back(summary);
+    return VGX_OK;
+  }
+  std::map<int64_t, Pose> getSubmapPoses() const {
+    std::map<int64_t, Pose> out;
+    for (const auto& kv : submap_index_) {
+      Pose p;
+      for (int k = 0; k < 4; ++k) p[k] = poses_[4 * static_cast<size_t>(kv.second) + k];
+      out[kv.first] = p;
+    }
+    return out;
+  }
+  const std::vector<vgx_pose_graph_summary>& getSolverSummaries() const { return summaries_; }
+  std::vector<vgx_pose_graph_iteration> lastHistory() const {
+    int32_t n = 0;
+    std::vector<vgx_pose_graph_iteration> out;
+    if (!graph_ || vgx_pose_graph_history(graph_, 0, nullptr, &n) != VGX_OK || n == 0) return out;
+    out.resize(static_cast<size_t>(n));
+    vgx_pose_graph_history(graph_, n, out.data(), nullptr);
+    return out;
+  }
+  const std::string& last_error() const { return error_; }
+
+ private:
+  int AddNode(std::map<int64_t, int32_t>& index, int64_t id, const Pose& pose, bool constant) {
+    auto it = index.find(id);
+    if (it != index.end()) {  // PoseGraph::addSubmapNode replaces a node that exists
+      for (int k = 0; k < 4; ++k) poses_[4 * static_cast<size_t>(it->second) + k] = pose[k];
+      dirty_ = dirty_ || (constant_[static_cast<size_t>(it->second)] != 0) != constant;
+      constant_[static_cast<size_t>(it->second)] = constant ? 1 : 0;
+      return it->second;
+    }
+    const int32_t node = static_cast<int32_t>(constant_.size());
+    index[id] = node;
+    constant_.push_back(constant ? 1 : 0);
+    poses_.insert(poses_.end(), pose.begin(), pose.end());
+    dirty_ = true;
+    return node;
+  }
+  bool AddEdge(int32_t a, int32_t b, const double t[3], double yaw, const double information[16]) {
+    vgx_pose_graph_edge e;
+    e.a = a;
+    e.b = b;
+    for (int k = 0; k < 3; ++k) e.t_obs[k] = t[k];
+    e.yaw_obs = yaw;
+    if (!SqrtInformation(information, e.sqrt_information)) return Fail("the information matrix is not positive definite");
+    edges_.push_back(e);
+    dirty_ = true;
+    return true;
+  }
+  // the handles follow the lists: rebuilt when nodes or constraints changed since the last solve
+  int Build() {
+    if (!dirty_ && graph_) return VGX_OK;
+    Release();
+    int rc = vgx_pose_graph_create(ctx_, static_cast<int32_t>(constant_.size()), constant_.data(), &graph_);
+    if (rc != VGX_OK) return Status(rc);
+    if (!regs_.empty()) {
+      rc = vgx_reg_batch_create(ctx_, static_cast<int32_t>(regs_.size()), regs_.data(), pairs_.data(), nullptr,
+                                static_cast<int32_t>(regs_.size()), &batch_);
+      if (rc != VGX_OK) return Status(rc);
+      rc = vgx_pose_graph_set_registration(graph_, batch_);
+      if (rc != VGX_OK) return Status(rc);
+    }
+    rc = vgx_pose_graph_set_edges(graph_, static_cast<int32_t>(edges_.size()), edges_.data());
+    if (rc != VGX_OK) return Status(rc);
+    dirty_ = false;
+    return VGX_OK;
+  }
+  void Release() {
+    if (graph_) vgx_pose_graph_destroy(graph_);
+    if (batch_) vgx_reg_batch_destroy(batch_);
+    graph_ = nullptr;
+    batch_ = nullptr;
+  }
+  int Status(int rc) {
+    error_ = vgx_last_error(ctx_);
+    return rc;
+  }
+  bool Fail(const char* what) {
+    error_ = what;
+    return false;
+  }
+
+  vgx_ctx ctx_;
+  vgx_pose_graph graph_ = nullptr;
+  vgx_reg_batch batch_ = nullptr;
+  vgx_pose_graph_options options_;
+  std::map<int64_t, int32_t> submap_index_, frame_index_;
+  std::vector<int32_t> constant_;
+  std::vector<double> poses_;
+  std::vector<vgx_reg> regs_;
+  std::vector<int32_t> pairs_;
+  std::vector<vgx_pose_graph_edge> edges_;
+  std::vector<vgx_pose_graph_summary> summaries_;
+  bool dirty_ = true;
+  std::string error_;
+};
+
+}  // namespace voxgraph_amd
+
+#endif  // VOXGRAPH_AMD_CPP_GPU_POSE_GRAPH_H_

@@ -554,6 +554,10 @@ struct vgx_reg_batch_s {
   vgx::PinnedBuffer h_rows;                          // [R x 8][R x 32][R x 32], or empty (too large: fetches copy slices)
   bool rows_have[3] = {false, false, false};         // what the last rows evaluation produced
   bool rows_mirrored = false;                        // the mirror holds the last evaluation (its copy may still be in flight)
+  // Lifetime (vgx::lifetime_mu()): pose graphs that were given this batch (vgx_pose_graph_set_registration);
+  // vgx_reg_batch_destroy while users > 0 is deferred to the last of them letting go (a graph then refuses to solve).
+  int users = 0;
+  bool destroy_requested = false;
 };
 
 // ---------------------------------------------------------------------------

@@ -1,0 +1,872 @@
+// Pose graph: the solve (include/voxgraph_amd.h).  Levenberg-Marquardt over the 4-DoF node poses: registration constraints
+// through a vgx_reg_batch, relative-pose edges on the host in f64, and the reduced normal equations assembled, damped,
+// factorised (dense right-looking Cholesky, 64-wide panels) and solved on the device in f64.  Every number follows the
+// order contract of the header: built with -ffp-contract=off, one rounded multiply and one rounded subtract at a time.
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <map>
+#include <new>
+
+#include "vgx_internal.h"
+
+using namespace vgx;
+
+namespace {
+
+constexpr int kPanel = 64;          // panel width = tile size of the factorisation
+constexpr int kMaxFreeNodes = 4096;
+constexpr int kMaxDenseN = 4 * kMaxFreeNodes;
+constexpr int kEdgeTermDoubles = 56;  // per edge on the device: g_a[4] g_b[4] aa[16] bb[16] ab[16]
+
+// ---------------------------------------------------------------------------
+// assembly: gather through index lists, fixed order, no atomics
+// ---------------------------------------------------------------------------
+struct BlockRecord {
+  int32_t bi, bj;        // block row / column in the reduced matrix
+  int32_t first, count;  // its items
+};
+// item = (offset << 2) | (source << 1) | transpose; source 0: the fused buffer, 1: the edge terms
+__global__ void pg_assemble_blocks_kernel(const BlockRecord* __restrict__ blocks, int n_blocks, const int32_t* __restrict__ items,
+                                          const double* __restrict__ fused, const double* __restrict__ edge, double* __restrict__ H,
+                                          int nf) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_blocks * 16) return;
+  const BlockRecord B = blocks[t >> 4];
+  const int e = t & 15, r = e >> 2, c = e & 3;
+  double acc = 0.0;
+  for (int k = 0; k < B.count; ++k) {
+    const int32_t it = items[B.first + k];
+    const double* src = (it & 2) ? edge : fused;
+    acc = acc + src[(size_t)(it >> 2) + ((it & 1) ? c * 4 + r : e)];
+  }
+  H[(size_t)(4 * B.bi + r) * nf + 4 * B.bj + c] = acc;
+}
+// per free node: records {first, count}; item = (offset << 1) | source
+__global__ void pg_assemble_gradient_kernel(const int32_t* __restrict__ first, const int32_t* __restrict__ items,
+                                            const double* __restrict__ fused, const double* __restrict__ edge, double* __restrict__ g,
+                                            int n_free_nodes) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_free_nodes * 4) return;
+  const int node = t >> 2, k = t & 3;
+  double acc = 0.0;
+  for (int i = first[node]; i < first[node + 1]; ++i) {
+    const int32_t it = items[i];
+    const double* src = (it & 1) ? edge : fused;
+    acc = acc + src[(size_t)(it >> 1) + k];
+  }
+  g[t] = acc;
+}
+// element [0] of every constraint's 45-block
+__global__ void pg_gather_cost_kernel(const double* __restrict__ normal, int n, double* __restrict__ cost) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < n) cost[c] = normal[(size_t)c * kNormalSize];
+}
+// A = H on the diagonal plus clip(H_ii, 1e-6, 1e32) / radius (A holds a copy of H already)
+__global__ void pg_damp_kernel(const double* __restrict__ H, double* __restrict__ A, int nf, double radius) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nf) return;
+  const double h = H[(size_t)i * nf + i];
+  const double d2 = h < 1e-6 ? 1e-6 : (h > 1e32 ? 1e32 : h);  // (a NaN stays a NaN, as numpy's clip leaves it)
+  A[(size_t)i * nf + i] = h + d2 / radius;
+}
+
+// ---------------------------------------------------------------------------
+// Cholesky, right-looking, 64-wide panels (lower triangle of row-major A, in place)
+// ---------------------------------------------------------------------------
+// 1. the diagonal tile, one workgroup, in LDS
+__global__ __launch_bounds__(256) void pg_chol_diag_kernel(double* __restrict__ A, int n, int k0, int w, int* __restrict__ flag) {
+  if (*flag) return;
+  __shared__ double T[kPanel * (kPanel + 1)];
+  const int tid = threadIdx.x;
+  for (int e = tid; e < kPanel * kPanel; e += 256) {
+    const int i = e >> 6, j = e & 63;
+    T[i * (kPanel + 1) + j] = (i < w && j <= i) ? A[(size_t)(k0 + i) * n + k0 + j] : 0.0;
+  }
+  __syncthreads();
+  bool bad = false;
+  for (int k = 0; k < w; ++k) {
+    const double akk = T[k * (kPanel + 1) + k];
+    if (!(akk > 0.0) || isinf(akk)) bad = true;
+    const double lkk = sqrt(akk);
+    __syncthreads();
+    if (tid == 0) T[k * (kPanel + 1) + k] = lkk;
+    if (tid > k && tid < w) T[tid * (kPanel + 1) + k] = T[tid * (kPanel + 1) + k] / lkk;
+    __syncthreads();
+    for (int e = tid; e < kPanel * kPanel; e += 256) {
+      const int i = e >> 6, j = e & 63;
+      if (j > k && j <= i && i < w)
+        T[i * (kPanel + 1) + j] = T[i * (kPanel + 1) + j] - T[i * (kPanel + 1) + k] * T[j * (kPanel + 1) + k];
+    }
+    __syncthreads();
+  }
+  for (int e = tid; e < kPanel * kPanel; e += 256) {
+    const int i = e >> 6, j = e & 63;
+    if (i < w && j <= i) A[(size_t)(k0 + i) * n + k0 + j] = T[i * (kPanel + 1) + j];
+  }
+  if (bad && tid == 0) *flag = 1;
+}
+
+// 2. the panel below it: 64 rows per workgroup, one row per lane, against the factored tile
+__global__ __launch_bounds__(64) void pg_chol_panel_kernel(double* __restrict__ A, int n, int k0, int w, const int* __restrict__ flag) {
+  if (*flag) return;
+  __shared__ double Lt[kPanel * (kPanel + 1) / 2];  // packed lower triangle: (c, j) at c (c + 1) / 2 + j
+  __shared__ double R[kPanel * (kPanel + 1)];
+  const int t = threadIdx.x;
+  const int row0 = k0 + w + blockIdx.x * kPanel;
+  for (int r = 0; r < w; ++r)
+    if (t <= r) Lt[r * (r + 1) / 2 + t] = A[(size_t)(k0 + r) * n + k0 + t];
+  for (int r = 0; r < kPanel; ++r)
+    R[r * (kPanel + 1) + t] = (row0 + r < n && t < w) ? A[(size_t)(row0 + r) * n + k0 + t] : 0.0;
+  __syncthreads();
+  if (row0 + t < n) {
+    double* row = R + t * (kPanel + 1);
+    for (int j = 0; j < w; ++j) {
+      const double x = row[j] / Lt[j * (j + 1) / 2 + j];
+      row[j] = x;
+      for (int c = j + 1; c < w; ++c) row[c] = row[c] - x * Lt[c * (c + 1) / 2 + j];
+    }
+  }
+  __syncthreads();
+  for (int r = 0; r < kPanel; ++r)
+    if (row0 + r < n && t < w) A[(size_t)(row0 + r) * n + k0 + t] = R[r * (kPanel + 1) + t];
+}
+
+// 3. the trailing tiles on or below the diagonal: a 64 x 64 tile per workgroup, a 4 x 4 micro-tile per thread; the
+// accumulators START from the stored a_ij and subtract product by product in ascending k (never a sum of products)
+constexpr int kChunk = 32;            // panel columns staged per pass
+constexpr int kStride = kPanel + 2;   // LDS row stride of a staged chunk, [k][row]: 16-byte aligned rows
+__global__ __launch_bounds__(256) void pg_chol_trailing_kernel(double* __restrict__ A, int n, int k0, int w, int tile0,
+                                                              const int* __restrict__ flag) {
+  if (*flag) return;
+  __shared__ alignas(16) double PI[kChunk * kStride];
+  __shared__ alignas(16) double PJ[kChunk * kStride];
+  const int tid = threadIdx.x;
+  const int t = blockIdx.x;
+  int I = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+  while (I * (I + 1) / 2 > t) --I;
+  while ((I + 1) * (I + 2) / 2 <= t) ++I;
+  const int J = t - I * (I + 1) / 2;
+  const int i0 = (tile0 + I) * kPanel, j0 = (tile0 + J) * kPanel;
+  const int ty = tid >> 4, tx = tid & 15;
+  double acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int row = i0 + ty * 4 + a, col = j0 + tx * 4 + b;
+      acc[a][b] = (row < n && col <= row) ? A[(size_t)row * n + col] : 0.0;
+    }
+  for (int kc = 0; kc < w; kc += kChunk) {
+    __syncthreads();
+    {
+      const int k = tid & (kChunk - 1);
+      for (int r = tid / kChunk; r < kPanel; r += 256 / kChunk) {
+        const bool in_k = kc + k < w;
+        PI[k * kStride + r] = (in_k && i0 + r < n) ? A[(size_t)(i0 + r) * n + k0 + kc + k] : 0.0;
+        PJ[k * kStride + r] = (in_k && j0 + r < n) ? A[(size_t)(j0 + r) * n + k0 + kc + k] : 0.0;
+      }
+    }
+    __syncthreads();
+    const int kn = min(kChunk, w - kc);
+    for (int k = 0; k < kn; ++k) {
+      const double2 a01 = *reinterpret_cast<const double2*>(&PI[k * kStride + ty * 4]);
+      const double2 a23 = *reinterpret_cast<const double2*>(&PI[k * kStride + ty * 4 + 2]);
+      const double2 b01 = *reinterpret_cast<const double2*>(&PJ[k * kStride + tx * 4]);
+      const double2 b23 = *reinterpret_cast<const double2*>(&PJ[k * kStride + tx * 4 + 2]);
+      const double av[4] = {a01.x, a01.y, a23.x, a23.y};
+      const double bv[4] = {b01.x, b01.y, b23.x, b23.y};
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = acc[a][b] - av[a] * bv[b];
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int row = i0 + ty * 4 + a, col = j0 + tx * 4 + b;
+      if (row < n && col <= row) A[(size_t)row * n + col] = acc[a][b];
+    }
+}
+
+// ---------------------------------------------------------------------------
+// substitutions: one workgroup, column-oriented, panel by panel (b in place)
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void pg_forward_kernel(const double* __restrict__ L, int n, double* __restrict__ b) {
+  __shared__ double Lt[kPanel * (kPanel + 1)];
+  __shared__ double yb[kPanel];
+  const int tid = threadIdx.x;
+  for (int k0 = 0; k0 < n; k0 += kPanel) {
+    const int w = min(kPanel, n - k0);
+    for (int e = tid; e < kPanel * kPanel; e += 1024) {
+      const int i = e >> 6, j = e & 63;
+      Lt[i * (kPanel + 1) + j] = (i < w && j <= i) ? L[(size_t)(k0 + i) * n + k0 + j] : 1.0;
+    }
+    __syncthreads();
+    if (tid < 64) {  // the panel's own triangle: one wavefront, the running value of row `tid` in a register
+      double y = tid < w ? b[k0 + tid] : 0.0;
+      for (int j = 0; j < w; ++j) {
+        if (tid == j) y = y / Lt[j * (kPanel + 1) + j];
+        const double yj = __shfl(y, j);
+        if (tid > j) y = y - Lt[tid * (kPanel + 1) + j] * yj;
+      }
+      yb[tid] = y;
+      if (tid < w) b[k0 + tid] = y;
+    }
+    __syncthreads();
+    for (int i = k0 + w + tid; i < n; i += 1024) {
+      double acc = b[i];
+      const double* row = L + (size_t)i * n + k0;
+      for (int k = 0; k < w; ++k) acc = acc - row[k] * yb[k];
+      b[i] = acc;
+    }
+    __syncthreads();
+  }
+}
+__global__ __launch_bounds__(1024) void pg_backward_kernel(const double* __restrict__ L, int n, double* __restrict__ b) {
+  __shared__ double Lt[kPanel * (kPanel + 1)];
+  __shared__ double xb[kPanel];
+  const int tid = threadIdx.x;
+  for (int k0 = ((n - 1) / kPanel) * kPanel; k0 >= 0; k0 -= kPanel) {
+    const int w = min(kPanel, n - k0);
+    for (int e = tid; e < kPanel * kPanel; e += 1024) {
+      const int i = e >> 6, j = e & 63;
+      Lt[i * (kPanel + 1) + j] = (i < w && j <= i) ? L[(size_t)(k0 + i) * n + k0 + j] : 1.0;
+    }
+    __syncthreads();
+    if (tid < 64) {
+      double y = tid < w ? b[k0 + tid] : 0.0;
+      for (int j = w - 1; j >= 0; --j) {
+        if (tid == j) y = y / Lt[j * (kPanel + 1) + j];
+        const double xj = __shfl(y, j);
+        if (tid < j) y = y - Lt[j * (kPanel + 1) + tid] * xj;
+      }
+      xb[tid] = y;
+      if (tid < w) b[k0 + tid] = y;
+    }
+    __syncthreads();
+    for (int i = tid; i < k0; i += 1024) {
+      double acc = b[i];
+      for (int k = w - 1; k >= 0; --k) acc = acc - L[(size_t)(k0 + k) * n + i] * xb[k];
+      b[i] = acc;
+    }
+    __syncthreads();
+  }
+}
+// step = -z, Hs = H step (per row, ascending columns, from 0.0); out = [step nf][Hs nf]
+__global__ void pg_negate_kernel(const double* __restrict__ z, double* __restrict__ out, int nf) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nf) out[i] = -z[i];
+}
+__global__ __launch_bounds__(64) void pg_matvec_kernel(const double* __restrict__ H, double* __restrict__ out, int nf) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= nf) return;
+  const double* row = H + (size_t)r * nf;
+  double acc = 0.0;
+  for (int c = 0; c < nf; ++c) acc = acc + row[c] * out[c];
+  out[nf + r] = acc;
+}
+
+// queues the factorisation of the n x n matrix A on the context's stream; *d_flag becomes 1 at a bad pivot (ctx->mu held)
+int queue_cholesky(vgx_ctx ctx, double* A, int n, int* d_flag) {
+  VGX_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(int), ctx->stream));
+  const int n_tiles = (n + kPanel - 1) / kPanel;
+  for (int k0 = 0; k0 < n; k0 += kPanel) {
+    const int w = std::min(kPanel, n - k0);
+    hipLaunchKernelGGL(pg_chol_diag_kernel, dim3(1), dim3(256), 0, ctx->stream, A, n, k0, w, d_flag);
+    const int below = n - k0 - w;
+    if (below > 0) {
+      hipLaunchKernelGGL(pg_chol_panel_kernel, dim3((below + kPanel - 1) / kPanel), dim3(64), 0, ctx->stream, A, n, k0, w, d_flag);
+      const int tile0 = k0 / kPanel + 1, m = n_tiles - tile0;
+      hipLaunchKernelGGL(pg_chol_trailing_kernel, dim3(m * (m + 1) / 2), dim3(256), 0, ctx->stream, A, n, k0, w, tile0, d_flag);
+    }
+  }
+  VGX_HIP(ctx, hipGetLastError());
+  return VGX_OK;
+}
+// ... and of the two substitutions on the right-hand side in d_x (in place)
+int queue_substitutions(vgx_ctx ctx, const double* L, int n, double* d_x) {
+  hipLaunchKernelGGL(pg_forward_kernel, dim3(1), dim3(1024), 0, ctx->stream, L, n, d_x);
+  hipLaunchKernelGGL(pg_backward_kernel, dim3(1), dim3(1024), 0, ctx->stream, L, n, d_x);
+  VGX_HIP(ctx, hipGetLastError());
+  return VGX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// relative-pose edges, host, f64 (relative_pose_cost_function_inl.h:8-70 with analytic Jacobians)
+// ---------------------------------------------------------------------------
+double normalize_angle(double a) {
+  const double two_pi = 2.0 * M_PI;
+  return a - two_pi * std::floor((a + M_PI) / two_pi);
+}
+// cost = r.r; with `terms` also g_a g_b aa bb ab (kEdgeTermDoubles); every sum ascending from 0.0
+double edge_terms(const vgx_pose_graph_edge& e, const double* pa, const double* pb, double* terms) {
+  const double c = std::cos(pa[3]), s = std::sin(pa[3]);
+  const double d0 = pb[0] - pa[0], d1 = pb[1] - pa[1], d2 = pb[2] - pa[2];
+  const double err[4] = {c * d0 + s * d1 - e.t_obs[0], -s * d0 + c * d1 - e.t_obs[1], d2 - e.t_obs[2],
+                         normalize_angle(pb[3] - pa[3] - e.yaw_obs)};
+  const double* S = e.sqrt_information;
+  double r[4];
+  double cost = 0.0;
+  for (int i = 0; i < 4; ++i) {
+    double acc = 0.0;
+    for (int k = 0; k < 4; ++k) acc = acc + S[4 * i + k] * err[k];
+    r[i] = acc;
+  }
+  for (int i = 0; i < 4; ++i) cost = cost + r[i] * r[i];
+  if (!terms) return cost;
+  double Ja[16] = {0}, Jb[16] = {0};
+  Jb[0] = c, Jb[1] = s, Jb[4] = -s, Jb[5] = c, Jb[10] = 1.0, Jb[15] = 1.0;
+  for (int i = 0; i < 16; ++i) Ja[i] = -Jb[i];
+  Ja[3] = -s * d0 + c * d1;
+  Ja[7] = -c * d0 - s * d1;
+  double SJa[16], SJb[16];
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 4; ++j) {
+      double x = 0.0, y = 0.0;
+      for (int k = 0; k < 4; ++k) {
+        x = x + S[4 * i + k] * Ja[4 * k + j];
+        y = y + S[4 * i + k] * Jb[4 * k + j];
+      }
+      SJa[4 * i + j] = x;
+      SJb[4 * i + j] = y;
+    }
+  double *ga = terms, *gb = terms + 4, *aa = terms + 8, *bb = terms + 24, *ab = terms + 40;
+  for (int i = 0; i < 4; ++i) {
+    double x = 0.0, y = 0.0;
+    for (int k = 0; k < 4; ++k) {
+      x = x + SJa[4 * k + i] * r[k];
+      y = y + SJb[4 * k + i] * r[k];
+    }
+    ga[i] = x;
+    gb[i] = y;
+    for (int j = 0; j < 4; ++j) {
+      double p = 0.0, q = 0.0, m = 0.0;
+      for (int k = 0; k < 4; ++k) {
+        p = p + SJa[4 * k + i] * SJa[4 * k + j];
+        q = q + SJb[4 * k + i] * SJb[4 * k + j];
+        m = m + SJa[4 * k + i] * SJb[4 * k + j];
+      }
+      aa[4 * i + j] = p;
+      bb[4 * i + j] = q;
+      ab[4 * i + j] = m;
+    }
+  }
+  return cost;
+}
+
+double seconds_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
+}  // namespace
+
+struct vgx_pose_graph_s {
+  vgx_ctx ctx = nullptr;
+  int32_t n_nodes = 0;
+  std::vector<int32_t> pos;  // node -> index among the free nodes (ascending), or -1: constant
+  std::vector<int32_t> free_nodes;
+  int nf = 0;                // 4 x free nodes
+  vgx_reg_batch batch = nullptr;
+  std::vector<vgx_pose_graph_edge> edges;
+  std::mutex mu;             // one solve (or setter) at a time
+  // the index lists of the assembly, rebuilt when the constraints changed or registration is switched off / on
+  bool lists_made = false, lists_with_reg = false;
+  int n_blocks = 0;
+  DeviceArray<BlockRecord> d_blocks;
+  DeviceArray<int32_t> d_block_items, d_grad_first, d_grad_items;
+  // the system
+  DeviceArray<double> d_H, d_A, d_g, d_x, d_out, d_fused, d_edge, d_cost;
+  DeviceArray<int> d_flag;
+  PinnedBuffer h_io;         // doubles: [step nf][H step nf][g nf][edge terms 56 E][costs n] + the flag
+  bool system_valid = false;
+  std::vector<vgx_pose_graph_iteration> history;
+};
+
+namespace {
+
+void release_batch(vgx_pose_graph pg) {
+  vgx_reg_batch b = pg->batch;
+  if (!b) return;
+  pg->batch = nullptr;
+  bool destroy = false;
+  {
+    std::lock_guard<std::mutex> lt(lifetime_mu());
+    destroy = --b->users == 0 && b->destroy_requested;
+  }
+  if (destroy) (void)vgx_reg_batch_destroy(b);
+}
+
+// Index lists in the contract's order.  with_reg: the fused buffer's blocks take part.
+int make_lists(vgx_pose_graph pg, bool with_reg) {
+  vgx_ctx ctx = pg->ctx;
+  const int n = pg->n_nodes, nfn = (int)pg->free_nodes.size();
+  const vgx_reg_batch b = with_reg ? pg->batch : nullptr;
+  const int m = b ? b->n : 0;
+  if (vgx_reg_fused_size(n, m) >= (int64_t)1 << 29 || (int64_t)pg->edges.size() * kEdgeTermDoubles >= (int64_t)1 << 29)
+    return set_error(ctx, VGX_ERR_UNSUPPORTED, "vgx_pose_graph_optimize: the constraint list is too long for the 32-bit index lists");
+  std::map<std::pair<int32_t, int32_t>, std::vector<int32_t>> blocks;
+  std::vector<std::vector<int32_t>> grad((size_t)nfn);
+  auto add = [&](int node_r, int node_c, int64_t offset, int source, int transpose) {
+    const int32_t r = pg->pos[(size_t)node_r], c = pg->pos[(size_t)node_c];
+    if (r < 0 || c < 0) return;
+    blocks[{r, c}].push_back((int32_t)(offset << 2 | source << 1 | transpose));
+  };
+  if (b) {
+    for (int i = 0; i < n; ++i) {  // 1. the fused buffer's diagonal blocks (and its gradient)
+      add(i, i, 1 + 4 * (int64_t)n + 16 * (int64_t)i, 0, 0);
+      if (pg->pos[(size_t)i] >= 0) grad[(size_t)pg->pos[(size_t)i]].push_back((int32_t)((1 + 4 * (int64_t)i) << 1));
+    }
+    for (int c = 0; c < m; ++c) {  // 2. the off-diagonal blocks in constraint-list order
+      const int a = b->node_pair[2 * (size_t)c], bb = b->node_pair[2 * (size_t)c + 1];
+      const int64_t off = 1 + 20 * (int64_t)n + 16 * (int64_t)c;
+      add(a, bb, off, 0, 0);
+      add(bb, a, off, 0, 1);
+    }
+  }
+  for (size_t e = 0; e < pg->edges.size(); ++e) {  // 3. the edges in list order: aa, bb, ab, ab^T
+    const int a = pg->edges[e].a, bb = pg->edges[e].b;
+    const int64_t base = (int64_t)e * kEdgeTermDoubles;
+    add(a, a, base + 8, 1, 0);
+    add(bb, bb, base + 24, 1, 0);
+    add(a, bb, base + 40, 1, 0);
+    add(bb, a, base + 40, 1, 1);
+    if (pg->pos[(size_t)a] >= 0) grad[(size_t)pg->pos[(size_t)a]].push_back((int32_t)(base << 1 | 1));
+    if (pg->pos[(size_t)bb] >= 0) grad[(size_t)pg->pos[(size_t)bb]].push_back((int32_t)((base + 4) << 1 | 1));
+  }
+  std::vector<BlockRecord> records;
+  std::vector<int32_t> items, gfirst((size_t)nfn + 1, 0), gitems;
+  for (const auto& kv : blocks) {
+    records.push_back({kv.first.first, kv.first.second, (int32_t)items.size(), (int32_t)kv.second.size()});
+    items.insert(items.end(), kv.second.begin(), kv.second.end());
+  }
+  for (int i = 0; i < nfn; ++i) {
+    gitems.insert(gitems.end(), grad[(size_t)i].begin(), grad[(size_t)i].end());
+    gfirst[(size_t)i + 1] = (int32_t)gitems.size();
+  }
+  if (items.empty()) items.push_back(0);
+  if (gitems.empty()) gitems.push_back(0);
+  if (records.empty()) records.push_back({0, 0, 0, 0});
+  pg->n_blocks = (int)blocks.size();
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  VGX_HIP(ctx, hipSetDevice(ctx->device));
+  VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  int rc = upload_new(ctx, pg->d_blocks, records.data(), records.size() * sizeof(BlockRecord));
+  if (rc == VGX_OK) rc = upload_new(ctx, pg->d_block_items, items.data(), items.size() * sizeof(int32_t));
+  if (rc == VGX_OK) rc = upload_new(ctx, pg->d_grad_first, gfirst.data(), gfirst.size() * sizeof(int32_t));
+  if (rc == VGX_OK) rc = upload_new(ctx, pg->d_grad_items, gitems.data(), gitems.size() * sizeof(int32_t));
+  if (rc != VGX_OK) return rc;
+  const size_t nf = (size_t)pg->nf, n_fused = (size_t)vgx_reg_fused_size(n, m), E = pg->edges.size();
+  hipError_t e = hipSuccess;
+  for (DeviceBuffer* buf : {(DeviceBuffer*)&pg->d_H, (DeviceBuffer*)&pg->d_A})
+    if (e == hipSuccess) e = buf->reserve(nf * nf * sizeof(double));
+  if (e == hipSuccess) e = pg->d_g.reserve(nf * sizeof(double));
+  if (e == hipSuccess) e = pg->d_x.reserve(nf * sizeof(double));
+  if (e == hipSuccess) e = pg->d_out.reserve(2 * nf * sizeof(double));
+  if (e == hipSuccess) e = pg->d_fused.reserve(n_fused * sizeof(double));
+  if (e == hipSuccess) e = pg->d_edge.reserve(std::max<size_t>(1, E) * kEdgeTermDoubles * sizeof(double));
+  if (e == hipSuccess) e = pg->d_cost.reserve((size_t)std::max(1, m) * sizeof(double));
+  if (e == hipSuccess) e = pg->d_flag.reserve(sizeof(int));
+  if (e != hipSuccess) return alloc_error(ctx, e, "vgx_pose_graph_optimize: allocating the dense system");
+  e = pg->h_io.reserve((3 * nf + E * kEdgeTermDoubles + (size_t)m + 2) * sizeof(double));
+  if (e != hipSuccess) return alloc_error(ctx, e, "vgx_pose_graph_optimize: allocating the pinned staging");
+  // blocks no constraint touches stay zero: the lists never write them
+  VGX_HIP(ctx, hipMemsetAsync(pg->d_H.p, 0, nf * nf * sizeof(double), ctx->stream));
+  VGX_HIP(ctx, hipMemsetAsync(pg->d_fused.p, 0, n_fused * sizeof(double), ctx->stream));
+  pg->lists_made = true;
+  pg->lists_with_reg = with_reg;
+  pg->system_valid = false;
+  return VGX_OK;
+}
+
+struct Solve {
+  vgx_pose_graph pg;
+  bool with_reg;
+  double reg_seconds = 0, la_seconds = 0;
+  int full_evaluations = 0, cost_evaluations = 0;
+  double* h_step() const { return pg->h_io.as<double>(); }
+  double* h_Hs() const { return h_step() + pg->nf; }
+  double* h_g() const { return h_step() + 2 * (size_t)pg->nf; }
+  double* h_edge() const { return h_step() + 3 * (size_t)pg->nf; }
+  double* h_costs() const { return h_edge() + pg->edges.size() * kEdgeTermDoubles; }
+  int* h_flag() const { return reinterpret_cast<int*>(h_costs() + (with_reg ? pg->batch->n : 0) + 1); }
+
+  double edge_cost(const double* poses, bool terms) const {
+    double cost = 0.0;
+    for (size_t e = 0; e < pg->edges.size(); ++e) {
+      const vgx_pose_graph_edge& E = pg->edges[e];
+      cost = cost + edge_terms(E, poses + 4 * (size_t)E.a, poses + 4 * (size_t)E.b, terms ? h_edge() + e * kEdgeTermDoubles : nullptr);
+    }
+    return cost;
+  }
+  // residuals and Jacobians: H and g on the device, g and the cost on the host
+  int evaluate_full(const double* poses, double* cost) {
+    vgx_ctx ctx = pg->ctx;
+    const vgx_reg_batch b = with_reg ? pg->batch : nullptr;
+    const int m = b ? b->n : 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (m > 0) {
+      int rc = vgx_reg_batch_evaluate_normal(b, poses, pg->n_nodes, nullptr, nullptr, nullptr);
+      if (rc < 0) return rc;
+      rc = vgx_reg_batch_assemble(b, nullptr, pg->n_nodes, pg->d_fused.p, 1);
+      if (rc < 0) return rc;
+    }
+    const double ecost = edge_cost(poses, true);
+    {
+      std::lock_guard<std::mutex> lk(ctx->mu);
+      VGX_HIP(ctx, hipSetDevice(ctx->device));
+      const size_t E = pg->edges.size();
+      if (m > 0) {
+        hipLaunchKernelGGL(pg_gather_cost_kernel, dim3((m + 255) / 256), dim3(256), 0, ctx->stream, b->d_normal.as<double>(), m,
+                           pg->d_cost.get());
+        VGX_HIP(ctx, hipMemcpyAsync(h_costs(), pg->d_cost.p, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+      }
+      if (E > 0)
+        VGX_HIP(ctx, hipMemcpyAsync(pg->d_edge.p, h_edge(), E * kEdgeTermDoubles * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+      if (pg->n_blocks > 0)
+        hipLaunchKernelGGL(pg_assemble_blocks_kernel, dim3((pg->n_blocks * 16 + 255) / 256), dim3(256), 0, ctx->stream, pg->d_blocks.get(),
+                           pg->n_blocks, pg->d_block_items.get(), pg->d_fused.get(), pg->d_edge.get(), pg->d_H.get(), pg->nf);
+      hipLaunchKernelGGL(pg_assemble_gradient_kernel, dim3((pg->nf + 255) / 256), dim3(256), 0, ctx->stream, pg->d_grad_first.get(),
+                         pg->d_grad_items.get(), pg->d_fused.get(), pg->d_edge.get(), pg->d_g.get(), pg->nf / 4);
+      VGX_HIP(ctx, hipGetLastError());
+      VGX_HIP(ctx, hipMemcpyAsync(h_g(), pg->d_g.p, (size_t)pg->nf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+      VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    double reg = 0.0;
+    for (int c = 0; c < m; ++c) reg = reg + h_costs()[c];
+    *cost = 0.5 * (reg + ecost);
+    reg_seconds += seconds_since(t0);
+    ++full_evaluations;
+    pg->system_valid = true;
+    return VGX_OK;
+  }
+  int evaluate_cost(const double* poses, double* cost) {
+    const vgx_reg_batch b = with_reg ? pg->batch : nullptr;
+    const int m = b ? b->n : 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    double reg = 0.0;
+    if (m > 0) {
+      const int rc = vgx_reg_batch_evaluate_cost(b, poses, pg->n_nodes, nullptr, h_costs(), nullptr);
+      if (rc < 0) return rc;
+      for (int c = 0; c < m; ++c) reg = reg + h_costs()[c];
+    }
+    *cost = 0.5 * (reg + edge_cost(poses, false));
+    reg_seconds += seconds_since(t0);
+    ++cost_evaluations;
+    return VGX_OK;
+  }
+  // step and H step on the host; *failed: the factorisation met a bad pivot
+  int solve_step(double radius, bool* failed) {
+    vgx_ctx ctx = pg->ctx;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int nf = pg->nf;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    VGX_HIP(ctx, hipSetDevice(ctx->device));
+    VGX_HIP(ctx, hipMemcpyAsync(pg->d_A.p, pg->d_H.p, (size_t)nf * nf * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    hipLaunchKernelGGL(pg_damp_kernel, dim3((nf + 255) / 256), dim3(256), 0, ctx->stream, pg->d_H.get(), pg->d_A.get(), nf, radius);
+    int rc = queue_cholesky(ctx, pg->d_A.get(), nf, pg->d_flag.get());
+    if (rc != VGX_OK) return rc;
+    VGX_HIP(ctx, hipMemcpyAsync(pg->d_x.p, pg->d_g.p, (size_t)nf * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    rc = queue_substitutions(ctx, pg->d_A.get(), nf, pg->d_x.get());
+    if (rc != VGX_OK) return rc;
+    hipLaunchKernelGGL(pg_negate_kernel, dim3((nf + 255) / 256), dim3(256), 0, ctx->stream, pg->d_x.get(), pg->d_out.get(), nf);
+    hipLaunchKernelGGL(pg_matvec_kernel, dim3((nf + 63) / 64), dim3(64), 0, ctx->stream, pg->d_H.get(), pg->d_out.get(), nf);
+    VGX_HIP(ctx, hipGetLastError());
+    VGX_HIP(ctx, hipMemcpyAsync(h_step(), pg->d_out.p, 2 * (size_t)nf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    VGX_HIP(ctx, hipMemcpyAsync(h_flag(), pg->d_flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *failed = *h_flag() != 0;
+    la_seconds += seconds_since(t0);
+    return VGX_OK;
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+void vgx_pose_graph_options_default(vgx_pose_graph_options* o) {
+  if (!o) return;
+  o->parameter_tolerance = 3e-3;
+  o->function_tolerance = 1e-6;
+  o->gradient_tolerance = 1e-10;
+  o->max_solver_time_in_seconds = 4.0;
+  o->initial_trust_region_radius = 1e4;
+  o->max_num_iterations = 50;
+  o->exclude_registration_constraints = 0;
+}
+
+int vgx_pose_graph_create(vgx_ctx ctx, int32_t n_nodes, const int32_t* constant, vgx_pose_graph* out) {
+  if (!ctx || !out) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_create: NULL context or output");
+  *out = nullptr;
+  if (n_nodes <= 0) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_create: an empty graph (n_nodes <= 0)");
+  vgx_pose_graph pg = new (std::nothrow) vgx_pose_graph_s;
+  if (!pg) return set_error(ctx, VGX_ERR_NOMEM, "vgx_pose_graph_create: out of host memory");
+  pg->ctx = ctx;
+  pg->n_nodes = n_nodes;
+  pg->pos.assign((size_t)n_nodes, -1);
+  for (int i = 0; i < n_nodes; ++i)
+    if (constant ? constant[i] == 0 : i != 0) {
+      pg->pos[(size_t)i] = (int32_t)pg->free_nodes.size();
+      pg->free_nodes.push_back(i);
+    }
+  if ((int)pg->free_nodes.size() > kMaxFreeNodes) {
+    const size_t n_free = pg->free_nodes.size();
+    delete pg;
+    return set_error(ctx, VGX_ERR_UNSUPPORTED, "vgx_pose_graph_create: " + std::to_string(n_free) + " free nodes; the dense solve takes " +
+                                                   std::to_string(kMaxFreeNodes) + " at the most");
+  }
+  pg->nf = 4 * (int)pg->free_nodes.size();
+  *out = pg;
+  return VGX_OK;
+}
+
+int vgx_pose_graph_destroy(vgx_pose_graph pg) {
+  if (!pg) return VGX_ERR_INVALID;
+  {
+    std::lock_guard<std::mutex> lk(pg->ctx->mu);
+    (void)hipSetDevice(pg->ctx->device);
+    (void)hipStreamSynchronize(pg->ctx->stream);
+  }
+  release_batch(pg);
+  delete pg;
+  return VGX_OK;
+}
+
+int vgx_pose_graph_set_registration(vgx_pose_graph pg, vgx_reg_batch batch) {
+  if (!pg) return VGX_ERR_INVALID;
+  vgx_ctx ctx = pg->ctx;
+  std::lock_guard<std::mutex> lk(pg->mu);
+  if (batch) {
+    if (batch->ctx != ctx) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_set_registration: the batch belongs to another context");
+    if (batch->n_global != batch->n)
+      return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_set_registration: a sharded batch (n_global != n); the solve needs the whole list");
+    for (int32_t v : batch->node_pair)
+      if (v < 0 || v >= pg->n_nodes)
+        return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_set_registration: the batch names a node out of range");
+    std::lock_guard<std::mutex> lt(lifetime_mu());
+    if (batch->destroy_requested) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_set_registration: the batch was destroyed");
+    ++batch->users;
+  }
+  release_batch(pg);
+  pg->batch = batch;
+  pg->lists_made = false;
+  return VGX_OK;
+}
+
+int vgx_pose_graph_set_edges(vgx_pose_graph pg, int32_t n_edges, const vgx_pose_graph_edge* edges) {
+  if (!pg) return VGX_ERR_INVALID;
+  vgx_ctx ctx = pg->ctx;
+  if (n_edges < 0 || (n_edges > 0 && !edges)) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_set_edges: n_edges < 0 or NULL edges");
+  for (int e = 0; e < n_edges; ++e) {
+    if (edges[e].a < 0 || edges[e].a >= pg->n_nodes || edges[e].b < 0 || edges[e].b >= pg->n_nodes)
+      return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_set_edges: edge " + std::to_string(e) + " names a node out of range");
+    if (edges[e].a == edges[e].b)
+      return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_set_edges: edge " + std::to_string(e) + " joins a node to itself");
+  }
+  std::lock_guard<std::mutex> lk(pg->mu);
+  pg->edges.assign(edges, edges + n_edges);
+  pg->lists_made = false;
+  return VGX_OK;
+}
+
+int vgx_pose_graph_optimize(vgx_pose_graph pg, const vgx_pose_graph_options* options, double* poses, vgx_pose_graph_summary* summary) {
+  if (!pg) return VGX_ERR_INVALID;
+  vgx_ctx ctx = pg->ctx;
+  if (!poses) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_optimize: NULL poses");
+  std::lock_guard<std::mutex> lk(pg->mu);
+  vgx_pose_graph_options opt;
+  vgx_pose_graph_options_default(&opt);
+  if (options) opt = *options;
+  vgx_pose_graph_summary S;
+  std::memset(&S, 0, sizeof(S));
+  S.num_free_nodes = (int32_t)pg->free_nodes.size();
+  pg->history.clear();
+  const auto t0 = std::chrono::steady_clock::now();
+  for (size_t i = 0; i < 4 * (size_t)pg->n_nodes; ++i)
+    if (!std::isfinite(poses[i])) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_optimize: a pose is not finite");
+  if (!(opt.initial_trust_region_radius > 0.0))
+    return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_optimize: initial_trust_region_radius must be positive");
+  if (pg->batch) {
+    std::lock_guard<std::mutex> lt(lifetime_mu());
+    if (pg->batch->destroy_requested)
+      return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_optimize: the registration batch was destroyed");
+  }
+  const bool with_reg = pg->batch && pg->batch->n > 0 && !opt.exclude_registration_constraints;
+  if (!with_reg && pg->edges.empty())
+    return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_optimize: a graph without constraints (no registration batch in use, no edges)");
+  if (pg->nf == 0) {  // nothing to optimise
+    S.termination_type = VGX_CONVERGENCE;
+    S.termination_reason = VGX_TERMINATION_NO_FREE_NODES;
+    S.total_seconds = seconds_since(t0);
+    if (summary) *summary = S;
+    return VGX_OK;
+  }
+  if (!pg->lists_made || pg->lists_with_reg != with_reg) {
+    const int rc = make_lists(pg, with_reg);
+    if (rc != VGX_OK) return rc;
+  }
+  Solve sv{pg, with_reg};
+  const int n = pg->n_nodes, nf = pg->nf;
+  std::vector<double> x(poses, poses + 4 * (size_t)n), cand(4 * (size_t)n), g((size_t)nf);
+  double cost = 0.0;
+  int rc = sv.evaluate_full(x.data(), &cost);
+  if (rc < 0) return rc;
+  std::copy(sv.h_g(), sv.h_g() + nf, g.begin());
+  S.initial_cost = cost;
+  double radius = opt.initial_trust_region_radius, decrease = 2.0;
+  int it = 0, reason = VGX_TERMINATION_MAX_ITERATIONS;
+  while (it < opt.max_num_iterations) {
+    ++it;
+    pg->history.push_back(vgx_pose_graph_iteration{cost, 0.0, 0.0, radius, 0.0, 0, 0});
+    vgx_pose_graph_iteration& rec = pg->history.back();
+    double gmax = 0.0;
+    for (int i = 0; i < nf; ++i) gmax = std::max(gmax, std::fabs(g[(size_t)i]));
+    if (gmax <= opt.gradient_tolerance) {
+      reason = VGX_TERMINATION_GRADIENT_TOLERANCE;
+      break;
+    }
+    bool failed = false;
+    rc = sv.solve_step(radius, &failed);
+    if (rc < 0) return rc;
+    if (failed) {
+      rec.factorization_failed = 1;
+      ++S.num_factorization_failures;
+      radius /= decrease;
+      decrease *= 2.0;
+      continue;
+    }
+    const double* step = sv.h_step();
+    const double* Hs = sv.h_Hs();
+    double s2 = 0.0, x2 = 0.0;
+    for (int i = 0; i < nf; ++i) s2 = s2 + step[i] * step[i];
+    for (int i = 0; i < nf; ++i) {
+      const double v = x[4 * (size_t)pg->free_nodes[(size_t)(i >> 2)] + (i & 3)];
+      x2 = x2 + v * v;
+    }
+    const double step_norm = std::sqrt(s2);
+    rec.step_norm = step_norm;
+    if (step_norm <= opt.parameter_tolerance * (std::sqrt(x2) + opt.parameter_tolerance)) {
+      reason = VGX_TERMINATION_PARAMETER_TOLERANCE;
+      break;
+    }
+    cand = x;
+    for (int i = 0; i < nf; ++i) {
+      double& v = cand[4 * (size_t)pg->free_nodes[(size_t)(i >> 2)] + (i & 3)];
+      v = v + step[i];
+    }
+    for (int k = 0; k < n; ++k) cand[4 * (size_t)k + 3] = normalize_angle(cand[4 * (size_t)k + 3]);
+    double trial = 0.0;
+    rc = sv.evaluate_cost(cand.data(), &trial);
+    if (rc < 0) return rc;
+    double gs = 0.0, sHs = 0.0;
+    for (int i = 0; i < nf; ++i) gs = gs + g[(size_t)i] * step[i];
+    for (int i = 0; i < nf; ++i) sHs = sHs + step[i] * Hs[i];
+    const double model_decrease = -(gs + 0.5 * sHs);
+    const double rho = model_decrease > 0.0 ? (cost - trial) / model_decrease : -1.0;
+    rec.trial_cost = trial;
+    rec.gain_ratio = rho;
+    if (rho > 1e-3) {
+      rec.accepted = 1;
+      ++S.num_successful_steps;
+      double new_cost = 0.0;
+      rc = sv.evaluate_full(cand.data(), &new_cost);
+      if (rc < 0) return rc;
+      const double rel = std::fabs(cost - new_cost) / std::max(cost, 1e-300);
+      x = cand;
+      cost = new_cost;
+      std::copy(sv.h_g(), sv.h_g() + nf, g.begin());
+      const double q = 2.0 * rho - 1.0;
+      radius = std::min(radius / std::max(1.0 / 3.0, 1.0 - q * q * q), 1e16);
+      decrease = 2.0;
+      if (rel <= opt.function_tolerance) {
+        reason = VGX_TERMINATION_FUNCTION_TOLERANCE;
+        break;
+      }
+    } else {
+      radius /= decrease;
+      decrease *= 2.0;
+    }
+    if (seconds_since(t0) > opt.max_solver_time_in_seconds) {
+      reason = VGX_TERMINATION_MAX_SOLVER_TIME;
+      break;
+    }
+  }
+  std::copy(x.begin(), x.end(), poses);
+  S.termination_reason = reason;
+  S.termination_type = reason <= VGX_TERMINATION_GRADIENT_TOLERANCE ? VGX_CONVERGENCE : VGX_NO_CONVERGENCE;
+  S.num_iterations = it;
+  S.num_full_evaluations = sv.full_evaluations;
+  S.num_cost_evaluations = sv.cost_evaluations;
+  S.final_cost = cost;
+  S.registration_seconds = sv.reg_seconds;
+  S.linear_algebra_seconds = sv.la_seconds;
+  S.total_seconds = seconds_since(t0);
+  if (summary) *summary = S;
+  return VGX_OK;
+}
+
+int vgx_pose_graph_history(vgx_pose_graph pg, int32_t capacity, vgx_pose_graph_iteration* iterations, int32_t* n_iterations) {
+  if (!pg) return VGX_ERR_INVALID;
+  if (capacity < 0 || (capacity > 0 && !iterations))
+    return set_error(pg->ctx, VGX_ERR_INVALID, "vgx_pose_graph_history: capacity < 0 or NULL iterations");
+  std::lock_guard<std::mutex> lk(pg->mu);
+  if (n_iterations) *n_iterations = (int32_t)pg->history.size();
+  const size_t k = std::min(pg->history.size(), (size_t)capacity);
+  if (k) std::memcpy(iterations, pg->history.data(), k * sizeof(vgx_pose_graph_iteration));
+  return VGX_OK;
+}
+
+int vgx_pose_graph_download_system(vgx_pose_graph pg, int32_t* n_free_variables, double* H, double* g) {
+  if (!pg) return VGX_ERR_INVALID;
+  vgx_ctx ctx = pg->ctx;
+  std::lock_guard<std::mutex> lk(pg->mu);
+  if (n_free_variables) *n_free_variables = pg->nf;
+  if (!H && !g) return VGX_OK;
+  if (!pg->system_valid) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_download_system: no solve has evaluated the system yet");
+  const size_t nf = (size_t)pg->nf;
+  std::lock_guard<std::mutex> lc(ctx->mu);
+  VGX_HIP(ctx, hipSetDevice(ctx->device));
+  VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (H) VGX_HIP(ctx, hipMemcpy(H, pg->d_H.p, nf * nf * sizeof(double), hipMemcpyDeviceToHost));
+  if (g) VGX_HIP(ctx, hipMemcpy(g, pg->d_g.p, nf * sizeof(double), hipMemcpyDeviceToHost));
+  return VGX_OK;
+}
+
+int vgx_dense_spd_solve(vgx_ctx ctx, int32_t n, const double* A, const double* b, double* x, double* L) {
+  if (!ctx) return VGX_ERR_INVALID;
+  if (n < 1 || n > kMaxDenseN)
+    return set_error(ctx, n < 1 ? VGX_ERR_INVALID : VGX_ERR_UNSUPPORTED, "vgx_dense_spd_solve: n must be in [1, " + std::to_string(kMaxDenseN) + "]");
+  if (!A || !b || !x) return set_error(ctx, VGX_ERR_INVALID, "vgx_dense_spd_solve: NULL A, b or x");
+  const size_t N = (size_t)n;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  VGX_HIP(ctx, hipSetDevice(ctx->device));
+  DeviceArray<double> d_A, d_x;
+  DeviceArray<int> d_flag;
+  hipError_t e = d_A.alloc_n(N * N);
+  if (e == hipSuccess) e = d_x.alloc_n(N);
+  if (e == hipSuccess) e = d_flag.alloc_n(1);
+  if (e != hipSuccess) return alloc_error(ctx, e, "vgx_dense_spd_solve: allocating the matrix");
+  VGX_HIP(ctx, hipMemcpyAsync(d_A.p, A, N * N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  VGX_HIP(ctx, hipMemcpyAsync(d_x.p, b, N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  int rc = queue_cholesky(ctx, d_A.get(), n, d_flag.get());
+  if (rc == VGX_OK) rc = queue_substitutions(ctx, d_A.get(), n, d_x.get());
+  if (rc != VGX_OK) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+  }
+  int flag = 0;
+  VGX_HIP(ctx, hipMemcpyAsync(&flag, d_flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  VGX_HIP(ctx, hipMemcpyAsync(x, d_x.p, N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (L) VGX_HIP(ctx, hipMemcpyAsync(L, d_A.p, N * N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (L)
+    for (size_t i = 0; i < N; ++i)
+      for (size_t j = i + 1; j < N; ++j) L[i * N + j] = 0.0;
+  if (flag) return set_error(ctx, VGX_ERR_NOT_POSITIVE_DEFINITE, "vgx_dense_spd_solve: the matrix is not positive definite (a pivot is not positive or not finite)");
+  return VGX_OK;
+}
+
+}  // extern "C"

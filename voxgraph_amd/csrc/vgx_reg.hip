@@ -2413,6 +2413,13 @@ int vgx_reg_batch_create(vgx_ctx ctx, int32_t n, const vgx_reg* regs, const int3
 
 int vgx_reg_batch_destroy(vgx_reg_batch b) {
   if (!b) return VGX_ERR_INVALID;
+  {
+    std::lock_guard<std::mutex> lt(lifetime_mu());
+    if (b->users > 0) {  // a pose graph still lists it: carried out when the last one lets go (vgx_pose_graph.hip)
+      b->destroy_requested = true;
+      return VGX_OK;
+    }
+  }
   (void)hipSetDevice(b->ctx->device);
   (void)hipStreamSynchronize(b->ctx->stream);
   std::vector<vgx_reg> orphans;  // cost functions destroyed by their owner while this batch listed them
