@@ -1549,7 +1549,8 @@ VGX_API int vgx_map_file_write(const char* path, int32_t format, double voxel_si
  * vgx_pose_graph_set_edges: replaces the list of relative-pose edges (allowed between solves): residual =
  * sqrt_information * [R(yaw_a)^T (t_b - t_a) - t_obs, normalize(yaw_b - yaw_a - yaw_obs)], sqrt_information a full
  * row-major 4x4 (the reference multiplies by a matrix, :60).  An absolute constraint is an edge from a constant
- * reference-frame node. */
+ * reference-frame node.  Refused with VGX_ERR_INVALID, the list left as it was: n_edges < 0 or NULL edges, an edge that
+ * names a node out of range or joins a node to itself, an edge whose t_obs, yaw_obs or sqrt_information is not finite. */
 typedef struct vgx_pose_graph_s* vgx_pose_graph;
 typedef struct vgx_pose_graph_edge {
   int32_t a, b;

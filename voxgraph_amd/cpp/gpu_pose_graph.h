@@ -155,6 +155,8 @@ class GpuPoseGraph {
     return true;
   }
   // the handles follow the lists: rebuilt when nodes or constraints changed since the last solve
+  // (vgx_pose_graph_set_edges refuses an edge whose t_obs, yaw_obs or sqrt_information is not finite: optimize() then
+  // returns VGX_ERR_INVALID and last_error() says which edge)
   int Build() {
     if (!dirty_ && graph_) return VGX_OK;
     Release();

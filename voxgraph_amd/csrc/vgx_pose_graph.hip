@@ -665,6 +665,11 @@ int vgx_pose_graph_set_edges(vgx_pose_graph pg, int32_t n_edges, const vgx_pose_
       return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_set_edges: edge " + std::to_string(e) + " names a node out of range");
     if (edges[e].a == edges[e].b)
       return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_set_edges: edge " + std::to_string(e) + " joins a node to itself");
+    bool finite = std::isfinite(edges[e].yaw_obs);
+    for (double v : edges[e].t_obs) finite = finite && std::isfinite(v);
+    for (double v : edges[e].sqrt_information) finite = finite && std::isfinite(v);
+    if (!finite)
+      return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_set_edges: edge " + std::to_string(e) + " has a t_obs, yaw_obs or sqrt_information that is not finite");
   }
   std::lock_guard<std::mutex> lk(pg->mu);
   pg->edges.assign(edges, edges + n_edges);
@@ -722,8 +727,11 @@ int vgx_pose_graph_optimize(vgx_pose_graph pg, const vgx_pose_graph_options* opt
     ++it;
     pg->history.push_back(vgx_pose_graph_iteration{cost, 0.0, 0.0, radius, 0.0, 0, 0});
     vgx_pose_graph_iteration& rec = pg->history.back();
-    double gmax = 0.0;
-    for (int i = 0; i < nf; ++i) gmax = std::max(gmax, std::fabs(g[(size_t)i]));
+    double gmax = 0.0;  // a NaN stays: max |g| of a NaN gradient is a NaN, which is not <= the tolerance
+    for (int i = 0; i < nf; ++i) {
+      const double a = std::fabs(g[(size_t)i]);
+      if (a > gmax || std::isnan(a)) gmax = a;
+    }
     if (gmax <= opt.gradient_tolerance) {
       reason = VGX_TERMINATION_GRADIENT_TOLERANCE;
       break;
