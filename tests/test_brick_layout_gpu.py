@@ -104,7 +104,9 @@ def test_vps8_grids_on_both_layouts(capi):
     sdf = synth.sphere_ground_sdf((1.6, 1.6, 1.2), 1.0, 0.35)
     sm = synth.make_submap(sdf, 0.1, 8, (0, 0, 0), (4, 4, 3), trunc=0.3, esdf_max=1.0, drop_empty_blocks=True)
     poses = np.array([[0.0, 0.0, 0.0, 0.0], [0.13, -0.07, 0.04, 0.05]])
-    got = []
+    layer = H.oracle_layer(sm)
+    xyz, dist, w = H.oracle_points(sm)
+    got, part = [], []
     for layout in (capi.BRICKS_APRON, capi.BRICKS_QUAD):
         ctx = capi.Context(0)
         ctx.set_brick_layout(layout)
@@ -116,15 +118,89 @@ def test_vps8_grids_on_both_layouts(capi):
         batch = capi.RegistrationBatch(ctx, [cf], [(0, 1)])
         _, normal = batch.evaluate_normal(poses)
         got.append((r, jo, je, normal.copy()))
-        for o in (batch, cf, g):
+        for o in (batch, cf):
             o.destroy()
+        part.append(_vps8_partial_tile_entry_points(capi, ctx, g, (xyz, dist, w), poses))
+        g.destroy()
         ctx.close()
-    layer = H.oracle_layer(sm)
-    xyz, dist, w = H.oracle_points(sm)
     ok, r0, jo0, je0 = orc.reg_evaluate(layer, xyz, dist, w, poses[0], poses[1])
     assert ok and np.array_equal(got[0][0], r0) and np.array_equal(got[0][1], jo0) and np.array_equal(got[0][2], je0)
     for x, y in zip(got[0], got[1]):
         assert np.array_equal(x, y)
+    # the partial-tile rows are the oracle's on the cropped arrays, and every entry point's output is the same on both layouts
+    m = len(part[0]["rows"][0])
+    ok, r0, jo0, je0 = orc.reg_evaluate(layer, xyz[:m], dist[:m], w[:m], poses[0], poses[1])
+    assert ok and all(np.array_equal(x, y) for x, y in zip(part[0]["rows"], (r0, jo0, je0)))
+    assert int((np.abs(jo0).sum(1) > 0).sum()) > 1000
+    assert part[0].keys() == part[1].keys()
+    for key in part[0]:
+        for x, y in zip(part[0][key], part[1][key]):
+            assert np.array_equal(x, y, equal_nan=True), key
+
+
+def _vps8_partial_tile_entry_points(capi, ctx, g, points, poses):
+    """The vps-8 arms of the batched entry points on a point set that ends in a partial tile and a partial chunk: the
+    identities the suite asserts between them at vps 16 (tests/test_reg_gpu.py), all bit for bit.  -> what each wrote"""
+    import torch
+    xyz, dist, w = points
+    n = 11781                                             # 11 tiles of 1024 + 517 points, 23 chunks of 512 + 5 points
+    assert len(w) >= n and n % 1024 != 0 and n % 512 != 0
+    g.set_points(capi.POINTS_VOXELS, xyz[:n], dist[:n], w[:n], capi.POINTS_KEEP_ORDER)
+    cf = capi.RegistrationCostFunction(ctx, g, g, capi.default_config(registration_point_type=capi.POINTS_VOXELS))
+    assert cf.num_residuals() == n
+    r, jo, je = np.zeros(n), np.zeros((n, 4)), np.zeros((n, 4))
+    assert cf.Evaluate([poses[0], poses[1]], r, [jo, je])                    # drop-in f64 rows
+    batch = capi.RegistrationBatch(ctx, [cf], [(0, 1)])
+    assert batch.num_residuals() == n
+
+    def nan_rows(dtype):
+        return [torch.full(shape, float("nan"), dtype=dtype, device="cuda:0") for shape in ((n,), (n, 4), (n, 4))]
+
+    def host(bufs):
+        ctx.synchronize()
+        return tuple(t.cpu().numpy() for t in bufs)
+
+    # f64 rows into the caller's arrays and into the batch's own: the drop-in Evaluate's
+    d64 = nan_rows(torch.float64)
+    torch.cuda.synchronize()
+    assert np.all(batch.evaluate_points_f64(poses, *(t.data_ptr() for t in d64)) == 0)
+    p64 = host(d64)
+    assert all(np.array_equal(x, y) for x, y in zip(p64, (r, jo, je)))
+    assert np.all(batch.evaluate_rows_f64(poses) == 0)
+    rows = batch.fetch_rows_f64(0, n)
+    assert all(np.array_equal(x, y) for x, y in zip(rows, (r, jo, je)))
+    # f32 rows: the single-constraint device pass's, and the f64 rows' rounding
+    d32, s32 = nan_rows(torch.float32), nan_rows(torch.float32)
+    torch.cuda.synchronize()
+    assert np.all(batch.evaluate_points(poses, *(t.data_ptr() for t in d32)) == 0)
+    assert cf.evaluate_device_f32(poses[0], poses[1], *(t.data_ptr() for t in s32))
+    p32, single32 = host(d32), host(s32)
+    assert all(np.array_equal(x.view(np.uint32), y.view(np.uint32)) for x, y in zip(p32, single32))
+    assert all(np.array_equal(x.view(np.uint32), y.astype(np.float32).view(np.uint32)) for x, y in zip(p32, (r, jo, je)))
+    # blocked rows, re-based with blocked_layout(): the same f32 rows, the last block's padding untouched
+    nbytes, per, first = batch.blocked_layout()
+    assert per == 1024 and int(first[1]) == -(-n // per) and nbytes == int(first[1]) * per * 36
+    blocks = torch.full((nbytes // 4,), float("nan"), dtype=torch.float32, device="cuda:0")
+    torch.cuda.synchronize()
+    assert np.all(batch.evaluate_points_blocked(poses, blocks.data_ptr()) == 0)
+    (B,) = host([blocks])
+    B = B.reshape(-1, 9 * per)
+    for k0 in range(0, n, per):
+        blk, k = B[int(first[0]) + k0 // per], min(per, n - k0)
+        s = slice(k0, k0 + k)
+        assert np.array_equal(blk[:k].view(np.uint32), p32[0][s].view(np.uint32))
+        assert np.array_equal(blk[per:5 * per].reshape(per, 4)[:k].view(np.uint32), p32[1][s].view(np.uint32))
+        assert np.array_equal(blk[5 * per:].reshape(per, 4)[:k].view(np.uint32), p32[2][s].view(np.uint32))
+        assert np.isnan(blk[k:per]).all() and np.isnan(blk[per:5 * per].reshape(per, 4)[k:]).all()
+        assert np.isnan(blk[5 * per:].reshape(per, 4)[k:]).all()
+    # the cost-only fused pass: element 0 of the full pass's 45-block (vgx_reg_batch_evaluate_cost)
+    st_n, normal = batch.evaluate_normal(poses)
+    st_c, cost = batch.evaluate_cost(poses)
+    assert np.array_equal(st_n, st_c) and np.array_equal(cost.view(np.uint64), normal[:, 0].copy().view(np.uint64)) and cost[0] > 0
+    for o in (batch, cf):
+        o.destroy()
+    return dict(rows=(r, jo, je), points_f64=p64, fetched=rows, points=p32, single=single32, blocked=(B,),
+                normal=(normal.copy(),), cost=(cost.copy(),))
 
 
 def test_a_batch_refuses_submaps_of_different_layouts(capi):

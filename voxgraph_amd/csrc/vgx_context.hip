@@ -51,10 +51,7 @@ __global__ __launch_bounds__(256) void brickify_kernel(
   float* out = bricks + (size_t)b * CELLS;
   for (int cell = threadIdx.x; cell < CELLS; cell += blockDim.x) {
     int cx, cy, cz;
-    if (!BrickLayout<VPS, LAYOUT>::decode(cell, cx, cy, cz)) {
-      out[cell] = 0.0f;  // padding, never read
-      continue;
-    }
+    BrickLayout<VPS, LAYOUT>::decode(cell, cx, cy, cz);
     int ox = cx == VPS, oy = cy == VPS, oz = cz == VPS;
     int sx = bx + ox, sy = by + oy, sz = bz + oz;
     int slot = b;
@@ -93,15 +90,10 @@ int launch_brickify(vgx_submap sm, int which) {
   sm->grid[which].layout = layout;
   int3 mn = make_int3(sm->lut_min[0], sm->lut_min[1], sm->lut_min[2]);
   int3 dm = make_int3(sm->lut_dim[0], sm->lut_dim[1], sm->lut_dim[2]);
-#define VGX_BRICKIFY(VPS, LAYOUT)                                                                       \
-  hipLaunchKernelGGL((brickify_kernel<VPS, LAYOUT>), dim3(sm->n_blocks), dim3(256), 0, ctx->stream,    \
-                     sm->d_block_index, sm->d_lut, mn, dm, dist, w, obs, sm->grid[which].d_bricks)
-  if (sm->vps == 16) {
-    if (layout == 0) VGX_BRICKIFY(16, 0); else if (layout == 1) VGX_BRICKIFY(16, 1); else VGX_BRICKIFY(16, 2);
-  } else {
-    if (layout == 0) VGX_BRICKIFY(8, 0); else if (layout == 1) VGX_BRICKIFY(8, 1); else VGX_BRICKIFY(8, 2);
-  }
-#undef VGX_BRICKIFY
+  dispatch_brick(sm->vps, layout, [&](auto V, auto L) {
+    hipLaunchKernelGGL((brickify_kernel<V(), L()>), dim3(sm->n_blocks), dim3(256), 0, ctx->stream, sm->d_block_index, sm->d_lut, mn, dm,
+                       dist, w, obs, sm->grid[which].d_bricks);
+  });
   VGX_HIP(ctx, hipGetLastError());
   sm->grid[which].present = true;
   return VGX_OK;

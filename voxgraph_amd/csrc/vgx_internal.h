@@ -12,6 +12,7 @@
 #include <initializer_list>
 #include <random>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -38,40 +39,43 @@ namespace vgx {
 //      two cache lines.  4.25 x memory.  Fastest where evaluations are scattered (sampling mode: every
 //      touched line is an HBM fetch): -14 % per evaluation of the shipped configuration, +18-25 % on the
 //      all-points passes (profiles/README.md, round 3).
-//   2  4^3 sub-tiles with their own aprons (5^3 floats, padded to 128): the four x-pairs of a
-//      neighbourhood lie within 128 B.  2 x memory.  Measured in between; not selectable through
-//      vgx_ctx_set_brick_layout.
+// A third layout, 4^3 sub-tiles with their own aprons (2 x memory), was measured in between the two and not kept
+// (profiles/README.md, "Brick layouts", row 2).
 template <int VPS, int LAYOUT>
 struct BrickLayout {
+  static_assert(LAYOUT == 0 || LAYOUT == 1, "apron (0) or quad (1) bricks");
   static constexpr int B = VPS + 1;
-  static constexpr int S = VPS / 4;
-  static constexpr int cells = LAYOUT == 0 ? B * B * B : (LAYOUT == 1 ? B * VPS * VPS * 4 : S * S * S * 128);
+  static constexpr int cells = LAYOUT == 0 ? B * B * B : B * VPS * VPS * 4;
   // float offset of a base voxel's neighbourhood anchor inside its brick
   __host__ __device__ static int anchor(int vx, int vy, int vz) {
     if (LAYOUT == 0) return vx + B * (vy + B * vz);
-    if (LAYOUT == 1) return 4 * (vx + B * (vy + VPS * vz));
-    return 128 * ((vx >> 2) + S * ((vy >> 2) + S * (vz >> 2))) + (vx & 3) + 5 * ((vy & 3) + 5 * (vz & 3));
+    return 4 * (vx + B * (vy + VPS * vz));
   }
-  // brick float index -> apron cell (cx, cy, cz in [0, VPS]); false: padding
-  __host__ __device__ static bool decode(int i, int& cx, int& cy, int& cz) {
+  // brick float index -> apron cell (cx, cy, cz in [0, VPS])
+  __host__ __device__ static void decode(int i, int& cx, int& cy, int& cz) {
     if (LAYOUT == 0) {
       cx = i % B; cy = (i / B) % B; cz = i / (B * B);
-      return true;
+      return;
     }
-    if (LAYOUT == 1) {
-      const int comp = i & 3, e = i >> 2;
-      cx = e % B; cy = (e / B) % VPS + (comp & 1); cz = e / (B * VPS) + (comp >> 1);
-      return true;
-    }
-    const int s = i >> 7, k = i & 127;
-    if (k >= 125) return false;
-    cx = 4 * (s % S) + k % 5; cy = 4 * ((s / S) % S) + (k / 5) % 5; cz = 4 * (s / (S * S)) + k / 25;
-    return true;
+    const int comp = i & 3, e = i >> 2;
+    cx = e % B; cy = (e / B) % VPS + (comp & 1); cz = e / (B * VPS) + (comp >> 1);
   }
 };
+// The one place that enumerates (vps, layout): the two runtime values become compile-time ones, handed to a generic
+// lambda as std::integral_constants -- f(V, L) names BrickLayout<V(), L()> or a kernel<V(), L(), ...>.  vps is 16 or 8
+// (a submap of any other is refused when it is created), layout VGX_BRICKS_APRON or VGX_BRICKS_QUAD (vgx_ctx_set_brick_layout).
+template <class F>
+inline auto dispatch_brick(int vps, int layout, F&& f) {
+  using std::integral_constant;
+  if (vps == 16) {
+    if (layout == VGX_BRICKS_QUAD) return f(integral_constant<int, 16>{}, integral_constant<int, 1>{});
+    return f(integral_constant<int, 16>{}, integral_constant<int, 0>{});
+  }
+  if (layout == VGX_BRICKS_QUAD) return f(integral_constant<int, 8>{}, integral_constant<int, 1>{});
+  return f(integral_constant<int, 8>{}, integral_constant<int, 0>{});
+}
 inline size_t brick_cells(int vps, int layout) {
-  if (vps == 16) return layout == 0 ? BrickLayout<16, 0>::cells : (layout == 1 ? BrickLayout<16, 1>::cells : BrickLayout<16, 2>::cells);
-  return layout == 0 ? BrickLayout<8, 0>::cells : (layout == 1 ? BrickLayout<8, 1>::cells : BrickLayout<8, 2>::cells);
+  return dispatch_brick(vps, layout, [](auto V, auto L) { return (size_t)BrickLayout<V(), L()>::cells; });
 }
 
 struct GridDev {
@@ -80,7 +84,7 @@ struct GridDev {
   int32_t lut_min[3];
   int32_t lut_dim[3];
   float voxel_size, voxel_size_inv, block_size, block_size_inv;
-  int32_t layout;        // brick layout of `bricks` (0 apron, 1 quad, 2 sub-tiles)
+  int32_t layout;        // brick layout of `bricks` (0 apron, 1 quad)
 };
 
 // Per-evaluation pose data of one constraint, computed on the host in the

@@ -159,7 +159,7 @@ __device__ __forceinline__ void load_neighbours(const float* cell, float d[8]) {
     d[0] = q0.x; d[2] = q0.y; d[1] = q0.z; d[3] = q0.w;
     d[4] = q1.x; d[6] = q1.y; d[5] = q1.z; d[7] = q1.w;
   } else {
-    constexpr int SY = LAYOUT == 0 ? VPS + 1 : 5, SZ = LAYOUT == 0 ? (VPS + 1) * (VPS + 1) : 25;
+    constexpr int SY = VPS + 1, SZ = (VPS + 1) * (VPS + 1);
     // x is the contiguous axis, so (k, k+4) is one 8-byte load
     f32x2 p0 = *(const VGX_GLOBAL f32x2u*)(cell);
     f32x2 p1 = *(const VGX_GLOBAL f32x2u*)(cell + SZ);
@@ -1643,20 +1643,10 @@ static void launch_points(vgx_ctx ctx, int vps, int layout, const ConstraintDev*
                      ctx->stream, d_desc, d_pack, d_tiles, n_tiles, d_tile_dead);
   dim3 grid(((n_tiles + 7) / 8) * 8), block(kBlockThreads);
   using O4 = typename Out4<OUT>::type;
-#define VGX_LAUNCH_POINTS(VPS, LAYOUT)                                                              \
-  hipLaunchKernelGGL((reg_eval_points_kernel<VPS, LAYOUT, OUT, kPointsPerThread>), grid, block, 0, \
-                     ctx->stream, d_desc, d_pack, d_tiles, d_tile_dead, n_tiles, (OUT*)res, (O4*)jr, (O4*)je, blocked ? 1 : 0)
-  if (layout == 0) {
-    if (vps == 16) VGX_LAUNCH_POINTS(16, 0);
-    else VGX_LAUNCH_POINTS(8, 0);
-  } else if (layout == 1) {
-    if (vps == 16) VGX_LAUNCH_POINTS(16, 1);
-    else VGX_LAUNCH_POINTS(8, 1);
-  } else {
-    if (vps == 16) VGX_LAUNCH_POINTS(16, 2);
-    else VGX_LAUNCH_POINTS(8, 2);
-  }
-#undef VGX_LAUNCH_POINTS
+  dispatch_brick(vps, layout, [&](auto V, auto L) {
+    hipLaunchKernelGGL((reg_eval_points_kernel<V(), L(), OUT, kPointsPerThread>), grid, block, 0, ctx->stream, d_desc, d_pack, d_tiles,
+                       d_tile_dead, n_tiles, (OUT*)res, (O4*)jr, (O4*)je, blocked ? 1 : 0);
+  });
 }
 
 template <typename OUT>
@@ -1666,21 +1656,10 @@ static void launch_points_single(hipStream_t stream, int vps, const ConstraintDe
   if (n_tiles <= 0) return;
   dim3 grid(((n_tiles + 7) / 8) * 8), block(kBlockThreads);
   using O4 = typename Out4<OUT>::type;
-#define VGX_LAUNCH_SINGLE(VPS, LAYOUT)                                                                       \
-  hipLaunchKernelGGL((reg_eval_points_single_kernel<VPS, LAYOUT, OUT, kPointsPerThread>), grid, block, 0, stream, \
-                     desc, pack, n_tiles, (OUT*)res, (O4*)jr, (O4*)je)
-  const int layout = desc.grid.layout;
-  if (layout == 0) {
-    if (vps == 16) VGX_LAUNCH_SINGLE(16, 0);
-    else VGX_LAUNCH_SINGLE(8, 0);
-  } else if (layout == 1) {
-    if (vps == 16) VGX_LAUNCH_SINGLE(16, 1);
-    else VGX_LAUNCH_SINGLE(8, 1);
-  } else {
-    if (vps == 16) VGX_LAUNCH_SINGLE(16, 2);
-    else VGX_LAUNCH_SINGLE(8, 2);
-  }
-#undef VGX_LAUNCH_SINGLE
+  dispatch_brick(vps, desc.grid.layout, [&](auto V, auto L) {
+    hipLaunchKernelGGL((reg_eval_points_single_kernel<V(), L(), OUT, kPointsPerThread>), grid, block, 0, stream, desc, pack, n_tiles,
+                       (OUT*)res, (O4*)jr, (O4*)je);
+  });
 }
 
 // the visuals of the same evaluation: same grid, descriptor and pose pack as launch_points_single; cloud may be null
@@ -1690,27 +1669,14 @@ static void launch_visuals_single(hipStream_t stream, int vps, const ConstraintD
   const int n_tiles = (int)((desc.n + kTilePoints - 1) / kTilePoints);
   if (n_tiles <= 0 || (!cloud && !arrows)) return;
   dim3 grid(n_tiles), block(kBlockThreads);
-#define VGX_LAUNCH_VISUALS(VPS, LAYOUT)                                                                              \
-  do {                                                                                                               \
-    if (arrows)                                                                                                      \
-      hipLaunchKernelGGL((reg_visuals_single_kernel<VPS, LAYOUT, kPointsPerThread, true>), grid, block, 0, stream,   \
-                         desc, pack, mission, n_tiles, (f32x4*)cloud, arrows, origins);                              \
-    else                                                                                                             \
-      hipLaunchKernelGGL((reg_visuals_single_kernel<VPS, LAYOUT, kPointsPerThread, false>), grid, block, 0, stream,  \
-                         desc, pack, mission, n_tiles, (f32x4*)cloud, arrows, origins);                              \
-  } while (0)
-  const int layout = desc.grid.layout;
-  if (layout == 0) {
-    if (vps == 16) VGX_LAUNCH_VISUALS(16, 0);
-    else VGX_LAUNCH_VISUALS(8, 0);
-  } else if (layout == 1) {
-    if (vps == 16) VGX_LAUNCH_VISUALS(16, 1);
-    else VGX_LAUNCH_VISUALS(8, 1);
-  } else {
-    if (vps == 16) VGX_LAUNCH_VISUALS(16, 2);
-    else VGX_LAUNCH_VISUALS(8, 2);
-  }
-#undef VGX_LAUNCH_VISUALS
+  dispatch_brick(vps, desc.grid.layout, [&](auto V, auto L) {
+    if (arrows)
+      hipLaunchKernelGGL((reg_visuals_single_kernel<V(), L(), kPointsPerThread, true>), grid, block, 0, stream, desc, pack, mission,
+                         n_tiles, (f32x4*)cloud, arrows, origins);
+    else
+      hipLaunchKernelGGL((reg_visuals_single_kernel<V(), L(), kPointsPerThread, false>), grid, block, 0, stream, desc, pack, mission,
+                         n_tiles, (f32x4*)cloud, arrows, origins);
+  });
 }
 
 // T_mission__reading as RCF:80-88 builds it: the reading pose narrowed to f32, minkindr's exp
@@ -2522,6 +2488,37 @@ static int apply_launch_order(vgx_reg_batch b, const std::vector<Tile>& tiles, T
   return VGX_OK;
 }
 
+// The head of every batched evaluation (the caller holds ctx->mu and has set the device): the point sets are current
+// and the sampling constraints have drawn (batch_begin), then the pose packs and statuses of this evaluation.
+static int batch_evaluation_begin(vgx_reg_batch b, const double* poses, int32_t n_nodes, int32_t* status) {
+  const int rc = batch_begin(b);
+  return rc != VGX_OK ? rc : batch_upload_packs(b, poses, n_nodes, status);
+}
+
+}  // extern "C"
+
+// One materialising pass of the whole batch into the caller's rows (same conditions): OUT rows, `blocked`: res == jr == je,
+// one array of tile blocks.
+template <typename OUT>
+static int batch_points_pass(vgx_reg_batch b, const double* poses, int32_t n_nodes, void* res, void* jr, void* je, bool blocked,
+                             int32_t* status) {
+  vgx_ctx ctx = b->ctx;
+  int rc = batch_evaluation_begin(b, poses, n_nodes, status);
+  if (rc != VGX_OK) return rc;
+  if (b->n == 0) return VGX_OK;
+  if (!b->points_order_made && !b->tiles.empty()) {
+    rc = apply_launch_order(b, b->tiles, b->d_tiles.as<Tile>(), b->host_points_tile_first, /*points_pass=*/true);
+    if (rc != VGX_OK) return rc;
+    b->points_order_made = true;
+  }
+  launch_points<OUT>(ctx, b->regs[0]->reading->vps, b->layout, b->d_desc.as<ConstraintDev>(), b->d_pack.as<PosePack>(),
+                     b->d_tiles.as<Tile>(), b->d_tile_dead.as<unsigned char>(), (int)b->tiles.size(), res, jr, je, blocked);
+  VGX_HIP(ctx, hipGetLastError());
+  return VGX_OK;
+}
+
+extern "C" {
+
 int vgx_reg_batch_evaluate_points(vgx_reg_batch b, const double* poses, int32_t n_nodes,
                                   void* d_residuals, void* d_jac_ref, void* d_jac_read,
                                   int32_t* status) {
@@ -2530,19 +2527,7 @@ int vgx_reg_batch_evaluate_points(vgx_reg_batch b, const double* poses, int32_t 
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (!d_residuals) return set_error(ctx, VGX_ERR_INVALID, "vgx_reg_batch_evaluate_points: residuals == NULL");
   VGX_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = batch_begin(b);
-  if (rc == VGX_OK) rc = batch_upload_packs(b, poses, n_nodes, status);
-  if (rc != VGX_OK) return rc;
-  if (b->n == 0) return VGX_OK;
-  if (!b->points_order_made && !b->tiles.empty()) {
-    rc = apply_launch_order(b, b->tiles, b->d_tiles.as<Tile>(), b->host_points_tile_first, /*points_pass=*/true);
-    if (rc != VGX_OK) return rc;
-    b->points_order_made = true;
-  }
-  launch_points<float>(ctx, b->regs[0]->reading->vps, b->layout, b->d_desc.as<ConstraintDev>(), b->d_pack.as<PosePack>(),
-                       b->d_tiles.as<Tile>(), b->d_tile_dead.as<unsigned char>(), (int)b->tiles.size(), d_residuals, d_jac_ref, d_jac_read);
-  VGX_HIP(ctx, hipGetLastError());
-  return VGX_OK;
+  return batch_points_pass<float>(b, poses, n_nodes, d_residuals, d_jac_ref, d_jac_read, /*blocked=*/false, status);
 }
 
 // The materialising pass in Ceres' own types: f64 rows, every value the reference's f64 (include/voxgraph_amd.h).
@@ -2555,19 +2540,7 @@ int vgx_reg_batch_evaluate_points_f64(vgx_reg_batch b, const double* poses, int3
   if (((uintptr_t)d_jac_ref | (uintptr_t)d_jac_read) & 31u)
     return set_error(ctx, VGX_ERR_INVALID, "vgx_reg_batch_evaluate_points_f64: Jacobian arrays must be 32-byte aligned (one row)");
   VGX_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = batch_begin(b);
-  if (rc == VGX_OK) rc = batch_upload_packs(b, poses, n_nodes, status);
-  if (rc != VGX_OK) return rc;
-  if (b->n == 0) return VGX_OK;
-  if (!b->points_order_made && !b->tiles.empty()) {
-    rc = apply_launch_order(b, b->tiles, b->d_tiles.as<Tile>(), b->host_points_tile_first, /*points_pass=*/true);
-    if (rc != VGX_OK) return rc;
-    b->points_order_made = true;
-  }
-  launch_points<double>(ctx, b->regs[0]->reading->vps, b->layout, b->d_desc.as<ConstraintDev>(), b->d_pack.as<PosePack>(),
-                       b->d_tiles.as<Tile>(), b->d_tile_dead.as<unsigned char>(), (int)b->tiles.size(), d_residuals, d_jac_ref, d_jac_read);
-  VGX_HIP(ctx, hipGetLastError());
-  return VGX_OK;
+  return batch_points_pass<double>(b, poses, n_nodes, d_residuals, d_jac_ref, d_jac_read, /*blocked=*/false, status);
 }
 
 // One evaluation of every constraint as f64 rows KEPT BY THE BATCH, and the slice of one constraint fetched to the host:
@@ -2579,27 +2552,26 @@ int vgx_reg_batch_evaluate_rows_f64(vgx_reg_batch b, const double* poses, int32_
   if (!b || !poses) return VGX_ERR_INVALID;
   vgx_ctx ctx = b->ctx;
   const int64_t R = b->row_offset.back();
-  {
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    VGX_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t bytes[3] = {(size_t)std::max<int64_t>(R, 1) * 8, (size_t)std::max<int64_t>(R, 1) * 32, (size_t)std::max<int64_t>(R, 1) * 32};
-    const bool want[3] = {true, want_jac_ref != 0, want_jac_read != 0};
-    for (int a = 0; a < 3; ++a)
-      if (want[a] && !b->d_rows[a].p && b->d_rows[a].alloc(bytes[a]) != hipSuccess) {
-        (void)hipGetLastError();
-        return set_error(ctx, VGX_ERR_NOMEM, "vgx_reg_batch_evaluate_rows_f64: no device memory for the batch's own rows");
-      }
-    if (!b->h_rows.p && R > 0 && R * 72 <= kRowsMirrorLimit && b->h_rows.alloc((size_t)R * 72) != hipSuccess)
-      (void)hipGetLastError();   // no pinned memory: fetches copy their slices from the device
-    b->rows_mirrored = false;
-  }
-  int rc = vgx_reg_batch_evaluate_points_f64(b, poses, n_nodes, b->d_rows[0].as<double>(), want_jac_ref ? b->d_rows[1].as<double>() : nullptr,
-                                             want_jac_read ? b->d_rows[2].as<double>() : nullptr, status);
-  if (rc != VGX_OK) return rc;
+  // ONE critical section from the pass to the mirror's copies: no other thread's evaluation of this batch comes between the
+  // rows on the device, what rows_have says of them and what the mirror holds
   std::lock_guard<std::mutex> lk(ctx->mu);
+  VGX_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t bytes[3] = {(size_t)std::max<int64_t>(R, 1) * 8, (size_t)std::max<int64_t>(R, 1) * 32, (size_t)std::max<int64_t>(R, 1) * 32};
+  const bool want[3] = {true, want_jac_ref != 0, want_jac_read != 0};
+  for (int a = 0; a < 3; ++a)
+    if (want[a] && !b->d_rows[a].p && b->d_rows[a].alloc(bytes[a]) != hipSuccess) {
+      (void)hipGetLastError();
+      return set_error(ctx, VGX_ERR_NOMEM, "vgx_reg_batch_evaluate_rows_f64: no device memory for the batch's own rows");
+    }
+  if (!b->h_rows.p && R > 0 && R * 72 <= kRowsMirrorLimit && b->h_rows.alloc((size_t)R * 72) != hipSuccess)
+    (void)hipGetLastError();   // no pinned memory: fetches copy their slices from the device
+  b->rows_mirrored = false;
+  const int rc = batch_points_pass<double>(b, poses, n_nodes, b->d_rows[0].p, want[1] ? b->d_rows[1].p : nullptr,
+                                           want[2] ? b->d_rows[2].p : nullptr, /*blocked=*/false, status);
+  if (rc != VGX_OK) return rc;
   b->rows_have[0] = true;
-  b->rows_have[1] = want_jac_ref != 0;
-  b->rows_have[2] = want_jac_read != 0;
+  b->rows_have[1] = want[1];
+  b->rows_have[2] = want[2];
   if (b->h_rows.p && R > 0) {   // the whole evaluation in (up to) three copies behind the kernel: every fetch is a host copy
     VGX_HIP(ctx, hipMemcpyAsync(b->h_rows.p, b->d_rows[0].p, (size_t)R * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (b->rows_have[1])
@@ -2660,19 +2632,7 @@ int vgx_reg_batch_evaluate_points_blocked(vgx_reg_batch b, const double* poses, 
   if (((uintptr_t)d_blocks & 15u) != 0)
     return set_error(ctx, VGX_ERR_INVALID, "vgx_reg_batch_evaluate_points_blocked: blocks must be 16-byte aligned");
   VGX_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = batch_begin(b);
-  if (rc == VGX_OK) rc = batch_upload_packs(b, poses, n_nodes, status);
-  if (rc != VGX_OK) return rc;
-  if (b->n == 0) return VGX_OK;
-  if (!b->points_order_made && !b->tiles.empty()) {
-    rc = apply_launch_order(b, b->tiles, b->d_tiles.as<Tile>(), b->host_points_tile_first, /*points_pass=*/true);
-    if (rc != VGX_OK) return rc;
-    b->points_order_made = true;
-  }
-  launch_points<float>(ctx, b->regs[0]->reading->vps, b->layout, b->d_desc.as<ConstraintDev>(), b->d_pack.as<PosePack>(),
-                       b->d_tiles.as<Tile>(), b->d_tile_dead.as<unsigned char>(), (int)b->tiles.size(), d_blocks, d_blocks, d_blocks, /*blocked=*/true);
-  VGX_HIP(ctx, hipGetLastError());
-  return VGX_OK;
+  return batch_points_pass<float>(b, poses, n_nodes, d_blocks, d_blocks, d_blocks, /*blocked=*/true, status);
 }
 
 // Placement by measurement (include/voxgraph_amd.h): which of the caller's candidate arrays the materialising pass runs
@@ -2864,22 +2824,11 @@ static int launch_fused_tiles(vgx_reg_batch b) {
   const unsigned occupancy_pad = ctx->tsdf_integrators.load() > 0 ? 27u * 1024u : 0u;
   if (n_tiles > 0) {
     dim3 grid(n_tiles), block(kBlockThreads);
-    const int vps = b->regs[0]->reading->vps;
-#define VGX_LAUNCH_LEAN(VPS, LAYOUT)                                                                                \
-  hipLaunchKernelGGL((reg_eval_reduce_lean_kernel<VPS, LAYOUT, COST_ONLY>), grid, block, occupancy_pad, ctx->stream, \
-                     b->d_desc.as<ConstraintDev>(), b->d_pack.as<PosePack>(), b->d_reduce_tiles.as<Tile>(), n_tiles, \
-                     b->d_tile_first.as<int32_t>(), b->d_partials.as<double>())
-    if (b->layout == 1) {
-      if (vps == 16) VGX_LAUNCH_LEAN(16, 1);
-      else VGX_LAUNCH_LEAN(8, 1);
-    } else if (b->layout == 2) {
-      if (vps == 16) VGX_LAUNCH_LEAN(16, 2);
-      else VGX_LAUNCH_LEAN(8, 2);
-    } else {
-      if (vps == 16) VGX_LAUNCH_LEAN(16, 0);
-      else VGX_LAUNCH_LEAN(8, 0);
-    }
-#undef VGX_LAUNCH_LEAN
+    dispatch_brick(b->regs[0]->reading->vps, b->layout, [&](auto V, auto L) {
+      hipLaunchKernelGGL((reg_eval_reduce_lean_kernel<V(), L(), COST_ONLY>), grid, block, occupancy_pad, ctx->stream,
+                         b->d_desc.as<ConstraintDev>(), b->d_pack.as<PosePack>(), b->d_reduce_tiles.as<Tile>(), n_tiles,
+                         b->d_tile_first.as<int32_t>(), b->d_partials.as<double>());
+    });
     VGX_HIP(ctx, hipGetLastError());
   }
   return VGX_OK;
@@ -2893,8 +2842,7 @@ int vgx_reg_batch_evaluate_normal(vgx_reg_batch b, const double* poses, int32_t 
   vgx_ctx ctx = b->ctx;
   std::lock_guard<std::mutex> lk(ctx->mu);
   VGX_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = batch_begin(b);
-  if (rc == VGX_OK) rc = batch_upload_packs(b, poses, n_nodes, status);
+  int rc = batch_evaluation_begin(b, poses, n_nodes, status);
   if (rc != VGX_OK) return rc;
   if (b->n == 0) return VGX_OK;
   double* out = d_normal ? (double*)d_normal : b->d_normal.as<double>();
@@ -2924,8 +2872,7 @@ int vgx_reg_batch_evaluate_cost(vgx_reg_batch b, const double* poses, int32_t n_
   vgx_ctx ctx = b->ctx;
   std::lock_guard<std::mutex> lk(ctx->mu);
   VGX_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = batch_begin(b);
-  if (rc == VGX_OK) rc = batch_upload_packs(b, poses, n_nodes, status);
+  int rc = batch_evaluation_begin(b, poses, n_nodes, status);
   if (rc != VGX_OK) return rc;
   if (b->n == 0) return VGX_OK;
   // (the internal [n][45] array's first n doubles when the caller passes no device array: a cost-only evaluation
@@ -2952,7 +2899,10 @@ int vgx_reg_batch_launch_order(vgx_reg_batch b, int32_t pass, int32_t* grouped) 
   return VGX_OK;
 }
 
-// per constraint: residuals in chunks that survive the bounding-sphere test at the uploaded poses
+// per constraint: residuals in chunks that survive the bounding-sphere test at the uploaded poses.  The two entry points
+// below begin with batch_points_current + batch_upload_packs, NOT batch_evaluation_begin: they read chunk bounds and pose
+// packs only, and a count is no evaluation -- batch_begin would draw, and leave every sampling engine one evaluation
+// further on than the caller's next evaluation expects.
 static int count_live_each(vgx_reg_batch b, std::vector<unsigned long long>& each) {
   vgx_ctx ctx = b->ctx;
   each.assign((size_t)b->n, 0);
