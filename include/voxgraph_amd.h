@@ -1627,6 +1627,46 @@ VGX_API int vgx_pose_graph_download_system(vgx_pose_graph graph, int32_t* n_free
  * pivot is not positive or not finite (x and L are then unspecified); the solve above uses the same kernels. */
 VGX_API int vgx_dense_spd_solve(vgx_ctx ctx, int32_t n, const double* A, const double* b, double* x, double* L);
 
+/* ---- Pose graph: edge covariances ----------------------------------------- */
+/* PoseGraph::getEdgeCovarianceMap (pose_graph.cpp:117-163) as a library call: ceres::Covariance::Compute over the whole
+ * problem followed by GetCovarianceBlock per pair.  One full evaluation at `poses` (registration through the batch
+ * unless excluded), H assembled by the lists of the solve, factorised UNDAMPED by the same Cholesky, and the columns of
+ * H^-1 that the pairs name solved on the device: L L^T X = E, E the identity's columns of the distinct second nodes
+ * (of pairs between two free nodes) in ascending free position, built on the device.
+ *
+ * covariance[p] (row-major 4x4) = rows of node pairs[2p], columns of node pairs[2p + 1] of H^-1: the solution columns
+ * of node b = pairs[2p + 1] at the rows of node a = pairs[2p].  The computed inverse is not exactly symmetric, so
+ * (a, b) and (b, a) are two answers, each defined on its own; (a, a) and duplicates are allowed.  A pair that names a
+ * constant node gets sixteen zeros (as Ceres gives).
+ *
+ * THE ORDER CONTRACT, extended.  For every element of every solved column:
+ *   forward    y_i = (b_i - l_i0 y_0 - l_i1 y_1 - ...) / l_ii, k ascending;
+ *   backward   x_i = (y_i - l_ki x_k - ...) / l_ii, k descending from n - 1;
+ * each term one rounded multiply and one rounded subtract -- tests/pose_graph_ref.py's forward / backward applied to the
+ * column (tests/pose_graph_covariance_ref.py).  Rows above a unit column's 1 are not computed in the forward pass (they
+ * are +0.0 for a factor that passed the pivot check) and rows above the lowest one wanted are not computed in the
+ * backward pass: no delivered bit depends on either.
+ *
+ * poses host [n_nodes][4] f64, read only.  Synchronous, two host synchronisations (the evaluation's and the result's),
+ * one device-to-host copy.  The solved columns are held by the graph, grown on demand: at most (4 x free nodes)^2
+ * doubles, 2 GiB at the 4096-node limit.  Afterwards vgx_pose_graph_download_system returns the H, g of this evaluation.
+ * VGX_ERR_NOT_POSITIVE_DEFINITE when a pivot is not positive or not finite -- a rank-deficient graph, e.g. a free node
+ * that no constraint touches; `covariance` is then unspecified.  Refused with VGX_ERR_INVALID (vgx_last_error says
+ * which): NULL graph; NULL poses, pairs or covariance while n_pairs > 0; n_pairs < 0; a node index out of range; a pose
+ * that is not finite; the graph states vgx_pose_graph_optimize refuses.  A refused call leaves `covariance` untouched.
+ * n_pairs == 0 is VGX_OK and does nothing; a graph whose nodes are all constant returns zeros.  More than 2^26 pairs in
+ * one call: VGX_ERR_UNSUPPORTED. */
+VGX_API int vgx_pose_graph_covariance(vgx_pose_graph graph, const double* poses /* [n_nodes][4] */,
+                                      int32_t exclude_registration_constraints,
+                                      int32_t n_pairs, const int32_t* pairs /* [n_pairs][2] */,
+                                      double* covariance /* [n_pairs][16] */);
+/* The same kernels on a caller's matrix and general right-hand sides: solves A X = B for a symmetric positive definite
+ * A (host row-major [n][n], the LOWER triangle is read), B and X host [n][m] row-major (they may be the same array); L
+ * (nullable) as for vgx_dense_spd_solve.  1 <= n <= 16384, 1 <= m <= 16384.  Column c of X is bit for bit what
+ * vgx_dense_spd_solve returns for column c of B.  VGX_ERR_NOT_POSITIVE_DEFINITE as there (X and L then unspecified). */
+VGX_API int vgx_dense_spd_solve_many(vgx_ctx ctx, int32_t n, const double* A, int32_t m,
+                                     const double* B /* [n][m] */, double* X /* [n][m] */, double* L /* nullable */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -368,6 +368,8 @@ SIGNATURES = {
     "vgx_pose_graph_history": (C.c_int, [vp, C.c_int32, C.POINTER(PoseGraphIteration), i32p]),
     "vgx_pose_graph_download_system": (C.c_int, [vp, i32p, f64p, f64p]),
     "vgx_dense_spd_solve": (C.c_int, [vp, C.c_int32, f64p, f64p, f64p, f64p]),
+    "vgx_pose_graph_covariance": (C.c_int, [vp, f64p, C.c_int32, C.c_int32, i32p, f64p]),
+    "vgx_dense_spd_solve_many": (C.c_int, [vp, C.c_int32, f64p, C.c_int32, f64p, f64p, f64p]),
 }
 
 # every symbol include/voxgraph_amd_bench.h declares (libvoxgraph_amd_bench.so: test and benchmark tooling)
@@ -1086,6 +1088,16 @@ def dense_spd_solve(ctx, A, b, want_factor=True):
     return x, L
 
 
+def dense_spd_solve_many(ctx, A, B, want_factor=False):
+    """vgx_dense_spd_solve_many: A X = B for B [n][m] -> (X [n][m], L or None); raises as dense_spd_solve does"""
+    A, B = _f64(A), _f64(B)
+    n, m = B.shape
+    X = np.zeros((n, m))
+    L = np.zeros((n, n)) if want_factor else None
+    ctx.check(ctx.lib.vgx_dense_spd_solve_many(ctx.h, n, _ptr(A, f64p), m, _ptr(B, f64p), _ptr(X, f64p), _ptr(L, f64p)))
+    return X, L
+
+
 class PoseGraph:
     """vgx_pose_graph: PoseGraph::optimize() on the device (include/voxgraph_amd.h, "Pose graph: the solve")."""
 
@@ -1128,6 +1140,16 @@ class PoseGraph:
         H, g = np.zeros((n.value, n.value)), np.zeros(n.value)
         self.ctx.check(self.ctx.lib.vgx_pose_graph_download_system(self.h, None, _ptr(H, f64p), _ptr(g, f64p)))
         return H, g
+
+    def covariance(self, poses, pairs, exclude_registration=False):
+        """vgx_pose_graph_covariance -> [n_pairs][4][4]: block (a, b) of H^-1 at `poses` per pair (a, b) of node indices;
+        raises VgxError(ERR_NOT_POSITIVE_DEFINITE) on a rank-deficient graph"""
+        x = np.array(poses, np.float64).reshape(self.n_nodes, 4)
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        out = np.zeros((len(pr), 4, 4))
+        self.ctx.check(self.ctx.lib.vgx_pose_graph_covariance(self.h, _ptr(x, f64p), int(bool(exclude_registration)), len(pr),
+                                                              _ptr(pr, i32p), _ptr(out, f64p)))
+        return out
 
     def destroy(self):
         if self.h:

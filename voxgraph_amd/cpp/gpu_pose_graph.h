@@ -1,6 +1,6 @@
 // A host mirror of voxgraph::PoseGraph (voxgraph/include/voxgraph/backend/pose_graph.h) as far as solving goes, on
 // vgx_pose_graph (include/voxgraph_amd.h, "Pose graph: the solve"): nodes, registration / relative / absolute pose
-// constraints, optimize(), getSubmapPoses() and the stored summaries.  No Ceres, no Eigen.
+// constraints, optimize(), getSubmapPoses(), getEdgeCovarianceMap() and the stored summaries.  No Ceres, no Eigen.
 //
 //   voxgraph_amd::GpuPoseGraph graph(gpu_ctx);
 //   graph.addSubmapNode(id, pose, /*constant=*/id == first);            // pose_graph_interface.cpp:24-48
@@ -8,6 +8,8 @@
 //   graph.addRelativePoseConstraint(a, b, t_ab, yaw_ab, information);   // odometry, loop closures
 //   graph.addAbsolutePoseConstraint(frame, id, t, yaw, information);    // from a constant reference-frame node
 //   int rc = graph.optimize(/*exclude_registration_constraints=*/false);
+//   std::map<std::pair<int64_t, int64_t>, std::array<double, 16>> covariances = {{{first, second}, {}}};
+//   bool usable = graph.getEdgeCovarianceMap(&covariances);             // pose_graph.cpp:117-163
 //
 // Error convention: nothing is thrown out of optimize(); it returns the library's status and last_error() its text.
 #ifndef VOXGRAPH_AMD_CPP_GPU_POSE_GRAPH_H_
@@ -18,6 +20,7 @@
 #include <cstdint>
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "voxgraph_amd.h"
@@ -44,8 +47,23 @@ inline bool SqrtInformation(const double information[16], double sqrt_informatio
   return true;
 }
 
+// LoopClosureEdgeServer::publishLoopClosureEdges (loop_closure_edge_server.cpp:85-96): the 6x6 message covariance
+// {x, y, z, roll, pitch, yaw} of a 4-DoF block {x, y, z, yaw} -- every entry `unknown`
+// (kSetUnknownCovarianceEntriesTo), then the 4x4 into rows / columns {0, 1, 2, 5}.
+inline void FillLoopClosureEdgeCovariance(const double cov4[16], double out36[36], double unknown = 1e4) {
+  for (int i = 0; i < 36; ++i) out36[i] = unknown;
+  for (int r = 0; r < 4; ++r)
+    for (int c = 0; c < 4; ++c) out36[(r == 3 ? 5 : r) * 6 + (c == 3 ? 5 : c)] = cov4[4 * r + c];
+}
+// ... and :121-129, what it publishes when the covariances are not usable: the identity
+inline void IdentityLoopClosureEdgeCovariance(double out36[36]) {
+  for (int r = 0; r < 6; ++r)
+    for (int c = 0; c < 6; ++c) out36[r * 6 + c] = r == c ? 1.0 : 0.0;
+}
+
 class GpuPoseGraph {
  public:
+  using EdgeCovarianceMap = std::map<std::pair<int64_t, int64_t>, std::array<double, 16>>;  // keys: submap ids
   using Pose = std::array<double, 4>;  // x, y, z, yaw
   explicit GpuPoseGraph(vgx_ctx ctx) : ctx_(ctx) { vgx_pose_graph_options_default(&options_); }
   GpuPoseGraph(const GpuPoseGraph&) = delete;
@@ -115,6 +133,33 @@ class GpuPoseGraph {
       out[kv.first] = p;
     }
     return out;
+  }
+  // PoseGraph::getEdgeCovarianceMap (pose_graph.cpp:117-163): for every key (first, second) of the map the row-major 4x4
+  // covariance block of the two submap poses, from one evaluation of the whole problem (registration constraints
+  // included) at the current poses.  false -- the map is then not to be used -- on an unknown submap id or a failed
+  // computation (a rank-deficient graph; last_error() says which)
+  bool getEdgeCovarianceMap(EdgeCovarianceMap* map) {
+    if (!map) return Fail("getEdgeCovarianceMap: NULL map");
+    std::vector<int32_t> pairs;
+    for (const auto& kv : *map) {
+      if (!hasSubmapNode(kv.first.first) || !hasSubmapNode(kv.first.second)) return Fail("getEdgeCovarianceMap: unknown submap");
+      pairs.push_back(submap_index_[kv.first.first]);
+      pairs.push_back(submap_index_[kv.first.second]);
+    }
+    if (pairs.empty()) return true;
+    if (Build() != VGX_OK) return false;
+    std::vector<double> blocks(8 * pairs.size());
+    const int rc = vgx_pose_graph_covariance(graph_, poses_.data(), 0, static_cast<int32_t>(pairs.size() / 2), pairs.data(), blocks.data());
+    if (rc != VGX_OK) {
+      Status(rc);
+      return false;
+    }
+    size_t p = 0;
+    for (auto& kv : *map) {
+      for (int k = 0; k < 16; ++k) kv.second[static_cast<size_t>(k)] = blocks[16 * p + static_cast<size_t>(k)];
+      ++p;
+    }
+    return true;
   }
   const std::vector<vgx_pose_graph_summary>& getSolverSummaries() const { return summaries_; }
   std::vector<vgx_pose_graph_iteration> lastHistory() const {

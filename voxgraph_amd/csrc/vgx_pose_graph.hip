@@ -255,6 +255,169 @@ __global__ __launch_bounds__(1024) void pg_backward_kernel(const double* __restr
     __syncthreads();
   }
 }
+// ---------------------------------------------------------------------------
+// substitutions on many right-hand sides: X [n][m] row-major, in place; a workgroup owns kSolveCols columns and walks
+// the panels alone, so the two passes are one launch each and no workgroup waits for another
+// ---------------------------------------------------------------------------
+constexpr int kSolveCols = 32;                         // columns of X per workgroup
+constexpr int kSolveColGroups = kSolveCols / 4;        // 4 x 4 micro-tiles: column groups ...
+constexpr int kSolveRowGroups = 256 / kSolveColGroups; // ... and row groups of one pass of the row update
+constexpr int kSolveRows = 4 * kSolveRowGroups;        // rows of X updated per pass
+constexpr int kSolveK = 4096 / kSolveRows;             // columns of L staged per pass: 32 KB of LDS
+constexpr int kSolveStride = kSolveRows + 2;           // LDS row stride of the staged columns, [k][row]
+constexpr int kSolveYStride = kSolveCols + 2;          // ... and of the panel's solved rows, [k][column]
+constexpr int kSolveColsPerWave = kSolveCols / 4;
+constexpr int kSolveStage = kSolveK * kSolveStride > kPanel * (kPanel + 1) ? kSolveK * kSolveStride : kPanel * (kPanel + 1);
+static_assert(kSolveCols % 16 == 0 && kSolveCols <= 64 && kSolveK <= kPanel && kPanel % kSolveK == 0, "the shape of pg_solve_many_kernel");
+
+// row j of a wavefront's columns, column q in lane q: their divisions by l_jj are then ONE division for the wavefront
+// (the same operands per column, so the same bits) and not one per column
+__device__ __forceinline__ double pivot_row(const double (&y)[kSolveColsPerWave], int j, int lane) {
+  double d = 0.0;
+#pragma unroll
+  for (int q = 0; q < kSolveColsPerWave; ++q) {
+    const double v = __shfl(y[q], j);
+    if (lane == q) d = v;
+  }
+  return d;
+}
+
+// chunk_rows (nullable): per workgroup {the first row of its columns that is not zero, the lowest row wanted of them}.
+// Every element's history is that of pg_forward_kernel / pg_backward_kernel: the triangle in one wavefront per column
+// (kSolveColsPerWave columns interleaved), the other rows from accumulators that START at the stored value and subtract
+// product by product, k ascending (forward) or descending (backward).
+template <bool kBackward>
+__global__ __launch_bounds__(256) void pg_solve_many_kernel(const double* __restrict__ L, int n, double* __restrict__ X, int m,
+                                                           const int32_t* __restrict__ chunk_rows, const int* __restrict__ flag) {
+  if (*flag) return;
+  __shared__ alignas(16) double S[kSolveStage];  // the panel's triangle, then the staged columns of L
+  __shared__ alignas(16) double Y[kPanel * kSolveYStride];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tx = tid % kSolveColGroups, ty = tid / kSolveColGroups;
+  const int c0 = blockIdx.x * kSolveCols;
+  const int n_panels = (n + kPanel - 1) / kPanel;
+  // Unit right-hand sides.  Forward: the panels above a column's 1 are skipped -- there b_i = 0 and every y_k so far is
+  // +0.0, and with a factor that passed the pivot check (finite: an inf or NaN below the diagonal reaches a later pivot)
+  // 0.0 - l * 0.0 = +0.0 and +0.0 / l_ii = +0.0, which is what X holds already.  Backward: the pass stops after the
+  // panel of the lowest row wanted -- the rows above it take no part in the rows below.  No delivered bit changes.
+  const int p_first = (!kBackward && chunk_rows) ? chunk_rows[2 * blockIdx.x] / kPanel : 0;
+  const int p_last = (kBackward && chunk_rows) ? chunk_rows[2 * blockIdx.x + 1] / kPanel : 0;
+  for (int p = kBackward ? n_panels - 1 : p_first; kBackward ? p >= p_last : p < n_panels; p += kBackward ? -1 : 1) {
+    const int k0 = p * kPanel, w = min(kPanel, n - k0);
+    __syncthreads();
+    for (int e = tid; e < kPanel * kPanel; e += 256) {
+      const int i = e >> 6, j = e & 63;
+      S[i * (kPanel + 1) + j] = (i < w && j <= i) ? L[(size_t)(k0 + i) * n + k0 + j] : 1.0;
+    }
+    for (int e = tid; e < kPanel * kSolveCols; e += 256) {
+      const int r = e / kSolveCols, c = e % kSolveCols;
+      Y[r * kSolveYStride + c] = (r < w && c0 + c < m) ? X[(size_t)(k0 + r) * m + c0 + c] : 0.0;
+    }
+    __syncthreads();
+    {  // the panel's own triangle: row `lane` of this wavefront's columns in registers
+      double y[kSolveColsPerWave];
+#pragma unroll
+      for (int q = 0; q < kSolveColsPerWave; ++q) y[q] = Y[lane * kSolveYStride + wave * kSolveColsPerWave + q];
+      if (!kBackward) {
+        for (int j = 0; j < w; ++j) {
+          const double ljj = S[j * (kPanel + 1) + j], lij = lane > j ? S[lane * (kPanel + 1) + j] : 0.0;
+          const double d = pivot_row(y, j, lane) / ljj;
+#pragma unroll
+          for (int q = 0; q < kSolveColsPerWave; ++q) {
+            const double yj = __shfl(d, q);
+            if (lane == j) y[q] = yj;
+            if (lane > j) y[q] = y[q] - lij * yj;
+          }
+        }
+      } else {
+        for (int j = w - 1; j >= 0; --j) {
+          const double ljj = S[j * (kPanel + 1) + j], lji = lane < j ? S[j * (kPanel + 1) + lane] : 0.0;
+          const double d = pivot_row(y, j, lane) / ljj;
+#pragma unroll
+          for (int q = 0; q < kSolveColsPerWave; ++q) {
+            const double xj = __shfl(d, q);
+            if (lane == j) y[q] = xj;
+            if (lane < j) y[q] = y[q] - lji * xj;
+          }
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < kSolveColsPerWave; ++q) Y[lane * kSolveYStride + wave * kSolveColsPerWave + q] = y[q];
+    }
+    __syncthreads();
+    for (int e = tid; e < kPanel * kSolveCols; e += 256) {
+      const int r = e / kSolveCols, c = e % kSolveCols;
+      if (r < w && c0 + c < m) X[(size_t)(k0 + r) * m + c0 + c] = Y[r * kSolveYStride + c];
+    }
+    // the other rows: below the panel (forward), above it down to the last panel's first row (backward)
+    const int row_begin = kBackward ? p_last * kPanel : k0 + w, row_end = kBackward ? k0 : n;
+    for (int i0 = row_begin; i0 < row_end; i0 += kSolveRows) {
+      double acc[4][4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const int row = i0 + ty * 4 + a, col = c0 + tx * 4 + b;
+          acc[a][b] = (row < row_end && col < m) ? X[(size_t)row * m + col] : 0.0;
+        }
+      const int n_passes = (w + kSolveK - 1) / kSolveK;
+      for (int s = 0; s < n_passes; ++s) {
+        const int kc = (kBackward ? n_passes - 1 - s : s) * kSolveK;
+        __syncthreads();
+        if (!kBackward) {  // S[k][r] = l(i0 + r, k0 + kc + k): a row of L per kSolveK threads
+          const int k = tid % kSolveK;
+          for (int r = tid / kSolveK; r < kSolveRows; r += 256 / kSolveK)
+            S[k * kSolveStride + r] = (kc + k < w && i0 + r < row_end) ? L[(size_t)(i0 + r) * n + k0 + kc + k] : 0.0;
+        } else {           // S[k][r] = l(k0 + kc + k, i0 + r): a row of L per kSolveRows threads
+          const int r = tid % kSolveRows;
+          for (int k = tid / kSolveRows; k < kSolveK; k += 256 / kSolveRows)
+            S[k * kSolveStride + r] = (kc + k < w && i0 + r < row_end) ? L[(size_t)(k0 + kc + k) * n + i0 + r] : 0.0;
+        }
+        __syncthreads();
+        const int kn = min(kSolveK, w - kc);
+        for (int kk = 0; kk < kn; ++kk) {
+          const int k = kBackward ? kn - 1 - kk : kk;
+          const double2 a01 = *reinterpret_cast<const double2*>(&S[k * kSolveStride + ty * 4]);
+          const double2 a23 = *reinterpret_cast<const double2*>(&S[k * kSolveStride + ty * 4 + 2]);
+          const double2 b01 = *reinterpret_cast<const double2*>(&Y[(kc + k) * kSolveYStride + tx * 4]);
+          const double2 b23 = *reinterpret_cast<const double2*>(&Y[(kc + k) * kSolveYStride + tx * 4 + 2]);
+          const double av[4] = {a01.x, a01.y, a23.x, a23.y};
+          const double bv[4] = {b01.x, b01.y, b23.x, b23.y};
+#pragma unroll
+          for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) acc[a][b] = acc[a][b] - av[a] * bv[b];
+        }
+      }
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const int row = i0 + ty * 4 + a, col = c0 + tx * 4 + b;
+          if (row < row_end && col < m) X[(size_t)row * m + col] = acc[a][b];
+        }
+    }
+  }
+}
+// X [n][m] = the columns unit_row[c] of the identity
+__global__ void pg_unit_columns_kernel(double* __restrict__ X, int n, int m, const int32_t* __restrict__ unit_row) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (size_t)n * m) return;
+  const int i = (int)(t / m), c = (int)(t % m);
+  X[t] = unit_row[c] == i ? 1.0 : 0.0;
+}
+// out [n_pairs][16] = the 4x4 block of X at rows block[2p] .. + 3, columns block[2p + 1] .. + 3; zeros where either is
+// negative (a constant node).  out[16 n_pairs] = the factorisation's flag, so that one copy brings both.
+__global__ void pg_gather_blocks_kernel(const double* __restrict__ X, int m, const int32_t* __restrict__ block, int n_pairs,
+                                        const int* __restrict__ flag, double* __restrict__ out) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t == 0) out[(size_t)n_pairs * 16] = (double)*flag;
+  if (t >= n_pairs * 16) return;
+  const int p = t >> 4, r = (t >> 2) & 3, c = t & 3;
+  const int32_t row = block[2 * p], col = block[2 * p + 1];
+  out[t] = (row < 0 || col < 0) ? 0.0 : X[(size_t)(row + r) * m + col + c];
+}
+
 // step = -z, Hs = H step (per row, ascending columns, from 0.0); out = [step nf][Hs nf]
 __global__ void pg_negate_kernel(const double* __restrict__ z, double* __restrict__ out, int nf) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -290,6 +453,16 @@ int queue_cholesky(vgx_ctx ctx, double* A, int n, int* d_flag) {
 int queue_substitutions(vgx_ctx ctx, const double* L, int n, double* d_x) {
   hipLaunchKernelGGL(pg_forward_kernel, dim3(1), dim3(1024), 0, ctx->stream, L, n, d_x);
   hipLaunchKernelGGL(pg_backward_kernel, dim3(1), dim3(1024), 0, ctx->stream, L, n, d_x);
+  VGX_HIP(ctx, hipGetLastError());
+  return VGX_OK;
+}
+
+// ... and of the two substitutions on the m columns of d_X [n][m] (in place): two launches.  d_chunk_rows: nullable,
+// [ceil(m / kSolveCols)][2], see pg_solve_many_kernel
+int queue_solve_many(vgx_ctx ctx, const double* L, int n, double* d_X, int m, const int32_t* d_chunk_rows, const int* d_flag) {
+  const dim3 grid((m + kSolveCols - 1) / kSolveCols);
+  hipLaunchKernelGGL(pg_solve_many_kernel<false>, grid, dim3(256), 0, ctx->stream, L, n, d_X, m, d_chunk_rows, d_flag);
+  hipLaunchKernelGGL(pg_solve_many_kernel<true>, grid, dim3(256), 0, ctx->stream, L, n, d_X, m, d_chunk_rows, d_flag);
   VGX_HIP(ctx, hipGetLastError());
   return VGX_OK;
 }
@@ -383,6 +556,10 @@ struct vgx_pose_graph_s {
   PinnedBuffer h_io;         // doubles: [step nf][H step nf][g nf][edge terms 56 E][costs n] + the flag
   bool system_valid = false;
   std::vector<vgx_pose_graph_iteration> history;
+  // vgx_pose_graph_covariance: the solved columns [nf][m <= nf], the index lists, the blocks; grown on demand
+  DeviceArray<double> d_X, d_cov;
+  DeviceArray<int32_t> d_cov_index;
+  PinnedBuffer h_cov;        // [blocks 16 n_pairs + the flag, doubles][index lists, int32]
 };
 
 namespace {
@@ -874,6 +1051,151 @@ int vgx_dense_spd_solve(vgx_ctx ctx, int32_t n, const double* A, const double* b
     for (size_t i = 0; i < N; ++i)
       for (size_t j = i + 1; j < N; ++j) L[i * N + j] = 0.0;
   if (flag) return set_error(ctx, VGX_ERR_NOT_POSITIVE_DEFINITE, "vgx_dense_spd_solve: the matrix is not positive definite (a pivot is not positive or not finite)");
+  return VGX_OK;
+}
+
+int vgx_pose_graph_covariance(vgx_pose_graph pg, const double* poses, int32_t exclude_registration_constraints, int32_t n_pairs,
+                              const int32_t* pairs, double* covariance) {
+  if (!pg) return VGX_ERR_INVALID;
+  vgx_ctx ctx = pg->ctx;
+  if (n_pairs < 0) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance: n_pairs < 0");
+  if (n_pairs == 0) return VGX_OK;
+  if (!poses || !pairs || !covariance) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance: NULL poses, pairs or covariance");
+  if (n_pairs > (1 << 26)) return set_error(ctx, VGX_ERR_UNSUPPORTED, "vgx_pose_graph_covariance: more than 2^26 pairs in one call");
+  std::lock_guard<std::mutex> lk(pg->mu);
+  for (size_t i = 0; i < 2 * (size_t)n_pairs; ++i)
+    if (pairs[i] < 0 || pairs[i] >= pg->n_nodes)
+      return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance: pair " + std::to_string(i / 2) + " names a node out of range");
+  for (size_t i = 0; i < 4 * (size_t)pg->n_nodes; ++i)
+    if (!std::isfinite(poses[i])) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance: a pose is not finite");
+  if (pg->batch) {
+    std::lock_guard<std::mutex> lt(lifetime_mu());
+    if (pg->batch->destroy_requested)
+      return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance: the registration batch was destroyed");
+  }
+  const bool with_reg = pg->batch && pg->batch->n > 0 && !exclude_registration_constraints;
+  if (!with_reg && pg->edges.empty())
+    return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance: a graph without constraints (no registration batch in use, no edges)");
+  const size_t n_out = 16 * (size_t)n_pairs;
+  if (pg->nf == 0) {  // every node is constant
+    std::fill(covariance, covariance + n_out, 0.0);
+    return VGX_OK;
+  }
+  if (!pg->lists_made || pg->lists_with_reg != with_reg) {
+    const int rc = make_lists(pg, with_reg);
+    if (rc != VGX_OK) return rc;
+  }
+  // the columns to solve: the distinct second nodes (of pairs between free nodes) in ascending free position, and per
+  // node the lowest row any of its pairs wants
+  const int nf = pg->nf, nfn = nf / 4;
+  std::vector<int32_t> lowest((size_t)nfn, INT32_MAX), col_of((size_t)nfn, -1);
+  for (int p = 0; p < n_pairs; ++p) {
+    const int32_t a = pg->pos[(size_t)pairs[2 * p]], b = pg->pos[(size_t)pairs[2 * p + 1]];
+    if (a >= 0 && b >= 0) lowest[(size_t)b] = std::min(lowest[(size_t)b], 4 * a);
+  }
+  int m = 0;
+  for (int b = 0; b < nfn; ++b)
+    if (lowest[(size_t)b] != INT32_MAX) {
+      col_of[(size_t)b] = m;
+      m += 4;
+    }
+  const int n_chunks = (m + kSolveCols - 1) / kSolveCols;
+  const size_t n_index = (size_t)m + 2 * (size_t)n_chunks + 2 * (size_t)n_pairs;
+  {
+    std::lock_guard<std::mutex> lc(ctx->mu);
+    VGX_HIP(ctx, hipSetDevice(ctx->device));
+    hipError_t e = pg->d_X.reserve(std::max<size_t>(1, (size_t)nf * m) * sizeof(double));
+    if (e == hipSuccess) e = pg->d_cov.reserve((n_out + 1) * sizeof(double));
+    if (e == hipSuccess) e = pg->d_cov_index.reserve(n_index * sizeof(int32_t));
+    if (e != hipSuccess) return alloc_error(ctx, e, "vgx_pose_graph_covariance: allocating the solved columns");
+    e = pg->h_cov.reserve((n_out + 1) * sizeof(double) + n_index * sizeof(int32_t));
+    if (e != hipSuccess) return alloc_error(ctx, e, "vgx_pose_graph_covariance: allocating the pinned staging");
+  }
+  double* h_out = pg->h_cov.as<double>();
+  int32_t* h_unit_row = reinterpret_cast<int32_t*>(h_out + n_out + 1);
+  int32_t* h_chunk_rows = h_unit_row + m;
+  int32_t* h_block = h_chunk_rows + 2 * (size_t)n_chunks;
+  for (int c = 0; c < n_chunks; ++c) h_chunk_rows[2 * c + 1] = INT32_MAX;
+  for (int b = 0; b < nfn; ++b) {
+    const int c = col_of[(size_t)b];
+    if (c < 0) continue;
+    for (int k = 0; k < 4; ++k) h_unit_row[c + k] = 4 * b + k;
+    int32_t& low = h_chunk_rows[2 * (c / kSolveCols) + 1];  // (4 | kSolveCols: a node's columns share a chunk)
+    low = std::min(low, lowest[(size_t)b]);
+  }
+  for (int c = 0; c < n_chunks; ++c) h_chunk_rows[2 * c] = h_unit_row[c * kSolveCols];  // ascending: the chunk's first 1
+  for (int p = 0; p < n_pairs; ++p) {
+    const int32_t a = pg->pos[(size_t)pairs[2 * p]], b = pg->pos[(size_t)pairs[2 * p + 1]];
+    h_block[2 * p] = a >= 0 ? 4 * a : -1;
+    h_block[2 * p + 1] = b >= 0 ? col_of[(size_t)b] : -1;
+    if (a < 0) h_block[2 * p + 1] = -1;
+  }
+  Solve sv{pg, with_reg};
+  double cost = 0.0;
+  int rc = sv.evaluate_full(poses, &cost);
+  if (rc < 0) return rc;
+  {
+    std::lock_guard<std::mutex> lc(ctx->mu);
+    VGX_HIP(ctx, hipSetDevice(ctx->device));
+    int32_t* d_unit_row = pg->d_cov_index.get();
+    int32_t* d_chunk_rows = d_unit_row + m;
+    int32_t* d_block = d_chunk_rows + 2 * (size_t)n_chunks;
+    VGX_HIP(ctx, hipMemcpyAsync(d_unit_row, h_unit_row, n_index * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    VGX_HIP(ctx, hipMemcpyAsync(pg->d_A.p, pg->d_H.p, (size_t)nf * nf * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    rc = queue_cholesky(ctx, pg->d_A.get(), nf, pg->d_flag.get());  // undamped
+    if (rc != VGX_OK) return rc;
+    if (m > 0) {
+      const size_t total = (size_t)nf * m;
+      hipLaunchKernelGGL(pg_unit_columns_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, pg->d_X.get(), nf, m,
+                         d_unit_row);
+      rc = queue_solve_many(ctx, pg->d_A.get(), nf, pg->d_X.get(), m, d_chunk_rows, pg->d_flag.get());
+      if (rc != VGX_OK) return rc;
+    }
+    hipLaunchKernelGGL(pg_gather_blocks_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, ctx->stream, pg->d_X.get(), m, d_block,
+                       n_pairs, pg->d_flag.get(), pg->d_cov.get());
+    VGX_HIP(ctx, hipGetLastError());
+    VGX_HIP(ctx, hipMemcpyAsync(h_out, pg->d_cov.p, (n_out + 1) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  if (h_out[n_out] != 0.0)
+    return set_error(ctx, VGX_ERR_NOT_POSITIVE_DEFINITE,
+                     "vgx_pose_graph_covariance: H is not positive definite (a pivot is not positive or not finite): the graph is rank deficient");
+  std::memcpy(covariance, h_out, n_out * sizeof(double));
+  return VGX_OK;
+}
+
+int vgx_dense_spd_solve_many(vgx_ctx ctx, int32_t n, const double* A, int32_t m, const double* B, double* X, double* L) {
+  if (!ctx) return VGX_ERR_INVALID;
+  if (n < 1 || n > kMaxDenseN || m < 1 || m > kMaxDenseN)
+    return set_error(ctx, (n < 1 || m < 1) ? VGX_ERR_INVALID : VGX_ERR_UNSUPPORTED,
+                     "vgx_dense_spd_solve_many: n and m must be in [1, " + std::to_string(kMaxDenseN) + "]");
+  if (!A || !B || !X) return set_error(ctx, VGX_ERR_INVALID, "vgx_dense_spd_solve_many: NULL A, B or X");
+  const size_t N = (size_t)n, M = (size_t)m;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  VGX_HIP(ctx, hipSetDevice(ctx->device));
+  DeviceArray<double> d_A, d_X;
+  DeviceArray<int> d_flag;
+  hipError_t e = d_A.alloc_n(N * N);
+  if (e == hipSuccess) e = d_X.alloc_n(N * M);
+  if (e == hipSuccess) e = d_flag.alloc_n(1);
+  if (e != hipSuccess) return alloc_error(ctx, e, "vgx_dense_spd_solve_many: allocating the matrix and the right-hand sides");
+  VGX_HIP(ctx, hipMemcpyAsync(d_A.p, A, N * N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  VGX_HIP(ctx, hipMemcpyAsync(d_X.p, B, N * M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  int rc = queue_cholesky(ctx, d_A.get(), n, d_flag.get());
+  if (rc == VGX_OK) rc = queue_solve_many(ctx, d_A.get(), n, d_X.get(), m, nullptr, d_flag.get());
+  if (rc != VGX_OK) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+  }
+  int flag = 0;
+  VGX_HIP(ctx, hipMemcpyAsync(&flag, d_flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  VGX_HIP(ctx, hipMemcpyAsync(X, d_X.p, N * M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (L) VGX_HIP(ctx, hipMemcpyAsync(L, d_A.p, N * N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (L)
+    for (size_t i = 0; i < N; ++i)
+      for (size_t j = i + 1; j < N; ++j) L[i * N + j] = 0.0;
+  if (flag) return set_error(ctx, VGX_ERR_NOT_POSITIVE_DEFINITE, "vgx_dense_spd_solve_many: the matrix is not positive definite (a pivot is not positive or not finite)");
   return VGX_OK;
 }
 
