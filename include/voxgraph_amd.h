@@ -1509,9 +1509,11 @@ VGX_API int vgx_map_file_write(const char* path, int32_t format, double voxel_si
  * 4-DoF poses {x, y, z, yaw} of the graph's nodes, the registration constraints evaluated by a vgx_reg_batch, the
  * relative-pose constraints (odometry, loop closures, heights: RelativePoseCostFunction,
  * relative_pose_cost_function_inl.h:8-70) on the host in f64, and the damped normal equations assembled, factorised
- * (dense Cholesky) and solved on the device in f64.  No robust loss (the reference passes none, constraint.h:34), no
- * ordering, no sparsity: the reduced matrix is DENSE, (4 x free nodes)^2 doubles twice over -- more than 4096 free
- * nodes are refused with VGX_ERR_UNSUPPORTED (4 GiB at the limit).
+ * (Cholesky) and solved on the device in f64.  No robust loss (the reference passes none, constraint.h:34).  Two linear
+ * solvers.  The default, VGX_LINEAR_SOLVER_DENSE, has no ordering and no sparsity: the reduced matrix is DENSE,
+ * (4 x free nodes)^2 doubles twice over -- more than 4096 free nodes are refused with VGX_ERR_UNSUPPORTED (4 GiB at the
+ * limit).  VGX_LINEAR_SOLVER_TILE_SPARSE stores and factorises the 64 x 64 tiles that are structurally non-zero alone
+ * and has no such limit ("Pose graph: the tile-sparse solver" below).
  *
  * THE LOOP (what harness/lm.py restates for Ceres' trust-region minimiser).  Per iteration, at the accepted poses x
  * with cost, gradient g and Gauss-Newton matrix H over the free variables in ascending node order:
@@ -1666,6 +1668,102 @@ VGX_API int vgx_pose_graph_covariance(vgx_pose_graph graph, const double* poses 
  * vgx_dense_spd_solve returns for column c of B.  VGX_ERR_NOT_POSITIVE_DEFINITE as there (X and L then unspecified). */
 VGX_API int vgx_dense_spd_solve_many(vgx_ctx ctx, int32_t n, const double* A, int32_t m,
                                      const double* B /* [n][m] */, double* X /* [n][m] */, double* L /* nullable */);
+
+/* ---- Pose graph: the tile-sparse solver ------------------------------------ */
+/* The reference hands its problem to SPARSE_SCHUR (pose_graph.cpp:97).  VGX_LINEAR_SOLVER_TILE_SPARSE is the same
+ * right-looking 64-wide-panel Cholesky over a tile table: H and A / L are arrays of 64 x 64 f64 tiles (32 KiB each,
+ * row-major inside a tile, 16 nodes per tile), and a tile that is structurally zero in L is never stored, read or updated.
+ *
+ * STRUCTURE (host, made with the assembly's lists: whenever the constraints changed or registration is switched off
+ * or on).  The block graph has one vertex per free node and an edge per registration constraint and per relative-pose
+ * edge between two free nodes.  Tile (I, J) of H is stored when some 4x4 block of it is touched -- a joined pair at
+ * positions a, b with a / 16 == I, b / 16 == J -- and every diagonal tile is.  L's tiles are H's lower ones plus the
+ * symbolic fill at tile granularity: K ascending, every I >= J > K with (I, K) and (J, K) stored adds (I, J).  Per
+ * panel K: its stored tiles below the diagonal, and the update triples (target (I, J), sources (I, K), (J, K)).
+ *
+ * ORDERING decides the fill.  VGX_ORDER_NATURAL: the free nodes ascending.  VGX_ORDER_RCM: reverse Cuthill-McKee on
+ * the block graph, deterministic -- components in ascending order of their lowest node, each started at its
+ * minimum-degree node (ties: the lowest index), breadth-first, a node's new neighbours appended by ascending (degree,
+ * index), the whole sequence reversed.  VGX_ORDER_GIVEN: the caller's permutation, permutation[p] = the free node (its
+ * index among the free nodes) at position p.  With an order P other than natural the system solved is P H P^T: g goes
+ * in permuted, the step and H step come out in ascending node order, and the host's dot products and norms stay in
+ * ascending node order.
+ *
+ * THE ORDER CONTRACT, extended.  Assembly: the same lists, sources and order, stored at (tile, in-tile) addresses.
+ * Cholesky: every STORED element keeps the history a_ij <- a_ij - l_ik l_jk for k ascending, then one division or one
+ * sqrt; the only terms left out are products with an exact zero factor (a tile not stored).  So the factor EQUALS the
+ * dense solver's on P H P^T (tests/pose_graph_sparse_ref.py restates it bit for bit); it can differ in the sign of a
+ * zero alone: the dense -0.0 - (-0.0) is +0.0 where the sparse solver leaves -0.0.  Substitutions: after a panel's
+ * triangle only the rows (forward) / columns (backward) of the stored tiles are updated, the per-element k order
+ * unchanged.  H step: per row of P H P^T, ascending columns over the row's stored tiles, from 0.0.  A fill tile starts
+ * at +0.0.  A matrix with an inf or NaN off the diagonal is outside the equality (the dense solver multiplies it by
+ * the zeros this one skips); the bad-pivot rule itself is unchanged.
+ *
+ * LAUNCHES.  Three per panel (diagonal tile; the column's stored tiles; the panel's triples), one for a panel with an
+ * empty column below the diagonal; no workgroup waits for another, no cooperative launch, no captured graph.  A long
+ * graph is launch-bound: supernodes and level scheduling of independent panels are not done.
+ *
+ * LIMITS.  The free-node limit (4096) applies to the dense solver alone.  THE TILE CAP: the tiles of H and L together
+ * must fit the device memory that is free when the structure is made (hipMemGetInfo, less the graph's vectors), at
+ * 32 KiB a tile; a structure over it is refused with VGX_ERR_UNSUPPORTED by the call that makes the lists
+ * (vgx_pose_graph_optimize), the error text naming both figures.  The cap is taken at that moment: on a device that
+ * other processes allocate from, a structure accepted once can be refused the next time the lists are made, and the
+ * reverse.  At most 2^27 free nodes.  The host lists and the structure are sized by the graph: out of host memory is
+ * VGX_ERR_NOMEM from the same calls (and from vgx_pose_graph_tile_pattern and vgx_block_spd_solve).
+ * vgx_pose_graph_covariance keeps the DENSE factor and its limit whatever the solver setting: on a graph with more than
+ * 4096 free nodes it returns VGX_ERR_UNSUPPORTED, `covariance` untouched.  Selected inversion on the sparse factor is
+ * not done.  vgx_pose_graph_download_system in sparse mode returns H dense, in ascending node order, when
+ * 4 x free nodes <= 16384; beyond, VGX_ERR_UNSUPPORTED with g still delivered. */
+#define VGX_LINEAR_SOLVER_DENSE 0
+#define VGX_LINEAR_SOLVER_TILE_SPARSE 1
+#define VGX_ORDER_NATURAL 0
+#define VGX_ORDER_RCM 1
+#define VGX_ORDER_GIVEN 2
+typedef struct vgx_pose_graph_structure_stats {
+  int32_t n_free_variables;   /* 4 x free nodes */
+  int32_t n_panels;           /* tile rows */
+  int32_t n_launches;         /* per factorisation */
+  int32_t reserved;
+  int64_t n_h_tiles;          /* stored tiles of H (both triangles) */
+  int64_t n_l_tiles;          /* stored tiles of L: H's lower ones and the fill */
+  int64_t n_update_triples;
+  int64_t bytes;              /* device bytes of the tiles and the lists */
+} vgx_pose_graph_structure_stats;
+/* Allowed between solves.  permutation: [free nodes] for VGX_ORDER_GIVEN (copied), ignored otherwise; the dense solver
+ * ignores the ordering.  VGX_ERR_INVALID: an unknown solver or ordering, a permutation that is NULL or not one;
+ * VGX_ERR_UNSUPPORTED: the dense solver on a graph with more than 4096 free nodes.  A refused call changes nothing. */
+VGX_API int vgx_pose_graph_set_linear_solver(vgx_pose_graph graph, int32_t solver, int32_t ordering,
+                                             const int32_t* permutation /* [free nodes] or NULL */);
+/* vgx_pose_graph_create with the solver chosen at creation.  vgx_pose_graph_create makes a DENSE graph and keeps
+ * refusing more than 4096 free nodes; a graph past that limit is created here with VGX_LINEAR_SOLVER_TILE_SPARSE. */
+VGX_API int vgx_pose_graph_create_with_solver(vgx_ctx ctx, int32_t n_nodes, const int32_t* constant /* or NULL */,
+                                              int32_t solver, int32_t ordering, const int32_t* permutation,
+                                              vgx_pose_graph* out);
+/* the structure in use; valid once the tile-sparse solver has made its lists (a solve since the last change of the
+ * constraints or the solver), VGX_ERR_INVALID before */
+VGX_API int vgx_pose_graph_structure(vgx_pose_graph graph, vgx_pose_graph_structure_stats* stats);
+/* the order in use, permutation_out [free nodes]: position -> free node.  The identity for the dense solver.
+ * VGX_ORDER_RCM is made with the lists: VGX_ERR_INVALID before the first solve. */
+VGX_API int vgx_pose_graph_order(vgx_pose_graph graph, int32_t* permutation_out);
+/* The structure alone, on the host: no context, no HIP call.  pairs [n_pairs][2]: the joined free nodes (indices among
+ * the free nodes).  permutation: for VGX_ORDER_GIVEN.  permutation_out (nullable) [n_free_nodes]: the order; tiles
+ * (nullable when capacity == 0) [capacity][2]: the first `capacity` tiles of L as (row, column), sorted by (column,
+ * row); *n_tiles (nullable): their number.  VGX_ERR_INVALID: n_free_nodes < 1, a pair out of range, an unknown
+ * ordering, a permutation that is not one.  VGX_ERR_NOMEM: out of host memory. */
+VGX_API int vgx_pose_graph_tile_pattern(int32_t n_free_nodes, int32_t n_pairs, const int32_t* pairs, int32_t ordering,
+                                        const int32_t* permutation, int32_t* permutation_out, int32_t capacity,
+                                        int32_t* tiles, int32_t* n_tiles);
+/* The same kernels on a caller's matrix, vgx_dense_spd_solve's sibling: A symmetric positive definite of 4 x
+ * n_block_rows unknowns, given as the 4x4 blocks (row-major values[k], at block row bi[k], block column bj[k]) of its
+ * LOWER triangle (of a diagonal block the lower triangle is read); blocks not given are zero.  Natural order.  b and x
+ * host [4 n_block_rows].  stats nullable (n_h_tiles: the tiles the blocks touch).  tile_index (nullable)
+ * [n_l_tiles][2] = (row, column) of the factor's tiles, tile_values (nullable) [n_l_tiles][4096] their values, zeros
+ * above the diagonal and past the matrix; size them with vgx_pose_graph_tile_pattern.  VGX_ERR_INVALID: a block out of
+ * range, above the diagonal or given twice.  VGX_ERR_UNSUPPORTED: the tile cap.  VGX_ERR_NOT_POSITIVE_DEFINITE as for
+ * vgx_dense_spd_solve. */
+VGX_API int vgx_block_spd_solve(vgx_ctx ctx, int32_t n_block_rows, int32_t nnz, const int32_t* bi, const int32_t* bj,
+                                const double* values /* [nnz][16] */, const double* b, double* x,
+                                vgx_pose_graph_structure_stats* stats, int32_t* tile_index, double* tile_values);
 
 #ifdef __cplusplus
 }

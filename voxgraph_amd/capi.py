@@ -163,6 +163,16 @@ class PoseGraphIteration(C.Structure):
                 ("step_norm", C.c_double), ("accepted", C.c_int32), ("factorization_failed", C.c_int32)]
 
 
+class PoseGraphStructureStats(C.Structure):
+    _fields_ = [("n_free_variables", C.c_int32), ("n_panels", C.c_int32), ("n_launches", C.c_int32), ("reserved", C.c_int32),
+                ("n_h_tiles", C.c_int64), ("n_l_tiles", C.c_int64), ("n_update_triples", C.c_int64), ("bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+LINEAR_SOLVER_DENSE, LINEAR_SOLVER_TILE_SPARSE = 0, 1
+ORDER_NATURAL, ORDER_RCM, ORDER_GIVEN = 0, 1, 2
 CONVERGENCE, NO_CONVERGENCE, FAILURE = 0, 1, 2      # ceres::TerminationType
 (TERMINATION_PARAMETER_TOLERANCE, TERMINATION_FUNCTION_TOLERANCE, TERMINATION_GRADIENT_TOLERANCE, TERMINATION_MAX_ITERATIONS,
  TERMINATION_MAX_SOLVER_TIME, TERMINATION_NO_FREE_NODES) = range(6)
@@ -370,6 +380,13 @@ SIGNATURES = {
     "vgx_dense_spd_solve": (C.c_int, [vp, C.c_int32, f64p, f64p, f64p, f64p]),
     "vgx_pose_graph_covariance": (C.c_int, [vp, f64p, C.c_int32, C.c_int32, i32p, f64p]),
     "vgx_dense_spd_solve_many": (C.c_int, [vp, C.c_int32, f64p, C.c_int32, f64p, f64p, f64p]),
+    "vgx_pose_graph_set_linear_solver": (C.c_int, [vp, C.c_int32, C.c_int32, i32p]),
+    "vgx_pose_graph_create_with_solver": (C.c_int, [vp, C.c_int32, i32p, C.c_int32, C.c_int32, i32p, C.POINTER(vp)]),
+    "vgx_pose_graph_structure": (C.c_int, [vp, C.POINTER(PoseGraphStructureStats)]),
+    "vgx_pose_graph_order": (C.c_int, [vp, i32p]),
+    "vgx_pose_graph_tile_pattern": (C.c_int, [C.c_int32, C.c_int32, i32p, C.c_int32, i32p, i32p, C.c_int32, i32p, i32p]),
+    "vgx_block_spd_solve": (C.c_int, [vp, C.c_int32, C.c_int32, i32p, i32p, f64p, f64p, f64p, C.POINTER(PoseGraphStructureStats),
+                                      i32p, f64p]),
 }
 
 # every symbol include/voxgraph_amd_bench.h declares (libvoxgraph_amd_bench.so: test and benchmark tooling)
@@ -1098,15 +1115,86 @@ def dense_spd_solve_many(ctx, A, B, want_factor=False):
     return X, L
 
 
-class PoseGraph:
-    """vgx_pose_graph: PoseGraph::optimize() on the device (include/voxgraph_amd.h, "Pose graph: the solve")."""
+def tile_pattern(n_free_nodes, pairs, ordering=ORDER_NATURAL, permutation=None):
+    """vgx_pose_graph_tile_pattern (host only, no context) -> (order [n_free_nodes], L tiles [n][2] as (row, column) sorted
+    by (column, row)); pairs: the joined free nodes.  Raises ValueError where the library answers VGX_ERR_INVALID."""
+    lib = load()
+    pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    perm = None if permutation is None else np.ascontiguousarray(permutation, np.int32)
+    if perm is not None and len(perm) != n_free_nodes:
+        raise ValueError("tile_pattern: the permutation's length is not n_free_nodes")
+    order = np.zeros(max(int(n_free_nodes), 1), np.int32)
+    n = C.c_int32()
+    args = (int(n_free_nodes), len(pr), _ptr(pr, i32p) if len(pr) else None, int(ordering), _ptr(perm, i32p))
+    if lib.vgx_pose_graph_tile_pattern(*args, _ptr(order, i32p), 0, None, C.byref(n)) != OK:
+        raise ValueError("vgx_pose_graph_tile_pattern refused its input")
+    tiles = np.zeros((n.value, 2), np.int32)
+    if lib.vgx_pose_graph_tile_pattern(*args, None, n.value, _ptr(tiles, i32p), None) != OK:
+        raise ValueError("vgx_pose_graph_tile_pattern refused its input")
+    return order[:n_free_nodes], tiles
 
-    def __init__(self, ctx, n_nodes, constant=None):
+
+def block_spd_solve(ctx, n_block_rows, bi, bj, values, b, want_factor=True):
+    """vgx_block_spd_solve -> (x, stats dict, tile_index [n][2] or None, tile_values [n][64][64] or None); raises as
+    dense_spd_solve does"""
+    bi, bj = np.ascontiguousarray(bi, np.int32), np.ascontiguousarray(bj, np.int32)
+    values, b = _f64(values), _f64(b)
+    assert values.size == 16 * len(bi) == 16 * len(bj) and len(b) == 4 * n_block_rows
+    x = np.zeros(4 * n_block_rows)
+    stats = PoseGraphStructureStats()
+    index = tiles = None
+    if want_factor:
+        pairs = np.stack([bi, bj], 1)
+        inside = bool(len(pairs)) and pairs.min() >= 0 and pairs.max() < n_block_rows
+        n_tiles = len(tile_pattern(n_block_rows, pairs)[1]) if inside else 1
+        index, tiles = np.zeros((n_tiles, 2), np.int32), np.zeros((n_tiles, 64, 64))
+    ctx.check(ctx.lib.vgx_block_spd_solve(ctx.h, int(n_block_rows), len(bi), _ptr(bi, i32p), _ptr(bj, i32p), _ptr(values, f64p),
+                                          _ptr(b, f64p), _ptr(x, f64p), C.byref(stats), _ptr(index, i32p), _ptr(tiles, f64p)))
+    return x, stats.as_dict(), index, tiles
+
+
+class PoseGraph:
+    """vgx_pose_graph: PoseGraph::optimize() on the device (include/voxgraph_amd.h, "Pose graph: the solve").
+    linear_solver: LINEAR_SOLVER_DENSE (None: vgx_pose_graph_create) or LINEAR_SOLVER_TILE_SPARSE with an ordering."""
+
+    def __init__(self, ctx, n_nodes, constant=None, linear_solver=None, ordering=ORDER_NATURAL, permutation=None):
         self.ctx, self.n_nodes = ctx, int(n_nodes)
         flags = None if constant is None else np.ascontiguousarray(constant, np.int32)
         h = vp()
-        ctx.check(ctx.lib.vgx_pose_graph_create(ctx.h, self.n_nodes, _ptr(flags, i32p), C.byref(h)))
+        if linear_solver is None:
+            ctx.check(ctx.lib.vgx_pose_graph_create(ctx.h, self.n_nodes, _ptr(flags, i32p), C.byref(h)))
+        else:
+            perm = None if permutation is None else np.ascontiguousarray(permutation, np.int32)
+            ctx.check(ctx.lib.vgx_pose_graph_create_with_solver(ctx.h, self.n_nodes, _ptr(flags, i32p), int(linear_solver),
+                                                                int(ordering), _ptr(perm, i32p), C.byref(h)))
         self.h = h
+        self.n_free = self.n_nodes - 1 if constant is None else int(np.count_nonzero(np.asarray(constant) == 0))
+
+    def set_linear_solver(self, solver, ordering=ORDER_NATURAL, permutation=None):
+        perm = None if permutation is None else np.ascontiguousarray(permutation, np.int32)
+        if perm is not None and len(perm) != self.n_free:
+            raise VgxError(ERR_INVALID, "set_linear_solver: the permutation's length is not the number of free nodes")
+        self.ctx.check(self.ctx.lib.vgx_pose_graph_set_linear_solver(self.h, int(solver), int(ordering), _ptr(perm, i32p)))
+
+    def structure(self):
+        """vgx_pose_graph_structure -> dict"""
+        stats = PoseGraphStructureStats()
+        self.ctx.check(self.ctx.lib.vgx_pose_graph_structure(self.h, C.byref(stats)))
+        return stats.as_dict()
+
+    def order(self):
+        """vgx_pose_graph_order -> [free nodes]: position -> free node"""
+        out = np.zeros(max(self.n_free, 1), np.int32)
+        self.ctx.check(self.ctx.lib.vgx_pose_graph_order(self.h, _ptr(out, i32p)))
+        return out[:self.n_free]
+
+    def download_gradient(self):
+        """-> g [N] of the last full evaluation (the call vgx_pose_graph_download_system(graph, NULL, NULL, g))"""
+        n = C.c_int32()
+        self.ctx.check(self.ctx.lib.vgx_pose_graph_download_system(self.h, C.byref(n), None, None))
+        g = np.zeros(n.value)
+        self.ctx.check(self.ctx.lib.vgx_pose_graph_download_system(self.h, None, None, _ptr(g, f64p)))
+        return g
 
     def set_registration(self, batch):
         self.ctx.check(self.ctx.lib.vgx_pose_graph_set_registration(self.h, batch.h if batch is not None else None))

@@ -71,6 +71,36 @@ class GpuPoseGraph {
   ~GpuPoseGraph() { Release(); }
 
   vgx_pose_graph_options& options() { return options_; }
+  // The linear solver of the next solves (include/voxgraph_amd.h, "Pose graph: the tile-sparse solver"):
+  // VGX_LINEAR_SOLVER_DENSE (the default, 4096 free nodes at the most) or VGX_LINEAR_SOLVER_TILE_SPARSE with
+  // VGX_ORDER_NATURAL or VGX_ORDER_RCM.  (VGX_ORDER_GIVEN is a permutation of the free nodes in the order they were
+  // added: `permutation` is copied.)  getEdgeCovarianceMap keeps the dense factor and its limit.
+  // On a graph that stands (no node or constraint changed since the last solve) the setting goes to the live handle
+  // (vgx_pose_graph_set_linear_solver: the registration batch is kept) and a refusal is returned at once, nothing
+  // changed; otherwise it is kept for the next optimize(), which then reports a refusal.
+  int setLinearSolver(int32_t solver, int32_t ordering = VGX_ORDER_NATURAL, const std::vector<int32_t>& permutation = {}) {
+    if (graph_ && !dirty_) {
+      size_t n_free = 0;
+      for (int32_t c : constant_) n_free += c == 0;
+      if (ordering == VGX_ORDER_GIVEN && permutation.size() != n_free) {
+        Fail("setLinearSolver: the permutation's length is not the number of free nodes");
+        return VGX_ERR_INVALID;
+      }
+      const int rc = vgx_pose_graph_set_linear_solver(graph_, solver, ordering, permutation.empty() ? nullptr : permutation.data());
+      if (rc != VGX_OK) return Status(rc);
+    }
+    solver_ = solver;
+    ordering_ = ordering;
+    permutation_ = permutation;
+    return VGX_OK;
+  }
+  // vgx_pose_graph_structure of the last solve; false before one, or with the dense solver
+  bool getStructure(vgx_pose_graph_structure_stats* stats) {
+    if (!graph_ || !stats) return Fail("getStructure: no solve yet or NULL stats");
+    const int rc = vgx_pose_graph_structure(graph_, stats);
+    if (rc != VGX_OK) Status(rc);
+    return rc == VGX_OK;
+  }
 
   // nodes: submaps and reference frames share one numbering, in the order they were added
   int addSubmapNode(int64_t submap_id, const Pose& pose, bool constant) { return AddNode(submap_index_, submap_id, pose, constant); }
@@ -205,7 +235,14 @@ class GpuPoseGraph {
   int Build() {
     if (!dirty_ && graph_) return VGX_OK;
     Release();
-    int rc = vgx_pose_graph_create(ctx_, static_cast<int32_t>(constant_.size()), constant_.data(), &graph_);
+    size_t n_free = 0;
+    for (int32_t c : constant_) n_free += c == 0;
+    if (ordering_ == VGX_ORDER_GIVEN && permutation_.size() != n_free) {
+      Fail("setLinearSolver: the permutation's length is not the number of free nodes");
+      return VGX_ERR_INVALID;
+    }
+    int rc = vgx_pose_graph_create_with_solver(ctx_, static_cast<int32_t>(constant_.size()), constant_.data(), solver_, ordering_,
+                                               permutation_.empty() ? nullptr : permutation_.data(), &graph_);
     if (rc != VGX_OK) return Status(rc);
     if (!regs_.empty()) {
       rc = vgx_reg_batch_create(ctx_, static_cast<int32_t>(regs_.size()), regs_.data(), pairs_.data(), nullptr,
@@ -238,6 +275,8 @@ class GpuPoseGraph {
   vgx_pose_graph graph_ = nullptr;
   vgx_reg_batch batch_ = nullptr;
   vgx_pose_graph_options options_;
+  int32_t solver_ = VGX_LINEAR_SOLVER_DENSE, ordering_ = VGX_ORDER_NATURAL;
+  std::vector<int32_t> permutation_;
   std::map<int64_t, int32_t> submap_index_, frame_index_;
   std::vector<int32_t> constant_;
   std::vector<double> poses_;

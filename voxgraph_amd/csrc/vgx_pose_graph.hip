@@ -1,14 +1,17 @@
 // Pose graph: the solve (include/voxgraph_amd.h).  Levenberg-Marquardt over the 4-DoF node poses: registration constraints
 // through a vgx_reg_batch, relative-pose edges on the host in f64, and the reduced normal equations assembled, damped,
-// factorised (dense right-looking Cholesky, 64-wide panels) and solved on the device in f64.  Every number follows the
-// order contract of the header: built with -ffp-contract=off, one rounded multiply and one rounded subtract at a time.
+// factorised (right-looking Cholesky, 64-wide panels: dense, or over the stored 64 x 64 tiles alone) and solved on the
+// device in f64.  Every number follows the order contract of the header: built with -ffp-contract=off, one rounded
+// multiply and one rounded subtract at a time.
 #include <chrono>
 #include <cmath>
 #include <cstring>
 #include <map>
 #include <new>
+#include <set>
 
 #include "vgx_internal.h"
+#include "vgx_tile_pattern.h"
 
 using namespace vgx;
 
@@ -468,6 +471,305 @@ int queue_solve_many(vgx_ctx ctx, const double* L, int n, double* d_X, int m, co
 }
 
 // ---------------------------------------------------------------------------
+// the tile-sparse solver: H and A / L as arrays of 64 x 64 tiles (row-major inside a tile), the structure of
+// vgx_tile_pattern.h.  A tile that is structurally zero in L is not stored, read or updated; every stored element has
+// the history of the dense kernels above less the products with an exact zero factor.
+// ---------------------------------------------------------------------------
+constexpr int kTileDoubles = kPanel * kPanel;
+static_assert(kPanel == kTile, "one tile per panel");
+
+// the 4x4 block of record b lies in tile block_tile[b] of H; bi / bj are positions in the order in use
+__global__ void pg_assemble_blocks_tiled_kernel(const BlockRecord* __restrict__ blocks, const int32_t* __restrict__ block_tile, int n_blocks,
+                                                const int32_t* __restrict__ items, const double* __restrict__ fused,
+                                                const double* __restrict__ edge, double* __restrict__ Ht) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_blocks * 16) return;
+  const BlockRecord B = blocks[t >> 4];
+  const int e = t & 15, r = e >> 2, c = e & 3;
+  double acc = 0.0;
+  for (int k = 0; k < B.count; ++k) {
+    const int32_t it = items[B.first + k];
+    const double* src = (it & 2) ? edge : fused;
+    acc = acc + src[(size_t)(it >> 2) + ((it & 1) ? c * 4 + r : e)];
+  }
+  Ht[(size_t)block_tile[t >> 4] * kTileDoubles + (4 * (B.bi % kNodesPerTile) + r) * kPanel + 4 * (B.bj % kNodesPerTile) + c] = acc;
+}
+// A's tiles start as copies of H's; a tile of pure fill starts at +0.0
+__global__ __launch_bounds__(256) void pg_tiles_from_h_kernel(const double* __restrict__ Ht, double* __restrict__ At,
+                                                              const int32_t* __restrict__ l_from_h) {
+  const int32_t src = l_from_h[blockIdx.x];
+  double2* dst = reinterpret_cast<double2*>(At + (size_t)blockIdx.x * kTileDoubles);
+  const double2* from = reinterpret_cast<const double2*>(Ht + (size_t)(src < 0 ? 0 : src) * kTileDoubles);
+  for (int e = threadIdx.x; e < kTileDoubles / 2; e += 256) dst[e] = src < 0 ? make_double2(0.0, 0.0) : from[e];
+}
+__global__ void pg_damp_tiled_kernel(const double* __restrict__ Ht, double* __restrict__ At, const int32_t* __restrict__ h_diag,
+                                     const int32_t* __restrict__ col_first, int nf, double radius) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nf) return;
+  const int K = i / kPanel, e = (i % kPanel) * (kPanel + 1);
+  const double h = Ht[(size_t)h_diag[K] * kTileDoubles + e];
+  const double d2 = h < 1e-6 ? 1e-6 : (h > 1e32 ? 1e32 : h);
+  At[(size_t)col_first[K] * kTileDoubles + e] = h + d2 / radius;
+}
+
+// 1. the diagonal tile: pg_chol_diag_kernel on the tile's pointer (n = 64, k0 = 0)
+// 2. the stored tiles of column K below it, one per workgroup: tiles first + 1 + blockIdx.x of the list
+__global__ __launch_bounds__(64) void pg_chol_panel_tiled_kernel(double* __restrict__ At, int first, const int32_t* __restrict__ l_row,
+                                                                 int n, const int* __restrict__ flag) {
+  if (*flag) return;
+  __shared__ double Lt[kPanel * (kPanel + 1) / 2];
+  __shared__ double R[kPanel * (kPanel + 1)];
+  const int t = threadIdx.x;
+  const int tile = first + 1 + blockIdx.x;
+  const double* D = At + (size_t)first * kTileDoubles;
+  double* T = At + (size_t)tile * kTileDoubles;
+  const int rows = min(kPanel, n - l_row[tile] * kPanel);
+  for (int r = 0; r < kPanel; ++r)
+    if (t <= r) Lt[r * (r + 1) / 2 + t] = D[r * kPanel + t];
+  for (int r = 0; r < kPanel; ++r) R[r * (kPanel + 1) + t] = r < rows ? T[r * kPanel + t] : 0.0;
+  __syncthreads();
+  if (t < rows) {
+    double* row = R + t * (kPanel + 1);
+    for (int j = 0; j < kPanel; ++j) {
+      const double x = row[j] / Lt[j * (j + 1) / 2 + j];
+      row[j] = x;
+      for (int c = j + 1; c < kPanel; ++c) row[c] = row[c] - x * Lt[c * (c + 1) / 2 + j];
+    }
+  }
+  __syncthreads();
+  for (int r = 0; r < rows; ++r) T[r * kPanel + t] = R[r * (kPanel + 1) + t];
+}
+// 3. the update triples of panel K, one per workgroup: pg_chol_trailing_kernel's micro-tile, accumulators that start
+// from the stored value, the subtract inside the k loop
+__global__ __launch_bounds__(256) void pg_chol_trailing_tiled_kernel(double* __restrict__ At, const TileTriple* __restrict__ triples,
+                                                                    const int* __restrict__ flag) {
+  if (*flag) return;
+  __shared__ alignas(16) double PI[kChunk * kStride];
+  __shared__ alignas(16) double PJ[kChunk * kStride];
+  const int tid = threadIdx.x;
+  const TileTriple tr = triples[blockIdx.x];
+  double* T = At + (size_t)tr.target * kTileDoubles;
+  const double* SI = At + (size_t)tr.source_i * kTileDoubles;
+  const double* SJ = At + (size_t)tr.source_j * kTileDoubles;
+  const int rows_i = tr.rows & 255, rows_j = (tr.rows >> 8) & 255;
+  const bool diagonal = (tr.rows >> 16) != 0;
+  const int ty = tid >> 4, tx = tid & 15;
+  double acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int row = ty * 4 + a, col = tx * 4 + b;
+      acc[a][b] = (row < rows_i && (!diagonal || col <= row)) ? T[row * kPanel + col] : 0.0;
+    }
+  for (int kc = 0; kc < kPanel; kc += kChunk) {
+    __syncthreads();
+    {
+      const int k = tid & (kChunk - 1);
+      for (int r = tid / kChunk; r < kPanel; r += 256 / kChunk) {
+        PI[k * kStride + r] = r < rows_i ? SI[r * kPanel + kc + k] : 0.0;
+        PJ[k * kStride + r] = r < rows_j ? SJ[r * kPanel + kc + k] : 0.0;
+      }
+    }
+    __syncthreads();
+    for (int k = 0; k < kChunk; ++k) {
+      const double2 a01 = *reinterpret_cast<const double2*>(&PI[k * kStride + ty * 4]);
+      const double2 a23 = *reinterpret_cast<const double2*>(&PI[k * kStride + ty * 4 + 2]);
+      const double2 b01 = *reinterpret_cast<const double2*>(&PJ[k * kStride + tx * 4]);
+      const double2 b23 = *reinterpret_cast<const double2*>(&PJ[k * kStride + tx * 4 + 2]);
+      const double av[4] = {a01.x, a01.y, a23.x, a23.y};
+      const double bv[4] = {b01.x, b01.y, b23.x, b23.y};
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = acc[a][b] - av[a] * bv[b];
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int row = ty * 4 + a, col = tx * 4 + b;
+      if (row < rows_i && (!diagonal || col <= row)) T[row * kPanel + col] = acc[a][b];
+    }
+}
+
+// the substitutions of pg_forward_kernel / pg_backward_kernel: after a panel's triangle the rows of the column's
+// stored tiles alone (forward), the columns of the row's stored tiles alone (backward); 16 tiles per pass, a row or a
+// column per thread, the same k order
+__global__ __launch_bounds__(1024) void pg_forward_tiled_kernel(const double* __restrict__ Lt_, const int32_t* __restrict__ col_first,
+                                                               const int32_t* __restrict__ l_row, int n, double* __restrict__ b) {
+  __shared__ double Lt[kPanel * (kPanel + 1)];
+  __shared__ double yb[kPanel];
+  const int tid = threadIdx.x;
+  const int n_panels = (n + kPanel - 1) / kPanel;
+  for (int K = 0; K < n_panels; ++K) {
+    const int k0 = K * kPanel, w = min(kPanel, n - k0);
+    const int first = col_first[K], n_below = col_first[K + 1] - first - 1;
+    const double* D = Lt_ + (size_t)first * kTileDoubles;
+    for (int e = tid; e < kPanel * kPanel; e += 1024) {
+      const int i = e >> 6, j = e & 63;
+      Lt[i * (kPanel + 1) + j] = (i < w && j <= i) ? D[i * kPanel + j] : 1.0;
+    }
+    __syncthreads();
+    if (tid < 64) {
+      double y = tid < w ? b[k0 + tid] : 0.0;
+      for (int j = 0; j < w; ++j) {
+        if (tid == j) y = y / Lt[j * (kPanel + 1) + j];
+        const double yj = __shfl(y, j);
+        if (tid > j) y = y - Lt[tid * (kPanel + 1) + j] * yj;
+      }
+      yb[tid] = y;
+      if (tid < w) b[k0 + tid] = y;
+    }
+    __syncthreads();
+    for (int q = tid >> 6; q < n_below; q += 16) {
+      const int tile = first + 1 + q, r = tid & 63, i = l_row[tile] * kPanel + r;
+      if (i < n) {
+        double acc = b[i];
+        const double* row = Lt_ + (size_t)tile * kTileDoubles + r * kPanel;
+        for (int k = 0; k < w; ++k) acc = acc - row[k] * yb[k];
+        b[i] = acc;
+      }
+    }
+    __syncthreads();
+  }
+}
+__global__ __launch_bounds__(1024) void pg_backward_tiled_kernel(const double* __restrict__ Lt_, const int32_t* __restrict__ col_first,
+                                                                const int32_t* __restrict__ row_first, const int32_t* __restrict__ row_tile,
+                                                                const int32_t* __restrict__ row_col, int n, double* __restrict__ b) {
+  __shared__ double Lt[kPanel * (kPanel + 1)];
+  __shared__ double xb[kPanel];
+  const int tid = threadIdx.x;
+  for (int K = (n - 1) / kPanel; K >= 0; --K) {
+    const int k0 = K * kPanel, w = min(kPanel, n - k0);
+    const double* D = Lt_ + (size_t)col_first[K] * kTileDoubles;
+    for (int e = tid; e < kPanel * kPanel; e += 1024) {
+      const int i = e >> 6, j = e & 63;
+      Lt[i * (kPanel + 1) + j] = (i < w && j <= i) ? D[i * kPanel + j] : 1.0;
+    }
+    __syncthreads();
+    if (tid < 64) {
+      double y = tid < w ? b[k0 + tid] : 0.0;
+      for (int j = w - 1; j >= 0; --j) {
+        if (tid == j) y = y / Lt[j * (kPanel + 1) + j];
+        const double xj = __shfl(y, j);
+        if (tid < j) y = y - Lt[j * (kPanel + 1) + tid] * xj;
+      }
+      xb[tid] = y;
+      if (tid < w) b[k0 + tid] = y;
+    }
+    __syncthreads();
+    for (int q = row_first[K] + (tid >> 6); q < row_first[K + 1]; q += 16) {
+      const int c = tid & 63, i = row_col[q] * kPanel + c;  // (a column left of the diagonal tile: i < n)
+      const double* T = Lt_ + (size_t)row_tile[q] * kTileDoubles;
+      double acc = b[i];
+      for (int k = w - 1; k >= 0; --k) acc = acc - T[k * kPanel + c] * xb[k];
+      b[i] = acc;
+    }
+    __syncthreads();
+  }
+}
+// the right-hand side into the order in use: x[4 p + k] = g[4 order[p] + k]
+__global__ void pg_permute_kernel(const double* __restrict__ g, const int32_t* __restrict__ order, double* __restrict__ x, int nf) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nf) x[i] = g[4 * order[i >> 2] + (i & 3)];
+}
+// z <- -z (the step in the order in use, for H step), out = the step in ascending node order
+__global__ void pg_negate_permuted_kernel(double* __restrict__ z, const int32_t* __restrict__ order, double* __restrict__ out, int nf) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nf) return;
+  const double v = -z[i];
+  z[i] = v;
+  out[4 * order[i >> 2] + (i & 3)] = v;
+}
+// H step per row of the order in use: ascending columns over the row's stored tiles, from 0.0; out[nf + the row's
+// place in ascending node order]
+__global__ __launch_bounds__(64) void pg_matvec_tiled_kernel(const double* __restrict__ Ht, const int32_t* __restrict__ h_row_first,
+                                                            const int32_t* __restrict__ h_col, const double* __restrict__ step,
+                                                            const int32_t* __restrict__ order, double* __restrict__ out, int nf) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= nf) return;
+  const int I = r / kPanel;
+  double acc = 0.0;
+  for (int t = h_row_first[I]; t < h_row_first[I + 1]; ++t) {
+    const double* row = Ht + (size_t)t * kTileDoubles + (r % kPanel) * kPanel;
+    const int c0 = h_col[t] * kPanel, cn = min(kPanel, nf - c0);
+    for (int c = 0; c < cn; ++c) acc = acc + row[c] * step[c0 + c];
+  }
+  out[nf + 4 * order[r >> 2] + (r & 3)] = acc;
+}
+
+// the structure's lists on the device
+struct DeviceTiles {
+  DeviceArray<int32_t> col_first, l_row, row_first, row_tile, row_col, h_row_first, h_col, h_diag, l_from_h, order;
+  DeviceArray<TileTriple> triples;
+  size_t bytes = 0;  // of the lists
+};
+int upload_structure(vgx_ctx ctx, const TileStructure& S, DeviceTiles* d) {
+  d->bytes = 0;
+  auto up = [&](DeviceBuffer& buf, const void* src, size_t count, size_t size) {
+    static const int64_t zero[2] = {0, 0};
+    d->bytes += std::max<size_t>(1, count) * size;
+    return upload_new(ctx, buf, count ? src : zero, std::max<size_t>(1, count) * size);
+  };
+  int rc = up(d->col_first, S.col_first.data(), S.col_first.size(), 4);
+  if (rc == VGX_OK) rc = up(d->l_row, S.l_row.data(), S.l_row.size(), 4);
+  if (rc == VGX_OK) rc = up(d->row_first, S.row_first.data(), S.row_first.size(), 4);
+  if (rc == VGX_OK) rc = up(d->row_tile, S.row_tile.data(), S.row_tile.size(), 4);
+  if (rc == VGX_OK) rc = up(d->row_col, S.row_col.data(), S.row_col.size(), 4);
+  if (rc == VGX_OK) rc = up(d->h_row_first, S.h_row_first.data(), S.h_row_first.size(), 4);
+  if (rc == VGX_OK) rc = up(d->h_col, S.h_col.data(), S.h_col.size(), 4);
+  if (rc == VGX_OK) rc = up(d->h_diag, S.h_diag.data(), S.h_diag.size(), 4);
+  if (rc == VGX_OK) rc = up(d->l_from_h, S.l_from_h.data(), S.l_from_h.size(), 4);
+  if (rc == VGX_OK) rc = up(d->order, S.order.data(), S.order.size(), 4);
+  if (rc == VGX_OK) rc = up(d->triples, S.triples.data(), S.triples.size(), sizeof(TileTriple));
+  return rc;
+}
+// The tile cap: what the device has free when the structure is made, in 32 KiB tiles (hipMemGetInfo), less `reserve`
+// bytes for the graph's other arrays.  n_tiles over it: VGX_ERR_UNSUPPORTED.
+int check_tile_cap(vgx_ctx ctx, const char* who, size_t n_tiles, size_t held_bytes, size_t reserve) {
+  size_t free_bytes = 0, total = 0;
+  VGX_HIP(ctx, hipMemGetInfo(&free_bytes, &total));
+  free_bytes += held_bytes;  // (what the handle holds already is given back first)
+  const size_t cap = free_bytes > reserve ? (free_bytes - reserve) / (kTileDoubles * sizeof(double)) : 0;
+  if (n_tiles > cap || n_tiles >= ((size_t)1 << 31))
+    return set_error(ctx, VGX_ERR_UNSUPPORTED, std::string(who) + ": the tiles of H and L number " + std::to_string(n_tiles) +
+                                                   "; the tile cap (free device memory / 32 KiB per tile) is " + std::to_string(cap));
+  return VGX_OK;
+}
+// queues the factorisation over the tiles At: 3 launches per panel, 1 for a panel with nothing below its diagonal tile
+int queue_cholesky_tiled(vgx_ctx ctx, const TileStructure& S, const DeviceTiles& d, double* At, int n, int* d_flag) {
+  VGX_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(int), ctx->stream));
+  for (int K = 0; K < S.n_tile_rows; ++K) {
+    const int first = S.col_first[(size_t)K], below = S.col_first[(size_t)K + 1] - first - 1;
+    hipLaunchKernelGGL(pg_chol_diag_kernel, dim3(1), dim3(256), 0, ctx->stream, At + (size_t)first * kTileDoubles, kPanel, 0,
+                       S.rows_of(K), d_flag);
+    if (below > 0) {
+      hipLaunchKernelGGL(pg_chol_panel_tiled_kernel, dim3(below), dim3(64), 0, ctx->stream, At, first, d.l_row.get(), n, d_flag);
+      const int64_t t0 = S.triple_first[(size_t)K], nt = S.triple_first[(size_t)K + 1] - t0;
+      hipLaunchKernelGGL(pg_chol_trailing_tiled_kernel, dim3((unsigned)nt), dim3(256), 0, ctx->stream, At, d.triples.get() + t0, d_flag);
+    }
+  }
+  VGX_HIP(ctx, hipGetLastError());
+  return VGX_OK;
+}
+int queue_substitutions_tiled(vgx_ctx ctx, const DeviceTiles& d, const double* Lt, int n, double* d_x) {
+  hipLaunchKernelGGL(pg_forward_tiled_kernel, dim3(1), dim3(1024), 0, ctx->stream, Lt, d.col_first.get(), d.l_row.get(), n, d_x);
+  hipLaunchKernelGGL(pg_backward_tiled_kernel, dim3(1), dim3(1024), 0, ctx->stream, Lt, d.col_first.get(), d.row_first.get(),
+                     d.row_tile.get(), d.row_col.get(), n, d_x);
+  VGX_HIP(ctx, hipGetLastError());
+  return VGX_OK;
+}
+int block_spd_solve(vgx_ctx ctx, int32_t n_block_rows, int32_t nnz, const int32_t* bi, const int32_t* bj, const double* values,
+                    const double* b, double* x, vgx_pose_graph_structure_stats* stats, int32_t* tile_index, double* tile_values);
+int launches_per_factorisation(const TileStructure& S) {
+  int n = 0;
+  for (int K = 0; K < S.n_tile_rows; ++K) n += S.col_first[(size_t)K + 1] - S.col_first[(size_t)K] > 1 ? 3 : 1;
+  return n;
+}
+
+// ---------------------------------------------------------------------------
 // relative-pose edges, host, f64 (relative_pose_cost_function_inl.h:8-70 with analytic Jacobians)
 // ---------------------------------------------------------------------------
 double normalize_angle(double a) {
@@ -546,8 +848,16 @@ struct vgx_pose_graph_s {
   std::vector<vgx_pose_graph_edge> edges;
   std::mutex mu;             // one solve (or setter) at a time
   // the index lists of the assembly, rebuilt when the constraints changed or registration is switched off / on
-  bool lists_made = false, lists_with_reg = false;
+  bool lists_made = false, lists_with_reg = false, lists_sparse = false;
   int n_blocks = 0;
+  // the linear solver; with the tile-sparse one the structure of the lists, its device copy and the tiles of H and A / L
+  int32_t solver = VGX_LINEAR_SOLVER_DENSE, ordering = VGX_ORDER_NATURAL;
+  std::vector<int32_t> given_order;  // VGX_ORDER_GIVEN: position -> free node
+  TileStructure S;
+  DeviceTiles tiles;
+  DeviceArray<int32_t> d_block_tile;
+  DeviceArray<double> d_Ht, d_At;
+  size_t sparse_bytes = 0;
   DeviceArray<BlockRecord> d_blocks;
   DeviceArray<int32_t> d_block_items, d_grad_first, d_grad_items;
   // the system
@@ -577,18 +887,31 @@ void release_batch(vgx_pose_graph pg) {
 }
 
 // Index lists in the contract's order.  with_reg: the fused buffer's blocks take part.
-int make_lists(vgx_pose_graph pg, bool with_reg) {
+int make_lists_unguarded(vgx_pose_graph pg, bool with_reg, bool sparse) {
   vgx_ctx ctx = pg->ctx;
   const int n = pg->n_nodes, nfn = (int)pg->free_nodes.size();
   const vgx_reg_batch b = with_reg ? pg->batch : nullptr;
   const int m = b ? b->n : 0;
   if (vgx_reg_fused_size(n, m) >= (int64_t)1 << 29 || (int64_t)pg->edges.size() * kEdgeTermDoubles >= (int64_t)1 << 29)
     return set_error(ctx, VGX_ERR_UNSUPPORTED, "vgx_pose_graph_optimize: the constraint list is too long for the 32-bit index lists");
+  if (sparse) {  // the structure first: with an ordering the blocks sit at their positions in P H P^T
+    std::vector<int32_t> joined;
+    auto join = [&](int a, int bb) {
+      if (pg->pos[(size_t)a] < 0 || pg->pos[(size_t)bb] < 0) return;
+      joined.push_back(pg->pos[(size_t)a]);
+      joined.push_back(pg->pos[(size_t)bb]);
+    };
+    for (int c = 0; c < m; ++c) join(b->node_pair[2 * (size_t)c], b->node_pair[2 * (size_t)c + 1]);
+    for (const vgx_pose_graph_edge& e : pg->edges) join(e.a, e.b);
+    if (!build_tile_structure(nfn, (int64_t)(joined.size() / 2), joined.data(), pg->ordering, pg->given_order.data(), &pg->S))
+      return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_optimize: the ordering is not a permutation of the free nodes");
+  }
   std::map<std::pair<int32_t, int32_t>, std::vector<int32_t>> blocks;
   std::vector<std::vector<int32_t>> grad((size_t)nfn);
   auto add = [&](int node_r, int node_c, int64_t offset, int source, int transpose) {
-    const int32_t r = pg->pos[(size_t)node_r], c = pg->pos[(size_t)node_c];
+    int32_t r = pg->pos[(size_t)node_r], c = pg->pos[(size_t)node_c];
     if (r < 0 || c < 0) return;
+    if (sparse) r = pg->S.position[(size_t)r], c = pg->S.position[(size_t)c];
     blocks[{r, c}].push_back((int32_t)(offset << 2 | source << 1 | transpose));
   };
   if (b) {
@@ -614,8 +937,9 @@ int make_lists(vgx_pose_graph pg, bool with_reg) {
     if (pg->pos[(size_t)bb] >= 0) grad[(size_t)pg->pos[(size_t)bb]].push_back((int32_t)((base + 4) << 1 | 1));
   }
   std::vector<BlockRecord> records;
-  std::vector<int32_t> items, gfirst((size_t)nfn + 1, 0), gitems;
+  std::vector<int32_t> items, gfirst((size_t)nfn + 1, 0), gitems, block_tile;
   for (const auto& kv : blocks) {
+    if (sparse) block_tile.push_back(h_tile(pg->S, kv.first.first / kNodesPerTile, kv.first.second / kNodesPerTile));
     records.push_back({kv.first.first, kv.first.second, (int32_t)items.size(), (int32_t)kv.second.size()});
     items.insert(items.end(), kv.second.begin(), kv.second.end());
   }
@@ -626,7 +950,9 @@ int make_lists(vgx_pose_graph pg, bool with_reg) {
   if (items.empty()) items.push_back(0);
   if (gitems.empty()) gitems.push_back(0);
   if (records.empty()) records.push_back({0, 0, 0, 0});
+  if (block_tile.empty()) block_tile.push_back(0);
   pg->n_blocks = (int)blocks.size();
+  pg->lists_made = false;
   std::lock_guard<std::mutex> lk(ctx->mu);
   VGX_HIP(ctx, hipSetDevice(ctx->device));
   VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -637,8 +963,26 @@ int make_lists(vgx_pose_graph pg, bool with_reg) {
   if (rc != VGX_OK) return rc;
   const size_t nf = (size_t)pg->nf, n_fused = (size_t)vgx_reg_fused_size(n, m), E = pg->edges.size();
   hipError_t e = hipSuccess;
-  for (DeviceBuffer* buf : {(DeviceBuffer*)&pg->d_H, (DeviceBuffer*)&pg->d_A})
-    if (e == hipSuccess) e = buf->reserve(nf * nf * sizeof(double));
+  const size_t n_h = pg->S.h_col.size(), n_l = pg->S.l_row.size(), tile_bytes = kTileDoubles * sizeof(double);
+  if (sparse) {
+    pg->d_H.release();
+    pg->d_A.release();
+    pg->d_X.release();
+    rc = upload_new(ctx, pg->d_block_tile, block_tile.data(), block_tile.size() * sizeof(int32_t));
+    if (rc == VGX_OK) rc = upload_structure(ctx, pg->S, &pg->tiles);
+    if (rc == VGX_OK)
+      rc = check_tile_cap(ctx, "vgx_pose_graph_optimize", n_h + n_l, pg->d_Ht.bytes + pg->d_At.bytes,
+                          (6 * nf + n_fused + E * kEdgeTermDoubles + (size_t)m + 64) * sizeof(double));
+    if (rc != VGX_OK) return rc;
+    e = pg->d_Ht.reserve(n_h * tile_bytes);
+    if (e == hipSuccess) e = pg->d_At.reserve(n_l * tile_bytes);
+    pg->sparse_bytes = (n_h + n_l) * tile_bytes + pg->tiles.bytes + block_tile.size() * sizeof(int32_t);
+  } else {
+    pg->d_Ht.release();
+    pg->d_At.release();
+    for (DeviceBuffer* buf : {(DeviceBuffer*)&pg->d_H, (DeviceBuffer*)&pg->d_A})
+      if (e == hipSuccess) e = buf->reserve(nf * nf * sizeof(double));
+  }
   if (e == hipSuccess) e = pg->d_g.reserve(nf * sizeof(double));
   if (e == hipSuccess) e = pg->d_x.reserve(nf * sizeof(double));
   if (e == hipSuccess) e = pg->d_out.reserve(2 * nf * sizeof(double));
@@ -646,16 +990,30 @@ int make_lists(vgx_pose_graph pg, bool with_reg) {
   if (e == hipSuccess) e = pg->d_edge.reserve(std::max<size_t>(1, E) * kEdgeTermDoubles * sizeof(double));
   if (e == hipSuccess) e = pg->d_cost.reserve((size_t)std::max(1, m) * sizeof(double));
   if (e == hipSuccess) e = pg->d_flag.reserve(sizeof(int));
-  if (e != hipSuccess) return alloc_error(ctx, e, "vgx_pose_graph_optimize: allocating the dense system");
+  if (e != hipSuccess) return alloc_error(ctx, e, sparse ? "vgx_pose_graph_optimize: allocating the tiles" : "vgx_pose_graph_optimize: allocating the dense system");
   e = pg->h_io.reserve((3 * nf + E * kEdgeTermDoubles + (size_t)m + 2) * sizeof(double));
   if (e != hipSuccess) return alloc_error(ctx, e, "vgx_pose_graph_optimize: allocating the pinned staging");
   // blocks no constraint touches stay zero: the lists never write them
-  VGX_HIP(ctx, hipMemsetAsync(pg->d_H.p, 0, nf * nf * sizeof(double), ctx->stream));
+  if (sparse)
+    VGX_HIP(ctx, hipMemsetAsync(pg->d_Ht.p, 0, n_h * tile_bytes, ctx->stream));
+  else
+    VGX_HIP(ctx, hipMemsetAsync(pg->d_H.p, 0, nf * nf * sizeof(double), ctx->stream));
   VGX_HIP(ctx, hipMemsetAsync(pg->d_fused.p, 0, n_fused * sizeof(double), ctx->stream));
   pg->lists_made = true;
   pg->lists_with_reg = with_reg;
+  pg->lists_sparse = sparse;
   pg->system_valid = false;
   return VGX_OK;
+}
+
+// (the lists and the structure are host containers sized by the caller's graph: out of host memory is a status)
+int make_lists(vgx_pose_graph pg, bool with_reg, bool sparse) {
+  try {
+    return make_lists_unguarded(pg, with_reg, sparse);
+  } catch (const std::bad_alloc&) {
+    pg->lists_made = false;
+    return set_error(pg->ctx, VGX_ERR_NOMEM, "vgx_pose_graph_optimize: out of host memory for the index lists or the tile structure");
+  }
 }
 
 struct Solve {
@@ -702,7 +1060,11 @@ struct Solve {
       }
       if (E > 0)
         VGX_HIP(ctx, hipMemcpyAsync(pg->d_edge.p, h_edge(), E * kEdgeTermDoubles * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-      if (pg->n_blocks > 0)
+      if (pg->n_blocks > 0 && pg->lists_sparse)
+        hipLaunchKernelGGL(pg_assemble_blocks_tiled_kernel, dim3((pg->n_blocks * 16 + 255) / 256), dim3(256), 0, ctx->stream,
+                           pg->d_blocks.get(), pg->d_block_tile.get(), pg->n_blocks, pg->d_block_items.get(), pg->d_fused.get(),
+                           pg->d_edge.get(), pg->d_Ht.get());
+      else if (pg->n_blocks > 0)
         hipLaunchKernelGGL(pg_assemble_blocks_kernel, dim3((pg->n_blocks * 16 + 255) / 256), dim3(256), 0, ctx->stream, pg->d_blocks.get(),
                            pg->n_blocks, pg->d_block_items.get(), pg->d_fused.get(), pg->d_edge.get(), pg->d_H.get(), pg->nf);
       hipLaunchKernelGGL(pg_assemble_gradient_kernel, dim3((pg->nf + 255) / 256), dim3(256), 0, ctx->stream, pg->d_grad_first.get(),
@@ -741,6 +1103,30 @@ struct Solve {
     const int nf = pg->nf;
     std::lock_guard<std::mutex> lk(ctx->mu);
     VGX_HIP(ctx, hipSetDevice(ctx->device));
+    if (pg->lists_sparse) {
+      const DeviceTiles& d = pg->tiles;
+      hipLaunchKernelGGL(pg_tiles_from_h_kernel, dim3((unsigned)pg->S.l_row.size()), dim3(256), 0, ctx->stream, pg->d_Ht.get(),
+                         pg->d_At.get(), d.l_from_h.get());
+      hipLaunchKernelGGL(pg_damp_tiled_kernel, dim3((nf + 255) / 256), dim3(256), 0, ctx->stream, pg->d_Ht.get(), pg->d_At.get(),
+                         d.h_diag.get(), d.col_first.get(), nf, radius);
+      int rc = queue_cholesky_tiled(ctx, pg->S, d, pg->d_At.get(), nf, pg->d_flag.get());
+      if (rc != VGX_OK) return rc;
+      hipLaunchKernelGGL(pg_permute_kernel, dim3((nf + 255) / 256), dim3(256), 0, ctx->stream, pg->d_g.get(), d.order.get(),
+                         pg->d_x.get(), nf);
+      rc = queue_substitutions_tiled(ctx, d, pg->d_At.get(), nf, pg->d_x.get());
+      if (rc != VGX_OK) return rc;
+      hipLaunchKernelGGL(pg_negate_permuted_kernel, dim3((nf + 255) / 256), dim3(256), 0, ctx->stream, pg->d_x.get(), d.order.get(),
+                         pg->d_out.get(), nf);
+      hipLaunchKernelGGL(pg_matvec_tiled_kernel, dim3((nf + 63) / 64), dim3(64), 0, ctx->stream, pg->d_Ht.get(), d.h_row_first.get(),
+                         d.h_col.get(), pg->d_x.get(), d.order.get(), pg->d_out.get(), nf);
+      VGX_HIP(ctx, hipGetLastError());
+      VGX_HIP(ctx, hipMemcpyAsync(h_step(), pg->d_out.p, 2 * (size_t)nf * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+      VGX_HIP(ctx, hipMemcpyAsync(h_flag(), pg->d_flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+      VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      *failed = *h_flag() != 0;
+      la_seconds += seconds_since(t0);
+      return VGX_OK;
+    }
     VGX_HIP(ctx, hipMemcpyAsync(pg->d_A.p, pg->d_H.p, (size_t)nf * nf * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     hipLaunchKernelGGL(pg_damp_kernel, dim3((nf + 255) / 256), dim3(256), 0, ctx->stream, pg->d_H.get(), pg->d_A.get(), nf, radius);
     int rc = queue_cholesky(ctx, pg->d_A.get(), nf, pg->d_flag.get());
@@ -776,8 +1162,15 @@ void vgx_pose_graph_options_default(vgx_pose_graph_options* o) {
 }
 
 int vgx_pose_graph_create(vgx_ctx ctx, int32_t n_nodes, const int32_t* constant, vgx_pose_graph* out) {
+  return vgx_pose_graph_create_with_solver(ctx, n_nodes, constant, VGX_LINEAR_SOLVER_DENSE, VGX_ORDER_NATURAL, nullptr, out);
+}
+
+int vgx_pose_graph_create_with_solver(vgx_ctx ctx, int32_t n_nodes, const int32_t* constant, int32_t solver, int32_t ordering,
+                                      const int32_t* permutation, vgx_pose_graph* out) {
   if (!ctx || !out) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_create: NULL context or output");
   *out = nullptr;
+  if (solver != VGX_LINEAR_SOLVER_DENSE && solver != VGX_LINEAR_SOLVER_TILE_SPARSE)
+    return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_create: an unknown linear solver");
   if (n_nodes <= 0) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_create: an empty graph (n_nodes <= 0)");
   vgx_pose_graph pg = new (std::nothrow) vgx_pose_graph_s;
   if (!pg) return set_error(ctx, VGX_ERR_NOMEM, "vgx_pose_graph_create: out of host memory");
@@ -789,14 +1182,79 @@ int vgx_pose_graph_create(vgx_ctx ctx, int32_t n_nodes, const int32_t* constant,
       pg->pos[(size_t)i] = (int32_t)pg->free_nodes.size();
       pg->free_nodes.push_back(i);
     }
-  if ((int)pg->free_nodes.size() > kMaxFreeNodes) {
+  if (solver == VGX_LINEAR_SOLVER_DENSE && (int)pg->free_nodes.size() > kMaxFreeNodes) {
     const size_t n_free = pg->free_nodes.size();
     delete pg;
     return set_error(ctx, VGX_ERR_UNSUPPORTED, "vgx_pose_graph_create: " + std::to_string(n_free) + " free nodes; the dense solve takes " +
                                                    std::to_string(kMaxFreeNodes) + " at the most");
   }
+  if (pg->free_nodes.size() > ((size_t)1 << 27)) {
+    delete pg;
+    return set_error(ctx, VGX_ERR_UNSUPPORTED, "vgx_pose_graph_create: more than 2^27 free nodes");
+  }
   pg->nf = 4 * (int)pg->free_nodes.size();
+  if (solver != VGX_LINEAR_SOLVER_DENSE || ordering != VGX_ORDER_NATURAL) {
+    const int rc = vgx_pose_graph_set_linear_solver(pg, solver, ordering, permutation);
+    if (rc != VGX_OK) {
+      delete pg;
+      return rc;
+    }
+  }
   *out = pg;
+  return VGX_OK;
+}
+
+int vgx_pose_graph_set_linear_solver(vgx_pose_graph pg, int32_t solver, int32_t ordering, const int32_t* permutation) {
+  if (!pg) return VGX_ERR_INVALID;
+  vgx_ctx ctx = pg->ctx;
+  if (solver != VGX_LINEAR_SOLVER_DENSE && solver != VGX_LINEAR_SOLVER_TILE_SPARSE)
+    return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_set_linear_solver: an unknown linear solver");
+  if (ordering != VGX_ORDER_NATURAL && ordering != VGX_ORDER_RCM && ordering != VGX_ORDER_GIVEN)
+    return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_set_linear_solver: an unknown ordering");
+  const int32_t nfn = (int32_t)pg->free_nodes.size();
+  if (ordering == VGX_ORDER_GIVEN && !is_permutation(permutation, nfn))
+    return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_set_linear_solver: the permutation is NULL or not a permutation of the free nodes");
+  if (solver == VGX_LINEAR_SOLVER_DENSE && nfn > kMaxFreeNodes)
+    return set_error(ctx, VGX_ERR_UNSUPPORTED, "vgx_pose_graph_set_linear_solver: " + std::to_string(nfn) + " free nodes; the dense solve takes " +
+                                                   std::to_string(kMaxFreeNodes) + " at the most");
+  std::lock_guard<std::mutex> lk(pg->mu);
+  pg->solver = solver;
+  pg->ordering = ordering;
+  pg->given_order.clear();
+  if (ordering == VGX_ORDER_GIVEN) pg->given_order.assign(permutation, permutation + nfn);
+  pg->lists_made = false;
+  return VGX_OK;
+}
+
+int vgx_pose_graph_structure(vgx_pose_graph pg, vgx_pose_graph_structure_stats* stats) {
+  if (!pg) return VGX_ERR_INVALID;
+  vgx_ctx ctx = pg->ctx;
+  if (!stats) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_structure: NULL stats");
+  std::lock_guard<std::mutex> lk(pg->mu);
+  if (!pg->lists_made || !pg->lists_sparse)
+    return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_structure: the tile-sparse solver has made no lists yet (no solve since the last change)");
+  stats->n_free_variables = pg->nf;
+  stats->n_panels = pg->S.n_tile_rows;
+  stats->n_launches = launches_per_factorisation(pg->S);
+  stats->reserved = 0;
+  stats->n_h_tiles = (int64_t)pg->S.h_col.size();
+  stats->n_l_tiles = (int64_t)pg->S.l_row.size();
+  stats->n_update_triples = (int64_t)pg->S.triples.size();
+  stats->bytes = (int64_t)pg->sparse_bytes;
+  return VGX_OK;
+}
+
+int vgx_pose_graph_order(vgx_pose_graph pg, int32_t* permutation_out) {
+  if (!pg) return VGX_ERR_INVALID;
+  vgx_ctx ctx = pg->ctx;
+  if (!permutation_out) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_order: NULL output");
+  std::lock_guard<std::mutex> lk(pg->mu);
+  const size_t nfn = pg->free_nodes.size();
+  const bool dense = pg->solver == VGX_LINEAR_SOLVER_DENSE;
+  if (!dense && pg->ordering == VGX_ORDER_RCM && !(pg->lists_made && pg->lists_sparse))
+    return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_order: the RCM order is made with the lists (no solve since the last change)");
+  for (size_t i = 0; i < nfn; ++i)
+    permutation_out[i] = dense ? (int32_t)i : pg->ordering == VGX_ORDER_RCM ? pg->S.order[i] : pg->ordering == VGX_ORDER_GIVEN ? pg->given_order[i] : (int32_t)i;
   return VGX_OK;
 }
 
@@ -886,8 +1344,9 @@ int vgx_pose_graph_optimize(vgx_pose_graph pg, const vgx_pose_graph_options* opt
     if (summary) *summary = S;
     return VGX_OK;
   }
-  if (!pg->lists_made || pg->lists_with_reg != with_reg) {
-    const int rc = make_lists(pg, with_reg);
+  const bool sparse = pg->solver == VGX_LINEAR_SOLVER_TILE_SPARSE;
+  if (!pg->lists_made || pg->lists_with_reg != with_reg || pg->lists_sparse != sparse) {
+    const int rc = make_lists(pg, with_reg, sparse);
     if (rc != VGX_OK) return rc;
   }
   Solve sv{pg, with_reg};
@@ -1015,8 +1474,33 @@ int vgx_pose_graph_download_system(vgx_pose_graph pg, int32_t* n_free_variables,
   std::lock_guard<std::mutex> lc(ctx->mu);
   VGX_HIP(ctx, hipSetDevice(ctx->device));
   VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (H) VGX_HIP(ctx, hipMemcpy(H, pg->d_H.p, nf * nf * sizeof(double), hipMemcpyDeviceToHost));
   if (g) VGX_HIP(ctx, hipMemcpy(g, pg->d_g.p, nf * sizeof(double), hipMemcpyDeviceToHost));
+  if (H && pg->lists_sparse) {  // the tiles scattered to the dense matrix, in ascending node order whatever the order in use
+    if (nf > (size_t)kMaxDenseN)
+      return set_error(ctx, VGX_ERR_UNSUPPORTED, "vgx_pose_graph_download_system: the dense H of " + std::to_string(nf) +
+                                                     " free variables is not made (" + std::to_string(kMaxDenseN) + " at the most); g is delivered");
+    const TileStructure& S = pg->S;
+    std::vector<double> tiles;
+    try {
+      tiles.resize(S.h_col.size() * (size_t)kTileDoubles);
+    } catch (const std::bad_alloc&) {
+      return set_error(ctx, VGX_ERR_NOMEM, "vgx_pose_graph_download_system: out of host memory for the tiles of H");
+    }
+    VGX_HIP(ctx, hipMemcpy(tiles.data(), pg->d_Ht.p, tiles.size() * sizeof(double), hipMemcpyDeviceToHost));
+    std::fill(H, H + nf * nf, 0.0);
+    for (int32_t I = 0; I < S.n_tile_rows; ++I)
+      for (int32_t t = S.h_row_first[(size_t)I]; t < S.h_row_first[(size_t)I + 1]; ++t) {
+        const int32_t J = S.h_col[(size_t)t];
+        for (int r = 0; r < S.rows_of(I); ++r)
+          for (int c = 0; c < S.rows_of(J); ++c) {
+            const size_t row = 4 * (size_t)S.order[(size_t)(I * kNodesPerTile + r / 4)] + r % 4;
+            const size_t col = 4 * (size_t)S.order[(size_t)(J * kNodesPerTile + c / 4)] + c % 4;
+            H[row * nf + col] = tiles[(size_t)t * kTileDoubles + r * kPanel + c];
+          }
+      }
+  } else if (H) {
+    VGX_HIP(ctx, hipMemcpy(H, pg->d_H.p, nf * nf * sizeof(double), hipMemcpyDeviceToHost));
+  }
   return VGX_OK;
 }
 
@@ -1076,13 +1560,17 @@ int vgx_pose_graph_covariance(vgx_pose_graph pg, const double* poses, int32_t ex
   const bool with_reg = pg->batch && pg->batch->n > 0 && !exclude_registration_constraints;
   if (!with_reg && pg->edges.empty())
     return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance: a graph without constraints (no registration batch in use, no edges)");
+  if ((int)pg->free_nodes.size() > kMaxFreeNodes)
+    return set_error(ctx, VGX_ERR_UNSUPPORTED, "vgx_pose_graph_covariance: " + std::to_string(pg->free_nodes.size()) +
+                                                   " free nodes; the covariances take the dense factor, " + std::to_string(kMaxFreeNodes) +
+                                                   " free nodes at the most");
   const size_t n_out = 16 * (size_t)n_pairs;
   if (pg->nf == 0) {  // every node is constant
     std::fill(covariance, covariance + n_out, 0.0);
     return VGX_OK;
   }
-  if (!pg->lists_made || pg->lists_with_reg != with_reg) {
-    const int rc = make_lists(pg, with_reg);
+  if (!pg->lists_made || pg->lists_with_reg != with_reg || pg->lists_sparse) {  // (the dense lists, whatever the solver)
+    const int rc = make_lists(pg, with_reg, false);
     if (rc != VGX_OK) return rc;
   }
   // the columns to solve: the distinct second nodes (of pairs between free nodes) in ascending free position, and per
@@ -1199,4 +1687,95 @@ int vgx_dense_spd_solve_many(vgx_ctx ctx, int32_t n, const double* A, int32_t m,
   return VGX_OK;
 }
 
+int vgx_block_spd_solve(vgx_ctx ctx, int32_t n_block_rows, int32_t nnz, const int32_t* bi, const int32_t* bj, const double* values,
+                        const double* b, double* x, vgx_pose_graph_structure_stats* stats, int32_t* tile_index, double* tile_values) {
+  if (!ctx) return VGX_ERR_INVALID;
+  if (n_block_rows < 1 || nnz < 1) return set_error(ctx, VGX_ERR_INVALID, "vgx_block_spd_solve: n_block_rows < 1 or nnz < 1");
+  if (n_block_rows > (1 << 27)) return set_error(ctx, VGX_ERR_UNSUPPORTED, "vgx_block_spd_solve: more than 2^27 block rows");
+  if (!bi || !bj || !values || !b || !x) return set_error(ctx, VGX_ERR_INVALID, "vgx_block_spd_solve: NULL bi, bj, values, b or x");
+  try {
+    return block_spd_solve(ctx, n_block_rows, nnz, bi, bj, values, b, x, stats, tile_index, tile_values);
+  } catch (const std::bad_alloc&) {
+    return set_error(ctx, VGX_ERR_NOMEM, "vgx_block_spd_solve: out of host memory for the structure or the tiles");
+  }
+}
+
 }  // extern "C"
+
+namespace {
+int block_spd_solve(vgx_ctx ctx, int32_t n_block_rows, int32_t nnz, const int32_t* bi, const int32_t* bj, const double* values,
+                    const double* b, double* x, vgx_pose_graph_structure_stats* stats, int32_t* tile_index, double* tile_values) {
+  std::vector<int32_t> joined(2 * (size_t)nnz);
+  std::set<std::pair<int32_t, int32_t>> seen;
+  for (int32_t k = 0; k < nnz; ++k) {
+    if (bi[k] < 0 || bi[k] >= n_block_rows || bj[k] < 0 || bj[k] >= n_block_rows)
+      return set_error(ctx, VGX_ERR_INVALID, "vgx_block_spd_solve: block " + std::to_string(k) + " is out of range");
+    if (bj[k] > bi[k]) return set_error(ctx, VGX_ERR_INVALID, "vgx_block_spd_solve: block " + std::to_string(k) + " lies above the diagonal");
+    if (!seen.insert({bi[k], bj[k]}).second)
+      return set_error(ctx, VGX_ERR_INVALID, "vgx_block_spd_solve: block " + std::to_string(k) + " is given twice");
+    joined[2 * (size_t)k] = bi[k];
+    joined[2 * (size_t)k + 1] = bj[k];
+  }
+  TileStructure S;
+  if (!build_tile_structure(n_block_rows, nnz, joined.data(), kOrderNatural, nullptr, &S))
+    return set_error(ctx, VGX_ERR_INVALID, "vgx_block_spd_solve: the block list does not make a structure");
+  const size_t n_l = S.l_row.size(), N = 4 * (size_t)n_block_rows;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  VGX_HIP(ctx, hipSetDevice(ctx->device));
+  int rc = check_tile_cap(ctx, "vgx_block_spd_solve", n_l, 0, (N + 64) * sizeof(double));
+  if (rc != VGX_OK) return rc;
+  std::vector<double> tiles(n_l * (size_t)kTileDoubles, 0.0);
+  for (int32_t k = 0; k < nnz; ++k) {
+    double* T = tiles.data() + (size_t)S.l_tile(bi[k] / kNodesPerTile, bj[k] / kNodesPerTile) * kTileDoubles;
+    for (int r = 0; r < 4; ++r)
+      for (int c = 0; c < 4; ++c)
+        T[(4 * (bi[k] % kNodesPerTile) + r) * kPanel + 4 * (bj[k] % kNodesPerTile) + c] = values[16 * (size_t)k + 4 * r + c];
+  }
+  DeviceTiles d;
+  DeviceArray<double> d_At, d_x;
+  DeviceArray<int> d_flag;
+  rc = upload_structure(ctx, S, &d);
+  if (rc != VGX_OK) return rc;
+  hipError_t e = d_At.alloc_n(n_l * (size_t)kTileDoubles);
+  if (e == hipSuccess) e = d_x.alloc_n(N);
+  if (e == hipSuccess) e = d_flag.alloc_n(1);
+  if (e != hipSuccess) return alloc_error(ctx, e, "vgx_block_spd_solve: allocating the tiles");
+  VGX_HIP(ctx, hipMemcpyAsync(d_At.p, tiles.data(), tiles.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  VGX_HIP(ctx, hipMemcpyAsync(d_x.p, b, N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  rc = queue_cholesky_tiled(ctx, S, d, d_At.get(), (int)N, d_flag.get());
+  if (rc == VGX_OK) rc = queue_substitutions_tiled(ctx, d, d_At.get(), (int)N, d_x.get());
+  if (rc != VGX_OK) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+  }
+  int flag = 0;
+  VGX_HIP(ctx, hipMemcpyAsync(&flag, d_flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  VGX_HIP(ctx, hipMemcpyAsync(x, d_x.p, N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (tile_values) VGX_HIP(ctx, hipMemcpyAsync(tile_values, d_At.p, tiles.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (tile_index)
+    for (size_t t = 0; t < n_l; ++t) {
+      tile_index[2 * t] = S.l_row[t];
+      tile_index[2 * t + 1] = S.l_col[t];
+    }
+  if (tile_values)  // a diagonal tile above its diagonal, and the rows and columns past n: zeros
+    for (size_t t = 0; t < n_l; ++t)
+      for (int r = 0; r < kPanel; ++r)
+        for (int c = 0; c < kPanel; ++c)
+          if (r >= S.rows_of(S.l_row[t]) || c >= S.rows_of(S.l_col[t]) || (S.l_row[t] == S.l_col[t] && c > r))
+            tile_values[t * kTileDoubles + r * kPanel + c] = 0.0;
+  if (stats) {
+    stats->n_free_variables = (int32_t)N;
+    stats->n_panels = S.n_tile_rows;
+    stats->n_launches = launches_per_factorisation(S);
+    stats->reserved = 0;
+    stats->n_h_tiles = 0;
+    for (int32_t v : S.l_from_h) stats->n_h_tiles += v >= 0;
+    stats->n_l_tiles = (int64_t)n_l;
+    stats->n_update_triples = (int64_t)S.triples.size();
+    stats->bytes = (int64_t)(tiles.size() * sizeof(double) + d.bytes);
+  }
+  if (flag) return set_error(ctx, VGX_ERR_NOT_POSITIVE_DEFINITE, "vgx_block_spd_solve: the matrix is not positive definite (a pivot is not positive or not finite)");
+  return VGX_OK;
+}
+}  // namespace
