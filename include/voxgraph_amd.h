@@ -1765,6 +1765,104 @@ VGX_API int vgx_block_spd_solve(vgx_ctx ctx, int32_t n_block_rows, int32_t nnz, 
                                 const double* values /* [nnz][16] */, const double* b, double* x,
                                 vgx_pose_graph_structure_stats* stats, int32_t* tile_index, double* tile_values);
 
+/* ---- Scan-to-map registration ---------------------------------------------- */
+/* The refinement voxgraph_mapper.h:164 announces ("Map tracker handles the odometry input and refines it using
+ * scan-to-map ICP") and the reference's MapTracker does not perform: a scan's sensor pose T_S_C refined against the
+ * ACTIVE TSDF layer before the scan is integrated.  DEFINED HERE, not recalled: point-to-implicit-surface Gauss-Newton
+ * over a 4-DoF correction, the formulation the registration cost function uses between submaps.  voxblox's own
+ * mini-batch ICP class is a different scheme and is not restated.
+ *
+ * THE FORMULATION.  n sensor-frame points p_C (f32), a prior T_S_C = {qw,qx,qy,qz, tx,ty,tz} (f32, the integrator's
+ * convention), a correction delta = (x, y, z, yaw) in f64 applied about the sensor's prior position in the layer frame.
+ * All of the following in f32, one rounding per operation, no contraction:
+ *   q   = R_prior p_C                         Eigen _transformVector (v + w uv + u x uv, uv = 2 u x v)
+ *   c, s = (float)cos(yaw), (float)sin(yaw)   computed on the host in f64;  t' = (float)((double)t_prior + delta_xyz)
+ *   p_S = ((c qx - s qy) + tx', (s qx + c qy) + ty', qz + tz')
+ *   r   = D(p_S), the trilinear TSDF distance over the 8 neighbours (Interpolator<TsdfVoxel>: every neighbour's block
+ *         exists and every weight is > 0, else the point is not usable)
+ *   g_a = (dD/d dl_a) * voxel_size_inv, the exact derivative of the interpolant from the same 8 voxels:
+ *         d/d dl0 = ((c1 + dl1 c4) + dl2 c6) + (dl1 dl2) c7, d/d dl1 = ((c2 + dl0 c4) + dl2 c5) + (dl2 dl0) c7,
+ *         d/d dl2 = ((c3 + dl1 c5) + dl0 c6) + (dl0 dl1) c7 in the interpolant's coefficients
+ *   J   = (g_x, g_y, g_z, g_x ((-s) qx - c qy) + g_y (c qx - s qy))
+ * A point is a CANDIDATE when its index is a multiple of point_stride and |p_C|^2 = (x x + y y) + z z lies in
+ * [min_range_m^2, max_range_m^2] (f32; a NaN fails).  A candidate is USABLE when |p_S_a * block_size_inv| < 2^30 on
+ * every axis (so every non-finite point is skipped), the interpolation is valid and |D| < max_abs_distance_m (the
+ * clamped free-space plateau has no gradient and says nothing about the pose).
+ *
+ * THE ORDER CONTRACT.  Per usable point 15 f64 terms: r r; J_k r (k = 0..3); J_k J_l for k <= l in the order 00 01 02
+ * 03 11 12 13 22 23 33 -- products of two f32 values widened to f64, exact.  Only the additions round:
+ *   candidate j (point j * point_stride) belongs to workgroup j / 1024, thread (j % 1024) % 256, trip (j % 1024) / 256;
+ *   a thread adds its usable points' terms to 0.0 in ascending trip; the 64 lanes of a wave fold by
+ *   v[l] += v[l + o], o = 32, 16, 8, 4, 2, 1; lane 0 of wave 0, then waves 1, 2, 3 added in order: one partial per
+ *   workgroup.  The fold: partial b to thread b % 256 of ONE workgroup, added to 0.0 in ascending b; the same wave
+ *   fold; the 4 waves in order.  The two counts (usable, candidates) are int64 sums.
+ * The partition depends on n and point_stride alone, never on the device.  No float atomics; two launches and one host
+ * synchronisation per evaluation (tests/scan_registration_ref.py restates every bit).  cost = 0.5 sum r r.
+ *
+ * THE LOOP is vgx_pose_graph_optimize's ("Pose graph: the solve") with one free node, x = delta starting at 0: the
+ * same damping D^2 = clip(diag H, 1e-6, 1e32), A = H + diag(D^2 / radius), a 4x4 right-looking Cholesky on the host in
+ * the same per-element order (a failed pivot shrinks the radius), column-oriented substitutions, the yaw wrap, the
+ * gain ratio, the radius update and the five stopping rules.  ONE difference: there is no cost-only form -- every trial
+ * step is a full evaluation, an accepted step keeps its g and H, a rejected one discards them; evaluations = 1 + trial
+ * steps.  options->exclude_registration_constraints is ignored.
+ *
+ * THE OUTCOME.  usable = 1 iff the solve ended in VGX_CONVERGENCE and n_valid / n_candidates >= min_valid_ratio at
+ * both the first and the last accepted evaluation.  Then T_refined = {q_z(yaw) (x) q_prior, t_prior + delta_xyz}, formed
+ * in f64 from the f32 prior and rounded to f32 once; otherwise T_refined is the prior's bits, `delta` still what the
+ * solve ended at.  A scan that cannot be registered is an answer, not an error: VGX_OK with usable = 0.  Too few
+ * usable points at the prior: at once, zero iterations, termination VGX_FAILURE / VGX_TERMINATION_TOO_FEW_POINTS.
+ *
+ * The kernels run on the context's TSDF stream under the lock the integrators take: an evaluation is ordered behind
+ * every scan already queued on that layer, and the scan never leaves the device.  One call at a time per handle.
+ *
+ * Points: _set_points copies host points; _set_points_device and _set_scan BORROW (a device array ready with respect
+ * to the TSDF stream / a vgx_scan as it stands at each evaluation) until the next set or the handle's destruction.
+ * Refused with VGX_ERR_INVALID, nothing written (vgx_last_error says which): NULL arguments; no points set; a layer or
+ * scan of another context; a prior that is not finite or whose quaternion has | |q|^2 - 1 | > 1e-4; a delta that is not
+ * finite; point_stride < 1; max_abs_distance_m <= 0 or not finite; min_range_m > max_range_m or a NaN range; a
+ * min_valid_ratio that is not finite.  VGX_ERR_UNSUPPORTED: voxels_per_side other than 8 or 16; more than
+ * (2^31 - 1) * 1024 candidates (one launch). */
+typedef struct vgx_scan_registration_s* vgx_scan_registration;
+typedef struct vgx_scan_registration_config {
+  float min_range_m;         /* 0 */
+  float max_range_m;         /* +inf */
+  float max_abs_distance_m;  /* NO default (0: refused): below the layer's truncation distance, e.g. 0.55 of 0.6 m */
+  int32_t point_stride;      /* 1 */
+  float min_valid_ratio;     /* 0.5 */
+} vgx_scan_registration_config;
+#define VGX_TERMINATION_TOO_FEW_POINTS 6
+typedef struct vgx_scan_registration_summary {
+  int32_t usable;
+  int32_t termination_type;    /* VGX_CONVERGENCE / VGX_NO_CONVERGENCE / VGX_FAILURE */
+  int32_t termination_reason;  /* VGX_TERMINATION_* */
+  int32_t num_iterations;
+  int32_t num_successful_steps;
+  int32_t num_evaluations;     /* 1 + trial steps */
+  int32_t num_factorization_failures;
+  int32_t reserved;
+  int64_t n_candidates;
+  int64_t n_valid_first, n_valid_last; /* usable points at the prior / at the correction the solve ended at */
+  double initial_cost, final_cost;
+  double total_seconds;
+  double evaluation_seconds;   /* launch to result on the host, all evaluations */
+} vgx_scan_registration_summary;
+VGX_API void vgx_scan_registration_config_default(vgx_scan_registration_config* cfg);
+VGX_API int vgx_scan_registration_create(vgx_ctx ctx, const vgx_scan_registration_config* cfg, vgx_scan_registration* out);
+VGX_API int vgx_scan_registration_destroy(vgx_scan_registration reg);
+VGX_API int vgx_scan_registration_set_points(vgx_scan_registration reg, const float* points /* host [n][3] */, int64_t n);
+VGX_API int vgx_scan_registration_set_points_device(vgx_scan_registration reg, const void* d_points /* f32 [n][3] */, int64_t n);
+VGX_API int vgx_scan_registration_set_scan(vgx_scan_registration reg, vgx_scan scan);
+/* the normal equations at a given correction: out[15] = {sum r r, sum J_k r [4], sum J_k J_l [10]} */
+VGX_API int vgx_scan_registration_evaluate(vgx_scan_registration reg, vgx_tsdf_layer layer, const float T_S_C_prior[7],
+                                           const double delta[4], double out[15], int64_t* n_valid, int64_t* n_candidates);
+/* options NULL: vgx_pose_graph_options_default.  T_refined [7] and delta [4] are written on VGX_OK; summary nullable. */
+VGX_API int vgx_scan_registration_refine(vgx_scan_registration reg, vgx_tsdf_layer layer, const float T_S_C_prior[7],
+                                         const vgx_pose_graph_options* options, float T_refined[7], double delta[4],
+                                         vgx_scan_registration_summary* summary);
+/* the last refinement's iterations, as vgx_pose_graph_history */
+VGX_API int vgx_scan_registration_history(vgx_scan_registration reg, int32_t capacity, vgx_pose_graph_iteration* iterations,
+                                          int32_t* n_iterations);
+
 #ifdef __cplusplus
 }
 #endif

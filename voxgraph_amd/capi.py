@@ -171,13 +171,30 @@ class PoseGraphStructureStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+class ScanRegistrationConfig(C.Structure):
+    _fields_ = [("min_range_m", C.c_float), ("max_range_m", C.c_float), ("max_abs_distance_m", C.c_float),
+                ("point_stride", C.c_int32), ("min_valid_ratio", C.c_float)]
+
+
+class ScanRegistrationSummary(C.Structure):
+    _fields_ = [("usable", C.c_int32), ("termination_type", C.c_int32), ("termination_reason", C.c_int32),
+                ("num_iterations", C.c_int32), ("num_successful_steps", C.c_int32), ("num_evaluations", C.c_int32),
+                ("num_factorization_failures", C.c_int32), ("reserved", C.c_int32), ("n_candidates", C.c_int64),
+                ("n_valid_first", C.c_int64), ("n_valid_last", C.c_int64), ("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("total_seconds", C.c_double), ("evaluation_seconds", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 LINEAR_SOLVER_DENSE, LINEAR_SOLVER_TILE_SPARSE = 0, 1
 ORDER_NATURAL, ORDER_RCM, ORDER_GIVEN = 0, 1, 2
 CONVERGENCE, NO_CONVERGENCE, FAILURE = 0, 1, 2      # ceres::TerminationType
 (TERMINATION_PARAMETER_TOLERANCE, TERMINATION_FUNCTION_TOLERANCE, TERMINATION_GRADIENT_TOLERANCE, TERMINATION_MAX_ITERATIONS,
  TERMINATION_MAX_SOLVER_TIME, TERMINATION_NO_FREE_NODES) = range(6)
+TERMINATION_TOO_FEW_POINTS = 6                     # scan-to-map registration alone
 TERMINATION_NAMES = ("parameter_tolerance", "function_tolerance", "gradient_tolerance", "max_iterations", "max_solver_time",
-                     "no_free_nodes")          # harness/lm.py's names for the same rules
+                     "no_free_nodes", "too_few_points")   # harness/lm.py's names for the same rules
 
 TSDF_ORDER_MIXED, TSDF_ORDER_SORTED = 0, 1
 # what a vgx_map_msg holds; voxblox MapDerializationAction (include/voxgraph_amd.h, "Map messages")
@@ -387,6 +404,16 @@ SIGNATURES = {
     "vgx_pose_graph_tile_pattern": (C.c_int, [C.c_int32, C.c_int32, i32p, C.c_int32, i32p, i32p, C.c_int32, i32p, i32p]),
     "vgx_block_spd_solve": (C.c_int, [vp, C.c_int32, C.c_int32, i32p, i32p, f64p, f64p, f64p, C.POINTER(PoseGraphStructureStats),
                                       i32p, f64p]),
+    "vgx_scan_registration_config_default": (None, [C.POINTER(ScanRegistrationConfig)]),
+    "vgx_scan_registration_create": (C.c_int, [vp, C.POINTER(ScanRegistrationConfig), C.POINTER(vp)]),
+    "vgx_scan_registration_destroy": (C.c_int, [vp]),
+    "vgx_scan_registration_set_points": (C.c_int, [vp, f32p, C.c_int64]),
+    "vgx_scan_registration_set_points_device": (C.c_int, [vp, vp, C.c_int64]),
+    "vgx_scan_registration_set_scan": (C.c_int, [vp, vp]),
+    "vgx_scan_registration_evaluate": (C.c_int, [vp, vp, f32p, f64p, f64p, i64p, i64p]),
+    "vgx_scan_registration_refine": (C.c_int, [vp, vp, f32p, C.POINTER(PoseGraphOptions), f32p, f64p,
+                                               C.POINTER(ScanRegistrationSummary)]),
+    "vgx_scan_registration_history": (C.c_int, [vp, C.c_int32, C.POINTER(PoseGraphIteration), i32p]),
 }
 
 # every symbol include/voxgraph_amd_bench.h declares (libvoxgraph_amd_bench.so: test and benchmark tooling)
@@ -1802,6 +1829,81 @@ class Scan:
     def destroy(self):
         if self.h:
             self.ctx.lib.vgx_scan_destroy(self.h)
+            self.h = None
+
+
+def scan_registration_config(max_abs_distance_m, **kw):
+    """vgx_scan_registration_config: the defaults, max_abs_distance_m (which has none) and fields overridden by keyword"""
+    cfg = ScanRegistrationConfig()
+    load().vgx_scan_registration_config_default(C.byref(cfg))
+    cfg.max_abs_distance_m = max_abs_distance_m
+    for k, v in kw.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(k)
+        setattr(cfg, k, v)
+    return cfg
+
+
+class ScanRegistration:
+    """Scan-to-map registration (vgx_scan_registration): a scan's sensor pose T_S_C refined against the active TSDF layer
+    on the TSDF stream -- `T, usable = reg.refine(layer, T_prior)[:2]`, then integrate at T."""
+
+    def __init__(self, ctx, config):
+        self.ctx = ctx
+        self._keep = None            # a borrowed source stays alive with the handle
+        h = vp()
+        ctx.check(ctx.lib.vgx_scan_registration_create(ctx.h, None if config is None else C.byref(config), C.byref(h)))
+        self.h = h
+
+    def set_points(self, points, n=None):
+        """points: a numpy array [n][3] (copied), a torch device tensor [n][3] f32 (borrowed), a device address as an int
+        with n (borrowed), or a capi.Scan (borrowed: its points at each evaluation)"""
+        lib = self.ctx.lib
+        if isinstance(points, Scan):
+            self.ctx.check(lib.vgx_scan_registration_set_scan(self.h, points.h))
+            self._keep = points
+        elif isinstance(points, int):
+            self.ctx.check(lib.vgx_scan_registration_set_points_device(self.h, vp(points) if points else None, int(n)))
+            self._keep = None
+        elif hasattr(points, "data_ptr"):
+            if not points.is_cuda or str(points.dtype) != "torch.float32" or not points.is_contiguous():
+                raise TypeError("a contiguous float32 device tensor [n][3]")
+            m = points.numel() // 3
+            self.ctx.check(lib.vgx_scan_registration_set_points_device(self.h, vp(points.data_ptr()) if m else None, m))
+            self._keep = points
+        else:
+            p = _f32(points).reshape(-1, 3)
+            self.ctx.check(lib.vgx_scan_registration_set_points(self.h, _ptr(p, f32p) if len(p) else None, len(p)))
+            self._keep = None
+
+    def evaluate(self, layer, T_S_C_prior, delta=(0.0, 0.0, 0.0, 0.0)):
+        """-> (out [15]: sum r r, sum J_k r [4], sum J_k J_l [10]; n_valid; n_candidates)"""
+        T, d, out = _f32(T_S_C_prior), _f64(delta), np.zeros(15)
+        nv, nc = C.c_int64(), C.c_int64()
+        self.ctx.check(self.ctx.lib.vgx_scan_registration_evaluate(self.h, layer.h, _ptr(T, f32p), _ptr(d, f64p), _ptr(out, f64p),
+                                                                   C.byref(nv), C.byref(nc)))
+        return out, nv.value, nc.value
+
+    def refine(self, layer, T_S_C_prior, options=None, **kw):
+        """-> (T_refined [7] f32, usable, delta [4], summary dict); keywords override the default pose-graph options"""
+        opts = options if options is not None else pose_graph_options(**kw)
+        T, out, delta, s = _f32(T_S_C_prior), np.zeros(7, np.float32), np.zeros(4), ScanRegistrationSummary()
+        self.ctx.check(self.ctx.lib.vgx_scan_registration_refine(self.h, layer.h, _ptr(T, f32p), C.byref(opts), _ptr(out, f32p),
+                                                                 _ptr(delta, f64p), C.byref(s)))
+        d = s.as_dict()
+        d["termination"] = TERMINATION_NAMES[s.termination_reason]
+        return out, bool(s.usable), delta, d
+
+    def history(self):
+        n = C.c_int32()
+        self.ctx.check(self.ctx.lib.vgx_scan_registration_history(self.h, 0, None, C.byref(n)))
+        arr = (PoseGraphIteration * max(n.value, 1))()
+        self.ctx.check(self.ctx.lib.vgx_scan_registration_history(self.h, n.value, arr, None))
+        return [{name: getattr(arr[k], name) for name, _ in PoseGraphIteration._fields_} for k in range(n.value)]
+
+    def destroy(self):
+        if self.h:
+            self.ctx.lib.vgx_scan_registration_destroy(self.h)
             self.h = None
 
 

@@ -62,6 +62,20 @@ __device__ __forceinline__ float interp_trilinear(const float x[8], const float 
   return ((((((c0 + dl[0] * c1) + dl[1] * c2) + dl[2] * c3) + q4 * c4) + q5 * c5) + q6 * c6) + q7 * c7;
 }
 
+// The exact derivative of interp_trilinear's form with respect to dl (in voxels), from the same 8 values and in the same
+// coefficients; every sum left to right.  Defined here (scan-to-map registration, vgx_scan_reg.hip): voxblox has no
+// counterpart, its gradients are central differences of seven interpolations.
+__device__ __forceinline__ void interp_trilinear_gradient(const float x[8], const float dl[3], float g[3]) {
+  float c1 = -x[0] + x[4], c2 = -x[0] + x[2], c3 = -x[0] + x[1];
+  float c4 = ((x[0] - x[2]) - x[4]) + x[6];
+  float c5 = ((x[0] - x[1]) - x[2]) + x[3];
+  float c6 = ((x[0] - x[1]) - x[4]) + x[5];
+  float c7 = ((((((-x[0] + x[1]) + x[2]) - x[3]) + x[4]) - x[5]) - x[6]) + x[7];
+  g[0] = ((c1 + dl[1] * c4) + dl[2] * c6) + (dl[1] * dl[2]) * c7;
+  g[1] = ((c2 + dl[0] * c4) + dl[2] * c5) + (dl[2] * dl[0]) * c7;
+  g[2] = ((c3 + dl[1] * c5) + dl[0] * c6) + (dl[0] * dl[1]) * c7;
+}
+
 // Interpolator<VoxelType>::isVoxelValid on the layer's validity array: TSDF weight > 0, ESDF observed != 0
 __device__ __forceinline__ bool interp_valid(float w) { return w > 0.0f; }
 __device__ __forceinline__ bool interp_valid(uint8_t o) { return o != 0; }

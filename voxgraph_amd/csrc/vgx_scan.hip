@@ -113,6 +113,16 @@ struct vgx_scan_s {
   bool pageable = false;  // no pinned memory was to be had: uploads go straight from the caller's bytes
 };
 
+namespace vgx {
+vgx_ctx scan_context(vgx_scan S) { return S ? S->ctx : nullptr; }
+std::unique_lock<std::mutex> scan_borrow(vgx_scan S, const float** d_points, int64_t* n) {
+  std::unique_lock<std::mutex> lk(S->mu);
+  *n = S->n_points;
+  *d_points = S->n_points > 0 ? S->d_points.as<float>() : nullptr;
+  return lk;
+}
+}  // namespace vgx
+
 namespace {
 
 // Everything a decode is refused for that the layout, the configuration and the byte count alone decide; VGX_OK, or the

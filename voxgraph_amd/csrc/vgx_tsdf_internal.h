@@ -483,6 +483,11 @@ int det_next_chain(vgx_tsdf_integrator I, uint32_t tiles, TileChain* chain);
 int det_merged_commit(vgx_tsdf_integrator I, const float T[7], long long n, const float4* g_pg, const uint32_t* g_color,
                       const uint32_t* g_flags, uint32_t* g_count, const unsigned long long* keys_sorted,
                       const unsigned int* group_start, const unsigned int* counters, int64_t* n_updates);
+// vgx_scan.hip: the context a decoded scan lives on (vgx_scan_s is private to that file)
+vgx_ctx scan_context(vgx_scan S);
+// the scan's lock (taken before ctx->tsdf_mu, as the decode takes it) and what the scan holds now: while the caller keeps
+// the lock no decode can replace the array a queued kernel reads
+std::unique_lock<std::mutex> scan_borrow(vgx_scan S, const float** d_points, int64_t* n);
 }  // namespace vgx
 
 #endif  // VGX_TSDF_INTERNAL_H_
