@@ -834,6 +834,67 @@ VGX_API int vgx_tsdf_integrate_scan(vgx_tsdf_integrator integrator, const float 
 VGX_API int vgx_tsdf_integrate_merged_scan(vgx_tsdf_integrator integrator, const float T_G_C[7], vgx_scan scan,
                                            int32_t freespace_points, int64_t* n_updates);
 
+/* ---- Scan undistortion: a sweep moved into one frame by a pose track, inside the decode ---- */
+/* The reference's demo feeds voxgraph a cloud that lidar_undistortion has corrected (arche_demo.launch:6,12).  That
+ * package is not vendored: the rules below are DEFINED here, chosen so that a caller who makes every distinct stamp a
+ * knot gets one rigid transform per stamp.  vgx_scan_decode_msg_undistorted is vgx_scan_decode_msg with one more step
+ * per point: its time field picks a segment of the track and the point is moved from the sensor frame at its own time
+ * into the sensor frame at the scan's reference time.  Rules (what the kernel, vgx_scan.hip, and
+ * tests/scan_undistort_ref.py both follow; f32 unless it says f64, no contraction):
+ *   time field  kind UINT32 / FLOAT32 / FLOAT64: 4 / 4 / 8 little-endian bytes at `offset`, which must fit in point_step
+ *               and may be unaligned (under the dword path an 8-byte field is read as two words).
+ *               t = offset_s + (double)raw * scale: one rounded f64 multiply, then one rounded f64 add.
+ *   track       knot_T [n_knots][7] qw,qx,qy,qz, tx,ty,tz holds T_ref_sensor(knot_time[k]): the sensor at knot time k
+ *               expressed in the sensor frame at the scan's reference time.  Both arrays are HOST arrays and have been
+ *               read when the call returns.  1 <= n_knots <= 65536, the times finite and strictly ascending, every
+ *               knot_T entry finite.  Quaternions are not normalised by the library.
+ *   segment     k = (number of knots with knot_time <= t) - 1.  t < knot_time[0]: k = 0, a = 0, the point counts as
+ *               clamped.  t > knot_time[K-1]: k = K-1, a = 0, clamped.  t == knot_time[K-1]: k = K-1, a = 0, not clamped.
+ *               Otherwise a = (float)((t - t_k) / (t_{k+1} - t_k)), the subtractions and the division in f64.
+ *   point       g0 = knot k applied to p as the integrators apply T_G_C (Eigen's quaternion-vector product plus the
+ *               translation: uv = 2 (q x p), g = (p + qw uv + q x uv) + t, in that association).  a == 0.0f: the output is
+ *               g0 and knot k+1 is not evaluated.  Otherwise g1 = knot k+1 applied to p and out = g0 + a * (g1 - g0) per
+ *               component: exact in translation, chordal in rotation, no slerp and no transcendental.
+ *   filter      in this order: x, y, z finite as the plain decode tests them, else dropped (not finite); t finite, else
+ *               dropped (bad time); all three outputs finite, else dropped (overflowed).  Kept points stay in message
+ *               order, a vgx_scan still never holds a non-finite point, colours follow the plain decode unchanged.
+ *               (With an identity knot a kept -0.0 coordinate comes back as +0.0: it went through the arithmetic.)
+ * Refused with VGX_ERR_INVALID, the scan keeping what it held (vgx_last_error says which): NULL arguments, an unknown time
+ * kind, a time field that does not fit in point_step, scale or offset_s not finite, n_knots out of range, knot times not
+ * finite or not strictly ascending, a knot_T entry that is not finite, and everything the plain decode refuses.
+ * Streams: as the plain decode -- ONE kernel and ONE host synchronisation.  The knots go up as asynchronous copies on the
+ * TSDF stream ahead of the launch into a buffer the handle owns (it grows on demand behind a stream synchronisation); the
+ * three counters come back in the decode's one read-back, 40 bytes instead of 16. */
+#define VGX_SCAN_TIME_UINT32 0  /* e.g. Ouster's "t": nanoseconds since the sweep's start */
+#define VGX_SCAN_TIME_FLOAT32 1 /* e.g. Velodyne's "time": seconds */
+#define VGX_SCAN_TIME_FLOAT64 2 /* e.g. an absolute "timestamp" in seconds */
+#define VGX_SCAN_TRACK_MAX_KNOTS 65536
+typedef struct vgx_scan_time_field {
+  int32_t kind;    /* VGX_SCAN_TIME_* */
+  uint32_t offset; /* byte offset inside a point */
+  double scale;    /* seconds per unit of the raw value */
+  double offset_s; /* added after scaling */
+} vgx_scan_time_field;
+typedef struct vgx_scan_track {
+  int32_t n_knots;
+  const double* knot_time; /* HOST [n_knots] */
+  const float* knot_T;     /* HOST [n_knots][7] */
+} vgx_scan_track;
+/* HOST ONLY (no device, no context): VGX_OK, or the code an undistorting decode of n_bytes bytes is refused with */
+VGX_API int vgx_scan_undistort_check(const vgx_scan_layout* layout, const vgx_scan_time_field* time_field,
+                                     const vgx_scan_track* track, int64_t n_bytes);
+VGX_API int vgx_scan_decode_msg_undistorted(vgx_scan scan, const vgx_scan_layout* layout, const vgx_scan_config* cfg,
+                                            const vgx_scan_time_field* time_field, const vgx_scan_track* track,
+                                            const void* data, int64_t n_bytes);
+/* the same with the message already in DEVICE memory (the track's arrays stay host arrays) */
+VGX_API int vgx_scan_decode_msg_undistorted_device(vgx_scan scan, const vgx_scan_layout* layout, const vgx_scan_config* cfg,
+                                                   const vgx_scan_time_field* time_field, const vgx_scan_track* track,
+                                                   const void* d_data, int64_t n_bytes);
+/* Of the last decode: points dropped for a time that is not finite, points dropped because an output was not finite, kept
+ * points whose time lay outside the track.  Zeros after a plain decode.  vgx_scan_stats' n_dropped is the sum of all
+ * three drop reasons (not finite + bad time + overflowed).  Any may be NULL; no device work. */
+VGX_API int vgx_scan_undistort_stats(vgx_scan scan, int64_t* n_bad_time, int64_t* n_overflowed, int64_t* n_clamped);
+
 /* finishSubmap() hand-off without a host round trip: turns the active layer's blocks
  * into a (not yet finished) submap holding the raw TSDF layer and its TSDF sampling
  * grid; follow with vgx_submap_generate_esdf and vgx_submap_extract_voxel_points.  The

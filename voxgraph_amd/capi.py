@@ -105,6 +105,19 @@ class ScanConfig(C.Structure):
 SCAN_COLOR_NONE, SCAN_COLOR_RGB, SCAN_COLOR_INTENSITY = 0, 1, 2
 
 
+class ScanTimeField(C.Structure):
+    """vgx_scan_time_field: where a point's time lies and t = offset_s + raw * scale."""
+    _fields_ = [("kind", C.c_int32), ("offset", C.c_uint32), ("scale", C.c_double), ("offset_s", C.c_double)]
+
+
+class ScanTrackView(C.Structure):
+    """vgx_scan_track: host arrays of knot times [K] f64 and knot transforms [K][7] f32."""
+    _fields_ = [("n_knots", C.c_int32), ("knot_time", C.POINTER(C.c_double)), ("knot_T", C.POINTER(C.c_float))]
+
+
+SCAN_TIME_UINT32, SCAN_TIME_FLOAT32, SCAN_TIME_FLOAT64 = 0, 1, 2
+
+
 class EvaluationDetails(C.Structure):
     """vgx_voxel_evaluation_details: voxblox::utils::VoxelEvaluationDetails plus the f64 sum and the true min |e|."""
     _fields_ = [("rmse", C.c_float), ("max_error", C.c_float), ("min_error", C.c_float),
@@ -321,6 +334,12 @@ SIGNATURES = {
     "vgx_scan_decode_msg": (C.c_int, [vp, C.POINTER(ScanLayout), C.POINTER(ScanConfig), vp, C.c_int64]),
     "vgx_scan_decode_msg_device": (C.c_int, [vp, C.POINTER(ScanLayout), C.POINTER(ScanConfig), vp, C.c_int64]),
     "vgx_scan_stats": (C.c_int, [vp, i64p, i64p]),
+    "vgx_scan_undistort_check": (C.c_int, [C.POINTER(ScanLayout), C.POINTER(ScanTimeField), C.POINTER(ScanTrackView), C.c_int64]),
+    "vgx_scan_decode_msg_undistorted": (C.c_int, [vp, C.POINTER(ScanLayout), C.POINTER(ScanConfig), C.POINTER(ScanTimeField),
+                                                  C.POINTER(ScanTrackView), vp, C.c_int64]),
+    "vgx_scan_decode_msg_undistorted_device": (C.c_int, [vp, C.POINTER(ScanLayout), C.POINTER(ScanConfig), C.POINTER(ScanTimeField),
+                                                         C.POINTER(ScanTrackView), vp, C.c_int64]),
+    "vgx_scan_undistort_stats": (C.c_int, [vp, i64p, i64p, i64p]),
     "vgx_scan_download": (C.c_int, [vp, f32p, u8p]),
     "vgx_scan_device_pointers": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp)]),
     "vgx_tsdf_integrate_scan": (C.c_int, [vp, f32p, vp, C.c_int32, i64p]),
@@ -1783,6 +1802,69 @@ def scan_layout_check(layout, n_bytes):
     return load().vgx_scan_layout_check(None if layout is None else C.byref(layout), int(n_bytes))
 
 
+def scan_time_field(kind, offset, scale=1.0, offset_s=0.0):
+    """A vgx_scan_time_field: t = offset_s + raw * scale of the SCAN_TIME_* field at byte `offset` of a point."""
+    return ScanTimeField(int(kind), int(offset), float(scale), float(offset_s))
+
+
+def scan_track_view(knot_time, knot_T):
+    """A vgx_scan_track over host arrays (converted to contiguous f64 [K] / f32 [K][7]).  Returns (view, arrays): keep
+    the arrays alive as long as the view is used."""
+    kt = np.ascontiguousarray(knot_time, np.float64).reshape(-1)
+    kT = np.ascontiguousarray(knot_T, np.float32).reshape(-1, 7)
+    if len(kt) != len(kT):
+        raise ValueError("knot_time and knot_T differ in length")
+    return ScanTrackView(len(kt), kt.ctypes.data_as(C.POINTER(C.c_double)), kT.ctypes.data_as(C.POINTER(C.c_float))), (kt, kT)
+
+
+def scan_undistort_check(layout, time_field, knot_time, knot_T, n_bytes):
+    """vgx_scan_undistort_check (host only); knot_time None: a NULL track"""
+    view, keep = (None, None) if knot_time is None else scan_track_view(knot_time, knot_T)
+    return load().vgx_scan_undistort_check(None if layout is None else C.byref(layout), None if time_field is None else C.byref(time_field),
+                                           None if view is None else C.byref(view), int(n_bytes))
+
+
+class ScanTrack:
+    """Samples (t, T_fixed_sensor) of a sensor's pose and the vgx_scan_track they make for one scan -- the same
+    arithmetic as GpuScanTrack (voxgraph_amd/cpp/gpu_pointcloud_integrator.h), all of it f64, one rounding per operation:
+      r      the reference's inverse rotation: n = sqrt(((w w + x x) + y y) + z z) of q_ref, r = (w / n, -x / n, -y / n, -z / n)
+      q_rel  r (x) q_k, Hamilton product, every component summed left to right:
+             w = rw kw - rx kx - ry ky - rz kz        x = rw kx + rx kw + ry kz - rz ky
+             y = rw ky - rx kz + ry kw + rz kx        z = rw kz + rx ky - ry kx + rz kw
+             then divided by m = sqrt(((w w + x x) + y y) + z z)
+      t_rel  r applied to d = t_k - t_ref as the library applies a transform: uv = r.v x d, uv += uv, cc = r.v x uv,
+             t_rel = (d + rw uv) + cc
+      knot_time[k] = t_k - stamp; knot_T[k] = (q_rel, t_rel) cast to f32."""
+
+    def __init__(self):
+        self.times, self.poses = [], []
+
+    def add(self, t, T_fixed_sensor):
+        """T_fixed_sensor: qw,qx,qy,qz, tx,ty,tz of the sensor at time t in any fixed frame; times strictly ascending"""
+        self.times.append(float(t))
+        self.poses.append(np.asarray(T_fixed_sensor, np.float64).reshape(7).copy())
+
+    def relative_to(self, T_fixed_sensor_ref, stamp=0.0):
+        """-> (knot_time [K] f64, knot_T [K][7] f32): T_ref^-1 * T_k and t_k - stamp"""
+        ref = np.asarray(T_fixed_sensor_ref, np.float64).reshape(7)
+        P = np.array(self.poses, np.float64).reshape(-1, 7)
+        w, x, y, z = ref[:4]
+        n = np.sqrt(((w * w + x * x) + y * y) + z * z)
+        rw, rx, ry, rz = w / n, -x / n, -y / n, -z / n
+        kw, kx, ky, kz = P[:, 0], P[:, 1], P[:, 2], P[:, 3]
+        qw = rw * kw - rx * kx - ry * ky - rz * kz
+        qx = rw * kx + rx * kw + ry * kz - rz * ky
+        qy = rw * ky - rx * kz + ry * kw + rz * kx
+        qz = rw * kz + rx * ky - ry * kx + rz * kw
+        m = np.sqrt(((qw * qw + qx * qx) + qy * qy) + qz * qz)
+        dx, dy, dz = P[:, 4] - ref[4], P[:, 5] - ref[5], P[:, 6] - ref[6]
+        ux, uy, uz = ry * dz - rz * dy, rz * dx - rx * dz, rx * dy - ry * dx
+        ux, uy, uz = ux + ux, uy + uy, uz + uz
+        cx, cy, cz = ry * uz - rz * uy, rz * ux - rx * uz, rx * uy - ry * ux
+        T = np.stack([qw / m, qx / m, qy / m, qz / m, (dx + rw * ux) + cx, (dy + rw * uy) + cy, (dz + rw * uz) + cz], 1)
+        return np.array(self.times, np.float64) - np.float64(stamp), T.astype(np.float32)
+
+
 class Scan:
     """A raw PointCloud2 decoded on the GPU (vgx_scan): the finite points and their colours in message order; reused
     from message to message.  FastTsdfIntegrator.integrate_scan / integrate_merged_scan consume it."""
@@ -1806,11 +1888,35 @@ class Scan:
                                                                vp(d_data) if d_data else None, int(n_bytes)))
         return self.stats()
 
+    def decode_undistorted(self, layout, data, time_field, knot_time, knot_T, config=None):
+        """decode_msg with every point moved into the reference frame by the track (vgx_scan_decode_msg_undistorted):
+        knot_time [K] f64 ascending, knot_T [K][7] f32 = T_ref_sensor at the knot times.  Returns (points, dropped)."""
+        buf = np.frombuffer(data, np.uint8)
+        view, keep = scan_track_view(knot_time, knot_T)
+        self.ctx.check(self.ctx.lib.vgx_scan_decode_msg_undistorted(
+            self.h, C.byref(layout), None if config is None else C.byref(config), C.byref(time_field), C.byref(view),
+            vp(buf.ctypes.data) if buf.size else None, buf.size))
+        return self.stats()
+
+    def decode_undistorted_device(self, layout, d_data, n_bytes, time_field, knot_time, knot_T, config=None):
+        """the same with the message at device address d_data (ready with respect to the TSDF stream)"""
+        view, keep = scan_track_view(knot_time, knot_T)
+        self.ctx.check(self.ctx.lib.vgx_scan_decode_msg_undistorted_device(
+            self.h, C.byref(layout), None if config is None else C.byref(config), C.byref(time_field), C.byref(view),
+            vp(d_data) if d_data else None, int(n_bytes)))
+        return self.stats()
+
     def stats(self):
         """(points, dropped)"""
         n, d = C.c_int64(), C.c_int64()
         self.ctx.check(self.ctx.lib.vgx_scan_stats(self.h, C.byref(n), C.byref(d)))
         return n.value, d.value
+
+    def undistort_stats(self):
+        """(bad_time, overflowed, clamped) of the last decode; zeros after a plain one"""
+        b, o, c = C.c_int64(), C.c_int64(), C.c_int64()
+        self.ctx.check(self.ctx.lib.vgx_scan_undistort_stats(self.h, C.byref(b), C.byref(o), C.byref(c)))
+        return b.value, o.value, c.value
 
     def download(self):
         """(points [n][3] f32, rgba [n][4] uint8)"""

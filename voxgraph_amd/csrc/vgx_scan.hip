@@ -8,6 +8,12 @@
 // workgroup (block_exclusive_sum) and across the tiles before it (chain_exclusive_sum: the prefix sum inside the launch),
 // and each thread writes its kept points and their colours at its rank.  No atomics decide a position: the order is the
 // message's.  The last tile leaves the total for the host.
+//
+// The undistorting decode (include/voxgraph_amd.h, "Scan undistortion") is the same tile with one more step
+// between the test and the ranking: the point's time field picks a segment of a pose track (a binary search over the
+// knot times in global memory) and the point is moved into the reference frame by a linear blend of the two knots'
+// transforms of it.  Three counters (bad time, overflowed, clamped) are summed per wave and added to running device
+// words that are never cleared: the host subtracts what it read back last.
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -22,7 +28,8 @@ namespace vgx {
 constexpr int kScanIpt = 4;                    // consecutive points per thread
 constexpr int kScanTile = 256 * kScanIpt;      // points per workgroup
 constexpr size_t kScanStageBytes = 1u << 20;   // one pinned staging buffer (two of them, filled in turn)
-enum { kScanTicket = 0, kScanError = 1, kScanTotal = 2, kScanCtlWords = 4 };  // u64 words of vgx_scan_s::d_ctl
+// u64 words of vgx_scan_s::d_ctl; {error, total, bad time, overflowed, clamped} are read back in one copy
+enum { kScanTicket = 0, kScanError = 1, kScanTotal = 2, kScanBadTime = 3, kScanOverflowed = 4, kScanClamped = 5, kScanCtlWords = 8 };
 
 struct ScanMsg {
   const uint8_t* data;
@@ -31,6 +38,16 @@ struct ScanMsg {
   int32_t color_kind;
   float intensity_min, intensity_max;
   uint32_t constant;  // constant_rgba as the word the colour array holds (r in the low byte)
+};
+
+// the undistorting decode's arguments: the time field and the track (device copies of the caller's arrays)
+struct ScanDeskew {
+  const double* knot_time;  // [n_knots] strictly ascending
+  const float* knot_T;      // [n_knots][7] qw qx qy qz tx ty tz: T_ref_sensor(knot_time[k])
+  int32_t n_knots, time_kind;
+  uint32_t time_offset;
+  double scale, offset_s;
+  unsigned long long* counters;  // d_ctl + kScanBadTime: running sums {bad time, overflowed, clamped}
 };
 
 // the little-endian 32-bit field at p
@@ -54,13 +71,67 @@ __device__ __forceinline__ uint32_t scan_colour(const ScanMsg& m, uint32_t field
   return g | (g << 8) | (g << 16) | 0xff000000u;
 }
 
+// t = offset_s + (double)raw * scale of the point at p: one rounded f64 multiply, one rounded f64 add
 template <bool DWORDS>
-__global__ __launch_bounds__(256) void scan_decode_kernel(ScanMsg m, TileChain chain, float* __restrict__ points,
-                                                          uint32_t* __restrict__ rgba, unsigned long long* __restrict__ total) {
+__device__ __forceinline__ double scan_time(const ScanDeskew& u, const uint8_t* p) {
+  const uint32_t lo = scan_field<DWORDS>(p + u.time_offset);
+  double raw;
+  if (u.time_kind == VGX_SCAN_TIME_UINT32)
+    raw = (double)lo;
+  else if (u.time_kind == VGX_SCAN_TIME_FLOAT32)
+    raw = (double)__uint_as_float(lo);
+  else  // (an 8-byte field as two words: it need not be 8-aligned)
+    raw = __longlong_as_double((long long)(((unsigned long long)scan_field<DWORDS>(p + u.time_offset + 4) << 32) | lo));
+  const double scaled = raw * u.scale;
+  return u.offset_s + scaled;
+}
+
+// The point (x, y, z) observed at the finite time t, in the reference frame: the segment k = (knots with time <= t) - 1,
+// a in [0, 1] inside it (the f32 of a ratio below 1 may be 1), g0 + a * (g1 - g0) of the two knots' transforms of the point.  Before the first knot and from
+// the last knot on a = 0: the knot's transform alone.  clamped: t lies outside the track.
+__device__ __forceinline__ void scan_undistort(const ScanDeskew& u, double t, float& x, float& y, float& z, bool& clamped) {
+  int lo = 0, hi = u.n_knots;  // the number of knots with time <= t lies in [lo, hi]
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (u.knot_time[mid] <= t)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  const int k = lo > 0 ? lo - 1 : 0;
+  float a = 0.0f;
+  clamped = lo == 0;
+  if (lo == u.n_knots) {
+    clamped = t > u.knot_time[k];
+  } else if (lo > 0) {
+    const double t0 = u.knot_time[k], t1 = u.knot_time[k + 1];
+    a = (float)((t - t0) / (t1 - t0));
+  }
+  const float* T = u.knot_T + 7 * (size_t)k;
+  float g0x, g0y, g0z;
+  transform_point(T[0], T[1], T[2], T[3], T[4], T[5], T[6], x, y, z, g0x, g0y, g0z);
+  if (a != 0.0f) {
+    float g1x, g1y, g1z;
+    transform_point(T[7], T[8], T[9], T[10], T[11], T[12], T[13], x, y, z, g1x, g1y, g1z);
+    g0x = g0x + a * (g1x - g0x);
+    g0y = g0y + a * (g1y - g0y);
+    g0z = g0z + a * (g1z - g0z);
+  }
+  x = g0x;
+  y = g0y;
+  z = g0z;
+}
+
+// one tile of a decode; u == nullptr unless DESKEW
+template <bool DWORDS, bool DESKEW>
+__device__ __forceinline__ void scan_decode_tile(const ScanMsg& m, const ScanDeskew* u, const TileChain& chain,
+                                                 float* __restrict__ points, uint32_t* __restrict__ rgba,
+                                                 unsigned long long* __restrict__ total) {
   __shared__ uint32_t sh_word, sh4[4];
   const uint32_t tile = chain_tile(chain, &sh_word);
   const uint32_t base = (tile * 256u + threadIdx.x) * (uint32_t)kScanIpt;  // (n < 2^31: no overflow)
   uint32_t x[kScanIpt], y[kScanIpt], z[kScanIpt], c[kScanIpt], keep = 0;
+  uint32_t counts = 0;  // DESKEW: this thread's bad times | overflowed << 10 | clamped << 20 (a wave's sum: 256 at most each)
 #pragma unroll
   for (int e = 0; e < kScanIpt; ++e) {
     const uint32_t i = base + (uint32_t)e;
@@ -72,9 +143,36 @@ __global__ __launch_bounds__(256) void scan_decode_kernel(ScanMsg m, TileChain c
       x[e] = scan_field<DWORDS>(p + m.offset_x);
       y[e] = scan_field<DWORDS>(p + m.offset_y);
       z[e] = scan_field<DWORDS>(p + m.offset_z);
-      if (scan_finite(x[e]) && scan_finite(y[e]) && scan_finite(z[e])) {
+      bool kept = scan_finite(x[e]) && scan_finite(y[e]) && scan_finite(z[e]);
+      if (DESKEW && kept) {
+        const double t = scan_time<DWORDS>(*u, p);
+        if (!(fabs(t) < INFINITY)) {
+          kept = false;
+          counts += 1u;
+        } else {
+          float gx = __uint_as_float(x[e]), gy = __uint_as_float(y[e]), gz = __uint_as_float(z[e]);
+          bool clamped;
+          scan_undistort(*u, t, gx, gy, gz, clamped);
+          x[e] = __float_as_uint(gx);
+          y[e] = __float_as_uint(gy);
+          z[e] = __float_as_uint(gz);
+          kept = scan_finite(x[e]) && scan_finite(y[e]) && scan_finite(z[e]);
+          counts += kept ? (clamped ? 1u << 20 : 0u) : 1u << 10;
+        }
+      }
+      if (kept) {
         keep |= 1u << e;
         if (m.color_kind != VGX_SCAN_COLOR_NONE) c[e] = scan_colour(m, scan_field<DWORDS>(p + m.color_offset));
+      }
+    }
+  }
+  if (DESKEW) {
+    for (int d = 32; d > 0; d >>= 1) counts += (uint32_t)__shfl_xor((int)counts, d);
+    if ((threadIdx.x & 63u) == 0) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const uint32_t v = (counts >> (10 * k)) & 0x3ffu;
+        if (v) atomicAdd(u->counters + k, (unsigned long long)v);
       }
     }
   }
@@ -95,6 +193,19 @@ __global__ __launch_bounds__(256) void scan_decode_kernel(ScanMsg m, TileChain c
   }
 }
 
+template <bool DWORDS>
+__global__ __launch_bounds__(256) void scan_decode_kernel(ScanMsg m, TileChain chain, float* __restrict__ points,
+                                                          uint32_t* __restrict__ rgba, unsigned long long* __restrict__ total) {
+  scan_decode_tile<DWORDS, false>(m, nullptr, chain, points, rgba, total);
+}
+
+template <bool DWORDS>
+__global__ __launch_bounds__(256) void scan_decode_undistort_kernel(ScanMsg m, ScanDeskew u, TileChain chain,
+                                                                    float* __restrict__ points, uint32_t* __restrict__ rgba,
+                                                                    unsigned long long* __restrict__ total) {
+  scan_decode_tile<DWORDS, true>(m, &u, chain, points, rgba, total);
+}
+
 }  // namespace vgx
 
 using namespace vgx;
@@ -103,12 +214,19 @@ struct vgx_scan_s {
   vgx_ctx ctx = nullptr;
   std::mutex mu;
   int64_t n_points = 0, n_dropped = 0;  // the scan held now
+  int64_t n_bad_time = 0, n_overflowed = 0, n_clamped = 0;  // (zeros after a plain decode)
   DeviceBuffer d_points;                // float [cap][3]: room for every point of the largest message so far
   DeviceBuffer d_rgba;                  // u32 [cap] bytes r g b a
   DeviceBuffer d_msg;                   // the host variant's upload
-  // TileChain of the decode kernel: {ticket, error, total} and one word per tile, tagged with the launch's epoch
+  // TileChain of the decode kernel: {ticket, error, total, three running counters} and one word per tile, tagged with
+  // the launch's epoch
   DeviceBuffer d_ctl, d_state;
   uint32_t epoch = 0, tickets = 0;
+  // the undistorting decode: the track's upload (knot times, then knot transforms), and what the three running counters
+  // of d_ctl held at the last read-back (not known after a launch whose read-back failed: cleared before the next)
+  DeviceBuffer d_knots;
+  unsigned long long counters_base[3] = {0, 0, 0};
+  bool counters_known = true;
   UploadStage stage;      // host variant: halves of kScanStageBytes, allocated at first use
   bool pageable = false;  // no pinned memory was to be had: uploads go straight from the caller's bytes
 };
@@ -153,6 +271,33 @@ int scan_check(const vgx_scan_layout* l, const vgx_scan_config* c, int64_t n_byt
   return VGX_OK;
 }
 
+// Everything an undistorting decode is refused for on top of scan_check.
+int scan_undistort_check(const vgx_scan_layout* l, const vgx_scan_config* c, const vgx_scan_time_field* f, const vgx_scan_track* tr,
+                         int64_t n_bytes, std::string* why) {
+  auto fail = [why](const char* msg) {
+    if (why) *why = msg;
+    return (int)VGX_ERR_INVALID;
+  };
+  if (!f) return fail("NULL time field");
+  if (!tr) return fail("NULL track");
+  const int rc = scan_check(l, c, n_bytes, why);
+  if (rc != VGX_OK) return rc;
+  if (f->kind != VGX_SCAN_TIME_UINT32 && f->kind != VGX_SCAN_TIME_FLOAT32 && f->kind != VGX_SCAN_TIME_FLOAT64)
+    return fail("unknown time kind");
+  if ((uint64_t)f->offset + (f->kind == VGX_SCAN_TIME_FLOAT64 ? 8u : 4u) > (uint64_t)l->point_step)
+    return fail("the time field does not fit in point_step");
+  if (!std::isfinite(f->scale) || !std::isfinite(f->offset_s)) return fail("the time field's scale or offset_s is not finite");
+  if (tr->n_knots < 1 || tr->n_knots > VGX_SCAN_TRACK_MAX_KNOTS) return fail("n_knots is not in 1 .. 65536");
+  if (!tr->knot_time || !tr->knot_T) return fail("NULL knot array");
+  for (int32_t k = 0; k < tr->n_knots; ++k) {
+    if (!std::isfinite(tr->knot_time[k]) || (k > 0 && !(tr->knot_time[k] > tr->knot_time[k - 1])))
+      return fail("the knot times are not finite and strictly ascending");
+    for (int j = 0; j < 7; ++j)
+      if (!std::isfinite(tr->knot_T[7 * (size_t)k + j])) return fail("a knot_T entry is not finite");
+  }
+  return VGX_OK;
+}
+
 // the caller's bytes -> S->d_msg on stream st.  Through the pinned buffers piece by piece: the host copy of piece k
 // overlaps the upload of piece k - 1, and the caller's bytes have been read when the last piece is queued.
 int scan_upload(vgx_scan S, hipStream_t st, const void* data, size_t bytes) {
@@ -181,8 +326,10 @@ int scan_upload(vgx_scan S, hipStream_t st, const void* data, size_t bytes) {
 }
 
 // The decode of a message at d_data (device) on the TSDF stream; the caller holds S->mu and ctx->tsdf_mu, the device is
-// set, the layout has passed scan_check.  Ends with the call's one host synchronisation.
-int scan_decode_queued(vgx_scan S, const vgx_scan_layout& l, const vgx_scan_config& c, const uint8_t* d_data) {
+// set, the layout (and f, tr where given: the undistorting decode) has passed its check.  Ends with the call's one host
+// synchronisation.
+int scan_decode_queued(vgx_scan S, const vgx_scan_layout& l, const vgx_scan_config& c, const vgx_scan_time_field* f,
+                       const vgx_scan_track* tr, const uint8_t* d_data) {
   vgx_ctx ctx = S->ctx;
   hipStream_t st = ctx->tsdf_stream;
   const uint32_t n = l.width * l.height;
@@ -230,16 +377,49 @@ int scan_decode_queued(vgx_scan S, const vgx_scan_layout& l, const vgx_scan_conf
   m.intensity_min = c.intensity_min;
   m.intensity_max = c.intensity_max;
   std::memcpy(&m.constant, c.constant_rgba, 4);
-  const bool dwords = ((uintptr_t)d_data | l.point_step | l.row_step | l.offset_x | l.offset_y | l.offset_z | m.color_offset) % 4 == 0;
-  if (dwords)
-    hipLaunchKernelGGL(scan_decode_kernel<true>, dim3(tiles), dim3(256), 0, st, m, chain, S->d_points.as<float>(),
-                       S->d_rgba.as<uint32_t>(), ctl + kScanTotal);
-  else
-    hipLaunchKernelGGL(scan_decode_kernel<false>, dim3(tiles), dim3(256), 0, st, m, chain, S->d_points.as<float>(),
-                       S->d_rgba.as<uint32_t>(), ctl + kScanTotal);
+  bool dwords = ((uintptr_t)d_data | l.point_step | l.row_step | l.offset_x | l.offset_y | l.offset_z | m.color_offset) % 4 == 0;
+  if (!tr) {
+    if (dwords)
+      hipLaunchKernelGGL(scan_decode_kernel<true>, dim3(tiles), dim3(256), 0, st, m, chain, S->d_points.as<float>(),
+                         S->d_rgba.as<uint32_t>(), ctl + kScanTotal);
+    else
+      hipLaunchKernelGGL(scan_decode_kernel<false>, dim3(tiles), dim3(256), 0, st, m, chain, S->d_points.as<float>(),
+                         S->d_rgba.as<uint32_t>(), ctl + kScanTotal);
+  } else {
+    // the track goes up ahead of the launch: the times, then the transforms, in one buffer of the handle's
+    const size_t K = (size_t)tr->n_knots;
+    if (K * 36 > S->d_knots.bytes) {
+      VGX_HIP(ctx, hipStreamSynchronize(st));
+      const hipError_t e = S->d_knots.alloc(K * 36);
+      if (e != hipSuccess) return alloc_error(ctx, e, "scan: allocating the track");
+    }
+    VGX_HIP(ctx, hipMemcpyAsync(S->d_knots.p, tr->knot_time, K * 8, hipMemcpyHostToDevice, st));
+    VGX_HIP(ctx, hipMemcpyAsync(S->d_knots.as<char>() + K * 8, tr->knot_T, K * 28, hipMemcpyHostToDevice, st));
+    if (!S->counters_known) {
+      VGX_HIP(ctx, hipMemsetAsync(ctl + kScanBadTime, 0, 24, st));
+      S->counters_base[0] = S->counters_base[1] = S->counters_base[2] = 0;
+    }
+    S->counters_known = false;
+    ScanDeskew u{};
+    u.knot_time = S->d_knots.as<double>();
+    u.knot_T = reinterpret_cast<const float*>(S->d_knots.as<char>() + K * 8);
+    u.n_knots = tr->n_knots;
+    u.time_kind = f->kind;
+    u.time_offset = f->offset;
+    u.scale = f->scale;
+    u.offset_s = f->offset_s;
+    u.counters = ctl + kScanBadTime;
+    dwords = dwords && f->offset % 4 == 0;
+    if (dwords)
+      hipLaunchKernelGGL(scan_decode_undistort_kernel<true>, dim3(tiles), dim3(256), 0, st, m, u, chain, S->d_points.as<float>(),
+                         S->d_rgba.as<uint32_t>(), ctl + kScanTotal);
+    else
+      hipLaunchKernelGGL(scan_decode_undistort_kernel<false>, dim3(tiles), dim3(256), 0, st, m, u, chain, S->d_points.as<float>(),
+                         S->d_rgba.as<uint32_t>(), ctl + kScanTotal);
+  }
   VGX_HIP(ctx, hipGetLastError());
-  unsigned long long back[2] = {0, 0};  // {error, total}
-  VGX_HIP(ctx, hipMemcpyAsync(back, ctl + kScanError, 16, hipMemcpyDeviceToHost, st));
+  unsigned long long back[5] = {0, 0, 0, 0, 0};  // {error, total} and, undistorting, the three running counters
+  VGX_HIP(ctx, hipMemcpyAsync(back, ctl + kScanError, tr ? 40 : 16, hipMemcpyDeviceToHost, st));
   VGX_HIP(ctx, hipStreamSynchronize(st));
   if (back[0] != 0) {
     (void)hipMemsetAsync(ctl + kScanError, 0, 8, st);
@@ -247,18 +427,26 @@ int scan_decode_queued(vgx_scan S, const vgx_scan_layout& l, const vgx_scan_conf
   }
   S->n_points = (int64_t)back[1];
   S->n_dropped = (int64_t)n - S->n_points;
+  if (tr) {
+    S->n_bad_time = (int64_t)(back[2] - S->counters_base[0]);
+    S->n_overflowed = (int64_t)(back[3] - S->counters_base[1]);
+    S->n_clamped = (int64_t)(back[4] - S->counters_base[2]);
+    for (int k = 0; k < 3; ++k) S->counters_base[k] = back[2 + k];
+    S->counters_known = true;
+  }
   return VGX_OK;
 }
 
-int scan_decode(const char* fn, vgx_scan S, const vgx_scan_layout* l, const vgx_scan_config* cfg, const void* data, int64_t n_bytes,
-                bool on_device) {
+// f, tr: the undistorting decode's time field and track; both NULL for the plain decode
+int scan_decode(const char* fn, vgx_scan S, const vgx_scan_layout* l, const vgx_scan_config* cfg, bool undistort,
+                const vgx_scan_time_field* f, const vgx_scan_track* tr, const void* data, int64_t n_bytes, bool on_device) {
   if (!S) return VGX_ERR_INVALID;
   vgx_ctx ctx = S->ctx;
   vgx_scan_config c;
   vgx_scan_config_default(&c);
   if (cfg) c = *cfg;
   std::string why;
-  int rc = scan_check(l, &c, n_bytes, &why);
+  int rc = undistort ? scan_undistort_check(l, &c, f, tr, n_bytes, &why) : scan_check(l, &c, n_bytes, &why);
   const size_t n = rc == VGX_OK ? (size_t)l->width * l->height : 0;
   if (rc == VGX_OK && n > 0 && !data) {
     rc = VGX_ERR_INVALID;
@@ -269,6 +457,7 @@ int scan_decode(const char* fn, vgx_scan S, const vgx_scan_layout* l, const vgx_
   std::lock_guard<std::mutex> tsdf_lk(ctx->tsdf_mu);
   VGX_HIP(ctx, hipSetDevice(ctx->device));
   S->n_points = S->n_dropped = 0;  // (what a failure below leaves: no scan)
+  S->n_bad_time = S->n_overflowed = S->n_clamped = 0;
   if (n == 0) return VGX_OK;
   const uint8_t* d_data = static_cast<const uint8_t*>(data);
   if (!on_device) {
@@ -282,7 +471,7 @@ int scan_decode(const char* fn, vgx_scan S, const vgx_scan_layout* l, const vgx_
     if (rc != VGX_OK) return rc;
     d_data = S->d_msg.as<uint8_t>();
   }
-  return scan_decode_queued(S, *l, c, d_data);
+  return scan_decode_queued(S, *l, c, undistort ? f : nullptr, undistort ? tr : nullptr, d_data);
 }
 
 int scan_integrate(const char* fn, bool merged, vgx_tsdf_integrator I, const float T[7], vgx_scan S, int32_t freespace,
@@ -311,6 +500,11 @@ void vgx_scan_config_default(vgx_scan_config* cfg) {
 
 int vgx_scan_layout_check(const vgx_scan_layout* layout, int64_t n_bytes) { return scan_check(layout, nullptr, n_bytes, nullptr); }
 
+int vgx_scan_undistort_check(const vgx_scan_layout* layout, const vgx_scan_time_field* time_field, const vgx_scan_track* track,
+                             int64_t n_bytes) {
+  return scan_undistort_check(layout, nullptr, time_field, track, n_bytes, nullptr);
+}
+
 int vgx_scan_create(vgx_ctx ctx, vgx_scan* out) {
   if (!ctx || !out) return set_error(ctx, VGX_ERR_INVALID, "vgx_scan_create: NULL argument");
   vgx_scan S = new vgx_scan_s;
@@ -332,12 +526,33 @@ int vgx_scan_destroy(vgx_scan S) {
 }
 
 int vgx_scan_decode_msg(vgx_scan S, const vgx_scan_layout* layout, const vgx_scan_config* cfg, const void* data, int64_t n_bytes) {
-  return scan_decode("vgx_scan_decode_msg", S, layout, cfg, data, n_bytes, false);
+  return scan_decode("vgx_scan_decode_msg", S, layout, cfg, false, nullptr, nullptr, data, n_bytes, false);
 }
 
 int vgx_scan_decode_msg_device(vgx_scan S, const vgx_scan_layout* layout, const vgx_scan_config* cfg, const void* d_data,
                                int64_t n_bytes) {
-  return scan_decode("vgx_scan_decode_msg_device", S, layout, cfg, d_data, n_bytes, true);
+  return scan_decode("vgx_scan_decode_msg_device", S, layout, cfg, false, nullptr, nullptr, d_data, n_bytes, true);
+}
+
+int vgx_scan_decode_msg_undistorted(vgx_scan S, const vgx_scan_layout* layout, const vgx_scan_config* cfg,
+                                    const vgx_scan_time_field* time_field, const vgx_scan_track* track, const void* data,
+                                    int64_t n_bytes) {
+  return scan_decode("vgx_scan_decode_msg_undistorted", S, layout, cfg, true, time_field, track, data, n_bytes, false);
+}
+
+int vgx_scan_decode_msg_undistorted_device(vgx_scan S, const vgx_scan_layout* layout, const vgx_scan_config* cfg,
+                                           const vgx_scan_time_field* time_field, const vgx_scan_track* track, const void* d_data,
+                                           int64_t n_bytes) {
+  return scan_decode("vgx_scan_decode_msg_undistorted_device", S, layout, cfg, true, time_field, track, d_data, n_bytes, true);
+}
+
+int vgx_scan_undistort_stats(vgx_scan S, int64_t* n_bad_time, int64_t* n_overflowed, int64_t* n_clamped) {
+  if (!S) return VGX_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(S->mu);
+  if (n_bad_time) *n_bad_time = S->n_bad_time;
+  if (n_overflowed) *n_overflowed = S->n_overflowed;
+  if (n_clamped) *n_clamped = S->n_clamped;
+  return VGX_OK;
 }
 
 int vgx_scan_stats(vgx_scan S, int64_t* n_points, int64_t* n_dropped) {
