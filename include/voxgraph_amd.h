@@ -1924,6 +1924,117 @@ VGX_API int vgx_scan_registration_refine(vgx_scan_registration reg, vgx_tsdf_lay
 VGX_API int vgx_scan_registration_history(vgx_scan_registration reg, int32_t capacity, vgx_pose_graph_iteration* iterations,
                                           int32_t* n_iterations);
 
+/* ---- View rendering: range images ray-marched out of a TSDF layer ------------ */
+/* What the map looks like from a pose: per ray the range to the zero crossing of the trilinear TSDF, the surface point,
+ * the gradient, the weight and the colour there -- the inverse of vgx_tsdf_integrate.  DEFINED HERE, not recalled:
+ * voxblox has no ray caster over a layer (its RayCaster walks voxel indices for the integrators), DESIGN.md 27.  The
+ * rules are built so that a numpy restatement reproduces every bit (tests/view_render_ref.py): f32, one rounding per
+ * operation, no contraction, no transcendental or square root on the device, no float atomics.
+ *
+ * INPUTS.  A TSDF layer; a sensor pose T_L_C = {qw,qx,qy,qz, tx,ty,tz} (f32) in the layer's frame; n ray directions
+ * dir [n][3] (f32) in the sensor frame.  The library NEVER normalises a direction: the ray parameter s is in units of
+ * |dir| -- metres for unit directions -- and so are s_min, s_max, min_step, unknown_step and max_bracket.
+ *
+ * PER RAY.  o = t, d = R dir (Eigen _transformVector, the association of the map queries and scan registration).  A
+ * ray whose dir has a non-finite component or is exactly (+-0, +-0, +-0) has status BAD and takes no sample.  Otherwise
+ * s = s_min, have = false, and repeat:
+ *   1. if !(s <= s_max): MISS.
+ *   2. p_a = d_a * s + o_a (a multiply, then an add).
+ *   3. the sample is INVALID unless |p_a * block_size_inv| < 2^30 on every axis (a non-finite p fails) and
+ *      Interpolator<TsdfVoxel>::getVoxel(p, ., true) would succeed: all 8 neighbours' blocks exist, all 8 weights > 0.
+ *   4. valid: D = the trilinear distance over the 8 neighbours (the interpolant of the map queries), and
+ *        D > 0:        have = true; s0 = s; D0 = D; s = s + (D * step_scale > min_step ? D * step_scale : min_step)
+ *        not (D > 0):  HIT when have and (s - s0) <= max_bracket, with s_hit = s0 + (s - s0) * (D0 / (D0 - D));
+ *                      otherwise INSIDE -- the ray met the surface from behind, out of unknown space, or across a gap
+ *                      too wide to interpolate over
+ *      invalid: s = s + unknown_step; have, s0 and D0 are kept.
+ * AT A HIT one more sample at p_hit = d * s_hit + o.  Valid: status HIT, gradient_a = (dD/d dl_a) * voxel_size_inv (the
+ * exact derivative of the interpolant, "Scan-to-map registration"; layer frame, not normalised), weight = the
+ * interpolated weight, rgba = the interpolated colour of the map products (per channel, clamped to [0, 255], truncated)
+ * where the layer has colours, else 0.  Invalid: status HIT_UNSAMPLED, those three +0.  Either way range = s_hit and
+ * points = dir_a * s_hit in the SENSOR frame (unit pinhole rays: points[..][2] is the z-depth).  Without a hit range and
+ * points are +0: the integrators drop such points while min_ray_length_m > 0, and scan-to-map registration needs
+ * min_range_m > 0 to do the same.  n_samples counts the positions sampled (step 2), valid or not, plus the one at the hit.
+ *
+ * s_max / min(min_step, unknown_step) <= 65536 bounds the loop and keeps every increment far above one ulp of s.
+ * s_max, min_step, unknown_step and max_bracket have NO default (0 is refused); a starting point is the reach wanted,
+ * voxel_size / 4, voxel_size and the layer's truncation distance.
+ *
+ * image_width > 0 only changes which lane takes which ray (ray i is pixel (i % image_width, i / image_width); a wave
+ * takes an 8 x 8 tile, so its rays stay in neighbouring voxels); the results are the same bits.  The counts are int64
+ * sums (integer atomics).  A vgx_view owns the device outputs (range and status always, the others by flag), grown on
+ * demand; its device pointers hold until a later render grows them or the view is destroyed.  points plugs into
+ * vgx_scan_registration_set_points_device and vgx_tsdf_integrate_device as it stands.
+ *
+ * vgx_tsdf_layer_render_view (the active layer, the projected map) runs on the TSDF stream under the integrators' lock,
+ * ordered behind every scan already queued; vgx_submap_render_view reads a finished submap's raw TSDF layer on the
+ * registration stream under its lock, the pose in the submap's frame.  One launch, one 64-byte copy of the counts and
+ * one host synchronisation per call; the host-pointer forms copy the directions first.  One call at a time per handle.
+ *
+ * Refused with VGX_ERR_INVALID, nothing written: NULL arguments; a layer or submap of another context; n < 0; a pose
+ * that is not finite or whose quaternion has | |q|^2 - 1 | > 1e-4; a submap whose raw layers were released; at creation
+ * any field that is not finite, s_min < 0, s_min > s_max, step_scale <= 0, s_max / min_step / unknown_step /
+ * max_bracket <= 0, s_max / min(min_step, unknown_step) > 65536, image_width < 0, unknown flag bits;
+ * vgx_view_download of an output the flags do not hold.  VGX_ERR_UNSUPPORTED: voxels_per_side other than 8 or 16; more
+ * rays than one launch takes.  n = 0: VGX_OK, the view then holds no ray. */
+#define VGX_VIEW_MISS 0
+#define VGX_VIEW_HIT 1
+#define VGX_VIEW_INSIDE 2
+#define VGX_VIEW_BAD 3
+#define VGX_VIEW_HIT_UNSAMPLED 4
+#define VGX_VIEW_POINTS 1
+#define VGX_VIEW_GRADIENT 2
+#define VGX_VIEW_WEIGHT 4
+#define VGX_VIEW_RGBA 8
+#define VGX_VIEW_N_SAMPLES 16
+#define VGX_VIEW_ALL 31
+typedef struct vgx_view_s* vgx_view;
+typedef struct vgx_view_config {
+  float s_min;         /* 0 */
+  float s_max;         /* NO default (0: refused) */
+  float step_scale;    /* 0.75 */
+  float min_step;      /* NO default: e.g. voxel_size / 4 */
+  float unknown_step;  /* NO default: e.g. voxel_size */
+  float max_bracket;   /* NO default: e.g. the layer's truncation distance */
+  int32_t image_width; /* 0: rays map to lanes by index */
+  int32_t flags;       /* VGX_VIEW_POINTS; which optional outputs the view holds */
+} vgx_view_config;
+typedef struct vgx_view_counts {
+  int64_t n_rays, n_hit, n_hit_unsampled, n_miss, n_inside, n_bad;
+  int64_t n_samples;
+  int64_t reserved;
+} vgx_view_counts;
+VGX_API void vgx_view_config_default(vgx_view_config* cfg);
+/* host only: VGX_OK, or VGX_ERR_INVALID where vgx_view_create would refuse the config */
+VGX_API int vgx_view_config_check(const vgx_view_config* cfg);
+VGX_API int vgx_view_create(vgx_ctx ctx, const vgx_view_config* cfg, vgx_view* out);
+VGX_API int vgx_view_destroy(vgx_view view);
+/* the counts of the view held now (all zero before the first render) */
+VGX_API int vgx_view_stats(vgx_view view, vgx_view_counts* counts);
+/* every array nullable; range [n] f32, status [n] u8, points / gradient [n][3] f32, weight [n] f32, rgba [n] u32 (bytes
+ * r g b a, r lowest), n_samples [n] i32, n = counts.n_rays */
+VGX_API int vgx_view_download(vgx_view view, float* range, uint8_t* status, float* points, float* gradient, float* weight,
+                              uint32_t* rgba, int32_t* n_samples);
+/* NULL for an output the view does not hold, and for all of them while it holds no ray */
+VGX_API int vgx_view_device_pointers(vgx_view view, const float** range, const uint8_t** status, const float** points,
+                                     const float** gradient, const float** weight, const uint32_t** rgba,
+                                     const int32_t** n_samples);
+VGX_API int vgx_tsdf_layer_render_view(vgx_tsdf_layer layer, vgx_view view, const float T_L_C[7], int64_t n,
+                                       const float* dirs /* host [n][3] */);
+VGX_API int vgx_tsdf_layer_render_view_device(vgx_tsdf_layer layer, vgx_view view, const float T_L_C[7], int64_t n,
+                                              const void* d_dirs /* f32 [n][3], ready with respect to the TSDF stream */);
+VGX_API int vgx_submap_render_view(vgx_submap submap, vgx_view view, const float T_S_C[7], int64_t n, const float* dirs);
+VGX_API int vgx_submap_render_view_device(vgx_submap submap, vgx_view view, const float T_S_C[7], int64_t n,
+                                          const void* d_dirs /* ready with respect to the registration stream */);
+/* Host-only ray helpers: unit directions computed in f64 and rounded to f32 once, row-major dirs[row][col][3].
+ * pinhole: ((u - cx) / fx, (v - cy) / fy, 1) normalised, u the column, v the row.
+ * lidar:   az = -pi + azimuth_offset + col * 2 pi / width, el = elevation_min + row * (elevation_max - elevation_min) /
+ *          (height - 1) (height 1: elevation_min), dir = (cos el cos az, cos el sin az, sin el).
+ * VGX_ERR_INVALID: width or height < 1, NULL dirs, a parameter that is not finite, fx or fy zero. */
+VGX_API int vgx_view_rays_pinhole(int32_t width, int32_t height, double fx, double fy, double cx, double cy, float* dirs);
+VGX_API int vgx_view_rays_lidar(int32_t width, int32_t height, double elevation_min, double elevation_max,
+                                double azimuth_offset, float* dirs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -200,6 +200,22 @@ class ScanRegistrationSummary(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+class ViewConfig(C.Structure):
+    _fields_ = [("s_min", C.c_float), ("s_max", C.c_float), ("step_scale", C.c_float), ("min_step", C.c_float),
+                ("unknown_step", C.c_float), ("max_bracket", C.c_float), ("image_width", C.c_int32), ("flags", C.c_int32)]
+
+
+class ViewCounts(C.Structure):
+    _fields_ = [("n_rays", C.c_int64), ("n_hit", C.c_int64), ("n_hit_unsampled", C.c_int64), ("n_miss", C.c_int64),
+                ("n_inside", C.c_int64), ("n_bad", C.c_int64), ("n_samples", C.c_int64), ("reserved", C.c_int64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+VIEW_MISS, VIEW_HIT, VIEW_INSIDE, VIEW_BAD, VIEW_HIT_UNSAMPLED = range(5)
+VIEW_POINTS, VIEW_GRADIENT, VIEW_WEIGHT, VIEW_RGBA, VIEW_N_SAMPLES, VIEW_ALL = 1, 2, 4, 8, 16, 31
+
 LINEAR_SOLVER_DENSE, LINEAR_SOLVER_TILE_SPARSE = 0, 1
 ORDER_NATURAL, ORDER_RCM, ORDER_GIVEN = 0, 1, 2
 CONVERGENCE, NO_CONVERGENCE, FAILURE = 0, 1, 2      # ceres::TerminationType
@@ -433,6 +449,19 @@ SIGNATURES = {
     "vgx_scan_registration_refine": (C.c_int, [vp, vp, f32p, C.POINTER(PoseGraphOptions), f32p, f64p,
                                                C.POINTER(ScanRegistrationSummary)]),
     "vgx_scan_registration_history": (C.c_int, [vp, C.c_int32, C.POINTER(PoseGraphIteration), i32p]),
+    "vgx_view_config_default": (None, [C.POINTER(ViewConfig)]),
+    "vgx_view_config_check": (C.c_int, [C.POINTER(ViewConfig)]),
+    "vgx_view_create": (C.c_int, [vp, C.POINTER(ViewConfig), C.POINTER(vp)]),
+    "vgx_view_destroy": (C.c_int, [vp]),
+    "vgx_view_stats": (C.c_int, [vp, C.POINTER(ViewCounts)]),
+    "vgx_view_download": (C.c_int, [vp, f32p, u8p, f32p, f32p, f32p, u32p, i32p]),
+    "vgx_view_device_pointers": (C.c_int, [vp] + [C.POINTER(vp)] * 7),
+    "vgx_tsdf_layer_render_view": (C.c_int, [vp, vp, f32p, C.c_int64, f32p]),
+    "vgx_tsdf_layer_render_view_device": (C.c_int, [vp, vp, f32p, C.c_int64, vp]),
+    "vgx_submap_render_view": (C.c_int, [vp, vp, f32p, C.c_int64, f32p]),
+    "vgx_submap_render_view_device": (C.c_int, [vp, vp, f32p, C.c_int64, vp]),
+    "vgx_view_rays_pinhole": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, f32p]),
+    "vgx_view_rays_lidar": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, f32p]),
 }
 
 # every symbol include/voxgraph_amd_bench.h declares (libvoxgraph_amd_bench.so: test and benchmark tooling)
@@ -832,6 +861,13 @@ class Submap:
         t = None if T is None else np.ascontiguousarray(T, np.float32).reshape(12)
         self.ctx.check(self.ctx.lib.vgx_submap_surface_msg(self.h, int(point_type), _ptr(t, f32p), msg.h))
         return msg
+
+    def render_view(self, view, T_S_C, dirs, n=None):
+        """The view of this submap's raw TSDF layer from sensor pose T_S_C (submap frame) along dirs [n][3]
+        (vgx_submap_render_view / _device: a numpy array, a torch device tensor, or a device address with n).  Returns
+        the View."""
+        lib = self.ctx.lib
+        return _render_view(self.ctx, lib.vgx_submap_render_view, lib.vgx_submap_render_view_device, self, view, T_S_C, dirs, n)
 
     def release_raw_layers(self):
         self.ctx.check(self.ctx.lib.vgx_submap_release_raw_layers(self.h))
@@ -1553,6 +1589,12 @@ class TsdfLayer:
         self.ctx.check(self.ctx.lib.vgx_tsdf_layer_cloud(self.h, None if config is None else C.byref(config), cloud.h))
         return cloud
 
+    def render_view(self, view, T_L_C, dirs, n=None):
+        """The view of this layer from sensor pose T_L_C along dirs [n][3] (vgx_tsdf_layer_render_view / _device: a numpy
+        array, a torch device tensor, or a device address with n), behind every scan queued.  Returns the View."""
+        lib = self.ctx.lib
+        return _render_view(self.ctx, lib.vgx_tsdf_layer_render_view, lib.vgx_tsdf_layer_render_view_device, self, view, T_L_C, dirs, n)
+
     def serialize(self, msg=None):
         """voxblox::serializeLayerAsMsg of this layer, colours included (vgx_tsdf_layer_serialize).  Returns the MapMsg
         (a new one when msg is None)."""
@@ -2010,6 +2052,106 @@ class ScanRegistration:
     def destroy(self):
         if self.h:
             self.ctx.lib.vgx_scan_registration_destroy(self.h)
+            self.h = None
+
+
+def view_config(s_max, min_step, unknown_step, max_bracket, **kw):
+    """vgx_view_config: the defaults, the four fields that have none and fields overridden by keyword (s_min, step_scale,
+    image_width, flags)"""
+    cfg = ViewConfig()
+    load().vgx_view_config_default(C.byref(cfg))
+    cfg.s_max, cfg.min_step, cfg.unknown_step, cfg.max_bracket = s_max, min_step, unknown_step, max_bracket
+    for k, v in kw.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(k)
+        setattr(cfg, k, v)
+    return cfg
+
+
+def view_config_check(config):
+    """vgx_view_config_check (host only): OK, or the code vgx_view_create refuses this config with"""
+    return load().vgx_view_config_check(None if config is None else C.byref(config))
+
+
+def view_rays_pinhole(width, height, fx, fy, cx, cy):
+    """vgx_view_rays_pinhole (host only): unit directions [height * width][3] f32, row-major"""
+    dirs = np.zeros((int(height) * int(width), 3), np.float32)
+    rc = load().vgx_view_rays_pinhole(int(width), int(height), float(fx), float(fy), float(cx), float(cy), _ptr(dirs, f32p))
+    if rc != OK:
+        raise VgxError(rc, "vgx_view_rays_pinhole: width or height < 1, a parameter not finite, or a zero focal length")
+    return dirs
+
+
+def view_rays_lidar(width, height, elevation_min, elevation_max, azimuth_offset=0.0):
+    """vgx_view_rays_lidar (host only): unit directions [height * width][3] f32, row-major (one row per elevation)"""
+    dirs = np.zeros((int(height) * int(width), 3), np.float32)
+    rc = load().vgx_view_rays_lidar(int(width), int(height), float(elevation_min), float(elevation_max), float(azimuth_offset),
+                                    _ptr(dirs, f32p))
+    if rc != OK:
+        raise VgxError(rc, "vgx_view_rays_lidar: width or height < 1, or a parameter not finite")
+    return dirs
+
+
+ViewImage = collections.namedtuple("ViewImage", ["range", "status", "points", "gradient", "weight", "rgba", "n_samples"])
+
+
+def _render_view(ctx, host_call, device_call, source, view, T, dirs, n):
+    """dirs: a numpy array [n][3] (copied), a torch device tensor [n][3] f32, or a device address as an int with n"""
+    T = _f32(T)
+    if isinstance(dirs, int):
+        ctx.check(device_call(source.h, view.h, _ptr(T, f32p), int(n), vp(dirs) if dirs else None))
+    elif hasattr(dirs, "data_ptr"):
+        if not dirs.is_cuda or str(dirs.dtype) != "torch.float32" or not dirs.is_contiguous():
+            raise TypeError("a contiguous float32 device tensor [n][3]")
+        m = dirs.numel() // 3
+        ctx.check(device_call(source.h, view.h, _ptr(T, f32p), m, vp(dirs.data_ptr()) if m else None))
+    else:
+        d = _f32(dirs).reshape(-1, 3)
+        ctx.check(host_call(source.h, view.h, _ptr(T, f32p), len(d), _ptr(d, f32p) if len(d) else None))
+    return view
+
+
+class View:
+    """A rendered view on the GPU (vgx_view): per ray range, status and -- by the config's flags -- sensor-frame point,
+    gradient, weight, colour and sample count; reused from call to call."""
+
+    def __init__(self, ctx, config):
+        self.ctx = ctx
+        self.flags = 0 if config is None else int(config.flags)
+        h = vp()
+        ctx.check(ctx.lib.vgx_view_create(ctx.h, None if config is None else C.byref(config), C.byref(h)))
+        self.h = h
+
+    def stats(self):
+        """the counts of the view held now: n_rays, n_hit, n_hit_unsampled, n_miss, n_inside, n_bad, n_samples"""
+        c = ViewCounts()
+        self.ctx.check(self.ctx.lib.vgx_view_stats(self.h, C.byref(c)))
+        return c.as_dict()
+
+    def download(self):
+        """ViewImage(range [n] f32, status [n] u8, points [n][3], gradient [n][3], weight [n], rgba [n][4] u8, n_samples
+        [n] i32); None for an output the flags do not hold"""
+        n, f = self.stats()["n_rays"], self.flags
+        rng, status = np.zeros(n, np.float32), np.zeros(n, np.uint8)
+        points = np.zeros((n, 3), np.float32) if f & VIEW_POINTS else None
+        gradient = np.zeros((n, 3), np.float32) if f & VIEW_GRADIENT else None
+        weight = np.zeros(n, np.float32) if f & VIEW_WEIGHT else None
+        rgba = np.zeros((n, 4), np.uint8) if f & VIEW_RGBA else None
+        samples = np.zeros(n, np.int32) if f & VIEW_N_SAMPLES else None
+        self.ctx.check(self.ctx.lib.vgx_view_download(self.h, _ptr(rng, f32p), _ptr(status, u8p), _ptr(points, f32p),
+                                                      _ptr(gradient, f32p), _ptr(weight, f32p), _ptr(rgba, u32p),
+                                                      _ptr(samples, i32p)))
+        return ViewImage(rng, status, points, gradient, weight, rgba, samples)
+
+    def device_pointers(self):
+        """ViewImage of device addresses as ints (None where the view holds none)"""
+        p = [vp() for _ in range(7)]
+        self.ctx.check(self.ctx.lib.vgx_view_device_pointers(self.h, *[C.byref(x) for x in p]))
+        return ViewImage(*[x.value for x in p])
+
+    def destroy(self):
+        if self.h:
+            self.ctx.lib.vgx_view_destroy(self.h)
             self.h = None
 
 

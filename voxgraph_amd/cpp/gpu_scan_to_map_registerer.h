@@ -61,6 +61,13 @@ class GpuScanToMapRegisterer {
       throw std::runtime_error(std::string("vgx_scan_registration_set_points: ") + vgx_last_error(ctx_));
     return refine(T_S_C_prior, T_S_C_refined);
   }
+  // device points [n][3] f32, sensor frame, ready with respect to the TSDF stream (borrowed): a rendered view's points
+  // (GpuViewRenderer::renderInto)
+  bool refineSensorPoseDevice(const void* d_points_C, int64_t n_points, const float T_S_C_prior[7], float T_S_C_refined[7]) {
+    if (vgx_scan_registration_set_points_device(reg_, d_points_C, n_points) != VGX_OK)
+      throw std::runtime_error(std::string("vgx_scan_registration_set_points_device: ") + vgx_last_error(ctx_));
+    return refine(T_S_C_prior, T_S_C_refined);
+  }
   // voxblox::Pointcloud (AlignedVector<Eigen::Vector3f>: contiguous 12-byte elements), poses as {qw,qx,qy,qz, tx,ty,tz}
   template <class Pointcloud, class = typename Pointcloud::value_type>
   bool refineSensorPose(const Pointcloud& points_C, const float T_S_C_prior[7], float T_S_C_refined[7]) {
