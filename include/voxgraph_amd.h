@@ -1772,8 +1772,9 @@ VGX_API int vgx_dense_spd_solve_many(vgx_ctx ctx, int32_t n, const double* A, in
  * reverse.  At most 2^27 free nodes.  The host lists and the structure are sized by the graph: out of host memory is
  * VGX_ERR_NOMEM from the same calls (and from vgx_pose_graph_tile_pattern and vgx_block_spd_solve).
  * vgx_pose_graph_covariance keeps the DENSE factor and its limit whatever the solver setting: on a graph with more than
- * 4096 free nodes it returns VGX_ERR_UNSUPPORTED, `covariance` untouched.  Selected inversion on the sparse factor is
- * not done.  vgx_pose_graph_download_system in sparse mode returns H dense, in ascending node order, when
+ * 4096 free nodes it returns VGX_ERR_UNSUPPORTED, `covariance` untouched; vgx_pose_graph_covariance_sparse ("Pose graph:
+ * edge covariances on the tile-sparse factor" below) solves the same columns on the sparse factor and has no such limit.
+ * vgx_pose_graph_download_system in sparse mode returns H dense, in ascending node order, when
  * 4 x free nodes <= 16384; beyond, VGX_ERR_UNSUPPORTED with g still delivered. */
 #define VGX_LINEAR_SOLVER_DENSE 0
 #define VGX_LINEAR_SOLVER_TILE_SPARSE 1
@@ -1825,6 +1826,71 @@ VGX_API int vgx_pose_graph_tile_pattern(int32_t n_free_nodes, int32_t n_pairs, c
 VGX_API int vgx_block_spd_solve(vgx_ctx ctx, int32_t n_block_rows, int32_t nnz, const int32_t* bi, const int32_t* bj,
                                 const double* values /* [nnz][16] */, const double* b, double* x,
                                 vgx_pose_graph_structure_stats* stats, int32_t* tile_index, double* tile_values);
+
+/* ---- Pose graph: edge covariances on the tile-sparse factor ---------------- */
+/* vgx_pose_graph_covariance on the factor of the tile-sparse solver: the same blocks of H^-1, with no free-node limit
+ * and without the dense factor's work on structural zeros.  The graph's solver must be VGX_LINEAR_SOLVER_TILE_SPARSE
+ * (otherwise VGX_ERR_INVALID, the text pointing to vgx_pose_graph_covariance).  The call makes the sparse lists itself
+ * when they are not there -- before any solve (so VGX_ORDER_RCM works before a solve too), or after
+ * vgx_pose_graph_covariance has left dense lists behind -- and the tile cap can refuse it as it refuses
+ * vgx_pose_graph_optimize.
+ *
+ * THE SYSTEM.  P H P^T, P the order in use (natural, RCM or given): one full evaluation at `poses`, H's tiles copied
+ * into A's, factorised UNDAMPED by the tiled Cholesky.  THE COLUMNS solved are those of the distinct second nodes of
+ * the pairs between two free nodes, in ascending POSITION under P, four per node: column k of a node at position q is
+ * the identity's column 4 q + k.  covariance[p] = the solved columns of node pairs[2p + 1] at rows
+ * 4 pos(pairs[2p]) .. + 3 -- since (P H P^T)^-1 = P H^-1 P^T that is block (a, b) of H^-1, whatever the order.  A pair
+ * with a constant node gives sixteen zeros; (a, a), both directions of a pair and duplicates are allowed.
+ *
+ * THE ORDER CONTRACT.  Every delivered element has the history of tests/pose_graph_sparse_ref.py's forward and
+ * backward applied to its column:
+ *   forward    y_i = (b_i - l_i0 y_0 - l_i1 y_1 - ...) / l_ii, k ascending;
+ *   backward   x_i = (y_i - l_ki x_k - ...) / l_ii, k descending;
+ * each term one rounded multiply and one rounded subtract; the only terms left out are the products with a tile that
+ * is not stored.  So
+ *   - column c equals, bit for bit, what vgx_block_spd_solve -- or the graph's own tiled substitution -- gives for that
+ *     right-hand side alone;
+ *   - under the natural order the delivered blocks equal vgx_pose_graph_covariance's AS NUMBERS (-0.0 == +0.0): the
+ *     products left out are exact zeros of a finite factor, which change no value, only possibly the sign of a zero.
+ * Two skips, vgx_pose_graph_covariance's restated for positions under P: the forward pass of a workgroup (32 columns)
+ * starts at the panel of its first column's 1 -- above it b_i = 0 and every y_k so far is +0.0, and with a finite
+ * factor 0.0 - l * 0.0 = +0.0 and +0.0 / l_ii = +0.0, which is what the column holds already; the backward pass stops
+ * after the panel of the lowest row its columns' pairs want, and updates no tile left of that panel -- the rows above
+ * take no part in the rows below.  No delivered bit depends on either.  No other panel or tile is skipped.
+ *
+ * SLABS.  The solved columns live in X [4 x free nodes][S], S the largest multiple of 32 with
+ * 8 (4 x free nodes) S <= max_solve_bytes (0: the default, 1 GiB), 32 at the least whatever the budget and no more
+ * than the columns there are.  The columns are solved S at a time; chunks of 32 columns are independent, so the slab
+ * width changes no bit.  Per slab four launches (unit columns, forward, backward, gather of the slab's pairs into the
+ * one [n_pairs][16] device array); no workgroup waits for another, no cooperative launch, no captured graph.  The graph
+ * holds the slab buffer, grown on demand and never past max(max_solve_bytes, 32 columns).  Synchronous, two host
+ * synchronisations (the evaluation's and the result's).
+ *
+ * Refusals, VGX_ERR_NOT_POSITIVE_DEFINITE, n_pairs == 0, an all-constant graph and the 2^26 pair cap: as for
+ * vgx_pose_graph_covariance; max_solve_bytes < 0: VGX_ERR_INVALID.  A refused call leaves `covariance` untouched.
+ * Afterwards vgx_pose_graph_download_system returns this evaluation's H and g (the sparse-mode rules), and a later
+ * vgx_pose_graph_optimize or vgx_pose_graph_covariance on the handle gives the bits it gives on a fresh handle. */
+typedef struct vgx_pose_graph_covariance_stats {
+  int32_t n_columns;   /* columns of H^-1 solved: 4 x distinct second nodes of pairs between free nodes */
+  int32_t n_slabs;     /* column slabs the solve was cut into */
+  int32_t n_launches;  /* after the evaluation: the copy of H's tiles + the factorisation's + 4 per slab (unit columns,
+                        * forward, backward, gather) */
+  int32_t reserved;
+  int64_t solve_bytes; /* device bytes of the solved-column buffer actually used */
+} vgx_pose_graph_covariance_stats;
+VGX_API int vgx_pose_graph_covariance_sparse(vgx_pose_graph graph, const double* poses /* [n_nodes][4] */,
+                                             int32_t exclude_registration_constraints,
+                                             int32_t n_pairs, const int32_t* pairs /* [n_pairs][2] */,
+                                             int64_t max_solve_bytes /* 0: the default, 1 GiB */,
+                                             double* covariance /* [n_pairs][16] */,
+                                             vgx_pose_graph_covariance_stats* stats /* nullable */);
+/* The same kernels on a caller's matrix: vgx_block_spd_solve with m right-hand sides.  B and X host
+ * [4 n_block_rows][m] row-major (they may be the same array), 1 <= m <= 16384.  Column c of X is bit for bit what
+ * vgx_block_spd_solve returns for column c of B.  Refusals and VGX_ERR_NOT_POSITIVE_DEFINITE as there (X is then
+ * unspecified). */
+VGX_API int vgx_block_spd_solve_many(vgx_ctx ctx, int32_t n_block_rows, int32_t nnz, const int32_t* bi, const int32_t* bj,
+                                     const double* values /* [nnz][16] */, int32_t m,
+                                     const double* B /* [4 n_block_rows][m] */, double* X /* may be B */);
 
 /* ---- Scan-to-map registration ---------------------------------------------- */
 /* The refinement voxgraph_mapper.h:164 announces ("Map tracker handles the odometry input and refines it using

@@ -184,6 +184,14 @@ class PoseGraphStructureStats(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+class PoseGraphCovarianceStats(C.Structure):
+    _fields_ = [("n_columns", C.c_int32), ("n_slabs", C.c_int32), ("n_launches", C.c_int32), ("reserved", C.c_int32),
+                ("solve_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 class ScanRegistrationConfig(C.Structure):
     _fields_ = [("min_range_m", C.c_float), ("max_range_m", C.c_float), ("max_abs_distance_m", C.c_float),
                 ("point_stride", C.c_int32), ("min_valid_ratio", C.c_float)]
@@ -439,6 +447,9 @@ SIGNATURES = {
     "vgx_pose_graph_tile_pattern": (C.c_int, [C.c_int32, C.c_int32, i32p, C.c_int32, i32p, i32p, C.c_int32, i32p, i32p]),
     "vgx_block_spd_solve": (C.c_int, [vp, C.c_int32, C.c_int32, i32p, i32p, f64p, f64p, f64p, C.POINTER(PoseGraphStructureStats),
                                       i32p, f64p]),
+    "vgx_pose_graph_covariance_sparse": (C.c_int, [vp, f64p, C.c_int32, C.c_int32, i32p, C.c_int64, f64p,
+                                                   C.POINTER(PoseGraphCovarianceStats)]),
+    "vgx_block_spd_solve_many": (C.c_int, [vp, C.c_int32, C.c_int32, i32p, i32p, f64p, C.c_int32, f64p, f64p]),
     "vgx_scan_registration_config_default": (None, [C.POINTER(ScanRegistrationConfig)]),
     "vgx_scan_registration_create": (C.c_int, [vp, C.POINTER(ScanRegistrationConfig), C.POINTER(vp)]),
     "vgx_scan_registration_destroy": (C.c_int, [vp]),
@@ -1235,6 +1246,23 @@ def block_spd_solve(ctx, n_block_rows, bi, bj, values, b, want_factor=True):
     return x, stats.as_dict(), index, tiles
 
 
+def block_spd_solve_many(ctx, n_block_rows, bi, bj, values, B, in_place=False):
+    """vgx_block_spd_solve_many: A X = B for B [4 n_block_rows][m] -> X [4 n_block_rows][m]; in_place: X is B's own array
+    (B must then be a C-contiguous float64 array).  Raises as block_spd_solve does"""
+    bi, bj = np.ascontiguousarray(bi, np.int32), np.ascontiguousarray(bj, np.int32)
+    values = _f64(values)
+    if in_place:
+        assert isinstance(B, np.ndarray) and B.dtype == np.float64 and B.flags.c_contiguous
+    else:
+        B = _f64(B)
+    n, m = B.shape
+    assert values.size == 16 * len(bi) == 16 * len(bj) and n == 4 * n_block_rows
+    X = B if in_place else np.zeros((n, m))
+    ctx.check(ctx.lib.vgx_block_spd_solve_many(ctx.h, int(n_block_rows), len(bi), _ptr(bi, i32p), _ptr(bj, i32p), _ptr(values, f64p),
+                                               m, _ptr(B, f64p), _ptr(X, f64p)))
+    return X
+
+
 class PoseGraph:
     """vgx_pose_graph: PoseGraph::optimize() on the device (include/voxgraph_amd.h, "Pose graph: the solve").
     linear_solver: LINEAR_SOLVER_DENSE (None: vgx_pose_graph_create) or LINEAR_SOLVER_TILE_SPARSE with an ordering."""
@@ -1320,6 +1348,19 @@ class PoseGraph:
         self.ctx.check(self.ctx.lib.vgx_pose_graph_covariance(self.h, _ptr(x, f64p), int(bool(exclude_registration)), len(pr),
                                                               _ptr(pr, i32p), _ptr(out, f64p)))
         return out
+
+    def covariance_sparse(self, poses, pairs, exclude_registration=False, max_solve_bytes=0):
+        """vgx_pose_graph_covariance_sparse -> ([n_pairs][4][4], stats dict): covariance()'s blocks from the tile-sparse
+        factor, the solved columns cut into slabs of at most max_solve_bytes (0: 1 GiB); the graph's solver must be
+        LINEAR_SOLVER_TILE_SPARSE"""
+        x = np.array(poses, np.float64).reshape(self.n_nodes, 4)
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        out = np.zeros((len(pr), 4, 4))
+        stats = PoseGraphCovarianceStats()
+        self.ctx.check(self.ctx.lib.vgx_pose_graph_covariance_sparse(self.h, _ptr(x, f64p), int(bool(exclude_registration)), len(pr),
+                                                                     _ptr(pr, i32p), int(max_solve_bytes), _ptr(out, f64p),
+                                                                     C.byref(stats)))
+        return out, stats.as_dict()
 
     def destroy(self):
         if self.h:

@@ -74,7 +74,8 @@ class GpuPoseGraph {
   // The linear solver of the next solves (include/voxgraph_amd.h, "Pose graph: the tile-sparse solver"):
   // VGX_LINEAR_SOLVER_DENSE (the default, 4096 free nodes at the most) or VGX_LINEAR_SOLVER_TILE_SPARSE with
   // VGX_ORDER_NATURAL or VGX_ORDER_RCM.  (VGX_ORDER_GIVEN is a permutation of the free nodes in the order they were
-  // added: `permutation` is copied.)  getEdgeCovarianceMap keeps the dense factor and its limit.
+  // added: `permutation` is copied.)  getEdgeCovarianceMap follows the setting: the dense factor (and its limit) with
+  // the dense solver, the tile-sparse factor (vgx_pose_graph_covariance_sparse, no free-node limit) with the other.
   // On a graph that stands (no node or constraint changed since the last solve) the setting goes to the live handle
   // (vgx_pose_graph_set_linear_solver: the registration batch is kept) and a refusal is returned at once, nothing
   // changed; otherwise it is kept for the next optimize(), which then reports a refusal.
@@ -167,8 +168,9 @@ class GpuPoseGraph {
   // PoseGraph::getEdgeCovarianceMap (pose_graph.cpp:117-163): for every key (first, second) of the map the row-major 4x4
   // covariance block of the two submap poses, from one evaluation of the whole problem (registration constraints
   // included) at the current poses.  false -- the map is then not to be used -- on an unknown submap id or a failed
-  // computation (a rank-deficient graph; last_error() says which)
-  bool getEdgeCovarianceMap(EdgeCovarianceMap* map) {
+  // computation (a rank-deficient graph; last_error() says which).  With the tile-sparse solver the columns are solved
+  // on the sparse factor, in slabs of at most `max_solve_bytes` (0: the library's default); lastCovarianceStats() tells
+  bool getEdgeCovarianceMap(EdgeCovarianceMap* map, int64_t max_solve_bytes = 0) {
     if (!map) return Fail("getEdgeCovarianceMap: NULL map");
     std::vector<int32_t> pairs;
     for (const auto& kv : *map) {
@@ -179,7 +181,12 @@ class GpuPoseGraph {
     if (pairs.empty()) return true;
     if (Build() != VGX_OK) return false;
     std::vector<double> blocks(8 * pairs.size());
-    const int rc = vgx_pose_graph_covariance(graph_, poses_.data(), 0, static_cast<int32_t>(pairs.size() / 2), pairs.data(), blocks.data());
+    const int32_t n_pairs = static_cast<int32_t>(pairs.size() / 2);
+    covariance_stats_ = vgx_pose_graph_covariance_stats();
+    const int rc = solver_ == VGX_LINEAR_SOLVER_TILE_SPARSE
+                       ? vgx_pose_graph_covariance_sparse(graph_, poses_.data(), 0, n_pairs, pairs.data(), max_solve_bytes, blocks.data(),
+                                                          &covariance_stats_)
+                       : vgx_pose_graph_covariance(graph_, poses_.data(), 0, n_pairs, pairs.data(), blocks.data());
     if (rc != VGX_OK) {
       Status(rc);
       return false;
@@ -191,6 +198,9 @@ class GpuPoseGraph {
     }
     return true;
   }
+  // what the last getEdgeCovarianceMap on the tile-sparse factor solved (columns, slabs, launches, bytes); zeros after
+  // one on the dense factor
+  const vgx_pose_graph_covariance_stats& lastCovarianceStats() const { return covariance_stats_; }
   const std::vector<vgx_pose_graph_summary>& getSolverSummaries() const { return summaries_; }
   std::vector<vgx_pose_graph_iteration> lastHistory() const {
     int32_t n = 0;
@@ -284,6 +294,7 @@ class GpuPoseGraph {
   std::vector<int32_t> pairs_;
   std::vector<vgx_pose_graph_edge> edges_;
   std::vector<vgx_pose_graph_summary> summaries_;
+  vgx_pose_graph_covariance_stats covariance_stats_ = vgx_pose_graph_covariance_stats();
   bool dirty_ = true;
   std::string error_;
 };

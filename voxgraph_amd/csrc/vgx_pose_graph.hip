@@ -670,6 +670,173 @@ __global__ __launch_bounds__(1024) void pg_backward_tiled_kernel(const double* _
     __syncthreads();
   }
 }
+// ---------------------------------------------------------------------------
+// the tiled substitutions on many right-hand sides: pg_solve_many_kernel over the tile lists.  X [n][m] row-major, in
+// place; a workgroup owns kSolveCols columns and walks the panels alone.  After a panel's triangle only the stored tiles
+// of the panel's column (forward) or row (backward) are updated -- two tiles per pass with the 4 x 4 micro-tile, a last
+// single tile with a 2 x 4 one, so that all 256 threads have rows either way.
+// ---------------------------------------------------------------------------
+static_assert(kSolveRows == 2 * kPanel && kSolveK * 2 == kPanel, "pg_solve_many_tiled_kernel takes two tiles per pass, half a tile's k range at a time");
+
+// One pass of the row update: kTiles tiles (32 kTiles rows of X per row group of threads, R = 2 kTiles rows per thread).
+// T[h]: the tile, i0[h]: the first row of X it updates, rows[h]: how many.  Forward: x_(i0 + r) -= T[r][k] y_k, k ascending;
+// backward: x_(i0 + r) -= T[k][r] x_k, k descending from w - 1.  The accumulators START at the stored value.
+template <bool kBackward, int kTiles>
+__device__ __forceinline__ void solve_many_tiles_pass(const double* const (&T)[2], const int (&i0)[2], const int (&rows)[2], int w,
+                                                      double* __restrict__ X, int m, int c0, double* __restrict__ S,
+                                                      const double* __restrict__ Y, int tid) {
+  constexpr int R = 2 * kTiles;
+  const int tx = tid % kSolveColGroups, ty = tid / kSolveColGroups;
+  const int lr0 = ty * R, h = lr0 >> 6, rt0 = lr0 & (kPanel - 1);  // (R | 64: a thread's rows lie in one tile)
+  double acc[R][4];
+#pragma unroll
+  for (int a = 0; a < R; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int col = c0 + tx * 4 + b;
+      acc[a][b] = (rt0 + a < rows[h] && col < m) ? X[(size_t)(i0[h] + rt0 + a) * m + col] : 0.0;
+    }
+  const int n_passes = (w + kSolveK - 1) / kSolveK;
+  for (int s = 0; s < n_passes; ++s) {
+    const int kc = (kBackward ? n_passes - 1 - s : s) * kSolveK;
+    __syncthreads();
+    if (!kBackward) {  // S[k][lr] = T[lr / 64][lr % 64][kc + k]: a tile row per kSolveK threads
+      const int k = tid % kSolveK;
+      for (int lr = tid / kSolveK; lr < kPanel * kTiles; lr += 256 / kSolveK) {
+        const int hh = lr >> 6, rt = lr & (kPanel - 1);
+        S[k * kSolveStride + lr] = (kc + k < w && rt < rows[hh]) ? T[hh][rt * kPanel + kc + k] : 0.0;
+      }
+    } else {           // S[k][lr] = T[lr / 64][kc + k][lr % 64]: a tile row per 64 threads
+      const int lr = tid % (kPanel * kTiles), hh = lr >> 6, rt = lr & (kPanel - 1);
+      for (int k = tid / (kPanel * kTiles); k < kSolveK; k += 256 / (kPanel * kTiles))
+        S[k * kSolveStride + lr] = (kc + k < w && rt < rows[hh]) ? T[hh][(kc + k) * kPanel + rt] : 0.0;
+    }
+    __syncthreads();
+    const int kn = min(kSolveK, w - kc);
+    for (int kk = 0; kk < kn; ++kk) {
+      const int k = kBackward ? kn - 1 - kk : kk;
+      double av[R];
+#pragma unroll
+      for (int a = 0; a < R; a += 2) {
+        const double2 v = *reinterpret_cast<const double2*>(&S[k * kSolveStride + lr0 + a]);
+        av[a] = v.x, av[a + 1] = v.y;
+      }
+      const double2 b01 = *reinterpret_cast<const double2*>(&Y[(kc + k) * kSolveYStride + tx * 4]);
+      const double2 b23 = *reinterpret_cast<const double2*>(&Y[(kc + k) * kSolveYStride + tx * 4 + 2]);
+      const double bv[4] = {b01.x, b01.y, b23.x, b23.y};
+#pragma unroll
+      for (int a = 0; a < R; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = acc[a][b] - av[a] * bv[b];
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < R; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int col = c0 + tx * 4 + b;
+      if (rt0 + a < rows[h] && col < m) X[(size_t)(i0[h] + rt0 + a) * m + col] = acc[a][b];
+    }
+}
+
+// chunk_rows (nullable): as for pg_solve_many_kernel, the rows being positions in the order in use.  The two skips keep
+// that kernel's argument: above the panel of a unit column's 1 every y is +0.0 (a finite factor), and the rows above
+// the panel of the lowest row wanted take no part in the rows below -- so a tile whose column lies left of that panel is
+// not updated in the backward pass.  Every delivered element has the history of pg_forward_tiled_kernel /
+// pg_backward_tiled_kernel on its column.
+template <bool kBackward>
+__global__ __launch_bounds__(256) void pg_solve_many_tiled_kernel(const double* __restrict__ Lt_, const int32_t* __restrict__ col_first,
+                                                                 const int32_t* __restrict__ l_row, const int32_t* __restrict__ row_first,
+                                                                 const int32_t* __restrict__ row_tile, const int32_t* __restrict__ row_col,
+                                                                 int n, double* __restrict__ X, int m,
+                                                                 const int32_t* __restrict__ chunk_rows, const int* __restrict__ flag) {
+  if (*flag) return;
+  __shared__ alignas(16) double S[kSolveStage];  // the panel's triangle, then the staged halves of one or two tiles
+  __shared__ alignas(16) double Y[kPanel * kSolveYStride];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c0 = blockIdx.x * kSolveCols;
+  const int n_panels = (n + kPanel - 1) / kPanel;
+  const int p_first = (!kBackward && chunk_rows) ? chunk_rows[2 * blockIdx.x] / kPanel : 0;
+  const int p_last = (kBackward && chunk_rows) ? chunk_rows[2 * blockIdx.x + 1] / kPanel : 0;
+  for (int p = kBackward ? n_panels - 1 : p_first; kBackward ? p >= p_last : p < n_panels; p += kBackward ? -1 : 1) {
+    const int k0 = p * kPanel, w = min(kPanel, n - k0);
+    const int first = col_first[p];
+    const double* D = Lt_ + (size_t)first * kTileDoubles;
+    __syncthreads();
+    for (int e = tid; e < kPanel * kPanel; e += 256) {
+      const int i = e >> 6, j = e & 63;
+      S[i * (kPanel + 1) + j] = (i < w && j <= i) ? D[i * kPanel + j] : 1.0;
+    }
+    for (int e = tid; e < kPanel * kSolveCols; e += 256) {
+      const int r = e / kSolveCols, c = e % kSolveCols;
+      Y[r * kSolveYStride + c] = (r < w && c0 + c < m) ? X[(size_t)(k0 + r) * m + c0 + c] : 0.0;
+    }
+    __syncthreads();
+    {  // the panel's own triangle: row `lane` of this wavefront's columns in registers
+      double y[kSolveColsPerWave];
+#pragma unroll
+      for (int q = 0; q < kSolveColsPerWave; ++q) y[q] = Y[lane * kSolveYStride + wave * kSolveColsPerWave + q];
+      if (!kBackward) {
+        for (int j = 0; j < w; ++j) {
+          const double ljj = S[j * (kPanel + 1) + j], lij = lane > j ? S[lane * (kPanel + 1) + j] : 0.0;
+          const double d = pivot_row(y, j, lane) / ljj;
+#pragma unroll
+          for (int q = 0; q < kSolveColsPerWave; ++q) {
+            const double yj = __shfl(d, q);
+            if (lane == j) y[q] = yj;
+            if (lane > j) y[q] = y[q] - lij * yj;
+          }
+        }
+      } else {
+        for (int j = w - 1; j >= 0; --j) {
+          const double ljj = S[j * (kPanel + 1) + j], lji = lane < j ? S[j * (kPanel + 1) + lane] : 0.0;
+          const double d = pivot_row(y, j, lane) / ljj;
+#pragma unroll
+          for (int q = 0; q < kSolveColsPerWave; ++q) {
+            const double xj = __shfl(d, q);
+            if (lane == j) y[q] = xj;
+            if (lane < j) y[q] = y[q] - lji * xj;
+          }
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < kSolveColsPerWave; ++q) Y[lane * kSolveYStride + wave * kSolveColsPerWave + q] = y[q];
+    }
+    __syncthreads();
+    for (int e = tid; e < kPanel * kSolveCols; e += 256) {
+      const int r = e / kSolveCols, c = e % kSolveCols;
+      if (r < w && c0 + c < m) X[(size_t)(k0 + r) * m + c0 + c] = Y[r * kSolveYStride + c];
+    }
+    // the stored tiles alone: below the diagonal one in the panel's column (forward), left of it in the panel's row
+    // down to the last panel's column (backward; the row list ascends by column)
+    int q = kBackward ? row_first[p] : first + 1;
+    const int q_end = kBackward ? row_first[p + 1] : col_first[p + 1];
+    if (kBackward)
+      while (q < q_end && row_col[q] < p_last) ++q;
+    for (; q < q_end; q += 2) {
+      const bool two = q + 1 < q_end;
+      const int qa = q, qb = two ? q + 1 : q;
+      const double* const T[2] = {Lt_ + (size_t)(kBackward ? row_tile[qa] : qa) * kTileDoubles,
+                                  Lt_ + (size_t)(kBackward ? row_tile[qb] : qb) * kTileDoubles};
+      const int i0[2] = {(kBackward ? row_col[qa] : l_row[qa]) * kPanel, (kBackward ? row_col[qb] : l_row[qb]) * kPanel};
+      const int rows[2] = {min(kPanel, n - i0[0]), min(kPanel, n - i0[1])};
+      if (two)
+        solve_many_tiles_pass<kBackward, 2>(T, i0, rows, w, X, m, c0, S, Y, tid);
+      else
+        solve_many_tiles_pass<kBackward, 1>(T, i0, rows, w, X, m, c0, S, Y, tid);
+    }
+  }
+}
+// out[16 list[3 t] + e] = the 4x4 block of the slab X [n][m] at rows list[3 t + 1] .. + 3, columns list[3 t + 2] .. + 3
+__global__ void pg_gather_slab_blocks_kernel(const double* __restrict__ X, int m, const int32_t* __restrict__ list, int n_list,
+                                             double* __restrict__ out) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_list * 16) return;
+  const int32_t* rec = list + 3 * (size_t)(t >> 4);
+  const int r = (t >> 2) & 3, c = t & 3;
+  out[(size_t)rec[0] * 16 + (t & 15)] = X[(size_t)(rec[1] + r) * m + rec[2] + c];
+}
+
 // the right-hand side into the order in use: x[4 p + k] = g[4 order[p] + k]
 __global__ void pg_permute_kernel(const double* __restrict__ g, const int32_t* __restrict__ order, double* __restrict__ x, int nf) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -761,8 +928,21 @@ int queue_substitutions_tiled(vgx_ctx ctx, const DeviceTiles& d, const double* L
   VGX_HIP(ctx, hipGetLastError());
   return VGX_OK;
 }
-int block_spd_solve(vgx_ctx ctx, int32_t n_block_rows, int32_t nnz, const int32_t* bi, const int32_t* bj, const double* values,
-                    const double* b, double* x, vgx_pose_graph_structure_stats* stats, int32_t* tile_index, double* tile_values);
+// ... and on the m columns of d_X [n][m] (in place): two launches.  d_chunk_rows: nullable, [ceil(m / kSolveCols)][2]
+int queue_solve_many_tiled(vgx_ctx ctx, const DeviceTiles& d, const double* Lt, int n, double* d_X, int m, const int32_t* d_chunk_rows,
+                           const int* d_flag) {
+  const dim3 grid((m + kSolveCols - 1) / kSolveCols);
+  hipLaunchKernelGGL(pg_solve_many_tiled_kernel<false>, grid, dim3(256), 0, ctx->stream, Lt, d.col_first.get(), d.l_row.get(),
+                     d.row_first.get(), d.row_tile.get(), d.row_col.get(), n, d_X, m, d_chunk_rows, d_flag);
+  hipLaunchKernelGGL(pg_solve_many_tiled_kernel<true>, grid, dim3(256), 0, ctx->stream, Lt, d.col_first.get(), d.l_row.get(),
+                     d.row_first.get(), d.row_tile.get(), d.row_col.get(), n, d_X, m, d_chunk_rows, d_flag);
+  VGX_HIP(ctx, hipGetLastError());
+  return VGX_OK;
+}
+// m == 0: one right-hand side through the single-column kernels; m > 0: b and x are [4 n_block_rows][m]
+int block_spd_solve(vgx_ctx ctx, const char* who, int32_t n_block_rows, int32_t nnz, const int32_t* bi, const int32_t* bj,
+                    const double* values, int32_t m, const double* b, double* x, vgx_pose_graph_structure_stats* stats,
+                    int32_t* tile_index, double* tile_values);
 int launches_per_factorisation(const TileStructure& S) {
   int n = 0;
   for (int K = 0; K < S.n_tile_rows; ++K) n += S.col_first[(size_t)K + 1] - S.col_first[(size_t)K] > 1 ? 3 : 1;
@@ -867,6 +1047,7 @@ struct vgx_pose_graph_s {
   bool system_valid = false;
   std::vector<vgx_pose_graph_iteration> history;
   // vgx_pose_graph_covariance: the solved columns [nf][m <= nf], the index lists, the blocks; grown on demand
+  // (vgx_pose_graph_covariance_sparse: d_X is the column slab [nf][S], held within its byte budget)
   DeviceArray<double> d_X, d_cov;
   DeviceArray<int32_t> d_cov_index;
   PinnedBuffer h_cov;        // [blocks 16 n_pairs + the flag, doubles][index lists, int32]
@@ -1652,6 +1833,177 @@ int vgx_pose_graph_covariance(vgx_pose_graph pg, const double* poses, int32_t ex
   return VGX_OK;
 }
 
+int vgx_pose_graph_covariance_sparse(vgx_pose_graph pg, const double* poses, int32_t exclude_registration_constraints, int32_t n_pairs,
+                                     const int32_t* pairs, int64_t max_solve_bytes, double* covariance,
+                                     vgx_pose_graph_covariance_stats* stats) {
+  if (!pg) return VGX_ERR_INVALID;
+  vgx_ctx ctx = pg->ctx;
+  if (n_pairs < 0) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance_sparse: n_pairs < 0");
+  if (max_solve_bytes < 0) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance_sparse: max_solve_bytes < 0");
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (n_pairs == 0) return VGX_OK;
+  if (!poses || !pairs || !covariance)
+    return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance_sparse: NULL poses, pairs or covariance");
+  if (n_pairs > (1 << 26)) return set_error(ctx, VGX_ERR_UNSUPPORTED, "vgx_pose_graph_covariance_sparse: more than 2^26 pairs in one call");
+  std::lock_guard<std::mutex> lk(pg->mu);
+  if (pg->solver != VGX_LINEAR_SOLVER_TILE_SPARSE)
+    return set_error(ctx, VGX_ERR_INVALID,
+                     "vgx_pose_graph_covariance_sparse: the graph's solver is not VGX_LINEAR_SOLVER_TILE_SPARSE; "
+                     "vgx_pose_graph_covariance takes the dense factor");
+  for (size_t i = 0; i < 2 * (size_t)n_pairs; ++i)
+    if (pairs[i] < 0 || pairs[i] >= pg->n_nodes)
+      return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance_sparse: pair " + std::to_string(i / 2) + " names a node out of range");
+  for (size_t i = 0; i < 4 * (size_t)pg->n_nodes; ++i)
+    if (!std::isfinite(poses[i])) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance_sparse: a pose is not finite");
+  if (pg->batch) {
+    std::lock_guard<std::mutex> lt(lifetime_mu());
+    if (pg->batch->destroy_requested)
+      return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance_sparse: the registration batch was destroyed");
+  }
+  const bool with_reg = pg->batch && pg->batch->n > 0 && !exclude_registration_constraints;
+  if (!with_reg && pg->edges.empty())
+    return set_error(ctx, VGX_ERR_INVALID,
+                     "vgx_pose_graph_covariance_sparse: a graph without constraints (no registration batch in use, no edges)");
+  const size_t n_out = 16 * (size_t)n_pairs;
+  if (pg->nf == 0) {  // every node is constant
+    std::fill(covariance, covariance + n_out, 0.0);
+    return VGX_OK;
+  }
+  if (!pg->lists_made || pg->lists_with_reg != with_reg || !pg->lists_sparse) {
+    const int rc = make_lists(pg, with_reg, true);
+    if (rc != VGX_OK) return rc;
+  }
+  // the columns to solve: the distinct second nodes (of pairs between free nodes) in ascending POSITION under the
+  // order in use, and per position the lowest row any of its pairs wants
+  const int nf = pg->nf, nfn = nf / 4;
+  const std::vector<int32_t>& position = pg->S.position;
+  auto place = [&](int32_t node) { return pg->pos[(size_t)node] < 0 ? -1 : position[(size_t)pg->pos[(size_t)node]]; };
+  std::vector<int32_t> lowest, col_of, slab_first;
+  int m = 0, n_free_pairs = 0;
+  try {
+    lowest.assign((size_t)nfn, INT32_MAX);
+    col_of.assign((size_t)nfn, -1);
+  } catch (const std::bad_alloc&) {
+    return set_error(ctx, VGX_ERR_NOMEM, "vgx_pose_graph_covariance_sparse: out of host memory for the column lists");
+  }
+  for (int p = 0; p < n_pairs; ++p) {
+    const int32_t a = place(pairs[2 * p]), b = place(pairs[2 * p + 1]);
+    if (a >= 0 && b >= 0) {
+      lowest[(size_t)b] = std::min(lowest[(size_t)b], 4 * a);
+      ++n_free_pairs;
+    }
+  }
+  for (int b = 0; b < nfn; ++b)
+    if (lowest[(size_t)b] != INT32_MAX) {
+      col_of[(size_t)b] = m;
+      m += 4;
+    }
+  // the slabs: S columns at a time, the largest multiple of kSolveCols with 8 nf S <= the budget, kSolveCols at the least
+  const int64_t budget = max_solve_bytes == 0 ? (int64_t)1 << 30 : max_solve_bytes;
+  const int64_t m_round = ((int64_t)m + kSolveCols - 1) / kSolveCols * kSolveCols;
+  const int64_t slab = std::max<int64_t>(kSolveCols, std::min<int64_t>(std::max<int64_t>(m_round, kSolveCols), budget / (8 * (int64_t)nf) / kSolveCols * kSolveCols));
+  const int n_slabs = (int)((m + slab - 1) / slab), n_chunks = (m + kSolveCols - 1) / kSolveCols;
+  const size_t x_doubles = (size_t)nf * (size_t)std::min<int64_t>(slab, std::max(m, 1));
+  const size_t x_limit = std::max<size_t>((size_t)budget, (size_t)nf * kSolveCols * sizeof(double));
+  const size_t n_index = (size_t)m + 2 * (size_t)n_chunks + 3 * (size_t)n_free_pairs + 1;
+  {
+    std::lock_guard<std::mutex> lc(ctx->mu);
+    VGX_HIP(ctx, hipSetDevice(ctx->device));
+    hipError_t e = hipSuccess;
+    if (pg->d_X.bytes < x_doubles * sizeof(double) || pg->d_X.bytes > x_limit) {  // grown on demand, never past the budget
+      VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      e = pg->d_X.alloc(x_doubles * sizeof(double));
+    }
+    if (e == hipSuccess) e = pg->d_cov.reserve((n_out + 1) * sizeof(double));
+    if (e == hipSuccess) e = pg->d_cov_index.reserve(n_index * sizeof(int32_t));
+    if (e != hipSuccess) return alloc_error(ctx, e, "vgx_pose_graph_covariance_sparse: allocating the solved columns");
+    e = pg->h_cov.reserve((n_out + 1) * sizeof(double) + n_index * sizeof(int32_t));
+    if (e != hipSuccess) return alloc_error(ctx, e, "vgx_pose_graph_covariance_sparse: allocating the pinned staging");
+  }
+  double* h_out = pg->h_cov.as<double>();
+  int32_t* h_unit_row = reinterpret_cast<int32_t*>(h_out + n_out + 1);
+  int32_t* h_chunk_rows = h_unit_row + m;
+  int32_t* h_list = h_chunk_rows + 2 * (size_t)n_chunks;  // per slab its pairs: {pair, first row, first column in the slab}
+  for (int c = 0; c < n_chunks; ++c) h_chunk_rows[2 * c + 1] = INT32_MAX;
+  for (int b = 0; b < nfn; ++b) {
+    const int c = col_of[(size_t)b];
+    if (c < 0) continue;
+    for (int k = 0; k < 4; ++k) h_unit_row[c + k] = 4 * b + k;
+    int32_t& low = h_chunk_rows[2 * (c / kSolveCols) + 1];  // (4 | kSolveCols: a node's columns share a chunk)
+    low = std::min(low, lowest[(size_t)b]);
+  }
+  for (int c = 0; c < n_chunks; ++c) h_chunk_rows[2 * c] = h_unit_row[c * kSolveCols];  // ascending: the chunk's first 1
+  try {
+    slab_first.assign((size_t)n_slabs + 1, 0);
+  } catch (const std::bad_alloc&) {
+    return set_error(ctx, VGX_ERR_NOMEM, "vgx_pose_graph_covariance_sparse: out of host memory for the column lists");
+  }
+  for (int pass = 0; pass < 2; ++pass) {  // a counting sort of the pairs by slab, stable
+    for (int p = 0; p < n_pairs; ++p) {
+      const int32_t a = place(pairs[2 * p]), b = place(pairs[2 * p + 1]);
+      if (a < 0 || b < 0) continue;
+      const int32_t col = col_of[(size_t)b], s = (int32_t)(col / slab);
+      if (pass == 0) {
+        ++slab_first[(size_t)s + 1];
+      } else {
+        int32_t* rec = h_list + 3 * (size_t)slab_first[(size_t)s]++;
+        rec[0] = p, rec[1] = 4 * a, rec[2] = (int32_t)(col - s * slab);
+      }
+    }
+    if (pass == 0)
+      for (int s = 0; s < n_slabs; ++s) slab_first[(size_t)s + 1] += slab_first[(size_t)s];
+    else
+      for (int s = n_slabs; s > 0; --s) slab_first[(size_t)s] = slab_first[(size_t)s - 1];
+    if (pass == 1) slab_first[0] = 0;
+  }
+  Solve sv{pg, with_reg};
+  double cost = 0.0;
+  int rc = sv.evaluate_full(poses, &cost);
+  if (rc < 0) return rc;
+  {
+    std::lock_guard<std::mutex> lc(ctx->mu);
+    VGX_HIP(ctx, hipSetDevice(ctx->device));
+    const DeviceTiles& d = pg->tiles;
+    int32_t* d_unit_row = pg->d_cov_index.get();
+    int32_t* d_chunk_rows = d_unit_row + m;
+    int32_t* d_list = d_chunk_rows + 2 * (size_t)n_chunks;
+    VGX_HIP(ctx, hipMemcpyAsync(d_unit_row, h_unit_row, n_index * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    VGX_HIP(ctx, hipMemsetAsync(pg->d_cov.p, 0, n_out * sizeof(double), ctx->stream));  // a pair with a constant node: zeros
+    hipLaunchKernelGGL(pg_tiles_from_h_kernel, dim3((unsigned)pg->S.l_row.size()), dim3(256), 0, ctx->stream, pg->d_Ht.get(),
+                       pg->d_At.get(), d.l_from_h.get());
+    rc = queue_cholesky_tiled(ctx, pg->S, d, pg->d_At.get(), nf, pg->d_flag.get());  // undamped
+    if (rc != VGX_OK) return rc;
+    for (int s = 0; s < n_slabs; ++s) {
+      const int64_t c_first = s * slab;
+      const int ms = (int)std::min<int64_t>(slab, m - c_first);
+      const size_t total = (size_t)nf * ms;
+      hipLaunchKernelGGL(pg_unit_columns_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, pg->d_X.get(), nf, ms,
+                         d_unit_row + c_first);
+      rc = queue_solve_many_tiled(ctx, d, pg->d_At.get(), nf, pg->d_X.get(), ms, d_chunk_rows + 2 * (c_first / kSolveCols), pg->d_flag.get());
+      if (rc != VGX_OK) return rc;
+      const int n_list = slab_first[(size_t)s + 1] - slab_first[(size_t)s];  // (> 0: every column has a pair that wants it)
+      hipLaunchKernelGGL(pg_gather_slab_blocks_kernel, dim3((unsigned)(((size_t)n_list * 16 + 255) / 256)), dim3(256), 0, ctx->stream,
+                         pg->d_X.get(), ms, d_list + 3 * (size_t)slab_first[(size_t)s], n_list, pg->d_cov.get());
+    }
+    VGX_HIP(ctx, hipGetLastError());
+    VGX_HIP(ctx, hipMemcpyAsync(h_out, pg->d_cov.p, n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    VGX_HIP(ctx, hipMemcpyAsync(h_out + n_out, pg->d_flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  if (stats) {
+    stats->n_columns = m;
+    stats->n_slabs = n_slabs;
+    stats->n_launches = 1 + launches_per_factorisation(pg->S) + 4 * n_slabs;
+    stats->reserved = 0;
+    stats->solve_bytes = m > 0 ? (int64_t)(x_doubles * sizeof(double)) : 0;
+  }
+  if (*reinterpret_cast<const int*>(h_out + n_out) != 0)
+    return set_error(ctx, VGX_ERR_NOT_POSITIVE_DEFINITE,
+                     "vgx_pose_graph_covariance_sparse: H is not positive definite (a pivot is not positive or not finite): the graph is rank deficient");
+  std::memcpy(covariance, h_out, n_out * sizeof(double));
+  return VGX_OK;
+}
+
 int vgx_dense_spd_solve_many(vgx_ctx ctx, int32_t n, const double* A, int32_t m, const double* B, double* X, double* L) {
   if (!ctx) return VGX_ERR_INVALID;
   if (n < 1 || n > kMaxDenseN || m < 1 || m > kMaxDenseN)
@@ -1694,35 +2046,51 @@ int vgx_block_spd_solve(vgx_ctx ctx, int32_t n_block_rows, int32_t nnz, const in
   if (n_block_rows > (1 << 27)) return set_error(ctx, VGX_ERR_UNSUPPORTED, "vgx_block_spd_solve: more than 2^27 block rows");
   if (!bi || !bj || !values || !b || !x) return set_error(ctx, VGX_ERR_INVALID, "vgx_block_spd_solve: NULL bi, bj, values, b or x");
   try {
-    return block_spd_solve(ctx, n_block_rows, nnz, bi, bj, values, b, x, stats, tile_index, tile_values);
+    return block_spd_solve(ctx, "vgx_block_spd_solve", n_block_rows, nnz, bi, bj, values, 0, b, x, stats, tile_index, tile_values);
   } catch (const std::bad_alloc&) {
     return set_error(ctx, VGX_ERR_NOMEM, "vgx_block_spd_solve: out of host memory for the structure or the tiles");
+  }
+}
+
+int vgx_block_spd_solve_many(vgx_ctx ctx, int32_t n_block_rows, int32_t nnz, const int32_t* bi, const int32_t* bj, const double* values,
+                             int32_t m, const double* B, double* X) {
+  if (!ctx) return VGX_ERR_INVALID;
+  if (n_block_rows < 1 || nnz < 1 || m < 1) return set_error(ctx, VGX_ERR_INVALID, "vgx_block_spd_solve_many: n_block_rows < 1, nnz < 1 or m < 1");
+  if (n_block_rows > (1 << 27)) return set_error(ctx, VGX_ERR_UNSUPPORTED, "vgx_block_spd_solve_many: more than 2^27 block rows");
+  if (m > kMaxDenseN) return set_error(ctx, VGX_ERR_UNSUPPORTED, "vgx_block_spd_solve_many: m must be in [1, " + std::to_string(kMaxDenseN) + "]");
+  if (!bi || !bj || !values || !B || !X) return set_error(ctx, VGX_ERR_INVALID, "vgx_block_spd_solve_many: NULL bi, bj, values, B or X");
+  try {
+    return block_spd_solve(ctx, "vgx_block_spd_solve_many", n_block_rows, nnz, bi, bj, values, m, B, X, nullptr, nullptr, nullptr);
+  } catch (const std::bad_alloc&) {
+    return set_error(ctx, VGX_ERR_NOMEM, "vgx_block_spd_solve_many: out of host memory for the structure or the tiles");
   }
 }
 
 }  // extern "C"
 
 namespace {
-int block_spd_solve(vgx_ctx ctx, int32_t n_block_rows, int32_t nnz, const int32_t* bi, const int32_t* bj, const double* values,
-                    const double* b, double* x, vgx_pose_graph_structure_stats* stats, int32_t* tile_index, double* tile_values) {
+int block_spd_solve(vgx_ctx ctx, const char* who_, int32_t n_block_rows, int32_t nnz, const int32_t* bi, const int32_t* bj,
+                    const double* values, int32_t m, const double* b, double* x, vgx_pose_graph_structure_stats* stats,
+                    int32_t* tile_index, double* tile_values) {
+  const std::string who(who_);
   std::vector<int32_t> joined(2 * (size_t)nnz);
   std::set<std::pair<int32_t, int32_t>> seen;
   for (int32_t k = 0; k < nnz; ++k) {
     if (bi[k] < 0 || bi[k] >= n_block_rows || bj[k] < 0 || bj[k] >= n_block_rows)
-      return set_error(ctx, VGX_ERR_INVALID, "vgx_block_spd_solve: block " + std::to_string(k) + " is out of range");
-    if (bj[k] > bi[k]) return set_error(ctx, VGX_ERR_INVALID, "vgx_block_spd_solve: block " + std::to_string(k) + " lies above the diagonal");
+      return set_error(ctx, VGX_ERR_INVALID, who + ": block " + std::to_string(k) + " is out of range");
+    if (bj[k] > bi[k]) return set_error(ctx, VGX_ERR_INVALID, who + ": block " + std::to_string(k) + " lies above the diagonal");
     if (!seen.insert({bi[k], bj[k]}).second)
-      return set_error(ctx, VGX_ERR_INVALID, "vgx_block_spd_solve: block " + std::to_string(k) + " is given twice");
+      return set_error(ctx, VGX_ERR_INVALID, who + ": block " + std::to_string(k) + " is given twice");
     joined[2 * (size_t)k] = bi[k];
     joined[2 * (size_t)k + 1] = bj[k];
   }
   TileStructure S;
   if (!build_tile_structure(n_block_rows, nnz, joined.data(), kOrderNatural, nullptr, &S))
-    return set_error(ctx, VGX_ERR_INVALID, "vgx_block_spd_solve: the block list does not make a structure");
+    return set_error(ctx, VGX_ERR_INVALID, who + ": the block list does not make a structure");
   const size_t n_l = S.l_row.size(), N = 4 * (size_t)n_block_rows;
   std::lock_guard<std::mutex> lk(ctx->mu);
   VGX_HIP(ctx, hipSetDevice(ctx->device));
-  int rc = check_tile_cap(ctx, "vgx_block_spd_solve", n_l, 0, (N + 64) * sizeof(double));
+  int rc = check_tile_cap(ctx, who_, n_l, 0, (N * (size_t)std::max(1, m) + 64) * sizeof(double));
   if (rc != VGX_OK) return rc;
   std::vector<double> tiles(n_l * (size_t)kTileDoubles, 0.0);
   for (int32_t k = 0; k < nnz; ++k) {
@@ -1737,20 +2105,22 @@ int block_spd_solve(vgx_ctx ctx, int32_t n_block_rows, int32_t nnz, const int32_
   rc = upload_structure(ctx, S, &d);
   if (rc != VGX_OK) return rc;
   hipError_t e = d_At.alloc_n(n_l * (size_t)kTileDoubles);
-  if (e == hipSuccess) e = d_x.alloc_n(N);
+  if (e == hipSuccess) e = d_x.alloc_n(N * (size_t)std::max(1, m));
   if (e == hipSuccess) e = d_flag.alloc_n(1);
-  if (e != hipSuccess) return alloc_error(ctx, e, "vgx_block_spd_solve: allocating the tiles");
+  if (e != hipSuccess) return alloc_error(ctx, e, (who + ": allocating the tiles").c_str());
   VGX_HIP(ctx, hipMemcpyAsync(d_At.p, tiles.data(), tiles.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  VGX_HIP(ctx, hipMemcpyAsync(d_x.p, b, N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  VGX_HIP(ctx, hipMemcpyAsync(d_x.p, b, N * (size_t)std::max(1, m) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   rc = queue_cholesky_tiled(ctx, S, d, d_At.get(), (int)N, d_flag.get());
-  if (rc == VGX_OK) rc = queue_substitutions_tiled(ctx, d, d_At.get(), (int)N, d_x.get());
+  if (rc == VGX_OK)
+    rc = m > 0 ? queue_solve_many_tiled(ctx, d, d_At.get(), (int)N, d_x.get(), m, nullptr, d_flag.get())
+               : queue_substitutions_tiled(ctx, d, d_At.get(), (int)N, d_x.get());
   if (rc != VGX_OK) {
     (void)hipStreamSynchronize(ctx->stream);
     return rc;
   }
   int flag = 0;
   VGX_HIP(ctx, hipMemcpyAsync(&flag, d_flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  VGX_HIP(ctx, hipMemcpyAsync(x, d_x.p, N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  VGX_HIP(ctx, hipMemcpyAsync(x, d_x.p, N * (size_t)std::max(1, m) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   if (tile_values) VGX_HIP(ctx, hipMemcpyAsync(tile_values, d_At.p, tiles.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (tile_index)
@@ -1775,7 +2145,7 @@ int block_spd_solve(vgx_ctx ctx, int32_t n_block_rows, int32_t nnz, const int32_
     stats->n_update_triples = (int64_t)S.triples.size();
     stats->bytes = (int64_t)(tiles.size() * sizeof(double) + d.bytes);
   }
-  if (flag) return set_error(ctx, VGX_ERR_NOT_POSITIVE_DEFINITE, "vgx_block_spd_solve: the matrix is not positive definite (a pivot is not positive or not finite)");
+  if (flag) return set_error(ctx, VGX_ERR_NOT_POSITIVE_DEFINITE, who + ": the matrix is not positive definite (a pivot is not positive or not finite)");
   return VGX_OK;
 }
 }  // namespace
