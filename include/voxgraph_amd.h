@@ -231,7 +231,27 @@ VGX_API int vgx_submap_block_index(vgx_submap submap, int32_t* block_index);
  * discontinuity, outside voxblox's defaults only: when default_distance_m > max_distance_m, a voxel of the shell beyond the limit
  * whose neighbour sits within that slack of it can take another neighbour's longer path or keep the default.
  * Fills the ESDF raw layer from the resident TSDF layer and rebuilds the ESDF sampling
- * grid.  cfg == NULL uses voxblox's defaults.  sweeps (nullable) = global passes used. */
+ * grid.  cfg == NULL uses voxblox's defaults.  sweeps (nullable) = global passes used.
+ * The result's bits are determined: it is the greatest fixed point of the f32 recurrence, whatever order the blocks ran in
+ * (tests/esdf_ref.py restates it in numpy, and the tests compare bit for bit).
+ * Configuration: max_distance_m > 0, default_distance_m > 0 and min_distance_m >= 0 are required (a NaN fails each), nothing
+ * else.  max_distance_m and default_distance_m may be huge or +inf (an uncapped ESDF): the number of passes is limited by
+ * 8 + 2 * ceil(max_distance_m / voxel_size) AND by the submap's voxel count + 1 (a best path visits no voxel twice), formed in
+ * floating point, so every valid configuration runs to the fixed point.  Should the limit ever be reached with voxels still
+ * changing, the call returns VGX_ERR_INVALID with a message, never VGX_OK over a partly relaxed layer; the ESDF sampling grid
+ * is then absent (it is dropped as soon as the layer is rewritten, also when a HIP call fails).
+ * Edges, as they are (the restated queue, oracle/esdf_oracle.c, does the same on each; none is changed quietly here):
+ *  - min_distance_m = 0 fixes no voxel, so nothing is a surface voxel and every observed voxel keeps sign * default_distance_m:
+ *    a layer without a single distance in it.  min_distance_m above the TSDF's truncation distance likewise fixes every voxel
+ *    the TSDF clipped, at the truncation distance.
+ *  - a TSDF distance of exactly +-0 outside the band (possible only with min_distance_m = 0) and a NaN TSDF distance under a
+ *    weight >= min_weight both have no sign: the voxel becomes observed with distance +0, is never a source and is never
+ *    updated -- an observed "surface" voxel that nobody measured.  With default_distance_m = inf it is 0 * inf = NaN instead.
+ *  - a NaN weight is not < min_weight, so the voxel counts as observed.
+ *  - max_distance_m below one voxel step: only fixed voxels below it are sources, their neighbours get one step, nothing
+ *    further moves; with default_distance_m <= one step nothing moves at all.
+ *  - default_distance_m < max_distance_m: voxels still at the default are sources too, harmlessly (default + step never
+ *    improves on the default); values above the default are never written. */
 typedef struct vgx_esdf_config {
   float max_distance_m;     /* 2.0   */
   float min_distance_m;     /* 0.2   */

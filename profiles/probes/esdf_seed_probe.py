@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""One seed of profiles/fuzz_esdf.py in detail: where the device ESDF and the restated queue differ, and by how much."""
+"""One seed of profiles/fuzz_esdf.py's first draw (shell-observed scenes only; the fuzzer has since gained a carved family and
+draws differently, the recorded finding 5840 keeps this draw and its own test) in detail: where the device ESDF and the restated
+queue differ, and by how much."""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

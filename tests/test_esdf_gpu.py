@@ -170,3 +170,171 @@ def test_the_max_distance_frontier_when_the_default_lies_beyond_it(capi, ctx):
     err, _ = _check_fixed_point(sm.block_index, td, ed, eo, vs, vps, kw["min_distance_m"], kw["max_distance_m"], kw["default_distance_m"])
     assert err < 1e-6                                                            # the device layer IS the recurrence's fixed point
     g.destroy()
+
+
+# ---- the long propagation: carved scenes (tests/esdf_scenes.py) against the numpy restatement (tests/esdf_ref.py), bit for bit ----
+# The device layer is the greatest fixed point of a monotone f32 recurrence, so its bits are determined: every test below
+# compares download_layers with the restatement by np.array_equal on the bits, distance and observed.  tests/test_esdf_cpu.py
+# holds the restatement itself to the queue and to analytic answers.
+from tests import esdf_ref  # noqa: E402
+from tests import esdf_scenes as S  # noqa: E402
+
+
+def _config(capi, cfg):
+    return capi.esdf_config(max_distance_m=cfg[0], min_distance_m=cfg[1], default_distance_m=cfg[2])
+
+
+def _assert_bits(what, ed, eo, rd, ro):
+    assert esdf_ref.same_bits(eo, ro), (what, "observed layer: voxels that differ", int((eo != ro).sum()))
+    bad = ed.view(np.uint32) != rd.view(np.uint32)
+    assert not bad.any(), (what, "distance layer: voxels that differ", int(bad.sum()), "largest difference",
+                           float(np.nanmax(np.abs(ed[bad] - rd[bad]))), "first", ed[bad][:4], rd[bad][:4])
+
+
+def _run_scene(capi, ctx, name, cfg):
+    """generate on a fresh submap of the scene; the layers must be the restatement's bits; -> (ed, eo, passes)"""
+    sc = S.scene(name)
+    g = capi.Submap(ctx, 0, sc.vs, sc.vps, sc.bi, sc.td, sc.tw, None, None)
+    try:
+        passes = g.generate_esdf(_config(capi, cfg))
+        td, tw, ed, eo = g.download_layers(sc.vps)
+    finally:
+        g.destroy()
+    rd, ro, sweeps = S.reference(name, cfg)
+    print("%s %s: %d blocks, %d passes on the device, %d Jacobi sweeps in the restatement" % (name, cfg, len(sc.bi), passes, sweeps))
+    assert esdf_ref.same_bits(td, sc.td) and esdf_ref.same_bits(tw, sc.tw)
+    _assert_bits((name, cfg), ed, eo, rd, ro)
+    return ed, eo, passes
+
+
+@pytest.mark.parametrize("name,cfg", S.cases(("box_vps8", "box_vps16", "box_vps8_5cm")))
+def test_carved_boxes_where_the_front_travels(capi, ctx, name, cfg):
+    """3 to 5 blocks a side at negative and positive block indices, 5 % holes, shuffled slots; voxblox's defaults and default > max"""
+    ed, eo, passes = _run_scene(capi, ctx, name, cfg)
+    free, moved, far = S.front_travel(S.scene(name), cfg, ed, eo)
+    print("   observed outside the band %d, ended below the default %d, farthest %.1f voxels from the band" % (free, moved, far))
+    assert 2 * moved > free and far > 12 and passes >= 3
+
+
+HALO = [n for n in S.SCENES if n.startswith("halo_")]
+
+
+@pytest.mark.parametrize("vps", [8, 16])
+def test_two_blocks_that_share_only_an_edge_or_only_a_corner(capi, ctx, vps):
+    """twelve edge offsets and eight corner offsets at vps 8, four of them at vps 16: whatever reaches the block without a source
+    came through one halo row (edge) or the single diagonal halo voxel (corner)"""
+    names = [n for n in HALO if n.startswith("halo_vps%d_" % vps)]
+    assert len(names) == (20 if vps == 8 else 4)
+    for name in names:
+        cfg = S.configs(name)[0]
+        ed, eo, _ = _run_scene(capi, ctx, name, cfg)
+        assert (np.abs(ed[0]) < F(cfg[2])).sum() > (vps ** 3) // 4          # slot 0 is the block without a source: it was reached
+
+
+@pytest.mark.parametrize("name", ["lut_corners_fed_vps8", "lut_corners_fed_vps16", "lut_corners_alone_vps8", "lut_corners_alone_vps16",
+                                  "unobserved_vps8", "unobserved_vps16"])
+def test_blocks_at_the_corners_of_the_block_box_and_an_unobserved_neighbour(capi, ctx, name):
+    cfg = S.configs(name)[0]
+    sc = S.scene(name)
+    ed, eo, _ = _run_scene(capi, ctx, name, cfg)
+    reached = (np.abs(ed) < F(cfg[2])).any(1)
+    if name.startswith("lut_corners_fed"):
+        assert reached.all()                                                 # every corner block through its one diagonal voxel
+    elif name.startswith("unobserved"):
+        assert not eo[1].any() and reached[[0, 2, 3, 4, 5]].all()            # round the unobserved block, not through it
+        v = S.voxel_index(sc.bi[:1], sc.vps)[0]
+        face = v[:, 0] == 2 * sc.vps                                         # the face of block (2,0,0) that touches it
+        nearest = v[face][np.argmin(np.abs(ed[0][face]))]
+        assert nearest[1] == sc.vps - 1                                      # entered from the second row, not straight through
+
+
+@pytest.mark.parametrize("cfg", S.configs("corridor"))
+def test_a_corridor_of_40_blocks(capi, ctx, cfg):
+    """the front crosses 40 blocks against the slot order.  The uncapped configurations (max_distance_m = inf, 1e10) reach 31.8 m
+    and need 80 passes.  Before the pass limit was formed in floating point, the cast of max_distance_m / voxel_size to int was
+    undefined for them: the limit came out as zero, no pass ran, and the call returned VGX_OK over a layer still at its initial
+    values (all 20 288 voxels outside the band wrong)."""
+    ed, eo, passes = _run_scene(capi, ctx, "corridor", cfg)
+    print("   corridor %s: %d passes, farthest value %.3f m" % (cfg, passes, np.abs(ed).max()))
+    if cfg[0] > 2.0:
+        assert np.abs(ed).max() > 31.5 and passes > 40
+
+
+@pytest.mark.parametrize("name", ["labyrinth_vps8", "labyrinth_vps16"])
+def test_a_labyrinth_of_unobserved_walls(capi, ctx, name):
+    for cfg in S.configs(name):
+        _run_scene(capi, ctx, name, cfg)
+
+
+@pytest.mark.parametrize("name", ["wall2_vps8", "wall3_vps8", "wall2_vps16", "wall3_vps16"])
+def test_signs_never_cross_a_one_voxel_band(capi, ctx, name):
+    sc = S.scene(name)
+    ed, eo, _ = _run_scene(capi, ctx, name, S.configs(name)[0])
+    assert np.all(ed[sc.td <= -F(0.3)] < 0) and np.all(ed[sc.td >= F(0.3)] > 0)
+
+
+@pytest.mark.parametrize("name,cfg", S.cases(("zeros", "nans", "box_small")))
+def test_arithmetic_edges(capi, ctx, name, cfg):
+    """min_distance_m = 0; +0.0 and -0.0 outside the band; NaN weights and NaN distances; max_distance_m below one voxel step;
+    default_distance_m below max_distance_m (what each does is stated at vgx_submap_generate_esdf in the header)"""
+    _run_scene(capi, ctx, name, cfg)
+
+
+def _assert_query_returns(g, sc, ed, eo):
+    q = g.query(synth.voxel_centres(sc.vs, sc.vps, sc.bi).reshape(-1, 3), layer="esdf", interpolate=False)
+    assert np.array_equal(q.valid, eo.ravel().astype(bool))
+    assert esdf_ref.same_bits(q.distance[q.valid], ed.ravel()[q.valid])
+
+
+def test_generating_again_replaces_the_layer_the_queries_and_the_sampling_grid(capi, ctx):
+    name = "box_whole"
+    first, second = S.configs(name)
+    sc = S.scene(name)
+    want = {c: S.reference(name, c)[:2] for c in (first, second)}
+    differ = (want[first][0] != want[second][0]) & (np.abs(want[second][0]) < 0.3) & (sc.tw >= 1)
+    assert differ.sum() > 100                                                # a stale sampling grid would show below
+    # a submap created with ESDF arrays of its own: the upload is overwritten
+    rng = np.random.default_rng(7)
+    g = capi.Submap(ctx, 0, sc.vs, sc.vps, sc.bi, sc.td, sc.tw, rng.uniform(-3, 3, sc.td.shape).astype(F), np.ones(sc.td.shape, np.uint8))
+    try:
+        g.query(np.zeros((4, 3), F), layer="esdf", interpolate=True)
+        for cfg in (first, second, first):
+            g.generate_esdf(_config(capi, cfg))
+            _, _, ed, eo = g.download_layers(sc.vps)
+            _assert_bits(("regenerated", cfg), ed, eo, *want[cfg])
+            _assert_query_returns(g, sc, ed, eo)
+            # the sampling grid is the new layer's: the new voxel points read back their own distances through it
+            n = g.extract_voxel_points(1.0, 0.3, True)
+            cf = capi.RegistrationCostFunction(ctx, g, g, capi.default_config(registration_point_type=capi.POINTS_VOXELS))
+            r = np.ones(n)
+            assert n > 100 and cf.Evaluate([np.zeros(4), np.zeros(4)], r, None) and np.all(r == 0)
+            cf.destroy()
+    finally:
+        g.destroy()
+
+
+def test_a_submap_handed_off_from_an_integrated_layer(capi, ctx):
+    """three small scans through the reproducible integrator: real carving (weight > 0 along every ray), then from_tsdf_layer and
+    generate_esdf; the restatement runs on the TSDF the submap itself downloads"""
+    vs, vps = 0.1, 8
+    layer = capi.TsdfLayer(ctx, vs, vps)
+    integ = capi.FastTsdfIntegrator(ctx, capi.voxgraph_tsdf_config(deterministic=1, default_truncation_distance=0.3), layer)
+    for T, pts in S.room_scans(3):
+        integ.integratePointCloud(T, pts)
+    g = capi.Submap.from_tsdf_layer(ctx, layer, 5)
+    try:
+        for cfg in (S.DEFAULT, (1.2, 0.15, 2.0)):
+            passes = g.generate_esdf(_config(capi, cfg))
+            td, tw, ed, eo = g.download_layers(vps)
+            sc = S.Scene(g.voxel_size, vps, g.block_index(), td, tw)
+            rd, ro, sweeps = esdf_ref.esdf_from_tsdf(sc.vs, vps, sc.bi, td, tw, *cfg, return_sweeps=True)
+            free, moved, far = S.front_travel(sc, cfg, ed, eo)
+            print("handed-off submap %s: %d blocks, %d passes, %d Jacobi sweeps; observed outside the band %d, moved %d, farthest %.1f voxels"
+                  % (cfg, len(sc.bi), passes, sweeps, free, moved, far))
+            _assert_bits(("hand-off", cfg), ed, eo, rd, ro)
+            assert len(sc.bi) > 30 and 2 * moved > free and far > 8
+            _assert_query_returns(g, sc, ed, eo)
+    finally:
+        g.destroy()
+        integ.destroy()
+        layer.destroy()

@@ -11,6 +11,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # (seeds, first) of the two map-product fuzzers: tests/test_fuzz_map_cpu.py checks the generator over exactly these
 MAP_LAYERS = (36, 300)
 MAP_MESHES = (60, 300)
+# (seeds, first) of the ESDF fuzzer: tests/test_esdf_cpu.py holds the restatement to the queue over exactly these draws
+ESDF = (24, 300)
 
 
 def _run(script, seeds, first):
@@ -80,3 +82,9 @@ def test_map_meshes_random_scenes_bit_identical_to_the_restatements():
     """the combined, submap and separated meshes at the drawn min_weight, each welded at two thresholds from 1e-10 to
     four times the scene's extent (thousands of soup vertices into one key)"""
     assert _run("fuzz_map_meshes", *MAP_MESHES) == 0
+
+
+def test_esdf_random_submaps_bit_identical_to_the_restatement_and_close_to_the_queue():
+    """shell-observed and carved submaps, random max / default / min distances: both ESDF layers the bits of tests/esdf_ref.py,
+    and the queue's contract (masks, fixed band, signs, never above, within 4 mm, fixed-point residual)"""
+    assert _run("fuzz_esdf", *ESDF) == 0

@@ -10,7 +10,10 @@
 // runs a few in-LDS sweeps (26 LDS reads per voxel per sweep, no global traffic), writes
 // the block back and raises a flag if anything moved; the host repeats passes until the
 // flag stays clear.  HBM traffic per pass: 4 B read (+ halo) + 4 B written per voxel.
+#include <algorithm>
 #include <cmath>
+#include <cstdint>
+#include <string>
 #include <vector>
 
 #include "vgx_internal.h"
@@ -174,10 +177,23 @@ int vgx_submap_generate_esdf(vgx_submap sm, const vgx_esdf_config* cfg_in, int32
                      cfg.default_distance_m, sm->d_esdf_distance, sm->d_esdf_observed);
   int3 mn = make_int3(sm->lut_min[0], sm->lut_min[1], sm->lut_min[2]);
   int3 dm = make_int3(sm->lut_dim[0], sm->lut_dim[1], sm->lut_dim[2]);
-  int passes = 0, rc = VGX_OK;
-  // the farthest a front travels is max_distance / voxel_size voxels; every pass
-  // advances it by at least one voxel across block borders
-  const int max_passes = 8 + (int)std::ceil(cfg.max_distance_m / sm->voxel_size) * 2;
+  int rc = VGX_OK;
+  // The pass limit.  A voxel's final value is the f32 sum of the steps along its best path from a source.  Once the voxel
+  // before it on that path is final, one more pass makes this one final too: its block stages that neighbour, in the tile
+  // or in the halo, and sweeps at least once.  So a best path of k steps is done after k passes, and one more pass sees
+  // nothing move.  Two bounds on k:
+  //  - by the configuration: every step adds at least one voxel_size and a source lies below max_distance_m, so
+  //    k <= max_distance_m / voxel_size + 1; the limit doubles that and adds 8, far more than f32 rounding along the path
+  //    can cost;
+  //  - by the submap, whatever the configuration (max_distance_m = inf, an uncapped ESDF, included): values only fall, so
+  //    a best path visits no voxel twice and k < the submap's voxel count.  (The longer side of the block box would not
+  //    do: a path that winds round unobserved walls is longer than any fixed multiple of it.)
+  // Both are formed in double: max_distance_m / voxel_size need not fit an int (inf, or 1e10 at 0.1 m voxels).
+  const double by_config = 8.0 + 2.0 * std::ceil((double)cfg.max_distance_m / (double)sm->voxel_size);
+  const double by_size = (double)nvox + 1.0;
+  const long long max_passes = (long long)std::min(by_config, by_size);  // (by_config may be +inf; by_size is finite)
+  long long passes = 0;
+  bool converged = false;
   while (passes < max_passes) {
     hipError_t e = hipMemsetAsync(d_changed, 0, sizeof(int), ctx->stream);
     if (e == hipSuccess) {
@@ -201,16 +217,25 @@ int vgx_submap_generate_esdf(vgx_submap sm, const vgx_esdf_config* cfg_in, int32
       break;
     }
     ++passes;
-    if (!h_changed) break;
+    if (!h_changed) {
+      converged = true;
+      break;
+    }
   }
-  if (rc != VGX_OK) return rc;
-  if (sweeps_out) *sweeps_out = passes;
-  // (re)build the ESDF sampling grid
+  // the ESDF layer was rewritten: whatever happens next, the sampling grid made from the old one is stale
   if (sm->grid[1].d_bricks) {
     sm->grid[1].d_bricks.release();
     sm->grid[1].present = false;
   }
   sm->grid[1].d_quad.release();  // (made on demand from the bricks just dropped: made again when next asked for)
+  if (rc != VGX_OK) return rc;
+  if (sweeps_out) *sweeps_out = (int32_t)std::min<long long>(passes, INT32_MAX);
+  // never a half-relaxed layer under VGX_OK: by the bounds above this means the relaxation itself is broken
+  if (!converged)
+    return set_error(ctx, VGX_ERR_INVALID,
+                     "vgx_submap_generate_esdf: still changing after " + std::to_string(passes) +
+                         " passes, the limit: the ESDF layer is only partly relaxed and has no sampling grid");
+  // (re)build the ESDF sampling grid
   return launch_brickify(sm, 1);
 }
 
