@@ -915,6 +915,116 @@ VGX_API int vgx_scan_decode_msg_undistorted_device(vgx_scan scan, const vgx_scan
  * three drop reasons (not finite + bad time + overflowed).  Any may be NULL; no device work. */
 VGX_API int vgx_scan_undistort_stats(vgx_scan scan, int64_t* n_bad_time, int64_t* n_overflowed, int64_t* n_clamped);
 
+/* ---- Depth-image scans: a sensor_msgs/Image depth frame unprojected, coloured and filtered inside the decode ---- */
+/* An RGB-D driver publishes a depth image (16UC1 counts or 32FC1 metres) with a CameraInfo and usually a registered colour
+ * image, not a cloud.  vgx_scan_decode_depth_image fills a vgx_scan from those: what depth_image_proc's point_cloud_xyz[rgb]
+ * nodelet followed by the PointCloud2 decode would leave, without the cloud ever existing.  Afterwards the handle is
+ * what it is after vgx_scan_decode_msg -- vgx_scan_stats / _download / _device_pointers, vgx_tsdf_integrate[_merged]_scan
+ * and vgx_scan_registration_set_scan behave alike -- and a handle may be decoded into by any decode kind in turn.
+ * depth_image_proc is not vendored: the rules are DEFINED here, and where one is modelled on it, it says [recalled].
+ * Rules (what the kernel, vgx_scan.hip, and tests/depth_image_ref.py both follow; f32 with one rounding per operation,
+ * no contraction, unless it says f64):
+ *   candidates  pixel (u, v) is a candidate iff u % stride_u == 0 && v % stride_v == 0.  wc = ceil(width / stride_u),
+ *               hc = ceil(height / stride_v), candidate i = (v / stride_v) * wc + (u / stride_u), n_candidates = wc * hc.
+ *               Kept points stay in ascending i: image row-major order, the order the reproducible integrator visits them in.
+ *   depth       16UC1: raw = the two little-endian bytes at depth + v * row_step + 2 u, z = (float)raw * depth_unit_m.
+ *               32FC1: z = the float whose four little-endian bytes lie at depth + v * row_step + 4 u.  Any row_step >=
+ *               width * bytes per pixel and any base address are legal; when the base and row_step are multiples of the
+ *               element size the kernel loads elements, else it assembles them from bytes; the result is the same.
+ *   filter      in this order, one counter each (vgx_scan_depth_stats):
+ *               1. invalid unless 0 < z && z < +inf.  For 16UC1 that is raw != 0, depth_image_proc's rule [recalled]; for
+ *                  32FC1 it also drops 0, -0 and negatives, which depth_image_proc keeps: a stated deviation (a point at
+ *                  or behind the optical centre is no measurement).
+ *               2. out of range unless min_depth_m <= z && z <= max_depth_m.
+ *               3. x = (((float)u - cxf) * z) * kx, y = (((float)v - cyf) * z) * ky with cxf = (float)cx, cyf = (float)cy,
+ *                  kx = (float)(1.0 / fx), ky = (float)(1.0 / fy): each formed on the host in f64 and rounded once.  The
+ *                  point is (x, y, z) in the optical frame (z forward, x right, y down).
+ *               4. overflowed unless x and y are finite.
+ *   track step  (the undistorting forms) for a point that survived: t = offset_s + (double)v * scale with v the row in the
+ *               full image, one rounded f64 multiply then one rounded f64 add; the segment, point and remaining filter
+ *               rules of "Scan undistortion" apply word for word (bad time, then overflowed after the track), counted by
+ *               vgx_scan_undistort_stats as they are there.  vgx_scan_depth_stats' n_overflowed counts step 4 only.
+ *   counters    vgx_scan_stats' n_dropped = n_candidates - n_points, the sum of all drop reasons (pixels the strides skip
+ *               are not drops).  vgx_scan_undistort_stats reports zeros after a depth decode without a track,
+ *               vgx_scan_depth_stats reports zeros after a PointCloud2 decode.
+ *   colour      of a kept point, from the bytes b0.. of the pixel at color + v * color_row_step + u * bytes per pixel:
+ *               RGB8 (b0, b1, b2, 255), BGR8 (b2, b1, b0, 255), RGBA8 (b0, b1, b2, b3), BGRA8 (b2, b1, b0, b3), MONO8
+ *               (b0, b0, b0, 255); NONE: vgx_scan_config.constant_rgba.  The config's intensity range is validated as the
+ *               other decodes validate it and is otherwise unused.
+ * Refused with VGX_ERR_INVALID before anything is uploaded or launched, the scan keeping what it held (vgx_last_error
+ * says which): NULL arguments (cfg may be NULL: the defaults), a colour image that is NULL while color_kind is not NONE,
+ * an unknown encoding or colour kind, row_step < width * bytes per pixel and the same for the colour image, n_bytes <
+ * (height - 1) * row_step + width * bytes per pixel when width * height > 0 for either image, fx or fy zero or not finite,
+ * cx or cy not finite, depth_unit_m not finite or <= 0 (16UC1), a NaN depth bound, min_depth_m < 0, min_depth_m >
+ * max_depth_m, a stride < 1, an intensity range the other decodes refuse, a row time whose scale or offset_s is not
+ * finite, and everything vgx_scan_undistort_check refuses in a track.  VGX_ERR_UNSUPPORTED: is_bigendian != 0; width *
+ * height >= 2^31.  width * height == 0, or every candidate dropped: VGX_OK and 0 points.  Out of device memory:
+ * VGX_ERR_NOMEM, and the handle then holds no scan.
+ * Streams and cost are the PointCloud2 decode's: the TSDF stream under the TSDF lock; the host forms upload the depth
+ * image and then the colour image through the handle's two pinned staging buffers filled in turn; ONE kernel whatever the
+ * size (tiles of 1024 consecutive candidates, four per thread, ranked inside the workgroup and along the tile chain: no
+ * atomic decides a position); ONE read-back of the counters (64 bytes), the call's one host synchronisation.  One call at
+ * a time per handle. */
+#define VGX_DEPTH_16UC1 0 /* uint16 counts, also "mono16" */
+#define VGX_DEPTH_32FC1 1 /* float32 metres */
+#define VGX_IMAGE_COLOR_NONE 0
+#define VGX_IMAGE_COLOR_RGB8 1
+#define VGX_IMAGE_COLOR_BGR8 2
+#define VGX_IMAGE_COLOR_RGBA8 3
+#define VGX_IMAGE_COLOR_BGRA8 4
+#define VGX_IMAGE_COLOR_MONO8 5
+typedef struct vgx_depth_image_layout {
+  uint32_t width, height, row_step; /* the depth image; row_step in bytes */
+  int32_t encoding;                 /* VGX_DEPTH_* */
+  int32_t is_bigendian;
+  int32_t color_kind;               /* VGX_IMAGE_COLOR_*; the colour image has the depth image's width and height */
+  uint32_t color_row_step;          /* not read for VGX_IMAGE_COLOR_NONE */
+} vgx_depth_image_layout;
+/* Fill it with vgx_depth_camera_default() before setting fields (fx, fy have no default); every field is validated. */
+typedef struct vgx_depth_camera {
+  double fx, fy, cx, cy;          /* CameraInfo K[0], K[4], K[2], K[5] of the RECTIFIED depth image */
+  float depth_unit_m;             /* 0.001: metres per count of a 16UC1 image; not read for 32FC1 */
+  float min_depth_m, max_depth_m; /* 0, +inf: the z-depth gate, both ends included */
+  int32_t stride_u, stride_v;     /* 1, 1: every stride-th column / row */
+} vgx_depth_camera;
+/* a rolling shutter's time of image row v: t = offset_s + (double)v * scale, in the track's time */
+typedef struct vgx_depth_row_time {
+  double scale, offset_s;
+} vgx_depth_row_time;
+VGX_API void vgx_depth_camera_default(vgx_depth_camera* camera);
+/* HOST ONLY (no device, no context): VGX_OK, or the code a decode of these byte counts is refused with.  It takes no
+ * config: the intensity range is checked by the decode calls alone.  color_n_bytes is not read for VGX_IMAGE_COLOR_NONE. */
+VGX_API int vgx_depth_image_check(const vgx_depth_image_layout* layout, const vgx_depth_camera* camera, int64_t depth_n_bytes,
+                                  int64_t color_n_bytes);
+/* ... and the code an undistorting decode is refused with */
+VGX_API int vgx_depth_image_undistort_check(const vgx_depth_image_layout* layout, const vgx_depth_camera* camera,
+                                            const vgx_depth_row_time* row_time, const vgx_scan_track* track,
+                                            int64_t depth_n_bytes, int64_t color_n_bytes);
+/* depth, color: the images' bytes in host memory (pageable is fine: they are read before the call returns); color is not
+ * read for VGX_IMAGE_COLOR_NONE; cfg == NULL: the defaults.  Returns with the scan decoded and counted. */
+VGX_API int vgx_scan_decode_depth_image(vgx_scan scan, const vgx_depth_image_layout* layout, const vgx_depth_camera* camera,
+                                        const vgx_scan_config* cfg, const void* depth, int64_t depth_n_bytes,
+                                        const void* color, int64_t color_n_bytes);
+/* the same with both images already in DEVICE memory, ready with respect to the TSDF stream (vgx_ctx_tsdf_wait_for_stream) */
+VGX_API int vgx_scan_decode_depth_image_device(vgx_scan scan, const vgx_depth_image_layout* layout,
+                                               const vgx_depth_camera* camera, const vgx_scan_config* cfg, const void* d_depth,
+                                               int64_t depth_n_bytes, const void* d_color, int64_t color_n_bytes);
+/* the same with the track step: a rolling-shutter frame taken while the camera moved (the track's arrays are HOST arrays) */
+VGX_API int vgx_scan_decode_depth_image_undistorted(vgx_scan scan, const vgx_depth_image_layout* layout,
+                                                    const vgx_depth_camera* camera, const vgx_scan_config* cfg,
+                                                    const vgx_depth_row_time* row_time, const vgx_scan_track* track,
+                                                    const void* depth, int64_t depth_n_bytes, const void* color,
+                                                    int64_t color_n_bytes);
+VGX_API int vgx_scan_decode_depth_image_undistorted_device(vgx_scan scan, const vgx_depth_image_layout* layout,
+                                                           const vgx_depth_camera* camera, const vgx_scan_config* cfg,
+                                                           const vgx_depth_row_time* row_time, const vgx_scan_track* track,
+                                                           const void* d_depth, int64_t depth_n_bytes, const void* d_color,
+                                                           int64_t color_n_bytes);
+/* Of the last decode: the pixels the strides kept, and of those the ones dropped as invalid, as out of range and because
+ * x or y was not finite.  Zeros after a PointCloud2 decode.  Any may be NULL; no device work. */
+VGX_API int vgx_scan_depth_stats(vgx_scan scan, int64_t* n_candidates, int64_t* n_invalid, int64_t* n_out_of_range,
+                                 int64_t* n_overflowed);
+
 /* finishSubmap() hand-off without a host round trip: turns the active layer's blocks
  * into a (not yet finished) submap holding the raw TSDF layer and its TSDF sampling
  * grid; follow with vgx_submap_generate_esdf and vgx_submap_extract_voxel_points.  The

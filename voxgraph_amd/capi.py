@@ -118,6 +118,30 @@ class ScanTrackView(C.Structure):
 SCAN_TIME_UINT32, SCAN_TIME_FLOAT32, SCAN_TIME_FLOAT64 = 0, 1, 2
 
 
+class DepthImageLayout(C.Structure):
+    """vgx_depth_image_layout: a sensor_msgs/Image depth frame's header and its registered colour image's."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("row_step", C.c_uint32), ("encoding", C.c_int32),
+                ("is_bigendian", C.c_int32), ("color_kind", C.c_int32), ("color_row_step", C.c_uint32)]
+
+
+class DepthCamera(C.Structure):
+    """vgx_depth_camera: the rectified pinhole model, the depth unit and gate, and the pixel strides."""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("depth_unit_m", C.c_float),
+                ("min_depth_m", C.c_float), ("max_depth_m", C.c_float), ("stride_u", C.c_int32), ("stride_v", C.c_int32)]
+
+
+class DepthRowTime(C.Structure):
+    """vgx_depth_row_time: t = offset_s + v * scale of image row v."""
+    _fields_ = [("scale", C.c_double), ("offset_s", C.c_double)]
+
+
+DEPTH_16UC1, DEPTH_32FC1 = 0, 1
+IMAGE_COLOR_NONE, IMAGE_COLOR_RGB8, IMAGE_COLOR_BGR8, IMAGE_COLOR_RGBA8, IMAGE_COLOR_BGRA8, IMAGE_COLOR_MONO8 = 0, 1, 2, 3, 4, 5
+DEPTH_BYTES_PER_PIXEL = {DEPTH_16UC1: 2, DEPTH_32FC1: 4}
+IMAGE_COLOR_BYTES_PER_PIXEL = {IMAGE_COLOR_NONE: 0, IMAGE_COLOR_RGB8: 3, IMAGE_COLOR_BGR8: 3, IMAGE_COLOR_RGBA8: 4,
+                               IMAGE_COLOR_BGRA8: 4, IMAGE_COLOR_MONO8: 1}
+
+
 class EvaluationDetails(C.Structure):
     """vgx_voxel_evaluation_details: voxblox::utils::VoxelEvaluationDetails plus the f64 sum and the true min |e|."""
     _fields_ = [("rmse", C.c_float), ("max_error", C.c_float), ("min_error", C.c_float),
@@ -364,6 +388,21 @@ SIGNATURES = {
     "vgx_scan_decode_msg_undistorted_device": (C.c_int, [vp, C.POINTER(ScanLayout), C.POINTER(ScanConfig), C.POINTER(ScanTimeField),
                                                          C.POINTER(ScanTrackView), vp, C.c_int64]),
     "vgx_scan_undistort_stats": (C.c_int, [vp, i64p, i64p, i64p]),
+    "vgx_depth_camera_default": (None, [C.POINTER(DepthCamera)]),
+    "vgx_depth_image_check": (C.c_int, [C.POINTER(DepthImageLayout), C.POINTER(DepthCamera), C.c_int64, C.c_int64]),
+    "vgx_depth_image_undistort_check": (C.c_int, [C.POINTER(DepthImageLayout), C.POINTER(DepthCamera), C.POINTER(DepthRowTime),
+                                                  C.POINTER(ScanTrackView), C.c_int64, C.c_int64]),
+    "vgx_scan_decode_depth_image": (C.c_int, [vp, C.POINTER(DepthImageLayout), C.POINTER(DepthCamera), C.POINTER(ScanConfig),
+                                              vp, C.c_int64, vp, C.c_int64]),
+    "vgx_scan_decode_depth_image_device": (C.c_int, [vp, C.POINTER(DepthImageLayout), C.POINTER(DepthCamera), C.POINTER(ScanConfig),
+                                                     vp, C.c_int64, vp, C.c_int64]),
+    "vgx_scan_decode_depth_image_undistorted": (C.c_int, [vp, C.POINTER(DepthImageLayout), C.POINTER(DepthCamera),
+                                                          C.POINTER(ScanConfig), C.POINTER(DepthRowTime), C.POINTER(ScanTrackView),
+                                                          vp, C.c_int64, vp, C.c_int64]),
+    "vgx_scan_decode_depth_image_undistorted_device": (C.c_int, [vp, C.POINTER(DepthImageLayout), C.POINTER(DepthCamera),
+                                                                 C.POINTER(ScanConfig), C.POINTER(DepthRowTime),
+                                                                 C.POINTER(ScanTrackView), vp, C.c_int64, vp, C.c_int64]),
+    "vgx_scan_depth_stats": (C.c_int, [vp, i64p, i64p, i64p, i64p]),
     "vgx_scan_download": (C.c_int, [vp, f32p, u8p]),
     "vgx_scan_device_pointers": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp)]),
     "vgx_tsdf_integrate_scan": (C.c_int, [vp, f32p, vp, C.c_int32, i64p]),
@@ -1907,6 +1946,56 @@ def scan_undistort_check(layout, time_field, knot_time, knot_T, n_bytes):
                                            None if view is None else C.byref(view), int(n_bytes))
 
 
+def depth_image_layout(**kw):
+    """A vgx_depth_image_layout from keywords (fields not given are 0; row_step and color_row_step default to width *
+    bytes per pixel of the encoding / colour kind)."""
+    lay = DepthImageLayout()
+    for k, v in kw.items():
+        if not hasattr(lay, k):
+            raise AttributeError(k)
+        setattr(lay, k, v)
+    if "row_step" not in kw:
+        lay.row_step = lay.width * DEPTH_BYTES_PER_PIXEL.get(lay.encoding, 0)
+    if "color_row_step" not in kw:
+        lay.color_row_step = lay.width * IMAGE_COLOR_BYTES_PER_PIXEL.get(lay.color_kind, 0)
+    return lay
+
+
+def depth_camera(**kw):
+    """vgx_depth_camera_default() with fields overridden by keyword (fx and fy have no default)."""
+    cam = DepthCamera()
+    load().vgx_depth_camera_default(C.byref(cam))
+    for k, v in kw.items():
+        if not hasattr(cam, k):
+            raise AttributeError(k)
+        setattr(cam, k, v)
+    return cam
+
+
+def depth_row_time(scale, offset_s=0.0):
+    """A vgx_depth_row_time: t = offset_s + v * scale of image row v."""
+    return DepthRowTime(float(scale), float(offset_s))
+
+
+def depth_image_check(layout, camera, depth_n_bytes, color_n_bytes=0, row_time=None, knot_time=None, knot_T=None):
+    """vgx_depth_image_check (host only): OK, or the code a decode of these byte counts is refused with; with a row time
+    or knots given, vgx_depth_image_undistort_check (either may then be None: a NULL argument)"""
+    lay, cam = (None if o is None else C.byref(o) for o in (layout, camera))
+    if row_time is None and knot_time is None:
+        return load().vgx_depth_image_check(lay, cam, int(depth_n_bytes), int(color_n_bytes))
+    view, keep = (None, None) if knot_time is None else scan_track_view(knot_time, knot_T)
+    return load().vgx_depth_image_undistort_check(lay, cam, None if row_time is None else C.byref(row_time),
+                                                  None if view is None else C.byref(view), int(depth_n_bytes), int(color_n_bytes))
+
+
+def _image_bytes(image):
+    """(pointer or None, byte count) of an image's bytes: bytes, bytearray or a contiguous array; None: no image"""
+    if image is None:
+        return None, 0
+    buf = np.frombuffer(image, np.uint8)
+    return (vp(buf.ctypes.data) if buf.size else None), buf.size
+
+
 class ScanTrack:
     """Samples (t, T_fixed_sensor) of a sensor's pose and the vgx_scan_track they make for one scan -- the same
     arithmetic as GpuScanTrack (voxgraph_amd/cpp/gpu_pointcloud_integrator.h), all of it f64, one rounding per operation:
@@ -1949,8 +2038,9 @@ class ScanTrack:
 
 
 class Scan:
-    """A raw PointCloud2 decoded on the GPU (vgx_scan): the finite points and their colours in message order; reused
-    from message to message.  FastTsdfIntegrator.integrate_scan / integrate_merged_scan consume it."""
+    """A raw PointCloud2 -- or a depth image with its camera model -- decoded on the GPU (vgx_scan): the kept points and
+    their colours in message / image order; reused from message to message.  FastTsdfIntegrator.integrate_scan /
+    integrate_merged_scan consume it."""
 
     def __init__(self, ctx):
         self.ctx = ctx
@@ -1989,11 +2079,47 @@ class Scan:
             vp(d_data) if d_data else None, int(n_bytes)))
         return self.stats()
 
+    def decode_depth_image(self, layout, camera, depth, color=None, config=None, row_time=None, knot_time=None, knot_T=None):
+        """A depth image and its registered colour image (host bytes: bytes, bytearray or contiguous arrays; color None
+        for IMAGE_COLOR_NONE) unprojected, filtered and coloured (vgx_scan_decode_depth_image); with row_time (a
+        DepthRowTime) and knots, every point moved into the reference frame by the track
+        (vgx_scan_decode_depth_image_undistorted).  Returns (points, dropped)."""
+        (dp, dn), (cp, cn) = _image_bytes(depth), _image_bytes(color)
+        cfg = None if config is None else C.byref(config)
+        if row_time is None:
+            self.ctx.check(self.ctx.lib.vgx_scan_decode_depth_image(self.h, C.byref(layout), C.byref(camera), cfg, dp, dn, cp, cn))
+        else:
+            view, keep = scan_track_view(knot_time, knot_T)
+            self.ctx.check(self.ctx.lib.vgx_scan_decode_depth_image_undistorted(
+                self.h, C.byref(layout), C.byref(camera), cfg, C.byref(row_time), C.byref(view), dp, dn, cp, cn))
+        return self.stats()
+
+    def decode_depth_image_device(self, layout, camera, d_depth, depth_n_bytes, d_color=None, color_n_bytes=0, config=None,
+                                  row_time=None, knot_time=None, knot_T=None):
+        """the same with the images at device addresses (ready with respect to the TSDF stream)"""
+        dp, cp = (vp(a) if a else None for a in (d_depth, d_color))
+        cfg = None if config is None else C.byref(config)
+        if row_time is None:
+            self.ctx.check(self.ctx.lib.vgx_scan_decode_depth_image_device(self.h, C.byref(layout), C.byref(camera), cfg, dp,
+                                                                           int(depth_n_bytes), cp, int(color_n_bytes)))
+        else:
+            view, keep = scan_track_view(knot_time, knot_T)
+            self.ctx.check(self.ctx.lib.vgx_scan_decode_depth_image_undistorted_device(
+                self.h, C.byref(layout), C.byref(camera), cfg, C.byref(row_time), C.byref(view), dp, int(depth_n_bytes), cp,
+                int(color_n_bytes)))
+        return self.stats()
+
     def stats(self):
         """(points, dropped)"""
         n, d = C.c_int64(), C.c_int64()
         self.ctx.check(self.ctx.lib.vgx_scan_stats(self.h, C.byref(n), C.byref(d)))
         return n.value, d.value
+
+    def depth_stats(self):
+        """(candidates, invalid, out_of_range, overflowed) of the last decode; zeros after a PointCloud2 decode"""
+        v = [C.c_int64() for _ in range(4)]
+        self.ctx.check(self.ctx.lib.vgx_scan_depth_stats(self.h, *(C.byref(x) for x in v)))
+        return tuple(x.value for x in v)
 
     def undistort_stats(self):
         """(bad_time, overflowed, clamped) of the last decode; zeros after a plain one"""
