@@ -1025,6 +1025,83 @@ VGX_API int vgx_scan_decode_depth_image_undistorted_device(vgx_scan scan, const 
 VGX_API int vgx_scan_depth_stats(vgx_scan scan, int64_t* n_candidates, int64_t* n_invalid, int64_t* n_out_of_range,
                                  int64_t* n_overflowed);
 
+/* ---- Projective depth-image integration: every voxel in view looks up ONE pixel and updates itself ---- */
+/* The way dense RGB-D mappers integrate a frame (KinectFusion; voxblox's ProjectiveTsdfIntegrator [recalled]): no cloud, no
+ * rays.  A gather -- one lane owns a voxel -- so nothing races, nothing is sorted and no approximate set is asked: the same
+ * frames give the same layer, block order included, bit for bit on every run.  Neither project is vendored: the rules are
+ * DEFINED here (what the kernel, vgx_projective.hip, and tests/projective_ref.py both follow; f32 with one rounding per
+ * operation, no contraction, unless it says f64).  The integrator, its vgx_tsdf_config and its layer are the existing ones.
+ * Config fields READ: default_truncation_distance (trunc), max_weight, voxel_carving_enabled, min_ray_length_m,
+ * max_ray_length_m, use_const_weight, allow_clear, use_weight_dropoff.  NOT read: use_sparsity_compensation_factor,
+ * sparsity_compensation_factor, start_voxel_subsampling_factor, max_consecutive_ray_collisions,
+ * clear_checks_every_n_frames, enable_anti_grazing, deterministic, integration_order.  Of vgx_depth_camera the strides are
+ * validated and otherwise not read: every pixel can be looked up.
+ *   candidates  vgx_tsdf_projective_box, on the host in f64: reach = min(max_depth_m, max_ray_length_m) + trunc (an
+ *               infinite max_depth_m is bounded by max_ray_length_m), taken as a Z-DEPTH.  The box is the axis-aligned box,
+ *               in the layer frame, of the camera centre and of the four points P = ((u - cx) / fx * reach, (v - cy) / fy *
+ *               reach, reach) for (u, v) in {-0.5, width - 0.5} x {-0.5, height - 0.5} (the corners of the area whose
+ *               pixels can be looked up), each moved by T_G_C as below (uv = qv x P, uv += uv, cc = qv x uv, (P + qw uv +
+ *               cc) + t).  Every voxel the rules can update has z <= reach (gates 3 and 4: z <= d + trunc and z <= r_v <= r_s + trunc;
+ *               a clearing one: r_v <= max_ray_length_m - trunc < r_s, so z < d) and lies in that pyramid.  [A ray RANGE of `reach` along
+ *               the corner rays would not contain them: the on-axis voxel at range reach lies beyond the corner points' plane.]
+ *               lo = floor(min / bs) - 1, hi = floor(max / bs) + 1 per axis with bs = (double)voxel_size * voxels_per_side:
+ *               the blocks that hold the extremes, widened by one block on every side.  Candidates are the blocks of
+ *               [lo, hi] in ascending (z, y, x) order; n_candidate_blocks counts all of them (the kernel rejects whole
+ *               blocks that provably find no pixel before it looks at their voxels; that changes no value and no count).
+ *   voxel       global index (vx, vy, vz) = block * voxels_per_side + local; centre g = ((float)v + 0.5f) * voxel_size per axis.
+ *   camera      p = g - t per axis, then rotated by the conjugate quaternion qv = (-qx, -qy, -qz), qw in the operation order
+ *               of the library's transforms: uv = qv x p (each component a b - c d), uv += uv, cc = qv x uv, and
+ *               (x, y, z) = (p + qw * uv) + cc.  The quaternion is used as given (not normalised).
+ *   pixel       no update unless z > 0.  uf = (x / z) * (float)fx + (float)cx, vf = (y / z) * (float)fy + (float)cy;
+ *               accepted iff 0 <= uf + 0.5f < (float)width and 0 <= vf + 0.5f < (float)height, tested in f32 before any
+ *               cast; ui = floorf(uf + 0.5f), vi = floorf(vf + 0.5f).  Nearest pixel only.
+ *   depth       d = the z of pixel (ui, vi) by the decode's depth rule; no update unless it passes the decode's filter
+ *               rules 1 (0 < d < +inf) and 2 (min_depth_m <= d <= max_depth_m).
+ *   ranges      r_v = sqrtf(x x + y y + z z) (summed left to right), s = r_v / z, r_s = d * s, sdf = (d - z) * s.
+ *   gates       in this order: 1. r_s < min_ray_length_m: no update.  2. r_s > max_ray_length_m: a clearing pixel -- an
+ *               update only if allow_clear && voxel_carving_enabled && r_v + trunc <= max_ray_length_m, with sdf =
+ *               max_ray_length_m - r_v, counted in n_cleared; the gates below are not asked.  3. sdf < -trunc: no
+ *               update.  4. sdf > trunc: an update only if voxel_carving_enabled, the sdf as it is, counted in n_carved.
+ *   weight      w = use_const_weight ? 1 : 1.0f / (d * d); if use_weight_dropoff && sdf < -voxel_size:
+ *               w = fmaxf((w * (trunc + sdf)) / (trunc - voxel_size), 0).  No sparsity factor.
+ *   update      updateTsdfVoxel as every integrator here applies it: W = w_old + w; nothing changes if W < 1e-6f; else
+ *               distance = clamp((sdf * w + d_old * w_old) / W, -trunc, trunc), the colour blended (Color::blendTwoColors
+ *               with weights w_old, w) only where |sdf| < trunc, weight = fminf(max_weight, W).  A voxel of a block the layer
+ *               does not hold is (0, 0, colour 0).  n_updates counts the voxels that changed (W >= 1e-6f); n_carved and
+ *               n_cleared count those of them that came through gate 4 / gate 2.
+ *   colour      of the incoming update: the registered colour image's pixel (ui, vi) by the decode's colour rule; with
+ *               VGX_IMAGE_COLOR_NONE opaque white (255, 255, 255, 255).
+ *   blocks      a block is allocated iff at least one of its voxels changed in this frame.  New blocks take pool slots in
+ *               ascending candidate order behind the blocks the layer already held (n_new_blocks of them).
+ * Validation is vgx_depth_image_check's, word for word, plus NULL handle / pose / image as the decode refuses them, before
+ * anything is uploaded or launched; width * height == 0: VGX_OK, nothing done.  A pose that is not finite: VGX_ERR_INVALID;
+ * width or height >= 2^24, both max_depth_m and max_ray_length_m unbounded, a box beyond +-2^30 blocks or of more than 2^24 blocks, or one the
+ * layer's block table cannot hold (2^28 cells): VGX_ERR_UNSUPPORTED, as the other integrators refuse such a reach.
+ * Streams and cost: the TSDF stream under the TSDF lock, one frame at a time per integrator; the host form uploads the
+ * depth image and then the colour image through the integrator's two pinned staging buffers filled in turn.  Room for every
+ * candidate block is reserved first: that reads the layer's exact block count behind everything queued -- the frame's ONE
+ * host synchronisation, before the upload.  Then ONE kernel whatever the size.  counts == NULL: the call returns with the
+ * frame QUEUED; with counts one read-back (56 bytes) more, and the call waits for the frame. */
+typedef struct vgx_projective_counts { /* of the last frame */
+  int64_t n_candidate_blocks, n_new_blocks, n_updates, n_carved, n_cleared;
+} vgx_projective_counts;
+/* depth, color: the images' bytes in host memory (read before the call returns); color is not read for VGX_IMAGE_COLOR_NONE */
+VGX_API int vgx_tsdf_integrate_depth_image(vgx_tsdf_integrator integrator, const float T_G_C[7],
+                                           const vgx_depth_image_layout* layout, const vgx_depth_camera* camera,
+                                           const void* depth, int64_t depth_n_bytes, const void* color, int64_t color_n_bytes,
+                                           vgx_projective_counts* counts /* NULL: queued, not waited for */);
+/* the same with both images already in DEVICE memory, ready with respect to the TSDF stream; they are read until the frame
+ * has run */
+VGX_API int vgx_tsdf_integrate_depth_image_device(vgx_tsdf_integrator integrator, const float T_G_C[7],
+                                                  const vgx_depth_image_layout* layout, const vgx_depth_camera* camera,
+                                                  const void* d_depth, int64_t depth_n_bytes, const void* d_color,
+                                                  int64_t color_n_bytes, vgx_projective_counts* counts);
+/* HOST ONLY (no device, no context): the candidate block box [lo, hi] of a frame (both ends included).  Refuses what
+ * vgx_depth_image_check refuses in the layout and the camera (byte counts aside) and the poses and reaches named above. */
+VGX_API int vgx_tsdf_projective_box(const vgx_depth_image_layout* layout, const vgx_depth_camera* camera,
+                                    const vgx_tsdf_config* cfg, const float T_G_C[7], float voxel_size, int32_t voxels_per_side,
+                                    int32_t lo[3], int32_t hi[3]);
+
 /* finishSubmap() hand-off without a host round trip: turns the active layer's blocks
  * into a (not yet finished) submap holding the raw TSDF layer and its TSDF sampling
  * grid; follow with vgx_submap_generate_esdf and vgx_submap_extract_voxel_points.  The

@@ -135,6 +135,12 @@ class DepthRowTime(C.Structure):
     _fields_ = [("scale", C.c_double), ("offset_s", C.c_double)]
 
 
+class ProjectiveCounts(C.Structure):
+    """vgx_projective_counts: of the last projectively integrated frame."""
+    _fields_ = [("n_candidate_blocks", C.c_int64), ("n_new_blocks", C.c_int64), ("n_updates", C.c_int64),
+                ("n_carved", C.c_int64), ("n_cleared", C.c_int64)]
+
+
 DEPTH_16UC1, DEPTH_32FC1 = 0, 1
 IMAGE_COLOR_NONE, IMAGE_COLOR_RGB8, IMAGE_COLOR_BGR8, IMAGE_COLOR_RGBA8, IMAGE_COLOR_BGRA8, IMAGE_COLOR_MONO8 = 0, 1, 2, 3, 4, 5
 DEPTH_BYTES_PER_PIXEL = {DEPTH_16UC1: 2, DEPTH_32FC1: 4}
@@ -403,6 +409,12 @@ SIGNATURES = {
                                                                  C.POINTER(ScanConfig), C.POINTER(DepthRowTime),
                                                                  C.POINTER(ScanTrackView), vp, C.c_int64, vp, C.c_int64]),
     "vgx_scan_depth_stats": (C.c_int, [vp, i64p, i64p, i64p, i64p]),
+    "vgx_tsdf_integrate_depth_image": (C.c_int, [vp, f32p, C.POINTER(DepthImageLayout), C.POINTER(DepthCamera), vp, C.c_int64,
+                                                 vp, C.c_int64, C.POINTER(ProjectiveCounts)]),
+    "vgx_tsdf_integrate_depth_image_device": (C.c_int, [vp, f32p, C.POINTER(DepthImageLayout), C.POINTER(DepthCamera), vp,
+                                                        C.c_int64, vp, C.c_int64, C.POINTER(ProjectiveCounts)]),
+    "vgx_tsdf_projective_box": (C.c_int, [C.POINTER(DepthImageLayout), C.POINTER(DepthCamera), C.POINTER(TsdfConfig), f32p,
+                                          C.c_float, C.c_int32, i32p, i32p]),
     "vgx_scan_download": (C.c_int, [vp, f32p, u8p]),
     "vgx_scan_device_pointers": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp)]),
     "vgx_tsdf_integrate_scan": (C.c_int, [vp, f32p, vp, C.c_int32, i64p]),
@@ -1988,6 +2000,16 @@ def depth_image_check(layout, camera, depth_n_bytes, color_n_bytes=0, row_time=N
                                                   None if view is None else C.byref(view), int(depth_n_bytes), int(color_n_bytes))
 
 
+def projective_box(layout, camera, config, T_G_C, voxel_size, vps):
+    """vgx_tsdf_projective_box (host only): (code, lo [3], hi [3]) -- the candidate block box of a projectively integrated
+    frame; layout / camera / config may be None (a NULL argument)"""
+    T = _f32(T_G_C)
+    lo, hi = np.zeros(3, np.int32), np.zeros(3, np.int32)
+    lay, cam, cfg = (None if o is None else C.byref(o) for o in (layout, camera, config))
+    rc = load().vgx_tsdf_projective_box(lay, cam, cfg, _ptr(T, f32p), float(voxel_size), int(vps), _ptr(lo, i32p), _ptr(hi, i32p))
+    return rc, lo, hi
+
+
 def _image_bytes(image):
     """(pointer or None, byte count) of an image's bytes: bytes, bytearray or a contiguous array; None: no image"""
     if image is None:
@@ -2648,6 +2670,27 @@ class FastTsdfIntegrator:
         self.ctx.check(self.ctx.lib.vgx_tsdf_integrate_scan(self.h, _ptr(T, f32p), scan.h, int(freespace_points),
                                                             C.byref(out) if count else None))
         return out.value
+
+    def integrate_depth_image(self, T_G_C, layout, camera, depth, color=None, count=True):
+        """Projective integration of a depth image and its registered colour image (host bytes; color None for
+        IMAGE_COLOR_NONE): vgx_tsdf_integrate_depth_image.  Returns the frame's counts as a dict; count=False: None, and
+        the call returns with the frame queued."""
+        T = _f32(T_G_C)
+        (dp, dn), (cp, cn) = _image_bytes(depth), _image_bytes(color)
+        out = ProjectiveCounts()
+        self.ctx.check(self.ctx.lib.vgx_tsdf_integrate_depth_image(self.h, _ptr(T, f32p), C.byref(layout), C.byref(camera), dp, dn,
+                                                                   cp, cn, C.byref(out) if count else None))
+        return {k: getattr(out, k) for k, _ in ProjectiveCounts._fields_} if count else None
+
+    def integrate_depth_image_device(self, T_G_C, layout, camera, d_depth, depth_n_bytes, d_color=None, color_n_bytes=0, count=True):
+        """the same with the images at device addresses (ready with respect to the TSDF stream)"""
+        T = _f32(T_G_C)
+        dp, cp = (vp(a) if a else None for a in (d_depth, d_color))
+        out = ProjectiveCounts()
+        self.ctx.check(self.ctx.lib.vgx_tsdf_integrate_depth_image_device(
+            self.h, _ptr(T, f32p), C.byref(layout), C.byref(camera), dp, int(depth_n_bytes), cp, int(color_n_bytes),
+            C.byref(out) if count else None))
+        return {k: getattr(out, k) for k, _ in ProjectiveCounts._fields_} if count else None
 
     def integrate_merged_scan(self, T_G_C, scan, freespace_points=False, count=True):
         """MergedTsdfIntegrator::integratePointCloud of a decoded Scan (vgx_tsdf_integrate_merged_scan)"""

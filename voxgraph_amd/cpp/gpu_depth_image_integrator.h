@@ -7,6 +7,7 @@
 //   CameraInfo::K[0], K[4], K[2], K[5]                    cameraOf (on top of camera(): depth unit, gate, strides)
 //   decode                                                -> vgx_scan_decode_depth_image[_undistorted]
 //   integrateDepthImage                                   decode, then vgx_tsdf_integrate_scan as GpuPointcloudIntegrator does
+//   integrateProjective                                   -> vgx_tsdf_integrate_depth_image: per-voxel projective update, no cloud
 // No ROS headers are needed: everything is templated on the message types and reads the members sensor_msgs::Image
 // (height, width, encoding, is_bigendian, step, data) and sensor_msgs::CameraInfo (K) have, so it compiles against the
 // real messages and against stand-ins alike.
@@ -128,6 +129,31 @@ class GpuDepthImageIntegrator {
     if (!layer) throw std::invalid_argument("integrateDepthImage: NULL layer");
     decodeUndistorted(depth, info, color, row_time, track);
     integrateScan(T_submap_camera_ref, layer);
+  }
+
+  // The frame integrated PROJECTIVELY (include/voxgraph_amd.h, "Projective depth-image integration"): every voxel in view
+  // looks up its pixel; no cloud is decoded, scan() and lastPointcloudSize() keep what they held.  The strides of camera()
+  // are not read, the scan config is not used (a frame without a colour image is integrated opaque white).  counts ==
+  // nullptr: returns with the frame queued (voxblox's void call); else the frame's counts, and the call waits for it.
+  template <class Transformation, class Image, class CameraInfo>
+  void integrateProjective(const Transformation& T_submap_camera, const Image& depth, const CameraInfo& info, const Image* color,
+                           GpuTsdfLayer* layer, vgx_projective_counts* counts = nullptr) {
+    if (!layer) throw std::invalid_argument("integrateProjective: NULL layer");
+    const vgx_depth_image_layout layout = layoutOf(depth, color);
+    const vgx_depth_camera cam = cameraOf(info);
+    const auto& q = T_submap_camera.getRotation();
+    const auto& t = T_submap_camera.getPosition();
+    const float T[7] = {(float)q.w(), (float)q.x(), (float)q.y(), (float)q.z(), (float)t[0], (float)t[1], (float)t[2]};
+    if (!tsdf_integrator_) tsdf_integrator_.reset(new GpuFastTsdfIntegrator(ctx_, tsdf_integrator_config_, layer));
+    tsdf_integrator_->setLayer(layer);
+    if (vgx_tsdf_integrate_depth_image(tsdf_integrator_->handle(), T, &layout, &cam, depth.data.data(), (int64_t)depth.data.size(),
+                                       color ? color->data.data() : nullptr, color ? (int64_t)color->data.size() : 0,
+                                       counts) != VGX_OK)
+      throw std::runtime_error(std::string("vgx_tsdf_integrate_depth_image: ") + vgx_last_error(ctx_));
+  }
+  template <class Transformation, class Image, class CameraInfo>
+  void integrateProjective(const Transformation& T_submap_camera, const Image& depth, const CameraInfo& info, GpuTsdfLayer* layer) {
+    integrateProjective(T_submap_camera, depth, info, static_cast<const Image*>(nullptr), layer);
   }
 
   // points of the last frame that were kept

@@ -596,6 +596,7 @@ int tsdf_read_stats(vgx_tsdf_layer L, int32_t* n_blocks, unsigned long long* dro
 }
 int64_t tsdf_last_scan_bound(vgx_tsdf_layer L) { return L->recent.empty() ? 0 : L->recent.back().second; }
 void tsdf_request_readback(vgx_tsdf_layer L) { request_readback(L); }
+void tsdf_note_allocations(vgx_tsdf_layer L, int64_t bound) { L->recent.emplace_back(++L->scan_seq, bound); }
 }  // namespace vgx
 
 extern "C" {

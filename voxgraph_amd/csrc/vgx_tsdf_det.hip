@@ -708,19 +708,6 @@ __device__ __forceinline__ UpdateTerm update_term(const vgx_tsdf_config& c, floa
   return u;
 }
 
-// the running average itself (the voxel mutex's critical section)
-__device__ __forceinline__ void apply_term(const vgx_tsdf_config& c, float sdf, float uw, uint32_t color, float& d, float& w,
-                                           uint32_t& col, bool& dirty) {
-  const float trunc = c.default_truncation_distance;
-  const float new_weight = w + uw;
-  if (new_weight < 1e-6f) return;  // kFloatEpsilon
-  const float new_sdf = (sdf * uw + d * w) / new_weight;
-  if (fabsf(sdf) < trunc) col = blended_color(col, color, w, uw);
-  d = (new_sdf > 0.0f) ? fminf(trunc, new_sdf) : fmaxf(-trunc, new_sdf);
-  w = fminf(c.max_weight, new_weight);
-  dirty = true;
-}
-
 template <bool ALLOCATE>
 __device__ __forceinline__ int block_slot(const TsdfLayerDev& L, int bx, int by, int bz) {
   if (ALLOCATE) return get_or_allocate_block(L, bx, by, bz);

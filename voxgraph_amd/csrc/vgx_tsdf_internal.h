@@ -114,6 +114,20 @@ __device__ __forceinline__ uint32_t blended_color(uint32_t oc, uint32_t color, f
   return nc;
 }
 
+// updateTsdfVoxel's running average itself (the voxel mutex's critical section): the reproducible mode's commit
+// (vgx_tsdf_det.hip) and the projective integrator (vgx_projective.hip)
+__device__ __forceinline__ void apply_term(const vgx_tsdf_config& c, float sdf, float uw, uint32_t color, float& d, float& w,
+                                           uint32_t& col, bool& dirty) {
+  const float trunc = c.default_truncation_distance;
+  const float new_weight = w + uw;
+  if (new_weight < 1e-6f) return;  // kFloatEpsilon
+  const float new_sdf = (sdf * uw + d * w) / new_weight;
+  if (fabsf(sdf) < trunc) col = blended_color(col, color, w, uw);
+  d = (new_sdf > 0.0f) ? fminf(trunc, new_sdf) : fmaxf(-trunc, new_sdf);
+  w = fminf(c.max_weight, new_weight);
+  dirty = true;
+}
+
 // RayCaster [recalled, voxblox integrator_utils.h] set up from sensor origin t and end point g (both
 // layer frame): ray_start / ray_end as the constructor computes them, then setupRayCaster on the
 // scaled ends -- from the far end towards the origin (cast_from_origin = false, the fast
@@ -448,6 +462,11 @@ struct vgx_tsdf_integrator_s {
   vgx::DeviceBuffer d_osort;
   size_t osort_bytes = 0;
   long long order_cap = 0;      // points
+  // projective depth-image integration (vgx_projective.hip): the host form's upload (the depth image, then its colour
+  // image at the next 16 bytes), the control words {ticket, error, the frame's counters} and the TileChain's word per
+  // candidate block, tagged with the launch's epoch
+  vgx::DeviceBuffer d_image, d_proj_ctl, d_proj_state;
+  uint32_t proj_epoch = 0, proj_tickets = 0;
 };
 
 namespace vgx {
@@ -459,6 +478,8 @@ int tsdf_reserve_blocks(vgx_tsdf_layer L, const int32_t lo[3], const int32_t hi[
 // exact block count and dropped updates (waits for the stream; the caller holds tsdf_mu)
 int tsdf_read_stats(vgx_tsdf_layer L, int32_t* n_blocks, unsigned long long* dropped);
 void tsdf_request_readback(vgx_tsdf_layer L);
+// a kernel that may allocate up to `bound` blocks has been queued (what the host's estimate of the count must allow for)
+void tsdf_note_allocations(vgx_tsdf_layer L, int64_t bound);
 // vgx_tsdf_coop.hip: the racing scan (one workgroup per 256 points: start set, cooperative walk, per-voxel folds);
 // stats: gather vgx_tsdf_integrator_walk_stats' numbers (a counted scan: I.wg_stats must hold a row per workgroup)
 // cloud_width: points per row of an organised cloud (0: unorganised) -- only which workgroup takes which point
