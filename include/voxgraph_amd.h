@@ -1102,6 +1102,140 @@ VGX_API int vgx_tsdf_projective_box(const vgx_depth_image_layout* layout, const 
                                     const vgx_tsdf_config* cfg, const float T_G_C[7], float voxel_size, int32_t voxels_per_side,
                                     int32_t lo[3], int32_t hi[3]);
 
+/* ---- LiDAR range images: a scan's points gathered into a spherical image, and its projective integration ---- */
+/* The projective integrator above for a spinning LiDAR (voxblox's ProjectiveTsdfIntegrator is a LiDAR range-image integrator
+ * [recalled]; not vendored: the rules are DEFINED here, what the kernels -- vgx_range_image.hip -- and
+ * tests/range_image_ref.py both follow; f32 with one rounding per operation, no contraction, unless it says f64).  A scan
+ * arrives as points, so the image is built first (vgx_range_image_build: two launches), then every voxel near a return looks
+ * up ONE cell and updates itself (vgx_tsdf_integrate_range_image: one launch).  No atomic touches a voxel, nothing is sorted:
+ * the same scans give the same layer, block order included, bit for bit on every run.
+ *   angle rule  vgx_atan2_rule(y, x) below: NO library transcendental is part of a rule (atan2f of the device and of numpy do
+ *               not agree bit for bit).  ax = |x|, ay = |y|, mx = fmaxf(ax, ay), mn = fminf(ax, ay); 0 unless mx > 0 [so
+ *               (0, 0) gives 0]; q = mn / mx (one correctly rounded division, q in [0, 1]); s = q * q;
+ *               p = C5; p = p * s + C4; ... ; p = p * s + C0 (Horner, a multiplication then an addition, each rounded);
+ *               a = p * q; if ay > ax: a = PI_2 - a; if x < 0: a = PI - a; if y < 0: a = -a.  The coefficients (a fit of
+ *               atan(q) / q in s over [0, 1]) and PI_2, PI are the hex floats below.  Its largest error against f64 atan2
+ *               is at most VGX_ATAN2_RULE_MAX_ERROR (measured 1.92e-6 rad over 4e6 directions, seams and axes included:
+ *               tests/test_range_image_cpu.py; the bar is 1 / 64 of the finest pitch accepted, 2 pi / 4096 / 64 = 2.4e-5).
+ *               Inputs are finite; the results lie in [-PI, PI].
+ *   model       vgx_lidar_model: width azimuth columns, height beam rows; azimuth_first_rad is the azimuth (atan2(y, x) in
+ *               the sensor frame) of column 0's centre; columns advance towards growing azimuth, or -- azimuth_clockwise,
+ *               as Ouster and Velodyne spin -- towards falling azimuth; elevation_first_rad / elevation_last_rad are the
+ *               elevations (atan2(z, hypot(x, y))) of the centres of rows 0 and height - 1, the rows uniform between them
+ *               (either may be the upper one).  Host constants, each rounded ONCE to f32 from f64:
+ *               su = (azimuth_clockwise ? -1 : 1) * (double)width / 6.283185307179586,
+ *               sv = (double)(height - 1) / ((double)elevation_last_rad - (double)elevation_first_rad).
+ *               vgx_range_image_check refuses -- VGX_ERR_INVALID: NULL, an angle that is not finite, azimuth_first_rad
+ *               outside [-PI, PI], the f32 constants (the column wrap below is ONE step), elevation_first_rad == elevation_last_rad with
+ *               height > 1, an elevation outside (-pi/2, pi/2), width or height < 1; VGX_ERR_UNSUPPORTED: width > 4096,
+ *               height > 256, width < 4, and height == 1 (a single beam has no pitch to take a row's extent from; no
+ *               vertical aperture field is defined: refused).  A beam table for non-uniform rows is not supported.
+ *   pixel       of a sensor-frame direction (x, y, z) with r = sqrtf(x x + y y + z z) (summed left to right), r > 0 and
+ *               finite: rho = sqrtf(x x + y y), az = rule(y, x), el = rule(z, rho);
+ *               uf = (az - azimuth_first_rad) * su, ua = uf + 0.5f, wrapped ONCE: if ua < 0: ua += (float)width, else if
+ *               ua >= (float)width: ua -= (float)width; ui = floorf(ua) clamped to [0, width - 1] (the wrapped sum can
+ *               round to width itself);  vf = (el - elevation_first_rad) * sv, va = vf + 0.5f; the row is accepted iff
+ *               0 <= va < (float)height, vi = floorf(va).  Nearest pixel only.  A direction on the z axis has rho = 0,
+ *               az = 0 and el = +-PI_2: outside every accepted model's rows unless a row reaches that far.
+ *   image       vgx_range_image_build, from the points of a vgx_scan (any decode kind) or of a device array, indices in
+ *               their order.  Point i is REJECTED BY RANGE unless r > 0 and r < +inf, else REJECTED BY ROW unless its row
+ *               is accepted, else KEPT.  A cell holds the kept point of its pixel with the smallest r, of bit-equal r the
+ *               smallest index [key = (u64)bits(r) << 32 | i under atomicMin: a positive float's bits order as the float
+ *               does], whatever order the lanes run in: {range = r, rgba = the point's colour -- opaque white where the
+ *               build is given no colours --, point_index = i}; an empty cell is {0, 0, -1}.  n_filled counts the cells
+ *               that are not empty, n_collided = n_kept - n_filled.  Of the WINNING points the image keeps, in the sensor
+ *               frame, max_range and per axis the smallest and largest coordinate (point_min / point_max) and the smallest
+ *               and largest component of the unit direction (x / r, y / r, z / r: dir_min / dir_max): min / max and
+ *               integer reductions, the order cannot show.  With no cell filled: max_range 0, the mins +inf, the maxs -inf.
+ *               [The box of the returns "pulled in to max_ray_length_m and pushed out by the truncation" needs a
+ *               vgx_tsdf_config; the build does not take one -- an image serves integrators of any configuration -- and
+ *               keeps these raw extremes; vgx_tsdf_range_image_box finishes the box on the host.]
+ *               The image owns what it needs: the scan handle may be decoded into again at once.  Two launches (scatter:
+ *               one lane per point; resolve: one lane per cell) behind one memset, on the TSDF stream under the TSDF lock.
+ *               counts != NULL: one read-back (the build's one host synchronisation); NULL: the build returns QUEUED and
+ *               vgx_range_image_stats / _download / vgx_tsdf_integrate_range_image perform the read when they need it.
+ *               n > 2^31 - 1 points: VGX_ERR_UNSUPPORTED.  n == 0: an image of empty cells.
+ *   integrate   vgx_tsdf_integrate_range_image(integrator, T_G_S, image, counts).  Config fields READ and NOT read: as the
+ *               depth-image integrator lists them above.  Per voxel: centre and the move into the sensor frame exactly as
+ *               there (voxel, camera); r_v = sqrtf(x x + y y + z z), no update unless r_v > 0; the pixel by the rule
+ *               above, no update outside the rows or where the cell is empty; r_s = the cell's range, sdf = r_s - r_v (the
+ *               true distance along the ray).  gates, in this order: 1. r_s < min_ray_length_m: no update.  2. r_s >
+ *               max_ray_length_m: an update only if allow_clear && voxel_carving_enabled && r_v + trunc <=
+ *               max_ray_length_m, with sdf = max_ray_length_m - r_v, counted in n_cleared; the gates below are not asked.
+ *               3. sdf < -trunc: no update.  4. sdf > trunc: an update only if voxel_carving_enabled, counted in n_carved.
+ *               weight w = use_const_weight ? 1 : 1.0f / (r_s * r_s); if use_weight_dropoff && sdf < -voxel_size:
+ *               w = fmaxf((w * (trunc + sdf)) / (trunc - voxel_size), 0).  No sparsity factor.  The colour is the cell's.
+ *               update, blocks, counts (vgx_projective_counts): word for word as above.
+ *   candidates  vgx_tsdf_range_image_box, on the host in f64: reach = min(max_ray_length_m, max_range) + trunc; refused
+ *               (VGX_ERR_UNSUPPORTED) unless finite [an image with no cell filled: the box of the sensor origin alone].
+ *               Per axis a of the sensor frame, over the winning points: a point pulled in to max_ray_length_m and pushed
+ *               out by trunc along its own ray is u_a (min(r, max_ray) + trunc) with u its unit direction, and
+ *               u_a min(r, max_ray) lies between 0 and both p_a and u_a max_ray: so
+ *               hi_a = max(0, min(point_max_a, dir_max_a * max_ray)) + trunc * max(0, dir_max_a),
+ *               lo_a = min(0, max(point_min_a, dir_min_a * max_ray)) + trunc * min(0, dir_min_a)  (the sensor origin is
+ *               inside; an infinite max_ray_length_m pulls nothing in: point_max_a / point_min_a alone).  That box's eight corners are moved by T_G_S (as the library's transforms: uv = qv x P, uv += uv,
+ *               cc = qv x uv, (P + qw uv + cc) + t); their axis-aligned box is widened on every side by
+ *               reach * (pitch_az + pitch_el + 4 VGX_ATAN2_RULE_MAX_ERROR), pitch_az = 2 pi / width, pitch_el =
+ *               |elevation_last_rad - elevation_first_rad| / (height - 1): a voxel's direction and its pixel's return each
+ *               lie within half a pitch (and the rule's error) of the pixel centre in both angles, so the voxel is at most
+ *               that angle off the return's ray, and at most reach times it away from the ray's point at its own range,
+ *               which the unwidened box holds (r_v <= min(r_s, max_ray) + trunc by gates 2 to 4).  Then
+ *               lo = floor(min / bs) - 1, hi = floor(max / bs) + 1 per axis, candidates in ascending (z, y, x), as above.
+ *               The same caps: a pose that is not finite VGX_ERR_INVALID; beyond +-2^30 blocks, more than 2^24 candidates
+ *               or a box the layer's block table cannot hold: VGX_ERR_UNSUPPORTED.
+ *               [The kernel rejects whole blocks early: bounding sphere wholly beyond reach, or wholly above the upper
+ *               row's cone or below the lower row's, the cones widened by half a pitch and the rule's error; a block that
+ *               contains the sensor is never rejected.  That changes no value and no count.]
+ * Streams and cost of the integration: as the depth-image integrator, without an upload -- the image is resident.  The
+ * image is read until the frame has run; a build into the same handle is ordered behind it (one stream). */
+#define VGX_ATAN2_RULE_MAX_ERROR 2.5e-6f
+#define VGX_ATAN2_C0 0x1.fffd04p-1f
+#define VGX_ATAN2_C1 -0x1.549b12p-2f
+#define VGX_ATAN2_C2 0x1.8c5ed6p-3f
+#define VGX_ATAN2_C3 -0x1.dce1aep-4f
+#define VGX_ATAN2_C4 0x1.af48bap-5f
+#define VGX_ATAN2_C5 -0x1.8001f8p-7f
+#define VGX_ATAN2_PI_2 0x1.921fb6p+0f
+#define VGX_ATAN2_PI 0x1.921fb6p+1f
+typedef struct vgx_lidar_model {
+  int32_t width, height;
+  float azimuth_first_rad;
+  int32_t azimuth_clockwise;
+  float elevation_first_rad, elevation_last_rad;
+} vgx_lidar_model;
+typedef struct vgx_range_image_counts { /* of the image the handle holds */
+  int64_t n_points, n_kept, n_filled, n_collided, n_rejected_range, n_rejected_rows;
+  float max_range;
+  float point_min[3], point_max[3], dir_min[3], dir_max[3];
+  int32_t pad_;
+} vgx_range_image_counts;
+typedef struct vgx_range_image_s* vgx_range_image;
+/* HOST ONLY: the rule itself, as the kernels evaluate it (built without contraction) */
+VGX_API float vgx_atan2_rule(float y, float x);
+/* HOST ONLY: VGX_OK, or why a model is refused */
+VGX_API int vgx_range_image_check(const vgx_lidar_model* model);
+/* HOST ONLY: the pixel rule; VGX_OK with *u, *v (v = -1: outside the rows), VGX_ERR_INVALID for NULL, a refused model or a
+ * direction whose r is not positive and finite */
+VGX_API int vgx_range_image_pixel(const vgx_lidar_model* model, float x, float y, float z, int32_t* u, int32_t* v);
+VGX_API int vgx_range_image_create(vgx_ctx ctx, vgx_range_image* out);
+VGX_API int vgx_range_image_destroy(vgx_range_image image);
+VGX_API int vgx_range_image_build(vgx_range_image image, const vgx_lidar_model* model, vgx_scan scan,
+                                  vgx_range_image_counts* counts /* NULL: queued, not waited for */);
+/* the same from device arrays (f32 [n][3], u32 [n] bytes r g b a or NULL), ready with respect to the TSDF stream and read
+ * until the build has run */
+VGX_API int vgx_range_image_build_device(vgx_range_image image, const vgx_lidar_model* model, const void* d_points,
+                                         const void* d_rgba, int64_t n, vgx_range_image_counts* counts);
+/* the counts of the image held (waits for a queued build); the model it was built for in *model if not NULL */
+VGX_API int vgx_range_image_stats(vgx_range_image image, vgx_range_image_counts* counts, vgx_lidar_model* model);
+/* range [height][width] f32, rgba [height][width][4] bytes, point_index [height][width] i32; any may be NULL */
+VGX_API int vgx_range_image_download(vgx_range_image image, float* range, uint8_t* rgba, int32_t* point_index);
+VGX_API int vgx_tsdf_integrate_range_image(vgx_tsdf_integrator integrator, const float T_G_S[7], vgx_range_image image,
+                                           vgx_projective_counts* counts /* NULL: queued, not waited for */);
+/* HOST ONLY: the candidate block box [lo, hi] (both ends included) of an image with these counts */
+VGX_API int vgx_tsdf_range_image_box(const vgx_lidar_model* model, const vgx_range_image_counts* image_counts,
+                                     const vgx_tsdf_config* cfg, const float T_G_S[7], float voxel_size,
+                                     int32_t voxels_per_side, int32_t lo[3], int32_t hi[3]);
+
 /* finishSubmap() hand-off without a host round trip: turns the active layer's blocks
  * into a (not yet finished) submap holding the raw TSDF layer and its TSDF sampling
  * grid; follow with vgx_submap_generate_esdf and vgx_submap_extract_voxel_points.  The

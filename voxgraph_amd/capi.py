@@ -141,6 +141,20 @@ class ProjectiveCounts(C.Structure):
                 ("n_carved", C.c_int64), ("n_cleared", C.c_int64)]
 
 
+class LidarModel(C.Structure):
+    """vgx_lidar_model: a spinning LiDAR's spherical image -- azimuth columns, uniform beam rows."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("azimuth_first_rad", C.c_float), ("azimuth_clockwise", C.c_int32),
+                ("elevation_first_rad", C.c_float), ("elevation_last_rad", C.c_float)]
+
+
+class RangeImageCounts(C.Structure):
+    """vgx_range_image_counts: of the range image a handle holds."""
+    _fields_ = [("n_points", C.c_int64), ("n_kept", C.c_int64), ("n_filled", C.c_int64), ("n_collided", C.c_int64),
+                ("n_rejected_range", C.c_int64), ("n_rejected_rows", C.c_int64), ("max_range", C.c_float),
+                ("point_min", C.c_float * 3), ("point_max", C.c_float * 3), ("dir_min", C.c_float * 3), ("dir_max", C.c_float * 3),
+                ("pad_", C.c_int32)]
+
+
 DEPTH_16UC1, DEPTH_32FC1 = 0, 1
 IMAGE_COLOR_NONE, IMAGE_COLOR_RGB8, IMAGE_COLOR_BGR8, IMAGE_COLOR_RGBA8, IMAGE_COLOR_BGRA8, IMAGE_COLOR_MONO8 = 0, 1, 2, 3, 4, 5
 DEPTH_BYTES_PER_PIXEL = {DEPTH_16UC1: 2, DEPTH_32FC1: 4}
@@ -415,6 +429,18 @@ SIGNATURES = {
                                                         C.c_int64, vp, C.c_int64, C.POINTER(ProjectiveCounts)]),
     "vgx_tsdf_projective_box": (C.c_int, [C.POINTER(DepthImageLayout), C.POINTER(DepthCamera), C.POINTER(TsdfConfig), f32p,
                                           C.c_float, C.c_int32, i32p, i32p]),
+    "vgx_atan2_rule": (C.c_float, [C.c_float, C.c_float]),
+    "vgx_range_image_check": (C.c_int, [C.POINTER(LidarModel)]),
+    "vgx_range_image_pixel": (C.c_int, [C.POINTER(LidarModel), C.c_float, C.c_float, C.c_float, i32p, i32p]),
+    "vgx_range_image_create": (C.c_int, [vp, C.POINTER(vp)]),
+    "vgx_range_image_destroy": (C.c_int, [vp]),
+    "vgx_range_image_build": (C.c_int, [vp, C.POINTER(LidarModel), vp, C.POINTER(RangeImageCounts)]),
+    "vgx_range_image_build_device": (C.c_int, [vp, C.POINTER(LidarModel), vp, vp, C.c_int64, C.POINTER(RangeImageCounts)]),
+    "vgx_range_image_stats": (C.c_int, [vp, C.POINTER(RangeImageCounts), C.POINTER(LidarModel)]),
+    "vgx_range_image_download": (C.c_int, [vp, f32p, u8p, i32p]),
+    "vgx_tsdf_integrate_range_image": (C.c_int, [vp, f32p, vp, C.POINTER(ProjectiveCounts)]),
+    "vgx_tsdf_range_image_box": (C.c_int, [C.POINTER(LidarModel), C.POINTER(RangeImageCounts), C.POINTER(TsdfConfig), f32p,
+                                           C.c_float, C.c_int32, i32p, i32p]),
     "vgx_scan_download": (C.c_int, [vp, f32p, u8p]),
     "vgx_scan_device_pointers": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp)]),
     "vgx_tsdf_integrate_scan": (C.c_int, [vp, f32p, vp, C.c_int32, i64p]),
@@ -2010,6 +2036,116 @@ def projective_box(layout, camera, config, T_G_C, voxel_size, vps):
     return rc, lo, hi
 
 
+def lidar_model(**kw):
+    """A vgx_lidar_model from keywords (fields not given are 0)."""
+    m = LidarModel()
+    for k, v in kw.items():
+        if not hasattr(m, k):
+            raise AttributeError(k)
+        setattr(m, k, v)
+    return m
+
+
+def range_image_check(model):
+    """vgx_range_image_check (host only): OK, or the code the model is refused with; None: a NULL argument"""
+    return load().vgx_range_image_check(None if model is None else C.byref(model))
+
+
+def atan2_rule(y, x):
+    """vgx_atan2_rule (host only) of f32 arrays, element by element"""
+    fn = load().vgx_atan2_rule
+    y, x = np.broadcast_arrays(np.asarray(y, np.float32), np.asarray(x, np.float32))
+    return np.array([fn(float(a), float(b)) for a, b in zip(y.ravel(), x.ravel())], np.float32).reshape(y.shape)
+
+
+def range_image_pixel(model, x, y, z):
+    """vgx_range_image_pixel (host only): (code, u, v); v = -1 outside the rows"""
+    u, v = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    rc = load().vgx_range_image_pixel(None if model is None else C.byref(model), float(x), float(y), float(z), _ptr(u, i32p), _ptr(v, i32p))
+    return rc, int(u[0]), int(v[0])
+
+
+def _counts_dict(c):
+    out = {}
+    for k, t in type(c)._fields_:
+        if k != "pad_":
+            v = getattr(c, k)
+            out[k] = np.array(v[:], np.float32) if hasattr(v, "__len__") else v
+    return out
+
+
+def range_image_counts(**kw):
+    """A vgx_range_image_counts from keywords (as RangeImage.stats() returns them)"""
+    c = RangeImageCounts()
+    for k, v in kw.items():
+        if hasattr(getattr(c, k), "__len__"):
+            v = (C.c_float * 3)(*[float(x) for x in v])
+        setattr(c, k, v)
+    return c
+
+
+def range_image_box(model, image_counts, config, T_G_S, voxel_size, vps):
+    """vgx_tsdf_range_image_box (host only): (code, lo [3], hi [3]); image_counts a dict (RangeImage.stats()) or a
+    RangeImageCounts; model / image_counts / config may be None (a NULL argument)"""
+    T = _f32(T_G_S)
+    lo, hi = np.zeros(3, np.int32), np.zeros(3, np.int32)
+    if isinstance(image_counts, dict):
+        image_counts = range_image_counts(**image_counts)
+    m, ic, cfg = (None if o is None else C.byref(o) for o in (model, image_counts, config))
+    rc = load().vgx_tsdf_range_image_box(m, ic, cfg, _ptr(T, f32p), float(voxel_size), int(vps), _ptr(lo, i32p), _ptr(hi, i32p))
+    return rc, lo, hi
+
+
+class RangeImage:
+    """A LiDAR scan gathered into a spherical range image on the GPU (vgx_range_image): per pixel the nearest return, its
+    colour and its point index; reused from scan to scan.  FastTsdfIntegrator.integrate_range_image consumes it."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        h = vp()
+        ctx.check(ctx.lib.vgx_range_image_create(ctx.h, C.byref(h)))
+        self.h = h
+
+    def build(self, model, scan, count=True):
+        """from a decoded Scan; returns the counts as a dict, count=False: None and the build is queued"""
+        out = RangeImageCounts()
+        self.ctx.check(self.ctx.lib.vgx_range_image_build(self.h, C.byref(model), scan.h, C.byref(out) if count else None))
+        return _counts_dict(out) if count else None
+
+    def build_device(self, model, d_points, d_rgba, n, count=True):
+        """from device arrays (f32 [n][3], u32 [n] or None) ready with respect to the TSDF stream"""
+        out = RangeImageCounts()
+        self.ctx.check(self.ctx.lib.vgx_range_image_build_device(self.h, C.byref(model), vp(d_points) if d_points else None,
+                                                                 vp(d_rgba) if d_rgba else None, int(n),
+                                                                 C.byref(out) if count else None))
+        return _counts_dict(out) if count else None
+
+    def stats(self):
+        """the counts of the image held, as a dict (waits for a queued build)"""
+        out = RangeImageCounts()
+        self.ctx.check(self.ctx.lib.vgx_range_image_stats(self.h, C.byref(out), None))
+        return _counts_dict(out)
+
+    def model(self):
+        m = LidarModel()
+        self.ctx.check(self.ctx.lib.vgx_range_image_stats(self.h, None, C.byref(m)))
+        return m
+
+    def download(self):
+        """(range [h][w] f32, rgba [h][w][4] u8, point_index [h][w] i32)"""
+        m = self.model()
+        rng = np.zeros((m.height, m.width), np.float32)
+        rgba = np.zeros((m.height, m.width, 4), np.uint8)
+        idx = np.zeros((m.height, m.width), np.int32)
+        self.ctx.check(self.ctx.lib.vgx_range_image_download(self.h, _ptr(rng, f32p), _ptr(rgba, u8p), _ptr(idx, i32p)))
+        return rng, rgba, idx
+
+    def destroy(self):
+        if self.h:
+            self.ctx.lib.vgx_range_image_destroy(self.h)
+            self.h = None
+
+
 def _image_bytes(image):
     """(pointer or None, byte count) of an image's bytes: bytes, bytearray or a contiguous array; None: no image"""
     if image is None:
@@ -2690,6 +2826,14 @@ class FastTsdfIntegrator:
         self.ctx.check(self.ctx.lib.vgx_tsdf_integrate_depth_image_device(
             self.h, _ptr(T, f32p), C.byref(layout), C.byref(camera), dp, int(depth_n_bytes), cp, int(color_n_bytes),
             C.byref(out) if count else None))
+        return {k: getattr(out, k) for k, _ in ProjectiveCounts._fields_} if count else None
+
+    def integrate_range_image(self, T_G_S, image, count=True):
+        """Projective integration of a RangeImage (vgx_tsdf_integrate_range_image).  Returns the frame's counts as a dict;
+        count=False: None, and the call returns with the frame queued."""
+        T = _f32(T_G_S)
+        out = ProjectiveCounts()
+        self.ctx.check(self.ctx.lib.vgx_tsdf_integrate_range_image(self.h, _ptr(T, f32p), image.h, C.byref(out) if count else None))
         return {k: getattr(out, k) for k, _ in ProjectiveCounts._fields_} if count else None
 
     def integrate_merged_scan(self, T_G_C, scan, freespace_points=False, count=True):

@@ -126,6 +126,7 @@ class GpuPointcloudIntegrator {
   }
   ~GpuPointcloudIntegrator() {
     tsdf_integrator_.reset();
+    if (range_image_) vgx_range_image_destroy(range_image_);
     vgx_scan_destroy(scan_);
   }
   GpuPointcloudIntegrator(const GpuPointcloudIntegrator&) = delete;
@@ -229,6 +230,35 @@ class GpuPointcloudIntegrator {
     integrate7(msg, T, layer, &track);
   }
 
+  // The projective route for a spinning LiDAR (include/voxgraph_amd.h, "LiDAR range images"): the message decoded as
+  // above, its points gathered into the range image of `model` (the nearest return per pixel), and every voxel near a
+  // return updated from the ONE pixel it projects into -- no rays, the same layer bit for bit on every run.  Returns with
+  // the frame queued unless `counts` is given.  The integrator's configuration and layer are integratePointcloud's.
+  template <class Msg, class Transformation>
+  void integrateProjective(const Transformation& T_submap_sensor, const Msg& msg, const vgx_lidar_model& model, GpuTsdfLayer* layer,
+                           vgx_projective_counts* counts = nullptr) {
+    const auto& q = T_submap_sensor.getRotation();
+    const auto& t = T_submap_sensor.getPosition();
+    const float T[7] = {(float)q.w(), (float)q.x(), (float)q.y(), (float)q.z(), (float)t[0], (float)t[1], (float)t[2]};
+    if (!layer) throw std::invalid_argument("integrateProjective: NULL layer");
+    if (vgx_range_image_check(&model) != VGX_OK) throw std::invalid_argument("integrateProjective: the LiDAR model is refused");
+    const vgx_scan_layout layout = layoutOf(msg);
+    if (vgx_scan_decode_msg(scan_, &layout, &scan_config_, msg.data.data(), (int64_t)msg.data.size()) != VGX_OK)
+      throw std::runtime_error(std::string("vgx_scan_decode_msg: ") + vgx_last_error(ctx_));
+    int64_t dropped = 0;
+    vgx_scan_stats(scan_, &last_points_, &dropped);
+    if (!range_image_ && vgx_range_image_create(ctx_, &range_image_) != VGX_OK)
+      throw std::runtime_error(std::string("vgx_range_image_create: ") + vgx_last_error(ctx_));
+    if (vgx_range_image_build(range_image_, &model, scan_, nullptr) != VGX_OK)
+      throw std::runtime_error(std::string("vgx_range_image_build: ") + vgx_last_error(ctx_));
+    if (!tsdf_integrator_) tsdf_integrator_.reset(new GpuFastTsdfIntegrator(ctx_, tsdf_integrator_config_, layer));
+    tsdf_integrator_->setLayer(layer);
+    if (vgx_tsdf_integrate_range_image(tsdf_integrator_->handle(), T, range_image_, counts) != VGX_OK)
+      throw std::runtime_error(std::string("vgx_tsdf_integrate_range_image: ") + vgx_last_error(ctx_));
+  }
+  // the range image of the last integrateProjective (NULL before the first)
+  vgx_range_image rangeImage() const { return range_image_; }
+
   // points of the last message that were integrated ("Integrating a pointcloud with %lu points", :80-81)
   int64_t lastPointcloudSize() const { return last_points_; }
   // the width the integrator was given for the last message: the message's, or 0 (unorganised) when points were dropped
@@ -264,6 +294,7 @@ class GpuPointcloudIntegrator {
   GpuFastTsdfIntegrator::Config tsdf_integrator_config_;
   vgx_scan_config scan_config_;
   vgx_scan scan_ = nullptr;
+  vgx_range_image range_image_ = nullptr;
   std::unique_ptr<GpuFastTsdfIntegrator> tsdf_integrator_;
   int64_t last_points_ = 0;
   int32_t last_cloud_width_ = 0;

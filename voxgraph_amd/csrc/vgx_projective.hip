@@ -3,7 +3,8 @@
 // A gather: a lane owns its voxels, so no atomic touches a voxel, nothing is sorted and no approximate set is asked --
 // the layer is the same bit for bit on every run by construction.
 //
-// ONE kernel per frame.  The host computes the candidate block box (vgx_tsdf_projective_box, f64) and makes room for it
+// ONE kernel per frame: the block walk of vgx_projective_kernel.h (shared with the LiDAR range-image integrator,
+// vgx_range_image.hip) instantiated for the pinhole frame below.  The host computes the candidate block box (vgx_tsdf_projective_box, f64) and makes room for it
 // (tsdf_reserve_blocks: its read of the exact block count is the frame's one host synchronisation); a workgroup of 512
 // lanes takes the candidate block of its ticket (TileChain, vgx_tsdf_internal.h: tickets are given in the order the
 // workgroups start, candidate = ticket, ascending (z, y, x)), every lane walks vps^3 / 512 voxels (1 or 8), one lane per
@@ -24,228 +25,88 @@
 #include <cstring>
 #include <string>
 
-#include "vgx_internal.h"
-#include "vgx_tsdf_internal.h"
+#include "vgx_projective_kernel.h"
 #include "vgx_depth_image.h"
 
 #pragma clang fp contract(off)
 
 namespace vgx {
 
-// u64 words of vgx_tsdf_integrator_s::d_proj_ctl
-enum { kProjTicket = 0, kProjError = 1, kProjNew = 2, kProjUpdates = 3, kProjCarved = 4, kProjCleared = 5, kProjDropped = 6,
-       kProjCtlWords = 8 };
-constexpr int kProjThreads = 512;             // lanes of a workgroup: one block of 8^3 voxels, an eighth of one of 16^3
 constexpr size_t kProjStageBytes = 1u << 20;  // one pinned staging piece of the host form
 
-struct ProjFrame {
+struct ProjFrame : ProjFrameBase {
   DepthImage img;  // depth, color, row_step, color_row_step, color_kind, unit, min_z, max_z
   uint32_t width, height;
   float fx, fy, cx, cy;  // (float) of the camera's
-  float qw, qx, qy, qz, tx, ty, tz;  // T_G_C
-  int32_t lo[3], nx, ny;  // the candidate box: its first block and its extent along x and y
-  uint32_t tiles;         // candidates
-  int32_t base_blocks;    // blocks the layer holds before the frame
   float z_far;            // no voxel beyond it can be updated (early reject only)
   int32_t reject;         // side planes usable (fx, fy > 0)
 };
 
-// the inverse of T_G_C applied to a layer-frame point: subtract the translation, then rotate by the conjugate quaternion
-// in transform_point's operation order (uv = qv x p, uv += uv, cc = qv x uv, p + qw uv + cc with qv = -(qx, qy, qz))
-__device__ __forceinline__ void to_camera(const ProjFrame& f, float gx, float gy, float gz, float& x, float& y, float& z) {
-  const float px = gx - f.tx, py = gy - f.ty, pz = gz - f.tz;
-  const float qx = -f.qx, qy = -f.qy, qz = -f.qz;
-  float uvx = qy * pz - qz * py, uvy = qz * px - qx * pz, uvz = qx * py - qy * px;
-  uvx += uvx; uvy += uvy; uvz += uvz;
-  const float ccx = qy * uvz - qz * uvy, ccy = qz * uvx - qx * uvz, ccz = qx * uvy - qy * uvx;
-  x = px + f.qw * uvx + ccx;
-  y = py + f.qw * uvy + ccy;
-  z = pz + f.qw * uvz + ccz;
-}
-
-// can any voxel of block (bx, by, bz) find a pixel?  (conservative: true when in doubt)
-__device__ __forceinline__ bool block_in_view(const ProjFrame& f, float block_size, int bx, int by, int bz) {
-  const float gx = ((float)bx + 0.5f) * block_size, gy = ((float)by + 0.5f) * block_size, gz = ((float)bz + 0.5f) * block_size;
-  float x, y, z;
-  to_camera(f, gx, gy, gz, x, y, z);
-  // the sphere around the block's voxel centres, 2 % wider, plus 1e-5 of every magnitude that went into a coordinate
-  // (f32: 6e-8 per operation, a dozen operations)
-  const float r = 0.8660254f * block_size * 1.02f +
-                  1e-5f * (fabsf(gx) + fabsf(gy) + fabsf(gz) + fabsf(f.tx) + fabsf(f.ty) + fabsf(f.tz));
-  if (!(z + r > 0.0f)) return false;      // z > 0 fails for every voxel
-  if (z - r > f.z_far) return false;      // beyond the depth gate and the ray length, truncation included
-  if (!f.reject) return true;
-  const float w = (float)f.width, h = (float)f.height;
-  const float l0 = f.cx + 0.5f, r0 = l0 - w, t0 = f.cy + 0.5f, b0 = t0 - h;
-  // 0 <= (x / z) fx + cx + 0.5 fails for every point of the sphere with z > 0 when the sphere lies wholly on the
-  // negative side of the plane fx x + (cx + 0.5) z = 0; the other three alike
-  if (f.fx * x + l0 * z < -r * sqrtf(f.fx * f.fx + l0 * l0)) return false;
-  if (f.fx * x + r0 * z > r * sqrtf(f.fx * f.fx + r0 * r0)) return false;
-  if (f.fy * y + t0 * z < -r * sqrtf(f.fy * f.fy + t0 * t0)) return false;
-  if (f.fy * y + b0 * z > r * sqrtf(f.fy * f.fy + b0 * b0)) return false;
-  return true;
-}
-
-// What the frame does to the voxel (vx, vy, vz): false = no update; else the update's sdf, weight and colour, and
-// kind = 0 inside the truncation band or behind the surface, 1 carved, 2 cleared.  The rules of the header, in its order.
+// the depth-image frame, as the generic block walk (vgx_projective_kernel.h) asks for it
 template <int ENC, bool ELEMENTS>
-__device__ __forceinline__ bool projective_term(const ProjFrame& f, const vgx_tsdf_config& c, float vs, int vx, int vy, int vz,
-                                                float& sdf, float& uw, uint32_t& color, int& kind) {
-  const float gx = ((float)vx + 0.5f) * vs, gy = ((float)vy + 0.5f) * vs, gz = ((float)vz + 0.5f) * vs;
-  float x, y, z;
-  to_camera(f, gx, gy, gz, x, y, z);
-  if (!(z > 0.0f)) return false;
-  const float uf = (x / z) * f.fx + f.cx, vf = (y / z) * f.fy + f.cy;
-  const float ua = uf + 0.5f, va = vf + 0.5f;
-  if (!(ua >= 0.0f && ua < (float)f.width && va >= 0.0f && va < (float)f.height)) return false;
-  const uint32_t ui = (uint32_t)floorf(ua), vi = (uint32_t)floorf(va);
-  const float d = depth_z<ENC, ELEMENTS>(f.img, f.img.depth + (size_t)vi * f.img.row_step, ui);
-  if (!(d > 0.0f && d < INFINITY)) return false;            // the decode's rule 1
-  if (!(d >= f.img.min_z && d <= f.img.max_z)) return false;  // ... and 2
-  const float trunc = c.default_truncation_distance;
-  const float r_v = norm3(x, y, z);
-  const float s = r_v / z;
-  const float r_s = d * s;
-  sdf = (d - z) * s;
-  kind = 0;
-  if (r_s < c.min_ray_length_m) return false;
-  if (r_s > c.max_ray_length_m) {
-    if (!(c.allow_clear && c.voxel_carving_enabled && r_v + trunc <= c.max_ray_length_m)) return false;
-    sdf = c.max_ray_length_m - r_v;
-    kind = 2;
-  } else {
-    if (sdf < -trunc) return false;
-    if (sdf > trunc) {
-      if (!c.voxel_carving_enabled) return false;
-      kind = 1;
-    }
+struct PinholeFrame : ProjFrame {
+  // can any voxel of block (bx, by, bz) find a pixel?  (conservative: true when in doubt)
+  __device__ __forceinline__ bool block_in_view(float block_size, int bx, int by, int bz) const {
+    const ProjFrame& f = *this;
+    float x, y, z;
+    const float r = block_sphere(f, block_size, bx, by, bz, x, y, z);
+    if (!(z + r > 0.0f)) return false;      // z > 0 fails for every voxel
+    if (z - r > f.z_far) return false;      // beyond the depth gate and the ray length, truncation included
+    if (!f.reject) return true;
+    const float w = (float)f.width, h = (float)f.height;
+    const float l0 = f.cx + 0.5f, r0 = l0 - w, t0 = f.cy + 0.5f, b0 = t0 - h;
+    // 0 <= (x / z) fx + cx + 0.5 fails for every point of the sphere with z > 0 when the sphere lies wholly on the
+    // negative side of the plane fx x + (cx + 0.5) z = 0; the other three alike
+    if (f.fx * x + l0 * z < -r * sqrtf(f.fx * f.fx + l0 * l0)) return false;
+    if (f.fx * x + r0 * z > r * sqrtf(f.fx * f.fx + r0 * r0)) return false;
+    if (f.fy * y + t0 * z < -r * sqrtf(f.fy * f.fy + t0 * t0)) return false;
+    if (f.fy * y + b0 * z > r * sqrtf(f.fy * f.fy + b0 * b0)) return false;
+    return true;
   }
-  uw = c.use_const_weight ? 1.0f : 1.0f / (d * d);
-  if (c.use_weight_dropoff && sdf < -vs) {  // update_term's drop-off (vgx_tsdf_det.hip)
-    uw = uw * (trunc + sdf) / (trunc - vs);
-    uw = fmaxf(uw, 0.0f);
-  }
-  color = f.img.color_kind == VGX_IMAGE_COLOR_NONE ? 0xffffffffu : depth_colour(f.img, ui, vi);
-  return true;
-}
 
-template <int ENC, bool ELEMENTS, int VPS>
-__global__ __launch_bounds__(kProjThreads) void projective_kernel(TsdfLayerDev L, vgx_tsdf_config c, ProjFrame f, TileChain chain,
-                                                        unsigned long long* __restrict__ ctl) {
-  constexpr int kShift = VPS == 16 ? 4 : 3, kMask = VPS - 1, kVpb = VPS * VPS * VPS, kVpt = kVpb / kProjThreads;
-  __shared__ uint32_t sh_word;
-  const uint32_t tile = chain_tile(chain, &sh_word);
-  // (tile < f.tiles: the launch has f.tiles workgroups and the ticket counts them)
-  const int bx = f.lo[0] + (int)(tile % (uint32_t)f.nx);
-  const int by = f.lo[1] + (int)((tile / (uint32_t)f.nx) % (uint32_t)f.ny);
-  const int bz = f.lo[2] + (int)(tile / ((uint32_t)f.nx * (uint32_t)f.ny));
-  // the block table covers the box (tsdf_reserve_blocks); a block outside it could only be dropped
-  const int rx = bx - L.lut_min[0], ry = by - L.lut_min[1], rz = bz - L.lut_min[2];
-  const bool in_table = (unsigned)rx < (unsigned)L.lut_dim[0] && (unsigned)ry < (unsigned)L.lut_dim[1] && (unsigned)rz < (unsigned)L.lut_dim[2];
-  const size_t cell = in_table ? (size_t)rx + (size_t)L.lut_dim[0] * ((size_t)ry + (size_t)L.lut_dim[1] * (size_t)rz) : 0;
-  int slot = in_table ? L.lut[cell] : -1;
-  if (slot >= L.max_blocks) slot = -1;
-  const bool present = slot >= 0;
-
-  // A block the layer holds is updated in place; of an absent one only "does a voxel change" is kept, and the voxels
-  // are formed again (a voxel of a fresh block is zero: nothing to load) once the block has its slot.
-  uint32_t dirty_mask = 0, n_updates = 0, n_carved = 0, n_cleared = 0;
-  if (block_in_view(f, (float)VPS * L.voxel_size, bx, by, bz)) {
-#pragma unroll 2
-    for (int k = 0; k < kVpt; ++k) {
-      const int v = k * kProjThreads + (int)threadIdx.x;
-      const int lx = v & kMask, ly = (v >> kShift) & kMask, lz = v >> (2 * kShift);
-      float sdf, uw;
-      uint32_t color;
-      int kind;
-      if (!projective_term<ENC, ELEMENTS>(f, c, L.voxel_size, bx * VPS + lx, by * VPS + ly, bz * VPS + lz, sdf, uw, color, kind)) continue;
-      float d = 0.0f, w = 0.0f;
-      uint32_t col = 0u;
-      const size_t at = (size_t)(present ? slot : 0) * kVpb + (size_t)v;
-      if (present) {
-        const unsigned long long old = L.voxels[at];
-        d = __uint_as_float((unsigned)(old & 0xffffffffull));
-        w = __uint_as_float((unsigned)(old >> 32));
-        col = L.rgba[at];
-      }
-      bool dirty = false;
-      apply_term(c, sdf, uw, color, d, w, col, dirty);
-      if (!dirty) continue;
-      if (present) {
-        L.voxels[at] = pack_voxel(d, w);
-        L.rgba[at] = col;
-      }
-      dirty_mask |= 1u << k;
-      ++n_updates;
-      n_carved += kind == 1;
-      n_cleared += kind == 2;
-    }
-  }
-  const bool any = __syncthreads_or(dirty_mask != 0u) != 0;
-  const uint32_t needed = (!present && any) ? 1u : 0u;
-  const uint32_t before = chain_exclusive_sum(chain, tile, needed, &sh_word);
-  if (needed) {
-    const long long s = (long long)f.base_blocks + (long long)before;
-    slot = (in_table && s < (long long)L.max_blocks) ? (int)s : -1;
-    if (slot >= 0) {
-      if (threadIdx.x == 0) {
-        L.block_index[3 * (size_t)slot + 0] = bx;
-        L.block_index[3 * (size_t)slot + 1] = by;
-        L.block_index[3 * (size_t)slot + 2] = bz;
-        L.lut[cell] = slot;
-      }
-#pragma unroll 2
-      for (int k = 0; k < kVpt; ++k) {
-        if (!(dirty_mask & (1u << k))) continue;
-        const int v = k * kProjThreads + (int)threadIdx.x;
-        const int lx = v & kMask, ly = (v >> kShift) & kMask, lz = v >> (2 * kShift);
-        float sdf, uw, d = 0.0f, w = 0.0f;
-        uint32_t color, col = 0u;
-        int kind;
-        bool dirty = false;
-        (void)projective_term<ENC, ELEMENTS>(f, c, L.voxel_size, bx * VPS + lx, by * VPS + ly, bz * VPS + lz, sdf, uw, color, kind);
-        apply_term(c, sdf, uw, color, d, w, col, dirty);
-        const size_t at = (size_t)slot * kVpb + (size_t)v;
-        L.voxels[at] = pack_voxel(d, w);
-        L.rgba[at] = col;
+  // What the frame does to the voxel (vx, vy, vz): false = no update; else the update's sdf, weight and colour, and
+  // kind = 0 inside the truncation band or behind the surface, 1 carved, 2 cleared.  The rules of the header, in its order.
+  __device__ __forceinline__ bool term(const vgx_tsdf_config& c, float vs, int vx, int vy, int vz, float& sdf, float& uw,
+                                       uint32_t& color, int& kind) const {
+    const ProjFrame& f = *this;
+    const float gx = ((float)vx + 0.5f) * vs, gy = ((float)vy + 0.5f) * vs, gz = ((float)vz + 0.5f) * vs;
+    float x, y, z;
+    to_camera(f, gx, gy, gz, x, y, z);
+    if (!(z > 0.0f)) return false;
+    const float uf = (x / z) * f.fx + f.cx, vf = (y / z) * f.fy + f.cy;
+    const float ua = uf + 0.5f, va = vf + 0.5f;
+    if (!(ua >= 0.0f && ua < (float)f.width && va >= 0.0f && va < (float)f.height)) return false;
+    const uint32_t ui = (uint32_t)floorf(ua), vi = (uint32_t)floorf(va);
+    const float d = depth_z<ENC, ELEMENTS>(f.img, f.img.depth + (size_t)vi * f.img.row_step, ui);
+    if (!(d > 0.0f && d < INFINITY)) return false;            // the decode's rule 1
+    if (!(d >= f.img.min_z && d <= f.img.max_z)) return false;  // ... and 2
+    const float trunc = c.default_truncation_distance;
+    const float r_v = norm3(x, y, z);
+    const float s = r_v / z;
+    const float r_s = d * s;
+    sdf = (d - z) * s;
+    kind = 0;
+    if (r_s < c.min_ray_length_m) return false;
+    if (r_s > c.max_ray_length_m) {
+      if (!(c.allow_clear && c.voxel_carving_enabled && r_v + trunc <= c.max_ray_length_m)) return false;
+      sdf = c.max_ray_length_m - r_v;
+      kind = 2;
+    } else {
+      if (sdf < -trunc) return false;
+      if (sdf > trunc) {
+        if (!c.voxel_carving_enabled) return false;
+        kind = 1;
       }
     }
-  }
-  if (any) {
-    // the frame's counters: a wave's sums, one atomic each (integer sums: the order does not show)
-    uint32_t a = n_updates, b = n_carved, e = n_cleared;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-      a += (uint32_t)__shfl_xor((int)a, d);
-      b += (uint32_t)__shfl_xor((int)b, d);
-      e += (uint32_t)__shfl_xor((int)e, d);
+    uw = c.use_const_weight ? 1.0f : 1.0f / (d * d);
+    if (c.use_weight_dropoff && sdf < -vs) {  // update_term's drop-off (vgx_tsdf_det.hip)
+      uw = uw * (trunc + sdf) / (trunc - vs);
+      uw = fmaxf(uw, 0.0f);
     }
-    if ((threadIdx.x & 63) == 0 && a != 0u) {
-      if (slot >= 0) {
-        atomicAdd(ctl + kProjUpdates, (unsigned long long)a);
-        if (b) atomicAdd(ctl + kProjCarved, (unsigned long long)b);
-        if (e) atomicAdd(ctl + kProjCleared, (unsigned long long)e);
-      } else {  // no room (cannot happen after tsdf_reserve_blocks): reported as the other integrators report it
-        atomicAdd(ctl + kProjDropped, (unsigned long long)a);
-        atomicAdd(L.dropped, (unsigned long long)a);
-      }
-    }
+    color = f.img.color_kind == VGX_IMAGE_COLOR_NONE ? 0xffffffffu : depth_colour(f.img, ui, vi);
+    return true;
   }
-  if (tile == f.tiles - 1u && threadIdx.x == 0) {
-    const long long total = (long long)f.base_blocks + (long long)before + (long long)needed;
-    *L.n_blocks = (int32_t)(total < (long long)L.max_blocks ? total : (long long)L.max_blocks);
-    ctl[kProjNew] = (unsigned long long)(before + needed);
-  }
-}
-
-template <int ENC, bool ELEMENTS>
-void projective_launch(hipStream_t st, const TsdfLayerDev& L, const vgx_tsdf_config& c, const ProjFrame& f, const TileChain& chain,
-                       unsigned long long* ctl) {
-  if (L.vps == 16)
-    hipLaunchKernelGGL((projective_kernel<ENC, ELEMENTS, 16>), dim3(f.tiles), dim3(kProjThreads), 0, st, L, c, f, chain, ctl);
-  else
-    hipLaunchKernelGGL((projective_kernel<ENC, ELEMENTS, 8>), dim3(f.tiles), dim3(kProjThreads), 0, st, L, c, f, chain, ctl);
-}
+};
 
 // The candidate block box, f64 throughout: the axis-aligned box (layer frame) of the camera centre and of the points
 // where the four image-corner rays -- through (-0.5, -0.5), (width - 0.5, -0.5), (-0.5, height - 0.5), (width - 0.5,
@@ -289,13 +150,97 @@ int projective_box(const vgx_depth_image_layout& l, const vgx_depth_camera& cam,
   return VGX_OK;
 }
 
+int projective_begin(const char* fn, vgx_tsdf_integrator I, const int32_t lo[3], const int32_t hi[3], ProjFrameBase* f) {
+  vgx_ctx ctx = I->ctx;
+  vgx_tsdf_layer L = I->layer;
+  const int64_t nx = (int64_t)hi[0] - lo[0] + 1, ny = (int64_t)hi[1] - lo[1] + 1, nz = (int64_t)hi[2] - lo[2] + 1;
+  if (nx * ny > kProjMaxCandidates || nx * ny * nz > kProjMaxCandidates)
+    return set_error(ctx, VGX_ERR_UNSUPPORTED, std::string(fn) + ": the candidate box holds more than 2^24 blocks");
+  const int64_t candidates = nx * ny * nz;
+  VGX_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->tsdf_stream;
+  // room for every candidate; waits for the stream and reads the exact block count: the frame's one host synchronisation
+  const int rc = tsdf_reserve_blocks(L, lo, hi, candidates);
+  if (rc != VGX_OK) return rc;
+  const int32_t base_blocks = (int32_t)L->known_blocks;  // (exact: tsdf_reserve_blocks has just read it behind everything queued)
+  // the control words and one chain word per candidate
+  if (!I->d_proj_ctl.p) {
+    const hipError_t e = I->d_proj_ctl.alloc(kProjCtlWords * 8);
+    if (e != hipSuccess) return alloc_error(ctx, e, "projective integration: allocating counters");
+    VGX_HIP(ctx, hipMemsetAsync(I->d_proj_ctl.p, 0, kProjCtlWords * 8, st));
+    I->proj_tickets = 0;
+  }
+  if ((size_t)candidates * 8 > I->d_proj_state.bytes) {
+    VGX_HIP(ctx, hipStreamSynchronize(st));
+    const hipError_t e = I->d_proj_state.reserve((size_t)candidates * 8, 0, true);
+    if (e != hipSuccess) return alloc_error(ctx, e, "projective integration: allocating tile words");
+    VGX_HIP(ctx, hipMemsetAsync(I->d_proj_state.p, 0, I->d_proj_state.bytes, st));  // (epoch 0: no launch's tag)
+  }
+  if (I->proj_epoch >= kChainEpochMax) {
+    VGX_HIP(ctx, hipMemsetAsync(I->d_proj_state.p, 0, I->d_proj_state.bytes, st));
+    I->proj_epoch = 0;
+  }
+  for (int a = 0; a < 3; ++a) f->lo[a] = lo[a];
+  f->nx = (int32_t)nx;
+  f->ny = (int32_t)ny;
+  f->tiles = (uint32_t)candidates;
+  f->base_blocks = base_blocks;
+  return VGX_OK;
+}
+
+int projective_chain(vgx_tsdf_integrator I, const ProjFrameBase& f, TileChain* chain) {
+  vgx_ctx ctx = I->ctx;
+  unsigned long long* ctl = I->d_proj_ctl.as<unsigned long long>();
+  VGX_HIP(ctx, hipMemsetAsync(ctl + kProjNew, 0, 8 * (kProjCtlWords - kProjNew), ctx->tsdf_stream));
+  chain->state = I->d_proj_state.as<unsigned long long>();
+  chain->epoch = ++I->proj_epoch;
+  chain->ticket = ctl + kProjTicket;
+  chain->ticket_base = I->proj_tickets;
+  chain->error = ctl + kProjError;
+  I->proj_tickets += f.tiles;
+  return VGX_OK;
+}
+
+int projective_end(const char* fn, vgx_tsdf_integrator I, const ProjFrameBase& f, vgx_projective_counts* counts) {
+  vgx_ctx ctx = I->ctx;
+  hipStream_t st = ctx->tsdf_stream;
+  unsigned long long* ctl = I->d_proj_ctl.as<unsigned long long>();
+  VGX_HIP(ctx, hipGetLastError());
+  tsdf_note_allocations(I->layer, (int64_t)f.tiles);
+  if (counts) {
+    unsigned long long back[kProjCtlWords - kProjError] = {};
+    VGX_HIP(ctx, hipMemcpyAsync(back, ctl + kProjError, sizeof(back), hipMemcpyDeviceToHost, st));
+    VGX_HIP(ctx, hipStreamSynchronize(st));
+    if (back[0] != 0) {
+      (void)hipMemsetAsync(ctl + kProjError, 0, 8, st);
+      return set_error(ctx, VGX_ERR_HIP, std::string(fn) + ": a candidate block never reported (internal error)");
+    }
+    if (back[kProjDropped - kProjError] != 0)
+      return set_error(ctx, VGX_ERR_NOMEM, std::string(fn) + ": voxel updates were dropped (no room for a block)");
+    vgx_projective_counts out{};
+    out.n_candidate_blocks = (int64_t)f.tiles;
+    out.n_new_blocks = (int64_t)back[kProjNew - kProjError];
+    out.n_updates = (int64_t)back[kProjUpdates - kProjError];
+    out.n_carved = (int64_t)back[kProjCarved - kProjError];
+    out.n_cleared = (int64_t)back[kProjCleared - kProjError];
+    *counts = out;
+  }
+  return VGX_OK;
+}
+
 }  // namespace vgx
 
 using namespace vgx;
 
 namespace {
 
-constexpr int64_t kMaxCandidates = (int64_t)1 << 24;
+template <int ENC, bool ELEMENTS>
+void pinhole_launch(hipStream_t st, const TsdfLayerDev& L, const vgx_tsdf_config& c, const ProjFrame& f, const TileChain& chain,
+                    unsigned long long* ctl) {
+  PinholeFrame<ENC, ELEMENTS> frame;
+  static_cast<ProjFrame&>(frame) = f;
+  projective_launch(st, L, c, frame, chain, ctl);
+}
 
 // the images' bytes into the integrator's image buffer through its pinned staging halves (pieces of 1 MiB, filled in turn)
 int upload_image(vgx_tsdf_integrator I, const void* data, size_t bytes, size_t dst) {
@@ -359,33 +304,10 @@ int integrate_depth_image(const char* fn, vgx_tsdf_integrator I, const float T[7
   int32_t lo[3], hi[3];
   rc = projective_box(*l, *cam, c, T, L->dev.voxel_size, L->dev.vps, lo, hi, &why);
   if (rc != VGX_OK) return set_error(ctx, rc, std::string(fn) + ": " + why);
-  const int64_t nx = (int64_t)hi[0] - lo[0] + 1, ny = (int64_t)hi[1] - lo[1] + 1, nz = (int64_t)hi[2] - lo[2] + 1;
-  if (nx * ny > kMaxCandidates || nx * ny * nz > kMaxCandidates)
-    return set_error(ctx, VGX_ERR_UNSUPPORTED, std::string(fn) + ": the candidate box holds more than 2^24 blocks");
-  const int64_t candidates = nx * ny * nz;
-  VGX_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->tsdf_stream;
-  // room for every candidate; waits for the stream and reads the exact block count: the frame's one host synchronisation
-  rc = tsdf_reserve_blocks(L, lo, hi, candidates);
+  ProjFrame f{};
+  rc = projective_begin(fn, I, lo, hi, &f);
   if (rc != VGX_OK) return rc;
-  const int32_t base_blocks = (int32_t)L->known_blocks;  // (exact: tsdf_reserve_blocks has just read it behind everything queued)
-  // the control words and one chain word per candidate
-  if (!I->d_proj_ctl.p) {
-    const hipError_t e = I->d_proj_ctl.alloc(kProjCtlWords * 8);
-    if (e != hipSuccess) return alloc_error(ctx, e, "projective integration: allocating counters");
-    VGX_HIP(ctx, hipMemsetAsync(I->d_proj_ctl.p, 0, kProjCtlWords * 8, st));
-    I->proj_tickets = 0;
-  }
-  if ((size_t)candidates * 8 > I->d_proj_state.bytes) {
-    VGX_HIP(ctx, hipStreamSynchronize(st));
-    const hipError_t e = I->d_proj_state.reserve((size_t)candidates * 8, 0, true);
-    if (e != hipSuccess) return alloc_error(ctx, e, "projective integration: allocating tile words");
-    VGX_HIP(ctx, hipMemsetAsync(I->d_proj_state.p, 0, I->d_proj_state.bytes, st));  // (epoch 0: no launch's tag)
-  }
-  if (I->proj_epoch >= kChainEpochMax) {
-    VGX_HIP(ctx, hipMemsetAsync(I->d_proj_state.p, 0, I->d_proj_state.bytes, st));
-    I->proj_epoch = 0;
-  }
+  hipStream_t st = ctx->tsdf_stream;
   const bool colour = l->color_kind != VGX_IMAGE_COLOR_NONE;
   const uint8_t* d_depth = static_cast<const uint8_t*>(depth);
   const uint8_t* d_color = colour ? static_cast<const uint8_t*>(color) : nullptr;
@@ -405,16 +327,6 @@ int integrate_depth_image(const char* fn, vgx_tsdf_integrator I, const float T[7
     d_depth = I->d_image.as<uint8_t>();
     d_color = colour ? d_depth + cat : nullptr;
   }
-  unsigned long long* ctl = I->d_proj_ctl.as<unsigned long long>();
-  VGX_HIP(ctx, hipMemsetAsync(ctl + kProjNew, 0, 8 * (kProjCtlWords - kProjNew), st));
-  TileChain chain;
-  chain.state = I->d_proj_state.as<unsigned long long>();
-  chain.epoch = ++I->proj_epoch;
-  chain.ticket = ctl + kProjTicket;
-  chain.ticket_base = I->proj_tickets;
-  chain.error = ctl + kProjError;
-  I->proj_tickets += (uint32_t)candidates;
-  ProjFrame f{};
   f.img.depth = d_depth;
   f.img.color = d_color;
   f.img.row_step = l->row_step;
@@ -431,42 +343,22 @@ int integrate_depth_image(const char* fn, vgx_tsdf_integrator I, const float T[7
   f.cy = (float)cam->cy;
   f.qw = T[0]; f.qx = T[1]; f.qy = T[2]; f.qz = T[3];
   f.tx = T[4]; f.ty = T[5]; f.tz = T[6];
-  for (int a = 0; a < 3; ++a) f.lo[a] = lo[a];
-  f.nx = (int32_t)nx;
-  f.ny = (int32_t)ny;
-  f.tiles = (uint32_t)candidates;
-  f.base_blocks = base_blocks;
   f.z_far = std::fmin(cam->max_depth_m, c.max_ray_length_m) + c.default_truncation_distance;
   f.reject = f.fx > 0.0f && f.fy > 0.0f && std::isfinite(f.fx) && std::isfinite(f.fy);
+  TileChain chain;
+  rc = projective_chain(I, f, &chain);
+  if (rc != VGX_OK) return rc;
+  unsigned long long* ctl = I->d_proj_ctl.as<unsigned long long>();
   const bool sixteen = l->encoding == VGX_DEPTH_16UC1;
   const bool elements = ((uintptr_t)d_depth | l->row_step) % (sixteen ? 2u : 4u) == 0;
   if (sixteen) {
-    if (elements) projective_launch<VGX_DEPTH_16UC1, true>(st, L->dev, c, f, chain, ctl);
-    else projective_launch<VGX_DEPTH_16UC1, false>(st, L->dev, c, f, chain, ctl);
+    if (elements) pinhole_launch<VGX_DEPTH_16UC1, true>(st, L->dev, c, f, chain, ctl);
+    else pinhole_launch<VGX_DEPTH_16UC1, false>(st, L->dev, c, f, chain, ctl);
   } else {
-    if (elements) projective_launch<VGX_DEPTH_32FC1, true>(st, L->dev, c, f, chain, ctl);
-    else projective_launch<VGX_DEPTH_32FC1, false>(st, L->dev, c, f, chain, ctl);
+    if (elements) pinhole_launch<VGX_DEPTH_32FC1, true>(st, L->dev, c, f, chain, ctl);
+    else pinhole_launch<VGX_DEPTH_32FC1, false>(st, L->dev, c, f, chain, ctl);
   }
-  VGX_HIP(ctx, hipGetLastError());
-  tsdf_note_allocations(L, candidates);
-  if (counts) {
-    unsigned long long back[kProjCtlWords - kProjError] = {};
-    VGX_HIP(ctx, hipMemcpyAsync(back, ctl + kProjError, sizeof(back), hipMemcpyDeviceToHost, st));
-    VGX_HIP(ctx, hipStreamSynchronize(st));
-    if (back[0] != 0) {
-      (void)hipMemsetAsync(ctl + kProjError, 0, 8, st);
-      return set_error(ctx, VGX_ERR_HIP, std::string(fn) + ": a candidate block never reported (internal error)");
-    }
-    if (back[kProjDropped - kProjError] != 0)
-      return set_error(ctx, VGX_ERR_NOMEM, std::string(fn) + ": voxel updates were dropped (no room for a block)");
-    out.n_candidate_blocks = candidates;
-    out.n_new_blocks = (int64_t)back[kProjNew - kProjError];
-    out.n_updates = (int64_t)back[kProjUpdates - kProjError];
-    out.n_carved = (int64_t)back[kProjCarved - kProjError];
-    out.n_cleared = (int64_t)back[kProjCleared - kProjError];
-    *counts = out;
-  }
-  return VGX_OK;
+  return projective_end(fn, I, f, counts);
 }
 
 }  // namespace

@@ -351,6 +351,11 @@ std::unique_lock<std::mutex> scan_borrow(vgx_scan S, const float** d_points, int
   *d_points = S->n_points > 0 ? S->d_points.as<float>() : nullptr;
   return lk;
 }
+std::unique_lock<std::mutex> scan_borrow(vgx_scan S, const float** d_points, const uint32_t** d_rgba, int64_t* n) {
+  std::unique_lock<std::mutex> lk = scan_borrow(S, d_points, n);
+  *d_rgba = S->n_points > 0 ? S->d_rgba.as<uint32_t>() : nullptr;
+  return lk;
+}
 }  // namespace vgx
 
 namespace {

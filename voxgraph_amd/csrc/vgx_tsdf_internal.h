@@ -509,6 +509,7 @@ vgx_ctx scan_context(vgx_scan S);
 // the scan's lock (taken before ctx->tsdf_mu, as the decode takes it) and what the scan holds now: while the caller keeps
 // the lock no decode can replace the array a queued kernel reads
 std::unique_lock<std::mutex> scan_borrow(vgx_scan S, const float** d_points, int64_t* n);
+std::unique_lock<std::mutex> scan_borrow(vgx_scan S, const float** d_points, const uint32_t** d_rgba, int64_t* n);  // ... with the colours
 }  // namespace vgx
 
 #endif  // VGX_TSDF_INTERNAL_H_
