@@ -1129,7 +1129,8 @@ VGX_API int vgx_tsdf_projective_box(const vgx_depth_image_layout* layout, const 
  *               outside [-PI, PI], the f32 constants (the column wrap below is ONE step), elevation_first_rad == elevation_last_rad with
  *               height > 1, an elevation outside (-pi/2, pi/2), width or height < 1; VGX_ERR_UNSUPPORTED: width > 4096,
  *               height > 256, width < 4, and height == 1 (a single beam has no pitch to take a row's extent from; no
- *               vertical aperture field is defined: refused).  A beam table for non-uniform rows is not supported.
+ *               vertical aperture field is defined: refused).  Non-uniform rows, per-row azimuth offsets and
+ *               single-row scanners: "LiDAR range images: beam tables" below.
  *   pixel       of a sensor-frame direction (x, y, z) with r = sqrtf(x x + y y + z z) (summed left to right), r > 0 and
  *               finite: rho = sqrtf(x x + y y), az = rule(y, x), el = rule(z, rho);
  *               uf = (az - azimuth_first_rad) * su, ua = uf + 0.5f, wrapped ONCE: if ua < 0: ua += (float)width, else if
@@ -1235,6 +1236,76 @@ VGX_API int vgx_tsdf_integrate_range_image(vgx_tsdf_integrator integrator, const
 VGX_API int vgx_tsdf_range_image_box(const vgx_lidar_model* model, const vgx_range_image_counts* image_counts,
                                      const vgx_tsdf_config* cfg, const float T_G_S[7], float voxel_size,
                                      int32_t voxels_per_side, int32_t lo[3], int32_t hi[3]);
+
+/* ---- LiDAR range images: beam tables (non-uniform rows, per-row azimuth offsets, single-row scanners) ---- */
+/* A second sensor model for the range image above: every row has an elevation of its own, boundaries derived
+ * from its neighbours', and an azimuth offset.  The uniform model keeps its rule and its bits; this text is the definition
+ * of the table rule, which vgx_range_image.hip and tests/beam_table_ref.py both follow.  Every call that takes the model
+ * copies the two arrays before it returns.
+ *   derived     host constants, each formed in f64 from the f32 inputs and rounded ONCE to f32.  su: the uniform model's.
+ *               s_0 < ... < s_{H-1}: the elevations in ascending order (the table, or the table reversed);
+ *               L = (double)row_half_extent_max_rad; mid_k = (s_k + s_{k+1}) * 0.5.  Interior boundaries:
+ *               hi_k = min(mid_k, s_k + L), lo_{k+1} = max(mid_k, s_{k+1} - L) [L = +inf: the same f64, hence the same
+ *               f32 -- no gap, no overlap].  Outer boundaries: lo_0 = s_0 - min(mid_0 - s_0, L),
+ *               hi_{H-1} = s_{H-1} + min(s_{H-1} - mid_{H-2}, L).  H == 1: lo_0 = s_0 - L, hi_0 = s_0 + L.  After the
+ *               rounding each boundary is clamped to [-VGX_ATAN2_PI_2, VGX_ATAN2_PI_2].
+ *   check       vgx_range_image_check_beams refuses -- VGX_ERR_INVALID: a NULL model or elevation array, an angle that is
+ *               not finite, |azimuth_first_rad| > PI, an elevation with |e| >= pi/2, a table that is not strictly
+ *               monotone, a limit that is not > 0 (NaN included), an offset with |off| > VGX_ATAN2_PI_2, width or height
+ *               < 1, height == 1 with an infinite limit, rounded boundaries that do not satisfy lo_k < hi_k and
+ *               hi_k <= lo_{k+1} for every k; VGX_ERR_UNSUPPORTED: width > 4096, height > 256, width < 4.  A single row
+ *               IS accepted when the limit is finite: the limit is its extent.
+ *   pixel       of a direction with positive finite range; rho, az, el as above (vgx_atan2_rule).  Row: k* = the largest k
+ *               with lo_k <= el, plain f32 compares; none, or !(el < hi_{k*}): outside the rows (above or below them, or
+ *               in a gap between two rows the limit clipped).  vi = k* for an ascending table, H - 1 - k* for a
+ *               descending one.  Column (defined only inside a row: it needs the row's offset):
+ *               ua = ((az - azimuth_first_rad) - off_vi) * su + 0.5f, wrapped in TWO passes, each: if ua < 0:
+ *               ua += (float)width, else if ua >= (float)width: ua -= (float)width  [|uf| <= 1.25 width: two passes always
+ *               suffice, one does not]; ui = floorf(ua) clamped to [0, width - 1].  Nearest pixel only.
+ *   image       vgx_range_image_build_beams / _beams_device: cells, keys, counts and extremes word for word as above;
+ *               only the pixel rule differs.  n_rejected_rows includes directions in a gap.  One handle may hold a uniform
+ *               image, then a table image, then a uniform one.  The image keeps the table on the device and uploads it
+ *               (one copy on the TSDF stream, behind any frame that still reads the table held) only when it differs from
+ *               the one held.  vgx_range_image_beams reports the table of the image held; vgx_range_image_stats fills its
+ *               vgx_lidar_model with the shared fields and the table's FIRST and LAST elevation: a summary, not the model.
+ *   integrate   vgx_tsdf_integrate_range_image, unchanged: the image knows which kind it holds.  Gates, weights, update,
+ *               block order and counts as above.
+ *   candidates  vgx_tsdf_range_image_box_beams: the uniform rule with pitch_el replaced by
+ *               ext_max = max_k((double)hi_k - (double)lo_k) of the rounded boundaries: a voxel and its pixel's return lie
+ *               in the same row and in the same column of that row's offset grid, at most one extent apart in each angle
+ *               plus twice the rule's error.  [Early block reject: the cones of lo_0 and hi_{H-1}, widened by the rule's
+ *               error; a cone that closes on the axis and the gaps between rows reject nothing.  No value, no count
+ *               changes.] */
+typedef struct vgx_lidar_beam_model {
+  int32_t width, height;                /* columns; rows = beams                                   */
+  float azimuth_first_rad;              /* as vgx_lidar_model                                      */
+  int32_t azimuth_clockwise;            /* as vgx_lidar_model                                      */
+  const float* row_elevation_rad;       /* [height], strictly ascending or strictly descending     */
+  const float* row_azimuth_offset_rad;  /* [height] or NULL (zeros): added to azimuth_first_rad for that row */
+  float row_half_extent_max_rad;        /* > 0; +inf: neighbouring rows meet halfway               */
+} vgx_lidar_beam_model;
+/* HOST ONLY: VGX_OK, or why a model is refused */
+VGX_API int vgx_range_image_check_beams(const vgx_lidar_beam_model* model);
+/* HOST ONLY: the pixel rule; VGX_OK with *u, *v (u = v = -1: outside the rows), VGX_ERR_INVALID for NULL, a refused model or
+ * a direction whose r is not positive and finite */
+VGX_API int vgx_range_image_pixel_beams(const vgx_lidar_beam_model* model, float x, float y, float z, int32_t* u, int32_t* v);
+/* as vgx_range_image_build / _build_device: the same locks in the same order, the TSDF stream, queued without counts */
+VGX_API int vgx_range_image_build_beams(vgx_range_image image, const vgx_lidar_beam_model* model, vgx_scan scan,
+                                        vgx_range_image_counts* counts /* NULL: queued, not waited for */);
+VGX_API int vgx_range_image_build_beams_device(vgx_range_image image, const vgx_lidar_beam_model* model, const void* d_points,
+                                               const void* d_rgba, int64_t n, vgx_range_image_counts* counts);
+/* the table the image held was built for: *is_table 0 (a uniform image; the other outputs are left alone) or 1, with
+ * row_elevation [height], row_azimuth_offset [height] (zeros where the model gave NULL) and the limit; any may be NULL */
+VGX_API int vgx_range_image_beams(vgx_range_image image, int32_t* is_table, float* row_elevation, float* row_azimuth_offset,
+                                  float* row_half_extent_max_rad);
+/* HOST ONLY: the candidate block box [lo, hi] (both ends included) of a table image with these counts */
+VGX_API int vgx_tsdf_range_image_box_beams(const vgx_lidar_beam_model* model, const vgx_range_image_counts* image_counts,
+                                           const vgx_tsdf_config* cfg, const float T_G_S[7], float voxel_size,
+                                           int32_t voxels_per_side, int32_t lo[3], int32_t hi[3]);
+/* HOST ONLY: dirs [height][width][3] f32, the unit direction through the centre of every pixel, computed in f64 and rounded
+ * once: az = (azimuth_first_rad + off_row) + col / su with su in f64, el = row_elevation_rad[row], dir = (cos el cos az,
+ * cos el sin az, sin el).  A sweep of exactly this sensor for the view renderer.  VGX_ERR_INVALID: NULL, a refused model */
+VGX_API int vgx_view_rays_lidar_beams(const vgx_lidar_beam_model* model, float* dirs);
 
 /* finishSubmap() hand-off without a host round trip: turns the active layer's blocks
  * into a (not yet finished) submap holding the raw TSDF layer and its TSDF sampling

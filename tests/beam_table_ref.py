@@ -1,0 +1,158 @@
+"""numpy restatement of the beam-table range image (include/voxgraph_amd.h, "LiDAR range images: beam tables"): the derived
+row boundaries, the check, the pixel rule (rows by plain f32 compares, the column from the row's own azimuth offset, wrapped
+twice), the candidate box and the pixel-centre rays.  Everything else -- the image, the gates, the weights, the update, the
+block order -- is tests/range_image_ref.py's own code, evaluated with this module's pixel rule wherever the model is a
+table (build, integrate and box below are its functions, untouched, looking `pixel` up here).  Needs no device."""
+import types
+
+import numpy as np
+
+from tests import range_image_ref as R
+
+F = np.float32
+OK, ERR_INVALID, ERR_UNSUPPORTED = R.OK, R.ERR_INVALID, R.ERR_UNSUPPORTED
+Config, Layer, Model = R.Config, R.Layer, R.Model
+PI_2, PI, TWO_PI = R.PI_2, R.PI, R.TWO_PI
+HALF_PI = 1.5707963267948966
+
+
+class BeamModel:
+    """vgx_lidar_beam_model and its derived constants.  lo, hi, off_sorted: f32 [height] in ASCENDING elevation."""
+
+    def __init__(self, width, row_elevation_rad, row_azimuth_offset_rad=None, azimuth_first_rad=0.0, azimuth_clockwise=0,
+                 row_half_extent_max_rad=np.inf):
+        self.width, self.azimuth_clockwise = int(width), int(azimuth_clockwise)
+        self.azimuth_first_rad, self.row_half_extent_max_rad = F(azimuth_first_rad), F(row_half_extent_max_rad)
+        self.row_elevation_rad = np.asarray(row_elevation_rad, F).reshape(-1)
+        self.row_azimuth_offset_rad = None if row_azimuth_offset_rad is None else np.asarray(row_azimuth_offset_rad, F).reshape(-1)
+        self.height = len(self.row_elevation_rad)
+        self.offsets = np.zeros(self.height, F) if self.row_azimuth_offset_rad is None else self.row_azimuth_offset_rad
+        self.descending = self.height > 1 and bool(self.row_elevation_rad[1] < self.row_elevation_rad[0])
+        self._derive()
+
+    def _derive(self):
+        """each boundary formed in f64, rounded once to f32, then clamped to [-PI_2, PI_2]"""
+        H, L = self.height, float(self.row_half_extent_max_rad)
+        s = self.row_elevation_rad.astype(np.float64)
+        s = s[::-1] if self.descending else s
+        with np.errstate(all="ignore"):
+            if H == 1:
+                lo, hi = s - L, s + L
+            elif H > 1:
+                mid = (s[:-1] + s[1:]) * 0.5
+                lo, hi = np.empty(H), np.empty(H)
+                hi[:-1] = np.minimum(mid, s[:-1] + L)
+                lo[1:] = np.maximum(mid, s[1:] - L)
+                lo[0] = s[0] - min(mid[0] - s[0], L)
+                hi[-1] = s[-1] + min(s[-1] - mid[-1], L)
+            else:
+                lo = hi = np.zeros(0)
+            self.lo = np.clip(lo.astype(F), -PI_2, PI_2)
+            self.hi = np.clip(hi.astype(F), -PI_2, PI_2)
+        self.off_sorted = self.offsets[::-1] if self.descending else self.offsets
+
+    def capi(self, capi, **more):
+        kw = dict(width=self.width, row_elevation_rad=self.row_elevation_rad, row_azimuth_offset_rad=self.row_azimuth_offset_rad,
+                  azimuth_first_rad=self.azimuth_first_rad, azimuth_clockwise=self.azimuth_clockwise,
+                  row_half_extent_max_rad=self.row_half_extent_max_rad)
+        kw.update(more)
+        return capi.lidar_beam_model(**kw)
+
+    @property
+    def su(self):
+        return F((-1.0 if self.azimuth_clockwise else 1.0) * float(self.width) / TWO_PI)
+
+    @property
+    def pitch_az(self):
+        return TWO_PI / self.width
+
+    @property
+    def ext_max(self):
+        return float((self.hi.astype(np.float64) - self.lo.astype(np.float64)).max())
+
+    pitch_el = ext_max          # what range_image_ref.box widens by: the rule with pitch_el replaced by ext_max
+
+    def check(self):
+        e, off, H = self.row_elevation_rad.astype(np.float64), self.offsets.astype(np.float64), self.height
+        L = float(self.row_half_extent_max_rad)
+        if self.width < 1 or H < 1 or not np.isfinite(float(self.azimuth_first_rad)) or abs(float(self.azimuth_first_rad)) > float(PI):
+            return ERR_INVALID
+        if not L > 0:
+            return ERR_INVALID
+        if H > 256:
+            return ERR_UNSUPPORTED
+        if not (np.isfinite(e).all() and np.isfinite(off).all()) or not (np.abs(e) < HALF_PI).all() or (np.abs(off) > float(PI_2)).any():
+            return ERR_INVALID
+        d = np.diff(self.row_elevation_rad)
+        if not ((d > 0).all() or (d < 0).all()):
+            return ERR_INVALID
+        if self.width > 4096 or self.width < 4:
+            return ERR_UNSUPPORTED
+        if H == 1 and np.isinf(L):
+            return ERR_INVALID
+        if not ((self.lo < self.hi).all() and (self.hi[:-1] <= self.lo[1:]).all()):
+            return ERR_INVALID
+        return OK
+
+    def direction(self, u, v, d_el=0.0):
+        """the unit direction (f64) at column u (may be fractional) of row v (integers), d_el radians above the row's centre"""
+        v = np.asarray(v, np.int64)
+        az = float(self.azimuth_first_rad) + self.offsets.astype(np.float64)[v] + np.asarray(u, np.float64) / float(self.su)
+        el = self.row_elevation_rad.astype(np.float64)[v] + d_el
+        return np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)], -1)
+
+    def extent(self, v):
+        """(lo, hi) f64 of table row v"""
+        k = self.height - 1 - np.asarray(v) if self.descending else np.asarray(v)
+        return self.lo.astype(np.float64)[k], self.hi.astype(np.float64)[k]
+
+    def rays(self):
+        """vgx_view_rays_lidar_beams: [height * width][3] f32, su in f64"""
+        su = (-1.0 if self.azimuth_clockwise else 1.0) * float(self.width) / TWO_PI
+        el = self.row_elevation_rad.astype(np.float64)[:, None]
+        az = (float(self.azimuth_first_rad) + self.offsets.astype(np.float64))[:, None] + np.arange(self.width)[None, :] / su
+        d = np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el) + 0 * az], -1)
+        return d.reshape(-1, 3).astype(F)
+
+
+def uniform_as_table(m):
+    """the table that restates a uniform range_image_ref.Model's row centres (offsets zero, the limit inf)"""
+    el = float(m.elevation_first_rad) + np.arange(m.height) * ((float(m.elevation_last_rad) - float(m.elevation_first_rad)) / (m.height - 1))
+    return BeamModel(m.width, el, None, m.azimuth_first_rad, m.azimuth_clockwise)
+
+
+def beam_pixel(m, x, y, z):
+    """the table's pixel rule on f32 arrays of directions with a positive finite range: (ui, vi, inside); -1, -1 outside"""
+    x, y, z = (np.asarray(a, F) for a in (x, y, z))
+    with np.errstate(all="ignore"):
+        rho = np.sqrt(x * x + y * y)
+        az, el = R.atan2_rule(y, x), R.atan2_rule(z, rho)
+        k = np.searchsorted(m.lo, el, side="right") - 1      # lo ascends (the check): the largest k with lo_k <= el, -1: none
+        k0 = np.maximum(k, 0)
+        ok = (k >= 0) & (el < m.hi[k0])
+        off = m.off_sorted[k0]
+        ua = ((az - m.azimuth_first_rad) - off) * m.su + F(0.5)
+        w = F(m.width)
+        for _ in range(2):
+            ua = np.where(ua < 0, ua + w, np.where(ua >= w, ua - w, ua)).astype(F)
+        ui = np.clip(np.floor(ua).astype(np.int64), 0, m.width - 1)
+        vi = (m.height - 1 - k0) if m.descending else k0
+    return np.where(ok, ui, -1), np.where(ok, vi, -1).astype(np.int64), ok
+
+
+def pixel(m, x, y, z):
+    return beam_pixel(m, x, y, z) if isinstance(m, BeamModel) else R.pixel(m, x, y, z)
+
+
+def _with_this_pixel_rule(fn):
+    """range_image_ref's function, its globals this module's: `pixel` (and through integrate `box`) resolve here"""
+    return types.FunctionType(fn.__code__, globals(), fn.__name__, fn.__defaults__, fn.__closure__)
+
+
+# what range_image_ref's code refers to by name
+Image, Frame, norm3, atan2_rule, P, MAX_ERROR = R.Image, R.Frame, R.norm3, R.atan2_rule, R.P, R.MAX_ERROR
+NO_RANGE, OUTSIDE_ROWS, EMPTY_CELL, TOO_SHORT, CLEAR_REFUSED, BEHIND, CARVE_REFUSED, NO_CHANGE, UPDATED, CARVED, CLEARED = range(11)
+same_counts = R.same_counts
+box = R.box                                   # (reads the model's pitch_az and pitch_el only)
+build = _with_this_pixel_rule(R.build)
+integrate = _with_this_pixel_rule(R.integrate)

@@ -147,6 +147,14 @@ class LidarModel(C.Structure):
                 ("elevation_first_rad", C.c_float), ("elevation_last_rad", C.c_float)]
 
 
+class LidarBeamModel(C.Structure):
+    """vgx_lidar_beam_model: a spinning LiDAR whose rows have elevations and azimuth offsets of their own (make one with
+    lidar_beam_model(), which keeps the arrays alive)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("azimuth_first_rad", C.c_float), ("azimuth_clockwise", C.c_int32),
+                ("row_elevation_rad", C.POINTER(C.c_float)), ("row_azimuth_offset_rad", C.POINTER(C.c_float)),
+                ("row_half_extent_max_rad", C.c_float)]
+
+
 class RangeImageCounts(C.Structure):
     """vgx_range_image_counts: of the range image a handle holds."""
     _fields_ = [("n_points", C.c_int64), ("n_kept", C.c_int64), ("n_filled", C.c_int64), ("n_collided", C.c_int64),
@@ -441,6 +449,13 @@ SIGNATURES = {
     "vgx_tsdf_integrate_range_image": (C.c_int, [vp, f32p, vp, C.POINTER(ProjectiveCounts)]),
     "vgx_tsdf_range_image_box": (C.c_int, [C.POINTER(LidarModel), C.POINTER(RangeImageCounts), C.POINTER(TsdfConfig), f32p,
                                            C.c_float, C.c_int32, i32p, i32p]),
+    "vgx_range_image_check_beams": (C.c_int, [C.POINTER(LidarBeamModel)]),
+    "vgx_range_image_pixel_beams": (C.c_int, [C.POINTER(LidarBeamModel), C.c_float, C.c_float, C.c_float, i32p, i32p]),
+    "vgx_range_image_build_beams": (C.c_int, [vp, C.POINTER(LidarBeamModel), vp, C.POINTER(RangeImageCounts)]),
+    "vgx_range_image_build_beams_device": (C.c_int, [vp, C.POINTER(LidarBeamModel), vp, vp, C.c_int64, C.POINTER(RangeImageCounts)]),
+    "vgx_range_image_beams": (C.c_int, [vp, i32p, f32p, f32p, f32p]),
+    "vgx_tsdf_range_image_box_beams": (C.c_int, [C.POINTER(LidarBeamModel), C.POINTER(RangeImageCounts), C.POINTER(TsdfConfig), f32p,
+                                                 C.c_float, C.c_int32, i32p, i32p]),
     "vgx_scan_download": (C.c_int, [vp, f32p, u8p]),
     "vgx_scan_device_pointers": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp)]),
     "vgx_tsdf_integrate_scan": (C.c_int, [vp, f32p, vp, C.c_int32, i64p]),
@@ -550,6 +565,7 @@ SIGNATURES = {
     "vgx_submap_render_view_device": (C.c_int, [vp, vp, f32p, C.c_int64, vp]),
     "vgx_view_rays_pinhole": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, f32p]),
     "vgx_view_rays_lidar": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, f32p]),
+    "vgx_view_rays_lidar_beams": (C.c_int, [C.POINTER(LidarBeamModel), f32p]),
 }
 
 # every symbol include/voxgraph_amd_bench.h declares (libvoxgraph_amd_bench.so: test and benchmark tooling)
@@ -2046,6 +2062,54 @@ def lidar_model(**kw):
     return m
 
 
+def lidar_beam_model(width, row_elevation_rad, row_azimuth_offset_rad=None, azimuth_first_rad=0.0, azimuth_clockwise=0,
+                     row_half_extent_max_rad=float("inf"), height=None):
+    """A vgx_lidar_beam_model; height defaults to the table's length.  The f32 copies of the two arrays hang on the
+    structure, so they live as long as it does."""
+    m = LidarBeamModel()
+    el = np.ascontiguousarray(row_elevation_rad, np.float32).reshape(-1)
+    off = None if row_azimuth_offset_rad is None else np.ascontiguousarray(row_azimuth_offset_rad, np.float32).reshape(-1)
+    m.width, m.height = int(width), len(el) if height is None else int(height)
+    m.azimuth_first_rad, m.azimuth_clockwise, m.row_half_extent_max_rad = azimuth_first_rad, int(azimuth_clockwise), row_half_extent_max_rad
+    m.row_elevation_rad = _ptr(el, f32p)
+    m.row_azimuth_offset_rad = None if off is None else _ptr(off, f32p)
+    m._keep = (el, off)
+    return m
+
+
+def range_image_check_beams(model):
+    """vgx_range_image_check_beams (host only): OK, or the code the model is refused with; None: a NULL argument"""
+    return load().vgx_range_image_check_beams(None if model is None else C.byref(model))
+
+
+def range_image_pixel_beams(model, x, y, z):
+    """vgx_range_image_pixel_beams (host only): (code, u, v); u = v = -1 outside the rows"""
+    u, v = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    rc = load().vgx_range_image_pixel_beams(None if model is None else C.byref(model), float(x), float(y), float(z), _ptr(u, i32p),
+                                            _ptr(v, i32p))
+    return rc, int(u[0]), int(v[0])
+
+
+def range_image_box_beams(model, image_counts, config, T_G_S, voxel_size, vps):
+    """vgx_tsdf_range_image_box_beams (host only): as range_image_box, for a LidarBeamModel"""
+    T = _f32(T_G_S)
+    lo, hi = np.zeros(3, np.int32), np.zeros(3, np.int32)
+    if isinstance(image_counts, dict):
+        image_counts = range_image_counts(**image_counts)
+    m, ic, cfg = (None if o is None else C.byref(o) for o in (model, image_counts, config))
+    rc = load().vgx_tsdf_range_image_box_beams(m, ic, cfg, _ptr(T, f32p), float(voxel_size), int(vps), _ptr(lo, i32p), _ptr(hi, i32p))
+    return rc, lo, hi
+
+
+def view_rays_lidar_beams(model):
+    """vgx_view_rays_lidar_beams (host only): unit directions [height * width][3] f32 through the pixel centres, row-major"""
+    dirs = np.zeros((model.height * model.width, 3), np.float32)
+    rc = load().vgx_view_rays_lidar_beams(C.byref(model), _ptr(dirs, f32p))
+    if rc != OK:
+        raise VgxError(rc, "vgx_view_rays_lidar_beams: the model is refused")
+    return dirs
+
+
 def range_image_check(model):
     """vgx_range_image_check (host only): OK, or the code the model is refused with; None: a NULL argument"""
     return load().vgx_range_image_check(None if model is None else C.byref(model))
@@ -2109,15 +2173,17 @@ class RangeImage:
     def build(self, model, scan, count=True):
         """from a decoded Scan; returns the counts as a dict, count=False: None and the build is queued"""
         out = RangeImageCounts()
-        self.ctx.check(self.ctx.lib.vgx_range_image_build(self.h, C.byref(model), scan.h, C.byref(out) if count else None))
+        fn = self.ctx.lib.vgx_range_image_build_beams if isinstance(model, LidarBeamModel) else self.ctx.lib.vgx_range_image_build
+        self.ctx.check(fn(self.h, C.byref(model), scan.h, C.byref(out) if count else None))
         return _counts_dict(out) if count else None
 
     def build_device(self, model, d_points, d_rgba, n, count=True):
         """from device arrays (f32 [n][3], u32 [n] or None) ready with respect to the TSDF stream"""
         out = RangeImageCounts()
-        self.ctx.check(self.ctx.lib.vgx_range_image_build_device(self.h, C.byref(model), vp(d_points) if d_points else None,
-                                                                 vp(d_rgba) if d_rgba else None, int(n),
-                                                                 C.byref(out) if count else None))
+        lib = self.ctx.lib
+        fn = lib.vgx_range_image_build_beams_device if isinstance(model, LidarBeamModel) else lib.vgx_range_image_build_device
+        self.ctx.check(fn(self.h, C.byref(model), vp(d_points) if d_points else None, vp(d_rgba) if d_rgba else None, int(n),
+                          C.byref(out) if count else None))
         return _counts_dict(out) if count else None
 
     def stats(self):
@@ -2127,9 +2193,19 @@ class RangeImage:
         return _counts_dict(out)
 
     def model(self):
+        """the uniform model the image was built for; of a table image a summary: the shared fields and the table's first
+        and last elevation (beams() gives the table)"""
         m = LidarModel()
         self.ctx.check(self.ctx.lib.vgx_range_image_stats(self.h, None, C.byref(m)))
         return m
+
+    def beams(self):
+        """vgx_range_image_beams: None for a uniform image, else (row_elevation [h], row_azimuth_offset [h], limit)"""
+        h = self.model().height
+        is_table, limit = np.zeros(1, np.int32), np.zeros(1, np.float32)
+        el, off = np.zeros(h, np.float32), np.zeros(h, np.float32)
+        self.ctx.check(self.ctx.lib.vgx_range_image_beams(self.h, _ptr(is_table, i32p), _ptr(el, f32p), _ptr(off, f32p), _ptr(limit, f32p)))
+        return (el, off, float(limit[0])) if is_table[0] else None
 
     def download(self):
         """(range [h][w] f32, rgba [h][w][4] u8, point_index [h][w] i32)"""

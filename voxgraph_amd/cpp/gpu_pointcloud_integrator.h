@@ -20,6 +20,7 @@
 #ifndef VOXGRAPH_AMD_CPP_GPU_POINTCLOUD_INTEGRATOR_H_
 #define VOXGRAPH_AMD_CPP_GPU_POINTCLOUD_INTEGRATOR_H_
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <memory>
@@ -237,24 +238,39 @@ class GpuPointcloudIntegrator {
   template <class Msg, class Transformation>
   void integrateProjective(const Transformation& T_submap_sensor, const Msg& msg, const vgx_lidar_model& model, GpuTsdfLayer* layer,
                            vgx_projective_counts* counts = nullptr) {
-    const auto& q = T_submap_sensor.getRotation();
-    const auto& t = T_submap_sensor.getPosition();
-    const float T[7] = {(float)q.w(), (float)q.x(), (float)q.y(), (float)q.z(), (float)t[0], (float)t[1], (float)t[2]};
-    if (!layer) throw std::invalid_argument("integrateProjective: NULL layer");
     if (vgx_range_image_check(&model) != VGX_OK) throw std::invalid_argument("integrateProjective: the LiDAR model is refused");
-    const vgx_scan_layout layout = layoutOf(msg);
-    if (vgx_scan_decode_msg(scan_, &layout, &scan_config_, msg.data.data(), (int64_t)msg.data.size()) != VGX_OK)
-      throw std::runtime_error(std::string("vgx_scan_decode_msg: ") + vgx_last_error(ctx_));
-    int64_t dropped = 0;
-    vgx_scan_stats(scan_, &last_points_, &dropped);
-    if (!range_image_ && vgx_range_image_create(ctx_, &range_image_) != VGX_OK)
-      throw std::runtime_error(std::string("vgx_range_image_create: ") + vgx_last_error(ctx_));
-    if (vgx_range_image_build(range_image_, &model, scan_, nullptr) != VGX_OK)
-      throw std::runtime_error(std::string("vgx_range_image_build: ") + vgx_last_error(ctx_));
-    if (!tsdf_integrator_) tsdf_integrator_.reset(new GpuFastTsdfIntegrator(ctx_, tsdf_integrator_config_, layer));
-    tsdf_integrator_->setLayer(layer);
-    if (vgx_tsdf_integrate_range_image(tsdf_integrator_->handle(), T, range_image_, counts) != VGX_OK)
-      throw std::runtime_error(std::string("vgx_tsdf_integrate_range_image: ") + vgx_last_error(ctx_));
+    integrateProjectiveBy(T_submap_sensor, msg, layer, counts, "vgx_range_image_build",
+                          [&](vgx_range_image image, vgx_scan scan) { return vgx_range_image_build(image, &model, scan, nullptr); });
+  }
+  // The same for a sensor described by a beam table (include/voxgraph_amd.h, "LiDAR range images: beam tables"): rows with
+  // elevations and azimuth offsets of their own, strictly monotone -- sortedBeamTable brings a table in laser order there.
+  template <class Msg, class Transformation>
+  void integrateProjective(const Transformation& T_submap_sensor, const Msg& msg, const vgx_lidar_beam_model& model, GpuTsdfLayer* layer,
+                           vgx_projective_counts* counts = nullptr) {
+    if (vgx_range_image_check_beams(&model) != VGX_OK) throw std::invalid_argument("integrateProjective: the beam table is refused");
+    integrateProjectiveBy(T_submap_sensor, msg, layer, counts, "vgx_range_image_build_beams",
+                          [&](vgx_range_image image, vgx_scan scan) { return vgx_range_image_build_beams(image, &model, scan, nullptr); });
+  }
+  // A beam table as sensors publish it -- in laser (firing) order, not monotone -- sorted by ascending elevation, with the
+  // permutation: row k of the sorted table is laser order[k].  view() is valid while the object lives and is not changed.
+  struct SortedBeamTable {
+    std::vector<float> row_elevation_rad, row_azimuth_offset_rad;
+    std::vector<int32_t> order;
+    vgx_lidar_beam_model view(int32_t width, float azimuth_first_rad, int32_t azimuth_clockwise, float row_half_extent_max_rad) const {
+      return vgx_lidar_beam_model{width, (int32_t)row_elevation_rad.size(), azimuth_first_rad, azimuth_clockwise, row_elevation_rad.data(),
+                                  row_azimuth_offset_rad.empty() ? nullptr : row_azimuth_offset_rad.data(), row_half_extent_max_rad};
+    }
+  };
+  // azimuth_offset_rad may be NULL (no offsets).  Equal elevations stay in laser order (and the check then refuses the table).
+  static SortedBeamTable sortedBeamTable(const float* elevation_rad, const float* azimuth_offset_rad, int32_t n) {
+    SortedBeamTable t;
+    for (int32_t k = 0; k < n; ++k) t.order.push_back(k);
+    std::stable_sort(t.order.begin(), t.order.end(), [&](int32_t a, int32_t b) { return elevation_rad[a] < elevation_rad[b]; });
+    for (int32_t k : t.order) {
+      t.row_elevation_rad.push_back(elevation_rad[k]);
+      if (azimuth_offset_rad) t.row_azimuth_offset_rad.push_back(azimuth_offset_rad[k]);
+    }
+    return t;
   }
   // the range image of the last integrateProjective (NULL before the first)
   vgx_range_image rangeImage() const { return range_image_; }
@@ -266,6 +282,28 @@ class GpuPointcloudIntegrator {
   vgx_scan scan() const { return scan_; }
 
  private:
+  // build: int(vgx_range_image, vgx_scan), the image of the decoded scan; `what` names it in the error
+  template <class Msg, class Transformation, class Build>
+  void integrateProjectiveBy(const Transformation& T_submap_sensor, const Msg& msg, GpuTsdfLayer* layer, vgx_projective_counts* counts,
+                             const char* what, Build build) {
+    const auto& q = T_submap_sensor.getRotation();
+    const auto& t = T_submap_sensor.getPosition();
+    const float T[7] = {(float)q.w(), (float)q.x(), (float)q.y(), (float)q.z(), (float)t[0], (float)t[1], (float)t[2]};
+    if (!layer) throw std::invalid_argument("integrateProjective: NULL layer");
+    const vgx_scan_layout layout = layoutOf(msg);
+    if (vgx_scan_decode_msg(scan_, &layout, &scan_config_, msg.data.data(), (int64_t)msg.data.size()) != VGX_OK)
+      throw std::runtime_error(std::string("vgx_scan_decode_msg: ") + vgx_last_error(ctx_));
+    int64_t dropped = 0;
+    vgx_scan_stats(scan_, &last_points_, &dropped);
+    if (!range_image_ && vgx_range_image_create(ctx_, &range_image_) != VGX_OK)
+      throw std::runtime_error(std::string("vgx_range_image_create: ") + vgx_last_error(ctx_));
+    if (build(range_image_, scan_) != VGX_OK) throw std::runtime_error(std::string(what) + ": " + vgx_last_error(ctx_));
+    if (!tsdf_integrator_) tsdf_integrator_.reset(new GpuFastTsdfIntegrator(ctx_, tsdf_integrator_config_, layer));
+    tsdf_integrator_->setLayer(layer);
+    if (vgx_tsdf_integrate_range_image(tsdf_integrator_->handle(), T, range_image_, counts) != VGX_OK)
+      throw std::runtime_error(std::string("vgx_tsdf_integrate_range_image: ") + vgx_last_error(ctx_));
+  }
+
   template <class Msg>
   void integrate7(const Msg& msg, const float T_submap_sensor[7], GpuTsdfLayer* layer, const GpuScanTrack::Knots* track) {
     if (!layer) throw std::invalid_argument("integratePointcloud: NULL layer");  // CHECK_NOTNULL(submap_ptr)
