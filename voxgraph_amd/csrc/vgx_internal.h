@@ -519,7 +519,7 @@ struct vgx_reg_batch_s {
   int32_t n_draw_tiles = 0;
   vgx::DeviceBuffer d_drawn;          // float4; sampling: the point {x,y,z,d} every row uses in this evaluation (reg_gather_points_kernel)
   vgx::DeviceBuffer d_drawn_idx;      // int32 ... and its index in the point set (reg_draw_kernel)
-  vgx::DeviceBuffer d_tile_dead;      // bytes; per materialising-pass tile, per launch: every chunk culled (rows are zeros)
+  vgx::DeviceBuffer d_tile_dead;      // one BIT per materialising-pass tile, per launch: every chunk culled (rows are zeros)
   vgx::DeviceBuffer d_tile_first;     // int32 [n+1] first tile of each constraint
   vgx::DeviceBuffer d_partials;       // double [n_tiles][4 wavefronts][kPartialSize]
   vgx::DeviceBuffer d_normal;         // double [n][45] (internal, when caller passes none)
@@ -658,7 +658,9 @@ int engine_to_device(vgx_ctx ctx, SamplerEngine& e);
 void make_pose_pack(const double ref_pose[4], const double read_pose[4], PosePack* out);
 std::vector<Tile> make_tiles(int32_t constraint, int64_t n, int tile_points);
 constexpr int kBlockThreads = 256;
-constexpr int kPointsPerThread = 4;  // measured 5.09-5.28 / 5.06-5.12 / 5.77-5.79 ms at 2 / 4 / 8 (config 3)
+// measured 4.38-4.41 / 4.35-4.37 / 4.67-4.68 ms per pass at 2 / 4 / 8 (config 3, a thread's point loads issued together:
+// profiles/points_load_chain.txt; an earlier kernel, which issued them one after the other, measured 5.09-5.28 / 5.06-5.12 / 5.77-5.79)
+constexpr int kPointsPerThread = 4;
 constexpr int kTilePoints = kBlockThreads * kPointsPerThread;
 }  // namespace vgx
 

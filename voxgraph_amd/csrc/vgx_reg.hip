@@ -495,11 +495,38 @@ __global__ __launch_bounds__(256) void reg_gather_points_kernel(const Constraint
   }
 }
 
-// the point residual i of a sampling constraint uses: the batch's precomputed draw, or (one-constraint
-// drop-in launch) the draw itself
-__device__ __forceinline__ f32x4 sampled_point(const ConstraintDev& C, int64_t i) {
-  if (C.sample_pts) return as_global(reinterpret_cast<const f32x4*>(C.sample_pts))[C.row0 + i];
-  return as_global(reinterpret_cast<const f32x4*>(C.xyzd))[weighted_draw(C, i)];
+// The PPT points (and weights) of one thread of a materialising tile: residual j * kBlockThreads + threadIdx.x of the
+// `count` that start at `start`; lanes past the end load residual `start` and drop it later.  A sampling constraint
+// (RCF:113-122) uses the batch's precomputed draw, or (one-constraint drop-in launch) draws here, with weight 1.
+// Which of the three sources it is, is decided ONCE, around whole loops: with the test inside the per-point loop the
+// compiler branches round every point's loads and waits vmcnt(0) at each merge, so point j + 1 was requested only when
+// point j had arrived -- PPT dependent round trips where one is needed (profiles/points_load_chain.txt).  As written
+// every load of a path is issued before the first wait.
+template <int PPT>
+__device__ __forceinline__ void load_tile_points(const ConstraintDev& C, int64_t start, int count, f32x4 pt[PPT],
+                                                 float w[PPT]) {
+  int64_t i[PPT];
+#pragma unroll
+  for (int j = 0; j < PPT; ++j) {
+    const int local = j * kBlockThreads + (int)threadIdx.x;
+    i[j] = start + (local < count ? local : 0);
+  }
+  if (C.sample_raw == nullptr) {
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) pt[j] = as_global(reinterpret_cast<const f32x4*>(C.xyzd))[i[j]];
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) w[j] = as_global(C.weight)[i[j]];
+    return;
+  }
+  if (C.sample_pts) {
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) pt[j] = as_global(reinterpret_cast<const f32x4*>(C.sample_pts))[C.row0 + i[j]];
+  } else {
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) pt[j] = as_global(reinterpret_cast<const f32x4*>(C.xyzd))[weighted_draw(C, i[j])];
+  }
+#pragma unroll
+  for (int j = 0; j < PPT; ++j) w[j] = 1.0f;  // RCF:121
 }
 
 
@@ -516,26 +543,34 @@ __device__ __forceinline__ bool tile_outside(const ConstraintDev& C, const PoseP
     if (q * kChunkPoints < tile.count) any_live |= !chunk_outside(C.grid, P, C.chunk_bounds[chunk0 + q]);
   return !any_live;
 }
-// one thread per tile of the batched launch, in launch order
+// one thread per tile of the batched launch, in launch order.  The verdicts leave as one bit per tile, a wavefront's 64
+// in one 64-bit ballot (bit t & 31 of 32-bit word t >> 5): reg_eval_points_kernel reads its tile's word at a uniform
+// index, which a 32-bit word lets the compiler do on the scalar path, in the same clause as the tile descriptor (a
+// byte load goes through the vector path: one more round trip in front of every workgroup's first descriptor load).
 template <int PPT>
 __global__ __launch_bounds__(256) void reg_points_tile_dead_kernel(const ConstraintDev* __restrict__ cons,
                                                                   const PosePack* __restrict__ packs,
                                                                   const Tile* __restrict__ tiles, int n_tiles,
-                                                                  unsigned char* __restrict__ dead) {
+                                                                  unsigned long long* __restrict__ dead) {
   const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= n_tiles) return;
-  const Tile tile = tiles[t];
-  const ConstraintDev& C = cons[tile.constraint];
-  dead[t] = tile_cullable(C) && tile_outside<PPT>(C, packs[tile.constraint], tile);
+  bool verdict = false;
+  if (t < n_tiles) {
+    const Tile tile = tiles[t];
+    const ConstraintDev& C = cons[tile.constraint];
+    verdict = tile_cullable(C) && tile_outside<PPT>(C, packs[tile.constraint], tile);
+  }
+  const unsigned long long mask = __ballot(verdict);
+  if ((threadIdx.x & 63) == 0 && t < n_tiles) dead[t >> 6] = mask;  // t: the wavefront's first tile, a multiple of 64
 }
+// bytes of the verdict words of n_tiles tiles
+static inline size_t tile_dead_bytes(size_t n_tiles) { return ((n_tiles + 63) / 64) * sizeof(unsigned long long); }
 
 template <int VPS, int LAYOUT, typename OUT, int PPT>
 __device__ __forceinline__ void reg_eval_points_body(
     const ConstraintDev& C, const PosePack& P, const Tile& tile, int dead_hint, OUT* __restrict__ residuals,
     typename Out4<OUT>::type* __restrict__ jac_ref, typename Out4<OUT>::type* __restrict__ jac_read) {
   const GridDev g = C.grid;
-  const bool sampled = C.sample_raw != nullptr;
-  const bool want_jac = (jac_ref != nullptr) | (jac_read != nullptr);
+  const bool want_jac =(jac_ref != nullptr) | (jac_read != nullptr);
   // Chunk culling, as in the fused pass: when the bounding spheres of the tile's 512-point chunks all
   // map outside the reading submap's block box, none of its points finds a block (RCF:165-166), so
   // with no_correspondence_cost == 0 its rows are zeros whatever the points are: they are written
@@ -571,19 +606,7 @@ __device__ __forceinline__ void reg_eval_points_body(
   const float* cell[PPT];
   float Dx[PPT], Dy[PPT], Dz[PPT];
   float d[PPT][8];
-#pragma unroll
-  for (int j = 0; j < PPT; ++j) {
-    int local = j * kBlockThreads + (int)threadIdx.x;
-    bool active = local < tile.count;
-    int64_t i = tile.start + (active ? local : 0);
-    if (sampled) {
-      pt[j] = sampled_point(C, i);
-      w[j] = 1.0f;  // RCF:121
-    } else {
-      pt[j] = as_global(reinterpret_cast<const f32x4*>(C.xyzd))[i];
-      w[j] = as_global(C.weight)[i];
-    }
-  }
+  load_tile_points<PPT>(C, tile.start, tile.count, pt, w);
   // stage 1: exact base voxel of every point (registers only)
   Located loc[PPT];
   bool have[PPT];
@@ -635,13 +658,13 @@ __device__ __forceinline__ void reg_eval_points_body(
 template <int VPS, int LAYOUT, typename OUT, int PPT>
 __global__ __launch_bounds__(kBlockThreads) void reg_eval_points_kernel(
     const ConstraintDev* __restrict__ cons, const PosePack* __restrict__ packs,
-    const Tile* __restrict__ tiles, const unsigned char* __restrict__ tile_dead, int n_tiles,
+    const Tile* __restrict__ tiles, const uint32_t* __restrict__ tile_dead, int n_tiles,
     OUT* __restrict__ residuals, typename Out4<OUT>::type* __restrict__ jac_ref,
     typename Out4<OUT>::type* __restrict__ jac_read, int blocked) {
   const int t = blockIdx.x;
   if (t >= n_tiles) return;
   const Tile tile = tiles[t];
-  const int dead = tile_dead[t];
+  const int dead = (int)((tile_dead[t >> 5] >> (t & 31)) & 1u);  // reg_points_tile_dead_kernel's bit: a scalar load
   const ConstraintDev& C = cons[tile.constraint];
   if (blocked) {
     // ONE output stream (vgx_reg_batch_evaluate_points_blocked): `residuals` is the base of an array of tile blocks,
@@ -679,7 +702,7 @@ __global__ __launch_bounds__(kBlockThreads) void reg_eval_points_single_kernel(
 // ---------------------------------------------------------------------------
 // kernel 1v: the cost-function visuals of one constraint (vgx_reg_evaluate_visuals)
 // ---------------------------------------------------------------------------
-// The visuals instantiation of the drop-in materialising pass: same tiles, same point loads (sampled_point: the same
+// The visuals instantiation of the drop-in materialising pass: same tiles, same point loads (load_tile_points: the same
 // draws from the same engine outputs), same locate_stage1 / load_neighbours / eval_point, so r_u and j below are the
 // values the rows kernel scales.  What it writes per row (rules: include/voxgraph_amd.h, "Cost-function visuals"):
 //   cloud    32 B  pcl::PointXYZI {p_m.x, p_m.y, p_m.z, 1.0f | f32(f64(f32(r_u)) * factor), 0, 0, 0}: two 16-byte stores
@@ -705,25 +728,12 @@ __global__ __launch_bounds__(kBlockThreads) void reg_visuals_single_kernel(Const
   const int64_t left = C.n - start;
   const int count = (int)(left < kBlockThreads * PPT ? left : kBlockThreads * PPT);
   const GridDev g = C.grid;
-  const bool sampled = C.sample_raw != nullptr;
 
   f32x4 pt[PPT];
   float w[PPT];
   const float* cell[PPT];
   float d[PPT][8];
-#pragma unroll
-  for (int j = 0; j < PPT; ++j) {
-    int local = j * kBlockThreads + (int)threadIdx.x;
-    bool active = local < count;
-    int64_t i = start + (active ? local : 0);
-    if (sampled) {
-      pt[j] = sampled_point(C, i);
-      w[j] = 1.0f;  // RCF:121
-    } else {
-      pt[j] = as_global(reinterpret_cast<const f32x4*>(C.xyzd))[i];
-      w[j] = as_global(C.weight)[i];
-    }
-  }
+  load_tile_points<PPT>(C, start, count, pt, w);
   Located loc[PPT];
   bool have[PPT];
   const bool grid_empty = g.bricks == nullptr;  // reading submap without blocks
@@ -963,21 +973,30 @@ __global__ __launch_bounds__(kBlockThreads, kLeanWaves) void reg_eval_reduce_lea
 
   f32x4 pt_next[PPT];
   float w_next[PPT];
-  bool live_next = chunk_live(0);
-  if (live_next) {
+  // the points of the iteration that starts at `base`: the sampling test stands round the loops, not inside them, so
+  // that every point of an iteration is requested before the first is waited for (see load_tile_points)
+  auto prefetch = [&](int base) {
+    int64_t i[PPT];
 #pragma unroll
     for (int j = 0; j < PPT; ++j) {
-      int local = j * kBlockThreads + (int)threadIdx.x;
-      int64_t i = tile.start + (local < tile.count ? local : 0);
-      if (sampled) {
-        pt_next[j] = as_global(reinterpret_cast<const f32x4*>(C.sample_pts))[C.row0 + i];
-        w_next[j] = 1.0f;  // RCF:121
-      } else {
-        pt_next[j] = as_global(reinterpret_cast<const f32x4*>(C.xyzd))[i];
-        w_next[j] = as_global(C.weight)[i];
+      const int local = base + j * kBlockThreads + (int)threadIdx.x;
+      i[j] = tile.start + (local < tile.count ? local : 0);
+    }
+    if (sampled) {
+#pragma unroll
+      for (int j = 0; j < PPT; ++j) pt_next[j] = as_global(reinterpret_cast<const f32x4*>(C.sample_pts))[C.row0 + i[j]];
+#pragma unroll
+      for (int j = 0; j < PPT; ++j) w_next[j] = 1.0f;  // RCF:121
+    } else {
+#pragma unroll
+      for (int j = 0; j < PPT; ++j) {
+        pt_next[j] = as_global(reinterpret_cast<const f32x4*>(C.xyzd))[i[j]];
+        w_next[j] = as_global(C.weight)[i[j]];
       }
     }
-  }
+  };
+  bool live_next = chunk_live(0);
+  if (live_next) prefetch(0);
   for (int base = 0; base < tile.count; base += kIterPoints) {
     f32x4 pt[PPT];
     float w[PPT];
@@ -990,20 +1009,7 @@ __global__ __launch_bounds__(kBlockThreads, kLeanWaves) void reg_eval_reduce_lea
     live_next = false;
     if (base + kIterPoints < tile.count) {
       live_next = chunk_live((base + kIterPoints) / kChunkPoints);
-      if (live_next) {
-#pragma unroll
-        for (int j = 0; j < PPT; ++j) {
-          int local = base + kIterPoints + j * kBlockThreads + (int)threadIdx.x;
-          int64_t i = tile.start + (local < tile.count ? local : 0);
-          if (sampled) {
-            pt_next[j] = as_global(reinterpret_cast<const f32x4*>(C.sample_pts))[C.row0 + i];
-            w_next[j] = 1.0f;
-          } else {
-            pt_next[j] = as_global(reinterpret_cast<const f32x4*>(C.xyzd))[i];
-            w_next[j] = as_global(C.weight)[i];
-          }
-        }
-      }
+      if (live_next) prefetch(base + kIterPoints);
     }
     if (!live) continue;
     Located loc[PPT];
@@ -1636,7 +1642,7 @@ __global__ void reg_scatter_normal_kernel(const double* __restrict__ normal, int
 // ---------------------------------------------------------------------------
 template <typename OUT>
 static void launch_points(vgx_ctx ctx, int vps, int layout, const ConstraintDev* d_desc, const PosePack* d_pack,
-                          const Tile* d_tiles, unsigned char* d_tile_dead, int n_tiles, void* res, void* jr,
+                          const Tile* d_tiles, unsigned long long* d_tile_dead, int n_tiles, void* res, void* jr,
                           void* je, bool blocked = false) {
   if (n_tiles <= 0) return;
   hipLaunchKernelGGL(reg_points_tile_dead_kernel<kPointsPerThread>, dim3((n_tiles + 255) / 256), dim3(256), 0,
@@ -1645,7 +1651,7 @@ static void launch_points(vgx_ctx ctx, int vps, int layout, const ConstraintDev*
   using O4 = typename Out4<OUT>::type;
   dispatch_brick(vps, layout, [&](auto V, auto L) {
     hipLaunchKernelGGL((reg_eval_points_kernel<V(), L(), OUT, kPointsPerThread>), grid, block, 0, ctx->stream, d_desc, d_pack, d_tiles,
-                       d_tile_dead, n_tiles, (OUT*)res, (O4*)jr, (O4*)je, blocked ? 1 : 0);
+                       (const uint32_t*)d_tile_dead, n_tiles, (OUT*)res, (O4*)jr, (O4*)je, blocked ? 1 : 0);
   });
 }
 
@@ -2343,7 +2349,7 @@ int vgx_reg_batch_create(vgx_ctx ctx, int32_t n, const vgx_reg* regs, const int3
   build_node_csr(n, node_pair, ex->csr_nodes, first, items);
   int rc = upload_new(ctx, b->d_desc, desc.data(), desc.size() * sizeof(ConstraintDev));
   if (rc == VGX_OK) rc = upload_new(ctx, b->d_tiles, b->tiles.data(), b->tiles.size() * sizeof(Tile));
-  if (rc == VGX_OK && !b->tiles.empty() && b->d_tile_dead.alloc(b->tiles.size()) != hipSuccess) rc = VGX_ERR_NOMEM;
+  if (rc == VGX_OK && !b->tiles.empty() && b->d_tile_dead.alloc(tile_dead_bytes(b->tiles.size())) != hipSuccess) rc = VGX_ERR_NOMEM;
   if (rc == VGX_OK && b->any_sampling) {
     const std::vector<Tile> dt = make_draw_order(desc, points_tile_first, b->tiles);
     b->n_draw_tiles = (int32_t)dt.size();
@@ -2512,7 +2518,7 @@ static int batch_points_pass(vgx_reg_batch b, const double* poses, int32_t n_nod
     b->points_order_made = true;
   }
   launch_points<OUT>(ctx, b->regs[0]->reading->vps, b->layout, b->d_desc.as<ConstraintDev>(), b->d_pack.as<PosePack>(),
-                     b->d_tiles.as<Tile>(), b->d_tile_dead.as<unsigned char>(), (int)b->tiles.size(), res, jr, je, blocked);
+                     b->d_tiles.as<Tile>(), b->d_tile_dead.as<unsigned long long>(), (int)b->tiles.size(), res, jr, je, blocked);
   VGX_HIP(ctx, hipGetLastError());
   return VGX_OK;
 }
