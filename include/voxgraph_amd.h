@@ -2402,6 +2402,94 @@ VGX_API int vgx_scan_registration_refine(vgx_scan_registration reg, vgx_tsdf_lay
 VGX_API int vgx_scan_registration_history(vgx_scan_registration reg, int32_t capacity, vgx_pose_graph_iteration* iterations,
                                           int32_t* n_iterations);
 
+/* ---- Scan localisation ------------------------------------------------------- */
+/* Where is the sensor in the map that is already finished?  A scan's points against the ESDF (or TSDF) of POSED,
+ * FINISHED submaps: one evaluation at a pose, many poses scored in one call, the best one refined.  It serves
+ * re-localisation after the tracker is lost, the check of a proposed loop closure before it becomes a relative-pose
+ * edge, and the start pose when mapping resumes in a loaded map (vgx_map_file_load_submap).  DEFINED HERE, not recalled:
+ * the reference takes loop closures from outside and never verifies them.
+ *
+ * THE HANDLE is vgx_scan_registration: its points (host, device, vgx_scan), ranges, point_stride, max_abs_distance_m
+ * and min_valid_ratio apply unchanged, and vgx_scan_registration_history serves _refine_map and _localize too.
+ * vgx_scan_registration_set_map lists 1 <= n <= 64 finished submaps of the handle's context and of ONE voxels_per_side
+ * (8 or 16; voxel sizes may differ), each with a general unit-quaternion pose T_M_S (M: the mission frame).  T_S_M is
+ * formed once in f32 by vgx_submap_query's rule (conjugate rotation, translation -(q^-1 t)).  The handle takes a user
+ * count on every listed submap, as vgx_reg_create does: a vgx_submap_destroy meanwhile is deferred to the next _set_map
+ * or the handle's destruction.  n_submaps = 0 clears the map.  A submap whose chosen layer is no longer resident
+ * (vgx_submap_release_raw_layers, or an ESDF never generated) is refused by the next evaluation, VGX_ERR_INVALID.
+ *
+ * THE FORMULATION.  f32, one rounding per operation, no contraction, except where f64 is named.  Candidates by
+ * "Scan-to-map registration"'s rule: the stride, then the range gate.  Per candidate, with c, s, t' as there:
+ *   q   = R_prior p_C
+ *   p_M = ((c qx - s qy) + tx', (s qx + c qy) + ty', qz + tz')
+ * Per candidate and submap k, in ASCENDING k:
+ *   p_S = T_S_M,k p_M                          Eigen _transformVector, then + t
+ *   the term is USABLE iff |p_S,a * block_size_inv| < 2^30 on every axis, all 8 neighbours exist in the submap's block
+ *   table and are valid (ESDF observed != 0, TSDF weight > 0), and |r| < max_abs_distance_m, r the trilinear distance
+ *   g_S = (dD/d dl) * voxel_size_inv           the exact derivative of the interpolant, as there
+ *   g_M = R(T_M_S,k) g_S                       the rotation alone (_transformVector), not renormalised
+ *   J   = (g_Mx, g_My, g_Mz, g_Mx ((-s) qx - c qy) + g_My (c qx - s qy))
+ * THE LOSS is Huber's, in f64 and in arithmetic alone (no log, no sqrt: every operation is IEEE-exact):
+ *   rd = (double)r, a = (double)huber_delta_m;   |rd| <= a: w = 1, rho = rd rd;   else w = a / |rd|,
+ *   rho = (2 a) |rd| - a a
+ *   s0 += rho;   s[1 + k] += Jd[k] (w rd);   s[kl] += (w Jd[k]) Jd[l] in the pair order 00 01 02 03 11 12 13 22 23 33
+ * With w = 1 (huber_delta_m = +inf, the default) these are "Scan-to-map registration"'s bits.  cost = 0.5 s0.  The
+ * normal equations are the iteratively-reweighted-least-squares ones: there is NO second-order correction of the loss.
+ * Three int64 counts: n_candidates; n_points_valid, the candidates with at least one usable term; n_terms.
+ *
+ * THE ORDER CONTRACT is "Scan-to-map registration"'s partition: candidate j to slot j / 1024, thread (j % 1024) % 256,
+ * trip (j % 1024) / 256.  A thread adds its terms to 0.0 in ascending trip and within a trip in ascending k; then the
+ * same wave tree, the waves in order, and the same fold of the slots' partials.  vgx_scan_registration_score_poses
+ * applies the partition per pose with score_point_stride in place of point_stride.  A pose's result never depends on the
+ * other poses of the call, on the device, or on which workgroup did the work.  No float atomics.
+ *
+ * _evaluate_map: two launches, one synchronisation.  out[15] = {s0, s[1..4], s[kl]}.
+ * _score_poses: the cost alone at delta = 0 (c = 1, s = 0), for n_poses poses T_M_C [n_poses][7] (host): one upload of
+ * the pose table, two launches and one synchronisation whatever n_poses.  For equal strides cost[m] is bit for bit
+ * 0.5 out[0] of _evaluate_map(T_m, 0), and the counts are its counts.  Every output array is nullable.
+ * _refine_map: "Scan-to-map registration"'s LOOP and OUTCOME with this evaluation; n_valid_first / n_valid_last carry
+ * n_points_valid, and usable needs n_points_valid / n_candidates >= min_valid_ratio at the first and the last accepted
+ * evaluation.
+ * _localize: _score_poses; a pose is ELIGIBLE iff n_candidates > 0 and n_points_valid / n_candidates >= min_valid_ratio
+ * (f64); score = cost / n_terms, one f64 division; best_index the lowest score, ties to the lowest index; then
+ * _refine_map from T[best_index].  No eligible pose: VGX_OK, best_index = -1, a zeroed summary with usable = 0,
+ * VGX_FAILURE / VGX_TERMINATION_TOO_FEW_POINTS, T_refined the bits of T[0], delta = 0, an empty history.  n_poses = 0
+ * does that too, and then T_refined is not written.
+ *
+ * The calls run on the REGISTRATION side: the stream and the lock of vgx_submap_query, ordered behind
+ * vgx_submap_generate_esdf.  A vgx_scan source is complete when its decode returned; a borrowed device array must be
+ * ready with respect to the registration stream.  One call at a time per handle.
+ *
+ * Refused with VGX_ERR_INVALID, nothing written: NULL arguments; no map or no points set; a pose (of a submap, a prior,
+ * a hypothesis) that is not finite or whose quaternion has | |q|^2 - 1 | > 1e-4; a delta that is not finite; a submap
+ * of another context; submaps of different voxels_per_side; n_submaps < 0 or > 64; a layer value that is neither
+ * VGX_EVAL_LAYER_ESDF nor _TSDF; huber_delta_m <= 0 or NaN; score_point_stride < 1; n_poses < 0; a layer not resident.
+ * VGX_ERR_UNSUPPORTED: voxels_per_side other than 8 or 16; a launch of more than 2^31 - 1 workgroups (candidates / 1024,
+ * times n_poses).  A refused _set_map leaves the map it found. */
+typedef struct vgx_scan_map_config {
+  int32_t layer;              /* VGX_EVAL_LAYER_ESDF */
+  float huber_delta_m;        /* +inf: plain least squares */
+  int32_t score_point_stride; /* 1: the stride of _score_poses (and of _localize's scoring) in place of point_stride */
+  int32_t reserved;
+} vgx_scan_map_config;
+VGX_API void vgx_scan_map_config_default(vgx_scan_map_config* cfg);
+/* cfg NULL: the defaults */
+VGX_API int vgx_scan_registration_set_map(vgx_scan_registration reg, const vgx_scan_map_config* cfg, int32_t n_submaps,
+                                          const vgx_submap* submaps, const float* T_M_S /* [n_submaps][7] */);
+/* the three counts are nullable */
+VGX_API int vgx_scan_registration_evaluate_map(vgx_scan_registration reg, const float T_M_C_prior[7], const double delta[4],
+                                               double out[15], int64_t* n_terms, int64_t* n_points_valid,
+                                               int64_t* n_candidates);
+VGX_API int vgx_scan_registration_refine_map(vgx_scan_registration reg, const float T_M_C_prior[7],
+                                             const vgx_pose_graph_options* options, float T_refined[7], double delta[4],
+                                             vgx_scan_registration_summary* summary);
+VGX_API int vgx_scan_registration_score_poses(vgx_scan_registration reg, int32_t n_poses,
+                                              const float* T_M_C /* host [n_poses][7] */, double* cost, int64_t* n_terms,
+                                              int64_t* n_points_valid, int64_t* n_candidates);
+VGX_API int vgx_scan_registration_localize(vgx_scan_registration reg, int32_t n_poses, const float* T_M_C,
+                                           const vgx_pose_graph_options* options, int32_t* best_index, float T_refined[7],
+                                           double delta[4], vgx_scan_registration_summary* summary);
+
 /* ---- View rendering: range images ray-marched out of a TSDF layer ------------ */
 /* What the map looks like from a pose: per ray the range to the zero crossing of the trilinear TSDF, the surface point,
  * the gradient, the weight and the colour there -- the inverse of vgx_tsdf_integrate.  DEFINED HERE, not recalled:

@@ -260,6 +260,10 @@ class ScanRegistrationSummary(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
 
 
+class ScanMapConfig(C.Structure):
+    _fields_ = [("layer", C.c_int32), ("huber_delta_m", C.c_float), ("score_point_stride", C.c_int32), ("reserved", C.c_int32)]
+
+
 class ViewConfig(C.Structure):
     _fields_ = [("s_min", C.c_float), ("s_max", C.c_float), ("step_scale", C.c_float), ("min_step", C.c_float),
                 ("unknown_step", C.c_float), ("max_bracket", C.c_float), ("image_width", C.c_int32), ("flags", C.c_int32)]
@@ -552,6 +556,14 @@ SIGNATURES = {
     "vgx_scan_registration_refine": (C.c_int, [vp, vp, f32p, C.POINTER(PoseGraphOptions), f32p, f64p,
                                                C.POINTER(ScanRegistrationSummary)]),
     "vgx_scan_registration_history": (C.c_int, [vp, C.c_int32, C.POINTER(PoseGraphIteration), i32p]),
+    "vgx_scan_map_config_default": (None, [C.POINTER(ScanMapConfig)]),
+    "vgx_scan_registration_set_map": (C.c_int, [vp, C.POINTER(ScanMapConfig), C.c_int32, C.POINTER(vp), f32p]),
+    "vgx_scan_registration_evaluate_map": (C.c_int, [vp, f32p, f64p, f64p, i64p, i64p, i64p]),
+    "vgx_scan_registration_refine_map": (C.c_int, [vp, f32p, C.POINTER(PoseGraphOptions), f32p, f64p,
+                                                   C.POINTER(ScanRegistrationSummary)]),
+    "vgx_scan_registration_score_poses": (C.c_int, [vp, C.c_int32, f32p, f64p, i64p, i64p, i64p]),
+    "vgx_scan_registration_localize": (C.c_int, [vp, C.c_int32, f32p, C.POINTER(PoseGraphOptions), i32p, f32p, f64p,
+                                                 C.POINTER(ScanRegistrationSummary)]),
     "vgx_view_config_default": (None, [C.POINTER(ViewConfig)]),
     "vgx_view_config_check": (C.c_int, [C.POINTER(ViewConfig)]),
     "vgx_view_create": (C.c_int, [vp, C.POINTER(ViewConfig), C.POINTER(vp)]),
@@ -2450,10 +2462,71 @@ class ScanRegistration:
         self.ctx.check(self.ctx.lib.vgx_scan_registration_history(self.h, n.value, arr, None))
         return [{name: getattr(arr[k], name) for name, _ in PoseGraphIteration._fields_} for k in range(n.value)]
 
+    # ---- scan localisation (vgx_scan_registration_*_map, _score_poses, _localize): posed finished submaps ----
+    def set_map(self, submaps, poses=None, config=None):
+        """submaps: capi.Submap handles (at most 64, none clears the map); poses T_M_S [n][7]; config: scan_map_config(...)"""
+        n = len(submaps)
+        hs = (vp * max(n, 1))(*[sm.h for sm in submaps])
+        T = _f32(poses if n else np.zeros((0, 7))).reshape(-1, 7)
+        if len(T) != n:
+            raise ValueError("one pose per submap")
+        self.ctx.check(self.ctx.lib.vgx_scan_registration_set_map(self.h, None if config is None else C.byref(config), n,
+                                                                  hs if n else None, _ptr(T, f32p) if n else None))
+
+    def evaluate_map(self, T_M_C_prior, delta=(0.0, 0.0, 0.0, 0.0)):
+        """-> (out [15], n_terms, n_points_valid, n_candidates)"""
+        T, d, out = _f32(T_M_C_prior), _f64(delta), np.zeros(15)
+        nt, nv, nc = C.c_int64(), C.c_int64(), C.c_int64()
+        self.ctx.check(self.ctx.lib.vgx_scan_registration_evaluate_map(self.h, _ptr(T, f32p), _ptr(d, f64p), _ptr(out, f64p),
+                                                                       C.byref(nt), C.byref(nv), C.byref(nc)))
+        return out, nt.value, nv.value, nc.value
+
+    def refine_map(self, T_M_C_prior, options=None, **kw):
+        """-> (T_refined [7] f32, usable, delta [4], summary dict); keywords override the default pose-graph options"""
+        opts = options if options is not None else pose_graph_options(**kw)
+        T, out, delta, s = _f32(T_M_C_prior), np.zeros(7, np.float32), np.zeros(4), ScanRegistrationSummary()
+        self.ctx.check(self.ctx.lib.vgx_scan_registration_refine_map(self.h, _ptr(T, f32p), C.byref(opts), _ptr(out, f32p),
+                                                                     _ptr(delta, f64p), C.byref(s)))
+        d = s.as_dict()
+        d["termination"] = TERMINATION_NAMES[s.termination_reason]
+        return out, bool(s.usable), delta, d
+
+    def score_poses(self, poses):
+        """poses T_M_C [m][7] -> (cost [m] f64, n_terms [m], n_points_valid [m], n_candidates [m]) at delta = 0"""
+        T = _f32(poses).reshape(-1, 7)
+        m = len(T)
+        cost = np.zeros(m)
+        counts = [np.zeros(m, np.int64) for _ in range(3)]
+        self.ctx.check(self.ctx.lib.vgx_scan_registration_score_poses(self.h, m, _ptr(T, f32p) if m else None, _ptr(cost, f64p),
+                                                                      *[_ptr(c, i64p) for c in counts]))
+        return (cost, *counts)
+
+    def localize(self, poses, options=None, **kw):
+        """-> (best_index, T_refined [7] f32, usable, delta [4], summary dict): the hypotheses scored, the best one refined"""
+        opts = options if options is not None else pose_graph_options(**kw)
+        T = _f32(poses).reshape(-1, 7)
+        best, out, delta, s = C.c_int32(), np.zeros(7, np.float32), np.zeros(4), ScanRegistrationSummary()
+        self.ctx.check(self.ctx.lib.vgx_scan_registration_localize(self.h, len(T), _ptr(T, f32p) if len(T) else None, C.byref(opts),
+                                                                   C.byref(best), _ptr(out, f32p), _ptr(delta, f64p), C.byref(s)))
+        d = s.as_dict()
+        d["termination"] = TERMINATION_NAMES[s.termination_reason]
+        return best.value, out, bool(s.usable), delta, d
+
     def destroy(self):
         if self.h:
             self.ctx.lib.vgx_scan_registration_destroy(self.h)
             self.h = None
+
+
+def scan_map_config(**kw):
+    """vgx_scan_map_config: the defaults and fields overridden by keyword; layer takes "esdf" / "tsdf" too"""
+    cfg = ScanMapConfig()
+    load().vgx_scan_map_config_default(C.byref(cfg))
+    for k, v in kw.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(k)
+        setattr(cfg, k, {"esdf": EVAL_LAYER_ESDF, "tsdf": EVAL_LAYER_TSDF}.get(v, v) if k == "layer" else v)
+    return cfg
 
 
 def view_config(s_max, min_step, unknown_step, max_bracket, **kw):
