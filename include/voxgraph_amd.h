@@ -2326,7 +2326,10 @@ VGX_API int vgx_block_spd_solve_many(vgx_ctx ctx, int32_t n_block_rows, int32_t 
  * A point is a CANDIDATE when its index is a multiple of point_stride and |p_C|^2 = (x x + y y) + z z lies in
  * [min_range_m^2, max_range_m^2] (f32; a NaN fails).  A candidate is USABLE when |p_S_a * block_size_inv| < 2^30 on
  * every axis (so every non-finite point is skipped), the interpolation is valid and |D| < max_abs_distance_m (the
- * clamped free-space plateau has no gradient and says nothing about the pose).
+ * clamped free-space plateau has no gradient and says nothing about the pose).  SPECIAL VOXEL VALUES fall under these
+ * comparisons as IEEE decides them: a weight that is NaN, -0.0, +0.0 or negative is not > 0 (the voxel is unobserved), a
+ * denormal or +inf weight is; a NaN or infinite D -- any NaN or +-inf among the 8 distances -- fails |D| <
+ * max_abs_distance_m and the point has no term; -0.0 and denormal distances are ordinary values (nothing is flushed).
  *
  * THE ORDER CONTRACT.  Per usable point 15 f64 terms: r r; J_k r (k = 0..3); J_k J_l for k <= l in the order 00 01 02
  * 03 11 12 13 22 23 33 -- products of two f32 values widened to f64, exact.  Only the additions round:
@@ -2426,6 +2429,8 @@ VGX_API int vgx_scan_registration_history(vgx_scan_registration reg, int32_t cap
  *   p_S = T_S_M,k p_M                          Eigen _transformVector, then + t
  *   the term is USABLE iff |p_S,a * block_size_inv| < 2^30 on every axis, all 8 neighbours exist in the submap's block
  *   table and are valid (ESDF observed != 0, TSDF weight > 0), and |r| < max_abs_distance_m, r the trilinear distance
+ *   (special voxel values as in "Scan-to-map registration": a NaN, zero of either sign or negative TSDF weight is not
+ *   > 0, a denormal or +inf one is; a NaN or infinite r has no term; -0.0 and denormal distances are ordinary values)
  *   g_S = (dD/d dl) * voxel_size_inv           the exact derivative of the interpolant, as there
  *   g_M = R(T_M_S,k) g_S                       the rotation alone (_transformVector), not renormalised
  *   J   = (g_Mx, g_My, g_Mz, g_Mx ((-s) qx - c qy) + g_My (c qx - s qy))
@@ -2521,6 +2526,12 @@ VGX_API int vgx_scan_registration_localize(vgx_scan_registration reg, int32_t n_
  * points = dir_a * s_hit in the SENSOR frame (unit pinhole rays: points[..][2] is the z-depth).  Without a hit range and
  * points are +0: the integrators drop such points while min_ray_length_m > 0, and scan-to-map registration needs
  * min_range_m > 0 to do the same.  n_samples counts the positions sampled (step 2), valid or not, plus the one at the hit.
+ * SPECIAL VOXEL VALUES fall under these comparisons as IEEE decides them.  A weight that is NaN, -0.0, +0.0 or negative
+ * is not > 0 (the sample is invalid), a denormal or +inf weight is (the interpolated weight at the hit is then inf or NaN
+ * by the interpolant's arithmetic).  A NaN D is "not (D > 0)": bracketed it is a hit whose range and points are NaN and
+ * whose status is HIT_UNSAMPLED (the sample at a NaN position is invalid), unbracketed it is INSIDE.  D = +inf makes
+ * s = +inf: MISS.  D = -inf bracketed gives s_hit = s0 exactly, the hit at the last positive sample; unbracketed INSIDE.
+ * -0.0 is "not (D > 0)"; a denormal D > 0 is a positive distance (nothing is flushed).
  *
  * s_max / min(min_step, unknown_step) <= 65536 bounds the loop and keeps every increment far above one ulp of s.
  * s_max, min_step, unknown_step and max_bracket have NO default (0 is refused); a starting point is the reach wanted,

@@ -277,14 +277,17 @@ def eval_partner(rng, sm, vs, vps):
     return synth.SubmapData(float(F(vs)), vps, np.ascontiguousarray(pbi), td, tw, ed, eo, np.zeros(4))
 
 
-def compare(name, got, want):
+def compare(name, got, want, nan_equal=False):
     """exact comparison of two arrays (or tuples of arrays, None allowed) by their bytes: None when equal, else a
-    message with the shapes or the first differing flat indices (of 4-byte words where the item size allows)"""
+    message with the shapes or the first differing flat indices (of 4-byte words where the item size allows).
+    nan_equal (off by default; the layer readers' fuzzer): in a float array a NaN equals a NaN whatever its sign and
+    payload -- a kernel and x86 numpy give different default NaNs for inf - inf -- and nothing else changes: -0.0 is
+    not +0.0, a NaN is no number."""
     if isinstance(want, (tuple, list)):
         if len(got) != len(want):
             return f"{name}: {len(got)} arrays, want {len(want)}"
         for i, (g, w) in enumerate(zip(got, want)):
-            msg = compare(f"{name}[{i}]", g, w)
+            msg = compare(f"{name}[{i}]", g, w, nan_equal)
             if msg:
                 return msg
         return None
@@ -295,9 +298,14 @@ def compare(name, got, want):
     g, w = np.ascontiguousarray(got), np.ascontiguousarray(want)
     if g.shape != w.shape or g.dtype != w.dtype:
         return f"{name}: shape {g.shape} {g.dtype}, want {w.shape} {w.dtype}"
-    word = np.uint32 if g.dtype.itemsize % 4 == 0 else np.uint8
-    a, b = g.reshape(-1).view(word), w.reshape(-1).view(word)
-    bad = np.flatnonzero(a != b)
+    if nan_equal and g.dtype.kind == "f":
+        word = {4: np.uint32, 8: np.uint64}[g.dtype.itemsize]               # one word per number
+        a, b = g.reshape(-1).view(word), w.reshape(-1).view(word)
+        bad = np.flatnonzero((a != b) & ~(np.isnan(g.reshape(-1)) & np.isnan(w.reshape(-1))))
+    else:
+        word = np.uint32 if g.dtype.itemsize % 4 == 0 else np.uint8
+        a, b = g.reshape(-1).view(word), w.reshape(-1).view(word)
+        bad = np.flatnonzero(a != b)
     if len(bad):
         i = int(bad[0])
         return f"{name}: {len(bad)} of {a.size} words differ, first at {bad[:5].tolist()}: got {a[i]:#x} want {b[i]:#x}"

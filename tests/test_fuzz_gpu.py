@@ -13,6 +13,9 @@ MAP_LAYERS = (36, 300)
 MAP_MESHES = (60, 300)
 # (seeds, first) of the ESDF fuzzer: tests/test_esdf_cpu.py holds the restatement to the queue over exactly these draws
 ESDF = (24, 300)
+# (seeds, first) of the layer readers' fuzzer: tests/test_fuzz_readers_cpu.py checks the generator over exactly these.  The
+# count is the largest whose restatement side stays within 1.5 times that of MAP_LAYERS (profiles/README.md)
+READERS = (144, 300)
 
 
 def _run(script, seeds, first):
@@ -82,6 +85,13 @@ def test_map_meshes_random_scenes_bit_identical_to_the_restatements():
     """the combined, submap and separated meshes at the drawn min_weight, each welded at two thresholds from 1e-10 to
     four times the scene's extent (thousands of soup vertices into one key)"""
     assert _run("fuzz_map_meshes", *MAP_MESHES) == 0
+
+
+def test_layer_readers_random_scenes_bit_identical_to_the_restatements():
+    """views of the live layer and of a finished submap (both launches), scan-to-map registration (evaluate, refine) and
+    scan localisation (evaluate_map, score_poses, localize) on scenes far from the origin, with grid-aligned poses, empty
+    and duplicated submaps, and voxels that hold NaN, +-inf, -0.0, denormals and negative weights; a NaN equals a NaN"""
+    assert _run("fuzz_layer_readers", *READERS) == 0
 
 
 def test_esdf_random_submaps_bit_identical_to_the_restatement_and_close_to_the_queue():

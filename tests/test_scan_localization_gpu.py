@@ -418,3 +418,56 @@ def test_refusals(ctx, random_scene):
     for x in (reg, foreign, mixed):
         x.destroy()
     other.close()
+
+
+def test_special_voxel_values_fall_under_the_stated_comparisons(ctx):
+    """One point in the cube CELL of tests/special_voxel_scene.py's layer (D = Z0 - z, r = 0.0275 there) as a finished submap
+    under the identity pose, the same field in its ESDF; a special value planted into CELL.  The expectations are IEEE's
+    under the header's comparisons -- "TSDF weight > 0", "ESDF observed != 0", "|r| < max_abs_distance_m" -- written down
+    by hand.  (An ESDF's validity is a byte: it has no special values.)"""
+    from tests import special_voxel_scene as Z
+    bi, d, w = Z.layer()
+    seen = np.ones(d.shape, np.uint8)
+    point = np.array([[Z.X, Z.Y, Z.Z_IN]], F)
+    nb7, cell, other = [Z.NEIGHBOUR_7], Z.CELL, [Z.CELL[1]]
+
+    def evaluate(layer, dd=d, ww=w):
+        """(evaluate_map's result, score_poses' result) on a submap with these TSDF arrays, the distance in its ESDF too"""
+        sm = capi.Submap(ctx, 0, Z.VOXEL_SIZE, Z.VPS, bi, dd, ww, dd, seen)
+        reg, _, _ = _reg(ctx, [sm], [IDENTITY], dict(max_abs_distance_m=0.2), layer=layer)
+        reg.set_points(point)
+        got, score = reg.evaluate_map(IDENTITY), reg.score_poses([IDENTITY])
+        reg.destroy()
+        sm.destroy()
+        assert score[0][0] == 0.5 * got[0][0] and (score[1][0], score[2][0], score[3][0]) == got[1:]
+        return got
+
+    def no_term(got):
+        return got[1:] == (0, 0, 1) and not _bits(got[0]).any()                   # a candidate without a term; every sum +0
+
+    for layer in ("tsdf", "esdf"):
+        base = evaluate(layer)
+        assert base[1:] == (1, 1, 1) and abs(base[0][0] - 0.0275 ** 2) < 1e-6 and abs(base[0][3] + 0.0275) < 1e-4
+        # distance NaN, +inf, -inf (in neighbour 7 they reach r as they are; in another the inf meets its negation: NaN)
+        # and 3e38: |r| < max_abs_distance_m fails: no term
+        for where, value in ((nb7, np.nan), (nb7, np.inf), (nb7, -np.inf), (other, np.inf), (other, -np.inf), (nb7, 3e38), (cell, 3e38)):
+            assert no_term(evaluate(layer, Z.plant(bi, d, where, value))), (layer, value)
+        # -0.0, 0.0 and 1e-40 in one neighbour are ordinary values: the same bits from all three, not the unplanted ones
+        sums = [evaluate(layer, Z.plant(bi, d, nb7, value)) for value in (-0.0, 0.0, 1e-40)]
+        assert all(g[1:] == (1, 1, 1) for g in sums) and len({g[0].tobytes() for g in sums}) == 1 and sums[0][0][0] != base[0][0]
+        # all 8 neighbours -0.0: r is a zero, |r| < max: a term, every sum a zero
+        got = evaluate(layer, Z.plant(bi, d, cell, -0.0))
+        assert got[1:] == (1, 1, 1) and not got[0].any()
+        # all 8 neighbours 1e-40: r = 1e-40 exactly, a residual like any other: rho = r r, exact in f64 -- a device that
+        # flushed denormals would give 0
+        got = evaluate(layer, Z.plant(bi, d, cell, 1e-40))
+        assert got[1:] == (1, 1, 1) and got[0][0] == float(F(1e-40)) ** 2 > 0 and not got[0][1:].any()
+    # TSDF weights: 1e-40 (a denormal) and +inf are > 0, the sums those of weight 1; NaN, -0.0, 0.0, -1 are not: no term.
+    # The ESDF reads `observed`, so there the same weights change nothing
+    base = evaluate("tsdf")
+    for value in Z.WEIGHTS_OBSERVED:
+        got = evaluate("tsdf", ww=Z.plant(bi, w, nb7, value))
+        assert got[1:] == (1, 1, 1) and np.array_equal(_bits(got[0]), _bits(base[0])), value
+    for value in Z.WEIGHTS_UNOBSERVED:
+        assert no_term(evaluate("tsdf", ww=Z.plant(bi, w, nb7, value))), value
+        assert evaluate("esdf", ww=Z.plant(bi, w, nb7, value))[1:] == (1, 1, 1)

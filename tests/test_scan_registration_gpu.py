@@ -325,3 +325,49 @@ def test_refusals(ctx, room):
     for x in (reg, foreign, foreign_scan):
         x.destroy()
     other.close()
+
+
+def test_special_voxel_values_fall_under_the_stated_comparisons(ctx):
+    """One point in the cube CELL of tests/special_voxel_scene.py's layer (D = Z0 - z, r = 0.0275 there), identity prior,
+    no correction; a special value planted into CELL.  The expectations are IEEE's under the header's comparisons --
+    "every weight is > 0", "|D| < max_abs_distance_m" -- written down by hand."""
+    from tests import special_voxel_scene as Z
+    bi, d, w = Z.layer()
+    layer = capi.TsdfLayer(ctx, Z.VOXEL_SIZE, Z.VPS)
+    reg = capi.ScanRegistration(ctx, capi.scan_registration_config(0.2))
+    reg.set_points(np.array([[Z.X, Z.Y, Z.Z_IN]], F))
+    identity = np.array([1, 0, 0, 0, 0, 0, 0], F)
+
+    def evaluate(dd=d, ww=w):
+        layer.upload(bi, dd, ww)
+        return reg.evaluate(layer, identity)
+
+    def no_term(got):
+        return got[1:] == (0, 1) and not _bits(got[0]).any()                      # a candidate, not usable; every sum +0
+
+    nb7, cell, other = [Z.NEIGHBOUR_7], Z.CELL, [Z.CELL[1]]
+    base = evaluate()
+    assert base[1:] == (1, 1) and abs(base[0][0] - 0.0275 ** 2) < 1e-6 and abs(base[0][3] + 0.0275) < 1e-4      # sum r r, sum J_z r
+    # weight 1e-40 (a denormal) and +inf are > 0: the voxel is observed, the point usable, the sums those of weight 1
+    for value in Z.WEIGHTS_OBSERVED:
+        got = evaluate(ww=Z.plant(bi, w, nb7, value))
+        assert got[1:] == (1, 1) and np.array_equal(_bits(got[0]), _bits(base[0])), value
+    # weight NaN, -0.0, 0.0, -1 are not > 0: not observed, the point not usable
+    for value in Z.WEIGHTS_UNOBSERVED:
+        assert no_term(evaluate(ww=Z.plant(bi, w, nb7, value))), value
+    # distance NaN, +inf, -inf (in neighbour 7 they reach r as they are; in another the inf meets its negation: NaN) and
+    # 3e38: |r| < max_abs_distance_m fails for an infinity, for a NaN and for 1e37: no term
+    for where, value in ((nb7, np.nan), (nb7, np.inf), (nb7, -np.inf), (other, np.inf), (other, -np.inf), (nb7, 3e38), (cell, 3e38)):
+        assert no_term(evaluate(Z.plant(bi, d, where, value))), value
+    # -0.0, 0.0 and 1e-40 in one neighbour are ordinary values: the same bits from all three, not the unplanted ones
+    sums = [evaluate(Z.plant(bi, d, nb7, value)) for value in (-0.0, 0.0, 1e-40)]
+    assert all(g[1:] == (1, 1) for g in sums) and len({g[0].tobytes() for g in sums}) == 1 and sums[0][0][0] != base[0][0]
+    # all 8 neighbours -0.0: r is a zero, |r| < max: usable, every term a zero
+    got = evaluate(Z.plant(bi, d, cell, -0.0))
+    assert got[1:] == (1, 1) and not got[0].any()
+    # all 8 neighbours 1e-40: r = 1e-40 exactly (every coefficient but c0 is x - x = 0), a residual like any other: its
+    # square, exact in f64, is the sum -- a device that flushed denormals would give 0
+    got = evaluate(Z.plant(bi, d, cell, 1e-40))
+    assert got[1:] == (1, 1) and got[0][0] == float(F(1e-40)) ** 2 > 0 and not got[0][1:].any()
+    reg.destroy()
+    layer.destroy()

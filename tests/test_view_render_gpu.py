@@ -5,6 +5,7 @@ with both ray mappings and every flag; the layer the reproducible integrator bui
 scan; the submap entry; colours; the points handed on by device pointer to scan registration and to an integrator; and
 every refusal."""
 import math
+import types
 
 import numpy as np
 import pytest
@@ -322,3 +323,80 @@ def test_refusals(ctx, random_scene):
     for x in (empty, view, sm, foreign_sm, foreign_view, foreign_layer):
         x.destroy()
     other.close()
+
+
+def test_special_voxel_values_fall_under_the_stated_comparisons(ctx):
+    """One ray straight up through tests/special_voxel_scene.py's layer (D = Z0 - z), a special value planted into the
+    cube CELL on its way.  The expectations are IEEE's under the header's rules, written down by hand:
+    s_min puts the first sample in the cube below CELL (D = 0.11 > 0: have, s0 = s_min), the second falls into CELL."""
+    from tests import special_voxel_scene as Z
+    bi, d, w = Z.layer()
+    T = np.array([1, 0, 0, 0, Z.X, Z.Y, -0.7], F)
+    up = np.array([[0, 0, 1]], F)
+    cfg = dict(s_min=0.5, s_max=1.4, min_step=0.025, unknown_step=0.1, max_bracket=0.2)
+    bracketed = capi.View(ctx, capi.view_config(flags=capi.VIEW_ALL, **cfg))
+    unbracketed = capi.View(ctx, capi.view_config(flags=capi.VIEW_ALL, **dict(cfg, s_min=0.58)))   # the first sample in CELL
+    layer = capi.TsdfLayer(ctx, Z.VOXEL_SIZE, Z.VPS)
+
+    def render(dd=d, ww=w, view=bracketed):
+        layer.upload(bi, dd, ww)
+        got = layer.render_view(view, T, up).download()
+        return types.SimpleNamespace(status=int(got.status[0]), range=got.range[0], point=got.points[0], gradient=got.gradient[0],
+                                     weight=got.weight[0], rgba=got.rgba[0], n_samples=int(got.n_samples[0]))
+
+    def zero_bits(*arrays):
+        return all(not np.ascontiguousarray(a).view(np.uint8).any() for a in arrays)
+
+    nb7, cell, other = [Z.NEIGHBOUR_7], Z.CELL, [Z.CELL[1]]        # (CELL[1]: x 1, y 2, z 7 -- not in the cube below either)
+    # nothing planted: samples at z = -0.2, -0.1175, -0.0925, -0.0675 (the first D < 0), the hit at z = Z0
+    base = render()
+    assert base.status == capi.VIEW_HIT and abs(base.range - 0.61) < 1e-3 and base.n_samples == 5 and base.weight == 1
+    assert np.allclose(base.gradient, [0, 0, -1], atol=1e-3) and np.allclose(base.point, [0, 0, base.range])
+    # weight 1e-40 (a denormal) and +inf are > 0: observed, the same march; the interpolated weight is the interpolant's
+    for value in Z.WEIGHTS_OBSERVED:
+        got = render(ww=Z.plant(bi, w, nb7, value))
+        assert got.status == capi.VIEW_HIT and got.range.tobytes() == base.range.tobytes() and got.n_samples == 5, value
+        assert (0 < got.weight < 1) if np.isfinite(value) else not np.isfinite(got.weight), (value, got.weight)
+    # weight NaN, -0.0, 0.0, -1 are not > 0: every sample in CELL and in the cube above it (which holds neighbour 7 too) is
+    # invalid and advances by unknown_step -- z = -0.1175, -0.0175 -- and the next valid one, z = 0.0825 with D < 0, lies
+    # 0.2825 > max_bracket behind s0: INSIDE
+    for value in Z.WEIGHTS_UNOBSERVED:
+        got = render(ww=Z.plant(bi, w, nb7, value))
+        assert got.status == capi.VIEW_INSIDE and got.n_samples == 4 and zero_bits(got.range, got.point, got.gradient, got.weight, got.rgba), value
+    # distance NaN under valid weights is "not (D > 0)".  Bracketed: a hit whose range is s0 + gap * (D0 / (D0 - NaN)) = NaN;
+    # the sample at a NaN position is invalid: HIT_UNSAMPLED, gradient / weight / rgba +0, the point dir * NaN.
+    # An inf in neighbour 1 meets its own negation in the coefficients (c3 = +-inf, c5 = -+inf): the same NaN.
+    for where, value in ((nb7, np.nan), (other, np.inf), (other, -np.inf)):
+        got = render(Z.plant(bi, d, where, value))
+        assert got.status == capi.VIEW_HIT_UNSAMPLED and np.isnan(got.range) and np.isnan(got.point).all() and got.n_samples == 3, value
+        assert zero_bits(got.gradient, got.weight, got.rgba)
+        # unbracketed (no positive sample before it): INSIDE
+        got = render(Z.plant(bi, d, where, value), view=unbracketed)
+        assert got.status == capi.VIEW_INSIDE and got.n_samples == 1 and zero_bits(got.range, got.point, got.gradient, got.weight, got.rgba)
+    # distance +inf in neighbour 7 reaches D as +inf > 0: the step is inf, s = inf, and !(s <= s_max): MISS
+    got = render(Z.plant(bi, d, nb7, np.inf))
+    assert got.status == capi.VIEW_MISS and got.n_samples == 2 and zero_bits(got.range, got.point, got.gradient, got.weight, got.rgba)
+    # distance -inf there reaches D as -inf, not > 0 and bracketed: s_hit = s0 + gap * (D0 / (D0 + inf)) = s0 + gap * 0 = s0
+    # exactly -- the hit is reported AT the last positive sample, whose cube is clean: HIT, the field's gradient
+    got = render(Z.plant(bi, d, nb7, -np.inf))
+    assert got.status == capi.VIEW_HIT and got.range.tobytes() == F(0.5).tobytes() and got.n_samples == 3
+    assert np.allclose(got.gradient, [0, 0, -1], atol=1e-3) and got.weight == 1
+    # ... and unbracketed it is INSIDE, like every D that is not > 0
+    assert render(Z.plant(bi, d, nb7, -np.inf), view=unbracketed).status == capi.VIEW_INSIDE
+    # -0.0, 0.0 and 1e-40 in one neighbour are ordinary values: they flow through (added to a non-zero partial sum the
+    # three give the same bits), the surface moves within CELL
+    ranges = [render(Z.plant(bi, d, nb7, value)) for value in (-0.0, 0.0, 1e-40)]
+    assert all(g.status == capi.VIEW_HIT and 0.55 < g.range < 0.65 for g in ranges)
+    assert len({g.range.tobytes() for g in ranges}) == 1 and ranges[0].range != base.range
+    # all 8 neighbours -0.0 (four of them are the upper face of the cube below: D0 = 0.08 there, the second sample at
+    # z = -0.14): D is a zero, and a zero is "not > 0" whatever its sign: the hit at the second sample itself,
+    # s_hit = s0 + gap * (D0 / (D0 - 0)) = s0 + gap
+    got = render(Z.plant(bi, d, cell, -0.0))
+    assert got.status == capi.VIEW_HIT and got.n_samples == 3 and abs(got.range - 0.56) < 1e-3
+    # all 8 neighbours 1e-40: D = 1e-40 > 0, a positive distance like any other (a device that flushed denormals would see
+    # the zero above).  The march goes on by min_step through CELL -- z = -0.14, -0.115, -0.09, -0.065 -- to z = -0.04 in the
+    # cube above, D < 0; the hit lies a hair (1e-40 / 0.014 of the gap) past the last of them, z = -0.065
+    got = render(Z.plant(bi, d, cell, 1e-40))
+    assert got.status == capi.VIEW_HIT and got.n_samples == 7 and abs(got.range - 0.635) < 1e-3
+    for x in (bracketed, unbracketed, layer):
+        x.destroy()
