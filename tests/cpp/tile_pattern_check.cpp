@@ -1,6 +1,7 @@
 // The tile structure code (voxgraph_amd/csrc/vgx_tile_pattern.h) in a program of its own, to be built with
 // -fsanitize=address,undefined and no HIP (tests/test_pose_graph_sparse_cpu.py): the pattern scenes of the CPU tests under
-// the three orderings, the invariants of the lists, and malformed input.  Prints "tile_pattern_check ok" and exits 0.
+// the three orderings, the invariants of the lists, malformed input, and a seeded sweep of a few thousand random structures of
+// the fuzzer's families (profiles/fuzz_pose_graph_scene.py).  Prints "tile_pattern_check ok" and exits 0.
 #include <cstdio>
 #include <cstdlib>
 #include <numeric>
@@ -33,8 +34,14 @@ static void check_structure(int32_t n, const std::vector<int32_t>& pairs, int32_
     const int32_t a = S.position[(size_t)pairs[2 * p]] / kNodesPerTile, b = S.position[(size_t)pairs[2 * p + 1]] / kNodesPerTile;
     CHECK(S.l_tile(std::max(a, b), std::min(a, b)) >= 0 && h_tile(S, a, b) >= 0 && h_tile(S, b, a) >= 0);
   }
+  const int32_t n_tiles = (int32_t)S.l_row.size();
   for (const TileTriple& t : S.triples) {                                      // closed under the fill rule
-    CHECK(t.target >= 0 && t.target < (int32_t)S.l_row.size());
+    // (a fill tile missing from the list would make l_tile answer -1: the kernel's target would lie before the array)
+    CHECK(t.target >= 0 && t.target < n_tiles && t.source_i >= 0 && t.source_i < n_tiles && t.source_j >= 0 && t.source_j < n_tiles);
+    CHECK(S.l_tile(S.l_row[(size_t)t.source_i], S.l_row[(size_t)t.source_j]) == t.target);
+    CHECK(t.rows == (S.rows_of(S.l_row[(size_t)t.source_i]) | S.rows_of(S.l_row[(size_t)t.source_j]) << 8 |
+                     (S.l_row[(size_t)t.source_i] == S.l_row[(size_t)t.source_j]) << 16));
+    CHECK((t.rows & 255) >= 4 && ((t.rows >> 8) & 255) >= 4 && (t.rows & 255) <= kTile && (t.rows & 3) == 0);
     CHECK(S.l_row[(size_t)t.target] == S.l_row[(size_t)t.source_i] && S.l_col[(size_t)t.target] == S.l_row[(size_t)t.source_j]);
     CHECK(S.l_col[(size_t)t.source_i] == S.l_col[(size_t)t.source_j] && S.l_col[(size_t)t.source_i] < S.l_col[(size_t)t.target]);
     CHECK((t.rows & 255) == S.rows_of(S.l_row[(size_t)t.target]) && ((t.rows >> 8) & 255) == S.rows_of(S.l_col[(size_t)t.target]));
@@ -44,6 +51,91 @@ static void check_structure(int32_t n, const std::vector<int32_t>& pairs, int32_
   size_t from_h = 0;
   for (int32_t v : S.l_from_h) from_h += v >= 0;
   CHECK(2 * from_h - (size_t)nT == S.h_col.size());
+}
+
+// ---- the seeded sweep: a small generator of its own, so that every platform draws the same structures ----
+struct Lcg {
+  uint64_t state;
+  uint32_t next() {
+    state = state * 6364136223846793005ull + 1442695040888963407ull;
+    return (uint32_t)(state >> 33);
+  }
+  int32_t below(int32_t n) { return (int32_t)(next() % (uint32_t)n); }        // n >= 1
+  bool chance(int percent) { return below(100) < percent; }
+};
+
+// family 0 .. 8: empty, chain, chain with second neighbours, random pairs, hub, arrow, band with closures, components with
+// isolated nodes, a chain relabelled by a random permutation -- in either direction, then repeated pairs and a node with itself
+static std::vector<int32_t> random_pairs(Lcg& r, int family, int32_t n) {
+  std::vector<int32_t> p;
+  auto join = [&](int32_t a, int32_t b) {
+    if (r.chance(50)) std::swap(a, b);
+    p.insert(p.end(), {a, b});
+  };
+  if (n >= 2) {
+    if (family == 1 || family == 2) {
+      for (int32_t i = 0; i + 1 < n; ++i) join(i + 1, i);
+      if (family == 2)
+        for (int32_t i = 0; i + 2 < n; ++i) join(i + 2, i);
+    } else if (family == 3) {
+      const int32_t count = n * (1 + r.below(8)) / 2;
+      for (int32_t k = 0; k < count; ++k) join(r.below(n), r.below(n));        // (a node with itself among them)
+    } else if (family == 4) {
+      const int32_t at[4] = {0, n / 2, n - 1, r.below(n)};
+      const int32_t hub = at[r.below(4)];
+      const int percent = 30 + r.below(60);
+      for (int32_t i = 0; i < n; ++i)
+        if (i != hub && r.chance(percent)) join(hub, i);
+      if (r.chance(50))
+        for (int32_t i = 0; i + 1 < n; ++i) join(i + 1, i);
+    } else if (family == 5) {
+      for (int32_t i = 1; i < n; ++i) join(i, 0);
+    } else if (family == 6) {
+      const int32_t width = 1 + r.below(3);
+      for (int32_t w = 1; w <= width; ++w)
+        for (int32_t i = 0; i + w < n; ++i) join(i + w, i);
+      for (int32_t k = r.below(4); k >= 0; --k) join(r.below(n), r.below(n));
+    } else if (family == 7) {
+      int32_t last = -1;
+      for (int32_t i = 0; i < n; ++i) {
+        if (r.chance(4)) last = -1;                                             // a new component starts
+        if (r.chance(15)) continue;                                             // an isolated node
+        if (last >= 0) join(last, i);
+        last = i;
+      }
+    } else if (family == 8) {
+      std::vector<int32_t> label((size_t)n);
+      std::iota(label.begin(), label.end(), 0);
+      for (int32_t i = n - 1; i > 0; --i) std::swap(label[(size_t)i], label[(size_t)r.below(i + 1)]);
+      for (int32_t i = 0; i + 1 < n; ++i) join(label[(size_t)i + 1], label[(size_t)i]);
+    }
+  }
+  if (!p.empty() && r.chance(50))
+    for (int k = 0; k < 3; ++k) {
+      const size_t q = 2 * (size_t)r.below((int32_t)(p.size() / 2));
+      p.insert(p.end(), {p[q], p[q + 1]});                                      // a repeated pair
+    }
+  if (r.chance(30)) {
+    const int32_t v = r.below(n);
+    p.insert(p.end(), {v, v});                                                  // a node with itself
+  }
+  return p;
+}
+
+static void sweep(int n_structures) {
+  Lcg r{20240607};
+  const int32_t sizes[] = {1, 2, 15, 16, 17, 31, 32, 33, 48, 63, 64, 65, 100, 130};
+  for (int k = 0; k < n_structures; ++k) {
+    const int family = k % 9;
+    const int32_t n = (k % 12 == 11) ? 280 + r.below(51) : sizes[r.below((int32_t)(sizeof(sizes) / sizeof(sizes[0])))];
+    const std::vector<int32_t> pairs = random_pairs(r, family, n);
+    std::vector<int32_t> given((size_t)n);
+    std::iota(given.begin(), given.end(), 0);
+    for (int32_t i = n - 1; i > 0; --i) std::swap(given[(size_t)i], given[(size_t)r.below(i + 1)]);
+    check_structure(n, pairs, kOrderNatural, nullptr);
+    check_structure(n, pairs, kOrderRcm, nullptr);
+    check_structure(n, pairs, kOrderGiven, given.data());
+  }
 }
 
 int main() {
@@ -74,6 +166,7 @@ int main() {
     check_structure(n, scene.second, kOrderRcm, nullptr);
     check_structure(n, scene.second, kOrderGiven, given.data());
   }
+  sweep(3000);
   // malformed input is refused, not read past
   TileStructure S;
   const int32_t repeat[4] = {0, 1, 1, 3}, beyond[4] = {0, 1, 2, 4}, good[4] = {3, 1, 0, 2};

@@ -144,19 +144,34 @@ def assemble(n_nodes, constant, pairs, fused, edges, terms, swap_steps_2_and_3=F
     return H, g
 
 
+_CHOLESKY_STRIP = 64
+
+
 def cholesky(A, sum_products_first=False):
     """Unblocked right-looking Cholesky of the lower triangle of A -> L (zeros above the diagonal)."""
     A = np.array(A, np.float64)
     n = A.shape[0]
     if sum_products_first:                     # the WRONG order of the mutation check: per 64-wide panel, products summed first
         return _cholesky_summed(A)
-    for k in range(n):
-        akk = A[k, k]
-        if not (akk > 0.0) or math.isinf(akk):
-            raise NotPositiveDefinite(k)
-        A[k, k] = math.sqrt(akk)
-        A[k + 1:, k] = A[k + 1:, k] / A[k, k]
-        A[k + 1:, k + 1:] -= np.outer(A[k + 1:, k], A[k + 1:, k])
+    # `A[k + 1:, k + 1:] -= outer(column k, column k)` for k ascending, in an order of loops that keeps a strip of columns in
+    # the cache: a strip first takes the products of every finished column left of it, k ascending, then its own columns'
+    # as they are finished.  Every element below the diagonal sees the statement's operations in the statement's order --
+    # per k one rounded product, then one rounded difference -- and a bad pivot is still the first in ascending k; what the
+    # strips skip lies above the diagonal and is dropped at the end.
+    products = np.empty((n, min(n, _CHOLESKY_STRIP)))
+    for c0 in range(0, n, _CHOLESKY_STRIP):
+        c1 = min(n, c0 + _CHOLESKY_STRIP)
+        strip, p = A[c0:, c0:c1], products[:n - c0, :c1 - c0]
+        for k in range(c0):
+            np.multiply(A[c0:, k, None], A[None, c0:c1, k], out=p)
+            np.subtract(strip, p, out=strip)
+        for k in range(c0, c1):
+            akk = A[k, k]
+            if not (akk > 0.0) or math.isinf(akk):
+                raise NotPositiveDefinite(k)
+            A[k, k] = math.sqrt(akk)
+            A[k + 1:, k] = A[k + 1:, k] / A[k, k]
+            A[k + 1:, k + 1:c1] -= np.outer(A[k + 1:, k], A[k + 1:c1, k])
     return np.tril(A)
 
 

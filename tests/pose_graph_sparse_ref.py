@@ -188,14 +188,22 @@ def matvec(h_tiles, n, s):
 
 
 # ---- the solve (edges only) -----------------------------------------------------------------------------------------
-def assemble(n_nodes, constant, edges, terms, order):
+def joined_free_pairs(pos, reg_pairs, edges):
+    """the free-node pairs of the block graph: the registration constraints, then the edges"""
+    joined = [(int(a), int(b)) for a, b in reg_pairs] + [(e[0], e[1]) for e in edges]
+    return [(pos[a], pos[b]) for a, b in joined if pos[a] >= 0 and pos[b] >= 0]
+
+
+def assemble(n_nodes, constant, edges, terms, order, reg_pairs=(), fused=None):
     """-> (H's tiles of P H P^T, g in ascending node order, H's key set, L's tile list): every 4x4 block 0.0 plus its
-    contributions in the contract's order (edges in list order: aa, bb, ab, ab^T)"""
+    contributions in the contract's order (the fused buffer's diagonal blocks and gradients per node, its off-diagonal
+    blocks per constraint (a, b) and (b, a)^T, where there are registration constraints; then the edges in list order:
+    aa, bb, ab, ab^T)"""
     pos, nfree = ref.free_positions(n_nodes, constant)
     position = [0] * nfree
     for p, node in enumerate(order):
         position[node] = p
-    pairs = [(pos[e[0]], pos[e[1]]) for e in edges if pos[e[0]] >= 0 and pos[e[1]] >= 0]
+    pairs = joined_free_pairs(pos, reg_pairs, edges)
     h_keys, l_tiles = tile_pattern(nfree, pairs, order)
     H = {key: np.zeros((TILE, TILE)) for key in h_keys}
     g = np.zeros(4 * nfree)
@@ -205,6 +213,17 @@ def assemble(n_nodes, constant, edges, terms, order):
             r, c = 4 * position[pos[a]], 4 * position[pos[b]]
             H[(r // TILE, c // TILE)][r % TILE:r % TILE + 4, c % TILE:c % TILE + 4] += block
 
+    if fused is not None:
+        n = n_nodes
+        diag = np.asarray(fused[1 + 4 * n:1 + 20 * n]).reshape(n, 4, 4)
+        for i in range(n):
+            add(i, i, diag[i])
+            if pos[i] >= 0:
+                g[4 * pos[i]:4 * pos[i] + 4] += fused[1 + 4 * i:5 + 4 * i]
+        off = np.asarray(fused[1 + 20 * n:1 + 20 * n + 16 * len(reg_pairs)]).reshape(-1, 4, 4)
+        for c, (a, b) in enumerate(reg_pairs):
+            add(a, b, off[c])
+            add(b, a, off[c].T)
     for e, t in zip(edges, terms):
         a, b = e[0], e[1]
         _, ga, gb, aa, bb, ab = t
@@ -232,30 +251,39 @@ def unpermuted(v, order):
 
 def solve(n_nodes, constant, edges, poses0, ordering=NATURAL, given=None, parameter_tolerance=3e-3, function_tolerance=1e-6,
           gradient_tolerance=1e-10, max_num_iterations=50, max_solver_time_in_seconds=4.0, initial_trust_region_radius=1e4,
-          keep=None):
-    """pose_graph_ref.solve's loop over the tiles of P H P^T, edges only -> (poses, summary dict, history).  keep: a dict
-    that receives the order, the tile lists and the last H and g"""
+          keep=None, registration=None):
+    """pose_graph_ref.solve's loop over the tiles of P H P^T -> (poses, summary dict, history).  keep: a dict that receives
+    the order, the tile lists and the last H and g.  registration: what pose_graph_ref.solve takes (None: edges only)"""
+    registration = ref.ZeroRegistration() if registration is None else registration
     t0 = time.perf_counter()
     pos, nfree = ref.free_positions(n_nodes, constant)
     free_vars = [4 * i + k for i in range(n_nodes) if pos[i] >= 0 for k in range(4)]
     nf = 4 * nfree
-    pairs = [(pos[e[0]], pos[e[1]]) for e in edges if pos[e[0]] >= 0 and pos[e[1]] >= 0]
+    pairs = joined_free_pairs(pos, registration.pairs, edges)
     order = make_order(nfree, pairs, ordering, given)
     x = np.array(poses0, np.float64).reshape(n_nodes, 4).copy()
     history = []
 
+    def total(costs, ecost):
+        reg = 0.0
+        for c in costs:
+            reg = reg + float(c)
+        return 0.5 * (reg + ecost)
+
     def full(p):
+        fused, costs = registration.full(p)
         terms = [ref.edge_terms(e, p[e[0]], p[e[1]]) for e in edges]
         ecost = 0.0
         for t in terms:
             ecost = ecost + t[0]
-        return (0.5 * (0.0 + ecost),) + assemble(n_nodes, constant, edges, terms, order)
+        return (total(costs, ecost),) + assemble(n_nodes, constant, edges, terms, order, registration.pairs, fused)
 
     def cost_only(p):
+        costs = registration.cost(p)
         ecost = 0.0
         for e in edges:
             ecost = ecost + ref.edge_terms(e, p[e[0]], p[e[1]], want_terms=False)
-        return 0.5 * (0.0 + ecost)
+        return total(costs, ecost)
 
     cost, H, g, h_keys, l_tiles = full(x)
     if keep is not None:

@@ -16,6 +16,9 @@ ESDF = (24, 300)
 # (seeds, first) of the layer readers' fuzzer: tests/test_fuzz_readers_cpu.py checks the generator over exactly these.  The
 # count is the largest whose restatement side stays within 1.5 times that of MAP_LAYERS (profiles/README.md)
 READERS = (144, 300)
+# (seeds, first) of the pose-graph fuzzer: tests/test_fuzz_pose_graph_cpu.py checks the generator over exactly these.  The
+# count follows the readers' rule (profiles/README.md); the size schedule has a period of 24 seeds
+POSE_GRAPH = (32, 300)
 
 
 def _run(script, seeds, first):
@@ -92,6 +95,13 @@ def test_layer_readers_random_scenes_bit_identical_to_the_restatements():
     scan localisation (evaluate_map, score_poses, localize) on scenes far from the origin, with grid-aligned poses, empty
     and duplicated submaps, and voxels that hold NaN, +-inf, -0.0, denormals and negative weights; a NaN equals a NaN"""
     assert _run("fuzz_layer_readers", *READERS) == 0
+
+
+def test_pose_graph_random_graphs_bit_identical_to_the_restatements():
+    """random block matrices (bad pivots among them), edges-only graphs and registration lists over a ring of 12 submaps:
+    both Cholesky routes, the three orderings, both covariance routes and the slabs against the sequential restatements,
+    every bit; sparse in natural order next to dense as numbers (the sign of a zero may differ)"""
+    assert _run("fuzz_pose_graph", *POSE_GRAPH) == 0
 
 
 def test_esdf_random_submaps_bit_identical_to_the_restatement_and_close_to_the_queue():
