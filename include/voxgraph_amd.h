@@ -487,7 +487,11 @@ VGX_API int vgx_reg_batch_evaluate_normal(vgx_reg_batch batch,
  * d_cost: DEVICE pointer [n] f64 (nullable); cost_host: host [n] (nullable; implies a stream synchronisation).
  * With d_cost == NULL the batch's internal block array serves as scratch: the blocks a previous
  * vgx_reg_batch_evaluate_normal(d_normal == NULL) left there (what vgx_reg_batch_assemble / _scatter_normal read when
- * THEY are given NULL) are gone -- evaluate the blocks again before assembling.  Deterministic.
+ * THEY are given NULL) are gone -- evaluate the blocks again before assembling.  The batch keeps count of it:
+ * vgx_reg_batch_assemble / _scatter_normal with d_normal == NULL return VGX_ERR_INVALID ("the batch's internal array holds
+ * no blocks") until a vgx_reg_batch_evaluate_normal(d_normal == NULL) has succeeded on the handle with no cost-only
+ * evaluation into the internal array since.  An evaluation into the caller's own arrays leaves the internal blocks, and
+ * whether they can be read, as they were.  Deterministic.
  * SAMPLING constraints (sampling_ratio != -1): EVERY evaluation of a batch -- points, normal or cost -- is one Evaluate of
  * every constraint in list order and DRAWS its points from the reference point sets' engines, as every call of the
  * reference's Evaluate does (registration_cost_function.cpp:113-122): a cost-only evaluation followed by a full one at the

@@ -19,12 +19,21 @@ READERS = (144, 300)
 # (seeds, first) of the pose-graph fuzzer: tests/test_fuzz_pose_graph_cpu.py checks the generator over exactly these.  The
 # count follows the readers' rule (profiles/README.md); the size schedule has a period of 24 seeds
 POSE_GRAPH = (32, 300)
+# (seeds, first) of the registration batch's sequence fuzzer: tests/test_fuzz_reg_sequences_cpu.py checks the generator over
+# exactly these.  The schedule has a period of 12 seeds; the readers' rule would hold 72, two periods keep the test at a
+# few seconds (profiles/README.md)
+REG_SEQUENCES = (24, 300)
 
 
-def _run(script, seeds, first):
+def _load(script):
     spec = importlib.util.spec_from_file_location(script, os.path.join(ROOT, "profiles", script + ".py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
+    return mod
+
+
+def _run(script, seeds, first):
+    mod = _load(script)
     old = {k: os.environ.get(k) for k in ("SEEDS", "FIRST")}
     os.environ["SEEDS"], os.environ["FIRST"] = str(seeds), str(first)
     try:
@@ -108,3 +117,15 @@ def test_esdf_random_submaps_bit_identical_to_the_restatement_and_close_to_the_q
     """shell-observed and carved submaps, random max / default / min distances: both ESDF layers the bits of tests/esdf_ref.py,
     and the queue's contract (masks, fixed band, signs, never above, within 4 mm, fixed-point residual)"""
     assert _run("fuzz_esdf", *ESDF) == 0
+
+
+def test_one_long_lived_registration_batch_through_random_call_sequences():
+    """14 calls per batch handle -- every rows entry point, kept rows and late fetches, fused blocks and costs into the
+    internal and the caller's arrays, assemblies from both, live counts in between, drop-in and visuals evaluations,
+    refused calls of every kind, a placement trial and a pose-graph solve -- each held to the oracle's rows and, all-points
+    batches, to the same call on a fresh handle, bit for bit; sampling batches to the oracle's engines draw for draw.  Both
+    launch orders must have been met in either pass: a grouped order is what later poses could disagree with"""
+    rc, summary = _load("fuzz_reg_sequences").run(*REG_SEQUENCES)
+    assert rc == 0
+    for p, name in enumerate(("fused pass", "materialising pass")):
+        assert summary["grouped"][p] > 0 and summary["not_grouped"][p] > 0, (name, summary)

@@ -523,6 +523,8 @@ struct vgx_reg_batch_s {
   vgx::DeviceBuffer d_tile_first;     // int32 [n+1] first tile of each constraint
   vgx::DeviceBuffer d_partials;       // double [n_tiles][4 wavefronts][kPartialSize]
   vgx::DeviceBuffer d_normal;         // double [n][45] (internal, when caller passes none)
+  bool normal_holds_blocks = false;   // d_normal holds the blocks of a vgx_reg_batch_evaluate_normal(d_normal == NULL): what
+                                      // assemble / scatter_normal(NULL) may read (cleared by whatever else writes d_normal)
   vgx::PinnedBuffer h_normal;         // double [n][45]: staging of the host copies (normal_host / cost_host)
   vgx::DeviceBuffer d_node_pair;      // int32
   vgx::DeviceBuffer d_global_index;   // int32

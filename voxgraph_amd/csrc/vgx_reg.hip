@@ -2449,20 +2449,26 @@ static int batch_begin(vgx_reg_batch b) {
   return VGX_OK;
 }
 
+static int batch_nodes_within(vgx_reg_batch b, int32_t n_nodes) {
+  for (int32_t v : b->node_pair)
+    if (v >= n_nodes) return set_error(b->ctx, VGX_ERR_INVALID, "vgx_reg_batch: node index >= n_nodes");
+  return VGX_OK;
+}
+
 // pose packs for every constraint -> pinned staging (double-buffered) -> device.
 // No stream synchronisation: the host only waits until the H2D copy that last used
 // this staging half has finished, so it prepares evaluation k+1 while k still runs.
 static int batch_upload_packs(vgx_reg_batch b, const double* poses, int32_t n_nodes, int32_t* status) {
   vgx_ctx ctx = b->ctx;
   if (b->n == 0) return VGX_OK;
+  const int rc_nodes = batch_nodes_within(b, n_nodes);   // before a staging half is taken: a refused call leaves the handle as it was
+  if (rc_nodes != VGX_OK) return rc_nodes;
   int turn = 0;
   hipError_t waited = hipSuccess;
   PosePack* stage = static_cast<PosePack*>(b->pack_stage.next(&turn, &waited));
   VGX_HIP(ctx, waited);
   for (int c = 0; c < b->n; ++c) {
     int i = b->node_pair[2 * (size_t)c], j = b->node_pair[2 * (size_t)c + 1];
-    if (i >= n_nodes || j >= n_nodes)
-      return set_error(ctx, VGX_ERR_INVALID, "vgx_reg_batch: node index >= n_nodes");
     make_pose_pack(poses + 4 * (size_t)i, poses + 4 * (size_t)j, &stage[c]);
     if (status) status[c] = reg_status(b->regs[(size_t)c]);
   }
@@ -2496,8 +2502,14 @@ static int apply_launch_order(vgx_reg_batch b, const std::vector<Tile>& tiles, T
 
 // The head of every batched evaluation (the caller holds ctx->mu and has set the device): the point sets are current
 // and the sampling constraints have drawn (batch_begin), then the pose packs and statuses of this evaluation.
+// Everything that can REFUSE the call comes before the draw: a refused call is no Evaluate
+// (registration_cost_function.cpp:113-122 draws inside Evaluate) and leaves every engine where it was.
 static int batch_evaluation_begin(vgx_reg_batch b, const double* poses, int32_t n_nodes, int32_t* status) {
-  const int rc = batch_begin(b);
+  int rc = batch_points_current(b);
+  if (rc != VGX_OK) return rc;
+  rc = batch_nodes_within(b, n_nodes);
+  if (rc != VGX_OK) return rc;
+  rc = batch_begin(b);
   return rc != VGX_OK ? rc : batch_upload_packs(b, poses, n_nodes, status);
 }
 
@@ -2852,11 +2864,13 @@ int vgx_reg_batch_evaluate_normal(vgx_reg_batch b, const double* poses, int32_t 
   if (rc != VGX_OK) return rc;
   if (b->n == 0) return VGX_OK;
   double* out = d_normal ? (double*)d_normal : b->d_normal.as<double>();
+  if (!d_normal) b->normal_holds_blocks = false;   // until every launch below is queued
   rc = launch_fused_tiles<false>(b);
   if (rc != VGX_OK) return rc;
   hipLaunchKernelGGL(reg_finalize_kernel, dim3(b->n), dim3(256), 0, ctx->stream, b->d_desc.as<ConstraintDev>(), b->d_pack.as<PosePack>(),
                      b->d_tile_first.as<int32_t>(), b->d_partials.as<double>(), out);
   VGX_HIP(ctx, hipGetLastError());
+  if (!d_normal) b->normal_holds_blocks = true;
   if (normal_host) {
     // through the batch's own PINNED block: a copy into the caller's pageable memory is staged by the runtime behind a
     // process-wide lock, and a scan submitted from the mapping thread meanwhile waited for this evaluation to finish
@@ -2881,9 +2895,11 @@ int vgx_reg_batch_evaluate_cost(vgx_reg_batch b, const double* poses, int32_t n_
   int rc = batch_evaluation_begin(b, poses, n_nodes, status);
   if (rc != VGX_OK) return rc;
   if (b->n == 0) return VGX_OK;
-  // (the internal [n][45] array's first n doubles when the caller passes no device array: a cost-only evaluation
-  // invalidates nothing the caller can see -- vgx_reg_batch_evaluate_normal rewrites the array before anyone reads it)
+  // (the internal [n][45] array's first n doubles when the caller passes no device array: the blocks an earlier
+  // vgx_reg_batch_evaluate_normal(d_normal == NULL) left there are gone, as the header says, and the flag makes
+  // vgx_reg_batch_assemble / _scatter_normal(NULL) refuse to read the mix until the blocks are evaluated again)
   double* out = d_cost ? (double*)d_cost : b->d_normal.as<double>();
+  if (!d_cost) b->normal_holds_blocks = false;
   rc = launch_fused_tiles<true>(b);
   if (rc != VGX_OK) return rc;
   hipLaunchKernelGGL(reg_finalize_cost_kernel, dim3((unsigned)((b->n + 3) / 4)), dim3(64), 0, ctx->stream, b->d_desc.as<ConstraintDev>(), (int)b->n,
@@ -3011,6 +3027,9 @@ int vgx_reg_batch_assemble(vgx_reg_batch b, const void* d_normal, int32_t n_node
   vgx_reg_batch ex = b;
   if (n_nodes < ex->csr_nodes)
     return set_error(ctx, VGX_ERR_INVALID, "vgx_reg_batch_assemble: n_nodes smaller than the largest node index");
+  if (!d_normal && b->n > 0 && !b->normal_holds_blocks)
+    return set_error(ctx, VGX_ERR_INVALID, "vgx_reg_batch_assemble: d_normal == NULL, and the batch's internal array holds no blocks "
+                                           "(no vgx_reg_batch_evaluate_normal(d_normal == NULL) yet, or a cost-only evaluation since)");
   VGX_HIP(ctx, hipSetDevice(ctx->device));
   const double* nb = d_normal ? (const double*)d_normal : b->d_normal.as<double>();
   if (zero_first)
@@ -3037,6 +3056,9 @@ int vgx_reg_batch_scatter_normal(vgx_reg_batch b, const void* d_normal, void* d_
   if (!b || !d_normal_all) return VGX_ERR_INVALID;
   vgx_ctx ctx = b->ctx;
   std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!d_normal && b->n > 0 && !b->normal_holds_blocks)
+    return set_error(ctx, VGX_ERR_INVALID, "vgx_reg_batch_scatter_normal: d_normal == NULL, and the batch's internal array holds no blocks "
+                                           "(no vgx_reg_batch_evaluate_normal(d_normal == NULL) yet, or a cost-only evaluation since)");
   VGX_HIP(ctx, hipSetDevice(ctx->device));
   if (zero_first)
     VGX_HIP(ctx, hipMemsetAsync(d_normal_all, 0, (size_t)b->n_global * kNormalSize * sizeof(double), ctx->stream));
