@@ -2616,6 +2616,95 @@ VGX_API int vgx_view_rays_pinhole(int32_t width, int32_t height, double fx, doub
 VGX_API int vgx_view_rays_lidar(int32_t width, int32_t height, double elevation_min, double elevation_max,
                                 double azimuth_offset, float* dirs);
 
+/* ---- Planar map: the 2D occupancy and distance grid of a layer's height band -------- */
+/* What a 2D planner takes: the voxels of a layer between two heights collapsed along z into a grid of cells -- state,
+ * nav_msgs/OccupancyGrid occupancy, clearance, obstacle height -- and the exact planar Euclidean distance to the nearest
+ * obstacle cell, clipped.  Every submap frame and the mission frame are gravity-aligned (the pose graph is 4-DoF), so a
+ * band of z rows is well defined in any layer and nothing is resampled.  Sources: a vgx_tsdf_layer (the active submap
+ * or the projected map) and a finished submap's raw TSDF or ESDF layer.
+ * Rules (what the kernels, vgx_planar.hip, and tests/planar_map_ref.py both follow; f32 with no contraction unless
+ * marked int):
+ *   cell       global voxel index on x and y, ix = block_x * vps + local_x (int32).  The grid is row-major, x fastest:
+ *              cell = (iy - y0) * W + (ix - x0), OccupancyGrid's order, with its origin at the corner (x0 * voxel_size,
+ *              y0 * voxel_size).  A layer whose block table reaches block indices that overflow ix: VGX_ERR_INVALID.
+ *   observed   the clouds' rule: ESDF observed != 0; TSDF weight > min_weight, strictly (a NaN weight is not observed).
+ *   band       a voxel row with centre cz = voxel_centre((float)bz * block_size, lz, voxel_size) -- block_size =
+ *              (float)vps * voxel_size, the helper that of every other product -- is in the band iff z_min <= cz &&
+ *              cz <= z_max.  A block none of whose rows passes this very comparison is skipped unread.
+ *   voxel      occupied_v: in the band, observed, d <= occupied_distance.  free_v: in the band, observed,
+ *              d > occupied_distance.  A NaN distance is neither; +-inf classify by the comparison.
+ *   column     a cell's voxels are walked in ascending global z; missing blocks are skipped.  n_occ, n_free: int32.
+ *   state      u8: 2 (occupied) if n_occ >= 1, else 1 (free) if n_free >= min_free_voxels, else 0 (unknown).
+ *   clearance  f32: the smallest d over the classified voxels; it starts at the first one and is replaced only when
+ *              d < current, strictly, so ties (+-0) are decided by z order.  +0.0f where state is 0 -- also where fewer
+ *              than min_free_voxels free voxels were seen.
+ *   height     f32: cz of the highest occupied_v; +0.0f where state != 2.
+ *   occupancy  i8: -1 / 0 / 100 for state 0 / 1 / 2.
+ *   box        use_box = 0: the x/y extent, in whole blocks, of the allocated blocks that have at least one row in the
+ *              band; none: W = H = 0 and VGX_OK.  use_box = 1: cell_min[2], cell_dim[2] in global voxel indices, not
+ *              necessarily block-aligned (a rolling window); cells outside the layer are unknown.  cell_dim >= 0 and
+ *              cell_min + cell_dim <= 2^31 - 1; W * H <= 2^28, else VGX_ERR_INVALID.
+ *   distance   f32 per cell.  Obstacle cells: state 2, and state 0 when unknown_is_obstacle != 0.  R =
+ *              (int)ceil((double)max_distance_m / (double)voxel_size), on the host; max_distance_m finite and > 0 and
+ *              R <= 2048, so that 2 R^2 < 2^24 and (float)d2 is exact.  Row pass (int): g[y][x] = the smallest |x - x'|
+ *              over the obstacle cells of row y with |x - x'| <= R, or none.  Column pass (int): d2 = min over
+ *              |dy| <= R, row y + dy inside the grid, g[y + dy][x] not none, of dy * dy + g * g.  Then m =
+ *              sqrtf((float)d2) * voxel_size and distance = m < max_distance_m ? m : max_distance_m; max_distance_m
+ *              where nothing was found; 0 on obstacle cells.  Nothing outside the box is an obstacle.  A candidate
+ *              outside the square window is at least (R + 1) * voxel_size away and clips anyway: the result is the
+ *              exact Euclidean distance transform, clipped.
+ *   totals     the number of cells in each state, counts[3] int64, indexed by state.
+ * The handle is reused from call to call: its device buffers grow on demand; one call at a time per handle.
+ * Refused with VGX_ERR_INVALID before anything is written, the map keeping what it held (vgx_last_error says which): a
+ * NULL source, map or cfg (there is no default band), a map of another context, z_min, z_max or occupied_distance not
+ * finite, z_min > z_max, a min_weight that is negative or not finite, min_free_voxels < 1, max_distance_m not finite or
+ * <= 0 or R > 2048, a bad box, a submap layer that is not resident in raw form, a layer value that is neither
+ * VGX_EVAL_LAYER_ESDF nor _TSDF.  VGX_ERR_UNSUPPORTED: voxels_per_side other than 8 or 16.  Out of device memory:
+ * VGX_ERR_NOMEM, and the map then holds 0 cells.
+ * Passes: [the box: one kernel over the block slots, integer min / max] -- gather (one lane per cell walks the band's z
+ * blocks through the layer's dense block table; no atomics on cells, integer atomics for the three totals) -- row pass
+ * -- column pass: a fixed number of launches whatever the size.  Two host synchronisations (the box, then the end with
+ * the totals); one with use_box.  vgx_submap_layer_planar_map runs on the registration stream under the registration
+ * lock, behind vgx_submap_generate_esdf; vgx_tsdf_layer_planar_map on the TSDF stream under the TSDF lock, behind the
+ * scans and merges already queued.  Both return with the map complete. */
+typedef struct vgx_planar_map_config {
+  float z_min, z_max;          /* NaN: the band has no default and must be set (metres, the layer's frame) */
+  float occupied_distance;     /* 0: at or behind the surface */
+  float min_weight;            /* 1e-3, TSDF sources only */
+  int32_t min_free_voxels;     /* 1 */
+  int32_t unknown_is_obstacle; /* 0 */
+  float max_distance_m;        /* 2 */
+  int32_t use_box;             /* 0 */
+  int32_t cell_min[2];         /* 0, 0 (use_box: x0, y0, global voxel indices) */
+  int32_t cell_dim[2];         /* 0, 0 (use_box: W, H) */
+} vgx_planar_map_config;
+typedef struct vgx_planar_map_s* vgx_planar_map;
+/* fills all but the band: z_min = z_max = NaN, so that an unset band is refused */
+VGX_API void vgx_planar_map_config_default(vgx_planar_map_config* cfg);
+VGX_API int vgx_planar_map_create(vgx_ctx ctx, vgx_planar_map* out);
+VGX_API int vgx_planar_map_destroy(vgx_planar_map map);
+/* a vgx_tsdf_layer: the active submap or the projected map */
+VGX_API int vgx_tsdf_layer_planar_map(vgx_tsdf_layer layer, const vgx_planar_map_config* cfg, vgx_planar_map map);
+/* a finished submap's raw layer: layer = VGX_EVAL_LAYER_ESDF / VGX_EVAL_LAYER_TSDF */
+VGX_API int vgx_submap_layer_planar_map(vgx_submap submap, int32_t layer, const vgx_planar_map_config* cfg,
+                                        vgx_planar_map map);
+/* any pointer may be NULL; cell_min = {x0, y0}, cell_dim = {W, H}, counts indexed by state */
+VGX_API int vgx_planar_map_stats(vgx_planar_map map, int32_t cell_min[2], int32_t cell_dim[2], float* voxel_size,
+                                 int64_t counts[3]);
+/* A measuring aid, off by default: with enable != 0 the producing calls record events between their launches, and
+ * vgx_planar_map_pass_ms returns the device time of the last producing call by pass (milliseconds): ms[0] the box kernel
+ * (0 with use_box, or where no block has a row in the band), ms[1] gather, ms[2] row pass, ms[3] column pass; all 0 for a
+ * map of 0 cells or while timing is off.  What profiles/planar_map_bench.py reports. */
+VGX_API int vgx_planar_map_set_timing(vgx_planar_map map, int32_t enable);
+VGX_API int vgx_planar_map_pass_ms(vgx_planar_map map, float ms[4]);
+/* state [H][W] u8, occupancy [H][W] i8, clearance, height, distance [H][W] f32; any may be NULL */
+VGX_API int vgx_planar_map_download(vgx_planar_map map, uint8_t* state, int8_t* occupancy, float* clearance, float* height,
+                                    float* distance);
+/* DEVICE pointers to the same five arrays (NULL while the map holds 0 cells); valid until the next producing call on
+ * the handle or its destruction.  Any may be NULL. */
+VGX_API int vgx_planar_map_device_pointers(vgx_planar_map map, const uint8_t** state, const int8_t** occupancy,
+                                           const float** clearance, const float** height, const float** distance);
+
 #ifdef __cplusplus
 }
 #endif

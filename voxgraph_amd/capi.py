@@ -90,6 +90,14 @@ class CloudConfig(C.Structure):
 CLOUD_DISTANCE, CLOUD_SURFACE_DISTANCE, CLOUD_SURFACE_COLOR = 0, 1, 2
 
 
+class PlanarMapConfig(C.Structure):
+    """vgx_planar_map_config: the height band, the voxel classes, the grid box and the distance limit of a planar map
+    (include/voxgraph_amd.h, "Planar map")."""
+    _fields_ = [("z_min", C.c_float), ("z_max", C.c_float), ("occupied_distance", C.c_float), ("min_weight", C.c_float),
+                ("min_free_voxels", C.c_int32), ("unknown_is_obstacle", C.c_int32), ("max_distance_m", C.c_float),
+                ("use_box", C.c_int32), ("cell_min", C.c_int32 * 2), ("cell_dim", C.c_int32 * 2)]
+
+
 class ScanLayout(C.Structure):
     """vgx_scan_layout: a sensor_msgs/PointCloud2 header with the field names resolved to byte offsets."""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("point_step", C.c_uint32), ("row_step", C.c_uint32),
@@ -501,6 +509,16 @@ SIGNATURES = {
     "vgx_cloud_device_pointers": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
     "vgx_submap_layer_cloud": (C.c_int, [vp, C.c_int32, C.POINTER(CloudConfig), vp]),
     "vgx_tsdf_layer_cloud": (C.c_int, [vp, C.POINTER(CloudConfig), vp]),
+    "vgx_planar_map_config_default": (None, [C.POINTER(PlanarMapConfig)]),
+    "vgx_planar_map_create": (C.c_int, [vp, C.POINTER(vp)]),
+    "vgx_planar_map_destroy": (C.c_int, [vp]),
+    "vgx_tsdf_layer_planar_map": (C.c_int, [vp, C.POINTER(PlanarMapConfig), vp]),
+    "vgx_submap_layer_planar_map": (C.c_int, [vp, C.c_int32, C.POINTER(PlanarMapConfig), vp]),
+    "vgx_planar_map_stats": (C.c_int, [vp, i32p, i32p, f32p, i64p]),
+    "vgx_planar_map_set_timing": (C.c_int, [vp, C.c_int32]),
+    "vgx_planar_map_pass_ms": (C.c_int, [vp, f32p]),
+    "vgx_planar_map_download": (C.c_int, [vp, u8p, C.POINTER(C.c_int8), f32p, f32p, f32p]),
+    "vgx_planar_map_device_pointers": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
     "vgx_evaluate_layers_rmse_cloud": (C.c_int, [vp, vp, C.c_int32, C.c_int32, C.POINTER(EvaluationDetails),
                                                  C.POINTER(CloudConfig), vp]),
     "vgx_map_msg_create": (C.c_int, [vp, C.POINTER(vp)]),
@@ -961,6 +979,15 @@ class Submap:
         self.ctx.check(self.ctx.lib.vgx_submap_layer_cloud(self.h, int(which), None if config is None else C.byref(config),
                                                            cloud.h))
         return cloud
+
+    def layer_planar_map(self, layer, config, planar_map=None):
+        """The planar map of the raw ESDF or TSDF layer's height band (vgx_submap_layer_planar_map; config:
+        planar_map_config(z_min=..., z_max=..., ...)).  Returns the PlanarMap (a new one when planar_map is None)."""
+        planar_map = planar_map if planar_map is not None else PlanarMap(self.ctx)
+        which = {"esdf": EVAL_LAYER_ESDF, "tsdf": EVAL_LAYER_TSDF}.get(layer, layer)
+        self.ctx.check(self.ctx.lib.vgx_submap_layer_planar_map(self.h, int(which), None if config is None else C.byref(config),
+                                                                planar_map.h))
+        return planar_map
 
     def serialize_layer(self, layer="tsdf", msg=None):
         """voxblox::serializeLayerAsMsg of the raw TSDF or ESDF layer (vgx_submap_serialize_layer).  Returns the MapMsg
@@ -1735,6 +1762,13 @@ class TsdfLayer:
         self.ctx.check(self.ctx.lib.vgx_tsdf_layer_cloud(self.h, None if config is None else C.byref(config), cloud.h))
         return cloud
 
+    def planar_map(self, config, planar_map=None):
+        """The planar map of this layer's height band (vgx_tsdf_layer_planar_map; config: planar_map_config(z_min=...,
+        z_max=..., ...)).  Returns the PlanarMap (a new one when planar_map is None)."""
+        planar_map = planar_map if planar_map is not None else PlanarMap(self.ctx)
+        self.ctx.check(self.ctx.lib.vgx_tsdf_layer_planar_map(self.h, None if config is None else C.byref(config), planar_map.h))
+        return planar_map
+
     def render_view(self, view, T_L_C, dirs, n=None):
         """The view of this layer from sensor pose T_L_C along dirs [n][3] (vgx_tsdf_layer_render_view / _device: a numpy
         array, a torch device tensor, or a device address with n), behind every scan queued.  Returns the View."""
@@ -1905,6 +1939,68 @@ class Cloud:
     def destroy(self):
         if self.h:
             self.ctx.lib.vgx_cloud_destroy(self.h)
+            self.h = None
+
+
+def planar_map_config(**kw):
+    """vgx_planar_map_config_default() with fields overridden: z_min, z_max (both required by the producing calls),
+    occupied_distance, min_weight, min_free_voxels, unknown_is_obstacle, max_distance_m, use_box, cell_min, cell_dim."""
+    cfg = PlanarMapConfig()
+    load().vgx_planar_map_config_default(C.byref(cfg))
+    for k, v in kw.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(k)
+        if k in ("cell_min", "cell_dim"):
+            v = (C.c_int32 * 2)(int(v[0]), int(v[1]))
+        setattr(cfg, k, v)
+    return cfg
+
+
+class PlanarMap:
+    """A layer's height band as a 2D grid on the GPU (vgx_planar_map): state, occupancy, clearance, height and the
+    clipped planar distance per cell, row-major with x fastest; reused from call to call."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        h = vp()
+        ctx.check(ctx.lib.vgx_planar_map_create(ctx.h, C.byref(h)))
+        self.h = h
+
+    def stats(self):
+        """((x0, y0), (W, H), voxel_size, (unknown, free, occupied) cell counts)"""
+        mn, dim, vs, counts = (C.c_int32 * 2)(), (C.c_int32 * 2)(), C.c_float(), (C.c_int64 * 3)()
+        self.ctx.check(self.ctx.lib.vgx_planar_map_stats(self.h, mn, dim, C.byref(vs), counts))
+        return (mn[0], mn[1]), (dim[0], dim[1]), vs.value, tuple(counts)
+
+    def download(self):
+        """(state [H][W] u8, occupancy [H][W] i8, clearance, height, distance [H][W] f32)"""
+        _, (w, h), _, _ = self.stats()
+        state = np.zeros((h, w), np.uint8)
+        occupancy = np.zeros((h, w), np.int8)
+        clearance, height, distance = (np.zeros((h, w), np.float32) for _ in range(3))
+        self.ctx.check(self.ctx.lib.vgx_planar_map_download(self.h, _ptr(state, u8p), _ptr(occupancy, C.POINTER(C.c_int8)),
+                                                            _ptr(clearance, f32p), _ptr(height, f32p), _ptr(distance, f32p)))
+        return state, occupancy, clearance, height, distance
+
+    def set_timing(self, enable=True):
+        """record events between the passes of the producing calls from now on (off by default)"""
+        self.ctx.check(self.ctx.lib.vgx_planar_map_set_timing(self.h, 1 if enable else 0))
+
+    def pass_ms(self):
+        """device milliseconds of the last producing call, with set_timing(True): (box, gather, row pass, column pass)"""
+        ms = (C.c_float * 4)()
+        self.ctx.check(self.ctx.lib.vgx_planar_map_pass_ms(self.h, ms))
+        return tuple(ms)
+
+    def device_pointers(self):
+        """(state, occupancy, clearance, height, distance) device addresses as ints (None while the map holds 0 cells)"""
+        p = [vp() for _ in range(5)]
+        self.ctx.check(self.ctx.lib.vgx_planar_map_device_pointers(self.h, *[C.byref(x) for x in p]))
+        return tuple(x.value for x in p)
+
+    def destroy(self):
+        if self.h:
+            self.ctx.lib.vgx_planar_map_destroy(self.h)
             self.h = None
 
 

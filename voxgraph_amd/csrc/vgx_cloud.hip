@@ -9,12 +9,12 @@
 //   2. rocprim::exclusive_scan of the per-block counts (int64); the total comes back once, to size the output
 //   3. cloud_emit_kernel: the same classification; positions inside the workgroup from ballots / popcounts per wave and
 //      the waves' counts in LDS, in (step, wave) order -- no atomics: the order is that of the voxels' linear indices
-// Three source layouts (SRC): a finished submap's ESDF (f32 distance + u8 observed) and TSDF (f32 distance + f32 weight)
-// layers, and a vgx_tsdf_layer's packed {distance, weight} words with their colours.
+// The three source layouts (SRC) are those of vgx_cloud_src.h, shared with the planar map.
 #include <algorithm>
 #include <cmath>
 #include <string>
 
+#include "vgx_cloud_src.h"
 #include "vgx_internal.h"
 #include "vgx_tsdf_internal.h"
 
@@ -22,33 +22,12 @@
 
 namespace vgx {
 
-enum { kCloudSrcEsdf = 0, kCloudSrcTsdf = 1, kCloudSrcPacked = 2 };
-
-struct CloudSrc {
-  const int32_t* block_index;  // [slots][3]
-  // the layer's block count where only the device knows it when the passes are queued (an active layer's allocation
-  // counter, an evaluation's error-block count); null: every slot of the grid is a block
-  const void* live_blocks;
-  int32_t live_blocks_is_64;
-  const float* dist;                // ESDF / TSDF
-  const void* seen;                 // ESDF: u8 observed; TSDF: f32 weight
-  const unsigned long long* words;  // packed: {distance (lo), weight (hi)}
-  const uint32_t* rgba;             // packed
-  float voxel_size;
-};
-
 struct CloudRule {
   int32_t kind;
   float surface_distance, min_weight;
   int32_t slice_axis;
   float slice_value;
 };
-
-__device__ __forceinline__ int cloud_live_blocks(const CloudSrc& s, int slots) {
-  if (!s.live_blocks) return slots;
-  const long long n = s.live_blocks_is_64 ? *static_cast<const long long*>(s.live_blocks) : (long long)*static_cast<const int32_t*>(s.live_blocks);
-  return (int)(n < (long long)slots ? n : (long long)slots);
-}
 
 // Bit i: voxel index i of this block on the slice axis passes the slice rule |centre - plane| <= voxel_size / 2 + 1e-6f
 // (f32).  From the block index alone: 0 rejects the block before any voxel is read, and the voxels of a kept block test
