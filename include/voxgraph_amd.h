@@ -2705,6 +2705,114 @@ VGX_API int vgx_planar_map_download(vgx_planar_map map, uint8_t* state, int8_t* 
 VGX_API int vgx_planar_map_device_pointers(vgx_planar_map map, const uint8_t** state, const int8_t** occupancy,
                                            const float** clearance, const float** height, const float** distance);
 
+/* ---- Elevation map: 2.5D surface height, slope, step and traversability of a layer's height band -------- */
+/* What a legged or rough-terrain planner takes: per cell of the planar map's grid the height of the surface to sub-voxel
+ * accuracy, the headroom above it, the step height and support of its neighbourhood, the surface gradient and slope, a
+ * traversability class, and the exact planar Euclidean distance to the nearest non-traversable cell, clipped.  The
+ * formulation is this library's own: neither voxgraph nor voxblox builds such a grid.  Sources: a vgx_tsdf_layer (the
+ * active submap or the projected map) and a finished submap's raw TSDF or ESDF layer.
+ * Rules (what the kernels, vgx_elevation.hip, and tests/elevation_map_ref.py both follow; f32 with no contraction
+ * unless marked int):
+ *   shared     cell, grid order, box, observed and band are exactly the planar map's rules above: the global voxel index
+ *              and x fastest; the default box from the blocks with a row in the band, or a rolling window; W * H <= 2^28;
+ *              the voxel_centre helper and z_min <= cz && cz <= z_max.
+ *   column     walk a cell's voxel rows in descending global z, from the top row of the band to the bottom one; rows
+ *              that belong to a missing block are included.  A voxel is classified when it is in the band, observed,
+ *              and its distance d is not NaN; it is free_v when d > 0.0f, else solid_v.  Carry run (int), the number of
+ *              consecutive classified free_v voxels immediately above the current row; any row that is unclassified,
+ *              solid_v, missing or out of band resets run to 0.  A crossing is a solid_v voxel l met with run >= 1.
+ *              Then d_u is the distance of the voxel directly above, t = (-d_l) / (d_u - d_l), and if
+ *              !(t >= 0.0f && t <= 1.0f) then t = 0.5f (that case arises from +-inf operands).  h = cz_l + t *
+ *              voxel_size and headroom = run.  n_free, n_solid and crossings are int32 counts; crossings is stored as
+ *              u8, saturating at 255.  Adjacency never skips a row: a missing block between two voxels is not a
+ *              crossing; a pair that straddles a z block boundary is one.
+ *   outputs    pick chooses the first crossing met (0: the highest) or the last one (1: the lowest).  state u8: 1 =
+ *              surface (at least one crossing); 3 = blocked (no crossing, n_solid >= 1); 2 = hole (no crossing, n_solid
+ *              == 0, n_free >= min_free_voxels); 0 = unknown (everything else).  height f32: h of the chosen crossing,
+ *              +0.0f where state is not 1.  headroom i32: voxels, 0 where state is not 1.  crossings u8.
+ *   step       the window is the cells within Chebyshev distance step_radius_cells (0..64) inside the box.  support
+ *              (u16) is the number of state-1 cells in the window, the cell itself included; step = max(height) -
+ *              min(height) over those cells.  Both are 0 where the cell's own state is not 1.  Max and min are exact,
+ *              computed separably: a row pass, then a column pass -- O(radius) per cell.
+ *   gradient   for a cell in state 1 (any other cell has both axes undefined).  On x, with h_r and h_l the heights of
+ *              the x + 1 and x - 1 cells where they are inside the box and in state 1: both: gx = (h_r - h_l) / (2.0f *
+ *              voxel_size); only right: (h_r - h) / voxel_size; only left: (h - h_l) / voxel_size; neither: the axis is
+ *              undefined.  gy is formed likewise.  slope = sqrtf(gx * gx + gy * gy) when both axes are defined;
+ *              otherwise the slope is undefined, stored as +0.0f, with slope_valid (u8) = 0.  grad is stored as f32[2],
+ *              zeros where the slope is undefined.
+ *   class      u8, decided in this order.  1. state 0 gives class 0.  2. state 3 gives class 2.  3. state 2 gives class
+ *              2 if hole_is_obstacle, else 0.  4. state 1: headroom < min_headroom_voxels gives 2; else !slope_valid ||
+ *              support < min_support gives 0; else slope > max_slope || step > max_step_m gives 2; else 1.
+ *              (0 unknown, 1 traversable, 2 not traversable.)
+ *   distance   f32, to the nearest obstacle cell: class 2, and also class 0 when unknown_is_obstacle.  The planar map's
+ *              rule word for word: the same R, with R <= 2048; an integer row pass and an integer column pass;
+ *              sqrtf((float)d2) * voxel_size; the clip; nothing outside the box is an obstacle.
+ *   totals     the number of cells in each state, state_counts[4], and in each class, class_counts[3]; int64.
+ * The handle is reused from call to call: its device buffers grow on demand; one call at a time per handle.
+ * Refused with VGX_ERR_INVALID before anything is written, the map keeping what it held (vgx_last_error says which): the
+ * planar map's list -- a NULL source, map or cfg (there is no default band), a map of another context, z_min or z_max
+ * not finite, z_min > z_max, a min_weight that is negative or not finite, min_free_voxels < 1, max_distance_m not finite
+ * or <= 0 or R > 2048, a bad box, a submap layer that is not resident in raw form, a layer value that is neither
+ * VGX_EVAL_LAYER_ESDF nor _TSDF -- and pick not 0 or 1, step_radius_cells outside 0..64, min_support < 1,
+ * min_headroom_voxels < 1, max_slope or max_step_m NaN or negative.  VGX_ERR_UNSUPPORTED: voxels_per_side other than 8
+ * or 16.  Out of device memory: VGX_ERR_NOMEM, and the map then holds 0 cells.
+ * Passes: [the box, the planar map's kernel] -- gather (one lane per cell walks the band's z blocks downwards through
+ * the dense block table; no atomics on cells, integer atomics for the state totals) -- step row pass -- step column pass
+ * with the gradient, slope and class (integer atomics for the class totals) -- distance row pass -- distance column pass
+ * (the planar map's two kernels over the class): a fixed number of launches whatever the size.  Two host
+ * synchronisations (the box, then the end with the totals); one with use_box.  No float atomics.
+ * vgx_submap_layer_elevation_map runs on the registration stream under the registration lock;
+ * vgx_tsdf_layer_elevation_map on the TSDF stream under the TSDF lock, behind the scans and merges already queued.  Both
+ * return with the map complete. */
+typedef struct vgx_elevation_map_config {
+  float z_min, z_max;           /* NaN: the band has no default and must be set (metres, the layer's frame) */
+  float min_weight;             /* 1e-3, TSDF sources only */
+  int32_t min_free_voxels;      /* 1 */
+  int32_t pick;                 /* 0 = the highest crossing, 1 = the lowest */
+  int32_t step_radius_cells;    /* 1 (0..64) */
+  int32_t min_support;          /* 1 */
+  float max_slope;              /* 1.0, rise over run */
+  float max_step_m;             /* 0.2 */
+  int32_t min_headroom_voxels;  /* 1 */
+  int32_t hole_is_obstacle;     /* 1 */
+  int32_t unknown_is_obstacle;  /* 0 */
+  float max_distance_m;         /* 2 */
+  int32_t use_box;              /* 0 */
+  int32_t cell_min[2];          /* 0, 0 (use_box: x0, y0, global voxel indices) */
+  int32_t cell_dim[2];          /* 0, 0 (use_box: W, H) */
+} vgx_elevation_map_config;
+typedef struct vgx_elevation_map_s* vgx_elevation_map;
+/* fills all but the band: z_min = z_max = NaN, so that an unset band is refused */
+VGX_API void vgx_elevation_map_config_default(vgx_elevation_map_config* cfg);
+VGX_API int vgx_elevation_map_create(vgx_ctx ctx, vgx_elevation_map* out);
+VGX_API int vgx_elevation_map_destroy(vgx_elevation_map map);
+/* a vgx_tsdf_layer: the active submap or the projected map */
+VGX_API int vgx_tsdf_layer_elevation_map(vgx_tsdf_layer layer, const vgx_elevation_map_config* cfg, vgx_elevation_map map);
+/* a finished submap's raw layer: layer = VGX_EVAL_LAYER_ESDF / VGX_EVAL_LAYER_TSDF */
+VGX_API int vgx_submap_layer_elevation_map(vgx_submap submap, int32_t layer, const vgx_elevation_map_config* cfg,
+                                           vgx_elevation_map map);
+/* any pointer may be NULL; cell_min = {x0, y0}, cell_dim = {W, H}, state_counts indexed by state, class_counts by class */
+VGX_API int vgx_elevation_map_stats(vgx_elevation_map map, int32_t cell_min[2], int32_t cell_dim[2], float* voxel_size,
+                                    int64_t state_counts[4], int64_t class_counts[3]);
+/* A measuring aid, off by default (no event is made or recorded while off): with enable != 0 the producing calls record
+ * events between their launches, and vgx_elevation_map_pass_ms returns the device time of the last producing call by
+ * pass (milliseconds): ms[0] the box kernel (0 with use_box, or where no block has a row in the band), ms[1] gather,
+ * ms[2] step row pass, ms[3] step column pass with slope and class, ms[4] distance row pass, ms[5] distance column pass;
+ * all 0 for a map of 0 cells or while timing is off.  What profiles/elevation_map_bench.py reports. */
+VGX_API int vgx_elevation_map_set_timing(vgx_elevation_map map, int32_t enable);
+VGX_API int vgx_elevation_map_pass_ms(vgx_elevation_map map, float ms[6]);
+/* state, crossings, slope_valid, cls [H][W] u8; headroom [H][W] i32; support [H][W] u16; height, step, slope, distance
+ * [H][W] f32; grad [H][W][2] f32 (gx, gy); any may be NULL */
+VGX_API int vgx_elevation_map_download(vgx_elevation_map map, uint8_t* state, float* height, int32_t* headroom,
+                                       uint8_t* crossings, uint16_t* support, float* step, float* grad, float* slope,
+                                       uint8_t* slope_valid, uint8_t* cls, float* distance);
+/* DEVICE pointers to the same eleven arrays (NULL while the map holds 0 cells); valid until the next producing call on
+ * the handle or its destruction.  Any may be NULL. */
+VGX_API int vgx_elevation_map_device_pointers(vgx_elevation_map map, const uint8_t** state, const float** height,
+                                              const int32_t** headroom, const uint8_t** crossings, const uint16_t** support,
+                                              const float** step, const float** grad, const float** slope,
+                                              const uint8_t** slope_valid, const uint8_t** cls, const float** distance);
+
 #ifdef __cplusplus
 }
 #endif

@@ -98,6 +98,16 @@ class PlanarMapConfig(C.Structure):
                 ("use_box", C.c_int32), ("cell_min", C.c_int32 * 2), ("cell_dim", C.c_int32 * 2)]
 
 
+class ElevationMapConfig(C.Structure):
+    """vgx_elevation_map_config: the height band, the crossing picked, the step window, the traversability limits, the
+    grid box and the distance limit of an elevation map (include/voxgraph_amd.h, "Elevation map")."""
+    _fields_ = [("z_min", C.c_float), ("z_max", C.c_float), ("min_weight", C.c_float), ("min_free_voxels", C.c_int32),
+                ("pick", C.c_int32), ("step_radius_cells", C.c_int32), ("min_support", C.c_int32), ("max_slope", C.c_float),
+                ("max_step_m", C.c_float), ("min_headroom_voxels", C.c_int32), ("hole_is_obstacle", C.c_int32),
+                ("unknown_is_obstacle", C.c_int32), ("max_distance_m", C.c_float), ("use_box", C.c_int32),
+                ("cell_min", C.c_int32 * 2), ("cell_dim", C.c_int32 * 2)]
+
+
 class ScanLayout(C.Structure):
     """vgx_scan_layout: a sensor_msgs/PointCloud2 header with the field names resolved to byte offsets."""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("point_step", C.c_uint32), ("row_step", C.c_uint32),
@@ -519,6 +529,16 @@ SIGNATURES = {
     "vgx_planar_map_pass_ms": (C.c_int, [vp, f32p]),
     "vgx_planar_map_download": (C.c_int, [vp, u8p, C.POINTER(C.c_int8), f32p, f32p, f32p]),
     "vgx_planar_map_device_pointers": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+    "vgx_elevation_map_config_default": (None, [C.POINTER(ElevationMapConfig)]),
+    "vgx_elevation_map_create": (C.c_int, [vp, C.POINTER(vp)]),
+    "vgx_elevation_map_destroy": (C.c_int, [vp]),
+    "vgx_tsdf_layer_elevation_map": (C.c_int, [vp, C.POINTER(ElevationMapConfig), vp]),
+    "vgx_submap_layer_elevation_map": (C.c_int, [vp, C.c_int32, C.POINTER(ElevationMapConfig), vp]),
+    "vgx_elevation_map_stats": (C.c_int, [vp, i32p, i32p, f32p, i64p, i64p]),
+    "vgx_elevation_map_set_timing": (C.c_int, [vp, C.c_int32]),
+    "vgx_elevation_map_pass_ms": (C.c_int, [vp, f32p]),
+    "vgx_elevation_map_download": (C.c_int, [vp, u8p, f32p, i32p, u8p, C.POINTER(C.c_uint16), f32p, f32p, f32p, u8p, u8p, f32p]),
+    "vgx_elevation_map_device_pointers": (C.c_int, [vp] + [C.POINTER(vp)] * 11),
     "vgx_evaluate_layers_rmse_cloud": (C.c_int, [vp, vp, C.c_int32, C.c_int32, C.POINTER(EvaluationDetails),
                                                  C.POINTER(CloudConfig), vp]),
     "vgx_map_msg_create": (C.c_int, [vp, C.POINTER(vp)]),
@@ -988,6 +1008,15 @@ class Submap:
         self.ctx.check(self.ctx.lib.vgx_submap_layer_planar_map(self.h, int(which), None if config is None else C.byref(config),
                                                                 planar_map.h))
         return planar_map
+
+    def layer_elevation_map(self, layer, config, elevation_map=None):
+        """The elevation map of the raw ESDF or TSDF layer's height band (vgx_submap_layer_elevation_map; config:
+        elevation_map_config(z_min=..., z_max=..., ...)).  Returns the ElevationMap (a new one when elevation_map is None)."""
+        elevation_map = elevation_map if elevation_map is not None else ElevationMap(self.ctx)
+        which = {"esdf": EVAL_LAYER_ESDF, "tsdf": EVAL_LAYER_TSDF}.get(layer, layer)
+        self.ctx.check(self.ctx.lib.vgx_submap_layer_elevation_map(self.h, int(which), None if config is None else C.byref(config),
+                                                                   elevation_map.h))
+        return elevation_map
 
     def serialize_layer(self, layer="tsdf", msg=None):
         """voxblox::serializeLayerAsMsg of the raw TSDF or ESDF layer (vgx_submap_serialize_layer).  Returns the MapMsg
@@ -1769,6 +1798,13 @@ class TsdfLayer:
         self.ctx.check(self.ctx.lib.vgx_tsdf_layer_planar_map(self.h, None if config is None else C.byref(config), planar_map.h))
         return planar_map
 
+    def elevation_map(self, config, elevation_map=None):
+        """The elevation map of this layer's height band (vgx_tsdf_layer_elevation_map; config: elevation_map_config(
+        z_min=..., z_max=..., ...)).  Returns the ElevationMap (a new one when elevation_map is None)."""
+        elevation_map = elevation_map if elevation_map is not None else ElevationMap(self.ctx)
+        self.ctx.check(self.ctx.lib.vgx_tsdf_layer_elevation_map(self.h, None if config is None else C.byref(config), elevation_map.h))
+        return elevation_map
+
     def render_view(self, view, T_L_C, dirs, n=None):
         """The view of this layer from sensor pose T_L_C along dirs [n][3] (vgx_tsdf_layer_render_view / _device: a numpy
         array, a torch device tensor, or a device address with n), behind every scan queued.  Returns the View."""
@@ -2001,6 +2037,73 @@ class PlanarMap:
     def destroy(self):
         if self.h:
             self.ctx.lib.vgx_planar_map_destroy(self.h)
+            self.h = None
+
+
+def elevation_map_config(**kw):
+    """vgx_elevation_map_config_default() with fields overridden: z_min, z_max (both required by the producing calls),
+    min_weight, min_free_voxels, pick, step_radius_cells, min_support, max_slope, max_step_m, min_headroom_voxels,
+    hole_is_obstacle, unknown_is_obstacle, max_distance_m, use_box, cell_min, cell_dim."""
+    cfg = ElevationMapConfig()
+    load().vgx_elevation_map_config_default(C.byref(cfg))
+    for k, v in kw.items():
+        if not hasattr(cfg, k):
+            raise AttributeError(k)
+        if k in ("cell_min", "cell_dim"):
+            v = (C.c_int32 * 2)(int(v[0]), int(v[1]))
+        setattr(cfg, k, v)
+    return cfg
+
+
+class ElevationMap:
+    """A layer's height band as a 2.5D surface on the GPU (vgx_elevation_map): state, height, headroom, crossings,
+    support, step, gradient, slope, class and the clipped planar distance per cell, row-major with x fastest; reused from
+    call to call."""
+    FIELDS = (("state", np.uint8), ("height", np.float32), ("headroom", np.int32), ("crossings", np.uint8), ("support", np.uint16),
+              ("step", np.float32), ("grad", np.float32), ("slope", np.float32), ("slope_valid", np.uint8), ("cls", np.uint8),
+              ("distance", np.float32))
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        h = vp()
+        ctx.check(ctx.lib.vgx_elevation_map_create(ctx.h, C.byref(h)))
+        self.h = h
+
+    def stats(self):
+        """((x0, y0), (W, H), voxel_size, (unknown, surface, hole, blocked) cell counts, (unknown, traversable,
+        not traversable) cell counts)"""
+        mn, dim, vs, states, classes = (C.c_int32 * 2)(), (C.c_int32 * 2)(), C.c_float(), (C.c_int64 * 4)(), (C.c_int64 * 3)()
+        self.ctx.check(self.ctx.lib.vgx_elevation_map_stats(self.h, mn, dim, C.byref(vs), states, classes))
+        return (mn[0], mn[1]), (dim[0], dim[1]), vs.value, tuple(states), tuple(classes)
+
+    def download(self):
+        """the eleven arrays in FIELDS' order, [H][W] each (grad: [H][W][2])"""
+        _, (w, h), _, _, _ = self.stats()
+        out = [np.zeros((h, w, 2) if name == "grad" else (h, w), dt) for name, dt in self.FIELDS]
+        self.ctx.check(self.ctx.lib.vgx_elevation_map_download(self.h, *[a.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(a.dtype)))
+                                                                         for a in out]))
+        return tuple(out)
+
+    def set_timing(self, enable=True):
+        """record events between the passes of the producing calls from now on (off by default)"""
+        self.ctx.check(self.ctx.lib.vgx_elevation_map_set_timing(self.h, 1 if enable else 0))
+
+    def pass_ms(self):
+        """device milliseconds of the last producing call, with set_timing(True): (box, gather, step row pass, step
+        column pass with slope and class, distance row pass, distance column pass)"""
+        ms = (C.c_float * 6)()
+        self.ctx.check(self.ctx.lib.vgx_elevation_map_pass_ms(self.h, ms))
+        return tuple(ms)
+
+    def device_pointers(self):
+        """the eleven arrays' device addresses as ints, in FIELDS' order (None while the map holds 0 cells)"""
+        p = [vp() for _ in range(11)]
+        self.ctx.check(self.ctx.lib.vgx_elevation_map_device_pointers(self.h, *[C.byref(x) for x in p]))
+        return tuple(x.value for x in p)
+
+    def destroy(self):
+        if self.h:
+            self.ctx.lib.vgx_elevation_map_destroy(self.h)
             self.h = None
 
 

@@ -11,88 +11,26 @@
 //   2. planar_row_kernel: g[y][x] = the distance in cells to the nearest obstacle cell of row y within R, or none (u16)
 //   3. planar_column_kernel: d2 = min over |dy| <= R of dy^2 + g[y + dy][x]^2 (int), left once dy^2 >= the best so far;
 //      then sqrtf, the voxel size and the clip
-// A fixed number of launches whatever the size.  The source layouts are those of the layer clouds (vgx_cloud_src.h).
+// A fixed number of launches whatever the size.  The source layouts are those of the layer clouds (vgx_cloud_src.h); the
+// box kernel and the two distance passes are shared with the elevation map (vgx_planar_passes.h).
 #include <climits>
 #include <cmath>
 #include <string>
 
 #include "vgx_cloud_src.h"
 #include "vgx_internal.h"
+#include "vgx_planar_passes.h"
 #include "vgx_tsdf_internal.h"
 
 #pragma clang fp contract(off)
 
 namespace vgx {
 
-constexpr int kPlanarTile = 16;         // gather: cells per workgroup side
-constexpr int kPlanarPassX = 32;        // row and column passes: a workgroup is 32 x 8 cells
-constexpr int kPlanarPassY = 8;
-constexpr uint16_t kPlanarNone = 0xffffu;
-constexpr int kPlanarMaxR = 2048;
-constexpr int32_t kPlanarBoxInit = 0x7f7f7f7f;  // what a memset of 0x7f leaves: above every block index (|index| < 2^28)
-
-// the layer's dense block table: [dim.z][dim.y][dim.x] -> slot of the block pool, or < 0
-struct PlanarTable {
-  const int32_t* lut;
-  int32_t lut_min[3], lut_dim[3];
-  int32_t slots;  // of the block pool: an entry at or beyond it is never followed
-};
-
 struct PlanarRule {
   float z_min, z_max, occupied_distance, min_weight, max_distance_m;
   int32_t min_free_voxels, unknown_is_obstacle, R;
   int32_t bz_lo, bz_hi;  // the z blocks of the table with a row in the band lie in [bz_lo, bz_hi] (empty: lo > hi)
 };
-
-struct PlanarBox {
-  int32_t x0, y0, W, H;
-  long long tx0, ty0;  // x0, y0 rounded down to the gather tile
-  int32_t tiles_x, tiles_y;
-};
-
-// Bit i: row i (on z) of a block with z index bz is in the band, z_min <= cz && cz <= z_max.  From the block index
-// alone: 0 rejects the block before any voxel is read, and the rows of a kept block test their bit -- the same
-// comparison either way.  Host and device (the host finds [bz_lo, bz_hi] with it).
-template <int VPS>
-__host__ __device__ __forceinline__ uint32_t planar_band_rows(float z_min, float z_max, int bz, float vs) {
-  const float origin = (float)bz * ((float)VPS * vs);
-  uint32_t rows = 0;
-#pragma unroll
-  for (int i = 0; i < VPS; ++i) {
-    const float cz = voxel_centre(origin, i, vs);
-    if (z_min <= cz && cz <= z_max) rows |= 1u << i;
-  }
-  return rows;
-}
-
-__device__ __forceinline__ bool planar_obstacle(uint8_t state, int unknown_is_obstacle) {
-  return state == 2 || (unknown_is_obstacle != 0 && state == 0);
-}
-
-// box[4] = min of {bx, by, -bx, -by} over the live blocks with a row in the band (kPlanarBoxInit where there is none)
-template <int VPS>
-__global__ __launch_bounds__(256) void planar_box_kernel(CloudSrc s, PlanarRule r, int slots, int32_t* __restrict__ box) {
-  const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
-  int v[4] = {INT_MAX, INT_MAX, INT_MAX, INT_MAX};
-  if (b < (long long)cloud_live_blocks(s, slots)) {
-    const int32_t* bi = s.block_index + 3 * (size_t)b;
-    if (planar_band_rows<VPS>(r.z_min, r.z_max, bi[2], s.voxel_size) != 0u) {
-      v[0] = bi[0];
-      v[1] = bi[1];
-      v[2] = -bi[0];
-      v[3] = -bi[1];
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] = min(v[k], __shfl_xor(v[k], o));
-  }
-  if ((threadIdx.x & 63) == 0 && v[0] != INT_MAX) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) atomicMin(box + k, v[k]);
-  }
-}
 
 template <int VPS, int SRC>
 __global__ __launch_bounds__(256) void planar_gather_kernel(CloudSrc s, PlanarTable t, PlanarRule r, PlanarBox b,
@@ -161,59 +99,6 @@ __global__ __launch_bounds__(256) void planar_gather_kernel(CloudSrc s, PlanarTa
   if (threadIdx.x < 3 && s_tot[threadIdx.x]) atomicAdd(totals + threadIdx.x, (unsigned long long)s_tot[threadIdx.x]);
 }
 
-__global__ __launch_bounds__(256) void planar_row_kernel(const uint8_t* __restrict__ state, int W, int H, int tiles_x, int R,
-                                                         int unknown_is_obstacle, uint16_t* __restrict__ g) {
-  const int x = kPlanarPassX * (int)(blockIdx.x % (unsigned)tiles_x) + (int)(threadIdx.x % kPlanarPassX);
-  const int y = kPlanarPassY * (int)(blockIdx.x / (unsigned)tiles_x) + (int)(threadIdx.x / kPlanarPassX);
-  if (x >= W || y >= H) return;
-  const uint8_t* row = state + (size_t)y * (size_t)W;
-  int best = kPlanarNone;
-  if (planar_obstacle(row[x], unknown_is_obstacle)) {
-    best = 0;
-  } else {
-    for (int k = 1; k <= R; ++k) {
-      const bool left = x - k >= 0, right = x + k < W;
-      if (!left && !right) break;
-      if ((left && planar_obstacle(row[x - k], unknown_is_obstacle)) || (right && planar_obstacle(row[x + k], unknown_is_obstacle))) {
-        best = k;
-        break;
-      }
-    }
-  }
-  g[(size_t)y * (size_t)W + (size_t)x] = (uint16_t)best;
-}
-
-__global__ __launch_bounds__(256) void planar_column_kernel(const uint16_t* __restrict__ g, int W, int H, int tiles_x, int R,
-                                                            float voxel_size, float max_distance_m, float* __restrict__ distance) {
-  const int x = kPlanarPassX * (int)(blockIdx.x % (unsigned)tiles_x) + (int)(threadIdx.x % kPlanarPassX);
-  const int y = kPlanarPassY * (int)(blockIdx.x / (unsigned)tiles_x) + (int)(threadIdx.x / kPlanarPassX);
-  if (x >= W || y >= H) return;
-  const uint16_t* col = g + (size_t)x;
-  int best = INT_MAX;  // none
-  const int g0 = col[(size_t)y * (size_t)W];
-  if (g0 != kPlanarNone) best = g0 * g0;
-  for (int dy = 1; dy <= R; ++dy) {
-    const int dy2 = dy * dy;
-    if (dy2 >= best) break;  // no later row can be nearer
-    const bool up = y - dy >= 0, down = y + dy < H;
-    if (!up && !down) break;
-    if (up) {
-      const int gg = col[(size_t)(y - dy) * (size_t)W];
-      if (gg != kPlanarNone) best = min(best, dy2 + gg * gg);
-    }
-    if (down) {
-      const int gg = col[(size_t)(y + dy) * (size_t)W];
-      if (gg != kPlanarNone) best = min(best, dy2 + gg * gg);
-    }
-  }
-  float out = max_distance_m;
-  if (best != INT_MAX) {
-    const float m = sqrtf((float)best) * voxel_size;
-    out = m < max_distance_m ? m : max_distance_m;
-  }
-  distance[(size_t)y * (size_t)W + (size_t)x] = out;
-}
-
 }  // namespace vgx
 
 using namespace vgx;
@@ -248,8 +133,6 @@ struct vgx_planar_map_s {
 
 namespace {
 
-constexpr long long kPlanarMaxCells = 1ll << 28;
-
 // Refusals shared by the two producers, before anything is written; the rule comes back without its z blocks.
 int planar_check(vgx_ctx ctx, const char* fn, const vgx_planar_map_config* cfg, vgx_planar_map M, float voxel_size, PlanarRule* rule) {
   auto fail = [ctx, fn](const std::string& msg) { return set_error(ctx, VGX_ERR_INVALID, std::string(fn) + ": " + msg); };
@@ -276,16 +159,6 @@ int planar_check(vgx_ctx ctx, const char* fn, const vgx_planar_map_config* cfg, 
   return VGX_OK;
 }
 
-// ix = block_x * vps + local_x must fit int32 for every block the table can hold, on x and y
-bool planar_table_fits(const int32_t lut_min[3], const int32_t lut_dim[3], int vps) {
-  for (int a = 0; a < 2; ++a) {
-    if (lut_dim[a] <= 0) continue;
-    const long long lo = (long long)lut_min[a] * vps, hi = ((long long)lut_min[a] + lut_dim[a]) * vps - 1;
-    if (lo < (long long)INT32_MIN || hi > (long long)INT32_MAX) return false;
-  }
-  return true;
-}
-
 int ensure_cells(vgx_planar_map M, size_t n) {
   if (!M->d_meta.p) {
     const hipError_t e = M->d_meta.alloc(64);
@@ -307,22 +180,11 @@ void launch_gather(hipStream_t st, const CloudSrc& s, const PlanarTable& t, cons
                      M->d_meta.as<unsigned long long>());
 }
 
-long long floor_to(long long v, long long m) { return v >= 0 ? v / m * m : -((-v + m - 1) / m) * m; }
-
 // The passes on stream st (the caller holds the map's and the stream's locks, the device is set).  `slots`: block slots
 // of the pool; s.live_blocks says how many of them are blocks where only the device knows.
 int planar_generate(vgx_ctx ctx, const char* fn, hipStream_t st, int src, int vps, const CloudSrc& s, const PlanarTable& t,
                     PlanarRule r, const vgx_planar_map_config& cfg, int slots, vgx_planar_map M) {
-  // the table's z blocks with a row in the band: the very comparison of the kernels
-  if (t.lut_dim[0] > 0 && t.lut_dim[1] > 0)
-    for (int k = 0; k < t.lut_dim[2]; ++k) {
-      const int bz = t.lut_min[2] + k;
-      const uint32_t rows = vps == 16 ? planar_band_rows<16>(r.z_min, r.z_max, bz, s.voxel_size)
-                                      : planar_band_rows<8>(r.z_min, r.z_max, bz, s.voxel_size);
-      if (rows == 0u) continue;
-      if (r.bz_lo > r.bz_hi) r.bz_lo = bz;
-      r.bz_hi = bz;
-    }
+  planar_band_blocks(t, vps, r.z_min, r.z_max, s.voxel_size, &r.bz_lo, &r.bz_hi);
   if (!M->d_meta.p) {
     const int rc = ensure_cells(M, 0);
     if (rc != VGX_OK) return rc;
@@ -334,50 +196,22 @@ int planar_generate(vgx_ctx ctx, const char* fn, hipStream_t st, int src, int vp
   bool boxed = false;
   unsigned long long* d_totals = M->d_meta.as<unsigned long long>();
   int32_t* d_box = reinterpret_cast<int32_t*>(static_cast<char*>(M->d_meta.p) + 32);
-  long long x0 = 0, y0 = 0, W = 0, H = 0;
-  if (cfg.use_box != 0) {
-    x0 = cfg.cell_min[0];
-    y0 = cfg.cell_min[1];
-    W = cfg.cell_dim[0];
-    H = cfg.cell_dim[1];
-  } else if (slots > 0 && r.bz_lo <= r.bz_hi) {
-    int32_t box[4];
-    VGX_HIP(ctx, hipMemsetAsync(d_box, 0x7f, 16, st));
-    const unsigned groups = (unsigned)(((long long)slots + 255) / 256);
-    if (timing) VGX_HIP(ctx, hipEventRecord(M->ev[0], st));
-    if (vps == 16) hipLaunchKernelGGL(planar_box_kernel<16>, dim3(groups), dim3(256), 0, st, s, r, slots, d_box);
-    else hipLaunchKernelGGL(planar_box_kernel<8>, dim3(groups), dim3(256), 0, st, s, r, slots, d_box);
-    VGX_HIP(ctx, hipGetLastError());
-    if (timing) VGX_HIP(ctx, hipEventRecord(M->ev[1], st));
-    boxed = timing;
-    VGX_HIP(ctx, hipMemcpyAsync(box, d_box, 16, hipMemcpyDeviceToHost, st));
-    VGX_HIP(ctx, hipStreamSynchronize(st));
-    if (box[0] != kPlanarBoxInit) {
-      x0 = (long long)box[0] * vps;
-      y0 = (long long)box[1] * vps;
-      W = ((long long)-box[2] - box[0] + 1) * vps;
-      H = ((long long)-box[3] - box[1] + 1) * vps;
-    }
-    if (W * H > kPlanarMaxCells) return set_error(ctx, VGX_ERR_INVALID, std::string(fn) + ": the band's blocks span more than 2^28 cells");
-  }
+  long long box[4];
+  int rc = planar_find_box(ctx, fn, st, vps, s, r.z_min, r.z_max, r.bz_lo <= r.bz_hi, slots, cfg.use_box, cfg.cell_min, cfg.cell_dim, d_box,
+                           timing ? M->ev : nullptr, box, &boxed);
+  if (rc != VGX_OK) return rc;
+  boxed = boxed && timing;
+  const long long x0 = box[0], y0 = box[1], W = box[2], H = box[3];
   const size_t cells = (size_t)(W * H);
   // from here on the map is replaced
   M->W = M->H = 0;
   M->counts[0] = M->counts[1] = M->counts[2] = 0;
   M->pass_ms[0] = M->pass_ms[1] = M->pass_ms[2] = M->pass_ms[3] = 0.0f;
-  int rc = ensure_cells(M, cells);
+  rc = ensure_cells(M, cells);
   if (rc != VGX_OK) return rc;
   unsigned long long totals[3] = {0, 0, 0};
   if (cells > 0) {
-    PlanarBox b{};
-    b.x0 = (int32_t)x0;
-    b.y0 = (int32_t)y0;
-    b.W = (int32_t)W;
-    b.H = (int32_t)H;
-    b.tx0 = floor_to(x0, kPlanarTile);
-    b.ty0 = floor_to(y0, kPlanarTile);
-    b.tiles_x = (int32_t)((x0 + W - b.tx0 + kPlanarTile - 1) / kPlanarTile);
-    b.tiles_y = (int32_t)((y0 + H - b.ty0 + kPlanarTile - 1) / kPlanarTile);
+    const PlanarBox b = planar_make_box(x0, y0, W, H);
     VGX_HIP(ctx, hipMemsetAsync(d_totals, 0, 24, st));
     if (timing) VGX_HIP(ctx, hipEventRecord(M->ev[2], st));
     if (vps == 16) {
@@ -393,7 +227,8 @@ int planar_generate(vgx_ctx ctx, const char* fn, hipStream_t st, int src, int vp
     if (timing) VGX_HIP(ctx, hipEventRecord(M->ev[3], st));
     const int ptx = (int)((W + kPlanarPassX - 1) / kPlanarPassX), pty = (int)((H + kPlanarPassY - 1) / kPlanarPassY);
     const dim3 grid((unsigned)ptx * (unsigned)pty);
-    hipLaunchKernelGGL(planar_row_kernel, grid, dim3(256), 0, st, M->d_state.as<uint8_t>(), (int)W, (int)H, ptx, r.R, r.unknown_is_obstacle,
+    hipLaunchKernelGGL(planar_row_kernel<PlanarObstacle>, grid, dim3(256), 0, st, M->d_state.as<uint8_t>(), (int)W, (int)H, ptx, r.R,
+                       PlanarObstacle{r.unknown_is_obstacle},
                        M->d_g.as<uint16_t>());
     VGX_HIP(ctx, hipGetLastError());
     if (timing) VGX_HIP(ctx, hipEventRecord(M->ev[4], st));
@@ -523,25 +358,11 @@ int vgx_submap_layer_planar_map(vgx_submap sm, int32_t layer, const vgx_planar_m
   // the submap's layers and block table are read under the registration lock: another thread may release or generate them
   std::lock_guard<std::mutex> map_lk(M->mu);
   std::lock_guard<std::mutex> reg_lk(ctx->mu);
-  if (sm->n_blocks > 0 && (tsdf ? (!sm->d_tsdf_distance || !sm->d_tsdf_weight) : (!sm->d_esdf_distance || !sm->d_esdf_observed)))
-    return set_error(ctx, VGX_ERR_INVALID,
-                     std::string(kFn) + (tsdf ? ": TSDF" : ": ESDF") + " layer not resident (released, or never generated)");
-  if (sm->vps != 8 && sm->vps != 16) return set_error(ctx, VGX_ERR_UNSUPPORTED, std::string(kFn) + ": voxels_per_side must be 8 or 16");
-  if (!planar_table_fits(sm->lut_min, sm->lut_dim, sm->vps))
-    return set_error(ctx, VGX_ERR_INVALID, std::string(kFn) + ": block indices overflow the int32 voxel index");
-  VGX_HIP(ctx, hipSetDevice(ctx->device));
   CloudSrc s{};
-  s.block_index = sm->d_block_index;
-  s.dist = tsdf ? sm->d_tsdf_distance : sm->d_esdf_distance;
-  s.seen = tsdf ? (const void*)sm->d_tsdf_weight : (const void*)sm->d_esdf_observed;
-  s.voxel_size = sm->voxel_size;
   PlanarTable t{};
-  t.lut = sm->d_lut;
-  for (int a = 0; a < 3; ++a) {
-    t.lut_min[a] = sm->lut_min[a];
-    t.lut_dim[a] = sm->n_blocks > 0 ? sm->lut_dim[a] : 0;
-  }
-  t.slots = sm->n_blocks;
+  rc = planar_submap_source(sm, tsdf, kFn, &s, &t);
+  if (rc != VGX_OK) return rc;
+  VGX_HIP(ctx, hipSetDevice(ctx->device));
   return planar_generate(ctx, kFn, ctx->stream, tsdf ? kCloudSrcTsdf : kCloudSrcEsdf, sm->vps, s, t, rule, *cfg, sm->n_blocks, M);
 }
 
@@ -555,25 +376,11 @@ int vgx_tsdf_layer_planar_map(vgx_tsdf_layer L, const vgx_planar_map_config* cfg
   std::lock_guard<std::mutex> map_lk(M->mu);
   std::lock_guard<std::mutex> tsdf_lk(ctx->tsdf_mu);
   VGX_HIP(ctx, hipSetDevice(ctx->device));
-  const TsdfLayerDev& d = L->dev;
-  if (d.vps != 8 && d.vps != 16) return set_error(ctx, VGX_ERR_UNSUPPORTED, std::string(kFn) + ": voxels_per_side must be 8 or 16");
-  if (!planar_table_fits(d.lut_min, d.lut_dim, d.vps))
-    return set_error(ctx, VGX_ERR_INVALID, std::string(kFn) + ": block indices overflow the int32 voxel index");
   CloudSrc s{};
-  s.block_index = d.block_index;
-  // behind the scans and merges queued on the TSDF stream, whose allocation counter only the device knows
-  s.live_blocks = d.n_blocks;
-  s.live_blocks_is_64 = 0;
-  s.words = d.voxels;
-  s.rgba = d.rgba;
-  s.voxel_size = d.voxel_size;
   PlanarTable t{};
-  t.lut = d.lut;
-  for (int a = 0; a < 3; ++a) {
-    t.lut_min[a] = d.lut_min[a];
-    t.lut_dim[a] = d.lut ? d.lut_dim[a] : 0;
-  }
-  t.slots = d.max_blocks;
+  rc = planar_layer_source(L, kFn, &s, &t);
+  if (rc != VGX_OK) return rc;
+  const TsdfLayerDev& d = L->dev;
   return planar_generate(ctx, kFn, ctx->tsdf_stream, kCloudSrcPacked, d.vps, s, t, rule, *cfg, d.max_blocks, M);
 }
 
