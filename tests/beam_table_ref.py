@@ -115,6 +115,32 @@ class BeamModel:
         return d.reshape(-1, 3).astype(F)
 
 
+BINS = 256                                    # kBeamBins of voxgraph_amd/csrc/vgx_range_image.hip
+
+
+def coarse_table(m):
+    """the coarse table in front of the row walk, as beam_model_check states its construction (the rule itself is stated
+    without any search): -> (bin_scale f32, first u8 [BINS]).  BINS bins from lo_0 to hi_{H-1}, the scale clamped to 1e6;
+    a bin's entry is the largest row whose lo is at or below the lower edge of the bin BEFORE it."""
+    lo = m.lo.astype(np.float64)
+    scale = min(F(BINS / (float(m.hi[-1]) - lo[0])), F(1e6))
+    edges = lo[0] + np.arange(-1, BINS - 1) / float(scale)                  # of the bin before each bin
+    first = np.maximum(np.searchsorted(lo, edges, side="right") - 1, 0)
+    first[0] = 0
+    assert first.max() <= 255
+    return F(scale), first.astype(np.uint8)
+
+
+def walk_length(m, el):
+    """for f32 elevations at or above lo_0: (the row the rule answers, the coarse table's entry of the elevation's bin) --
+    their difference is how far the walk behind the table goes: 0 no step, 1 .. 3 one trip, 6 or more at least two"""
+    el = np.asarray(el, F)
+    scale, first = coarse_table(m)
+    t = (el - m.lo[0]) * scale
+    b = np.where(t < F(BINS - 1), t, BINS - 1).astype(np.int64)
+    return np.searchsorted(m.lo, el, side="right") - 1, first[b].astype(np.int64)
+
+
 def uniform_as_table(m):
     """the table that restates a uniform range_image_ref.Model's row centres (offsets zero, the limit inf)"""
     el = float(m.elevation_first_rad) + np.arange(m.height) * ((float(m.elevation_last_rad) - float(m.elevation_first_rad)) / (m.height - 1))

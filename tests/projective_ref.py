@@ -146,7 +146,7 @@ class Layer:
         return L
 
     def download(self):
-        return self.block_index, self.distance, self.weight, self.rgba[..., None].view(np.uint8).reshape(len(self.rgba), -1, 4)
+        return self.block_index, self.distance, self.weight, self.rgba[..., None].view(np.uint8).reshape(len(self.rgba), self.vps ** 3, 4)   # (no -1: a layer without blocks)
 
 
 class Frame:

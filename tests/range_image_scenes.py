@@ -2,7 +2,8 @@
 +x wall has an opening onto a far wall beyond max_ray_length_m, with planted points: pixels without a return, a
 zero-length point, second returns in a pixel (nearer, farther and bit-equal), a point above the rows, a return shorter
 than min_ray_length_m, points on the +-pi seam.  Rendered in f64 from plane equations; needs no device.  The sensor
-frame is x forward, y left, z up."""
+frame is x forward, y left, z up.  SENSOR_MODELS and SENSOR_CASES: the same room seen by sensors of real sizes, up to the
+4096 x 256 the check accepts (profiles/range_image_sensor_sizes.txt)."""
 import numpy as np
 
 from tests import range_image_ref as R
@@ -22,6 +23,21 @@ MODELS = {
     "128x16": R.Model(128, 16, -1.0, 0, -0.4, 0.5),
 }
 TILTED = pose(qmul(quat([0, 0, 1], 0.6), quat([1, 0.3, 0], 0.12)), [0.2, -0.1, 0.15])
+# the sizes of real sensors, up to the limit vgx_range_image_check accepts (pitches down to 1.5 mrad)
+SENSOR_MODELS = {
+    # clockwise, column 0 looks backwards, the top row first, +-22.5 degrees
+    "1024x64": R.Model(1024, 64, PI32, 1, 0.3927, -0.3927),
+    # counter-clockwise from an odd azimuth, the bottom row first
+    "2048x128": R.Model(2048, 128, -1.0, 0, -0.4, 0.5),
+    # the limit: pitches of 1.53 mrad in both angles
+    "4096x256": R.Model(4096, 256, 2.5, 1, 0.196, -0.195),
+    # a width that is no power of two, +-15 degrees
+    "1800x16": R.Model(1800, 16, 0.7, 0, -0.2618, 0.2618),
+    # a field of view of 0.02 rad: the two cones nearly meet
+    "512x4": R.Model(512, 4, 0.0, 1, -0.01, 0.01),
+    # looking up only: both cones on one side, the top one near the axis
+    "360x32_up": R.Model(360, 32, 0.3, 0, 0.6, 1.5),
+}
 
 
 def ranges(dirs, T=IDENTITY):
@@ -111,3 +127,34 @@ def case(name):
 def track(n=5):
     """poses along a short track through the room"""
     return [pose(quat([0, 0, 1], 0.15 * k), [0.1 * k, -0.05 * k, 0.02 * k]) for k in range(n)]
+
+
+# name -> (sensor model, the room far from the origin, vps): two scans into one layer each, 0.1 m voxels, rays up to 4 m
+SENSOR_CASES = {
+    "1024x64": ("1024x64", False, 8),
+    "2048x128": ("2048x128", False, 8),
+    "4096x256": ("4096x256", False, 8),
+    "1800x16": ("1800x16", False, 8),
+    "512x4": ("512x4", False, 8),
+    "360x32_up": ("360x32_up", False, 8),
+    "1024x64_vps16": ("1024x64", False, 16),
+    "4096x256_far": ("4096x256", True, 8),
+}
+
+
+def sensor_poses(far=False):
+    """-> [(the pose the room is seen from, the pose the scan is integrated at)]: TILTED, then a moved pose of track()"""
+    return [(np.asarray(T, F), np.asarray(far_from_origin(T) if far else T, F)) for T in (TILTED, track()[2])]
+
+
+def sensor_scan(m, k, scan_fn=None):
+    """scan k (0 or 1) of a sensor case -> (points, rgba); the same near the origin and far from it"""
+    return (scan_fn or scan)(m, sensor_poses()[k][0], seed=3 + k)
+
+
+def sensor_case(name, cases=None, models=None, scan_fn=None):
+    """-> (Model, [(points, rgba, pose)] of the two scans, Config, voxel size, vps); the three keywords: the beam tables'"""
+    model, far, vps = (cases or SENSOR_CASES)[name]
+    m = (models or SENSOR_MODELS)[model]
+    scans = [(*sensor_scan(m, k, scan_fn), T) for k, (_, T) in enumerate(sensor_poses(far))]
+    return m, scans, config(0.1), 0.1, vps

@@ -2,7 +2,9 @@
 (vgx_range_image_pixel_beams) against the numpy restatement (tests/beam_table_ref.py) and on hand-worked directions, the
 round trip of vgx_view_rays_lidar_beams, vgx_tsdf_range_image_box_beams against the restatement's box and that box against
 every voxel the rules update, every refusal, the new symbols, and that the scenes of tests/test_beam_table_gpu.py reach every
-branch of the rules -- a direction and a voxel in a hole between two rows included."""
+branch of the rules -- a direction and a voxel in a hole between two rows included.  At sensor sizes (S.SENSOR_MODELS, up to
+256 rows): that the tables reach every arm of the row walk, two trips round its loop, a table entry above 127 and the clamped
+scale; the host pixel rule on every lo_k and hi_k and the rule's own column boundaries; every pixel-centre ray; the box."""
 import ctypes as C
 import os
 import re
@@ -13,7 +15,7 @@ import pytest
 
 from tests import beam_table_ref as B
 from tests import beam_table_scenes as S
-from tests.test_range_image_cpu import _poses
+from tests.test_range_image_cpu import _poses, column_and_seam_directions, directions_at_elevations, host_pixels, random_directions
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
@@ -207,6 +209,134 @@ def test_the_box_holds_every_voxel_the_rules_update():
     pts, rgba = S.scan(m, S.TILTED)
     for k, T in enumerate(_poses()[::2]):      # (the room moves with the sensor: the scan is the same, the layer frame is not)
         held(m, pts, rgba, S.config(0.2), T, 0.2, 8, k)
+
+
+# ---- sensor sizes (S.SENSOR_MODELS: up to 256 rows, gaps down to 1 mrad; and the uniform 2048 x 128 sensor as a table)
+
+SENSOR_TABLES = {**S.SENSOR_MODELS, "uniform_2048x128": S.UNIFORM_2048x128}
+# The fields of view of these tables hold too few voxel centres for a thousand updates: 17 m^3 of room are 17 000 voxels of
+# 0.1 m, of which a band of d rad around a cone holds about d / 2 (the room spans some 2 rad of elevation seen from inside
+# it): 2e-3 rad (64 x 2, rows 1e-3 rad apart) some tens, 2e-5 rad (256 x 1 at a limit of 1e-5) none.  The frame is compared
+# on the device all the same: its candidates, its cones and its counts.  Every other integration updates more than 1000.
+LEAST_UPDATES = {"256x1_thin": -1, "64x2_close": 20}
+
+
+def _elevations(pts):
+    """the angle rule's elevation of every point with a range"""
+    x, y, z = pts[:, 0], pts[:, 1], pts[:, 2]
+    return B.atan2_rule(z, np.sqrt(x * x + y * y))[B.norm3(x, y, z) > 0]
+
+
+def test_the_sensor_tables_reach_the_whole_row_search():
+    """no scene passes on nothing: the scan directions of the sensor tables take the row walk behind the coarse table through
+    no step, each of its three arms and two trips round its loop; a table entry above 127; the clamped scale"""
+    met = {}
+    for name, m in S.SENSOR_MODELS.items():
+        assert m.check() == B.OK, name
+        el = _elevations(S.scan(m, S.TILTED)[0])
+        k, entry = B.walk_length(m, el[el >= m.lo[0]])
+        assert (k >= entry).all()                                       # (an entry never overshoots)
+        met[name] = sorted(set((k - entry).tolist()))
+    print("answer row - table entry, per sensor table:", met)
+    every = set().union(*met.values())
+    assert {0, 1, 2, 3} <= every and max(every) >= 6
+    assert max(met["512x256_descending"]) >= 2                         # (beyond the first arm with first[] entries above 127)
+    # the tables of tests/beam_table_scenes.py MODELS end in the first arm or without a step: what these scenes add
+    for m in S.MODELS.values():
+        k, entry = B.walk_length(m, np.linspace(float(m.lo[0]), float(m.hi[-1]), 100_001).astype(F)[1:])
+        assert (k - entry).max() <= 1
+    assert B.coarse_table(S.SENSOR_MODELS["512x256_descending"])[1].max() > 127
+    thin = S.SENSOR_MODELS["256x1_thin"]
+    span = float(thin.hi[-1]) - float(thin.lo[0])
+    assert B.BINS / span > 1e6 and B.coarse_table(thin)[0] == F(1e6)
+    pts, rgba = S.scan(thin, S.TILTED)
+    img = B.build(thin, pts, rgba)
+    t = (_elevations(pts)[img.pixel_of_point[B.norm3(*pts.T) > 0] >= 0] - thin.lo[0]) * F(1e6)
+    # (the row is bins 0 .. 20 of the 256; the scan's returns, 0.3 half extents around its centre, fall into several of them)
+    assert img.counts["n_filled"] > 200 and 0 <= t.min() and t.max() <= 20 and len(np.unique(t.astype(int))) >= 5
+
+
+@pytest.mark.parametrize("name", list(SENSOR_TABLES))
+def test_host_pixel_rule_equals_the_restatement_at_sensor_sizes(capi, name):
+    """bit for bit (pixels are integers): 1e5 random directions, directions whose elevation by the angle rule is every lo_k
+    and hi_k and its f32 neighbours, the rule's own column boundaries in five rows, and either side of the seam"""
+    m = SENSOR_TABLES[name]
+    assert m.check() == B.OK
+    near, exact = directions_at_elevations(np.concatenate([m.lo, m.hi]), az=0.3)
+    rows = np.unique(np.linspace(0, m.height - 1, 5).astype(int))
+    columns, straddled = column_and_seam_directions(m, m.offsets[rows], m.row_elevation_rad[rows].astype(np.float64), B.beam_pixel)
+    p = np.concatenate([random_directions(6, float(m.lo[0]), float(m.hi[-1])), near, columns])
+    ui, vi, ok = B.beam_pixel(m, p[:, 0], p[:, 1], p[:, 2])
+    got = host_pixels(capi.load().vgx_range_image_pixel_beams, m.capi(capi), p)
+    assert np.array_equal(got[:, 0], ui) and np.array_equal(got[:, 1], vi), name
+    assert ok.sum() > 10_000 and (~ok).sum() > 10_000 and ((ui < 0) == (vi < 0)).all()
+    assert len(np.unique(vi[ok])) == m.height and len(np.unique(ui[ok])) == m.width and straddled == len(rows) * m.width
+    # a boundary met bit-equal belongs to the row above it (or, the top row's hi and the upper edge of a hole: to none)
+    on = B.atan2_rule(near[:, 2], np.sqrt(near[:, 0] * near[:, 0] + near[:, 1] * near[:, 1]))[:2 * m.height]
+    hit = on == np.concatenate([m.lo, m.hi])
+    assert exact == hit.sum() > m.height // 4
+    k = np.arange(m.height)
+    row_of = (m.height - 1 - k) if m.descending else k
+    v_on = vi[100_000:100_000 + 2 * m.height]
+    assert np.array_equal(v_on[:m.height][hit[:m.height]], row_of[hit[:m.height]])
+    meets = np.append(m.hi[:-1] == m.lo[1:], False)                   # hi_k is lo_{k+1}: the row above; else no row
+    want_hi = np.where(meets, np.roll(row_of, -1), -1)
+    assert np.array_equal(v_on[m.height:][hit[m.height:]], want_hi[hit[m.height:]])
+    print(f"{name}: {len(p)} directions, {exact} of {2 * m.height} row boundaries met bit-equal")
+
+
+@pytest.mark.parametrize("name", list(SENSOR_TABLES))
+def test_every_pixel_centre_ray_maps_back_to_its_own_pixel_at_sensor_sizes(capi, name):
+    """every ray of vgx_view_rays_lidar_beams, formed in f64 and rounded once, through the f32 rule: its own pixel, for all
+    pixels -- exact by construction, as in the uniform test"""
+    m = SENSOR_TABLES[name]
+    d = m.rays()
+    v, u = np.meshgrid(np.arange(m.height), np.arange(m.width), indexing="ij")
+    ui, vi, ok = B.beam_pixel(m, d[:, 0], d[:, 1], d[:, 2])
+    misses = int(((ui != u.ravel()) | (vi != v.ravel())).sum())
+    print(f"{name}: {misses} misses over {len(d)} pixel-centre rays")
+    assert misses == 0
+    got = capi.view_rays_lidar_beams(m.capi(capi))                       # the library's own rays through its own host rule
+    pick =np.unique(np.concatenate([np.arange(0, len(d), 61), np.arange(m.height) * m.width, np.arange(1, m.height + 1) * m.width - 1]))
+    px = host_pixels(capi.load().vgx_range_image_pixel_beams, m.capi(capi), got[pick])
+    assert np.array_equal(px[:, 0], u.ravel()[pick]) and np.array_equal(px[:, 1], v.ravel()[pick])
+
+
+@pytest.mark.parametrize("name", list(S.SENSOR_MODELS))
+def test_the_box_holds_every_voxel_the_rules_update_at_sensor_sizes(capi, name):
+    """the method of test_the_box_holds_every_voxel_the_rules_update where the widest row is a few mrad and the box's widening
+    a fraction of a voxel: near the origin and far from it, with the LIBRARY's box (host only), which is the restatement's"""
+    m = S.SENSOR_MODELS[name]
+    pts, rgba = S.scan(m, S.TILTED)
+    img, cfg, vs, vps = B.build(m, pts, rgba), S.config(0.1), 0.1, 8
+    for T in (S.TILTED, S.far_from_origin(S.TILTED)):
+        T = np.asarray(T, F)
+        rc, lo, hi = capi.range_image_box_beams(m.capi(capi), img.counts, cfg.capi(capi), T, vs, vps)
+        code, rlo, rhi = B.box(m, img.counts, cfg, T, vs, vps)
+        assert rc == code == capi.OK and np.array_equal(lo, rlo) and np.array_equal(hi, rhi), (name, T, lo, rlo, hi, rhi)
+        fr = B.integrate(B.Layer(vs, vps), T, img, cfg, lo_hi=(lo - 2, hi + 2))
+        blocks = fr.voxel[fr.branch >= B.UPDATED] // vps
+        assert len(blocks) > LEAST_UPDATES.get(name, 1000) and (blocks > lo).all() and (blocks < hi).all(), (name, T)
+
+
+def test_the_sensor_sized_gpu_scenes_pass_on_something():
+    """what the sensor-sized tests of tests/test_beam_table_gpu.py build and integrate, in the restatement alone"""
+    seen = set()
+    for name, (model, _, _) in S.SENSOR_CASES.items():
+        m, scans, cfg, vs, vps = S.sensor_case(name)
+        L = B.Layer(vs, vps)
+        for k, (pts, rgba, T) in enumerate(scans):
+            img = B.build(m, pts, rgba)
+            c = img.counts
+            assert c["n_filled"] > 0.9 * m.width * m.height and c["n_collided"] >= 4 and c["n_rejected_range"] == 1 and c["n_rejected_rows"] >= 1
+            fr = B.integrate(L, T, img, cfg)
+            seen |= set(np.unique(fr.branch).tolist())
+            assert fr.counts["n_updates"] > LEAST_UPDATES.get(model, 1000) and fr.counts["n_candidate_blocks"] > 200, (name, k, fr.counts)
+            if model not in LEAST_UPDATES:
+                assert fr.new_blocks > 10 if k == 0 else fr.held_blocks > 10
+        if S.hole(m) is not None:                          # voxels in the holes between the clusters, rejected by rows
+            assert (fr.branch == B.OUTSIDE_ROWS).sum() > 1000
+    assert {B.UPDATED, B.CARVED, B.CLEARED, B.BEHIND, B.EMPTY_CELL, B.OUTSIDE_ROWS, B.TOO_SHORT, B.CLEAR_REFUSED} <= seen
 
 
 def test_refusals_of_the_host_only_calls(capi):

@@ -1,7 +1,8 @@
 """The beam-table range image and its projective integration on the device (vgx_range_image_build_beams and its device
 form, vgx_tsdf_integrate_range_image on a table image; voxgraph_amd/csrc/vgx_range_image.hip) against the numpy restatement
 (tests/beam_table_ref.py), bit for bit: the image's ranges, colours, winning indices and counts; the layer's distance,
-weight, colour, block index in slot order and all five counts of a frame."""
+weight, colour, block index in slot order and all five counts of a frame.  The same at sensor sizes, up to 256 rows and
+rows 1.2 mrad apart: build, full coverage, the uniform 2048 x 128 sensor as a table, two scans a layer, a rendered view."""
 import numpy as np
 import pytest
 
@@ -366,6 +367,101 @@ def test_refusals_leave_the_layer_untouched(capi, ctx, rigs, cases):
     _equal(o.layer, oref)
     assert r.integrate(T) == B.integrate(ref, T, img, cfg).counts          # and the integrator works on
     _equal(r.layer, ref)
+
+
+# ---- sensor sizes (S.SENSOR_MODELS: up to 256 rows, clusters of rows a third of a coarse bin apart -- every arm of the row
+# walk and its loop --, a clamped bin scale; tests/test_beam_table_cpu.py holds that these scenes reach all of that)
+
+@pytest.fixture(scope="module")
+def sensors():
+    """(table name, scan 0 or 1) -> (BeamModel, points, rgba, the restated Image): computed when first asked for, left unchanged"""
+    made = {}
+
+    def get(name, k=0):
+        if (name, k) not in made:
+            m = S.SENSOR_MODELS[name]
+            pts, rgba = S.sensor_scan(m, k)
+            made[name, k] = (m, pts, rgba, B.build(m, pts, rgba))
+        return made[name, k]
+    return get
+
+
+@pytest.mark.parametrize("name", list(S.SENSOR_MODELS))
+def test_sensor_sized_image_equals_the_restatement(rigs, sensors, name):
+    """from a decoded scan counted and from device arrays queued: cells, colours, indices, all counts and the extremes"""
+    m, pts, rgba, want = sensors(name)
+    r = rigs(S.config(0.1), 0.1, 8)
+    assert B.same_counts(r.build(m, pts, rgba), want.counts)
+    _same_image(r.image, want)
+    assert r.build(m, pts[::-1], rgba[::-1], through_scan=False, count=False) is None
+    _same_image(r.image, B.build(m, pts[::-1], rgba[::-1]))
+
+
+@pytest.mark.parametrize("name", list(S.SENSOR_MODELS))
+def test_one_return_per_pixel_centre_fills_every_pixel(capi, rigs, name):
+    m = S.SENSOR_MODELS[name]
+    n = m.width * m.height
+    order = np.random.default_rng(9).permutation(n)
+    pts = (capi.view_rays_lidar_beams(m.capi(capi)) * (1.5 + np.sin(0.01 * np.arange(n))).astype(F)[:, None])[order]
+    r = rigs(S.config(0.1), 0.1, 8)
+    c = r.build(m, pts, np.arange(n, dtype=np.uint32), through_scan=False)
+    assert c["n_filled"] == c["n_kept"] == c["n_points"] == n and c["n_collided"] == c["n_rejected_rows"] == c["n_rejected_range"] == 0
+    rng, rgba, index = r.image.download()
+    index = index.reshape(-1)
+    assert np.array_equal(index[order], np.arange(n))              # every pixel holds its own centre's point: a permutation
+    assert np.array_equal(np.ascontiguousarray(rgba).view(np.uint32).reshape(-1), index.astype(np.uint32))
+    assert np.array_equal(rng.reshape(-1)[order], B.norm3(pts[:, 0], pts[:, 1], pts[:, 2]))
+
+
+def test_the_uniform_2048x128_sensor_given_as_a_table_builds_the_uniform_image(rigs):
+    u, t = U.SENSOR_MODELS["2048x128"], S.UNIFORM_2048x128
+    pts, rgba = U.scan(u, S.TILTED)
+    want = B.build(u, pts, rgba)
+    as_table = B.build(t, pts, rgba)
+    assert Z.same_image((as_table.range, as_table.rgba.view(np.uint8).reshape(u.height, u.width, 4), as_table.index), want) is None
+    r = rigs(S.config(0.1), 0.1, 8)
+    for m, through_scan in ((t, True), (u, False), (t, False)):
+        assert B.same_counts(r.build(m, pts, rgba, through_scan), want.counts)
+        assert Z.same_image(r.image.download(), want) is None
+        assert (r.image.beams() is None) == (m is u)
+
+
+@pytest.mark.parametrize("name", list(S.SENSOR_CASES))
+def test_sensor_sized_scans_equal_the_restatement(rigs, sensors, name):
+    """a scan at TILTED and a second from a moved pose of track() into the same layer: the block index in slot order,
+    distance, weight, colour and the five counts of each frame"""
+    model, far, vps = S.SENSOR_CASES[name]
+    cfg, vs = S.config(0.1), 0.1
+    ref, r = B.Layer(vs, vps), rigs(cfg, vs, vps)
+    for k, (_, T) in enumerate(S.sensor_poses(far)):
+        m, pts, rgba, img = sensors(model, k)
+        want = B.integrate(ref, T, img, cfg).counts
+        r.build(m, pts, rgba, through_scan=k == 1, count=False)
+        assert r.integrate(T) == want
+        _equal(r.layer, ref)
+    assert len(ref.block_index) > 20 or model in S.THIN
+
+
+def test_a_view_rendered_with_the_clustered_tables_rays_fills_its_own_pixels(capi, ctx, rigs, sensors):
+    """test_a_view_rendered_with_the_models_rays_fills_its_own_pixels at 1024 x 128 with rows 1.2 mrad apart"""
+    cfg = S.config(0.1)
+    r = rigs(cfg, 0.1, 8)
+    for k, (_, T) in enumerate(S.sensor_poses()):
+        m, pts, rgba, _ = sensors("1024x128_clustered", k)
+        r.build(m, pts, rgba, count=False)
+        r.integrate(T, count=False)
+    dirs = capi.view_rays_lidar_beams(m.capi(capi))
+    view = capi.View(ctx, capi.view_config(flags=0, s_max=6.0, min_step=0.025, unknown_step=0.1, max_bracket=0.3))
+    try:
+        got = r.layer.render_view(view, S.track(3)[1], dirs).download()
+    finally:
+        view.destroy()
+    hit = got.status == capi.VIEW_HIT
+    assert hit.sum() > 0.3 * len(dirs)
+    pts = np.where(hit[:, None], dirs * got.range[:, None], F(0)).astype(F)       # (a ray without a return: a zero-length point)
+    counts = r.build(m, pts, np.zeros(len(pts), np.uint32), through_scan=False)
+    assert counts["n_collided"] == 0 and counts["n_filled"] == int(hit.sum()) and counts["n_rejected_rows"] == 0
+    assert np.array_equal(r.image.download()[2].reshape(-1), np.where(hit, np.arange(len(dirs)), -1))
 
 
 @pytest.mark.parametrize("seed", range(100))

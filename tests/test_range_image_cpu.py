@@ -1,7 +1,10 @@
 """LiDAR range images without a device: the angle rule's error against f64 atan2 and its host form against the numpy
 restatement (tests/range_image_ref.py) bit for bit, the pixel rule on hand-worked directions, hand-worked voxels on a beam,
 vgx_tsdf_range_image_box (host only) against the restatement's box and that box against every voxel the rules update,
-the new symbols and their refusals, and that the scenes of tests/test_range_image_gpu.py reach every branch of the rules."""
+the new symbols and their refusals, and that the scenes of tests/test_range_image_gpu.py reach every branch of the rules.
+At sensor sizes (S.SENSOR_MODELS, up to 4096 x 256): the host pixel rule against the restatement on random directions and on
+the rule's own row and column boundaries, every pixel-centre ray back into its own pixel, the box against every voxel the
+rules update, and that those scenes pass on something."""
 import ctypes as C
 import os
 import re
@@ -247,6 +250,174 @@ def test_the_box_holds_every_voxel_the_rules_update():
     pts, rgba = S.scan(m, S.TILTED)
     for k, T in enumerate(_poses()):      # (the room moves with the sensor: the scan is the same, the layer frame is not)
         held(m, pts, rgba, S.config(0.2), T, 0.2, 8, k)
+
+
+# ---- sensor sizes (S.SENSOR_MODELS: up to 4096 x 256, pitches down to 1.5 mrad)
+
+def host_pixels(fn, cm, p):
+    """the library's host pixel rule `fn` (vgx_range_image_pixel or its _beams form) on directions p [n][3] -> [n][2] (u, v)"""
+    u, v = C.c_int32(), C.c_int32()
+    pu, pv, ref, out = C.byref(u), C.byref(v), C.byref(cm), np.empty((len(p), 2), np.int64)
+    for k, (x, y, z) in enumerate(p.tolist()):
+        assert fn(ref, x, y, z, pu, pv) == 0
+        out[k] = u.value, v.value
+    return out
+
+
+def random_directions(seed, el_lo, el_hi, n=100_000):
+    """f32 [n][3]: half of them anywhere, half within and just beyond the elevations the rows cover; ranges over 12 octaves"""
+    rng = np.random.default_rng(seed)
+    anywhere = rng.normal(size=(n // 2, 3))
+    anywhere /= np.linalg.norm(anywhere, axis=1)[:, None]
+    pad = 0.2 * (el_hi - el_lo) + min(0.01, el_hi - el_lo)
+    el, az = rng.uniform(el_lo - pad, min(el_hi + pad, 1.57), n - n // 2), rng.uniform(-np.pi, np.pi, n - n // 2)
+    rows = np.stack([np.cos(el) * np.cos(az), np.cos(el) * np.sin(az), np.sin(el)], 1)
+    return (np.concatenate([anywhere, rows]) * np.exp2(rng.uniform(-6, 6, (n, 1)))).astype(F)
+
+
+def directions_at_elevations(targets, az=0.0):
+    """-> (f32 [3 len(targets)][3], how many exact hits): for every f32 elevation in `targets` a direction at azimuth `az`
+    whose elevation BY THE ANGLE RULE is bit-equal to it (where the 81 f32 neighbours of z tried hold one), the one with the
+    largest elevation below it and the one with the smallest above"""
+    b = np.asarray(targets, F).astype(np.float64)
+    ca, sa = np.cos(az), np.sin(az)
+    g = b.copy()                          # the geometric elevation the rule gives `b` for: two steps against its smooth error
+    for _ in range(2):
+        g -= R.atan2_rule(np.sin(g).astype(F), np.cos(g).astype(F)).astype(np.float64) - b
+    x, y = (np.cos(g) * ca).astype(F)[:, None], (np.cos(g) * sa).astype(F)[:, None]
+    z0 = np.sin(g).astype(F)
+    z = (z0.astype(np.float64)[:, None] + np.arange(-40, 41)[None, :] * np.spacing(np.abs(z0)).astype(np.float64)[:, None]).astype(F)
+    x, y = np.broadcast_to(x, z.shape), np.broadcast_to(y, z.shape)
+    el = R.atan2_rule(z, np.sqrt(x * x + y * y)).astype(np.float64)
+    t = b[:, None]
+    rows = np.arange(len(b))
+    on = np.abs(el - t).argmin(1)
+    below = np.where(el < t, el, -np.inf).argmax(1)
+    above = np.where(el > t, el, np.inf).argmin(1)
+    assert (el[rows, below] < b).all() and (el[rows, above] > b).all()
+    pick = np.concatenate([on, below, above])
+    rows3 = np.concatenate([rows, rows, rows])
+    return np.stack([x[rows3, pick], y[rows3, pick], z[rows3, pick]], 1), int((el[rows, on] == b).sum())
+
+
+def column_and_seam_directions(m, offsets, elevations, pixel):
+    """-> (f32 [n][3], the column boundaries straddled): for every given (azimuth offset, elevation) row and every column
+    boundary of it, the four neighbouring directions, of 129 spaced 5e-8 rad around the boundary's f64 azimuth, between which
+    `pixel` (the restated rule) changes the column -- the rule's OWN boundary, two directions either side; and directions
+    either side of the +-pi seam"""
+    out, straddled = [], 0
+    u = np.arange(m.width)
+    for off, e in zip(offsets, elevations):
+        az = (float(m.azimuth_first_rad) + float(off) + (u - 0.5) / float(m.su))[:, None] + np.arange(-64, 65)[None, :] * 5e-8
+        d = np.stack([np.cos(az) * np.cos(e), np.sin(az) * np.cos(e), np.sin(e) + 0 * az], -1).astype(F)
+        ui = pixel(m, d[..., 0], d[..., 1], d[..., 2])[0]
+        change = ui[:, 1:] != ui[:, :-1]
+        straddled += int(change.any(1).sum())
+        j = change.argmax(1)[:, None] + np.arange(-1, 3)[None, :]
+        out.append(d[u[:, None], np.clip(j, 0, 128)].reshape(-1, 3))
+        tiny = np.array([0.0, -0.0, 1e-30, -1e-30, 1e-7, -1e-7, 1e-5, -1e-5, 1e-3, -1e-3], F)
+        for r in (1.0, 3.7):
+            out.append(np.stack([np.full(10, -r, F), tiny * F(r), np.full(10, r * np.tan(e), F)], 1))
+    return np.concatenate(out).astype(F), straddled
+
+
+def _row_edges(m):
+    """the f64 elevations of the uniform rows' boundaries, half a pitch beyond the first and the last centre included"""
+    return float(m.elevation_first_rad) + (np.arange(m.height + 1) - 0.5) / float(m.sv)
+
+
+@pytest.mark.parametrize("name", list(S.SENSOR_MODELS))
+def test_host_pixel_rule_equals_the_restatement_at_sensor_sizes(capi, name):
+    """bit for bit (pixels are integers): 1e5 random directions, directions on every row boundary by the angle rule's own
+    elevation and its f32 neighbours, on every column boundary, and either side of the seam"""
+    m = S.SENSOR_MODELS[name]
+    assert m.check() == R.OK
+    edges = _row_edges(m)
+    rows = np.unique(np.linspace(0, m.height - 1, 5).astype(int))
+    centres = float(m.elevation_first_rad) + rows / float(m.sv)
+    near, exact = directions_at_elevations(edges.astype(F), az=0.3)
+    columns, straddled = column_and_seam_directions(m, np.zeros(len(rows)), centres, R.pixel)
+    p = np.concatenate([random_directions(5, edges.min(), edges.max()), near, columns])
+    assert len(p) >= 100_000 + 3 * (m.height + 1) + 4 * len(rows) * m.width
+    ui, vi, ok = R.pixel(m, p[:, 0], p[:, 1], p[:, 2])
+    got = host_pixels(capi.load().vgx_range_image_pixel, m.capi(capi), p)
+    assert np.array_equal(got[:, 0], ui) and np.array_equal(got[:, 1], vi), name
+    # nothing passed on nothing: rows and no rows, every column and every row met, every column boundary straddled
+    assert ok.sum() > 10_000 and (~ok).sum() > 10_000 and (vi[~ok] == -1).all()
+    assert len(np.unique(ui)) == m.width and len(np.unique(vi[ok])) == m.height and straddled == len(rows) * m.width
+    print(f"{name}: {len(p)} directions, {exact} of {m.height + 1} row boundaries met bit-equal")
+
+
+@pytest.mark.parametrize("name", list(S.SENSOR_MODELS))
+def test_every_pixel_centre_ray_maps_back_to_its_own_pixel_at_sensor_sizes(capi, name):
+    """the ray through a pixel's centre, formed in f64 from the model's angles and rounded once: the f32 rule gives that
+    pixel, for all pixels -- exact by construction (a centre is half a pitch from every boundary, the rule's error is
+    VGX_ATAN2_RULE_MAX_ERROR and a few f32 roundings of the pixel coordinate), and held to the geometry, not to a restatement"""
+    m = S.SENSOR_MODELS[name]
+    v, u = np.meshgrid(np.arange(m.height), np.arange(m.width), indexing="ij")
+    d = m.centre(u, v).reshape(-1, 3).astype(F)
+    ui, vi, ok = R.pixel(m, d[:, 0], d[:, 1], d[:, 2])
+    misses = int(((ui != u.ravel()) | (vi != v.ravel()) | ~ok).sum())
+    print(f"{name}: {misses} misses over {len(d)} pixel-centre rays")
+    assert misses == 0
+    # ... and so says the library's host form, on every 61st pixel, the first and the last column of every row
+    pick = np.unique(np.concatenate([np.arange(0, len(d), 61), np.arange(m.height) * m.width, np.arange(1, m.height + 1) * m.width - 1]))
+    got = host_pixels(capi.load().vgx_range_image_pixel, m.capi(capi), d[pick])
+    assert np.array_equal(got[:, 0], u.ravel()[pick]) and np.array_equal(got[:, 1], v.ravel()[pick])
+
+
+# the first scan of the 512 x 4 sensor: its field of view of 0.027 rad (four rows of 6.7 mrad) is a disc through the room of
+# about 10 m^2 x 0.027 rad x 1.3 m mean range = 0.35 m^3: 350 voxel centres of 0.1 m, more where it runs on through the
+# opening and behind the walls -- a thousand updates do not fit into it.  Every other integration updates more than 1000.
+LEAST_UPDATES = {"512x4": 300}
+
+
+@pytest.fixture(scope="module")
+def sensor_images():
+    """name -> (Model, points, rgba, Image) of the scan at TILTED, computed once and left unchanged"""
+    out = {}
+    for name, m in S.SENSOR_MODELS.items():
+        pts, rgba = S.scan(m, S.TILTED)
+        out[name] = (m, pts, rgba, R.build(m, pts, rgba))
+    return out
+
+
+@pytest.mark.parametrize("name", list(S.SENSOR_MODELS))
+def test_the_box_holds_every_voxel_the_rules_update_at_sensor_sizes(capi, sensor_images, name):
+    """the method of test_the_box_holds_every_voxel_the_rules_update at pitches down to 1.5 mrad, where the box's widening
+    (reach times the pitches) is a fraction of a voxel: near the origin and far from it, with the LIBRARY's box (host only),
+    which is the restatement's"""
+    m, pts, rgba, img = sensor_images[name]
+    cfg, vs, vps = S.config(0.1), 0.1, 8
+    for T in (S.TILTED, S.far_from_origin(S.TILTED)):
+        T = np.asarray(T, F)
+        rc, lo, hi = capi.range_image_box(m.capi(capi), img.counts, cfg.capi(capi), T, vs, vps)
+        code, rlo, rhi = R.box(m, img.counts, cfg, T, vs, vps)
+        assert rc == code == capi.OK and np.array_equal(lo, rlo) and np.array_equal(hi, rhi), (name, T, lo, rlo, hi, rhi)
+        fr = R.integrate(R.Layer(vs, vps), T, img, cfg, lo_hi=(lo - 2, hi + 2))
+        blocks = fr.voxel[fr.branch >= R.UPDATED] // vps
+        assert len(blocks) > LEAST_UPDATES.get(name, 1000) and (blocks > lo).all() and (blocks < hi).all(), (name, T)
+
+
+def test_the_sensor_sized_gpu_scenes_pass_on_something():
+    """what the sensor-sized tests of tests/test_range_image_gpu.py build and integrate, in the restatement alone"""
+    seen = set()
+    for name in S.SENSOR_CASES:
+        m, scans, cfg, vs, vps = S.sensor_case(name)
+        L = R.Layer(vs, vps)
+        for k, (pts, rgba, T) in enumerate(scans):
+            img = R.build(m, pts, rgba)
+            c = img.counts
+            # an image of many workgroups, nearly full, with the planted collisions and rejections
+            assert c["n_filled"] > 0.9 * m.width * m.height and c["n_collided"] >= 4 and c["n_rejected_range"] == 1 and c["n_rejected_rows"] >= 1
+            fr = R.integrate(L, T, img, cfg)
+            seen |= set(np.unique(fr.branch).tolist())
+            least = LEAST_UPDATES.get(S.SENSOR_CASES[name][0], 1000) if k == 0 else 1000
+            assert fr.counts["n_updates"] > least and fr.counts["n_candidate_blocks"] > 200, (name, k, fr.counts)
+            assert fr.new_blocks > 10 if k == 0 else fr.held_blocks > 10
+    assert {R.UPDATED, R.CARVED, R.CLEARED, R.BEHIND, R.EMPTY_CELL, R.OUTSIDE_ROWS, R.TOO_SHORT, R.CLEAR_REFUSED} <= seen
+    big = S.SENSOR_MODELS["4096x256"]
+    assert big.width * big.height == 1024 * 4 * 256                  # 1024 workgroups of the resolve, four cells a lane
 
 
 def test_refusals_of_the_host_only_calls(capi):

@@ -1,7 +1,8 @@
 """The LiDAR range image and its projective integration on the device (vgx_range_image_build and its device form,
 vgx_tsdf_integrate_range_image; voxgraph_amd/csrc/vgx_range_image.hip) against the numpy restatement
 (tests/range_image_ref.py), bit for bit: the image's ranges, colours, winning indices and counts; the layer's distance,
-weight, colour, block index in slot order and all five counts of a frame; and the surface against the ray-cast routes'."""
+weight, colour, block index in slot order and all five counts of a frame; and the surface against the ray-cast routes'.
+The same at sensor sizes, up to 4096 x 256: build, full coverage, two scans a layer, an organised message, a rendered view."""
 import numpy as np
 import pytest
 
@@ -346,6 +347,124 @@ def test_the_surface_is_consistent_with_the_ray_cast_routes(capi, ctx, rigs):
     errors = [_median_range_error(capi, ctx, r.layer, held_out, dirs.astype(F), truth) for r in (a, b, c)]
     print(f"median |range error|: range image {errors[0]:.5f} m, reproducible ray cast {errors[1]:.5f} m, racing ray cast {errors[2]:.5f} m")
     assert errors[0] <= errors[1] + 0.5 * vs, errors
+
+
+# ---- sensor sizes (S.SENSOR_MODELS: up to 4096 x 256 -- 1024 workgroups of the resolve, a million keys --, pitches down to
+# 1.5 mrad; tests/test_range_image_cpu.py holds that these scenes pass on something)
+
+@pytest.fixture(scope="module")
+def sensors():
+    """(model name, scan 0 or 1) -> (Model, points, rgba, the restated Image): computed when first asked for, left unchanged"""
+    made = {}
+
+    def get(name, k=0):
+        if (name, k) not in made:
+            m = S.SENSOR_MODELS[name]
+            pts, rgba = S.sensor_scan(m, k)
+            made[name, k] = (m, pts, rgba, R.build(m, pts, rgba))
+        return made[name, k]
+    return get
+
+
+@pytest.mark.parametrize("name", list(S.SENSOR_MODELS))
+def test_sensor_sized_image_equals_the_restatement(rigs, sensors, name):
+    """from a decoded scan counted and from device arrays queued: cells, colours, indices, all counts and the extremes"""
+    m, pts, rgba, want = sensors(name)
+    r = rigs(S.config(0.1), 0.1, 8)
+    assert R.same_counts(r.build(m, pts, rgba), want.counts)
+    _same_image(r.image, want)
+    assert r.build(m, pts[::-1], rgba[::-1], through_scan=False, count=False) is None
+    _same_image(r.image, R.build(m, pts[::-1], rgba[::-1]))
+
+
+@pytest.mark.parametrize("name", list(S.SENSOR_MODELS))
+def test_one_return_per_pixel_centre_fills_every_pixel(rigs, name):
+    m = S.SENSOR_MODELS[name]
+    n = m.width * m.height
+    v, u = np.meshgrid(np.arange(m.height), np.arange(m.width), indexing="ij")
+    order = np.random.default_rng(9).permutation(n)
+    pts = (m.centre(u, v).reshape(-1, 3) * (1.5 + np.sin(0.01 * np.arange(n)))[:, None]).astype(F)[order]
+    r = rigs(S.config(0.1), 0.1, 8)
+    c = r.build(m, pts, np.arange(n, dtype=np.uint32), through_scan=False)
+    assert c["n_filled"] == c["n_kept"] == c["n_points"] == n and c["n_collided"] == c["n_rejected_rows"] == c["n_rejected_range"] == 0
+    rng, rgba, index = r.image.download()
+    index = index.reshape(-1)
+    assert np.array_equal(index[order], np.arange(n))              # every pixel holds its own centre's point: a permutation
+    assert np.array_equal(np.ascontiguousarray(rgba).view(np.uint32).reshape(-1), index.astype(np.uint32))
+    assert np.array_equal(rng.reshape(-1)[order], R.norm3(pts[:, 0], pts[:, 1], pts[:, 2]))
+
+
+@pytest.mark.parametrize("name", list(S.SENSOR_CASES))
+def test_sensor_sized_scans_equal_the_restatement(rigs, sensors, name):
+    """a scan at TILTED and a second from a moved pose of track() into the same layer: the block index in slot order,
+    distance, weight, colour and the five counts of each frame"""
+    model, far, vps = S.SENSOR_CASES[name]
+    cfg, vs = S.config(0.1), 0.1
+    ref, r = R.Layer(vs, vps), rigs(cfg, vs, vps)
+    for k, (_, T) in enumerate(S.sensor_poses(far)):
+        m, pts, rgba, img = sensors(model, k)
+        want = R.integrate(ref, T, img, cfg).counts
+        r.build(m, pts, rgba, through_scan=k == 1, count=False)
+        assert r.integrate(T) == want
+        _equal(r.layer, ref)
+    assert len(ref.block_index) > 20
+
+
+def test_sensor_sized_chain_from_an_organised_message_on_the_device(capi, ctx, rigs):
+    """a 2048 x 128 organised PointCloud2 in device memory: decoded there, built into the image, integrated -- the image of
+    the points the scan holds and the layer are the restatement's"""
+    m, cfg, vs, vps = S.SENSOR_MODELS["2048x128"], S.config(0.1), 0.1, 8
+    rng = np.random.default_rng(17)
+    v, u = np.meshgrid(np.arange(m.height), np.arange(m.width), indexing="ij")
+    dirs = m.centre(u + rng.uniform(-0.3, 0.3, u.shape), v + rng.uniform(-0.3, 0.3, v.shape)).reshape(-1, 3)
+    pts = (dirs * S.ranges(dirs, S.TILTED)[:, None]).astype(F)              # in pixel order: row after row of the sensor
+    pts[rng.random(len(pts)) < 0.05] = np.nan                                # pixels without a return
+    rgba = rng.integers(0, 1 << 32, len(pts), dtype=np.uint64).astype(np.uint32)
+    data, layout = S.message(pts, rgba)
+    layout.update(width=m.width, height=m.height, row_step=16 * m.width)
+    r = rigs(cfg, vs, vps)
+    scan = capi.Scan(ctx)
+    try:
+        keep, address = Z.on_device(data)
+        n, dropped = scan.decode_msg_device(capi.scan_layout(**layout), address, len(data))
+        held = np.isfinite(pts).all(1)
+        assert n == held.sum() > 0.9 * len(pts) and n + dropped == len(pts)
+        assert r.image.build(m.capi(capi), scan, count=False) is None
+        got = r.integrate(S.TILTED)
+        cloud, colours = scan.download()
+        assert np.array_equal(cloud.view(np.uint32), pts[held].view(np.uint32))
+        want = R.build(m, cloud, np.ascontiguousarray(colours).view(np.uint32)[:, 0])
+        assert want.counts["n_filled"] == n
+        _same_image(r.image, want)
+        ref = R.Layer(vs, vps)
+        assert got == R.integrate(ref, S.TILTED, want, cfg).counts and got["n_updates"] > 1000
+        _equal(r.layer, ref)
+    finally:
+        scan.destroy()
+
+
+def test_a_view_rendered_with_the_sensor_sized_models_rays_fills_its_own_pixels(capi, ctx, rigs, sensors):
+    """a layer rendered along the f64-formed pixel-centre rays of the 2048 x 128 model, the hits built into its image: every
+    pixel whose ray returned is filled by its own ray's point, and no two returns share a pixel"""
+    cfg = S.config(0.1)
+    r = rigs(cfg, 0.1, 8)
+    for k, (_, T) in enumerate(S.sensor_poses()):
+        m, pts, rgba, _ = sensors("2048x128", k)
+        r.build(m, pts, rgba, count=False)
+        r.integrate(T, count=False)
+    v, u = np.meshgrid(np.arange(m.height), np.arange(m.width), indexing="ij")
+    dirs = m.centre(u, v).reshape(-1, 3).astype(F)
+    view = capi.View(ctx, capi.view_config(flags=0, s_max=6.0, min_step=0.025, unknown_step=0.1, max_bracket=0.3))
+    try:
+        got = r.layer.render_view(view, S.track(3)[1], dirs).download()
+    finally:
+        view.destroy()
+    hit = got.status == capi.VIEW_HIT
+    assert hit.sum() > 0.3 * len(dirs)
+    pts = np.where(hit[:, None], dirs * got.range[:, None], F(0)).astype(F)       # (a ray without a return: a zero-length point)
+    counts = r.build(m, pts, np.zeros(len(pts), np.uint32), through_scan=False)
+    assert counts["n_collided"] == 0 and counts["n_filled"] == int(hit.sum()) and counts["n_rejected_rows"] == 0
+    assert np.array_equal(r.image.download()[2].reshape(-1), np.where(hit, np.arange(len(dirs)), -1))
 
 
 @pytest.mark.parametrize("seed", range(100))
