@@ -231,6 +231,20 @@ def test_refusals_and_empty_queries(ctx):
     assert lib.vgx_submap_query_device(sm.h, 1, 1, None, 0, None, None, None, None, None) == capi.OK
     assert (dist == 7).all() and (val == 9).all()
     assert rc(layer=1, flags=3, g=grad, w=wgt) == capi.OK  # and the same call with good arguments runs
+    # a submap without a block, with and without a pose, every route: every query invalid, every output zero
+    none = capi.Submap(ctx, 6, d.voxel_size, d.vps, np.zeros((0, 3), np.int32), np.zeros((0, d.vps ** 3), F),
+                       np.zeros((0, d.vps ** 3), F))
+    near = rng.uniform(-1, 1, (n, 3)).astype(F)
+    turn = np.array([np.cos(0.4), 0, np.sin(0.4), 0, 0.3, -0.2, 0.1], F)
+    for T in (None, turn):
+        for layer, flags in ((0, 0), (0, 1), (0, 3), (1, 0), (1, 1), (1, 3)):
+            for a, fill in ((dist, 7.0), (grad, 7.0), (wgt, 7.0), (val, 9)):
+                a[...] = fill
+            assert rc(h=none.h, layer=layer, flags=flags, T=T, p=near, g=grad if flags & 2 else None, w=wgt if layer else None) == capi.OK
+            assert not dist.any() and not val.any(), (layer, flags)
+            assert not grad.any() if flags & 2 else (grad == 7).all()
+            assert not wgt.any() if layer else (wgt == 7).all()
+    none.destroy()
     # a released raw layer, an ESDF never generated
     sm.release_raw_layers()
     assert rc() == capi.ERR_INVALID and rc(layer=1) == capi.ERR_INVALID

@@ -120,6 +120,25 @@ def test_evaluate_map_over_layers_losses_submap_counts_and_corrections(ctx, rand
                     assert 0 < got[2] <= got[1] <= K * got[2] and got[3] < n
                     assert K == 1 or got[1] > got[2]
                 reg.destroy()
+    # a submap without a block listed before or after a real one: its table misses every lookup, so the sums, the counts
+    # and the scores are the real submap's alone, bit for bit
+    vox = submaps[0].vps ** 3
+    none = capi.Submap(ctx, 30, submaps[0].voxel_size, submaps[0].vps, np.zeros((0, 3), np.int32), np.zeros((0, vox), F),
+                       np.zeros((0, vox), F))
+    for layer in ("esdf", "tsdf"):
+        cfg = dict(max_abs_distance_m=0.45 if layer == "esdf" else 0.25)
+        alone, _, _ = _reg(ctx, submaps[:1], poses[:1], cfg, layer=layer, huber_delta_m=0.3)
+        alone.set_points(pc[:300])
+        want, want_score = alone.evaluate_map(T, DELTAS[1]), alone.score_poses([T])
+        assert want[1] > 0
+        for listed, at in (([none, submaps[0]], [poses[1], poses[0]]), ([submaps[0], none], [poses[0], poses[1]])):
+            reg, _, _ = _reg(ctx, listed, at, cfg, layer=layer, huber_delta_m=0.3)
+            reg.set_points(pc[:300])
+            _same(reg.evaluate_map(T, DELTAS[1]), want)
+            assert all(np.array_equal(_bits(g), _bits(w)) for g, w in zip(reg.score_poses([T]), want_score))
+            reg.destroy()
+        alone.destroy()
+    none.destroy()
 
 
 def test_host_device_and_scan_sources_agree(ctx, random_scene):

@@ -87,6 +87,16 @@ struct GridDev {
   int32_t layout;        // brick layout of `bricks` (0 apron, 1 quad)
 };
 
+// A raw voxel layer's dense block table as the layer readers take it (vgx_interp.h's interp_base / interp_slot /
+// layer_interp read exactly these fields): the descriptors of the map queries, the views, scan registration and
+// localisation, the projected map and the isosurface points derive from it.  Filled only by submap_table (below) and
+// live_layer_table (vgx_tsdf_internal.h).  GridDev above is the sampling grid's own form (int32_t[3], bricks).
+struct LayerTable {
+  const int32_t* lut;  // dense [dim.z][dim.y][dim.x]: the block's slot, negative when absent
+  int3 lut_min, lut_dim;
+  float voxel_size, voxel_size_inv, block_size, block_size_inv;
+};
+
 // Per-evaluation pose data of one constraint, computed on the host in the
 // reference's own f32 arithmetic (registration_cost_function.cpp:69-110).
 struct alignas(16) PosePack {
@@ -472,6 +482,21 @@ struct vgx_submap_s {
   int users = 0;
   bool destroy_requested = false;
 };
+
+namespace vgx {
+// a finished submap's block table.  A submap with no blocks gets lut_dim = 0: every lookup misses.
+inline LayerTable submap_table(const vgx_submap_s* sm) {
+  LayerTable t{};
+  t.lut = sm->d_lut;
+  t.lut_min = make_int3(sm->lut_min[0], sm->lut_min[1], sm->lut_min[2]);
+  if (sm->n_blocks > 0) t.lut_dim = make_int3(sm->lut_dim[0], sm->lut_dim[1], sm->lut_dim[2]);
+  t.voxel_size = sm->voxel_size;
+  t.voxel_size_inv = sm->voxel_size_inv;
+  t.block_size = sm->block_size;
+  t.block_size_inv = sm->block_size_inv;
+  return t;
+}
+}  // namespace vgx
 
 struct vgx_reg_s {
   vgx_ctx ctx = nullptr;

@@ -50,6 +50,33 @@ __device__ __forceinline__ int interp_slot(const P& p, int bx, int by, int bz) {
   return p.lut[rx + p.lut_dim.x * (ry + p.lut_dim.y * rz)];
 }
 
+// The neighbour walk: the 8 neighbours of the low neighbour (blk, vox) (k: x = bit 2, y = bit 1, z = bit 0, a voxel index
+// past the block carrying into the next block), each as its voxel's offset at[k] into a [slot][VPS^3] array.  False when
+// a neighbour's block is absent; its at[k] is then formed with slot 0, so that a caller may form all 8 before it looks.
+template <int VPS, class P>
+__device__ __forceinline__ bool interp_neighbours(const P& p, const int blk[3], const int vox[3], size_t at[8]) {
+  constexpr int VOX = VPS * VPS * VPS;
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int off[3] = {(k >> 2) & 1, (k >> 1) & 1, k & 1};
+    int nb[3], nv[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      nb[a] = blk[a];
+      nv[a] = vox[a] + off[a];
+      if (nv[a] >= VPS) {
+        nb[a]++;
+        nv[a] -= VPS;
+      }
+    }
+    const int slot = interp_slot(p, nb[0], nb[1], nb[2]);
+    ok = ok && slot >= 0;
+    at[k] = (size_t)(slot >= 0 ? slot : 0) * VOX + (size_t)(nv[0] + VPS * (nv[1] + VPS * nv[2]));
+  }
+  return ok;
+}
+
 // interpVoxel's trilinear form over the 8 neighbours (k: x = bit 2, y = bit 1, z = bit 0) in oracle/iso_oracle.c's
 // association
 __device__ __forceinline__ float interp_trilinear(const float x[8], const float dl[3]) {
@@ -140,27 +167,14 @@ __device__ bool tsdf_interp(const P& p, const float pos[3], float& dist, float& 
 // words are not live next to the 16 distance / weight values.
 template <int VPS, class P>
 __device__ __forceinline__ uint32_t tsdf_color_interp(const P& p, const uint32_t* __restrict__ rgba, const float pos[3]) {
-  constexpr int VOX = VPS * VPS * VPS;
   int blk[3], vox[3];
   float dl[3];
   interp_base<VPS>(p, pos, blk, vox, dl);
+  size_t at[8];
+  const bool all = interp_neighbours<VPS>(p, blk, vox, at);  // (true: the caller checked)
   uint32_t c[8];
 #pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    int off[3] = {(k >> 2) & 1, (k >> 1) & 1, k & 1};
-    int nb[3], nv[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      nb[a] = blk[a];
-      nv[a] = vox[a] + off[a];
-      if (nv[a] >= VPS) {
-        nb[a]++;
-        nv[a] -= VPS;
-      }
-    }
-    const int slot = interp_slot(p, nb[0], nb[1], nb[2]);
-    c[k] = slot >= 0 ? rgba[(size_t)slot * VOX + (size_t)(nv[0] + VPS * (nv[1] + VPS * nv[2]))] : 0u;  // (present: the caller checked)
-  }
+  for (int k = 0; k < 8; ++k) c[k] = all ? rgba[at[k]] : 0u;
   uint32_t out = 0;
 #pragma unroll
   for (int ch = 0; ch < 4; ++ch) {

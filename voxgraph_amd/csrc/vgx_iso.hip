@@ -27,13 +27,10 @@ namespace vgx {
 
 constexpr unsigned long long kEmptyKey = ~0ull;
 
-struct IsoParams {
+struct IsoParams : LayerTable {
   const int32_t* block_index;
-  const int32_t* lut;
-  int3 lut_min, lut_dim;
   const float* tsdf_d;
   const float* tsdf_w;
-  float voxel_size, voxel_size_inv, block_size, block_size_inv;
   float min_weight;
   double threshold_inv;
   unsigned long long* keys;  // dedup table
@@ -339,16 +336,10 @@ extern "C" int vgx_submap_extract_isosurface_points(vgx_submap sm, double min_vo
   }
 
   IsoParams p{};
+  static_cast<LayerTable&>(p) = submap_table(sm);
   p.block_index = sm->d_block_index;
-  p.lut = sm->d_lut;
-  p.lut_min = make_int3(sm->lut_min[0], sm->lut_min[1], sm->lut_min[2]);
-  p.lut_dim = make_int3(sm->lut_dim[0], sm->lut_dim[1], sm->lut_dim[2]);
   p.tsdf_d = sm->d_tsdf_distance;
   p.tsdf_w = sm->d_tsdf_weight;
-  p.voxel_size = sm->voxel_size;
-  p.voxel_size_inv = sm->voxel_size_inv;
-  p.block_size = sm->block_size;
-  p.block_size_inv = sm->block_size_inv;
   p.min_weight = (float)min_voxel_weight;  // MeshIntegratorConfig::min_weight is a float (VSM:211-212)
   // getConnectedMesh(&mesh, 0.5 * voxel_size): FloatingPoint threshold, double inverse
   const float threshold = (float)(0.5 * (double)sm->voxel_size);

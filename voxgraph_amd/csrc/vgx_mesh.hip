@@ -24,6 +24,7 @@
 
 #include "vgx_internal.h"
 #include "vgx_mc_tables.h"
+#include "vgx_pose.h"
 #include "vgx_tsdf_internal.h"
 
 #pragma clang fp contract(off)
@@ -219,16 +220,6 @@ struct EmitPose {
   uint32_t* colors;  // [T]
 };
 
-// Eigen _transformVector without the translation: transform_point's formula up to its `+ t`
-__device__ __forceinline__ void rotate_vector(const float q[4], float px, float py, float pz, float& gx, float& gy, float& gz) {
-  float uvx = q[2] * pz - q[3] * py, uvy = q[3] * px - q[1] * pz, uvz = q[1] * py - q[2] * px;
-  uvx += uvx; uvy += uvy; uvz += uvz;
-  const float ccx = q[2] * uvz - q[3] * uvy, ccy = q[3] * uvx - q[1] * uvz, ccz = q[1] * uvy - q[2] * uvx;
-  gx = (px + q[0] * uvx) + ccx;
-  gy = (py + q[0] * uvy) + ccy;
-  gz = (pz + q[0] * uvz) + ccz;
-}
-
 // One block's triangles at [base, end), its corners staged into m: the cubes in visiting order, a workgroup-wide exclusive
 // scan of their counts per round of 256 cubes, each cube writing its triangles at its own offset.  POSED: each vertex
 // through transform_point(T), the normal through the rotation alone (not renormalised), the colour stored per triangle.
@@ -286,7 +277,12 @@ __device__ __forceinline__ void emit_block(const MeshSrc& s, const int32_t* bi, 
           for (int q = 0; q < 3; ++q)
             transform_point(T.q[0], T.q[1], T.q[2], T.q[3], T.t[0], T.t[1], T.t[2], p[q][0], p[q][1], p[q][2], p[q][0], p[q][1],
                             p[q][2]);
-          rotate_vector(T.q, nx, ny, nz, nx, ny, nz);
+          const float nrm[3] = {nx, ny, nz};
+          float rot[3];
+          quat_rotate(T.q, nrm, rot);  // (transform_point's formula up to its `+ t`)
+          nx = rot[0];
+          ny = rot[1];
+          nz = rot[2];
           T.colors[at] = T.rgba;
         }
         float* v = vertices + 9 * at;
@@ -893,11 +889,9 @@ int vgx_submaps_generate_separated_mesh(vgx_ctx ctx, int32_t n, const vgx_submap
       return fail(VGX_ERR_INVALID, at + "raw TSDF layer not resident (released?)");
     if (sm->voxel_size != submaps[0]->voxel_size || sm->vps != submaps[0]->vps)
       return fail(VGX_ERR_INVALID, at + "voxel_size / voxels_per_side differ from submap 0's");
-    const float* T = T_M_S + 7 * (size_t)i;
-    for (int k = 0; k < 7; ++k)
-      if (!std::isfinite(T[k])) return fail(VGX_ERR_INVALID, at + "pose value not finite");
-    const double n2 = (double)T[0] * T[0] + (double)T[1] * T[1] + (double)T[2] * T[2] + (double)T[3] * T[3];
-    if (std::fabs(n2 - 1.0) > 1e-4) return fail(VGX_ERR_INVALID, at + "pose quaternion not unit (|q|^2 - 1 > 1e-4)");
+    const PoseDefect bad = pose_defect(T_M_S + 7 * (size_t)i);
+    if (bad == kPoseNotFinite) return fail(VGX_ERR_INVALID, at + "pose value not finite");
+    if (bad == kPoseNotUnit) return fail(VGX_ERR_INVALID, at + "pose quaternion not unit (|q|^2 - 1 > 1e-4)");
     n_entries += sm->n_blocks;
     if (sm->n_blocks == 0) continue;
     for (int a = 0; a < 3; ++a) {

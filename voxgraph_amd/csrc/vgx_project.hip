@@ -19,19 +19,17 @@
 
 #include "vgx_internal.h"
 #include "vgx_interp.h"
+#include "vgx_pose.h"
 #include "vgx_tsdf_internal.h"
 
 #pragma clang fp contract(off)
 
 namespace vgx {
 
-struct alignas(16) ProjectSrc {
-  // tsdf_interp's fields (the submap's raw layer)
-  const int32_t* lut;
-  int3 lut_min, lut_dim;
+struct alignas(16) ProjectSrc : LayerTable {
+  // tsdf_interp's other fields (the submap's raw layer)
   const float* tsdf_d;
   const float* tsdf_w;
-  float voxel_size, voxel_size_inv, block_size, block_size_inv;
   // candidate pairs
   const int32_t* block_index;
   const uint8_t* has_data;
@@ -39,18 +37,6 @@ struct alignas(16) ProjectSrc {
   float q_sl[4], t_sl[3];  // T_S_L = T_L_S.inverse(): layer voxel centres into the source
   const uint32_t* tsdf_rgba;  // the submap's colours, or null (read by the COLOR instantiations only)
 };
-
-// Eigen's _transformVector plus translation (the oracle's quat_rotate, then + t)
-__host__ __device__ __forceinline__ void rigid_apply(const float q[4], const float t[3], const float v[3], float out[3]) {
-  float uv0 = q[2] * v[2] - q[3] * v[1], uv1 = q[3] * v[0] - q[1] * v[2], uv2 = q[1] * v[1] - q[2] * v[0];
-  uv0 += uv0;
-  uv1 += uv1;
-  uv2 += uv2;
-  const float c0 = q[2] * uv2 - q[3] * uv1, c1 = q[3] * uv0 - q[1] * uv2, c2 = q[1] * uv1 - q[2] * uv0;
-  out[0] = (v[0] + q[0] * uv0 + c0) + t[0];
-  out[1] = (v[1] + q[0] * uv1 + c1) + t[1];
-  out[2] = (v[2] + q[0] * uv2 + c2) + t[2];
-}
 
 // target-block range [lo, hi] of one source block (its box grown by one voxel, 8 corners into the layer frame),
 // clipped to the candidate box
@@ -268,18 +254,6 @@ namespace {
 
 int fail_fn(vgx_ctx ctx, int code, const char* fn, const std::string& msg) { return set_error(ctx, code, fn + msg); }
 
-// T.inverse() in f32 as kindr forms it: conjugate rotation, translation -(q^-1 t)
-void inverse_pose(const float q[4], const float t[3], float qi[4], float ti[3]) {
-  qi[0] = q[0];
-  qi[1] = -q[1];
-  qi[2] = -q[2];
-  qi[3] = -q[3];
-  const float zero[3] = {0.0f, 0.0f, 0.0f};
-  float r[3];
-  rigid_apply(qi, zero, t, r);
-  for (int a = 0; a < 3; ++a) ti[a] = -r[a];
-}
-
 // vgx_tsdf_layer_merge_submaps (copy = false) and vgx_tsdf_layer_transform_submap (copy = true, n = 1): one pair build,
 // one sort, one reservation; the copy additionally refuses a layer that is not empty
 int project_submaps(vgx_tsdf_layer L, int32_t n, const vgx_submap* submaps, const float* T_L_S, int64_t* n_blocks_out,
@@ -298,11 +272,9 @@ int project_submaps(vgx_tsdf_layer L, int32_t n, const vgx_submap* submaps, cons
       return fail(ctx, VGX_ERR_INVALID, at + "voxel_size / voxels_per_side differ from the layer's (no resampling)");
     if (sm->n_blocks > 0 && (!sm->d_tsdf_distance || !sm->d_tsdf_weight))
       return fail(ctx, VGX_ERR_INVALID, at + "raw TSDF layer not resident (released?)");
-    const float* T = T_L_S + 7 * (size_t)i;
-    for (int k = 0; k < 7; ++k)
-      if (!std::isfinite(T[k])) return fail(ctx, VGX_ERR_INVALID, at + "pose value not finite");
-    const double n2 = (double)T[0] * T[0] + (double)T[1] * T[1] + (double)T[2] * T[2] + (double)T[3] * T[3];
-    if (std::fabs(n2 - 1.0) > 1e-4) return fail(ctx, VGX_ERR_INVALID, at + "pose quaternion not unit (|q|^2 - 1 > 1e-4)");
+    const PoseDefect bad = pose_defect(T_L_S + 7 * (size_t)i);
+    if (bad == kPoseNotFinite) return fail(ctx, VGX_ERR_INVALID, at + "pose value not finite");
+    if (bad == kPoseNotUnit) return fail(ctx, VGX_ERR_INVALID, at + "pose quaternion not unit (|q|^2 - 1 > 1e-4)");
   }
   std::lock_guard<std::mutex> tsdf_lk(ctx->tsdf_mu);
   std::lock_guard<std::mutex> reg_lk(ctx->mu);  // (lock order: tsdf_mu, then mu)
@@ -347,15 +319,9 @@ int project_submaps(vgx_tsdf_layer L, int32_t n, const vgx_submap* submaps, cons
       }
     }
     ProjectSrc& s = src[(size_t)i];
-    s.lut = sm->d_lut;
-    s.lut_min = make_int3(sm->lut_min[0], sm->lut_min[1], sm->lut_min[2]);
-    s.lut_dim = make_int3(sm->lut_dim[0], sm->lut_dim[1], sm->lut_dim[2]);
+    static_cast<LayerTable&>(s) = submap_table(sm);
     s.tsdf_d = sm->d_tsdf_distance;
     s.tsdf_w = sm->d_tsdf_weight;
-    s.voxel_size = sm->voxel_size;
-    s.voxel_size_inv = sm->voxel_size_inv;
-    s.block_size = sm->block_size;
-    s.block_size_inv = sm->block_size_inv;
     s.block_index = sm->d_block_index;
     s.has_data = sm->d_block_has_data;
     s.tsdf_rgba = sm->d_tsdf_rgba;

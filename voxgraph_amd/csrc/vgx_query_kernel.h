@@ -15,16 +15,13 @@
 
 #include "vgx_internal.h"
 #include "vgx_interp.h"
+#include "vgx_pose.h"
 
 #pragma clang fp contract(off)
 
 namespace vgx {
 
-struct QueryDev {
-  // layer_interp's fields (the submap's raw layer)
-  const int32_t* lut;
-  int3 lut_min, lut_dim;
-  float voxel_size, voxel_size_inv, block_size, block_size_inv;
+struct QueryDev : LayerTable {  // (the submap's raw layer)
   const float* val;  // ESDF or TSDF distance
   const void* vld;   // ESDF observed (uint8) or TSDF weight (float)
   int32_t posed;
@@ -40,18 +37,6 @@ struct QueryDev {
 };
 
 constexpr int kQueryThreads = 256;
-
-// Eigen _transformVector (then + t): rigid_apply of vgx_project.hip, the rule of vgx_tsdf_layer_merge_submaps
-__device__ __forceinline__ void query_rotate(const float q[4], const float v[3], float out[3]) {
-  float uv0 = q[2] * v[2] - q[3] * v[1], uv1 = q[3] * v[0] - q[1] * v[2], uv2 = q[1] * v[1] - q[2] * v[0];
-  uv0 += uv0;
-  uv1 += uv1;
-  uv2 += uv2;
-  const float c0 = q[2] * uv2 - q[3] * uv1, c1 = q[3] * uv0 - q[1] * uv2, c2 = q[1] * uv1 - q[2] * uv0;
-  out[0] = (v[0] + q[0] * uv0) + c0;
-  out[1] = (v[1] + q[0] * uv1) + c1;
-  out[2] = (v[2] + q[0] * uv2) + c2;
-}
 
 // Interpolator::getNearestDistance [recalled]: p's own voxel (vgx_interp.h's floor rule, clamped into the block), which
 // must exist and be valid; its own distance and (TSDF) weight
@@ -164,14 +149,17 @@ __global__ __launch_bounds__(kQueryThreads) __attribute__((amdgpu_waves_per_eu(4
   float x[3] = {q.points[3 * i], q.points[3 * i + 1], q.points[3 * i + 2]};
   float p[3];
   if (q.posed) {
-    query_rotate(q.q_sq, x, p);
+    quat_rotate(q.q_sq, x, p);  // (rigid_apply's two steps written out: through the helper the gradient instantiations spilled)
 #pragma unroll
     for (int a = 0; a < 3; ++a) p[a] = p[a] + q.t_sq[a];
   } else {
 #pragma unroll
     for (int a = 0; a < 3; ++a) p[a] = x[a];
   }
-  // a coordinate whose block index would leave [-2^30, 2^30) -- every non-finite one -- makes the query invalid
+  // a coordinate whose block index would leave [-2^30, 2^30) -- every non-finite one -- makes the query invalid.  (The
+  // rule stays written out in each reader: as a shared predicate it took the gradient instantiations here from 95 / 108
+  // VGPRs to 128 with 12 to 52 bytes of scratch, the localisation kernel into the next VGPR granule, and the view
+  // kernel's LiDAR case 5 % of its time.)
   bool ok = true;
 #pragma unroll
   for (int a = 0; a < 3; ++a) ok = ok && fabsf(p[a] * q.block_size_inv) < 1073741824.0f;
@@ -256,7 +244,7 @@ __global__ __launch_bounds__(kQueryThreads) __attribute__((amdgpu_waves_per_eu(4
 #pragma unroll
         for (int a = 0; a < 3; ++a) gs[a] = (dk[2 + 2 * a] - dk[1 + 2 * a]) / two_vs;
         if (q.posed) {
-          query_rotate(q.q_qs, gs, g);
+          quat_rotate(q.q_qs, gs, g);
         } else {
 #pragma unroll
           for (int a = 0; a < 3; ++a) g[a] = gs[a];
@@ -301,18 +289,6 @@ inline hipError_t launch_query(hipStream_t st, const QueryDev& q, int vps, bool 
 
 inline int query_fail(vgx_ctx ctx, const std::string& msg) { return set_error(ctx, VGX_ERR_INVALID, "vgx_submap_query: " + msg); }
 
-// Eigen _transformVector, then + t (rigid_apply of vgx_project.hip), on the host in f32
-inline void host_rigid_apply(const float q[4], const float t[3], const float v[3], float out[3]) {
-  float uv0 = q[2] * v[2] - q[3] * v[1], uv1 = q[3] * v[0] - q[1] * v[2], uv2 = q[1] * v[1] - q[2] * v[0];
-  uv0 += uv0;
-  uv1 += uv1;
-  uv2 += uv2;
-  const float c0 = q[2] * uv2 - q[3] * uv1, c1 = q[3] * uv0 - q[1] * uv2, c2 = q[1] * uv1 - q[2] * uv0;
-  out[0] = (v[0] + q[0] * uv0 + c0) + t[0];
-  out[1] = (v[1] + q[0] * uv1 + c1) + t[1];
-  out[2] = (v[2] + q[0] * uv2 + c2) + t[2];
-}
-
 // The checks of both calls (refused before anything is written), then the kernel's descriptor.  Returns VGX_OK with
 // *run = false when there is nothing to do (n = 0).
 inline int query_prepare(vgx_submap sm, int32_t layer, int32_t flags, const float* T_Q_S, int64_t n, const void* points,
@@ -330,39 +306,22 @@ inline int query_prepare(vgx_submap sm, int32_t layer, int32_t flags, const floa
   if (sm->n_blocks > 0 && (tsdf ? !(sm->d_tsdf_distance && sm->d_tsdf_weight) : !(sm->d_esdf_distance && sm->d_esdf_observed)))
     return query_fail(ctx, std::string(tsdf ? "TSDF" : "ESDF") + " layer not resident (released, or never generated)");
   if (T_Q_S) {
-    for (int k = 0; k < 7; ++k)
-      if (!std::isfinite(T_Q_S[k])) return query_fail(ctx, "pose value not finite");
-    const double n2 = (double)T_Q_S[0] * T_Q_S[0] + (double)T_Q_S[1] * T_Q_S[1] + (double)T_Q_S[2] * T_Q_S[2] +
-                      (double)T_Q_S[3] * T_Q_S[3];
-    if (std::fabs(n2 - 1.0) > 1e-4) return query_fail(ctx, "pose quaternion not unit (|q|^2 - 1 > 1e-4)");
+    const PoseDefect bad = pose_defect(T_Q_S);
+    if (bad == kPoseNotFinite) return query_fail(ctx, "pose value not finite");
+    if (bad == kPoseNotUnit) return query_fail(ctx, "pose quaternion not unit (|q|^2 - 1 > 1e-4)");
   }
   if (sm->vps != 8 && sm->vps != 16) return set_error(ctx, VGX_ERR_UNSUPPORTED, "vgx_submap_query: voxels_per_side not 8 or 16");
   if ((n + kQueryThreads - 1) / kQueryThreads > 0x7fffffffll) return set_error(ctx, VGX_ERR_UNSUPPORTED, "vgx_submap_query: n too large for one launch");
   if (n == 0) return VGX_OK;
   q = QueryDev{};
-  q.lut = sm->d_lut;
-  q.lut_min = make_int3(sm->lut_min[0], sm->lut_min[1], sm->lut_min[2]);
-  q.lut_dim = make_int3(sm->lut_dim[0], sm->lut_dim[1], sm->lut_dim[2]);
-  if (sm->n_blocks == 0) q.lut_dim = make_int3(0, 0, 0);  // (no block: every lookup misses)
-  q.voxel_size = sm->voxel_size;
-  q.voxel_size_inv = sm->voxel_size_inv;
-  q.block_size = sm->block_size;
-  q.block_size_inv = sm->block_size_inv;
+  static_cast<LayerTable&>(q) = submap_table(sm);
   q.val = tsdf ? sm->d_tsdf_distance : sm->d_esdf_distance;
   q.vld = tsdf ? (const void*)sm->d_tsdf_weight : (const void*)sm->d_esdf_observed;
   q.posed = T_Q_S ? 1 : 0;
   q.offsets32 = (uint64_t)sm->n_blocks * (uint64_t)(sm->vps * sm->vps * sm->vps) < (1ull << 32) ? 1 : 0;
   if (T_Q_S) {
-    // T_S_Q = T_Q_S.inverse() once in f32: conjugate rotation, translation -(q^-1 t) (vgx_tsdf_layer_merge_submaps' rule)
     for (int k = 0; k < 4; ++k) q.q_qs[k] = T_Q_S[k];
-    q.q_sq[0] = T_Q_S[0];
-    q.q_sq[1] = -T_Q_S[1];
-    q.q_sq[2] = -T_Q_S[2];
-    q.q_sq[3] = -T_Q_S[3];
-    const float zero[3] = {0.0f, 0.0f, 0.0f};
-    float r[3];
-    host_rigid_apply(q.q_sq, zero, T_Q_S + 4, r);
-    for (int a = 0; a < 3; ++a) q.t_sq[a] = -r[a];
+    inverse_pose(T_Q_S, T_Q_S + 4, q.q_sq, q.t_sq);  // T_S_Q, once in f32
   }
   q.n = n;
   run = true;

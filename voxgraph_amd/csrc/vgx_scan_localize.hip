@@ -123,14 +123,17 @@ __global__ __launch_bounds__(kScanRegThreads) void scan_map_eval_kernel(ScanMapD
     if (!(range2 >= d.min_range2 && range2 <= d.max_range2)) continue;
     ++n_cand;
     float q[3];
-    query_rotate(pq, pc, q);
+    quat_rotate(pq, pc, q);
     const float pm[3] = {(c * q[0] - s * q[1]) + pt[0], (s * q[0] + c * q[1]) + pt[1], q[2] + pt[2]};
     bool any = false;
 #pragma unroll 1
     for (int m = 0; m < d.n_submaps; ++m) {
       const ScanMapSubmapDev& sm = d.submaps[m];  // (uniform: scalar loads)
       float pos[3];
-      query_rotate(sm.q_sm, pm, pos);
+      // rigid_apply and (below) interp_neighbours in this kernel's own lines: through rigid_apply the cost-only
+      // instantiations came out a different instruction stream, through interp_neighbours their 24 gathers became flat
+      // loads (16 of them with the table taken by value first)
+      quat_rotate(sm.q_sm, pm, pos);
 #pragma unroll
       for (int a = 0; a < 3; ++a) pos[a] = pos[a] + sm.t_sm[a];
       // the query kernel's rule: a block coordinate outside (-2^30, 2^30) -- every non-finite point -- is skipped
@@ -194,7 +197,7 @@ __global__ __launch_bounds__(kScanRegThreads) void scan_map_eval_kernel(ScanMapD
         interp_trilinear_gradient(x, dl, gl);
 #pragma unroll
         for (int a3 = 0; a3 < 3; ++a3) gs[a3] = gl[a3] * sm.voxel_size_inv;
-        query_rotate(sm.q_ms, gs, J);  // J[0..2] = g_M
+        quat_rotate(sm.q_ms, gs, J);  // J[0..2] = g_M
         J[3] = J[0] * ((-s) * q[0] - c * q[1]) + J[1] * (c * q[0] - s * q[1]);
         const double Jd[4] = {(double)J[0], (double)J[1], (double)J[2], (double)J[3]};
         const double wr = w * rd;
@@ -280,7 +283,7 @@ int map_table(const char* fn, vgx_scan_registration R) {
     changed = changed || e.val != val || e.vld != vld || e.lut != sm->d_lut.get();
     e.val = val;
     e.vld = vld;
-    e.lut = sm->d_lut;
+    static_cast<LayerTable&>(e) = submap_table(sm);
   }
   if (changed) {
     const size_t bytes = n * sizeof(ScanMapSubmapDev);
@@ -476,27 +479,11 @@ int vgx_scan_registration_set_map(vgx_scan_registration R, const vgx_scan_map_co
   int rc = map_check_poses(fn, ctx, n_submaps, T_M_S, "the pose of submap");
   if (rc != VGX_OK) return rc;
   for (int32_t k = 0; k < n_submaps; ++k) {
-    vgx_submap sm = submaps[k];
     const float* T = T_M_S + 7 * (size_t)k;
     ScanMapSubmapDev& e = desc[(size_t)k];
-    e = ScanMapSubmapDev{};
-    e.lut_min = make_int3(sm->lut_min[0], sm->lut_min[1], sm->lut_min[2]);
-    e.lut_dim = make_int3(sm->lut_dim[0], sm->lut_dim[1], sm->lut_dim[2]);
-    if (sm->n_blocks == 0) e.lut_dim = make_int3(0, 0, 0);  // (no block: every lookup misses)
-    e.voxel_size = sm->voxel_size;
-    e.voxel_size_inv = sm->voxel_size_inv;
-    e.block_size = sm->block_size;
-    e.block_size_inv = sm->block_size_inv;
-    // T_S_M = T_M_S.inverse() once in f32: conjugate rotation, translation -(q^-1 t) (vgx_submap_query's rule)
+    e = ScanMapSubmapDev{};  // (the block table and the layer pointers: map_table, at every evaluation)
     for (int i = 0; i < 4; ++i) e.q_ms[i] = T[i];
-    e.q_sm[0] = T[0];
-    e.q_sm[1] = -T[1];
-    e.q_sm[2] = -T[2];
-    e.q_sm[3] = -T[3];
-    const float zero[3] = {0.0f, 0.0f, 0.0f};
-    float r[3];
-    host_rigid_apply(e.q_sm, zero, T + 4, r);
-    for (int a = 0; a < 3; ++a) e.t_sm[a] = -r[a];
+    inverse_pose(T, T + 4, e.q_sm, e.t_sm);  // T_S_M, once in f32
   }
   std::lock_guard<std::mutex> lk(R->mu);
   {

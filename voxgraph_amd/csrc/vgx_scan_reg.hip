@@ -27,11 +27,7 @@
 
 namespace vgx {
 
-struct ScanRegDev {
-  // interp_base's / interp_slot's fields over the live layer
-  const int32_t* lut;
-  int3 lut_min, lut_dim;
-  float voxel_size, voxel_size_inv, block_size, block_size_inv;
+struct ScanRegDev : LayerTable {  // (the live layer's)
   const unsigned long long* voxels;  // [blocks][vps^3] {distance (lo), weight (hi)}
   const float* points;               // [n][3] sensor frame
   long long n_strided;               // candidates by stride alone: ceil(n / stride)
@@ -85,7 +81,6 @@ __device__ __forceinline__ void scan_reg_block_fold(double (&v)[kScanRegSums], l
 
 template <int VPS>
 __global__ __launch_bounds__(kScanRegThreads) void scan_reg_eval_kernel(ScanRegDev d) {
-  constexpr int VOX = VPS * VPS * VPS;
   double acc[kScanRegSums];
 #pragma unroll
   for (int k = 0; k < kScanRegSums; ++k) acc[k] = 0.0;
@@ -101,7 +96,7 @@ __global__ __launch_bounds__(kScanRegThreads) void scan_reg_eval_kernel(ScanRegD
     if (!(range2 >= d.min_range2 && range2 <= d.max_range2)) continue;
     ++n_cand;
     float q[3];
-    query_rotate(d.q, pc, q);
+    quat_rotate(d.q, pc, q);
     const float pos[3] = {(d.c * q[0] - d.s * q[1]) + d.t[0], (d.s * q[0] + d.c * q[1]) + d.t[1], q[2] + d.t[2]};
     // the query kernel's rule: a block coordinate outside (-2^30, 2^30) -- every non-finite point -- is skipped
     bool ok = true;
@@ -111,26 +106,9 @@ __global__ __launch_bounds__(kScanRegThreads) void scan_reg_eval_kernel(ScanRegD
     int blk[3], vox[3];
     float dl[3];
     interp_base<VPS>(d, pos, blk, vox, dl);
-    // the 8 neighbours (k: x = bit 2, y = bit 1, z = bit 0): the addresses first, then the gathers together
+    // the 8 neighbours' addresses first, then the gathers together
     size_t at[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int off[3] = {(k >> 2) & 1, (k >> 1) & 1, k & 1};
-      int nb[3], nv[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        nb[a] = blk[a];
-        nv[a] = vox[a] + off[a];
-        if (nv[a] >= VPS) {
-          nb[a]++;
-          nv[a] -= VPS;
-        }
-      }
-      const int slot = interp_slot(d, nb[0], nb[1], nb[2]);
-      ok = ok && slot >= 0;
-      at[k] = (size_t)(slot >= 0 ? slot : 0) * VOX + (size_t)(nv[0] + VPS * (nv[1] + VPS * nv[2]));
-    }
-    if (!ok) continue;
+    if (!interp_neighbours<VPS>(d, blk, vox, at)) continue;
     float x[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -197,10 +175,9 @@ int reg_check(const char* fn, vgx_scan_registration R, vgx_tsdf_layer L, const f
   vgx_ctx ctx = R->ctx;
   if (!L || !T) return reg_fail(ctx, fn, "NULL layer or prior");
   if (L->ctx != ctx) return reg_fail(ctx, fn, "the layer belongs to another context");
-  for (int k = 0; k < 7; ++k)
-    if (!std::isfinite(T[k])) return reg_fail(ctx, fn, "the prior is not finite");
-  const double n2 = (double)T[0] * T[0] + (double)T[1] * T[1] + (double)T[2] * T[2] + (double)T[3] * T[3];
-  if (std::fabs(n2 - 1.0) > 1e-4) return reg_fail(ctx, fn, "the prior's quaternion is not unit (| |q|^2 - 1 | > 1e-4)");
+  const PoseDefect bad = pose_defect(T);
+  if (bad == kPoseNotFinite) return reg_fail(ctx, fn, "the prior is not finite");
+  if (bad == kPoseNotUnit) return reg_fail(ctx, fn, "the prior's quaternion is not unit (| |q|^2 - 1 | > 1e-4)");
   if (delta)
     for (int k = 0; k < 4; ++k)
       if (!std::isfinite(delta[k])) return reg_fail(ctx, fn, "delta is not finite");
@@ -270,14 +247,7 @@ int reg_evaluate_locked(vgx_scan_registration R, vgx_tsdf_layer L, const float* 
   }
   const TsdfLayerDev& ld = L->dev;
   ScanRegDev d{};
-  d.lut = ld.lut;
-  d.lut_min = make_int3(ld.lut_min[0], ld.lut_min[1], ld.lut_min[2]);
-  d.lut_dim = make_int3(ld.lut_dim[0], ld.lut_dim[1], ld.lut_dim[2]);
-  if (!ld.lut || L->lut_cells == 0) d.lut_dim = make_int3(0, 0, 0);  // (no block table yet: every lookup misses)
-  d.voxel_size = ld.voxel_size;
-  d.voxel_size_inv = ld.voxel_size_inv;
-  d.block_size = (float)ld.vps * ld.voxel_size;
-  d.block_size_inv = 1.0f / d.block_size;
+  static_cast<LayerTable&>(d) = live_layer_table(L);
   d.voxels = ld.voxels;
   d.points = d_points;
   d.n_strided = strided;

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "vgx_internal.h"
+#include "vgx_pose.h"
 
 namespace vgx {
 
@@ -30,12 +31,9 @@ struct ScanRegPartial {  // 136 B
 
 constexpr int kScanMapMaxSubmaps = 64;
 
-// one posed finished submap as the localisation kernels read it: interp_base's / interp_slot's fields over the chosen raw
-// layer, T_S_M (mission-frame points into the submap frame) and the rotation of T_M_S (gradients back)
-struct ScanMapSubmapDev {
-  const int32_t* lut;
-  int3 lut_min, lut_dim;
-  float voxel_size, voxel_size_inv, block_size, block_size_inv;
+// one posed finished submap as the localisation kernels read it: its block table, the chosen raw layer, T_S_M
+// (mission-frame points into the submap frame) and the rotation of T_M_S (gradients back)
+struct ScanMapSubmapDev : LayerTable {
   const float* val;  // ESDF or TSDF distance
   const void* vld;   // ESDF observed (uint8) or TSDF weight (float)
   float q_sm[4], t_sm[3];
@@ -85,11 +83,8 @@ inline double reg_normalize_angle(double a) {
 
 // a pose {qw,qx,qy,qz, tx,ty,tz}: finite, and the quaternion unit by the 1e-4 rule; else what is wrong with it
 inline const char* reg_pose_error(const float* T) {
-  for (int k = 0; k < 7; ++k)
-    if (!std::isfinite(T[k])) return "is not finite";
-  const double n2 = (double)T[0] * T[0] + (double)T[1] * T[1] + (double)T[2] * T[2] + (double)T[3] * T[3];
-  if (std::fabs(n2 - 1.0) > 1e-4) return "has a quaternion that is not unit (| |q|^2 - 1 | > 1e-4)";
-  return nullptr;
+  const PoseDefect bad = pose_defect(T);
+  return bad == kPoseNotFinite ? "is not finite" : bad == kPoseNotUnit ? "has a quaternion that is not unit (| |q|^2 - 1 | > 1e-4)" : nullptr;
 }
 
 // The points of this evaluation (R->mu held, no context lock held: a scan's own lock comes before them and is handed to

@@ -411,6 +411,23 @@ struct vgx_tsdf_layer_s {
   int64_t bound_blocks = 0;
 };
 
+namespace vgx {
+// a live layer's block table (the caller holds tsdf_mu).  A layer with no table yet gets lut_dim = 0: every lookup
+// misses.  The layer keeps no block size: it is (float)vps * voxel_size here, and its inverse 1.0f / that.
+inline LayerTable live_layer_table(const vgx_tsdf_layer_s* L) {
+  const TsdfLayerDev& ld = L->dev;
+  LayerTable t{};
+  t.lut = ld.lut;
+  t.lut_min = make_int3(ld.lut_min[0], ld.lut_min[1], ld.lut_min[2]);
+  if (ld.lut && L->lut_cells > 0) t.lut_dim = make_int3(ld.lut_dim[0], ld.lut_dim[1], ld.lut_dim[2]);
+  t.voxel_size = ld.voxel_size;
+  t.voxel_size_inv = ld.voxel_size_inv;
+  t.block_size = (float)ld.vps * ld.voxel_size;
+  t.block_size_inv = 1.0f / t.block_size;
+  return t;
+}
+}  // namespace vgx
+
 struct vgx_tsdf_integrator_s {
   vgx_ctx ctx = nullptr;
   vgx_tsdf_layer layer = nullptr;
