@@ -110,6 +110,28 @@ VGX_API int vgx_tsdf_integrator_read_event_trace(vgx_tsdf_integrator integrator,
 VGX_API int vgx_tsdf_integrator_download_sets(vgx_tsdf_integrator integrator, uint64_t* start_set, uint64_t* observed_set,
                                               int64_t state[3]);
 
+/* ---- handle age (test tooling, like vgx_tsdf_integrator_set_speculation) ------------------------------------------------
+ * The kernels that take a prefix sum inside one launch tag their tile words with the launch's EPOCH, 1 .. 2^30 - 1 (after
+ * that the words are cleared and the tags start over), and take their tiles as TICKETS from a 32-bit count that is never
+ * reset (csrc/vgx_chain_clock.h, DESIGN.md "Handle age").  A handle reaches the rollover after weeks of use and the ticket
+ * wrap after a day; these calls put a handle there at once (tests/test_handle_age_gpu.py).  Results never depend on them.
+ *
+ * A setter takes the locks a launch of the handle takes, sets what the host hands the next launch, and writes `tickets`,
+ * zero-extended, into the device's ticket word on the TSDF stream.  It never touches the tile words: the stale tags of
+ * real launches stay.  VGX_ERR_INVALID: epoch outside 0 .. 2^30 - 1, tickets outside 0 .. 2^32 - 1, or a handle that has
+ * not launched yet (no decode / no projective frame / no reproducible or merged scan: the words do not exist).  A refused
+ * call changes nothing.  The getters' pointers may be NULL. */
+/* a vgx_scan: the clock of its decodes (PointCloud2 and depth image alike) */
+VGX_API int vgx_scan_set_age(vgx_scan scan, int64_t epoch, int64_t tickets);
+VGX_API int vgx_scan_get_age(vgx_scan scan, int64_t* epoch, int64_t* tickets);
+/* a vgx_tsdf_integrator: the clock of its projective frames (depth-image and range-image integration) */
+VGX_API int vgx_tsdf_integrator_set_projective_age(vgx_tsdf_integrator integrator, int64_t epoch, int64_t tickets);
+VGX_API int vgx_tsdf_integrator_get_projective_age(vgx_tsdf_integrator integrator, int64_t* epoch, int64_t* tickets);
+/* ... and the epoch of its reproducible-mode scratch (the reproducible mode's and the merged integrator's chained
+ * launches and sweeps; its tickets restart with every scan).  Both refuse while the scratch does not exist. */
+VGX_API int vgx_tsdf_integrator_set_reproducible_age(vgx_tsdf_integrator integrator, int64_t epoch);
+VGX_API int vgx_tsdf_integrator_get_reproducible_age(vgx_tsdf_integrator integrator, int64_t* epoch);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,6 +165,22 @@ def lattice(seed=0, name="xyzrgb32"):
     return m.fill(rng, xyz, rng.integers(0, 2 ** 32, m.n, dtype=np.uint64).astype(np.uint32))
 
 
+def aged_pair(seed=0, width=1031, height=67):
+    """two XYZI messages of one size for the handle-age tests (tests/test_handle_age_gpu.py): 69 077 points in 68 tiles of
+    1024 -- a ragged last tile, and tiles 65 to 67 look back through a second window of 64 tiles -- each with about 30 %
+    of its points not finite, chosen from different seeds: every tile keeps another number of points in the two, so no
+    tile's sum in one message is its sum in the other"""
+    pair = []
+    for k in range(2):
+        rng = np.random.default_rng(4000 + 2 * seed + k)
+        m = Msg(width, height, STEP["xyzi32"], FIELDS["xyzi32"])
+        xyz = rng.uniform(-8, 8, (m.n, 3)).astype(F)
+        bad = np.flatnonzero(rng.random(m.n) < 0.3)
+        xyz[bad, rng.integers(0, 3, len(bad))] = rng.choice(np.array([np.nan, np.inf, -np.inf], F), len(bad))
+        pair.append(m.fill(rng, xyz, rng.uniform(-100, 12000, m.n).astype(F)))
+    return pair
+
+
 # every layout the decode tests walk: name -> builder
 LAYOUTS = {
     "xyz16": lambda: small("xyz16", 1),

@@ -39,8 +39,11 @@ def test_library_exports_every_declared_symbol(capi):
     assert not set(tooling) & set(product), sorted(set(tooling) & set(product))
     assert set(tooling) <= set(_exported(capi.BENCH_LIB_PATH))
     assert tooling == ["vgx_bench_alloc_scattered", "vgx_bench_atomic_roundtrip", "vgx_bench_free_scattered", "vgx_bench_stream_ceiling",
+                       "vgx_scan_get_age", "vgx_scan_set_age",
                        "vgx_synth_city_scan", "vgx_synth_city_submap", "vgx_tsdf_integrator_download_sets",
+                       "vgx_tsdf_integrator_get_projective_age", "vgx_tsdf_integrator_get_reproducible_age",
                        "vgx_tsdf_integrator_read_event_trace", "vgx_tsdf_integrator_read_trace", "vgx_tsdf_integrator_set_event_trace",
+                       "vgx_tsdf_integrator_set_projective_age", "vgx_tsdf_integrator_set_reproducible_age",
                        "vgx_tsdf_integrator_set_speculation", "vgx_tsdf_integrator_walk_stats"]
 
 

@@ -635,7 +635,15 @@ BENCH_SIGNATURES = {
     "vgx_tsdf_integrator_set_event_trace": (C.c_int, [vp, C.c_int64]),
     "vgx_tsdf_integrator_read_event_trace": (C.c_int, [vp, C.POINTER(C.c_uint64), C.c_int64, i64p, i64p]),
     "vgx_tsdf_integrator_download_sets": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), i64p]),
+    "vgx_scan_set_age": (C.c_int, [vp, C.c_int64, C.c_int64]),
+    "vgx_scan_get_age": (C.c_int, [vp, i64p, i64p]),
+    "vgx_tsdf_integrator_set_projective_age": (C.c_int, [vp, C.c_int64, C.c_int64]),
+    "vgx_tsdf_integrator_get_projective_age": (C.c_int, [vp, i64p, i64p]),
+    "vgx_tsdf_integrator_set_reproducible_age": (C.c_int, [vp, C.c_int64]),
+    "vgx_tsdf_integrator_get_reproducible_age": (C.c_int, [vp, i64p]),
 }
+
+CHAIN_EPOCH_MAX = (1 << 30) - 1   # csrc/vgx_chain_clock.h kChainEpochMax
 
 _lib = None
 
@@ -2572,6 +2580,16 @@ class Scan:
         self.ctx.check(self.ctx.lib.vgx_scan_undistort_stats(self.h, C.byref(b), C.byref(o), C.byref(c)))
         return b.value, o.value, c.value
 
+    def set_age(self, epoch, tickets):
+        """test tooling: the decode's chain clock (vgx_scan_set_age)"""
+        self.ctx.check(self.ctx.lib.vgx_scan_set_age(self.h, int(epoch), int(tickets)))
+
+    def get_age(self):
+        """test tooling: (epoch, tickets) of the decode's chain clock"""
+        e, t = C.c_int64(), C.c_int64()
+        self.ctx.check(self.ctx.lib.vgx_scan_get_age(self.h, C.byref(e), C.byref(t)))
+        return e.value, t.value
+
     def download(self):
         """(points [n][3] f32, rgba [n][4] uint8)"""
         n, _ = self.stats()
@@ -3200,6 +3218,26 @@ class FastTsdfIntegrator:
         """test tooling (reproducible mode): write rays out `depth` steps deep at first when a scan's complete
         walks exceed `threshold` steps; the layer does not depend on either"""
         self.ctx.check(self.ctx.lib.vgx_tsdf_integrator_set_speculation(self.h, depth, threshold))
+
+    def set_projective_age(self, epoch, tickets):
+        """test tooling: the chain clock of the projective frames (vgx_tsdf_integrator_set_projective_age)"""
+        self.ctx.check(self.ctx.lib.vgx_tsdf_integrator_set_projective_age(self.h, int(epoch), int(tickets)))
+
+    def get_projective_age(self):
+        """test tooling: (epoch, tickets) of the projective frames' chain clock"""
+        e, t = C.c_int64(), C.c_int64()
+        self.ctx.check(self.ctx.lib.vgx_tsdf_integrator_get_projective_age(self.h, C.byref(e), C.byref(t)))
+        return e.value, t.value
+
+    def set_reproducible_age(self, epoch):
+        """test tooling: the epoch of the reproducible-mode scratch (vgx_tsdf_integrator_set_reproducible_age)"""
+        self.ctx.check(self.ctx.lib.vgx_tsdf_integrator_set_reproducible_age(self.h, int(epoch)))
+
+    def get_reproducible_age(self):
+        """test tooling: the epoch of the reproducible-mode scratch"""
+        e = C.c_int64()
+        self.ctx.check(self.ctx.lib.vgx_tsdf_integrator_get_reproducible_age(self.h, C.byref(e)))
+        return e.value
 
     def read_trace(self, max_workgroups):
         """last counted racing scan -> [workgroups][16] float64: four stamps in microseconds relative to the first start,

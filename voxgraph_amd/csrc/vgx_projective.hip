@@ -168,17 +168,13 @@ int projective_begin(const char* fn, vgx_tsdf_integrator I, const int32_t lo[3],
     const hipError_t e = I->d_proj_ctl.alloc(kProjCtlWords * 8);
     if (e != hipSuccess) return alloc_error(ctx, e, "projective integration: allocating counters");
     VGX_HIP(ctx, hipMemsetAsync(I->d_proj_ctl.p, 0, kProjCtlWords * 8, st));
-    I->proj_tickets = 0;
+    I->proj_clock.tickets = 0;
   }
   if ((size_t)candidates * 8 > I->d_proj_state.bytes) {
     VGX_HIP(ctx, hipStreamSynchronize(st));
     const hipError_t e = I->d_proj_state.reserve((size_t)candidates * 8, 0, true);
     if (e != hipSuccess) return alloc_error(ctx, e, "projective integration: allocating tile words");
     VGX_HIP(ctx, hipMemsetAsync(I->d_proj_state.p, 0, I->d_proj_state.bytes, st));  // (epoch 0: no launch's tag)
-  }
-  if (I->proj_epoch >= kChainEpochMax) {
-    VGX_HIP(ctx, hipMemsetAsync(I->d_proj_state.p, 0, I->d_proj_state.bytes, st));
-    I->proj_epoch = 0;
   }
   for (int a = 0; a < 3; ++a) f->lo[a] = lo[a];
   f->nx = (int32_t)nx;
@@ -192,12 +188,13 @@ int projective_chain(vgx_tsdf_integrator I, const ProjFrameBase& f, TileChain* c
   vgx_ctx ctx = I->ctx;
   unsigned long long* ctl = I->d_proj_ctl.as<unsigned long long>();
   VGX_HIP(ctx, hipMemsetAsync(ctl + kProjNew, 0, 8 * (kProjCtlWords - kProjNew), ctx->tsdf_stream));
+  ChainTake t;
+  VGX_HIP(ctx, chain_take(&I->proj_clock, f.tiles, I->d_proj_state, ctx->tsdf_stream, &t));
   chain->state = I->d_proj_state.as<unsigned long long>();
-  chain->epoch = ++I->proj_epoch;
+  chain->epoch = t.epoch;
   chain->ticket = ctl + kProjTicket;
-  chain->ticket_base = I->proj_tickets;
+  chain->ticket_base = t.ticket_base;
   chain->error = ctl + kProjError;
-  I->proj_tickets += f.tiles;
   return VGX_OK;
 }
 

@@ -32,10 +32,7 @@ namespace vgx {
 constexpr int kScanIpt = 4;                    // consecutive points per thread
 constexpr int kScanTile = 256 * kScanIpt;      // points per workgroup
 constexpr size_t kScanStageBytes = 1u << 20;   // one pinned staging buffer (two of them, filled in turn)
-// u64 words of vgx_scan_s::d_ctl; {error, total, bad time, overflowed, clamped} are read back in one copy, and after a
-// depth-image decode the three words behind them with it
-enum { kScanTicket = 0, kScanError = 1, kScanTotal = 2, kScanBadTime = 3, kScanOverflowed = 4, kScanClamped = 5,
-       kScanDepthInvalid = 6, kScanDepthOutOfRange = 7, kScanDepthOverflowed = 8, kScanCtlWords = 16 };
+// (the u64 words of vgx_scan_s::d_ctl, kScan*, and vgx_scan_s itself: vgx_tsdf_internal.h)
 
 struct ScanMsg {
   const uint8_t* data;
@@ -320,29 +317,6 @@ __global__ __launch_bounds__(256) void depth_decode_undistort_kernel(DepthImage 
 
 using namespace vgx;
 
-struct vgx_scan_s {
-  vgx_ctx ctx = nullptr;
-  std::mutex mu;
-  int64_t n_points = 0, n_dropped = 0;  // the scan held now
-  int64_t n_bad_time = 0, n_overflowed = 0, n_clamped = 0;  // (zeros after a plain decode)
-  int64_t depth_candidates = 0, depth_invalid = 0, depth_out_of_range = 0, depth_overflowed = 0;  // (zeros after a PointCloud2)
-  DeviceBuffer d_points;                // float [cap][3]: room for every point of the largest message so far
-  DeviceBuffer d_rgba;                  // u32 [cap] bytes r g b a
-  DeviceBuffer d_msg;                   // the host variant's upload (a depth image, then its colour image at the next 16 bytes)
-  // TileChain of the decode kernel: {ticket, error, total, three running counters} and one word per tile, tagged with
-  // the launch's epoch
-  DeviceBuffer d_ctl, d_state;
-  uint32_t epoch = 0, tickets = 0;
-  // the undistorting decode: the track's upload (knot times, then knot transforms), and what the three running counters
-  // of d_ctl held at the last read-back (not known after a launch whose read-back failed: cleared before the next);
-  // depth_base: the same for the depth-image decode's three
-  DeviceBuffer d_knots;
-  unsigned long long counters_base[3] = {0, 0, 0}, depth_base[3] = {0, 0, 0};
-  bool counters_known = true;
-  UploadStage stage;      // host variant: halves of kScanStageBytes, allocated at first use
-  bool pageable = false;  // no pinned memory was to be had: uploads go straight from the caller's bytes
-};
-
 namespace vgx {
 vgx_ctx scan_context(vgx_scan S) { return S ? S->ctx : nullptr; }
 std::unique_lock<std::mutex> scan_borrow(vgx_scan S, const float** d_points, int64_t* n) {
@@ -505,9 +479,9 @@ int scan_upload(vgx_scan S, hipStream_t st, const void* data, size_t bytes, size
   return VGX_OK;
 }
 
-// Room for a decode of n candidates in `tiles` tiles, queued on the TSDF stream: the arrays, the control words, the tile
-// words, and the launch's chain.
-int scan_reserve(vgx_scan S, uint32_t n, uint32_t tiles, TileChain* chain_out) {
+// Room for a decode of n candidates in `tiles` tiles, queued on the TSDF stream: the arrays, the control words and the
+// tile words.
+int scan_reserve(vgx_scan S, uint32_t n, uint32_t tiles) {
   vgx_ctx ctx = S->ctx;
   hipStream_t st = ctx->tsdf_stream;
   if ((size_t)n * 4 > S->d_rgba.bytes) {
@@ -519,7 +493,7 @@ int scan_reserve(vgx_scan S, uint32_t n, uint32_t tiles, TileChain* chain_out) {
     const hipError_t e = S->d_ctl.alloc(kScanCtlWords * 8);
     if (e != hipSuccess) return alloc_error(ctx, e, "scan: allocating counters");
     VGX_HIP(ctx, hipMemsetAsync(S->d_ctl.p, 0, kScanCtlWords * 8, st));
-    S->tickets = 0;
+    S->clock.tickets = 0;
   }
   if ((size_t)tiles * 8 > S->d_state.bytes) {
     VGX_HIP(ctx, hipStreamSynchronize(st));
@@ -527,19 +501,20 @@ int scan_reserve(vgx_scan S, uint32_t n, uint32_t tiles, TileChain* chain_out) {
     if (e != hipSuccess) return alloc_error(ctx, e, "scan: allocating tile words");
     VGX_HIP(ctx, hipMemsetAsync(S->d_state.p, 0, S->d_state.bytes, st));  // (epoch 0: no launch's tag)
   }
-  if (S->epoch >= kChainEpochMax) {  // (after 2^30 decodes: start the tags over)
-    VGX_HIP(ctx, hipMemsetAsync(S->d_state.p, 0, S->d_state.bytes, st));
-    S->epoch = 0;
-  }
+  return VGX_OK;
+}
+
+// The launch's chain, after scan_reserve.  Right before the launch: nothing that can fail may come between.
+int scan_chain(vgx_scan S, uint32_t tiles, TileChain* chain) {
+  vgx_ctx ctx = S->ctx;
+  ChainTake t;
+  VGX_HIP(ctx, chain_take(&S->clock, tiles, S->d_state, ctx->tsdf_stream, &t));
   unsigned long long* ctl = S->d_ctl.as<unsigned long long>();
-  TileChain chain;
-  chain.state = S->d_state.as<unsigned long long>();
-  chain.epoch = ++S->epoch;
-  chain.ticket = ctl + kScanTicket;
-  chain.ticket_base = S->tickets;
-  chain.error = ctl + kScanError;
-  S->tickets += tiles;
-  *chain_out = chain;
+  chain->state = S->d_state.as<unsigned long long>();
+  chain->epoch = t.epoch;
+  chain->ticket = ctl + kScanTicket;
+  chain->ticket_base = t.ticket_base;
+  chain->error = ctl + kScanError;
   return VGX_OK;
 }
 
@@ -583,8 +558,7 @@ int scan_decode_queued(vgx_scan S, const vgx_scan_layout& l, const vgx_scan_conf
   hipStream_t st = ctx->tsdf_stream;
   const uint32_t n = l.width * l.height;
   const uint32_t tiles = (n + kScanTile - 1) / kScanTile;
-  TileChain chain;
-  int rc = scan_reserve(S, n, tiles, &chain);
+  int rc = scan_reserve(S, n, tiles);
   if (rc != VGX_OK) return rc;
   unsigned long long* ctl = S->d_ctl.as<unsigned long long>();
   ScanMsg m{};
@@ -602,7 +576,10 @@ int scan_decode_queued(vgx_scan S, const vgx_scan_layout& l, const vgx_scan_conf
   m.intensity_max = c.intensity_max;
   std::memcpy(&m.constant, c.constant_rgba, 4);
   bool dwords = ((uintptr_t)d_data | l.point_step | l.row_step | l.offset_x | l.offset_y | l.offset_z | m.color_offset) % 4 == 0;
+  // (the chain is taken right before the launch: nothing that can fail may come between)
+  TileChain chain;
   if (!tr) {
+    if ((rc = scan_chain(S, tiles, &chain)) != VGX_OK) return rc;
     if (dwords)
       hipLaunchKernelGGL(scan_decode_kernel<true>, dim3(tiles), dim3(256), 0, st, m, chain, S->d_points.as<float>(),
                          S->d_rgba.as<uint32_t>(), ctl + kScanTotal);
@@ -617,6 +594,7 @@ int scan_decode_queued(vgx_scan S, const vgx_scan_layout& l, const vgx_scan_conf
     u.scale = f->scale;
     u.offset_s = f->offset_s;
     dwords = dwords && f->offset % 4 == 0;
+    if ((rc = scan_chain(S, tiles, &chain)) != VGX_OK) return rc;
     if (dwords)
       hipLaunchKernelGGL(scan_decode_undistort_kernel<true>, dim3(tiles), dim3(256), 0, st, m, u, chain, S->d_points.as<float>(),
                          S->d_rgba.as<uint32_t>(), ctl + kScanTotal);
@@ -702,8 +680,7 @@ int depth_decode_queued(vgx_scan S, const vgx_depth_image_layout& l, const vgx_d
   const uint32_t wc = (l.width - 1) / su + 1, hc = (l.height - 1) / sv + 1;  // (width, height >= 1 here)
   const uint32_t n = wc * hc;
   const uint32_t tiles = (n + kScanTile - 1) / kScanTile;
-  TileChain chain;
-  int rc = scan_reserve(S, n, tiles, &chain);
+  int rc = scan_reserve(S, n, tiles);
   if (rc != VGX_OK) return rc;
   unsigned long long* ctl = S->d_ctl.as<unsigned long long>();
   DepthImage m{};
@@ -738,6 +715,9 @@ int depth_decode_queued(vgx_scan S, const vgx_depth_image_layout& l, const vgx_d
   float* points = S->d_points.as<float>();
   uint32_t* rgba = S->d_rgba.as<uint32_t>();
   const ScanDeskew* up = tr ? &u : nullptr;
+  // (the chain is taken right before the launch: nothing that can fail may come between)
+  TileChain chain;
+  if ((rc = scan_chain(S, tiles, &chain)) != VGX_OK) return rc;
   if (sixteen) {
     if (elements)
       depth_launch<VGX_DEPTH_16UC1, true>(st, tiles, m, up, chain, points, rgba, ctl + kScanTotal);

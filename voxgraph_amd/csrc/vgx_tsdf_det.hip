@@ -69,10 +69,9 @@ struct DetScratch {
   unsigned long long* d_ctr = nullptr;  // ctr_mem, typed
   unsigned long long* h_ctr = nullptr;  // ctr_host_mem, typed
   // the sweeps (det_sweep_kernel): one 8-byte state per tile of the sorted accesses, tagged with the sweep's
-  // epoch so that nothing has to be cleared between sweeps; zeroed when (re)allocated
+  // epoch so that nothing has to be cleared between sweeps; zeroed when (re)allocated.  The words are shared with every
+  // TileChain launch, and so is the clock that numbers them: vgx_tsdf_integrator_s::det_clock
   DeviceBuffer tile_state;
-  uint32_t sweep_epoch = 0;      // ... and of every TileChain launch (one counter: the words are shared)
-  uint32_t chain_tickets = 0;    // TileChain workgroups launched since the scan's first kernel zeroed kCtrChainTicket
   // what the sweep's last block tells the host (pinned, written from the kernel): sweep sequence number << 2 |
   // error << 1 | "a stopping step moved"
   unsigned long long* h_flag = nullptr;  // flag_mem, typed
@@ -356,7 +355,6 @@ struct UpdateOp {  // 1 for an access that updates its voxel
 constexpr int kSweepIpt = 8;
 static_assert(kSweepIpt % 4 == 0, "whole 16-byte loads");
 constexpr uint32_t kSweepTile = 256u * kSweepIpt;
-constexpr unsigned long long kSweepEpochMax = (1ull << 30) - 1;
 
 __device__ __forceinline__ void load8(const uint32_t* __restrict__ a, uint32_t base, uint32_t N, uint32_t (&v)[kSweepIpt]) {
   if (base + kSweepIpt <= N) {  // base is a multiple of kSweepIpt: aligned 16-byte loads
@@ -1145,20 +1143,19 @@ int sort_by_slot(vgx_ctx ctx, DetScratch* S, const uint32_t* keys, uint32_t* key
 }
 
 // the chain of the next prefix-sum launch over `tiles` workgroups: room for its words, its epoch, its ticket base
-int next_chain(vgx_ctx ctx, DetScratch* S, uint32_t tiles, TileChain* ch) {
+// (the callers launch right behind it: nothing that can fail may come between)
+int next_chain(vgx_tsdf_integrator I, uint32_t tiles, TileChain* ch) {
+  vgx_ctx ctx = I->ctx;
+  DetScratch* S = I->det;
   int rc = grow_zeroed(ctx, S->tile_state, (size_t)tiles * 8);
   if (rc != VGX_OK) return rc;
-  if (S->sweep_epoch >= kChainEpochMax) {  // (after 2^30 launches: start the tags over)
-    VGX_HIP(ctx, hipMemsetAsync(S->tile_state.p, 0, S->tile_state.bytes, ctx->tsdf_stream));
-    S->sweep_epoch = 0;
-  }
-  ++S->sweep_epoch;
+  ChainTake t;
+  VGX_HIP(ctx, chain_take(&I->det_clock, tiles, S->tile_state, ctx->tsdf_stream, &t));
   ch->state = S->tile_state.as<unsigned long long>();
-  ch->epoch = S->sweep_epoch;
+  ch->epoch = t.epoch;
   ch->ticket = S->d_ctr + kCtrChainTicket;
-  ch->ticket_base = S->chain_tickets;
+  ch->ticket_base = t.ticket_base;
   ch->error = S->d_ctr + kCtrError;
-  S->chain_tickets += tiles;
   return VGX_OK;
 }
 
@@ -1256,13 +1253,13 @@ static int ensure_scratch(vgx_tsdf_integrator I) {
 int det_counters(vgx_tsdf_integrator I, unsigned long long** d_ctr) {
   DET_TRY(ensure_scratch(I));
   *d_ctr = I->det->d_ctr;
-  I->det->chain_tickets = 0;  // (the caller's first kernel zeroes the counters)
+  I->det_clock.tickets = 0;  // (the caller's first kernel zeroes the counters)
   return VGX_OK;
 }
 
 // the TileChain of the merged integrator's next prefix-sum launch (vgx_tsdf.hip), after det_counters
 int det_next_chain(vgx_tsdf_integrator I, uint32_t tiles, TileChain* chain) {
-  return next_chain(I->ctx, I->det, tiles, chain);
+  return next_chain(I, tiles, chain);
 }
 
 // ---- 3. the updates that happen, in sorted order -> compaction, new blocks, ordered application ----
@@ -1300,7 +1297,7 @@ static int det_commit(vgx_tsdf_integrator I, DetScratch* S, const float T[7], si
     uint32_t* m_word = S->acc_key.as<uint32_t>() + N;  // (free since the sort)
     const uint32_t finish_tiles = (uint32_t)((N + kSweepTile - 1) / kSweepTile);
     TileChain chain;
-    DET_TRY(next_chain(ctx, S, finish_tiles, &chain));
+    DET_TRY(next_chain(I, finish_tiles, &chain));
     if (update->flags)
       hipLaunchKernelGGL(det_finish_kernel<true>, dim3(finish_tiles), dim3(256), 0, st, (uint32_t)N, S->s_key.as<uint32_t>(),
                          S->s_idx.as<uint32_t>(), S->s_h.as<uint32_t>(), S->last.as<uint32_t>(), *update, chain, m_word,
@@ -1448,7 +1445,7 @@ int det_integrate(vgx_tsdf_integrator I, const float T[7], const void* d_points,
   const bool start_capped = may_cap_at_all && S->start_capped;
   const bool keep_marks = start_capped && S->ext_points == n;  // the previous scan's pioneers: written out completely at once
   S->ext_points = -1;  // (until this scan has left its own)
-  S->chain_tickets = 0;  // (det_points_kernel zeroes the counters)
+  I->det_clock.tickets = 0;  // (det_points_kernel zeroes the counters)
   hipLaunchKernelGGL(det_points_kernel, dim3(blocks_for(np + 1)), dim3(256), 0, st, c, vsi, T[0], T[1], T[2], T[3], T[4], T[5],
                      T[6], (const float*)d_points, (const uint32_t*)d_rgba, (long long)n, order, (int)freespace,
                      I->dev.start_offset, S->ray_pg.as<float4>(), S->ray_color.as<uint32_t>(), S->ray_flags.as<uint32_t>(),
@@ -1483,7 +1480,7 @@ int det_integrate(vgx_tsdf_integrator I, const float T[7], const void* d_points,
     {
       const uint32_t count_tiles = blocks_for(np + 1);
       TileChain chain;
-      DET_TRY(next_chain(ctx, S, count_tiles, &chain));
+      DET_TRY(next_chain(I, count_tiles, &chain));
       hipLaunchKernelGGL(det_count_kernel, dim3(count_tiles), dim3(256), 0, st, c, vsi, T[4], T[5], T[6], (long long)n,
                          S->ray_pg.as<float4>(), S->ray_flags.as<uint32_t>(), S->ext.as<uint8_t>(), S->count.as<uint32_t>(),
                          S->full_count.as<uint32_t>(), S->start_key_sorted.as<uint32_t>(), S->start_seq_sorted.as<uint32_t>(),
@@ -1555,12 +1552,10 @@ int det_integrate(vgx_tsdf_integrator I, const float T[7], const void* d_points,
         if (issued > n + 2 + ahead + (walks_done > 1 ? (long long)N : 0))  // (a warm start: at least a step a sweep)
           return set_error(ctx, VGX_ERR_HIP, "TSDF reproducible mode: the sweeps did not settle (internal error)");
         while (issued <= heard + 1 + ahead) {
-          if (S->sweep_epoch >= kSweepEpochMax) {  // (after 2^30 sweeps: start the tags over)
-            VGX_HIP(ctx, hipMemsetAsync(S->tile_state.p, 0, S->tile_state.bytes, st));
-            S->sweep_epoch = 0;
-          }
-          ++S->sweep_epoch;
-          hipLaunchKernelGGL(det_sweep_kernel, dim3(tiles), dim3(256), 0, st, (uint32_t)N, (unsigned long long)S->sweep_epoch,
+          // (a sweep takes its tiles from kCtrTicket, which its ray kernel zeroes again: an epoch, no chain tickets)
+          ChainTake sweep;
+          VGX_HIP(ctx, chain_take(&I->det_clock, 0, S->tile_state, st, &sweep));
+          hipLaunchKernelGGL(det_sweep_kernel, dim3(tiles), dim3(256), 0, st, (uint32_t)N, (unsigned long long)sweep.epoch,
                              S->d_ctr, S->tile_state.as<unsigned long long>(), S->s_key.as<uint32_t>(),
                              S->s_idx.as<uint32_t>(), S->s_h.as<uint32_t>(), S->s_r.as<uint32_t>(), S->s_k.as<uint32_t>(),
                              S->T.as<int32_t>(), I->dev.observed_set, I->dev.observed_offset, S->seen.as<uint8_t>(),
@@ -1621,7 +1616,7 @@ int det_merged_commit(vgx_tsdf_integrator I, const float T[7], long long n, cons
   {
     const uint32_t scan_tiles = (uint32_t)((G + 1 + 256 * kScanIpt - 1) / (256 * kScanIpt));
     TileChain chain;
-    DET_TRY(next_chain(ctx, S, scan_tiles, &chain));
+    DET_TRY(next_chain(I, scan_tiles, &chain));
     hipLaunchKernelGGL(det_offsets_kernel, dim3(scan_tiles), dim3(256), 0, st, (const uint32_t*)g_count, S->off.as<uint32_t>(),
                        (uint32_t)(G + 1), chain);
     VGX_HIP(ctx, hipGetLastError());

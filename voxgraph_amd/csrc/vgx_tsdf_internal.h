@@ -11,6 +11,7 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "vgx_chain_clock.h"
 #include "vgx_internal.h"
 
 namespace vgx {
@@ -249,7 +250,25 @@ struct TileChain {
   uint32_t ticket_base;
   unsigned long long* error;   // set to 3 if a tile that started before this one never reported (internal error)
 };
-constexpr unsigned long long kChainEpochMax = (1ull << 30) - 1;
+
+// The host side of one launch: the epoch and the ticket base of the handle's clock (ChainClock, vgx_chain_clock.h: the one
+// place the epochs roll over and the tickets are counted), and the stream-ordered clearing of the tile words where the
+// epochs have started over.  Called right before the launch: nothing that can fail may come between taking a chain and
+// the launch -- tickets taken for workgroups that never start leave every later launch's ticket base too high.  (An error
+// here leaves the clock as it was.)
+inline hipError_t chain_take(ChainClock* clock, uint32_t tiles, const DeviceBuffer& words, hipStream_t st, ChainTake* out) {
+  const ChainClock before = *clock;
+  const ChainTake t = clock->take(tiles);
+  if (t.clear_first) {
+    const hipError_t e = hipMemsetAsync(words.p, 0, words.bytes, st);
+    if (e != hipSuccess) {
+      *clock = before;
+      return e;
+    }
+  }
+  *out = t;
+  return hipSuccess;
+}
 
 // this workgroup's tile; every thread calls it (sh: one shared word)
 __device__ __forceinline__ uint32_t chain_tile(const TileChain& ch, uint32_t* sh) {
@@ -483,7 +502,42 @@ struct vgx_tsdf_integrator_s {
   // image at the next 16 bytes), the control words {ticket, error, the frame's counters} and the TileChain's word per
   // candidate block, tagged with the launch's epoch
   vgx::DeviceBuffer d_image, d_proj_ctl, d_proj_state;
-  uint32_t proj_epoch = 0, proj_tickets = 0;
+  vgx::ChainClock proj_clock;
+  // the reproducible mode's chain launches and sweeps (vgx_tsdf_det.hip; they share DetScratch::tile_state, so one clock).
+  // Its tickets count the TileChain workgroups launched since the scan's first kernel zeroed kCtrChainTicket.  Here and
+  // not in the scratch object, where the tooling library can age it.
+  vgx::ChainClock det_clock;
+};
+
+// ---- a decoded scan (vgx_scan.hip) ----
+namespace vgx {
+// u64 words of vgx_scan_s::d_ctl; {error, total, bad time, overflowed, clamped} are read back in one copy, and after a
+// depth-image decode the three words behind them with it
+enum { kScanTicket = 0, kScanError = 1, kScanTotal = 2, kScanBadTime = 3, kScanOverflowed = 4, kScanClamped = 5,
+       kScanDepthInvalid = 6, kScanDepthOutOfRange = 7, kScanDepthOverflowed = 8, kScanCtlWords = 16 };
+}  // namespace vgx
+
+struct vgx_scan_s {
+  vgx_ctx ctx = nullptr;
+  std::mutex mu;
+  int64_t n_points = 0, n_dropped = 0;  // the scan held now
+  int64_t n_bad_time = 0, n_overflowed = 0, n_clamped = 0;  // (zeros after a plain decode)
+  int64_t depth_candidates = 0, depth_invalid = 0, depth_out_of_range = 0, depth_overflowed = 0;  // (zeros after a PointCloud2)
+  vgx::DeviceBuffer d_points;           // float [cap][3]: room for every point of the largest message so far
+  vgx::DeviceBuffer d_rgba;             // u32 [cap] bytes r g b a
+  vgx::DeviceBuffer d_msg;              // the host variant's upload (a depth image, then its colour image at the next 16 bytes)
+  // TileChain of the decode kernel: {ticket, error, total, three running counters} and one word per tile, tagged with
+  // the launch's epoch
+  vgx::DeviceBuffer d_ctl, d_state;
+  vgx::ChainClock clock;
+  // the undistorting decode: the track's upload (knot times, then knot transforms), and what the three running counters
+  // of d_ctl held at the last read-back (not known after a launch whose read-back failed: cleared before the next);
+  // depth_base: the same for the depth-image decode's three
+  vgx::DeviceBuffer d_knots;
+  unsigned long long counters_base[3] = {0, 0, 0}, depth_base[3] = {0, 0, 0};
+  bool counters_known = true;
+  vgx::UploadStage stage;  // host variant: halves of kScanStageBytes, allocated at first use
+  bool pageable = false;   // no pinned memory was to be had: uploads go straight from the caller's bytes
 };
 
 namespace vgx {
@@ -521,7 +575,7 @@ int det_next_chain(vgx_tsdf_integrator I, uint32_t tiles, TileChain* chain);
 int det_merged_commit(vgx_tsdf_integrator I, const float T[7], long long n, const float4* g_pg, const uint32_t* g_color,
                       const uint32_t* g_flags, uint32_t* g_count, const unsigned long long* keys_sorted,
                       const unsigned int* group_start, const unsigned int* counters, int64_t* n_updates);
-// vgx_scan.hip: the context a decoded scan lives on (vgx_scan_s is private to that file)
+// vgx_scan.hip: the context a decoded scan lives on
 vgx_ctx scan_context(vgx_scan S);
 // the scan's lock (taken before ctx->tsdf_mu, as the decode takes it) and what the scan holds now: while the caller keeps
 // the lock no decode can replace the array a queued kernel reads
