@@ -58,39 +58,41 @@ int main(int argc, char** argv) {
     empty.addSubmapNode(1, {1, 0, 0, 0}, false);
     if (empty.optimize() != VGX_ERR_INVALID || empty.last_error().find("without constraints") == std::string::npos) rc = 20;
   }
-  GpuPoseGraph graph(ctx);
-  const int n = 8;
-  graph.addReferenceFrameNode(0, {0, 0, 0, 0});
-  for (int k = 0; k < n; ++k) {
-    const double a = 2.0 * M_PI * k / n;
-    graph.addSubmapNode(100 + k, {2.0 * std::cos(a) - 2.0 + 0.05 * k, 2.0 * std::sin(a) - 0.03 * k, 0.01 * k, 0.9 * a / M_PI - 0.01 * k}, k == 0);
-  }
-  for (int k = 0; k + 1 < n; ++k) {
-    const double a = 2.0 * M_PI * k / n, b = 2.0 * M_PI * (k + 1) / n;
-    const double dx = 2.0 * (std::cos(b) - std::cos(a)), dy = 2.0 * (std::sin(b) - std::sin(a)), ya = 0.9 * a / M_PI;
-    const double t[3] = {std::cos(ya) * dx + std::sin(ya) * dy, -std::sin(ya) * dx + std::cos(ya) * dy, 0.0};
-    if (!graph.addRelativePoseConstraint(100 + k, 101 + k, t, 0.9 * (b - a) / M_PI, kOdometryInformation)) rc = 21;
-  }
-  {
-    const double a = 2.0 * M_PI * (n - 1) / n, ya = 0.9 * a / M_PI;
-    const double dx = 2.0 * (1.0 - std::cos(a)), dy = -2.0 * std::sin(a);
-    const double t[3] = {std::cos(ya) * dx + std::sin(ya) * dy, -std::sin(ya) * dx + std::cos(ya) * dy, 0.0};
-    if (!graph.addRelativePoseConstraint(100 + n - 1, 100, t, -ya, kLoopInformation)) rc = 22;
-    const double height[3] = {-4.0, 0.0, 0.0};
-    if (!graph.addAbsolutePoseConstraint(0, 100 + n / 2, height, 0.9, kOdometryInformation)) rc = 23;
-  }
-  if (rc == 0 && graph.optimize(false) != VGX_OK) {
-    std::printf("optimize: %s\n", graph.last_error().c_str());
-    rc = 24;
-  }
-  if (rc == 0) {
-    const vgx_pose_graph_summary& s = graph.getSolverSummaries().back();
-    if (s.termination_type != VGX_CONVERGENCE || !(s.final_cost < s.initial_cost) || graph.lastHistory().size() != static_cast<size_t>(s.num_iterations))
-      rc = 25;
-    std::ofstream out(argv[1], std::ios::binary);
-    const double head[4] = {static_cast<double>(s.num_iterations), static_cast<double>(s.termination_reason), s.initial_cost, s.final_cost};
-    out.write(reinterpret_cast<const char*>(head), sizeof(head));
-    for (const auto& kv : graph.getSubmapPoses()) out.write(reinterpret_cast<const char*>(kv.second.data()), 4 * sizeof(double));
+  {  // (the graph goes before its context does: its destructor synchronises the context's stream)
+    GpuPoseGraph graph(ctx);
+    const int n = 8;
+    graph.addReferenceFrameNode(0, {0, 0, 0, 0});
+    for (int k = 0; k < n; ++k) {
+      const double a = 2.0 * M_PI * k / n;
+      graph.addSubmapNode(100 + k, {2.0 * std::cos(a) - 2.0 + 0.05 * k, 2.0 * std::sin(a) - 0.03 * k, 0.01 * k, 0.9 * a / M_PI - 0.01 * k}, k == 0);
+    }
+    for (int k = 0; k + 1 < n; ++k) {
+      const double a = 2.0 * M_PI * k / n, b = 2.0 * M_PI * (k + 1) / n;
+      const double dx = 2.0 * (std::cos(b) - std::cos(a)), dy = 2.0 * (std::sin(b) - std::sin(a)), ya = 0.9 * a / M_PI;
+      const double t[3] = {std::cos(ya) * dx + std::sin(ya) * dy, -std::sin(ya) * dx + std::cos(ya) * dy, 0.0};
+      if (!graph.addRelativePoseConstraint(100 + k, 101 + k, t, 0.9 * (b - a) / M_PI, kOdometryInformation)) rc = 21;
+    }
+    {
+      const double a = 2.0 * M_PI * (n - 1) / n, ya = 0.9 * a / M_PI;
+      const double dx = 2.0 * (1.0 - std::cos(a)), dy = -2.0 * std::sin(a);
+      const double t[3] = {std::cos(ya) * dx + std::sin(ya) * dy, -std::sin(ya) * dx + std::cos(ya) * dy, 0.0};
+      if (!graph.addRelativePoseConstraint(100 + n - 1, 100, t, -ya, kLoopInformation)) rc = 22;
+      const double height[3] = {-4.0, 0.0, 0.0};
+      if (!graph.addAbsolutePoseConstraint(0, 100 + n / 2, height, 0.9, kOdometryInformation)) rc = 23;
+    }
+    if (rc == 0 && graph.optimize(false) != VGX_OK) {
+      std::printf("optimize: %s\n", graph.last_error().c_str());
+      rc = 24;
+    }
+    if (rc == 0) {
+      const vgx_pose_graph_summary& s = graph.getSolverSummaries().back();
+      if (s.termination_type != VGX_CONVERGENCE || !(s.final_cost < s.initial_cost) || graph.lastHistory().size() != static_cast<size_t>(s.num_iterations))
+        rc = 25;
+      std::ofstream out(argv[1], std::ios::binary);
+      const double head[4] = {static_cast<double>(s.num_iterations), static_cast<double>(s.termination_reason), s.initial_cost, s.final_cost};
+      out.write(reinterpret_cast<const char*>(head), sizeof(head));
+      for (const auto& kv : graph.getSubmapPoses()) out.write(reinterpret_cast<const char*>(kv.second.data()), 4 * sizeof(double));
+    }
   }
   vgx_ctx_destroy(ctx);
   if (rc == 0) std::printf("POSE_GRAPH_SMOKE_OK\n");

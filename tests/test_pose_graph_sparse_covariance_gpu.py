@@ -91,6 +91,29 @@ def test_block_spd_solve_many_is_the_restatement_and_the_single_solve_bit_for_bi
     assert same is B and same_bits(B, X0)
 
 
+def test_block_spd_solve_many_on_the_arrowhead_takes_a_last_single_tile_after_pairs_both_ways(capi, ctx):
+    """block_scenes()[1156]: all 190 tiles of 19 tile rows are stored, so tile column K has 18 - K tiles below the diagonal and
+    tile row K has K left of it.  An odd count above 1 is one or more passes of two tiles and then the pass of a single
+    tile: columns 1, 3, .. 15 forward, rows 3, 5, .. 17 backward.  With every tile stored the history is the dense
+    solver's, so X is also vgx_dense_spd_solve_many's bit for bit; m = 33: a second workgroup with one column."""
+    rows, pairs = block_scenes()[1156]
+    m = sref.block_matrix(rows, pairs, seed=1156)
+    n = m["n"]
+    h_keys, l_tiles = sref.tile_pattern(rows, m["pairs"], list(range(rows)))
+    below = [len(v) - 1 for _, v in sorted(sref.columns_of(l_tiles).items())]
+    assert len(l_tiles) == 190 and below == list(range(18, -1, -1)) and sum(1 for c in below if c > 1 and c % 2) == 8
+    L = scov.factor(sref.to_tiles(m["A"], [t for t in l_tiles if t in h_keys]), n, l_tiles)
+    B = right_hand_sides(n, 33, 1156)
+    X = capi.block_spd_solve_many(ctx, rows, m["bi"], m["bj"], m["values"], B)
+    X0 = scov.solve_many(L, n, l_tiles, B)
+    Xd, _ = capi.dense_spd_solve_many(ctx, m["A"], B)
+    print(f"arrowhead: max |X - X0| {np.abs(X - X0).max():.3e}, max |X - dense X| {np.abs(X - Xd).max():.3e}")
+    assert same_bits(X, X0) and same_bits(X, Xd)
+    for c in (0, 16, 32):                                                # ... and a column IS the single solve of that column
+        x, _, _, _ = capi.block_spd_solve(ctx, rows, m["bi"], m["bj"], m["values"], B[:, c].copy(), want_factor=False)
+        assert same_bits(X[:, c], x), c
+
+
 def test_block_spd_solve_many_reports_what_is_not_positive_definite(capi, ctx):
     rows, pairs = block_scenes()[300]
     m = sref.block_matrix(rows, pairs, seed=300)

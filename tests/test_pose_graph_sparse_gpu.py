@@ -49,10 +49,13 @@ def _break_chain(pairs, tiles):
 
 def block_scenes():
     """n -> (block rows, pairs): one partial tile; the tile edge; an arrow (tiles (1, 0), (2, 0) stored, (2, 1) pure fill); a
-    band with a closure whose fill runs along tile row 4; 18 panels, the columns of tiles 7, 8 and 12 empty below the diagonal"""
+    band with a closure whose fill runs along tile row 4; 18 panels, the columns of tiles 7, 8 and 12 empty below the diagonal;
+    an arrowhead of 19 tile rows (the last 4 rows wide) whose fill stores all 190 tiles: 18 and 17 tiles below the diagonal in
+    columns 0 and 1, 17 and 18 left of it in the last two rows -- more than the 16 a pass of the substitutions takes"""
     return {4: (1, []), 64: (16, sref.chain_pairs(16)), 68: (17, sref.chain_pairs(17)), 132: (33, [(i, 0) for i in range(1, 33)]),
             300: (75, sref.chain_pairs(75, closures=[(74, 3)])),
-            1100: (275, _break_chain(sref.chain_pairs(275), (3, 7, 8, 12)) + [(270, 20)])}
+            1100: (275, _break_chain(sref.chain_pairs(275), (3, 7, 8, 12)) + [(270, 20)]),
+            1156: (289, [(i, 0) for i in range(1, 289)])}
 
 
 def scattered(index, tiles, n):
@@ -83,6 +86,10 @@ def test_block_spd_solve_equals_the_dense_solve_and_is_the_restatement_bit_for_b
         assert {(4, 1), (4, 2)} == set(l_tiles) - h_keys and (4, 0) in h_keys
     if n == 1100:
         assert nT == 18 and stats["n_launches"] < 3 * 17 + 1 - 4 and len(l_tiles) < nT * (nT + 1) // 2 // 3
+    if n == 1156:                                                        # every tile stored: the dense solver's history, so its bits
+        below = [len(rows_of) - 1 for _, rows_of in sorted(sref.columns_of(l_tiles).items())]
+        assert nT == 19 and len(l_tiles) == 190 and below == list(range(18, -1, -1)) and max(below) > 16
+        assert same_bits(L, Ld) and same_bits(x, xd)
 
 
 def test_block_spd_solve_refuses_what_it_cannot_take(capi, ctx):

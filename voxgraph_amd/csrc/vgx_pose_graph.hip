@@ -110,6 +110,34 @@ __global__ __launch_bounds__(256) void pg_chol_diag_kernel(double* __restrict__ 
   if (bad && tid == 0) *flag = 1;
 }
 
+// ---------------------------------------------------------------------------
+// The arithmetic the dense and the tile-sparse factorisation share, written once: both compile to the instruction
+// streams they had with these lines written out in each kernel.  The substitutions' shared steps (the triangle fill,
+// the one-wavefront triangle solve, the panel phase of the many-column solve) stay written out per kernel: as
+// helpers they cost time on the device (profiles/pose_graph_shared_time.txt).
+// ---------------------------------------------------------------------------
+// one row of the panel below a factored tile against that tile's packed triangle Lt: (c, j) at c (c + 1) / 2 + j
+__device__ __forceinline__ void chol_panel_row_solve(double* row, const double* Lt, int w) {
+  for (int j = 0; j < w; ++j) {
+    const double x = row[j] / Lt[j * (j + 1) / 2 + j];
+    row[j] = x;
+    for (int c = j + 1; c < w; ++c) row[c] = row[c] - x * Lt[c * (c + 1) / 2 + j];
+  }
+}
+// acc -= a b^T for one staged column, product by product: a = pa[0 .. 3], b = pb[0 .. 3] (in LDS, 16-byte aligned).
+// One rounded multiply and one rounded subtract at a time, never a sum of products.  The loop over the columns stays
+// with the caller: its order is the caller's (ascending, or descending in a backward pass), and so is its unrolling.
+__device__ __forceinline__ void rank_update_4x4(double (&acc)[4][4], const double* pa, const double* pb) {
+  const double2 a01 = *reinterpret_cast<const double2*>(pa), a23 = *reinterpret_cast<const double2*>(pa + 2);
+  const double2 b01 = *reinterpret_cast<const double2*>(pb), b23 = *reinterpret_cast<const double2*>(pb + 2);
+  const double av[4] = {a01.x, a01.y, a23.x, a23.y};
+  const double bv[4] = {b01.x, b01.y, b23.x, b23.y};
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = acc[a][b] - av[a] * bv[b];
+}
+
 // 2. the panel below it: 64 rows per workgroup, one row per lane, against the factored tile
 __global__ __launch_bounds__(64) void pg_chol_panel_kernel(double* __restrict__ A, int n, int k0, int w, const int* __restrict__ flag) {
   if (*flag) return;
@@ -122,14 +150,7 @@ __global__ __launch_bounds__(64) void pg_chol_panel_kernel(double* __restrict__ 
   for (int r = 0; r < kPanel; ++r)
     R[r * (kPanel + 1) + t] = (row0 + r < n && t < w) ? A[(size_t)(row0 + r) * n + k0 + t] : 0.0;
   __syncthreads();
-  if (row0 + t < n) {
-    double* row = R + t * (kPanel + 1);
-    for (int j = 0; j < w; ++j) {
-      const double x = row[j] / Lt[j * (j + 1) / 2 + j];
-      row[j] = x;
-      for (int c = j + 1; c < w; ++c) row[c] = row[c] - x * Lt[c * (c + 1) / 2 + j];
-    }
-  }
+  if (row0 + t < n) chol_panel_row_solve(R + t * (kPanel + 1), Lt, w);
   __syncthreads();
   for (int r = 0; r < kPanel; ++r)
     if (row0 + r < n && t < w) A[(size_t)(row0 + r) * n + k0 + t] = R[r * (kPanel + 1) + t];
@@ -172,18 +193,7 @@ __global__ __launch_bounds__(256) void pg_chol_trailing_kernel(double* __restric
     }
     __syncthreads();
     const int kn = min(kChunk, w - kc);
-    for (int k = 0; k < kn; ++k) {
-      const double2 a01 = *reinterpret_cast<const double2*>(&PI[k * kStride + ty * 4]);
-      const double2 a23 = *reinterpret_cast<const double2*>(&PI[k * kStride + ty * 4 + 2]);
-      const double2 b01 = *reinterpret_cast<const double2*>(&PJ[k * kStride + tx * 4]);
-      const double2 b23 = *reinterpret_cast<const double2*>(&PJ[k * kStride + tx * 4 + 2]);
-      const double av[4] = {a01.x, a01.y, a23.x, a23.y};
-      const double bv[4] = {b01.x, b01.y, b23.x, b23.y};
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = acc[a][b] - av[a] * bv[b];
-    }
+    for (int k = 0; k < kn; ++k) rank_update_4x4(acc, &PI[k * kStride + ty * 4], &PJ[k * kStride + tx * 4]);
   }
 #pragma unroll
   for (int a = 0; a < 4; ++a)
@@ -380,16 +390,7 @@ __global__ __launch_bounds__(256) void pg_solve_many_kernel(const double* __rest
         const int kn = min(kSolveK, w - kc);
         for (int kk = 0; kk < kn; ++kk) {
           const int k = kBackward ? kn - 1 - kk : kk;
-          const double2 a01 = *reinterpret_cast<const double2*>(&S[k * kSolveStride + ty * 4]);
-          const double2 a23 = *reinterpret_cast<const double2*>(&S[k * kSolveStride + ty * 4 + 2]);
-          const double2 b01 = *reinterpret_cast<const double2*>(&Y[(kc + k) * kSolveYStride + tx * 4]);
-          const double2 b23 = *reinterpret_cast<const double2*>(&Y[(kc + k) * kSolveYStride + tx * 4 + 2]);
-          const double av[4] = {a01.x, a01.y, a23.x, a23.y};
-          const double bv[4] = {b01.x, b01.y, b23.x, b23.y};
-#pragma unroll
-          for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) acc[a][b] = acc[a][b] - av[a] * bv[b];
+          rank_update_4x4(acc, &S[k * kSolveStride + ty * 4], &Y[(kc + k) * kSolveYStride + tx * 4]);
         }
       }
 #pragma unroll
@@ -528,14 +529,7 @@ __global__ __launch_bounds__(64) void pg_chol_panel_tiled_kernel(double* __restr
     if (t <= r) Lt[r * (r + 1) / 2 + t] = D[r * kPanel + t];
   for (int r = 0; r < kPanel; ++r) R[r * (kPanel + 1) + t] = r < rows ? T[r * kPanel + t] : 0.0;
   __syncthreads();
-  if (t < rows) {
-    double* row = R + t * (kPanel + 1);
-    for (int j = 0; j < kPanel; ++j) {
-      const double x = row[j] / Lt[j * (j + 1) / 2 + j];
-      row[j] = x;
-      for (int c = j + 1; c < kPanel; ++c) row[c] = row[c] - x * Lt[c * (c + 1) / 2 + j];
-    }
-  }
+  if (t < rows) chol_panel_row_solve(R + t * (kPanel + 1), Lt, kPanel);
   __syncthreads();
   for (int r = 0; r < rows; ++r) T[r * kPanel + t] = R[r * (kPanel + 1) + t];
 }
@@ -572,18 +566,8 @@ __global__ __launch_bounds__(256) void pg_chol_trailing_tiled_kernel(double* __r
       }
     }
     __syncthreads();
-    for (int k = 0; k < kChunk; ++k) {
-      const double2 a01 = *reinterpret_cast<const double2*>(&PI[k * kStride + ty * 4]);
-      const double2 a23 = *reinterpret_cast<const double2*>(&PI[k * kStride + ty * 4 + 2]);
-      const double2 b01 = *reinterpret_cast<const double2*>(&PJ[k * kStride + tx * 4]);
-      const double2 b23 = *reinterpret_cast<const double2*>(&PJ[k * kStride + tx * 4 + 2]);
-      const double av[4] = {a01.x, a01.y, a23.x, a23.y};
-      const double bv[4] = {b01.x, b01.y, b23.x, b23.y};
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = acc[a][b] - av[a] * bv[b];
-    }
+#pragma unroll  // (whole, as the compiler chose for these lines written out; through the call it would stop at four)
+    for (int k = 0; k < kChunk; ++k) rank_update_4x4(acc, &PI[k * kStride + ty * 4], &PJ[k * kStride + tx * 4]);
   }
 #pragma unroll
   for (int a = 0; a < 4; ++a)
@@ -1327,6 +1311,132 @@ struct Solve {
   }
 };
 
+// vgx_dense_spd_solve (m == 0: one right-hand side through the single-column kernels) and vgx_dense_spd_solve_many
+// (m > 0: b and x are [n][m]); the entry points have checked the arguments
+int dense_spd_solve(vgx_ctx ctx, const char* who_, int32_t n, const double* A, int32_t m, const double* b, double* x, double* L) {
+  const std::string who(who_);
+  const size_t N = (size_t)n, n_rhs = N * (size_t)std::max(1, m);
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  VGX_HIP(ctx, hipSetDevice(ctx->device));
+  DeviceArray<double> d_A, d_x;
+  DeviceArray<int> d_flag;
+  hipError_t e = d_A.alloc_n(N * N);
+  if (e == hipSuccess) e = d_x.alloc_n(n_rhs);
+  if (e == hipSuccess) e = d_flag.alloc_n(1);
+  if (e != hipSuccess) return alloc_error(ctx, e, (who + (m > 0 ? ": allocating the matrix and the right-hand sides" : ": allocating the matrix")).c_str());
+  VGX_HIP(ctx, hipMemcpyAsync(d_A.p, A, N * N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  VGX_HIP(ctx, hipMemcpyAsync(d_x.p, b, n_rhs * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  int rc = queue_cholesky(ctx, d_A.get(), n, d_flag.get());
+  if (rc == VGX_OK)
+    rc = m > 0 ? queue_solve_many(ctx, d_A.get(), n, d_x.get(), m, nullptr, d_flag.get()) : queue_substitutions(ctx, d_A.get(), n, d_x.get());
+  if (rc != VGX_OK) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+  }
+  int flag = 0;
+  VGX_HIP(ctx, hipMemcpyAsync(&flag, d_flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+  VGX_HIP(ctx, hipMemcpyAsync(x, d_x.p, n_rhs * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  if (L) VGX_HIP(ctx, hipMemcpyAsync(L, d_A.p, N * N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (L)
+    for (size_t i = 0; i < N; ++i)
+      for (size_t j = i + 1; j < N; ++j) L[i * N + j] = 0.0;
+  if (flag) return set_error(ctx, VGX_ERR_NOT_POSITIVE_DEFINITE, who + ": the matrix is not positive definite (a pivot is not positive or not finite)");
+  return VGX_OK;
+}
+
+// What vgx_pose_graph_covariance and vgx_pose_graph_covariance_sparse (`sparse`, with its max_solve_bytes and stats; the
+// dense call passes 0 and NULL) check before they plan their columns, in the one order both report in.  Takes pg->mu
+// into `lk`.  *go: the caller goes on; else it returns the result (VGX_OK where there is nothing to solve, the
+// covariances then written).  *with_reg: the registration batch takes part.  Leaves the index lists made for the call.
+int covariance_begin(vgx_pose_graph pg, const char* who_, bool sparse, const double* poses, int32_t exclude_registration_constraints,
+                     int32_t n_pairs, const int32_t* pairs, int64_t max_solve_bytes, double* covariance,
+                     vgx_pose_graph_covariance_stats* stats, std::unique_lock<std::mutex>& lk, bool* with_reg, bool* go) {
+  *go = false;
+  if (!pg) return VGX_ERR_INVALID;
+  vgx_ctx ctx = pg->ctx;
+  const std::string who(who_);
+  if (n_pairs < 0) return set_error(ctx, VGX_ERR_INVALID, who + ": n_pairs < 0");
+  if (max_solve_bytes < 0) return set_error(ctx, VGX_ERR_INVALID, who + ": max_solve_bytes < 0");
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (n_pairs == 0) return VGX_OK;
+  if (!poses || !pairs || !covariance) return set_error(ctx, VGX_ERR_INVALID, who + ": NULL poses, pairs or covariance");
+  if (n_pairs > (1 << 26)) return set_error(ctx, VGX_ERR_UNSUPPORTED, who + ": more than 2^26 pairs in one call");
+  lk = std::unique_lock<std::mutex>(pg->mu);
+  if (sparse && pg->solver != VGX_LINEAR_SOLVER_TILE_SPARSE)
+    return set_error(ctx, VGX_ERR_INVALID,
+                     who + ": the graph's solver is not VGX_LINEAR_SOLVER_TILE_SPARSE; vgx_pose_graph_covariance takes the dense factor");
+  for (size_t i = 0; i < 2 * (size_t)n_pairs; ++i)
+    if (pairs[i] < 0 || pairs[i] >= pg->n_nodes)
+      return set_error(ctx, VGX_ERR_INVALID, who + ": pair " + std::to_string(i / 2) + " names a node out of range");
+  for (size_t i = 0; i < 4 * (size_t)pg->n_nodes; ++i)
+    if (!std::isfinite(poses[i])) return set_error(ctx, VGX_ERR_INVALID, who + ": a pose is not finite");
+  if (pg->batch) {
+    std::lock_guard<std::mutex> lt(lifetime_mu());
+    if (pg->batch->destroy_requested) return set_error(ctx, VGX_ERR_INVALID, who + ": the registration batch was destroyed");
+  }
+  *with_reg = pg->batch && pg->batch->n > 0 && !exclude_registration_constraints;
+  if (!*with_reg && pg->edges.empty())
+    return set_error(ctx, VGX_ERR_INVALID, who + ": a graph without constraints (no registration batch in use, no edges)");
+  if (!sparse && (int)pg->free_nodes.size() > kMaxFreeNodes)
+    return set_error(ctx, VGX_ERR_UNSUPPORTED, who + ": " + std::to_string(pg->free_nodes.size()) +
+                                                   " free nodes; the covariances take the dense factor, " + std::to_string(kMaxFreeNodes) +
+                                                   " free nodes at the most");
+  if (pg->nf == 0) {  // every node is constant
+    std::fill(covariance, covariance + 16 * (size_t)n_pairs, 0.0);
+    return VGX_OK;
+  }
+  if (!pg->lists_made || pg->lists_with_reg != *with_reg || pg->lists_sparse != sparse) {  // (the dense call: the dense lists, whatever the solver)
+    const int rc = make_lists(pg, *with_reg, sparse);
+    if (rc != VGX_OK) return rc;
+  }
+  *go = true;
+  return VGX_OK;
+}
+
+// The columns a covariance call solves: the distinct second nodes of the pairs between free nodes, four columns each,
+// ascending by place(node) -- a free node's position (among the free nodes, or under the order in use), -1 for a
+// constant node.  col_of[position] = its first column or -1; m columns; index = [unit_row m][chunk_rows 2 n_chunks], the
+// lists pg_unit_columns_kernel and the solve on many right-hand sides take: the row of each column's 1, and per chunk of
+// kSolveCols columns {the first row that is not zero, the lowest row any pair wants of them}.  false: out of host memory.
+struct CovarianceColumns {
+  std::vector<int32_t> col_of, index;
+  int m = 0, n_chunks = 0, n_free_pairs = 0;
+};
+template <class Place>
+bool plan_covariance_columns(int nfn, int32_t n_pairs, const int32_t* pairs, Place place, CovarianceColumns* out) try {
+  std::vector<int32_t> lowest((size_t)nfn, INT32_MAX);  // per position: the lowest row any of its pairs wants
+  out->col_of.assign((size_t)nfn, -1);
+  out->m = out->n_free_pairs = 0;
+  for (int p = 0; p < n_pairs; ++p) {
+    const int32_t a = place(pairs[2 * p]), b = place(pairs[2 * p + 1]);
+    if (a >= 0 && b >= 0) {
+      lowest[(size_t)b] = std::min(lowest[(size_t)b], 4 * a);
+      ++out->n_free_pairs;
+    }
+  }
+  for (int b = 0; b < nfn; ++b)
+    if (lowest[(size_t)b] != INT32_MAX) {
+      out->col_of[(size_t)b] = out->m;
+      out->m += 4;
+    }
+  const int m = out->m, n_chunks = out->n_chunks = (m + kSolveCols - 1) / kSolveCols;
+  out->index.assign((size_t)m + 2 * (size_t)n_chunks, INT32_MAX);
+  int32_t* unit_row = out->index.data();
+  int32_t* chunk_rows = unit_row + m;
+  for (int b = 0; b < nfn; ++b) {
+    const int c = out->col_of[(size_t)b];
+    if (c < 0) continue;
+    for (int k = 0; k < 4; ++k) unit_row[c + k] = 4 * b + k;
+    int32_t& low = chunk_rows[2 * (c / kSolveCols) + 1];  // (4 | kSolveCols: a node's columns share a chunk)
+    low = std::min(low, lowest[(size_t)b]);
+  }
+  for (int c = 0; c < n_chunks; ++c) chunk_rows[2 * c] = unit_row[c * kSolveCols];  // ascending: the chunk's first 1
+  return true;
+} catch (const std::bad_alloc&) {
+  return false;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1690,86 +1800,25 @@ int vgx_dense_spd_solve(vgx_ctx ctx, int32_t n, const double* A, const double* b
   if (n < 1 || n > kMaxDenseN)
     return set_error(ctx, n < 1 ? VGX_ERR_INVALID : VGX_ERR_UNSUPPORTED, "vgx_dense_spd_solve: n must be in [1, " + std::to_string(kMaxDenseN) + "]");
   if (!A || !b || !x) return set_error(ctx, VGX_ERR_INVALID, "vgx_dense_spd_solve: NULL A, b or x");
-  const size_t N = (size_t)n;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  VGX_HIP(ctx, hipSetDevice(ctx->device));
-  DeviceArray<double> d_A, d_x;
-  DeviceArray<int> d_flag;
-  hipError_t e = d_A.alloc_n(N * N);
-  if (e == hipSuccess) e = d_x.alloc_n(N);
-  if (e == hipSuccess) e = d_flag.alloc_n(1);
-  if (e != hipSuccess) return alloc_error(ctx, e, "vgx_dense_spd_solve: allocating the matrix");
-  VGX_HIP(ctx, hipMemcpyAsync(d_A.p, A, N * N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  VGX_HIP(ctx, hipMemcpyAsync(d_x.p, b, N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  int rc = queue_cholesky(ctx, d_A.get(), n, d_flag.get());
-  if (rc == VGX_OK) rc = queue_substitutions(ctx, d_A.get(), n, d_x.get());
-  if (rc != VGX_OK) {
-    (void)hipStreamSynchronize(ctx->stream);
-    return rc;
-  }
-  int flag = 0;
-  VGX_HIP(ctx, hipMemcpyAsync(&flag, d_flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  VGX_HIP(ctx, hipMemcpyAsync(x, d_x.p, N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (L) VGX_HIP(ctx, hipMemcpyAsync(L, d_A.p, N * N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (L)
-    for (size_t i = 0; i < N; ++i)
-      for (size_t j = i + 1; j < N; ++j) L[i * N + j] = 0.0;
-  if (flag) return set_error(ctx, VGX_ERR_NOT_POSITIVE_DEFINITE, "vgx_dense_spd_solve: the matrix is not positive definite (a pivot is not positive or not finite)");
-  return VGX_OK;
+  return dense_spd_solve(ctx, "vgx_dense_spd_solve", n, A, 0, b, x, L);
 }
 
 int vgx_pose_graph_covariance(vgx_pose_graph pg, const double* poses, int32_t exclude_registration_constraints, int32_t n_pairs,
                               const int32_t* pairs, double* covariance) {
-  if (!pg) return VGX_ERR_INVALID;
+  std::unique_lock<std::mutex> lk;
+  bool with_reg = false, go = false;
+  int rc = covariance_begin(pg, "vgx_pose_graph_covariance", false, poses, exclude_registration_constraints, n_pairs, pairs, 0, covariance,
+                            nullptr, lk, &with_reg, &go);
+  if (!go) return rc;
   vgx_ctx ctx = pg->ctx;
-  if (n_pairs < 0) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance: n_pairs < 0");
-  if (n_pairs == 0) return VGX_OK;
-  if (!poses || !pairs || !covariance) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance: NULL poses, pairs or covariance");
-  if (n_pairs > (1 << 26)) return set_error(ctx, VGX_ERR_UNSUPPORTED, "vgx_pose_graph_covariance: more than 2^26 pairs in one call");
-  std::lock_guard<std::mutex> lk(pg->mu);
-  for (size_t i = 0; i < 2 * (size_t)n_pairs; ++i)
-    if (pairs[i] < 0 || pairs[i] >= pg->n_nodes)
-      return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance: pair " + std::to_string(i / 2) + " names a node out of range");
-  for (size_t i = 0; i < 4 * (size_t)pg->n_nodes; ++i)
-    if (!std::isfinite(poses[i])) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance: a pose is not finite");
-  if (pg->batch) {
-    std::lock_guard<std::mutex> lt(lifetime_mu());
-    if (pg->batch->destroy_requested)
-      return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance: the registration batch was destroyed");
-  }
-  const bool with_reg = pg->batch && pg->batch->n > 0 && !exclude_registration_constraints;
-  if (!with_reg && pg->edges.empty())
-    return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance: a graph without constraints (no registration batch in use, no edges)");
-  if ((int)pg->free_nodes.size() > kMaxFreeNodes)
-    return set_error(ctx, VGX_ERR_UNSUPPORTED, "vgx_pose_graph_covariance: " + std::to_string(pg->free_nodes.size()) +
-                                                   " free nodes; the covariances take the dense factor, " + std::to_string(kMaxFreeNodes) +
-                                                   " free nodes at the most");
-  const size_t n_out = 16 * (size_t)n_pairs;
-  if (pg->nf == 0) {  // every node is constant
-    std::fill(covariance, covariance + n_out, 0.0);
-    return VGX_OK;
-  }
-  if (!pg->lists_made || pg->lists_with_reg != with_reg || pg->lists_sparse) {  // (the dense lists, whatever the solver)
-    const int rc = make_lists(pg, with_reg, false);
-    if (rc != VGX_OK) return rc;
-  }
-  // the columns to solve: the distinct second nodes (of pairs between free nodes) in ascending free position, and per
-  // node the lowest row any of its pairs wants
-  const int nf = pg->nf, nfn = nf / 4;
-  std::vector<int32_t> lowest((size_t)nfn, INT32_MAX), col_of((size_t)nfn, -1);
-  for (int p = 0; p < n_pairs; ++p) {
-    const int32_t a = pg->pos[(size_t)pairs[2 * p]], b = pg->pos[(size_t)pairs[2 * p + 1]];
-    if (a >= 0 && b >= 0) lowest[(size_t)b] = std::min(lowest[(size_t)b], 4 * a);
-  }
-  int m = 0;
-  for (int b = 0; b < nfn; ++b)
-    if (lowest[(size_t)b] != INT32_MAX) {
-      col_of[(size_t)b] = m;
-      m += 4;
-    }
-  const int n_chunks = (m + kSolveCols - 1) / kSolveCols;
-  const size_t n_index = (size_t)m + 2 * (size_t)n_chunks + 2 * (size_t)n_pairs;
+  // the columns to solve, in ascending free position
+  const int nf = pg->nf;
+  CovarianceColumns cols;
+  if (!plan_covariance_columns(nf / 4, n_pairs, pairs, [&](int32_t node) { return pg->pos[(size_t)node]; }, &cols))
+    return set_error(ctx, VGX_ERR_NOMEM, "vgx_pose_graph_covariance: out of host memory for the column lists");
+  const std::vector<int32_t>& col_of = cols.col_of;
+  const int m = cols.m, n_chunks = cols.n_chunks;
+  const size_t n_out = 16 * (size_t)n_pairs, n_index = cols.index.size() + 2 * (size_t)n_pairs;
   {
     std::lock_guard<std::mutex> lc(ctx->mu);
     VGX_HIP(ctx, hipSetDevice(ctx->device));
@@ -1781,18 +1830,9 @@ int vgx_pose_graph_covariance(vgx_pose_graph pg, const double* poses, int32_t ex
     if (e != hipSuccess) return alloc_error(ctx, e, "vgx_pose_graph_covariance: allocating the pinned staging");
   }
   double* h_out = pg->h_cov.as<double>();
-  int32_t* h_unit_row = reinterpret_cast<int32_t*>(h_out + n_out + 1);
-  int32_t* h_chunk_rows = h_unit_row + m;
-  int32_t* h_block = h_chunk_rows + 2 * (size_t)n_chunks;
-  for (int c = 0; c < n_chunks; ++c) h_chunk_rows[2 * c + 1] = INT32_MAX;
-  for (int b = 0; b < nfn; ++b) {
-    const int c = col_of[(size_t)b];
-    if (c < 0) continue;
-    for (int k = 0; k < 4; ++k) h_unit_row[c + k] = 4 * b + k;
-    int32_t& low = h_chunk_rows[2 * (c / kSolveCols) + 1];  // (4 | kSolveCols: a node's columns share a chunk)
-    low = std::min(low, lowest[(size_t)b]);
-  }
-  for (int c = 0; c < n_chunks; ++c) h_chunk_rows[2 * c] = h_unit_row[c * kSolveCols];  // ascending: the chunk's first 1
+  int32_t* h_unit_row = reinterpret_cast<int32_t*>(h_out + n_out + 1);  // [unit_row m][chunk_rows 2 n_chunks][block 2 n_pairs]
+  std::copy(cols.index.begin(), cols.index.end(), h_unit_row);
+  int32_t* h_block = h_unit_row + cols.index.size();
   for (int p = 0; p < n_pairs; ++p) {
     const int32_t a = pg->pos[(size_t)pairs[2 * p]], b = pg->pos[(size_t)pairs[2 * p + 1]];
     h_block[2 * p] = a >= 0 ? 4 * a : -1;
@@ -1801,7 +1841,7 @@ int vgx_pose_graph_covariance(vgx_pose_graph pg, const double* poses, int32_t ex
   }
   Solve sv{pg, with_reg};
   double cost = 0.0;
-  int rc = sv.evaluate_full(poses, &cost);
+  rc = sv.evaluate_full(poses, &cost);
   if (rc < 0) return rc;
   {
     std::lock_guard<std::mutex> lc(ctx->mu);
@@ -1836,76 +1876,31 @@ int vgx_pose_graph_covariance(vgx_pose_graph pg, const double* poses, int32_t ex
 int vgx_pose_graph_covariance_sparse(vgx_pose_graph pg, const double* poses, int32_t exclude_registration_constraints, int32_t n_pairs,
                                      const int32_t* pairs, int64_t max_solve_bytes, double* covariance,
                                      vgx_pose_graph_covariance_stats* stats) {
-  if (!pg) return VGX_ERR_INVALID;
+  std::unique_lock<std::mutex> lk;
+  bool with_reg = false, go = false;
+  int rc = covariance_begin(pg, "vgx_pose_graph_covariance_sparse", true, poses, exclude_registration_constraints, n_pairs, pairs,
+                            max_solve_bytes, covariance, stats, lk, &with_reg, &go);
+  if (!go) return rc;
   vgx_ctx ctx = pg->ctx;
-  if (n_pairs < 0) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance_sparse: n_pairs < 0");
-  if (max_solve_bytes < 0) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance_sparse: max_solve_bytes < 0");
-  if (stats) std::memset(stats, 0, sizeof(*stats));
-  if (n_pairs == 0) return VGX_OK;
-  if (!poses || !pairs || !covariance)
-    return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance_sparse: NULL poses, pairs or covariance");
-  if (n_pairs > (1 << 26)) return set_error(ctx, VGX_ERR_UNSUPPORTED, "vgx_pose_graph_covariance_sparse: more than 2^26 pairs in one call");
-  std::lock_guard<std::mutex> lk(pg->mu);
-  if (pg->solver != VGX_LINEAR_SOLVER_TILE_SPARSE)
-    return set_error(ctx, VGX_ERR_INVALID,
-                     "vgx_pose_graph_covariance_sparse: the graph's solver is not VGX_LINEAR_SOLVER_TILE_SPARSE; "
-                     "vgx_pose_graph_covariance takes the dense factor");
-  for (size_t i = 0; i < 2 * (size_t)n_pairs; ++i)
-    if (pairs[i] < 0 || pairs[i] >= pg->n_nodes)
-      return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance_sparse: pair " + std::to_string(i / 2) + " names a node out of range");
-  for (size_t i = 0; i < 4 * (size_t)pg->n_nodes; ++i)
-    if (!std::isfinite(poses[i])) return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance_sparse: a pose is not finite");
-  if (pg->batch) {
-    std::lock_guard<std::mutex> lt(lifetime_mu());
-    if (pg->batch->destroy_requested)
-      return set_error(ctx, VGX_ERR_INVALID, "vgx_pose_graph_covariance_sparse: the registration batch was destroyed");
-  }
-  const bool with_reg = pg->batch && pg->batch->n > 0 && !exclude_registration_constraints;
-  if (!with_reg && pg->edges.empty())
-    return set_error(ctx, VGX_ERR_INVALID,
-                     "vgx_pose_graph_covariance_sparse: a graph without constraints (no registration batch in use, no edges)");
-  const size_t n_out = 16 * (size_t)n_pairs;
-  if (pg->nf == 0) {  // every node is constant
-    std::fill(covariance, covariance + n_out, 0.0);
-    return VGX_OK;
-  }
-  if (!pg->lists_made || pg->lists_with_reg != with_reg || !pg->lists_sparse) {
-    const int rc = make_lists(pg, with_reg, true);
-    if (rc != VGX_OK) return rc;
-  }
-  // the columns to solve: the distinct second nodes (of pairs between free nodes) in ascending POSITION under the
-  // order in use, and per position the lowest row any of its pairs wants
-  const int nf = pg->nf, nfn = nf / 4;
+  // the columns to solve, in ascending POSITION under the order in use
+  const int nf = pg->nf;
   const std::vector<int32_t>& position = pg->S.position;
   auto place = [&](int32_t node) { return pg->pos[(size_t)node] < 0 ? -1 : position[(size_t)pg->pos[(size_t)node]]; };
-  std::vector<int32_t> lowest, col_of, slab_first;
-  int m = 0, n_free_pairs = 0;
-  try {
-    lowest.assign((size_t)nfn, INT32_MAX);
-    col_of.assign((size_t)nfn, -1);
-  } catch (const std::bad_alloc&) {
+  CovarianceColumns cols;
+  if (!plan_covariance_columns(nf / 4, n_pairs, pairs, place, &cols))
     return set_error(ctx, VGX_ERR_NOMEM, "vgx_pose_graph_covariance_sparse: out of host memory for the column lists");
-  }
-  for (int p = 0; p < n_pairs; ++p) {
-    const int32_t a = place(pairs[2 * p]), b = place(pairs[2 * p + 1]);
-    if (a >= 0 && b >= 0) {
-      lowest[(size_t)b] = std::min(lowest[(size_t)b], 4 * a);
-      ++n_free_pairs;
-    }
-  }
-  for (int b = 0; b < nfn; ++b)
-    if (lowest[(size_t)b] != INT32_MAX) {
-      col_of[(size_t)b] = m;
-      m += 4;
-    }
+  const std::vector<int32_t>& col_of = cols.col_of;
+  const int m = cols.m;
+  const size_t n_out = 16 * (size_t)n_pairs;
+  std::vector<int32_t> slab_first;
   // the slabs: S columns at a time, the largest multiple of kSolveCols with 8 nf S <= the budget, kSolveCols at the least
   const int64_t budget = max_solve_bytes == 0 ? (int64_t)1 << 30 : max_solve_bytes;
   const int64_t m_round = ((int64_t)m + kSolveCols - 1) / kSolveCols * kSolveCols;
   const int64_t slab = std::max<int64_t>(kSolveCols, std::min<int64_t>(std::max<int64_t>(m_round, kSolveCols), budget / (8 * (int64_t)nf) / kSolveCols * kSolveCols));
-  const int n_slabs = (int)((m + slab - 1) / slab), n_chunks = (m + kSolveCols - 1) / kSolveCols;
+  const int n_slabs = (int)((m + slab - 1) / slab), n_chunks = cols.n_chunks;
   const size_t x_doubles = (size_t)nf * (size_t)std::min<int64_t>(slab, std::max(m, 1));
   const size_t x_limit = std::max<size_t>((size_t)budget, (size_t)nf * kSolveCols * sizeof(double));
-  const size_t n_index = (size_t)m + 2 * (size_t)n_chunks + 3 * (size_t)n_free_pairs + 1;
+  const size_t n_index = cols.index.size() + 3 * (size_t)cols.n_free_pairs + 1;
   {
     std::lock_guard<std::mutex> lc(ctx->mu);
     VGX_HIP(ctx, hipSetDevice(ctx->device));
@@ -1921,18 +1916,9 @@ int vgx_pose_graph_covariance_sparse(vgx_pose_graph pg, const double* poses, int
     if (e != hipSuccess) return alloc_error(ctx, e, "vgx_pose_graph_covariance_sparse: allocating the pinned staging");
   }
   double* h_out = pg->h_cov.as<double>();
-  int32_t* h_unit_row = reinterpret_cast<int32_t*>(h_out + n_out + 1);
-  int32_t* h_chunk_rows = h_unit_row + m;
-  int32_t* h_list = h_chunk_rows + 2 * (size_t)n_chunks;  // per slab its pairs: {pair, first row, first column in the slab}
-  for (int c = 0; c < n_chunks; ++c) h_chunk_rows[2 * c + 1] = INT32_MAX;
-  for (int b = 0; b < nfn; ++b) {
-    const int c = col_of[(size_t)b];
-    if (c < 0) continue;
-    for (int k = 0; k < 4; ++k) h_unit_row[c + k] = 4 * b + k;
-    int32_t& low = h_chunk_rows[2 * (c / kSolveCols) + 1];  // (4 | kSolveCols: a node's columns share a chunk)
-    low = std::min(low, lowest[(size_t)b]);
-  }
-  for (int c = 0; c < n_chunks; ++c) h_chunk_rows[2 * c] = h_unit_row[c * kSolveCols];  // ascending: the chunk's first 1
+  int32_t* h_unit_row = reinterpret_cast<int32_t*>(h_out + n_out + 1);  // [unit_row m][chunk_rows 2 n_chunks][the slabs' pairs]
+  std::copy(cols.index.begin(), cols.index.end(), h_unit_row);
+  int32_t* h_list = h_unit_row + cols.index.size();  // per slab its pairs: {pair, first row, first column in the slab}
   try {
     slab_first.assign((size_t)n_slabs + 1, 0);
   } catch (const std::bad_alloc&) {
@@ -1958,7 +1944,7 @@ int vgx_pose_graph_covariance_sparse(vgx_pose_graph pg, const double* poses, int
   }
   Solve sv{pg, with_reg};
   double cost = 0.0;
-  int rc = sv.evaluate_full(poses, &cost);
+  rc = sv.evaluate_full(poses, &cost);
   if (rc < 0) return rc;
   {
     std::lock_guard<std::mutex> lc(ctx->mu);
@@ -2010,33 +1996,7 @@ int vgx_dense_spd_solve_many(vgx_ctx ctx, int32_t n, const double* A, int32_t m,
     return set_error(ctx, (n < 1 || m < 1) ? VGX_ERR_INVALID : VGX_ERR_UNSUPPORTED,
                      "vgx_dense_spd_solve_many: n and m must be in [1, " + std::to_string(kMaxDenseN) + "]");
   if (!A || !B || !X) return set_error(ctx, VGX_ERR_INVALID, "vgx_dense_spd_solve_many: NULL A, B or X");
-  const size_t N = (size_t)n, M = (size_t)m;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  VGX_HIP(ctx, hipSetDevice(ctx->device));
-  DeviceArray<double> d_A, d_X;
-  DeviceArray<int> d_flag;
-  hipError_t e = d_A.alloc_n(N * N);
-  if (e == hipSuccess) e = d_X.alloc_n(N * M);
-  if (e == hipSuccess) e = d_flag.alloc_n(1);
-  if (e != hipSuccess) return alloc_error(ctx, e, "vgx_dense_spd_solve_many: allocating the matrix and the right-hand sides");
-  VGX_HIP(ctx, hipMemcpyAsync(d_A.p, A, N * N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  VGX_HIP(ctx, hipMemcpyAsync(d_X.p, B, N * M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  int rc = queue_cholesky(ctx, d_A.get(), n, d_flag.get());
-  if (rc == VGX_OK) rc = queue_solve_many(ctx, d_A.get(), n, d_X.get(), m, nullptr, d_flag.get());
-  if (rc != VGX_OK) {
-    (void)hipStreamSynchronize(ctx->stream);
-    return rc;
-  }
-  int flag = 0;
-  VGX_HIP(ctx, hipMemcpyAsync(&flag, d_flag.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  VGX_HIP(ctx, hipMemcpyAsync(X, d_X.p, N * M * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  if (L) VGX_HIP(ctx, hipMemcpyAsync(L, d_A.p, N * N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  VGX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (L)
-    for (size_t i = 0; i < N; ++i)
-      for (size_t j = i + 1; j < N; ++j) L[i * N + j] = 0.0;
-  if (flag) return set_error(ctx, VGX_ERR_NOT_POSITIVE_DEFINITE, "vgx_dense_spd_solve_many: the matrix is not positive definite (a pivot is not positive or not finite)");
-  return VGX_OK;
+  return dense_spd_solve(ctx, "vgx_dense_spd_solve_many", n, A, m, B, X, L);
 }
 
 int vgx_block_spd_solve(vgx_ctx ctx, int32_t n_block_rows, int32_t nnz, const int32_t* bi, const int32_t* bj, const double* values,
