@@ -395,7 +395,10 @@ VGX_API int vgx_reg_batch_row_offsets(vgx_reg_batch batch, int64_t* row_offset);
  * receives VGX_OK / VGX_EVALUATE_FALSE per constraint.  Asynchronous.
  * Alignment: 16 bytes is required (float4 stores); more buys nothing (measured
  * with the placement held fixed: profiles/r05_points_placement.txt).  WHERE the
- * arrays lie physically does matter: vgx_reg_batch_choose_outputs below. */
+ * arrays lie physically does matter: vgx_reg_batch_choose_outputs below.
+ * Each wavefront stores whole 64-row spans counted from the arrays' bases, whatever a constraint's row_offset is (a batch
+ * launched in the grouped order keeps its point loads aligned instead); that saves the split sectors only on bases aligned
+ * to 256 bytes, as hipMalloc's and torch's are (profiles/points_row_alignment.txt). */
 VGX_API int vgx_reg_batch_evaluate_points(vgx_reg_batch batch,
                                           const double* poses, int32_t n_nodes,
                                           void* d_residuals, void* d_jac_ref,

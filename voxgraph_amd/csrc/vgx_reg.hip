@@ -495,7 +495,19 @@ __global__ __launch_bounds__(256) void reg_gather_points_kernel(const Constraint
   }
 }
 
-// The PPT points (and weights) of one thread of a materialising tile: residual j * kBlockThreads + threadIdx.x of the
+// Which residual of its tile a thread takes in slot j.  With shift 0 it is j * kBlockThreads + threadIdx.x.  The rows
+// pass rotates the assignment by shift = (first row of the tile) & 63, so that the 64 rows one wavefront stores with one
+// instruction begin on a multiple of 64 rows of the output arrays -- whole 256-byte (residuals) and 1 KiB (Jacobian)
+// spans, where an unrotated wavefront shares a partly written sector with its neighbour at both ends.  The first
+// span of a tile is then `shift` rows short: those lanes wrap to the last `shift` residuals of a whole tile.  Every
+// residual of the tile is still taken by exactly one (thread, slot); a slot is active iff its residual is < the count.
+template <int PPT>
+__device__ __forceinline__ int tile_local(int j, int shift) {
+  static_assert(((PPT * kBlockThreads) & (PPT * kBlockThreads - 1)) == 0, "the rotation wraps with a mask");
+  return (j * kBlockThreads + (int)threadIdx.x - shift) & (PPT * kBlockThreads - 1);
+}
+
+// The PPT points (and weights) of one thread of a materialising tile: residual tile_local(j, shift) of the
 // `count` that start at `start`; lanes past the end load residual `start` and drop it later.  A sampling constraint
 // (RCF:113-122) uses the batch's precomputed draw, or (one-constraint drop-in launch) draws here, with weight 1.
 // Which of the three sources it is, is decided ONCE, around whole loops: with the test inside the per-point loop the
@@ -503,12 +515,12 @@ __global__ __launch_bounds__(256) void reg_gather_points_kernel(const Constraint
 // point j had arrived -- PPT dependent round trips where one is needed (profiles/points_load_chain.txt).  As written
 // every load of a path is issued before the first wait.
 template <int PPT>
-__device__ __forceinline__ void load_tile_points(const ConstraintDev& C, int64_t start, int count, f32x4 pt[PPT],
-                                                 float w[PPT]) {
+__device__ __forceinline__ void load_tile_points(const ConstraintDev& C, int64_t start, int count, int shift,
+                                                 f32x4 pt[PPT], float w[PPT]) {
   int64_t i[PPT];
 #pragma unroll
   for (int j = 0; j < PPT; ++j) {
-    const int local = j * kBlockThreads + (int)threadIdx.x;
+    const int local = tile_local<PPT>(j, shift);
     i[j] = start + (local < count ? local : 0);
   }
   if (C.sample_raw == nullptr) {
@@ -567,7 +579,7 @@ static inline size_t tile_dead_bytes(size_t n_tiles) { return ((n_tiles + 63) / 
 
 template <int VPS, int LAYOUT, typename OUT, int PPT>
 __device__ __forceinline__ void reg_eval_points_body(
-    const ConstraintDev& C, const PosePack& P, const Tile& tile, int dead_hint, OUT* __restrict__ residuals,
+    const ConstraintDev& C, const PosePack& P, const Tile& tile, int dead_hint, int shift, OUT* __restrict__ residuals,
     typename Out4<OUT>::type* __restrict__ jac_ref, typename Out4<OUT>::type* __restrict__ jac_read) {
   const GridDev g = C.grid;
   const bool want_jac =(jac_ref != nullptr) | (jac_read != nullptr);
@@ -590,7 +602,7 @@ __device__ __forceinline__ void reg_eval_points_body(
     if (!any_live) {
 #pragma unroll
       for (int j = 0; j < PPT; ++j) {
-        int local = j * kBlockThreads + (int)threadIdx.x;
+        int local = tile_local<PPT>(j, shift);
         if (local >= tile.count) continue;
         int64_t row = C.row0 + tile.start + local;
         store_out(&residuals[row], (OUT)0);  // r = w * 0, Jacobians zero (RCF:165-170)
@@ -606,7 +618,7 @@ __device__ __forceinline__ void reg_eval_points_body(
   const float* cell[PPT];
   float Dx[PPT], Dy[PPT], Dz[PPT];
   float d[PPT][8];
-  load_tile_points<PPT>(C, tile.start, tile.count, pt, w);
+  load_tile_points<PPT>(C, tile.start, tile.count, shift, pt, w);
   // stage 1: exact base voxel of every point (registers only)
   Located loc[PPT];
   bool have[PPT];
@@ -638,7 +650,7 @@ __device__ __forceinline__ void reg_eval_points_body(
   }
 #pragma unroll
   for (int j = 0; j < PPT; ++j) {
-    int local = j * kBlockThreads + (int)threadIdx.x;
+    int local = tile_local<PPT>(j, shift);
     if (local >= tile.count) continue;
     PointEval e = eval_point(d[j], have[j], Dx[j], Dy[j], Dz[j], g.voxel_size_inv, P,
                              pt[j].x, pt[j].y, pt[j].w, w[j], C.no_corr_cost, want_jac);
@@ -660,7 +672,7 @@ __global__ __launch_bounds__(kBlockThreads) void reg_eval_points_kernel(
     const ConstraintDev* __restrict__ cons, const PosePack* __restrict__ packs,
     const Tile* __restrict__ tiles, const uint32_t* __restrict__ tile_dead, int n_tiles,
     OUT* __restrict__ residuals, typename Out4<OUT>::type* __restrict__ jac_ref,
-    typename Out4<OUT>::type* __restrict__ jac_read, int blocked) {
+    typename Out4<OUT>::type* __restrict__ jac_read, int blocked, int shift_mask) {
   const int t = blockIdx.x;
   if (t >= n_tiles) return;
   const Tile tile = tiles[t];
@@ -677,10 +689,13 @@ __global__ __launch_bounds__(kBlockThreads) void reg_eval_points_kernel(
     OUT* r_t = reinterpret_cast<OUT*>(blk) - first;
     O4* jr_t = reinterpret_cast<O4*>(blk + (long long)(PPT * kBlockThreads) * (long long)sizeof(OUT)) - first;
     O4* je_t = reinterpret_cast<O4*>(blk + (long long)(PPT * kBlockThreads) * (long long)(sizeof(OUT) + sizeof(O4))) - first;
-    reg_eval_points_body<VPS, LAYOUT, OUT, PPT>(C, packs[tile.constraint], tile, dead, r_t, jr_t, je_t);
+    reg_eval_points_body<VPS, LAYOUT, OUT, PPT>(C, packs[tile.constraint], tile, dead, /*shift=*/0, r_t, jr_t, je_t);
     return;
   }
-  reg_eval_points_body<VPS, LAYOUT, OUT, PPT>(C, packs[tile.constraint], tile, dead, residuals, jac_ref, jac_read);
+  // a constraint's first row is the sum of the counts before it: anything modulo 64 (tile.start is a multiple of the tile).
+  // shift_mask is 63, or 0 where the launch keeps its point loads on their lines instead (launch_points)
+  const int shift = (int)((C.row0 + tile.start) & shift_mask);
+  reg_eval_points_body<VPS, LAYOUT, OUT, PPT>(C, packs[tile.constraint], tile, dead, shift, residuals, jac_ref, jac_read);
 }
 
 // drop-in form (one constraint per Evaluate): descriptor and pose pack travel as kernel
@@ -696,7 +711,7 @@ __global__ __launch_bounds__(kBlockThreads) void reg_eval_points_single_kernel(
   tile.start = (int64_t)t * (kBlockThreads * PPT);
   int64_t left = C.n - tile.start;
   tile.count = (int32_t)(left < kBlockThreads * PPT ? left : kBlockThreads * PPT);
-  reg_eval_points_body<VPS, LAYOUT, OUT, PPT>(C, P, tile, /*dead_hint=*/-1, residuals, jac_ref, jac_read);
+  reg_eval_points_body<VPS, LAYOUT, OUT, PPT>(C, P, tile, /*dead_hint=*/-1, /*shift=*/0, residuals, jac_ref, jac_read);
 }
 
 // ---------------------------------------------------------------------------
@@ -733,7 +748,7 @@ __global__ __launch_bounds__(kBlockThreads) void reg_visuals_single_kernel(Const
   float w[PPT];
   const float* cell[PPT];
   float d[PPT][8];
-  load_tile_points<PPT>(C, start, count, pt, w);
+  load_tile_points<PPT>(C, start, count, /*shift=*/0, pt, w);
   Located loc[PPT];
   bool have[PPT];
   const bool grid_empty = g.bricks == nullptr;  // reading submap without blocks
@@ -1643,15 +1658,21 @@ __global__ void reg_scatter_normal_kernel(const double* __restrict__ normal, int
 template <typename OUT>
 static void launch_points(vgx_ctx ctx, int vps, int layout, const ConstraintDev* d_desc, const PosePack* d_pack,
                           const Tile* d_tiles, unsigned long long* d_tile_dead, int n_tiles, void* res, void* jr,
-                          void* je, bool blocked = false) {
+                          void* je, bool blocked, bool grouped) {
   if (n_tiles <= 0) return;
+  // Aligned row stores (tile_local) put the point loads `shift` rows off their lines: a wavefront's 64 points and weights
+  // touch 9 + 3 lines where they touched 8 + 2.  A launch that is bound by its row writes gains (config 3: -2.5 %, the
+  // full-overlap workload in plain order -3.9 %); a launch in the grouped order, chosen where the constraints of a reference
+  // submap find its points in one XCD's L2 and which is bound by those requests, loses (+12 %), so it keeps its loads
+  // aligned (profiles/points_row_alignment.txt)
+  const int shift_mask = grouped ? 0 : 63;
   hipLaunchKernelGGL(reg_points_tile_dead_kernel<kPointsPerThread>, dim3((n_tiles + 255) / 256), dim3(256), 0,
                      ctx->stream, d_desc, d_pack, d_tiles, n_tiles, d_tile_dead);
   dim3 grid(((n_tiles + 7) / 8) * 8), block(kBlockThreads);
   using O4 = typename Out4<OUT>::type;
   dispatch_brick(vps, layout, [&](auto V, auto L) {
     hipLaunchKernelGGL((reg_eval_points_kernel<V(), L(), OUT, kPointsPerThread>), grid, block, 0, ctx->stream, d_desc, d_pack, d_tiles,
-                       (const uint32_t*)d_tile_dead, n_tiles, (OUT*)res, (O4*)jr, (O4*)je, blocked ? 1 : 0);
+                       (const uint32_t*)d_tile_dead, n_tiles, (OUT*)res, (O4*)jr, (O4*)je, blocked ? 1 : 0, shift_mask);
   });
 }
 
@@ -2530,7 +2551,8 @@ static int batch_points_pass(vgx_reg_batch b, const double* poses, int32_t n_nod
     b->points_order_made = true;
   }
   launch_points<OUT>(ctx, b->regs[0]->reading->vps, b->layout, b->d_desc.as<ConstraintDev>(), b->d_pack.as<PosePack>(),
-                     b->d_tiles.as<Tile>(), b->d_tile_dead.as<unsigned long long>(), (int)b->tiles.size(), res, jr, je, blocked);
+                     b->d_tiles.as<Tile>(), b->d_tile_dead.as<unsigned long long>(), (int)b->tiles.size(), res, jr, je, blocked,
+                     b->points_order_grouped);
   VGX_HIP(ctx, hipGetLastError());
   return VGX_OK;
 }
